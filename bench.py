@@ -300,7 +300,11 @@ def main():
     ap.add_argument("--corpus-sessions", type=int, default=2, help="also run the FLEURS-like corpus with this many concurrent sessions per GPU (vox_model_set_sessions: hidden contexts + model replicas + "
                     "library threads behind the same vox_transcribe_batch call; `fleurs_like_sessions`); <= 1 = skip")
     ap.add_argument("--gemv-iters", type=int, default=260)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step returned (the clip's token ids, as float64) "
+                    "to DIR/ids.npy (rank r > 0: DIR/ids_rank<r>.npy); inputs depend only on the arguments, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.dump_outputs is not None and args.steps < 1:
+        ap.error("--dump-outputs needs --steps >= 1 (it writes what the last timed step computed)")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` by hand: spawn the N ranks ourselves, exactly the way the driver does
@@ -363,6 +367,9 @@ def main():
             stage_ms[k] += tm[k]
     ctx.synchronize(); torch.cuda.synchronize(); barrier()
     elapsed_local = time.perf_counter() - t0
+    if args.dump_outputs is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "ids.npy" if rank == 0 else f"ids_rank{rank}.npy"), np.asarray(ids, dtype=np.float64))
     elapsed = elapsed_local
     per_rank_ms = [elapsed_local * 1e3 / max(args.steps, 1)]; per_rank_bcast_s = [bcast_s]
     if world > 1:

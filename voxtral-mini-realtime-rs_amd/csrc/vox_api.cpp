@@ -2333,6 +2333,9 @@ static int32_t transcribe_batch_impl(vox_model* m, int32_t n, const float* const
         }
         return VOX_OK;
     };
+    // Inside a stream capture a step runs its groups one after another on `s`: a graph of more than one parallel branch makes hipGraphLaunch hand the
+    // branches extra streams, and it reads past the end of its stream list when one of them shares the launch stream's hardware queue (a host crash).
+    bool in_capture = false;
     auto step = [&](uint32_t active) -> int32_t {
         eng_per_step = 0;
         float* h = b_h.as<float>(); float* xn = b_xn.as<float>(); float* qkv = b_qkv.as<float>(); float* att = b_att.as<float>(); float* act = b_act.as<float>();
@@ -2340,7 +2343,7 @@ static int32_t transcribe_batch_impl(vox_model* m, int32_t n, const float* const
             // groups are independent sequences: every active group but the first runs its whole layer chain on a side stream (fork / join with events, which
             // a stream capture records as parallel graph branches), so the latency-bound skinny kernels of different groups overlap
             int n_act = 0; for (int gi = 0; gi < n_grp; gi++) n_act += (active >> gi) & 1u;
-            const bool fork = n_act > 1 && !use_eng && !knob_str("VOX_BATCH_SERIAL_GROUPS");
+            const bool fork = n_act > 1 && !use_eng && !in_capture && !knob_str("VOX_BATCH_SERIAL_GROUPS");
             if (fork) {
                 VOXCHK(ensure_aux(n_act - 1));
                 HIPCHK(hipEventRecord(cx->ev_fork, s));
@@ -2397,7 +2400,7 @@ static int32_t transcribe_batch_impl(vox_model* m, int32_t n, const float* const
         if (!ge) {
             HIPCHK(hipStreamSynchronize(s));
             HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-            const int32_t r = step(act);
+            in_capture = true; const int32_t r = step(act); in_capture = false;
             hipGraph_t graph = nullptr;
             const hipError_t ce = hipStreamEndCapture(s, &graph);
             if (graph) graphs.gr.push_back(graph);
@@ -2786,6 +2789,8 @@ static int32_t transcribe_continuous_impl(vox_model* m, int32_t n, const float* 
             g.ssq_part = ssq_f; g.n_part = 16; g.norm_eps = c.norm_eps; HIPCHK(launch_q4_gemm(g, EPI_STORE, sg));
             return VOX_OK;
         };
+        // inside a stream capture the branches of a step run one after another on `s` (same kernels, same buffers): see transcribe_batch_impl's `in_capture`
+        bool in_capture = false;
         auto step = [&](uint32_t active) -> int32_t {
             int n_act = 0; for (int gi = 0; gi < G; gi++) n_act += (active >> gi) & 1u;
             eng_per_step = 0;
@@ -2794,7 +2799,7 @@ static int32_t transcribe_continuous_impl(vox_model* m, int32_t n, const float* 
                 if (gb < 0) HIPCHK(launch_decode_engine_b16(engine_params(ga, 0), s));
                 else HIPCHK(launch_decode_engine_b16x2(engine_params(ga, 0, true), engine_params(gb, 1, true), s));
                 eng_per_step = 1;
-                if (gb >= 0) {      // the second group's tail on a side stream
+                if (gb >= 0 && !in_capture) {      // the second group's tail on a side stream
                     if (!cx->ev_fork) HIPCHK(hipEventCreateWithFlags(&cx->ev_fork, hipEventDisableTiming));
                     if (!cx->aux[0]) HIPCHK(hipStreamCreateWithFlags(&cx->aux[0], hipStreamNonBlocking));
                     if (!cx->ev_join[0]) HIPCHK(hipEventCreateWithFlags(&cx->ev_join[0], hipEventDisableTiming));
@@ -2803,7 +2808,7 @@ static int32_t transcribe_continuous_impl(vox_model* m, int32_t n, const float* 
                     HIPCHK(hipEventRecord(cx->ev_join[0], cx->aux[0]));
                 }
                 VOXCHK(engine_tail(ga, s));
-                if (gb >= 0) HIPCHK(hipStreamWaitEvent(s, cx->ev_join[0], 0));
+                if (gb >= 0) { if (in_capture) VOXCHK(engine_tail(gb, s)); else HIPCHK(hipStreamWaitEvent(s, cx->ev_join[0], 0)); }
                 HIPCHK(launch_argmax_embed_slots(sp, Sl, s));
                 return VOX_OK;
             }
@@ -2817,15 +2822,18 @@ static int32_t transcribe_continuous_impl(vox_model* m, int32_t n, const float* 
                         if (!cx->aux[j]) HIPCHK(hipStreamCreateWithFlags(&cx->aux[j], hipStreamNonBlocking));
                         if (!cx->ev_join[j]) HIPCHK(hipEventCreateWithFlags(&cx->ev_join[j], hipEventDisableTiming));
                     }
-                    HIPCHK(hipEventRecord(cx->ev_fork, s));
-                    for (int j = 1; j < nc; j++) { HIPCHK(hipStreamWaitEvent(cx->aux[j - 1], cx->ev_fork, 0)); VOXCHK(wide_chain(szc[j], cx->aux[j - 1], g0c[j], j)); HIPCHK(hipEventRecord(cx->ev_join[j - 1], cx->aux[j - 1])); }
-                    VOXCHK(wide_chain(szc[0], s, 0, 0));
-                    for (int j = 1; j < nc; j++) HIPCHK(hipStreamWaitEvent(s, cx->ev_join[j - 1], 0));
+                    if (in_capture) { for (int j = 0; j < nc; j++) VOXCHK(wide_chain(szc[j], s, g0c[j], j)); }
+                    else {
+                        HIPCHK(hipEventRecord(cx->ev_fork, s));
+                        for (int j = 1; j < nc; j++) { HIPCHK(hipStreamWaitEvent(cx->aux[j - 1], cx->ev_fork, 0)); VOXCHK(wide_chain(szc[j], cx->aux[j - 1], g0c[j], j)); HIPCHK(hipEventRecord(cx->ev_join[j - 1], cx->aux[j - 1])); }
+                        VOXCHK(wide_chain(szc[0], s, 0, 0));
+                        for (int j = 1; j < nc; j++) HIPCHK(hipStreamWaitEvent(s, cx->ev_join[j - 1], 0));
+                    }
                     HIPCHK(launch_argmax_embed_slots(sp, Sl, s)); return VOX_OK;
                 }
                 if (prefix) { VOXCHK(wide_chain(n_act, s)); HIPCHK(launch_argmax_embed_slots(sp, Sl, s)); return VOX_OK; }
             }
-            const bool fork = n_act > 1 && !knob_str("VOX_BATCH_SERIAL_GROUPS");
+            const bool fork = n_act > 1 && !in_capture && !knob_str("VOX_BATCH_SERIAL_GROUPS");
             if (fork) {
                 if (!cx->ev_fork) HIPCHK(hipEventCreateWithFlags(&cx->ev_fork, hipEventDisableTiming));
                 for (int i = 0; i < n_act - 1 && i < 3; i++) {
@@ -2883,7 +2891,7 @@ static int32_t transcribe_continuous_impl(vox_model* m, int32_t n, const float* 
         std::vector<std::pair<uint32_t, int>> eng_in_graph;      // engine launches per replay of every captured set
         auto capture = [&](uint32_t act, hipGraphExec_t* out) -> int32_t {
             HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-            const int32_t r = step(act);
+            in_capture = true; const int32_t r = step(act); in_capture = false;
             hipGraph_t graph = nullptr;
             const hipError_t ce = hipStreamEndCapture(s, &graph);
             if (graph) graphs.gr.push_back(graph);
