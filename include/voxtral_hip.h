@@ -230,7 +230,8 @@ int32_t vox_model_set_decode_engine(vox_model* m, int32_t on, int32_t* active_or
  * launch of the batched decode-layer engine (same eligibility as above) whenever one or two 16-row groups are active -- a batch of n <= 16 rows (one group per
  * launch), and in a wider batch's continuous decode the steps with one or two active slot groups (TWO groups per launch: group B's phase runs while group A's
  * hand-off resolves; DESIGN.md sections 3.3c / 3.3e).  Steps with three or four active groups take the launch-based step (4 launches per layer and group, the groups'
- * chains forked on side streams: measured faster than engine launches back to back).  on = 0 selects the launch-based step everywhere, on < 0 only queries.
+ * chains back to back on the session stream, as every chain of a batched step since the corpus crash fix; measured, with the chains then forked on side
+ * streams, faster than engine launches back to back).  on = 0 selects the launch-based step everywhere, on < 0 only queries.
  * *active_or_null: is the engine armed; *launches_or_null: engine launches enqueued so far (eager + graph replays) -- the number that says whether a given call used
  * it.  A hand-off timeout inside the engine re-runs the batch (the session, for a wide batch) on the launch-based step (a warning on stderr); three such strikes
  * switch the engine off for the model.  Environment VOX_BATCH_ENGINE=0: off at load time. */

@@ -381,6 +381,35 @@ def test_model_set_sessions_splits_large_calls_and_keeps_every_units_ids(pkg, ct
         assert m.set_batch_engine()[1] > n0 and all(np.array_equal(a, b) for a, b in zip(sh, own))
 
 
+def test_warm_forms_follow_the_launched_chains(pkg, ctx, tiny, capfd, monkeypatch):
+    """ADVICE r6 finding 2: a context records which step forms have launched their kernels outside a capture (their dynamic-LDS limits are raised at the first launch).
+    Keyed by the number of active groups, an unshared four-group call (two two-group wide chains) marked four groups as warm, and a later shared four-group call
+    (one four-group wide chain) met that chain's first launch inside a graph capture.  The forms are keyed by the chains a step launches: on one fresh context the
+    unshared call and then the shared call both succeed, and the shared call's ids are those of the same call on another fresh shared context."""
+    m, _, _ = tiny
+    t = pkg.TimeEmbedding(256).embed(6.0)
+    clips = [pkg.synth.synth_audio(0.6 + 0.11 * ((5 * i) % 13), seed=4200 + i) for i in range(80)]
+    monkeypatch.setenv("VOX_BATCH_NO_CALIB", "1"); monkeypatch.setenv("VOX_BATCH_VERBOSE", "1")
+    monkeypatch.setenv("VOX_BATCH_SLOT_GROUPS", "5")
+    capfd.readouterr(); m.transcribe_batch(clips, t)
+    if "80 slots" not in capfd.readouterr().err:      # more than four groups are planned only when wide_geom_ok holds for the model
+        pytest.skip("the wide step does not cover the tiny model's geometry")
+    clips = clips[:64]
+    monkeypatch.setenv("VOX_BATCH_SLOT_GROUPS", "4")
+    ca, cb = pkg.Context(0), pkg.Context(0)
+    ma, mb = m.replicate(ca), m.replicate(cb)
+    try:
+        own = ma.transcribe_batch(clips, t)      # four groups on a context that owns its GPU: two two-group wide chains per step
+        assert "64 slots" in capfd.readouterr().err
+        ca.set_shared(True); cb.set_shared(True)
+        shared = ma.transcribe_batch(clips, t)      # the same plan on a shared context: one four-group wide chain per step
+        fresh = mb.transcribe_batch(clips, t)
+        assert len(shared) == len(fresh) == len(own) == 64
+        assert all(np.array_equal(a, b) for a, b in zip(shared, fresh)), "shared call after an unshared one: ids differ from a fresh shared context"
+    finally:
+        ma.close(); mb.close(); ca.close(); cb.close()
+
+
 def test_two_contexts_two_threads_and_model_replicate(pkg, ctx, tiny):
     """The header promises "a handle is not thread-safe, distinct contexts are independent" (include/voxtral_hip.h:15-16) and SURVEY.md section 8(e) describes the
     in-process multi-GPU shape -- one host thread + one vox_ctx + one model replica per GPU (what a Rust `voxtral-transcribe`, bin/transcribe.rs:60-128, would do).

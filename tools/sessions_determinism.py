@@ -50,7 +50,7 @@ def many(concurrent=True):
 def cmp(a, b): return sum(int(len(x) == len(y) and (x == y).all()) for x, y in zip(a, b))
 os.environ["VOX_BATCH_NO_CALIB"] = "1"
 CONFIGS = [("default", {}), ("no wide step", {"VOX_BATCH_NO_WIDE": "1"}), ("no engine", {"VOX_BATCH_CONT_NO_ENGINE": "1"}),
-           ("chains only", {"VOX_BATCH_NO_WIDE": "1", "VOX_BATCH_CONT_NO_ENGINE": "1"}), ("chains only, groups in series", {"VOX_BATCH_NO_WIDE": "1", "VOX_BATCH_CONT_NO_ENGINE": "1", "VOX_BATCH_SERIAL_GROUPS": "1"}),
+           ("chains only", {"VOX_BATCH_NO_WIDE": "1", "VOX_BATCH_CONT_NO_ENGINE": "1"}),
            ("no graphs", {"VOX_BATCH_NO_GRAPH": "1"})]
 sel = os.environ.get("DET_CONFIGS")
 for name, env in CONFIGS:
