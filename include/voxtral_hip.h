@@ -62,7 +62,8 @@ int32_t vox_ctx_synchronize(vox_ctx* ctx);
 /* shared != 0: this context SHARES its GPU with other sessions (more contexts of this process -- one host thread each, see vox_model_replicate -- or other processes).
  * The batch entry points then stay off the batched decode engines (their 256 persistent workgroups need the GPU to themselves: next to another session their bounded
  * hand-off waits expire and the session is run twice) and the slot planner prices its steps with the table scaled by ONE measured factor instead of per-form
- * measurements (which scatter under contention) and records none.  Results do not change.  Default 0.  (No reference counterpart: the reference runs one utterance at a
+ * measurements (which scatter under contention) and records none.  Per step the logits stay within f32 summation-order noise (2e-4 of the largest, what the tests assert
+ * against the single-stream path) whatever the plan, so ids change only after a near-tie; the plan (hence the order of the sums) may differ from an unshared call's.  Default 0.  (No reference counterpart: the reference runs one utterance at a
  * time, bin/transcribe.rs:112-126; this is what a multi-threaded host sets on every context of a GPU it runs more than one session on.) */
 int32_t vox_ctx_set_shared(vox_ctx* ctx, int32_t shared);
 int32_t vox_ctx_stream(vox_ctx* ctx, void** hip_stream_out);   /* hipStream_t, for event timing */
@@ -257,8 +258,11 @@ int32_t vox_transcribe_audio(vox_model* m, const float* samples, size_t n, const
  * n <= 16: one 16-row group, one decode-layer engine launch per step.  n > 16: CONTINUOUS BATCHING -- every utterance is encoded (stacked, packed: no padding to the
  * longest) and prefilled up front; the decode step then runs over 16 .. 128 SLOTS, and a slot whose utterance has its last token takes the next utterance of its
  * host-planned queue inside the same step (token counts are a pure function of the sample count: there is no EOS, gguf/model.rs:936-960), so the groups stay full
- * until the queues run dry; steps with one or two active groups are one engine launch for all their layers (vox_model_set_batch_engine).  Ids per utterance do not
- * depend on n, on the slot or on the neighbours (tested at full size). */
+ * until the queues run dry; steps with one or two active groups are one engine launch for all their layers (vox_model_set_batch_engine).  Per decode step, every
+ * utterance's logits are within f32 summation-order noise (2e-4 of the largest logit, asserted for every step form against the teacher-forced single-stream logits:
+ * vox_debug_batch_tap_*) of the single-stream path, whatever n, the slot, the neighbours or the plan; so its ids equal the single-stream ids except after a near-tie,
+ * where the forms' different K-split summation orders may break the tie differently.  Ids are bit-identical call to call only with the same slot plan:
+ * VOX_BATCH_NO_CALIB=1 makes the plan a function of the input lengths alone (otherwise measured step costs steer it). */
 int32_t vox_transcribe_batch(vox_model* m, int32_t n, const float* const* samples, const size_t* n_samples, const float* t_embed,
                              int32_t* const* out_ids, const int32_t* caps, int32_t* n_ids, int32_t mem_kind);
 /* The same call with the CLI's normalisation semantics (bin/transcribe.rs:207-265): the reference peak-normalises the FILE once, splits it into chunks of
@@ -274,7 +278,7 @@ int32_t vox_transcribe_batch_ex(vox_model* m, int32_t n, const float* const* sam
  * sessions = 1).  One session leaves the GPU idle wherever its launch-bound decode steps wait; a second one fills the gaps: 647 FLEURS-like clips x 1.16 - 1.20 over a 64-slot session on one
  * MI355X (the plain call now plans up to 128 slots as two chains per step -- the same overlap -- so sessions add ~1 % there: they are for one GPU shared by
  * independent callers).  Units that share a norm_group stay in one session; every context involved counts as shared for the call (vox_ctx_set_shared); results are per
- * unit and do not depend on the split.  vox_get_stage_timings then reports the longest session's stage times and the call's wall time.  Smaller calls and every other
+ * unit: a unit's logits stay within f32 summation-order noise of the single-stream path whichever session runs it, so its ids depend on the split only after a near-tie.  vox_get_stage_timings then reports the longest session's stage times and the call's wall time.  Smaller calls and every other
  * entry point are unchanged.  (No reference counterpart -- the reference transcribes one file at a time, bin/transcribe.rs:112-126; a host that prefers its own threads
  * uses vox_model_replicate + vox_ctx_set_shared instead.)  Q4 (GGUF) models. */
 int32_t vox_model_set_sessions(vox_model* m, int32_t sessions);
@@ -372,6 +376,14 @@ int32_t vox_bench_wide(vox_model* m, int32_t which, int32_t mt, int32_t iters, d
  * s_memrealtime counter at 4 points; _fetch copies out[n_slots][n_waves][4] back and switches the instrumentation off. */
 int32_t vox_debug_timeline_start(vox_ctx* ctx, int32_t n_slots, int32_t n_waves);
 int32_t vox_debug_timeline_fetch(vox_ctx* ctx, uint64_t* out, size_t cap_words, int32_t* slots_used, int32_t* meta /* [n_slots][4] {0 gemv / 1 attention, epilogue, N, K}, may be NULL */);
+/* Logits tap of the batched decoder (tests).  _arm: the NEXT vox_transcribe_batch / _ex call on m (and only that one, whatever its outcome) copies, for each caller
+ * index units[j] (the i of samples[i]; distinct, < that call's n), the f32 logits row each of its ids was taken from: row k of unit j is the row whose argmax is
+ * out_ids[units[j]][k] -- row 0 the prefill's lm_head row, rows 1.. the decode steps', whatever the step form, the slot or a refill.  One small kernel per step in
+ * front of the argmax launch, captured into the step graphs with it; without an armed tap nothing is launched.  A call that would split into sessions
+ * (vox_model_set_sessions) fails with VOX_ERR_UNSUPPORTED.  _fetch (after a successful tapped call): out [n_units][max_rows][vocab] (rows past a unit's count are
+ * zero), rows_per_unit[j] = rows the call produced for unit j -- more than max_rows: the rest were dropped.  VOX_ERR_INVALID: bad arguments, or nothing to fetch. */
+int32_t vox_debug_batch_tap_arm(vox_model* m, const int32_t* units, int32_t n_units, int32_t max_rows);
+int32_t vox_debug_batch_tap_fetch(vox_model* m, float* out, int32_t* rows_per_unit);
 
 #ifdef __cplusplus
 }

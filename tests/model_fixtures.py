@@ -1,5 +1,6 @@
 """Shared helpers for model-level tests: deterministic synthetic GGUFs (cached in the temp dir)."""
 import os
+import re
 import tempfile
 
 import numpy as np
@@ -93,6 +94,71 @@ def check_batch_rows(pkg, ctx, model, clips, t_embed, outs, tol):
         first = check_greedy_ids(ids, rids, rlg, tol)
         identical += int(first == len(rids))
     return identical
+
+
+PREFIX = [1] + [32] * 37      # BOS + 37 x STREAMING_PAD: the decoder's 38-token prefix (gguf/model.rs:887-902)
+
+
+def _dec_positions(T, R=4):
+    """Decoder positions of a T-frame log-mel: two stride-2 convolutions, then R frames per position (conv.rs:47-48, adapter.rs:114)."""
+    cl = lambda L: (L - 1) // 2 + 1
+    return cl(cl(T)) // R
+
+
+def teacher_forced_logits(pkg, ctx, model, x, t_embed, ids, oracle=None):
+    """The logits rows that predicted `ids` ([len(ids)][vocab], row k -> ids[k]) with the sequence's OWN ids fed back as the token inputs: PREFIX + ids[:-1] (the last
+    position's input is never read by a kept row, causal).  Default: vox_forward_streaming on the device log-mel the batch path computes (single_stream_reference's mel):
+    the prefill / large-M GEMM path, no decode kernel in common with the batched step forms.  oracle = an oracle_lib.Model: the CPU oracle on its own mel -- encode_audio,
+    embed_tokens, one causal forward_hidden_with_cache over every position, lm_head (f32, sequential sums)."""
+    ids = np.asarray(ids, dtype=np.int32); n = len(ids)
+    assert n >= 1
+    if oracle is None:
+        mel = np.ascontiguousarray(pkg.MelSpectrogram.voxtral(ctx).compute_log(pkg.pad_audio(pkg.peak_normalize(x))).T)
+    else:
+        import oracle_lib
+        xn = np.array(x, dtype=np.float32, copy=True); oracle_lib.lib().orc_peak_normalize(xn, xn.size, 0.95)
+        mel = np.ascontiguousarray(oracle_lib.mel_compute_log(oracle_lib.pad_audio(xn)).T)
+    S = _dec_positions(mel.shape[1], model.config.reshape_factor)
+    assert S >= 38 and n == max(S - 38, 1), (S, n)
+    toks = np.array((PREFIX + list(ids[:-1]) + [32] * S)[:S], dtype=np.int32)
+    if oracle is None:
+        lg = model.forward_streaming(mel[None], toks, t_embed)[0]
+    else:
+        audio = oracle.encode_audio(mel)
+        assert audio.shape[0] == S
+        oc = oracle.cache(max(S, 8))
+        try:
+            h = oracle.forward_hidden_with_cache(audio + oracle.embed_tokens(toks), t_embed, oc)
+        finally:
+            oracle.cache_free(oc)
+        lg = oracle.lm_head(h[37:37 + n])
+        return np.asarray(lg, dtype=np.float32)
+    return lg[37:37 + n]
+
+
+def argmax_low(rows):
+    """Row-wise argmax with the lowest index winning ties (np.argmax does that)."""
+    return np.argmax(np.asarray(rows), axis=1)
+
+
+def top2_margin(row):
+    s = np.sort(np.asarray(row, dtype=np.float64)); return float(s[-1] - s[-2])
+
+
+def parse_batch_verbose(err):
+    """The VOX_BATCH_VERBOSE lines of one batch call: lock-step parts [(rows, groups, steps, form)], continuous sessions [slots], decode steps per continuous step form
+    (summed over sessions) and the slot plan of the last continuous session (caller units per slot, in queue order)."""
+    out = {"lockstep": [], "slots": [], "forms": {"chains": 0, "engine1": 0, "engine2": 0, "wide": 0, "split": 0}, "plan": None}
+    for r, g, st, f in re.findall(r"lock-step batch: (\d+) rows, (\d+) groups, (\d+) steps, step form (\S+)", err):
+        out["lockstep"].append((int(r), int(g), int(st), f))
+    out["slots"] = [int(x) for x in re.findall(r"continuous batch: \d+ utterances, (\d+) slots", err)]
+    for line in re.findall(r"continuous batch step forms: ([^\n]*)", err):
+        for k, v in re.findall(r"(\w+) (\d+)", line):
+            out["forms"][k] += int(v)
+    plans = re.findall(r"slot plan \(caller units per slot\):([^\n]*)", err)
+    if plans:
+        out["plan"] = [[int(u) for u in q.split()] for q in plans[-1].split("|")]
+    return out
 
 
 def dense_head_sha(path, nbytes=64 << 20):

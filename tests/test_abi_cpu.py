@@ -164,6 +164,21 @@ def test_synthetic_gguf_is_readable_by_both(pkg, orc, tmp_path):
     assert wq.shape == (128, 128) and abs(float(wq.mean())) < 2e-3 and 0.02 < float(wq.std()) < 0.04
 
 
+def test_batch_tap_symbols_and_bad_arguments(pkg):
+    """The batched decoder's logits tap (vox_debug_batch_tap_*) is exported and bound, and refuses bad arguments with VOX_ERR_INVALID before it touches a device."""
+    L = pkg.lib()
+    for name in ("vox_debug_batch_tap_arm", "vox_debug_batch_tap_fetch"):
+        assert hasattr(L, name) and name in pkg._lib.SIGNATURES
+    u = (C.c_int32 * 2)(0, 1)
+    cases = [((None, u, 2, 4), "null model"), ((None, u, 0, 4), "tap unit list"), ((None, u, -1, 4), "tap unit list"), ((None, None, 2, 4), "tap unit list"),
+             ((None, u, 2, 0), "max_rows"), ((None, u, 2, -3), "max_rows")]
+    for args, msg in cases:
+        assert L.vox_debug_batch_tap_arm(*args) == 1, args
+        assert msg in L.vox_last_error().decode(), (args, L.vox_last_error())
+    out = np.zeros(4, np.float32); rows = (C.c_int32 * 2)()
+    assert L.vox_debug_batch_tap_fetch(None, out.ctypes.data, rows) == 1
+
+
 def test_integration_md_sys_block_is_complete_and_current(pkg):
     """INTEGRATION.md section 2 is generated from the header: every declared symbol has its Rust declaration and the block is not stale."""
     import subprocess, sys

@@ -8,7 +8,7 @@ import os
 import numpy as np
 import pytest
 
-from model_fixtures import cache_dir, check_batch_rows, check_greedy_ids, dense_head_sha, full_dense_safetensors, rel_err
+from model_fixtures import argmax_low, cache_dir, check_batch_rows, check_greedy_ids, dense_head_sha, full_dense_safetensors, parse_batch_verbose, rel_err, teacher_forced_logits, top2_margin
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-4
@@ -981,6 +981,157 @@ def test_full_two_sessions_one_gpu_same_ids(pkg, full, monkeypatch):
         m.set_batch_engine(was)
 
 
+# step forms that exist only at the real geometry: (clips of _full_form_clips, environment, what VOX_BATCH_VERBOSE must show, needs the batched engine)
+_FULL_FORMS = {
+    "engine_one_group_n6": (6, {}, lambda v: [p[:2] + p[3:] for p in v["lockstep"]] == [(6, 1, "engine")], True),
+    "engine_two_groups_n24": (24, {"VOX_BATCH_SLOT_GROUPS": "2"}, lambda v: v["slots"] == [32] and v["forms"]["engine2"] > 0, True),
+    "chains_g3_n40": (40, {"VOX_BATCH_SLOT_GROUPS": "3", "VOX_BATCH_CONT_NO_ENGINE": "1"}, lambda v: v["slots"] == [48] and v["forms"]["chains"] > 0, False),
+    "wide_g2_n40": (40, {"VOX_BATCH_SLOT_GROUPS": "2", "VOX_BATCH_WIDE_MIN": "2", "VOX_BATCH_CONT_NO_ENGINE": "1"}, lambda v: v["slots"] == [32] and v["forms"]["wide"] > 0, False),
+    "wide_g3_n56": (56, {"VOX_BATCH_SLOT_GROUPS": "3", "VOX_BATCH_WIDE_MIN": "3", "VOX_BATCH_CONT_NO_ENGINE": "1"}, lambda v: v["slots"] == [48] and v["forms"]["wide"] > 0, False),
+    "wide_g4_one_chain_n72": (72, {"VOX_BATCH_SLOT_GROUPS": "4", "VOX_BATCH_WIDE_MIN": "4", "VOX_BATCH_CONT_NO_ENGINE": "1", "VOX_BATCH_NO_WIDE_SPLIT": "1"},
+                              lambda v: v["slots"] == [64] and v["forms"]["wide"] > 0, False),
+    "split_g5_n90": (90, {"VOX_BATCH_SLOT_GROUPS": "5"}, lambda v: v["slots"] == [80] and v["forms"]["split"] > 0, False),
+    "split_g8_n130": (130, {"VOX_BATCH_SLOT_GROUPS": "8"}, lambda v: v["slots"] == [128] and v["forms"]["split"] > 0, False),
+    "lockstep_n64": (64, {"VOX_BATCH_NO_CONTINUOUS": "1"}, lambda v: [p[1:2] + p[3:] for p in v["lockstep"]] == [(4, "xf-chains")], False),
+}
+
+
+def _full_form_clips(pkg, n):
+    """2 .. 5 s clips, arbitrary order; units 0 and 1 are the two shortest (2.0 and 2.1 s: the oracle's units)."""
+    secs = [2.0, 2.1] + [2.2 + 2.8 * ((13 * i) % 31) / 30.0 for i in range(128)]
+    return [pkg.synth.synth_audio(s, seed=9100 + i) for i, s in enumerate(secs[:n])]
+
+
+@pytest.fixture(scope="module")
+def full_tf_cache():
+    return {}
+
+
+def _tapped_call(m, clips, t, env, monkeypatch, capfd, pick):
+    """One untapped call under `env` (VOX_BATCH_VERBOSE: the form and the slot plan), then the same call with the units pick(verbose) tapped: same ids."""
+    monkeypatch.setenv("VOX_BATCH_NO_CALIB", "1"); monkeypatch.setenv("VOX_BATCH_VERBOSE", "1")
+    for k, val in env.items():
+        monkeypatch.setenv(k, val)
+    try:
+        capfd.readouterr()
+        plain = m.transcribe_batch(clips, t)
+        v = parse_batch_verbose(capfd.readouterr().err)
+        units = pick(v)
+        outs, taps = m.transcribe_batch(clips, t, tap_units=units)
+        capfd.readouterr()
+    finally:
+        for k in env:
+            monkeypatch.delenv(k)
+    assert all(np.array_equal(a, b) for a, b in zip(plain, outs)), "an armed tap changed the ids"
+    return outs, dict(zip(units, taps)), v
+
+
+def _special_units(v, clips):
+    """slot 0, the last slot of the last group, the last unit that starts in a vacated slot and the first unit of slot 15 of every group (continuous); the first row of
+    every group (lock-step, rows run longest first); the shortest and the longest unit; units 0 and 1."""
+    lens = [len(c) for c in clips]; sp = {"u0": 0, "u1": 1, "shortest": int(np.argmin(lens)), "longest": int(np.argmax(lens))}
+    if v["plan"]:
+        sp["slot0"] = v["plan"][0][0]; sp["last_slot"] = next(q[0] for q in reversed(v["plan"]) if q)      # (more slots than units: the last ones stay empty)
+        refills = [q[1] for q in v["plan"] if len(q) > 1]
+        if refills:
+            sp["refill"] = refills[-1]
+        for g in range(len(v["plan"]) // 16):      # one unit in every slot group: what is indexed per group (pos, kv_row, ssq / XF strides, a split chain's g0)
+            if v["plan"][16 * g + 15]:
+                sp[f"group{g}"] = v["plan"][16 * g + 15][0]
+    else:
+        order = sorted(range(len(clips)), key=lambda i: -lens[i])
+        sp["group_last_row"] = order[min(len(order) - 1, 15)]
+        for g in range(1, (len(order) + 15) // 16):
+            sp[f"group{g}_row0"] = order[16 * g]
+    return sp
+
+
+@pytest.mark.parametrize("form", list(_FULL_FORMS))
+def test_full_batch_logits_step_forms_vs_teacher_forced(pkg, full, form, capfd, monkeypatch, full_tf_cache):
+    """Every full-size step form of the batched decoder (the batched engine's one- and two-group launches, the 3-group launch chains, the wide step at 2 / 3 / 4 groups, the
+    split wide step at 5 and 8 groups, the 64-row lock-step batch) at LOGIT precision on the RANDOM checkpoint (seed 42: near-ties everywhere, so the ids alone would hide a
+    small error): 6 .. 12 tapped units per form -- slot 0, the last slot, a refilled slot, one slot of every group, the shortest and the longest -- every row's argmax is its id and every row is within
+    TOL * max|ref| of the teacher-forced logits (vox_forward_streaming, the prefill path); units 0 and 1 (the two shortest clips) also against the CPU oracle's teacher-forced
+    logits (computed once for all forms)."""
+    m, o, ctx = full
+    n, env, ran, needs_eng = _FULL_FORMS[form]
+    if needs_eng and not m.set_batch_engine()[0]:
+        pytest.skip("batched decode engine not available on this device (needs 256 CUs)")
+    t = pkg.TimeEmbedding(3072).embed(6.0)
+    clips = _full_form_clips(pkg, n)
+    sp = {}
+
+    def pick(v):
+        sp.update(_special_units(v, clips))
+        return sorted(set(sp.values()))
+    outs, taps, v = _tapped_call(m, clips, t, env, monkeypatch, capfd, pick)
+    assert ran(v), f"{form}: the form did not run: {v}"
+    if v["plan"] and n > len(v["plan"]):
+        assert "refill" in sp, f"{form}: no slot took a second unit"
+    worst = worst_o = 0.0
+    for u, tp in taps.items():
+        ids = outs[u]
+        assert tp.shape == (len(ids), 131072) and np.array_equal(argmax_low(tp), ids), f"{form}, unit {u}: the tapped rows are not those the ids were taken from"
+        key = ("gpu", u, ids.tobytes())
+        if key not in full_tf_cache:
+            full_tf_cache[key] = teacher_forced_logits(pkg, ctx, m, clips[u], t, ids)
+        e = rel_err(tp, full_tf_cache[key]); worst = max(worst, e)
+        assert e <= TOL, f"{form}, unit {u} ({[k for k, x in sp.items() if x == u]}): max|tap - teacher forced| = {e:.3e} of max|ref|"
+        if u in (0, 1):
+            key = ("oracle", u, ids.tobytes())
+            if key not in full_tf_cache:
+                full_tf_cache[key] = teacher_forced_logits(pkg, ctx, m, clips[u], t, ids, oracle=o)
+            e = rel_err(tp, full_tf_cache[key]); worst_o = max(worst_o, e)
+            assert e <= TOL, f"{form}, unit {u}: max|tap - oracle teacher forced| = {e:.3e} of max|ref|"
+    print(f"batch logits, full size, {form}: {len(taps)} units / {sum(len(x) for x in taps.values())} rows tapped, worst rel err {worst:.2e} vs teacher-forced GPU, "
+          f"{worst_o:.2e} vs oracle; units {sp}; verbose {v['lockstep'] or v['forms']}")
+
+
+def _differ_only_at_near_ties(ids_a, tap_a, ids_b, tap_b, what):
+    """Two step forms' rows of one unit: identical ids, or rows within 2 TOL * scale up to and including the first differing step, where BOTH forms' own top-2 margins are
+    below 2 TOL * scale (a genuine tie of the two summation orders).  Returns the first differing step (len if none)."""
+    scale = max(1.0, float(np.abs(tap_a).max()), float(np.abs(tap_b).max()))
+    k = 0
+    while k < min(len(ids_a), len(ids_b)) and ids_a[k] == ids_b[k]:
+        k += 1
+    upto = min(k + 1, len(ids_a), len(ids_b))
+    d = float(np.abs(tap_a[:upto].astype(np.float64) - tap_b[:upto]).max()) if upto else 0.0
+    assert d <= 2 * TOL * scale, f"{what}: rows differ by {d:.3e} (scale {scale:.1f}) before the ids part"
+    if k < min(len(ids_a), len(ids_b)):
+        ma, mb = top2_margin(tap_a[k]), top2_margin(tap_b[k])
+        assert ma < 2 * TOL * scale and mb < 2 * TOL * scale, f"{what}: ids differ at step {k} with top-2 margins {ma:.3e} / {mb:.3e} (scale {scale:.1f}): not a tie"
+    assert len(ids_a) == len(ids_b)
+    return k
+
+
+def test_full_step_forms_differ_only_at_near_ties(pkg, full, capfd, monkeypatch, full_tf_cache):
+    """ADVICE r6 finding 1 as a checked property: the step forms sum their K-splits in different orders, so a unit's ids may depend on the slot plan -- but only through
+    near-ties.  One clip set through the default plan (up to 8 groups, split wide chains) and through <= 4 groups (VOX_BATCH_MAX_GROUPS=4), VOX_BATCH_NO_CALIB=1, with the
+    same units tapped (every unit whose ids differ between the two, and four more): rows agree within 2 TOL * scale up to the first differing id, where both forms' own top-2
+    margins are below 2 TOL * scale; each form matches its own teacher-forced reference everywhere."""
+    m, _, ctx = full
+    t = pkg.TimeEmbedding(3072).embed(6.0)
+    clips = _full_form_clips(pkg, 130)
+    monkeypatch.setenv("VOX_BATCH_NO_CALIB", "1")
+    a = m.transcribe_batch(clips, t)
+    monkeypatch.setenv("VOX_BATCH_MAX_GROUPS", "4"); b = m.transcribe_batch(clips, t); monkeypatch.delenv("VOX_BATCH_MAX_GROUPS")
+    diff = [u for u in range(len(clips)) if not np.array_equal(a[u], b[u])]
+    units = sorted(set(diff[:8]) | {0, 1, 64, 129})
+    ra, ta, _ = _tapped_call(m, clips, t, {}, monkeypatch, capfd, lambda v: units)
+    rb, tb, vb = _tapped_call(m, clips, t, {"VOX_BATCH_MAX_GROUPS": "4"}, monkeypatch, capfd, lambda v: units)
+    assert vb["slots"] and max(vb["slots"]) <= 64
+    assert all(np.array_equal(x, y) for x, y in zip(a, ra)) and all(np.array_equal(x, y) for x, y in zip(b, rb))
+    firsts = {}
+    for u in units:
+        firsts[u] = _differ_only_at_near_ties(ra[u], ta[u], rb[u], tb[u], f"unit {u}")
+        for ids, tp in ((ra[u], ta[u]), (rb[u], tb[u])):
+            key = ("gpu", u, ids.tobytes())
+            if key not in full_tf_cache:
+                full_tf_cache[key] = teacher_forced_logits(pkg, ctx, m, clips[u], t, ids)
+            assert rel_err(tp, full_tf_cache[key]) <= TOL, f"unit {u}: a form misses its own teacher-forced reference"
+    print(f"default plan vs <= 4 groups: {len(diff)} of {len(clips)} units differ, each at a verified near-tie (first differing step per tapped unit {firsts})")
+
+
 def test_full_128_slots_two_wide_chains(pkg, full, monkeypatch):
     """More than four slot groups (end of round 6): 150 clips of 2 .. 8 s on up to 128 slots -- every step with n >= 4 active groups runs as two wide chains of ceil(n / 2) and
     floor(n / 2) groups on two streams.  Same ids as on <= 64 slots (VOX_BATCH_MAX_GROUPS=4) except at near-ties (a clip meets the three-group launch chains at other steps),
@@ -993,11 +1144,34 @@ def test_full_128_slots_two_wide_chains(pkg, full, monkeypatch):
     a = m.transcribe_batch(clips, t); b = m.transcribe_batch(clips, t)
     assert all(np.array_equal(x, y) for x, y in zip(a, b))
     assert sum(int(np.array_equal(x, y)) for x, y in zip(ref, a)) >= len(clips) - 4
+    others = {"default": a}
     for G in (7, 8):
         monkeypatch.setenv("VOX_BATCH_SLOT_GROUPS", str(G))
         g = m.transcribe_batch(clips, t)
         assert sum(int(np.array_equal(x, y)) for x, y in zip(ref, g)) >= len(clips) - 4, G
+        others[G] = g
     monkeypatch.delenv("VOX_BATCH_SLOT_GROUPS")
+    # every clip that differs from the <= 64-slot ids does so at a near-tie of the tapped logits of both calls (the plans are deterministic: the tapped calls repeat them)
+    diff = {k: [u for u in range(len(clips)) if not np.array_equal(ref[u], g[u])] for k, g in others.items()}
+    units = sorted(set(u for d in diff.values() for u in d))
+    n_checked = 0
+    if units:
+        monkeypatch.setenv("VOX_BATCH_MAX_GROUPS", "4"); rr, rt = m.transcribe_batch(clips, t, tap_units=units); monkeypatch.delenv("VOX_BATCH_MAX_GROUPS")
+        assert all(np.array_equal(x, y) for x, y in zip(ref, rr))
+        for k, g in others.items():
+            if not diff[k]:
+                continue
+            if k != "default":
+                monkeypatch.setenv("VOX_BATCH_SLOT_GROUPS", str(k))
+            try:
+                gg, gt = m.transcribe_batch(clips, t, tap_units=diff[k])
+            finally:
+                monkeypatch.delenv("VOX_BATCH_SLOT_GROUPS", raising=False)
+            assert all(np.array_equal(x, y) for x, y in zip(g, gg))
+            for j, u in enumerate(diff[k]):
+                _differ_only_at_near_ties(rr[u], rt[units.index(u)], gg[u], gt[j], f"{k} vs <= 4 groups, clip {u}")
+                n_checked += 1
+    print(f"128 slots: differing clips per plan {diff}; {n_checked} differences verified as near-ties of the tapped logits")
 
 
 def test_full_model_set_sessions_two(pkg, full, monkeypatch):

@@ -10,7 +10,7 @@ Tolerances (stated here, used below):
 import numpy as np
 import pytest
 
-from model_fixtures import check_batch_rows, check_greedy_ids, fake_mel, golden, golden_gguf, rel_err, tiny_gguf
+from model_fixtures import argmax_low, check_batch_rows, check_greedy_ids, fake_mel, golden, golden_gguf, parse_batch_verbose, rel_err, teacher_forced_logits, tiny_gguf
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-4
@@ -408,6 +408,115 @@ def test_warm_forms_follow_the_launched_chains(pkg, ctx, tiny, capfd, monkeypatc
         assert all(np.array_equal(a, b) for a, b in zip(shared, fresh)), "shared call after an unshared one: ids differ from a fresh shared context"
     finally:
         ma.close(); mb.close(); ca.close(); cb.close()
+
+
+# the step forms of the batched decoder the tiny model runs: (clips of the 90 below, environment, what VOX_BATCH_VERBOSE must show)
+_TINY_FORMS = {
+    "one_group_n12": (12, {}, lambda v: [p[:2] + p[3:] for p in v["lockstep"]] == [(12, 1, "xf-chains")]),
+    "lockstep_n20": (20, {"VOX_BATCH_NO_CONTINUOUS": "1"}, lambda v: [p[1:2] + p[3:] for p in v["lockstep"]] == [(2, "xf-chains")]),
+    "lockstep_n40_ragged": (40, {"VOX_BATCH_NO_CONTINUOUS": "1"}, lambda v: [p[1:2] + p[3:] for p in v["lockstep"]] == [(3, "xf-chains")]),
+    "no_xf_n40": (40, {"VOX_BATCH_NO_XF": "1"}, lambda v: [p[1:2] + p[3:] for p in v["lockstep"]] == [(3, "f32")]),
+    **{f"continuous_g{G}": (90, {"VOX_BATCH_SLOT_GROUPS": str(G)}, (lambda G: lambda v: v["slots"] == [16 * G] and sum(v["forms"].values()) > 0)(G)) for G in (1, 2, 3, 4)},
+    **{f"wide_g{G}": (90, {"VOX_BATCH_SLOT_GROUPS": str(G), "VOX_BATCH_WIDE_MIN": "2", "VOX_BATCH_CONT_NO_ENGINE": "1", **({"VOX_BATCH_NO_WIDE_SPLIT": "1"} if G == 4 else {})},
+                      (lambda G: lambda v: v["slots"] == [16 * G] and v["forms"]["wide"] > 0)(G)) for G in (2, 3, 4)},
+    **{f"split_g{G}": (90, {"VOX_BATCH_SLOT_GROUPS": str(G)}, (lambda G: lambda v: v["slots"] == [16 * G] and v["forms"]["split"] > 0)(G)) for G in (5, 6)},
+}
+_WIDE_FORMS = {k for k in _TINY_FORMS if k.startswith(("wide", "split"))}
+
+
+@pytest.fixture(scope="module")
+def tf_cache():
+    return {}
+
+
+@pytest.mark.parametrize("form", list(_TINY_FORMS))
+def test_batch_logits_every_step_form_vs_teacher_forced(pkg, orc, ctx, tiny, form, capfd, monkeypatch, tf_cache):
+    """Every step form of the batched decoder at LOGIT precision: the per-unit logits tap (vox_debug_batch_tap_*) of one call against the teacher-forced logits of the same
+    ids (the sequence's own ids fed back: no divergence, so every row of every tapped unit is asserted -- no near-tie escape).  Each tapped row's argmax is its id (lowest index
+    on ties); max|tap - ref| <= TOL * max|ref| against vox_forward_streaming (the prefill path: no decode kernel in common) for every tapped unit, and against the CPU oracle
+    for the shortest unit and a refilled / last-slot one.  Ragged 0.4 .. 4.5 s clips of test_transcribe_batch_continuous_slots; the tiny vocabulary makes a row 2 KB, so
+    every unit of the call is tapped: slot 0, the last slot of the last group, the units that start in a vacated slot, the shortest and the longest among them.
+    VOX_BATCH_VERBOSE proves the form ran."""
+    m, o, _ = tiny
+    t = pkg.TimeEmbedding(256).embed(6.0)
+    n, env, ran = _TINY_FORMS[form]
+    secs = [0.4 + 0.23 * ((7 * i) % 19) for i in range(90)]
+    secs[5] = 0.05; secs[41] = 0.12
+    clips = [pkg.synth.synth_audio(s, seed=1900 + i) for i, s in enumerate(secs)][:n]
+    monkeypatch.setenv("VOX_BATCH_NO_CALIB", "1"); monkeypatch.setenv("VOX_BATCH_VERBOSE", "1")
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    capfd.readouterr()
+    outs, taps = m.transcribe_batch(clips, t, tap_units=list(range(n)))
+    v = parse_batch_verbose(capfd.readouterr().err)
+    for k in env:
+        monkeypatch.delenv(k)
+    assert m.timings()["graph_replays"] > 0
+    if form in _WIDE_FORMS and v["slots"] and v["forms"]["wide"] + v["forms"]["split"] == 0:
+        pytest.skip(f"{form}: the wide step does not cover the tiny geometry (covered at full size: test_full_batch_logits_step_forms_vs_teacher_forced)")
+    assert ran(v), f"{form}: the form did not run: {v}"
+    lens = [len(x) for x in outs]
+    special = {"shortest": int(np.argmin([len(c) for c in clips])), "longest": int(np.argmax([len(c) for c in clips]))}
+    if v["plan"]:
+        special["slot0"] = v["plan"][0][0]; special["last_slot"] = next(q[0] for q in reversed(v["plan"]) if q)      # (more slots than units: the last ones stay empty)
+        refills = [q[1] for q in v["plan"] if len(q) > 1]
+        if n > len(v["plan"]):
+            assert refills, f"{n} clips on {len(v['plan'])} slots: some slot must take a second unit"
+        if refills:
+            special["refill"] = refills[-1]
+    worst = 0.0
+    for u in range(n):
+        ids, tp = outs[u], taps[u]
+        assert tp.shape == (lens[u], 512)
+        assert np.array_equal(argmax_low(tp), ids), f"{form}, unit {u}: the tapped rows are not those the ids were taken from"
+        key = ("gpu", u, ids.tobytes())
+        if key not in tf_cache:
+            tf_cache[key] = teacher_forced_logits(pkg, ctx, m, clips[u], t, ids)
+        e = rel_err(tp, tf_cache[key]); worst = max(worst, e)
+        assert e <= TOL, f"{form}, unit {u} ({[k for k, x in special.items() if x == u]}): max|tap - teacher forced| = {e:.3e} of max|ref|"
+    worst_o = 0.0
+    for u in sorted({special["shortest"], special.get("refill", special.get("last_slot", special["longest"]))}):
+        key = ("oracle", u, outs[u].tobytes())
+        if key not in tf_cache:
+            tf_cache[key] = teacher_forced_logits(pkg, ctx, m, clips[u], t, outs[u], oracle=o)
+        e = rel_err(taps[u], tf_cache[key]); worst_o = max(worst_o, e)
+        assert e <= TOL, f"{form}, unit {u}: max|tap - oracle teacher forced| = {e:.3e} of max|ref|"
+    print(f"batch logits, tiny, {form}: {n} units / {sum(lens)} rows tapped, worst rel err {worst:.2e} vs teacher-forced GPU, {worst_o:.2e} vs oracle; "
+          f"special units {special}; verbose {v['lockstep'] or v['forms']}")
+
+
+def test_batch_tap_contract(pkg, ctx, tiny):
+    """vox_debug_batch_tap_*: the tap is consumed by the next batch call (a plain one too) and fetched once; rows past max_rows are dropped and counted (rows_per_unit);
+    a tapped unit outside the call fails the call; a call that would run as several sessions fails with VOX_ERR_UNSUPPORTED instead of filling part of the tap."""
+    import ctypes as C
+    m, _, _ = tiny
+    L = pkg.lib(); t = pkg.TimeEmbedding(256).embed(6.0)
+    clips = [pkg.synth.synth_audio(1.0 + 0.7 * i, seed=600 + i) for i in range(4)]
+    outs, taps = m.transcribe_batch(clips, t, tap_units=[2, 0])
+    assert [len(x) for x in taps] == [len(outs[2]), len(outs[0])] and len(outs[0]) > 2
+    fetch = lambda buf, rows: L.vox_debug_batch_tap_fetch(m.h, buf.ctypes.data, rows)
+    assert L.vox_debug_batch_tap_arm(m.h, (C.c_int32 * 2)(0, 2), 2, 2) == 0
+    again = m.transcribe_batch(clips, t)                                     # a plain call consumes the armed tap
+    assert all(np.array_equal(a, b) for a, b in zip(outs, again))
+    buf = np.zeros((2, 2, 512), np.float32); rows = (C.c_int32 * 2)()
+    assert fetch(buf, rows) == 0
+    assert list(rows) == [len(outs[0]), len(outs[2])]                        # counted, though only max_rows = 2 were kept
+    assert np.array_equal(buf[0], taps[1][:2]) and np.array_equal(buf[1], taps[0][:2])
+    assert fetch(buf, rows) == 1                                             # fetched once
+    assert L.vox_debug_batch_tap_arm(m.h, (C.c_int32 * 1)(7), 1, 8) == 0
+    with pytest.raises(pkg.VoxError, match="out of range"):
+        m.transcribe_batch(clips, t)                                         # unit 7 of a 4-unit call
+    assert fetch(buf, rows) == 1                                             # consumed by the failed call
+    assert len(m.transcribe_batch(clips, t)) == 4                            # and nothing is left armed
+    many = [pkg.synth.synth_audio(0.6, seed=650 + i) for i in range(256)]
+    m.set_sessions(2)
+    try:
+        with pytest.raises(pkg.VoxError) as ei:
+            m.transcribe_batch(many, t, tap_units=[0, 255])                  # 256 units = two sessions
+        assert ei.value.code == 5 and "session" in str(ei.value)
+        assert fetch(buf, rows) == 1
+    finally:
+        m.set_sessions(1)
 
 
 def test_two_contexts_two_threads_and_model_replicate(pkg, ctx, tiny):

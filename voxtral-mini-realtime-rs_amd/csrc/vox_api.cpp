@@ -812,6 +812,8 @@ struct vox_model {
     vox_cache* pw_pend_cache = nullptr; uint64_t pw_pend_gen = 0; int pw_pend_rows = 0; bool pw_verdict_failed = false;
     unsigned* pw_err_pin = nullptr;      // pinned host copy of the engine's error word, refreshed (async) behind every piecewise engine launch: checked without a device round trip
     vox_timings timings{};
+    // vox_debug_batch_tap_*: units (caller indices) armed for the next batch call; `on` during that call; out / rows hold the call's rows until fetched
+    struct { std::vector<int> units; int max_rows = 0; bool armed = false, on = false, ready = false; float* out = nullptr; int* rows = nullptr; } tap;
 };
 
 // arena layout planner: pass 1 (base == nullptr) only sizes, pass 2 hands out pointers
@@ -1212,6 +1214,8 @@ static void model_release(vox_model* m) {
                     (void*)m->engb_tab[0], (void*)m->engb_tab[1], (void*)m->engb_tab[2], (void*)m->engb_tab[3], (void*)m->pw_x, (void*)m->pw_hidden, (void*)m->pw_logits, (void*)m->pw_part_val, (void*)m->pw_part_idx, (void*)m->pw_ids, (void*)m->pw_zero, (void*)m->pw_tab})
         if (p) (void)hipFree(p);
     if (m->pw_err_pin) (void)hipHostFree(m->pw_err_pin);
+    if (m->tap.out) (void)hipFree(m->tap.out);
+    if (m->tap.rows) (void)hipFree(m->tap.rows);
     delete m;
 }
 extern "C" int32_t vox_model_free(vox_model* m) { model_release(m); return VOX_OK; }
@@ -2296,6 +2300,29 @@ static bool batch_xf_ok(const vox_model* m) {
     const vox_model_cfg& c = m->cfg; const int D = c.dec_dim, QD = c.dec_heads * c.dec_head_dim, F = c.dec_ffn;
     return m->tok.w.fmt == WFMT_Q4_0 && m->dec[0].wqkv.w.fmt == WFMT_Q4_0 && m->tok.w.qt && m->dec[0].wqkv.w.qt && D % 128 == 0 && QD % 128 == 0 && F % 128 == 0 && !knob_str("VOX_BATCH_NO_XF");
 }
+// the logits tap of one driver call (vox_debug_batch_tap_*): clip_unit[i] = the tap index of the driver's utterance i (slot_of[i] = its caller index), or -1.  Off:
+// no buffer, no launch.  rows(...) enqueues the copy of the rows the next argmax launch reads (launch_batch_tap), inside a capture as well as eagerly.
+struct BatchTapCall {
+    vox_model* m; DevBuf clip_unit; int n = 0;
+    bool on() const { return clip_unit.p != nullptr; }
+    int32_t init(vox_model* mm, int nn, const int* slot_of, hipStream_t s) {
+        m = mm; n = nn;
+        if (!m->tap.on) return VOX_OK;
+        std::vector<int> cu(n, -1); bool any = false;
+        for (int i = 0; i < n; i++) for (size_t j = 0; j < m->tap.units.size(); j++) if (m->tap.units[j] == slot_of[i]) { cu[i] = (int)j; any = true; }
+        if (!any) return VOX_OK;
+        HIPCHK(clip_unit.alloc_pooled(m->ctx, (size_t)n * 4));
+        HIPCHK(hipMemcpyAsync(clip_unit.p, cu.data(), (size_t)n * 4, hipMemcpyHostToDevice, s)); HIPCHK(hipStreamSynchronize(s));      // (cu goes out of scope)
+        return VOX_OK;
+    }
+    int32_t rows(const float* logits, int n_rows, const int* slot_clip, int clip0, const int* pos, const int* seq_len, hipStream_t s) const {
+        if (!on()) return VOX_OK;
+        BatchTapParams p{}; p.logits = logits; p.vocab = m->cfg.vocab; p.slot_clip = slot_clip; p.clip0 = clip0; p.pos = pos; p.seq_len = seq_len;
+        p.clip_unit = (const int*)clip_unit.p; p.n_clips = n; p.out = m->tap.out; p.rows = m->tap.rows; p.n_units = (int)m->tap.units.size(); p.max_rows = m->tap.max_rows; p.first_pos = 38;
+        HIPCHK(launch_batch_tap(p, n_rows, s));
+        return VOX_OK;
+    }
+};
 static int32_t transcribe_batch_impl(vox_model* m, int32_t n, const float* const* samples, const size_t* n_samples, const float* t_embed,
                                      int32_t* const* out_ids, const int32_t* caps, int32_t* n_ids, int32_t mem_kind, const int* slot_of, bool allow_engine = true,
                                      const float* const* unit_scale = nullptr) {      // unit_scale[i]: device float the front-end multiplies unit i by (vox_transcribe_batch_ex: the peak scale of the unit's FILE); null = every unit normalises itself      // slot_of[i]: the caller's slot of row i (error messages)
@@ -2314,6 +2341,7 @@ static int32_t transcribe_batch_impl(vox_model* m, int32_t n, const float* const
     const size_t seq_stride = (size_t)KV * max_seq * hd, layer_stride = (size_t)n * seq_stride;
     size_t mel_floats = 0; for (int i = 0; i < n; i++) mel_floats += (size_t)128 * T[i];
     DevBuf b_audio, b_k, b_v, b_tok, b_pos, b_len, b_h, b_xn, b_qkv, b_att, b_act, b_logits, b_px, b_mel, b_scale, b_smp, b_xf1, b_xf2, b_xf3, b_ssq;
+    BatchTapCall tap; VOXCHK(tap.init(m, n, slot_of, s));
     BatchDrain drain{cx};
     HIPCHK(b_audio.alloc_pooled(cx, (size_t)n * audio_rows * D * 4)); HIPCHK(b_k.alloc_pooled(cx, layer_stride * c.dec_layers * 4)); HIPCHK(b_v.alloc_pooled(cx, layer_stride * c.dec_layers * 4));
     HIPCHK(b_tok.alloc_pooled(cx, (size_t)n * tstride * 4)); HIPCHK(b_pos.alloc_pooled(cx, (size_t)n * 4)); HIPCHK(b_len.alloc_pooled(cx, (size_t)n * 4));
@@ -2379,6 +2407,7 @@ static int32_t transcribe_batch_impl(vox_model* m, int32_t n, const float* const
         }
     }
     // first generated token of every utterance + the first step's input (and, XF step, its folded first RMSNorm)
+    VOXCHK(tap.rows(b_logits.as<float>(), n, nullptr, 0, d_pos, b_len.as<int>(), s));
     HIPCHK(launch_argmax_embed_batch(b_logits.as<float>(), n, V, d_tok, tstride, d_pos, b_len.as<int>(), m->tok.w, d_audio, (long)audio_rows * D, D, b_h.as<float>(), s,
                                      use_xf ? b_xf1.as<uint16_t>() : nullptr, use_xf ? m->dec[0].attn_norm : nullptr, use_xf ? b_ssq.as<float>() : nullptr,
                                      (long)(xf_bytes(D) / 2), parts_D * 16));
@@ -2401,6 +2430,7 @@ static int32_t transcribe_batch_impl(vox_model* m, int32_t n, const float* const
                 HIPCHK(launch_decode_engine_b16(ep, s));      // the group's 26 layers as one launch, then its lm_head
                 VOXCHK(engb_group_tail(m, xb, b_ssq_e.as<float>(), gi, ng, s));
             }
+            VOXCHK(tap.rows(b_logits.as<float>(), n, nullptr, 0, d_pos, b_len.as<int>(), s));
             if (use_eng) HIPCHK(launch_argmax_embed_batch(b_logits.as<float>(), n, V, d_tok, tstride, d_pos, b_len.as<int>(), m->tok.w, d_audio, (long)audio_rows * D, D, h, s));      // the engine reads the f32 rows
             else HIPCHK(launch_argmax_embed_batch(b_logits.as<float>(), n, V, d_tok, tstride, d_pos, b_len.as<int>(), m->tok.w, d_audio, (long)audio_rows * D, D, h, s,
                                                   b_xf1.as<uint16_t>(), m->dec[0].attn_norm, b_ssq.as<float>(), (long)(xf_bytes(D) / 2), parts_D * 16));
@@ -2421,6 +2451,7 @@ static int32_t transcribe_batch_impl(vox_model* m, int32_t n, const float* const
         }
         HIPCHK(launch_rms_norm(h, D, n, D, m->dec_norm, nullptr, c.norm_eps, xn, D, s));
         { GemmParams g{}; g.w = m->tok.w; g.x = xn; g.x_stride = D; g.M = n; g.out = b_logits.as<float>(); g.out_stride = V; HIPCHK(launch_q4_gemm(g, EPI_STORE, s)); }
+        VOXCHK(tap.rows(b_logits.as<float>(), n, nullptr, 0, d_pos, b_len.as<int>(), s));
         HIPCHK(launch_argmax_embed_batch(b_logits.as<float>(), n, V, d_tok, tstride, d_pos, b_len.as<int>(), m->tok.w, d_audio, (long)audio_rows * D, D, h, s));
         return VOX_OK;
     };
@@ -2446,6 +2477,7 @@ static int32_t transcribe_batch_impl(vox_model* m, int32_t n, const float* const
     VOXCHK(copy_out_ids(n, S, tstride, d_tok, out_ids, n_ids, &total, s));
     m->timings.preprocess_ms = pre_ms; m->timings.encode_ms = enc_ms; m->timings.decode_ms = now_ms() - t1; m->timings.total_ms = now_ms() - t0;
     m->timings.decode_tokens = total; m->timings.graph_replays = replays;
+    if (knob_str("VOX_BATCH_VERBOSE")) fprintf(stderr, "[voxtral_hip] lock-step batch: %d rows, %d groups, %d steps, step form %s\n", n, n_grp, steps, use_eng ? "engine" : use_xf ? "xf-chains" : "f32");
     return VOX_OK;
 }
 
@@ -2578,6 +2610,7 @@ static int32_t transcribe_continuous_impl(vox_model* m, int32_t n, const float* 
 
     DevBuf b_audio, b_k, b_v, b_tok, b_posc, b_len, b_h0, b_aoff, b_px, b_xn, b_lg0, b_mel, b_scale, b_smp;
     DevBuf b_queue, b_sclip, b_sqpos, b_pos, b_kvrow, b_h, b_qkv, b_att, b_logits, b_xf1, b_xf2, b_xf3, b_ssq, b_ssq_e;
+    BatchTapCall tap; VOXCHK(tap.init(m, n, slot_of, s));
     BatchDrain drain{cx};
     HIPCHK(b_audio.alloc_pooled(cx, audio_floats * 4)); HIPCHK(b_k.alloc_pooled(cx, layer_stride * c.dec_layers * 4)); HIPCHK(b_v.alloc_pooled(cx, layer_stride * c.dec_layers * 4));
     HIPCHK(b_tok.alloc_pooled(cx, (size_t)n * tstride * 4)); HIPCHK(b_posc.alloc_pooled(cx, (size_t)n * 4)); HIPCHK(b_len.alloc_pooled(cx, (size_t)n * 4));
@@ -2640,6 +2673,7 @@ static int32_t transcribe_continuous_impl(vox_model* m, int32_t n, const float* 
         // logits of every utterance's last prefix row -> its first generated token and its first decode input h0 = audio[38] + embed(token)
         HIPCHK(launch_rms_norm(px + (size_t)(PREFIX_LEN - 1) * D, PREFIX_LEN * D, nc, D, m->dec_norm, nullptr, c.norm_eps, b_xn.as<float>(), D, s));
         { GemmParams g{}; g.w = m->tok.w; g.x = b_xn.as<float>(); g.x_stride = D; g.M = nc; g.out = b_lg0.as<float>(); g.out_stride = V; HIPCHK(launch_q4_gemm(g, EPI_STORE, s)); }
+        VOXCHK(tap.rows(b_lg0.as<float>(), nc, nullptr, c0, b_posc.as<int>() + c0, b_len.as<int>() + c0, s));
         HIPCHK(launch_argmax_embed_batch(b_lg0.as<float>(), nc, V, d_tok + (size_t)c0 * tstride, tstride, b_posc.as<int>() + c0, b_len.as<int>() + c0, m->tok.w, d_audio, 0, D,
                                          b_h0.as<float>() + (size_t)c0 * D, s, nullptr, nullptr, nullptr, 0, 0, b_aoff.as<long>() + c0));
         // (the last chunk's prefill is not waited for here when a decode follows: the decode's buffers are set up and its graphs captured -- host work, ~6-10 ms per
@@ -2652,6 +2686,7 @@ static int32_t transcribe_continuous_impl(vox_model* m, int32_t n, const float* 
     double t1 = now_ms();
     // ---- (B) + (C): the slot decode
     int replays = 0, n_captures = 0; double capture_ms = 0.0;
+    int form_steps[5] = {0, 0, 0, 0, 0};      // VOX_BATCH_VERBOSE: decode steps on the launch chains, the one- / two-group engine, one wide chain, two or more wide chains
     if (steps > 0) {
         const int parts_D = q4_skinny_resid_xf_parts(D);
         HIPCHK(b_sclip.alloc_pooled(cx, (size_t)Sl * 4)); HIPCHK(b_sqpos.alloc_pooled(cx, (size_t)Sl * 4));
@@ -2764,6 +2799,7 @@ static int32_t transcribe_continuous_impl(vox_model* m, int32_t n, const float* 
                 for (int gi = 0; gi < G; gi++)
                     if ((active >> gi) & 1u) VOXCHK(xf_group_chain(m, xb, gi, 16, d_pos, d_kvrow, true, 0, b_k.as<float>(), b_v.as<float>(), layer_stride, seq_stride, max_seq, s));
             }
+            VOXCHK(tap.rows(b_logits.as<float>(), Sl, b_sclip.as<int>(), 0, d_pos, nullptr, s));
             HIPCHK(launch_argmax_embed_slots(sp, Sl, s));      // (retired groups' slots are idle: slot_clip < 0)
             return VOX_OK;
         };
@@ -2814,6 +2850,7 @@ static int32_t transcribe_continuous_impl(vox_model* m, int32_t n, const float* 
                 seg_act[n_seg] = __builtin_popcount(act); n_seg++; last_act = act;
             }
             if (n_seg > 0) seg_n[n_seg - 1]++;
+            { const StepForm f = form_of(act); form_steps[(f.bits & kEng1) ? 1 : (f.bits & kEng2) ? 2 : f.nc == 1 ? 3 : f.nc > 1 ? 4 : 0]++; }
             m->engb_launches += eng_launches(act);
             if (no_graph) { VOXCHK(step(act)); continue; }
             if (hipGraphLaunch(graphs.find(act), s) != hipSuccess) return fail(VOX_ERR_HIP, "hipGraphLaunch failed");
@@ -2834,6 +2871,12 @@ static int32_t transcribe_continuous_impl(vox_model* m, int32_t n, const float* 
     m->timings.preprocess_ms = pre_ms; m->timings.encode_ms = enc_ms; m->timings.decode_ms = pf_ms + (now_ms() - t1); m->timings.total_ms = now_ms() - t0;
     m->timings.decode_tokens = total; m->timings.graph_replays = replays;
     if (knob_str("VOX_BATCH_VERBOSE")) fprintf(stderr, "[voxtral_hip] continuous batch: %d utterances, %d slots, %d steps (plan %.1f ms), front-end %.1f ms, encode %.1f ms (%d chunks), prefill %.1f ms (%d graph captures, %.1f ms of host time, under the last chunk's), decode %.1f ms; step costs used %.2f / %.2f / %.2f / %.2f / %.2f / %.2f / %.2f / %.2f ms\n", n, Sl, steps, plan.cost_ms, pre_ms, enc_ms, n_chunks, pf_ms, n_captures, capture_ms, now_ms() - t1, step_cost[1], step_cost[2], step_cost[3], step_cost[4], step_cost[5], step_cost[6], step_cost[7], step_cost[8]);
+    if (knob_str("VOX_BATCH_VERBOSE")) {
+        fprintf(stderr, "[voxtral_hip] continuous batch step forms: chains %d, engine1 %d, engine2 %d, wide %d, split %d\n", form_steps[0], form_steps[1], form_steps[2], form_steps[3], form_steps[4]);
+        std::string q = "[voxtral_hip] continuous batch slot plan (caller units per slot):";
+        for (size_t sl = 0; sl < plan.queue.size(); sl++) { q += sl ? " |" : " "; for (int u : plan.queue[sl]) q += " " + std::to_string(slot_of[u]); }
+        fprintf(stderr, "%s\n", q.c_str());
+    }
     return VOX_OK;
 }
 
@@ -2922,13 +2965,26 @@ static int32_t transcribe_batch_sessions(vox_model* m, int S, int32_t n, const f
 }
 extern "C" int32_t vox_transcribe_batch_ex(vox_model* m, int32_t n, const float* const* samples_in, const size_t* n_samples, const int32_t* norm_group, const float* t_embed,
                                            int32_t* const* out_ids, const int32_t* caps, int32_t* n_ids, int32_t mem_kind_in) {
-    ARGCHK(m && samples_in && n_samples && t_embed && out_ids && caps && n_ids, "null argument"); ARGCHK(n > 0 && n <= 4096, "batch size %d out of range (1..4096)", n);
+    ARGCHK(m, "null model");
+    const bool tapped = m->tap.armed; m->tap.armed = false;      // an armed tap is consumed by this call, whatever its outcome
+    ARGCHK(samples_in && n_samples && t_embed && out_ids && caps && n_ids, "null argument"); ARGCHK(n > 0 && n <= 4096, "batch size %d out of range (1..4096)", n);
+    if (tapped) {
+        for (int u : m->tap.units) ARGCHK(u < n, "tapped unit %d out of range (batch of %d)", u, n);
+        VOXCHK(ctx_bind(m->ctx));
+        const size_t bytes = m->tap.units.size() * (size_t)m->tap.max_rows * m->cfg.vocab * 4;
+        HIPCHK(hipMalloc((void**)&m->tap.out, bytes)); HIPCHK(hipMalloc((void**)&m->tap.rows, m->tap.units.size() * 4));
+        HIPCHK(hipMemset(m->tap.out, 0, bytes)); HIPCHK(hipMemset(m->tap.rows, 0, m->tap.units.size() * 4));
+    }
     if (!m->twins.empty() && !knob_str("VOX_BATCH_ONE_SESSION")) {
         const int S = std::min((int)m->twins.size() + 1, n / kMinUnitsPerSession);
+        if (S > 1 && tapped) return fail(VOX_ERR_UNSUPPORTED, "the batch logits tap covers one session: this call would run as %d (vox_model_set_sessions)", S);
         if (S > 1) { for (int i = 0; i < n; i++) ARGCHK(samples_in[i] && n_samples[i] > 0, "empty audio in batch slot %d", i);
                      return transcribe_batch_sessions(m, S, n, samples_in, n_samples, norm_group, t_embed, out_ids, caps, n_ids, mem_kind_in); }
     }
-    return transcribe_batch_one_session(m, n, samples_in, n_samples, norm_group, t_embed, out_ids, caps, n_ids, mem_kind_in);
+    m->tap.on = tapped;
+    const int32_t r = transcribe_batch_one_session(m, n, samples_in, n_samples, norm_group, t_embed, out_ids, caps, n_ids, mem_kind_in);
+    m->tap.on = false; m->tap.ready = tapped && r == VOX_OK;
+    return r;
 }
 static int32_t transcribe_batch_one_session(vox_model* m, int32_t n, const float* const* samples_in, const size_t* n_samples, const int32_t* norm_group, const float* t_embed,
                                             int32_t* const* out_ids, const int32_t* caps, int32_t* n_ids, int32_t mem_kind_in) {
@@ -3518,5 +3574,34 @@ extern "C" int32_t vox_debug_timeline_fetch(vox_ctx* c, uint64_t* out, size_t ca
     HIPCHK(hipMemcpy(out, g_tl_dev, words * 8, hipMemcpyDeviceToHost));
     *slots_used = tl_slots_used();
     (void)tl_configure(nullptr, 0, 0); (void)hipFree(g_tl_dev); g_tl_dev = nullptr;
+    return VOX_OK;
+}
+
+// ---- debug: per-unit logits tap of the batched decoder (BatchTapCall, launch_batch_tap)
+static void tap_release(vox_model* m) {
+    if (m->tap.out || m->tap.rows) (void)hipSetDevice(m->ctx->device);
+    if (m->tap.out) (void)hipFree(m->tap.out);
+    if (m->tap.rows) (void)hipFree(m->tap.rows);
+    m->tap.out = nullptr; m->tap.rows = nullptr; m->tap.armed = m->tap.ready = false;
+}
+extern "C" int32_t vox_debug_batch_tap_arm(vox_model* m, const int32_t* units, int32_t n_units, int32_t max_rows) {
+    ARGCHK(units && n_units > 0 && n_units <= 4096, "bad tap unit list (%d units)", n_units); ARGCHK(max_rows > 0 && max_rows <= 65536, "max_rows %d out of range (1..65536)", max_rows);
+    ARGCHK(m, "null model");
+    std::vector<int> u(units, units + n_units);
+    for (int i = 0; i < n_units; i++) { ARGCHK(u[i] >= 0, "tapped unit %d < 0", u[i]); for (int j = 0; j < i; j++) ARGCHK(u[j] != u[i], "unit %d tapped twice", u[i]); }
+    tap_release(m);
+    m->tap.units = u; m->tap.max_rows = max_rows; m->tap.armed = true;
+    return VOX_OK;
+}
+extern "C" int32_t vox_debug_batch_tap_fetch(vox_model* m, float* out, int32_t* rows_per_unit) {
+    ARGCHK(m && out && rows_per_unit, "null argument");
+    if (!m->tap.ready) { tap_release(m); return fail(VOX_ERR_INVALID, "no batch tap to fetch (arm one, then make one successful vox_transcribe_batch call)"); }
+    VOXCHK(ctx_bind(m->ctx));
+    const size_t nu = m->tap.units.size();
+    HIPCHK(hipDeviceSynchronize());
+    const hipError_t e1 = hipMemcpy(out, m->tap.out, nu * (size_t)m->tap.max_rows * m->cfg.vocab * 4, hipMemcpyDeviceToHost);
+    const hipError_t e2 = hipMemcpy(rows_per_unit, m->tap.rows, nu * 4, hipMemcpyDeviceToHost);
+    tap_release(m);
+    if (e1 != hipSuccess || e2 != hipSuccess) return fail(VOX_ERR_HIP, "batch tap copy failed");
     return VOX_OK;
 }

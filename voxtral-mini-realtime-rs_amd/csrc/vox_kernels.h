@@ -213,6 +213,17 @@ struct SlotStepParams {
     int init;                                          // 1: no argmax, every slot takes the head of its queue
 };
 hipError_t launch_argmax_embed_slots(const SlotStepParams& p, int n_slots, hipStream_t s);
+// debug (vox_debug_batch_tap_*): copy the logits rows the next argmax launch of a batched decode takes its tokens from.  Row r belongs to utterance slot_clip[r]
+// (slot_clip null: clip0 + r; < 0: an idle slot, nothing written) and yields that utterance's token at position pos[r] + 1 -- when seq_len is given, only if
+// pos[r] + 1 < seq_len[r], as argmax_embed_batch_kernel -- which is id k = pos[r] + 1 - first_pos of its output.  Utterances with clip_unit[c] = j >= 0 are tapped:
+// the row goes to out[j][k] (k < max_rows; a later row is dropped) and rows[j] = max(rows[j], k + 1), so rows[j] > max_rows tells how many were dropped.
+struct BatchTapParams {
+    const float* logits; int vocab;                    // [n_rows][vocab]
+    const int* slot_clip; int clip0; const int* pos; const int* seq_len;      // per row (seq_len may be null)
+    const int* clip_unit; int n_clips;                 // per utterance of the driver call: tap index or -1
+    float* out; int* rows; int n_units, max_rows, first_pos;      // out [n_units][max_rows][vocab]
+};
+hipError_t launch_batch_tap(const BatchTapParams& p, int n_rows, hipStream_t s);
 hipError_t launch_occupy(int workgroups, int micros, hipStream_t s);      // test hook: spin `workgroups` x 1024 threads for `micros` us
 hipError_t launch_add_rows(const float* a, const float* b, float* out, long n, hipStream_t s);
 hipError_t launch_gelu(float* x, long n, hipStream_t s);

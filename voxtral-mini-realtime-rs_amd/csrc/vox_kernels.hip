@@ -4318,6 +4318,29 @@ hipError_t launch_argmax_embed_slots(const SlotStepParams& p, int n_slots, hipSt
     return hipGetLastError();
 }
 
+// one workgroup per row (see BatchTapParams): every index is checked before the row is read or written
+__global__ __launch_bounds__(256) void batch_tap_kernel(const BatchTapParams p) {
+    const int r = blockIdx.x;
+    const int c = p.slot_clip ? p.slot_clip[r] : p.clip0 + r;
+    if (c < 0 || c >= p.n_clips) return;
+    const int j = p.clip_unit[c];
+    if (j < 0 || j >= p.n_units) return;
+    const int cur = p.pos[r] + 1;
+    if (p.seq_len && cur >= p.seq_len[r]) return;      // the argmax launch writes no token for this row
+    const int k = cur - p.first_pos;
+    if (k < 0) return;
+    if (threadIdx.x == 0) atomicMax(p.rows + j, k + 1);
+    if (k >= p.max_rows) return;
+    const float* src = p.logits + (size_t)r * p.vocab; float* dst = p.out + ((size_t)j * p.max_rows + k) * p.vocab;
+    if ((p.vocab & 3) == 0) { for (int i = threadIdx.x; i < (p.vocab >> 2); i += blockDim.x) reinterpret_cast<float4*>(dst)[i] = reinterpret_cast<const float4*>(src)[i]; }
+    else for (int i = threadIdx.x; i < p.vocab; i += blockDim.x) dst[i] = src[i];
+}
+hipError_t launch_batch_tap(const BatchTapParams& p, int n_rows, hipStream_t s) {
+    if (n_rows <= 0 || !p.logits || !p.pos || !p.clip_unit || !p.out || !p.rows || p.vocab <= 0 || p.n_units <= 0 || p.max_rows <= 0 || p.n_clips <= 0) return hipErrorInvalidValue;
+    batch_tap_kernel<<<dim3(n_rows), dim3(256), 0, s>>>(p);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------
 // Sample-rate conversion (audio/resample.rs:16-52 `resample`).  The reference calls rubato 1.0's synchronous FFT resampler (`Fft`, FixedSync::Input,
 // chunk 1024, 2 sub-chunks): blocks of fft_in samples, zero-padded to 2 fft_in, real FFT, times the FFT of a Blackman-Harris^2 windowed sinc, the

@@ -515,11 +515,13 @@ class Q4VoxtralModel:
         check(lib().vox_transcribe_audio(self.h, ptr, n_samples, _ptr(t), _ptr(ids), cap, C.byref(n), kind))
         return ids[:n.value].copy()
 
-    def transcribe_batch(self, samples_list, t_embed, device_ptrs=None, n_samples=None, norm_group=None):
+    def transcribe_batch(self, samples_list, t_embed, device_ptrs=None, n_samples=None, norm_group=None, tap_units=None):
         """Batched whole-path transcription of independent utterances (<= 4096; wider than 16: continuous batching over decode slots): list of float32 sample arrays
         (or device pointers + lengths) -> list of id arrays.  Decode steps are batched so weights stream once per step.
         norm_group (vox_transcribe_batch_ex): per unit, the id of the FILE whose peak normalises it (the CLI's semantics: normalise the file, then chunk it,
-        bin/transcribe.rs:207-226); < 0 = use the unit as it is; None = every unit normalises itself."""
+        bin/transcribe.rs:207-226); < 0 = use the unit as it is; None = every unit normalises itself.
+        tap_units (vox_debug_batch_tap_*): unit indices whose logits rows are tapped -> (outs, taps), taps[j] [len(outs[tap_units[j]])][vocab] f32: row k is the row
+        out_ids[tap_units[j]][k] was the argmax of."""
         t = _f32(t_embed).reshape(-1)
         if device_ptrs is None:
             arrs = [_f32(x) for x in samples_list]; n = len(arrs)
@@ -529,6 +531,14 @@ class Q4VoxtralModel:
         caps = [int(lens[i]) // 1280 + 128 for i in range(n)]
         outs = [np.zeros(cp, dtype=np.int32) for cp in caps]
         optrs = (C.c_void_p * n)(*[o.ctypes.data for o in outs]); ccaps = (C.c_int32 * n)(*caps); nids = (C.c_int32 * n)()
+        if tap_units is not None:
+            units = [int(u) for u in tap_units]
+            if not units or any(u < 0 or u >= n for u in units):
+                raise ValueError("tap_units: indices into this call's units")
+            from .audio import PadConfig
+            pc = PadConfig.voxtral()
+            max_rows = max(1, max(pc.padded_len(int(lens[u])) // 2560 - 35 for u in units))      # >= max(S - 38, 1): S <= padded / 2560 + 1 decoder positions
+            check(lib().vox_debug_batch_tap_arm(self.h, (C.c_int32 * len(units))(*units), len(units), max_rows))
         if norm_group is None:
             check(lib().vox_transcribe_batch(self.h, n, ptrs, lens, _ptr(t), optrs, ccaps, nids, kind))
         else:
@@ -536,7 +546,18 @@ class Q4VoxtralModel:
                 raise ValueError("norm_group needs one entry per unit")
             grp = (C.c_int32 * n)(*[int(g) for g in norm_group])
             check(lib().vox_transcribe_batch_ex(self.h, n, ptrs, lens, grp, _ptr(t), optrs, ccaps, nids, kind))
-        return [outs[i][:nids[i]].copy() for i in range(n)]
+        res = [outs[i][:nids[i]].copy() for i in range(n)]
+        if tap_units is None:
+            return res
+        V = self.config.vocab
+        buf = np.zeros((len(units), max_rows, V), dtype=np.float32); rows = (C.c_int32 * len(units))()
+        check(lib().vox_debug_batch_tap_fetch(self.h, buf.ctypes.data, rows))
+        taps = []
+        for j, u in enumerate(units):
+            if rows[j] != len(res[u]):
+                raise VoxError(1, f"batch tap: unit {u} has {rows[j]} tapped rows for {len(res[u])} ids (max_rows {max_rows})")
+            taps.append(buf[j, :rows[j]].copy())
+        return res, taps
 
     def timings(self):
         t = _lib.Timings(); check(lib().vox_get_stage_timings(self.h, C.byref(t)))
