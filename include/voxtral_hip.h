@@ -356,6 +356,10 @@ int32_t vox_get_stage_timings(const vox_model* m, vox_timings* out);
 /* The VOX_* measurement knobs (kernel-selection overrides used by tools/ and by the A/B tests) are read from the environment ONCE, at vox_ctx_create;
  * this re-reads them (tests that flip a knob between two calls).  Not part of the reference surface. */
 int32_t vox_debug_reload_knobs(void);
+/* Test hook: attention launches enqueued by this process so far, by kernel form (host-side counts; the replays of a captured graph are not counted):
+ * out[0] short-sequence prefill, [1] MFMA prefill, [2] f32 VALU prefill (VOX_ATTN_F32), [3] single-query decode, [4] its speculative-row form (VOX_ATTN_SPEC),
+ * [5] batched GQA decode, [6] fused attention + wo, [7] single-stream decode-engine launches (the whole step).  Entries past [7] are written as 0. */
+int32_t vox_debug_attn_launches(uint64_t* out, int32_t cap);
 /* Test hook: launch `workgroups` x 1024-thread workgroups that spin for `micros` microseconds on a side stream of the context and return at once (vox_ctx_synchronize does
  * not wait for them; vox_ctx_destroy does).  Used to test the decode engines against a GPU that is not theirs alone (tests/test_gpu_fullsize.py). */
 int32_t vox_debug_occupy(vox_ctx* ctx, int32_t workgroups, int32_t micros);

@@ -642,6 +642,8 @@ void orc_model_free(orc_model* m) {
     free(m->owned); free(m->enc); free(m->dec); orc_gguf_close(m->g); free(m);
 }
 void orc_model_config(const orc_model* m, orc_model_cfg* out) { *out = m->cfg; }
+/* test hook: the decoder's sliding window (default 8192, models/config.rs) -- the suite moves it by one to show that its window-edge probes see an off-by-one */
+void orc_model_set_dec_window(orc_model* m, int window) { m->cfg.dec_window = window; }
 
 int orc_enc_seq_len(const orc_model* m, int T) { (void)m; return orc_conv_out_len(orc_conv_out_len(T)); }
 
@@ -875,6 +877,11 @@ void orc_cache_update(orc_cache* c, int layer, int pos, const float* k, const fl
         memcpy(c->k + dst, k + src, sizeof(float) * c->hd); memcpy(c->v + dst, v + src, sizeof(float) * c->hd);
     }
     if (pos + n > c->len) c->len = pos + n;
+}
+/* vox_cache_truncate: forget every row from `len` on (0 <= len <= seq_len); the next forward appends at `len` again.  0, or -1 (nothing changed) out of range */
+int orc_cache_truncate(orc_cache* c, int len) {
+    if (len < 0 || len > c->len) return -1;
+    c->len = len; return 0;
 }
 
 /* gguf/model.rs:665-677 -> :370-387 -> :125-174, :250-255, :220-224 */

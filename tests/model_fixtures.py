@@ -199,3 +199,83 @@ def component_weight(name):
     shape = COMPONENT_SHAPES[name]
     rng = np.random.default_rng([COMPONENT_SEED, zlib.crc32(name.encode())])
     return ((0.02 if name.endswith(".bias") else 0.03) * rng.standard_normal(shape)).astype(np.float32)
+
+
+# ---- the decoder's sliding window (8192 positions, models/config.rs) past the point where it starts to move
+DEC_WINDOW = 8192
+EDGE_V_SCALE = 100.0       # one such key of ~8193 visible ones moves the tiny model's hidden states and logits by >= 60x the suite's 2e-4 (tests/test_oracle_window_edges.py)
+
+
+def window_edge_rows(positions, window=DEC_WINDOW):
+    """The two keys at the window's edge for every query position p: p - window - 1 (the last key a query at p must NOT see: the oracle masks
+    |p - j| > window) and p - window (the first key it must see) -- those that exist.  A kernel whose window starts one key early or late adds or
+    drops exactly one of them."""
+    rows = set()
+    for p in positions:
+        rows.update(j for j in (p - window - 1, p - window) if j >= 0)
+    return np.array(sorted(rows), dtype=np.int64)
+
+
+def edge_kv(seed, lo, hi, n_kv, hd, edge_rows=(), v_scale=EDGE_V_SCALE, block=256):
+    """K / V rows lo .. hi-1 of a synthetic cache layer, [n_kv][hi - lo][hd] (what vox_cache_update / orc_cache_update take): N(0, 1), drawn per
+    `block` rows from default_rng([*seed, block index]) so that any row range can be (re)written alike on both sides without the rest of the layer
+    (seed: e.g. (base, layer)).  The V rows listed in edge_rows are scaled by v_scale: with ~8193 visible keys one key holds ~1/8193 of the softmax
+    weight, and at N(0, 1) an off-by-one in the window's first key would move the result by less than the tolerance."""
+    seed = tuple(np.atleast_1d(seed).tolist())
+    k = np.empty((n_kv, hi - lo, hd), np.float32); v = np.empty_like(k)
+    for b in range(lo // block, (hi + block - 1) // block):
+        rng = np.random.default_rng(seed + (b,))
+        kb = rng.standard_normal((n_kv, block, hd), dtype=np.float32); vb = rng.standard_normal((n_kv, block, hd), dtype=np.float32)
+        r0, r1 = max(lo, b * block), min(hi, (b + 1) * block)
+        k[:, r0 - lo:r1 - lo] = kb[:, r0 - b * block:r1 - b * block]; v[:, r0 - lo:r1 - lo] = vb[:, r0 - b * block:r1 - b * block]
+    e = np.asarray(edge_rows, dtype=np.int64)
+    e = e[(e >= lo) & (e < hi)] - lo
+    v[:, e] *= np.float32(v_scale)
+    return k, v
+
+
+def fill_edge_caches(caches, n_layers, n_kv, hd, lo, hi, edge_rows, seed=2026, step=2048):
+    """Write rows lo .. hi-1 of every layer of each cache in `caches` (callables (layer, pos, k, v): a vox cache's update, or the oracle's
+    cache_update bound to its cache) with edge_kv data -- in slices of `step` rows, so a 26-layer cache never needs its whole host copy at once."""
+    for l in range(n_layers):
+        for a in range(lo, hi, step):
+            b = min(hi, a + step)
+            k, v = edge_kv((seed, l), a, b, n_kv, hd, edge_rows)
+            for upd in caches:
+                upd(l, a, k, v)
+
+
+def attn_launches(pkg):
+    """Attention launches of this process so far by kernel form (vox_debug_attn_launches)."""
+    import ctypes
+    out = (ctypes.c_uint64 * 8)()
+    assert pkg.lib().vox_debug_attn_launches(out, 8) == 0
+    names = ("prefill_small", "prefill_mfma", "prefill_f32", "decode", "decode_spec", "decode_gqa", "attn_wo", "engine")
+    return dict(zip(names, (int(x) for x in out)))
+
+
+def launches_since(pkg, before):
+    now = attn_launches(pkg)
+    return {k: now[k] - before[k] for k in now if now[k] != before[k]}
+
+
+# vox_attention at hd 128 past the decoder window's first move: (M, kv_len, offset, window); every case runs at GQA 4:1 and 2:1
+EDGE_ATTN_CASES = [
+    (1, 8193, 8192, DEC_WINDOW),         # the last position whose window has not moved
+    (1, 8194, 8193, DEC_WINDOW),         # the first that has: key 0 out, key 1 in
+    (1, 8256, 8255, DEC_WINDOW),         # first visible key 63, the last of a 64-key tile (the MFMA kernel starts at its query block's tile)
+    (70, 8263, 8193, DEC_WINDOW),        # two query blocks, both moved
+    (80, 8230, 8150, DEC_WINDOW),        # a block that straddles the first move (rows 8150 .. 8213), then one that starts past it
+    (38, 16384, 16346, DEC_WINDOW),      # the last rows a decoder cache can hold
+    (200, 200, 0, 20),                   # a small window at hd 128
+    (200, 200, 0, 65),                   # ... whose third block's first visible key is 63
+]
+
+
+def edge_attention_inputs(M, kv, H, KV, off, win, hd=128, seed=0):
+    """q [M][H*hd] (N(0, 1.5^2)), k / v [kv][KV*hd] (edge_kv rows, token-major) for one EDGE_ATTN_CASES case, the V rows at every query's window
+    edge scaled (window_edge_rows)."""
+    rng = np.random.default_rng([seed, M, kv, off])
+    q = (1.5 * rng.standard_normal((M, H * hd))).astype(np.float32)
+    k, v = edge_kv((seed, 1, kv, off), 0, kv, KV, hd, window_edge_rows(range(off, off + M), win))
+    return q, np.ascontiguousarray(k.transpose(1, 0, 2).reshape(kv, KV * hd)), np.ascontiguousarray(v.transpose(1, 0, 2).reshape(kv, KV * hd))

@@ -121,6 +121,8 @@ def lib():
         "orc_cache_free": (None, [vp]),
         "orc_cache_len": (C.c_int, [vp]),
         "orc_cache_reset": (None, [vp]),
+        "orc_cache_truncate": (C.c_int, [vp, C.c_int]),
+        "orc_model_set_dec_window": (None, [vp, C.c_int]),
         "orc_cache_update": (None, [vp, C.c_int, C.c_int, f32p, f32p, C.c_int]),
         "orc_forward_hidden_with_cache": (None, [vp, f32p, C.c_int, f32p, vp, f32p]),
         "orc_lm_head": (None, [vp, f32p, C.c_int, f32p]),
@@ -287,6 +289,16 @@ class Model:
 
     def cache_free(self, c):
         lib().orc_cache_free(c)
+
+    def cache_len(self, c):
+        return lib().orc_cache_len(c)
+
+    def cache_truncate(self, c, n):
+        if lib().orc_cache_truncate(c, n) != 0:
+            raise ValueError(f"truncate to {n}: the cache holds {lib().orc_cache_len(c)} rows")
+
+    def set_dec_window(self, w):
+        lib().orc_model_set_dec_window(self.h, w); self.cfg.dec_window = w
 
     def cache_update(self, c, layer, pos, k, v):
         k = f32(k); v = f32(v)

@@ -8,7 +8,8 @@ import os
 import numpy as np
 import pytest
 
-from model_fixtures import argmax_low, cache_dir, check_batch_rows, check_greedy_ids, dense_head_sha, full_dense_safetensors, parse_batch_verbose, rel_err, teacher_forced_logits, top2_margin
+from model_fixtures import (argmax_low, attn_launches, cache_dir, check_batch_rows, check_greedy_ids, dense_head_sha, fill_edge_caches, full_dense_safetensors, launches_since,
+                            parse_batch_verbose, rel_err, teacher_forced_logits, top2_margin, window_edge_rows)
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-4
@@ -1289,3 +1290,85 @@ def test_full_30s_heavytail_vs_oracle_golden(pkg, orc):
         assert e_enc < TOL and e_dec < 2 * TOL and e_lm < TOL
     finally:
         m.close(); o.close(); ctx.close()
+
+
+# ---- past the decoder's 8192-position sliding window, full size (model_fixtures.window_edge_rows / fill_edge_caches: the V rows at every probe's window edge
+# scaled, written alike into the library's and the oracle's cache).  Caches of more than 1024 rows take the per-operator kernels.
+FULL_EDGE_FORMS = [("attn_wo", {}),                                                   # attn_wo_kernel: attention + wo in one launch (the default)
+                   ("decode", {"VOX_NO_ATTN_WO": "1"}),                               # attn_decode_kernel, then the wo GEMV
+                   ("decode_spec", {"VOX_NO_ATTN_WO": "1", "VOX_ATTN_SPEC": "1"})]    # its speculative-row form
+
+
+def _full_edge_steps(pkg, o, dec, c, oc, t, positions, forms, monkeypatch, worst, n_layers=26, D=3072):
+    """Decode steps at `positions` (consecutive, starting at both caches' length): the oracle once, then every form in `forms` (name, knobs, expected
+    launches per step) from the same length (the library's cache truncated back) -- hidden states and all logits within TOL, equal argmax."""
+    p0 = positions[0]
+    assert c.seq_len() == p0 and o.cache_len(oc) == p0
+    xs = [(0.3 * np.random.default_rng([79, p]).standard_normal((1, D))).astype(np.float32) for p in positions]
+    refs = []
+    for x in xs:
+        rh = o.forward_hidden_with_cache(x, t, oc); refs.append((rh, o.lm_head(rh)))
+    for name, knobs, expect in forms:
+        for k in ("VOX_NO_ATTN_WO", "VOX_ATTN_SPEC"):
+            monkeypatch.delenv(k, raising=False)
+        for k, v in knobs.items():
+            monkeypatch.setenv(k, v)
+        c.truncate(p0)
+        for p, x, (rh, rl) in zip(positions, xs, refs):
+            before = attn_launches(pkg)
+            gh = dec.forward_hidden_with_cache(x[None], t, c)[0]
+            assert launches_since(pkg, before) == expect, (name, p)
+            gl = dec.lm_head(gh[None])[0]
+            eh, el = rel_err(gh, rh), rel_err(gl, rl)
+            assert eh < TOL and el < TOL, (name, p, eh, el)
+            assert int(gl.argmax()) == int(rl.argmax()), (name, p)
+            w = worst.setdefault(name, [0.0, 0.0]); w[0] = max(w[0], eh); w[1] = max(w[1], el)
+    for k in ("VOX_NO_ATTN_WO", "VOX_ATTN_SPEC"):
+        monkeypatch.delenv(k, raising=False)
+
+
+def test_full_decode_past_the_window_edge_vs_oracle(pkg, orc, full, monkeypatch):
+    """Decode steps at positions 8191 .. 8194 (the window's first move at 8193) and at the last rows 16382 / 16383 of a 16384-row cache (attn_wo_kernel's
+    64 KB score buffer) under the three per-operator forms, against the oracle on every logit.  Each step's attention launches are counted: 26 of the
+    form's kernel and nothing else."""
+    m, o, _ = full
+    KV, HD, D, L, N = 8, 128, 3072, 26, 16384
+    t = pkg.TimeEmbedding(D).embed(6.0); dec = m.decoder()
+    runs = [[8191, 8192, 8193, 8194], [16382, 16383]]
+    edges = window_edge_rows([p for r in runs for p in r])
+    forms = [(name, knobs, {name: L}) for name, knobs in FULL_EDGE_FORMS]
+    oc = o.cache(N); c = dec.create_cache_preallocated(N)
+    worst = {}
+    try:
+        filled = 0
+        for run in runs:
+            fill_edge_caches([c.update, lambda l, a, k, v: o.cache_update(oc, l, a, k, v)], L, KV, HD, filled, run[0], edges)
+            filled = run[0]
+            _full_edge_steps(pkg, o, dec, c, oc, t, run, forms, monkeypatch, worst)
+    finally:
+        o.cache_free(oc); c.close()
+    for name, (eh, el) in worst.items():
+        print(f"full size past the window edge, {name}: hidden {eh:.2e}, all 131072 logits {el:.2e} of the largest")
+
+
+@pytest.mark.parametrize("max_seq", [1024, 1025])
+def test_full_decode_at_a_full_engine_score_buffer_vs_oracle(pkg, orc, full, monkeypatch, max_seq):
+    """Decode steps at positions 1022 and 1023: on a 1024-row cache the single-stream engine serves them, the second with its LDS score buffer (SC_MAX =
+    1024 floats) full; on a 1025-row cache the per-operator path does (attn_wo_kernel).  Both against the oracle on every logit; the launches tell the path."""
+    m, o, _ = full
+    KV, HD, D, L = 8, 128, 3072, 26
+    engine = m.set_decode_engine(True)
+    if max_seq == 1024 and not engine:
+        pytest.skip("decode engine not available on this device (needs 256 CUs)")
+    t = pkg.TimeEmbedding(D).embed(6.0); dec = m.decoder()
+    oc = o.cache(max_seq); c = dec.create_cache_preallocated(max_seq)
+    worst = {}
+    try:
+        fill_edge_caches([c.update, lambda l, a, k, v: o.cache_update(oc, l, a, k, v)], L, KV, HD, 0, 1022, ())
+        form = ("engine", {}, {"engine": 1}) if max_seq == 1024 else ("attn_wo", {}, {"attn_wo": L})
+        _full_edge_steps(pkg, o, dec, c, oc, t, [1022, 1023], [form], monkeypatch, worst)
+        assert c.seq_len() == 1024
+    finally:
+        o.cache_free(oc); c.close()
+    for name, (eh, el) in worst.items():
+        print(f"full size at positions 1022 / 1023, max_seq {max_seq}, {name}: hidden {eh:.2e}, all 131072 logits {el:.2e} of the largest")

@@ -10,7 +10,8 @@ Tolerances (stated here, used below):
 import numpy as np
 import pytest
 
-from model_fixtures import argmax_low, check_batch_rows, check_greedy_ids, fake_mel, golden, golden_gguf, parse_batch_verbose, rel_err, teacher_forced_logits, tiny_gguf
+from model_fixtures import (DEC_WINDOW, argmax_low, attn_launches, check_batch_rows, check_greedy_ids, fake_mel, fill_edge_caches, golden, golden_gguf, launches_since,
+                            parse_batch_verbose, rel_err, teacher_forced_logits, tiny_gguf, window_edge_rows)
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-4
@@ -734,3 +735,122 @@ def test_exported_gguf_round_trip_on_device(pkg, orc, ctx, tmp_path, scheme):
             md.close()
     finally:
         m.close(); o.close()
+
+
+# ---- past the decoder's 8192-position sliding window (model_fixtures.window_edge_rows / fill_edge_caches): caches of 16384 rows (the RoPE table's
+# length, the longest a decoder cache may be) take the per-operator kernels, and a realtime stream reaches position 8193 after ~11 minutes of audio
+EDGE_SEQ = 16384
+
+
+def _edge_pair(tiny, probes):
+    m, o, dims = tiny
+    c = m.decoder().create_cache_preallocated(EDGE_SEQ); oc = o.cache(EDGE_SEQ)
+    edges = window_edge_rows(probes)
+    fill = lambda lo, hi: fill_edge_caches([c.update, lambda l, a, k, v: o.cache_update(oc, l, a, k, v)], dims.dec_layers, dims.dec_kv_heads, 128, lo, hi, edges)
+    return c, oc, fill
+
+
+def _edge_check(pkg, dec, o, c, oc, x, t, worst, expect):
+    """forward_hidden_with_cache of rows x at the cache's length on both sides: hidden states and logits within TOL, equal argmax; the attention
+    launches of the call are exactly `expect`."""
+    before = attn_launches(pkg)
+    gh = dec.forward_hidden_with_cache(x[None], t, c)[0]
+    assert launches_since(pkg, before) == expect
+    rh = o.forward_hidden_with_cache(x, t, oc)
+    gl = dec.lm_head(gh[None])[0]; rl = o.lm_head(rh)
+    eh, el = rel_err(gh, rh), rel_err(gl, rl)
+    assert eh < TOL and el < TOL, (c.seq_len(), eh, el)
+    assert (gl.argmax(1) == rl.argmax(1)).all()
+    worst[0] = max(worst[0], eh); worst[1] = max(worst[1], el)
+
+
+@pytest.mark.parametrize("spec", [False, True])
+def test_decode_steps_past_the_window_edge_vs_oracle(pkg, tiny, monkeypatch, spec):
+    """Single-row decode steps (attn_decode_kernel; VOX_ATTN_SPEC=1: its speculative form, which requests rows 0 .. 159 before it knows the position
+    and has to request them again once the window has moved) through positions 8190 .. 8195, then 8353, 12345 and the last rows 16382 / 16383, against
+    the oracle on the same synthetic cache rows.  The V rows at every probe's window edge are scaled: an off-by-one moves the result by >= 60x TOL."""
+    m, o, dims = tiny
+    if spec:
+        monkeypatch.setenv("VOX_ATTN_SPEC", "1")
+    t = pkg.TimeEmbedding(dims.dec_dim).embed(6.0); dec = m.decoder()
+    runs = [list(range(8190, 8196)), [8353], [12345], [16382, 16383]]
+    c, oc, fill = _edge_pair(tiny, [p for r in runs for p in r])
+    worst = [0.0, 0.0]
+    try:
+        filled = 0
+        for run in runs:
+            fill(filled, run[0]); filled = run[0]          # (re)writes the rows the previous run's steps wrote: edge rows keep their data
+            assert c.seq_len() == run[0] and o.cache_len(oc) == run[0]
+            for p in run:
+                x = (0.5 * np.random.default_rng([41, p]).standard_normal((1, dims.dec_dim))).astype(np.float32)
+                _edge_check(pkg, dec, o, c, oc, x, t, worst, {"decode_spec" if spec else "decode": dims.dec_layers})
+        assert c.seq_len() == EDGE_SEQ
+    finally:
+        c.close(); o.cache_free(oc)
+    print(f"decode steps past the window edge (spec={spec}): hidden {worst[0]:.2e}, logits {worst[1]:.2e} of the largest")
+
+
+@pytest.mark.parametrize("form", ["mfma", "f32"])
+def test_appends_past_the_window_edge_vs_oracle(pkg, tiny, monkeypatch, form):
+    """Multi-row appends through forward_hidden_with_cache (the MFMA prefill attention; VOX_ATTN_F32=1: the f32 kernel) where the window moves inside
+    the call: 9 rows at 8188 (rows 8188 .. 8196), 70 rows at 8150 (a 64-row query block that straddles the first move, then one past it) and 70 rows
+    at 8255 (a block whose first visible key, 63, is the last of a 64-key tile)."""
+    m, o, dims = tiny
+    if form == "f32":
+        monkeypatch.setenv("VOX_ATTN_F32", "1")
+    t = pkg.TimeEmbedding(dims.dec_dim).embed(6.0); dec = m.decoder()
+    appends = [(8188, 9), (8150, 70), (8255, 70)]
+    worst = [0.0, 0.0]
+    for off, M in appends:
+        c, oc, fill = _edge_pair(tiny, range(off, off + M))
+        try:
+            fill(0, off)
+            x = (0.5 * np.random.default_rng([43, off, M]).standard_normal((M, dims.dec_dim))).astype(np.float32)
+            _edge_check(pkg, dec, o, c, oc, x, t, worst, {"prefill_mfma" if form == "mfma" else "prefill_f32": dims.dec_layers})
+            assert c.seq_len() == off + M
+        finally:
+            c.close(); o.cache_free(oc)
+    print(f"appends past the window edge ({form}): hidden {worst[0]:.2e}, logits {worst[1]:.2e} of the largest")
+
+
+def test_decoder_cache_range_limits(pkg, tiny):
+    """A decoder cache holds at most 16384 rows (the RoPE table): 16385 is refused; on a full cache a further row is refused with "overflow" by the
+    forward and by vox_cache_update, and the cache's length does not move."""
+    m, _, dims = tiny
+    dec = m.decoder(); t = pkg.TimeEmbedding(dims.dec_dim).embed(6.0)
+    with pytest.raises(pkg.VoxError, match="out of range"):
+        dec.create_cache_preallocated(EDGE_SEQ + 1)
+    c = dec.create_cache_preallocated(EDGE_SEQ)
+    try:
+        k = np.ones((dims.dec_kv_heads, 1, 128), np.float32)
+        for l in range(dims.dec_layers):
+            c.update(l, EDGE_SEQ - 1, k, k)
+        assert c.seq_len() == EDGE_SEQ
+        with pytest.raises(pkg.VoxError, match="overflow"):
+            dec.forward_hidden_with_cache(np.zeros((1, 1, dims.dec_dim), np.float32), t, c)
+        with pytest.raises(pkg.VoxError, match="overflow"):
+            c.update(0, EDGE_SEQ, k, k)
+        assert c.seq_len() == EDGE_SEQ
+    finally:
+        c.close()
+
+
+def test_forward_with_cache_across_the_window_edge_equals_composed_calls(pkg, tiny):
+    """One forward_with_cache chunk whose decoder rows cross position 8192 (a decoder cache filled to 8180, then the 22 rows of a first 352-frame chunk) is
+    bit-identical to encode_audio_with_cache -> forward_hidden_with_cache -> lm_head on twin caches, as test_composite_forwards_equal_composed_calls_and_the_oracle."""
+    m, o, dims = tiny
+    t = pkg.TimeEmbedding(dims.dec_dim).embed(6.0); dec = m.decoder()
+    da, db = dec.create_cache_preallocated(EDGE_SEQ), dec.create_cache_preallocated(EDGE_SEQ)
+    ea, eb = m.create_encoder_cache(), m.create_encoder_cache()
+    try:
+        start = 8180
+        fill_edge_caches([da.update, db.update], dims.dec_layers, dims.dec_kv_heads, 128, 0, start, window_edge_rows(range(start, start + 64)))
+        chunk = np.ascontiguousarray(fake_mel(352, seed=12))
+        lw = m.forward_with_cache(chunk[None], t, ea, da)[0]
+        au = m.encode_audio_with_cache(chunk[None], eb)
+        assert au.shape[1] == lw.shape[0] and start + lw.shape[0] > DEC_WINDOW + 1, lw.shape
+        assert np.array_equal(lw, dec.lm_head(dec.forward_hidden_with_cache(au, t, db))[0])
+        assert da.seq_len() == db.seq_len() == start + lw.shape[0]
+    finally:
+        for cc in (da, db, ea, eb):
+            cc.close()

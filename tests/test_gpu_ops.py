@@ -311,6 +311,32 @@ def test_attention_f32_switch_vs_oracle(pkg, orc, ctx, monkeypatch):
     monkeypatch.delenv("VOX_ATTN_F32")
 
 
+
+@pytest.mark.parametrize("form", ["mfma", "f32"])
+def test_attention_past_the_decoder_window_edge_vs_oracle(pkg, orc, ctx, monkeypatch, form):
+    """vox_attention at hd 128, GQA 4:1 and 2:1, where the decoder's 8192-position window has started to move (model_fixtures.EDGE_ATTN_CASES: one query
+    at 8192 / 8193 / 8255, 70 rows from 8193, 80 rows straddling the first move, 38 rows ending at 16384, small windows).  The V rows of the two keys at
+    every query's window edge (p - window - 1 out, p - window in) are scaled, so a window that starts one key early or late fails by > 100x the bound
+    (tests/test_oracle_window_edges.py).  MFMA kernel and VOX_ATTN_F32=1; tolerance |d| <= 2e-5 * max|ref|, as above."""
+    from importlib import import_module
+    from model_fixtures import EDGE_ATTN_CASES, attn_launches, edge_attention_inputs, launches_since
+    attention = import_module(pkg.__name__ + ".gguf").attention
+    if form == "f32":
+        monkeypatch.setenv("VOX_ATTN_F32", "1")
+    worst = 0.0
+    for (M, kv, off, win) in EDGE_ATTN_CASES:
+        for H, KV in ((4, 1), (4, 2)):
+            q, k, v = edge_attention_inputs(M, kv, H, KV, off, win)
+            ref = np.zeros((M, H * 128), np.float32)
+            orc.lib().orc_attention(q, k, v, M, kv, H, KV, 128, off, 1, win, ref)
+            before = attn_launches(pkg)
+            out = attention(ctx, q, k, v, H, KV, offset=off, window=win)
+            assert launches_since(pkg, before) == {"prefill_mfma" if form == "mfma" else "prefill_f32": 1}
+            err = np.abs(out - ref).max() / np.abs(ref).max()
+            assert err < 2e-5, (M, kv, off, win, H, KV, err)
+            worst = max(worst, err)
+    print(f"attention past the window edge ({form}): worst {worst:.2e} of the largest")
+
 @pytest.mark.parametrize("m,k,n", [(1001, 1280, 6144), (2344, 2048, 1280 + 48), (700, 5120, 10240)])
 def test_q4_gemm_big_kernel_matches_tile_kernel(pkg, orc, ctx, monkeypatch, m, k, n):
     """Large-M MFMA GEMM (64x256 tiles, tile-ordered weights, bit-trick B fragments + -136 correction MFMA) against the 32x128 kernel on

@@ -1016,6 +1016,7 @@ hipError_t launch_decode_engine(const EngParams& p, hipStream_t s) {
         attr_done.set(dev);
     }
     decode_engine_kernel<<<dim3(NCU), dim3(NTHR), L_TOTAL, s>>>(p);
+    attn_form_note(ATTN_FORM_ENGINE);
     return hipGetLastError();
 }
 

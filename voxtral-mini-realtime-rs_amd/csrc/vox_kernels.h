@@ -165,6 +165,11 @@ hipError_t launch_attn_decode(const AttnParams& p, int hd, int max_seq, hipStrea
 // single sequence: attention + the wo linear in one launch; acc[wo.N] (int64, zero on entry) receives the product in 2^-32 fixed point (consumer: PRO_RMS_MUL_SUM)
 bool attn_wo_supported(const AttnParams& p, const Q4W& wo, int hd, int max_seq);
 hipError_t launch_attn_wo(const AttnParams& p, const Q4W& wo, long long* acc, int max_seq, hipStream_t s);
+// host-side launch counts of the attention kernels and of the single-stream decode engine, by form (vox_debug_attn_launches: tests assert which path a call took)
+enum AttnForm { ATTN_FORM_PREFILL_SMALL, ATTN_FORM_PREFILL_MFMA, ATTN_FORM_PREFILL_F32, ATTN_FORM_DECODE, ATTN_FORM_DECODE_SPEC, ATTN_FORM_DECODE_GQA, ATTN_FORM_WO,
+                ATTN_FORM_ENGINE, ATTN_FORM_COUNT };
+void attn_form_note(AttnForm f);
+void attn_form_counts(unsigned long long out[ATTN_FORM_COUNT]);
 
 // gelu(conv1d k3 s2 p1): in [Cin][L] -> out; out_token_major: out[t][co] else out[co][t]
 hipError_t launch_conv1d_gelu(const float* in, int Cin, int L, const float* w, const float* b, int Cout, float* out,

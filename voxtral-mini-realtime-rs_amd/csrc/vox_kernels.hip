@@ -25,6 +25,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -62,6 +63,9 @@ static int tl_take_slot(int type, int epi, int N, int K) {
     return g_tl_next++;
 }
 void tl_slot_meta(int slot, int out[4]) { for (int i = 0; i < 4; i++) out[i] = (slot >= 0 && slot < 4096) ? g_tl_meta[slot][i] : 0; }
+static std::atomic<unsigned long long> g_attn_forms[ATTN_FORM_COUNT];      // launches enqueued by the host (a captured graph's replays are not counted)
+void attn_form_note(AttnForm f) { g_attn_forms[f].fetch_add(1, std::memory_order_relaxed); }
+void attn_form_counts(unsigned long long out[ATTN_FORM_COUNT]) { for (int i = 0; i < ATTN_FORM_COUNT; i++) out[i] = g_attn_forms[i].load(std::memory_order_relaxed); }
 
 // ------------------------------------------------------------------------------------------------
 // device helpers
@@ -3277,6 +3281,7 @@ static hipError_t attn_prefill_mfma_launch(const AttnParams& p, hipStream_t s, i
     hipError_t e = ensure_dyn_lds(kern, lds, &attr_done);
     if (e != hipSuccess) return e;
     kern<<<dim3((p.M + 63) / 64, p.n_heads, n_seq), dim3(256), lds, s>>>(p);
+    attn_form_note(ATTN_FORM_PREFILL_MFMA);
     return hipGetLastError();
 }
 // ---- causal attention of a SHORT sequence from position 0 (<= 48 rows: the 38-token decoder prefill, gguf/model.rs:908-919 -> Q4Attention::forward_with_cache with an
@@ -3350,6 +3355,7 @@ static hipError_t attn_prefill_small_launch(const AttnParams& p, hipStream_t s, 
     hipError_t e = ensure_dyn_lds(kern, lds, &done); if (e != hipSuccess) return e;
     const int rows = p.out_xf_tiles ? ((p.M + 15) / 16) * 16 : p.M;
     kern<<<dim3(p.n_heads, n_seq, (rows + 3) / 4), dim3(256), lds, s>>>(p);
+    attn_form_note(ATTN_FORM_PREFILL_SMALL);
     return hipGetLastError();
 }
 hipError_t launch_attn_prefill(const AttnParams& p, int hd, hipStream_t s, int n_seq) {
@@ -3372,6 +3378,7 @@ hipError_t launch_attn_prefill(const AttnParams& p, int hd, hipStream_t s, int n
         if (e != hipSuccess) return e;
         kern<<<grid, dim3(256), lds, s>>>(p);
     } else return hipErrorInvalidValue;
+    attn_form_note(ATTN_FORM_PREFILL_F32);
     return hipGetLastError();
 }
 
@@ -3784,6 +3791,7 @@ hipError_t launch_attn_wo(const AttnParams& p_in, const Q4W& wo, long long* acc,
     hipError_t e = ensure_dyn_lds(kern, lds, &attr_done);
     if (e != hipSuccess) return e;
     kern<<<dim3(256), dim3(256), lds, s>>>(p, wo, acc);
+    attn_form_note(ATTN_FORM_WO);
     return hipGetLastError();
 }
 
@@ -3796,6 +3804,7 @@ hipError_t launch_attn_decode(const AttnParams& p_in, int hd, int max_seq, hipSt
         hipError_t e = ensure_dyn_lds(kern, 4 * lds, &attr_done);
         if (e != hipSuccess) return e;
         kern<<<dim3(p.n_kv_heads, n_seq), dim3(256), 4 * lds, s>>>(p);
+        attn_form_note(ATTN_FORM_DECODE_GQA);
         return hipGetLastError();
     }
     // Speculative K / V rows (attn_decode_core SPEC) are opt-in (VOX_ATTN_SPEC=1): measured neutral for one sequence (the position word is not the
@@ -3808,15 +3817,18 @@ hipError_t launch_attn_decode(const AttnParams& p_in, int hd, int max_seq, hipSt
         hipError_t e = ensure_dyn_lds(kern, lds, &attr_done);
         if (e != hipSuccess) return e;
         kern<<<dim3(p.n_heads, n_seq), dim3(256), lds, s>>>(p);
+        attn_form_note(ATTN_FORM_DECODE_SPEC);
     } else if (hd == 128) {
         auto kern = attn_decode_kernel<128, false>;
         static DevOnce attr_done;
         hipError_t e = ensure_dyn_lds(kern, lds, &attr_done);
         if (e != hipSuccess) return e;
         kern<<<dim3(p.n_heads, n_seq), dim3(256), lds, s>>>(p);
+        attn_form_note(ATTN_FORM_DECODE);
     } else if (hd == 64) {
         auto kern = attn_decode_kernel<64, false>;
         kern<<<dim3(p.n_heads, n_seq), dim3(256), lds, s>>>(p);
+        attn_form_note(ATTN_FORM_DECODE);
     } else return hipErrorInvalidValue;
     return hipGetLastError();
 }
