@@ -9,12 +9,14 @@ workload = BASELINE.json configs[2] "Single 16 s WAV, Q4_0 GGUF on 1xMI355X").  
 random Q4_0 in the real GGUF layout (no checkpoint is available offline); token count is a pure function
 of audio length (no EOS), so throughput does not depend on weight values.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+A plain run does only what the headline figure needs: it synthesises the weights in host memory, loads them, warms up, times the K steps,
+writes --dump-outputs and prints the result line.  Everything else it can measure (the extras below, the roofline) runs only with --full.
 N > 1: one rank per GPU.  Launched by the driver through torch.distributed.run (RANK / WORLD_SIZE in the environment), or -- when
 WORLD_SIZE is not set -- bench.py re-executes ITSELF through the same launcher (shard.spawn_ranks) after checking that the box has N
 GPUs; it fails loudly otherwise.  Independent utterances per rank ("weak" scaling: every rank transcribes its own clip each step),
 rank 0 parses the GGUF and the packed weight arena reaches the other ranks through ONE RCCL broadcast; no collective in the data path.
-Rank 0 prints ONE JSON line.  Extras in the same line (never `value`):
+Rank 0 prints ONE JSON line.  With --full, extras in the same line (never `value`):
   `batch`       BASELINE configs[3]: 16 clips through vox_transcribe_batch (N = 1)
   `f32`         BASELINE configs[1]: the same clip through the f32 SafeTensors path (dense bf16 weights, N = 1)
   `fleurs_like` BASELINE configs[4] stand-in: 647 clips with FLEURS-like durations sharded LPT over the ranks, each rank's share in ONE vox_transcribe_batch call (continuous batching; --fleurs-batch)
@@ -47,12 +49,60 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
+def synthetic_gguf_image(synth, dims, seed, threads=1, header_only=False):
+    """The bytes synth.write_synthetic_gguf(path, dims, seed) writes, built in host memory by `threads` threads (every tensor has its own
+    generator, so the order of filling does not matter): no file, so a run neither leaves 2.5 GB behind nor reads what an earlier run wrote.
+    `header_only`: the tensor data stays zero (ranks > 0 only lay the arena out and receive the weights by broadcast).
+    tests/test_bench_cpu.py holds it byte for byte against synth.write_synthetic_gguf."""
+    import struct
+    from concurrent.futures import ThreadPoolExecutor
+    man = synth.tensor_manifest(dims)
+    # header and 32-byte aligned tensor offsets exactly as synth.write_gguf lays them out
+    head = bytearray(struct.pack("<IIQQ", 0x46554747, 3, len(man), 1))
+    head += synth._gguf_str("general.architecture") + struct.pack("<I", 8) + synth._gguf_str("voxtral")
+    spans, off = [], 0
+    for name, shape, kind, _ in man:
+        ne = int(np.prod(shape))
+        sz = ne // 32 * 18 if kind == "q4" else ne * 4
+        head += synth._gguf_str(name) + struct.pack("<I", len(shape))
+        for dim in reversed(shape):
+            head += struct.pack("<Q", int(dim))
+        head += struct.pack("<IQ", synth.GGML_Q4_0 if kind == "q4" else synth.GGML_F32, off)
+        spans.append((off, sz))
+        off = (off + sz + 31) // 32 * 32
+    head += b"\0" * ((32 - len(head) % 32) % 32)
+    base = len(head)
+    img = np.zeros(base + spans[-1][0] + spans[-1][1], dtype=np.uint8)
+    img[:base] = np.frombuffer(bytes(head), dtype=np.uint8)
+    if header_only:
+        return img
+
+    def fill(i):
+        # synth.write_synthetic_gguf's generator (no override, no heavy tail, not peaked)
+        name, shape, kind, sigma = man[i]
+        rng = np.random.default_rng([seed, i]); ne = int(np.prod(shape))
+        if kind == "q4":
+            data = synth.synth_q4_blocks(rng, ne, sigma)
+        elif kind == "norm":
+            data = (1.0 + sigma * rng.standard_normal(ne)).astype(np.float32)
+        else:
+            data = (sigma * rng.standard_normal(ne)).astype(np.float32)
+        o, sz = spans[i]
+        img[base + o:base + o + sz] = data.view(np.uint8)
+
+    with ThreadPoolExecutor(max(1, threads)) as ex:
+        list(ex.map(fill, sorted(range(len(man)), key=lambda i: -spans[i][1])))      # largest first: no long tensor left for the end
+    return img
+
+
 def full_gguf_path(pkg, seed, rank, barrier):
+    """The full-size synthetic Q4_0 GGUF as a file, kept in $VOX_BENCH_DIR (default /tmp) for the measurement scripts under tools/ that load it by path.
+    A bench run never calls this: it builds its own copy in memory."""
     path = os.path.join(os.environ.get("VOX_BENCH_DIR", "/tmp"), f"vox_bench_full_q4_seed{seed}.gguf")
     if rank == 0 and not os.path.exists(path):
         t0 = time.time()
         tmp = path + ".tmp"
-        pkg.synth.write_synthetic_gguf(tmp, pkg.synth.ModelDims(), seed=seed)
+        synthetic_gguf_image(pkg.synth, pkg.synth.ModelDims(), seed, threads=min(16, os.cpu_count() or 1)).tofile(tmp)
         os.replace(tmp, path)
         log(f"[bench] wrote synthetic full-size Q4_0 GGUF {path} ({os.path.getsize(path) / 1e9:.2f} GB) in {time.time() - t0:.1f}s")
     barrier()
@@ -287,6 +337,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--seconds", type=float, default=16.0)
     ap.add_argument("--seed", type=int, default=42)
+    ap.add_argument("--full", action="store_true", help="also run everything beyond the headline figure (off by default): the roofline's own GEMV and engine launches, the batch, "
+                    "FLEURS-like corpus, streaming-encoder, piecewise and f32 extras and the CPU baseline; the options below choose among them and act only with --full")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=float(os.environ.get("VOX_CPU_BASELINE_S", "16.0")))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--batch", type=int, default=16, help="also report BASELINE configs[3] (B utterances through vox_transcribe_batch) at N=1; 0 = skip")
@@ -337,7 +389,19 @@ def main():
     pkg = load_package()
     pkg.lib()   # fails loudly if the HIP library is missing
     ctx = pkg.Context(local)
-    path = full_gguf_path(pkg, args.seed, rank, barrier)
+    # the synthetic full-size Q4_0 GGUF, made afresh in host memory by every run (rank > 0: the header alone, its weights come by broadcast)
+    t0 = time.time()
+    img = synthetic_gguf_image(pkg.synth, pkg.synth.ModelDims(), args.seed, threads=min(16, os.cpu_count() or 1), header_only=(rank != 0))
+    synth_s = time.time() - t0
+    log(f"[bench] synthesised the full-size Q4_0 GGUF in memory ({img.size / 1e9:.2f} GB{', header only' if rank != 0 else ''}) in {synth_s:.1f}s")
+    path = None
+    if args.full and world == 1 and not (args.no_piecewise and args.no_cpu_baseline):
+        # the piecewise extra (a process of its own) and the CPU baseline read the model from a file: this run's own copy, removed at exit
+        import atexit, shutil, tempfile
+        gguf_dir = tempfile.mkdtemp(prefix="vox_bench_", dir=os.environ.get("VOX_BENCH_DIR"))
+        atexit.register(shutil.rmtree, gguf_dir, True)
+        path = os.path.join(gguf_dir, f"vox_bench_full_q4_seed{args.seed}.gguf")
+        img.tofile(path)
 
     t0 = time.time()
     # N > 1: rank 0 parses + repacks; the PRIMARY part of the device arena (the Q4 row planes + f32 tensors: 2.5 GB) reaches the other ranks by ONE RCCL broadcast over
@@ -345,7 +409,9 @@ def main():
     import importlib
     shard_mod = importlib.import_module(pkg.__name__ + ".shard")
     bst = {}
-    model = shard_mod.load_replicated(pkg, ctx, path, rank, world, local=local, stats=bst)
+    loader = pkg.Q4ModelLoader.from_bytes(img)
+    model = shard_mod.load_replicated(pkg, ctx, None, rank, world, local=local, loader=loader, stats=bst)
+    loader.reader.close(); del loader, img      # the model holds its own device copy
     bcast_s = float(bst.get("seconds", 0.0)); bcast_bytes = int(bst.get("bytes", 0))
     load_s = time.time() - t0
     cfg = model.config
@@ -395,14 +461,14 @@ def main():
     value = world * steps * n_ids / elapsed
 
     fleurs = None
-    if args.fleurs_clips > 0:
+    if args.full and args.fleurs_clips > 0:
         try:
             fleurs = fleurs_like_extra(pkg, ctx, model, t_embed, rank, world, dist, args.fleurs_clips, max(1, min(4096, args.fleurs_batch)) if args.fleurs_batch > 0 else 4096,
                                        simulate_world=args.simulate_world, bcast_bytes=model.arena()[1])
         except Exception as e:     # an extra never costs the headline line
             fleurs = {"error": str(e)} if rank == 0 else None
     fleurs_cli = None
-    if args.fleurs_clips > 0 and args.cli_chunk_frames > 0:
+    if args.full and args.fleurs_clips > 0 and args.cli_chunk_frames > 0:
         try:      # the same corpus on the reference CLI's semantics (1200-frame chunks as units): the pipeline wer.py / `voxtral-transcribe --batch` run
             fleurs_cli = fleurs_like_extra(pkg, ctx, model, t_embed, rank, world, dist, args.fleurs_clips, 4096, simulate_world=args.simulate_world, bcast_bytes=model.arena()[1],
                                            chunk_frames=args.cli_chunk_frames)
@@ -410,7 +476,7 @@ def main():
             fleurs_cli = {"error": str(e)} if rank == 0 else None
 
     fleurs_s = None
-    if args.fleurs_clips > 0 and args.corpus_sessions > 1:
+    if args.full and args.fleurs_clips > 0 and args.corpus_sessions > 1:
         try:      # the same corpus (un-chunked), every rank's share as `corpus_sessions` concurrent sessions on its GPU (overlap inside a rank's share)
             fleurs_s = fleurs_like_extra(pkg, ctx, model, t_embed, rank, world, dist, args.fleurs_clips, 4096, simulate_world=0, bcast_bytes=model.arena()[1], sessions=args.corpus_sessions)
         except Exception as e:
@@ -434,10 +500,11 @@ def main():
             "decode_tok_per_s_ref_def": round(n_ids / (stage_ms["decode_ms"] / 1e3), 2) if stage_ms["decode_ms"] > 0 else None,
             "stage_ms": {k: round(v, 3) for k, v in stage_ms.items()},
             "per_rank_ms_per_step": [round(v, 3) for v in per_rank_ms],
-            "distributed": dist_info, "load_s": round(load_s, 2), "weight_broadcast_s": round(bcast_s, 3), "weight_broadcast_bytes": bcast_bytes, "weight_bytes": model.weight_bytes(), "device_memory": model.memory(),
+            "distributed": dist_info, "weight_synthesis_s": round(synth_s, 2), "load_s": round(load_s, 2), "weight_broadcast_s": round(bcast_s, 3), "weight_broadcast_bytes": bcast_bytes, "weight_bytes": model.weight_bytes(), "device_memory": model.memory(),
             "note": "value = ids emitted by all ranks / max-over-ranks wall time of the whole pipeline; decode_tok_per_s_ref_def follows "
                     "bin/e2e_bench.rs:236-240 (ids / decode-stage time); vs_baseline divides by the reference's 19.4 tok/s measured on a DGX Spark GB10",
         }
+    if rank == 0 and args.full:      # everything beyond the headline figure
         if fleurs_cli is not None:
             out["fleurs_like_cli"] = fleurs_cli
             if fleurs is not None and "error" not in fleurs and "error" not in fleurs_cli:
