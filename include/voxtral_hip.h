@@ -388,6 +388,12 @@ int32_t vox_debug_timeline_fetch(vox_ctx* ctx, uint64_t* out, size_t cap_words, 
  * zero), rows_per_unit[j] = rows the call produced for unit j -- more than max_rows: the rest were dropped.  VOX_ERR_INVALID: bad arguments, or nothing to fetch. */
 int32_t vox_debug_batch_tap_arm(vox_model* m, const int32_t* units, int32_t n_units, int32_t max_rows);
 int32_t vox_debug_batch_tap_fetch(vox_model* m, float* out, int32_t* rows_per_unit);
+/* One stacked encoder + adapter run (tests): the n <= 128 host log-mels mels[i] ([128][T[i]]) through the encoder stack exactly as the batch drivers run it, layout 0 =
+ * padded (every clip S_pad rows: the lock-step vox_transcribe_batch of <= 16 units), 1 = packed (every clip its own rows: one stack of the continuous batch).  out receives
+ * every clip's adapter rows back to back ([rows_per_clip[i]][dec_dim] each, rows_per_clip[i] = floor(S_enc_i / 4)); cap_rows = rows out can hold.  report[4]: stacked
+ * encoder rows, w2 split-K slices, wo split-K slices (0 = unsplit), q|k|v launches that ran RoPE in the GEMM's epilogue.  VOX_ERR_INVALID on bad arguments. */
+int32_t vox_debug_encode_batch(vox_model* m, int32_t n, const float* const* mels, const int32_t* T, int32_t layout, float* out, int64_t cap_rows,
+                               int32_t* rows_per_clip, int64_t* report);
 
 #ifdef __cplusplus
 }

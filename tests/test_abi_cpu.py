@@ -179,6 +179,26 @@ def test_batch_tap_symbols_and_bad_arguments(pkg):
     assert L.vox_debug_batch_tap_fetch(None, out.ctypes.data, rows) == 1
 
 
+def test_debug_encode_batch_symbol_and_bad_arguments(pkg):
+    """The stacked-encoder hook (vox_debug_encode_batch) is exported and bound, and refuses bad arguments with VOX_ERR_INVALID before it touches a device."""
+    L = pkg.lib()
+    assert hasattr(L, "vox_debug_encode_batch") and "vox_debug_encode_batch" in pkg._lib.SIGNATURES
+    mel = np.zeros((128, 400), np.float32)
+    mels = (C.c_void_p * 2)(mel.ctypes.data, mel.ctypes.data); T = (C.c_int32 * 2)(400, 400)
+    out = np.zeros((64, 8), np.float32); rows = (C.c_int32 * 2)(); rep = (C.c_int64 * 4)()
+    dummy = C.c_void_p(1)      # a model pointer that must never be dereferenced: every case fails on an argument checked before the model is read
+    cases = [((None, 2, mels, T, 1), "null model"), ((dummy, 0, mels, T, 1), "out of range"), ((dummy, -1, mels, T, 1), "out of range"),
+             ((dummy, 129, mels, T, 1), "out of range"), ((dummy, 2, mels, T, 2), "layout"), ((dummy, 2, mels, T, -1), "layout"),
+             ((dummy, 2, None, T, 0), "null argument"), ((dummy, 2, mels, None, 0), "null argument")]
+    for (m, n, ms, ts, layout), msg in cases:
+        assert L.vox_debug_encode_batch(m, n, ms, ts, layout, out.ctypes.data, 64, rows, rep) == 1, (m, n, layout)
+        assert msg in L.vox_last_error().decode(), (n, layout, L.vox_last_error())
+    assert L.vox_debug_encode_batch(dummy, 2, mels, T, 0, None, 64, rows, rep) == 1 and "null argument" in L.vox_last_error().decode()
+    bad_T = (C.c_int32 * 2)(400, 0)
+    assert L.vox_debug_encode_batch(dummy, 2, mels, bad_T, 0, out.ctypes.data, 64, rows, rep) == 1 and "empty mel" in L.vox_last_error().decode()
+    assert L.vox_abi_version() == 1
+
+
 def test_integration_md_sys_block_is_complete_and_current(pkg):
     """INTEGRATION.md section 2 is generated from the header: every declared symbol has its Rust declaration and the block is not stale."""
     import subprocess, sys

@@ -1372,3 +1372,82 @@ def test_full_decode_at_a_full_engine_score_buffer_vs_oracle(pkg, orc, full, mon
         o.cache_free(oc); c.close()
     for name, (eh, el) in worst.items():
         print(f"full size at positions 1022 / 1023, max_seq {max_seq}, {name}: hidden {eh:.2e}, all 131072 logits {el:.2e} of the largest")
+
+
+# ---- the stacked encoder at full size (vox_debug_encode_batch): every form a stack of the batch drivers takes, against the clips encoded one at a time.  Encoder rows
+# of a clip: ~25 per second of audio + 76 + 17 pad tokens (7.44 s), so clips longer than ~22.5 s pass the 750-row window.  The forms switch on the stacked rows Mtot:
+# w2 / wo split-K (4 / 2 slices) while the unsplit w2 grid has < 1024 workgroups (Mtot < ~3264), RoPE in the q|k|v GEMM's epilogue from 1024 of its 64 x 256 workgroups
+# (Mtot > 2688).  The single clip (pinned to the oracle by the 16 s and 30 s goldens) takes split-K and the separate RoPE kernel, so a stack differs from it by
+# summation order only.
+_ENC_STACK_A = [23.5, 25.0, 26.5]                                  # 3 long clips, ~2440 rows: split-K on, fused RoPE off
+_ENC_STACK_B = [30.0, 3.0, 27.0, 10.0, 24.0, 18.0, 6.0, 14.0]      # 3 of 8 past the window, ~4800 rows: fused RoPE on, split-K off
+_ENC_STACK_CASES = {
+    "A_packed": (_ENC_STACK_A, 1, {}, lambda r: r["ksp"] == 4 and r["ksp_wo"] == 2 and r["fused_rope"] == 0),
+    "B_packed": (_ENC_STACK_B, 1, {}, lambda r: r["ksp"] == 0 and r["ksp_wo"] == 0 and r["fused_rope"] == 32),
+    "B_packed_no_rope_fuse": (_ENC_STACK_B, 1, {"VOX_NO_ROPE_FUSE": "1"}, lambda r: r["ksp"] == 0 and r["fused_rope"] == 0),
+    "B_packed_splitk4": (_ENC_STACK_B, 1, {"VOX_ENC_SPLITK": "4"}, lambda r: r["ksp"] == 4 and r["ksp_wo"] == 2 and r["fused_rope"] == 32),
+    "B_padded": (_ENC_STACK_B, 0, {}, lambda r: r["ksp"] == 0 and r["ksp_wo"] == 0 and r["fused_rope"] == 32),
+}
+ENC_STACK_TOL = 1e-4      # measured <= 2.9e-5 (B; A bit-identical); a window one key off moves rows >= 750 by >= 5.9e-3, RoPE positions restarting 4 rows late by 0.27
+
+
+@pytest.fixture(scope="module")
+def enc_singles():
+    return {}
+
+
+@pytest.mark.parametrize("case", list(_ENC_STACK_CASES))
+def test_full_encode_stack_forms_vs_single_clips(pkg, full, case, monkeypatch, enc_singles):
+    """Full-size encoder stacks (vox_debug_encode_batch) in every form the batch drivers take -- split-K on a small stack of long clips, fused RoPE without split-K on a large
+    ragged one, fused RoPE forced off, split-K forced on, the padded layout -- the form report proving which ran; every clip's adapter rows against the same clip encoded
+    alone, rows below and from encoder row 750 (the window) reported apart."""
+    m, _, ctx = full
+    secs, layout, env, form_ok = _ENC_STACK_CASES[case]
+    mels = []
+    for i, s in enumerate(secs):
+        key = (s, 5300 + i)
+        if key not in enc_singles:
+            mel = _mel_of(pkg, ctx, s, seed=key[1])[0]
+            enc_singles[key] = (mel, m.encode_audio(mel[None])[0])
+        mels.append(enc_singles[key])
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    try:
+        outs, rep = m.debug_encode_batch([mel for mel, _ in mels], layout)
+    finally:
+        for k in env:
+            monkeypatch.delenv(k)
+    assert form_ok(rep), f"{case}: the stack did not take the form it is here for: {rep}"
+    assert sum(s > 22.5 for s in secs) >= 3
+    worst_lo = worst_hi = 0.0
+    for s, (mel, single), out in zip(secs, mels, outs):
+        assert out.shape == single.shape and out.shape[0] > 0, (s, out.shape, single.shape)
+        amax = float(np.abs(single).max()); d = np.abs(out.astype(np.float64) - single).max(axis=1) / amax
+        lo, hi = float(d[:187].max()), float(d[187:].max()) if d.shape[0] > 187 else 0.0      # adapter row 187 = encoder rows 748 .. 751
+        worst_lo = max(worst_lo, lo); worst_hi = max(worst_hi, hi)
+        assert max(lo, hi) <= ENC_STACK_TOL, f"{case}, {s} s clip: max|stack - single| = {lo:.3e} (rows < 750) / {hi:.3e} (rows >= 748) of max|single|"
+    print(f"encoder stack, full size, {case}: form {rep}, worst rel err vs single clips {worst_lo:.2e} (encoder rows < 748), {worst_hi:.2e} (rows >= 748)")
+
+
+def test_full_batch_logits_long_clips_past_the_encoder_window_vs_teacher_forced(pkg, full, capfd, monkeypatch, full_tf_cache):
+    """20 clips of 3 .. 30 s, six of them longer than 22.5 s (past the encoder's 750-row window), through one continuous batch call with VOX_BATCH_CHUNK=8: three packed
+    encoder stacks, the next one's front-end under the current encoder.  Every long unit and one unit of every stack tapped: each row's argmax is its id and each row is
+    within TOL * max|ref| of the teacher-forced logits of the single-clip path (vox_forward_streaming)."""
+    m, _, ctx = full
+    t = pkg.TimeEmbedding(3072).embed(6.0)
+    secs = [3.0 + 27.0 * ((11 * i) % 20) / 19.0 for i in range(20)]
+    clips = [pkg.synth.synth_audio(s, seed=5600 + i) for i, s in enumerate(secs)]
+    long_units = [i for i, s in enumerate(secs) if s > 22.5]
+    assert len(long_units) >= 4
+    units = sorted(set(long_units) | {0, 8, 17})      # (one unit of each stack besides the long ones)
+    outs, taps, v = _tapped_call(m, clips, t, {"VOX_BATCH_CHUNK": "8"}, monkeypatch, capfd, lambda v: units)
+    assert v["slots"], f"not a continuous batch: {v}"
+    worst = 0.0
+    for u, tp in taps.items():
+        ids = outs[u]
+        assert tp.shape == (len(ids), 131072) and np.array_equal(argmax_low(tp), ids), f"unit {u}: the tapped rows are not those the ids were taken from"
+        ref = teacher_forced_logits(pkg, ctx, m, clips[u], t, ids)
+        e = rel_err(tp, ref); worst = max(worst, e)
+        assert e <= TOL, f"unit {u} ({secs[u]:.1f} s): max|tap - teacher forced| = {e:.3e} of max|ref|"
+    print(f"batch logits, full size, long clips, 3 stacks of <= 8: {len(taps)} units ({len(long_units)} past the window) / {sum(len(x) for x in taps.values())} rows tapped, "
+          f"worst rel err {worst:.2e} vs teacher-forced GPU; verbose {v['forms']}")

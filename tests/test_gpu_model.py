@@ -854,3 +854,113 @@ def test_forward_with_cache_across_the_window_edge_equals_composed_calls(pkg, ti
     finally:
         for cc in (da, db, ea, eb):
             cc.close()
+
+
+# ---- the stacked encoder (vox_debug_encode_batch: one stack exactly as the batch drivers run it) around its 750-row sliding window and the layout edges.  Encoder rows
+# of a T-frame log-mel: ceil(ceil(T / 2) / 2).  Below 6337 stacked rows (where the w1|w3 GEMM, N = 512, would take the large-M kernel: 2 x ceil(M / 64) >= 200
+# workgroups) every row of a stack runs the per-row kernels of a single clip, so a clip's rows in the stack must be BIT-IDENTICAL to the clip encoded alone -- the bar that
+# sees a RoPE position shifted by the same amount on every row of a clip (relative positions unchanged: float rounding only).  Where the kernels differ by summation
+# order -- a clip alone with <= 48 adapter rows (< 196 encoder rows) runs its adapter GEMMs in the skinny kernels; the 17-clip padded stack (17000 rows) its w1|w3 in the
+# large-M kernel -- the clip is held to ORDER_TOL instead (measured <= 7.2e-6 of max|single|).
+ORDER_TOL = 2e-5
+_STACK_T = {"w750": 3000, "w751": 3004, "r850": 3400, "r1000": 4000,      # exactly the window, one past it, past it, far past it
+            "short": 401, "odd": 1146, "none": 9}                          # 101 rows (< 160: padded up), 287 rows (not a multiple of 4), 3 rows (no adapter row at all)
+_STACKS = {
+    "n2_long_first": ["r1000", "short"],
+    "n5_long_between": ["short", "w751", "none", "w750", "odd"],
+    "n17_long_last": ["none", "short", "odd", "w750", "short", "odd", "short", "none", "w751", "short", "odd", "short", "r1000", "short", "none", "odd", "r850"],
+}
+_ENC_REFS = {}
+
+
+def _stack_mels(kinds):
+    """One fake log-mel per stack member; the j-th occurrence of a kind is the same array in every stack (its references are computed once)."""
+    seen = {}; out = []
+    for k in kinds:
+        j = seen[k] = seen.get(k, -1) + 1
+        out.append(((k, j), fake_mel(_STACK_T[k], seed=7000 + 31 * j + _STACK_T[k])))
+    return out
+
+
+def _enc_rows(T):
+    return -(-(-(-T // 2)) // 2)
+
+
+@pytest.mark.parametrize("layout", ["padded", "packed"])
+@pytest.mark.parametrize("stack", list(_STACKS))
+def test_encode_stack_vs_oracle_and_single_clip(pkg, tiny, stack, layout):
+    """A stack of clips of mixed lengths around the encoder's 750-row window (vox_debug_encode_batch, layout 0 = the lock-step driver's padded rows, 1 = the continuous
+    driver's packed rows): every clip's adapter rows within TOL of the CPU oracle and bit-identical to the clip through vox_encode_audio alone (ORDER_TOL where the two run
+    different kernels); the stack's rows are those the layout gives (padded: n x the longest rounded up to 4; packed: every clip max(rows rounded up to 4, 160)); its
+    attention is one stacked prefill_mfma launch per layer."""
+    m, o, dims = tiny
+    kinds = _STACKS[stack]; mels = _stack_mels(kinds)
+    Ts = [mel.shape[1] for _, mel in mels]; rows = [_enc_rows(T) for T in Ts]
+    before = attn_launches(pkg)
+    outs, rep = m.debug_encode_batch([mel for _, mel in mels], 0 if layout == "padded" else 1)
+    ran = launches_since(pkg, before)
+    assert ran == {"prefill_mfma": dims.enc_layers}, ran
+    mtot = len(kinds) * -(-max(rows) // 4) * 4 if layout == "padded" else sum(max(-(-r // 4) * 4, 160) for r in rows)
+    assert rep == {"Mtot": mtot, "ksp": 0, "ksp_wo": 0, "fused_rope": 0}, rep
+    worst_o = worst_s = 0.0
+    big = 2 * -(-mtot // 64) >= 200
+    for (key, mel), T, out in zip(mels, Ts, outs):
+        if key not in _ENC_REFS:
+            _ENC_REFS[key] = (o.encode_audio(mel), m.encode_audio(mel[None])[0])
+        ref, single = _ENC_REFS[key]
+        assert out.shape == ref.shape == single.shape == (_enc_rows(T) // 4, 256), (key, out.shape, ref.shape, single.shape)
+        if not ref.shape[0]:
+            continue
+        e = rel_err(out, ref); worst_o = max(worst_o, e)
+        assert e < TOL, f"{stack}, {layout}, clip {key} (T {T}): {e:.3e} of max|oracle|"
+        d = rel_err(out, single)
+        if single.shape[0] <= 48 or big:
+            worst_s = max(worst_s, d)
+            assert d <= ORDER_TOL, f"{stack}, {layout}, clip {key} (T {T}): max|stacked - single| = {d:.3e} of max|single|"
+        elif not np.array_equal(out, single):
+            bad = np.nonzero(np.abs(out - single).max(axis=1))[0]
+            raise AssertionError(f"{stack}, {layout}, clip {key} (T {T}): stacked rows differ from the clip alone at adapter rows {bad[:8]}... "
+                                 f"({len(bad)} of {out.shape[0]}; encoder rows {4 * bad[0]}..), max {d:.3e} of max|single|")
+    print(f"encoder stack, tiny, {stack} {layout}: Mtot {rep['Mtot']}, worst rel err {worst_o:.2e} vs oracle; stacked == single clip bit for bit "
+          f"where the kernels are the same, worst rel err {worst_s:.2e} where they differ")
+
+
+@pytest.mark.parametrize("form", ["continuous_g2", "continuous_g2_chunk8", "lockstep_n20"])
+def test_batch_logits_long_clips_past_the_encoder_window_vs_teacher_forced(pkg, orc, ctx, tiny, form, capfd, monkeypatch, tf_cache):
+    """Clips longer than 22.5 s (padded past 3000 frames: past the encoder's 750-row window) among short ones, through a whole batch call at LOGIT precision: packed encoder
+    stacks (continuous_g2; with VOX_BATCH_CHUNK=8 three stacks, the next one's front-end under the current encoder) and one padded stack (lockstep_n20).  Every unit is tapped:
+    each row's argmax is its id and each row is within TOL * max|ref| of the teacher-forced logits of the single-clip path; the longest unit also against the CPU oracle."""
+    m, o, _ = tiny
+    t = pkg.TimeEmbedding(256).embed(6.0)
+    base = "continuous_g2" if form.startswith("continuous_g2") else form
+    _, env, ran = _TINY_FORMS[base]
+    env = dict(env, **({"VOX_BATCH_CHUNK": "8"} if form.endswith("chunk8") else {}))
+    secs = [0.4 + 0.23 * ((7 * i) % 19) for i in range(20)]
+    for i, s in zip((0, 7, 12, 19), (29.5, 23.0, 26.0, 24.5)):      # first, between short ones, the last of the call
+        secs[i] = s
+    clips = [pkg.synth.synth_audio(s, seed=4700 + i) for i, s in enumerate(secs)]
+    monkeypatch.setenv("VOX_BATCH_NO_CALIB", "1"); monkeypatch.setenv("VOX_BATCH_VERBOSE", "1")
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    capfd.readouterr()
+    outs, taps = m.transcribe_batch(clips, t, tap_units=list(range(len(clips))))
+    v = parse_batch_verbose(capfd.readouterr().err)
+    for k in env:
+        monkeypatch.delenv(k)
+    assert ran(v), f"{form}: the form did not run: {v}"
+    worst = 0.0
+    for u, (ids, tp) in enumerate(zip(outs, taps)):
+        assert tp.shape == (len(ids), 512) and np.array_equal(argmax_low(tp), ids), f"{form}, unit {u}: the tapped rows are not those the ids were taken from"
+        key = ("gpu", "long", u, ids.tobytes())
+        if key not in tf_cache:
+            tf_cache[key] = teacher_forced_logits(pkg, ctx, m, clips[u], t, ids)
+        e = rel_err(tp, tf_cache[key]); worst = max(worst, e)
+        assert e <= TOL, f"{form}, unit {u} ({secs[u]:.1f} s): max|tap - teacher forced| = {e:.3e} of max|ref|"
+    u = int(np.argmax(secs))
+    key = ("oracle", "long", u, outs[u].tobytes())
+    if key not in tf_cache:
+        tf_cache[key] = teacher_forced_logits(pkg, ctx, m, clips[u], t, outs[u], oracle=o)
+    e_o = rel_err(taps[u], tf_cache[key])
+    assert e_o <= TOL, f"{form}, unit {u} ({secs[u]:.1f} s): max|tap - oracle teacher forced| = {e_o:.3e} of max|ref|"
+    print(f"batch logits, tiny, long clips, {form}: {len(clips)} units / {sum(len(x) for x in outs)} rows tapped, worst rel err {worst:.2e} vs teacher-forced GPU, "
+          f"{e_o:.2e} vs oracle (unit {u}, {secs[u]:.1f} s); verbose {v['lockstep'] or v['forms']}")

@@ -146,6 +146,7 @@ SIGNATURES = {
     "vox_debug_timeline_fetch": (i32, [vp, vp, sz, P(i32), vp]),
     "vox_debug_batch_tap_arm": (i32, [vp, P(i32), i32, i32]),
     "vox_debug_batch_tap_fetch": (i32, [vp, vp, P(i32)]),
+    "vox_debug_encode_batch": (i32, [vp, i32, P(vp), P(i32), i32, vp, C.c_int64, P(i32), P(C.c_int64)]),
 }
 
 _LIB = None

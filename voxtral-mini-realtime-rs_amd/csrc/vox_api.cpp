@@ -1415,7 +1415,10 @@ static int32_t conv_stem_dev(vox_model* m, const float* d_mel, int T, float* c1,
 // 401 ms padded, profiles/r05_continuous_sweep.txt).
 static int enc_packed_rows_of(const vox_model* m, int T) { const int R = m->cfg.reshape_factor; return std::max((enc_rows(T) + R - 1) / R * R, R * 40); }
 static long enc_packed_rows(const vox_model* m, const int* T, int n) { long r = 0; for (int i = 0; i < n; i++) r += enc_packed_rows_of(m, T[i]); return r; }
-static int32_t encode_batch_dev(vox_model* m, int n, const float* const* d_mels, const int* T, float* audio_out, int audio_rows, int* S4_out, long* audio_off_out = nullptr) {
+// which forms a stack took (vox_debug_encode_batch): stacked rows, w2 / wo split-K slice counts (0 = unsplit), q|k|v launches with RoPE in the GEMM's epilogue
+struct EncForms { long Mtot = 0; int ksp = 0, ksp_wo = 0, fused_rope = 0; };
+static int32_t encode_batch_dev(vox_model* m, int n, const float* const* d_mels, const int* T, float* audio_out, int audio_rows, int* S4_out, long* audio_off_out = nullptr,
+                                EncForms* forms = nullptr) {
     const vox_model_cfg& c = m->cfg; vox_ctx* cx = m->ctx; hipStream_t s = cx->stream;
     const int D = c.enc_dim, H = c.enc_heads, hd = c.enc_head_dim, QD = H * hd, F = c.enc_ffn, R = c.reshape_factor;
     const bool packed = audio_off_out != nullptr;
@@ -1449,6 +1452,7 @@ static int32_t encode_batch_dev(vox_model* m, int n, const float* const* d_mels,
     for (int l = 0; ksp_wo && l < c.enc_layers; l++) if (m->enc[l].wo.w.fmt != WFMT_Q4_0 || !m->enc[l].wo.w.qt || m->enc[l].wo.w.nb / 4 < ksp_wo || m->enc[l].wo.w.nb % 4) ksp_wo = 0;
     const size_t need = c1_floats + (size_t)Mtot * D * 2 + (size_t)Mtot * QD * 4 + (size_t)Mtot * F + (size_t)(M4 + 1) * m->ad0.w.N + (size_t)ksp * Mtot * D + 1024;
     VOXCHK(ensure(&m->ws, &m->ws_floats, need));
+    if (forms) { forms->Mtot = Mtot; forms->ksp = ksp; forms->ksp_wo = ksp_wo; forms->fused_rope = 0; }
     float* c1 = m->ws; float* x = c1 + c1_floats / 64 * 64; float* xn = x + (size_t)Mtot * D; float* qkv = xn + (size_t)Mtot * D;
     float* att = qkv + (size_t)Mtot * QD * 3; float* ffn = att + (size_t)Mtot * QD; float* ah = ffn + (size_t)Mtot * F; float* w2p = ah + (size_t)(M4 + 1) * m->ad0.w.N;
     const int* d_len = nullptr; const int* d_roff = nullptr; const int* d_rpos = nullptr;
@@ -1482,7 +1486,8 @@ static int32_t encode_batch_dev(vox_model* m, int n, const float* const* d_mels,
         if (Mtot > 48) {      // q|k|v with RoPE on the q and k columns: in the large-M GEMM's epilogue where that kernel runs, else store + rope_kernel (launch_q4_gemm, EPI_ROPE_ROWS)
             GemmParams g{}; g.w = L.wqkv.w; g.x = xn; g.x_stride = D; g.M = Mtot; g.out = qkv; g.out_stride = 3 * QD; g.bias = L.wqkv.bias;
             g.rope_cos = m->enc_cos; g.rope_sin = m->enc_sin; g.hd = hd; g.n_q = 2 * QD; g.pos = d_rpos; g.rope_seq_rows = seq_rows;
-            HIPCHK(launch_q4_gemm(g, EPI_ROPE_ROWS, s));
+            bool fused = false; HIPCHK(launch_q4_gemm(g, EPI_ROPE_ROWS, s, &fused));
+            if (forms && fused) forms->fused_rope++;
         } else {
             VOXCHK(q4_linear_dev(cx, L.wqkv.w, L.wqkv.bias, xn, D, Mtot, qkv, 3 * QD));
             HIPCHK(launch_rope(qkv, Mtot, 3 * QD, 2 * QD, hd, 0, m->enc_cos, m->enc_sin, s, seq_rows, d_rpos));
@@ -3609,5 +3614,43 @@ extern "C" int32_t vox_debug_batch_tap_fetch(vox_model* m, float* out, int32_t* 
     const hipError_t e2 = hipMemcpy(rows_per_unit, m->tap.rows, nu * 4, hipMemcpyDeviceToHost);
     tap_release(m);
     if (e1 != hipSuccess || e2 != hipSuccess) return fail(VOX_ERR_HIP, "batch tap copy failed");
+    return VOX_OK;
+}
+
+// ---- debug: one encoder stack exactly as a batch driver runs it (encode_batch_dev), the adapter rows of every clip copied back with the forms the stack took
+extern "C" int32_t vox_debug_encode_batch(vox_model* m, int32_t n, const float* const* mels, const int32_t* T, int32_t layout, float* out, int64_t cap_rows,
+                                          int32_t* rows_per_clip, int64_t* report) {
+    ARGCHK(m, "null model");
+    ARGCHK(n > 0 && n <= 128, "encoder stack of %d clips out of range (1..128)", n);
+    ARGCHK(layout == 0 || layout == 1, "layout %d: 0 padded, 1 packed", layout);
+    ARGCHK(mels && T && out && rows_per_clip && report, "null argument");
+    for (int i = 0; i < n; i++) ARGCHK(mels[i] && T[i] > 0, "clip %d: empty mel", i);
+    const vox_model_cfg& c = m->cfg; const int R = c.reshape_factor, D = c.dec_dim, PREFIX_LEN = 38;
+    const std::vector<int> Ti(T, T + n);
+    long need_rows = 0; for (int i = 0; i < n; i++) need_rows += enc_rows(Ti[i]) / R;
+    ARGCHK(cap_rows >= need_rows, "output capacity %lld rows < %ld", (long long)cap_rows, need_rows);
+    VOXCHK(ctx_bind(m->ctx)); hipStream_t s = m->ctx->stream;
+    size_t mel_floats = 0; for (int i = 0; i < n; i++) mel_floats += (size_t)c.n_mels * Ti[i];
+    // the audio buffer as the drivers size it: padded = n budgets of audio_rows rows (transcribe_batch_impl), packed = every clip's packed rows / R back to back
+    int audio_rows = 0; size_t audio_floats = 0; std::vector<long> off(n, 0);
+    if (layout == 0) { audio_rows = std::max(enc_row_budget(m, Ti.data(), n) / R, PREFIX_LEN + 1); audio_floats = (size_t)n * audio_rows * D; for (int i = 0; i < n; i++) off[i] = (long)i * audio_rows * D; }
+    else audio_floats = (size_t)(enc_packed_rows(m, Ti.data(), n) / R) * D;
+    DevBuf b_mel, b_audio;
+    HIPCHK(b_mel.alloc(mel_floats * 4)); HIPCHK(b_audio.alloc(audio_floats * 4));
+    HIPCHK(hipMemsetAsync(b_audio.p, 0, audio_floats * 4, s));
+    std::vector<const float*> d_mels(n); size_t mo = 0;
+    for (int i = 0; i < n; i++) {
+        float* d = b_mel.as<float>() + mo; mo += (size_t)c.n_mels * Ti[i];
+        HIPCHK(hipMemcpyAsync(d, mels[i], (size_t)c.n_mels * Ti[i] * 4, hipMemcpyHostToDevice, s)); d_mels[i] = d;
+    }
+    std::vector<int> S4(n, 0); EncForms f;
+    VOXCHK(encode_batch_dev(m, n, d_mels.data(), Ti.data(), b_audio.as<float>(), audio_rows, S4.data(), layout == 1 ? off.data() : nullptr, &f));
+    HIPCHK(hipStreamSynchronize(s));
+    size_t o = 0;
+    for (int i = 0; i < n; i++) {
+        if (S4[i] > 0) HIPCHK(hipMemcpy(out + o, b_audio.as<float>() + off[i], (size_t)S4[i] * D * 4, hipMemcpyDeviceToHost));
+        o += (size_t)S4[i] * D; rows_per_clip[i] = S4[i];
+    }
+    report[0] = f.Mtot; report[1] = f.ksp; report[2] = f.ksp_wo; report[3] = f.fused_rope;
     return VOX_OK;
 }

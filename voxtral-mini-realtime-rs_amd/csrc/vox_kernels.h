@@ -102,7 +102,7 @@ bool q4_wide_plan(const Q4W& w, int mt, int epi, WidePlan* pl);
 size_t q4_wide_planes_bytes(const Q4W& w, int mt, const WidePlan& pl);
 hipError_t launch_q4_wide(const GemmParams& p, int epi, hipStream_t s);      // p.xf (+ xf_gstride), p.wide_mt, p.kz_scratch (planes); epilogue fields as launch_q4_gemm's XF step
 hipError_t launch_q4_tile_build(Q4W w, uint4* qt, uint16_t* st, hipStream_t s);
-hipError_t launch_q4_gemm(const GemmParams& p, int epi, hipStream_t s);
+hipError_t launch_q4_gemm(const GemmParams& p, int epi, hipStream_t s, bool* fused_rope = nullptr);      // EPI_ROPE_ROWS: *fused_rope (if given) = the RoPE ran in the GEMM's epilogue
 // dense f32-class GEMM on two bf16 weight planes (w.fmt == WFMT_BF16X2; the conv stem as an im2col GEMM); epi: EPI_STORE / EPI_GELU
 hipError_t launch_dense2_gemm(const GemmParams& p, int epi, hipStream_t s);
 hipError_t launch_transpose(const float* in, int R, int C, float* out, hipStream_t s);   // [R][C] -> [C][R]

@@ -2765,12 +2765,14 @@ static hipError_t gemm_launch_f(const GemmParams& p, int epi, hipStream_t s) {
 }
 hipError_t launch_rope(float* buf, int M, int stride, int n_rot, int hd, int pos_off, const float* cos_t, const float* sin_t, hipStream_t s, int seq_rows, const int* row_pos);
 static hipError_t launch_q4_gemm_epi(const GemmParams& p, int epi, hipStream_t s, bool* fused_rope);
-hipError_t launch_q4_gemm(const GemmParams& p, int epi, hipStream_t s) {
+hipError_t launch_q4_gemm(const GemmParams& p, int epi, hipStream_t s, bool* fused_rope) {
+    if (fused_rope) *fused_rope = false;
     if (epi != EPI_ROPE_ROWS) return launch_q4_gemm_epi(p, epi, s, nullptr);
     // the encoder's q|k|v: RoPE in the large-M kernel's epilogue (one launch and one pass over the rows less per layer); every other kernel stores and rope_kernel follows
     if (!p.rope_cos || !p.rope_sin || p.hd <= 0 || p.n_q <= 0 || p.n_q > p.w.N || p.n_q % 2) return hipErrorInvalidValue;
     bool fused = false;
     hipError_t e = launch_q4_gemm_epi(p, EPI_ROPE_ROWS, s, &fused);
+    if (fused_rope) *fused_rope = fused;
     if (e != hipSuccess || fused) return e;
     return launch_rope(p.out, p.M, p.out_stride, p.n_q, p.hd, 0, p.rope_cos, p.rope_sin, s, p.rope_seq_rows, p.pos);
 }

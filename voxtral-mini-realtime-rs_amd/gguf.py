@@ -479,6 +479,21 @@ class Q4VoxtralModel:
         check(lib().vox_encode_audio(self.h, _ptr(mel), T, _ptr(out), cap, C.byref(S), 0))
         return out[:S.value].reshape(1, S.value, self.config.dec_dim).copy()
 
+    def debug_encode_batch(self, mels, layout):
+        """vox_debug_encode_batch: log-mels [128,T_i] as ONE encoder stack, the way the batch drivers run it (layout 0 padded = lock-step, 1 packed = continuous)
+        -> (list of [S4_i, dec_dim] adapter rows, form report {Mtot, ksp, ksp_wo, fused_rope})"""
+        arrs = [_f32(x) for x in mels]; arrs = [np.ascontiguousarray(a.reshape(a.shape[-2], a.shape[-1])) for a in arrs]; n = len(arrs)
+        Ts = [a.shape[1] for a in arrs]
+        cap = sum(T // 16 + 2 for T in Ts)
+        D = self.config.dec_dim
+        out = np.zeros((cap, D), dtype=np.float32); rows = (C.c_int32 * max(n, 1))(); rep = (C.c_int64 * 4)()
+        ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in arrs])
+        check(lib().vox_debug_encode_batch(self.h, n, ptrs, (C.c_int32 * max(n, 1))(*Ts), layout, _ptr(out), cap, rows, rep))
+        res, o = [], 0
+        for i in range(n):
+            res.append(out[o:o + rows[i]].copy()); o += rows[i]
+        return res, {"Mtot": rep[0], "ksp": rep[1], "ksp_wo": rep[2], "fused_rope": rep[3]}
+
     def create_encoder_cache(self, capacity_rows=0):
         return EncoderCaches(self, capacity_rows)
 
