@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-operator timing of the wide decode step (vox_bench_wide): GEMM launch, finishing launch, both, and the same operator as `mt` 16-row skinny launches.
-    python tools/wide_bench.py [mt=4] [iters=104]        (VOX_WIDE_FORCE="N:ntw:kz" tries another plan for one weight shape)"""
+    python tools/wide_bench.py [mt=4] [iters=104]"""
 import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))

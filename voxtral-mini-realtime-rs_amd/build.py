@@ -7,7 +7,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
-LIB_PATH = os.environ.get("VOX_LIB") or os.path.join(PKG_DIR, "libvoxtral_hip.so")   # VOX_LIB: measurement builds (ablations)
+LIB_PATH = os.environ.get("VOX_LIB") or os.path.join(PKG_DIR, "libvoxtral_hip.so")   # VOX_LIB: a measurement build (variant_lib_path)
 SOURCES = ["vox_kernels.hip", "vox_engine.hip", "vox_engine_b16.hip", "vox_api.cpp"]
 HEADERS = ["vox_kernels.h", "vox_engine_common.h", os.path.join("..", "..", "include", "voxtral_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -52,17 +52,7 @@ def build_all(verbose: bool = False, force: bool = False, tag: str | None = None
     return lib_path
 
 
-VARIANTS = {"timeline": ["-DVOX_TIMELINE"],      # measurement builds (tools/timeline.py)
-            "pk_as_compiled": ["-DVOX_PK_AS_COMPILED"],      # rope / dense GEMV / split-K norm / batched engine with hipcc's own packed-FP32 forms (the MI355X hazard's encodings): A/B of what avoiding them costs
-            "gemm_oldstage": ["-DVOX_GEMM_OLD_STAGING"],
-            # q4_gemm_big_kernel, round-5 A/Bs (tools/gemm_big_ab.py, profiles/r05_gemm_big_slots.txt): the round-4 loop nest (one chain in flight, packed scale FMAs, single A-plane
-            # buffer), the single-buffer form of the product loop, the hand-ordered slot form, and its timing-only ablations (wrong results)
-            "big_serial": ["-DVOX_GEMM_BIG_SERIAL", "-DVOX_GEMM_BIG_PKFMA", "-DVOX_GEMM_BIG_SBUF"], "big_sbuf": ["-DVOX_GEMM_BIG_SBUF"], "big_slots": ["-DVOX_GEMM_BIG_SLOTS"],
-            "big_slots_nomfma": ["-DVOX_GEMM_BIG_SLOTS", "-DVOX_ABL_S_NOMFMA"], "big_slots_nofma": ["-DVOX_GEMM_BIG_SLOTS", "-DVOX_ABL_S_NOFMA"], "big_slots_nods": ["-DVOX_GEMM_BIG_SLOTS", "-DVOX_ABL_S_NODS"],      # q4_gemm_kernel with the pre-round-5 LDS staging map (16-way bank conflicts on the writes): same-box A/B
-            # GEMV ablations (tools/gemv_ablate.py; results are wrong by construction, only the timing is read)
-            "abl_noscale": ["-DVOX_ABL_NOSCALE"], "abl_nox": ["-DVOX_ABL_NOX"], "abl_wfirst": ["-DVOX_ABL_WFIRST"],      # (abl_wfirst predates the x-first default and is a no-op now)
-            "abl_noconsume": ["-DVOX_ABL_NOCONSUME"], "abl_xfirst_resid": ["-DVOX_ABL_XFIRST_RESID_ONLY"], "abl_xfirst_noswiglu": ["-DVOX_ABL_XFIRST_NO_SWIGLU"], "abl_noreduce": ["-DVOX_ABL_NOREDUCE"],
-            "abl_all": ["-DVOX_ABL_NOSCALE", "-DVOX_ABL_NOX", "-DVOX_ABL_NOCONSUME", "-DVOX_ABL_NOREDUCE"]}
+VARIANTS = {"timeline": ["-DVOX_TIMELINE"]}      # measurement build (tools/timeline.py)
 
 if __name__ == "__main__":
     import sys

@@ -1708,7 +1708,7 @@ static int32_t decoder_prefill_dev(vox_model* m, float* x, int M, vox_cache* kc,
     // q4_skinny_mt_kernel consumes) into the context's XF scratch -- no f32 xn, no conversion launch for q|k|v and w1|w3
     auto xf_ok = [&](const Q4W& w) { return w.fmt == WFMT_Q4_0 && w.qt && w.st && w.nb % 4 == 0 && w.K == D && D % 128 == 0 && D <= 10240; };
     bool norm_xf = n_seq == 1 && M > 16 && M <= 48 && knob_str("VOX_PREFILL_NO_NORM_XF") == nullptr &&
-                   knob_str("VOX_NO_SKINNY_MT") == nullptr && knob_str("VOX_PREFILL_KERNEL") == nullptr;      // (the kernel-selection knobs of tools/prefill_bench.py act on f32-row GEMMs)
+                   knob_str("VOX_NO_SKINNY_MT") == nullptr;      // (VOX_NO_SKINNY_MT: GEMMs on f32 rows)
     if (norm_xf) {
         if (!cx->xf_scratch) { cx->xf_scratch_bytes = (size_t)3 * 16384 * 64; if (hipMalloc((void**)&cx->xf_scratch, cx->xf_scratch_bytes) != hipSuccess) { (void)hipGetLastError(); cx->xf_scratch = nullptr; cx->xf_scratch_bytes = 0; } }
         norm_xf = cx->xf_scratch != nullptr;
@@ -3449,20 +3449,6 @@ extern "C" int32_t vox_bench_wide(vox_model* m, int32_t which, int32_t mt, int32
         }
         return VOX_OK;
     };
-    if (const char* tl = knob_str("VOX_WIDE_TL")) {      // in-kernel timeline of ONE GEMM launch (layer atoi(tl)): s_memrealtime stamps (100 MHz) of wave 0 of every workgroup
-        const int n_wg = ((w0[which]->N / 16 + 4 * pl.ntw - 1) / (4 * pl.ntw)) * pl.kz;
-        DevBuf b_tl; HIPCHK(b_tl.alloc((size_t)n_wg * 64)); HIPCHK(hipMemset(b_tl.p, 0, (size_t)n_wg * 64));
-        GemmParams g = params(atoi(tl), true, 0); g.bias = (const float*)b_tl.p;
-        setenv("VOX_WIDE_ABL", "8", 1); vox_debug_reload_knobs();
-        HIPCHK(launch_q4_wide(g, epis[which] | 0x100, s)); HIPCHK(hipStreamSynchronize(s));
-        unsetenv("VOX_WIDE_ABL"); vox_debug_reload_knobs();
-        std::vector<unsigned long long> h((size_t)n_wg * 8); HIPCHK(hipMemcpy(h.data(), b_tl.p, h.size() * 8, hipMemcpyDeviceToHost));
-        unsigned long long t0 = ~0ull; for (int i = 0; i < n_wg; i++) if (h[(size_t)i * 8]) t0 = std::min(t0, h[(size_t)i * 8]);
-        static const char* nm[8] = {"entry", "prologue issued", "A(0) in registers + cs", "first barrier passed", "step 0 done", "step 1 done", "all steps done", "stored"};
-        fprintf(stderr, "[wide timeline] operator %d, %d workgroups, %d steps per slice; microseconds after the first workgroup's entry: min / median / max over workgroups\n", which, n_wg, pl.sps);
-        for (int k = 0; k < 8; k++) { std::vector<double> v; for (int i = 0; i < n_wg; i++) if (h[(size_t)i * 8 + k]) v.push_back((double)(h[(size_t)i * 8 + k] - t0) * 0.01); if (v.empty()) continue; std::sort(v.begin(), v.end());
-            fprintf(stderr, "  %-24s %7.2f %7.2f %7.2f\n", nm[k], v.front(), v[v.size() / 2], v.back()); }
-    }
     out_us[1] = 0.0;
     VOXCHK(timed(0, &out_us[0])); if (which != 4) VOXCHK(timed(1, &out_us[1])); VOXCHK(timed(2, &out_us[2])); VOXCHK(timed(3, &out_us[3]));
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);

@@ -915,30 +915,18 @@ __global__ __launch_bounds__(NTHR, 1) void decode_engine_kernel(const EngParams 
     if (tid == 0) c->xcc_id = __builtin_amdgcn_s_getreg((20) | (0 << 6) | ((4 - 1) << 11));      // HW_REG_XCC_ID (id 20), bits 3:0
     __syncthreads();
     Tl tl; tl.on = p.tl != nullptr && lane == 0; tl.buf = p.tl ? p.tl + (size_t)blockIdx.x * 32 : nullptr;
-#ifndef ENG_ROLES
-#define ENG_ROLES 7
-#endif
     if (wave == 0) {
         tl(19);
-#ifdef ENG_PRIO_LOADER
-        __builtin_amdgcn_s_setprio(ENG_PRIO_LOADER);
-#endif
-        if (ENG_ROLES & 1) eng_loader(p, c, (unsigned)(uintptr_t)(lds + L_RING), lane, tl);
+        eng_loader(p, c, (unsigned)(uintptr_t)(lds + L_RING), lane, tl);
     } else if (wave == 1) {
-#ifdef ENG_PRIO_COMM
-        __builtin_amdgcn_s_setprio(ENG_PRIO_COMM);
-#endif
-        if (ENG_ROLES & 2) eng_comm(p, c, lds, lane, tl);
+        eng_comm(p, c, lds, lane, tl);
         // the last workgroup-independent act of the launch: bump the serial (every workgroup has read it long before any lm_head input existed)
         if (blockIdx.x == 0 && lane == 0) {
             const unsigned sv = *p.serial; asm volatile("" ::: "memory"); *p.serial = sv + 1u;
             if (p.flags & ENGF_ARGMAX_IN) { const int pv_ = *p.pos_rw; asm volatile("" ::: "memory"); *p.pos_rw = pv_ + 1; }      // likewise: every workgroup read the position when it started
         }
     } else {
-#ifdef ENG_PRIO_CONS
-        __builtin_amdgcn_s_setprio(ENG_PRIO_CONS);
-#endif
-        if (ENG_ROLES & 4) eng_consumer(p, c, lds, wave - 2, lane, tl);
+        eng_consumer(p, c, lds, wave - 2, lane, tl);
     }
 }
 

@@ -513,13 +513,7 @@ __device__ __forceinline__ void b16_comm(BCtl* c, unsigned char* lds, const int 
 // parameters are re-read from the kernarg segment with scalar loads, LDS is addressed from its base, and the lane index is made opaque at every phase entry.  Written as
 // one loop body with shared state, hipcc hoisted every phase's loop-invariant, lane-derived values out of the layer loop and carried them across all the other phases:
 // 180 VGPRs spilled into the hot loops (each phase alone fits: q|k|v and w1|w3 128 VGPRs with the wave's 64 registers of A fragments, attention 114).  Calling the
-// phases (noinline) also ends every live range but costs 48 callee-saved VGPRs stored and reloaded per call -- 1.4 MB of scratch traffic per CU and layer; -DB16_NOINLINE
-// keeps that form for comparison.
-#ifndef B16_NOINLINE
-#define B16_PHASE __device__ __forceinline__
-#else
-#define B16_PHASE __device__ __attribute__((noinline))
-#endif
+// phases (noinline) also ends every live range but costs 48 callee-saved VGPRs stored and reloaded per call -- 1.4 MB of scratch traffic per CU and layer.
 constexpr int CB_LAYER = 5;      // workgroup barriers among the consumer waves per layer: q|k|v, wo, w1|w3 (2), w2
 
 struct BCons {
@@ -585,7 +579,7 @@ struct BCons {
 
 // ================= q|k|v: 16 + 8 weight rows x K 3072, K split over the 12 waves =================
 template <int NG, bool KVR>
-B16_PHASE void ph_qkv(int cw_, int lane, int l_, int q_) {
+__device__ __forceinline__ void ph_qkv(int cw_, int lane, int l_, int q_) {
     B16_PROLOGUE
     unsigned char* part = lds + BL_PART;
     const unsigned P0 = pkL + (unsigned)(q * QKV_PK);
@@ -653,7 +647,7 @@ B16_PHASE void ph_qkv(int cw_, int lane, int l_, int q_) {
 
 // ================= attention: head h of sequence 2 s + team, six waves, per-wave online softmax over the wave's keys =================
 template <int NG, bool KVR>
-B16_PHASE void ph_attn(int cw_, int lane, int l_, int q_) {
+__device__ __forceinline__ void ph_attn(int cw_, int lane, int l_, int q_) {
     B16_PROLOGUE
     const int* posl = reinterpret_cast<const int*>(lds + L_POS(q));
     const float* qkvn = reinterpret_cast<const float*>(lds + L_QKVN(q));
@@ -728,11 +722,7 @@ B16_PHASE void ph_attn(int cw_, int lane, int l_, int q_) {
     }
     B16_GUARD(1);
     *reinterpret_cast<float2*>(po + cw * 128 + lane * 2) = o;
-#ifdef VOX_PK_AS_COMPILED
-    if (lane == 0) { ml[2 * cw] = m_run; ml[2 * cw + 1] = l_run; }
-#else
     if (lane == 0) { volatile float* mlv = ml; mlv[2 * cw] = m_run; mlv[2 * cw + 1] = l_run; }      // (two 4-byte stores: as one 8-byte store hipcc swapped the pair with v_pk_mov_b32 op_sel:[1,0] -- vox_kernels.h, VOX_NO_PK_F32)
-#endif
     cs.tbarrier(team, 6u * ((unsigned)(NG * l + q) + 1u));
     if (tw == 0) {      // combine the team's six partials (fixed order), normalise, publish head h's output of sequence msq as wo's A fragments (hi + lo)
         float M = -INFINITY;
@@ -767,7 +757,7 @@ B16_PHASE void ph_attn(int cw_, int lane, int l_, int q_) {
 
 // ================= wo: rows [96 j, +96) x the 512 columns of the XCD group's four heads -> plane g =================
 template <int NG, bool KVR>
-B16_PHASE void ph_wo(int cw_, int lane, int l_, int q_) {
+__device__ __forceinline__ void ph_wo(int cw_, int lane, int l_, int q_) {
     B16_PROLOGUE
     unsigned char* part = lds + BL_PART;
     const unsigned P0 = pkL + (unsigned)(NG * QKV_PK + q * WO_PK);
@@ -804,7 +794,7 @@ B16_PHASE void ph_wo(int cw_, int lane, int l_, int q_) {
 
 // ================= w1|w3: 72 interleaved gate / up rows x K 3072 -> 36 SwiGLU outputs x 16 sequences =================
 template <int NG, bool KVR>
-B16_PHASE void ph_w13(int cw_, int lane, int l_, int q_) {
+__device__ __forceinline__ void ph_w13(int cw_, int lane, int l_, int q_) {
     B16_PROLOGUE
     unsigned char* part = lds + BL_PART;
     // SwiGLU outputs [16 m][36].  One group: in the CB lines, which are dead behind the first barrier.  NG > 1: the other group's pass writes ITS CB lines while waves 0..2
@@ -891,7 +881,7 @@ B16_PHASE void ph_w13(int cw_, int lane, int l_, int q_) {
 
 // ================= w2: rows [96 j, +96) x the XCD group's 1152 columns -> plane g =================
 template <int NG, bool KVR>
-B16_PHASE void ph_w2(int cw_, int lane, int l_, int q_) {
+__device__ __forceinline__ void ph_w2(int cw_, int lane, int l_, int q_) {
     B16_PROLOGUE
     unsigned char* part = lds + BL_PART;
     const unsigned P0 = pkL + (unsigned)(NG * PK_LAYER_M + q * W2_PK);
@@ -1019,17 +1009,14 @@ __global__ __launch_bounds__(NTHR, 1) void decode_engine_b16_kernel(const EngBAr
     if (tid == 0) c->xcc_id = __builtin_amdgcn_s_getreg((20) | (0 << 6) | ((4 - 1) << 11));      // HW_REG_XCC_ID
     __syncthreads();
     Tl tl; tl.on = p.tl != nullptr && lane == 0; tl.buf = p.tl ? p.tl + (size_t)blockIdx.x * 32 : nullptr;
-#ifndef B16_ROLES
-#define B16_ROLES 7
-#endif
-    if (wave == 0) { tl(19); if (B16_ROLES & 1) b16_loader<NG>(p, c, (unsigned)(uintptr_t)(lds + BL_RING), lane, tl); }
+    if (wave == 0) { tl(19); b16_loader<NG>(p, c, (unsigned)(uintptr_t)(lds + BL_RING), lane, tl); }
     else if (wave == 1) {
-        if (B16_ROLES & 2) b16_comm<NG>(c, lds, lane, tl);
+        b16_comm<NG>(c, lds, lane, tl);
         if (blockIdx.x == 0 && lane == 0) {
 #pragma unroll
             for (int q = 0; q < NG; q++) { unsigned* sp = a.g[q].serial; const unsigned sv = *sp; asm volatile("" ::: "memory"); *sp = sv + 1u; }
         }
-    } else if (B16_ROLES & 4) b16_consumer<NG, KVR>(c, lds, wave - 2, lane);
+    } else b16_consumer<NG, KVR>(c, lds, wave - 2, lane);
 }
 
 // 256 per-CU partial sums of squares -> 16 (fixed order), the count the launch-based lm_head GEMM's prologue takes

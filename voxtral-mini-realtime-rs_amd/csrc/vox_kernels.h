@@ -323,7 +323,7 @@ hipError_t launch_engb_ssq_fold(const float* ssq256, float* ssq16, hipStream_t s
 int engb_lds_bytes();
 int engb_lds_bytes2();                                // ... of the two-group launch
 
-// ---- measurement knobs: VOX_* environment snapshot (taken at vox_ctx_create / vox_debug_reload_knobs); launch paths never call getenv
+// ---- knobs: VOX_* environment snapshot (taken at vox_ctx_create / vox_debug_reload_knobs); launch paths never call getenv
 void knobs_load_once();      // vox_ctx_create: build the snapshot if it does not exist yet (thread-safe)
 void knobs_reload();         // vox_debug_reload_knobs (tests): replace the snapshot
 // MI355X behaviour found in round 6 (tools/repro/pk_fp32_corun.cpp, profiles/r06_pk_fp32_corun.txt): a packed-FP32 VALU instruction (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32)
@@ -333,11 +333,7 @@ void knobs_reload();         // vox_debug_reload_knobs (tests): replace the snap
 // squares, a swapped 8-byte LDS store in the batched engine), so: kernels where they appeared are compiled without packed FP32 (this attribute) or re-worded, and
 // tests/test_abi_cpu.py::test_no_packed_fp32_src1_swap scans every shipped code object for them (tools/kernel_resources.py).  (Only rope_kernel's instance was ever seen to
 // fail in the product -- two sessions on one GPU; the others are removed because the stand-alone reproducer fails on their encoding.)
-#ifdef VOX_PK_AS_COMPILED      // measurement build `pk_as_compiled` (build.py VARIANTS): the kernels as hipcc packs them -- what the hazard costs to avoid
-#define VOX_NO_PK_F32
-#else
 #define VOX_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
-#endif
 const char* knob_str(const char* name);      // nullptr when unset
 
 // ---- timeline instrumentation (measurement builds only, -DVOX_TIMELINE): every q4_gemv / attn_decode launch gets the next slot and its

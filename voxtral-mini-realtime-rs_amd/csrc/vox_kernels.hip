@@ -228,20 +228,14 @@ __global__ __launch_bounds__(64 * NWV, 1) void q4_gemv_kernel(const GemvParams p
     constexpr bool HAS_MUL = PRO == PRO_RMS_MUL || PRO == PRO_RMS_MUL_SUM, SUMP = PRO == PRO_RMS_MUL_SUM;
     constexpr int NPART = 2;                                          // PRO_RMS_MUL_SUM: the 4 int64 accumulators of a piece = two 16-byte loads
     float4 xp[NX], gp[PRO != PRO_NONE ? NX : 1], mp[HAS_MUL ? NX : 1], pp[SUMP ? NX : 1][SUMP ? NPART : 1];
-#define VOX_XLOAD                                                                                        \
-    _Pragma("unroll") for (int i = 0; i < NX; i++) {                                                     \
-        const int pc = min(tid + NT * i, npieces - 1);                                                   \
-        xp[i] = reinterpret_cast<const float4*>(xg)[pc];                                                 \
-        if (SUMP) { pp[i][0] = reinterpret_cast<const float4*>(p.xacc)[2 * pc]; pp[i][1] = reinterpret_cast<const float4*>(p.xacc)[2 * pc + 1]; } \
-        if (PRO != PRO_NONE) gp[i] = reinterpret_cast<const float4*>(p.gamma)[pc];                       \
-        if (HAS_MUL) mp[i] = reinterpret_cast<const float4*>(p.mul)[pc];                                 \
-    }
-#if defined(VOX_ABL_NOX)          /* measurement build: no activation loads at all (results wrong) */
 #pragma unroll
-    for (int i = 0; i < NX; i++) { xp[i] = make_float4(1.f, 2.f, 3.f, 4.f); gp[PRO != PRO_NONE ? i : 0] = xp[i]; mp[HAS_MUL ? i : 0] = xp[i]; if (SUMP) for (int u = 0; u < NPART; u++) pp[i][u] = make_float4(0.f, 0.f, 0.f, 0.f); }
-#elif !defined(VOX_ABL_WFIRST)
-    VOX_XLOAD
-#endif
+    for (int i = 0; i < NX; i++) {
+        const int pc = min(tid + NT * i, npieces - 1);
+        xp[i] = reinterpret_cast<const float4*>(xg)[pc];
+        if (SUMP) { pp[i][0] = reinterpret_cast<const float4*>(p.xacc)[2 * pc]; pp[i][1] = reinterpret_cast<const float4*>(p.xacc)[2 * pc + 1]; }
+        if (PRO != PRO_NONE) gp[i] = reinterpret_cast<const float4*>(p.gamma)[pc];
+        if (HAS_MUL) mp[i] = reinterpret_cast<const float4*>(p.mul)[pc];
+    }
     // per-pass lane constants: chunk-in-group -> (row in group, chunk in row)
     int vcl[P], cp[P], rp[P]; bool okp[P];
 #pragma unroll
@@ -257,28 +251,11 @@ __global__ __launch_bounds__(64 * NWV, 1) void q4_gemv_kernel(const GemvParams p
     _Pragma("unroll") for (int q_ = 0; q_ < P; q_++) {                                                   \
         const size_t idx = (size_t)(G_) * rnb + vcl[q_];                                                 \
         Q_[q_] = ld_nt_u4(p.w.qs + idx);                                                                 \
-        D_[q_] = VOX_SCLOAD(idx);                                                                        \
+        D_[q_] = __builtin_nontemporal_load(p.w.sc + idx);                                               \
     }
-#ifdef VOX_ABL_NOSCALE            /* measurement build: no block-scale loads (results wrong) */
-#define VOX_SCLOAD(I_) ((uint16_t)0x3c00)
-#else
-#define VOX_SCLOAD(I_) __builtin_nontemporal_load(p.w.sc + (I_))
-#endif
-    // No weight request before the activation vector is staged: the vector is a cross-XCD read that otherwise queues behind the weight bursts of
-    // the workgroups that started first (3 x 3 back-to-back pairs, tools/gemv_ablate.py: q|k|v 6.75 -> 6.20 us, w2 7.9 -> 7.6, wo 4.75 -> 4.65;
+    // No weight request before the activation vector is staged (step (3) below): the vector is a cross-XCD read that otherwise queues behind the
+    // weight bursts of the workgroups that started first (3 x 3 back-to-back pairs: q|k|v 6.75 -> 6.20 us, w2 7.9 -> 7.6, wo 4.75 -> 4.65;
     // w1|w3 and lm_head neutral).
-#ifdef VOX_ABL_XFIRST_RESID_ONLY      /* measurement build: the earlier setting (only wo / w2 wait for the vector) */
-    constexpr bool XFIRST = PRO == PRO_NONE && EPI == EPI_RESID;
-#elif defined(VOX_ABL_XFIRST_NO_SWIGLU)  /* measurement build: w1|w3 keeps the weights-with-vector order */
-    constexpr bool XFIRST = EPI != EPI_SWIGLU;
-#else
-    constexpr bool XFIRST = true;
-#endif
-    if (!XFIRST) { VOX_WLOAD(qa, da, min(g, n_groups - 1)) }
-#if defined(VOX_ABL_WFIRST) && !defined(VOX_ABL_NOX)       /* measurement build: weights issued BEFORE the activation loads */
-    VOX_XLOAD
-#endif
-#undef VOX_XLOAD
 
     // (3) prologue on the activation vector (RMSNorm (+Ada multiplier) fused), staged to LDS.  The row scale 1/rms is a scalar, so it
     // commutes with the dot products: x * gamma is staged UNnormalised right away and every row result is multiplied by rstd in
@@ -325,7 +302,7 @@ __global__ __launch_bounds__(64 * NWV, 1) void q4_gemv_kernel(const GemvParams p
         }
     }
     __syncthreads();
-    if (XFIRST) { VOX_WLOAD(qa, da, min(g, n_groups - 1)) }
+    VOX_WLOAD(qa, da, min(g, n_groups - 1))
     VOX_TL(p.tl_slot, blockIdx.x * NWV + wave, 1);
     // burn RmsNorm divides by sqrt(mean(x^2) + eps); we multiply by the reciprocal
     float ssq = 0.f;
@@ -352,11 +329,11 @@ __global__ __launch_bounds__(64 * NWV, 1) void q4_gemv_kernel(const GemvParams p
                     const float4 v = xs[xs_piece(cp[q_], j)];                                                          \
                     xv[4 * j + 0] = v.x; xv[4 * j + 1] = v.y; xv[4 * j + 2] = v.z; xv[4 * j + 3] = v.w;                \
                 }                                                                                                      \
-                const float val = f16_bits_to_f32(D_[q_]) * (VOX_DOT(Q_[q_], xv) - 8.0f * sxs[cp[q_]]);                \
+                const float val = f16_bits_to_f32(D_[q_]) * (q4_chunk_dot(Q_[q_], xv) - 8.0f * sxs[cp[q_]]);          \
                 _Pragma("unroll") for (int r = 0; r < R; r++) acc[r] += (R == 1 || rp[q_] == r) ? val : 0.f;           \
             }                                                                                                          \
         }                                                                                                              \
-        VOX_REDUCE                                                                                                     \
+        _Pragma("unroll") for (int r = 0; r < R; r++) acc[r] = wave_sum(acc[r]);                                     \
         if (PRO != PRO_NONE) { _Pragma("unroll") for (int r = 0; r < R; r++) acc[r] *= rstd; }                          \
         if (EPI == EPI_STORE || EPI == EPI_RESID || EPI == EPI_GELU) {                                                 \
             _Pragma("unroll") for (int r = 0; r < R; r++) {                                                            \
@@ -403,16 +380,6 @@ __global__ __launch_bounds__(64 * NWV, 1) void q4_gemv_kernel(const GemvParams p
             }                                                                                                          \
         }                                                                                                              \
     }
-#ifdef VOX_ABL_NOCONSUME
-#define VOX_DOT(Q_, X_) (__uint_as_float(((Q_).x ^ (Q_).y ^ (Q_).z ^ (Q_).w) & 0x3fffffffu) + (X_)[0])
-#else
-#define VOX_DOT(Q_, X_) q4_chunk_dot(Q_, X_)
-#endif
-#ifdef VOX_ABL_NOREDUCE
-#define VOX_REDUCE _Pragma("unroll") for (int r = 0; r < R; r++) acc[r] = readlane_f(acc[r], 0);
-#else
-#define VOX_REDUCE _Pragma("unroll") for (int r = 0; r < R; r++) acc[r] = wave_sum(acc[r]);
-#endif
 
     // software-pipelined, unrolled by two so the double buffer needs no register copies
     while (g < n_groups) {
@@ -426,10 +393,7 @@ __global__ __launch_bounds__(64 * NWV, 1) void q4_gemv_kernel(const GemvParams p
         g += n_waves;
     }
 #undef VOX_WLOAD
-#undef VOX_SCLOAD
 #undef VOX_GROUP
-#undef VOX_DOT
-#undef VOX_REDUCE
     VOX_TL(p.tl_slot, blockIdx.x * NWV + wave, 3);
     if (EPI == EPI_ARGMAX) {
         if (lane == 0) { red[NWV + wave] = best; reinterpret_cast<int*>(red)[2 * NWV + wave] = best_i; }
@@ -461,7 +425,7 @@ static hipError_t ensure_dyn_lds(Kern kern, size_t lds, DevOnce* done) {
 }
 
 static hipError_t launch_dense_gemv(const GemvParams& p, int ny, int pro, int epi, hipStream_t s);
-// Measurement knobs (VOX_*): the environment is read ONCE -- at vox_ctx_create, or by vox_debug_reload_knobs() for the tests that flip a knob at run time -- into a
+// Knobs (VOX_*): the environment is read ONCE -- at vox_ctx_create, or by vox_debug_reload_knobs() for the tests that flip a knob at run time -- into a
 // table; no launch path calls getenv.  Lookups are read-only between reloads (a reload while another thread launches is the caller's race, as with setenv itself).
 // The table is an IMMUTABLE snapshot: it is built once (first vox_ctx_create / first knob_str) and afterwards only ever REPLACED as a whole by vox_debug_reload_knobs (tests;
 // documented as not thread-safe against running launches).  Launch paths hold c_str() pointers into it, so a second vox_ctx_create on another thread -- one context per
@@ -497,12 +461,9 @@ static bool gemv_has(int R, int P) {
 }
 static inline int passes_for(int K, int R) { return (R * (K / 32) + 63) / 64; }
 
-// rows per wave. Prefers the R that fills every pass exactly (R*nb % 64 == 0). Tuning knobs (measurement only):
-// VOX_GEMV_R / VOX_GEMV_R_PAIR / VOX_GEMV_R_ARGMAX override the choice when the (R, P) pair is instantiated.
+// rows per wave. Prefers the R that fills every pass exactly (R*nb % 64 == 0).
 int q4_gemv_default_R(int N, int K, int epi) {
     const bool pair = (epi == EPI_SWIGLU || epi == EPI_ROPE_KV);
-    const int e = env_int(epi == EPI_ARGMAX ? "VOX_GEMV_R_ARGMAX" : pair ? "VOX_GEMV_R_PAIR" : "VOX_GEMV_R");
-    if (e && N % e == 0 && gemv_has(e, passes_for(K, e)) && (!pair || e % 2 == 0)) return e;
     const int nb = K / 32;
     const int order_exact[3] = {pair ? 2 : 1, pair ? 4 : 2, 4};
     for (int i = 0; i < 3; i++) {   // exact fit, unless it needs so many passes that the register file halves occupancy
@@ -518,21 +479,18 @@ int q4_gemv_default_R(int N, int K, int epi) {
 // number of workgroups for a GEMV over N rows with R rows per wave: every wave gets an equal whole number of row
 // groups where possible, at most ~3 workgroups per CU stay resident and stream (persistent waves).
 int dense_gemv_grid(int N);
-// waves per workgroup of the decode GEMV: 4 (768 workgroups), 6 (512) or 12 (256, one per CU) -- same total waves, fewer copies of the
-// staged activation vector.  VOX_GEMV_NWV overrides (measurement knob).
+// waves per workgroup of the decode GEMV: 4 (768 workgroups) or 12 (256, one per CU) -- same total waves, fewer copies of the
+// staged activation vector.
 // Round-2 measurements (profiles/r02_decode_knobs.txt): 12-wave workgroups (one copy of x per CU instead of three) win where the staged
 // vector is long or the kernel is long enough to amortise the bigger barrier -- wo (K = 4096) 4.93 -> 4.68 us, w2 (K = 9216) 8.31 -> 7.89 us,
 // w1|w3 9.58 -> 9.25 us -- and lose on q|k|v (RoPE / cache epilogue; 6.08 -> 6.16) and lm_head (38.9 -> 41.1).
 int q4_gemv_nwv(int K, int epi) {
-    const int e = env_int("VOX_GEMV_NWV");
-    if (e == 4 || e == 6 || e == 12) return e;
     if (epi == EPI_ARGMAX || epi == EPI_ROPE_KV) return 4;
     return (K >= 4096 || epi == EPI_SWIGLU) ? 12 : 4;
 }
 static int q4_gemv_grid_w(int N, int R, int nwv) {
     const int n_groups = N / R;
-    int target = env_int("VOX_GEMV_WGS"); if (target <= 0) target = 768;
-    target = target * 4 / nwv;                      // the same number of waves for every workgroup size
+    const int target = 768 * 4 / nwv;               // the same number of waves for every workgroup size
     int wgs = (n_groups + nwv - 1) / nwv;
     if (wgs > target) {
         const int iters = (n_groups + nwv * target - 1) / (nwv * target);
@@ -565,7 +523,6 @@ static hipError_t gemv_launch_t(const GemvParams& p, int ny, hipStream_t s) {
     if (fat) {
         const int nwv = q4_gemv_nwv(p.w.K, EPI);
         if (nwv == 12) return gemv_launch_w<P, R, PRO, EPI, fat ? 12 : 4>(p, ny, s);
-        if (nwv == 6) return gemv_launch_w<P, R, PRO, EPI, fat ? 6 : 4>(p, ny, s);
     }
     return gemv_launch_w<P, R, PRO, EPI, 4>(p, ny, s);
 }
@@ -955,24 +912,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void q
     for (int i = 0; i < MT; i++) {
         const int f = tid + 256 * i, sm = f >> 4, j = (f >> 2) & 3, g = f & 3;
         xrow[i] = p.x + (size_t)min(m0 + sm, M - 1) * p.x_stride;
-#ifdef VOX_GEMM_OLD_STAGING      /* measurement build (build.py gemm_oldstage): the pre-round-5 layout, for the same-box A/B in profiles/r05_gemm_staging_ab.txt */
-        slot[i] = (j * MT + (sm >> 4)) * 64 + g * 16 + (sm & 15);
-#else
         slot[i] = (j * MT + (sm >> 4)) * 64 + g * 16 + ((sm & 15) ^ (4 * j + g));
-#endif
         xo_a[i] = 32 * j + (FMT == WFMT_Q4_0 ? 4 * g : 8 * g); xo_b[i] = 32 * j + (FMT == WFMT_Q4_0 ? 16 + 4 * g : 8 * g + 4);
     }
     // MFMA role
     const int wg = lane >> 4;
     int rdl[4];      // where this lane's A fragment of block j sits inside its 64-slot block (see the staging map)
 #pragma unroll
-    for (int j = 0; j < 4; j++) {
-#ifdef VOX_GEMM_OLD_STAGING
-        rdl[j] = lane;
-#else
-        rdl[j] = (lane & 48) | ((lane & 15) ^ (4 * j + wg));
-#endif
-    }
+    for (int j = 0; j < 4; j++) rdl[j] = (lane & 48) | ((lane & 15) ^ (4 * j + wg));
     const uint32_t* wq[NT]; const uint16_t* ws[NT]; const uint4* wd16[NT]; const uint4* wqt[NT]; int wn[NT]; bool wok[NT];
 #pragma unroll
     for (int t = 0; t < NT; t++) {
@@ -1397,11 +1344,6 @@ __device__ __forceinline__ bf16x8 v4_as_bf16x8(u32x4_t v) { union { u32x4_t u; b
 // to the top, 1 - 13 KB of scratch per lane, 10 x slower.)
 template <int MT, int NTW, bool DIRECT>
 __global__ __launch_bounds__(256, 2) void q4_wide_kernel(const GemmParams p, const int sps, float* __restrict__ planes) {
-    constexpr int SPS = 0;
-    unsigned long long* tlb = (SPS == 0 && (p.ksplit & 8)) ? reinterpret_cast<unsigned long long*>(const_cast<float*>(p.bias)) + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8 : nullptr;
-#define VOX_WTL(I_) { if (SPS == 0 && tlb && threadIdx.x == 0) tlb[I_] = __builtin_amdgcn_s_memrealtime(); }
-    VOX_WTL(0)
-    const int abl = p.ksplit;      // measurement only (tools/wide_bench.py, VOX_WIDE_ABL): 1 no MFMA work, 2 no A loads past the prologue, 4 no weight loads past it (results wrong)
     extern __shared__ __attribute__((aligned(16))) u32x4_t wlds[];      // [2 stages][MT][hi, lo][4 j][64 lanes]
     __shared__ float s_rstd[MT * 16]; __shared__ float s_pp[16 * 16];
     __shared__ __attribute__((aligned(16))) float s_cs[2][MT][4][4][4];      // [stage][group][block j][lane group g][4 rows]: the -136 sum(x) correction of every (row, block) of the step
@@ -1433,7 +1375,6 @@ __global__ __launch_bounds__(256, 2) void q4_wide_kernel(const GemmParams p, con
 #define VOX_WISSUE(B_, S_) { _Pragma("unroll") for (int t = 0; t < NTW; t++) { wr[B_][t] = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(wq[t] + 64 * (S_))); sr[B_][t] = *reinterpret_cast<const u32x2_t*>(ws[t] + 64 * (S_)); } }
     VOX_AISSUE(0, 0) VOX_WISSUE(0, 0)
     __builtin_amdgcn_sched_barrier(0);
-    VOX_WTL(1)
     if (WD == 2) { const int s1 = min(1, sps - 1); VOX_WISSUE(1, s1) }
     __builtin_amdgcn_sched_barrier(0);
     if (DIRECT) {      // fused RMSNorm, consumer side (as q4_skinny_kernel PRO): rstd of every row from the producer's partial sums of squares; requested behind the first operands
@@ -1460,53 +1401,46 @@ __global__ __launch_bounds__(256, 2) void q4_wide_kernel(const GemmParams p, con
             if (li == 0) *reinterpret_cast<f32x4*>(&s_cs[(K_) & 1][mt][wave][g][0]) = c_;                          \
         }                                                                                                          \
         _Pragma("unroll") for (int u = 0; u < NA; u++) stg[tid + 256 * u] = areg[0][u];                     \
-        if ((S_) == 0) VOX_WTL(2)                                                                                  \
         __syncthreads();      /* stage (K_ & 1) holds step S_; every wave is done with step S_ - 1 (the other stage) */ \
-        if ((S_) == 0) VOX_WTL(3)                                                                                  \
         uint32_t dw[NTW][4]; u32x2_t sv[NTW];                                                                        \
         _Pragma("unroll") for (int t = 0; t < NTW; t++) { dw[t][0] = wr[(K_) % WD][t].x; dw[t][1] = wr[(K_) % WD][t].y; dw[t][2] = wr[(K_) % WD][t].z; dw[t][3] = wr[(K_) % WD][t].w; sv[t] = sr[(K_) % WD][t]; } \
         __builtin_amdgcn_sched_barrier(0);                                                                         \
-        { const int sa = min((S_) + 1, sps - 1), sn = min((S_) + WD, sps - 1); if (!(abl & 2)) VOX_AISSUE(0, sa) if (!(abl & 4)) VOX_WISSUE((K_) % WD, sn) }      /* in consumption order: A one step ahead, the weights two */ \
+        { const int sa = min((S_) + 1, sps - 1), sn = min((S_) + WD, sps - 1); VOX_AISSUE(0, sa) VOX_WISSUE((K_) % WD, sn) }      /* in consumption order: A one step ahead, the weights two */ \
         __builtin_amdgcn_sched_barrier(0);                                                                         \
-        if (!(abl & 1)) {                                                                                          \
-            /* groups in sets of MH (all MT, or two at MT 4 x NTW 2, which sits at the 256-register limit): the set's chains are interleaved -- every MFMA's input comes \
-               from MH * NTW MFMAs earlier, not from the one before it -- and, where the registers allow (PF), block j + 1's fragments are requested before block j is multiplied */ \
-            constexpr int MH = MT * NTW >= 12 ? 1 : (MT * NTW >= 8 ? MT / 2 : MT), NH = MT / MH; constexpr bool PF = NH == 1;      \
-            u32x4_t fr[PF ? 2 : 1][MH][2]; f32x4 csr[PF ? 2 : 1][MH];                                              \
-            if (PF) { _Pragma("unroll") for (int mt = 0; mt < MH; mt++) { fr[0][mt][0] = stg[((mt * 2 + 0) * 4 + 0) * 64 + lane]; fr[0][mt][1] = stg[((mt * 2 + 1) * 4 + 0) * 64 + lane]; \
-                                                                           csr[0][mt] = *reinterpret_cast<const f32x4*>(&s_cs[(K_) & 1][mt][0][g][0]); } } \
-            _Pragma("unroll") for (int j = 0; j < 4; j++) {                                                        \
-                bf16x8 bw[NTW]; float d[NTW];                                                                      \
-                _Pragma("unroll") for (int t = 0; t < NTW; t++) {                                                  \
-                    bw[t] = as_bf16x8(q4_dword_to_bf16x8_biased(dw[t][j]));                                        \
-                    const uint32_t sc2 = (j >> 1) ? sv[t].y : sv[t].x;                                             \
-                    d[t] = f16_bits_to_f32((uint16_t)((j & 1) ? (sc2 >> 16) : (sc2 & 0xFFFFu)));                   \
-                }                                                                                                  \
-                _Pragma("unroll") for (int h = 0; h < NH; h++) {                                                   \
-                    constexpr int dummy_ = 0; (void)dummy_;                                                        \
-                    const int cur = PF ? (j & 1) : 0;                                                              \
-                    if (!PF) { _Pragma("unroll") for (int mt = 0; mt < MH; mt++) { const int mg_ = h * MH + mt; fr[0][mt][0] = stg[((mg_ * 2 + 0) * 4 + j) * 64 + lane]; fr[0][mt][1] = stg[((mg_ * 2 + 1) * 4 + j) * 64 + lane]; \
-                                                                                    csr[0][mt] = *reinterpret_cast<const f32x4*>(&s_cs[(K_) & 1][mg_][j][g][0]); } } \
-                    else if (j < 3) { _Pragma("unroll") for (int mt = 0; mt < MH; mt++) { fr[(j + 1) & 1][mt][0] = stg[((mt * 2 + 0) * 4 + j + 1) * 64 + lane]; fr[(j + 1) & 1][mt][1] = stg[((mt * 2 + 1) * 4 + j + 1) * 64 + lane]; \
-                                                                                           csr[(j + 1) & 1][mt] = *reinterpret_cast<const f32x4*>(&s_cs[(K_) & 1][mt][j + 1][g][0]); } } \
-                    f32x4 tt[MH][NTW];                                                                             \
-                    _Pragma("unroll") for (int mt = 0; mt < MH; mt++)                                              \
-                        _Pragma("unroll") for (int t = 0; t < NTW; t++) tt[mt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v4_as_bf16x8(fr[cur][mt][0]), bw[t], csr[cur][mt], 0, 0, 0); \
-                    _Pragma("unroll") for (int mt = 0; mt < MH; mt++)                                              \
-                        _Pragma("unroll") for (int t = 0; t < NTW; t++) tt[mt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v4_as_bf16x8(fr[cur][mt][1]), bw[t], tt[mt][t], 0, 0, 0); \
-                    _Pragma("unroll") for (int mt = 0; mt < MH; mt++)                                              \
-                        _Pragma("unroll") for (int t = 0; t < NTW; t++) acc[h * MH + mt][t] = __builtin_elementwise_fma((f32x4){d[t], d[t], d[t], d[t]}, tt[mt][t], acc[h * MH + mt][t]); \
-                }                                                                                                  \
+        /* groups in sets of MH (all MT, or two at MT 4 x NTW 2, which sits at the 256-register limit): the set's chains are interleaved -- every MFMA's input comes \
+           from MH * NTW MFMAs earlier, not from the one before it -- and, where the registers allow (PF), block j + 1's fragments are requested before block j is multiplied */ \
+        constexpr int MH = MT * NTW >= 12 ? 1 : (MT * NTW >= 8 ? MT / 2 : MT), NH = MT / MH; constexpr bool PF = NH == 1; \
+        u32x4_t fr[PF ? 2 : 1][MH][2]; f32x4 csr[PF ? 2 : 1][MH];                                                  \
+        if (PF) { _Pragma("unroll") for (int mt = 0; mt < MH; mt++) { fr[0][mt][0] = stg[((mt * 2 + 0) * 4 + 0) * 64 + lane]; fr[0][mt][1] = stg[((mt * 2 + 1) * 4 + 0) * 64 + lane]; \
+                                                                       csr[0][mt] = *reinterpret_cast<const f32x4*>(&s_cs[(K_) & 1][mt][0][g][0]); } } \
+        _Pragma("unroll") for (int j = 0; j < 4; j++) {                                                            \
+            bf16x8 bw[NTW]; float d[NTW];                                                                          \
+            _Pragma("unroll") for (int t = 0; t < NTW; t++) {                                                      \
+                bw[t] = as_bf16x8(q4_dword_to_bf16x8_biased(dw[t][j]));                                            \
+                const uint32_t sc2 = (j >> 1) ? sv[t].y : sv[t].x;                                                 \
+                d[t] = f16_bits_to_f32((uint16_t)((j & 1) ? (sc2 >> 16) : (sc2 & 0xFFFFu)));                       \
+            }                                                                                                      \
+            _Pragma("unroll") for (int h = 0; h < NH; h++) {                                                       \
+                constexpr int dummy_ = 0; (void)dummy_;                                                            \
+                const int cur = PF ? (j & 1) : 0;                                                                  \
+                if (!PF) { _Pragma("unroll") for (int mt = 0; mt < MH; mt++) { const int mg_ = h * MH + mt; fr[0][mt][0] = stg[((mg_ * 2 + 0) * 4 + j) * 64 + lane]; fr[0][mt][1] = stg[((mg_ * 2 + 1) * 4 + j) * 64 + lane]; \
+                                                                                csr[0][mt] = *reinterpret_cast<const f32x4*>(&s_cs[(K_) & 1][mg_][j][g][0]); } } \
+                else if (j < 3) { _Pragma("unroll") for (int mt = 0; mt < MH; mt++) { fr[(j + 1) & 1][mt][0] = stg[((mt * 2 + 0) * 4 + j + 1) * 64 + lane]; fr[(j + 1) & 1][mt][1] = stg[((mt * 2 + 1) * 4 + j + 1) * 64 + lane]; \
+                                                                                       csr[(j + 1) & 1][mt] = *reinterpret_cast<const f32x4*>(&s_cs[(K_) & 1][mt][j + 1][g][0]); } } \
+                f32x4 tt[MH][NTW];                                                                                 \
+                _Pragma("unroll") for (int mt = 0; mt < MH; mt++)                                                  \
+                    _Pragma("unroll") for (int t = 0; t < NTW; t++) tt[mt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v4_as_bf16x8(fr[cur][mt][0]), bw[t], csr[cur][mt], 0, 0, 0); \
+                _Pragma("unroll") for (int mt = 0; mt < MH; mt++)                                                  \
+                    _Pragma("unroll") for (int t = 0; t < NTW; t++) tt[mt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v4_as_bf16x8(fr[cur][mt][1]), bw[t], tt[mt][t], 0, 0, 0); \
+                _Pragma("unroll") for (int mt = 0; mt < MH; mt++)                                                  \
+                    _Pragma("unroll") for (int t = 0; t < NTW; t++) acc[h * MH + mt][t] = __builtin_elementwise_fma((f32x4){d[t], d[t], d[t], d[t]}, tt[mt][t], acc[h * MH + mt][t]); \
             }                                                                                                      \
         }                                                                                                          \
     }
     for (int s0 = 0; s0 < sps; s0 += 2) {
         VOX_WSTEP(0, s0)
-        if (s0 == 0) VOX_WTL(4)
         if (s0 + 1 < sps) VOX_WSTEP(1, s0 + 1)
-        if (s0 == 0) VOX_WTL(5)
     }
-    VOX_WTL(6)
 #undef VOX_WSTEP
 #undef VOX_AISSUE
 #undef VOX_WISSUE
@@ -1546,13 +1480,10 @@ __global__ __launch_bounds__(256, 2) void q4_wide_kernel(const GemmParams p, con
                     float* dst = planes + ((((size_t)z * MT + mt) * n_tiles + tile0 + t) * 64 + lane) * 4;
                     // WRITE-THROUGH plane stores: plain stores leave 6 - 14 MB dirty in the XCD L2s, which the kernel boundary then writes back before the finishing launch
                     // may start (MI355X_MICROARCH.md: boundary + B / 6 TB/s; publish-large: write-through wins) -- measured 102.5 -> 96.3 us per layer of GEMM + finishing
-                    // launches at four groups (VOX_WIDE_ABL=16: plain stores)
-                    if (!(p.ksplit & 16)) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" :: "v"(dst), "v"(acc[mt][t]) : "memory");
-                    else *reinterpret_cast<float4*>(dst) = make_float4(acc[mt][t][0], acc[mt][t][1], acc[mt][t][2], acc[mt][t][3]);
+                    // launches at four groups, against plain stores
+                    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" :: "v"(dst), "v"(acc[mt][t]) : "memory");
                 }
     }
-    VOX_WTL(7)
-#undef VOX_WTL
 }
 // finishing launch of the wide step: wave = one (group, n-tile): the K-slice planes summed in slice order (all loads in flight), then q4_skinny_kernel's epilogue for
 // that tile, on the group's rows / XF planes / partial sums of squares.  grid (ceil(n_tiles / 4), MT).
@@ -1645,23 +1576,22 @@ __global__ __launch_bounds__(256) void wide_finish_kernel(const GemmParams p, co
     }
 }
 // plan of one wide GEMM: n-tiles per wave, K slices.  Enough workgroups to fill the chip twice over where the shape allows (2 workgroups of 4 waves per CU), slices of
-// whole K steps.  VOX_WIDE_FORCE="N:ntw:kz" overrides one weight shape (measurement knob).
+// whole K steps.
 bool q4_wide_plan(const Q4W& w, int mt, int epi, WidePlan* pl) {
     if (mt < 2 || mt > 4 || w.fmt != WFMT_Q4_0 || !w.qt || !w.st || w.nb % 4 || w.N % 16) return false;
     if (epi != EPI_STORE && epi != EPI_ROPE_KV && epi != EPI_RESID_XF && epi != EPI_SWIGLU_XF) return false;
     const int nq = w.nb / 4, tiles = w.N / 16;
     int ntw = tiles >= 384 ? 2 : 1, kz = 1;
-    if (epi == EPI_STORE && tiles >= 4096 && !knob_str("VOX_WIDE_LM_NTW2")) ntw = 4;      // the lm_head (8192 n-tiles): 512 workgroups = ONE round of resident workgroups instead of two, half the activation re-reads
+    if (epi == EPI_STORE && tiles >= 4096) ntw = 4;      // the lm_head (8192 n-tiles): 512 workgroups = ONE round of resident workgroups instead of two, half the activation re-reads
     if (epi != EPI_STORE) {
         const int ranges = (tiles + 4 * ntw - 1) / (4 * ntw);
         for (int d = 1; d <= nq; d++) if (nq % d == 0) { kz = d; if ((long)ranges * d >= 320) break; }
         if (kz > 24) { for (int d = 24; d >= 1; d--) if (nq % d == 0) { kz = d; break; } }
     }
-    if (const char* f = knob_str("VOX_WIDE_FORCE")) { int fn = 0, fw = 0, fk = 0; if (sscanf(f, "%d:%d:%d", &fn, &fw, &fk) == 3 && fn == w.N && (fw == 1 || fw == 2 || (fw == 4 && epi == EPI_STORE)) && fk >= 1 && fk <= 24 && nq % fk == 0 && (epi != EPI_STORE || fk == 1)) { ntw = fw; kz = fk; } }
     pl->ntw = ntw; pl->kz = kz; pl->sps = nq / kz;
     return true;
 }
-size_t q4_wide_planes_bytes(const Q4W& w, int mt, const WidePlan& pl) { return pl.kz > 1 || true ? (size_t)pl.kz * mt * ((w.N + 15) / 16) * 256 * sizeof(float) : 0; }
+size_t q4_wide_planes_bytes(const Q4W& w, int mt, const WidePlan& pl) { return (size_t)pl.kz * mt * ((w.N + 15) / 16) * 256 * sizeof(float); }
 template <int MT, int NTW, bool DIRECT>
 static hipError_t wide_launch(const GemmParams& p, const WidePlan& pl, hipStream_t s) {
     const int tiles = (p.w.N + 15) / 16;
@@ -1669,8 +1599,6 @@ static hipError_t wide_launch(const GemmParams& p, const WidePlan& pl, hipStream
     const size_t lds = (size_t)2 * MT * 8 * 64 * sizeof(uint4);
     auto kern = q4_wide_kernel<MT, NTW, DIRECT>; static DevOnce done;
     hipError_t e = ensure_dyn_lds(kern, lds, &done); if (e != hipSuccess) return e;
-    if (knob_str("VOX_WIDE_DEBUG")) { static bool said = false; if (!said) { said = true; int occ = -1; (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void*>(kern), 256, lds);
-        hipFuncAttributes fa{}; (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kern)); fprintf(stderr, "[wide] MT %d NTW %d direct %d: grid %u x %u, %d steps per slice, lds %zu + %zu static, %d regs, occupancy %d workgroups / CU\n", MT, NTW, (int)DIRECT, grid.x, grid.y, pl.sps, lds, (size_t)fa.sharedSizeBytes, fa.numRegs, occ); } }
     kern<<<grid, dim3(256), lds, s>>>(p, pl.sps, p.kz_scratch);
     return hipGetLastError();
 }
@@ -1680,13 +1608,12 @@ hipError_t launch_q4_wide(const GemmParams& p, int epi_stage, hipStream_t s) {  
     const int MT = p.wide_mt;
     if (!p.xf || p.M != 16 * MT || !q4_wide_plan(p.w, MT, epi, &pl)) return hipErrorInvalidValue;
     const bool direct = epi == EPI_STORE;
-    GemmParams pa = p; pa.ksplit = env_int("VOX_WIDE_ABL");
     if (direct) { if (!p.out || !p.ssq_part || p.n_part < 1) return hipErrorInvalidValue; }
     else if (!p.kz_scratch || p.kz_scratch_bytes < q4_wide_planes_bytes(p.w, MT, pl)) return hipErrorInvalidValue;
     hipError_t e = hipErrorInvalidValue;
-#define VOX_W(M_, N_) if (MT == M_ && pl.ntw == N_) e = direct ? wide_launch<M_, N_, true>(pa, pl, s) : wide_launch<M_, N_, false>(pa, pl, s);
+#define VOX_W(M_, N_) if (MT == M_ && pl.ntw == N_) e = direct ? wide_launch<M_, N_, true>(p, pl, s) : wide_launch<M_, N_, false>(p, pl, s);
     if (only_finish) e = hipSuccess; else { VOX_W(2, 1) VOX_W(2, 2) VOX_W(3, 1) VOX_W(3, 2) VOX_W(4, 1) VOX_W(4, 2)
-        if (direct && pl.ntw == 4) { if (MT == 2) e = wide_launch<2, 4, true>(pa, pl, s); else if (MT == 3) e = wide_launch<3, 4, true>(pa, pl, s); else if (MT == 4) e = wide_launch<4, 4, true>(pa, pl, s); } }
+        if (direct && pl.ntw == 4) { if (MT == 2) e = wide_launch<2, 4, true>(p, pl, s); else if (MT == 3) e = wide_launch<3, 4, true>(p, pl, s); else if (MT == 4) e = wide_launch<4, 4, true>(p, pl, s); } }
 #undef VOX_W
     if (e != hipSuccess || direct || only_gemm) return e;
     dim3 fgrid(((p.w.N + 15) / 16 + 3) / 4, MT);
@@ -2000,18 +1927,15 @@ static hipError_t skinny_mt_launch(const GemmParams& p, int epi, hipStream_t s) 
 }
 // The pieces of the two-dimensional 17..48-row GEMM for callers that fold the finishing sum into their next kernel (the decoder prefill):
 // round 6: the prefill's 17..48-row GEMMs run on q4_wide_kernel (the rows' XF tiles staged through LDS once per workgroup, corrections once per workgroup, the tiles'
-// MFMA chains interleaved; row-major planes for the same finishing kernels) with its own K split; VOX_PREFILL_WIDE=0: q4_skinny_mt2_kernel (the round-3 form)
+// MFMA chains interleaved; row-major planes for the same finishing kernels) with its own K split; where the wide plan does not apply, q4_skinny_mt2_kernel (the round-3 form)
 static bool prefill_wide_plan(const Q4W& w, int M, WidePlan* pl) {
-    const char* e = knob_str("VOX_PREFILL_WIDE");
-    return !(e && e[0] == '0') && env_int("VOX_SKINNY_MT2") == 0 && M > 16 && M <= 48 && w.N % 16 == 0 && q4_wide_plan(w, (M + 15) / 16, EPI_ROPE_KV, pl);
+    return M > 16 && M <= 48 && w.N % 16 == 0 && q4_wide_plan(w, (M + 15) / 16, EPI_ROPE_KV, pl);
 }
 int q4_skinny_mt2_plan(const Q4W& w, int M) {      // K slices the 2-D kernel would use for this operator, 0 = not applicable
-    if (w.fmt != WFMT_Q4_0 || !w.qt || !w.st || w.nb % 4 || w.N % 2 || M <= 16 || M > 48 || env_int("VOX_SKINNY_MT2") < 0) return 0;
+    if (w.fmt != WFMT_Q4_0 || !w.qt || !w.st || w.nb % 4 || w.N % 2 || M <= 16 || M > 48) return 0;
     { WidePlan pl; if (prefill_wide_plan(w, M, &pl)) return pl.kz; }
     const int tiles = (w.N + 15) / 16, nq = w.nb / 4, wg1 = (tiles + 3) / 4;
-    int KZ = std::min(std::min(8, nq), std::max(1, (384 + wg1 - 1) / wg1));
-    { const int e = env_int("VOX_SKINNY_MT2"); if (e > 0) KZ = std::min(e, nq); }
-    return KZ;
+    return std::min(std::min(8, nq), std::max(1, (384 + wg1 - 1) / wg1));
 }
 hipError_t launch_xf_rows(const float* x, int x_stride, int M, int K, uint16_t* xf, hipStream_t s) {      // f32 rows -> ceil(M / 16) XF tiles
     const int mt = (M + 15) / 16; const long total = (long)mt * 16 * (K >> 2);
@@ -2095,24 +2019,21 @@ hipError_t launch_splitk_finish_resid(const float* planes, int KZ, int M, int N,
 static hipError_t launch_q4_skinny_mt(const GemmParams& p_in, int epi, hipStream_t s) {
     GemmParams p = p_in;
     const int mt = (p.M + 15) / 16, tiles = (p.w.N + 15) / 16;
-    if (!p.xf && p.xf_scratch && p.xf_scratch_bytes >= (size_t)mt * p.w.K * 64 && p.w.K % 128 == 0 && !env_int("VOX_SKINNY_MT_NO_XF")) {
+    if (!p.xf && p.xf_scratch && p.xf_scratch_bytes >= (size_t)mt * p.w.K * 64 && p.w.K % 128 == 0) {
         // rows -> XF tiles once per GEMM (a ~3 us launch), then the conversion-free kernel
         const long total = (long)mt * 16 * (p.w.K >> 2);
         xf_rows_kernel<<<dim3((unsigned)std::min<long>((total + 255) / 256, 1024)), dim3(256), 0, s>>>(p.x, p.x_stride, p.M, p.w.K, p.xf_scratch, mt);
         p.xf = reinterpret_cast<const uint4*>(p.xf_scratch);
     }
     int ntw = tiles >= 512 ? 2 : 1;                           // two n-tiles per wave only while >= 256 workgroups remain
-    { const int e = env_int("VOX_SKINNY_MT_NTW"); if (e == 1 || e == 2) ntw = e; }
-    // two-dimensional form (q4_skinny_mt2_kernel): K slices so that >= 384 workgroups remain; needs the XF tiles and room for the planes.  VOX_SKINNY_MT2=-1: off
-    if (p.xf && p.kz_scratch && p.w.N % 2 == 0 && env_int("VOX_SKINNY_MT2") >= 0) {
-        if (!env_int("VOX_SKINNY_MT_NTW")) ntw = 1;      // one n-tile per wave here (w1|w3 with two: 3.32 vs 3.23 ms per prefill, profiles/r03_prefill_2d_kernel.txt)
-        const int nq = p.w.nb / 4, wg1 = (tiles + 4 * ntw - 1) / (4 * ntw);
-        int KZ = std::min(std::min(8, nq), std::max(1, (384 + wg1 - 1) / wg1));
-        { const int e = env_int("VOX_SKINNY_MT2"); if (e > 0) KZ = std::min(e, nq); }
+    // two-dimensional form (q4_skinny_mt2_kernel): K slices so that >= 384 workgroups remain; needs the XF tiles and room for the planes
+    if (p.xf && p.kz_scratch && p.w.N % 2 == 0) {
+        ntw = 1;      // one n-tile per wave here (w1|w3 with two: 3.32 vs 3.23 ms per prefill, profiles/r03_prefill_2d_kernel.txt)
+        const int nq = p.w.nb / 4, wg1 = (tiles + 3) / 4;
+        const int KZ = std::min(std::min(8, nq), std::max(1, (384 + wg1 - 1) / wg1));
         if ((size_t)KZ * p.M * p.w.N * 4 <= p.kz_scratch_bytes) {
-#define VOX_MT2(M_, N_) if (mt == M_ && ntw == N_) return skinny_mt2_launch<M_, N_>(p, epi, KZ, s)
-            VOX_MT2(2, 1); VOX_MT2(2, 2); VOX_MT2(3, 1); VOX_MT2(3, 2);
-#undef VOX_MT2
+            if (mt == 2) return skinny_mt2_launch<2, 1>(p, epi, KZ, s);
+            if (mt == 3) return skinny_mt2_launch<3, 1>(p, epi, KZ, s);
         }
     }
 #define VOX_MTN(M_, N_) if (mt == M_ && ntw == N_) return skinny_mt_launch<M_, N_>(p, epi, s)
@@ -2121,21 +2042,10 @@ static hipError_t launch_q4_skinny_mt(const GemmParams& p_in, int epi, hipStream
     return hipErrorInvalidValue;
 }
 
-// split_pair with its two subtractions kept SCALAR: packed (v_pk_add_f32) they need (a, b) in a register pair -- for the slotted GEMM's staging that was a round of v_mov
-// from freshly loaded registers at the end of every K step, each behind an s_waitcnt on a load issued moments earlier
-__device__ __forceinline__ void split_pair_np(float a, float b, uint32_t& hi, uint32_t& lo) {
-    hi = cvt_pk_bf16(a, b);
-    float ra = a - __uint_as_float(hi << 16); asm("" : "+v"(ra));
-    const float rb = b - __uint_as_float(hi & 0xFFFF0000u);
-    lo = cvt_pk_bf16(ra, rb);
-}
-// acc += d * t as FOUR v_fma_f32 (VOX_GEMM_BIG_PKFMA: as the f32x4 elementwise fma, which hipcc lowers to two v_pk_fma_f32): beside MFMAs a packed f32 VALU instruction
+// acc += d * t as FOUR v_fma_f32, not as the f32x4 elementwise fma (which hipcc lowers to two v_pk_fma_f32): beside MFMAs a packed f32 VALU instruction
 // costs ~22 cycles more than the two plain FMAs it replaces (MI355X_MICROARCH.md, per-instruction constants), and plain v_fma_f32 is 2 cycles per wave on gfx950.  The empty
 // asm keeps the SLP vectoriser from re-packing the four scalars.
 __device__ __forceinline__ f32x4 scale_fma(float d, f32x4 t, f32x4 acc) {
-#ifdef VOX_GEMM_BIG_PKFMA
-    return __builtin_elementwise_fma((f32x4){d, d, d, d}, t, acc);
-#else
     // (d opaque as an f32 register: with the f16 -> f32 conversion visible hipcc fuses it into v_fma_mix_f32, which measured as the most expensive instruction of the K
     // step -- removing the 256 of them took a third off the kernel, profiles/r05_gemm_big_slots.txt)
     float dd = d; asm("" : "+v"(dd));
@@ -2143,7 +2053,6 @@ __device__ __forceinline__ f32x4 scale_fma(float d, f32x4 t, f32x4 acc) {
 #pragma unroll
     for (int r = 0; r < 4; r++) { float a = fmaf(dd, t[r], acc[r]); asm("" : "+v"(a)); o[r] = a; }
     return o;
-#endif
 }
 
 typedef __amdgpu_buffer_rsrc_t vsrd_t;
@@ -2162,7 +2071,7 @@ __device__ __forceinline__ uint2 vbuf_u2(vsrd_t sd, unsigned voff, unsigned soff
 //    fragments; nibbles -> bf16 by the bit trick 0x4300|q = 128+q, and the -136*sum(x) correction enters as the initial
 //    accumulator through one ones-MFMA pair per (m-tile, block), shared by the four n-tiles (uses the same hi+lo values,
 //    so the split error cancels exactly).
-//  * per (m-tile, n-tile, block): 2 MFMAs + 2 packed FMAs for the f16 block scale.
+//  * per (m-tile, n-tile, block): 2 MFMAs + 4 FMAs for the f16 block scale (scale_fma).
 // ------------------------------------------------------------------------------------------------
 template <int WGM, int WGN, int EPI>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void q4_gemm_big_kernel(const GemmParams p) {
@@ -2175,7 +2084,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void q
     const int wm = wave / WGN, wn = wave % WGN;
     const int m0 = blockIdx.y * BM, n0 = blockIdx.x * (64 * WGN);
     const int n_tiles = (N + 15) >> 4;
-#if !defined(VOX_GEMM_BIG_SERIAL)
     // Addressing = buffer loads: ONE 32-bit byte offset per lane for the A rows (wave w stages rows 16 w + li of the workgroup's 64, K slots 32 u + 4 g: pair (j = u, i = w)),
     // one for the weight tiles and one for their scales, the n-tile as a wave-uniform SGPR offset -- 64-bit per-lane pointers (4 rows + 4 tiles + 4 scale rows = 24 VGPRs)
     // left the pipelined loop below 10 VGPRs short.  Out-of-range tiles / K slots read zeros (buffer bounds), the epilogue's guards drop their results.
@@ -2199,169 +2107,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void q
     _Pragma("unroll") for (int t = 0; t < 4; t++) {                                                            \
         W_[t] = vbuf_u4(qsrd, qo + (unsigned)(Q_) * 1024u, (unsigned)(tile0 + t) * (unsigned)nq * 1024u);      \
         S_[t] = vbuf_u2(ssrd, so + (unsigned)(Q_) * 128u, (unsigned)(tile0 + t) * (unsigned)nq * 128u); }
-#else
-    // staging role: wave handles pairs {wave + 4u}; lane (g, li) stages row 16*i + li, K slots of group g
-    const float* xrow[NU];
-#pragma unroll
-    for (int u = 0; u < NU; u++) {
-        const int pair = wave + 4 * u, j = pair / MTB, i = pair % MTB;
-        xrow[u] = p.x + (size_t)min(m0 + 16 * i + li, M - 1) * p.x_stride + 32 * j + 4 * g;
-    }
-    // MFMA role
-    const uint4* wq[4]; const uint16_t* ws[4];
-#pragma unroll
-    for (int t = 0; t < 4; t++) {
-        const size_t T = (size_t)min((n0 >> 4) + wn * 4 + t, n_tiles - 1);
-        wq[t] = p.w.qt + T * nq * 64 + lane; ws[t] = p.w.st + (T * nq * 16 + li) * 4;
-    }
-    f32x4 acc[4][4];
-#pragma unroll
-    for (int t = 0; t < 4; t++)
-#pragma unroll
-        for (int i = 0; i < 4; i++) acc[t][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    float4 xa[NU], xb[NU]; uint4 bw[4], bwn[4]; uint2 bs[4], bsn[4];
-#define VOX_ALOAD(Q_)                                                                                          \
-    _Pragma("unroll") for (int u = 0; u < NU; u++) {                                                           \
-        xa[u] = *reinterpret_cast<const float4*>(xrow[u] + 128 * (Q_));                                        \
-        xb[u] = *reinterpret_cast<const float4*>(xrow[u] + 128 * (Q_) + 16); }
-#define VOX_BLOAD(W_, S_, Q_)                                                                                  \
-    _Pragma("unroll") for (int t = 0; t < 4; t++) {                                                            \
-        W_[t] = wq[t][(size_t)64 * (Q_)]; S_[t] = *reinterpret_cast<const uint2*>(ws[t] + 64 * (Q_)); }
-#endif
     VOX_ALOAD(0)
     VOX_BLOAD(bw, bs, 0)
     // B operand of the correction MFMA: bf16(-136) in every slot (0xC308, exact), so  sum_k x~_k * (-136)  comes out of the matrix core directly
     const bf16x8 m136 = as_bf16x8(make_uint4(0xC308C308u, 0xC308C308u, 0xC308C308u, 0xC308C308u));
-#if !defined(VOX_GEMM_BIG_SERIAL) && !defined(VOX_GEMM_BIG_SLOTS) && !defined(VOX_GEMM_BIG_SBUF) && !defined(VOX_ABL_BIG_NOCS) && !defined(VOX_ABL_BIG_NOFMA) && !defined(VOX_GEMM_BIG_OWNCS)
-#define VOX_BIG_SHARED_CS 1
     // round 6: the -136 sum(x) correction of a (row, block) is the same for all four waves (they share the workgroup's 64 rows) -- it is computed ONCE per workgroup, by the
     // wave that stages the fragment (what it has just split IS the MFMA A operand of (block u, m-tile wave) for its lane), and published with the planes: 8 correction MFMAs
-    // per wave and K step instead of 32 (160 -> 136 MFMAs per step; VOX_GEMM_BIG_OWNCS build: every wave its own, the round-5 form)
+    // per wave and K step instead of 32 (160 -> 136 MFMAs per step; in round 5 every wave computed its own)
     __shared__ __attribute__((aligned(16))) float s_bcs[2][4][MTB][4][4];      // [buffer][block j][m-tile][lane group g][4 rows]
-#define VOX_STAGE_CS(BUF_, U_, HI_, LO_) {                                                                     \
-        f32x4 c_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(HI_), m136, (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0); \
-        c_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(LO_), m136, c_, 0, 0, 0);                       \
-        if (li == 0) *reinterpret_cast<f32x4*>(&s_bcs[(BUF_) == blds ? 0 : 1][U_][wave][g][0]) = c_; }
-#else
-#define VOX_STAGE_CS(BUF_, U_, HI_, LO_)
-#endif
 #define VOX_STAGE(BUF_)                                                                                        \
     _Pragma("unroll") for (int u = 0; u < NU; u++) {     /* K-slot order of the bit-trick B fragment: {4g, 4g+2, 16+4g, 16+4g+2, 4g+1, 4g+3, 16+4g+1, 16+4g+3} */ \
         uint4 hi, lo;                                                                                          \
         split_pair(xa[u].x, xa[u].z, hi.x, lo.x); split_pair(xb[u].x, xb[u].z, hi.y, lo.y);                    \
         split_pair(xa[u].y, xa[u].w, hi.z, lo.z); split_pair(xb[u].y, xb[u].w, hi.w, lo.w);                    \
-        VOX_STAGE_CS(BUF_, u, hi, lo)                                                                          \
+        f32x4 c_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(hi), m136, (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0); \
+        c_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(lo), m136, c_, 0, 0, 0);                        \
+        if (li == 0) *reinterpret_cast<f32x4*>(&s_bcs[(BUF_) == blds ? 0 : 1][u][wave][g][0]) = c_;             \
         (BUF_)[(wave + 4 * u) * 64 + lane] = hi; (BUF_)[PLANE + (wave + 4 * u) * 64 + lane] = lo; }
-#if defined(VOX_GEMM_BIG_SLOTS)
-    // HAND-ORDERED K step (round 5): a wave issues in order, so its VALU work only runs under its own MFMAs if the two alternate in the instruction stream -- PMC on the
-    // loop-nest form (profiles/r05_pmc_gemm_big.txt): matrix pipe 44 % busy, VALU 47 % busy, next to no overlap (both workgroups of a CU drift into lock-step: all waves
-    // convert, then all multiply).  The K step is 16 groups (block jj, m-tile i) of ten MFMA SLOTS; every slot = one MFMA + the VALU / LDS / VMEM work that is independent
-    // of it, fenced by sched_barrier(0) so that hipcc keeps the order:
-    //   slots 0-3  hi MFMA of n-tile t                 + the PREVIOUS group's four scale FMAs of n-tile t (its lo MFMA is >= 4 slots old); slot 0: the next group's A fragments (ds_read)
-    //   slot  4    correction MFMA a of the NEXT group + one split_pair of the next K step's staging (double-buffered planes)
-    //   slots 5, 6 lo MFMA of n-tiles 0, 1             + (last m-tile of a block) the next block's nibbles -> bf16 IN PLACE: the fragment's last reader has just issued
-    //   slot  7    correction MFMA b of the next group + the staging's ds_writes and the A loads of the K step after next (their registers are free again)
-    //   slots 8, 9 lo MFMA of n-tiles 2, 3             + next block's n-tiles 2, 3
-    // Dependent MFMAs are >= 3 slots apart, every VALU reads MFMA results >= 4 slots old: no s_nop padding.
-    VOX_STAGE(blds)
-    __syncthreads();
-    { const int q1 = min(1, nq - 1); VOX_ALOAD(q1) VOX_BLOAD(bwn, bsn, q1) }
-    bf16x8 bf[4];
-#pragma unroll
-    for (int t = 0; t < 4; t++) bf[t] = as_bf16x8(q4_dword_to_bf16x8_biased(bw[t].x));
-    f32x4 T[2][4]; bf16x8 AH[2], AL[2]; f32x4 cs[2];
-#define VOX_SB() __builtin_amdgcn_sched_barrier(0)
-#if defined(VOX_ABL_S_NOMFMA)      /* timing-only ablations of the slotted loop (wrong results) */
-#define VOX_MF(A_, B_, C_) (C_)
-#else
-#define VOX_MF(A_, B_, C_) __builtin_amdgcn_mfma_f32_16x16x32_bf16(A_, B_, C_, 0, 0, 0)
-#endif
-#if defined(VOX_ABL_S_NOFMA)
-#define VOX_SF(D_, T_, ACC_) (T_)
-#else
-#define VOX_SF(D_, T_, ACC_) scale_fma(D_, T_, ACC_)
-#endif
-#if defined(VOX_ABL_S_NODS)
-#define VOX_LDSR(EXPR_) as_bf16x8(make_uint4(0x3f803f80u + lane, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u))
-#else
-#define VOX_LDSR(EXPR_) as_bf16x8(EXPR_)
-#endif
-#define VOX_DSC(JJ_, t_) f16_bits_to_f32((uint16_t)((((JJ_) & 2) ? BS[t_].y : BS[t_].x) >> (((JJ_) & 1) ? 16 : 0)))
-    // (the K loop runs two steps per trip with the roles of the two weight-register sets swapped: a rotating copy at the end of a step made hipcc land the next loads in
-    // temporaries and wait for ALL outstanding loads before the barrier)
-    auto kstep = [&](const int q, uint4 (&BW)[4], uint2 (&BS)[4], uint4 (&BN)[4]) __attribute__((always_inline)) {
-        uint4* const cur = blds + (q & 1) * (2 * PLANE);
-        uint4* const nxt = blds + ((q + 1) & 1) * (2 * PLANE);
-        const int q2 = min(q + 2, nq - 1);
-        AH[0] = VOX_LDSR(cur[(wm * 4) * 64 + lane]); AL[0] = VOX_LDSR(cur[PLANE + (wm * 4) * 64 + lane]);
-        AH[1] = VOX_LDSR(cur[(wm * 4 + 1) * 64 + lane]);
-        cs[0] = VOX_MF(AH[0], m136, ((f32x4){0.f, 0.f, 0.f, 0.f}));
-        cs[0] = VOX_MF(AL[0], m136, cs[0]);
-        uint4 shi, slo;
-        VOX_SB();
-#pragma unroll
-        for (int gI = 0; gI < 16; gI++) {
-            const int jj = gI >> 2, i = gI & 3, P = gI & 1, Q = P ^ 1, jp = (gI - 1) >> 2, ip = (gI - 1) & 3, u = gI >> 2, part = gI & 3;
-            // ---- slots 0-3
-#pragma unroll
-            for (int t = 0; t < 4; t++) {
-                T[P][t] = VOX_MF(AH[P], bf[t], cs[P]);
-                if (gI > 0) acc[t][ip] = VOX_SF(VOX_DSC(jp, t), T[Q][t], acc[t][ip]);
-                if (t == 0 && gI < 15) {      // the next group's lo fragment: its register's last reader (the previous group's lo MFMA of n-tile 3) has just issued; first use 7 slots away
-                    const int jn = (gI + 1) >> 2, in_ = (gI + 1) & 3;
-                    AL[Q] = VOX_LDSR(cur[PLANE + (jn * MTB + wm * 4 + in_) * 64 + lane]);
-                }
-                VOX_SB();
-            }
-            // ---- slot 4
-            if (gI < 15) cs[Q] = VOX_MF(AH[Q], m136, ((f32x4){0.f, 0.f, 0.f, 0.f}));
-            if (gI < 14) {      // the hi fragment of the group after next, into the register this group's hi MFMAs have just finished with: ten slots ahead of its first use
-                const int jn = (gI + 2) >> 2, in_ = (gI + 2) & 3;
-                AH[P] = VOX_LDSR(cur[(jn * MTB + wm * 4 + in_) * 64 + lane]);
-            }
-            if (part == 0) split_pair_np(xa[u].x, xa[u].z, shi.x, slo.x);
-            else if (part == 1) split_pair_np(xb[u].x, xb[u].z, shi.y, slo.y);
-            else if (part == 2) split_pair_np(xa[u].y, xa[u].w, shi.z, slo.z);
-            else split_pair_np(xb[u].y, xb[u].w, shi.w, slo.w);
-            VOX_SB();
-            // ---- slots 5, 6
-#pragma unroll
-            for (int t = 0; t < 2; t++) {
-                T[P][t] = VOX_MF(AL[P], bf[t], T[P][t]);
-                if (i == 3) bf[t] = as_bf16x8(q4_dword_to_bf16x8_biased(jj == 0 ? BW[t].y : jj == 1 ? BW[t].z : jj == 2 ? BW[t].w : BN[t].x));
-                VOX_SB();
-            }
-            // ---- slot 7
-            if (gI < 15) cs[Q] = VOX_MF(AL[Q], m136, cs[Q]);
-            if (part == 3) {
-                nxt[(wave + 4 * u) * 64 + lane] = shi; nxt[PLANE + (wave + 4 * u) * 64 + lane] = slo;
-                xa[u] = vbuf_f4(xsrd, xo + (unsigned)q2 * 512u + (unsigned)u * 128u, 0);
-                xb[u] = vbuf_f4(xsrd, xo + (unsigned)q2 * 512u + (unsigned)u * 128u + 64u, 0);
-            }
-            VOX_SB();
-            // ---- slots 8, 9
-#pragma unroll
-            for (int t = 2; t < 4; t++) {
-                T[P][t] = VOX_MF(AL[P], bf[t], T[P][t]);
-                if (i == 3) bf[t] = as_bf16x8(q4_dword_to_bf16x8_biased(jj == 0 ? BW[t].y : jj == 1 ? BW[t].z : jj == 2 ? BW[t].w : BN[t].x));
-                VOX_SB();
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < 4; t++) acc[t][3] = VOX_SF(VOX_DSC(3, t), T[1][t], acc[t][3]);      // the last group's scale FMAs
-        VOX_BLOAD(BW, BS, q2)                                     // this step's weight registers are free: the step after next lands in them
-        __syncthreads();                                          // every wave is done with this step's planes, the next step's are complete
-    };
-    for (int q = 0; q < nq; q += 2) {
-        kstep(q, bw, bs, bwn);
-        if (q + 1 < nq) kstep(q + 1, bwn, bsn, bw);
-    }
-#undef VOX_SB
-#undef VOX_DSC
-#undef VOX_MF
-#undef VOX_SF
-#undef VOX_LDSR
-#elif !defined(VOX_GEMM_BIG_SBUF)
     // double-buffered A planes (2 x 32 KB per workgroup, two workgroups per CU): K step q + 1 is staged into the other buffer BEFORE step q's MFMAs, one barrier per K step
     VOX_STAGE(blds)
     __syncthreads();
@@ -2372,17 +2134,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void q
         if (q + 1 < nq) { VOX_STAGE(nxt) }                      // (last read in step q - 1, behind that step's barrier)
         if (q > 0) { const int q1 = min(q + 1, nq - 1); VOX_BLOAD(bwn, bsn, q1) }
         { const int q2 = min(q + 2, nq - 1); VOX_ALOAD(q2) }
-#define blds cur
-#else
-    for (int q = 0; q < nq; q++) {
-        __syncthreads();                                          // every wave is done reading the previous K step
-        VOX_STAGE(blds)
-        __syncthreads();
-        { const int q1 = min(q + 1, nq - 1); VOX_ALOAD(q1) VOX_BLOAD(bwn, bsn, q1) }      // unconditional (clamped) prefetch
-        __builtin_amdgcn_sched_barrier(0);
-#endif
-#if !defined(VOX_GEMM_BIG_SLOTS)
-#if !defined(VOX_GEMM_BIG_SERIAL) && !defined(VOX_ABL_BIG_NOCS) && !defined(VOX_ABL_BIG_NOFMA)
         // SOFTWARE-PIPELINED over the 16 (block j, m-tile i) groups of a K step: a group's ten MFMAs (correction pair, then the four n-tiles' hi MFMAs, then their lo MFMAs --
         // four independent chains, so a lo MFMA finds its hi result ready) are issued BEFORE the previous group's eight scale FMAs.  Written group by group -- MFMA, dependent
         // MFMA, dependent FMA per n-tile -- hipcc kept that order and padded every FMA with s_nop 7: one chain in flight per wave, the matrix pipe 38 % busy (round-1 PMC).
@@ -2399,14 +2150,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void q
             }
 #pragma unroll
             for (int i = 0; i < 4; i++) {
-                const bf16x8 ah = as_bf16x8(blds[(jj * MTB + wm * 4 + i) * 64 + lane]);
-                const bf16x8 al = as_bf16x8(blds[PLANE + (jj * MTB + wm * 4 + i) * 64 + lane]);
-#ifdef VOX_BIG_SHARED_CS
+                const bf16x8 ah = as_bf16x8(cur[(jj * MTB + wm * 4 + i) * 64 + lane]);
+                const bf16x8 al = as_bf16x8(cur[PLANE + (jj * MTB + wm * 4 + i) * 64 + lane]);
                 const f32x4 cs = *reinterpret_cast<const f32x4*>(&s_bcs[q & 1][jj][wm * 4 + i][g][0]);
-#else
-                f32x4 cs = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, m136, (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-                cs = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, m136, cs, 0, 0, 0);
-#endif
                 f32x4 tn[4];
 #pragma unroll
                 for (int t = 0; t < 4; t++) tn[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bf[t], cs, 0, 0, 0);
@@ -2423,55 +2169,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void q
         }
 #pragma unroll
         for (int t = 0; t < 4; t++) acc[t][3] = scale_fma(dp[t], tp[t], acc[t][3]);
-#else
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            bf16x8 bf[4]; float d[4];
-#pragma unroll
-            for (int t = 0; t < 4; t++) {
-                const uint32_t w_ = j == 0 ? bw[t].x : j == 1 ? bw[t].y : j == 2 ? bw[t].z : bw[t].w;
-                bf[t] = as_bf16x8(q4_dword_to_bf16x8_biased(w_));
-                const uint32_t pr = (j & 2) ? bs[t].y : bs[t].x;
-                d[t] = f16_bits_to_f32((uint16_t)((j & 1) ? (pr >> 16) : (pr & 0xFFFFu)));
-            }
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const bf16x8 ah = as_bf16x8(blds[(j * MTB + wm * 4 + i) * 64 + lane]);
-                const bf16x8 al = as_bf16x8(blds[PLANE + (j * MTB + wm * 4 + i) * 64 + lane]);
-#ifdef VOX_ABL_BIG_NOCS      /* measurement build: results wrong, shows what the correction MFMAs cost */
-                f32x4 cs = (f32x4){0.f, 0.f, 0.f, 0.f};
-#else
-                f32x4 cs = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, m136, (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-                cs = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, m136, cs, 0, 0, 0);
-#endif
-#pragma unroll
-                for (int t = 0; t < 4; t++) {
-#ifdef VOX_ABL_BIG_NOFMA
-                    f32x4 tt = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bf[t], acc[t][i], 0, 0, 0);
-#else
-                    f32x4 tt = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bf[t], cs, 0, 0, 0);
-#endif
-                    tt = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bf[t], tt, 0, 0, 0);
-#ifdef VOX_ABL_BIG_NOFMA     /* measurement build: accumulate in the matrix core, no block scale */
-                    acc[t][i] = tt;
-#else
-                    acc[t][i] = scale_fma(d[t], tt, acc[t][i]);
-#endif
-                }
-            }
-        }
-#endif
 #pragma unroll
         for (int t = 0; t < 4; t++) { bw[t] = bwn[t]; bs[t] = bsn[t]; }
-#if !defined(VOX_GEMM_BIG_SBUF)
-#undef blds
         __syncthreads();                                          // every wave is done with this step's buffer, the next step's is complete
-#endif
     }
-#endif      // !VOX_GEMM_BIG_SLOTS
 #undef VOX_STAGE
-#undef VOX_STAGE_CS
-#undef VOX_BIG_SHARED_CS
 #undef VOX_ALOAD
 #undef VOX_BLOAD
 #pragma unroll
@@ -2510,11 +2212,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void q
 template <int WGM, int WGN>
 static hipError_t gemm_big_launch(const GemmParams& p, int epi, hipStream_t s) {
     dim3 grid((p.w.N + 64 * WGN - 1) / (64 * WGN), (p.M + 64 * WGM - 1) / (64 * WGM));
-#if !defined(VOX_GEMM_BIG_SBUF) || defined(VOX_GEMM_BIG_SLOTS)
     const size_t lds = (size_t)2 * 2 * 4 * (4 * WGM) * 64 * sizeof(uint4);      // two buffers of WGM * 32 KB
-#else
-    const size_t lds = (size_t)2 * 4 * (4 * WGM) * 64 * sizeof(uint4);      // WGM * 32 KB
-#endif
 #define VOX_E(E_) case E_: { auto kern = q4_gemm_big_kernel<WGM, WGN, E_>; static DevOnce done;          \
         hipError_t e = ensure_dyn_lds(kern, lds, &done); if (e != hipSuccess) return e;                       \
         kern<<<grid, dim3(256), lds, s>>>(p); break; }
@@ -2647,10 +2345,9 @@ static hipError_t skinny_launch_n(const GemmParams& p, int epi, int ks, hipStrea
         if (!TILED) return hipErrorInvalidValue;
         const bool pro = p.ssq_part != nullptr;
         if (pro && (p.n_part < 1 || p.n_part > 12 * (64 * ks / 16))) return hipErrorInvalidValue;     // partials per thread (q4_skinny_kernel PRO)
-        // straight-line in-order pipeline when every wave owns exactly STEPS K-steps (the decode-step shapes of the real model); VOX_SKINNY_NO_STEPS=1:
-        // the legacy loop (measurement knob)
+        // straight-line in-order pipeline when every wave owns exactly STEPS K-steps (the decode-step shapes of the real model); other shapes: the loop
         const int nq = p.w.nb / 4, per = nq % ks == 0 ? nq / ks : 0;
-        if (per && !env_int("VOX_SKINNY_NO_STEPS")) {
+        if (per) {
 #define VOX_ST(N_, E_, P_, S_) if (NTW == N_ && epi == E_ && (int)pro == P_ && per == S_) { \
             if (E_ == EPI_RESID_XF && (!p.xf_out || !p.xf_w || !p.ssq_out)) return hipErrorInvalidValue; \
             q4_skinny_kernel<N_, E_, 1, 1, P_, S_><<<grid, dim3(64 * ks), lds, s>>>(p); return hipGetLastError(); }
@@ -2691,16 +2388,12 @@ static hipError_t launch_q4_skinny(const GemmParams& p_in, int epi, hipStream_t 
     GemmParams p = p_in; p.tl_slot = tl_take_slot(2, epi, p.w.N, p.w.K);
     const int nq = p.w.nb / 4, tiles = (p.w.N + 15) / 16;
     // n-tiles per wave: as many as still leave >= 192 workgroups (N = 3072 has only 192 tiles); split-K over 4 waves, 8 when
-    // the grid is small and K is long enough.  VOX_SKINNY_NTW / VOX_SKINNY_KS are measurement knobs.
+    // the grid is small and K is long enough.
     int ntw = tiles >= 4 * 192 ? 4 : (tiles >= 2 * 192 ? 2 : 1);      // the x fragments are converted once per wave: more tiles per wave = less VALU
     int ks = nq >= 4 ? 4 : (nq >= 2 ? 2 : 1);
     if (tiles / ntw < 256 && nq >= 16) ks = 8;                        // profiles/r01_skinny_sweep.txt
-    { const int e = env_int("VOX_SKINNY_NTW"); if (e == 1 || e == 2 || e == 4) ntw = e; }
-    { const char* f = knob_str("VOX_SKINNY_FORCE");      // measurement knob "N:ntw:ks": override for one weight shape only
-      if (f) { int fn = 0, fw = 0, fk = 0; if (sscanf(f, "%d:%d:%d", &fn, &fw, &fk) == 3 && fn == p.w.N && (fw == 1 || fw == 2 || fw == 4) && (fk == 1 || fk == 2 || fk == 4 || fk == 8)) { ntw = fw; ks = fk; } } }
     if (epi == EPI_RESID_XF) ntw = 1;       // its partial sums of squares are per workgroup = per 16-column tile
-    { const int e = env_int("VOX_SKINNY_KS"); if (e == 1 || e == 2 || e == 4 || e == 8) ks = e; }
-    const bool tiled = p.w.qt && p.w.st && !env_int("VOX_SKINNY_NO_TILE");
+    const bool tiled = p.w.qt && p.w.st;
     // (three n-tiles per wave for w1|w3 -- 768 = 3 x 256 workgroups instead of 576 -- was a round-2 knob: no faster, 15 spilled VGPRs; removed in round 5)
     if (ntw == 4) return tiled ? skinny_launch_n<4, 1>(p, epi, ks, s) : skinny_launch_n<4, 0>(p, epi, ks, s);
     if (ntw == 2) return tiled ? skinny_launch_n<2, 1>(p, epi, ks, s) : skinny_launch_n<2, 0>(p, epi, ks, s);
@@ -2733,29 +2426,15 @@ static hipError_t gemm_launch_f(const GemmParams& p, int epi, hipStream_t s) {
         return hipGetLastError();
     }
     // tile choice from the round-1 sweep (profiles/r01_gemm_sweep.txt): 16-row tiles up to M = 48, 32-row tiles above;
-    // two n-tiles per wave only when that still leaves >= 256 workgroups.  VOX_GEMM_MT / VOX_GEMM_NT / VOX_GEMM_K32 are
-    // measurement knobs.
-    int mt = p.M <= 48 ? 1 : 2;
+    // two n-tiles per wave only when that still leaves >= 256 workgroups.
+    const int mt = p.M <= 48 ? 1 : 2;
     int nt = 2;
     auto wgs = [&](int mt_, int nt_) { return (long)((p.w.N + 64 * nt_ - 1) / (64 * nt_)) * ((p.M + 16 * mt_ - 1) / (16 * mt_)); };
     if (wgs(mt, 2) < 256) nt = 1;
-    { const int e = env_int("VOX_GEMM_MT"); if (e == 1 || e == 2) mt = e; }
-    { const int e = env_int("VOX_GEMM_NT"); if (e == 1 || e == 2) nt = e; }
-    if (env_int("VOX_GEMM_K32") || (!env_int("VOX_GEMM_MT") && p.M > 48 && env_int("VOX_GEMM_K32_BIG"))) {
-        dim3 grid((p.w.N + 63) / 64, (p.M + 63) / 64);
-        switch (epi) {
-        case EPI_STORE: q4_gemm_k32_kernel<EPI_STORE, FMT><<<grid, dim3(256), 0, s>>>(p); break;
-        case EPI_RESID: q4_gemm_k32_kernel<EPI_RESID, FMT><<<grid, dim3(256), 0, s>>>(p); break;
-        case EPI_GELU: q4_gemm_k32_kernel<EPI_GELU, FMT><<<grid, dim3(256), 0, s>>>(p); break;
-        case EPI_SWIGLU: q4_gemm_k32_kernel<EPI_SWIGLU, FMT><<<grid, dim3(256), 0, s>>>(p); break;
-        default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
     // 32-row tiles on the tile-ordered copy (no cross-lane transpose of the weight words): the single-clip encoder's wo / w2 (N = 1280, 800 rows)
-    // 8.79 -> 8.33 ms per clip with two n-tiles per wave at 250 workgroups (48-row tiles: 9.2-9.4 ms).  VOX_GEMM_NO_TB=1: the row-plane form.
-    if (FMT == WFMT_Q4_0 && p.w.qt && p.w.st && mt == 2 && !env_int("VOX_GEMM_NO_TB")) {
-        if (!env_int("VOX_GEMM_NT") && wgs(2, 2) >= 128) nt = 2;      // (threshold 64 / 128 / 200: 8.32 / 8.30 / 8.49 ms)
+    // 8.79 -> 8.33 ms per clip with two n-tiles per wave at 250 workgroups (48-row tiles: 9.2-9.4 ms).
+    if (FMT == WFMT_Q4_0 && p.w.qt && p.w.st && mt == 2) {
+        if (wgs(2, 2) >= 128) nt = 2;      // (threshold 64 / 128 / 200: 8.32 / 8.30 / 8.49 ms)
         return nt == 2 ? gemm_launch_mn<2, 2, WFMT_Q4_0, 1>(p, epi, s) : gemm_launch_mn<2, 1, WFMT_Q4_0, 1>(p, epi, s);
     }
 #define VOX_MN(M_, N_) if (mt == M_ && nt == N_) return gemm_launch_mn<M_, N_, FMT>(p, epi, s)
@@ -2779,7 +2458,7 @@ hipError_t launch_q4_gemm(const GemmParams& p, int epi, hipStream_t s, bool* fus
 static hipError_t launch_q4_gemm_epi(const GemmParams& p, int epi_in, hipStream_t s, bool* fused_rope) {
     int epi = epi_in == EPI_ROPE_ROWS ? EPI_STORE : epi_in;      // (EPI_ROPE_ROWS: only the large-M kernel below takes it; the others store, the caller ropes)
     if (p.w.K % 32 || p.M <= 0) return hipErrorInvalidValue;
-    if (p.ksplit > 1 && (p.M <= 48 || p.xf || p.w.nb % 4 || env_int("VOX_GEMM_K32") || p.w.fmt == WFMT_F32)) return hipErrorInvalidValue;      // split-K exists in q4_gemm_kernel only
+    if (p.ksplit > 1 && (p.M <= 48 || p.xf || p.w.nb % 4 || p.w.fmt == WFMT_F32)) return hipErrorInvalidValue;      // split-K exists in q4_gemm_kernel only
     if (p.w.fmt == WFMT_F32) {      // true-f32 dense weights: bf16 hi + lo planes on the matrix cores (3 MFMAs per product, f32-class like the conv stem)
         if (p.xf) return hipErrorInvalidValue;
         GemmParams v = p; v.w.fmt = WFMT_BF16X2; v.w.qt = nullptr; v.w.st = nullptr;
@@ -2791,20 +2470,17 @@ static hipError_t launch_q4_gemm_epi(const GemmParams& p, int epi_in, hipStream_
     if (p.M <= 16 && p.w.fmt == WFMT_Q4_0 && p.w.nb % 4 == 0 && !env_int("VOX_NO_SKINNY")) return launch_q4_skinny(p, epi, s);
     if (p.M > 16 && p.M <= 48 && p.w.fmt == WFMT_Q4_0 && p.w.qt && p.w.st && p.w.nb % 4 == 0 && (p.x_stride % 4) == 0 && (epi == EPI_STORE || epi == EPI_RESID || epi == EPI_GELU || epi == EPI_SWIGLU) &&
         !env_int("VOX_NO_SKINNY_MT")) {
-        // the 38-row decoder prefill: the weights are streamed ONCE for all m-tiles.  VOX_PREFILL_KERNEL: 0 auto, 1 = q4_skinny_mt_kernel (activation rows
-        // from L2 per wave), 2 = q4_gemm_kernel<3, NT, ., ., tile-ordered B> (48 x 64NT workgroup tile, activations staged + converted once per workgroup)
-        const int pk = env_int("VOX_PREFILL_KERNEL");
-        if (pk != 2) return launch_q4_skinny_mt(p, epi, s);      // measured (profiles/r02_prefill_kernels.txt): 5.69 ms (round 1) / 4.84 / 7.06 ms (the 48-row tile leaves 48..288 workgroups)
-        const long wg1 = (p.w.N + 63) / 64;
-        int nt = wg1 >= 512 ? 2 : 1; { const int e = env_int("VOX_GEMM_NT"); if (e == 1 || e == 2) nt = e; }
-        return nt == 2 ? gemm_launch_mn<3, 2, WFMT_Q4_0, 1>(p, epi, s) : gemm_launch_mn<3, 1, WFMT_Q4_0, 1>(p, epi, s);
+        // the 38-row decoder prefill: the weights are streamed ONCE for all m-tiles (q4_skinny_mt_kernel: activation rows from L2 per wave).  Measured against
+        // q4_gemm_kernel with a 48 x 64NT workgroup tile (activations staged + converted once per workgroup; it leaves 48..288 workgroups):
+        // 5.69 ms (round 1) / 4.84 / 7.06 ms (profiles/r02_prefill_kernels.txt)
+        return launch_q4_skinny_mt(p, epi, s);
     }
     if (p.w.fmt == WFMT_Q4_0 && p.w.qt && p.w.st && p.w.nb % 4 == 0 && (p.x_stride % 4) == 0) {
         // large M: 64 x 256 workgroup tiles (64 x 64 per wave) once they fill the chip -- 1.2-1.55x the 32 x 128 kernel
-        // (profiles/r01_gemm_sweep.txt).  VOX_GEMM_BIG: 0 auto, 1 force, -1 off (measurement knob)
+        // (profiles/r01_gemm_sweep.txt).  VOX_GEMM_BIG: 0 auto, 1 force, -1 off (cross-check knob: the tests compare the two kernels)
         const int big = env_int("VOX_GEMM_BIG");
         const long wg14 = (long)((p.w.N + 255) / 256) * ((p.M + 63) / 64);
-        int big_min = 200; { const int e = env_int("VOX_GEMM_BIG_MIN_WG"); if (e > 0) big_min = e; }      // measurement knob: workgroups of 64 x 256 from which the big kernel takes over
+        const int big_min = 200;      // workgroups of 64 x 256 from which the big kernel takes over
         // (the big kernel addresses its operands through 32-bit buffer offsets: activations, tiles and scales each below 4 GB -- beyond that the 32 x 128 kernel's 64-bit pointers serve)
         const bool fits32 = ((size_t)(p.M - 1) * p.x_stride + (size_t)p.w.K) * 4 < 0xFFFFFFF0ull && (size_t)((p.w.N + 15) / 16) * (p.w.nb / 4) * 1024 < 0xFFFFFFF0ull;
         // N % 256 == 0: the kernel hands its n-tile index to the buffer loads as the SGPR offset, which the hardware leaves out of the bounds check -- a partial last
@@ -3348,7 +3024,7 @@ __global__ __launch_bounds__(256) void attn_prefill_small_kernel(const AttnParam
 bool attn_prefill_small_ok(const AttnParams& p, int hd, int n_seq) {
     return hd == 128 && p.M >= 1 && p.M <= 48 && p.offset == 0 && p.kv_len == p.M && !p.seq_row_off && (p.window < 0 || p.window >= p.M) && (p.q_stride % 4) == 0 && (p.kv_row_stride % 4) == 0 &&
            n_seq == 1 /* stacked prefills (64 sequences x 10 row blocks x 32 heads of tiny workgroups) measured 1 % slower than the z-stacked MFMA kernel */ &&
-           !env_int("VOX_ATTN_NO_SMALL") && !env_int("VOX_ATTN_F32");
+           !env_int("VOX_ATTN_F32");
 }
 static hipError_t attn_prefill_small_launch(const AttnParams& p, hipStream_t s, int n_seq) {
     constexpr int HD = 128;
@@ -3800,7 +3476,7 @@ hipError_t launch_attn_wo(const AttnParams& p_in, const Q4W& wo, long long* acc,
 hipError_t launch_attn_decode(const AttnParams& p_in, int hd, int max_seq, hipStream_t s, int n_seq) {
     AttnParams p = p_in; p.tl_slot = tl_take_slot(1, 0, p.n_heads, hd);
     const size_t lds = (size_t)max_seq * sizeof(float);
-    if (hd == 128 && p.prefer_gqa && p.n_heads == 4 * p.n_kv_heads && p.kv_head_stride == max_seq * 128 && !env_int("VOX_ATTN_NO_GQA")) {
+    if (hd == 128 && p.prefer_gqa && p.n_heads == 4 * p.n_kv_heads && p.kv_head_stride == max_seq * 128) {
         auto kern = attn_decode_gqa_kernel<4>;      // many sequences: one workgroup per (KV head, sequence), K/V fetched once for its 4 query heads
         static DevOnce attr_done;
         hipError_t e = ensure_dyn_lds(kern, 4 * lds, &attr_done);
