@@ -360,6 +360,12 @@ int32_t vox_debug_reload_knobs(void);
  * out[0] short-sequence prefill, [1] MFMA prefill, [2] f32 VALU prefill (VOX_ATTN_F32), [3] single-query decode, [4] its speculative-row form (VOX_ATTN_SPEC),
  * [5] batched GQA decode, [6] fused attention + wo, [7] single-stream decode-engine launches (the whole step).  Entries past [7] are written as 0. */
 int32_t vox_debug_attn_launches(uint64_t* out, int32_t cap);
+/* Test hook: launches of the linear kernels enqueued by this process so far, by kernel form (host-side counts, as above; nothing is dispatched by them):
+ * out[0..2] Q4 GEMV with 1 / 2 / 4 rows per wave, [3] dense GEMV, [4] 5..16-row skinny GEMM, [5] 17..48-row skinny GEMM (one-dimensional form), [6] its split-K form,
+ * [7] rows -> XF tiles (helper of [5] / [6]), [8] split-K finishing sum (helper of [6]), [9..12] 16 x 64, 16 x 128, 32 x 64, 32 x 128 tile GEMM, [13] [14] the 32 x 64 and
+ * 32 x 128 tile GEMM on tile-ordered weights, [15] K % 128 != 0 GEMM, [16] 64 x 256 large-M GEMM, [17] its RoPE-epilogue form, [18] dense hi + lo GEMM, [19] wide
+ * batched-decode GEMM.  Entries past [19] are written as 0. */
+int32_t vox_debug_gemm_launches(uint64_t* out, int32_t cap);
 /* Test hook: launch `workgroups` x 1024-thread workgroups that spin for `micros` microseconds on a side stream of the context and return at once (vox_ctx_synchronize does
  * not wait for them; vox_ctx_destroy does).  Used to test the decode engines against a GPU that is not theirs alone (tests/test_gpu_fullsize.py). */
 int32_t vox_debug_occupy(vox_ctx* ctx, int32_t workgroups, int32_t micros);

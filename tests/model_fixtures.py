@@ -259,6 +259,23 @@ def launches_since(pkg, before):
     return {k: now[k] - before[k] for k in now if now[k] != before[k]}
 
 
+GEMM_FORMS = ("gemv_r1", "gemv_r2", "gemv_r4", "dense_gemv", "skinny", "skinny_mt", "skinny_mt2", "xf_rows", "splitk_finish", "tile_11", "tile_12", "tile_21", "tile_22",
+              "tile_21_tb", "tile_22_tb", "k32", "big", "big_rope", "dense2", "wide")
+
+
+def gemm_launches(pkg):
+    """Launches of the linear kernels of this process so far by kernel form (vox_debug_gemm_launches; the order of include/voxtral_hip.h)."""
+    import ctypes
+    out = (ctypes.c_uint64 * (len(GEMM_FORMS) + 1))()
+    assert pkg.lib().vox_debug_gemm_launches(out, len(GEMM_FORMS) + 1) == 0
+    return dict(zip(GEMM_FORMS, (int(x) for x in out)))
+
+
+def gemm_launches_since(pkg, before):
+    now = gemm_launches(pkg)
+    return {k: now[k] - before[k] for k in now if now[k] != before[k]}
+
+
 # vox_attention at hd 128 past the decoder window's first move: (M, kv_len, offset, window); every case runs at GQA 4:1 and 2:1
 EDGE_ATTN_CASES = [
     (1, 8193, 8192, DEC_WINDOW),         # the last position whose window has not moved

@@ -130,6 +130,12 @@ extern "C" int32_t vox_debug_attn_launches(uint64_t* out, int32_t cap) {
     for (int i = 0; i < cap; i++) out[i] = i < ATTN_FORM_COUNT ? (uint64_t)n[i] : 0;
     return VOX_OK;
 }
+extern "C" int32_t vox_debug_gemm_launches(uint64_t* out, int32_t cap) {
+    ARGCHK(out && cap > 0, "bad argument");
+    unsigned long long n[GEMM_FORM_COUNT]; gemm_form_counts(n);
+    for (int i = 0; i < cap; i++) out[i] = i < GEMM_FORM_COUNT ? (uint64_t)n[i] : 0;
+    return VOX_OK;
+}
 extern "C" int32_t vox_debug_occupy(vox_ctx* c, int32_t workgroups, int32_t micros) {
     ARGCHK(c && workgroups > 0 && workgroups <= 4096 && micros > 0 && micros <= 2000000, "bad argument"); VOXCHK(ctx_bind(c));
     if (!c->occupy_stream) HIPCHK(hipStreamCreateWithFlags(&c->occupy_stream, hipStreamNonBlocking));

@@ -170,6 +170,12 @@ enum AttnForm { ATTN_FORM_PREFILL_SMALL, ATTN_FORM_PREFILL_MFMA, ATTN_FORM_PREFI
                 ATTN_FORM_ENGINE, ATTN_FORM_COUNT };
 void attn_form_note(AttnForm f);
 void attn_form_counts(unsigned long long out[ATTN_FORM_COUNT]);
+// host-side launch counts of the linear kernels, by form (vox_debug_gemm_launches: tests assert which kernel a shape ran; counters only, nothing is dispatched by them).
+// TILE_mn = q4_gemm_kernel<MT m, NT n>, _TB its tile-ordered form; XF_ROWS / SPLITK_FINISH are the helper launches of the 17..48-row forms
+enum GemmForm { GEMM_FORM_GEMV_R1, GEMM_FORM_GEMV_R2, GEMM_FORM_GEMV_R4, GEMM_FORM_DENSE_GEMV, GEMM_FORM_SKINNY, GEMM_FORM_SKINNY_MT, GEMM_FORM_SKINNY_MT2, GEMM_FORM_XF_ROWS,
+                GEMM_FORM_SPLITK_FINISH, GEMM_FORM_TILE_11, GEMM_FORM_TILE_12, GEMM_FORM_TILE_21, GEMM_FORM_TILE_22, GEMM_FORM_TILE_21_TB, GEMM_FORM_TILE_22_TB, GEMM_FORM_K32,
+                GEMM_FORM_BIG, GEMM_FORM_BIG_ROPE, GEMM_FORM_DENSE2, GEMM_FORM_WIDE, GEMM_FORM_COUNT };
+void gemm_form_counts(unsigned long long out[GEMM_FORM_COUNT]);
 
 // gelu(conv1d k3 s2 p1): in [Cin][L] -> out; out_token_major: out[t][co] else out[co][t]
 hipError_t launch_conv1d_gelu(const float* in, int Cin, int L, const float* w, const float* b, int Cout, float* out,

@@ -66,6 +66,9 @@ void tl_slot_meta(int slot, int out[4]) { for (int i = 0; i < 4; i++) out[i] = (
 static std::atomic<unsigned long long> g_attn_forms[ATTN_FORM_COUNT];      // launches enqueued by the host (a captured graph's replays are not counted)
 void attn_form_note(AttnForm f) { g_attn_forms[f].fetch_add(1, std::memory_order_relaxed); }
 void attn_form_counts(unsigned long long out[ATTN_FORM_COUNT]) { for (int i = 0; i < ATTN_FORM_COUNT; i++) out[i] = g_attn_forms[i].load(std::memory_order_relaxed); }
+static std::atomic<unsigned long long> g_gemm_forms[GEMM_FORM_COUNT];      // as above, for the linear kernels: noted where the kernel is enqueued, after every argument check
+static void gemm_form_note(GemmForm f) { g_gemm_forms[f].fetch_add(1, std::memory_order_relaxed); }
+void gemm_form_counts(unsigned long long out[GEMM_FORM_COUNT]) { for (int i = 0; i < GEMM_FORM_COUNT; i++) out[i] = g_gemm_forms[i].load(std::memory_order_relaxed); }
 
 // ------------------------------------------------------------------------------------------------
 // device helpers
@@ -513,6 +516,7 @@ static hipError_t gemv_launch_w(const GemvParams& p, int ny, hipStream_t s) {
     static DevOnce attr_done;
     hipError_t e = ensure_dyn_lds(kern, lds, &attr_done);
     if (e != hipSuccess) return e;
+    gemm_form_note(R == 1 ? GEMM_FORM_GEMV_R1 : R == 2 ? GEMM_FORM_GEMV_R2 : GEMM_FORM_GEMV_R4);
     kern<<<grid, dim3(64 * NWV), lds, s>>>(p);
     return hipGetLastError();
 }
@@ -716,6 +720,7 @@ int dense_gemv_grid(int N) { const int wgs = (N / 2 + 3) / 4; return wgs > 2048 
 template <int PRO, int EPI>
 static hipError_t dense_launch_t(const GemvParams& p, int ny, hipStream_t s) {
     const size_t lds = (size_t)(p.w.K + 16) * sizeof(float);
+    gemm_form_note(GEMM_FORM_DENSE_GEMV);
     if (p.w.fmt == WFMT_F32) dense_gemv_kernel<PRO, EPI, 1><<<dim3(dense_gemv_grid(p.w.N), ny), dim3(256), lds, s>>>(p);
     else dense_gemv_kernel<PRO, EPI, 0><<<dim3(dense_gemv_grid(p.w.N), ny), dim3(256), lds, s>>>(p);
     return hipGetLastError();
@@ -1599,6 +1604,7 @@ static hipError_t wide_launch(const GemmParams& p, const WidePlan& pl, hipStream
     const size_t lds = (size_t)2 * MT * 8 * 64 * sizeof(uint4);
     auto kern = q4_wide_kernel<MT, NTW, DIRECT>; static DevOnce done;
     hipError_t e = ensure_dyn_lds(kern, lds, &done); if (e != hipSuccess) return e;
+    gemm_form_note(GEMM_FORM_WIDE);
     kern<<<grid, dim3(256), lds, s>>>(p, pl.sps, p.kz_scratch);
     return hipGetLastError();
 }
@@ -1890,9 +1896,12 @@ template <int MT, int NTW>
 static hipError_t skinny_mt2_launch(const GemmParams& p_in, int epi, int KZ, hipStream_t s) {
     GemmParams p = p_in; p.ksplit = KZ; p.out = p_in.kz_scratch;
     const int n_tiles = (p.w.N + 15) / 16;
+    if (epi != EPI_STORE && epi != EPI_RESID && epi != EPI_GELU && epi != EPI_SWIGLU) return hipErrorInvalidValue;
+    gemm_form_note(GEMM_FORM_SKINNY_MT2);
     q4_skinny_mt2_kernel<MT, NTW><<<dim3((n_tiles + 4 * NTW - 1) / (4 * NTW), KZ), dim3(256), (size_t)2 * MT * 8 * 64 * 16, s>>>(p);
     hipError_t e = hipGetLastError(); if (e != hipSuccess) return e;
     const long total = (long)p.M * p.w.N; const int blocks = (int)std::min<long>((total + 255) / 256, 2048);
+    gemm_form_note(GEMM_FORM_SPLITK_FINISH);
     switch (epi) {
     case EPI_STORE: splitk_finish_kernel<EPI_STORE><<<blocks, 256, 0, s>>>(p_in.kz_scratch, KZ, p.M, p.w.N, p.bias, nullptr, 0, p_in.out, p_in.out_stride); break;
     case EPI_RESID: splitk_finish_kernel<EPI_RESID><<<blocks, 256, 0, s>>>(p_in.kz_scratch, KZ, p.M, p.w.N, p.bias, p.resid, p.resid_stride, p_in.out, p_in.out_stride); break;
@@ -1906,6 +1915,8 @@ template <int MT, int NTW>
 static hipError_t skinny_mt_launch(const GemmParams& p, int epi, hipStream_t s) {
     dim3 grid((p.w.N + 16 * NTW - 1) / (16 * NTW));
     const size_t lds = (size_t)4 * MT * NTW * 64 * 4 * sizeof(float);
+    if (epi != EPI_STORE && epi != EPI_RESID && epi != EPI_GELU && epi != EPI_SWIGLU) return hipErrorInvalidValue;
+    gemm_form_note(GEMM_FORM_SKINNY_MT);
     if (p.xf) {
         switch (epi) {
         case EPI_STORE: q4_skinny_mt_kernel<MT, NTW, EPI_STORE, true><<<grid, dim3(256), lds, s>>>(p); break;
@@ -1940,6 +1951,7 @@ int q4_skinny_mt2_plan(const Q4W& w, int M) {      // K slices the 2-D kernel wo
 hipError_t launch_xf_rows(const float* x, int x_stride, int M, int K, uint16_t* xf, hipStream_t s) {      // f32 rows -> ceil(M / 16) XF tiles
     const int mt = (M + 15) / 16; const long total = (long)mt * 16 * (K >> 2);
     if (K % 128) return hipErrorInvalidValue;
+    gemm_form_note(GEMM_FORM_XF_ROWS);
     xf_rows_kernel<<<dim3((unsigned)std::min<long>((total + 255) / 256, 1024)), dim3(256), 0, s>>>(x, x_stride, M, K, xf, mt);
     return hipGetLastError();
 }
@@ -1952,6 +1964,7 @@ hipError_t launch_q4_skinny_mt2_planes(const GemmParams& p_in, int KZ, hipStream
           GemmParams q = p_in; q.wide_mt = mt; q.wide_rows = p.M; q.M = 16 * mt; q.xf_gstride = (long)2 * (p.w.nb / 4) * 256;
           return launch_q4_wide(q, EPI_ROPE_KV | 0x100, s);      // the GEMM launch alone: the caller's finishing kernels read the planes
       } }
+    if (mt == 2 || mt == 3) gemm_form_note(GEMM_FORM_SKINNY_MT2);
     if (mt == 2) q4_skinny_mt2_kernel<2, 1><<<dim3((n_tiles + 3) / 4, KZ), dim3(256), (size_t)2 * 2 * 8 * 64 * 16, s>>>(p);
     else if (mt == 3) q4_skinny_mt2_kernel<3, 1><<<dim3((n_tiles + 3) / 4, KZ), dim3(256), (size_t)2 * 3 * 8 * 64 * 16, s>>>(p);
     else return hipErrorInvalidValue;
@@ -2012,6 +2025,7 @@ hipError_t launch_splitk_finish_rope_kv(const float* planes, int KZ, int M, int 
 }
 hipError_t launch_splitk_finish_resid(const float* planes, int KZ, int M, int N, float* x, int x_stride, hipStream_t s) {      // x += sum of the planes
     const long total = (long)M * N;
+    gemm_form_note(GEMM_FORM_SPLITK_FINISH);
     splitk_finish_kernel<EPI_RESID><<<(int)std::min<long>((total + 255) / 256, 2048), 256, 0, s>>>(planes, KZ, M, N, nullptr, x, x_stride, x, x_stride);
     return hipGetLastError();
 }
@@ -2022,6 +2036,7 @@ static hipError_t launch_q4_skinny_mt(const GemmParams& p_in, int epi, hipStream
     if (!p.xf && p.xf_scratch && p.xf_scratch_bytes >= (size_t)mt * p.w.K * 64 && p.w.K % 128 == 0) {
         // rows -> XF tiles once per GEMM (a ~3 us launch), then the conversion-free kernel
         const long total = (long)mt * 16 * (p.w.K >> 2);
+        gemm_form_note(GEMM_FORM_XF_ROWS);
         xf_rows_kernel<<<dim3((unsigned)std::min<long>((total + 255) / 256, 1024)), dim3(256), 0, s>>>(p.x, p.x_stride, p.M, p.w.K, p.xf_scratch, mt);
         p.xf = reinterpret_cast<const uint4*>(p.xf_scratch);
     }
@@ -2215,7 +2230,7 @@ static hipError_t gemm_big_launch(const GemmParams& p, int epi, hipStream_t s) {
     const size_t lds = (size_t)2 * 2 * 4 * (4 * WGM) * 64 * sizeof(uint4);      // two buffers of WGM * 32 KB
 #define VOX_E(E_) case E_: { auto kern = q4_gemm_big_kernel<WGM, WGN, E_>; static DevOnce done;          \
         hipError_t e = ensure_dyn_lds(kern, lds, &done); if (e != hipSuccess) return e;                       \
-        kern<<<grid, dim3(256), lds, s>>>(p); break; }
+        gemm_form_note(E_ == EPI_ROPE_ROWS ? GEMM_FORM_BIG_ROPE : GEMM_FORM_BIG); kern<<<grid, dim3(256), lds, s>>>(p); break; }
     switch (epi) { VOX_E(EPI_STORE) VOX_E(EPI_RESID) VOX_E(EPI_GELU) VOX_E(EPI_SWIGLU) VOX_E(EPI_ROPE_ROWS) default: return hipErrorInvalidValue; }
 #undef VOX_E
     return hipGetLastError();
@@ -2226,11 +2241,13 @@ static hipError_t gemm_big_launch(const GemmParams& p, int epi, hipStream_t s) {
 // three MFMAs per product (ah*bh + al*bh + ah*bl) and the accumulation over all of K stays inside the matrix core (no scales, so no
 // per-block VALU at all).  Workgroup = 64 rows x (64*NTW) columns, wave = 64 x (16*NTW); K step 128; A rows may overlap (x_stride <
 // K: row t of a stride-2 kernel-3 convolution is the contiguous window [2t-1, 2t+1] of the token-major, zero-padded input).
-template <int NTW, int EPI>
+// KTAIL (K % 128 != 0, K % 32 == 0; no model shape, the operator entry only): the last K step holds 1..3 of its four 32-wide blocks; the missing blocks' loads are
+// redirected to the step's first block (in range) and their A fragments are written to LDS as zeros, so they add exact zeros to every sum.
+template <int NTW, int EPI, bool KTAIL = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void dense2_gemm_kernel(const GemmParams p) {
     extern __shared__ __attribute__((aligned(16))) uint4 dlds[];    // [hi/lo][j 4][4 m-tiles][64]
     constexpr int PLANE = 4 * 4 * 64;
-    const int N = p.w.N, K = p.w.K, M = p.M, nq = K >> 7;
+    const int N = p.w.N, K = p.w.K, M = p.M, nq = KTAIL ? (K + 127) >> 7 : K >> 7;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, li = lane & 15;
     const int m0 = blockIdx.y * 64, n0 = blockIdx.x * (64 * NTW);
     const float* xrow[4];
@@ -2252,12 +2269,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void d
         for (int i = 0; i < 4; i++) acc[t][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
     float4 xa[4], xb[4]; uint4 bh[NTW][4], bl[NTW][4], bhn[NTW][4], bln[NTW][4];
 #define VOX_ALOAD(Q_)                                                                                          \
-    _Pragma("unroll") for (int u = 0; u < 4; u++) {                                                            \
-        xa[u] = *reinterpret_cast<const float4*>(xrow[u] + 128 * (Q_));                                        \
-        xb[u] = *reinterpret_cast<const float4*>(xrow[u] + 128 * (Q_) + 4); }
+    _Pragma("unroll") for (int u = 0; u < 4; u++) {   /* (block j of the pair wave + 4u is u) */             \
+        const int ko = 128 * (Q_) - ((KTAIL && 128 * (Q_) + 32 * u >= K) ? 32 * u : 0);                       \
+        xa[u] = *reinterpret_cast<const float4*>(xrow[u] + ko);                                                \
+        xb[u] = *reinterpret_cast<const float4*>(xrow[u] + ko + 4); }
 #define VOX_BLOAD(H_, L_, Q_)                                                                                  \
     _Pragma("unroll") for (int t = 0; t < NTW; t++)                                                            \
-        _Pragma("unroll") for (int j = 0; j < 4; j++) { H_[t][j] = wh[t][(Q_) * 16 + j * 4]; L_[t][j] = wl[t][(Q_) * 16 + j * 4]; }
+        _Pragma("unroll") for (int j = 0; j < 4; j++) { const int jo = (KTAIL && 128 * (Q_) + 32 * j >= K) ? 0 : j * 4;   \
+            H_[t][j] = wh[t][(Q_) * 16 + jo]; L_[t][j] = wl[t][(Q_) * 16 + jo]; }
     VOX_ALOAD(0)
     VOX_BLOAD(bh, bl, 0)
     for (int q = 0; q < nq; q++) {
@@ -2265,6 +2284,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void d
 #pragma unroll
         for (int u = 0; u < 4; u++) {
             uint4 hi, lo; split_bf16x8(xa[u], xb[u], hi, lo);
+            if (KTAIL && 128 * q + 32 * u >= K) hi = lo = make_uint4(0u, 0u, 0u, 0u);
             dlds[(wave + 4 * u) * 64 + lane] = hi; dlds[PLANE + (wave + 4 * u) * 64 + lane] = lo;
         }
         __syncthreads();
@@ -2312,14 +2332,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void d
     }
 }
 hipError_t launch_dense2_gemm(const GemmParams& p, int epi, hipStream_t s) {
-    if (p.w.fmt != WFMT_BF16X2 || p.w.K % 128 || (p.x_stride % 4) || p.M <= 0) return hipErrorInvalidValue;
+    if (p.w.fmt != WFMT_BF16X2 || p.w.K % 32 || (p.x_stride % 4) || p.M <= 0) return hipErrorInvalidValue;
+    if (p.w.K % 128) {      // partial last K step: the KTAIL form, 64 x 64 workgroups
+        dim3 tgrid((p.w.N + 63) / 64, (p.M + 63) / 64);
+        switch (epi) {
+#define VOX_D2T(E_) case E_: gemm_form_note(GEMM_FORM_DENSE2); dense2_gemm_kernel<1, E_, true><<<tgrid, dim3(256), (size_t)2 * 4 * 4 * 64 * sizeof(uint4), s>>>(p); break;
+        VOX_D2T(EPI_STORE) VOX_D2T(EPI_GELU) VOX_D2T(EPI_RESID) VOX_D2T(EPI_SWIGLU) default: return hipErrorInvalidValue;
+#undef VOX_D2T
+        }
+        return hipGetLastError();
+    }
     // wide form = 64 x 128 workgroups (two n-tiles per wave).  Four n-tiles per wave (64 x 256) kept the current AND the prefetched hi + lo B fragments of four tiles in
     // registers -- 256 VGPRs for B alone: 187-212 spilled VGPRs, ~700 B of scratch per lane (round-4 disassembly); two tiles fit (tools/kernel_resources.py: no scratch).
     const long wg2 = (long)((p.w.N + 127) / 128) * ((p.M + 63) / 64);
     const size_t lds = (size_t)2 * 4 * 4 * 64 * sizeof(uint4);      // 32 KB
     const bool wide = wg2 >= 400;
     dim3 grid(wide ? (p.w.N + 127) / 128 : (p.w.N + 63) / 64, (p.M + 63) / 64);
-#define VOX_D2(E_) case E_: if (wide) dense2_gemm_kernel<2, E_><<<grid, dim3(256), lds, s>>>(p); else dense2_gemm_kernel<1, E_><<<grid, dim3(256), lds, s>>>(p); break;
+#define VOX_D2(E_) case E_: gemm_form_note(GEMM_FORM_DENSE2); if (wide) dense2_gemm_kernel<2, E_><<<grid, dim3(256), lds, s>>>(p); else dense2_gemm_kernel<1, E_><<<grid, dim3(256), lds, s>>>(p); break;
     switch (epi) { VOX_D2(EPI_STORE) VOX_D2(EPI_GELU) VOX_D2(EPI_RESID) VOX_D2(EPI_SWIGLU) default: return hipErrorInvalidValue; }
 #undef VOX_D2
     return hipGetLastError();
@@ -2395,9 +2424,12 @@ static hipError_t launch_q4_skinny(const GemmParams& p_in, int epi, hipStream_t 
     if (epi == EPI_RESID_XF) ntw = 1;       // its partial sums of squares are per workgroup = per 16-column tile
     const bool tiled = p.w.qt && p.w.st;
     // (three n-tiles per wave for w1|w3 -- 768 = 3 x 256 workgroups instead of 576 -- was a round-2 knob: no faster, 15 spilled VGPRs; removed in round 5)
-    if (ntw == 4) return tiled ? skinny_launch_n<4, 1>(p, epi, ks, s) : skinny_launch_n<4, 0>(p, epi, ks, s);
-    if (ntw == 2) return tiled ? skinny_launch_n<2, 1>(p, epi, ks, s) : skinny_launch_n<2, 0>(p, epi, ks, s);
-    return tiled ? skinny_launch_n<1, 1>(p, epi, ks, s) : skinny_launch_n<1, 0>(p, epi, ks, s);
+    hipError_t e;
+    if (ntw == 4) e = tiled ? skinny_launch_n<4, 1>(p, epi, ks, s) : skinny_launch_n<4, 0>(p, epi, ks, s);
+    else if (ntw == 2) e = tiled ? skinny_launch_n<2, 1>(p, epi, ks, s) : skinny_launch_n<2, 0>(p, epi, ks, s);
+    else e = tiled ? skinny_launch_n<1, 1>(p, epi, ks, s) : skinny_launch_n<1, 0>(p, epi, ks, s);
+    if (e == hipSuccess) gemm_form_note(GEMM_FORM_SKINNY);      // (skinny_launch_n returns an error only where it enqueued nothing)
+    return e;
 }
 
 template <int MT, int NT, int FMT, int TB = 0>
@@ -2407,6 +2439,7 @@ static hipError_t gemm_launch_mn(const GemmParams& p, int epi, hipStream_t s) {
     const size_t lds = (size_t)2 * 2 * 4 * MT * 64 * sizeof(uint4);     // MT * 16 KB
 #define VOX_E(E_) case E_: { auto kern = q4_gemm_kernel<MT, NT, E_, FMT, TB>; static DevOnce done;      \
         hipError_t e = ensure_dyn_lds(kern, lds, &done); if (e != hipSuccess) return e;                       \
+        gemm_form_note(TB ? (NT == 2 ? GEMM_FORM_TILE_22_TB : GEMM_FORM_TILE_21_TB) : MT == 1 ? (NT == 2 ? GEMM_FORM_TILE_12 : GEMM_FORM_TILE_11) : (NT == 2 ? GEMM_FORM_TILE_22 : GEMM_FORM_TILE_21)); \
         kern<<<grid, dim3(256), lds, s>>>(p); break; }
     switch (epi) { VOX_E(EPI_STORE) VOX_E(EPI_RESID) VOX_E(EPI_GELU) VOX_E(EPI_SWIGLU) default: return hipErrorInvalidValue; }
 #undef VOX_E
@@ -2416,6 +2449,8 @@ template <int FMT>
 static hipError_t gemm_launch_f(const GemmParams& p, int epi, hipStream_t s) {
     if (p.w.nb % 4) {   // K % 128 != 0: K-32 kernel
         dim3 grid((p.w.N + 63) / 64, (p.M + 63) / 64);
+        if (epi != EPI_STORE && epi != EPI_RESID && epi != EPI_GELU && epi != EPI_SWIGLU) return hipErrorInvalidValue;
+        gemm_form_note(GEMM_FORM_K32);
         switch (epi) {
         case EPI_STORE: q4_gemm_k32_kernel<EPI_STORE, FMT><<<grid, dim3(256), 0, s>>>(p); break;
         case EPI_RESID: q4_gemm_k32_kernel<EPI_RESID, FMT><<<grid, dim3(256), 0, s>>>(p); break;

@@ -224,7 +224,14 @@ def q4_matmul(x, weights: Q4Tensor):
 
 def linear_forward(weights: Q4Tensor, x, bias=None, epilogue=0):
     """Linear::forward with a fused epilogue (0 none, 1 GELU, 2 SwiGLU over interleaved gate / up rows -> N / 2 columns); x [B, M, K]."""
-    x = _f32(x); b, m, k = x.shape; n = weights.shape()[0]
+    x = _f32(x)
+    if x.ndim != 3:
+        raise VoxError(1, f"linear_forward expects a 3-D input, got {x.ndim}-D")
+    b, m, k = x.shape; n, kw = weights.shape()
+    if k != kw:      # the C entry takes K from the tensor: a shorter row would be read past its end
+        raise VoxError(1, f"linear_forward: input K={k} != weight K={kw}")
+    if bias is not None and np.size(bias) != n:
+        raise VoxError(1, f"linear_forward: bias has {np.size(bias)} elements, weight N={n}")
     out = np.empty((b, m, n // 2 if epilogue == 2 else n), dtype=np.float32)
     bb = None if bias is None else _f32(bias)
     check(lib().vox_linear_forward_ex(weights.ctx.h, weights.h, None if bb is None else _ptr(bb), _ptr(x), b, m, _ptr(out), epilogue, 0))
