@@ -227,6 +227,15 @@ int32_t vox_model_set_t_embed(vox_model* m, const float* t_embed_host);
  * the utterance is decoded again on the per-operator launches (a warning on stderr), the engine is re-armed for the next utterance and switched off after three such
  * strikes.  Environment VOX_ENGINE=0 sets the default to off at load time. */
 int32_t vox_model_set_decode_engine(vox_model* m, int32_t on, int32_t* active_or_null);
+/* Prefix state of vox_transcribe_audio (default on).  That entry pads every utterance on the left with the same silence (vox_pad_cfg_voxtral), so the first encoder rows
+ * and -- the decoder's prefix tokens being fixed -- the first decoder positions are the same for every utterance: functions of the weights (and of t_embed) alone.  The
+ * model computes them once from a silent mel (at its first vox_transcribe_audio call, or here when a t_embed is already set; again for the decoder part when t_embed
+ * changes) and afterwards runs the encoder layers over the remaining rows only and one ordinary decode step in place of the 38-token prefill.  Results do not depend on
+ * which call came first; they agree with the full computation to summation-order noise.  Entries that take a caller's mel or embeddings, the logits tap and the batch
+ * entries always run the full computation.  on = 0: the full computation everywhere (the state is freed); on < 0: query only.  *active_or_null: will it be used. */
+int32_t vox_model_set_prefix_cache(vox_model* m, int32_t on, int32_t* active_or_null);
+/* out = { state built (0 / 1), encoder rows held per layer, decoder positions held, device bytes held }; rows / positions are 0 for a geometry without a prefix. */
+int32_t vox_model_prefix_info(const vox_model* m, int32_t out[4]);
 /* Batched decode loop of vox_transcribe_batch (BASELINE configs[3] / [4]; the reference's model.rs:938-960 is batch-1): the 26 decoder layers of a step run as ONE
  * launch of the batched decode-layer engine (same eligibility as above) whenever one or two 16-row groups are active -- a batch of n <= 16 rows (one group per
  * launch), and in a wider batch's continuous decode the steps with one or two active slot groups (TWO groups per launch: group B's phase runs while group A's

@@ -767,7 +767,23 @@ static void cache_unregister(const vox_cache* k) { std::lock_guard<std::mutex> l
 static bool cache_alive(const vox_cache* k, uint64_t gen) { std::lock_guard<std::mutex> l(g_cache_mu); auto it = g_cache_live.find(k); return it != g_cache_live.end() && it->second == gen; }
 
 struct TensorMeta { std::vector<uint64_t> shape; int dtype = 0; uint64_t nbytes = 0; };
+// What vox_transcribe_audio computes identically for EVERY utterance, held once per model.  The library itself pads every utterance on the left
+// with silence (vox_pad_cfg_voxtral), the log-mel of silence is the constant floor, the conv stem is local, the encoder attention causal, and the decoder's prefix tokens
+// are fixed: encoder rows [0, RC) and decoder positions [0, PC) are functions of the weights (and of t_embed) alone.  Built from a silent mel, never from a caller's clip.
+struct PrefixState {
+    bool on = true;                        // vox_model_set_prefix_cache
+    int RC = 0, PC = 0;                    // encoder rows / decoder positions held; 0: this geometry has no prefix (prefix_bounds)
+    float* enc_kv = nullptr;               // [enc_layers][RC][k row | v row]: the RoPE'd keys and the values of rows 0 .. RC-1 of every encoder layer
+    float* audio = nullptr;                // [PC][dec_dim]: adapter rows 0 .. PC-1
+    float *dec_k = nullptr, *dec_v = nullptr;      // [dec_layers * dec_kv_heads][PC][head_dim]: decoder cache rows 0 .. PC-1 for the t_embed below
+    bool enc_built = false, dec_built = false;
+    std::vector<float> t_embed;            // the t_embed the decoder part was built with
+    float* capture = nullptr; int capture_rows = 0;      // while the encoder part is being built: encode_batch_dev stores every layer's k | v rows here
+    uint64_t enc_bytes = 0, dec_bytes = 0;
+};
+static const int VOX_PREFIX_TOKENS = 38, VOX_TOK_BOS = 1, VOX_TOK_STREAMING_PAD = 32;      // the decoder's fixed prefix: BOS + 37 x STREAMING_PAD (gguf/model.rs:891-892)
 struct vox_model {
+    PrefixState pfx;
     vox_ctx* ctx = nullptr; vox_model_cfg cfg{};
     std::vector<vox_model*> twins;      // vox_model_set_sessions: replicas on hidden contexts of the same device (owned: freed with the model)
     std::map<std::string, TensorMeta> manifest; bool is_q4 = false;      // name -> shape / dtype of every tensor the loader looked up (vox_model_replicate lays a second arena out from it, without the file)
@@ -1213,6 +1229,11 @@ static void graphs_destroy(vox_model* m) {
         if (m->graph[i]) { (void)hipGraphDestroy(m->graph[i]); m->graph[i] = nullptr; }
     }
 }
+static void prefix_release(vox_model* m) {
+    PrefixState& p = m->pfx;
+    for (float** q : {&p.enc_kv, &p.audio, &p.dec_k, &p.dec_v}) { if (*q) (void)hipFree(*q); *q = nullptr; }
+    p.enc_built = p.dec_built = false; p.enc_bytes = p.dec_bytes = 0; p.t_embed.clear();
+}
 static void model_release(vox_model* m) {
     if (!m) return;
     for (vox_model* t : m->twins) { vox_ctx* tc = t->ctx; model_release(t); (void)vox_ctx_destroy(tc); }
@@ -1225,6 +1246,7 @@ static void model_release(vox_model* m) {
                     (void*)m->d_h, (void*)m->d_h2, (void*)m->d_wo_acc, (void*)m->d_q, (void*)m->d_att, (void*)m->d_act, (void*)m->d_logits, (void*)m->d_part_val, (void*)m->d_part_idx, (void*)m->d_seq_len, (void*)m->d_seq_off, (void*)m->d_row_pos, (void*)m->d_prefix, (void*)m->enc_cos_s, (void*)m->enc_sin_s, (void*)m->eng_stream, (void*)m->eng_wob, (void*)m->eng_state, (void*)m->eng_tab, (void*)m->engb_state[0], (void*)m->engb_state[1], (void*)m->engb_state[2], (void*)m->engb_state[3],
                     (void*)m->engb_tab[0], (void*)m->engb_tab[1], (void*)m->engb_tab[2], (void*)m->engb_tab[3], (void*)m->pw_x, (void*)m->pw_hidden, (void*)m->pw_logits, (void*)m->pw_part_val, (void*)m->pw_part_idx, (void*)m->pw_ids, (void*)m->pw_zero, (void*)m->pw_tab})
         if (p) (void)hipFree(p);
+    prefix_release(m);
     if (m->pw_err_pin) (void)hipHostFree(m->pw_err_pin);
     if (m->tap.out) (void)hipFree(m->tap.out);
     if (m->tap.rows) (void)hipFree(m->tap.rows);
@@ -1325,6 +1347,7 @@ extern "C" int32_t vox_model_arena_finalize(vox_model* m) {
     for (Q4W* w : m->tiled) HIPCHK(launch_q4_tile_build(*w, const_cast<uint4*>(w->qt), const_cast<uint16_t*>(w->st), m->ctx->stream));
     HIPCHK(hipStreamSynchronize(m->ctx->stream));
     m->eng_ready = false; m->eng_tab_cache = nullptr;      // a stream packed from an earlier arena content is stale
+    prefix_release(m);                                     // ... and so is a prefix state computed from it
     if (m->eng_wob) { HIPCHK(hipStreamSynchronize(m->ctx->stream)); (void)hipFree(m->eng_wob); m->eng_wob = nullptr; }
     graphs_destroy(m);
     return VOX_OK;
@@ -1367,6 +1390,7 @@ extern "C" int32_t vox_model_set_t_embed(vox_model* m, const float* t_embed) {
     }
     HIPCHK(hipStreamSynchronize(cx->stream));
     m->t_embed_host.assign(t_embed, t_embed + c.dec_dim); m->t_embed_set = true;
+    m->pfx.dec_built = false;      // the decoder's prefix rows depend on the Ada scales (the encoder's do not): rebuilt at the next use
     return VOX_OK;
 }
 
@@ -1423,8 +1447,11 @@ static int enc_packed_rows_of(const vox_model* m, int T) { const int R = m->cfg.
 static long enc_packed_rows(const vox_model* m, const int* T, int n) { long r = 0; for (int i = 0; i < n; i++) r += enc_packed_rows_of(m, T[i]); return r; }
 // which forms a stack took (vox_debug_encode_batch): stacked rows, w2 / wo split-K slice counts (0 = unsplit), q|k|v launches with RoPE in the GEMM's epilogue
 struct EncForms { long Mtot = 0; int ksp = 0, ksp_wo = 0, fused_rope = 0; };
+// prefix_rows = r0 > 0 (one utterance, unpacked; a multiple of the reshape factor): rows [0, r0) of every layer are NOT computed -- their keys and values come from the
+// model's prefix state (m->pfx.enc_kv, the attention kernel's second K / V segment), the conv stem still runs over the whole clip (two launches; its symmetric padding is
+// why the mel is not simply cut), the layers carry rows r0 .. S-1 at RoPE positions r0 .., the adapter writes audio rows r0 / R .. and leaves the rows before them alone.
 static int32_t encode_batch_dev(vox_model* m, int n, const float* const* d_mels, const int* T, float* audio_out, int audio_rows, int* S4_out, long* audio_off_out = nullptr,
-                                EncForms* forms = nullptr) {
+                                EncForms* forms = nullptr, int prefix_rows = 0) {
     const vox_model_cfg& c = m->cfg; vox_ctx* cx = m->ctx; hipStream_t s = cx->stream;
     const int D = c.enc_dim, H = c.enc_heads, hd = c.enc_head_dim, QD = H * hd, F = c.enc_ffn, R = c.reshape_factor;
     const bool packed = audio_off_out != nullptr;
@@ -1437,7 +1464,11 @@ static int32_t encode_batch_dev(vox_model* m, int n, const float* const* d_mels,
     ARGCHK(S_pad <= m->enc_rope_len, "audio too long for the encoder RoPE table (%d > %d positions); chunk it (--max-mel-frames)", S_pad, m->enc_rope_len);
     std::vector<int> roff(n + 1, 0);      // packed: first row of every utterance
     if (packed) for (int i = 0; i < n; i++) roff[i + 1] = roff[i] + enc_packed_rows_of(m, T[i]);
-    const int Mtot = packed ? roff[n] : n * S_pad, M4 = packed ? Mtot / R : n == 1 ? S4_out[0] : Mtot / R;          // adapter rows
+    const int r0 = prefix_rows;
+    ARGCHK(r0 == 0 || (n == 1 && !packed && r0 % R == 0 && r0 < S_pad && m->pfx.enc_built && r0 == m->pfx.RC), "internal: encoder prefix of %d rows", r0);
+    const int Mfull = packed ? roff[n] : n * S_pad;                  // rows the conv stems write
+    const int Mtot = Mfull - r0, M4 = packed ? Mtot / R : n == 1 ? S4_out[0] - r0 / R : Mtot / R;          // rows the layers carry; adapter rows
+    ARGCHK(!m->pfx.capture || (n == 1 && !packed && r0 == 0 && m->pfx.capture_rows <= S_pad), "internal: prefix capture");
     ARGCHK(packed || n == 1 || audio_rows >= S_pad / R, "internal: audio row budget %d < %d", audio_rows, S_pad / R);
     int Tmax = 0; for (int i = 0; i < n; i++) Tmax = std::max(Tmax, T[i]);
     (void)T1max;
@@ -1456,10 +1487,10 @@ static int32_t encode_batch_dev(vox_model* m, int n, const float* const* d_mels,
     int ksp_wo = ksp ? 2 : 0;      // the same for wo (K = QD: 10 K-steps), two slices (7.85 -> 7.76 ms per clip; four: 7.93; profiles/r03_enc_splitk.txt); VOX_ENC_SPLITK_WO overrides
     if (ksp) { if (const char* e = knob_str("VOX_ENC_SPLITK_WO")) ksp_wo = atoi(e) > 1 ? std::min(atoi(e), ksp) : 0; }
     for (int l = 0; ksp_wo && l < c.enc_layers; l++) if (m->enc[l].wo.w.fmt != WFMT_Q4_0 || !m->enc[l].wo.w.qt || m->enc[l].wo.w.nb / 4 < ksp_wo || m->enc[l].wo.w.nb % 4) ksp_wo = 0;
-    const size_t need = c1_floats + (size_t)Mtot * D * 2 + (size_t)Mtot * QD * 4 + (size_t)Mtot * F + (size_t)(M4 + 1) * m->ad0.w.N + (size_t)ksp * Mtot * D + 1024;
+    const size_t need = c1_floats + (size_t)Mfull * D + (size_t)Mtot * D + (size_t)Mtot * QD * 4 + (size_t)Mtot * F + (size_t)(M4 + 1) * m->ad0.w.N + (size_t)ksp * Mtot * D + 1024;
     VOXCHK(ensure(&m->ws, &m->ws_floats, need));
     if (forms) { forms->Mtot = Mtot; forms->ksp = ksp; forms->ksp_wo = ksp_wo; forms->fused_rope = 0; }
-    float* c1 = m->ws; float* x = c1 + c1_floats / 64 * 64; float* xn = x + (size_t)Mtot * D; float* qkv = xn + (size_t)Mtot * D;
+    float* c1 = m->ws; float* x0 = c1 + c1_floats / 64 * 64; float* x = x0 + (size_t)r0 * D; float* xn = x0 + (size_t)Mfull * D; float* qkv = xn + (size_t)Mtot * D;      // x0: the conv stem's rows; x: the first row the layers carry
     float* att = qkv + (size_t)Mtot * QD * 3; float* ffn = att + (size_t)Mtot * QD; float* ah = ffn + (size_t)Mtot * F; float* w2p = ah + (size_t)(M4 + 1) * m->ad0.w.N;
     const int* d_len = nullptr; const int* d_roff = nullptr; const int* d_rpos = nullptr;
     if (n > 1 || packed) {
@@ -1482,7 +1513,7 @@ static int32_t encode_batch_dev(vox_model* m, int n, const float* const* d_mels,
     }
     for (int i = 0; i < n; i++) {
         if (S[i] <= 0) continue;
-        VOXCHK(conv_stem_dev(m, d_mels[i], T[i], c1, x + (packed ? (size_t)roff[i] : (size_t)i * S_pad) * D));
+        VOXCHK(conv_stem_dev(m, d_mels[i], T[i], c1, x0 + (packed ? (size_t)roff[i] : (size_t)i * S_pad) * D));
     }
     const int seq_rows = packed ? 0 : n > 1 ? S_pad : 0;
     for (int l = 0; l < c.enc_layers; l++) {
@@ -1491,15 +1522,20 @@ static int32_t encode_batch_dev(vox_model* m, int n, const float* const* d_mels,
         else HIPCHK(launch_rms_norm(x, D, Mtot, D, L.attn_norm, nullptr, c.norm_eps, xn, D, s));
         if (Mtot > 48) {      // q|k|v with RoPE on the q and k columns: in the large-M GEMM's epilogue where that kernel runs, else store + rope_kernel (launch_q4_gemm, EPI_ROPE_ROWS)
             GemmParams g{}; g.w = L.wqkv.w; g.x = xn; g.x_stride = D; g.M = Mtot; g.out = qkv; g.out_stride = 3 * QD; g.bias = L.wqkv.bias;
-            g.rope_cos = m->enc_cos; g.rope_sin = m->enc_sin; g.hd = hd; g.n_q = 2 * QD; g.pos = d_rpos; g.rope_seq_rows = seq_rows;
+            g.rope_cos = m->enc_cos + (size_t)r0 * (hd / 2); g.rope_sin = m->enc_sin + (size_t)r0 * (hd / 2);      // row i sits at position r0 + i: the tables are [position][hd / 2]
+            g.hd = hd; g.n_q = 2 * QD; g.pos = d_rpos; g.rope_seq_rows = seq_rows;
             bool fused = false; HIPCHK(launch_q4_gemm(g, EPI_ROPE_ROWS, s, &fused));
             if (forms && fused) forms->fused_rope++;
         } else {
             VOXCHK(q4_linear_dev(cx, L.wqkv.w, L.wqkv.bias, xn, D, Mtot, qkv, 3 * QD));
-            HIPCHK(launch_rope(qkv, Mtot, 3 * QD, 2 * QD, hd, 0, m->enc_cos, m->enc_sin, s, seq_rows, d_rpos));
+            HIPCHK(launch_rope(qkv, Mtot, 3 * QD, 2 * QD, hd, r0, m->enc_cos, m->enc_sin, s, seq_rows, d_rpos));
         }
+        if (m->pfx.capture)      // building the prefix state: this layer's k | v rows 0 .. capture_rows-1
+            HIPCHK(hipMemcpy2DAsync(m->pfx.capture + (size_t)l * m->pfx.capture_rows * 2 * QD, (size_t)2 * QD * 4, qkv + QD, (size_t)3 * QD * 4, (size_t)2 * QD * 4, (size_t)m->pfx.capture_rows,
+                                    hipMemcpyDeviceToDevice, s));
         AttnParams ap{}; ap.q = qkv; ap.q_stride = 3 * QD; ap.k = qkv + QD; ap.v = qkv + 2 * QD; ap.kv_row_stride = 3 * QD; ap.kv_head_stride = hd;
-        ap.out = att; ap.out_stride = QD; ap.M = S_pad; ap.kv_len = S_pad; ap.n_heads = H; ap.n_kv_heads = H; ap.offset = 0; ap.window = c.enc_window;
+        ap.out = att; ap.out_stride = QD; ap.M = S_pad - r0; ap.kv_len = S_pad; ap.n_heads = H; ap.n_kv_heads = H; ap.offset = r0; ap.window = c.enc_window;
+        if (r0) { ap.prefix_k = m->pfx.enc_kv + (size_t)l * r0 * 2 * QD; ap.prefix_v = ap.prefix_k + QD; ap.prefix_len = r0; ap.prefix_row_stride = 2 * QD; ap.prefix_head_stride = hd; }
         ap.seq_len = d_len; ap.q_seq_stride = S_pad * 3 * QD; ap.out_seq_stride = S_pad * QD; ap.kv_seq_stride = (long)S_pad * 3 * QD; ap.seq_row_off = d_roff;
         HIPCHK(launch_attn_prefill(ap, hd, s, n));
         if (ksp_wo) {      // (w2p is free here: the previous layer's w2 planes were consumed by this layer's first norm)
@@ -1518,15 +1554,15 @@ static int32_t encode_batch_dev(vox_model* m, int n, const float* const* d_mels,
     // reshape_encoder_output (models/adapter.rs:108-122): rows [0, 4*S4) of each utterance viewed as [S4][4D]; adapter (model.rs:745-749)
     VOXCHK(q4_linear_dev(cx, m->ad0.w, nullptr, xn, D * R, M4, ah, m->ad0.w.N, EPI_GELU));
     if (packed) { for (int i = 0; i < n; i++) audio_off_out[i] = (long)(roff[i] / R) * c.dec_dim; }
-    if (packed || n == 1 || audio_rows * R == S_pad) VOXCHK(q4_linear_dev(cx, m->ad2.w, nullptr, ah, m->ad0.w.N, M4, audio_out, c.dec_dim));
+    if (packed || n == 1 || audio_rows * R == S_pad) VOXCHK(q4_linear_dev(cx, m->ad2.w, nullptr, ah, m->ad0.w.N, M4, audio_out + (size_t)(r0 / R) * c.dec_dim, c.dec_dim));
     else for (int i = 0; i < n; i++)      // wider per-utterance stride on the output side
         VOXCHK(q4_linear_dev(cx, m->ad2.w, nullptr, ah + (size_t)i * (S_pad / R) * m->ad0.w.N, m->ad0.w.N, S_pad / R, audio_out + (size_t)i * audio_rows * c.dec_dim, c.dec_dim));
     return VOX_OK;
 }
-static int32_t encode_dev(vox_model* m, const float* d_mel, int T, int* S4_out) {
+static int32_t encode_dev(vox_model* m, const float* d_mel, int T, int* S4_out, int prefix_rows = 0) {
     const int S4 = enc_rows(T) / m->cfg.reshape_factor;
     if (S4 > 0) { size_t cap = (size_t)m->audio_cap * m->cfg.dec_dim; VOXCHK(ensure(&m->d_audio, &cap, (size_t)S4 * m->cfg.dec_dim)); m->audio_cap = (int)(cap / m->cfg.dec_dim); }
-    return encode_batch_dev(m, 1, &d_mel, &T, m->d_audio, S4, S4_out);
+    return encode_batch_dev(m, 1, &d_mel, &T, m->d_audio, S4, S4_out, nullptr, nullptr, prefix_rows);
 }
 
 // ---- KV cache (models/layers/kv_cache.rs:52-65,221-234)
@@ -1978,6 +2014,101 @@ static int32_t ensure_decode_state(vox_model* m, int S) {
     return VOX_OK;
 }
 
+// ---- prefix state (struct PrefixState): what the silent left pad of vox_transcribe_audio makes identical for every utterance
+// Bounds from the pad configuration.  Mel frame f reads padded samples [160 f - 200, 160 f + 200) (reflected at the start: still inside the pad), so frames 0 .. Fc =
+// (left - 200) / 160 are the constant floor whatever follows; conv-stem row s reads frames 4 s - 3 .. 4 s + 3 (two k3 s2 p1 convolutions), so rows 0 .. (Fc - 3) / 4 are
+// constant; the encoder attention is causal and RoPE starts at 0, so these rows stay constant through the layers.  RC = that row count rounded DOWN to a multiple of the
+// reshape factor (the adapter's [rows / R][R D] view of the live rows stays aligned); the decoder part covers positions 0 .. 36 = the prefix tokens whose successor is
+// also a prefix token, and is used only when the encoder part reaches that far (one ordinary step at position 37 then replaces the whole prefill).
+static void prefix_bounds(const vox_model* m, int* RC, int* PC) {
+    const vox_model_cfg& c = m->cfg; *RC = 0; *PC = 0;
+    vox_pad_cfg pc; vox_pad_cfg_voxtral(&pc);
+    const long left = (long)pad_left(&pc), R = c.reshape_factor;
+    if (left < 200 || R < 1 || c.n_mels != 128 || (c.enc_head_dim != 64 && c.enc_head_dim != 128) || m->enc.empty() || m->dec.empty()) return;
+    const long Fc = (left - 200) / 160, rows = Fc >= 3 ? (Fc - 3) / 4 + 1 : 0;
+    const long pcn = VOX_PREFIX_TOKENS - 1;
+    if (rows / R < pcn || pcn * R + 4 > m->enc_rope_len) return;
+    *PC = (int)pcn; *RC = (int)(pcn * R);
+}
+static bool prefix_active(const vox_model* m) { int rc, pc; prefix_bounds(m, &rc, &pc); return m->pfx.on && rc > 0; }
+static int32_t prefix_build(vox_model* m, const float* t_embed) {
+    PrefixState& p = m->pfx; const vox_model_cfg& c = m->cfg; vox_ctx* cx = m->ctx; hipStream_t s = cx->stream;
+    int RC, PC; prefix_bounds(m, &RC, &PC);
+    if (!p.on || RC <= 0) return VOX_OK;
+    if (p.enc_built && p.dec_built && p.t_embed.size() == (size_t)c.dec_dim && !std::memcmp(p.t_embed.data(), t_embed, (size_t)c.dec_dim * 4)) return VOX_OK;
+    const int QD = c.enc_heads * c.enc_head_dim, hd = c.dec_head_dim, KV = c.dec_kv_heads;
+    p.RC = RC; p.PC = PC;
+    // device memory for the state; a failed allocation is not an error of the call: the model goes back to the full computation (as the decode engine does without its stream)
+    const size_t rows_bytes = (size_t)PC * hd * 4, n_rows = (size_t)c.dec_layers * KV;
+    {
+        hipError_t e = hipSuccess;
+        auto A = [&](float** q, size_t n) { if (e == hipSuccess && !*q) e = hipMalloc((void**)q, n); };
+        A(&p.enc_kv, (size_t)c.enc_layers * RC * 2 * QD * 4); A(&p.audio, (size_t)PC * c.dec_dim * 4); A(&p.dec_k, rows_bytes * n_rows); A(&p.dec_v, rows_bytes * n_rows);
+        if (e != hipSuccess) {
+            (void)hipGetLastError(); prefix_release(m); p.on = false;
+            fprintf(stderr, "[voxtral_hip] prefix state: allocating %.1f MB failed (%s); every call runs the full computation\n",
+                    ((double)c.enc_layers * RC * 2 * QD * 4 + 2.0 * rows_bytes * n_rows) / 1e6, hipGetErrorString(e));
+            return VOX_OK;
+        }
+    }
+    if (!p.enc_built) {
+        // the encoder over a silent mel long enough that rows 0 .. RC-1 see nothing but it (RC + 4 rows), made by the mel kernel itself from an all-zero padded signal
+        const int Tb = 4 * (RC + 4);
+        p.enc_bytes = (uint64_t)c.enc_layers * RC * 2 * QD * 4 + (uint64_t)PC * c.dec_dim * 4;
+        MelTables t; VOXCHK(ctx_mel_tables(cx, &t));
+        DevBuf mel; HIPCHK(mel.alloc((size_t)c.n_mels * Tb * 4));
+        HIPCHK(launch_mel(nullptr, 0, (long)Tb * 160, 0, nullptr, t, mel.as<float>(), Tb, 1, s));
+        int S4 = 0; p.capture = p.enc_kv; p.capture_rows = RC;
+        const int32_t r = encode_dev(m, mel.as<float>(), Tb, &S4);
+        p.capture = nullptr; p.capture_rows = 0;
+        VOXCHK(r); ARGCHK(S4 >= PC, "internal: prefix build gave %d audio rows", S4);
+        HIPCHK(hipMemcpyAsync(p.audio, m->d_audio, (size_t)PC * c.dec_dim * 4, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));      // (mel is freed at the end of this block)
+        p.enc_built = true;
+    }
+    // the decoder's cache rows 0 .. PC-1: the ordinary prefill over the first PC prefix tokens (rows of a causal prefill do not depend on the rows behind them)
+    VOXCHK(vox_model_set_t_embed(m, t_embed));
+    VOXCHK(ensure_decode_state(m, VOX_PREFIX_TOKENS));
+    p.dec_bytes = 2 * (uint64_t)rows_bytes * n_rows;
+    std::vector<int32_t> prefix(VOX_PREFIX_TOKENS, VOX_TOK_STREAMING_PAD); prefix[0] = VOX_TOK_BOS;
+    HIPCHK(hipMemcpyAsync(m->d_tokens, prefix.data(), prefix.size() * 4, hipMemcpyHostToDevice, s));
+    if (!m->d_prefix) HIPCHK(hipMalloc((void**)&m->d_prefix, (size_t)VOX_PREFIX_TOKENS * c.dec_dim * 4));
+    HIPCHK(launch_embed(m->tok.w, m->d_tokens, PC, p.audio, c.dec_dim, nullptr, 0, 0, m->d_prefix, s));
+    m->cache->len = 0;
+    VOXCHK(decoder_prefill_dev(m, m->d_prefix, PC, m->cache, 0));
+    const size_t pitch = (size_t)m->cache->max_seq * hd * 4;      // cache: [layer][kv head][max_seq][hd], layers back to back
+    ARGCHK(cache_layer_floats(m, m->cache) == (size_t)KV * m->cache->max_seq * hd, "internal: cache layout");
+    HIPCHK(hipMemcpy2DAsync(p.dec_k, rows_bytes, m->cache->k, pitch, rows_bytes, n_rows, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpy2DAsync(p.dec_v, rows_bytes, m->cache->v, pitch, rows_bytes, n_rows, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    p.t_embed.assign(t_embed, t_embed + c.dec_dim); p.dec_built = true;      // (after vox_model_set_t_embed, which clears the flag when t_embed changes)
+    return VOX_OK;
+}
+// Does THIS call run on the prefix?  Only a clip that decodes at least one position behind the prefix tokens (then at least one live adapter row exists).
+static bool prefix_usable(const vox_model* m, int T) {
+    const PrefixState& p = m->pfx; const vox_model_cfg& c = m->cfg;
+    if (!p.on || !p.enc_built || !p.dec_built || p.RC <= 0 || knob_str("VOX_ATTN_F32")) return false;
+    const int S = enc_rows(T);
+    return S / c.reshape_factor > VOX_PREFIX_TOKENS && S <= m->enc_rope_len;
+}
+extern "C" int32_t vox_model_set_prefix_cache(vox_model* m, int32_t on, int32_t* active) {
+    ARGCHK(m, "null argument"); VOXCHK(ctx_bind(m->ctx));
+    if (on >= 0) {
+        m->pfx.on = on != 0;
+        if (!m->pfx.on) { HIPCHK(hipStreamSynchronize(m->ctx->stream)); prefix_release(m); }
+        else if (m->t_embed_set) { std::vector<float> te = m->t_embed_host; VOXCHK(prefix_build(m, te.data())); }      // (before the first utterance the build waits for its t_embed)
+    }
+    if (active) *active = prefix_active(m) ? 1 : 0;
+    return VOX_OK;
+}
+extern "C" int32_t vox_model_prefix_info(const vox_model* m, int32_t out[4]) {
+    ARGCHK(m && out, "null argument");
+    int rc, pc; prefix_bounds(m, &rc, &pc);
+    const uint64_t b = (m->pfx.enc_kv ? m->pfx.enc_bytes : 0) + (m->pfx.dec_k ? m->pfx.dec_bytes : 0);
+    out[0] = m->pfx.enc_built && m->pfx.dec_built ? 1 : 0; out[1] = rc; out[2] = pc; out[3] = (int32_t)std::min<uint64_t>(b, 0x7fffffff);
+    return VOX_OK;
+}
+
 // one full sync-free decode step. On entry d_h holds the step's input embedding (audio[cur] + embed(token[cur])):
 // 26 layers -> final norm + lm_head (argmax partials) -> fused tail: token[cur+1], cur++, next step's d_h.
 // mode 0: the step and the launch that turns its argmax partials into the next token + input (every path).  Engine only -- mode 1: the engine launch alone, its
@@ -1998,15 +2129,19 @@ static int32_t decode_step_enqueue(vox_model* m, float* logits_out, int mode = 0
 }
 
 // transcribe_streaming on device-resident mel [n_mels][T]  (gguf/model.rs:873-963)
+// from_padded_samples: d_mel is the log-mel of samples the library itself padded (vox_transcribe_audio) -- the only case in which the model's prefix state stands for the
+// first encoder rows and decoder positions (a caller's own mel may hold anything there).
 static int32_t transcribe_dev(vox_model* m, const float* d_mel, int T, const float* t_embed, int32_t* out_ids, int32_t cap, int32_t* n_ids,
-                              float* logits_host) {
+                              float* logits_host, bool from_padded_samples = false) {
     const vox_model_cfg& c = m->cfg; vox_ctx* cx = m->ctx; hipStream_t s = cx->stream;
-    const int PREFIX_LEN = 38, BOS = 1, STREAMING_PAD = 32;
+    const int PREFIX_LEN = VOX_PREFIX_TOKENS, BOS = VOX_TOK_BOS, STREAMING_PAD = VOX_TOK_STREAMING_PAD;
     VOXCHK(vox_model_set_t_embed(m, t_embed));
+    const bool pfx = from_padded_samples && !logits_host && prefix_usable(m, T);      // (prefix_build ran before the mel was made: vox_transcribe_audio)
+    const int PC = pfx ? m->pfx.PC : 0;
     double t0 = now_ms();
     RoctxScope whole("transcribe_streaming"); RoctxStage stage;
     stage.begin("encode_audio");
-    int S = 0; VOXCHK(encode_dev(m, d_mel, T, &S));
+    int S = 0; VOXCHK(encode_dev(m, d_mel, T, &S, pfx ? m->pfx.RC : 0));
     HIPCHK(hipStreamSynchronize(s));                       // e2e_bench.rs:161-167 forces a sync here too
     stage.end();
     m->timings.encode_ms = now_ms() - t0; t0 = now_ms();
@@ -2025,26 +2160,38 @@ static int32_t transcribe_dev(vox_model* m, const float* d_mel, int T, const flo
     std::vector<int32_t> prefix(PREFIX_LEN, STREAMING_PAD); prefix[0] = BOS;      // model.rs:891-892
     HIPCHK(hipMemcpyAsync(m->d_tokens, prefix.data(), PREFIX_LEN * 4, hipMemcpyHostToDevice, s));
     m->cache->len = 0;
+    DevBuf dlog; float* d_logits_all = nullptr;
+    stage.begin("prefill");
+    if (pfx) {
+        // Positions 0 .. PC-1 (= 36) are the model's: their K / V rows are copied into the cache (every call: the cache may have been re-allocated, and a decode overwrites
+        // nothing below PC but a batch call may), and position PC = 37 -- the last prefix token, the first one whose output is kept -- runs as the first ordinary decode
+        // step below: no prefill, no separate lm_head; tokens[38] comes out of the same argmax chain as every later token.
+        const PrefixState& P = m->pfx; const size_t rows_bytes = (size_t)PC * c.dec_head_dim * 4, n_rows = (size_t)c.dec_layers * c.dec_kv_heads, pitch = (size_t)m->cache->max_seq * c.dec_head_dim * 4;
+        HIPCHK(hipMemcpy2DAsync(m->cache->k, pitch, P.dec_k, rows_bytes, rows_bytes, n_rows, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpy2DAsync(m->cache->v, pitch, P.dec_v, rows_bytes, rows_bytes, n_rows, hipMemcpyDeviceToDevice, s));
+        m->cache->len = PC;
+        HIPCHK(hipMemcpyAsync(m->d_pos, &PC, 4, hipMemcpyHostToDevice, s));
+        steps = S - PC - 1;                                              // pos = 37 .. S-2
+    } else {
     // prefix inputs = audio[:38] + embed(prefix)  (model.rs:896-902)
     if (!m->d_prefix) HIPCHK(hipMalloc((void**)&m->d_prefix, (size_t)PREFIX_LEN * c.dec_dim * 4));   // model-owned: no hipMalloc/hipFree in the timed path
     float* px = m->d_prefix;
-    stage.begin("prefill");
     HIPCHK(launch_embed(m->tok.w, m->d_tokens, PREFIX_LEN, m->d_audio, c.dec_dim, nullptr, 0, 0, px, s));
     VOXCHK(decoder_prefill_dev(m, px, PREFIX_LEN, m->cache, 0));
     m->cache->len = PREFIX_LEN;
     // lm_head on the last prefix row only (the reference computes all 38 and keeps the last, model.rs:916-923)
-    DevBuf dlog; float* d_logits_all = nullptr;
     if (logits_host) { HIPCHK(dlog.alloc((size_t)n * c.vocab * 4)); d_logits_all = dlog.as<float>(); }
     VOXCHK(lm_head_argmax_dev(m, px + (size_t)(PREFIX_LEN - 1) * c.dec_dim, d_logits_all));
     const int pos_init = PREFIX_LEN;
     HIPCHK(hipMemcpyAsync(m->d_pos, &pos_init, 4, hipMemcpyHostToDevice, s));
     HIPCHK(launch_argmax_final(m->d_part_val, m->d_part_idx, m->n_parts, m->d_tokens, m->d_pos, 0, 0, s));   // tokens[38]
     steps = std::max(S - PREFIX_LEN - 1, 0);                            // pos = 39 .. S-1 (model.rs:938)
+    }
     stage.begin("decode");
     // attn_wo accumulators: every step leaves them cleared (w2 does it); once per utterance they are cleared outright, so a call that failed
     // half-way through a layer cannot leak into the next one
     if (steps > 0 && m->d_wo_acc) HIPCHK(hipMemsetAsync(m->d_wo_acc, 0, (size_t)c.dec_layers * c.dec_dim * 8, s));
-    if (steps > 0) HIPCHK(launch_embed(m->tok.w, m->d_tokens, 1, m->d_audio, c.dec_dim, m->d_pos, 0, 0, m->d_h, s));   // input of the first decode step (audio[38] exists iff S >= 39)
+    if (steps > 0) HIPCHK(launch_embed(m->tok.w, m->d_tokens, 1, m->d_audio, c.dec_dim, m->d_pos, 0, 0, m->d_h, s));   // input of the first decode step (audio[38] exists iff S >= 39; on the prefix: audio[37] + embed(PAD))
     if (logits_host) {
         for (int i = 0; i < steps; i++) VOXCHK(decode_step_enqueue(m, d_logits_all + (size_t)(i + 1) * c.vocab));
     } else if (steps > 0) {
@@ -2106,7 +2253,7 @@ static int32_t transcribe_dev(vox_model* m, const float* d_mel, int T, const flo
         m->eng_suspended = false; graphs_destroy(m);      // (the graph captured during the re-run holds the per-operator launches)
         if (r != VOX_OK) return r;
     }
-    m->cache->len = PREFIX_LEN + steps;
+    m->cache->len = (pfx ? PC : PREFIX_LEN) + steps;
     *n_ids = n; m->timings.decode_tokens = n;
     m->timings.decode_ms = now_ms() - t0;
     return VOX_OK;
@@ -2148,6 +2295,7 @@ extern "C" int32_t vox_transcribe_audio(vox_model* m, const float* samples, size
     const vox_model_cfg& c = m->cfg; vox_ctx* cx = m->ctx; hipStream_t s = cx->stream;
     ARGCHK(c.n_mels == 128, "the log-mel front-end produces 128 bins; model expects %d", c.n_mels);
     m->timings = vox_timings{};
+    VOXCHK(prefix_build(m, t_embed));      // nothing to do once the model holds its prefix state for this t_embed (the first call of a model pays it, outside the stage times)
     const double t0 = now_ms();
     const float* d_s = samples;
     if (mem_kind == VOX_MEM_HOST) {
@@ -2162,7 +2310,7 @@ extern "C" int32_t vox_transcribe_audio(vox_model* m, const float* samples, size
     HIPCHK(launch_mel(d_s, (long)n, (long)left, (long)right, cx->d_scale, t, m->d_mel, (int)T, 1, s));   // pad + log-mel, [128][T]
     HIPCHK(hipStreamSynchronize(s));
     m->timings.preprocess_ms = now_ms() - t0;
-    VOXCHK(transcribe_dev(m, m->d_mel, (int)T, t_embed, out_ids, cap, n_ids, nullptr));
+    VOXCHK(transcribe_dev(m, m->d_mel, (int)T, t_embed, out_ids, cap, n_ids, nullptr, true));
     m->timings.total_ms = m->timings.preprocess_ms + m->timings.encode_ms + m->timings.decode_ms;
     return VOX_OK;
 }

@@ -158,8 +158,12 @@ struct AttnParams {
     int spec_zero;        // always 0 (see attn_decode_kernel: keeps the position load a vector load)
     int spec_rows;        // decode (head-major cache, kv_row_stride == hd): rows per KV head in the cache; > 0 lets the kernel request the first
                           // 160 rows before the position word has arrived (attn_decode_core SPEC).  0: indices derived from the position.
+    // prefill, one sequence, MFMA kernel only (attn_prefill_prefix_ok): a second K / V segment in FRONT of k / v.  Key index j < prefix_len is row j of prefix_k / prefix_v
+    // ([kvh * prefix_head_stride + j * prefix_row_stride + d]); j >= prefix_len is row j - prefix_len of k / v.  offset = prefix_len, kv_len = prefix_len + M.
+    const float* prefix_k; const float* prefix_v; int prefix_len, prefix_row_stride, prefix_head_stride;
 };
 hipError_t launch_attn_prefill(const AttnParams& p, int hd, hipStream_t s, int n_seq = 1);     // M > 1, causal (+window)
+bool attn_prefill_prefix_ok(const AttnParams& p, int hd, int n_seq);     // may launch_attn_prefill take p's two K / V segments (prefix_len > 0)?
 bool attn_prefill_small_ok(const AttnParams& p, int hd, int n_seq);      // will launch_attn_prefill take the short-sequence kernel (<= 48 rows from position 0, f32; may write XF tiles: p.out_xf_tiles)?
 hipError_t launch_attn_decode(const AttnParams& p, int hd, int max_seq, hipStream_t s, int n_seq = 1);  // M == 1 per sequence
 // single sequence: attention + the wo linear in one launch; acc[wo.N] (int64, zero on entry) receives the product in 2^-32 fixed point (consumer: PRO_RMS_MUL_SUM)

@@ -2820,7 +2820,10 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(const AttnParams p) {
 // In every fragment the lane's column index is the query (lane & 15): running max, running sum and the rescale factor of
 // the online softmax are per-lane scalars; only the tile max needs a cross-lane step (xor 16, 32).
 // ------------------------------------------------------------------------------------------------
-template <int HD>
+// PFX: a second K / V segment in FRONT of k / v (AttnParams::prefix_k ...; one sequence only): key index j < prefix_len is row j of the prefix buffer (its own row / head
+// strides), j >= prefix_len is row j - prefix_len of k / v.  kv_len, offset, the causal mask, the window and the clamped loads all count on the concatenated index, so the
+// key tiles are the ones a single buffer of kv_len rows would give.  PFX = false is the kernel every other caller runs.
+template <int HD, bool PFX>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void attn_prefill_mfma_kernel(const AttnParams p) {
     constexpr int KS = HD / 32, DT = HD / 16, KROW = HD + 8, VROW = 72;
     extern __shared__ __attribute__((aligned(16))) uint16_t smh[];
@@ -2871,6 +2874,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
     const size_t kvso = p.seq_row_off ? (size_t)p.seq_row_off[sq] * p.kv_row_stride : (size_t)sq * p.kv_seq_stride;
     const float* kbase = p.k + kvso + (size_t)kvh * p.kv_head_stride;
     const float* vbase = p.v + kvso + (size_t)kvh * p.kv_head_stride;
+    const int n_pfx = PFX ? p.prefix_len : 0;
+    const float* pkbase = PFX ? p.prefix_k + (size_t)kvh * p.prefix_head_stride : nullptr;
+    const float* pvbase = PFX ? p.prefix_v + (size_t)kvh * p.prefix_head_stride : nullptr;
+    // row J_ of the concatenated keys / values
+#define VOX_ATT_ROW(BASE_, PBASE_, J_) \
+    ((PFX && (J_) < n_pfx) ? (PBASE_) + (size_t)(J_) * p.prefix_row_stride : (BASE_) + (size_t)((J_) - n_pfx) * p.kv_row_stride)
 
     // register-staged software pipeline: the global loads of tile t+1 are in flight while tile t is being multiplied
     constexpr int NK = (64 * (HD / 4)) / 256, NV = (32 * (HD / 4)) / 256;
@@ -2879,13 +2888,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
     _Pragma("unroll") for (int u = 0; u < NK; u++) {                                                                \
         const int i = tid + 256 * u, key = i / (HD / 4), d4 = i % (HD / 4);                                         \
         const int jc = min((J0_) + key, kv_len - 1);   /* unconditional clamped loads; masked keys get p = 0 */   \
-        kreg[u] = *reinterpret_cast<const float4*>(kbase + (size_t)jc * p.kv_row_stride + d4 * 4);                  \
+        kreg[u] = *reinterpret_cast<const float4*>(VOX_ATT_ROW(kbase, pkbase, jc) + d4 * 4);                        \
     }                                                                                                               \
     _Pragma("unroll") for (int u = 0; u < NV; u++) {                                                                \
         const int i = tid + 256 * u, kp = i / (HD / 4), d4 = i % (HD / 4);                                          \
         const int ja = min((J0_) + 2 * kp, kv_len - 1), jb = min((J0_) + 2 * kp + 1, kv_len - 1);               \
-        vra[u] = *reinterpret_cast<const float4*>(vbase + (size_t)ja * p.kv_row_stride + d4 * 4);                   \
-        vrb[u] = *reinterpret_cast<const float4*>(vbase + (size_t)jb * p.kv_row_stride + d4 * 4);                   \
+        vra[u] = *reinterpret_cast<const float4*>(VOX_ATT_ROW(vbase, pvbase, ja) + d4 * 4);                         \
+        vrb[u] = *reinterpret_cast<const float4*>(VOX_ATT_ROW(vbase, pvbase, jb) + d4 * 4);                         \
     }
     const int j_first = (j_lo / 64) * 64, j_last = (j_hi / 64) * 64;
     VOX_ATT_LOAD(j_first)
@@ -2977,6 +2986,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
         }
     }
 #undef VOX_ATT_LOAD
+#undef VOX_ATT_ROW
     lsum += __shfl_xor(lsum, 16, 64); lsum += __shfl_xor(lsum, 32, 64);
     if (m < M) {
         const float inv = 1.0f / lsum;
@@ -2986,10 +2996,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
             *reinterpret_cast<float4*>(op + dt * 16) = make_float4(o[dt][0] * inv, o[dt][1] * inv, o[dt][2] * inv, o[dt][3] * inv);
     }
 }
-template <int HD>
+template <int HD, bool PFX>
 static hipError_t attn_prefill_mfma_launch(const AttnParams& p, hipStream_t s, int n_seq) {
     constexpr size_t lds = ((size_t)2 * 64 * (HD + 8) + (size_t)2 * HD * 72) * sizeof(uint16_t);
-    auto kern = attn_prefill_mfma_kernel<HD>;
+    auto kern = attn_prefill_mfma_kernel<HD, PFX>;
     static DevOnce attr_done;
     hipError_t e = ensure_dyn_lds(kern, lds, &attr_done);
     if (e != hipSuccess) return e;
@@ -3071,13 +3081,22 @@ static hipError_t attn_prefill_small_launch(const AttnParams& p, hipStream_t s, 
     attn_form_note(ATTN_FORM_PREFILL_SMALL);
     return hipGetLastError();
 }
+bool attn_prefill_prefix_ok(const AttnParams& p, int hd, int n_seq) {
+    return (hd == 64 || hd == 128) && n_seq == 1 && !p.seq_len && !p.seq_row_off && !p.out_xf_tiles && p.prefix_k && p.prefix_v && p.prefix_len > 0 && p.offset == p.prefix_len &&
+           p.M >= 1 && p.kv_len == p.prefix_len + p.M && (p.q_stride % 4) == 0 && (p.kv_row_stride % 4) == 0 && (p.prefix_row_stride % 4) == 0 && (p.prefix_head_stride % 4) == 0 &&
+           !env_int("VOX_ATTN_F32");
+}
 hipError_t launch_attn_prefill(const AttnParams& p, int hd, hipStream_t s, int n_seq) {
     if (attn_prefill_small_ok(p, hd, n_seq)) return attn_prefill_small_launch(p, s, n_seq);
     if (p.out_xf_tiles) return hipErrorInvalidValue;      // (XF output exists in the short-sequence kernel only: callers ask attn_prefill_small_ok first)
     const int f32_only = env_int("VOX_ATTN_F32");               // ablation / cross-check knob: the f32 VALU kernel (read from the knob table per launch: tests toggle it)
+    if (p.prefix_len > 0) {      // two K / V segments: the MFMA kernel only, one sequence (a caller asks attn_prefill_prefix_ok first)
+        if (!attn_prefill_prefix_ok(p, hd, n_seq)) return hipErrorInvalidValue;
+        return hd == 64 ? attn_prefill_mfma_launch<64, true>(p, s, 1) : attn_prefill_mfma_launch<128, true>(p, s, 1);
+    }
     if (!f32_only && (p.q_stride % 4) == 0 && (p.kv_row_stride % 4) == 0) {
-        if (hd == 64) return attn_prefill_mfma_launch<64>(p, s, n_seq);
-        if (hd == 128) return attn_prefill_mfma_launch<128>(p, s, n_seq);
+        if (hd == 64) return attn_prefill_mfma_launch<64, false>(p, s, n_seq);
+        if (hd == 128) return attn_prefill_mfma_launch<128, false>(p, s, n_seq);
     }
     if (n_seq != 1 || p.seq_len) return hipErrorInvalidValue;      // stacked sequences: MFMA kernel only
     dim3 grid((p.M + 63) / 64, p.n_heads);

@@ -447,6 +447,15 @@ class Q4VoxtralModel:
         """Persistent decode-step engine (one launch per token) on / off; returns whether it is active (it needs the real decoder geometry on a 256-CU device)."""
         a = C.c_int32(); check(lib().vox_model_set_decode_engine(self.h, 1 if on else 0, C.byref(a))); return bool(a.value)
 
+    def set_prefix_cache(self, on=None) -> bool:
+        """Prefix state of transcribe_audio (what the silent left pad makes identical for every utterance, computed once per model) on / off (None: query); returns
+        whether it is in use.  Off = the full computation for every call."""
+        a = C.c_int32(); check(lib().vox_model_set_prefix_cache(self.h, -1 if on is None else (1 if on else 0), C.byref(a))); return bool(a.value)
+
+    def prefix_info(self):
+        """The prefix state: built yet, encoder rows and decoder positions it covers, device bytes it holds."""
+        v = (C.c_int32 * 4)(); check(lib().vox_model_prefix_info(self.h, v)); return {"built": bool(v[0]), "encoder_rows": v[1], "decoder_positions": v[2], "bytes": v[3]}
+
     def memory(self):
         """Device bytes: weight arena, its primary (broadcast) part, the decode engines' weight stream, the engines' edge buffers."""
         v = (C.c_uint64 * 4)(); check(lib().vox_model_memory(self.h, v)); return {"arena": v[0], "arena_primary": v[1], "engine_stream": v[2], "engine_state": v[3]}
