@@ -367,7 +367,8 @@ int32_t vox_get_stage_timings(const vox_model* m, vox_timings* out);
 int32_t vox_debug_reload_knobs(void);
 /* Test hook: attention launches enqueued by this process so far, by kernel form (host-side counts; the replays of a captured graph are not counted):
  * out[0] short-sequence prefill, [1] MFMA prefill, [2] f32 VALU prefill (VOX_ATTN_F32), [3] single-query decode, [4] its speculative-row form (VOX_ATTN_SPEC),
- * [5] batched GQA decode, [6] fused attention + wo, [7] single-stream decode-engine launches (the whole step).  Entries past [7] are written as 0. */
+ * [5] batched GQA decode, [6] fused attention + wo, [7] single-stream decode-engine launches (the whole step), [8] the live stream's ring attention (RoPE + K / V append + windowed
+ * attention in one launch: exactly enc_layers per tick of a vox_stream).  Entries past [8] are written as 0. */
 int32_t vox_debug_attn_launches(uint64_t* out, int32_t cap);
 /* Test hook: launches of the linear kernels enqueued by this process so far, by kernel form (host-side counts, as above; nothing is dispatched by them):
  * out[0..2] Q4 GEMV with 1 / 2 / 4 rows per wave, [3] dense GEMV, [4] 5..16-row skinny GEMM, [5] 17..48-row skinny GEMM (one-dimensional form), [6] its split-K form,
@@ -409,6 +410,54 @@ int32_t vox_debug_batch_tap_fetch(vox_model* m, float* out, int32_t* rows_per_un
  * encoder rows, w2 split-K slices, wo split-K slices (0 = unsplit), q|k|v launches that ran RoPE in the GEMM's epilogue.  VOX_ERR_INVALID on bad arguments. */
 int32_t vox_debug_encode_batch(vox_model* m, int32_t n, const float* const* mels, const int32_t* T, int32_t layout, float* out, int64_t cap_rows,
                                int32_t* rows_per_clip, int64_t* report);
+
+/* ---- live streaming session (no reference counterpart: the reference transcribes finished files, bin/transcribe.rs:112-126) ------------------------------------------
+ * A vox_stream is fed 16 kHz samples in pieces of any size and hands back token ids as soon as they are determined.  After vox_stream_finish the concatenation of
+ * everything it handed back is the id sequence vox_transcribe_streaming gives for the log-mel of pad_audio(gain * x) of the concatenated samples x (gain = 0.95 / max|x|:
+ * vox_transcribe_audio(x)) -- per step the logits agree to f32 summation-order noise, so the ids agree up to the first near-tie of the offline path's own logits.
+ *   Cut-independence: the session advances in TICKS of one decoder position (16 mel frames -> 4 encoder rows -> 1 adapter row -> 1 decode step) however much audio a
+ *   push brought, so the ids, and which call returns which id, are a function of the samples and the gain alone -- not of how they were cut into pushes, nor of what
+ *   else ran on the model in between (other streams, offline calls).
+ *   Schedule: decoder position p >= 37 is determined once n >= 2560 (p - 37) + 40 samples have been pushed; the step at position p yields id p - 37.  The first id is
+ *   due after 40 samples, the second after 2 600; a push returns every id that became due, no later.  vox_stream_finish appends the right pad (vox_pad_cfg_voxtral) and
+ *   runs the remaining ticks: vox_pad_len(n) / 2560 - 38 ids in all, the offline count.  vox_stream_schedule is the same arithmetic on the host.
+ *   State: a stream owns its encoder K / V (a ring of enc_capacity_rows rows per layer and head, addressed modulo the capacity: eviction costs nothing), its decoder
+ *   cache, a 65 536-sample ring, its tokens and a 16-int device block with the per-tick integers, and starts from the model's prefix state (built for its t_embed at
+ *   create / reset if the model does not hold it; copied, so later changes of the model's prefix cache or t_embed do not disturb a live stream).  Several streams may live
+ *   on one model (same context, one thread) in any interleaving with each other and with offline calls.  A stream may not outlive its model.
+ *   Decode step: one launch of the decode engine while the stream's decoder cache has <= 1024 rows (164 s of audio; vox_model_set_decode_engine), the per-operator
+ *   launches after.  An engine hand-off timeout (shared GPU) is not the caller's error: the unverified steps of the push are decoded again on the per-operator launches.
+ *   One stream synchronisation per call, none per tick (a push of more than 1024 positions synchronises every 1024, and once where the decoder cache doubles: 1024, 2048,
+ *   ...; host samples are copied with hipMemcpyAsync from the caller's pageable memory, which the runtime stages: the call may block there as well; a t_embed other than the
+ *   model's current one is re-selected first, which synchronises).
+ *   Side effects on the model: create and reset build the model's prefix state for the stream's t_embed when the model does not hold it (vox_model_set_prefix_cache's setting
+ *   is restored afterwards: a model with the cache off gets it freed again) -- that runs a prefill through the model-owned decoder cache and replaces a prefix state built
+ *   for another t_embed, which the next offline call with that t_embed rebuilds; results never depend on it.  As everywhere, a prefix state that cannot be allocated
+ *   switches the model's prefix cache off (create / reset then fail with VOX_ERR_HIP).
+ * LIMITS: one decoder position = 2560 samples = 160 ms.  A session ends at 16 384 decoder positions (the decoder RoPE table; the encoder's 65 536-position table ends at
+ * the same point), about 43 minutes: later pushes are refused until vox_stream_reset.  16 kHz in (no resampling inside the stream).  Q4 (GGUF) models whose conv stem
+ * runs as im2col GEMMs (3 n_mels and 3 enc_dim multiples of 128); dense SafeTensors models: VOX_ERR_UNSUPPORTED. */
+typedef struct vox_stream vox_stream;
+/* gain: every sample is multiplied by it before the mel (a stream has no file peak; 1.0 = as given).
+ * enc_capacity_rows: rows of the encoder K / V ring, 0 = enc_window + 8 rounded up to a multiple of 64 (768: 0.4 GB of K / V per stream at full size; a ring needs no
+ *   slack, any capacity above enc_window + 4 gives the same bits); must exceed enc_window + 4.
+ * max_positions: decoder positions the session can reach, 0 = the decoder RoPE table (16 384). */
+int32_t vox_stream_create(vox_model* m, const float* t_embed, float gain, int32_t enc_capacity_rows, int32_t max_positions, vox_stream** out);
+/* samples host or device (mem_kind), ids host.  cap smaller than the ids the call will produce (known from the schedule before any work), a push after finish, a push
+ * that would pass max_positions: VOX_ERR_INVALID BEFORE any state changes -- the call can be repeated. */
+int32_t vox_stream_push(vox_stream* s, const float* samples, size_t n, int32_t mem_kind, int32_t* out_ids, int32_t cap, int32_t* n_ids);
+int32_t vox_stream_finish(vox_stream* s, int32_t* out_ids, int32_t cap, int32_t* n_ids);
+int32_t vox_stream_reset(vox_stream* s);          /* back to the state after create: the next push starts a new utterance */
+int32_t vox_stream_free(vox_stream* s);
+/* samples pushed, decoder positions done, ids handed out, encoder stream position, encoder ring rows in use, device bytes held,
+ * decode steps run on the engine, decode steps run per operator */
+int32_t vox_stream_info(const vox_stream* s, int64_t out[8]);
+/* host only: after n_samples pushed (finished = 0) or at the end of an n_samples utterance (finished = 1): decoder positions determined, ids due */
+int32_t vox_stream_schedule(size_t n_samples, int32_t finished, int32_t* positions, int32_t* ids);
+/* test tap, modelled on vox_debug_batch_tap_*: from now on keep the f32 logits row behind each id handed out (up to max_rows); fetch copies them to the host
+ * ([min(rows, max_rows)][vocab]; *rows = rows produced since arm) and ends the tap */
+int32_t vox_debug_stream_tap_arm(vox_stream* s, int32_t max_rows);
+int32_t vox_debug_stream_tap_fetch(vox_stream* s, float* out_rows_x_vocab, int32_t* rows);
 
 #ifdef __cplusplus
 }

@@ -150,6 +150,15 @@ SIGNATURES = {
     "vox_debug_batch_tap_arm": (i32, [vp, P(i32), i32, i32]),
     "vox_debug_batch_tap_fetch": (i32, [vp, vp, P(i32)]),
     "vox_debug_encode_batch": (i32, [vp, i32, P(vp), P(i32), i32, vp, C.c_int64, P(i32), P(C.c_int64)]),
+    "vox_stream_create": (i32, [vp, vp, f32, i32, i32, P(vp)]),
+    "vox_stream_push": (i32, [vp, vp, sz, i32, vp, i32, P(i32)]),
+    "vox_stream_finish": (i32, [vp, vp, i32, P(i32)]),
+    "vox_stream_reset": (i32, [vp]),
+    "vox_stream_free": (i32, [vp]),
+    "vox_stream_info": (i32, [vp, P(i64 * 8)]),
+    "vox_stream_schedule": (i32, [sz, i32, P(i32), P(i32)]),
+    "vox_debug_stream_tap_arm": (i32, [vp, i32]),
+    "vox_debug_stream_tap_fetch": (i32, [vp, vp, P(i32)]),
 }
 
 _LIB = None

@@ -71,6 +71,31 @@ def transcribe_one(pkg, path, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed
     return " ".join(texts)
 
 
+def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms):
+    """--live: the file through a live session (vox_stream) in pieces of `chunk_ms` milliseconds, the text so far on stderr whenever ids arrive.  The gain is the
+    file's peak scale 0.95 / max|x| (bin/transcribe.rs:207; a file is known in advance -- a microphone caller passes its own), the whole file is one utterance (no
+    --max-mel-frames chunks: the session's state is bounded by its ring), so the line equals the un-chunked path's."""
+    x, sr = load_wav(path)
+    if sr != 16000:
+        log(f"  resampling {sr} Hz -> 16 kHz"); x = resample_to_16k(x, sr, mel.ctx, pkg)
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    peak = np.float32(np.abs(x).max()) if x.size else np.float32(0)
+    gain = float(np.float32(0.95) / peak) if peak >= 1e-10 else 1.0              # audio/io.rs:59-68
+    step = max(1, int(round(16000 * chunk_ms / 1000.0)))
+    stream = model.create_stream(t_embed, gain=gain)
+    try:
+        ids = []
+        text = lambda: tokenizer.decode([t for t in ids if t >= 1000]).strip()   # :309-318
+        for a in range(0, x.size, step):
+            new = stream.push(x[a:a + step])
+            if new.size:
+                ids.extend(int(t) for t in new); log(f"  [{min(a + step, x.size) / 16000:8.2f} s] {text()}")
+        ids.extend(int(t) for t in stream.finish())
+        return text()
+    finally:
+        stream.close()
+
+
 def file_costs(paths):
     """Decode cost of a file ~ its duration (the reference has no early stop): the file size is the proxy that needs no decode."""
     import os
@@ -205,7 +230,14 @@ def main(argv=None):
     ap.add_argument("--sessions-per-gpu", type=int, default=1, help="extension (with --batch, Q4 GGUF): this many concurrent sessions on every GPU (own context + model replica + "
                     "library thread each: vox_model_set_sessions): one session's launch-bound decode steps leave gaps a second session fills (647 FLEURS-like clips: 3.7 s against 4.3 s; "
                     "calls with fewer than 128 units per session stay on one); same lines")
+    ap.add_argument("--live", action="store_true", help="extension: feed every file through a live streaming session (vox_stream) in --live-chunk-ms pieces; the text so far "
+                    "goes to stderr as ids arrive, stdout keeps one final line per input, equal to the un-chunked path's (Q4 GGUF, one GPU, no --batch)")
+    ap.add_argument("--live-chunk-ms", type=int, default=160, help="with --live: milliseconds of audio per push (one decoder position = 160 ms)")
     a = ap.parse_args(argv)
+    if a.live and (a.gpus > 1 or a.batch > 1 or a.live_chunk_ms <= 0):
+        ap.error("--live runs one file at a time on one GPU (no --gpus / --batch) with --live-chunk-ms > 0")
+    if a.live and not a.gguf:
+        ap.error("--live needs a Q4 GGUF model (--gguf): live sessions do not serve the f32 SafeTensors path")
     if a.audio_list and a.audio:
         ap.error("--audio-list conflicts with --audio")
     if a.gguf and not a.tokenizer:
@@ -286,7 +318,8 @@ def main(argv=None):
             return texts[i]
         p = paths[i]
         try:
-            t1 = time.time(); text = transcribe_one(pkg, p, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed)
+            t1 = time.time()
+            text = transcribe_live(pkg, p, model, tokenizer, mel, t_embed, a.live_chunk_ms) if a.live else transcribe_one(pkg, p, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed)
             log(f"{p}: {time.time() - t1:.3f}s")
         except Exception as e:      # per-utterance failure isolates to that line (empty), eval_wer.py:211-223 tolerates it
             log(f"Error transcribing {p}: {e}"); text = ""; rc = 1

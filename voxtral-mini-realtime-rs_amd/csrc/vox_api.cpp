@@ -1667,6 +1667,17 @@ extern "C" int32_t vox_encoder_cache_apply_sliding_window(vox_cache* kc, int32_t
     VOXCHK(enc_cache_evict(kc->m, kc, window)); HIPCHK(hipStreamSynchronize(kc->ctx->stream)); return VOX_OK;
 }
 
+// the 65 536-position RoPE table of the streaming encoder (the load-time table's formula, models/layers/rope.rs:35-64), built at first use
+static int32_t enc_stream_rope_ensure(vox_model* m) {
+    if (m->enc_cos_s) return VOX_OK;
+    const vox_model_cfg& c = m->cfg; const int hd = c.enc_head_dim;
+    const int len = 1 << 16, half = hd / 2; std::vector<float> ct((size_t)len * half), st((size_t)len * half);
+    for (int i = 0; i < len; i++) for (int j = 0; j < half; j++) { const float inv = 1.0f / std::pow(c.rope_theta, (float)(2 * j) / (float)hd), fr = (float)i * inv; ct[(size_t)i * half + j] = std::cos(fr); st[(size_t)i * half + j] = std::sin(fr); }
+    HIPCHK(hipMalloc((void**)&m->enc_cos_s, ct.size() * 4)); HIPCHK(hipMalloc((void**)&m->enc_sin_s, st.size() * 4));
+    HIPCHK(hipMemcpy(m->enc_cos_s, ct.data(), ct.size() * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(m->enc_sin_s, st.data(), st.size() * 4, hipMemcpyHostToDevice));
+    m->enc_rope_s_len = len;
+    return VOX_OK;
+}
 static int32_t encode_with_cache_dev(vox_model* m, const float* d_mel, int T, vox_cache* kc, int* S4_out) {
     const vox_model_cfg& c = m->cfg; vox_ctx* cx = m->ctx; hipStream_t s = cx->stream;
     const int D = c.enc_dim, H = c.enc_heads, hd = c.enc_head_dim, QD = H * hd, F = c.enc_ffn, R = c.reshape_factor;
@@ -1677,13 +1688,7 @@ static int32_t encode_with_cache_dev(vox_model* m, const float* d_mel, int T, vo
     // RoPE table for absolute stream positions (the load-time table covers 4096 rows, gguf/loader.rs:196-198)
     const float *cos_t = m->enc_cos, *sin_t = m->enc_sin;
     if (kc->abs_pos + S > m->enc_rope_len) {
-        if (!m->enc_cos_s) {
-            const int len = 1 << 16, half = hd / 2; std::vector<float> ct((size_t)len * half), st((size_t)len * half);
-            for (int i = 0; i < len; i++) for (int j = 0; j < half; j++) { const float inv = 1.0f / std::pow(c.rope_theta, (float)(2 * j) / (float)hd), fr = (float)i * inv; ct[(size_t)i * half + j] = std::cos(fr); st[(size_t)i * half + j] = std::sin(fr); }
-            HIPCHK(hipMalloc((void**)&m->enc_cos_s, ct.size() * 4)); HIPCHK(hipMalloc((void**)&m->enc_sin_s, st.size() * 4));
-            HIPCHK(hipMemcpy(m->enc_cos_s, ct.data(), ct.size() * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(m->enc_sin_s, st.data(), st.size() * 4, hipMemcpyHostToDevice));
-            m->enc_rope_s_len = len;
-        }
+        VOXCHK(enc_stream_rope_ensure(m));
         ARGCHK(kc->abs_pos + S <= m->enc_rope_s_len, "stream of %d encoder positions exceeds the streaming RoPE table (%d)", kc->abs_pos + S, m->enc_rope_s_len);
         cos_t = m->enc_cos_s; sin_t = m->enc_sin_s;
     }
@@ -1960,6 +1965,14 @@ static bool engb_prepare(vox_model* m, int n_grp) {
     return true;
 }
 static bool engine_active(const vox_model* m) { return m->eng_on && !m->eng_suspended && m->eng_ready && m->cache && m->eng_tab_cache == m->cache && m->eng_tab_k == m->cache->k && m->cache->max_seq <= 1024; }
+// a hand-off timeout inside the single-stream engine (its error word was read as non-zero): count the strike, re-arm the engine's state for the next launch, drop the
+// captured decode graphs; three strikes switch the engine off for the life of the model.  What each caller re-runs, and what it tells its user, is the caller's.
+static int32_t engine_strike(vox_model* m) {
+    m->eng_strikes++;
+    HIPCHK(hipMemsetAsync(m->eng_state, 0, eng_state_bytes(), m->ctx->stream)); m->eng_launches = 0; graphs_destroy(m);
+    if (m->eng_strikes >= 3) { m->eng_ok = false; m->eng_on = false; }
+    return VOX_OK;
+}
 static EngParams engine_params(vox_model* m, float* logits_out, bool argmax_in = false) {
     const vox_model_cfg& c = m->cfg;
     EngParams ep{}; ep.stream = m->eng_stream; ep.cu_stride = eng_stream_bytes(c.dec_layers, c.vocab) / 256; ep.layers = m->eng_tab; ep.n_layers = c.dec_layers; ep.h_in = m->d_h; ep.final_norm = m->dec_norm;
@@ -2243,11 +2256,9 @@ static int32_t transcribe_dev(vox_model* m, const float* d_mel, int T, const flo
         // of that attempt are not trustworthy -- the SAME utterance is decoded again on the per-operator launches (the encoder output is still in place), the engine is
         // re-armed for the next utterance, and after three strikes it is switched off for the life of the model.
         const unsigned e = m->eng_err_host[0];
-        m->eng_strikes++;
+        VOXCHK(engine_strike(m));
         fprintf(stderr, "[voxtral_hip] decode engine: hand-off timeout (code %u, workgroup %u), strike %d of 3; this utterance is decoded again on the per-operator path%s\n",
                 e & 0xff, (e >> 8) & 0xff, m->eng_strikes, m->eng_strikes >= 3 ? ", the engine is switched off" : "");
-        HIPCHK(hipMemsetAsync(m->eng_state, 0, eng_state_bytes(), s)); m->eng_launches = 0; graphs_destroy(m);
-        if (m->eng_strikes >= 3) { m->eng_ok = false; m->eng_on = false; }
         m->eng_suspended = true; eng_failed = false;
         const int32_t r = decode_once();
         m->eng_suspended = false; graphs_destroy(m);      // (the graph captured during the re-run holds the per-operator launches)
@@ -3285,13 +3296,12 @@ static int32_t pw_engine_verdict(vox_model* m) {
     const unsigned e = *(volatile unsigned*)m->pw_err_pin;
     if (!e) return VOX_OK;
     m->pw_err_pin[0] = 0u; m->pw_eng_used = false;
-    m->eng_strikes++; m->pw_memo = false; m->pw_verdict_failed = true;
+    m->pw_memo = false; m->pw_verdict_failed = true;
     // take back every row that is not known to be good: the failed step's, and whatever was appended behind it before the failure was seen
     int len_now = -1;
     if (m->pw_pend_rows > 0 && m->pw_pend_cache && cache_alive(m->pw_pend_cache, m->pw_pend_gen)) { m->pw_pend_cache->len = std::max(m->pw_pend_cache->len - m->pw_pend_rows, 0); len_now = m->pw_pend_cache->len; }
     m->pw_pend_rows = 0; m->pw_pend_cache = nullptr; if (m->ctx->pw_model == m) m->ctx->pw_model = nullptr;
-    HIPCHK(hipMemsetAsync(m->eng_state, 0, eng_state_bytes(), m->ctx->stream)); m->eng_launches = 0; graphs_destroy(m);
-    if (m->eng_strikes >= 3) { m->eng_ok = false; m->eng_on = false; }
+    VOXCHK(engine_strike(m));
     return fail(VOX_ERR_HIP, "decode engine: hand-off timeout (code %u, workgroup %u), strike %d of 3: the GPU is shared; the KV cache is back at length %d -- repeat the step%s", e & 0xff, (e >> 8) & 0xff, m->eng_strikes,
                 len_now, m->eng_strikes >= 3 ? " (the engine is now switched off, the per-operator launches serve it)" : "");
 }
@@ -3792,5 +3802,359 @@ extern "C" int32_t vox_debug_encode_batch(vox_model* m, int32_t n, const float* 
         o += (size_t)S4[i] * D; rows_per_clip[i] = S4[i];
     }
     report[0] = f.Mtot; report[1] = f.ksp; report[2] = f.ksp_wo; report[3] = f.fused_rope;
+    return VOX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Live streaming session (vox_stream).  16 kHz samples go in in pieces of any size, token ids come back as soon as they are determined, and the
+// concatenation of everything handed back is what vox_transcribe_streaming gives for the log-mel of pad_audio(gain * samples).
+// The session always advances in TICKS of one decoder position -- 4 R mel frames -> R encoder rows -> 1 adapter row -> 1 decode step -- however the samples were cut
+// into pushes: a large push is a loop of identical ticks, so the ids (and which call returns which) are a function of the samples and the gain alone.  It starts from
+// the model's prefix state (encoder rows 0 .. RC-1, decoder positions 0 .. PC-1 of the silent left pad): a live session starts where the silence ends.
+//   schedule: decoder position p is determined once its last mel frame 4 R p + 4 R - 1 is, i.e. once left + n >= 640 R (p + 1) + 40 padded samples exist;
+//   per tick: stream_mel_kernel (4 R new frames + 3 halo frames, token-major) -> conv stem as two small im2col GEMMs on the halo buffer -> enc_layers x { RMSNorm,
+//   q|k|v GEMV, stream_attn_kernel (RoPE + ring append + windowed attention), wo, RMSNorm, w1|w3, w2 } -> final norm, adapter -> stream_embed_kernel -> one decode step
+//   (engine launch while the stream's decoder cache has <= 1024 rows, per-operator launches after) -> stream_advance_kernel (token, state block).
+// ------------------------------------------------------------------------------------------------
+static const int STREAM_SAMPLE_RING = 1 << 16;      // samples held on the device (a tick reads 160 (4 R + 2) + 400 of them)
+static const int STREAM_KEEP_ROWS = 1024;           // adapter rows kept for the re-run of unverified engine steps; a push verifies at least this often
+static const int STREAM_ENGINE_ROWS = 1024;         // the decode engine serves caches of at most this many rows (pw_engine_ready)
+struct vox_stream {
+    vox_model* m = nullptr; vox_ctx* ctx = nullptr;
+    std::vector<float> t_embed; float gain = 1.0f;
+    int cap = 0, max_pos = 0, RC = 0, PC = 0; long left = 0;
+    float *kring = nullptr, *vring = nullptr; size_t ring_layer = 0;      // encoder K / V ring: [enc_layers][enc_heads][cap][hd]
+    vox_cache* dec = nullptr;                                             // decoder cache (grows from STREAM_ENGINE_ROWS rows by doubling, up to max_pos)
+    float *samples = nullptr, *audio_keep = nullptr, *ws = nullptr;
+    int *tokens = nullptr, *state = nullptr;
+    unsigned* err_pin = nullptr;                                          // pinned host copy of the decode engine's error word
+    MelTables mel{};
+    // host mirror of the session
+    int64_t n_pushed = 0, n_written = 0;      // samples the caller gave; samples in the ring (after finish: + the right pad)
+    int pos = 0, ids_out = 0, verified_pos = 0, verified_tap_rows = 0; bool finished = false, eng_unverified = false;
+    uint64_t eng_steps = 0, op_steps = 0, verified_eng_steps = 0, verified_op_steps = 0, bytes = 0;
+    EngLayerTab* eng_tab = nullptr; float* part_val = nullptr; int* part_idx = nullptr;      // the decode engine's layer table for the stream's cache, its argmax partials (256)
+    float* tap = nullptr; int tap_max = 0, tap_rows = 0;
+    int h_state[STRM_WORDS]; int h_pos_word = 0; std::vector<int32_t> h_prefix; std::vector<EngLayerTab> h_tab;
+};
+
+static long stream_spp(int R) { return 640L * R; }      // samples per decoder position: R encoder rows x 4 frames x 160
+// decoder positions determined after n samples of an unfinished stream: position p's last frame 4 R p + 4 R - 1 reads padded samples up to 640 R (p + 1) + 40
+static long stream_positions(long left, int R, int64_t n) { const int64_t a = left + n - 40; return a < 0 ? 0 : (long)(a / stream_spp(R)); }
+
+extern "C" int32_t vox_stream_schedule(size_t n_samples, int32_t finished, int32_t* positions, int32_t* ids) {
+    ARGCHK(positions && ids, "null argument"); ARGCHK(n_samples <= ((size_t)1 << 40), "sample count out of range");
+    vox_pad_cfg pc; vox_pad_cfg_voxtral(&pc);
+    const long left = (long)pad_left(&pc); const int R = 4;
+    long P;
+    if (finished) { size_t total; VOXCHK(vox_pad_len(n_samples, &pc, &total)); P = (long)(total / (size_t)stream_spp(R)); *ids = (int32_t)std::max(P - VOX_PREFIX_TOKENS, 0L); }
+    else { P = stream_positions(left, R, (int64_t)n_samples); *ids = (int32_t)std::max(P - (VOX_PREFIX_TOKENS - 1), 0L); }
+    *positions = (int32_t)P;
+    return VOX_OK;
+}
+
+static int32_t stream_dec_alloc(vox_stream* st, int rows) {      // a fresh decoder cache of `rows` rows (the old one is freed)
+    if (st->dec && st->dec->max_seq == rows) return VOX_OK;
+    if (st->dec) { HIPCHK(hipStreamSynchronize(st->ctx->stream)); cache_unregister(st->dec); (void)hipFree(st->dec->k); (void)hipFree(st->dec->v); delete st->dec; st->dec = nullptr; }
+    return cache_alloc(st->m, rows, &st->dec);
+}
+// the cache is full and the session may go on: twice the rows (at most max_pos), the rows so far copied over.  Happens at a position, not at a push: cut-independent.
+static int32_t stream_dec_grow(vox_stream* st) {
+    vox_model* m = st->m; const vox_model_cfg& c = m->cfg; hipStream_t s = st->ctx->stream; vox_cache* kc = st->dec;
+    const int old = kc->max_seq, rows = std::min(st->max_pos, 2 * old), hd = c.dec_head_dim;
+    ARGCHK(rows > old, "internal: decoder cache of %d rows cannot grow", old);
+    const size_t planes = (size_t)c.dec_layers * c.dec_kv_heads, nb = planes * rows * hd * 4;
+    float *nk = nullptr, *nv = nullptr;
+    if (hipMalloc((void**)&nk, nb) != hipSuccess || hipMalloc((void**)&nv, nb) != hipSuccess) { (void)hipGetLastError(); if (nk) (void)hipFree(nk); return fail(VOX_ERR_HIP, "hipMalloc of a %d-row decoder cache failed", rows); }
+    HIPCHK(hipMemsetAsync(nk, 0, nb, s)); HIPCHK(hipMemsetAsync(nv, 0, nb, s));
+    HIPCHK(hipMemcpy2DAsync(nk, (size_t)rows * hd * 4, kc->k, (size_t)old * hd * 4, (size_t)old * hd * 4, planes, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpy2DAsync(nv, (size_t)rows * hd * 4, kc->v, (size_t)old * hd * 4, (size_t)old * hd * 4, planes, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    (void)hipFree(kc->k); (void)hipFree(kc->v);
+    cache_unregister(kc); kc->k = nk; kc->v = nv; kc->max_seq = rows; kc->layer_stride = (size_t)c.dec_kv_heads * rows * hd; cache_register(kc);      // (a new generation: the engine's layer table for the old planes is stale)
+    return VOX_OK;
+}
+
+// the state after create / reset: the prefix state of the stream's t_embed (built here when the model does not hold it, whatever vox_model_set_prefix_cache says --
+// the model's own setting is restored) copied into the stream's ring, decoder cache and tokens; the stream does not look at the model's copy again
+static int32_t stream_load_initial(vox_stream* st) {
+    vox_model* m = st->m; const vox_model_cfg& c = m->cfg; hipStream_t s = st->ctx->stream; PrefixState& P = m->pfx;
+    const bool was_on = P.on; P.on = true;
+    int32_t r = prefix_build(m, st->t_embed.data());
+    if (r == VOX_OK && !(P.enc_built && P.dec_built && P.RC == st->RC && P.PC == st->PC)) r = fail(VOX_ERR_HIP, "the prefix state a stream starts from could not be built");
+    auto body = [&]() -> int32_t {
+        VOXCHK(stream_dec_alloc(st, std::min(st->max_pos, STREAM_ENGINE_ROWS)));
+        const int H = c.enc_heads, hd = c.enc_head_dim, PC = st->PC, RC = st->RC;
+        HIPCHK(launch_stream_ring_init(P.enc_kv, c.enc_layers, RC, H, hd, st->cap, st->kring, st->vring, s));
+        const size_t rows_bytes = (size_t)PC * c.dec_head_dim * 4, n_rows = (size_t)c.dec_layers * c.dec_kv_heads, pitch = (size_t)st->dec->max_seq * c.dec_head_dim * 4;
+        HIPCHK(hipMemcpy2DAsync(st->dec->k, pitch, P.dec_k, rows_bytes, rows_bytes, n_rows, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpy2DAsync(st->dec->v, pitch, P.dec_v, rows_bytes, rows_bytes, n_rows, hipMemcpyDeviceToDevice, s));
+        st->dec->len = PC;
+        st->h_tab.resize(c.dec_layers);      // the engine's view of THIS cache: no table is rebuilt (and nothing synchronised) when streams and piecewise callers alternate
+        for (int l = 0; l < c.dec_layers; l++) st->h_tab[l] = EngLayerTab{m->dec[l].attn_norm, m->dec[l].ffn_norm, m->dec[l].ada_mul, st->dec->k + (size_t)l * st->dec->layer_stride, st->dec->v + (size_t)l * st->dec->layer_stride};
+        HIPCHK(hipMemcpyAsync(st->eng_tab, st->h_tab.data(), sizeof(EngLayerTab) * c.dec_layers, hipMemcpyHostToDevice, s));
+        st->h_prefix.assign(VOX_PREFIX_TOKENS, VOX_TOK_STREAMING_PAD); st->h_prefix[0] = VOX_TOK_BOS;
+        HIPCHK(hipMemcpyAsync(st->tokens, st->h_prefix.data(), st->h_prefix.size() * 4, hipMemcpyHostToDevice, s));
+        std::memset(st->h_state, 0, sizeof st->h_state);
+        st->h_state[STRM_POS] = PC; st->h_state[STRM_ENC_POS] = RC; st->h_state[STRM_FRAME] = 4 * RC; st->h_state[STRM_HEAD] = RC % st->cap;
+        HIPCHK(hipMemcpyAsync(st->state, st->h_state, sizeof st->h_state, hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return VOX_OK;
+    };
+    if (r == VOX_OK) r = body();
+    if (!was_on) { (void)hipStreamSynchronize(s); prefix_release(m); P.on = false; }
+    if (r != VOX_OK) return r;
+    st->n_pushed = st->n_written = 0; st->pos = st->verified_pos = st->PC; st->ids_out = 0; st->finished = false; st->eng_unverified = false;
+    st->eng_steps = st->op_steps = st->verified_eng_steps = st->verified_op_steps = 0; st->tap_rows = st->verified_tap_rows = 0;
+    return VOX_OK;
+}
+
+static void stream_release(vox_stream* st) {
+    if (!st) return;
+    (void)hipSetDevice(st->ctx->device); (void)hipStreamSynchronize(st->ctx->stream);      // never dereferences st->m: a stream may not outlive its model, but freeing it late must not crash
+    if (st->dec) { cache_unregister(st->dec); (void)hipFree(st->dec->k); (void)hipFree(st->dec->v); delete st->dec; }
+    for (void* p : {(void*)st->kring, (void*)st->vring, (void*)st->samples, (void*)st->audio_keep, (void*)st->ws, (void*)st->tokens, (void*)st->state, (void*)st->tap, (void*)st->eng_tab, (void*)st->part_val, (void*)st->part_idx}) if (p) (void)hipFree(p);
+    if (st->err_pin) (void)hipHostFree(st->err_pin);
+    delete st;
+}
+
+extern "C" int32_t vox_stream_create(vox_model* m, const float* t_embed, float gain, int32_t enc_capacity_rows, int32_t max_positions, vox_stream** out) {
+    ARGCHK(m && t_embed && out, "null argument"); ARGCHK(std::isfinite(gain), "gain is not finite");
+    VOXCHK(ctx_bind(m->ctx));
+    const vox_model_cfg& c = m->cfg; vox_ctx* cx = m->ctx;
+    if (!m->is_q4) return fail(VOX_ERR_UNSUPPORTED, "live streaming sessions serve Q4 (GGUF) models");
+    int RC, PC; prefix_bounds(m, &RC, &PC);
+    ARGCHK(RC > 0 && c.reshape_factor == 4 && PC == VOX_PREFIX_TOKENS - 1, "this model geometry has no prefix state for a stream to start from");
+    if (!m->conv1_g.qs || !m->conv2_g.qs) return fail(VOX_ERR_UNSUPPORTED, "the stream's conv stem runs as im2col GEMMs: 3 n_mels and 3 enc_dim must be multiples of 128");
+    ARGCHK(c.enc_window + 1 <= 1024, "encoder window %d exceeds the stream attention's 1023 keys", c.enc_window);
+    const int R = c.reshape_factor;
+    int cap = enc_capacity_rows; if (cap == 0) cap = (std::max(c.enc_window + 8, RC) + 63) / 64 * 64;      // a ring needs no slack: anything above window + 4 is exact
+    ARGCHK(cap > c.enc_window + 4 && cap >= RC, "encoder ring capacity %d must exceed the sliding window + 4 (%d)", cap, c.enc_window + 4);
+    const int pos_limit = std::min(m->dec_rope_len, (1 << 16) / R);      // the decoder RoPE table and the 65 536-position streaming encoder table end together
+    int maxp = max_positions; if (maxp == 0) maxp = pos_limit;
+    ARGCHK(maxp > VOX_PREFIX_TOKENS && maxp <= pos_limit, "max_positions %d out of range (%d..%d)", maxp, VOX_PREFIX_TOKENS + 1, pos_limit);
+    VOXCHK(enc_stream_rope_ensure(m));
+    vox_stream* st = new vox_stream(); st->m = m; st->ctx = cx; st->t_embed.assign(t_embed, t_embed + c.dec_dim); st->gain = gain; st->cap = cap; st->max_pos = maxp; st->RC = RC; st->PC = PC;
+    { vox_pad_cfg pc; vox_pad_cfg_voxtral(&pc); st->left = (long)pad_left(&pc); }
+    const int D = c.enc_dim, QD = c.enc_heads * c.enc_head_dim, F = c.enc_ffn, DD = c.dec_dim;
+    st->ring_layer = (size_t)c.enc_heads * cap * c.enc_head_dim;
+    const size_t ring_b = (size_t)c.enc_layers * st->ring_layer * 4, keep_b = (size_t)STREAM_KEEP_ROWS * DD * 4;
+    const size_t ws_f = (size_t)(4 * R + 3) * c.n_mels + (size_t)(2 * R + 1) * D + (size_t)2 * R * D + (size_t)R * QD * 4 + (size_t)R * F + m->ad0.w.N + (size_t)2 * DD + 256;
+    hipError_t e = hipSuccess;
+    auto A = [&](void** q, size_t n) { if (e == hipSuccess) { e = hipMalloc(q, n); if (e == hipSuccess) st->bytes += n; } };
+    A((void**)&st->kring, ring_b); A((void**)&st->vring, ring_b); A((void**)&st->samples, (size_t)STREAM_SAMPLE_RING * 4); A((void**)&st->audio_keep, keep_b);
+    A((void**)&st->ws, ws_f * 4); A((void**)&st->tokens, (size_t)(maxp + 2) * 4); A((void**)&st->state, sizeof(int) * STRM_WORDS);
+    A((void**)&st->eng_tab, sizeof(EngLayerTab) * std::max(c.dec_layers, 32)); A((void**)&st->part_val, 256 * 4); A((void**)&st->part_idx, 256 * 4);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&st->err_pin, 8, hipHostMallocDefault);
+    if (e != hipSuccess) { (void)hipGetLastError(); stream_release(st); return fail(VOX_ERR_HIP, "allocating the stream's device state failed: %s", hipGetErrorString(e)); }
+    st->err_pin[0] = st->err_pin[1] = 0u;
+    int32_t r = ctx_mel_tables(cx, &st->mel);
+    if (r == VOX_OK && hipMemsetAsync(st->samples, 0, (size_t)STREAM_SAMPLE_RING * 4, cx->stream) != hipSuccess) r = fail(VOX_ERR_HIP, "hipMemsetAsync failed");
+    if (r == VOX_OK) r = stream_load_initial(st);
+    if (r != VOX_OK) { stream_release(st); return r; }
+    *out = st; return VOX_OK;
+}
+extern "C" int32_t vox_stream_free(vox_stream* st) { stream_release(st); return VOX_OK; }
+extern "C" int32_t vox_stream_reset(vox_stream* st) {
+    ARGCHK(st, "null stream"); VOXCHK(ctx_bind(st->ctx));
+    HIPCHK(hipStreamSynchronize(st->ctx->stream));
+    return stream_load_initial(st);
+}
+extern "C" int32_t vox_stream_info(const vox_stream* st, int64_t out[8]) {
+    ARGCHK(st && out, "null argument");
+    const int R = st->m->cfg.reshape_factor;
+    const uint64_t dec_b = st->dec ? 2 * (uint64_t)st->m->cfg.dec_layers * st->dec->layer_stride * 4 : 0, tap_b = st->tap ? (uint64_t)st->tap_max * st->m->cfg.vocab * 4 : 0;
+    out[0] = st->n_pushed; out[1] = st->pos; out[2] = st->ids_out; out[3] = (int64_t)R * st->pos; out[4] = std::min<int64_t>((int64_t)R * st->pos, st->cap);
+    out[5] = (int64_t)(st->bytes + dec_b + tap_b); out[6] = (int64_t)st->eng_steps; out[7] = (int64_t)st->op_steps;
+    return VOX_OK;
+}
+
+// the decode step of a tick: input row in the stream's h buffer, position in the state block.  enc_rows = 0: the re-run of an unverified step (the state's encoder
+// words stay).  logits_row: where the step's f32 logits go (the tap), or null.
+static int32_t stream_decode_step(vox_stream* st, float* h, float* logits_row, int enc_rows) {
+    vox_model* m = st->m; hipStream_t s = st->ctx->stream; vox_cache* kc = st->dec;
+    ARGCHK(kc->len == st->pos && st->pos < kc->max_seq, "internal: stream decoder cache at %d, position %d of %d", kc->len, st->pos, kc->max_seq);
+    int* pos_word = st->state + STRM_POS;
+    // the engine's conditions on a caller's cache (pw_engine_ready) with the stream's own layer table and argmax partials
+    bool eng = m->eng_ok && m->eng_on && !m->eng_suspended && kc->max_seq <= STREAM_ENGINE_ROWS;
+    if (eng) eng = engine_stream_prepare(m) == VOX_OK && m->eng_ready;
+    if (eng) {      // one launch: the layers against the stream's cache + final norm + lm_head (argmax partials, logits on request)
+        if (m->eng_launches + 16 > (1ull << 25)) { HIPCHK(hipMemsetAsync(m->eng_state, 0, eng_state_bytes(), s)); m->eng_launches = 0; }
+        m->eng_launches += 1;
+        EngParams ep = pw_engine_params(m, kc, h); ep.layers = st->eng_tab; ep.part_val = st->part_val; ep.part_idx = st->part_idx;
+        ep.pos_ptr = pos_word; ep.pos_off = 0; ep.logits_out = logits_row;
+        HIPCHK(launch_decode_engine(ep, s));
+        HIPCHK(launch_stream_advance(st->part_val, st->part_idx, 256, st->tokens, st->state, enc_rows, 4 * enc_rows, st->cap, s));
+        st->eng_steps++; st->eng_unverified = true;
+    } else {
+        VOXCHK(decoder_step_dev(m, h, kc, pos_word, 0));
+        VOXCHK(lm_head_argmax_dev(m, h, logits_row));
+        HIPCHK(launch_stream_advance(m->d_part_val, m->d_part_idx, m->n_parts, st->tokens, st->state, enc_rows, 4 * enc_rows, st->cap, s));
+        st->op_steps++;
+    }
+    kc->len = ++st->pos;
+    return VOX_OK;
+}
+static float* stream_tap_row(vox_stream* st) {
+    if (!st->tap) return nullptr;
+    const int k = st->tap_rows++;
+    return k < st->tap_max ? st->tap + (size_t)k * st->m->cfg.vocab : nullptr;
+}
+// behind the decode-engine steps since the last verification: synchronise, read the engine's error word; a hand-off timeout (the GPU is shared) takes those steps back and
+// runs them again on the per-operator launches from the kept adapter rows -- the caller sees ids, not an error (the policy of transcribe_dev; three strikes switch the engine off)
+static int32_t stream_verify_enqueue(vox_stream* st) {      // the engine's error word on its way to the pinned host word (lands with the next synchronisation)
+    if (!st->eng_unverified) return VOX_OK;
+    EngParams ep{}; eng_state_carve(st->m->eng_state, &ep);
+    HIPCHK(hipMemcpyAsync(st->err_pin, ep.err, 8, hipMemcpyDeviceToHost, st->ctx->stream));
+    return VOX_OK;
+}
+static int32_t stream_settle(vox_stream* st, bool* reran) {      // behind that synchronisation
+    vox_model* m = st->m; const vox_model_cfg& c = m->cfg; hipStream_t s = st->ctx->stream;
+    if (reran) *reran = false;
+    const unsigned e = st->eng_unverified ? st->err_pin[0] : 0u;
+    st->eng_unverified = false;
+    if (e) {
+        st->err_pin[0] = 0u; VOXCHK(engine_strike(m));
+        const int p0 = st->verified_pos, p1 = st->pos;
+        fprintf(stderr, "[voxtral_hip] decode engine: hand-off timeout (code %u, workgroup %u), strike %d of 3; the stream's steps %d..%d are decoded again on the per-operator path%s\n",
+                e & 0xff, (e >> 8) & 0xff, m->eng_strikes, p0, p1 - 1, m->eng_strikes >= 3 ? ", the engine is switched off" : "");
+        ARGCHK(p1 - p0 <= STREAM_KEEP_ROWS, "internal: %d unverified stream steps", p1 - p0);
+        st->eng_steps = st->verified_eng_steps; st->op_steps = st->verified_op_steps;      // the re-run below counts every step again, on the path it then takes
+        st->pos = p0; st->dec->len = p0; st->tap_rows = st->verified_tap_rows; st->h_pos_word = p0;
+        HIPCHK(hipMemcpyAsync(st->state + STRM_POS, &st->h_pos_word, 4, hipMemcpyHostToDevice, s));
+        if (m->d_wo_acc) HIPCHK(hipMemsetAsync(m->d_wo_acc, 0, (size_t)c.dec_layers * c.dec_dim * 8, s));
+        float* h = st->ws;      // (the tick's buffers are free between ticks)
+        m->eng_suspended = true;
+        int32_t r = VOX_OK;
+        for (int p = p0; p < p1 && r == VOX_OK; p++) {
+            const hipError_t he = launch_stream_embed_kept(m->tok.w, st->tokens, st->audio_keep, STREAM_KEEP_ROWS, c.dec_dim, st->state, h, s);
+            if (he != hipSuccess) { r = fail(VOX_ERR_HIP, "launch_stream_embed_kept failed: %s", hipGetErrorString(he)); break; }
+            r = stream_decode_step(st, h, stream_tap_row(st), 0);
+        }
+        m->eng_suspended = false;
+        VOXCHK(r);
+        HIPCHK(hipStreamSynchronize(s));
+        if (reran) *reran = true;
+    }
+    st->verified_pos = st->pos; st->verified_tap_rows = st->tap_rows; st->verified_eng_steps = st->eng_steps; st->verified_op_steps = st->op_steps;
+    return VOX_OK;
+}
+static int32_t stream_verify(vox_stream* st) {      // inside a long push: before the kept rows run out, before the decoder cache moves
+    if (st->eng_unverified) { VOXCHK(stream_verify_enqueue(st)); HIPCHK(hipStreamSynchronize(st->ctx->stream)); }
+    return stream_settle(st, nullptr);
+}
+
+static int32_t stream_tick(vox_stream* st) {
+    vox_model* m = st->m; const vox_model_cfg& c = m->cfg; vox_ctx* cx = st->ctx; hipStream_t s = cx->stream;
+    const int D = c.enc_dim, H = c.enc_heads, hd = c.enc_head_dim, QD = H * hd, F = c.enc_ffn, R = c.reshape_factor, DD = c.dec_dim, Cm = c.n_mels;
+    const int NF = 4 * R + 3, N1 = 2 * R + 1;      // mel frames with the halo (conv row s reads frames 4 s - 3 .. 4 s + 3), conv1 rows with theirs (2 s - 1 .. 2 s + 1)
+    if (st->pos - st->verified_pos >= STREAM_KEEP_ROWS) VOXCHK(stream_verify(st));      // the kept adapter rows cover the unverified steps
+    if (st->pos >= st->dec->max_seq) { VOXCHK(stream_verify(st)); VOXCHK(stream_dec_grow(st)); }
+    float* halo = st->ws; float* c1 = halo + (size_t)NF * Cm; float* x = c1 + (size_t)N1 * D; float* xn = x + (size_t)R * D; float* qkv = xn + (size_t)R * D;
+    float* att = qkv + (size_t)R * QD * 3; float* ffn = att + (size_t)R * QD; float* ah = ffn + (size_t)R * F; float* arow = ah + m->ad0.w.N; float* h = arow + DD;
+    HIPCHK(launch_stream_mel(st->samples, STREAM_SAMPLE_RING - 1, st->left, st->gain, st->mel, st->state, 3, NF, halo, s));
+    // conv stem without padding rows, memsets or a transpose: conv1 row i of the tick is the window of halo rows [2 i, 2 i + 2], conv row i the window of conv1 rows [2 i, 2 i + 2]
+    { GemmParams g{}; g.w = m->conv1_g; g.x = halo; g.x_stride = 2 * Cm; g.M = N1; g.out = c1; g.out_stride = D; g.bias = m->conv1_b; HIPCHK(launch_dense2_gemm(g, EPI_GELU, s)); }
+    { GemmParams g{}; g.w = m->conv2_g; g.x = c1; g.x_stride = 2 * D; g.M = R; g.out = x; g.out_stride = D; g.bias = m->conv2_b; HIPCHK(launch_dense2_gemm(g, EPI_GELU, s)); }
+    for (int l = 0; l < c.enc_layers; l++) {
+        const EncLayer& L = m->enc[l];
+        HIPCHK(launch_rms_norm(x, D, R, D, L.attn_norm, nullptr, c.norm_eps, xn, D, s));
+        VOXCHK(q4_linear_dev(cx, L.wqkv.w, L.wqkv.bias, xn, D, R, qkv, 3 * QD));
+        StreamAttnParams ap{}; ap.qkv = qkv; ap.qkv_stride = 3 * QD; ap.kring = st->kring + (size_t)l * st->ring_layer; ap.vring = st->vring + (size_t)l * st->ring_layer; ap.cap = st->cap;
+        ap.cos_t = m->enc_cos_s; ap.sin_t = m->enc_sin_s; ap.state = st->state; ap.out = att; ap.out_stride = QD; ap.M = R; ap.n_heads = H; ap.window = c.enc_window;
+        HIPCHK(launch_stream_attn(ap, hd, s));
+        VOXCHK(q4_linear_dev(cx, L.wo.w, L.wo.bias, att, QD, R, x, D, EPI_RESID, x, D));
+        HIPCHK(launch_rms_norm(x, D, R, D, L.ffn_norm, nullptr, c.norm_eps, xn, D, s));
+        VOXCHK(q4_linear_dev(cx, L.w13.w, nullptr, xn, D, R, ffn, F, EPI_SWIGLU));
+        VOXCHK(q4_linear_dev(cx, L.w2.w, L.w2.bias, ffn, F, R, x, D, EPI_RESID, x, D));
+    }
+    HIPCHK(launch_rms_norm(x, D, R, D, m->enc_norm, nullptr, c.norm_eps, xn, D, s));
+    VOXCHK(q4_linear_dev(cx, m->ad0.w, nullptr, xn, D * R, 1, ah, m->ad0.w.N, EPI_GELU));      // the R rows viewed as one [R D] row (models/adapter.rs:108-122)
+    VOXCHK(q4_linear_dev(cx, m->ad2.w, nullptr, ah, m->ad0.w.N, 1, arow, DD));
+    HIPCHK(launch_stream_embed(m->tok.w, st->tokens, arow, st->audio_keep, STREAM_KEEP_ROWS, DD, st->state, h, s));
+    return stream_decode_step(st, h, stream_tap_row(st), R);
+}
+
+// append `n` samples (src null: zeros, the right pad) and run every tick up to position `target` as soon as its samples are in the ring
+static int32_t stream_feed(vox_stream* st, const float* src, size_t n, int32_t mem_kind, int target) {
+    hipStream_t s = st->ctx->stream; const int R = st->m->cfg.reshape_factor;
+    size_t done = 0;
+    while (done < n || st->pos < target) {
+        const long lo = std::max(0L, (4L * R * st->pos - 3) * 160 - 200 - st->left);      // the oldest sample the next tick reads
+        const size_t room = (size_t)STREAM_SAMPLE_RING - (size_t)(st->n_written - lo), chunk = std::min(n - done, room);
+        for (size_t w = 0; w < chunk;) {      // at most two pieces: the ring wraps
+            const size_t off = (size_t)((st->n_written + (int64_t)w) & (STREAM_SAMPLE_RING - 1)), len = std::min(chunk - w, (size_t)STREAM_SAMPLE_RING - off);
+            if (!src) HIPCHK(hipMemsetAsync(st->samples + off, 0, len * 4, s));
+            else HIPCHK(hipMemcpyAsync(st->samples + off, src + done + w, len * 4, mem_kind == VOX_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+            w += len;
+        }
+        st->n_written += (int64_t)chunk; done += chunk;
+        const int avail = (int)std::min<long>(target, stream_positions(st->left, R, st->n_written));
+        if (chunk == 0 && st->pos >= avail) return fail(VOX_ERR_INVALID, "internal: stream stalled at position %d of %d", st->pos, target);
+        while (st->pos < avail) VOXCHK(stream_tick(st));
+    }
+    return VOX_OK;
+}
+// what a push / finish does around its ticks: the stream's own Ada scales, clean accumulators, then the ids of the call behind ONE synchronisation
+static int32_t stream_run(vox_stream* st, const float* src, size_t n, int32_t mem_kind, int target, int32_t* out_ids, int32_t* n_ids) {
+    vox_model* m = st->m; const vox_model_cfg& c = m->cfg; hipStream_t s = st->ctx->stream;
+    const int due = target - st->pos;
+    if (m->pw_pend_rows > 0) VOXCHK(pw_sync(m));      // unverified engine steps of the piecewise surface share the engine's error word: settled first
+    VOXCHK(vox_model_set_t_embed(m, st->t_embed.data()));
+    if (due > 0 && m->d_wo_acc) HIPCHK(hipMemsetAsync(m->d_wo_acc, 0, (size_t)c.dec_layers * c.dec_dim * 8, s));
+    VOXCHK(stream_feed(st, src, n, mem_kind, target));
+    int32_t* ids_dev = st->tokens + VOX_PREFIX_TOKENS + st->ids_out;
+    VOXCHK(stream_verify_enqueue(st));
+    if (due > 0) HIPCHK(hipMemcpyAsync(out_ids, ids_dev, (size_t)due * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));      // the call's one synchronisation: ids and the engine's verdict land together
+    bool reran = false; VOXCHK(stream_settle(st, &reran));
+    if (reran && due > 0) { HIPCHK(hipMemcpyAsync(out_ids, ids_dev, (size_t)due * 4, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s)); }
+    st->ids_out += due; *n_ids = due;
+    return VOX_OK;
+}
+
+extern "C" int32_t vox_stream_push(vox_stream* st, const float* samples, size_t n, int32_t mem_kind, int32_t* out_ids, int32_t cap, int32_t* n_ids) {
+    ARGCHK(st && n_ids && (samples || n == 0), "null argument"); ARGCHK(cap >= 0 && (out_ids || cap == 0), "bad output buffer"); ARGCHK(n <= ((size_t)1 << 36), "push of %zu samples", n);
+    ARGCHK(mem_kind == VOX_MEM_HOST || mem_kind == VOX_MEM_DEVICE, "bad mem_kind %d", mem_kind);
+    ARGCHK(!st->finished, "the stream is finished: vox_stream_reset starts the next utterance");
+    const long P = stream_positions(st->left, st->m->cfg.reshape_factor, st->n_pushed + (int64_t)n);
+    ARGCHK(P <= st->max_pos, "the push would reach decoder position %ld of a stream created for %d (vox_stream_reset starts over)", P, st->max_pos);
+    const int target = std::max((int)P, st->pos), due = target - st->pos;
+    ARGCHK(cap >= due, "out_ids capacity %d < %d ids due", cap, due);      // BEFORE anything is appended: the call can be repeated
+    VOXCHK(ctx_bind(st->ctx));
+    st->n_pushed += (int64_t)n;
+    return stream_run(st, samples, n, mem_kind, target, out_ids, n_ids);
+}
+extern "C" int32_t vox_stream_finish(vox_stream* st, int32_t* out_ids, int32_t cap, int32_t* n_ids) {
+    ARGCHK(st && n_ids, "null argument"); ARGCHK(cap >= 0 && (out_ids || cap == 0), "bad output buffer");
+    ARGCHK(!st->finished, "the stream is finished already");
+    vox_pad_cfg pc; vox_pad_cfg_voxtral(&pc);
+    size_t total; VOXCHK(vox_pad_len((size_t)st->n_pushed, &pc, &total));
+    const int S = (int)(total / (size_t)stream_spp(st->m->cfg.reshape_factor));
+    ARGCHK(S - 1 <= st->max_pos, "finishing would reach decoder position %d of a stream created for %d", S - 1, st->max_pos);
+    const int target = std::max(S - 1, st->pos), due = target - st->pos;      // the steps at positions 37 .. S - 2 yield the S - 38 ids of the offline path
+    ARGCHK(cap >= due, "out_ids capacity %d < %d ids due", cap, due);
+    VOXCHK(ctx_bind(st->ctx));
+    const size_t right = total - (size_t)st->left - (size_t)st->n_pushed;
+    VOXCHK(stream_run(st, nullptr, right, VOX_MEM_DEVICE, target, out_ids, n_ids));
+    st->finished = true;
+    return VOX_OK;
+}
+
+extern "C" int32_t vox_debug_stream_tap_arm(vox_stream* st, int32_t max_rows) {
+    ARGCHK(st, "null stream"); ARGCHK(max_rows > 0 && max_rows <= 65536, "max_rows %d out of range (1..65536)", max_rows); VOXCHK(ctx_bind(st->ctx));
+    HIPCHK(hipStreamSynchronize(st->ctx->stream));
+    if (st->tap) { (void)hipFree(st->tap); st->tap = nullptr; }
+    HIPCHK(hipMalloc((void**)&st->tap, (size_t)max_rows * st->m->cfg.vocab * 4));
+    st->tap_max = max_rows; st->tap_rows = st->verified_tap_rows = 0;
+    return VOX_OK;
+}
+extern "C" int32_t vox_debug_stream_tap_fetch(vox_stream* st, float* out, int32_t* rows) {
+    ARGCHK(st && out && rows, "null argument"); ARGCHK(st->tap, "no stream tap to fetch (vox_debug_stream_tap_arm)"); VOXCHK(ctx_bind(st->ctx));
+    HIPCHK(hipStreamSynchronize(st->ctx->stream));
+    const int k = std::min(st->tap_rows, st->tap_max);
+    if (k > 0) HIPCHK(hipMemcpy(out, st->tap, (size_t)k * st->m->cfg.vocab * 4, hipMemcpyDeviceToHost));
+    *rows = st->tap_rows;
+    (void)hipFree(st->tap); st->tap = nullptr; st->tap_max = 0; st->tap_rows = st->verified_tap_rows = 0;
     return VOX_OK;
 }

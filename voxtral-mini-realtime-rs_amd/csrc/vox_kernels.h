@@ -171,7 +171,7 @@ bool attn_wo_supported(const AttnParams& p, const Q4W& wo, int hd, int max_seq);
 hipError_t launch_attn_wo(const AttnParams& p, const Q4W& wo, long long* acc, int max_seq, hipStream_t s);
 // host-side launch counts of the attention kernels and of the single-stream decode engine, by form (vox_debug_attn_launches: tests assert which path a call took)
 enum AttnForm { ATTN_FORM_PREFILL_SMALL, ATTN_FORM_PREFILL_MFMA, ATTN_FORM_PREFILL_F32, ATTN_FORM_DECODE, ATTN_FORM_DECODE_SPEC, ATTN_FORM_DECODE_GQA, ATTN_FORM_WO,
-                ATTN_FORM_ENGINE, ATTN_FORM_COUNT };
+                ATTN_FORM_ENGINE, ATTN_FORM_STREAM_RING, ATTN_FORM_COUNT };
 void attn_form_note(AttnForm f);
 void attn_form_counts(unsigned long long out[ATTN_FORM_COUNT]);
 // host-side launch counts of the linear kernels, by form (vox_debug_gemm_launches: tests assert which kernel a shape ran; counters only, nothing is dispatched by them).
@@ -352,5 +352,38 @@ const char* knob_str(const char* name);      // nullptr when unset
 hipError_t tl_configure(unsigned long long* buf, int n_slots, int n_waves);   // buf == nullptr: off
 int tl_slots_used();
 void tl_slot_meta(int slot, int out[4]);    // {0 gemv / 1 attention, epi, N, K} of the launch that took `slot`
+
+// ---- live streaming session (vox_stream): the session advances in TICKS of one decoder position (16 mel frames -> 4 encoder rows -> 1 adapter row ->
+// 1 decode step).  The integers a tick depends on live in one device block per stream, advanced by the tick's last kernel, so a tick's launch arguments never change.
+enum StreamWord { STRM_POS = 0,         // decoder position of the next tick (= its adapter row, its decoder cache row; the step yields tokens[position + 1])
+                  STRM_ENC_POS = 1,     // encoder stream position of the tick's first row (RoPE position, ring row before the modulo)
+                  STRM_FRAME = 2,       // first NEW mel frame of the tick (the halo starts halo_back frames before it)
+                  STRM_HEAD = 3,        // STRM_ENC_POS modulo the ring capacity
+                  STRM_TICKS = 4,       // ticks run since create / reset
+                  STRM_WORDS = 16 };    // block size in ints (the rest is reserved: a later group of N streams holds N such blocks back to back)
+// front end: the log-mel frames STRM_FRAME - halo_back .. + n_frames - 1 of the virtually padded signal zeros(left) + gain * samples, token-major ([n_frames][128]: the layout the
+// conv stem's im2col GEMM reads).  Sample i of the stream lives at ring[i & ring_mask]; every sample a frame reads has been written (the host runs a tick only then),
+// the reflections of mel_kernel never apply (left >= 200, and the right end of a finished stream is its zero pad).
+hipError_t launch_stream_mel(const float* ring, int ring_mask, long left, float gain, MelTables t, const int* state, int halo_back, int n_frames, float* out, hipStream_t s);
+// one encoder layer's attention for the tick's M <= 8 rows against the stream's K / V ring: RoPE on q and k at the absolute stream position, k / v appended at
+// position % cap, query m attends the keys j <= position_m, position_m - j <= window in ascending order of j (the ring changes addresses, not the order).  cap > window + M.
+struct StreamAttnParams {
+    const float* qkv; int qkv_stride;        // [M][q | k | v], each n_heads * hd wide, not rotated
+    float* kring; float* vring; int cap;     // this layer's ring, [n_heads][cap][hd]
+    const float* cos_t; const float* sin_t;  // [positions][hd / 2]
+    const int* state;
+    float* out; int out_stride;              // [M][n_heads * hd]
+    int M, n_heads, window;
+};
+hipError_t launch_stream_attn(const StreamAttnParams& p, int hd, hipStream_t s);
+// rows 0 .. rows-1 of every layer's ring from token-major k | v rows (the model's prefix state: [layers][rows][k row | v row])
+hipError_t launch_stream_ring_init(const float* kv, int layers, int rows, int n_heads, int hd, int cap, float* kring, float* vring, hipStream_t s);
+// h = audio_row + embed(tokens[STRM_POS]); the adapter row is also kept in audio_keep[STRM_POS % keep_rows] (an engine hand-off timeout re-runs the decode steps from there)
+hipError_t launch_stream_embed(Q4W tok, const int* tokens, const float* audio_row, float* audio_keep, int keep_rows, int D, const int* state, float* h, hipStream_t s);
+// the same input from the kept row (the re-run)
+hipError_t launch_stream_embed_kept(Q4W tok, const int* tokens, const float* audio_keep, int keep_rows, int D, const int* state, float* h, hipStream_t s);
+// tokens[STRM_POS + 1] = argmax over the lm_head partials (lowest index wins ties), then the state advances by one tick (enc_rows encoder rows, frames mel frames;
+// enc_rows = 0: a decode-only re-run moves STRM_POS alone)
+hipError_t launch_stream_advance(const float* part_val, const int* part_idx, int n_parts, int* tokens, int* state, int enc_rows, int frames, int cap, hipStream_t s);
 
 }  // namespace vox

@@ -4204,4 +4204,205 @@ hipError_t launch_gelu(float* x, long n, hipStream_t s) {
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// live streaming session (vox_stream): the kernels of one tick that are not the row-independent operators.  Every per-tick integer comes from the stream's device
+// state block (StreamWord), so the launch arguments of a tick never change.
+// ------------------------------------------------------------------------------------------------
+// front end: mel_kernel's arithmetic (windowed frame, 400-point table DFT, Slaney bank, log10 / floor / scale) on frames of a sample ring, written token-major with
+// the conv stem's halo in front.  No reflection branch: the host guarantees left >= 200 and runs a tick only when every sample its frames read has been written.
+__global__ __launch_bounds__(256) void stream_mel_kernel(const float* __restrict__ ring, int ring_mask, long left, float gain, MelTables t, const int* __restrict__ state,
+                                                         int halo_back, float* __restrict__ out) {
+    __shared__ float fr[400];
+    __shared__ float ct[400], st[400];
+    __shared__ float pw[201 + 3];
+    const int tid = threadIdx.x;
+    const long f = (long)state[STRM_FRAME] - halo_back + blockIdx.x;
+    for (int j = tid; j < 400; j += 256) {
+        const long ai = f * 160 + j - 200 - left;      // index into the stream's samples; below 0: the silent left pad
+        float v = 0.f;
+        if (ai >= 0) { v = ring[ai & (long)ring_mask]; v *= gain; }
+        fr[j] = v * t.window[j];
+        ct[j] = t.cos_t[j]; st[j] = t.sin_t[j];
+    }
+    __syncthreads();
+    if (tid < 201) {
+        float re = 0.f, im = 0.f; int ph = 0;
+        for (int j = 0; j < 400; j++) {
+            const float v = fr[j];
+            re = fmaf(v, ct[ph], re); im = fmaf(-v, st[ph], im);
+            ph += tid; if (ph >= 400) ph -= 400;
+        }
+        pw[tid] = re * re + im * im;
+    }
+    __syncthreads();
+    if (tid < 128) {
+        const int lo = t.fb_lo[tid], hi = t.fb_hi[tid];
+        const float* row = t.fb + tid * 201;
+        float acc = 0.f;
+        for (int j = lo; j < hi; j++) acc += row[j] * pw[j];
+        float v = log10f(fmaxf(acc, 1e-10f));
+        v = fmaxf(v, 1.5f - 8.0f);
+        v = (v + 4.0f) / 4.0f;
+        out[(size_t)blockIdx.x * 128 + tid] = v;
+    }
+}
+hipError_t launch_stream_mel(const float* ring, int ring_mask, long left, float gain, MelTables t, const int* state, int halo_back, int n_frames, float* out, hipStream_t s) {
+    if (n_frames <= 0 || left < 200 || (ring_mask & (ring_mask + 1))) return hipErrorInvalidValue;
+    stream_mel_kernel<<<dim3(n_frames), dim3(256), 0, s>>>(ring, ring_mask, left, gain, t, state, halo_back, out);
+    return hipGetLastError();
+}
+
+// RoPE + K / V append + windowed attention of one encoder layer for the tick's rows, one workgroup per (head, query row).  The workgroup rotates the tick's k rows
+// 0 .. m of its head itself (LDS), so no workgroup reads a ring row another one writes in this launch: ring rows are read for positions below the tick's first only, and
+// with cap > window + M the rows written now hold positions no query of the tick sees any more.  Scores: 16 lanes per key (one float4 each at hd 64), the keys in
+// ascending position; softmax and the weighted sum in fixed order over the key index relative to the window start -- the ring capacity changes addresses only.
+// (VOX_NO_PK_F32: the rotation is the pair arithmetic of rope_kernel.)
+template <int HD>
+__global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_attn_kernel(const StreamAttnParams p) {
+    constexpr int HALF = HD / 2, G = 256 / HD;
+    __shared__ __attribute__((aligned(16))) float qs[HD];
+    __shared__ __attribute__((aligned(16))) float kn[8][HD];
+    __shared__ __attribute__((aligned(16))) float vn[8][HD];
+    __shared__ float sc[1024];
+    __shared__ float red[G][HD];
+    __shared__ float wred[4];
+    const int h = blockIdx.x, m = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int enc_pos = p.state[STRM_ENC_POS], qpos = enc_pos + m, QD = p.n_heads * HD;
+    for (int i = tid; i < (m + 2) * HALF; i += 256) {      // k rows 0 .. m, then the query row
+        const int r = i / HALF, j = i - r * HALF; const bool isq = r == m + 1; const int row = isq ? m : r;
+        const size_t ti = (size_t)(enc_pos + row) * HALF + j;
+        const float c = p.cos_t[ti], sn = p.sin_t[ti];
+        const float* src = p.qkv + (size_t)row * p.qkv_stride + (isq ? 0 : QD) + h * HD + 2 * j;
+        const float xr = src[0], xi = src[1];
+        float* dst = isq ? qs : kn[r];
+        dst[2 * j] = xr * c - xi * sn; dst[2 * j + 1] = xr * sn + xi * c;
+    }
+    for (int i = tid; i < (m + 1) * HD; i += 256) { const int r = i / HD, d = i - r * HD; vn[r][d] = p.qkv[(size_t)r * p.qkv_stride + 2 * QD + h * HD + d]; }
+    __syncthreads();
+    const size_t hbase = (size_t)h * p.cap * HD;
+    if (tid < HD) { const size_t slot = hbase + (size_t)(qpos % p.cap) * HD + tid; p.kring[slot] = kn[m][tid]; p.vring[slot] = vn[m][tid]; }
+    const int j0 = max(0, qpos - p.window), nk = qpos - j0 + 1;      // keys j0 .. qpos (host: window + 1 <= 1024)
+    const int g = tid >> 4, li = tid & 15;
+    const float scale = HD == 64 ? 0.125f : 0.08838834764831845f;      // head_dim^-0.5
+    for (int i0 = 0; i0 < nk; i0 += 16) {      // uniform trip count: the row sums below need every lane
+        const int i = min(i0 + g, nk - 1), j = j0 + i;
+        float dot = 0.f;
+#pragma unroll
+        for (int u = 0; u < HD / 64; u++) {
+            const int o = (u * 16 + li) * 4;
+            const float4 kv = j < enc_pos ? *reinterpret_cast<const float4*>(p.kring + hbase + (size_t)(j % p.cap) * HD + o) : *reinterpret_cast<const float4*>(&kn[j - enc_pos][o]);
+            const float4 qv = *reinterpret_cast<const float4*>(&qs[o]);
+            dot = fmaf(qv.x, kv.x, dot); dot = fmaf(qv.y, kv.y, dot); dot = fmaf(qv.z, kv.z, dot); dot = fmaf(qv.w, kv.w, dot);
+        }
+        dot = row16_sum(dot);
+        if (li == 0 && i0 + g < nk) sc[i] = dot * scale;
+    }
+    __syncthreads();
+    float mx = -INFINITY;
+    for (int i = tid; i < nk; i += 256) mx = fmaxf(mx, sc[i]);
+    mx = wave_max(mx);
+    if (lane == 0) wred[wave] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(wred[0], wred[1]), fmaxf(wred[2], wred[3]));
+    __syncthreads();
+    float sum = 0.f;
+    for (int i = tid; i < nk; i += 256) { const float e = expf(sc[i] - mx); sc[i] = e; sum += e; }
+    sum = wave_sum(sum);
+    if (lane == 0) wred[wave] = sum;
+    __syncthreads();
+    sum = (wred[0] + wred[1]) + (wred[2] + wred[3]);
+    const int d = tid % HD, kg = tid / HD;
+    float acc = 0.f;
+    for (int i = kg; i < nk; i += G) {
+        const int j = j0 + i;
+        const float vv = j < enc_pos ? p.vring[hbase + (size_t)(j % p.cap) * HD + d] : vn[j - enc_pos][d];
+        acc = fmaf(sc[i], vv, acc);
+    }
+    red[kg][d] = acc;
+    __syncthreads();
+    if (tid < HD) {
+        float o = red[0][tid];
+#pragma unroll
+        for (int q = 1; q < G; q++) o += red[q][tid];
+        p.out[(size_t)m * p.out_stride + h * HD + tid] = o / sum;
+    }
+}
+hipError_t launch_stream_attn(const StreamAttnParams& p, int hd, hipStream_t s) {
+    if (p.M < 1 || p.M > 8 || p.window < 0 || p.window + 1 > 1024 || p.cap <= p.window + p.M || ((uintptr_t)p.kring & 15) || ((uintptr_t)p.vring & 15)) return hipErrorInvalidValue;      // (the ring rows are read as float4: hd % 4 == 0 holds for 64 / 128)
+    attn_form_note(ATTN_FORM_STREAM_RING);
+    if (hd == 64) stream_attn_kernel<64><<<dim3(p.n_heads, p.M), dim3(256), 0, s>>>(p);
+    else if (hd == 128) stream_attn_kernel<128><<<dim3(p.n_heads, p.M), dim3(256), 0, s>>>(p);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+__global__ void stream_ring_init_kernel(const float* __restrict__ kv, int layers, int rows, int n_heads, int hd, int cap, float* __restrict__ kring, float* __restrict__ vring) {
+    const int QD = n_heads * hd;
+    const long total = (long)layers * rows * QD;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int c = (int)(i % QD); const long lr = i / QD; const int r = (int)(lr % rows), l = (int)(lr / rows), h = c / hd, d = c - h * hd;
+        const size_t dst = (((size_t)l * n_heads + h) * cap + r) * hd + d, src = (size_t)lr * 2 * QD + c;
+        kring[dst] = kv[src]; vring[dst] = kv[src + QD];
+    }
+}
+hipError_t launch_stream_ring_init(const float* kv, int layers, int rows, int n_heads, int hd, int cap, float* kring, float* vring, hipStream_t s) {
+    if (rows <= 0 || rows > cap) return hipErrorInvalidValue;
+    const long total = (long)layers * rows * n_heads * hd;
+    int blocks = (int)((total + 255) / 256); if (blocks > 2048) blocks = 2048;
+    stream_ring_init_kernel<<<dim3(blocks), dim3(256), 0, s>>>(kv, layers, rows, n_heads, hd, cap, kring, vring);
+    return hipGetLastError();
+}
+
+// the decode step's input row of a tick (gguf/model.rs:942-948 with the audio row just made by the adapter); KEEP: the adapter row is copied to the stream's kept rows first
+template <int KEEP>
+__global__ __launch_bounds__(256) void stream_embed_kernel(Q4W tok, const int* __restrict__ tokens, const float* __restrict__ audio_row, float* __restrict__ audio_keep, int keep_rows,
+                                                           int D, const int* __restrict__ state, float* __restrict__ h) {
+    const int pos = state[STRM_POS];
+    float* kept = audio_keep + (size_t)(pos % keep_rows) * D;
+    if (KEEP) for (int i = threadIdx.x; i < D; i += 256) kept[i] = audio_row[i];
+    embed_row(tok, tokens[pos], KEEP ? audio_row : kept, h, D);
+}
+hipError_t launch_stream_embed(Q4W tok, const int* tokens, const float* audio_row, float* audio_keep, int keep_rows, int D, const int* state, float* h, hipStream_t s) {
+    stream_embed_kernel<1><<<dim3(1), dim3(256), 0, s>>>(tok, tokens, audio_row, audio_keep, keep_rows, D, state, h);
+    return hipGetLastError();
+}
+hipError_t launch_stream_embed_kept(Q4W tok, const int* tokens, const float* audio_keep, int keep_rows, int D, const int* state, float* h, hipStream_t s) {
+    stream_embed_kernel<0><<<dim3(1), dim3(256), 0, s>>>(tok, tokens, nullptr, const_cast<float*>(audio_keep), keep_rows, D, state, h);
+    return hipGetLastError();
+}
+
+// the tick's last kernel: argmax_final_kernel's reduction, then the state block moves on
+__global__ __launch_bounds__(256) void stream_advance_kernel(const float* __restrict__ pv, const int* __restrict__ pi, int n_parts, int* __restrict__ tokens, int* __restrict__ state,
+                                                             int enc_rows, int frames, int cap) {
+    __shared__ float bv[256];
+    __shared__ int bi[256];
+    float v = -INFINITY; int idx = 0x7fffffff;
+    for (int i = threadIdx.x; i < n_parts; i += 256) {
+        const float x = pv[i]; const int ii = pi[i];
+        if (x > v || (x == v && ii < idx)) { v = x; idx = ii; }
+    }
+    bv[threadIdx.x] = v; bi[threadIdx.x] = idx;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) {
+            const float x = bv[threadIdx.x + s]; const int ii = bi[threadIdx.x + s];
+            if (x > bv[threadIdx.x] || (x == bv[threadIdx.x] && ii < bi[threadIdx.x])) { bv[threadIdx.x] = x; bi[threadIdx.x] = ii; }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const int pos = state[STRM_POS];
+        tokens[pos + 1] = bi[0];
+        state[STRM_POS] = pos + 1;
+        if (enc_rows > 0) {
+            const int e = state[STRM_ENC_POS] + enc_rows;
+            state[STRM_ENC_POS] = e; state[STRM_HEAD] = e % cap; state[STRM_FRAME] += frames; state[STRM_TICKS] += 1;
+        }
+    }
+}
+hipError_t launch_stream_advance(const float* part_val, const int* part_idx, int n_parts, int* tokens, int* state, int enc_rows, int frames, int cap, hipStream_t s) {
+    stream_advance_kernel<<<dim3(1), dim3(256), 0, s>>>(part_val, part_idx, n_parts, tokens, state, enc_rows, frames, cap);
+    return hipGetLastError();
+}
+
 }  // namespace vox

@@ -397,6 +397,69 @@ def argmax_rows_dev(ctx, logits_ptr, rows, vocab):
     return ids
 
 
+def stream_schedule(n_samples: int, finished: bool = False):
+    """vox_stream_schedule (host arithmetic): (decoder positions determined, ids due) after `n_samples` pushed, or at the end of an n_samples utterance."""
+    p = C.c_int32(); i = C.c_int32()
+    check(lib().vox_stream_schedule(int(n_samples), 1 if finished else 0, C.byref(p), C.byref(i)))
+    return p.value, i.value
+
+
+class LiveStream:
+    """A live streaming session (vox_stream): push 16 kHz samples in pieces of any size, get token ids back as soon as they are determined; after finish() the
+    concatenation equals transcribe_streaming on the log-mel of pad_audio(gain * samples).  One decoder position = 2560 samples = 160 ms."""
+
+    def __init__(self, model, t_embed, gain=1.0, enc_capacity_rows=0, max_positions=0):
+        self.model = model; self.h = C.c_void_p()
+        check(lib().vox_stream_create(model.h, _ptr(_f32(t_embed).reshape(-1)), float(gain), int(enc_capacity_rows), int(max_positions), C.byref(self.h)))
+        model._caches.add(self)
+
+    def _ids(self, call, n_new, finished):
+        due = stream_schedule(self.info()["samples"] + n_new, finished)[1] - self.info()["ids"]
+        ids = np.zeros(max(due, 1), dtype=np.int32); n = C.c_int32()
+        check(call(_ptr(ids), ids.size, C.byref(n)))
+        return ids[:n.value].copy()
+
+    def push(self, samples=None, device_ptr=None, n_samples=None) -> np.ndarray:
+        """Append samples (a float32 array, or a device pointer + count) -> the ids that became determined (possibly none)."""
+        if device_ptr is None:
+            x = _f32(samples).reshape(-1); n_samples = x.size; ptr = _ptr(x) if x.size else None; kind = 0
+        else:
+            ptr = C.c_void_p(device_ptr); kind = 1
+        return self._ids(lambda o, c, n: lib().vox_stream_push(self.h, ptr, n_samples, kind, o, c, n), n_samples, False)
+
+    def finish(self) -> np.ndarray:
+        """End of the utterance: the right pad is appended, the remaining ids come back."""
+        return self._ids(lambda o, c, n: lib().vox_stream_finish(self.h, o, c, n), 0, True)
+
+    def reset(self):
+        check(lib().vox_stream_reset(self.h))
+
+    def info(self):
+        v = (C.c_int64 * 8)(); check(lib().vox_stream_info(self.h, v))
+        return dict(zip(("samples", "positions", "ids", "encoder_position", "ring_rows", "bytes", "engine_steps", "operator_steps"), (int(x) for x in v)))
+
+    def tap_arm(self, max_rows):
+        check(lib().vox_debug_stream_tap_arm(self.h, int(max_rows))); self._tap_max = int(max_rows)
+
+    def tap_fetch(self):
+        """The f32 logits rows behind the ids handed out since tap_arm: [rows][vocab]."""
+        buf = np.zeros((self._tap_max, self.model.config.vocab), dtype=np.float32); rows = C.c_int32()
+        check(lib().vox_debug_stream_tap_fetch(self.h, _ptr(buf), C.byref(rows)))
+        if rows.value > self._tap_max:
+            raise VoxError(1, f"stream tap: {rows.value} rows for a tap of {self._tap_max}")
+        return buf[:rows.value].copy()
+
+    def close(self):
+        if self.h:
+            lib().vox_stream_free(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Q4VoxtralModel:
     """gguf/model.rs:759-989"""
 
@@ -545,6 +608,11 @@ class Q4VoxtralModel:
         ids = np.zeros(cap, dtype=np.int32); n = C.c_int32()
         check(lib().vox_transcribe_audio(self.h, ptr, n_samples, _ptr(t), _ptr(ids), cap, C.byref(n), kind))
         return ids[:n.value].copy()
+
+    def create_stream(self, t_embed, gain=1.0, enc_capacity_rows=0, max_positions=0) -> LiveStream:
+        """A live session on this model (vox_stream_create): push(x) -> ids, finish(), reset(), info(), close().  gain multiplies every sample (a stream has no
+        file peak: 0.95 / max|x| of a known file reproduces transcribe_audio)."""
+        return LiveStream(self, t_embed, gain, enc_capacity_rows, max_positions)
 
     def transcribe_batch(self, samples_list, t_embed, device_ptrs=None, n_samples=None, norm_group=None, tap_units=None):
         """Batched whole-path transcription of independent utterances (<= 4096; wider than 16: continuous batching over decode slots): list of float32 sample arrays
