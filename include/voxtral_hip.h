@@ -410,6 +410,14 @@ int32_t vox_debug_batch_tap_fetch(vox_model* m, float* out, int32_t* rows_per_un
  * encoder rows, w2 split-K slices, wo split-K slices (0 = unsplit), q|k|v launches that ran RoPE in the GEMM's epilogue.  VOX_ERR_INVALID on bad arguments. */
 int32_t vox_debug_encode_batch(vox_model* m, int32_t n, const float* const* mels, const int32_t* T, int32_t layout, float* out, int64_t cap_rows,
                                int32_t* rows_per_clip, int64_t* report);
+/* The continuous batch driver's planner on its own (tests): host arithmetic only -- no context, no device.  _step_costs: the per-step cost in ms of 1..8 lock-step
+ * groups (index 0 unused, written as 0) the planner prices a call with, from a cost table `base` and the step times `meas` a context has measured (0 = form not seen
+ * yet); calib 0: the table alone; shared != 0: a GPU shared with other sessions (the common measured / table ratio only).  _plan_slots: job i needs steps[i] >= 1 decode
+ * steps; force_G 0 = the cost model picks the group count (<= max_groups, 1..8).  Returns the group count G, for every job its slot (0 .. 16 G - 1) and its position in
+ * that slot's queue, steps_g[k] / run_g[k] = the steps group k's longest slot needs / the steps group k stays active (entries past G - 1: 0), and the plan's cost. */
+int32_t vox_debug_step_costs(const double base[9], const double meas[9], int32_t calib, int32_t shared, double out[9]);
+int32_t vox_debug_plan_slots(const int32_t* steps, int32_t n, int32_t force_G, int32_t max_groups, const double step_ms[9], int32_t* G, int32_t* job_slot,
+                             int32_t* job_qpos, int32_t steps_g[8], int32_t run_g[8], double* cost_ms);
 
 /* ---- live streaming session (no reference counterpart: the reference transcribes finished files, bin/transcribe.rs:112-126) ------------------------------------------
  * A vox_stream is fed 16 kHz samples in pieces of any size and hands back token ids as soon as they are determined.  After vox_stream_finish the concatenation of

@@ -156,6 +156,8 @@ SIGNATURES = {
     "vox_stream_reset": (i32, [vp]),
     "vox_stream_free": (i32, [vp]),
     "vox_stream_info": (i32, [vp, P(i64 * 8)]),
+    "vox_debug_step_costs": (i32, [P(C.c_double), P(C.c_double), i32, i32, P(C.c_double)]),
+    "vox_debug_plan_slots": (i32, [P(i32), i32, i32, i32, P(C.c_double), P(i32), P(i32), P(i32), P(i32), P(i32), P(C.c_double)]),
     "vox_stream_schedule": (i32, [sz, i32, P(i32), P(i32)]),
     "vox_debug_stream_tap_arm": (i32, [vp, i32]),
     "vox_debug_stream_tap_fetch": (i32, [vp, vp, P(i32)]),

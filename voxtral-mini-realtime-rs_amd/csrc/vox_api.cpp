@@ -2331,6 +2331,8 @@ extern "C" int32_t vox_transcribe_audio(vox_model* m, const float* samples, size
 // advances all sequences (rows of one skinny MFMA GEMM per linear, so the Q4 weights are streamed once per step for the
 // whole batch), per-sequence positions / KV-cache slices / audio rows live on the device, the step is hipGraph-replayed.
 static const int32_t VOX_RETRY_ON_LAUNCHES = -1000;      // internal: a batched engine timed out; the driver's caller serves the call again on the launch-based step
+// run(allow_engine): one driver call; a call whose engine timed out is served again on the launch-based step
+template <class Run> static int32_t retry_on_launches(Run run) { int32_t r = run(true); if (r == VOX_RETRY_ON_LAUNCHES) r = run(false); return r; }
 // Both batched drivers run every chain of a decode step back to back on the session stream, eager or captured (until the corpus crash fix they forked the chains onto
 // side streams: hipGraphLaunch of a graph with parallel branches reads past the end of its stream list when one shares the launch stream's hardware queue, a host crash).
 // declared after a driver's pooled buffers: on every exit path the streams that may still use them are drained before the buffers go back to the pool
@@ -2339,7 +2341,7 @@ struct BatchDrain { vox_ctx* c; ~BatchDrain() { (void)hipStreamSynchronize(c->st
 // positions to decode up to (0: shorter than the prefix, emits nothing, model.rs:887-889; S == 38 still writes tokens[38], model.rs:922-926); checks the caller's capacities
 static int32_t batch_lengths(const vox_model* m, int n, const float* const* samples, const size_t* n_samples, const int32_t* caps, const int* slot_of,
                              std::vector<int>& T, std::vector<int>& S, std::vector<int>& len, int* Smax) {
-    const int PREFIX_LEN = 38;
+    const int PREFIX_LEN = VOX_PREFIX_TOKENS;
     vox_pad_cfg pc; vox_pad_cfg_voxtral(&pc);
     T.assign(n, 0); S.assign(n, 0); len.assign(n, 0); *Smax = 0;
     for (int i = 0; i < n; i++) {
@@ -2371,16 +2373,16 @@ static int32_t front_end_units(const MelTables& mt, int i0, int nu, const float*
 }
 // prefix tokens (BOS + STREAMING_PAD), first positions (the prefix's last row) and sequence lengths of n utterances up to the device (gguf/model.rs:887-902)
 static int32_t upload_prefix(int n, int tstride, const std::vector<int>& len, int* d_tok, int* d_pos, int* d_len, hipStream_t s) {
-    const int PREFIX_LEN = 38, BOS = 1, STREAMING_PAD = 32;
-    std::vector<int32_t> prefix((size_t)n * tstride, 0); std::vector<int> pos0(n, PREFIX_LEN - 1);
-    for (int i = 0; i < n; i++) { prefix[(size_t)i * tstride] = BOS; for (int r = 1; r < PREFIX_LEN; r++) prefix[(size_t)i * tstride + r] = STREAMING_PAD; }
-    HIPCHK(hipMemcpyAsync(d_tok, prefix.data(), prefix.size() * 4, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(d_pos, pos0.data(), (size_t)n * 4, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(d_len, len.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+    std::vector<int32_t> prefix((size_t)n * tstride, 0); std::vector<int> pos0(n, VOX_PREFIX_TOKENS - 1);
+    for (int i = 0; i < n; i++) { prefix[(size_t)i * tstride] = VOX_TOK_BOS; for (int r = 1; r < VOX_PREFIX_TOKENS; r++) prefix[(size_t)i * tstride + r] = VOX_TOK_STREAMING_PAD; }
+    HIPCHK(hipMemcpyAsync(d_tok, prefix.data(), prefix.size() * 4, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(d_pos, pos0.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_len, len.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipStreamSynchronize(s));      // the host vectors go out of scope
     return VOX_OK;
 }
 // every utterance's generated ids (tokens[38 ..]; S == 38 still emits its first token, model.rs:922-926) into the caller's arrays; *total = their number
 static int32_t copy_out_ids(int n, const std::vector<int>& S, int tstride, const int* d_tok, int32_t* const* out_ids, int32_t* n_ids, int* total, hipStream_t s) {
-    const int PREFIX_LEN = 38;
+    const int PREFIX_LEN = VOX_PREFIX_TOKENS;
     std::vector<int32_t> host_tok((size_t)n * tstride);
     HIPCHK(hipMemcpyAsync(host_tok.data(), d_tok, host_tok.size() * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s)); *total = 0;
@@ -2430,43 +2432,85 @@ struct StepGraphs {
 };
 // XF planes of one 16-row group over K columns: bf16 hi + lo in MFMA A-operand order
 static size_t xf_bytes(int K) { return (size_t)2 * (K / 128) * 256 * 16; }
-// the buffers of a batched XF decode step: f32 rows (h, qkv, logits; att unread), XF planes and partial sums of squares one block per 16-row group, `*_gs` elements apart
-struct XfBufs { float *h, *qkv, *att, *logits, *ssq; uint16_t *xf1, *xf2, *xf3; long xf1_gs, xf2_gs, xf3_gs, ssq_gs; };
-// One 16-row group's XF decode step on stream sg: 4 launches per layer and the lm_head (RMSNorm folded into producers and consumers, RoPE + KV-cache write in the q|k|v
-// GEMM's epilogue).  Group gi is rows 16 gi .. 16 gi + ng - 1 of pos and of the buffers; k / v: layer 0's cache slab (layer l at + l layer_stride), row r's slice at
-// + r seq_stride, or, with kv_row, the slice kv_row[r] names.
-static int32_t xf_group_chain(const vox_model* m, const XfBufs& b, int gi, int ng, const int* pos, const int* kv_row, bool prefer_gqa, int spec_rows,
-                              float* k, float* v, size_t layer_stride, size_t seq_stride, int max_seq, hipStream_t sg) {
+// What a batched XF decode step works on.  f32 rows (h, qkv, logits; att unread), XF planes and partial sums of squares one block per 16-row group, `*_gs` elements apart.
+// k / v: layer 0's cache slab (layer l at + l layer_stride), row r's slice at + r seq_stride, or, with kv_row, the slice kv_row[r] names; pos: the rows' positions.
+// ssq_e: the batched engine's sums of squares (one block of 256 + 16 rows per group); planes: the wide step's K-split scratch, planes_bytes per chain.
+struct XfBufs {
+    float *h, *qkv, *att, *logits, *ssq; uint16_t *xf1, *xf2, *xf3; long xf1_gs, xf2_gs, xf3_gs, ssq_gs;
+    float *k, *v; size_t layer_stride, seq_stride; int max_seq; const int *pos, *kv_row; bool no_xcd_remap;
+    float* ssq_e; void* planes; size_t planes_bytes;
+};
+// the XF planes and ssq blocks of a step over n_grp groups (0: none, the group strides alone): from the pool, zeroed on s, bound to b
+struct XfPlanes {
+    DevBuf xf1, xf2, xf3, ssq;
+    int32_t alloc(const vox_model* m, int n_grp, hipStream_t s, XfBufs* b) {
+        const vox_model_cfg& c = m->cfg; vox_ctx* cx = m->ctx;
+        const size_t b1 = xf_bytes(c.dec_dim), b2 = xf_bytes(c.dec_heads * c.dec_head_dim), b3 = xf_bytes(c.dec_ffn), bs = (size_t)q4_skinny_resid_xf_parts(c.dec_dim) * 16 * 4;
+        b->xf1_gs = (long)(b1 / 2); b->xf2_gs = (long)(b2 / 2); b->xf3_gs = (long)(b3 / 2); b->ssq_gs = (long)(bs / 4);
+        if (!n_grp) return VOX_OK;
+        HIPCHK(xf1.alloc_pooled(cx, b1 * n_grp)); HIPCHK(xf2.alloc_pooled(cx, b2 * n_grp)); HIPCHK(xf3.alloc_pooled(cx, b3 * n_grp)); HIPCHK(ssq.alloc_pooled(cx, bs * n_grp));
+        HIPCHK(hipMemsetAsync(xf1.p, 0, b1 * n_grp, s)); HIPCHK(hipMemsetAsync(xf2.p, 0, b2 * n_grp, s)); HIPCHK(hipMemsetAsync(xf3.p, 0, b3 * n_grp, s));
+        HIPCHK(hipMemsetAsync(ssq.p, 0, bs * n_grp, s));
+        b->xf1 = xf1.as<uint16_t>(); b->xf2 = xf2.as<uint16_t>(); b->xf3 = xf3.as<uint16_t>(); b->ssq = ssq.as<float>();
+        return VOX_OK;
+    }
+};
+// One chain of an XF decode step on stream sg: 4 launches per layer and the lm_head (RMSNorm folded into producers and consumers, RoPE + KV-cache write in the q|k|v
+// GEMM's epilogue).  mtw == 0: ONE 16-row group, rows 16 g0i .. 16 g0i + ng - 1 of the buffers, through launch_q4_gemm.  mtw = 2..4 (the WIDE chain, round 6): the slot
+// groups g0i .. g0i + mtw - 1 as ONE GEMM per operator (launch_q4_wide: one weight fetch and one nibble -> bf16 conversion per K step for all groups, the groups' XF
+// planes staged through LDS once per workgroup, K split over workgroups + a finishing launch with the step's epilogue), their attention in one launch, the lm_head as one
+// GEMM; `chain`: which slice of the planes scratch.  The fields only launch_q4_wide reads are set on that path alone.
+static int32_t xf_chain(const vox_model* m, const XfBufs& b, int g0i, int ng, int mtw, int chain, bool prefer_gqa, int spec_rows, hipStream_t sg) {
     const vox_model_cfg& c = m->cfg;
     const int D = c.dec_dim, H = c.dec_heads, KV = c.dec_kv_heads, hd = c.dec_head_dim, QD = H * hd, W = QD + 2 * KV * hd, F = c.dec_ffn, V = c.vocab;
-    const int parts_D = q4_skinny_resid_xf_parts(D), r0 = gi * 16;
-    uint16_t* xf1 = b.xf1 + (size_t)gi * b.xf1_gs; uint16_t* xf2 = b.xf2 + (size_t)gi * b.xf2_gs; uint16_t* xf3 = b.xf3 + (size_t)gi * b.xf3_gs; float* ssq = b.ssq + (size_t)gi * b.ssq_gs;
-    float* hg = b.h + (size_t)r0 * D; float* qg = b.qkv + (size_t)r0 * W; const int* pg = pos + r0; const int* rg = kv_row ? kv_row + r0 : nullptr; const size_t row0 = kv_row ? 0 : (size_t)r0 * seq_stride;
+    const int parts_D = q4_skinny_resid_xf_parts(D), max_seq = b.max_seq, M = mtw ? 16 * mtw : ng;
+    const int r0 = g0i * 16;      // the chain's first group: its planes, sums, rows, positions and cache slices (a wide chain's further groups follow at the group strides)
+    uint16_t* xf1 = b.xf1 + (size_t)g0i * b.xf1_gs; uint16_t* xf2 = b.xf2 + (size_t)g0i * b.xf2_gs; uint16_t* xf3 = b.xf3 + (size_t)g0i * b.xf3_gs; float* ssq = b.ssq + (size_t)g0i * b.ssq_gs;
+    float* hg = b.h + (size_t)r0 * D; float* qg = b.qkv + (size_t)r0 * W; const int* pg = b.pos + r0; const int* rg = b.kv_row ? b.kv_row + r0 : nullptr;
+    const size_t row0 = b.kv_row ? 0 : (size_t)r0 * b.seq_stride;
+    auto gemm = [&](GemmParams g, const Q4W& w, const uint16_t* xin, int K, int epi) -> hipError_t {      // g: the operator's epilogue fields
+        g.w = w; g.xf = (const uint4*)xin; g.M = M; if (mtw || epi != EPI_RESID_XF) g.norm_eps = c.norm_eps;
+        if (!mtw) return launch_q4_gemm(g, epi, sg);
+        g.wide_mt = mtw; g.xf_gstride = (long)(xf_bytes(K) / 16); g.kz_scratch_bytes = b.planes_bytes;
+        g.kz_scratch = reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(b.planes) + (size_t)chain * b.planes_bytes);
+        if (g.ssq_part) g.ssq_part_gstride = b.ssq_gs;
+        if (epi == EPI_RESID_XF) { g.xf_out_gstride = b.xf1_gs; g.ssq_out_gstride = b.ssq_gs; } else if (epi == EPI_SWIGLU_XF) g.xf_out_gstride = b.xf3_gs;
+        return launch_q4_wide(g, epi, sg);
+    };
     for (int l = 0; l < c.dec_layers; l++) {
         const DecLayer& L = m->dec[l];
-        float* kl = k + (size_t)l * layer_stride + row0; float* vl = v + (size_t)l * layer_stride + row0;
-        { GemmParams g{}; g.w = L.wqkv.w; g.xf = (const uint4*)xf1; g.M = ng; g.out = qg; g.out_stride = W;
-          g.ssq_part = ssq; g.n_part = l == 0 ? 1 : parts_D; g.norm_eps = c.norm_eps;
-          g.pos = pg; g.rope_cos = m->dec_cos; g.rope_sin = m->dec_sin; g.hd = hd; g.n_q = QD; g.n_kv = KV; g.kc = kl; g.vc = vl; g.kv_seq_stride = (long)seq_stride; g.kv_head_stride = max_seq * hd; g.kv_row = rg;
-          HIPCHK(launch_q4_gemm(g, EPI_ROPE_KV, sg)); }
-        AttnParams ap{}; ap.q = qg; ap.k = kl; ap.v = vl; ap.kv_row_stride = hd; ap.kv_head_stride = max_seq * hd; ap.out = b.att; ap.n_heads = H; ap.n_kv_heads = KV;
-        ap.offset = 0; ap.window = c.dec_window; ap.pos_ptr = pg; ap.M = 1; ap.pos_per_seq = 1; ap.q_seq_stride = W; ap.out_seq_stride = QD; ap.kv_seq_stride = (long)seq_stride; ap.kv_row = rg;
-        ap.out_xf = xf2; ap.prefer_gqa = prefer_gqa; ap.no_xcd_remap = knob_str("VOX_ATTN_NO_XCD") != nullptr; ap.spec_rows = spec_rows;
-        HIPCHK(launch_attn_decode(ap, hd, max_seq, sg, ng));
-        { GemmParams g{}; g.w = L.wo.w; g.xf = (const uint4*)xf2; g.M = ng; g.out = hg; g.out_stride = D; g.resid = hg; g.resid_stride = D;
-          g.xf_out = xf1; g.xf_w = L.ffn_norm; g.xf_w2 = L.ada_mul; g.ssq_out = ssq; HIPCHK(launch_q4_gemm(g, EPI_RESID_XF, sg)); }
-        { GemmParams g{}; g.w = L.w13.w; g.xf = (const uint4*)xf1; g.M = ng; g.out = (float*)xf3; g.out_stride = F;
-          g.ssq_part = ssq; g.n_part = parts_D; g.norm_eps = c.norm_eps; HIPCHK(launch_q4_gemm(g, EPI_SWIGLU_XF, sg)); }
-        { GemmParams g{}; g.w = L.w2.w; g.xf = (const uint4*)xf3; g.M = ng; g.out = hg; g.out_stride = D; g.resid = hg; g.resid_stride = D;
-          g.xf_out = xf1; g.xf_w = l + 1 < c.dec_layers ? m->dec[l + 1].attn_norm : m->dec_norm; g.xf_w2 = nullptr; g.ssq_out = ssq; HIPCHK(launch_q4_gemm(g, EPI_RESID_XF, sg)); }
+        float* kl = b.k + (size_t)l * b.layer_stride + row0; float* vl = b.v + (size_t)l * b.layer_stride + row0;
+        { GemmParams g{}; g.out = qg; g.out_stride = W; g.ssq_part = ssq; g.n_part = l == 0 ? 1 : parts_D; g.pos = pg; g.rope_cos = m->dec_cos; g.rope_sin = m->dec_sin;
+          g.hd = hd; g.n_q = QD; g.n_kv = KV; g.kc = kl; g.vc = vl; g.kv_seq_stride = (long)b.seq_stride; g.kv_head_stride = max_seq * hd; g.kv_row = rg;
+          HIPCHK(gemm(g, L.wqkv.w, xf1, D, EPI_ROPE_KV)); }
+        AttnParams ap{}; ap.q = qg; ap.k = kl; ap.v = vl; ap.kv_row_stride = hd; ap.kv_head_stride = max_seq * hd; ap.n_heads = H; ap.n_kv_heads = KV;
+        ap.offset = 0; ap.window = c.dec_window; ap.pos_ptr = pg; ap.M = 1; ap.pos_per_seq = 1; ap.q_seq_stride = W; ap.out_seq_stride = QD; ap.kv_seq_stride = (long)b.seq_stride;
+        ap.kv_row = rg; ap.out_xf = xf2; ap.prefer_gqa = prefer_gqa; ap.no_xcd_remap = b.no_xcd_remap; ap.spec_rows = spec_rows;
+        ap.out = b.att; if (mtw) { ap.out = b.att + (size_t)g0i * 16 * QD; ap.out_xf_gstride = b.xf2_gs; }
+        HIPCHK(launch_attn_decode(ap, hd, max_seq, sg, M));
+        { GemmParams g{}; g.out = hg; g.out_stride = D; g.resid = hg; g.resid_stride = D; g.xf_out = xf1; g.xf_w = L.ffn_norm; g.xf_w2 = L.ada_mul; g.ssq_out = ssq;
+          HIPCHK(gemm(g, L.wo.w, xf2, QD, EPI_RESID_XF)); }
+        { GemmParams g{}; g.out = (float*)xf3; g.out_stride = F; g.ssq_part = ssq; g.n_part = parts_D; HIPCHK(gemm(g, L.w13.w, xf1, D, EPI_SWIGLU_XF)); }
+        { GemmParams g{}; g.out = hg; g.out_stride = D; g.resid = hg; g.resid_stride = D; g.xf_out = xf1; g.ssq_out = ssq;
+          g.xf_w = l + 1 < c.dec_layers ? m->dec[l + 1].attn_norm : m->dec_norm; g.xf_w2 = nullptr; HIPCHK(gemm(g, L.w2.w, xf3, F, EPI_RESID_XF)); }
     }
-    { GemmParams g{}; g.w = m->tok.w; g.xf = (const uint4*)xf1; g.M = ng; g.out = b.logits + (size_t)r0 * V; g.out_stride = V;
-      g.ssq_part = ssq; g.n_part = parts_D; g.norm_eps = c.norm_eps; HIPCHK(launch_q4_gemm(g, EPI_STORE, sg)); }
+    { GemmParams g{}; g.out = b.logits + (size_t)g0i * 16 * V; g.out_stride = V; g.ssq_part = ssq; g.n_part = parts_D; HIPCHK(gemm(g, m->tok.w, xf1, D, EPI_STORE)); }
     return VOX_OK;
 }
-// after a batched engine launch: group gi's 256 partial sums of squares (ssq_e, one block of 256 + 16 rows per group) -> 16, then its lm_head over ng rows
-static int32_t engb_group_tail(const vox_model* m, const XfBufs& b, float* ssq_e, int gi, int ng, hipStream_t s) {
-    float* ssq_p = ssq_e + (size_t)gi * (256 + 16) * 16; float* ssq_f = ssq_p + 256 * 16;
+// The batched decode-layer engine's parameters for group gi (n_rows of its 16): layer table `tab`, edge-buffer block `blk` (a block belongs to a launch, not to a
+// group: tags carry the block's launch serial), `two`: one half of a two-group launch.  Cache slices per slot when b.kv_row is set.
+static EngBParams engb_params(const vox_model* m, const XfBufs& b, int gi, int n_rows, int tab, int blk, bool two) {
+    const vox_model_cfg& c = m->cfg; const int r0 = gi * 16;
+    EngBParams ep{}; ep.stream = m->eng_stream; ep.stream_wo = m->eng_wob; ep.layers = m->engb_tab[tab]; ep.n_layers = c.dec_layers; ep.kv_seq_stride = (long)b.seq_stride;
+    ep.h_in = b.h + (size_t)r0 * c.dec_dim; ep.h_stride = c.dec_dim; ep.n_rows = n_rows; ep.final_norm = m->dec_norm; ep.pos = b.pos + r0; ep.kv_row = b.kv_row ? b.kv_row + r0 : nullptr;
+    ep.rope_cos = m->dec_cos; ep.rope_sin = m->dec_sin; ep.max_seq = b.max_seq; ep.window = c.dec_window; ep.eps = c.norm_eps;
+    engb_state_carve(m->engb_state[blk], &ep);
+    ep.xf_out = b.xf1 + (size_t)gi * b.xf1_gs; ep.ssq_out = b.ssq_e + (size_t)gi * (256 + 16) * 16; ep.tl = nullptr; ep.tl_layer = -1; ep.flags = two ? m->engb_flags2 : m->engb_flags;
+    return ep;
+}
+// after a batched engine launch: group gi's 256 partial sums of squares (b.ssq_e) -> 16, then its lm_head over ng rows
+static int32_t engb_group_tail(const vox_model* m, const XfBufs& b, int gi, int ng, hipStream_t s) {
+    float* ssq_p = b.ssq_e + (size_t)gi * (256 + 16) * 16; float* ssq_f = ssq_p + 256 * 16;
     HIPCHK(launch_engb_ssq_fold(ssq_p, ssq_f, s));
     GemmParams g{}; g.w = m->tok.w; g.xf = (const uint4*)(b.xf1 + (size_t)gi * b.xf1_gs); g.M = ng; g.out = b.logits + (size_t)gi * 16 * m->cfg.vocab; g.out_stride = m->cfg.vocab;
     g.ssq_part = ssq_f; g.n_part = 16; g.norm_eps = m->cfg.norm_eps; HIPCHK(launch_q4_gemm(g, EPI_STORE, s));
@@ -2494,18 +2538,58 @@ struct BatchTapCall {
     int32_t rows(const float* logits, int n_rows, const int* slot_clip, int clip0, const int* pos, const int* seq_len, hipStream_t s) const {
         if (!on()) return VOX_OK;
         BatchTapParams p{}; p.logits = logits; p.vocab = m->cfg.vocab; p.slot_clip = slot_clip; p.clip0 = clip0; p.pos = pos; p.seq_len = seq_len;
-        p.clip_unit = (const int*)clip_unit.p; p.n_clips = n; p.out = m->tap.out; p.rows = m->tap.rows; p.n_units = (int)m->tap.units.size(); p.max_rows = m->tap.max_rows; p.first_pos = 38;
+        p.clip_unit = (const int*)clip_unit.p; p.n_clips = n; p.out = m->tap.out; p.rows = m->tap.rows; p.n_units = (int)m->tap.units.size(); p.max_rows = m->tap.max_rows;
+        p.first_pos = VOX_PREFIX_TOKENS;
         HIPCHK(launch_batch_tap(p, n_rows, s));
         return VOX_OK;
     }
 };
+// Stacked 38-token prefill of nc utterances (gguf/model.rs:887-919) on s: x0[i][r] = audio[aoff[i]][r] + embed(tok[i][r]) into px, the decoder over all nc x 38 rows
+// against the cache slices k / v (utterance i's at + i seq_stride), then the logits of every utterance's last prefix row (RMSNorm -> xn, lm_head -> logits): what its
+// first generated token is taken from.  Utterances shorter than the prefix emit nothing (model.rs:887-889) -- they ride along as idle rows.
+static int32_t prefill_first_logits(vox_model* m, int nc, const int* tok, int tstride, const float* audio, const long* aoff, float* px, float* k, float* v, int max_seq,
+                                    size_t layer_stride, size_t seq_stride, float* xn, float* logits, hipStream_t s) {
+    const vox_model_cfg& c = m->cfg; const int D = c.dec_dim, PREFIX_LEN = VOX_PREFIX_TOKENS;
+    for (int i = 0; i < nc; i++)
+        HIPCHK(launch_embed(m->tok.w, tok + (size_t)i * tstride, PREFIX_LEN, audio + aoff[i], D, nullptr, 0, 0, px + (size_t)i * PREFIX_LEN * D, s));
+    vox_cache view; view.m = m; view.ctx = m->ctx; view.k = k; view.v = v; view.max_seq = max_seq; view.len = 0; view.layer_stride = layer_stride;
+    VOXCHK(decoder_prefill_dev(m, px, nc * PREFIX_LEN, &view, 0, nc, (long)seq_stride));
+    HIPCHK(launch_rms_norm(px + (size_t)(PREFIX_LEN - 1) * D, PREFIX_LEN * D, nc, D, m->dec_norm, nullptr, c.norm_eps, xn, D, s));
+    { GemmParams g{}; g.w = m->tok.w; g.x = xn; g.x_stride = D; g.M = nc; g.out = logits; g.out_stride = c.vocab; HIPCHK(launch_q4_gemm(g, EPI_STORE, s)); }
+    return VOX_OK;
+}
+// the lock-step step of a model the XF step does not cover: n f32 rows through every layer and the lm_head (xn, act: normalised rows, FFN rows)
+static int32_t f32_batch_layers(const vox_model* m, const XfBufs& b, int n, float* xn, float* act, hipStream_t s) {
+    const vox_model_cfg& c = m->cfg;
+    const int D = c.dec_dim, H = c.dec_heads, KV = c.dec_kv_heads, hd = c.dec_head_dim, QD = H * hd, W = QD + 2 * KV * hd, F = c.dec_ffn, max_seq = b.max_seq;
+    float* h = b.h;
+    for (int l = 0; l < c.dec_layers; l++) {
+        const DecLayer& L = m->dec[l]; float* kl = b.k + (size_t)l * b.layer_stride; float* vl = b.v + (size_t)l * b.layer_stride;
+        HIPCHK(launch_rms_norm(h, D, n, D, L.attn_norm, nullptr, c.norm_eps, xn, D, s));
+        { GemmParams g{}; g.w = L.wqkv.w; g.x = xn; g.x_stride = D; g.M = n; g.out = b.qkv; g.out_stride = W; HIPCHK(launch_q4_gemm(g, EPI_STORE, s)); }
+        HIPCHK(launch_rope_kv_batch(b.qkv, n, W, QD, KV, hd, b.pos, m->dec_cos, m->dec_sin, kl, vl, (long)b.seq_stride, max_seq * hd, s));
+        AttnParams ap{}; ap.q = b.qkv; ap.k = kl; ap.v = vl; ap.kv_row_stride = hd; ap.kv_head_stride = max_seq * hd; ap.out = b.att; ap.n_heads = H; ap.n_kv_heads = KV;
+        ap.offset = 0; ap.window = c.dec_window; ap.pos_ptr = b.pos; ap.M = 1; ap.pos_per_seq = 1; ap.q_seq_stride = W; ap.out_seq_stride = QD;
+        ap.kv_seq_stride = (long)b.seq_stride; ap.spec_rows = max_seq;
+        HIPCHK(launch_attn_decode(ap, hd, max_seq, s, n));
+        { GemmParams g{}; g.w = L.wo.w; g.x = b.att; g.x_stride = QD; g.M = n; g.out = h; g.out_stride = D; g.resid = h; g.resid_stride = D; HIPCHK(launch_q4_gemm(g, EPI_RESID, s)); }
+        HIPCHK(launch_rms_norm(h, D, n, D, L.ffn_norm, L.ada_mul, c.norm_eps, xn, D, s));
+        { GemmParams g{}; g.w = L.w13.w; g.x = xn; g.x_stride = D; g.M = n; g.out = act; g.out_stride = F; HIPCHK(launch_q4_gemm(g, EPI_SWIGLU, s)); }
+        { GemmParams g{}; g.w = L.w2.w; g.x = act; g.x_stride = F; g.M = n; g.out = h; g.out_stride = D; g.resid = h; g.resid_stride = D; HIPCHK(launch_q4_gemm(g, EPI_RESID, s)); }
+    }
+    HIPCHK(launch_rms_norm(h, D, n, D, m->dec_norm, nullptr, c.norm_eps, xn, D, s));
+    { GemmParams g{}; g.w = m->tok.w; g.x = xn; g.x_stride = D; g.M = n; g.out = b.logits; g.out_stride = c.vocab; HIPCHK(launch_q4_gemm(g, EPI_STORE, s)); }
+    return VOX_OK;
+}
 static int32_t transcribe_batch_impl(vox_model* m, int32_t n, const float* const* samples, const size_t* n_samples, const float* t_embed,
                                      int32_t* const* out_ids, const int32_t* caps, int32_t* n_ids, int32_t mem_kind, const int* slot_of, bool allow_engine = true,
-                                     const float* const* unit_scale = nullptr) {      // unit_scale[i]: device float the front-end multiplies unit i by (vox_transcribe_batch_ex: the peak scale of the unit's FILE); null = every unit normalises itself      // slot_of[i]: the caller's slot of row i (error messages)
+                                     const float* const* unit_scale = nullptr) {
+    // unit_scale[i]: device float the front-end multiplies unit i by (vox_transcribe_batch_ex: the peak scale of the unit's FILE); null = every unit normalises itself
+    // slot_of[i]: the caller's slot of row i (error messages)
     VOXCHK(ctx_bind(m->ctx));
     const vox_model_cfg& c = m->cfg; vox_ctx* cx = m->ctx; hipStream_t s = cx->stream;
     ARGCHK(c.n_mels == 128, "the log-mel front-end produces 128 bins; model expects %d", c.n_mels);
-    const int PREFIX_LEN = 38;
+    const int PREFIX_LEN = VOX_PREFIX_TOKENS;
     const int D = c.dec_dim, H = c.dec_heads, KV = c.dec_kv_heads, hd = c.dec_head_dim, QD = H * hd, KD = KV * hd, W = QD + 2 * KD, F = c.dec_ffn, V = c.vocab;
     VOXCHK(vox_model_set_t_embed(m, t_embed));
     m->timings = vox_timings{};
@@ -2516,7 +2600,7 @@ static int32_t transcribe_batch_impl(vox_model* m, int32_t n, const float* const
     const int audio_rows = std::max(enc_row_budget(m, T.data(), n) / c.reshape_factor, PREFIX_LEN + 1);   // per-utterance row budget of the stacked audio embeddings
     const size_t seq_stride = (size_t)KV * max_seq * hd, layer_stride = (size_t)n * seq_stride;
     size_t mel_floats = 0; for (int i = 0; i < n; i++) mel_floats += (size_t)128 * T[i];
-    DevBuf b_audio, b_k, b_v, b_tok, b_pos, b_len, b_h, b_xn, b_qkv, b_att, b_act, b_logits, b_px, b_mel, b_scale, b_smp, b_xf1, b_xf2, b_xf3, b_ssq;
+    DevBuf b_audio, b_k, b_v, b_tok, b_pos, b_len, b_h, b_xn, b_qkv, b_att, b_act, b_logits, b_px, b_mel, b_scale, b_smp; XfPlanes xfp;
     BatchTapCall tap; VOXCHK(tap.init(m, n, slot_of, s));
     BatchDrain drain{cx};
     HIPCHK(b_audio.alloc_pooled(cx, (size_t)n * audio_rows * D * 4)); HIPCHK(b_k.alloc_pooled(cx, layer_stride * c.dec_layers * 4)); HIPCHK(b_v.alloc_pooled(cx, layer_stride * c.dec_layers * 4));
@@ -2526,7 +2610,7 @@ static int32_t transcribe_batch_impl(vox_model* m, int32_t n, const float* const
     HIPCHK(b_mel.alloc_pooled(cx, std::max<size_t>(mel_floats, 1) * 4)); HIPCHK(b_scale.alloc_pooled(cx, (size_t)n * 4));
     HIPCHK(hipMemsetAsync(b_tok.p, 0, (size_t)n * tstride * 4, s)); HIPCHK(hipMemsetAsync(b_h.p, 0, (size_t)n * D * 4, s));
     HIPCHK(hipMemsetAsync(b_audio.p, 0, (size_t)n * audio_rows * D * 4, s));
-    float* d_audio = b_audio.as<float>(); int* d_tok = b_tok.as<int>(); int* d_pos = b_pos.as<int>();
+    float* d_audio = b_audio.as<float>(); int* d_tok = b_tok.as<int>(); int* d_pos = b_pos.as<int>(); int* d_len = b_len.as<int>(); float* logits = b_logits.as<float>();
     const double t0 = now_ms();
     // (1) front-end per utterance, no host synchronisation in between: peak-normalise -> (virtual) pad -> log-mel
     std::vector<const float*> d_mels(n);
@@ -2539,17 +2623,10 @@ static int32_t transcribe_batch_impl(vox_model* m, int32_t n, const float* const
     for (int i = 0; i < n; i++) ARGCHK(S4[i] == S[i], "internal: sequence length mismatch (%d vs %d)", S4[i], S[i]);
     HIPCHK(hipStreamSynchronize(s)); const double t1 = now_ms();
     const double pre_ms = t_pre - t0, enc_ms = t1 - t_pre;
-    // (3) stacked 38-token prefill (gguf/model.rs:887-919): x0[i][r] = audio[i][r] + embed(prefix[r]); utterances shorter than the
-    // prefix emit nothing (model.rs:887-889) -- they ride along as idle rows
-    VOXCHK(upload_prefix(n, tstride, len, d_tok, d_pos, b_len.as<int>(), s));
-    float* px = b_px.as<float>();
-    for (int i = 0; i < n; i++)
-        HIPCHK(launch_embed(m->tok.w, d_tok + (size_t)i * tstride, PREFIX_LEN, d_audio + (size_t)i * audio_rows * D, D, nullptr, 0, 0, px + (size_t)i * PREFIX_LEN * D, s));
-    vox_cache view; view.m = m; view.ctx = cx; view.k = b_k.as<float>(); view.v = b_v.as<float>(); view.max_seq = max_seq; view.len = 0; view.layer_stride = layer_stride;
-    VOXCHK(decoder_prefill_dev(m, px, n * PREFIX_LEN, &view, 0, n, (long)seq_stride));
-    // logits of every utterance's last prefix row -> first generated token + first step input (same tail as a decode step)
-    HIPCHK(launch_rms_norm(px + (size_t)(PREFIX_LEN - 1) * D, PREFIX_LEN * D, n, D, m->dec_norm, nullptr, c.norm_eps, b_xn.as<float>(), D, s));
-    { GemmParams g{}; g.w = m->tok.w; g.x = b_xn.as<float>(); g.x_stride = D; g.M = n; g.out = b_logits.as<float>(); g.out_stride = V; HIPCHK(launch_q4_gemm(g, EPI_STORE, s)); }
+    // (3) stacked 38-token prefill; its lm_head rows -> first generated token + first step input (same tail as a decode step)
+    VOXCHK(upload_prefix(n, tstride, len, d_tok, d_pos, d_len, s));
+    std::vector<long> aoff(n); for (int i = 0; i < n; i++) aoff[i] = (long)i * audio_rows * D;
+    VOXCHK(prefill_first_logits(m, n, d_tok, tstride, d_audio, aoff.data(), b_px.as<float>(), b_k.as<float>(), b_v.as<float>(), max_seq, layer_stride, seq_stride, b_xn.as<float>(), logits, s));
     // (4) batched decode steps
     int steps = 0; for (int i = 0; i < n; i++) steps = std::max(steps, S[i] - PREFIX_LEN - 1);
     // The step's GEMM inputs live as XF fragment planes (bf16 hi+lo in MFMA A-operand order, written once by the producing kernel), so
@@ -2557,36 +2634,36 @@ static int32_t transcribe_batch_impl(vox_model* m, int32_t n, const float* const
     // 16 rows (one MFMA m-tile); the groups of a layer run back to back so the second group finds the layer's weights in L2 / MALL.
     const bool use_xf = batch_xf_ok(m);
     const int n_grp = (n + 15) / 16;
-    const int parts_D = q4_skinny_resid_xf_parts(D);
-    if (use_xf) {
-        HIPCHK(b_xf1.alloc_pooled(cx, xf_bytes(D) * n_grp)); HIPCHK(b_xf2.alloc_pooled(cx, xf_bytes(QD) * n_grp)); HIPCHK(b_xf3.alloc_pooled(cx, xf_bytes(F) * n_grp));
-        HIPCHK(hipMemsetAsync(b_xf1.p, 0, xf_bytes(D) * n_grp, s)); HIPCHK(hipMemsetAsync(b_xf2.p, 0, xf_bytes(QD) * n_grp, s)); HIPCHK(hipMemsetAsync(b_xf3.p, 0, xf_bytes(F) * n_grp, s));
-        HIPCHK(b_ssq.alloc_pooled(cx, (size_t)parts_D * 16 * 4 * n_grp)); HIPCHK(hipMemsetAsync(b_ssq.p, 0, (size_t)parts_D * 16 * 4 * n_grp, s));
-    }
-    const XfBufs xb{b_h.as<float>(), b_qkv.as<float>(), b_att.as<float>(), b_logits.as<float>(), b_ssq.as<float>(), b_xf1.as<uint16_t>(), b_xf2.as<uint16_t>(), b_xf3.as<uint16_t>(),
-                    (long)(xf_bytes(D) / 2), (long)(xf_bytes(QD) / 2), (long)(xf_bytes(F) / 2), (long)parts_D * 16};
+    XfBufs xb{}; xb.h = b_h.as<float>(); xb.qkv = b_qkv.as<float>(); xb.att = b_att.as<float>(); xb.logits = logits;
+    VOXCHK(xfp.alloc(m, use_xf ? n_grp : 0, s, &xb));
+    xb.k = b_k.as<float>(); xb.v = b_v.as<float>(); xb.layer_stride = layer_stride; xb.seq_stride = seq_stride; xb.max_seq = max_seq; xb.pos = d_pos; xb.kv_row = nullptr;
+    xb.no_xcd_remap = knob_str("VOX_ATTN_NO_XCD") != nullptr;
     // Batched decode-layer ENGINE (vox_engine_b16.hip): the 26 layers of a 16-row group as ONE persistent launch on the single-stream engine's packet stream; the group's
     // 5 x 26 launches remain as the fallback (other geometries, dense checkpoints, VOX_BATCH_ENGINE=0, a hand-off timeout).  The launch owns all 256 CUs, so the groups of
     // a step run back to back -- measured on the 647-clip corpus in 64-clip batches (four groups): 6 770 tok/s against 8 540 for the launch chains, then forked on side
     // streams (profiles/r04_b16_fleurs_engine_vs_launches.txt), so batches wider than one group keep the launches (VOX_BATCH_ENGINE_WIDE=1: engine for every width).
     const bool use_eng = allow_engine && !m->ctx->shared && use_xf && steps > 0 && (n_grp == 1 || knob_str("VOX_BATCH_ENGINE_WIDE")) && engb_prepare(m, n_grp);
     DevBuf b_ssq_e;
-    std::vector<EngLayerTab> eng_tabs;
+    std::vector<EngLayerTab> eng_tabs((size_t)(use_eng ? n_grp : 0) * c.dec_layers);      // (alive until the copies below have run: the call's last synchronisation)
     if (use_eng) {
-        HIPCHK(b_ssq_e.alloc_pooled(cx, (size_t)(256 + 16) * 16 * 4 * n_grp));
-        eng_tabs.resize((size_t)n_grp * c.dec_layers);
+        HIPCHK(b_ssq_e.alloc_pooled(cx, (size_t)(256 + 16) * 16 * 4 * n_grp)); xb.ssq_e = b_ssq_e.as<float>();
         for (int gi = 0; gi < n_grp; gi++) {
+            EngLayerTab* tab = eng_tabs.data() + (size_t)gi * c.dec_layers; const size_t g_off = (size_t)gi * 16 * seq_stride;
             for (int l = 0; l < c.dec_layers; l++)
-                eng_tabs[(size_t)gi * c.dec_layers + l] = EngLayerTab{m->dec[l].attn_norm, m->dec[l].ffn_norm, m->dec[l].ada_mul, b_k.as<float>() + (size_t)l * layer_stride + (size_t)gi * 16 * seq_stride,
-                                                                      b_v.as<float>() + (size_t)l * layer_stride + (size_t)gi * 16 * seq_stride};
-            HIPCHK(hipMemcpyAsync(m->engb_tab[gi], eng_tabs.data() + (size_t)gi * c.dec_layers, sizeof(EngLayerTab) * c.dec_layers, hipMemcpyHostToDevice, s));
+                tab[l] = EngLayerTab{m->dec[l].attn_norm, m->dec[l].ffn_norm, m->dec[l].ada_mul, xb.k + (size_t)l * layer_stride + g_off, xb.v + (size_t)l * layer_stride + g_off};
+            HIPCHK(hipMemcpyAsync(m->engb_tab[gi], tab, sizeof(EngLayerTab) * c.dec_layers, hipMemcpyHostToDevice, s));
         }
     }
-    // first generated token of every utterance + the first step's input (and, XF step, its folded first RMSNorm)
-    VOXCHK(tap.rows(b_logits.as<float>(), n, nullptr, 0, d_pos, b_len.as<int>(), s));
-    HIPCHK(launch_argmax_embed_batch(b_logits.as<float>(), n, V, d_tok, tstride, d_pos, b_len.as<int>(), m->tok.w, d_audio, (long)audio_rows * D, D, b_h.as<float>(), s,
-                                     use_xf ? b_xf1.as<uint16_t>() : nullptr, use_xf ? m->dec[0].attn_norm : nullptr, use_xf ? b_ssq.as<float>() : nullptr,
-                                     (long)(xf_bytes(D) / 2), parts_D * 16));
+    // argmax of every row's logits -> its next token, position + 1, next step input (the XF step, not the engine, which reads the f32 rows: also its folded first RMSNorm)
+    const bool gqa = n_grp > 1 || knob_str("VOX_ATTN_GQA");
+    auto next_input = [&](bool xf_in, bool first = false) -> int32_t {
+        VOXCHK(tap.rows(logits, n, nullptr, 0, d_pos, d_len, s));
+        if (!xf_in && !first) HIPCHK(launch_argmax_embed_batch(logits, n, V, d_tok, tstride, d_pos, d_len, m->tok.w, d_audio, (long)audio_rows * D, D, xb.h, s));
+        else HIPCHK(launch_argmax_embed_batch(logits, n, V, d_tok, tstride, d_pos, d_len, m->tok.w, d_audio, (long)audio_rows * D, D, xb.h, s,
+                                              xf_in ? xb.xf1 : nullptr, xf_in ? m->dec[0].attn_norm : nullptr, xf_in ? xb.ssq : nullptr, xb.xf1_gs, (int)xb.ssq_gs));
+        return VOX_OK;
+    };
+    VOXCHK(next_input(use_xf, true));      // first generated token of every utterance + the first step's input
     // `active`: bit gi = group gi still has a sequence that needs this step.  A group whose sequences have all reached their last position is RETIRED: its layer
     // chain is not launched any more (its rows idle in place in the argmax / embedding kernel, whose token write is guarded by the sequence length) -- a ragged
     // batch pays for each group only as long as that group's longest member runs, not for the batch's longest member in every group.
@@ -2594,42 +2671,15 @@ static int32_t transcribe_batch_impl(vox_model* m, int32_t n, const float* const
     // steps on its own stream -- no join, groups drifting freely -- was measured 12 % SLOWER on the 647-clip corpus (8 520 -> 7 630 tok/s,
     // profiles/r03_batch_independent_groups.txt): groups in lock-step find each other's weights in L2 / MALL, drifting groups stream them from HBM once each.
     auto step = [&](uint32_t active) -> int32_t {
-        float* h = b_h.as<float>(); float* xn = b_xn.as<float>(); float* qkv = b_qkv.as<float>(); float* att = b_att.as<float>(); float* act = b_act.as<float>();
-        if (use_xf) {
-            for (int gi = 0; gi < n_grp; gi++) {
-                if (!((active >> gi) & 1u)) continue;
-                const int r0 = gi * 16, ng = std::min(16, n - r0);
-                if (!use_eng) { VOXCHK(xf_group_chain(m, xb, gi, ng, d_pos, nullptr, n_grp > 1 || knob_str("VOX_ATTN_GQA"), max_seq, b_k.as<float>(), b_v.as<float>(), layer_stride, seq_stride, max_seq, s)); continue; }
-                EngBParams ep{}; ep.stream = m->eng_stream; ep.stream_wo = m->eng_wob; ep.layers = m->engb_tab[gi]; ep.n_layers = c.dec_layers; ep.kv_seq_stride = (long)seq_stride; ep.h_in = b_h.as<float>() + (size_t)r0 * D; ep.h_stride = D; ep.n_rows = ng;
-                ep.final_norm = m->dec_norm; ep.pos = d_pos + r0; ep.rope_cos = m->dec_cos; ep.rope_sin = m->dec_sin; ep.max_seq = max_seq; ep.window = c.dec_window; ep.eps = c.norm_eps;
-                engb_state_carve(m->engb_state[gi], &ep); ep.xf_out = b_xf1.as<uint16_t>() + (size_t)gi * xb.xf1_gs; ep.ssq_out = b_ssq_e.as<float>() + (size_t)gi * (256 + 16) * 16; ep.tl = nullptr; ep.tl_layer = -1; ep.flags = m->engb_flags;
-                HIPCHK(launch_decode_engine_b16(ep, s));      // the group's 26 layers as one launch, then its lm_head
-                VOXCHK(engb_group_tail(m, xb, b_ssq_e.as<float>(), gi, ng, s));
-            }
-            VOXCHK(tap.rows(b_logits.as<float>(), n, nullptr, 0, d_pos, b_len.as<int>(), s));
-            if (use_eng) HIPCHK(launch_argmax_embed_batch(b_logits.as<float>(), n, V, d_tok, tstride, d_pos, b_len.as<int>(), m->tok.w, d_audio, (long)audio_rows * D, D, h, s));      // the engine reads the f32 rows
-            else HIPCHK(launch_argmax_embed_batch(b_logits.as<float>(), n, V, d_tok, tstride, d_pos, b_len.as<int>(), m->tok.w, d_audio, (long)audio_rows * D, D, h, s,
-                                                  b_xf1.as<uint16_t>(), m->dec[0].attn_norm, b_ssq.as<float>(), (long)(xf_bytes(D) / 2), parts_D * 16));
-            return VOX_OK;
+        if (!use_xf) { VOXCHK(f32_batch_layers(m, xb, n, b_xn.as<float>(), b_act.as<float>(), s)); return next_input(false); }
+        for (int gi = 0; gi < n_grp; gi++) {
+            if (!((active >> gi) & 1u)) continue;
+            const int ng = std::min(16, n - gi * 16);
+            if (!use_eng) { VOXCHK(xf_chain(m, xb, gi, ng, 0, 0, gqa, max_seq, s)); continue; }
+            HIPCHK(launch_decode_engine_b16(engb_params(m, xb, gi, ng, gi, gi, false), s));      // the group's 26 layers as one launch, then its lm_head
+            VOXCHK(engb_group_tail(m, xb, gi, ng, s));
         }
-        for (int l = 0; l < c.dec_layers; l++) {
-            const DecLayer& L = m->dec[l]; float* kl = b_k.as<float>() + (size_t)l * layer_stride; float* vl = b_v.as<float>() + (size_t)l * layer_stride;
-            HIPCHK(launch_rms_norm(h, D, n, D, L.attn_norm, nullptr, c.norm_eps, xn, D, s));
-            { GemmParams g{}; g.w = L.wqkv.w; g.x = xn; g.x_stride = D; g.M = n; g.out = qkv; g.out_stride = W; HIPCHK(launch_q4_gemm(g, EPI_STORE, s)); }
-            HIPCHK(launch_rope_kv_batch(qkv, n, W, QD, KV, hd, d_pos, m->dec_cos, m->dec_sin, kl, vl, (long)seq_stride, max_seq * hd, s));
-            AttnParams ap{}; ap.q = qkv; ap.k = kl; ap.v = vl; ap.kv_row_stride = hd; ap.kv_head_stride = max_seq * hd; ap.out = att; ap.n_heads = H; ap.n_kv_heads = KV;
-            ap.offset = 0; ap.window = c.dec_window; ap.pos_ptr = d_pos; ap.M = 1; ap.pos_per_seq = 1; ap.q_seq_stride = W; ap.out_seq_stride = QD; ap.kv_seq_stride = (long)seq_stride; ap.spec_rows = max_seq;
-            HIPCHK(launch_attn_decode(ap, hd, max_seq, s, n));
-            { GemmParams g{}; g.w = L.wo.w; g.x = att; g.x_stride = QD; g.M = n; g.out = h; g.out_stride = D; g.resid = h; g.resid_stride = D; HIPCHK(launch_q4_gemm(g, EPI_RESID, s)); }
-            HIPCHK(launch_rms_norm(h, D, n, D, L.ffn_norm, L.ada_mul, c.norm_eps, xn, D, s));
-            { GemmParams g{}; g.w = L.w13.w; g.x = xn; g.x_stride = D; g.M = n; g.out = act; g.out_stride = F; HIPCHK(launch_q4_gemm(g, EPI_SWIGLU, s)); }
-            { GemmParams g{}; g.w = L.w2.w; g.x = act; g.x_stride = F; g.M = n; g.out = h; g.out_stride = D; g.resid = h; g.resid_stride = D; HIPCHK(launch_q4_gemm(g, EPI_RESID, s)); }
-        }
-        HIPCHK(launch_rms_norm(h, D, n, D, m->dec_norm, nullptr, c.norm_eps, xn, D, s));
-        { GemmParams g{}; g.w = m->tok.w; g.x = xn; g.x_stride = D; g.M = n; g.out = b_logits.as<float>(); g.out_stride = V; HIPCHK(launch_q4_gemm(g, EPI_STORE, s)); }
-        VOXCHK(tap.rows(b_logits.as<float>(), n, nullptr, 0, d_pos, b_len.as<int>(), s));
-        HIPCHK(launch_argmax_embed_batch(b_logits.as<float>(), n, V, d_tok, tstride, d_pos, b_len.as<int>(), m->tok.w, d_audio, (long)audio_rows * D, D, h, s));
-        return VOX_OK;
+        return next_input(!use_eng);
     };
     // steps of group gi = those of its longest member; with the rows sorted by length (vox_transcribe_batch does that) the groups retire last to first
     std::vector<int> steps_g(n_grp, 0);
@@ -2653,7 +2703,8 @@ static int32_t transcribe_batch_impl(vox_model* m, int32_t n, const float* const
     VOXCHK(copy_out_ids(n, S, tstride, d_tok, out_ids, n_ids, &total, s));
     m->timings.preprocess_ms = pre_ms; m->timings.encode_ms = enc_ms; m->timings.decode_ms = now_ms() - t1; m->timings.total_ms = now_ms() - t0;
     m->timings.decode_tokens = total; m->timings.graph_replays = replays;
-    if (knob_str("VOX_BATCH_VERBOSE")) fprintf(stderr, "[voxtral_hip] lock-step batch: %d rows, %d groups, %d steps, step form %s\n", n, n_grp, steps, use_eng ? "engine" : use_xf ? "xf-chains" : "f32");
+    if (knob_str("VOX_BATCH_VERBOSE"))
+        fprintf(stderr, "[voxtral_hip] lock-step batch: %d rows, %d groups, %d steps, step form %s\n", n, n_grp, steps, use_eng ? "engine" : use_xf ? "xf-chains" : "f32");
     return VOX_OK;
 }
 
@@ -2675,6 +2726,23 @@ static const double kStepMs[9] = {0.0, 1.84, 2.08, 2.75, 3.15, 3.55, 3.80, 4.35,
 // ... with the batched decode-layer engine serving the steps of <= 2 active groups (one group: decode_engine_b16_kernel<1>, 1.06 ms + tail; two: the two-group launch,
 // 1.60 ms + tail; three and four groups stay on the launch chains -- a two-group launch + a one- or two-group launch back to back: 2.9 / 3.4 ms against 2.75 / 3.40)
 static const double kStepMsEng[9] = {0.0, 1.17, 1.77, 2.75, 3.15, 3.55, 3.80, 4.35, 4.70};      // (four groups: the wide step, round 6)
+// Step costs the planner prices a session with: the table `base`, corrected by what the context has measured (`meas`, 0 = form not seen yet) -- a form seen before costs
+// what it cost (clock, a shared GPU, another geometry), a form not seen yet the table's value times the mean measured / table ratio of the forms that were.  calib off
+// (VOX_BATCH_NO_CALIB=1): the table alone.
+static void step_costs(const double* base, const double* meas, bool calib, bool shared, double* out) {
+    double ratio = 0.0; int nr = 0;
+    for (int g2 = 1; g2 <= kMaxGroups; g2++) if (calib && meas[g2] > 0.0) { ratio += meas[g2] / base[g2]; nr++; }
+    ratio = nr ? std::min(4.0, std::max(0.25, ratio / nr)) : 1.0;
+    // The common factor (clock, a GPU shared with another session) is taken as measured; a form's deviation from it is trusted within +-15 % only, and a step of more
+    // groups never costs less than one of fewer: next to a second session on the GPU (tools/two_sessions_probe.py) the per-form figures scatter (a 3-group step "measured"
+    // at 5.35 ms against 4.18 for four groups made the next session plan 48 slots instead of 64: 4.71 s instead of 3.77 s for the corpus)
+    out[0] = 0.0;
+    for (int g2 = 1; g2 <= kMaxGroups; g2++) {
+        const double common = base[g2] * ratio;
+        out[g2] = (calib && !shared && meas[g2] > 0.0) ? common * std::min(1.15, std::max(0.85, meas[g2] / common)) : common;      // (a shared GPU: the common factor only)
+        out[g2] = std::max(out[g2], out[g2 - 1]);
+    }
+}
 struct SlotPlan { int G = 0; std::vector<std::vector<int>> queue; std::vector<int> steps_g; double cost_ms = 0.0; };
 // jobs: (decode steps, utterance) with steps >= 1.  LPT onto 16 G slots, slots ordered by load (so the groups retire last to first), G by the cost model.
 static SlotPlan plan_slots(const std::vector<std::pair<int, int>>& jobs_in, int force_G, const double* step_ms, int max_groups = 4) {
@@ -2696,6 +2764,28 @@ static SlotPlan plan_slots(const std::vector<std::pair<int, int>>& jobs_in, int 
     }
     return best;
 }
+// A plan as the decode loop uses it: the slot queues flattened (slot sl's k-th utterance at h_queue[sl q_stride + k], -1 behind its last), the steps of the whole
+// decode, and how long each group RUNS.  A group retires when its queues are empty -- but every distinct set of active groups is a graph capture + instantiation
+// (~10 ms): a group that would retire fewer than kRetireSlack steps before the next longer one keeps running with idle slots instead (harmless: idle rows compute on zeros).
+static const int kRetireSlack = 12;
+struct SlotSchedule {
+    SlotPlan plan; int G = 1, Sl = 16, q_stride = 1, steps = 0; std::vector<int> h_queue; int run_g[kMaxGroups] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t active_at(int t) const { uint32_t a = 0; for (int gi = 0; gi < G; gi++) if (t < run_g[gi]) a |= 1u << gi; return a; }
+};
+static SlotSchedule slot_schedule(const std::vector<std::pair<int, int>>& jobs, int force_G, const double* step_ms, int max_groups) {
+    SlotSchedule z; z.plan = plan_slots(jobs, force_G, step_ms, max_groups);
+    const SlotPlan& plan = z.plan;
+    z.G = std::max(plan.G, 1); z.Sl = 16 * z.G;
+    for (auto& q : plan.queue) z.q_stride = std::max(z.q_stride, (int)q.size() + 1);
+    z.h_queue.assign((size_t)z.Sl * z.q_stride, -1);
+    for (size_t sl = 0; sl < plan.queue.size(); sl++) for (size_t k = 0; k < plan.queue[sl].size(); k++) z.h_queue[sl * z.q_stride + k] = plan.queue[sl][k];
+    z.steps = plan.steps_g.empty() ? 0 : plan.steps_g[0];
+    for (size_t gi = 0; gi < plan.steps_g.size(); gi++) z.run_g[gi] = plan.steps_g[gi];
+    for (int gi = 1; gi < z.G; gi++) {      // walk from the longest group down: snap a group to the previous one's run length when it is close
+        if (z.run_g[gi - 1] - plan.steps_g[gi] < kRetireSlack) z.run_g[gi] = z.run_g[gi - 1];
+    }
+    return z;
+}
 // the wide step's geometry: every decoder layer the shape of layer 0, tile-ordered Q4 copies, no biases, plans for 2 .. 4 groups per chain
 static bool wide_geom_ok(const vox_model* m) {
     const vox_model_cfg& c = m->cfg;
@@ -2716,354 +2806,384 @@ static size_t wide_planes_bytes(const vox_model* m, int mt_max) {
     for (int mtw = 2; mtw <= mt_max; mtw++) for (auto& o : ops) { WidePlan pl; if (q4_wide_plan(*o.w, mtw, o.epi, &pl)) bytes = std::max(bytes, q4_wide_planes_bytes(*o.w, mtw, pl)); }
     return bytes;
 }
-static int32_t transcribe_continuous_impl(vox_model* m, int32_t n, const float* const* samples, const size_t* n_samples, const float* t_embed,
-                                          int32_t* const* out_ids, const int32_t* caps, int32_t* n_ids, int32_t mem_kind, const int* slot_of, bool allow_engine,
-                                          const float* const* unit_scale = nullptr) {
-    VOXCHK(ctx_bind(m->ctx));
-    const vox_model_cfg& c = m->cfg; vox_ctx* cx = m->ctx; hipStream_t s = cx->stream;
-    ARGCHK(c.n_mels == 128, "the log-mel front-end produces 128 bins; model expects %d", c.n_mels);
-    const int PREFIX_LEN = 38;
-    int CHUNK = 64; if (const char* e = knob_str("VOX_BATCH_CHUNK")) CHUNK = std::max(1, std::min(128, atoi(e)));      // utterances per encoder / prefill stack (measurement knob: 128 measured equal to 64, profiles/r05_continuous_sweep.txt)
-    const int D = c.dec_dim, H = c.dec_heads, KV = c.dec_kv_heads, hd = c.dec_head_dim, QD = H * hd, KD = KV * hd, W = QD + 2 * KD, F = c.dec_ffn, V = c.vocab, R = c.reshape_factor;
-    VOXCHK(vox_model_set_t_embed(m, t_embed));
-    m->timings = vox_timings{};
-    MelTables mt; VOXCHK(ctx_mel_tables(cx, &mt));
-    std::vector<int> S, T, len; int Smax = 0;
-    VOXCHK(batch_lengths(m, n, samples, n_samples, caps, slot_of, T, S, len, &Smax));
-    const int max_seq = std::max((Smax + 63) / 64 * 64, 64), tstride = std::max(Smax, PREFIX_LEN) + 2;
-    const size_t seq_stride = (size_t)KV * max_seq * hd, layer_stride = (size_t)(n + 1) * seq_stride;      // slice n of every layer: the scratch slice idle slots write to and read
-    // the stacked encoder runs in chunks of <= 64 utterances, PACKED (encode_batch_dev: every utterance its own rows, no padding to the longest): the audio rows of
-    // utterance i start audio_off[i] floats into the audio buffer
-    const int n_chunks = (n + CHUNK - 1) / CHUNK;
-    std::vector<int> chunk0(n_chunks + 1, 0);      // full chunks first (measured on 81 utterances: 64 + 17 against 41 + 40 -- the packed encoder costs the same, 247 ms, the stacked prefill 57 instead of 66 ms)
-    for (int ci = 0; ci < n_chunks; ci++) chunk0[ci + 1] = std::min(n, chunk0[ci] + CHUNK);
-    std::vector<size_t> aoff_c(n_chunks); std::vector<long> audio_off(n);
-    size_t audio_floats = 0, mel_max = 0, smp_max = 0;
-    for (int ci = 0; ci < n_chunks; ci++) {
-        const int c0 = chunk0[ci], nc = chunk0[ci + 1] - c0;
-        aoff_c[ci] = audio_floats;
-        size_t mf = 0, sf = 0; long rows = 0;
-        for (int i = c0; i < c0 + nc; i++) { audio_off[i] = (long)(aoff_c[ci] + (size_t)(rows / R) * D); rows += enc_packed_rows_of(m, T[i]); mf += (size_t)128 * T[i]; sf += n_samples[i]; }
-        audio_floats += (size_t)(rows / R) * D; mel_max = std::max(mel_max, mf); smp_max = std::max(smp_max, sf);
-    }
-    audio_floats += (size_t)(PREFIX_LEN + 2) * D;      // slack behind the last utterance: a (never occurring, see test_audio_entry_points_never_reach_prefix_len_edge) S < 39 reads a row past its own
-    // the decode plan (host only: lengths are known)
-    std::vector<std::pair<int, int>> jobs;
-    for (int i = 0; i < n; i++) if (len[i] > PREFIX_LEN + 1) jobs.emplace_back(len[i] - PREFIX_LEN - 1, i);
-    int force_G = 0; if (const char* e = knob_str("VOX_BATCH_SLOT_GROUPS")) force_G = std::max(0, std::min(kMaxGroups, atoi(e)));
+// Every knob the continuous driver consults, read once per session (cont_policy), and what follows from them once the plan's group count G is known (cont_policy_groups).
+struct ContPolicy {
+    int chunk = 64;      // utterances per encoder / prefill stack (VOX_BATCH_CHUNK, measurement knob: 128 measured equal to 64, profiles/r05_continuous_sweep.txt)
+    int force_G = 0, max_groups = 4;      // VOX_BATCH_SLOT_GROUPS; more than four groups = two wide chains per step (VOX_BATCH_MAX_GROUPS caps it)
+    bool shared = false, use_eng = false, calib = true, no_fe_overlap = false, no_graph = false, verbose = false, no_xcd = false, no_wide = false, no_wide_split = false;
+    int wide_min = 4, wide_chains = 2;      // VOX_BATCH_WIDE_MIN = 2 / 3: measurement knob and tests; VOX_BATCH_WIDE_CHAINS: measurement knob, more than two chains per step
+    int G = 1; bool wide_ok = false, wide_split = false;
+};
+static ContPolicy cont_policy(vox_model* m, bool allow_engine, bool have_jobs) {
+    ContPolicy p; p.shared = m->ctx->shared;
+    if (const char* e = knob_str("VOX_BATCH_CHUNK")) p.chunk = std::max(1, std::min(128, atoi(e)));
+    if (const char* e = knob_str("VOX_BATCH_SLOT_GROUPS")) p.force_G = std::max(0, std::min(kMaxGroups, atoi(e)));
+    p.no_wide = knob_str("VOX_BATCH_NO_WIDE") != nullptr; p.no_wide_split = knob_str("VOX_BATCH_NO_WIDE_SPLIT") != nullptr;
     // more than four groups = two wide chains per step: needs the wide step's geometry and a GPU of its own (on a shared one the other session fills the gaps)
-    int max_groups = 4;
-    if (!cx->shared && !knob_str("VOX_BATCH_NO_WIDE") && !knob_str("VOX_BATCH_NO_WIDE_SPLIT") && wide_geom_ok(m)) { max_groups = kMaxGroups; if (const char* e = knob_str("VOX_BATCH_MAX_GROUPS")) max_groups = std::max(1, std::min(kMaxGroups, atoi(e))); }
-    if (force_G > max_groups) force_G = max_groups;
+    if (!p.shared && !p.no_wide && !p.no_wide_split && wide_geom_ok(m)) {
+        p.max_groups = kMaxGroups; if (const char* e = knob_str("VOX_BATCH_MAX_GROUPS")) p.max_groups = std::max(1, std::min(kMaxGroups, atoi(e)));
+    }
+    if (p.force_G > p.max_groups) p.force_G = p.max_groups;
     // the steps of one or two active groups go through the batched decode-layer engine (vox_engine_b16.hip: one launch per step for the 26 layers of both groups, cache
     // slices per slot through EngBParams::kv_row); wider steps, other geometries, VOX_BATCH_ENGINE=0 and the re-run after a hand-off timeout use the launch chains
-    const bool use_eng = allow_engine && !cx->shared && !jobs.empty() && !knob_str("VOX_BATCH_CONT_NO_ENGINE") && engb_prepare(m, 2);
-    // step costs: the table above, corrected by what this context has measured -- a form seen before costs what it cost (clock, a shared GPU, another geometry), a form not
-    // seen yet the table's value times the mean measured / table ratio of the forms that were.  VOX_BATCH_NO_CALIB=1: the table alone.
-    double base_tab[9]; for (int g2 = 0; g2 < 9; g2++) base_tab[g2] = (use_eng ? kStepMsEng : kStepMs)[g2];
-    if (!cx->shared && !knob_str("VOX_BATCH_NO_WIDE_SPLIT")) base_tab[4] = 2.95;      // four groups as two two-group wide chains (below): 3.12 -> 2.92 ms net of the prefill (measured with the chains forked)
-    double step_cost[9]; const double* base_cost = base_tab; const bool calib = !knob_str("VOX_BATCH_NO_CALIB");
-    {
-        const double* meas = cx->step_ms_meas[use_eng ? 0 : 1]; double ratio = 0.0; int nr = 0;
-        for (int g2 = 1; g2 <= kMaxGroups; g2++) if (calib && meas[g2] > 0.0) { ratio += meas[g2] / base_cost[g2]; nr++; }
-        ratio = nr ? std::min(4.0, std::max(0.25, ratio / nr)) : 1.0;
-        // The common factor (clock, a GPU shared with another session) is taken as measured; a form's deviation from it is trusted within +-15 % only, and a step of more
-        // groups never costs less than one of fewer: next to a second session on the GPU (tools/two_sessions_probe.py) the per-form figures scatter (a 3-group step "measured"
-        // at 5.35 ms against 4.18 for four groups made the next session plan 48 slots instead of 64: 4.71 s instead of 3.77 s for the corpus)
-        step_cost[0] = 0.0;
-        for (int g2 = 1; g2 <= kMaxGroups; g2++) {
-            const double common = base_cost[g2] * ratio;
-            step_cost[g2] = (calib && !cx->shared && meas[g2] > 0.0) ? common * std::min(1.15, std::max(0.85, meas[g2] / common)) : common;      // (a shared GPU: the common factor only)
-            step_cost[g2] = std::max(step_cost[g2], step_cost[g2 - 1]);
-        }
+    p.use_eng = allow_engine && !p.shared && have_jobs && !knob_str("VOX_BATCH_CONT_NO_ENGINE") && engb_prepare(m, 2);
+    p.calib = !knob_str("VOX_BATCH_NO_CALIB"); p.no_fe_overlap = knob_str("VOX_BATCH_NO_FE_OVERLAP") != nullptr; p.no_graph = knob_str("VOX_BATCH_NO_GRAPH") != nullptr;
+    p.verbose = knob_str("VOX_BATCH_VERBOSE") != nullptr; p.no_xcd = knob_str("VOX_ATTN_NO_XCD") != nullptr;
+    if (const char* e = knob_str("VOX_BATCH_WIDE_MIN")) p.wide_min = std::max(2, std::min(5, atoi(e)));
+    if (const char* e = knob_str("VOX_BATCH_WIDE_CHAINS")) p.wide_chains = std::max(2, std::min(4, atoi(e)));
+    return p;
+}
+// The wide step serves the steps with >= wide_min active groups, 4 by default.  Measured (tools/wide_probe.py, 24 s clips, every slot busy; profiles/r06_wide_step.txt):
+// 64 slots 3.26 ms per step against 3.55 on four launch chains, then forked, 48 slots 3.11 against 3.04.
+// wide_split: a four-group step as TWO two-group wide chains instead of one four-group chain, run back to back on `s` like every chain of a step.  Measured with the two chains
+// forked on two streams (round 6): a third of a wide step is dependency gaps between its ~236 launches (profiles/r06_corpus_sessions.txt), and the two chains filled
+// each other's -- every weight is streamed twice, which a step at 0.7 TB/s can afford: 64-slot step 3.49 -> 3.29 ms (prefill included), corpus 4.54 -> 4.37 s, same
+// ids (profiles/r06_wide_split.txt).  NOT on a shared GPU (vox_ctx_set_shared / sessions): there the other session already filled the gaps and four concurrent chains
+// only contended (two sessions: 3.80 s without, 4.46 s with).  VOX_BATCH_NO_WIDE_SPLIT=1: one chain.
+static void cont_policy_groups(ContPolicy& p, const vox_model* m, int G) {
+    p.G = G;
+    p.wide_ok = !p.no_wide && G >= p.wide_min && wide_geom_ok(m);
+    p.wide_split = p.wide_ok && G >= 4 && p.wide_min <= 4 && !p.shared && !p.no_wide_split;
+}
+// What a step of `active` runs: the engine (groups ga, gb), nc wide chains of szc[j] groups from group 0, or (nc == 0) one launch chain per active group.  `bits`:
+// the kernels it launches, for warm_forms (the dynamic-LDS limits are raised at a kernel's first launch on a device -- see cont_warm_forms).
+enum : uint32_t { kChains = 1u, kEng1 = 2u, kEng2 = 4u, kWide2 = 8u };      // (kWide2 << (mt - 2): wide chains of mt = 2, 3, 4 groups)
+struct StepForm {
+    int n_act = 0, ga = -1, gb = -1, nc = 0, szc[4] = {0, 0, 0, 0}; uint32_t bits = 0;
+    bool engine() const { return (bits & (kEng1 | kEng2)) != 0; }
+    int report_slot() const { return (bits & kEng1) ? 1 : (bits & kEng2) ? 2 : nc == 1 ? 3 : nc > 1 ? 4 : 0; }      // cont_report: chains, engine1, engine2, wide, split
+};
+static StepForm form_of(const ContPolicy& p, uint32_t active) {
+    StepForm f;
+    for (int gi = 0; gi < p.G; gi++) if ((active >> gi) & 1u) { f.n_act++; if (f.ga < 0) f.ga = gi; else f.gb = gi; }
+    if (p.use_eng && f.n_act <= 2) { f.bits = f.gb < 0 ? kEng1 : kEng2; return f; }
+    if (p.wide_ok && f.n_act >= p.wide_min && active == (1u << f.n_act) - 1) {      // (active groups are a prefix: the slots are ordered by load)
+        f.nc = p.wide_split && f.n_act >= 4 ? std::max(2, std::min(p.wide_chains, f.n_act / 2)) : 1;      // chains of >= 2 groups, sizes balanced, the larger ones first
+        for (int j = 0; j < f.nc; j++) { f.szc[j] = f.n_act / f.nc + (j < f.n_act % f.nc ? 1 : 0); f.bits |= kWide2 << (f.szc[j] - 2); }
+        return f;
     }
-    const SlotPlan plan = plan_slots(jobs, force_G, step_cost, max_groups);
-    const int G = std::max(plan.G, 1), Sl = 16 * G;
-    int q_stride = 1; for (auto& q : plan.queue) q_stride = std::max(q_stride, (int)q.size() + 1);
-    std::vector<int> h_queue((size_t)Sl * q_stride, -1);
-    for (size_t sl = 0; sl < plan.queue.size(); sl++) for (size_t k = 0; k < plan.queue[sl].size(); k++) h_queue[sl * q_stride + k] = plan.queue[sl][k];
-    const int steps = plan.steps_g.empty() ? 0 : plan.steps_g[0];
-
+    f.bits = kChains; return f;
+}
+// The stacked encoder runs in chunks of <= CHUNK utterances, PACKED (encode_batch_dev: every utterance its own rows, no padding to the longest): chunk ci is utterances
+// chunk0[ci] .. chunk0[ci + 1] - 1, its audio rows start aoff_c[ci] floats into the audio buffer and those of utterance i audio_off[i] floats; mel_max / smp_max: the
+// largest chunk's log-mel floats / samples.  Host arithmetic only.
+struct ChunkLayout { int n_chunks = 0; std::vector<int> chunk0; std::vector<size_t> aoff_c; std::vector<long> audio_off; size_t audio_floats = 0, mel_max = 0, smp_max = 0; };
+static ChunkLayout chunk_layout(const vox_model* m, const std::vector<int>& T, const size_t* n_samples, int CHUNK) {
+    const int n = (int)T.size(), R = m->cfg.reshape_factor, D = m->cfg.dec_dim;
+    ChunkLayout z; z.n_chunks = (n + CHUNK - 1) / CHUNK;
+    // full chunks first (measured on 81 utterances: 64 + 17 against 41 + 40 -- the packed encoder costs the same, 247 ms, the stacked prefill 57 instead of 66 ms)
+    z.chunk0.assign(z.n_chunks + 1, 0);
+    for (int ci = 0; ci < z.n_chunks; ci++) z.chunk0[ci + 1] = std::min(n, z.chunk0[ci] + CHUNK);
+    z.aoff_c.resize(z.n_chunks); z.audio_off.resize(n);
+    for (int ci = 0; ci < z.n_chunks; ci++) {
+        const int c0 = z.chunk0[ci], nc = z.chunk0[ci + 1] - c0;
+        z.aoff_c[ci] = z.audio_floats;
+        size_t mf = 0, sf = 0; long rows = 0;
+        for (int i = c0; i < c0 + nc; i++) { z.audio_off[i] = (long)(z.aoff_c[ci] + (size_t)(rows / R) * D); rows += enc_packed_rows_of(m, T[i]); mf += (size_t)128 * T[i]; sf += n_samples[i]; }
+        z.audio_floats += (size_t)(rows / R) * D; z.mel_max = std::max(z.mel_max, mf); z.smp_max = std::max(z.smp_max, sf);
+    }
+    // slack behind the last utterance: a (never occurring, see test_audio_entry_points_never_reach_prefix_len_edge) S < 39 reads a row past its own
+    z.audio_floats += (size_t)(VOX_PREFIX_TOKENS + 2) * D;
+    return z;
+}
+// (an event where the set of active groups changes: the runs in between are what the planner's next session on this context is priced with)
+struct StepSegments { int n[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, act[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, n_seg = 0; };
+// One continuous session: the call's arguments, its plan (host only), its device buffers and its timers.  The pooled buffers go back to the pool when the session goes out
+// of scope; `drain`, declared after them, empties the streams first.
+struct ContSession {
+    vox_model* m; vox_ctx* cx; hipStream_t s; MelTables mt;
+    int n = 0; const float* const* samples = nullptr; const size_t* n_samples = nullptr; const float* const* unit_scale = nullptr; int32_t mem_kind = 0; const int* slot_of = nullptr;
+    std::vector<int> S, T, len; int max_seq = 0, tstride = 0; size_t seq_stride = 0, layer_stride = 0;      // slice n of every layer: the scratch slice idle slots write to and read
+    ContPolicy pol; ChunkLayout lay; SlotSchedule sch; double step_cost[9];
+    bool fe_overlap = false; size_t mel_half = 1, smp_half = 1; int ncm = 0;      // front-end buffers: halves of the ping-pong, ncm = utterances of the largest chunk
     DevBuf b_audio, b_k, b_v, b_tok, b_posc, b_len, b_h0, b_aoff, b_px, b_xn, b_lg0, b_mel, b_scale, b_smp;
-    DevBuf b_queue, b_sclip, b_sqpos, b_pos, b_kvrow, b_h, b_qkv, b_att, b_logits, b_xf1, b_xf2, b_xf3, b_ssq, b_ssq_e;
-    BatchTapCall tap; VOXCHK(tap.init(m, n, slot_of, s));
-    BatchDrain drain{cx};
-    HIPCHK(b_audio.alloc_pooled(cx, audio_floats * 4)); HIPCHK(b_k.alloc_pooled(cx, layer_stride * c.dec_layers * 4)); HIPCHK(b_v.alloc_pooled(cx, layer_stride * c.dec_layers * 4));
-    HIPCHK(b_tok.alloc_pooled(cx, (size_t)n * tstride * 4)); HIPCHK(b_posc.alloc_pooled(cx, (size_t)n * 4)); HIPCHK(b_len.alloc_pooled(cx, (size_t)n * 4));
-    HIPCHK(b_h0.alloc_pooled(cx, (size_t)n * D * 4)); HIPCHK(b_aoff.alloc_pooled(cx, (size_t)n * sizeof(long)));
-    const int ncm = std::min(n, CHUNK);
-    HIPCHK(b_px.alloc_pooled(cx, (size_t)ncm * PREFIX_LEN * D * 4)); HIPCHK(b_xn.alloc_pooled(cx, (size_t)ncm * D * 4)); HIPCHK(b_lg0.alloc_pooled(cx, (size_t)ncm * V * 4));
-    // front-end buffers TWICE: chunk ci + 1's samples go up and its log-mel is computed on a second stream while chunk ci's encoder runs (VOX_BATCH_NO_FE_OVERLAP=1: one stream)
-    // (not on a shared context: with two sessions uploading from two threads the second stream made each session's encoder stage 1.8 x longer under the HIP runtime that
-    // PyTorch bundles -- bench.py: 3.82 -> 4.55 s for the two-session corpus -- while the stand-alone runtime did not care)
-    const bool fe_overlap = n_chunks > 1 && !cx->shared && !knob_str("VOX_BATCH_NO_FE_OVERLAP");
-    const size_t mel_half = std::max<size_t>(mel_max, 1), smp_half = std::max<size_t>(smp_max, 1);
-    HIPCHK(b_mel.alloc_pooled(cx, mel_half * 4 * (fe_overlap ? 2 : 1))); HIPCHK(b_scale.alloc_pooled(cx, (size_t)ncm * 4 * (fe_overlap ? 2 : 1)));
-    if (mem_kind == VOX_MEM_HOST) HIPCHK(b_smp.alloc_pooled(cx, smp_half * 4 * (fe_overlap ? 2 : 1)));
-    if (fe_overlap) {
-        if (!cx->fe_stream) HIPCHK(hipStreamCreateWithFlags(&cx->fe_stream, hipStreamNonBlocking));
-        for (int k = 0; k < 2; k++) { if (!cx->ev_fe[k]) HIPCHK(hipEventCreateWithFlags(&cx->ev_fe[k], hipEventDisableTiming)); if (!cx->ev_enc[k]) HIPCHK(hipEventCreateWithFlags(&cx->ev_enc[k], hipEventDisableTiming)); }
+    DevBuf b_queue, b_sclip, b_sqpos, b_pos, b_kvrow, b_h, b_qkv, b_att, b_logits, b_ssq_e, b_planes; XfPlanes xfp; XfBufs xb{}; SlotStepParams sp{};      // the decode step's
+    BatchTapCall tap; BatchDrain drain;
+    double pre_ms = 0.0, enc_ms = 0.0, pf_ms = 0.0, t0 = 0.0, t1 = 0.0, capture_ms = 0.0; int replays = 0, n_captures = 0;
+    int form_steps[5] = {0, 0, 0, 0, 0};      // VOX_BATCH_VERBOSE: decode steps on the launch chains, the one- / two-group engine, one wide chain, two or more wide chains
+    explicit ContSession(vox_model* mm) : m(mm), cx(mm->ctx), s(mm->ctx->stream), drain{mm->ctx} {}
+    // phase A's buffers and everything the host uploads once: prefix tokens, audio offsets, slot queues, the engine's layer table
+    int32_t alloc() {
+        const vox_model_cfg& c = m->cfg; const int D = c.dec_dim, V = c.vocab;
+        HIPCHK(b_audio.alloc_pooled(cx, lay.audio_floats * 4)); HIPCHK(b_k.alloc_pooled(cx, layer_stride * c.dec_layers * 4)); HIPCHK(b_v.alloc_pooled(cx, layer_stride * c.dec_layers * 4));
+        HIPCHK(b_tok.alloc_pooled(cx, (size_t)n * tstride * 4)); HIPCHK(b_posc.alloc_pooled(cx, (size_t)n * 4)); HIPCHK(b_len.alloc_pooled(cx, (size_t)n * 4));
+        HIPCHK(b_h0.alloc_pooled(cx, (size_t)n * D * 4)); HIPCHK(b_aoff.alloc_pooled(cx, (size_t)n * sizeof(long)));
+        ncm = std::min(n, pol.chunk);
+        HIPCHK(b_px.alloc_pooled(cx, (size_t)ncm * VOX_PREFIX_TOKENS * D * 4)); HIPCHK(b_xn.alloc_pooled(cx, (size_t)ncm * D * 4)); HIPCHK(b_lg0.alloc_pooled(cx, (size_t)ncm * V * 4));
+        // front-end buffers TWICE: chunk ci + 1's samples go up and its log-mel is computed on a second stream while chunk ci's encoder runs (VOX_BATCH_NO_FE_OVERLAP=1: one stream)
+        // (not on a shared context: with two sessions uploading from two threads the second stream made each session's encoder stage 1.8 x longer under the HIP runtime that
+        // PyTorch bundles -- bench.py: 3.82 -> 4.55 s for the two-session corpus -- while the stand-alone runtime did not care)
+        fe_overlap = lay.n_chunks > 1 && !cx->shared && !pol.no_fe_overlap;
+        const int halves = fe_overlap ? 2 : 1;
+        mel_half = std::max<size_t>(lay.mel_max, 1); smp_half = std::max<size_t>(lay.smp_max, 1);
+        HIPCHK(b_mel.alloc_pooled(cx, mel_half * 4 * halves)); HIPCHK(b_scale.alloc_pooled(cx, (size_t)ncm * 4 * halves));
+        if (mem_kind == VOX_MEM_HOST) HIPCHK(b_smp.alloc_pooled(cx, smp_half * 4 * halves));
+        if (fe_overlap) {
+            if (!cx->fe_stream) HIPCHK(hipStreamCreateWithFlags(&cx->fe_stream, hipStreamNonBlocking));
+            for (int k = 0; k < 2; k++) {
+                if (!cx->ev_fe[k]) HIPCHK(hipEventCreateWithFlags(&cx->ev_fe[k], hipEventDisableTiming));
+                if (!cx->ev_enc[k]) HIPCHK(hipEventCreateWithFlags(&cx->ev_enc[k], hipEventDisableTiming));
+            }
+        }
+        HIPCHK(hipMemsetAsync(b_audio.p, 0, lay.audio_floats * 4, s)); HIPCHK(hipMemsetAsync(b_h0.p, 0, (size_t)n * D * 4, s));
+        VOXCHK(upload_prefix(n, tstride, len, b_tok.as<int>(), b_posc.as<int>(), b_len.as<int>(), s));
+        HIPCHK(hipMemcpyAsync(b_aoff.p, lay.audio_off.data(), (size_t)n * sizeof(long), hipMemcpyHostToDevice, s));
+        const std::vector<int>& hq = sch.h_queue;      // (the slot queues too: no pageable copy may sit behind phase A)
+        HIPCHK(b_queue.alloc_pooled(cx, hq.size() * 4)); HIPCHK(hipMemcpyAsync(b_queue.p, hq.data(), hq.size() * 4, hipMemcpyHostToDevice, s));
+        std::vector<EngLayerTab> tab(c.dec_layers);      // the engine's layer table, one for every group: the layers' slabs (cache slices are picked per slot)
+        for (int l = 0; l < c.dec_layers; l++)
+            tab[l] = EngLayerTab{m->dec[l].attn_norm, m->dec[l].ffn_norm, m->dec[l].ada_mul, b_k.as<float>() + (size_t)l * layer_stride, b_v.as<float>() + (size_t)l * layer_stride};
+        if (pol.use_eng) HIPCHK(hipMemcpyAsync(m->engb_tab[0], tab.data(), sizeof(EngLayerTab) * c.dec_layers, hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));      // the host vectors go out of scope
+        return VOX_OK;
     }
-    HIPCHK(hipMemsetAsync(b_audio.p, 0, audio_floats * 4, s)); HIPCHK(hipMemsetAsync(b_h0.p, 0, (size_t)n * D * 4, s));
-    float* d_audio = b_audio.as<float>(); int* d_tok = b_tok.as<int>();
-    VOXCHK(upload_prefix(n, tstride, len, d_tok, b_posc.as<int>(), b_len.as<int>(), s));
-    HIPCHK(hipMemcpyAsync(b_aoff.p, audio_off.data(), (size_t)n * sizeof(long), hipMemcpyHostToDevice, s));
-    HIPCHK(b_queue.alloc_pooled(cx, h_queue.size() * 4)); HIPCHK(hipMemcpyAsync(b_queue.p, h_queue.data(), h_queue.size() * 4, hipMemcpyHostToDevice, s));      // (the slot queues too: no pageable copy may sit behind phase A)
-    std::vector<EngLayerTab> tab(c.dec_layers);      // the engine's layer table, one for every group: the layers' slabs (cache slices are picked per slot)
-    for (int l = 0; l < c.dec_layers; l++) tab[l] = EngLayerTab{m->dec[l].attn_norm, m->dec[l].ffn_norm, m->dec[l].ada_mul, b_k.as<float>() + (size_t)l * layer_stride, b_v.as<float>() + (size_t)l * layer_stride};
-    if (use_eng) HIPCHK(hipMemcpyAsync(m->engb_tab[0], tab.data(), sizeof(EngLayerTab) * c.dec_layers, hipMemcpyHostToDevice, s));
-    HIPCHK(hipStreamSynchronize(s));      // the host vectors go out of scope
-    // ---- (A) front-end, stacked encoder and stacked 38-token prefill, chunk by chunk
-    double pre_ms = 0.0, enc_ms = 0.0, pf_ms = 0.0; const double t0 = now_ms();
     // front-end of chunk cj (samples up, peak, log-mel) into half cj & 1 of the buffers, on stream sf; returns the chunk's mel pointers
-    auto front_end = [&](int cj, hipStream_t sf, std::vector<const float*>& d_mels) -> int32_t {
-        const int c0 = chunk0[cj], nc = chunk0[cj + 1] - c0, half = fe_overlap ? (cj & 1) : 0;
+    int32_t front_end(int cj, hipStream_t sf, std::vector<const float*>& d_mels) {
+        const int c0 = lay.chunk0[cj], nc = lay.chunk0[cj + 1] - c0, half = fe_overlap ? (cj & 1) : 0;
         d_mels.assign(nc, nullptr);
         return front_end_units(mt, c0, nc, samples, n_samples, T.data(), unit_scale, mem_kind == VOX_MEM_HOST ? b_smp.as<float>() + (size_t)half * smp_half : nullptr,
                                b_mel.as<float>() + (size_t)half * mel_half, b_scale.as<float>() + (size_t)half * ncm, d_mels.data(), sf);
-    };
-    std::vector<const float*> mels_cur, mels_next;
-    for (int ci = 0; ci < n_chunks; ci++) {
-        const int c0 = chunk0[ci], nc = chunk0[ci + 1] - c0;
+    }
+    // the front-end overlap's event ping-pong, behind chunk ci's encoder on s: chunk ci + 1's front-end goes onto the second stream
+    int32_t front_end_ahead(int ci, std::vector<const float*>& mels_next) {
+        HIPCHK(hipEventRecord(cx->ev_enc[ci & 1], s));      // this chunk's encoder has read half ci & 1 of the front-end buffers
+        if (ci + 1 < lay.n_chunks) {      // the next chunk's front-end: its half was last read by chunk ci - 1's encoder
+            if (ci >= 1) HIPCHK(hipStreamWaitEvent(cx->fe_stream, cx->ev_enc[(ci + 1) & 1], 0));
+            VOXCHK(front_end(ci + 1, cx->fe_stream, mels_next)); HIPCHK(hipEventRecord(cx->ev_fe[(ci + 1) & 1], cx->fe_stream));
+        }
+        return VOX_OK;
+    }
+    // ---- (A) one chunk: front-end, stacked encoder, stacked 38-token prefill, first token and first decode input h0 = audio[38] + embed(token) of its utterances
+    int32_t stage_chunk(int ci, std::vector<const float*>& mels_cur, std::vector<const float*>& mels_next) {
+        const int D = m->cfg.dec_dim, V = m->cfg.vocab;
+        const int c0 = lay.chunk0[ci], nc = lay.chunk0[ci + 1] - c0;
+        float* d_audio = b_audio.as<float>(); int* d_tok = b_tok.as<int>();
         const double ta = now_ms();
         if (!fe_overlap || ci == 0) { VOXCHK(front_end(ci, s, mels_cur)); HIPCHK(hipStreamSynchronize(s)); }
-        else { mels_cur.swap(mels_next); HIPCHK(hipStreamWaitEvent(s, cx->ev_fe[ci & 1], 0)); }      // (issued under the previous chunk's encoder, below)
-        std::vector<const float*>& d_mels = mels_cur;
+        else { mels_cur.swap(mels_next); HIPCHK(hipStreamWaitEvent(s, cx->ev_fe[ci & 1], 0)); }      // (issued under the previous chunk's encoder: front_end_ahead)
         const double tb = now_ms();
         std::vector<int> S4(nc); std::vector<long> aoff_rel(nc);
-        VOXCHK(encode_batch_dev(m, nc, d_mels.data(), T.data() + c0, d_audio + aoff_c[ci], 0, S4.data(), aoff_rel.data()));
-        for (int i = 0; i < nc; i++) ARGCHK(S4[i] == S[c0 + i] && (long)aoff_c[ci] + aoff_rel[i] == audio_off[c0 + i], "internal: sequence length / audio offset mismatch (%d vs %d)", S4[i], S[c0 + i]);
-        if (fe_overlap) {
-            HIPCHK(hipEventRecord(cx->ev_enc[ci & 1], s));      // this chunk's encoder has read half ci & 1 of the front-end buffers
-            if (ci + 1 < n_chunks) {      // the next chunk's front-end: its half was last read by chunk ci - 1's encoder
-                if (ci >= 1) HIPCHK(hipStreamWaitEvent(cx->fe_stream, cx->ev_enc[(ci + 1) & 1], 0));
-                VOXCHK(front_end(ci + 1, cx->fe_stream, mels_next)); HIPCHK(hipEventRecord(cx->ev_fe[(ci + 1) & 1], cx->fe_stream));
-            }
-        }
+        VOXCHK(encode_batch_dev(m, nc, mels_cur.data(), T.data() + c0, d_audio + lay.aoff_c[ci], 0, S4.data(), aoff_rel.data()));
+        for (int i = 0; i < nc; i++)
+            ARGCHK(S4[i] == S[c0 + i] && (long)lay.aoff_c[ci] + aoff_rel[i] == lay.audio_off[c0 + i], "internal: sequence length / audio offset mismatch (%d vs %d)", S4[i], S[c0 + i]);
+        if (fe_overlap) VOXCHK(front_end_ahead(ci, mels_next));
         HIPCHK(hipStreamSynchronize(s)); const double tc = now_ms();
-        float* px = b_px.as<float>();
-        for (int i = c0; i < c0 + nc; i++)
-            HIPCHK(launch_embed(m->tok.w, d_tok + (size_t)i * tstride, PREFIX_LEN, d_audio + audio_off[i], D, nullptr, 0, 0, px + (size_t)(i - c0) * PREFIX_LEN * D, s));
-        vox_cache view; view.m = m; view.ctx = cx; view.k = b_k.as<float>() + (size_t)c0 * seq_stride; view.v = b_v.as<float>() + (size_t)c0 * seq_stride; view.max_seq = max_seq; view.len = 0; view.layer_stride = layer_stride;
-        VOXCHK(decoder_prefill_dev(m, px, nc * PREFIX_LEN, &view, 0, nc, (long)seq_stride));
-        // logits of every utterance's last prefix row -> its first generated token and its first decode input h0 = audio[38] + embed(token)
-        HIPCHK(launch_rms_norm(px + (size_t)(PREFIX_LEN - 1) * D, PREFIX_LEN * D, nc, D, m->dec_norm, nullptr, c.norm_eps, b_xn.as<float>(), D, s));
-        { GemmParams g{}; g.w = m->tok.w; g.x = b_xn.as<float>(); g.x_stride = D; g.M = nc; g.out = b_lg0.as<float>(); g.out_stride = V; HIPCHK(launch_q4_gemm(g, EPI_STORE, s)); }
+        VOXCHK(prefill_first_logits(m, nc, d_tok + (size_t)c0 * tstride, tstride, d_audio, lay.audio_off.data() + c0, b_px.as<float>(), b_k.as<float>() + (size_t)c0 * seq_stride,
+                                    b_v.as<float>() + (size_t)c0 * seq_stride, max_seq, layer_stride, seq_stride, b_xn.as<float>(), b_lg0.as<float>(), s));
         VOXCHK(tap.rows(b_lg0.as<float>(), nc, nullptr, c0, b_posc.as<int>() + c0, b_len.as<int>() + c0, s));
         HIPCHK(launch_argmax_embed_batch(b_lg0.as<float>(), nc, V, d_tok + (size_t)c0 * tstride, tstride, b_posc.as<int>() + c0, b_len.as<int>() + c0, m->tok.w, d_audio, 0, D,
                                          b_h0.as<float>() + (size_t)c0 * D, s, nullptr, nullptr, nullptr, 0, 0, b_aoff.as<long>() + c0));
         // (the last chunk's prefill is not waited for here when a decode follows: the decode's buffers are set up and its graphs captured -- host work, ~6-10 ms per
         // distinct set of active groups -- while the GPU is still busy with it; the prefill timer closes behind that)
-        const bool defer = ci == n_chunks - 1 && steps > 0;
+        const bool defer = ci == lay.n_chunks - 1 && sch.steps > 0;
         if (!defer) HIPCHK(hipStreamSynchronize(s));
         const double td = now_ms();
         pre_ms += tb - ta; enc_ms += tc - tb; pf_ms += td - tc;
+        return VOX_OK;
     }
-    double t1 = now_ms();
-    // ---- (B) + (C): the slot decode
-    int replays = 0, n_captures = 0; double capture_ms = 0.0;
-    int form_steps[5] = {0, 0, 0, 0, 0};      // VOX_BATCH_VERBOSE: decode steps on the launch chains, the one- / two-group engine, one wide chain, two or more wide chains
-    if (steps > 0) {
-        const int parts_D = q4_skinny_resid_xf_parts(D);
+    // the decode's buffers: slot state, the step's rows and planes, the zeroed scratch cache slice, the wide step's planes scratch
+    int32_t decode_alloc() {
+        const vox_model_cfg& c = m->cfg;
+        const int D = c.dec_dim, QD = c.dec_heads * c.dec_head_dim, W = QD + 2 * c.dec_kv_heads * c.dec_head_dim, V = c.vocab, G = sch.G, Sl = sch.Sl;
         HIPCHK(b_sclip.alloc_pooled(cx, (size_t)Sl * 4)); HIPCHK(b_sqpos.alloc_pooled(cx, (size_t)Sl * 4));
         HIPCHK(b_pos.alloc_pooled(cx, (size_t)Sl * 4)); HIPCHK(b_kvrow.alloc_pooled(cx, (size_t)Sl * 4)); HIPCHK(b_h.alloc_pooled(cx, (size_t)Sl * D * 4));
         HIPCHK(b_qkv.alloc_pooled(cx, (size_t)Sl * W * 4)); HIPCHK(b_att.alloc_pooled(cx, (size_t)Sl * QD * 4)); HIPCHK(b_logits.alloc_pooled(cx, (size_t)Sl * V * 4));
-        HIPCHK(b_xf1.alloc_pooled(cx, xf_bytes(D) * G)); HIPCHK(b_xf2.alloc_pooled(cx, xf_bytes(QD) * G)); HIPCHK(b_xf3.alloc_pooled(cx, xf_bytes(F) * G));
-        HIPCHK(b_ssq.alloc_pooled(cx, (size_t)parts_D * 16 * 4 * G));
-        HIPCHK(hipMemsetAsync(b_xf1.p, 0, xf_bytes(D) * G, s)); HIPCHK(hipMemsetAsync(b_xf2.p, 0, xf_bytes(QD) * G, s)); HIPCHK(hipMemsetAsync(b_xf3.p, 0, xf_bytes(F) * G, s));
-        HIPCHK(hipMemsetAsync(b_ssq.p, 0, (size_t)parts_D * 16 * 4 * G, s)); HIPCHK(hipMemsetAsync(b_h.p, 0, (size_t)Sl * D * 4, s)); HIPCHK(hipMemsetAsync(b_qkv.p, 0, (size_t)Sl * W * 4, s));
+        VOXCHK(xfp.alloc(m, G, s, &xb));
+        HIPCHK(hipMemsetAsync(b_h.p, 0, (size_t)Sl * D * 4, s)); HIPCHK(hipMemsetAsync(b_qkv.p, 0, (size_t)Sl * W * 4, s));
         // the scratch cache slice (index n of every layer): zeros, so that an idle slot's attention stays finite
         for (int l = 0; l < c.dec_layers; l++) {      // (one memset per layer: the pitch of a 2-D memset would be the layer stride -- tens of GB for a corpus-sized session)
             HIPCHK(hipMemsetAsync(b_k.as<float>() + (size_t)l * layer_stride + (size_t)n * seq_stride, 0, seq_stride * 4, s));
             HIPCHK(hipMemsetAsync(b_v.as<float>() + (size_t)l * layer_stride + (size_t)n * seq_stride, 0, seq_stride * 4, s));
         }
-        int* d_pos = b_pos.as<int>(); int* d_kvrow = b_kvrow.as<int>();
-        if (use_eng) HIPCHK(b_ssq_e.alloc_pooled(cx, (size_t)(256 + 16) * 16 * 4 * G));      // per group: the launch's 256 partial sums of squares + their fold
-        SlotStepParams sp{};
-        sp.logits = b_logits.as<float>(); sp.vocab = V; sp.tokens = d_tok; sp.tok_stride = tstride; sp.clip_len = b_len.as<int>();
-        sp.slot_clip = b_sclip.as<int>(); sp.slot_qpos = b_sqpos.as<int>(); sp.queue = b_queue.as<int>(); sp.q_stride = q_stride;
-        sp.pos = d_pos; sp.kv_row = d_kvrow; sp.n_clips = n; sp.first_pos = PREFIX_LEN; sp.tok = m->tok.w; sp.audio = d_audio; sp.audio_off = b_aoff.as<long>(); sp.D = D;
-        sp.h0 = b_h0.as<float>(); sp.h = b_h.as<float>(); sp.xf = b_xf1.as<uint16_t>(); sp.xf_w = m->dec[0].attn_norm; sp.ssq_out = b_ssq.as<float>();
-        sp.xf_group_stride = (long)(xf_bytes(D) / 2); sp.ssq_group_stride = parts_D * 16;
-        const XfBufs xb{b_h.as<float>(), b_qkv.as<float>(), b_att.as<float>(), b_logits.as<float>(), b_ssq.as<float>(), b_xf1.as<uint16_t>(), b_xf2.as<uint16_t>(), b_xf3.as<uint16_t>(),
-                        (long)(xf_bytes(D) / 2), (long)(xf_bytes(QD) / 2), (long)(xf_bytes(F) / 2), (long)parts_D * 16};
-        // WIDE step (round 6): the layer operators of 2..4 active slot groups as ONE GEMM each (launch_q4_wide: one weight fetch and one nibble -> bf16 conversion per K
-        // step for all groups, the groups' XF planes staged through LDS once per workgroup, K split over workgroups + a finishing launch with the step's epilogue), the
-        // attention of all groups in one launch, the lm_head as one GEMM.  Active groups are always a prefix 0 .. n_act - 1 (the slots are ordered by load).
-        // Measured (tools/wide_probe.py, 24 s clips, every slot busy; profiles/r06_wide_step.txt): 64 slots 3.26 ms per step against 3.55 on four launch chains, then forked, 48 slots
-        // 3.11 against 3.04 -- the wide step serves the steps with >= wide_min active groups, 4 by default (VOX_BATCH_WIDE_MIN=2 / 3: measurement knob and tests).
-        int wide_min = 4; if (const char* e = knob_str("VOX_BATCH_WIDE_MIN")) wide_min = std::max(2, std::min(5, atoi(e)));
-        const bool wide_ok = !knob_str("VOX_BATCH_NO_WIDE") && G >= wide_min && wide_geom_ok(m);
-        // A four-group step as TWO two-group wide chains instead of one four-group chain, run back to back on `s` like every chain of a step.  Measured with the two chains
-        // forked on two streams (round 6): a third of a wide step is dependency gaps between its ~236 launches (profiles/r06_corpus_sessions.txt), and the two chains filled
-        // each other's -- every weight is streamed twice, which a step at 0.7 TB/s can afford: 64-slot step 3.49 -> 3.29 ms (prefill included), corpus 4.54 -> 4.37 s, same
-        // ids (profiles/r06_wide_split.txt).  NOT on a shared GPU (vox_ctx_set_shared / sessions): there the other session already filled the gaps and four concurrent chains
-        // only contended (two sessions: 3.80 s without, 4.46 s with).  VOX_BATCH_NO_WIDE_SPLIT=1: one chain.
-        const bool wide_split = wide_ok && G >= 4 && wide_min <= 4 && !cx->shared && !knob_str("VOX_BATCH_NO_WIDE_SPLIT");
-        if (G > 4 && !wide_split) return fail(VOX_ERR_INVALID, "internal: %d slot groups planned without the two-chain wide step", G);
-        const size_t planes_bytes = wide_ok ? wide_planes_bytes(m, std::min(G, 4)) : 0;      // per chain
-        DevBuf b_planes;
-        int wide_chains = 2; if (const char* e = knob_str("VOX_BATCH_WIDE_CHAINS")) wide_chains = std::max(2, std::min(4, atoi(e)));      // measurement knob: more than two chains per step
-        if (wide_ok) HIPCHK(b_planes.alloc_pooled(cx, planes_bytes * (wide_split ? wide_chains : 1)));
-        auto wide_chain = [&](int mtw, hipStream_t sg, int g0, int chain) -> int32_t {      // groups g0 .. g0 + mtw - 1; `chain`: which slice of the planes scratch
-            uint16_t* xf1 = b_xf1.as<uint16_t>() + (size_t)g0 * (xf_bytes(D) / 2); uint16_t* xf2 = b_xf2.as<uint16_t>() + (size_t)g0 * (xf_bytes(QD) / 2); uint16_t* xf3 = b_xf3.as<uint16_t>() + (size_t)g0 * (xf_bytes(F) / 2);
-            float* ssq = b_ssq.as<float>() + (size_t)g0 * parts_D * 16;
-            float* hg = b_h.as<float>() + (size_t)g0 * 16 * D; float* qg = b_qkv.as<float>() + (size_t)g0 * 16 * W;
-            const int* d_pos_g = d_pos + 16 * g0; const int* d_kvrow_g = d_kvrow + 16 * g0;
-            auto base = [&](const Q4W& w, const uint16_t* xin, int K) {
-                GemmParams g{}; g.w = w; g.xf = (const uint4*)xin; g.xf_gstride = (long)(xf_bytes(K) / 16); g.M = 16 * mtw; g.wide_mt = mtw;
-                g.kz_scratch = reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(b_planes.p) + (size_t)chain * planes_bytes); g.kz_scratch_bytes = planes_bytes; g.norm_eps = c.norm_eps; return g;
-            };
-            for (int l = 0; l < c.dec_layers; l++) {
-                const DecLayer& L = m->dec[l];
-                float* kl = b_k.as<float>() + (size_t)l * layer_stride; float* vl = b_v.as<float>() + (size_t)l * layer_stride;
-                { GemmParams g = base(L.wqkv.w, xf1, D); g.out = qg; g.out_stride = W; g.ssq_part = ssq; g.ssq_part_gstride = (long)parts_D * 16; g.n_part = l == 0 ? 1 : parts_D;
-                  g.pos = d_pos_g; g.rope_cos = m->dec_cos; g.rope_sin = m->dec_sin; g.hd = hd; g.n_q = QD; g.n_kv = KV; g.kc = kl; g.vc = vl; g.kv_seq_stride = (long)seq_stride; g.kv_head_stride = max_seq * hd; g.kv_row = d_kvrow_g;
-                  HIPCHK(launch_q4_wide(g, EPI_ROPE_KV, sg)); }
-                AttnParams ap{}; ap.q = qg; ap.k = kl; ap.v = vl; ap.kv_row_stride = hd; ap.kv_head_stride = max_seq * hd; ap.out = b_att.as<float>() + (size_t)g0 * 16 * QD; ap.n_heads = H; ap.n_kv_heads = KV;
-                ap.offset = 0; ap.window = c.dec_window; ap.pos_ptr = d_pos_g; ap.M = 1; ap.pos_per_seq = 1; ap.q_seq_stride = W; ap.out_seq_stride = QD; ap.kv_seq_stride = (long)seq_stride; ap.kv_row = d_kvrow_g;
-                ap.out_xf = xf2; ap.out_xf_gstride = (long)(xf_bytes(QD) / 2); ap.prefer_gqa = 1; ap.no_xcd_remap = knob_str("VOX_ATTN_NO_XCD") != nullptr; ap.spec_rows = 0;
-                HIPCHK(launch_attn_decode(ap, hd, max_seq, sg, 16 * mtw));
-                { GemmParams g = base(L.wo.w, xf2, QD); g.out = hg; g.out_stride = D; g.resid = hg; g.resid_stride = D;
-                  g.xf_out = xf1; g.xf_out_gstride = (long)(xf_bytes(D) / 2); g.xf_w = L.ffn_norm; g.xf_w2 = L.ada_mul; g.ssq_out = ssq; g.ssq_out_gstride = (long)parts_D * 16;
-                  HIPCHK(launch_q4_wide(g, EPI_RESID_XF, sg)); }
-                { GemmParams g = base(L.w13.w, xf1, D); g.out = (float*)xf3; g.out_stride = F; g.xf_out_gstride = (long)(xf_bytes(F) / 2);
-                  g.ssq_part = ssq; g.ssq_part_gstride = (long)parts_D * 16; g.n_part = parts_D; HIPCHK(launch_q4_wide(g, EPI_SWIGLU_XF, sg)); }
-                { GemmParams g = base(L.w2.w, xf3, F); g.out = hg; g.out_stride = D; g.resid = hg; g.resid_stride = D;
-                  g.xf_out = xf1; g.xf_out_gstride = (long)(xf_bytes(D) / 2); g.xf_w = l + 1 < c.dec_layers ? m->dec[l + 1].attn_norm : m->dec_norm; g.xf_w2 = nullptr; g.ssq_out = ssq; g.ssq_out_gstride = (long)parts_D * 16;
-                  HIPCHK(launch_q4_wide(g, EPI_RESID_XF, sg)); }
-            }
-            { GemmParams g = base(m->tok.w, xf1, D); g.out = b_logits.as<float>() + (size_t)g0 * 16 * V; g.out_stride = V; g.ssq_part = ssq; g.ssq_part_gstride = (long)parts_D * 16; g.n_part = parts_D;
-              HIPCHK(launch_q4_wide(g, EPI_STORE, sg)); }
-            return VOX_OK;
-        };
-        auto engine_params = [&](int gi, int blk, bool two = false) {
-            const int r0 = gi * 16;
-            EngBParams ep{}; ep.stream = m->eng_stream; ep.stream_wo = m->eng_wob; ep.layers = m->engb_tab[0]; ep.n_layers = c.dec_layers; ep.kv_seq_stride = (long)seq_stride;
-            ep.h_in = b_h.as<float>() + (size_t)r0 * D; ep.h_stride = D; ep.n_rows = 16; ep.final_norm = m->dec_norm; ep.pos = d_pos + r0; ep.kv_row = d_kvrow + r0;
-            ep.rope_cos = m->dec_cos; ep.rope_sin = m->dec_sin; ep.max_seq = max_seq; ep.window = c.dec_window; ep.eps = c.norm_eps;
-            engb_state_carve(m->engb_state[blk], &ep);      // (an edge-buffer block belongs to a launch, not to a group: tags carry the block's launch serial)
-            ep.xf_out = b_xf1.as<uint16_t>() + (size_t)gi * (xf_bytes(D) / 2); ep.ssq_out = b_ssq_e.as<float>() + (size_t)gi * (256 + 16) * 16; ep.tl = nullptr; ep.tl_layer = -1; ep.flags = two ? m->engb_flags2 : m->engb_flags;
-            return ep;
-        };
-        // What a step of `active` runs: the engine (groups ga, gb), nc wide chains of szc[j] groups from group 0, or (nc == 0) one launch chain per active group.  `bits`:
-        // the kernels it launches, for warm_forms (the dynamic-LDS limits are raised at a kernel's first launch on a device -- see the warm-up below).
-        enum : uint32_t { kChains = 1u, kEng1 = 2u, kEng2 = 4u, kWide2 = 8u };      // (kWide2 << (mt - 2): wide chains of mt = 2, 3, 4 groups)
-        struct StepForm { int n_act = 0, ga = -1, gb = -1, nc = 0, szc[4] = {0, 0, 0, 0}; uint32_t bits = 0; };
-        auto form_of = [&](uint32_t active) {
-            StepForm f;
-            for (int gi = 0; gi < G; gi++) if ((active >> gi) & 1u) { f.n_act++; if (f.ga < 0) f.ga = gi; else f.gb = gi; }
-            if (use_eng && f.n_act <= 2) { f.bits = f.gb < 0 ? kEng1 : kEng2; return f; }
-            if (wide_ok && f.n_act >= wide_min && active == (1u << f.n_act) - 1) {      // (active groups are a prefix: the slots are ordered by load)
-                f.nc = wide_split && f.n_act >= 4 ? std::max(2, std::min(wide_chains, f.n_act / 2)) : 1;      // chains of >= 2 groups, sizes balanced, the larger ones first
-                for (int j = 0; j < f.nc; j++) { f.szc[j] = f.n_act / f.nc + (j < f.n_act % f.nc ? 1 : 0); f.bits |= kWide2 << (f.szc[j] - 2); }
-                return f;
-            }
-            f.bits = kChains; return f;
-        };
-        auto eng_launches = [&](uint32_t active) { return (form_of(active).bits & (kEng1 | kEng2)) ? 1u : 0u; };      // per step of `active`
-        auto step = [&](uint32_t active) -> int32_t {      // every chain back to back on `s`, then the argmax / next-input launch of all slots
-            const StepForm f = form_of(active);
-            if (f.bits & (kEng1 | kEng2)) {
-                if (f.gb < 0) HIPCHK(launch_decode_engine_b16(engine_params(f.ga, 0), s));
-                else HIPCHK(launch_decode_engine_b16x2(engine_params(f.ga, 0, true), engine_params(f.gb, 1, true), s));
-                VOXCHK(engb_group_tail(m, xb, b_ssq_e.as<float>(), f.ga, 16, s));
-                if (f.gb >= 0) VOXCHK(engb_group_tail(m, xb, b_ssq_e.as<float>(), f.gb, 16, s));
-            } else if (f.nc > 0) {
-                for (int j = 0, g0 = 0; j < f.nc; g0 += f.szc[j], j++) VOXCHK(wide_chain(f.szc[j], s, g0, j));
-            } else {
-                for (int gi = 0; gi < G; gi++)
-                    if ((active >> gi) & 1u) VOXCHK(xf_group_chain(m, xb, gi, 16, d_pos, d_kvrow, true, 0, b_k.as<float>(), b_v.as<float>(), layer_stride, seq_stride, max_seq, s));
-            }
-            VOXCHK(tap.rows(b_logits.as<float>(), Sl, b_sclip.as<int>(), 0, d_pos, nullptr, s));
-            HIPCHK(launch_argmax_embed_slots(sp, Sl, s));      // (retired groups' slots are idle: slot_clip < 0)
-            return VOX_OK;
-        };
-        // a group retires when its queues are empty -- but every distinct set of active groups is a graph capture + instantiation (~10 ms): a group that would retire
-        // fewer than kRetireSlack steps before the next longer one keeps running with idle slots instead (harmless: idle rows compute on zeros)
-        const int kRetireSlack = 12;
-        std::vector<int> run_g(plan.steps_g.begin(), plan.steps_g.end());
-        for (int gi = 1; gi < G; gi++) {      // walk from the longest group down: snap a group to the previous one's run length when it is close
-            if (run_g[gi - 1] - plan.steps_g[gi] < kRetireSlack) run_g[gi] = run_g[gi - 1];
+        if (pol.use_eng) HIPCHK(b_ssq_e.alloc_pooled(cx, (size_t)(256 + 16) * 16 * 4 * G));      // per group: the launch's 256 partial sums of squares + their fold
+        xb.h = b_h.as<float>(); xb.qkv = b_qkv.as<float>(); xb.att = b_att.as<float>(); xb.logits = b_logits.as<float>();
+        xb.k = b_k.as<float>(); xb.v = b_v.as<float>(); xb.layer_stride = layer_stride; xb.seq_stride = seq_stride; xb.max_seq = max_seq;
+        xb.pos = b_pos.as<int>(); xb.kv_row = b_kvrow.as<int>(); xb.no_xcd_remap = pol.no_xcd; xb.ssq_e = b_ssq_e.as<float>();
+        sp.logits = xb.logits; sp.vocab = V; sp.tokens = b_tok.as<int>(); sp.tok_stride = tstride; sp.clip_len = b_len.as<int>();
+        sp.slot_clip = b_sclip.as<int>(); sp.slot_qpos = b_sqpos.as<int>(); sp.queue = b_queue.as<int>(); sp.q_stride = sch.q_stride;
+        sp.pos = b_pos.as<int>(); sp.kv_row = b_kvrow.as<int>(); sp.n_clips = n; sp.first_pos = VOX_PREFIX_TOKENS; sp.tok = m->tok.w; sp.audio = b_audio.as<float>();
+        sp.audio_off = b_aoff.as<long>(); sp.D = D;
+        sp.h0 = b_h0.as<float>(); sp.h = xb.h; sp.xf = xb.xf1; sp.xf_w = m->dec[0].attn_norm; sp.ssq_out = xb.ssq;
+        sp.xf_group_stride = xb.xf1_gs; sp.ssq_group_stride = (int)xb.ssq_gs;
+        if (G > 4 && !pol.wide_split) return fail(VOX_ERR_INVALID, "internal: %d slot groups planned without the two-chain wide step", G);
+        xb.planes_bytes = pol.wide_ok ? wide_planes_bytes(m, std::min(G, 4)) : 0;      // per chain
+        if (pol.wide_ok) HIPCHK(b_planes.alloc_pooled(cx, xb.planes_bytes * (pol.wide_split ? pol.wide_chains : 1)));
+        xb.planes = b_planes.p;
+        return VOX_OK;
+    }
+    // ---- (C) the decode step over slots: every chain of the step's form back to back on `s`, then the argmax / next-input launch of all slots.  What the
+    // graphs are captured from and the eager steps run.
+    int32_t step(uint32_t active) {
+        const StepForm f = form_of(pol, active);
+        if (f.engine()) {
+            if (f.gb < 0) HIPCHK(launch_decode_engine_b16(engb_params(m, xb, f.ga, 16, 0, 0, false), s));
+            else HIPCHK(launch_decode_engine_b16x2(engb_params(m, xb, f.ga, 16, 0, 0, true), engb_params(m, xb, f.gb, 16, 0, 1, true), s));
+            VOXCHK(engb_group_tail(m, xb, f.ga, 16, s));
+            if (f.gb >= 0) VOXCHK(engb_group_tail(m, xb, f.gb, 16, s));
+        } else if (f.nc > 0) {
+            for (int j = 0, g0 = 0; j < f.nc; g0 += f.szc[j], j++) VOXCHK(xf_chain(m, xb, g0, 16, f.szc[j], j, true, 0, s));
+        } else {
+            for (int gi = 0; gi < sch.G; gi++)
+                if ((active >> gi) & 1u) VOXCHK(xf_chain(m, xb, gi, 16, 0, 0, true, 0, s));
         }
-        auto active_at = [&](int t) { uint32_t a = 0; for (int gi = 0; gi < G; gi++) if (t < run_g[gi]) a |= 1u << gi; return a; };
-        StepGraphs graphs(s);
-        const bool no_graph = knob_str("VOX_BATCH_NO_GRAPH") != nullptr;
-        // The step's kernels raise their dynamic-LDS limits at their first launch on a device (hipFuncSetAttribute: not something to do inside a capture).  The chains a
-        // step runs have different kernels (form_of's bits) and a plan may use several; the limits are per DEVICE, so the flags are the context's, not the process's (ADVICE
-        // r5: a second vox_ctx on another GPU, or the launch chains after an engine-timeout re-run, met their first launch inside a capture; ADVICE r6: keyed by the number
-        // of active groups, a shared call's four-group wide chain met its first launch inside a capture after an unshared call's two two-group chains).  A step that needs a
-        // chain this context has not run yet takes ONE eager step on all-idle slots first (slot_clip -1: the argmax / next-input launch returns at once; zero rows against
-        // the zeroed scratch slice; nothing of the session's state moves); every real step is then a graph replay.
+        VOXCHK(tap.rows(xb.logits, sch.Sl, b_sclip.as<int>(), 0, xb.pos, nullptr, s));
+        HIPCHK(launch_argmax_embed_slots(sp, sch.Sl, s));      // (retired groups' slots are idle: slot_clip < 0)
+        return VOX_OK;
+    }
+    uint32_t eng_launches(uint32_t active) const { return form_of(pol, active).engine() ? 1u : 0u; }      // per step of `active`
+    // The step's kernels raise their dynamic-LDS limits at their first launch on a device (hipFuncSetAttribute: not something to do inside a capture).  The chains a
+    // step runs have different kernels (form_of's bits) and a plan may use several; the limits are per DEVICE, so the flags are the context's, not the process's (ADVICE
+    // r5: a second vox_ctx on another GPU, or the launch chains after an engine-timeout re-run, met their first launch inside a capture; ADVICE r6: keyed by the number
+    // of active groups, a shared call's four-group wide chain met its first launch inside a capture after an unshared call's two two-group chains).  A step that needs a
+    // chain this context has not run yet takes ONE eager step on all-idle slots first (slot_clip -1: the argmax / next-input launch returns at once; zero rows against
+    // the zeroed scratch slice; nothing of the session's state moves); every real step is then a graph replay.
+    int32_t warm_forms() {
+        const int Sl = sch.Sl;
         bool idle_set = false;
-        for (int t = 0; t < steps && !no_graph; t++) {
-            const uint32_t act = active_at(t), f = form_of(act).bits;
+        for (int t = 0; t < sch.steps && !pol.no_graph; t++) {
+            const uint32_t act = sch.active_at(t), f = form_of(pol, act).bits;
             if ((cx->warm_forms & f) == f) continue;
-            if (!idle_set) { HIPCHK(hipMemsetAsync(b_sclip.p, 0xFF, (size_t)Sl * 4, s)); HIPCHK(hipMemsetD32Async((hipDeviceptr_t)d_pos, PREFIX_LEN, Sl, s)); HIPCHK(hipMemsetD32Async((hipDeviceptr_t)d_kvrow, n, Sl, s)); idle_set = true; }
+            if (!idle_set) {
+                HIPCHK(hipMemsetAsync(b_sclip.p, 0xFF, (size_t)Sl * 4, s)); HIPCHK(hipMemsetD32Async((hipDeviceptr_t)b_pos.p, VOX_PREFIX_TOKENS, Sl, s));
+                HIPCHK(hipMemsetD32Async((hipDeviceptr_t)b_kvrow.p, n, Sl, s)); idle_set = true;
+            }
             VOXCHK(step(act)); m->engb_launches += eng_launches(act); cx->warm_forms |= f;
         }
-        sp.init = 1; HIPCHK(launch_argmax_embed_slots(sp, Sl, s)); sp.init = 0;      // every slot takes the first utterance of its queue
-        if (!no_graph) {      // one graph per distinct set of active groups, captured NOW: the stream still holds the last chunk's prefill, the GPU is busy while the host records
-            const double tg = now_ms();
-            for (int t = 0; t < steps; t++) {
-                const uint32_t act = active_at(t);
-                if (graphs.find(act)) continue;
-                hipGraphExec_t ge = nullptr;
-                VOXCHK(graphs.capture(act, step, &ge));
-                n_captures++;
-            }
-            capture_ms = now_ms() - tg;
+        return VOX_OK;
+    }
+    // one graph per distinct set of active groups, captured NOW: the stream still holds the last chunk's prefill, the GPU is busy while the host records
+    int32_t capture(StepGraphs& graphs) {
+        auto one_step = [this](uint32_t active) { return step(active); };      // the single callable handed to StepGraphs::capture
+        const double tg = now_ms();
+        for (int t = 0; t < sch.steps; t++) {
+            const uint32_t act = sch.active_at(t);
+            if (graphs.find(act)) continue;
+            hipGraphExec_t ge = nullptr;
+            VOXCHK(graphs.capture(act, one_step, &ge));
+            n_captures++;
         }
-        HIPCHK(hipStreamSynchronize(s));      // phase A (and the set-up behind it) is done: the prefill timer closes here, the decode timer starts
-        { const double tn = now_ms(); pf_ms += tn - t1; t1 = tn; }
-        // (an event where the set of active groups changes: the runs in between are what the planner's next session on this context is priced with)
-        int seg_n[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, seg_act[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, n_seg = 0; uint32_t last_act = 0;
-        for (int t = 0; t < steps; t++) {
-            const uint32_t act = active_at(t);
-            if (calib && !no_graph && act != last_act && n_seg < 9) {
-                if (!cx->ev_seg[n_seg]) HIPCHK(hipEventCreate(&cx->ev_seg[n_seg]));
-                HIPCHK(hipEventRecord(cx->ev_seg[n_seg], s));
-                seg_act[n_seg] = __builtin_popcount(act); n_seg++; last_act = act;
+        capture_ms = now_ms() - tg;
+        return VOX_OK;
+    }
+    // the decode loop: one graph replay (VOX_BATCH_NO_GRAPH: one eager step) per step of the schedule, a segment event wherever the set of active groups changes
+    int32_t replay(StepGraphs& graphs, StepSegments& seg) {
+        uint32_t last_act = 0;
+        for (int t = 0; t < sch.steps; t++) {
+            const uint32_t act = sch.active_at(t);
+            if (pol.calib && !pol.no_graph && act != last_act && seg.n_seg < 9) {
+                if (!cx->ev_seg[seg.n_seg]) HIPCHK(hipEventCreate(&cx->ev_seg[seg.n_seg]));
+                HIPCHK(hipEventRecord(cx->ev_seg[seg.n_seg], s));
+                seg.act[seg.n_seg] = __builtin_popcount(act); seg.n_seg++; last_act = act;
             }
-            if (n_seg > 0) seg_n[n_seg - 1]++;
-            { const StepForm f = form_of(act); form_steps[(f.bits & kEng1) ? 1 : (f.bits & kEng2) ? 2 : f.nc == 1 ? 3 : f.nc > 1 ? 4 : 0]++; }
+            if (seg.n_seg > 0) seg.n[seg.n_seg - 1]++;
+            form_steps[form_of(pol, act).report_slot()]++;
             m->engb_launches += eng_launches(act);
-            if (no_graph) { VOXCHK(step(act)); continue; }
+            if (pol.no_graph) { VOXCHK(step(act)); continue; }
             if (hipGraphLaunch(graphs.find(act), s) != hipSuccess) return fail(VOX_ERR_HIP, "hipGraphLaunch failed");
             replays++;
         }
-        if (n_seg > 0) { if (!cx->ev_seg[n_seg]) HIPCHK(hipEventCreate(&cx->ev_seg[n_seg])); HIPCHK(hipEventRecord(cx->ev_seg[n_seg], s)); }
-        VOXCHK(engb_timeout_check(m, use_eng ? 2 : 0, true, s));
-        for (int k = 0; k < n_seg && !cx->shared; k++) {      // runs of >= 8 steps only: shorter ones are mostly their first replay (a shared GPU: nothing is recorded)
+        if (seg.n_seg > 0) { if (!cx->ev_seg[seg.n_seg]) HIPCHK(hipEventCreate(&cx->ev_seg[seg.n_seg])); HIPCHK(hipEventRecord(cx->ev_seg[seg.n_seg], s)); }
+        return VOX_OK;
+    }
+    // the measured segment times into the context's step_ms_meas: runs of >= 8 steps only: shorter ones are mostly their first replay (a shared GPU: nothing is recorded)
+    void fold_segments(const StepSegments& seg) {
+        for (int k = 0; k < seg.n_seg && !cx->shared; k++) {
             float ms = 0.f;
-            if (seg_n[k] >= 8 && seg_act[k] >= 1 && seg_act[k] <= kMaxGroups && hipEventElapsedTime(&ms, cx->ev_seg[k], cx->ev_seg[k + 1]) == hipSuccess && ms > 0.f) {
-                double& mm = cx->step_ms_meas[use_eng ? 0 : 1][seg_act[k]]; const double v = (double)ms / seg_n[k];
+            if (seg.n[k] >= 8 && seg.act[k] >= 1 && seg.act[k] <= kMaxGroups && hipEventElapsedTime(&ms, cx->ev_seg[k], cx->ev_seg[k + 1]) == hipSuccess && ms > 0.f) {
+                double& mm = cx->step_ms_meas[pol.use_eng ? 0 : 1][seg.act[k]]; const double v = (double)ms / seg.n[k];
                 mm = mm > 0.0 ? 0.7 * mm + 0.3 * v : v;
             } else (void)hipGetLastError();
         }
     }
-    int total = 0;
-    VOXCHK(copy_out_ids(n, S, tstride, d_tok, out_ids, n_ids, &total, s));
-    m->timings.preprocess_ms = pre_ms; m->timings.encode_ms = enc_ms; m->timings.decode_ms = pf_ms + (now_ms() - t1); m->timings.total_ms = now_ms() - t0;
-    m->timings.decode_tokens = total; m->timings.graph_replays = replays;
-    if (knob_str("VOX_BATCH_VERBOSE")) fprintf(stderr, "[voxtral_hip] continuous batch: %d utterances, %d slots, %d steps (plan %.1f ms), front-end %.1f ms, encode %.1f ms (%d chunks), prefill %.1f ms (%d graph captures, %.1f ms of host time, under the last chunk's), decode %.1f ms; step costs used %.2f / %.2f / %.2f / %.2f / %.2f / %.2f / %.2f / %.2f ms\n", n, Sl, steps, plan.cost_ms, pre_ms, enc_ms, n_chunks, pf_ms, n_captures, capture_ms, now_ms() - t1, step_cost[1], step_cost[2], step_cost[3], step_cost[4], step_cost[5], step_cost[6], step_cost[7], step_cost[8]);
-    if (knob_str("VOX_BATCH_VERBOSE")) {
-        fprintf(stderr, "[voxtral_hip] continuous batch step forms: chains %d, engine1 %d, engine2 %d, wide %d, split %d\n", form_steps[0], form_steps[1], form_steps[2], form_steps[3], form_steps[4]);
+    // ---- (B) + (C): the slot decode.  Set-up, warm-up and capture run on the host while the stream still holds the last chunk's prefill.
+    int32_t decode() {
+        VOXCHK(decode_alloc());
+        StepGraphs graphs(s);
+        VOXCHK(warm_forms());
+        sp.init = 1; HIPCHK(launch_argmax_embed_slots(sp, sch.Sl, s)); sp.init = 0;      // every slot takes the first utterance of its queue
+        if (!pol.no_graph) VOXCHK(capture(graphs));
+        HIPCHK(hipStreamSynchronize(s));      // phase A (and the set-up behind it) is done: the prefill timer closes here, the decode timer starts
+        { const double tn = now_ms(); pf_ms += tn - t1; t1 = tn; }
+        StepSegments seg;
+        VOXCHK(replay(graphs, seg));
+        VOXCHK(engb_timeout_check(m, pol.use_eng ? 2 : 0, true, s));
+        fold_segments(seg);
+        return VOX_OK;
+    }
+    // VOX_BATCH_VERBOSE (tests/model_fixtures.py parses these lines)
+    void report() const {
+        const double* sc = step_cost; const int* fs = form_steps;
+        fprintf(stderr, "[voxtral_hip] continuous batch: %d utterances, %d slots, %d steps (plan %.1f ms), front-end %.1f ms, encode %.1f ms (%d chunks), prefill %.1f ms "
+                        "(%d graph captures, %.1f ms of host time, under the last chunk's), decode %.1f ms; step costs used %.2f / %.2f / %.2f / %.2f / %.2f / %.2f / %.2f / %.2f ms\n",
+                n, sch.Sl, sch.steps, sch.plan.cost_ms, pre_ms, enc_ms, lay.n_chunks, pf_ms, n_captures, capture_ms, now_ms() - t1,
+                sc[1], sc[2], sc[3], sc[4], sc[5], sc[6], sc[7], sc[8]);
+        fprintf(stderr, "[voxtral_hip] continuous batch step forms: chains %d, engine1 %d, engine2 %d, wide %d, split %d\n", fs[0], fs[1], fs[2], fs[3], fs[4]);
         std::string q = "[voxtral_hip] continuous batch slot plan (caller units per slot):";
-        for (size_t sl = 0; sl < plan.queue.size(); sl++) { q += sl ? " |" : " "; for (int u : plan.queue[sl]) q += " " + std::to_string(slot_of[u]); }
+        for (size_t sl = 0; sl < sch.plan.queue.size(); sl++) { q += sl ? " |" : " "; for (int u : sch.plan.queue[sl]) q += " " + std::to_string(slot_of[u]); }
         fprintf(stderr, "%s\n", q.c_str());
     }
+};
+// lengths -> plan -> buffers -> stage chunks -> decode -> copy out -> timings
+static int32_t transcribe_continuous_impl(vox_model* m, int32_t n, const float* const* samples, const size_t* n_samples, const float* t_embed,
+                                          int32_t* const* out_ids, const int32_t* caps, int32_t* n_ids, int32_t mem_kind, const int* slot_of, bool allow_engine,
+                                          const float* const* unit_scale = nullptr) {
+    VOXCHK(ctx_bind(m->ctx));
+    const vox_model_cfg& c = m->cfg; const int PREFIX_LEN = VOX_PREFIX_TOKENS;
+    ARGCHK(c.n_mels == 128, "the log-mel front-end produces 128 bins; model expects %d", c.n_mels);
+    VOXCHK(vox_model_set_t_embed(m, t_embed));
+    m->timings = vox_timings{};
+    ContSession z(m); z.n = n; z.samples = samples; z.n_samples = n_samples; z.unit_scale = unit_scale; z.mem_kind = mem_kind; z.slot_of = slot_of;
+    VOXCHK(ctx_mel_tables(z.cx, &z.mt));
+    int Smax = 0;
+    VOXCHK(batch_lengths(m, n, samples, n_samples, caps, slot_of, z.T, z.S, z.len, &Smax));
+    z.max_seq = std::max((Smax + 63) / 64 * 64, 64); z.tstride = std::max(Smax, PREFIX_LEN) + 2;
+    z.seq_stride = (size_t)c.dec_kv_heads * z.max_seq * c.dec_head_dim; z.layer_stride = (size_t)(n + 1) * z.seq_stride;
+    // the plan (host only: lengths are known)
+    std::vector<std::pair<int, int>> jobs;
+    for (int i = 0; i < n; i++) if (z.len[i] > PREFIX_LEN + 1) jobs.emplace_back(z.len[i] - PREFIX_LEN - 1, i);
+    z.pol = cont_policy(m, allow_engine, !jobs.empty());
+    z.lay = chunk_layout(m, z.T, n_samples, z.pol.chunk);
+    double base_tab[9]; for (int g2 = 0; g2 < 9; g2++) base_tab[g2] = (z.pol.use_eng ? kStepMsEng : kStepMs)[g2];
+    // four groups as two two-group wide chains (cont_policy_groups): 3.12 -> 2.92 ms net of the prefill (measured with the chains forked)
+    if (!z.pol.shared && !z.pol.no_wide_split) base_tab[4] = 2.95;
+    step_costs(base_tab, z.cx->step_ms_meas[z.pol.use_eng ? 0 : 1], z.pol.calib, z.pol.shared, z.step_cost);
+    z.sch = slot_schedule(jobs, z.pol.force_G, z.step_cost, z.pol.max_groups);
+    cont_policy_groups(z.pol, m, z.sch.G);
+    VOXCHK(z.tap.init(m, n, slot_of, z.s));
+    VOXCHK(z.alloc());
+    z.t0 = now_ms();
+    std::vector<const float*> mels_cur, mels_next;
+    for (int ci = 0; ci < z.lay.n_chunks; ci++) VOXCHK(z.stage_chunk(ci, mels_cur, mels_next));
+    z.t1 = now_ms();
+    if (z.sch.steps > 0) VOXCHK(z.decode());
+    int total = 0;
+    VOXCHK(copy_out_ids(n, z.S, z.tstride, z.b_tok.as<int>(), out_ids, n_ids, &total, z.s));
+    m->timings.preprocess_ms = z.pre_ms; m->timings.encode_ms = z.enc_ms; m->timings.decode_ms = z.pf_ms + (now_ms() - z.t1); m->timings.total_ms = now_ms() - z.t0;
+    m->timings.decode_tokens = total; m->timings.graph_replays = z.replays;
+    if (z.pol.verbose) z.report();
+    return VOX_OK;
+}
+extern "C" int32_t vox_debug_step_costs(const double* base, const double* meas, int32_t calib, int32_t shared, double* out) {
+    ARGCHK(base && meas && out, "null argument");
+    step_costs(base, meas, calib != 0, shared != 0, out);
+    return VOX_OK;
+}
+extern "C" int32_t vox_debug_plan_slots(const int32_t* steps, int32_t n, int32_t force_G, int32_t max_groups, const double* step_ms, int32_t* G, int32_t* job_slot,
+                                        int32_t* job_qpos, int32_t* steps_g, int32_t* run_g, double* cost_ms) {
+    ARGCHK(n >= 0 && (steps || n == 0) && step_ms && G && (job_slot || n == 0) && (job_qpos || n == 0) && steps_g && run_g && cost_ms, "null argument");
+    ARGCHK(force_G >= 0 && force_G <= kMaxGroups && max_groups >= 1 && max_groups <= kMaxGroups, "group count out of range");
+    std::vector<std::pair<int, int>> jobs;
+    for (int i = 0; i < n; i++) { ARGCHK(steps[i] >= 1, "job %d: %d steps", i, steps[i]); jobs.emplace_back(steps[i], i); }
+    const SlotSchedule z = slot_schedule(jobs, force_G, step_ms, max_groups);
+    *G = z.G; *cost_ms = z.plan.cost_ms;
+    for (int k = 0; k < kMaxGroups; k++) { steps_g[k] = k < (int)z.plan.steps_g.size() ? z.plan.steps_g[k] : 0; run_g[k] = z.run_g[k]; }
+    for (int sl = 0; sl < z.Sl; sl++)
+        for (int k = 0; k < z.q_stride; k++) { const int j = z.h_queue[(size_t)sl * z.q_stride + k]; if (j >= 0) { job_slot[j] = sl; job_qpos[j] = k; } }
     return VOX_OK;
 }
 
 // Entry point: rows are processed LONGEST FIRST (a stable sort of the caller's slots by sample count; sequence length is monotone in it), so that the
 // 16-row groups of the decode loop retire last to first (see `step` above) -- results are per row and land in the caller's slot i whatever the internal order.
-static int32_t transcribe_batch_launches(vox_model* m, int32_t n, const float* const* samples, const size_t* n_samples, const float* t_embed,
-                                         int32_t* const* out_ids, const int32_t* caps, int32_t* n_ids, int32_t mem_kind, const int* slot_of, const float* const* unit_scale) {
-    int32_t r = transcribe_batch_impl(m, n, samples, n_samples, t_embed, out_ids, caps, n_ids, mem_kind, slot_of, true, unit_scale);
-    if (r == VOX_RETRY_ON_LAUNCHES) r = transcribe_batch_impl(m, n, samples, n_samples, t_embed, out_ids, caps, n_ids, mem_kind, slot_of, false, unit_scale);
-    return r;
-}
 extern "C" int32_t vox_transcribe_batch(vox_model* m, int32_t n, const float* const* samples, const size_t* n_samples, const float* t_embed,
                                         int32_t* const* out_ids, const int32_t* caps, int32_t* n_ids, int32_t mem_kind) {
     return vox_transcribe_batch_ex(m, n, samples, n_samples, nullptr, t_embed, out_ids, caps, n_ids, mem_kind);
@@ -3228,10 +3348,10 @@ static int32_t transcribe_batch_one_session(vox_model* m, int32_t n, const float
     for (int pi = 0, a = 0; pi < n_parts && r == VOX_OK; pi++) {
         const int b = a + (n - a) / (n_parts - pi);      // equal contiguous parts of the sorted order
         const int np = b - a;
-        if (cont) {
-            r = transcribe_continuous_impl(m, np, p_s.data() + a, p_n.data() + a, t_embed, p_o.data() + a, p_c.data() + a, p_k.data() + a, mem_kind, order.data() + a, true, usc ? usc + a : nullptr);
-            if (r == VOX_RETRY_ON_LAUNCHES) r = transcribe_continuous_impl(m, np, p_s.data() + a, p_n.data() + a, t_embed, p_o.data() + a, p_c.data() + a, p_k.data() + a, mem_kind, order.data() + a, false, usc ? usc + a : nullptr);
-        } else r = transcribe_batch_launches(m, np, p_s.data() + a, p_n.data() + a, t_embed, p_o.data() + a, p_c.data() + a, p_k.data() + a, mem_kind, order.data() + a, usc ? usc + a : nullptr);
+        r = retry_on_launches([&](bool engine) {
+            return (cont ? transcribe_continuous_impl : transcribe_batch_impl)(m, np, p_s.data() + a, p_n.data() + a, t_embed, p_o.data() + a, p_c.data() + a, p_k.data() + a, mem_kind,
+                                                                               order.data() + a, engine, usc ? usc + a : nullptr);
+        });
         acc.preprocess_ms += m->timings.preprocess_ms; acc.encode_ms += m->timings.encode_ms; acc.decode_ms += m->timings.decode_ms; acc.total_ms += m->timings.total_ms;
         acc.decode_tokens += m->timings.decode_tokens; acc.graph_replays += m->timings.graph_replays;
         m->batch_sessions++; a = b;
