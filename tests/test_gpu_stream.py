@@ -235,13 +235,37 @@ def test_ring_wrap_is_exact(pkg, ctx, model):
 
 
 # ---- 5. isolation ---------------------------------------------------------------------------------------------------------------------------------------------------
+def _piecewise(m, t, cache, calls, nxt=None):
+    """`calls` generate_step_with_cache calls on a caller-owned cache: the 38-token prefix when nothing has been fed yet (nxt None), then one token per call, the argmax
+    fed back.  (ids, logits of every call, the token the next call takes)."""
+    ids, lgs = [], []
+    for _ in range(calls):
+        lg = m.generate_step_with_cache([1] + [32] * 37 if nxt is None else [nxt], t, cache)
+        nxt = int(lg[-1].argmax()); ids.append(nxt); lgs.append(lg)
+    return ids, lgs, nxt
+
+
+def _same_piecewise(got, solo, first):
+    assert got[0] == solo[0][first:first + len(got[0])]
+    for k, lg in enumerate(got[1]):
+        assert np.array_equal(lg, solo[1][first + k]), f"piecewise call {first + k}: logits differ from the undisturbed sequence"
+
+
 def test_streams_and_offline_calls_do_not_disturb_each_other(pkg, ctx, model):
+    """Two streams, offline calls, a batch and a piecewise caller alternate on one model: on the full-size model three clients of the decode engine, each with its own
+    layer table (the tiny model has no engine: the same plumbing on the per-operator launches)."""
     m, size = model
     S = pkg.synth; t = _t(pkg, m); t2 = _t(pkg, m, delay=3.0)
     xa = S.synth_audio(9.0, seed=501); xb = _loud(6.5, 502); xo = S.synth_audio(4.0, seed=503)
     batch = [S.synth_audio(2.0 + 0.25 * i, seed=600 + i) for i in range(20)]
     solo_a = _stream_ids(pkg, m, xa, t, size=3200); solo_b = _stream_ids(pkg, m, xb, t2, size=1777)
     off_solo = m.transcribe_audio(xo, t); off2_solo = m.transcribe_audio(xo, t2)
+    kc0 = m.create_decoder_cache_preallocated(256)
+    try:
+        pw_solo = _piecewise(m, t, kc0, 12)      # the prefix call + 11 one-token calls, nothing in between
+    finally:
+        kc0.close()
+    kc = half = None; pw_halves = 0
     os.environ["VOX_BATCH_NO_CALIB"] = "1"      # the plan a function of the lengths alone: batch ids comparable call to call (include/voxtral_hip.h)
     try:
         batch_solo = m.transcribe_batch(batch, t)
@@ -251,6 +275,11 @@ def test_streams_and_offline_calls_do_not_disturb_each_other(pkg, ctx, model):
             ga, gb = [], []
             for i in range(max(len(ca), len(cb))):
                 if i < len(ca): ga.append(a.push(xa[ca[i][0]:ca[i][1]]))
+                if i == 2:      # the same piecewise sequence on a fresh cache, in two halves between the pushes: bit for bit (the same kernels on the same inputs)
+                    kc = m.create_decoder_cache_preallocated(256)
+                    half = _piecewise(m, t, kc, 6); _same_piecewise(half, pw_solo, 0); pw_halves += 1
+                if i == 6:
+                    _same_piecewise(_piecewise(m, t, kc, 6, half[2]), pw_solo, 6); assert kc.seq_len() == 38 + 11; pw_halves += 1
                 if i == 3: assert np.array_equal(m.transcribe_audio(xo, t), off_solo)
                 if i < len(cb): gb.append(b.push(xb[cb[i][0]:cb[i][1]]))
                 if i == 5:
@@ -259,12 +288,14 @@ def test_streams_and_offline_calls_do_not_disturb_each_other(pkg, ctx, model):
                     assert not m.set_prefix_cache(False)
                     assert np.array_equal(m.transcribe_audio(xo, t2), off2_solo)
             ga.append(a.finish()); gb.append(b.finish())
+            assert pw_halves == 2      # (both halves of the piecewise sequence ran: the loop reached i == 2 and i == 6)
             assert np.array_equal(np.concatenate(ga), solo_a) and np.array_equal(np.concatenate(gb), solo_b)
             a.reset()
             assert np.array_equal(_run(pkg, a, xa, ca)[0], solo_a)      # (the prefix cache is off on the model: the stream builds what it starts from itself)
             assert not m.set_prefix_cache(None)
         finally:
             a.close(); b.close()
+            if kc is not None: kc.close()
     finally:
         os.environ.pop("VOX_BATCH_NO_CALIB", None)
 

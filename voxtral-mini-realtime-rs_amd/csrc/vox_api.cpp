@@ -765,6 +765,20 @@ static std::mutex g_cache_mu; static std::unordered_map<const vox_cache*, uint64
 static void cache_register(vox_cache* k) { std::lock_guard<std::mutex> l(g_cache_mu); k->gen = ++g_cache_gen; g_cache_live[k] = k->gen; }
 static void cache_unregister(const vox_cache* k) { std::lock_guard<std::mutex> l(g_cache_mu); g_cache_live.erase(k); }
 static bool cache_alive(const vox_cache* k, uint64_t gen) { std::lock_guard<std::mutex> l(g_cache_mu); auto it = g_cache_live.find(k); return it != g_cache_live.end() && it->second == gen; }
+// frees a cache nothing on the GPU reads any more: synchronising first, and dropping whatever remembers it, is the caller's
+static void cache_release(vox_cache*& k) { if (!k) return; cache_unregister(k); (void)hipFree(k->k); (void)hipFree(k->v); delete k; k = nullptr; }
+
+// What one client of the single-stream decode engine (the offline path, the piecewise decoder surface, a live stream) holds of it: the device layer table for ITS cache,
+// where the launch leaves its 256 argmax partials, and the pinned host word the engine's error word is copied to.  `host` is what `tab` holds, valid for exactly
+// (cache, gen): engine_bind rebuilds it for another cache or generation and leaves it alone otherwise, so clients that alternate on one model never disturb each other.
+struct EngBinding {
+    EngLayerTab* tab = nullptr; float* part_val = nullptr; int* part_idx = nullptr; unsigned* err_word = nullptr; const vox_cache* cache = nullptr; uint64_t gen = 0; std::vector<EngLayerTab> host;
+};
+static void binding_release(EngBinding& b) {
+    for (void* p : {(void*)b.tab, (void*)b.part_val, (void*)b.part_idx}) if (p) (void)hipFree(p);
+    if (b.err_word) (void)hipHostFree(b.err_word);
+    b = EngBinding{};
+}
 
 struct TensorMeta { std::vector<uint64_t> shape; int dtype = 0; uint64_t nbytes = 0; };
 // What vox_transcribe_audio computes identically for EVERY utterance, held once per model.  The library itself pads every utterance on the left
@@ -812,10 +826,9 @@ struct vox_model {
     float* d_h2 = nullptr; long long* d_wo_acc = nullptr;      // fused attention + wo decode launch: residual stream after wo; per-layer fixed-point accumulators [dec_layers][dec_dim]
     int n_parts = 0, argmax_R = 8;
     // persistent decode-step engine (vox_engine.hip): one launch per token for the real decoder geometry; eng_ok = eligible, eng_ready = stream packed + state allocated
-    bool eng_ok = false, eng_on = true, eng_ready = false; unsigned char* eng_stream = nullptr; unsigned char* eng_state = nullptr; EngLayerTab* eng_tab = nullptr;
-    const vox_cache* eng_tab_cache = nullptr; const float* eng_tab_k = nullptr; std::vector<EngLayerTab> eng_tab_host;      // (cache object, its K base) the device layer table was built for
+    bool eng_ok = false, eng_on = true, eng_ready = false; unsigned char* eng_stream = nullptr; unsigned char* eng_state = nullptr; unsigned long long eng_launches = 0;
+    EngBinding eng_offline, eng_pw;      // the engine against the model's own cache (partials: d_part_val / d_part_idx, not owned) and against a piecewise caller's cache
     int eng_flags = 128 | 512 | 1, eng_pace = 50;      // XCD-local edges; probe-less all-gather, swept 0.5 us after the CU's own rows went out; one LDS-DMA packet in flight while the CU polls memory
-    unsigned long long eng_launches = 0; unsigned eng_err_host[2] = {0, 0};
     int eng_strikes = 0; bool eng_suspended = false;      // hand-off timeouts so far (3: the engine is switched off for good); suspended: the current utterance is being re-run on the per-operator path
     // batched decode-layer engine (vox_engine_b16.hip): one launch per 16-row group and step on the same packet stream; per-group edge buffers + layer tables
     unsigned char* eng_wob = nullptr;      // the batched engine's wo stream (XCD-group K split, launch_eng_pack op 5): 7 MB per layer
@@ -829,16 +842,14 @@ struct vox_model {
     hipGraph_t graph[2] = {nullptr, nullptr}; hipGraphExec_t graph_exec[2] = {nullptr, nullptr}; int graph_unroll = 0, graph_mode = 0;
     const vox_cache* graph_cache = nullptr; const float* graph_audio = nullptr;
     // piecewise decoder surface (embed_tokens_from_ids / forward_hidden_with_cache / lm_head on caller-owned caches): model-owned workspaces, and the decode engine's
-    // layer table for the caller's cache.  pw_memo: row 0 of pw_hidden is the final norm's output of an engine launch that ALSO produced that row's logits (pw_logits)
-    // and argmax partials (pw_part_*), so lm_head on that very buffer has nothing left to compute.
+    // layer table for the caller's cache (eng_pw).  pw_memo: row 0 of pw_hidden is the final norm's output of an engine launch that ALSO produced that row's logits (pw_logits)
+    // and argmax partials (eng_pw.part_*): lm_head on that very buffer has nothing left to compute.  eng_pw.err_word is refreshed (async) behind every engine launch: no round trip.
     float *pw_x = nullptr, *pw_hidden = nullptr, *pw_logits = nullptr; size_t pw_x_cap = 0, pw_hidden_cap = 0, pw_logits_cap = 0;
-    float* pw_part_val = nullptr; int* pw_part_idx = nullptr; int* pw_ids = nullptr; int pw_ids_cap = 0; int* pw_zero = nullptr;
-    EngLayerTab* pw_tab = nullptr; const vox_cache* pw_tab_cache = nullptr; uint64_t pw_tab_gen = 0;      // the table is valid for exactly this (cache, generation)
+    int* pw_ids = nullptr; int pw_ids_cap = 0; int* pw_zero = nullptr;
     bool pw_memo = false, pw_eng_used = false;
     // rows appended to a caller's cache by engine steps (and by anything run behind them) whose error word has not been read behind a stream synchronisation yet: a
     // hand-off timeout found later takes exactly these rows back (cache length -= pw_pend_rows), so "repeat the step" appends at the failed position again
     vox_cache* pw_pend_cache = nullptr; uint64_t pw_pend_gen = 0; int pw_pend_rows = 0; bool pw_verdict_failed = false;
-    unsigned* pw_err_pin = nullptr;      // pinned host copy of the engine's error word, refreshed (async) behind every piecewise engine launch: checked without a device round trip
     vox_timings timings{};
     // vox_debug_batch_tap_*: units (caller indices) armed for the next batch call; `on` during that call; out / rows hold the call's rows until fetched
     struct { std::vector<int> units; int max_rows = 0; bool armed = false, on = false, ready = false; float* out = nullptr; int* rows = nullptr; } tap;
@@ -1240,16 +1251,15 @@ static void model_release(vox_model* m) {
     m->twins.clear();
     (void)hipSetDevice(m->ctx->device); (void)hipStreamSynchronize(m->ctx->stream);
     graphs_destroy(m);
-    if (m->cache) { cache_unregister(m->cache); (void)hipFree(m->cache->k); (void)hipFree(m->cache->v); delete m->cache; }
+    cache_release(m->cache);
     if (m->ctx->pw_model == m) m->ctx->pw_model = nullptr;
-    for (void* p : {(void*)m->arena, (void*)m->ada_mul, (void*)m->ws, (void*)m->d_audio, (void*)m->d_mel, (void*)m->d_samples, (void*)m->d_tokens, (void*)m->d_pos,
-                    (void*)m->d_h, (void*)m->d_h2, (void*)m->d_wo_acc, (void*)m->d_q, (void*)m->d_att, (void*)m->d_act, (void*)m->d_logits, (void*)m->d_part_val, (void*)m->d_part_idx, (void*)m->d_seq_len, (void*)m->d_seq_off, (void*)m->d_row_pos, (void*)m->d_prefix, (void*)m->enc_cos_s, (void*)m->enc_sin_s, (void*)m->eng_stream, (void*)m->eng_wob, (void*)m->eng_state, (void*)m->eng_tab, (void*)m->engb_state[0], (void*)m->engb_state[1], (void*)m->engb_state[2], (void*)m->engb_state[3],
-                    (void*)m->engb_tab[0], (void*)m->engb_tab[1], (void*)m->engb_tab[2], (void*)m->engb_tab[3], (void*)m->pw_x, (void*)m->pw_hidden, (void*)m->pw_logits, (void*)m->pw_part_val, (void*)m->pw_part_idx, (void*)m->pw_ids, (void*)m->pw_zero, (void*)m->pw_tab})
-        if (p) (void)hipFree(p);
+    for (void* p : std::initializer_list<void*>{m->arena, m->ada_mul, m->ws, m->d_audio, m->d_mel, m->d_samples, m->d_tokens, m->d_pos, m->d_h, m->d_h2, m->d_wo_acc, m->d_q, m->d_att, m->d_act,
+                    m->d_logits, m->d_part_val, m->d_part_idx, m->d_seq_len, m->d_seq_off, m->d_row_pos, m->d_prefix, m->enc_cos_s, m->enc_sin_s, m->eng_stream, m->eng_wob, m->eng_state,
+                    m->engb_state[0], m->engb_state[1], m->engb_state[2], m->engb_state[3], m->engb_tab[0], m->engb_tab[1], m->engb_tab[2], m->engb_tab[3], m->pw_x, m->pw_hidden, m->pw_logits,
+                    m->pw_ids, m->pw_zero, m->tap.out, m->tap.rows}) if (p) (void)hipFree(p);
     prefix_release(m);
-    if (m->pw_err_pin) (void)hipHostFree(m->pw_err_pin);
-    if (m->tap.out) (void)hipFree(m->tap.out);
-    if (m->tap.rows) (void)hipFree(m->tap.rows);
+    m->eng_offline.part_val = nullptr; m->eng_offline.part_idx = nullptr;      // the model's d_part_val / d_part_idx, freed above: that binding points at them and does not own them
+    binding_release(m->eng_offline); binding_release(m->eng_pw);
     delete m;
 }
 extern "C" int32_t vox_model_free(vox_model* m) { model_release(m); return VOX_OK; }
@@ -1279,6 +1289,7 @@ static int32_t model_build(vox_ctx* ctx, const TensorSource* src_in, bool q4, bo
     A((void**)&m->d_h2, (size_t)c.dec_dim * 4); A((void**)&m->d_wo_acc, (size_t)c.dec_layers * c.dec_dim * 8);
     A((void**)&m->d_logits, (size_t)c.vocab * 4); A((void**)&m->d_part_val, (size_t)m->n_parts * 4 * 4); A((void**)&m->d_part_idx, (size_t)m->n_parts * 4 * 4);
     if (e != hipSuccess) { model_release(m); return fail(VOX_ERR_HIP, "hipMalloc of decode buffers failed: %s", hipGetErrorString(e)); }
+    m->eng_offline.part_val = m->d_part_val; m->eng_offline.part_idx = m->d_part_idx;      // the captured decode graphs and argmax_embed bake these pointers in: the binding points at them
     if (hipMemset(m->d_wo_acc, 0, (size_t)c.dec_layers * c.dec_dim * 8) != hipSuccess) { model_release(m); return fail(VOX_ERR_HIP, "hipMemset failed"); }
     for (int i = 0; i < c.dec_layers; i++) m->dec[i].ada_mul = m->ada_mul + (size_t)i * c.dec_dim;
     // decode engine eligibility: the real Voxtral decoder geometry, every decoder linear Q4_0 without bias, a 256-CU device.  VOX_ENGINE=0 keeps the per-operator launches.
@@ -1346,7 +1357,7 @@ extern "C" int32_t vox_model_arena_finalize(vox_model* m) {
     ARGCHK(m, "null argument"); VOXCHK(ctx_bind(m->ctx));
     for (Q4W* w : m->tiled) HIPCHK(launch_q4_tile_build(*w, const_cast<uint4*>(w->qt), const_cast<uint16_t*>(w->st), m->ctx->stream));
     HIPCHK(hipStreamSynchronize(m->ctx->stream));
-    m->eng_ready = false; m->eng_tab_cache = nullptr;      // a stream packed from an earlier arena content is stale
+    m->eng_ready = false; m->eng_offline.cache = nullptr;      // a stream packed from an earlier arena content is stale
     prefix_release(m);                                     // ... and so is a prefix state computed from it
     if (m->eng_wob) { HIPCHK(hipStreamSynchronize(m->ctx->stream)); (void)hipFree(m->eng_wob); m->eng_wob = nullptr; }
     graphs_destroy(m);
@@ -1581,8 +1592,7 @@ extern "C" int32_t vox_decoder_cache_create(vox_model* m, int32_t max_seq, vox_c
 extern "C" int32_t vox_cache_free(vox_cache* k) {
     if (!k) return VOX_OK;
     (void)hipSetDevice(k->ctx->device); (void)hipStreamSynchronize(k->ctx->stream);   // never dereferences k->m: the model may be gone
-    cache_unregister(k);
-    (void)hipFree(k->k); (void)hipFree(k->v); delete k; return VOX_OK;
+    cache_release(k); return VOX_OK;
 }
 // KVCache::update on one layer of a pre-allocated cache (kv_cache.rs:116-136: slice_assign of k / v [1][heads][new_seq][hd] at rows pos .. pos + new_seq) -- for callers
 // that own their K / V (and for tests that need a cache at a position no prefill has reached).  The length shared by all layers (LayerCaches::seq_len,
@@ -1624,8 +1634,6 @@ extern "C" int32_t vox_cache_reset(vox_cache* k) {
     (void)cache_settle_pending(k);      // (a failed verdict only shortens a cache that is being emptied anyway: the strike is counted, the reset goes through)
     k->len = 0; k->abs_pos = 0; return VOX_OK;
 }
-
-static size_t cache_layer_floats(const vox_model* m, const vox_cache* k) { (void)m; return k->layer_stride; }
 
 // ---- streaming encoder: Q4AudioEncoder::create_cache / forward_with_cache (gguf/model.rs:437-459), Q4EncoderLayer::forward_with_cache
 // (:299-317), Q4Attention::forward_with_cache (:125-174), Q4VoxtralModel::encode_audio_with_cache (:791-799), eviction KVCache::apply_sliding_window
@@ -1750,7 +1758,7 @@ static int32_t decoder_prefill_dev(vox_model* m, float* x, int M, vox_cache* kc,
     const size_t need = (size_t)M * D + (size_t)M * W + (size_t)M * QD + (size_t)M * F + 1024;
     VOXCHK(ensure(&m->ws, &m->ws_floats, need));
     float* xn = m->ws; float* qkv = xn + (size_t)M * D; float* att = qkv + (size_t)M * W; float* ffn = att + (size_t)M * QD;
-    const size_t lf = cache_layer_floats(m, kc);
+    const size_t lf = kc->layer_stride;
     // 17..48 rows in one sequence (the 38-token prefill): both RMSNorms write their output straight as XF tiles (the MFMA A-fragments the
     // q4_skinny_mt_kernel consumes) into the context's XF scratch -- no f32 xn, no conversion launch for q|k|v and w1|w3
     auto xf_ok = [&](const Q4W& w) { return w.fmt == WFMT_Q4_0 && w.qt && w.st && w.nb % 4 == 0 && w.K == D && D % 128 == 0 && D <= 10240; };
@@ -1858,10 +1866,13 @@ static bool decode_layer_fuses_attn_wo(const vox_model* m, const DecLayer& L, co
            q4_gemv_default_R(L.w13.w.N, L.w13.w.K, EPI_SWIGLU) == 2;
 }
 
+// attn_wo accumulators: every step leaves them cleared (w2 does it); clearing them outright before a run of steps keeps a call that failed half-way through a layer from
+// leaking into the next one
+static int32_t wo_acc_clear(vox_model* m, hipStream_t s) { if (m->d_wo_acc) HIPCHK(hipMemsetAsync(m->d_wo_acc, 0, (size_t)m->cfg.dec_layers * m->cfg.dec_dim * 8, s)); return VOX_OK; }
 static int32_t decoder_step_dev(vox_model* m, float* h, vox_cache* kc, const int* pos_ptr, int pos_off) {
     const vox_model_cfg& c = m->cfg; hipStream_t s = m->ctx->stream;
     const int D = c.dec_dim, H = c.dec_heads, KV = c.dec_kv_heads, hd = c.dec_head_dim, QD = H * hd, KD = KV * hd, F = c.dec_ffn;
-    const size_t lf = cache_layer_floats(m, kc);
+    const size_t lf = kc->layer_stride;
     for (int l = 0; l < c.dec_layers; l++) {
         const DecLayer& L = m->dec[l]; float* kl = kc->k + (size_t)l * lf; float* vl = kc->v + (size_t)l * lf;
         GemvParams p{};
@@ -1908,11 +1919,10 @@ static int32_t engine_stream_prepare(vox_model* m) {
     if (!m->eng_stream) {
         hipError_t e = hipMalloc((void**)&m->eng_stream, sb);
         if (e == hipSuccess) e = hipMalloc((void**)&m->eng_state, eng_state_bytes());
-        if (e == hipSuccess) e = hipMalloc((void**)&m->eng_tab, sizeof(EngLayerTab) * 32);
         if (e != hipSuccess) {
             (void)hipGetLastError();
-            if (m->eng_stream) (void)hipFree(m->eng_stream); if (m->eng_state) (void)hipFree(m->eng_state); if (m->eng_tab) (void)hipFree(m->eng_tab);
-            m->eng_stream = nullptr; m->eng_state = nullptr; m->eng_tab = nullptr; m->eng_ok = false; m->eng_on = false; m->engb_ok = false;
+            if (m->eng_stream) (void)hipFree(m->eng_stream); if (m->eng_state) (void)hipFree(m->eng_state);
+            m->eng_stream = nullptr; m->eng_state = nullptr; m->eng_ok = false; m->eng_on = false; m->engb_ok = false;
             fprintf(stderr, "[voxtral_hip] decode engine: allocating the %.2f GB weight stream failed (%s); the launch-based decode paths are used\n", sb / 1e9, hipGetErrorString(e));
             return VOX_OK;
         }
@@ -1924,23 +1934,7 @@ static int32_t engine_stream_prepare(vox_model* m) {
         HIPCHK(launch_eng_pack(L.w13.w, 2, l, c.dec_layers, m->eng_stream, c.vocab, s)); HIPCHK(launch_eng_pack(L.w2.w, 3, l, c.dec_layers, m->eng_stream, c.vocab, s));
     }
     HIPCHK(launch_eng_pack(m->tok.w, 4, 0, c.dec_layers, m->eng_stream, c.vocab, s));
-    m->eng_ready = true; m->eng_tab_cache = nullptr;
-    return VOX_OK;
-}
-// decode engine: per-CU weight stream (a second copy of the decoder's Q4 bytes in consumption order, built on the GPU from the row planes), granule state, layer table
-static int32_t engine_prepare(vox_model* m) {
-    const vox_model_cfg& c = m->cfg; hipStream_t s = m->ctx->stream;
-    if (!m->eng_ok || !m->eng_on || m->eng_suspended || !m->cache || m->cache->max_seq > 1024) return VOX_OK;      // long caches keep the per-operator path (attention scores live in LDS)
-    VOXCHK(engine_stream_prepare(m));
-    if (!m->eng_ready) return VOX_OK;
-    if (m->eng_tab_cache != m->cache || m->eng_tab_k != m->cache->k) {      // (a re-allocated cache object can land on the old heap address: compare the device pointer too)
-        const size_t lf = cache_layer_floats(m, m->cache);
-        m->eng_tab_host.resize(c.dec_layers);
-        for (int l = 0; l < c.dec_layers; l++) m->eng_tab_host[l] = EngLayerTab{m->dec[l].attn_norm, m->dec[l].ffn_norm, m->dec[l].ada_mul, m->cache->k + (size_t)l * lf, m->cache->v + (size_t)l * lf};
-        HIPCHK(hipMemcpyAsync(m->eng_tab, m->eng_tab_host.data(), sizeof(EngLayerTab) * c.dec_layers, hipMemcpyHostToDevice, s));
-        HIPCHK(hipStreamSynchronize(s));
-        m->eng_tab_cache = m->cache; m->eng_tab_k = m->cache->k;
-    }
+    m->eng_ready = true;
     return VOX_OK;
 }
 // batched engine: the stream + one edge-buffer block and layer table per 16-row group
@@ -1964,7 +1958,6 @@ static bool engb_prepare(vox_model* m, int n_grp) {
     }
     return true;
 }
-static bool engine_active(const vox_model* m) { return m->eng_on && !m->eng_suspended && m->eng_ready && m->cache && m->eng_tab_cache == m->cache && m->eng_tab_k == m->cache->k && m->cache->max_seq <= 1024; }
 // a hand-off timeout inside the single-stream engine (its error word was read as non-zero): count the strike, re-arm the engine's state for the next launch, drop the
 // captured decode graphs; three strikes switch the engine off for the life of the model.  What each caller re-runs, and what it tells its user, is the caller's.
 static int32_t engine_strike(vox_model* m) {
@@ -1973,17 +1966,64 @@ static int32_t engine_strike(vox_model* m) {
     if (m->eng_strikes >= 3) { m->eng_ok = false; m->eng_on = false; }
     return VOX_OK;
 }
-static EngParams engine_params(vox_model* m, float* logits_out, bool argmax_in = false) {
+// ---- the single-stream engine's host side, shared by its clients (transcribe_dev, the piecewise decoder surface, vox_stream, vox_bench_decode_gemv).  Which path a step
+// took stays visible at every call site: the clients count steps by path, and each keeps its own recovery from a hand-off timeout.
+static const int ENGINE_MAX_ROWS = 1024;      // long caches keep the per-operator path (attention scores live in LDS)
+// the engines' view of the decoder layers over K / V planes [layer][..] that start at k / v: out[l] for every layer (group_off: a 16-row group's slice inside each layer)
+static void dec_layer_tab(const vox_model* m, float* k, float* v, size_t layer_stride, size_t group_off, EngLayerTab* out) {
+    for (size_t l = 0, o = group_off; l < (size_t)m->cfg.dec_layers; l++, o += layer_stride) out[l] = EngLayerTab{m->dec[l].attn_norm, m->dec[l].ffn_norm, m->dec[l].ada_mul, k + o, v + o};
+}
+// may the engine serve steps against this cache?  (suspended: a client is re-running steps on the per-operator path after a hand-off timeout)
+static bool engine_serves(const vox_model* m, const vox_cache* kc) { return m->eng_ok && m->eng_on && !m->eng_suspended && kc && kc->max_seq <= ENGINE_MAX_ROWS; }
+// the binding's table for `kc`, on its way to the device (the host copy lives in the binding: nothing to wait for)
+static hipError_t engine_tab_enqueue(vox_model* m, EngBinding& b, const vox_cache* kc) {
+    b.host.resize(m->cfg.dec_layers); dec_layer_tab(m, kc->k, kc->v, kc->layer_stride, 0, b.host.data());
+    const hipError_t e = hipMemcpyAsync(b.tab, b.host.data(), sizeof(EngLayerTab) * b.host.size(), hipMemcpyHostToDevice, m->ctx->stream);
+    b.cache = e == hipSuccess ? kc : nullptr; b.gen = kc->gen; return e;
+}
+// allocates whatever the binding still lacks (bytes: where a client that reports its footprint counts the device buffers)
+static hipError_t binding_alloc(const vox_model* m, EngBinding& b, uint64_t* bytes = nullptr) {
+    hipError_t e = hipSuccess; auto A = [&](void** q, size_t n) { if (e == hipSuccess && !*q && (e = hipMalloc(q, n)) == hipSuccess && bytes) *bytes += n; };
+    A((void**)&b.tab, sizeof(EngLayerTab) * std::max(m->cfg.dec_layers, 32)); A((void**)&b.part_val, 256 * 4); A((void**)&b.part_idx, 256 * 4);
+    if (e == hipSuccess && !b.err_word) { e = hipHostMalloc((void**)&b.err_word, 8, hipHostMallocDefault); if (e == hipSuccess) b.err_word[0] = b.err_word[1] = 0u; else b.err_word = nullptr; }
+    return e;
+}
+// May this client launch the engine against `kc` now?  Packs the weight stream at first use, allocates what the binding lacks, and rebuilds the layer table only for a
+// cache (or a generation of it: a freed cache's address may be handed out again) the binding does not hold -- a step on a bound cache copies and synchronises nothing.
+// A failure in here is not an error of the call: the per-operator launches serve it.
+static bool engine_bind(vox_model* m, EngBinding& b, const vox_cache* kc) {
+    if (!engine_serves(m, kc) || engine_stream_prepare(m) != VOX_OK || !m->eng_ready) return false;
+    hipError_t e = binding_alloc(m, b);
+    if (e == hipSuccess && (b.cache != kc || b.gen != kc->gen)) { e = engine_tab_enqueue(m, b, kc); if (e == hipSuccess) e = hipStreamSynchronize(m->ctx->stream); }
+    if (e != hipSuccess) { (void)hipGetLastError(); b.cache = nullptr; }
+    return e == hipSuccess;
+}
+// one launch's parameters: the client's table, partials and cache; input row, position = *pos_ptr + pos_off, optional f32 logits
+static EngParams engine_params(vox_model* m, const EngBinding& b, const vox_cache* kc, const float* h_in, const int* pos_ptr, int pos_off, float* logits_out) {
     const vox_model_cfg& c = m->cfg;
-    EngParams ep{}; ep.stream = m->eng_stream; ep.cu_stride = eng_stream_bytes(c.dec_layers, c.vocab) / 256; ep.layers = m->eng_tab; ep.n_layers = c.dec_layers; ep.h_in = m->d_h; ep.final_norm = m->dec_norm;
-    ep.pos_ptr = m->d_pos; ep.pos_off = 0; ep.rope_cos = m->dec_cos; ep.rope_sin = m->dec_sin; ep.max_seq = m->cache->max_seq; ep.window = c.dec_window; ep.eps = c.norm_eps;
-    eng_state_carve(m->eng_state, &ep); ep.part_val = m->d_part_val; ep.part_idx = m->d_part_idx; ep.logits_out = logits_out; ep.vocab = c.vocab; ep.tl = nullptr; ep.tl_layer = -1;
+    EngParams ep{}; ep.stream = m->eng_stream; ep.cu_stride = eng_stream_bytes(c.dec_layers, c.vocab) / 256; ep.layers = b.tab; ep.n_layers = c.dec_layers; ep.h_in = h_in; ep.final_norm = m->dec_norm;
+    ep.pos_ptr = pos_ptr; ep.pos_off = pos_off; ep.rope_cos = m->dec_cos; ep.rope_sin = m->dec_sin; ep.max_seq = kc->max_seq; ep.window = c.dec_window; ep.eps = c.norm_eps;
+    eng_state_carve(m->eng_state, &ep); ep.part_val = b.part_val; ep.part_idx = b.part_idx; ep.logits_out = logits_out; ep.vocab = c.vocab; ep.tl = nullptr; ep.tl_layer = -1;
     ep.flags = m->eng_flags; ep.pace_ticks = (m->eng_flags & 512) ? 0 : m->eng_pace; ep.ag_delay_ticks = (m->eng_flags & 512) ? m->eng_pace : 0;
-    if (argmax_in) {      // the launch forms its own input: argmax of the previous launch's partials, token -> d_tokens, embedding + audio row (vox_engine.hip comm_next_input)
-        ep.flags |= 65536; ep.h_in = nullptr; ep.tokens = m->d_tokens; ep.pos_rw = m->d_pos; ep.tok_qs = m->tok.w.qs; ep.tok_sc = m->tok.w.sc; ep.tok_nb = m->tok.w.nb; ep.audio = m->d_audio;
-    }
     return ep;
 }
+// before n launches are enqueued: tags = (launch serial + 1) * 64 + layer + 1 are 32-bit -- restart the serial long before they wrap (never inside a captured graph)
+static int32_t engine_take_serials(vox_model* m, unsigned long long n, hipStream_t s) {
+    if (m->eng_launches + n > (1ull << 25)) { HIPCHK(hipMemsetAsync(m->eng_state, 0, eng_state_bytes(), s)); m->eng_launches = 0; }
+    m->eng_launches += n; return VOX_OK;
+}
+// the engine's error word (first failure code of the launches so far, 0 = ok) on its way to a host word: lands with the next synchronisation of s
+static int32_t engine_err_enqueue(vox_model* m, unsigned* dst, hipStream_t s) {
+    EngParams ep{}; eng_state_carve(m->eng_state, &ep); HIPCHK(hipMemcpyAsync(dst, ep.err, 8, hipMemcpyDeviceToHost, s)); return VOX_OK;
+}
+// how every client names a non-zero error word e (strikes 0: a measurement launch, no strike is counted)
+static std::string engine_timeout_text(unsigned e, int strikes) {
+    char b[96]; const int n = snprintf(b, sizeof b, "hand-off timeout (code %u, workgroup %u)", e & 0xff, (e >> 8) & 0xff);
+    if (strikes > 0) snprintf(b + n, sizeof b - n, ", strike %d of 3", strikes);
+    return b;
+}
+// while it lives, the engine serves nobody: steps a client runs again after a hand-off timeout take the per-operator launches.  Restores what it found (re-runs nest).
+struct EngSuspend { vox_model* m; bool was; explicit EngSuspend(vox_model* m_) : m(m_), was(m_->eng_suspended) { m->eng_suspended = true; } ~EngSuspend() { m->eng_suspended = was; } };
 
 extern "C" int32_t vox_model_set_decode_engine(vox_model* m, int32_t on, int32_t* active) {
     ARGCHK(m, "null argument"); VOXCHK(ctx_bind(m->ctx));
@@ -2016,7 +2056,7 @@ static int32_t ensure_decode_state(vox_model* m, int S) {
     if (!m->cache || m->cache->max_seq < S) {
         int cap = std::max(S, 256); cap = std::min((cap + 255) / 256 * 256, m->dec_rope_len);
         ARGCHK(S <= cap, "sequence of %d decoder positions exceeds the RoPE table (%d)", S, m->dec_rope_len);
-        if (m->cache) { HIPCHK(hipStreamSynchronize(m->ctx->stream)); cache_unregister(m->cache); (void)hipFree(m->cache->k); (void)hipFree(m->cache->v); delete m->cache; m->cache = nullptr; m->eng_tab_cache = nullptr; m->eng_tab_k = nullptr; }
+        if (m->cache) { HIPCHK(hipStreamSynchronize(m->ctx->stream)); cache_release(m->cache); m->eng_offline.cache = nullptr; }
         graphs_destroy(m);
         VOXCHK(cache_alloc(m, cap, &m->cache));
     }
@@ -2090,12 +2130,20 @@ static int32_t prefix_build(vox_model* m, const float* t_embed) {
     m->cache->len = 0;
     VOXCHK(decoder_prefill_dev(m, m->d_prefix, PC, m->cache, 0));
     const size_t pitch = (size_t)m->cache->max_seq * hd * 4;      // cache: [layer][kv head][max_seq][hd], layers back to back
-    ARGCHK(cache_layer_floats(m, m->cache) == (size_t)KV * m->cache->max_seq * hd, "internal: cache layout");
+    ARGCHK(m->cache->layer_stride == (size_t)KV * m->cache->max_seq * hd, "internal: cache layout");
     HIPCHK(hipMemcpy2DAsync(p.dec_k, rows_bytes, m->cache->k, pitch, rows_bytes, n_rows, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpy2DAsync(p.dec_v, rows_bytes, m->cache->v, pitch, rows_bytes, n_rows, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipStreamSynchronize(s));
     p.t_embed.assign(t_embed, t_embed + c.dec_dim); p.dec_built = true;      // (after vox_model_set_t_embed, which clears the flag when t_embed changes)
     return VOX_OK;
+}
+// decoder positions 0 .. PC-1 of the prefix state into a cache: K / V rows of every (layer, kv head) plane, the cache then stands at PC
+static int32_t prefix_rows_into(vox_model* m, vox_cache* kc, hipStream_t s) {
+    const vox_model_cfg& c = m->cfg; const PrefixState& P = m->pfx;
+    const size_t rows_bytes = (size_t)P.PC * c.dec_head_dim * 4, n_rows = (size_t)c.dec_layers * c.dec_kv_heads, pitch = (size_t)kc->max_seq * c.dec_head_dim * 4;
+    HIPCHK(hipMemcpy2DAsync(kc->k, pitch, P.dec_k, rows_bytes, rows_bytes, n_rows, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpy2DAsync(kc->v, pitch, P.dec_v, rows_bytes, rows_bytes, n_rows, hipMemcpyDeviceToDevice, s));
+    kc->len = P.PC; return VOX_OK;
 }
 // Does THIS call run on the prefix?  Only a clip that decodes at least one position behind the prefix tokens (then at least one live adapter row exists).
 static bool prefix_usable(const vox_model* m, int T) {
@@ -2127,12 +2175,16 @@ extern "C" int32_t vox_model_prefix_info(const vox_model* m, int32_t out[4]) {
 // mode 0: the step and the launch that turns its argmax partials into the next token + input (every path).  Engine only -- mode 1: the engine launch alone, its
 // partials left for whoever comes next; mode 2: an engine launch that BEGINS with the argmax of the previous launch's partials (flags 65536): a chain
 // [mode 1] [mode 2] ... [mode 2] [argmax_final] is the same token sequence as mode 0 steps with one launch per token instead of two.
-static int32_t decode_step_enqueue(vox_model* m, float* logits_out, int mode = 0) {
+// eng: engine_bind(m, m->eng_offline, m->cache) said yes for this utterance (modes 1 and 2 exist only then).
+static int32_t decode_step_enqueue(vox_model* m, float* logits_out, bool eng, int mode = 0) {
     const vox_model_cfg& c = m->cfg; hipStream_t s = m->ctx->stream;
-    if (mode != 0) { HIPCHK(launch_decode_engine(engine_params(m, logits_out, mode == 2), s)); return VOX_OK; }
-    if (engine_active(m)) {      // one launch: 26 layers + final norm + lm_head + per-CU argmax partials
-        HIPCHK(launch_decode_engine(engine_params(m, logits_out), s));
-        HIPCHK(launch_argmax_embed(m->d_part_val, m->d_part_idx, 256, m->d_tokens, m->d_pos, m->tok.w, m->d_audio, c.dec_dim, m->d_h, s));
+    if (eng) {      // one launch: 26 layers + final norm + lm_head + per-CU argmax partials
+        EngParams ep = engine_params(m, m->eng_offline, m->cache, m->d_h, m->d_pos, 0, logits_out);
+        if (mode == 2) {      // the launch forms its own input: argmax of the previous launch's partials, token -> d_tokens, embedding + audio row (vox_engine.hip comm_next_input)
+            ep.flags |= 65536; ep.h_in = nullptr; ep.tokens = m->d_tokens; ep.pos_rw = m->d_pos; ep.tok_qs = m->tok.w.qs; ep.tok_sc = m->tok.w.sc; ep.tok_nb = m->tok.w.nb; ep.audio = m->d_audio;
+        }
+        HIPCHK(launch_decode_engine(ep, s));
+        if (mode == 0) HIPCHK(launch_argmax_embed(m->d_part_val, m->d_part_idx, 256, m->d_tokens, m->d_pos, m->tok.w, m->d_audio, c.dec_dim, m->d_h, s));
         return VOX_OK;
     }
     VOXCHK(decoder_step_dev(m, m->d_h, m->cache, m->d_pos, 0));
@@ -2165,11 +2217,7 @@ static int32_t transcribe_dev(vox_model* m, const float* d_mel, int T, const flo
     bool eng_failed = false; int steps = 0;
     auto decode_once = [&]() -> int32_t {
     VOXCHK(ensure_decode_state(m, S));
-    VOXCHK(engine_prepare(m));
-    if (engine_active(m)) {      // tags = (launch serial + 1) * 64 + layer + 1 are 32-bit: restart the serial long before they wrap (never inside a captured graph)
-        if (m->eng_launches + (unsigned long long)S + 8 > (1ull << 25)) { HIPCHK(hipMemsetAsync(m->eng_state, 0, eng_state_bytes(), s)); m->eng_launches = 0; }
-        m->eng_launches += (unsigned long long)S + 8;
-    }
+    const bool eng = engine_bind(m, m->eng_offline, m->cache); if (eng) VOXCHK(engine_take_serials(m, (unsigned long long)S + 8, s));
     std::vector<int32_t> prefix(PREFIX_LEN, STREAMING_PAD); prefix[0] = BOS;      // model.rs:891-892
     HIPCHK(hipMemcpyAsync(m->d_tokens, prefix.data(), PREFIX_LEN * 4, hipMemcpyHostToDevice, s));
     m->cache->len = 0;
@@ -2179,10 +2227,7 @@ static int32_t transcribe_dev(vox_model* m, const float* d_mel, int T, const flo
         // Positions 0 .. PC-1 (= 36) are the model's: their K / V rows are copied into the cache (every call: the cache may have been re-allocated, and a decode overwrites
         // nothing below PC but a batch call may), and position PC = 37 -- the last prefix token, the first one whose output is kept -- runs as the first ordinary decode
         // step below: no prefill, no separate lm_head; tokens[38] comes out of the same argmax chain as every later token.
-        const PrefixState& P = m->pfx; const size_t rows_bytes = (size_t)PC * c.dec_head_dim * 4, n_rows = (size_t)c.dec_layers * c.dec_kv_heads, pitch = (size_t)m->cache->max_seq * c.dec_head_dim * 4;
-        HIPCHK(hipMemcpy2DAsync(m->cache->k, pitch, P.dec_k, rows_bytes, rows_bytes, n_rows, hipMemcpyDeviceToDevice, s));
-        HIPCHK(hipMemcpy2DAsync(m->cache->v, pitch, P.dec_v, rows_bytes, rows_bytes, n_rows, hipMemcpyDeviceToDevice, s));
-        m->cache->len = PC;
+        VOXCHK(prefix_rows_into(m, m->cache, s));
         HIPCHK(hipMemcpyAsync(m->d_pos, &PC, 4, hipMemcpyHostToDevice, s));
         steps = S - PC - 1;                                              // pos = 37 .. S-2
     } else {
@@ -2201,28 +2246,26 @@ static int32_t transcribe_dev(vox_model* m, const float* d_mel, int T, const flo
     steps = std::max(S - PREFIX_LEN - 1, 0);                            // pos = 39 .. S-1 (model.rs:938)
     }
     stage.begin("decode");
-    // attn_wo accumulators: every step leaves them cleared (w2 does it); once per utterance they are cleared outright, so a call that failed
-    // half-way through a layer cannot leak into the next one
-    if (steps > 0 && m->d_wo_acc) HIPCHK(hipMemsetAsync(m->d_wo_acc, 0, (size_t)c.dec_layers * c.dec_dim * 8, s));
+    if (steps > 0) VOXCHK(wo_acc_clear(m, s));      // once per utterance
     if (steps > 0) HIPCHK(launch_embed(m->tok.w, m->d_tokens, 1, m->d_audio, c.dec_dim, m->d_pos, 0, 0, m->d_h, s));   // input of the first decode step (audio[38] exists iff S >= 39; on the prefix: audio[37] + embed(PAD))
     if (logits_host) {
-        for (int i = 0; i < steps; i++) VOXCHK(decode_step_enqueue(m, d_logits_all + (size_t)(i + 1) * c.vocab));
+        for (int i = 0; i < steps; i++) VOXCHK(decode_step_enqueue(m, d_logits_all + (size_t)(i + 1) * c.vocab, eng));
     } else if (steps > 0) {
         // Replayed graphs: one step per graph by default.  VOX_DECODE_UNROLL=U (measurement knob) also builds a U-step graph for the bulk of
         // the steps; measured in round 2 (profiles/r02_decode_knobs.txt): no gain -- graph boundaries are not where the time goes.
         // Engine path: the replayed launches take their input from the previous launch's argmax partials themselves (mode 2), so a step is ONE launch; the
         // utterance's first step runs eagerly as a plain launch (mode 1) and one argmax_final behind the last step writes the last token.  VOX_ENGINE_ARGMAX_IN=0:
         // the two-launch step (measurement knob).  With one or two launches per step the graph boundaries show: 8 steps per graph by default (engine path).
-        const bool chain = engine_active(m) && !(knob_str("VOX_ENGINE_ARGMAX_IN") && knob_str("VOX_ENGINE_ARGMAX_IN")[0] == '0');
+        const bool chain = eng && !(knob_str("VOX_ENGINE_ARGMAX_IN") && knob_str("VOX_ENGINE_ARGMAX_IN")[0] == '0');
         const int step_mode = chain ? 2 : 0;
-        int U = engine_active(m) ? 8 : 1; { const char* e = knob_str("VOX_DECODE_UNROLL"); if (e && atoi(e) >= 1 && atoi(e) <= 32) U = atoi(e); }
+        int U = eng ? 8 : 1; { const char* e = knob_str("VOX_DECODE_UNROLL"); if (e && atoi(e) >= 1 && atoi(e) <= 32) U = atoi(e); }
         if (m->graph_cache != m->cache || m->graph_audio != m->d_audio || m->graph_unroll != U || m->graph_mode != step_mode) {
             graphs_destroy(m); m->graph_cache = m->cache; m->graph_audio = m->d_audio; m->graph_unroll = U; m->graph_mode = step_mode;
         }
         auto capture = [&](int which, int n_steps) -> int32_t {
             HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
             int32_t r = VOX_OK;
-            for (int i = 0; i < n_steps && r == VOX_OK; i++) r = decode_step_enqueue(m, nullptr, step_mode);
+            for (int i = 0; i < n_steps && r == VOX_OK; i++) r = decode_step_enqueue(m, nullptr, eng, step_mode);
             hipError_t ce = hipStreamEndCapture(s, &m->graph[which]);
             if (r != VOX_OK) return r;
             HIPCHK(ce);
@@ -2230,9 +2273,9 @@ static int32_t transcribe_dev(vox_model* m, const float* d_mel, int T, const flo
             return VOX_OK;
         };
         int done = 0;
-        if (chain) { VOXCHK(decode_step_enqueue(m, nullptr, 1)); done = 1; }       // the utterance's first step: its input is in d_h
+        if (chain) { VOXCHK(decode_step_enqueue(m, nullptr, eng, 1)); done = 1; }       // the utterance's first step: its input is in d_h
         if (!m->graph_exec[0]) {
-            if (!chain) { VOXCHK(decode_step_enqueue(m, nullptr)); done = 1; }     // eager first step (also warms function attributes)
+            if (!chain) { VOXCHK(decode_step_enqueue(m, nullptr, eng)); done = 1; }     // eager first step (also warms function attributes)
             HIPCHK(hipStreamSynchronize(s));
             VOXCHK(capture(0, 1));
         }
@@ -2243,11 +2286,11 @@ static int32_t transcribe_dev(vox_model* m, const float* d_mel, int T, const flo
     }
     HIPCHK(hipMemcpyAsync(out_ids, m->d_tokens + PREFIX_LEN, (size_t)n * 4, hipMemcpyDeviceToHost, s));
     if (logits_host) HIPCHK(hipMemcpyAsync(logits_host, d_logits_all, (size_t)n * c.vocab * 4, hipMemcpyDeviceToHost, s));
-    const bool eng_used = engine_active(m) && steps > 0;
-    if (eng_used) { EngParams ep = engine_params(m, nullptr); HIPCHK(hipMemcpyAsync(m->eng_err_host, ep.err, 8, hipMemcpyDeviceToHost, s)); }
+    const bool eng_used = eng && steps > 0;
+    if (eng_used) VOXCHK(engine_err_enqueue(m, m->eng_offline.err_word, s));
     HIPCHK(hipStreamSynchronize(s));
     stage.end();
-    if (eng_used && m->eng_err_host[0]) { eng_failed = true; return VOX_OK; }
+    if (eng_used && m->eng_offline.err_word[0]) { eng_failed = true; return VOX_OK; }
     return VOX_OK;
     };
     VOXCHK(decode_once());
@@ -2255,13 +2298,12 @@ static int32_t transcribe_dev(vox_model* m, const float* d_mel, int T, const flo
         // A bounded hand-off wait expired inside the engine: its 256 workgroups were not co-resident for 20 ms (another kernel on the GPU, a CU mask, a debugger).  The ids
         // of that attempt are not trustworthy -- the SAME utterance is decoded again on the per-operator launches (the encoder output is still in place), the engine is
         // re-armed for the next utterance, and after three strikes it is switched off for the life of the model.
-        const unsigned e = m->eng_err_host[0];
+        const unsigned e = m->eng_offline.err_word[0];
         VOXCHK(engine_strike(m));
-        fprintf(stderr, "[voxtral_hip] decode engine: hand-off timeout (code %u, workgroup %u), strike %d of 3; this utterance is decoded again on the per-operator path%s\n",
-                e & 0xff, (e >> 8) & 0xff, m->eng_strikes, m->eng_strikes >= 3 ? ", the engine is switched off" : "");
-        m->eng_suspended = true; eng_failed = false;
-        const int32_t r = decode_once();
-        m->eng_suspended = false; graphs_destroy(m);      // (the graph captured during the re-run holds the per-operator launches)
+        fprintf(stderr, "[voxtral_hip] decode engine: %s; this utterance is decoded again on the per-operator path%s\n",
+                engine_timeout_text(e, m->eng_strikes).c_str(), m->eng_strikes >= 3 ? ", the engine is switched off" : "");
+        eng_failed = false; int32_t r; { EngSuspend off(m); r = decode_once(); }
+        graphs_destroy(m);      // (the graph captured during the re-run holds the per-operator launches)
         if (r != VOX_OK) return r;
     }
     m->cache->len = (pfx ? PC : PREFIX_LEN) + steps;
@@ -2648,9 +2690,8 @@ static int32_t transcribe_batch_impl(vox_model* m, int32_t n, const float* const
     if (use_eng) {
         HIPCHK(b_ssq_e.alloc_pooled(cx, (size_t)(256 + 16) * 16 * 4 * n_grp)); xb.ssq_e = b_ssq_e.as<float>();
         for (int gi = 0; gi < n_grp; gi++) {
-            EngLayerTab* tab = eng_tabs.data() + (size_t)gi * c.dec_layers; const size_t g_off = (size_t)gi * 16 * seq_stride;
-            for (int l = 0; l < c.dec_layers; l++)
-                tab[l] = EngLayerTab{m->dec[l].attn_norm, m->dec[l].ffn_norm, m->dec[l].ada_mul, xb.k + (size_t)l * layer_stride + g_off, xb.v + (size_t)l * layer_stride + g_off};
+            EngLayerTab* tab = eng_tabs.data() + (size_t)gi * c.dec_layers;
+            dec_layer_tab(m, xb.k, xb.v, layer_stride, (size_t)gi * 16 * seq_stride, tab);
             HIPCHK(hipMemcpyAsync(m->engb_tab[gi], tab, sizeof(EngLayerTab) * c.dec_layers, hipMemcpyHostToDevice, s));
         }
     }
@@ -2931,8 +2972,7 @@ struct ContSession {
         const std::vector<int>& hq = sch.h_queue;      // (the slot queues too: no pageable copy may sit behind phase A)
         HIPCHK(b_queue.alloc_pooled(cx, hq.size() * 4)); HIPCHK(hipMemcpyAsync(b_queue.p, hq.data(), hq.size() * 4, hipMemcpyHostToDevice, s));
         std::vector<EngLayerTab> tab(c.dec_layers);      // the engine's layer table, one for every group: the layers' slabs (cache slices are picked per slot)
-        for (int l = 0; l < c.dec_layers; l++)
-            tab[l] = EngLayerTab{m->dec[l].attn_norm, m->dec[l].ffn_norm, m->dec[l].ada_mul, b_k.as<float>() + (size_t)l * layer_stride, b_v.as<float>() + (size_t)l * layer_stride};
+        dec_layer_tab(m, b_k.as<float>(), b_v.as<float>(), layer_stride, 0, tab.data());
         if (pol.use_eng) HIPCHK(hipMemcpyAsync(m->engb_tab[0], tab.data(), sizeof(EngLayerTab) * c.dec_layers, hipMemcpyHostToDevice, s));
         HIPCHK(hipStreamSynchronize(s));      // the host vectors go out of scope
         return VOX_OK;
@@ -3378,51 +3418,29 @@ static int32_t pw_ids_dev(vox_model* m, const int32_t* ids, int n) {      // hos
     HIPCHK(hipMemcpyAsync(m->pw_ids, ids, (size_t)n * 4, hipMemcpyHostToDevice, m->ctx->stream));
     return VOX_OK;
 }
-// is the decode engine usable for ONE row against the caller's cache?  Builds the engine's layer table for that cache on first use.
+// is the decode engine usable for ONE row against the caller's cache?  Binds the piecewise table to that cache on first use.
 static bool pw_engine_ready(vox_model* m, vox_cache* kc) {
-    const vox_model_cfg& c = m->cfg; hipStream_t s = m->ctx->stream;
-    if (!m->eng_ok || !m->eng_on || m->eng_suspended || kc->max_seq > 1024 || kc->len >= kc->max_seq) return false;
-    if (engine_stream_prepare(m) != VOX_OK || !m->eng_ready) return false;
-    if (!m->pw_tab) {
-        if (hipMalloc((void**)&m->pw_tab, sizeof(EngLayerTab) * 32) != hipSuccess) { (void)hipGetLastError(); m->pw_tab = nullptr; return false; }
-        if (hipMalloc((void**)&m->pw_part_val, 256 * 4) != hipSuccess || hipMalloc((void**)&m->pw_part_idx, 256 * 4) != hipSuccess || hipMalloc((void**)&m->pw_zero, 4) != hipSuccess ||
-            hipMemsetAsync(m->pw_zero, 0, 4, s) != hipSuccess || hipHostMalloc((void**)&m->pw_err_pin, 8, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); m->pw_err_pin = nullptr; return false; }
-        m->pw_err_pin[0] = m->pw_err_pin[1] = 0u;
-    }
-    if (!m->pw_part_val || !m->pw_part_idx || !m->pw_zero || !m->pw_err_pin) return false;
-    if (m->pw_tab_cache != kc || m->pw_tab_gen != kc->gen) {
-        const size_t lf = cache_layer_floats(m, kc);
-        std::vector<EngLayerTab> tab(c.dec_layers);
-        for (int l = 0; l < c.dec_layers; l++) tab[l] = EngLayerTab{m->dec[l].attn_norm, m->dec[l].ffn_norm, m->dec[l].ada_mul, kc->k + (size_t)l * lf, kc->v + (size_t)l * lf};
-        if (hipMemcpyAsync(m->pw_tab, tab.data(), sizeof(EngLayerTab) * c.dec_layers, hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return false; }
-        m->pw_tab_cache = kc; m->pw_tab_gen = kc->gen;
-    }
-    return true;
+    if (kc->len >= kc->max_seq || !engine_bind(m, m->eng_pw, kc)) return false;
+    if (m->pw_zero) return true;      // the launch's position word: position = 0 + cache length
+    if (hipMalloc((void**)&m->pw_zero, 4) == hipSuccess && hipMemsetAsync(m->pw_zero, 0, 4, m->ctx->stream) == hipSuccess) return true;
+    (void)hipGetLastError(); if (m->pw_zero) (void)hipFree(m->pw_zero); m->pw_zero = nullptr; return false;
 }
-static EngParams pw_engine_params(vox_model* m, const vox_cache* kc, const float* x) {
-    const vox_model_cfg& c = m->cfg;
-    EngParams ep{}; ep.stream = m->eng_stream; ep.cu_stride = eng_stream_bytes(c.dec_layers, c.vocab) / 256; ep.layers = m->pw_tab; ep.n_layers = c.dec_layers; ep.h_in = x; ep.final_norm = m->dec_norm;
-    ep.pos_ptr = m->pw_zero; ep.pos_off = kc->len; ep.rope_cos = m->dec_cos; ep.rope_sin = m->dec_sin; ep.max_seq = kc->max_seq; ep.window = c.dec_window; ep.eps = c.norm_eps;
-    eng_state_carve(m->eng_state, &ep); ep.part_val = m->pw_part_val; ep.part_idx = m->pw_part_idx; ep.logits_out = m->pw_logits; ep.vocab = c.vocab; ep.tl = nullptr; ep.tl_layer = -1;
-    ep.flags = m->eng_flags; ep.pace_ticks = (m->eng_flags & 512) ? 0 : m->eng_pace; ep.ag_delay_ticks = (m->eng_flags & 512) ? m->eng_pace : 0;
-    return ep;
-}
-// after a stream synchronisation that covered a copy of the engine's error word into eng_err_host: a hand-off timeout fails the call loudly (the cache row of that step is
+// after a stream synchronisation that covered a copy of the engine's error word into eng_pw.err_word: a hand-off timeout fails the call loudly (the cache row of that step is
 // rewritten when the caller repeats it), counts a strike and re-arms the engine; three strikes switch it off for the model
 // (the error word reaches the host through a pinned buffer refreshed asynchronously behind every engine launch: a caller that stays on the device-resident entries
 // -- whose only synchronisation is vox_argmax_rows on the CONTEXT -- still gets the failure at its next decoder call, not silently wrong logits)
 static int32_t pw_engine_verdict(vox_model* m) {
-    if (!m->pw_err_pin) return VOX_OK;
-    const unsigned e = *(volatile unsigned*)m->pw_err_pin;
+    if (!m->eng_pw.err_word) return VOX_OK;
+    const unsigned e = *(volatile unsigned*)m->eng_pw.err_word;
     if (!e) return VOX_OK;
-    m->pw_err_pin[0] = 0u; m->pw_eng_used = false;
+    m->eng_pw.err_word[0] = 0u; m->pw_eng_used = false;
     m->pw_memo = false; m->pw_verdict_failed = true;
     // take back every row that is not known to be good: the failed step's, and whatever was appended behind it before the failure was seen
     int len_now = -1;
     if (m->pw_pend_rows > 0 && m->pw_pend_cache && cache_alive(m->pw_pend_cache, m->pw_pend_gen)) { m->pw_pend_cache->len = std::max(m->pw_pend_cache->len - m->pw_pend_rows, 0); len_now = m->pw_pend_cache->len; }
     m->pw_pend_rows = 0; m->pw_pend_cache = nullptr; if (m->ctx->pw_model == m) m->ctx->pw_model = nullptr;
     VOXCHK(engine_strike(m));
-    return fail(VOX_ERR_HIP, "decode engine: hand-off timeout (code %u, workgroup %u), strike %d of 3: the GPU is shared; the KV cache is back at length %d -- repeat the step%s", e & 0xff, (e >> 8) & 0xff, m->eng_strikes,
+    return fail(VOX_ERR_HIP, "decode engine: %s: the GPU is shared; the KV cache is back at length %d -- repeat the step%s", engine_timeout_text(e, m->eng_strikes).c_str(),
                 len_now, m->eng_strikes >= 3 ? " (the engine is now switched off, the per-operator launches serve it)" : "");
 }
 // behind a synchronisation of the stream: the pinned error word of every engine launch enqueued so far has landed -- read the verdict; clean: every pending row is verified
@@ -3479,16 +3497,15 @@ extern "C" int32_t vox_forward_hidden_with_cache_ex(vox_model* m, const float* x
     const float* xin = x;
     if (mem_kind != VOX_MEM_DEVICE) { HIPCHK(hipMemcpyAsync(m->pw_x, x, (size_t)M * D * 4, hipMemcpyHostToDevice, s)); xin = m->pw_x; }
     if (eng) {      // one launch: 26 layers against the caller's cache + final norm + lm_head (logits + argmax partials)
-        if (m->eng_launches + 16 > (1ull << 25)) { HIPCHK(hipMemsetAsync(m->eng_state, 0, eng_state_bytes(), s)); m->eng_launches = 0; }
-        m->eng_launches += 1;
-        const EngParams ep = pw_engine_params(m, kc, xin);
+        VOXCHK(engine_take_serials(m, 1, s));
+        const EngParams ep = engine_params(m, m->eng_pw, kc, xin, m->pw_zero, kc->len, m->pw_logits);
         HIPCHK(launch_decode_engine(ep, s));
         HIPCHK(launch_eng_hidden(ep, m->pw_hidden, s));
-        HIPCHK(hipMemcpyAsync(m->pw_err_pin, ep.err, 8, hipMemcpyDeviceToHost, s));      // pinned destination: truly asynchronous
+        VOXCHK(engine_err_enqueue(m, m->eng_pw.err_word, s));      // pinned destination: truly asynchronous
         m->pw_memo = true; m->pw_eng_used = true;
     } else {
         if (xin != m->pw_x) HIPCHK(hipMemcpyAsync(m->pw_x, xin, (size_t)M * D * 4, hipMemcpyDeviceToDevice, s));
-        if (M == 1) { if (m->d_wo_acc) HIPCHK(hipMemsetAsync(m->d_wo_acc, 0, (size_t)c.dec_layers * D * 8, s)); VOXCHK(decoder_step_dev(m, m->pw_x, kc, nullptr, kc->len)); }
+        if (M == 1) { VOXCHK(wo_acc_clear(m, s)); VOXCHK(decoder_step_dev(m, m->pw_x, kc, nullptr, kc->len)); }
         else VOXCHK(decoder_prefill_dev(m, m->pw_x, M, kc, kc->len));
         HIPCHK(launch_rms_norm(m->pw_x, D, M, D, m->dec_norm, nullptr, c.norm_eps, m->pw_hidden, D, s));   // model.rs:676
     }
@@ -3557,7 +3574,7 @@ extern "C" int32_t vox_lm_head_argmax(vox_model* m, const float* hidden, int32_t
     const vox_model_cfg& c = m->cfg; hipStream_t s = m->ctx->stream;
     if (m->pw_ids_cap < M) { if (m->pw_ids) HIPCHK(hipFree(m->pw_ids)); m->pw_ids = nullptr; m->pw_ids_cap = 0; const int cap = std::max(M, 64); HIPCHK(hipMalloc((void**)&m->pw_ids, (size_t)cap * 4)); m->pw_ids_cap = cap; }
     if (pw_memo_hit(m, hidden, M, mem_kind)) {
-        HIPCHK(launch_argmax_final(m->pw_part_val, m->pw_part_idx, 256, m->pw_ids, nullptr, 0, 0, s));
+        HIPCHK(launch_argmax_final(m->eng_pw.part_val, m->eng_pw.part_idx, 256, m->pw_ids, nullptr, 0, 0, s));
     } else {
         const float* hx = hidden;
         if (mem_kind != VOX_MEM_DEVICE) { VOXCHK(ensure(&m->pw_x, &m->pw_x_cap, (size_t)M * c.dec_dim)); HIPCHK(hipMemcpyAsync(m->pw_x, hidden, (size_t)M * c.dec_dim * 4, hipMemcpyHostToDevice, s)); hx = m->pw_x; }
@@ -3649,9 +3666,8 @@ static int32_t forward_composite(vox_model* m, int mode, const float* mel, int32
         // an engine hand-off timeout (a one-row call on a shared GPU): the verdict has taken the decoder row back; the ENCODER cache of mode 2 cannot be rewound (it may have
         // compacted itself), so the call is not failed -- the decoder rows run once more on the per-operator launches and the caller never sees a half-advanced pair of caches
         m->pw_verdict_failed = false;
-        const bool sv = m->eng_suspended; m->eng_suspended = true;
+        EngSuspend off(m);
         r = decode_rows(); rs = pw_sync(m);
-        m->eng_suspended = sv;
     }
     if (tmp) (void)vox_cache_free(tmp);
     return r != VOX_OK ? r : rs;
@@ -3749,22 +3765,22 @@ extern "C" int32_t vox_bench_decode_gemv(vox_model* m, int32_t which, int32_t it
     if (which == 5) {      // the whole decode step as ONE launch of the persistent engine, at the positions the 16 s bench clip decodes at (38 .. 145: four equal shares at 40, 75,
         // 110, 145 -- the step gets longer with the position, a single low position would overstate the in-product rate)
         if (!m->t_embed_set) { std::vector<float> te(c.dec_dim); vox_time_embedding(6.0f, c.dec_dim, te.data()); VOXCHK(vox_model_set_t_embed(m, te.data())); }
-        VOXCHK(engine_prepare(m));
-        if (!engine_active(m)) return fail(VOX_ERR_UNSUPPORTED, "decode engine not active for this model / device");
+        if (!engine_bind(m, m->eng_offline, m->cache)) return fail(VOX_ERR_UNSUPPORTED, "decode engine not active for this model / device");
         static const int bench_pos[4] = {40, 75, 110, 145};
         HIPCHK(hipMemcpyAsync(m->d_pos, &bench_pos[0], 4, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemsetAsync(m->d_h, 0, (size_t)c.dec_dim * 4, s));
         double bytes = 0; for (const Q4W* w : {&m->dec[0].wqkv.w, &m->dec[0].wo.w, &m->dec[0].w13.w, &m->dec[0].w2.w}) bytes += (double)w->N * w->nb * 18.0;
         *bytes_per_launch = bytes * c.dec_layers + (double)m->tok.w.N * m->tok.w.nb * 18.0;
         if (kernel_name) *kernel_name = "decode_engine_kernel";
-        const EngParams ep = engine_params(m, nullptr);
+        const int per_q = std::max(iters / 4, 1);
+        VOXCHK(engine_take_serials(m, 4ull * per_q + 3, s));      // three warm-up launches + four timed quarters
+        const EngParams ep = engine_params(m, m->eng_offline, m->cache, m->d_h, m->d_pos, 0, nullptr);
         for (int i = 0; i < 3; i++) HIPCHK(launch_decode_engine(ep, s));
         // one event pair per quarter, around the LAUNCHES only: the position update between the quarters (a 4-byte copy from pageable host memory: 20 - 250 us depending on
         // the box) used to sit inside the timed region -- 603 us per launch on one box, 628 on another where rocprofv3 saw 605 (round 6)
         // ... and the launches of a quarter go out as ONE graph replay, the way the product issues its steps (on some boxes ten plain launches in a row cost 25 us more per
         // launch than the same ten in a graph: 629 against 603 us where the product's own steps took 596)
         hipEvent_t ev[8]; for (auto& e : ev) HIPCHK(hipEventCreate(&e));
-        const int per_q = std::max(iters / 4, 1);
         hipGraph_t gq = nullptr; hipGraphExec_t gx = nullptr;
         HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
         hipError_t ce = hipSuccess; for (int i = 0; i < per_q && ce == hipSuccess; i++) ce = launch_decode_engine(ep, s);
@@ -3782,10 +3798,9 @@ extern "C" int32_t vox_bench_decode_gemv(vox_model* m, int32_t which, int32_t it
         for (auto& e : ev) (void)hipEventDestroy(e);
         (void)hipGraphExecDestroy(gx); (void)hipGraphDestroy(gq);
         iters = 4 * per_q;
-        m->eng_launches += (unsigned long long)iters + 3;
         *avg_us = (double)ms * 1000.0 / iters;
         unsigned err2[2] = {0, 0}; HIPCHK(hipMemcpy(err2, ep.err, 8, hipMemcpyDeviceToHost));
-        if (err2[0]) return fail(VOX_ERR_HIP, "decode engine: hand-off timeout (code %u, workgroup %u)", err2[0] & 0xff, (err2[0] >> 8) & 0xff);
+        if (err2[0]) return fail(VOX_ERR_HIP, "decode engine: %s", engine_timeout_text(err2[0], 0).c_str());
         return VOX_OK;
     }
     const int zero = 0; HIPCHK(hipMemcpyAsync(m->d_pos, &zero, 4, hipMemcpyHostToDevice, s));
@@ -3793,10 +3808,10 @@ extern "C" int32_t vox_bench_decode_gemv(vox_model* m, int32_t which, int32_t it
     HIPCHK(hipMemsetAsync(m->d_act, 0, (size_t)c.dec_ffn * 4, s));
     if (!m->t_embed_set) { std::vector<float> te(c.dec_dim); vox_time_embedding(6.0f, c.dec_dim, te.data()); VOXCHK(vox_model_set_t_embed(m, te.data())); }
     const int D = c.dec_dim, QD = c.dec_heads * c.dec_head_dim, KD = c.dec_kv_heads * c.dec_head_dim, F = c.dec_ffn, hd = c.dec_head_dim;
-    const size_t lf = cache_layer_floats(m, m->cache);
+    const size_t lf = m->cache->layer_stride;
     bool fused = false;
     { AttnParams ap{}; ap.n_heads = c.dec_heads; ap.n_kv_heads = c.dec_kv_heads; ap.kv_row_stride = hd; ap.kv_head_stride = m->cache->max_seq * hd;
-      fused = decode_layer_fuses_attn_wo(m, m->dec[0], ap, m->cache); if (fused) HIPCHK(hipMemsetAsync(m->d_wo_acc, 0, (size_t)c.dec_layers * D * 8, s)); }
+      fused = decode_layer_fuses_attn_wo(m, m->dec[0], ap, m->cache); if (fused) VOXCHK(wo_acc_clear(m, s)); }
     auto launch = [&](int l) -> int32_t {
         if (warm) l = 0;
         const DecLayer& L = m->dec[l % c.dec_layers]; GemvParams p{};
@@ -3938,24 +3953,22 @@ extern "C" int32_t vox_debug_encode_batch(vox_model* m, int32_t n, const float* 
 // ------------------------------------------------------------------------------------------------
 static const int STREAM_SAMPLE_RING = 1 << 16;      // samples held on the device (a tick reads 160 (4 R + 2) + 400 of them)
 static const int STREAM_KEEP_ROWS = 1024;           // adapter rows kept for the re-run of unverified engine steps; a push verifies at least this often
-static const int STREAM_ENGINE_ROWS = 1024;         // the decode engine serves caches of at most this many rows (pw_engine_ready)
 struct vox_stream {
     vox_model* m = nullptr; vox_ctx* ctx = nullptr;
     std::vector<float> t_embed; float gain = 1.0f;
     int cap = 0, max_pos = 0, RC = 0, PC = 0; long left = 0;
     float *kring = nullptr, *vring = nullptr; size_t ring_layer = 0;      // encoder K / V ring: [enc_layers][enc_heads][cap][hd]
-    vox_cache* dec = nullptr;                                             // decoder cache (grows from STREAM_ENGINE_ROWS rows by doubling, up to max_pos)
+    vox_cache* dec = nullptr;                                             // decoder cache (grows from ENGINE_MAX_ROWS rows by doubling, up to max_pos)
     float *samples = nullptr, *audio_keep = nullptr, *ws = nullptr;
     int *tokens = nullptr, *state = nullptr;
-    unsigned* err_pin = nullptr;                                          // pinned host copy of the decode engine's error word
     MelTables mel{};
     // host mirror of the session
     int64_t n_pushed = 0, n_written = 0;      // samples the caller gave; samples in the ring (after finish: + the right pad)
     int pos = 0, ids_out = 0, verified_pos = 0, verified_tap_rows = 0; bool finished = false, eng_unverified = false;
     uint64_t eng_steps = 0, op_steps = 0, verified_eng_steps = 0, verified_op_steps = 0, bytes = 0;
-    EngLayerTab* eng_tab = nullptr; float* part_val = nullptr; int* part_idx = nullptr;      // the decode engine's layer table for the stream's cache, its argmax partials (256)
+    EngBinding eng;      // the decode engine's layer table for the stream's cache, its argmax partials (256), the pinned host copy of its error word
     float* tap = nullptr; int tap_max = 0, tap_rows = 0;
-    int h_state[STRM_WORDS]; int h_pos_word = 0; std::vector<int32_t> h_prefix; std::vector<EngLayerTab> h_tab;
+    int h_state[STRM_WORDS]; int h_pos_word = 0; std::vector<int32_t> h_prefix;
 };
 
 static long stream_spp(int R) { return 640L * R; }      // samples per decoder position: R encoder rows x 4 frames x 160
@@ -3975,7 +3988,7 @@ extern "C" int32_t vox_stream_schedule(size_t n_samples, int32_t finished, int32
 
 static int32_t stream_dec_alloc(vox_stream* st, int rows) {      // a fresh decoder cache of `rows` rows (the old one is freed)
     if (st->dec && st->dec->max_seq == rows) return VOX_OK;
-    if (st->dec) { HIPCHK(hipStreamSynchronize(st->ctx->stream)); cache_unregister(st->dec); (void)hipFree(st->dec->k); (void)hipFree(st->dec->v); delete st->dec; st->dec = nullptr; }
+    if (st->dec) { HIPCHK(hipStreamSynchronize(st->ctx->stream)); cache_release(st->dec); }
     return cache_alloc(st->m, rows, &st->dec);
 }
 // the cache is full and the session may go on: twice the rows (at most max_pos), the rows so far copied over.  Happens at a position, not at a push: cut-independent.
@@ -4003,16 +4016,13 @@ static int32_t stream_load_initial(vox_stream* st) {
     int32_t r = prefix_build(m, st->t_embed.data());
     if (r == VOX_OK && !(P.enc_built && P.dec_built && P.RC == st->RC && P.PC == st->PC)) r = fail(VOX_ERR_HIP, "the prefix state a stream starts from could not be built");
     auto body = [&]() -> int32_t {
-        VOXCHK(stream_dec_alloc(st, std::min(st->max_pos, STREAM_ENGINE_ROWS)));
-        const int H = c.enc_heads, hd = c.enc_head_dim, PC = st->PC, RC = st->RC;
+        VOXCHK(stream_dec_alloc(st, std::min(st->max_pos, ENGINE_MAX_ROWS)));
+        const int H = c.enc_heads, hd = c.enc_head_dim, PC = st->PC, RC = st->RC;      // (== P.PC, P.RC: checked above)
         HIPCHK(launch_stream_ring_init(P.enc_kv, c.enc_layers, RC, H, hd, st->cap, st->kring, st->vring, s));
-        const size_t rows_bytes = (size_t)PC * c.dec_head_dim * 4, n_rows = (size_t)c.dec_layers * c.dec_kv_heads, pitch = (size_t)st->dec->max_seq * c.dec_head_dim * 4;
-        HIPCHK(hipMemcpy2DAsync(st->dec->k, pitch, P.dec_k, rows_bytes, rows_bytes, n_rows, hipMemcpyDeviceToDevice, s));
-        HIPCHK(hipMemcpy2DAsync(st->dec->v, pitch, P.dec_v, rows_bytes, rows_bytes, n_rows, hipMemcpyDeviceToDevice, s));
-        st->dec->len = PC;
-        st->h_tab.resize(c.dec_layers);      // the engine's view of THIS cache: no table is rebuilt (and nothing synchronised) when streams and piecewise callers alternate
-        for (int l = 0; l < c.dec_layers; l++) st->h_tab[l] = EngLayerTab{m->dec[l].attn_norm, m->dec[l].ffn_norm, m->dec[l].ada_mul, st->dec->k + (size_t)l * st->dec->layer_stride, st->dec->v + (size_t)l * st->dec->layer_stride};
-        HIPCHK(hipMemcpyAsync(st->eng_tab, st->h_tab.data(), sizeof(EngLayerTab) * c.dec_layers, hipMemcpyHostToDevice, s));
+        VOXCHK(prefix_rows_into(m, st->dec, s));
+        // the engine's view of THIS cache, in the stream's own binding: no table is rebuilt (and nothing synchronised) when streams, piecewise and offline callers alternate;
+        // uploaded here, behind this function's synchronisation, so that the first step finds its cache bound
+        HIPCHK(engine_tab_enqueue(m, st->eng, st->dec));
         st->h_prefix.assign(VOX_PREFIX_TOKENS, VOX_TOK_STREAMING_PAD); st->h_prefix[0] = VOX_TOK_BOS;
         HIPCHK(hipMemcpyAsync(st->tokens, st->h_prefix.data(), st->h_prefix.size() * 4, hipMemcpyHostToDevice, s));
         std::memset(st->h_state, 0, sizeof st->h_state);
@@ -4032,9 +4042,9 @@ static int32_t stream_load_initial(vox_stream* st) {
 static void stream_release(vox_stream* st) {
     if (!st) return;
     (void)hipSetDevice(st->ctx->device); (void)hipStreamSynchronize(st->ctx->stream);      // never dereferences st->m: a stream may not outlive its model, but freeing it late must not crash
-    if (st->dec) { cache_unregister(st->dec); (void)hipFree(st->dec->k); (void)hipFree(st->dec->v); delete st->dec; }
-    for (void* p : {(void*)st->kring, (void*)st->vring, (void*)st->samples, (void*)st->audio_keep, (void*)st->ws, (void*)st->tokens, (void*)st->state, (void*)st->tap, (void*)st->eng_tab, (void*)st->part_val, (void*)st->part_idx}) if (p) (void)hipFree(p);
-    if (st->err_pin) (void)hipHostFree(st->err_pin);
+    cache_release(st->dec);
+    for (void* p : {(void*)st->kring, (void*)st->vring, (void*)st->samples, (void*)st->audio_keep, (void*)st->ws, (void*)st->tokens, (void*)st->state, (void*)st->tap}) if (p) (void)hipFree(p);
+    binding_release(st->eng);
     delete st;
 }
 
@@ -4064,10 +4074,8 @@ extern "C" int32_t vox_stream_create(vox_model* m, const float* t_embed, float g
     auto A = [&](void** q, size_t n) { if (e == hipSuccess) { e = hipMalloc(q, n); if (e == hipSuccess) st->bytes += n; } };
     A((void**)&st->kring, ring_b); A((void**)&st->vring, ring_b); A((void**)&st->samples, (size_t)STREAM_SAMPLE_RING * 4); A((void**)&st->audio_keep, keep_b);
     A((void**)&st->ws, ws_f * 4); A((void**)&st->tokens, (size_t)(maxp + 2) * 4); A((void**)&st->state, sizeof(int) * STRM_WORDS);
-    A((void**)&st->eng_tab, sizeof(EngLayerTab) * std::max(c.dec_layers, 32)); A((void**)&st->part_val, 256 * 4); A((void**)&st->part_idx, 256 * 4);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&st->err_pin, 8, hipHostMallocDefault);
+    if (e == hipSuccess) e = binding_alloc(m, st->eng, &st->bytes);      // (here, not at the first step: the footprint a stream reports does not depend on what it has done)
     if (e != hipSuccess) { (void)hipGetLastError(); stream_release(st); return fail(VOX_ERR_HIP, "allocating the stream's device state failed: %s", hipGetErrorString(e)); }
-    st->err_pin[0] = st->err_pin[1] = 0u;
     int32_t r = ctx_mel_tables(cx, &st->mel);
     if (r == VOX_OK && hipMemsetAsync(st->samples, 0, (size_t)STREAM_SAMPLE_RING * 4, cx->stream) != hipSuccess) r = fail(VOX_ERR_HIP, "hipMemsetAsync failed");
     if (r == VOX_OK) r = stream_load_initial(st);
@@ -4095,16 +4103,10 @@ static int32_t stream_decode_step(vox_stream* st, float* h, float* logits_row, i
     vox_model* m = st->m; hipStream_t s = st->ctx->stream; vox_cache* kc = st->dec;
     ARGCHK(kc->len == st->pos && st->pos < kc->max_seq, "internal: stream decoder cache at %d, position %d of %d", kc->len, st->pos, kc->max_seq);
     int* pos_word = st->state + STRM_POS;
-    // the engine's conditions on a caller's cache (pw_engine_ready) with the stream's own layer table and argmax partials
-    bool eng = m->eng_ok && m->eng_on && !m->eng_suspended && kc->max_seq <= STREAM_ENGINE_ROWS;
-    if (eng) eng = engine_stream_prepare(m) == VOX_OK && m->eng_ready;
-    if (eng) {      // one launch: the layers against the stream's cache + final norm + lm_head (argmax partials, logits on request)
-        if (m->eng_launches + 16 > (1ull << 25)) { HIPCHK(hipMemsetAsync(m->eng_state, 0, eng_state_bytes(), s)); m->eng_launches = 0; }
-        m->eng_launches += 1;
-        EngParams ep = pw_engine_params(m, kc, h); ep.layers = st->eng_tab; ep.part_val = st->part_val; ep.part_idx = st->part_idx;
-        ep.pos_ptr = pos_word; ep.pos_off = 0; ep.logits_out = logits_row;
-        HIPCHK(launch_decode_engine(ep, s));
-        HIPCHK(launch_stream_advance(st->part_val, st->part_idx, 256, st->tokens, st->state, enc_rows, 4 * enc_rows, st->cap, s));
+    if (engine_bind(m, st->eng, kc)) {      // one launch: the layers against the stream's cache + final norm + lm_head (argmax partials, logits on request)
+        VOXCHK(engine_take_serials(m, 1, s));
+        HIPCHK(launch_decode_engine(engine_params(m, st->eng, kc, h, pos_word, 0, logits_row), s));
+        HIPCHK(launch_stream_advance(st->eng.part_val, st->eng.part_idx, 256, st->tokens, st->state, enc_rows, 4 * enc_rows, st->cap, s));
         st->eng_steps++; st->eng_unverified = true;
     } else {
         VOXCHK(decoder_step_dev(m, h, kc, pos_word, 0));
@@ -4123,35 +4125,31 @@ static float* stream_tap_row(vox_stream* st) {
 // behind the decode-engine steps since the last verification: synchronise, read the engine's error word; a hand-off timeout (the GPU is shared) takes those steps back and
 // runs them again on the per-operator launches from the kept adapter rows -- the caller sees ids, not an error (the policy of transcribe_dev; three strikes switch the engine off)
 static int32_t stream_verify_enqueue(vox_stream* st) {      // the engine's error word on its way to the pinned host word (lands with the next synchronisation)
-    if (!st->eng_unverified) return VOX_OK;
-    EngParams ep{}; eng_state_carve(st->m->eng_state, &ep);
-    HIPCHK(hipMemcpyAsync(st->err_pin, ep.err, 8, hipMemcpyDeviceToHost, st->ctx->stream));
-    return VOX_OK;
+    return st->eng_unverified ? engine_err_enqueue(st->m, st->eng.err_word, st->ctx->stream) : VOX_OK;
 }
 static int32_t stream_settle(vox_stream* st, bool* reran) {      // behind that synchronisation
     vox_model* m = st->m; const vox_model_cfg& c = m->cfg; hipStream_t s = st->ctx->stream;
     if (reran) *reran = false;
-    const unsigned e = st->eng_unverified ? st->err_pin[0] : 0u;
+    const unsigned e = st->eng_unverified ? st->eng.err_word[0] : 0u;
     st->eng_unverified = false;
     if (e) {
-        st->err_pin[0] = 0u; VOXCHK(engine_strike(m));
+        st->eng.err_word[0] = 0u; VOXCHK(engine_strike(m));
         const int p0 = st->verified_pos, p1 = st->pos;
-        fprintf(stderr, "[voxtral_hip] decode engine: hand-off timeout (code %u, workgroup %u), strike %d of 3; the stream's steps %d..%d are decoded again on the per-operator path%s\n",
-                e & 0xff, (e >> 8) & 0xff, m->eng_strikes, p0, p1 - 1, m->eng_strikes >= 3 ? ", the engine is switched off" : "");
+        fprintf(stderr, "[voxtral_hip] decode engine: %s; the stream's steps %d..%d are decoded again on the per-operator path%s\n",
+                engine_timeout_text(e, m->eng_strikes).c_str(), p0, p1 - 1, m->eng_strikes >= 3 ? ", the engine is switched off" : "");
         ARGCHK(p1 - p0 <= STREAM_KEEP_ROWS, "internal: %d unverified stream steps", p1 - p0);
         st->eng_steps = st->verified_eng_steps; st->op_steps = st->verified_op_steps;      // the re-run below counts every step again, on the path it then takes
         st->pos = p0; st->dec->len = p0; st->tap_rows = st->verified_tap_rows; st->h_pos_word = p0;
         HIPCHK(hipMemcpyAsync(st->state + STRM_POS, &st->h_pos_word, 4, hipMemcpyHostToDevice, s));
-        if (m->d_wo_acc) HIPCHK(hipMemsetAsync(m->d_wo_acc, 0, (size_t)c.dec_layers * c.dec_dim * 8, s));
+        VOXCHK(wo_acc_clear(m, s));
         float* h = st->ws;      // (the tick's buffers are free between ticks)
-        m->eng_suspended = true;
+        EngSuspend off(m);
         int32_t r = VOX_OK;
         for (int p = p0; p < p1 && r == VOX_OK; p++) {
             const hipError_t he = launch_stream_embed_kept(m->tok.w, st->tokens, st->audio_keep, STREAM_KEEP_ROWS, c.dec_dim, st->state, h, s);
             if (he != hipSuccess) { r = fail(VOX_ERR_HIP, "launch_stream_embed_kept failed: %s", hipGetErrorString(he)); break; }
             r = stream_decode_step(st, h, stream_tap_row(st), 0);
         }
-        m->eng_suspended = false;
         VOXCHK(r);
         HIPCHK(hipStreamSynchronize(s));
         if (reran) *reran = true;
@@ -4217,11 +4215,11 @@ static int32_t stream_feed(vox_stream* st, const float* src, size_t n, int32_t m
 }
 // what a push / finish does around its ticks: the stream's own Ada scales, clean accumulators, then the ids of the call behind ONE synchronisation
 static int32_t stream_run(vox_stream* st, const float* src, size_t n, int32_t mem_kind, int target, int32_t* out_ids, int32_t* n_ids) {
-    vox_model* m = st->m; const vox_model_cfg& c = m->cfg; hipStream_t s = st->ctx->stream;
+    vox_model* m = st->m; hipStream_t s = st->ctx->stream;
     const int due = target - st->pos;
     if (m->pw_pend_rows > 0) VOXCHK(pw_sync(m));      // unverified engine steps of the piecewise surface share the engine's error word: settled first
     VOXCHK(vox_model_set_t_embed(m, st->t_embed.data()));
-    if (due > 0 && m->d_wo_acc) HIPCHK(hipMemsetAsync(m->d_wo_acc, 0, (size_t)c.dec_layers * c.dec_dim * 8, s));
+    if (due > 0) VOXCHK(wo_acc_clear(m, s));
     VOXCHK(stream_feed(st, src, n, mem_kind, target));
     int32_t* ids_dev = st->tokens + VOX_PREFIX_TOKENS + st->ids_out;
     VOXCHK(stream_verify_enqueue(st));
