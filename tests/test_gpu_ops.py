@@ -353,3 +353,65 @@ def test_q4_gemm_big_kernel_matches_tile_kernel(pkg, orc, ctx, monkeypatch, m, k
     ref = orc.q4_matmul(q, n, k, x[:, rows])
     assert np.abs(big[:, rows] - ref).max() < 2e-5 * scale
     w.close()
+
+
+ARGMAX_RULE_V = [1, 3, 4, 5, 63, 64, 1023, 1024, 1025, 4099, 131072]
+
+
+def _argmax_rule_rows(V):
+    """[(case, row[V], planted winner)]: seeded normal background clipped to 3.0, every maximum planted as an exact float, so nothing hangs on a random near-tie."""
+    rng = np.random.default_rng(V)
+    rows = []
+
+    def case(name, plant, want, negative=False):
+        r = np.minimum(rng.standard_normal(V), 3.0).astype(np.float32)
+        if negative:
+            r = -np.abs(r) - np.float32(1.0)
+        for i, x in plant.items():
+            r[i] = x
+        rows.append((name, r, want))
+
+    case("maximum in the first column", {0: 7.0}, 0)
+    case("maximum in the last column", {V - 1: 7.0}, V - 1)
+    if V % 4 and V > 4:
+        case("maximum in the V % 4 leftovers", {V - V % 4: 7.0}, V - V % 4)
+    if V > 4096:      # 1024 threads x float4: columns 4092..4095 are the last thread's first sweep, 4096 is thread 0's second
+        case("equal maxima at 4093 and 4096: last thread of the last wave against thread 0's second sweep", {4093: 7.0, 4096: 7.0}, 4093)
+        case("equal maxima at 0 and 4096: one thread, two sweeps", {0: 7.0, 4096: 7.0}, 0)
+    if V >= 2:
+        case("equal maxima in the last two columns", {V - 2: 7.0, V - 1: 7.0}, V - 2)
+        case("+0.0 below -0.0", {V // 4: 0.0, V - 1: -0.0}, V // 4, negative=True)
+        case("-0.0 below +0.0", {V // 4: -0.0, V - 1: 0.0}, V // 4, negative=True)
+        case("NaN in column 0, finite maximum elsewhere", {0: np.nan, V // 2: 7.0}, V // 2)
+        case("NaN behind the maximum", {(V - 1) // 2: 7.0, V - 1: np.nan}, (V - 1) // 2)
+    case("+inf is the maximum", {V // 2: np.inf}, V // 2)
+    rows.append(("all NaN", np.full(V, np.nan, dtype=np.float32), 0))
+    rows.append(("all -inf", np.full(V, -np.inf, dtype=np.float32), 0))
+    return rows
+
+
+def test_argmax_rows_rule(pkg, ctx):
+    """The greedy argmax rule (csrc/vox_kernels.h, above launch_argmax_final) through vox_argmax_rows, device rows (the shared row scan and workgroup reduction) and host
+    rows: the largest value wins, the lowest index among equal values, a NaN never, 0 when nothing wins -- np.argmax with NaN replaced by -inf, asserted exactly.  Three
+    rows per call, every case in each of the three places where V % 4 != 0: rows 1 and 2 then start off a 16-byte boundary and take the single-column scan."""
+    import ctypes as C
+    n_calls = 0
+    for V in ARGMAX_RULE_V:
+        cases = _argmax_rule_rows(V)
+        cases += cases[:(-len(cases)) % 3]      # whole calls of three rows: the first cases once more
+        for rot in range(3 if V % 4 else 1):
+            order = cases[rot:] + cases[:rot]
+            for c0 in range(0, len(order), 3):
+                names = [n for n, _, _ in order[c0:c0 + 3]]
+                x = np.ascontiguousarray(np.stack([r for _, r, _ in order[c0:c0 + 3]]))
+                ref = np.argmax(np.where(np.isnan(x), -np.inf, x), axis=1)
+                assert ref.tolist() == [w for _, _, w in order[c0:c0 + 3]], (V, names)      # the planted winner is the reference's
+                dx = ctx.upload(x)
+                dev = pkg.argmax_rows_dev(ctx, dx, 3, V)
+                ctx.free(dx)
+                host = np.zeros(3, dtype=np.int32)
+                pkg._lib.check(pkg.lib().vox_argmax_rows(ctx.h, x.ctypes.data_as(C.c_void_p), 3, V, host.ctypes.data_as(C.c_void_p), 0))
+                assert dev.tolist() == ref.tolist(), ("device", V, rot, names)
+                assert host.tolist() == ref.tolist(), ("host", V, rot, names)
+                n_calls += 1
+    print(f"argmax rule: {n_calls} calls of 3 rows, device and host")

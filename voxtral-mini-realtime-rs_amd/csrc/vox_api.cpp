@@ -3554,11 +3554,17 @@ extern "C" int32_t vox_lm_head_ex(vox_model* m, const float* hidden, int32_t M, 
 }
 extern "C" int32_t vox_lm_head(vox_model* m, const float* hidden, int32_t M, float* logits) { return vox_lm_head_ex(m, hidden, M, logits, VOX_MEM_HOST); }
 
+// the device rule on a host row (vox_kernels.h, above launch_argmax_final): NaN never wins, lowest index on ties, 0 when nothing wins
+static int argmax_row_host(const float* row, int V) {
+    float v = -INFINITY; int b = 0x7fffffff;
+    for (int i = 0; i < V; i++) if (row[i] > v || (row[i] == v && i < b)) { v = row[i]; b = i; }
+    return b == 0x7fffffff ? 0 : b;
+}
 // `logits.argmax(2)` + the scalar read-back (e2e_bench.rs:219-220): ids always host; synchronises the stream
 extern "C" int32_t vox_argmax_rows(vox_ctx* c, const float* logits, int32_t M, int32_t V, int32_t* ids, int32_t mem_kind) {
     ARGCHK(c && logits && ids && M > 0 && V > 0, "bad argument"); VOXCHK(ctx_bind(c));
     if (mem_kind != VOX_MEM_DEVICE) {
-        for (int r = 0; r < M; r++) { const float* row = logits + (size_t)r * V; int b = 0; for (int i = 1; i < V; i++) if (row[i] > row[b]) b = i; ids[r] = b; }
+        for (int r = 0; r < M; r++) ids[r] = argmax_row_host(logits + (size_t)r * V, V);
         return VOX_OK;
     }
     DevBuf di; HIPCHK(di.alloc_pooled(c, (size_t)M * 4));

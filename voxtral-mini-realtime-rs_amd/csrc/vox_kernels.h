@@ -201,7 +201,12 @@ hipError_t launch_group_scale(const unsigned* group_max, const int* unit_group, 
 // h[i][:] = (audio ? audio[(a_base+i)][:] : 0) + dequant(tok[ids[id_base+i]]) ; bases add *pos_ptr if given
 hipError_t launch_embed(Q4W tok, const int* ids, int n, const float* audio, int D, const int* pos_ptr, int id_off,
                         int a_off, float* out, hipStream_t s);
-// final argmax over per-workgroup partials (lowest index wins ties); writes tokens[*pos_ptr+tok_off], then *pos_ptr += inc
+// ---- greedy argmax, the rule of every decode form: the largest logit wins, the lowest index wins among equal values (+0.0 == -0.0), and a NaN never wins.  Value
+// descending, index ascending is a strict total order over the non-NaN candidates, so every reduction tree yields the same (value, index) pair.  When nothing wins (a row
+// of NaN and -inf only) the index is the sentinel 0x7fffffff: the kernels that embed the token read row 0 for it and store it as it is, launch_argmax_rows stores 0.  The launches below
+// and the EPI_ARGMAX epilogues share one device implementation (argmax_take and block_argmax, vox_kernels.hip); the persistent engines keep their in-launch copies of the
+// same rule (comm_next_input and the per-CU partial, vox_engine.hip and vox_engine_b16.hip).
+// final argmax over per-workgroup partials; writes tokens[*pos_ptr+tok_off], then *pos_ptr += inc
 hipError_t launch_argmax_final(const float* part_val, const int* part_idx, int n_parts, int* tokens, int* pos_ptr,
                                int tok_off, int inc, hipStream_t s);
 // fused decode-step tail: tokens[*pos+1] = argmax(partials); *pos += 1; h = audio[*pos] + dequant(tok[tokens[*pos]])
@@ -242,7 +247,7 @@ hipError_t launch_batch_tap(const BatchTapParams& p, int n_rows, hipStream_t s);
 hipError_t launch_occupy(int workgroups, int micros, hipStream_t s);      // test hook: spin `workgroups` x 1024 threads for `micros` us
 hipError_t launch_add_rows(const float* a, const float* b, float* out, long n, hipStream_t s);
 hipError_t launch_gelu(float* x, long n, hipStream_t s);
-hipError_t launch_argmax_rows(const float* x, int rows, int V, int* out, hipStream_t s);      // out[r] = argmax of row r (lowest index wins ties)
+hipError_t launch_argmax_rows(const float* x, int rows, int V, int* out, hipStream_t s);      // out[r] = argmax of row r (0 when nothing wins)
 
 // ---- persistent decode-step engine (vox_engine.hip): the whole single-stream decode step -- 26 layers + final norm + tied lm_head + argmax
 // partials -- as ONE launch of 256 workgroups (one per CU) x 8 waves: wave 0 streams this CU's slice of every Q4 operator, in consumption order,
@@ -382,7 +387,7 @@ hipError_t launch_stream_ring_init(const float* kv, int layers, int rows, int n_
 hipError_t launch_stream_embed(Q4W tok, const int* tokens, const float* audio_row, float* audio_keep, int keep_rows, int D, const int* state, float* h, hipStream_t s);
 // the same input from the kept row (the re-run)
 hipError_t launch_stream_embed_kept(Q4W tok, const int* tokens, const float* audio_keep, int keep_rows, int D, const int* state, float* h, hipStream_t s);
-// tokens[STRM_POS + 1] = argmax over the lm_head partials (lowest index wins ties), then the state advances by one tick (enc_rows encoder rows, frames mel frames;
+// tokens[STRM_POS + 1] = argmax over the lm_head partials, then the state advances by one tick (enc_rows encoder rows, frames mel frames;
 // enc_rows = 0: a decode-only re-run moves STRM_POS alone)
 hipError_t launch_stream_advance(const float* part_val, const int* part_idx, int n_parts, int* tokens, int* state, int enc_rows, int frames, int cap, hipStream_t s);
 

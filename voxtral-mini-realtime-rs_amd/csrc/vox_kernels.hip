@@ -100,6 +100,47 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 // sum over aligned groups of 8 lanes (result in every lane of the group)
 __device__ __forceinline__ float group8_sum(float v) { v += dpp_mov<0xB1>(v); v += dpp_mov<0x4E>(v); v += dpp_mov<0x141>(v); return v; }
+// ---- greedy argmax (the rule: vox_kernels.h, above launch_argmax_final).  A running best starts at the sentinel (-inf, 0x7fffffff), which loses to every
+// candidate that can win and is what comes out when none can; every comparison of the rule in this file is argmax_take.
+// the candidate (x, i) replaces the best (v, idx) when it is larger, or equal at a lower index; a NaN compares false both ways and is never taken.  ASCENDING: the
+// caller's i only grows from one call to the next, so an equal value never has the lower index and that half of the test is left out -- the scan of a 131 072-column
+// row is then one compare and two selects per column (the full test compiles to masked branches there, several times the instructions).
+template <bool ASCENDING = false>
+__device__ __forceinline__ void argmax_take(float& v, int& idx, float x, int i) {
+    if (x > v || (!ASCENDING && x == v && i < idx)) { v = x; idx = i; }
+}
+// this thread's best over the lm_head partials (pv[i], pi[i]), i = threadIdx.x, threadIdx.x + NT, ...  (Both scans keep the running best in locals and hand it out at
+// the end: updated through the references, hipcc carries a second copy of the value through the row loop, a third select per column.)
+template <int NT>
+__device__ __forceinline__ void argmax_scan_partials(const float* __restrict__ pv, const int* __restrict__ pi, int n, float& v, int& idx) {
+    float bv = -INFINITY; int bi = 0x7fffffff;
+    for (int i = threadIdx.x; i < n; i += NT) argmax_take(bv, bi, pv[i], pi[i]);
+    v = bv; idx = bi;
+}
+// this thread's best over its columns of one logits row [V]: float4 loads when the row starts on a 16-byte boundary (a row of a [rows][V] matrix does for every row
+// only while V % 4 == 0), single columns otherwise and for the V % 4 leftovers.  Both loops walk up, the second above the first: ascending columns throughout.
+template <int NT>
+__device__ __forceinline__ void argmax_scan_row(const float* __restrict__ row, int V, float& v, int& idx) {
+    float bv = -INFINITY; int bi = 0x7fffffff;
+    const int V4 = ((reinterpret_cast<uintptr_t>(row) & 15) == 0) ? V >> 2 : 0;
+    for (int i = threadIdx.x; i < V4; i += NT) {
+        const float4 q = reinterpret_cast<const float4*>(row)[i];
+        argmax_take<true>(bv, bi, q.x, 4 * i); argmax_take<true>(bv, bi, q.y, 4 * i + 1); argmax_take<true>(bv, bi, q.z, 4 * i + 2); argmax_take<true>(bv, bi, q.w, 4 * i + 3);
+    }
+    for (int i = 4 * V4 + threadIdx.x; i < V; i += NT) argmax_take<true>(bv, bi, row[i], i);
+    v = bv; idx = bi;
+}
+// the workgroup's best of one (v, idx) per thread, NT threads (whole waves, at most 1024), all of them calling: xor shuffles inside the wave, one LDS entry per wave
+// (sv, si: NT / 64 entries each, the caller's to reuse behind its next barrier), one barrier.  Only thread 0 holds the result.
+template <int NT>
+__device__ __forceinline__ void block_argmax(float& v, int& idx, float* sv, int* si) {
+    static_assert(NT % 64 == 0 && NT <= 1024, "whole waves, at most 16");
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const float ov = __shfl_xor(v, o); const int oi = __shfl_xor(idx, o); argmax_take(v, idx, ov, oi); }
+    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = v; si[threadIdx.x >> 6] = idx; }
+    __syncthreads();
+    if (threadIdx.x == 0) for (int w = 1; w < NT / 64; w++) argmax_take(v, idx, sv[w], si[w]);
+}
 __device__ __forceinline__ float f16_bits_to_f32(uint16_t h) { return __half2float(__ushort_as_half(h)); }
 __device__ __forceinline__ float gelu_f(float x) { return x * 0.5f * (1.0f + erff(x / 1.41421356237309504880f)); }
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + expf(-x)); }
@@ -315,7 +356,7 @@ __global__ __launch_bounds__(64 * NWV, 1) void q4_gemv_kernel(const GemvParams p
     }
     const float rstd = PRO != PRO_NONE ? 1.0f / sqrtf(ssq / (float)K + p.eps) : 1.0f;
 
-    float best = -INFINITY; int best_i = 0x7fffffff;   // EPI_ARGMAX running (max, first index) of this wave
+    int best_i = 0x7fffffff; float best = -INFINITY;   // EPI_ARGMAX running (max, first index) of this wave
     constexpr bool ROPE = EPI == EPI_ROPE_KV;
     const int pos = ROPE ? (p.pos_ptr ? *p.pos_ptr : 0) + p.pos_off : 0;
 
@@ -379,7 +420,7 @@ __global__ __launch_bounds__(64 * NWV, 1) void q4_gemv_kernel(const GemvParams p
             _Pragma("unroll") for (int r = 0; r < R; r++) {                                                            \
                 const int n = row0 + r;                                                                                \
                 if (p.out && lane == r) p.out[(size_t)y * p.out_stride + n] = acc[r];                                  \
-                if (acc[r] > best || (acc[r] == best && n < best_i)) { best = acc[r]; best_i = n; }                    \
+                argmax_take(best, best_i, acc[r], n);                                                                  \
             }                                                                                                          \
         }                                                                                                              \
     }
@@ -403,10 +444,7 @@ __global__ __launch_bounds__(64 * NWV, 1) void q4_gemv_kernel(const GemvParams p
         __syncthreads();
         if (tid == 0) {
             float bv = red[NWV]; int bidx = reinterpret_cast<int*>(red)[2 * NWV];
-            for (int wv = 1; wv < NWV; wv++) {
-                const float v = red[NWV + wv]; const int ii = reinterpret_cast<int*>(red)[2 * NWV + wv];
-                if (v > bv || (v == bv && ii < bidx)) { bv = v; bidx = ii; }
-            }
+            for (int wv = 1; wv < NWV; wv++) argmax_take(bv, bidx, red[NWV + wv], reinterpret_cast<int*>(red)[2 * NWV + wv]);
             p.part_val[(size_t)y * gridDim.x + blockIdx.x] = bv;
             p.part_idx[(size_t)y * gridDim.x + blockIdx.x] = bidx;
         }
@@ -633,7 +671,7 @@ __global__ __launch_bounds__(256) VOX_NO_PK_F32 void dense_gemv_kernel(const Gem
         }
     }
     __syncthreads();
-    float best = -INFINITY; int best_i = 0x7fffffff;
+    int best_i = 0x7fffffff; float best = -INFINITY;
     const int pos = (EPI == EPI_ROPE_KV) ? (p.pos_ptr ? *p.pos_ptr : 0) + p.pos_off : 0;
     const int n_groups = N / R, n_waves = gridDim.x * 4;
     for (int g = blockIdx.x * 4 + wave; g < n_groups; g += n_waves) {
@@ -696,7 +734,7 @@ __global__ __launch_bounds__(256) VOX_NO_PK_F32 void dense_gemv_kernel(const Gem
             for (int r = 0; r < R; r++) {
                 const int n = row0 + r;
                 if (p.out && lane == r) p.out[(size_t)y * p.out_stride + n] = acc[r];
-                if (acc[r] > best || (acc[r] == best && n < best_i)) { best = acc[r]; best_i = n; }
+                argmax_take(best, best_i, acc[r], n);
             }
         }
     }
@@ -705,10 +743,7 @@ __global__ __launch_bounds__(256) VOX_NO_PK_F32 void dense_gemv_kernel(const Gem
         __syncthreads();
         if (tid == 0) {
             float bv = red[4]; int bidx = reinterpret_cast<int*>(red)[8];
-            for (int wv = 1; wv < 4; wv++) {
-                const float v = red[4 + wv]; const int ii = reinterpret_cast<int*>(red)[8 + wv];
-                if (v > bv || (v == bv && ii < bidx)) { bv = v; bidx = ii; }
-            }
+            for (int wv = 1; wv < 4; wv++) argmax_take(bv, bidx, red[4 + wv], reinterpret_cast<int*>(red)[8 + wv]);
             p.part_val[(size_t)y * gridDim.x + blockIdx.x] = bv;
             p.part_idx[(size_t)y * gridDim.x + blockIdx.x] = bidx;
         }
@@ -3822,25 +3857,14 @@ hipError_t launch_embed(Q4W tok, const int* ids, int n, const float* audio, int 
 
 __global__ __launch_bounds__(256) void argmax_final_kernel(const float* __restrict__ pv, const int* __restrict__ pi, int n_parts,
                                                            int* __restrict__ tokens, int* __restrict__ pos_ptr, int tok_off, int inc) {
-    __shared__ float bv[256];
-    __shared__ int bi[256];
-    float v = -INFINITY; int idx = 0x7fffffff;
-    for (int i = threadIdx.x; i < n_parts; i += 256) {
-        const float x = pv[i]; const int ii = pi[i];
-        if (x > v || (x == v && ii < idx)) { v = x; idx = ii; }
-    }
-    bv[threadIdx.x] = v; bi[threadIdx.x] = idx;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) {
-            const float x = bv[threadIdx.x + s]; const int ii = bi[threadIdx.x + s];
-            if (x > bv[threadIdx.x] || (x == bv[threadIdx.x] && ii < bi[threadIdx.x])) { bv[threadIdx.x] = x; bi[threadIdx.x] = ii; }
-        }
-        __syncthreads();
-    }
+    __shared__ float bv[4];
+    __shared__ int bi[4];
+    float v; int idx;
+    argmax_scan_partials<256>(pv, pi, n_parts, v, idx);
+    block_argmax<256>(v, idx, bv, bi);
     if (threadIdx.x == 0) {
         const int base = pos_ptr ? *pos_ptr : 0;
-        tokens[base + tok_off] = bi[0];
+        tokens[base + tok_off] = idx;
         if (pos_ptr && inc) *pos_ptr = base + inc;
     }
 }
@@ -3855,26 +3879,15 @@ hipError_t launch_argmax_final(const float* pv, const int* pi, int n_parts, int*
 __global__ __launch_bounds__(256) void argmax_embed_kernel(const float* __restrict__ pv, const int* __restrict__ pi, int n_parts,
                                                            int* __restrict__ tokens, int* __restrict__ pos_ptr, Q4W tok,
                                                            const float* __restrict__ audio, int D, float* __restrict__ h) {
-    __shared__ float bv[256];
-    __shared__ int bi[256];
+    __shared__ float bv[4];
+    __shared__ int bi[4];
     __shared__ int s_tok, s_cur;
-    float v = -INFINITY; int idx = 0x7fffffff;
-    for (int i = threadIdx.x; i < n_parts; i += 256) {
-        const float x = pv[i]; const int ii = pi[i];
-        if (x > v || (x == v && ii < idx)) { v = x; idx = ii; }
-    }
-    bv[threadIdx.x] = v; bi[threadIdx.x] = idx;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if (threadIdx.x < st) {
-            const float x = bv[threadIdx.x + st]; const int ii = bi[threadIdx.x + st];
-            if (x > bv[threadIdx.x] || (x == bv[threadIdx.x] && ii < bi[threadIdx.x])) { bv[threadIdx.x] = x; bi[threadIdx.x] = ii; }
-        }
-        __syncthreads();
-    }
+    float v; int idx;
+    argmax_scan_partials<256>(pv, pi, n_parts, v, idx);
+    block_argmax<256>(v, idx, bv, bi);
     if (threadIdx.x == 0) {
         const int cur = *pos_ptr + 1;
-        tokens[cur] = bi[0]; *pos_ptr = cur; s_tok = bi[0]; s_cur = cur;
+        tokens[cur] = idx; *pos_ptr = cur; s_tok = idx; s_cur = cur;
     }
     __syncthreads();
     embed_row(tok, s_tok, audio + (size_t)s_cur * D, h, D);
@@ -3921,59 +3934,51 @@ hipError_t launch_rope_kv_batch(float* qkv, int n, int stride, int n_q, int n_kv
     return hipGetLastError();
 }
 
-// one workgroup per sequence: argmax of its logits row (lowest index wins ties) -> tokens[s][pos+1], pos[s]++ (until the
+// the first layer's RMSNorm folded into the tail of a batched step: XF planes of the workgroup's input row hrow[D] times gamma (row `row` of its 16-row group's planes)
+// and the row's sum of squares -> ssq_out[row] (one partial): a strided sum per thread, wave_sum, then thread 0 adds the waves in order.  All threads call; wsum: one
+// entry per wave.
+__device__ __forceinline__ void xf_row_ssq(const float* __restrict__ hrow, const float* __restrict__ gamma, int D, uint16_t* __restrict__ xf, int row,
+                                           float* __restrict__ ssq_out, float* wsum) {
+    const int nt = blockDim.x;
+    __syncthreads();      // hrow was written by the whole workgroup
+    float ss = 0.f;
+    for (int c = threadIdx.x; c < (D >> 2); c += nt) {
+        float4 v = reinterpret_cast<const float4*>(hrow)[c]; const float4 gm = reinterpret_cast<const float4*>(gamma)[c];
+        ss += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+        v.x *= gm.x; v.y *= gm.y; v.z *= gm.z; v.w *= gm.w;
+        xf_store4(xf, D, row, 4 * c, v);
+    }
+    ss = wave_sum(ss);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = ss;
+    __syncthreads();
+    if (threadIdx.x == 0) { float a = 0.f; for (int w = 0; w < (nt >> 6); w++) a += wsum[w]; ssq_out[row] = a; }
+}
+
+// one workgroup per sequence: argmax of its logits row -> tokens[s][pos+1], pos[s]++ (until the
 // sequence's last position), then the next step's input h[s] = audio[s][pos] + embed(tokens[s][pos]).
 __global__ __launch_bounds__(1024) void argmax_embed_batch_kernel(const float* __restrict__ logits, int vocab, int* __restrict__ tokens,
                                                                  int tok_stride, int* __restrict__ pos, const int* __restrict__ seq_len, Q4W tok,
                                                                  const float* __restrict__ audio, long audio_seq_stride, int D, float* __restrict__ h,
                                                                  uint16_t* __restrict__ xf, const float* __restrict__ xf_w, float* __restrict__ ssq_out,
                                                                  long xf_group_stride, int ssq_group_stride, const long* __restrict__ audio_off) {
-    __shared__ float bv[1024];
-    __shared__ int bi[1024];
+    __shared__ float bv[16];
+    __shared__ int bi[16];
     __shared__ int s_tok, s_cur;
-    const int sq = blockIdx.x, nt = blockDim.x;
-    const float* lg = logits + (size_t)sq * vocab;
-    float v = -INFINITY; int idx = 0x7fffffff;
-    const int v4 = vocab >> 2;
-    for (int i = threadIdx.x; i < v4; i += nt) {            // ascending i per thread: first max wins
-        const float4 x = reinterpret_cast<const float4*>(lg)[i];
-        if (x.x > v) { v = x.x; idx = 4 * i; } if (x.y > v) { v = x.y; idx = 4 * i + 1; }
-        if (x.z > v) { v = x.z; idx = 4 * i + 2; } if (x.w > v) { v = x.w; idx = 4 * i + 3; }
-    }
-    for (int i = 4 * v4 + threadIdx.x; i < vocab; i += nt) { const float x = lg[i]; if (x > v) { v = x; idx = i; } }
-    bv[threadIdx.x] = v; bi[threadIdx.x] = idx;
-    __syncthreads();
-    for (int st = nt >> 1; st > 0; st >>= 1) {
-        if (threadIdx.x < st) {
-            const float x = bv[threadIdx.x + st]; const int ii = bi[threadIdx.x + st];
-            if (x > bv[threadIdx.x] || (x == bv[threadIdx.x] && ii < bi[threadIdx.x])) { bv[threadIdx.x] = x; bi[threadIdx.x] = ii; }
-        }
-        __syncthreads();
-    }
+    const int sq = blockIdx.x;
+    float v; int idx;
+    argmax_scan_row<1024>(logits + (size_t)sq * vocab, vocab, v, idx);
+    block_argmax<1024>(v, idx, bv, bi);
     if (threadIdx.x == 0) {
         int cur = pos[sq];
-        if (cur + 1 < seq_len[sq]) { cur += 1; tokens[(size_t)sq * tok_stride + cur] = bi[0]; pos[sq] = cur; }   // finished sequences idle in place
+        if (cur + 1 < seq_len[sq]) { cur += 1; tokens[(size_t)sq * tok_stride + cur] = idx; pos[sq] = cur; }   // finished sequences idle in place
         s_cur = cur; s_tok = tokens[(size_t)sq * tok_stride + cur];
     }
     __syncthreads();
     embed_row(tok, s_tok, audio + (audio_off ? (size_t)audio_off[sq] : (size_t)sq * audio_seq_stride) + (size_t)s_cur * D, h + (size_t)sq * D, D);      // audio_off: packed audio rows (no common stride)
     if (xf) {     // the first layer's RMSNorm folded in: XF planes of h * gamma and the row's sum of squares (one partial);
         // sequences are processed in groups of 16 rows, each group with its own XF planes / partial-sum block
-        xf += (size_t)(sq >> 4) * xf_group_stride; ssq_out += (size_t)(sq >> 4) * ssq_group_stride;
-        const int row = sq & 15;
-        __syncthreads();
-        float ss = 0.f;
-        for (int c = threadIdx.x; c < (D >> 2); c += nt) {
-            float4 v = reinterpret_cast<const float4*>(h + (size_t)sq * D)[c]; const float4 gm = reinterpret_cast<const float4*>(xf_w)[c];
-            ss += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
-            v.x *= gm.x; v.y *= gm.y; v.z *= gm.z; v.w *= gm.w;
-            xf_store4(xf, D, row, 4 * c, v);
-        }
-        ss = wave_sum(ss);
-        __syncthreads();
-        if ((threadIdx.x & 63) == 0) bv[threadIdx.x >> 6] = ss;
-        __syncthreads();
-        if (threadIdx.x == 0) { float a = 0.f; for (int w = 0; w < (nt >> 6); w++) a += bv[w]; ssq_out[row] = a; }
+        xf_row_ssq(h + (size_t)sq * D, xf_w, D, xf + (size_t)(sq >> 4) * xf_group_stride, sq & 15, ssq_out + (size_t)(sq >> 4) * ssq_group_stride, bv);
     }
 }
 hipError_t launch_argmax_embed_batch(const float* logits, int n, int vocab, int* tokens, int tok_stride, int* pos, const int* seq_len, Q4W tok,
@@ -3990,38 +3995,23 @@ hipError_t launch_argmax_embed_batch(const float* logits, int n, int vocab, int*
 // = the utterance's first decode input h0 (audio[38] + embed(first token), computed behind its prefill).  No host round trip, no idle step: the groups of a ragged
 // batch stay full until the queues run dry.  One workgroup per slot; `init` = 1: no argmax, every slot takes the head of its queue.
 __global__ __launch_bounds__(1024) void argmax_embed_slots_kernel(const SlotStepParams p) {
-    __shared__ float bv[1024];
-    __shared__ int bi[1024];
+    __shared__ float bv[16];
+    __shared__ int bi[16];
     __shared__ int s_tok, s_cur, s_c, s_mode;      // mode 0: next position of the same utterance; 1: the slot switched to utterance s_c; 2: the slot's queue is empty
     const int sl = blockIdx.x, nt = blockDim.x, D = p.D;
     const int c = p.init ? -1 : p.slot_clip[sl];
     if (!p.init && c < 0) return;                   // idle slot (uniform per workgroup): its input row and XF rows stay zero
-    if (!p.init) {
-        const float* lg = p.logits + (size_t)sl * p.vocab;
-        float v = -INFINITY; int idx = 0x7fffffff;
-        const int v4 = p.vocab >> 2;
-        for (int i = threadIdx.x; i < v4; i += nt) {            // ascending i per thread: first max wins (lowest index on ties, like argmax_embed_batch_kernel)
-            const float4 x = reinterpret_cast<const float4*>(lg)[i];
-            if (x.x > v) { v = x.x; idx = 4 * i; } if (x.y > v) { v = x.y; idx = 4 * i + 1; }
-            if (x.z > v) { v = x.z; idx = 4 * i + 2; } if (x.w > v) { v = x.w; idx = 4 * i + 3; }
-        }
-        for (int i = 4 * v4 + threadIdx.x; i < p.vocab; i += nt) { const float x = lg[i]; if (x > v) { v = x; idx = i; } }
-        bv[threadIdx.x] = v; bi[threadIdx.x] = idx;
-        __syncthreads();
-        for (int st = nt >> 1; st > 0; st >>= 1) {
-            if (threadIdx.x < st) {
-                const float x = bv[threadIdx.x + st]; const int ii = bi[threadIdx.x + st];
-                if (x > bv[threadIdx.x] || (x == bv[threadIdx.x] && ii < bi[threadIdx.x])) { bv[threadIdx.x] = x; bi[threadIdx.x] = ii; }
-            }
-            __syncthreads();
-        }
+    float v; int idx;
+    if (!p.init) {      // (uniform per launch)
+        argmax_scan_row<1024>(p.logits + (size_t)sl * p.vocab, p.vocab, v, idx);
+        block_argmax<1024>(v, idx, bv, bi);
     }
     if (threadIdx.x == 0) {
         bool take_next = p.init != 0; int q = -1;
         if (!p.init) {
             const int cur = p.pos[sl] + 1;            // the position the step just produced (pos = index of the last token written)
-            p.tokens[(size_t)c * p.tok_stride + cur] = bi[0];
-            if (cur + 1 < p.clip_len[c]) { p.pos[sl] = cur; s_cur = cur; s_tok = bi[0]; s_c = c; s_mode = 0; }
+            p.tokens[(size_t)c * p.tok_stride + cur] = idx;
+            if (cur + 1 < p.clip_len[c]) { p.pos[sl] = cur; s_cur = cur; s_tok = idx; s_c = c; s_mode = 0; }
             else { take_next = true; q = p.slot_qpos[sl]; }
         }
         if (take_next) {
@@ -4038,23 +4028,8 @@ __global__ __launch_bounds__(1024) void argmax_embed_slots_kernel(const SlotStep
         const float4* src = s_mode == 1 ? reinterpret_cast<const float4*>(p.h0 + (size_t)s_c * D) : nullptr;
         for (int i = threadIdx.x; i < (D >> 2); i += nt) reinterpret_cast<float4*>(hrow)[i] = src ? src[i] : make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    if (p.xf) {     // the first layer's RMSNorm folded in, exactly as argmax_embed_batch_kernel does for its rows (group = slot / 16, row = slot % 16)
-        uint16_t* xf = p.xf + (size_t)(sl >> 4) * p.xf_group_stride; float* ssq_out = p.ssq_out + (size_t)(sl >> 4) * p.ssq_group_stride;
-        const int row = sl & 15;
-        __syncthreads();
-        float ss = 0.f;
-        for (int k = threadIdx.x; k < (D >> 2); k += nt) {
-            float4 v = reinterpret_cast<const float4*>(hrow)[k]; const float4 gm = reinterpret_cast<const float4*>(p.xf_w)[k];
-            ss += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
-            v.x *= gm.x; v.y *= gm.y; v.z *= gm.z; v.w *= gm.w;
-            xf_store4(xf, D, row, 4 * k, v);
-        }
-        ss = wave_sum(ss);
-        __syncthreads();
-        if ((threadIdx.x & 63) == 0) bv[threadIdx.x >> 6] = ss;
-        __syncthreads();
-        if (threadIdx.x == 0) { float a = 0.f; for (int w = 0; w < (nt >> 6); w++) a += bv[w]; ssq_out[row] = a; }
-    }
+    if (p.xf)      // as argmax_embed_batch_kernel for its rows: group = slot / 16, row = slot % 16
+        xf_row_ssq(hrow, p.xf_w, D, p.xf + (size_t)(sl >> 4) * p.xf_group_stride, sl & 15, p.ssq_out + (size_t)(sl >> 4) * p.ssq_group_stride, bv);
 }
 hipError_t launch_argmax_embed_slots(const SlotStepParams& p, int n_slots, hipStream_t s) {
     if (n_slots <= 0 || !p.slot_clip || !p.slot_qpos || !p.queue || !p.pos || !p.kv_row || !p.h || !p.h0 || !p.tokens || !p.clip_len || !p.audio || !p.audio_off || (!p.init && !p.logits) || (p.D & 3)) return hipErrorInvalidValue;
@@ -4166,32 +4141,15 @@ hipError_t launch_add_rows(const float* a, const float* b, float* out, long n, h
 __global__ void gelu_kernel(float* __restrict__ x, long n) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) x[i] = gelu_f(x[i]);
 }
-// argmax of every row of x [rows][V] (lowest index wins ties, NaN never wins): `logits.argmax(2)` of the piecewise decode loop (bin/e2e_bench.rs:219).  One
+// argmax of every row of x [rows][V]: `logits.argmax(2)` of the piecewise decode loop (bin/e2e_bench.rs:219).  One
 // 1024-thread workgroup per row, float4 loads; a 131 072-column row is 512 KB = a few microseconds.
 __global__ __launch_bounds__(1024) void argmax_rows_kernel(const float* __restrict__ x, int V, int* __restrict__ out) {
     __shared__ float bv[16];
     __shared__ int bi[16];
-    const float* row = x + (size_t)blockIdx.x * V;
-    float v = -INFINITY; int idx = 0x7fffffff;
-    const int V4 = ((reinterpret_cast<uintptr_t>(row) & 15) == 0) ? V >> 2 : 0;
-    for (int i = threadIdx.x; i < V4; i += 1024) {
-        const float4 q = reinterpret_cast<const float4*>(row)[i];
-        const float e[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-        for (int u = 0; u < 4; u++) if (e[u] > v) { v = e[u]; idx = 4 * i + u; }      // ascending index per thread: strict > keeps the lowest
-    }
-    for (int i = 4 * V4 + threadIdx.x; i < V; i += 1024) { const float e = row[i]; if (e > v || (e == v && i < idx)) { v = e; idx = i; } }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(v, o); const int oi = __shfl_xor(idx, o);
-        if (ov > v || (ov == v && oi < idx)) { v = ov; idx = oi; }
-    }
-    if ((threadIdx.x & 63) == 0) { bv[threadIdx.x >> 6] = v; bi[threadIdx.x >> 6] = idx; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 16; w++) if (bv[w] > v || (bv[w] == v && bi[w] < idx)) { v = bv[w]; idx = bi[w]; }
-        out[blockIdx.x] = idx == 0x7fffffff ? 0 : idx;
-    }
+    float v; int idx;
+    argmax_scan_row<1024>(x + (size_t)blockIdx.x * V, V, v, idx);
+    block_argmax<1024>(v, idx, bv, bi);
+    if (threadIdx.x == 0) out[blockIdx.x] = idx == 0x7fffffff ? 0 : idx;
 }
 hipError_t launch_argmax_rows(const float* x, int rows, int V, int* out, hipStream_t s) {
     if (rows <= 0 || V <= 0) return hipErrorInvalidValue;
@@ -4371,28 +4329,17 @@ hipError_t launch_stream_embed_kept(Q4W tok, const int* tokens, const float* aud
     return hipGetLastError();
 }
 
-// the tick's last kernel: argmax_final_kernel's reduction, then the state block moves on
+// the tick's last kernel: the argmax over the lm_head partials, as argmax_final_kernel, then the state block moves on
 __global__ __launch_bounds__(256) void stream_advance_kernel(const float* __restrict__ pv, const int* __restrict__ pi, int n_parts, int* __restrict__ tokens, int* __restrict__ state,
                                                              int enc_rows, int frames, int cap) {
-    __shared__ float bv[256];
-    __shared__ int bi[256];
-    float v = -INFINITY; int idx = 0x7fffffff;
-    for (int i = threadIdx.x; i < n_parts; i += 256) {
-        const float x = pv[i]; const int ii = pi[i];
-        if (x > v || (x == v && ii < idx)) { v = x; idx = ii; }
-    }
-    bv[threadIdx.x] = v; bi[threadIdx.x] = idx;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) {
-            const float x = bv[threadIdx.x + s]; const int ii = bi[threadIdx.x + s];
-            if (x > bv[threadIdx.x] || (x == bv[threadIdx.x] && ii < bi[threadIdx.x])) { bv[threadIdx.x] = x; bi[threadIdx.x] = ii; }
-        }
-        __syncthreads();
-    }
+    __shared__ float bv[4];
+    __shared__ int bi[4];
+    float v; int idx;
+    argmax_scan_partials<256>(pv, pi, n_parts, v, idx);
+    block_argmax<256>(v, idx, bv, bi);
     if (threadIdx.x == 0) {
         const int pos = state[STRM_POS];
-        tokens[pos + 1] = bi[0];
+        tokens[pos + 1] = idx;
         state[STRM_POS] = pos + 1;
         if (enc_rows > 0) {
             const int e = state[STRM_ENC_POS] + enc_rows;
