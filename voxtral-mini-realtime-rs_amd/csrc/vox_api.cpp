@@ -14,6 +14,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <cassert>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -101,9 +102,15 @@ struct vox_ctx {
     double step_ms_meas[2][9] = {{0, 0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0, 0, 0}}; hipEvent_t ev_seg[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     uint32_t warm_forms = 0;      // continuous batch: step chains whose kernels have run once on this context's device (bit 0 launch chains, bit 1 one-group engine, bit 2 two-group engine, bits 3..5 wide chains of 2 / 3 / 4 groups)
     // XF tiles of a 17..48-row GEMM input (the 38-token prefill): 3 tiles x K columns x 64 B; sized once for K <= 16384, reused by every such GEMM of the stream
-    uint16_t* xf_scratch = nullptr; size_t xf_scratch_bytes = 0;
+    static constexpr size_t XF_SCRATCH_BYTES = (size_t)3 * 16384 * 64; uint16_t* xf_scratch = nullptr; size_t xf_scratch_bytes = 0;
     bool shared = false;      // vox_ctx_set_shared: other sessions run on this GPU (no batched engines, planner on the scaled table)
-    float* kz_scratch = nullptr; size_t kz_scratch_bytes = 0;      // K-slice planes of the 17..48-row GEMMs (q4_skinny_mt2_kernel): 8 x 48 x 18432 floats
+    static constexpr size_t KZ_SCRATCH_BYTES = (size_t)8 * 48 * 18432 * 4; float* kz_scratch = nullptr; size_t kz_scratch_bytes = 0;      // K-slice planes of the 17..48-row GEMMs (q4_skinny_mt2_kernel): 8 x 48 x 18432 floats
+    // The one owner of the two buffers above: allocates those asked for that are not there yet.  A failed allocation is not an error: the buffer stays null, size 0 (the caller takes a form without it)
+    void want_scratch(bool xf, bool kz) {
+        auto get = [](void** p, size_t* bytes, size_t want) { if (*p) return; *bytes = want; if (hipMalloc(p, want) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; *bytes = 0; } };
+        if (xf) get(reinterpret_cast<void**>(&xf_scratch), &xf_scratch_bytes, XF_SCRATCH_BYTES);
+        if (kz) get(reinterpret_cast<void**>(&kz_scratch), &kz_scratch_bytes, KZ_SCRATCH_BYTES);
+    }
     float* rs_matrix = nullptr; uint32_t rs_in = 0, rs_out = 0;    // block matrix of the last resampled rate pair (vox_resample)
     struct vox_model* pw_model = nullptr;      // the model with decode-engine steps of the piecewise surface enqueued on `stream` and not yet verified (see pw_after_sync)
 };
@@ -629,9 +636,8 @@ static int32_t q4_linear_dev(vox_ctx* c, const Q4W& w, const float* bias, const 
         GemmParams p{}; p.w = w; p.x = x; p.x_stride = x_stride; p.M = rows; p.out = out; p.out_stride = out_stride; p.bias = bias;
         p.resid = resid; p.resid_stride = resid_stride; p.ksplit = ksplit;
         if (rows > 16 && rows <= 48 && w.fmt == WFMT_Q4_0 && w.K <= 16384) {      // the prefill GEMMs: rows -> XF tiles once (launch_q4_skinny_mt)
-            if (!c->xf_scratch) { c->xf_scratch_bytes = (size_t)3 * 16384 * 64; if (hipMalloc((void**)&c->xf_scratch, c->xf_scratch_bytes) != hipSuccess) { (void)hipGetLastError(); c->xf_scratch = nullptr; c->xf_scratch_bytes = 0; } }
+            c->want_scratch(true, true);
             p.xf_scratch = c->xf_scratch; p.xf_scratch_bytes = c->xf_scratch_bytes;
-            if (!c->kz_scratch) { c->kz_scratch_bytes = (size_t)8 * 48 * 18432 * 4; if (hipMalloc((void**)&c->kz_scratch, c->kz_scratch_bytes) != hipSuccess) { (void)hipGetLastError(); c->kz_scratch = nullptr; c->kz_scratch_bytes = 0; } }
             p.kz_scratch = c->kz_scratch; p.kz_scratch_bytes = c->kz_scratch_bytes;
         }
         HIPCHK(launch_q4_gemm(p, epi, c->stream));
@@ -1750,109 +1756,143 @@ extern "C" int32_t vox_encode_audio_with_cache(vox_model* m, const float* mel, i
 // ---- multi-row decoder forward (prefill): x [M][D] device, in place; positions off..off+M-1  (gguf/model.rs:370-387).
 // n_seq > 1: x holds n_seq stacked sequences of seq_rows = M / n_seq rows, each with its own cache slice kv_seq_stride floats apart
 // (positions restart at off per sequence); the GEMMs run once over all M rows.
+// A layer keeps f32 rows between its launches, or -- 17..48 rows in one sequence (the 38-token prefill) -- both RMSNorms write their output straight as XF tiles (the MFMA
+// A-fragments the q4_skinny_mt_kernel consumes) into the context's XF scratch: no f32 xn, no conversion launch for q|k|v and w1|w3.  A GEMM on XF tiles may leave K-slice
+// planes in the context's plane buffer for the launch behind it to sum.  plan_prefill decides every layer's form, operator by operator; decoder_prefill_dev runs it.
+struct PrefillLayerForm {
+    enum Qkv : uint8_t { QKV_F32, QKV_XF, QKV_PLANES } qkv = QKV_F32;              // f32 rows | XF tiles, launch_q4_gemm | planes, their finish also applies RoPE and writes the k / v rows into the cache (three launches less)
+    enum Wo : uint8_t { WO_F32, WO_PLANES_ROWS, WO_PLANES_XF } wo = WO_F32;        // f32 rows | planes of the f32 attention rows (xf_rows) | of the XF tiles the short-sequence attention leaves; the RMSNorm behind sums them (one launch less)
+    enum W13 : uint8_t { W13_F32, W13_XF, W13_PLANES } w13 = W13_F32;              // f32 rows | XF tiles, launch_q4_gemm | planes, their finish writes SiLU(gate) * up straight into the XF tiles w2 reads (no f32 activations, no conversion launch)
+    enum W2 : uint8_t { W2_F32, W2_PLANES_ROWS, W2_PLANES_XF } w2 = W2_F32;        // f32 rows | planes of the f32 activations (xf_rows) | of the w1|w3 finish's XF tiles; the NEXT layer's first RMSNorm sums them
+    int kz_qkv = 0, kz_wo = 0, kz_13 = 0, kz_w2 = 0;      // K slices of the operator's planes
+    bool f32_rows() const { return qkv == QKV_F32 && wo == WO_F32 && w13 == W13_F32 && w2 == W2_F32; }
+    // Invariants: kz_x != 0 exactly when operator x is a planes form.  The norm that sums wo's planes writes XF tiles only: wo as planes -> w1|w3 not on f32 rows.  The w1|w3 finish
+    // needs that norm in front and leaves XF tiles only: W13_PLANES -> wo as planes, and W13_PLANES <-> W2_PLANES_XF.  w2's planes wait for an XF norm: `prev`->w2 as planes -> qkv not
+    // on f32 rows (a finishing kernel sums the last layer's).
+    bool valid(const PrefillLayerForm* prev) const {
+        return (kz_qkv != 0) == (qkv == QKV_PLANES) && (kz_wo != 0) == (wo != WO_F32) && (kz_13 != 0) == (w13 == W13_PLANES) && (kz_w2 != 0) == (w2 != W2_F32) && (wo == WO_F32 || w13 != W13_F32) &&
+               (w13 != W13_PLANES || wo != WO_F32) && (w13 == W13_PLANES) == (w2 == W2_PLANES_XF) && (!prev || prev->w2 == W2_F32 || qkv != QKV_F32);
+    }
+};
+// A prefill layer's attention launch but for its pointers and kv_seq_stride: plan_prefill asks attn_prefill_small_ok about what decoder_prefill_dev launches
+static AttnParams prefill_attn_params(const vox_model_cfg& c, int max_seq, int M, int n_seq, int off) {
+    const int hd = c.dec_head_dim, QD = c.dec_heads * hd, W = QD + 2 * c.dec_kv_heads * hd, seq_rows = n_seq > 1 ? M / n_seq : 0, Mq = n_seq > 1 ? seq_rows : M;
+    AttnParams ap{}; ap.q_stride = W; ap.kv_row_stride = hd; ap.kv_head_stride = max_seq * hd; ap.out_stride = QD; ap.M = Mq; ap.kv_len = off + Mq; ap.n_heads = c.dec_heads;
+    ap.n_kv_heads = c.dec_kv_heads; ap.offset = off; ap.window = c.dec_window; ap.q_seq_stride = seq_rows * W; ap.out_seq_stride = seq_rows * QD;
+    return ap;
+}
+// Every layer's form for one call; launches nothing.  Asks the context for the XF scratch when the call's shape and knobs allow XF tiles at all and for the plane buffer when planes
+// may be used, and decides on what it got; eligibility is per layer (a checkpoint may mix tensor formats).  Cross-check knobs: VOX_PREFILL_NO_NORM_XF, VOX_NO_SKINNY_MT (the GEMMs
+// on f32 rows): every layer on f32 rows; VOX_PREFILL_NO_SUMK: no planes (finishing kernels inside launch_q4_gemm instead); VOX_PREFILL_NO_FUSED_FIN: no QKV_PLANES, W13_PLANES, W2_PLANES_XF.
+static std::vector<PrefillLayerForm> plan_prefill(vox_model* m, int M, int n_seq, int off, int max_seq) {
+    using PF = PrefillLayerForm;
+    const vox_model_cfg& c = m->cfg; vox_ctx* cx = m->ctx;
+    const int D = c.dec_dim, hd = c.dec_head_dim, QD = c.dec_heads * hd, W = QD + 2 * c.dec_kv_heads * hd, F = c.dec_ffn;
+    const bool no_norm_xf = knob_str("VOX_PREFILL_NO_NORM_XF"), no_skinny_mt = knob_str("VOX_NO_SKINNY_MT"), no_sumk = knob_str("VOX_PREFILL_NO_SUMK"), no_fused_fin = knob_str("VOX_PREFILL_NO_FUSED_FIN");
+    std::vector<PF> forms(c.dec_layers);      // every operator on f32 rows
+    if (n_seq != 1 || M <= 16 || M > 48 || no_norm_xf || no_skinny_mt) return forms;
+    cx->want_scratch(true, false);
+    if (!cx->xf_scratch) return forms;
+    if (!no_sumk) cx->want_scratch(false, true);
+    const bool planes = !no_sumk && cx->kz_scratch, fin = planes && !no_fused_fin;      // planes summed by the norms | also the finishing kernels of q|k|v and w1|w3
+    auto xf_ok = [&](const Q4W& w) { return w.fmt == WFMT_Q4_0 && w.qt && w.st && w.nb % 4 == 0 && w.K == D && D % 128 == 0 && D <= 10240; };
+    auto kz_fits = [&](int kz, int N) { return (size_t)kz * M * N * 4 <= cx->kz_scratch_bytes; };
+    auto xf_fits = [&](int K) { return (size_t)((M + 15) / 16) * K * 64 <= cx->xf_scratch_bytes; };
+    // round 6: a short sequence from position 0 (the 38-token prefill) takes the short-sequence attention kernel, whose rows leave as the XF tiles the wo GEMM reads
+    // (no f32 round trip, no xf_rows launch) when that GEMM is the planes form
+    const bool att_xf = xf_fits(QD) && attn_prefill_small_ok(prefill_attn_params(c, max_seq, M, n_seq, off), hd, n_seq);
+    for (int l = 0; l < c.dec_layers; l++) {
+        const DecLayer& L = m->dec[l]; PF& f = forms[l];
+        if (xf_ok(L.wqkv.w)) {
+            f.kz_qkv = fin ? q4_skinny_mt2_plan(L.wqkv.w, M) : 0; if (!kz_fits(f.kz_qkv, W)) f.kz_qkv = 0;
+            f.qkv = f.kz_qkv ? PF::QKV_PLANES : PF::QKV_XF;
+        }
+        const bool w13_xf = xf_ok(L.w13.w);
+        f.kz_wo = planes && w13_xf && L.wo.w.N == D && QD % 128 == 0 ? q4_skinny_mt2_plan(L.wo.w, M) : 0; if (!kz_fits(f.kz_wo, D)) f.kz_wo = 0;
+        if (f.kz_wo) f.wo = att_xf ? PF::WO_PLANES_XF : PF::WO_PLANES_ROWS;
+        f.kz_w2 = planes && L.w2.w.N == D && F % 128 == 0 && F <= 16384 ? q4_skinny_mt2_plan(L.w2.w, M) : 0;
+        if (!kz_fits(f.kz_w2, D) || !(l + 1 == c.dec_layers || xf_ok(m->dec[l + 1].wqkv.w))) f.kz_w2 = 0;      // (the next layer's first norm has to be the XF one)
+        f.kz_13 = fin && f.kz_wo && f.kz_w2 && L.w13.w.N == 2 * F && xf_fits(F) ? q4_skinny_mt2_plan(L.w13.w, M) : 0; if (!kz_fits(f.kz_13, 2 * F)) f.kz_13 = 0;
+        f.w13 = f.kz_13 ? PF::W13_PLANES : w13_xf ? PF::W13_XF : PF::W13_F32;
+        if (f.kz_w2) f.w2 = f.kz_13 ? PF::W2_PLANES_XF : PF::W2_PLANES_ROWS;
+        assert(f.valid(l ? &forms[l - 1] : nullptr));
+    }
+    return forms;
+}
 static int32_t decoder_prefill_dev(vox_model* m, float* x, int M, vox_cache* kc, int off, int n_seq = 1, long kv_seq_stride = 0) {
+    using PF = PrefillLayerForm;
     const vox_model_cfg& c = m->cfg; vox_ctx* cx = m->ctx; hipStream_t s = cx->stream;
     const int D = c.dec_dim, H = c.dec_heads, KV = c.dec_kv_heads, hd = c.dec_head_dim, QD = H * hd, KD = KV * hd, W = QD + 2 * KD, F = c.dec_ffn;
-    const int seq_rows = n_seq > 1 ? M / n_seq : 0, Mq = n_seq > 1 ? seq_rows : M;
+    const int seq_rows = n_seq > 1 ? M / n_seq : 0;
     // workspace after the encoder region is reused: [xn | qkv | att | ffn]
     const size_t need = (size_t)M * D + (size_t)M * W + (size_t)M * QD + (size_t)M * F + 1024;
     VOXCHK(ensure(&m->ws, &m->ws_floats, need));
     float* xn = m->ws; float* qkv = xn + (size_t)M * D; float* att = qkv + (size_t)M * W; float* ffn = att + (size_t)M * QD;
-    const size_t lf = kc->layer_stride;
-    // 17..48 rows in one sequence (the 38-token prefill): both RMSNorms write their output straight as XF tiles (the MFMA A-fragments the
-    // q4_skinny_mt_kernel consumes) into the context's XF scratch -- no f32 xn, no conversion launch for q|k|v and w1|w3
-    auto xf_ok = [&](const Q4W& w) { return w.fmt == WFMT_Q4_0 && w.qt && w.st && w.nb % 4 == 0 && w.K == D && D % 128 == 0 && D <= 10240; };
-    bool norm_xf = n_seq == 1 && M > 16 && M <= 48 && knob_str("VOX_PREFILL_NO_NORM_XF") == nullptr &&
-                   knob_str("VOX_NO_SKINNY_MT") == nullptr;      // (VOX_NO_SKINNY_MT: GEMMs on f32 rows)
-    if (norm_xf) {
-        if (!cx->xf_scratch) { cx->xf_scratch_bytes = (size_t)3 * 16384 * 64; if (hipMalloc((void**)&cx->xf_scratch, cx->xf_scratch_bytes) != hipSuccess) { (void)hipGetLastError(); cx->xf_scratch = nullptr; cx->xf_scratch_bytes = 0; } }
-        norm_xf = cx->xf_scratch != nullptr;
-    }
-    auto linear_xf = [&](const Q4W& w, float* out, int out_stride, int epi) -> int32_t {
-        GemmParams p{}; p.w = w; p.xf = reinterpret_cast<const uint4*>(cx->xf_scratch); p.M = M; p.out = out; p.out_stride = out_stride;
-        if (!cx->kz_scratch) { cx->kz_scratch_bytes = (size_t)8 * 48 * 18432 * 4; if (hipMalloc((void**)&cx->kz_scratch, cx->kz_scratch_bytes) != hipSuccess) { (void)hipGetLastError(); cx->kz_scratch = nullptr; cx->kz_scratch_bytes = 0; } }
-        p.kz_scratch = cx->kz_scratch; p.kz_scratch_bytes = cx->kz_scratch_bytes;
-        HIPCHK(launch_q4_gemm(p, epi, s)); return VOX_OK;
+    const std::vector<PF> forms = plan_prefill(m, M, n_seq, off, kc->max_seq);
+    const DecLayer* L = nullptr; float *kl = nullptr, *vl = nullptr;      // the layer the pieces below work on
+    auto rope_kv_store = [&]() -> int32_t {
+        HIPCHK(launch_rope(qkv, M, W, QD + KD, hd, off, m->dec_cos, m->dec_sin, s, seq_rows));
+        HIPCHK(launch_kv_store(qkv, M, W, QD, KV, hd, off, kl, vl, kc->max_seq * hd, s, seq_rows, kv_seq_stride)); return VOX_OK;
     };
-    // wo / w2 (EPI_RESID) as two-dimensional GEMMs whose K-slice planes are summed by the RMSNorm that follows (one launch less per GEMM): `pend` = slices of the
-    // previous layer's w2 still waiting in the plane buffer.  VOX_PREFILL_NO_SUMK=1: finishing kernels instead.
-    const bool fuse_fin = norm_xf && knob_str("VOX_PREFILL_NO_SUMK") == nullptr;
-    const bool fuse_fin2 = fuse_fin && knob_str("VOX_PREFILL_NO_FUSED_FIN") == nullptr;      // finishing kernels of q|k|v (+ RoPE + cache write) and w1|w3 (+ SwiGLU -> XF tiles)
-    auto planes_gemm = [&](const Q4W& w, const float* in, int K, int KZ) -> int32_t {      // in [M][K] f32 -> XF tiles -> planes
-        HIPCHK(launch_xf_rows(in, K, M, K, cx->xf_scratch, s));
-        GemmParams p{}; p.w = w; p.xf = reinterpret_cast<const uint4*>(cx->xf_scratch); p.M = M; p.kz_scratch = cx->kz_scratch; p.kz_scratch_bytes = cx->kz_scratch_bytes;
-        HIPCHK(launch_q4_skinny_mt2_planes(p, KZ, s)); return VOX_OK;
+    auto attn_params = [&]() {
+        AttnParams ap = prefill_attn_params(c, kc->max_seq, M, n_seq, off); ap.q = qkv; ap.k = kl; ap.v = vl; ap.out = att; ap.kv_seq_stride = kv_seq_stride; return ap;
     };
-    if (fuse_fin && !cx->kz_scratch) { cx->kz_scratch_bytes = (size_t)8 * 48 * 18432 * 4; if (hipMalloc((void**)&cx->kz_scratch, cx->kz_scratch_bytes) != hipSuccess) { (void)hipGetLastError(); cx->kz_scratch = nullptr; cx->kz_scratch_bytes = 0; } }
-    int pend = 0;
-    for (int l = 0; l < c.dec_layers; l++) {
-        const DecLayer& L = m->dec[l]; float* kl = kc->k + (size_t)l * lf; float* vl = kc->v + (size_t)l * lf;
-        bool rope_done = false, act_in_xf = false;
-        if (norm_xf && xf_ok(L.wqkv.w)) {
-            if (pend) HIPCHK(launch_rms_norm_xf_sumk(x, D, M, D, cx->kz_scratch, pend, L.attn_norm, nullptr, c.norm_eps, cx->xf_scratch, s));      // + the previous layer's w2
-            else HIPCHK(launch_rms_norm_xf(x, D, M, D, L.attn_norm, nullptr, c.norm_eps, cx->xf_scratch, s));
-            pend = 0;
-            // q|k|v as a two-dimensional GEMM whose finishing kernel also applies RoPE and writes the k / v rows into the cache (three launches less per layer)
-            const int kz_qkv = fuse_fin2 && cx->kz_scratch && W == QD + 2 * KD ? q4_skinny_mt2_plan(L.wqkv.w, M) : 0;
-            if (kz_qkv && (size_t)kz_qkv * M * W * 4 <= cx->kz_scratch_bytes) {
-                GemmParams p{}; p.w = L.wqkv.w; p.xf = reinterpret_cast<const uint4*>(cx->xf_scratch); p.M = M; p.kz_scratch = cx->kz_scratch; p.kz_scratch_bytes = cx->kz_scratch_bytes;
-                HIPCHK(launch_q4_skinny_mt2_planes(p, kz_qkv, s));
-                HIPCHK(launch_splitk_finish_rope_kv(cx->kz_scratch, kz_qkv, M, W, qkv, W, QD, KV, hd, off, m->dec_cos, m->dec_sin, kl, vl, kc->max_seq * hd, s));
-                rope_done = true;
-            } else VOXCHK(linear_xf(L.wqkv.w, qkv, W, EPI_STORE));
-        } else {
-            if (pend) { HIPCHK(launch_splitk_finish_resid(cx->kz_scratch, pend, M, D, x, D, s)); pend = 0; }
-            HIPCHK(launch_rms_norm(x, D, M, D, L.attn_norm, nullptr, c.norm_eps, xn, D, s));
-            VOXCHK(q4_linear_dev(cx, L.wqkv.w, nullptr, xn, D, M, qkv, W));
-        }
-        if (!rope_done) {
-            HIPCHK(launch_rope(qkv, M, W, QD + KD, hd, off, m->dec_cos, m->dec_sin, s, seq_rows));
-            HIPCHK(launch_kv_store(qkv, M, W, QD, KV, hd, off, kl, vl, kc->max_seq * hd, s, seq_rows, kv_seq_stride));
-        }
-        AttnParams ap{}; ap.q = qkv; ap.q_stride = W; ap.k = kl; ap.v = vl; ap.kv_row_stride = hd; ap.kv_head_stride = kc->max_seq * hd;
-        ap.out = att; ap.out_stride = QD; ap.M = Mq; ap.kv_len = off + Mq; ap.n_heads = H; ap.n_kv_heads = KV; ap.offset = off; ap.window = c.dec_window;
-        ap.q_seq_stride = seq_rows * W; ap.out_seq_stride = seq_rows * QD; ap.kv_seq_stride = kv_seq_stride;
-        const int kz_wo = fuse_fin && cx->kz_scratch && xf_ok(L.w13.w) && L.wo.w.N == D && QD % 128 == 0 ? q4_skinny_mt2_plan(L.wo.w, M) : 0;
-        const bool wo_planes = kz_wo && (size_t)kz_wo * M * D * 4 <= cx->kz_scratch_bytes;
-        // round 6: a short sequence from position 0 (the 38-token prefill) takes the short-sequence attention kernel, whose rows leave as the XF tiles the wo GEMM reads
-        // (no f32 round trip, no xf_rows launch) when that GEMM is the planes form
-        const bool att_xf = wo_planes && n_seq == 1 && (size_t)((M + 15) / 16) * QD * 64 <= cx->xf_scratch_bytes && attn_prefill_small_ok(ap, hd, n_seq);
-        if (att_xf) { ap.out_xf_tiles = cx->xf_scratch; ap.out_xf_tile_stride = (long)2 * (QD >> 7) * 256 * 8; }
+    // ---- a layer on f32 rows
+    auto layer_f32 = [&]() -> int32_t {
+        HIPCHK(launch_rms_norm(x, D, M, D, L->attn_norm, nullptr, c.norm_eps, xn, D, s));
+        VOXCHK(q4_linear_dev(cx, L->wqkv.w, nullptr, xn, D, M, qkv, W));
+        VOXCHK(rope_kv_store());
+        HIPCHK(launch_attn_prefill(attn_params(), hd, s, n_seq));
+        VOXCHK(q4_linear_dev(cx, L->wo.w, nullptr, att, QD, M, x, D, EPI_RESID, x, D));
+        HIPCHK(launch_rms_norm(x, D, M, D, L->ffn_norm, L->ada_mul, c.norm_eps, xn, D, s));    // norm then Ada x*(1+s) (model.rs:382-385)
+        VOXCHK(q4_linear_dev(cx, L->w13.w, nullptr, xn, D, M, ffn, F, EPI_SWIGLU));
+        VOXCHK(q4_linear_dev(cx, L->w2.w, nullptr, ffn, F, M, x, D, EPI_RESID, x, D)); return VOX_OK;
+    };
+    // ---- a layer with operators on XF tiles (one sequence); pend = K slices of the previous layer's w2 waiting in the plane buffer.  An operator the planner left on f32 rows runs as above.
+    auto gemm_xf = [&](const Q4W& w) { GemmParams p{}; p.w = w; p.xf = reinterpret_cast<const uint4*>(cx->xf_scratch); p.M = M; p.kz_scratch = cx->kz_scratch; p.kz_scratch_bytes = cx->kz_scratch_bytes; return p; };
+    auto planes_from_xf = [&](const Q4W& w, int KZ) -> int32_t { HIPCHK(launch_q4_skinny_mt2_planes(gemm_xf(w), KZ, s)); return VOX_OK; };      // this operator over the XF tiles in scratch, into K-slice planes
+    auto linear_xf = [&](const Q4W& w, float* out, int out_stride, int epi) -> int32_t {      // ... into f32 rows: launch_q4_gemm picks the kernel, which may split K through the plane buffer
+        cx->want_scratch(false, true);
+        GemmParams p = gemm_xf(w); p.out = out; p.out_stride = out_stride; HIPCHK(launch_q4_gemm(p, epi, s)); return VOX_OK;
+    };
+    auto layer_xf = [&](const PF& f, int pend) -> int32_t {
+        if (f.qkv == PF::QKV_F32) {      // (pend == 0: PrefillLayerForm::valid)
+            HIPCHK(launch_rms_norm(x, D, M, D, L->attn_norm, nullptr, c.norm_eps, xn, D, s));
+            VOXCHK(q4_linear_dev(cx, L->wqkv.w, nullptr, xn, D, M, qkv, W));
+        } else if (pend) HIPCHK(launch_rms_norm_xf_sumk(x, D, M, D, cx->kz_scratch, pend, L->attn_norm, nullptr, c.norm_eps, cx->xf_scratch, s));      // + the previous layer's w2
+        else HIPCHK(launch_rms_norm_xf(x, D, M, D, L->attn_norm, nullptr, c.norm_eps, cx->xf_scratch, s));
+        if (f.qkv == PF::QKV_XF) VOXCHK(linear_xf(L->wqkv.w, qkv, W, EPI_STORE));
+        if (f.qkv == PF::QKV_PLANES) {
+            VOXCHK(planes_from_xf(L->wqkv.w, f.kz_qkv));
+            HIPCHK(launch_splitk_finish_rope_kv(cx->kz_scratch, f.kz_qkv, M, W, qkv, W, QD, KV, hd, off, m->dec_cos, m->dec_sin, kl, vl, kc->max_seq * hd, s));
+        } else VOXCHK(rope_kv_store());
+        AttnParams ap = attn_params();
+        if (f.wo == PF::WO_PLANES_XF) { ap.out_xf_tiles = cx->xf_scratch; ap.out_xf_tile_stride = (long)2 * (QD >> 7) * 256 * 8; }
         HIPCHK(launch_attn_prefill(ap, hd, s, n_seq));
-        if (wo_planes) {
-            if (att_xf) { GemmParams pw{}; pw.w = L.wo.w; pw.xf = reinterpret_cast<const uint4*>(cx->xf_scratch); pw.M = M; pw.kz_scratch = cx->kz_scratch; pw.kz_scratch_bytes = cx->kz_scratch_bytes;
-                          HIPCHK(launch_q4_skinny_mt2_planes(pw, kz_wo, s)); }
-            else VOXCHK(planes_gemm(L.wo.w, att, QD, kz_wo));
-            HIPCHK(launch_rms_norm_xf_sumk(x, D, M, D, cx->kz_scratch, kz_wo, L.ffn_norm, L.ada_mul, c.norm_eps, cx->xf_scratch, s));      // x += wo(att); norm then Ada x*(1+s) (model.rs:382-385)
-            // w1|w3 as planes whose finishing kernel writes SiLU(gate) * up straight into the XF tiles w2 reads (no f32 activations, no conversion launch)
-            const int kz_13 = fuse_fin2 && L.w13.w.N == 2 * F && F % 128 == 0 && F <= 16384 && L.w2.w.N == D ? q4_skinny_mt2_plan(L.w13.w, M) : 0;
-            const int kz_w2n = kz_13 ? q4_skinny_mt2_plan(L.w2.w, M) : 0;
-            if (kz_13 && kz_w2n && (size_t)kz_13 * M * 2 * F * 4 <= cx->kz_scratch_bytes && (size_t)kz_w2n * M * D * 4 <= cx->kz_scratch_bytes && (size_t)((M + 15) / 16) * F * 64 <= cx->xf_scratch_bytes &&
-                (l + 1 == c.dec_layers || xf_ok(m->dec[l + 1].wqkv.w))) {
-                GemmParams p{}; p.w = L.w13.w; p.xf = reinterpret_cast<const uint4*>(cx->xf_scratch); p.M = M; p.kz_scratch = cx->kz_scratch; p.kz_scratch_bytes = cx->kz_scratch_bytes;
-                HIPCHK(launch_q4_skinny_mt2_planes(p, kz_13, s));
-                HIPCHK(launch_splitk_finish_swiglu_xf(cx->kz_scratch, kz_13, M, 2 * F, nullptr, cx->xf_scratch, s));
-                act_in_xf = true;
-            } else VOXCHK(linear_xf(L.w13.w, ffn, F, EPI_SWIGLU));
+        if (f.wo == PF::WO_F32) {
+            VOXCHK(q4_linear_dev(cx, L->wo.w, nullptr, att, QD, M, x, D, EPI_RESID, x, D));
+            if (f.w13 == PF::W13_F32) HIPCHK(launch_rms_norm(x, D, M, D, L->ffn_norm, L->ada_mul, c.norm_eps, xn, D, s));    // norm then Ada x*(1+s) (model.rs:382-385)
+            else HIPCHK(launch_rms_norm_xf(x, D, M, D, L->ffn_norm, L->ada_mul, c.norm_eps, cx->xf_scratch, s));
         } else {
-            VOXCHK(q4_linear_dev(cx, L.wo.w, nullptr, att, QD, M, x, D, EPI_RESID, x, D));
-            if (norm_xf && xf_ok(L.w13.w)) {
-                HIPCHK(launch_rms_norm_xf(x, D, M, D, L.ffn_norm, L.ada_mul, c.norm_eps, cx->xf_scratch, s));    // norm then Ada x*(1+s) (model.rs:382-385)
-                VOXCHK(linear_xf(L.w13.w, ffn, F, EPI_SWIGLU));
-            } else {
-                HIPCHK(launch_rms_norm(x, D, M, D, L.ffn_norm, L.ada_mul, c.norm_eps, xn, D, s));    // norm then Ada x*(1+s) (model.rs:382-385)
-                VOXCHK(q4_linear_dev(cx, L.w13.w, nullptr, xn, D, M, ffn, F, EPI_SWIGLU));
-            }
+            if (f.wo == PF::WO_PLANES_ROWS) HIPCHK(launch_xf_rows(att, QD, M, QD, cx->xf_scratch, s));
+            VOXCHK(planes_from_xf(L->wo.w, f.kz_wo));
+            HIPCHK(launch_rms_norm_xf_sumk(x, D, M, D, cx->kz_scratch, f.kz_wo, L->ffn_norm, L->ada_mul, c.norm_eps, cx->xf_scratch, s));      // x += wo(att); norm then Ada x*(1+s) (model.rs:382-385)
         }
-        const int kz_w2 = fuse_fin && cx->kz_scratch && L.w2.w.N == D && F % 128 == 0 && F <= 16384 ? q4_skinny_mt2_plan(L.w2.w, M) : 0;
-        if (act_in_xf) {      // (conditions checked where the activations were written)
-            GemmParams p{}; p.w = L.w2.w; p.xf = reinterpret_cast<const uint4*>(cx->xf_scratch); p.M = M; p.kz_scratch = cx->kz_scratch; p.kz_scratch_bytes = cx->kz_scratch_bytes;
-            HIPCHK(launch_q4_skinny_mt2_planes(p, kz_w2, s)); pend = kz_w2;
-        } else if (kz_w2 && (size_t)kz_w2 * M * D * 4 <= cx->kz_scratch_bytes && (l + 1 == c.dec_layers || xf_ok(m->dec[l + 1].wqkv.w))) {
-            VOXCHK(planes_gemm(L.w2.w, ffn, F, kz_w2)); pend = kz_w2;
-        } else VOXCHK(q4_linear_dev(cx, L.w2.w, nullptr, ffn, F, M, x, D, EPI_RESID, x, D));
+        if (f.w13 == PF::W13_F32) VOXCHK(q4_linear_dev(cx, L->w13.w, nullptr, xn, D, M, ffn, F, EPI_SWIGLU));
+        if (f.w13 == PF::W13_XF) VOXCHK(linear_xf(L->w13.w, ffn, F, EPI_SWIGLU));
+        if (f.w13 == PF::W13_PLANES) {
+            VOXCHK(planes_from_xf(L->w13.w, f.kz_13));
+            HIPCHK(launch_splitk_finish_swiglu_xf(cx->kz_scratch, f.kz_13, M, 2 * F, nullptr, cx->xf_scratch, s));
+        }
+        if (f.w2 == PF::W2_F32) return q4_linear_dev(cx, L->w2.w, nullptr, ffn, F, M, x, D, EPI_RESID, x, D);
+        if (f.w2 == PF::W2_PLANES_ROWS) HIPCHK(launch_xf_rows(ffn, F, M, F, cx->xf_scratch, s));
+        return planes_from_xf(L->w2.w, f.kz_w2);      // summed by the next layer's first norm
+    };
+    for (int l = 0; l < c.dec_layers; l++) {
+        L = &m->dec[l]; kl = kc->k + (size_t)l * kc->layer_stride; vl = kc->v + (size_t)l * kc->layer_stride;
+        VOXCHK(forms[l].f32_rows() ? layer_f32() : layer_xf(forms[l], l ? forms[l - 1].kz_w2 : 0));
     }
-    if (pend) HIPCHK(launch_splitk_finish_resid(cx->kz_scratch, pend, M, D, x, D, s));      // the last layer's w2
+    if (!forms.empty() && forms.back().kz_w2) HIPCHK(launch_splitk_finish_resid(cx->kz_scratch, forms.back().kz_w2, M, D, x, D, s));      // the last layer's w2
     return VOX_OK;
 }
 
