@@ -802,6 +802,21 @@ struct PrefixState {
     uint64_t enc_bytes = 0, dec_bytes = 0;
 };
 static const int VOX_PREFIX_TOKENS = 38, VOX_TOK_BOS = 1, VOX_TOK_STREAMING_PAD = 32;      // the decoder's fixed prefix: BOS + 37 x STREAMING_PAD (gguf/model.rs:891-892)
+// the prefix itself, built here and nowhere else; static storage, so an upload from it has nothing to keep alive
+static const struct PrefixTokens {
+    int32_t t[VOX_PREFIX_TOKENS];
+    PrefixTokens() { std::fill(t, t + VOX_PREFIX_TOKENS, VOX_TOK_STREAMING_PAD); t[0] = VOX_TOK_BOS; }
+} PREFIX_TOKENS;
+// What decode_step_enqueue launches.  StepAndArgmax: the step and the launch that turns its argmax partials into the next token + input (every path).  Engine only --
+// EngineAlone: the engine launch, its partials left for whoever comes next; EngineArgmaxFirst: an engine launch that BEGINS with the argmax of the previous launch's partials
+// (flags 65536): [EngineAlone] [EngineArgmaxFirst] ... [EngineArgmaxFirst] [argmax_final] is the token sequence of StepAndArgmax steps with one launch per token, not two.
+enum class StepLaunch { StepAndArgmax, EngineAlone, EngineArgmaxFirst };
+// the single-clip decode graphs: [0] = one step, [1] = key.unroll steps (fewer graph boundaries).  Both bake the key's cache / audio (and the model's token) pointers
+// and its launch form in: graphs_for re-keys them, graphs_destroy drops them (the key stays: the next graphs_for with it captures afresh)
+struct DecodeGraphs {
+    struct Key { const vox_cache* cache; const float* audio; int unroll; StepLaunch launch; } key{nullptr, nullptr, 0, StepLaunch::StepAndArgmax};
+    hipGraph_t graph[2] = {nullptr, nullptr}; hipGraphExec_t exec[2] = {nullptr, nullptr};
+};
 struct vox_model {
     PrefixState pfx;
     vox_ctx* ctx = nullptr; vox_model_cfg cfg{};
@@ -824,7 +839,7 @@ struct vox_model {
     // decode state
     vox_cache* cache = nullptr;                           // internal cache for transcribe_streaming
     int *d_tokens = nullptr, *d_pos = nullptr; int tokens_cap = 0;
-    float* d_prefix = nullptr;                            // [38][dec_dim] prefill inputs (transcribe_dev)
+    float* d_prefix = nullptr;                            // [38][dec_dim] prefill inputs (prefill_prefix_rows)
     float *enc_cos_s = nullptr, *enc_sin_s = nullptr; int enc_rope_s_len = 0;   // RoPE tables for the streaming encoder (positions beyond the 4096-row load-time table)
     int* d_seq_len = nullptr; std::vector<int> h_seq_len;  // per-utterance encoder rows of a stacked batch
     int *d_seq_off = nullptr, *d_row_pos = nullptr; size_t row_pos_cap = 0; std::vector<int> h_seq_off, h_row_pos;      // packed stack: start row per utterance, position per row
@@ -844,9 +859,7 @@ struct vox_model {
     int engb_flags = 128 | 1 | 64 | 2048;
     int engb_flags2 = 128 | 1024;      // two-group launch: loader depth 2, never paused or thinned -- with two chains interleaved the stream is what a phase waits for (profiles/r05_b32_engine.txt: 61.4 us per layer against 65.4 with the one-group flags)
     unsigned engb_err_host[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
-    // decode graphs: [0] = one step, [1] = graph_unroll steps (fewer graph boundaries); both bake cache / audio / token pointers in
-    hipGraph_t graph[2] = {nullptr, nullptr}; hipGraphExec_t graph_exec[2] = {nullptr, nullptr}; int graph_unroll = 0, graph_mode = 0;
-    const vox_cache* graph_cache = nullptr; const float* graph_audio = nullptr;
+    DecodeGraphs graphs;
     // piecewise decoder surface (embed_tokens_from_ids / forward_hidden_with_cache / lm_head on caller-owned caches): model-owned workspaces, and the decode engine's
     // layer table for the caller's cache (eng_pw).  pw_memo: row 0 of pw_hidden is the final norm's output of an engine launch that ALSO produced that row's logits (pw_logits)
     // and argmax partials (eng_pw.part_*): lm_head on that very buffer has nothing left to compute.  eng_pw.err_word is refreshed (async) behind every engine launch: no round trip.
@@ -1241,9 +1254,10 @@ struct Loader {
 }  // namespace
 
 static void graphs_destroy(vox_model* m) {
+    DecodeGraphs& g = m->graphs;
     for (int i = 0; i < 2; i++) {
-        if (m->graph_exec[i]) { (void)hipGraphExecDestroy(m->graph_exec[i]); m->graph_exec[i] = nullptr; }
-        if (m->graph[i]) { (void)hipGraphDestroy(m->graph[i]); m->graph[i] = nullptr; }
+        if (g.exec[i]) { (void)hipGraphExecDestroy(g.exec[i]); g.exec[i] = nullptr; }
+        if (g.graph[i]) { (void)hipGraphDestroy(g.graph[i]); g.graph[i] = nullptr; }
     }
 }
 static void prefix_release(vox_model* m) {
@@ -2124,6 +2138,17 @@ static void prefix_bounds(const vox_model* m, int* RC, int* PC) {
     *PC = (int)pcn; *RC = (int)(pcn * R);
 }
 static bool prefix_active(const vox_model* m) { int rc, pc; prefix_bounds(m, &rc, &pc); return m->pfx.on && rc > 0; }
+// the decoder's fixed prefix on its way into a token buffer: the one upload every caller uses
+static hipError_t prefix_tokens_enqueue(int* d_tokens, hipStream_t s) { return hipMemcpyAsync(d_tokens, PREFIX_TOKENS.t, sizeof PREFIX_TOKENS.t, hipMemcpyHostToDevice, s); }
+// The prefill half of seeding a decode (seed_clip; prefix_build runs it once per model over its own adapter rows): inputs = audio[:rows] + embed(prefix tokens, already
+// in d_tokens) into the model-owned d_prefix (no hipMalloc / hipFree in the timed path), prefilled into the model's cache from row 0 (gguf/model.rs:896-915)
+static int32_t prefill_prefix_rows(vox_model* m, const float* audio, int rows) {
+    const vox_model_cfg& c = m->cfg;
+    if (!m->d_prefix) HIPCHK(hipMalloc((void**)&m->d_prefix, (size_t)VOX_PREFIX_TOKENS * c.dec_dim * 4));
+    HIPCHK(launch_embed(m->tok.w, m->d_tokens, rows, audio, c.dec_dim, nullptr, 0, 0, m->d_prefix, m->ctx->stream));
+    m->cache->len = 0;
+    return decoder_prefill_dev(m, m->d_prefix, rows, m->cache, 0);
+}
 static int32_t prefix_build(vox_model* m, const float* t_embed) {
     PrefixState& p = m->pfx; const vox_model_cfg& c = m->cfg; vox_ctx* cx = m->ctx; hipStream_t s = cx->stream;
     int RC, PC; prefix_bounds(m, &RC, &PC);
@@ -2163,12 +2188,8 @@ static int32_t prefix_build(vox_model* m, const float* t_embed) {
     VOXCHK(vox_model_set_t_embed(m, t_embed));
     VOXCHK(ensure_decode_state(m, VOX_PREFIX_TOKENS));
     p.dec_bytes = 2 * (uint64_t)rows_bytes * n_rows;
-    std::vector<int32_t> prefix(VOX_PREFIX_TOKENS, VOX_TOK_STREAMING_PAD); prefix[0] = VOX_TOK_BOS;
-    HIPCHK(hipMemcpyAsync(m->d_tokens, prefix.data(), prefix.size() * 4, hipMemcpyHostToDevice, s));
-    if (!m->d_prefix) HIPCHK(hipMalloc((void**)&m->d_prefix, (size_t)VOX_PREFIX_TOKENS * c.dec_dim * 4));
-    HIPCHK(launch_embed(m->tok.w, m->d_tokens, PC, p.audio, c.dec_dim, nullptr, 0, 0, m->d_prefix, s));
-    m->cache->len = 0;
-    VOXCHK(decoder_prefill_dev(m, m->d_prefix, PC, m->cache, 0));
+    HIPCHK(prefix_tokens_enqueue(m->d_tokens, s));
+    VOXCHK(prefill_prefix_rows(m, p.audio, PC));
     const size_t pitch = (size_t)m->cache->max_seq * hd * 4;      // cache: [layer][kv head][max_seq][hd], layers back to back
     ARGCHK(m->cache->layer_stride == (size_t)KV * m->cache->max_seq * hd, "internal: cache layout");
     HIPCHK(hipMemcpy2DAsync(p.dec_k, rows_bytes, m->cache->k, pitch, rows_bytes, n_rows, hipMemcpyDeviceToDevice, s));
@@ -2210,21 +2231,18 @@ extern "C" int32_t vox_model_prefix_info(const vox_model* m, int32_t out[4]) {
     return VOX_OK;
 }
 
-// one full sync-free decode step. On entry d_h holds the step's input embedding (audio[cur] + embed(token[cur])):
+// one full sync-free decode step, in the launch form `how` (StepLaunch). On entry d_h holds the step's input embedding (audio[cur] + embed(token[cur])):
 // 26 layers -> final norm + lm_head (argmax partials) -> fused tail: token[cur+1], cur++, next step's d_h.
-// mode 0: the step and the launch that turns its argmax partials into the next token + input (every path).  Engine only -- mode 1: the engine launch alone, its
-// partials left for whoever comes next; mode 2: an engine launch that BEGINS with the argmax of the previous launch's partials (flags 65536): a chain
-// [mode 1] [mode 2] ... [mode 2] [argmax_final] is the same token sequence as mode 0 steps with one launch per token instead of two.
-// eng: engine_bind(m, m->eng_offline, m->cache) said yes for this utterance (modes 1 and 2 exist only then).
-static int32_t decode_step_enqueue(vox_model* m, float* logits_out, bool eng, int mode = 0) {
+// eng: engine_bind(m, m->eng_offline, m->cache) said yes for this utterance (EngineAlone and EngineArgmaxFirst exist only then).
+static int32_t decode_step_enqueue(vox_model* m, float* logits_out, bool eng, StepLaunch how = StepLaunch::StepAndArgmax) {
     const vox_model_cfg& c = m->cfg; hipStream_t s = m->ctx->stream;
     if (eng) {      // one launch: 26 layers + final norm + lm_head + per-CU argmax partials
         EngParams ep = engine_params(m, m->eng_offline, m->cache, m->d_h, m->d_pos, 0, logits_out);
-        if (mode == 2) {      // the launch forms its own input: argmax of the previous launch's partials, token -> d_tokens, embedding + audio row (vox_engine.hip comm_next_input)
+        if (how == StepLaunch::EngineArgmaxFirst) {      // the launch forms its own input: argmax of the previous launch's partials, token -> d_tokens, embedding + audio row (vox_engine.hip comm_next_input)
             ep.flags |= 65536; ep.h_in = nullptr; ep.tokens = m->d_tokens; ep.pos_rw = m->d_pos; ep.tok_qs = m->tok.w.qs; ep.tok_sc = m->tok.w.sc; ep.tok_nb = m->tok.w.nb; ep.audio = m->d_audio;
         }
         HIPCHK(launch_decode_engine(ep, s));
-        if (mode == 0) HIPCHK(launch_argmax_embed(m->d_part_val, m->d_part_idx, 256, m->d_tokens, m->d_pos, m->tok.w, m->d_audio, c.dec_dim, m->d_h, s));
+        if (how == StepLaunch::StepAndArgmax) HIPCHK(launch_argmax_embed(m->d_part_val, m->d_part_idx, 256, m->d_tokens, m->d_pos, m->tok.w, m->d_audio, c.dec_dim, m->d_h, s));
         return VOX_OK;
     }
     VOXCHK(decoder_step_dev(m, m->d_h, m->cache, m->d_pos, 0));
@@ -2233,108 +2251,159 @@ static int32_t decode_step_enqueue(vox_model* m, float* logits_out, bool eng, in
     return VOX_OK;
 }
 
-// transcribe_streaming on device-resident mel [n_mels][T]  (gguf/model.rs:873-963)
+// ---- the single-clip driver (vox_transcribe_streaming, vox_transcribe_audio): transcribe_dev = encode, plan_clip, clip_attempt (seed_clip, run_decode_steps, copy-out,
+// one synchronisation, a verdict on the engine), the re-run policy after a hand-off timeout.
+// What a clip of S decoder positions asks of the decoder.  The reference: fewer than 38 positions give no ids (gguf/model.rs:887-889); the 38-token prefix is prefilled, the
+// argmax of its last row is the first id, tokens[38] (922-926); every pos in 39 .. S-1 is one step and one more id (938).  Here the ids are tokens[38 .. 38 + n_ids): the cache
+// is seeded with rows 0 .. first_pos - 1, then `steps` decode steps run from first_pos on, and first_pos + steps = max(S - 1, 38) rows stand in the cache afterwards.
+//   full form    first_pos = 38 (prefilled; tokens[38] from the prefill's lm_head), steps = max(S - 39, 0), n_ids = 1 + steps
+//   on prefix    first_pos = PC = 37 (rows copied from the model's prefix state; S > 38 there: prefix_usable), steps = S - 38 = n_ids: tokens[38] is the first step's
+struct ClipPlan { int S = 0, n_ids = 0, first_pos = 0, steps = 0; bool on_prefix = false, want_logits = false; };
+static ClipPlan plan_clip(int S, bool on_prefix, int PC, bool want_logits) {
+    ClipPlan p; p.S = S; p.on_prefix = on_prefix; p.want_logits = want_logits;
+    if (S < VOX_PREFIX_TOKENS) return p;      // n_ids == 0: nothing to decode
+    p.n_ids = std::max(S - VOX_PREFIX_TOKENS, 1);
+    p.first_pos = on_prefix ? PC : VOX_PREFIX_TOKENS;
+    p.steps = on_prefix ? S - PC - 1 : std::max(S - VOX_PREFIX_TOKENS - 1, 0);
+    return p;
+}
+
+// Leaves the model ready for the plan's first decode step: prefix tokens, cache rows 0 .. first_pos - 1, d_pos = first_pos; the full form also tokens[38] and (logits
+// tap) logits row 0.  Opens the roctx stage "prefill" behind the token upload.
+static int32_t seed_clip(vox_model* m, const ClipPlan& plan, DevBuf& dlog, RoctxStage& stage) {
+    const vox_model_cfg& c = m->cfg; hipStream_t s = m->ctx->stream;
+    HIPCHK(prefix_tokens_enqueue(m->d_tokens, s));
+    m->cache->len = 0;
+    stage.begin("prefill");
+    if (plan.on_prefix) {
+        // Positions 0 .. PC-1 (= 36) are the model's: their K / V rows are copied into the cache (every call: the cache may have been re-allocated, and a decode overwrites
+        // nothing below PC but a batch call may), and position PC = 37 -- the last prefix token, the first one whose output is kept -- runs as the first ordinary decode
+        // step: no prefill, no separate lm_head; tokens[38] comes out of the same argmax chain as every later token.
+        VOXCHK(prefix_rows_into(m, m->cache, s));
+    } else {
+        VOXCHK(prefill_prefix_rows(m, m->d_audio, plan.first_pos));
+        m->cache->len = plan.first_pos;
+        // lm_head on the last prefix row only (the reference computes all 38 and keeps the last, model.rs:916-923)
+        if (plan.want_logits) HIPCHK(dlog.alloc((size_t)plan.n_ids * c.vocab * 4));
+        VOXCHK(lm_head_argmax_dev(m, m->d_prefix + (size_t)(plan.first_pos - 1) * c.dec_dim, dlog.as<float>()));
+    }
+    HIPCHK(hipMemcpyAsync(m->d_pos, &plan.first_pos, 4, hipMemcpyHostToDevice, s));      // (the plan outlives the attempt's synchronisation)
+    if (!plan.on_prefix) HIPCHK(launch_argmax_final(m->d_part_val, m->d_part_idx, m->n_parts, m->d_tokens, m->d_pos, 0, 0, s));   // tokens[38]
+    return VOX_OK;
+}
+
+// the decode graphs for `key`: whatever was captured under another key is dropped first
+static DecodeGraphs& graphs_for(vox_model* m, const DecodeGraphs::Key& key) {
+    const DecodeGraphs::Key& k = m->graphs.key;
+    if (k.cache != key.cache || k.audio != key.audio || k.unroll != key.unroll || k.launch != key.launch) { graphs_destroy(m); m->graphs.key = key; }
+    return m->graphs;
+}
+// captures n_steps steps of the graphs' launch form as graph `which`; a failed enqueue still ends the capture, the first error is the one reported
+static int32_t graph_capture(vox_model* m, int which, int n_steps, bool eng) {
+    DecodeGraphs& g = m->graphs; hipStream_t s = m->ctx->stream;
+    HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    int32_t r = VOX_OK;
+    for (int i = 0; i < n_steps && r == VOX_OK; i++) r = decode_step_enqueue(m, nullptr, eng, g.key.launch);
+    hipError_t ce = hipStreamEndCapture(s, &g.graph[which]);
+    if (r != VOX_OK) return r;
+    HIPCHK(ce);
+    HIPCHK(hipGraphInstantiate(&g.exec[which], g.graph[which], nullptr, nullptr, 0));
+    return VOX_OK;
+}
+// steps per replayed graph.  VOX_DECODE_UNROLL=U (measurement knob) builds a U-step graph for the bulk of the steps next to the one-step graph; measured in round 2
+// (profiles/r02_decode_knobs.txt): no gain on the per-operator path -- graph boundaries are not where the time goes.  With the engine's one or two launches per step
+// the boundaries show: 8 steps per graph by default there.
+static int decode_unroll(bool eng) { const char* e = knob_str("VOX_DECODE_UNROLL"); return e && atoi(e) >= 1 && atoi(e) <= 32 ? atoi(e) : eng ? 8 : 1; }
+// the one-step graph exists, `done` of `steps` steps are enqueued: the rest as replays, U-step graphs first (built only for long enough utterances), then single steps
+static int32_t replay_rest(vox_model* m, bool eng, int done, int steps) {
+    DecodeGraphs& g = m->graphs; hipStream_t s = m->ctx->stream; const int U = g.key.unroll;
+    if (U > 1 && !g.exec[1] && steps - done >= 2 * U) VOXCHK(graph_capture(m, 1, U, eng));
+    while (U > 1 && g.exec[1] && steps - done >= U) { HIPCHK(hipGraphLaunch(g.exec[1], s)); done += U; m->timings.graph_replays += U; }
+    while (done < steps) { HIPCHK(hipGraphLaunch(g.exec[0], s)); done++; m->timings.graph_replays++; }
+    return VOX_OK;
+}
+// The three step drivers.  (1) eager, a logits row per step (the logits tap): row i + 1 of d_logits_all is the output of step i
+static int32_t steps_eager_logits(vox_model* m, const ClipPlan& plan, bool eng, float* d_logits_all) {
+    int32_t r = VOX_OK; for (int i = 0; i < plan.steps && r == VOX_OK; i++) r = decode_step_enqueue(m, d_logits_all + (size_t)(i + 1) * m->cfg.vocab, eng);
+    return r;
+}
+// (2) graph replay of two-launch steps: the per-operator launches, or the engine under VOX_ENGINE_ARGMAX_IN=0 (measurement knob)
+static int32_t steps_replayed(vox_model* m, const ClipPlan& plan, bool eng) {
+    const DecodeGraphs& g = graphs_for(m, {m->cache, m->d_audio, decode_unroll(eng), StepLaunch::StepAndArgmax});
+    int done = 0;
+    if (!g.exec[0]) {
+        VOXCHK(decode_step_enqueue(m, nullptr, eng)); done = 1;      // eager first step (also warms function attributes)
+        HIPCHK(hipStreamSynchronize(m->ctx->stream));
+        VOXCHK(graph_capture(m, 0, 1, eng));
+    }
+    return replay_rest(m, eng, done, plan.steps);
+}
+// (3) the engine's chained form: a step is ONE launch.  The utterance's first step runs eagerly as a plain launch (its input is in d_h), the replayed launches take
+// their input from the previous launch's argmax partials themselves, and one argmax_final behind the last step writes the last token.
+static int32_t steps_chained(vox_model* m, const ClipPlan& plan) {
+    hipStream_t s = m->ctx->stream;
+    const DecodeGraphs& g = graphs_for(m, {m->cache, m->d_audio, decode_unroll(true), StepLaunch::EngineArgmaxFirst});
+    VOXCHK(decode_step_enqueue(m, nullptr, true, StepLaunch::EngineAlone));
+    if (!g.exec[0]) { HIPCHK(hipStreamSynchronize(s)); VOXCHK(graph_capture(m, 0, 1, true)); }
+    VOXCHK(replay_rest(m, true, 1, plan.steps));
+    HIPCHK(launch_argmax_final(m->d_part_val, m->d_part_idx, 256, m->d_tokens, m->d_pos, 1, 1, s));      // the last step's token
+    return VOX_OK;
+}
+// the plan's decode steps behind seed_clip: the first step's input, then one of the three drivers
+static int32_t run_decode_steps(vox_model* m, const ClipPlan& plan, bool eng, float* d_logits_all) {
+    const vox_model_cfg& c = m->cfg; hipStream_t s = m->ctx->stream;
+    if (plan.steps <= 0) return VOX_OK;
+    VOXCHK(wo_acc_clear(m, s));      // once per utterance
+    HIPCHK(launch_embed(m->tok.w, m->d_tokens, 1, m->d_audio, c.dec_dim, m->d_pos, 0, 0, m->d_h, s));   // input of the first decode step (audio[38] exists iff S >= 39; on the prefix: audio[37] + embed(PAD))
+    if (plan.want_logits) return steps_eager_logits(m, plan, eng, d_logits_all);
+    const char* k = knob_str("VOX_ENGINE_ARGMAX_IN");
+    return eng && !(k && k[0] == '0') ? steps_chained(m, plan) : steps_replayed(m, plan, eng);
+}
+
+// One attempt at the plan on the model's own cache: decode state, engine binding and launch serials, seed_clip, run_decode_steps, ids (and logits) on their way to the
+// caller, the engine's error word behind them, ONE synchronisation.  *eng_timed_out: a bounded hand-off wait expired inside the engine -- the ids of this attempt are
+// not trustworthy (m->eng_offline.err_word holds the code); what happens then is the caller's.
+static int32_t clip_attempt(vox_model* m, const ClipPlan& plan, int32_t* out_ids, float* logits_host, bool* eng_timed_out) {
+    const vox_model_cfg& c = m->cfg; hipStream_t s = m->ctx->stream;
+    *eng_timed_out = false;
+    VOXCHK(ensure_decode_state(m, plan.S));
+    const bool eng = engine_bind(m, m->eng_offline, m->cache); if (eng) VOXCHK(engine_take_serials(m, (unsigned long long)plan.S + 8, s));
+    DevBuf dlog; RoctxStage stage;      // dlog: the logits tap's rows, allocated by seed_clip (null without the tap)
+    VOXCHK(seed_clip(m, plan, dlog, stage));
+    float* const d_logits_all = dlog.as<float>();
+    stage.begin("decode");
+    VOXCHK(run_decode_steps(m, plan, eng, d_logits_all));
+    HIPCHK(hipMemcpyAsync(out_ids, m->d_tokens + VOX_PREFIX_TOKENS, (size_t)plan.n_ids * 4, hipMemcpyDeviceToHost, s));
+    if (plan.want_logits) HIPCHK(hipMemcpyAsync(logits_host, d_logits_all, (size_t)plan.n_ids * c.vocab * 4, hipMemcpyDeviceToHost, s));
+    const bool eng_used = eng && plan.steps > 0;
+    if (eng_used) VOXCHK(engine_err_enqueue(m, m->eng_offline.err_word, s));
+    HIPCHK(hipStreamSynchronize(s));
+    stage.end();
+    *eng_timed_out = eng_used && m->eng_offline.err_word[0] != 0;
+    return VOX_OK;
+}
+
+// transcribe_streaming on device-resident mel [n_mels][T]  (gguf/model.rs:873-963): encode, plan, attempt, the re-run policy, bookkeeping.
 // from_padded_samples: d_mel is the log-mel of samples the library itself padded (vox_transcribe_audio) -- the only case in which the model's prefix state stands for the
 // first encoder rows and decoder positions (a caller's own mel may hold anything there).
 static int32_t transcribe_dev(vox_model* m, const float* d_mel, int T, const float* t_embed, int32_t* out_ids, int32_t cap, int32_t* n_ids,
                               float* logits_host, bool from_padded_samples = false) {
-    const vox_model_cfg& c = m->cfg; vox_ctx* cx = m->ctx; hipStream_t s = cx->stream;
-    const int PREFIX_LEN = VOX_PREFIX_TOKENS, BOS = VOX_TOK_BOS, STREAMING_PAD = VOX_TOK_STREAMING_PAD;
     VOXCHK(vox_model_set_t_embed(m, t_embed));
     const bool pfx = from_padded_samples && !logits_host && prefix_usable(m, T);      // (prefix_build ran before the mel was made: vox_transcribe_audio)
-    const int PC = pfx ? m->pfx.PC : 0;
     double t0 = now_ms();
-    RoctxScope whole("transcribe_streaming"); RoctxStage stage;
-    stage.begin("encode_audio");
-    int S = 0; VOXCHK(encode_dev(m, d_mel, T, &S, pfx ? m->pfx.RC : 0));
-    HIPCHK(hipStreamSynchronize(s));                       // e2e_bench.rs:161-167 forces a sync here too
+    RoctxScope whole("transcribe_streaming");
+    int S = 0; RoctxStage stage; stage.begin("encode_audio");
+    VOXCHK(encode_dev(m, d_mel, T, &S, pfx ? m->pfx.RC : 0));
+    HIPCHK(hipStreamSynchronize(m->ctx->stream));                       // e2e_bench.rs:161-167 forces a sync here too
     stage.end();
     m->timings.encode_ms = now_ms() - t0; t0 = now_ms();
     *n_ids = 0; m->timings.decode_tokens = 0; m->timings.graph_replays = 0;
-    if (S < PREFIX_LEN) { m->timings.decode_ms = 0; return VOX_OK; }               // model.rs:887-889
-    const int n = std::max(S - PREFIX_LEN, 1);                                      // S == 38: prefill + first token only (model.rs:922-926,938)
-    ARGCHK(cap >= n, "out_ids capacity %d < %d", cap, n);
-    bool eng_failed = false; int steps = 0;
-    auto decode_once = [&]() -> int32_t {
-    VOXCHK(ensure_decode_state(m, S));
-    const bool eng = engine_bind(m, m->eng_offline, m->cache); if (eng) VOXCHK(engine_take_serials(m, (unsigned long long)S + 8, s));
-    std::vector<int32_t> prefix(PREFIX_LEN, STREAMING_PAD); prefix[0] = BOS;      // model.rs:891-892
-    HIPCHK(hipMemcpyAsync(m->d_tokens, prefix.data(), PREFIX_LEN * 4, hipMemcpyHostToDevice, s));
-    m->cache->len = 0;
-    DevBuf dlog; float* d_logits_all = nullptr;
-    stage.begin("prefill");
-    if (pfx) {
-        // Positions 0 .. PC-1 (= 36) are the model's: their K / V rows are copied into the cache (every call: the cache may have been re-allocated, and a decode overwrites
-        // nothing below PC but a batch call may), and position PC = 37 -- the last prefix token, the first one whose output is kept -- runs as the first ordinary decode
-        // step below: no prefill, no separate lm_head; tokens[38] comes out of the same argmax chain as every later token.
-        VOXCHK(prefix_rows_into(m, m->cache, s));
-        HIPCHK(hipMemcpyAsync(m->d_pos, &PC, 4, hipMemcpyHostToDevice, s));
-        steps = S - PC - 1;                                              // pos = 37 .. S-2
-    } else {
-    // prefix inputs = audio[:38] + embed(prefix)  (model.rs:896-902)
-    if (!m->d_prefix) HIPCHK(hipMalloc((void**)&m->d_prefix, (size_t)PREFIX_LEN * c.dec_dim * 4));   // model-owned: no hipMalloc/hipFree in the timed path
-    float* px = m->d_prefix;
-    HIPCHK(launch_embed(m->tok.w, m->d_tokens, PREFIX_LEN, m->d_audio, c.dec_dim, nullptr, 0, 0, px, s));
-    VOXCHK(decoder_prefill_dev(m, px, PREFIX_LEN, m->cache, 0));
-    m->cache->len = PREFIX_LEN;
-    // lm_head on the last prefix row only (the reference computes all 38 and keeps the last, model.rs:916-923)
-    if (logits_host) { HIPCHK(dlog.alloc((size_t)n * c.vocab * 4)); d_logits_all = dlog.as<float>(); }
-    VOXCHK(lm_head_argmax_dev(m, px + (size_t)(PREFIX_LEN - 1) * c.dec_dim, d_logits_all));
-    const int pos_init = PREFIX_LEN;
-    HIPCHK(hipMemcpyAsync(m->d_pos, &pos_init, 4, hipMemcpyHostToDevice, s));
-    HIPCHK(launch_argmax_final(m->d_part_val, m->d_part_idx, m->n_parts, m->d_tokens, m->d_pos, 0, 0, s));   // tokens[38]
-    steps = std::max(S - PREFIX_LEN - 1, 0);                            // pos = 39 .. S-1 (model.rs:938)
-    }
-    stage.begin("decode");
-    if (steps > 0) VOXCHK(wo_acc_clear(m, s));      // once per utterance
-    if (steps > 0) HIPCHK(launch_embed(m->tok.w, m->d_tokens, 1, m->d_audio, c.dec_dim, m->d_pos, 0, 0, m->d_h, s));   // input of the first decode step (audio[38] exists iff S >= 39; on the prefix: audio[37] + embed(PAD))
-    if (logits_host) {
-        for (int i = 0; i < steps; i++) VOXCHK(decode_step_enqueue(m, d_logits_all + (size_t)(i + 1) * c.vocab, eng));
-    } else if (steps > 0) {
-        // Replayed graphs: one step per graph by default.  VOX_DECODE_UNROLL=U (measurement knob) also builds a U-step graph for the bulk of
-        // the steps; measured in round 2 (profiles/r02_decode_knobs.txt): no gain -- graph boundaries are not where the time goes.
-        // Engine path: the replayed launches take their input from the previous launch's argmax partials themselves (mode 2), so a step is ONE launch; the
-        // utterance's first step runs eagerly as a plain launch (mode 1) and one argmax_final behind the last step writes the last token.  VOX_ENGINE_ARGMAX_IN=0:
-        // the two-launch step (measurement knob).  With one or two launches per step the graph boundaries show: 8 steps per graph by default (engine path).
-        const bool chain = eng && !(knob_str("VOX_ENGINE_ARGMAX_IN") && knob_str("VOX_ENGINE_ARGMAX_IN")[0] == '0');
-        const int step_mode = chain ? 2 : 0;
-        int U = eng ? 8 : 1; { const char* e = knob_str("VOX_DECODE_UNROLL"); if (e && atoi(e) >= 1 && atoi(e) <= 32) U = atoi(e); }
-        if (m->graph_cache != m->cache || m->graph_audio != m->d_audio || m->graph_unroll != U || m->graph_mode != step_mode) {
-            graphs_destroy(m); m->graph_cache = m->cache; m->graph_audio = m->d_audio; m->graph_unroll = U; m->graph_mode = step_mode;
-        }
-        auto capture = [&](int which, int n_steps) -> int32_t {
-            HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-            int32_t r = VOX_OK;
-            for (int i = 0; i < n_steps && r == VOX_OK; i++) r = decode_step_enqueue(m, nullptr, eng, step_mode);
-            hipError_t ce = hipStreamEndCapture(s, &m->graph[which]);
-            if (r != VOX_OK) return r;
-            HIPCHK(ce);
-            HIPCHK(hipGraphInstantiate(&m->graph_exec[which], m->graph[which], nullptr, nullptr, 0));
-            return VOX_OK;
-        };
-        int done = 0;
-        if (chain) { VOXCHK(decode_step_enqueue(m, nullptr, eng, 1)); done = 1; }       // the utterance's first step: its input is in d_h
-        if (!m->graph_exec[0]) {
-            if (!chain) { VOXCHK(decode_step_enqueue(m, nullptr, eng)); done = 1; }     // eager first step (also warms function attributes)
-            HIPCHK(hipStreamSynchronize(s));
-            VOXCHK(capture(0, 1));
-        }
-        if (U > 1 && !m->graph_exec[1] && steps - done >= 2 * U) VOXCHK(capture(1, U));      // only worth building for long enough utterances
-        while (U > 1 && m->graph_exec[1] && steps - done >= U) { HIPCHK(hipGraphLaunch(m->graph_exec[1], s)); done += U; m->timings.graph_replays += U; }
-        while (done < steps) { HIPCHK(hipGraphLaunch(m->graph_exec[0], s)); done++; m->timings.graph_replays++; }
-        if (chain) HIPCHK(launch_argmax_final(m->d_part_val, m->d_part_idx, 256, m->d_tokens, m->d_pos, 1, 1, s));      // the last step's token
-    }
-    HIPCHK(hipMemcpyAsync(out_ids, m->d_tokens + PREFIX_LEN, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    if (logits_host) HIPCHK(hipMemcpyAsync(logits_host, d_logits_all, (size_t)n * c.vocab * 4, hipMemcpyDeviceToHost, s));
-    const bool eng_used = eng && steps > 0;
-    if (eng_used) VOXCHK(engine_err_enqueue(m, m->eng_offline.err_word, s));
-    HIPCHK(hipStreamSynchronize(s));
-    stage.end();
-    if (eng_used && m->eng_offline.err_word[0]) { eng_failed = true; return VOX_OK; }
-    return VOX_OK;
-    };
-    VOXCHK(decode_once());
-    if (eng_failed) {
+    const ClipPlan plan = plan_clip(S, pfx, m->pfx.PC, logits_host != nullptr);
+    if (plan.n_ids == 0) { m->timings.decode_ms = 0; return VOX_OK; }
+    ARGCHK(cap >= plan.n_ids, "out_ids capacity %d < %d", cap, plan.n_ids);
+    bool timed_out = false;
+    VOXCHK(clip_attempt(m, plan, out_ids, logits_host, &timed_out));
+    if (timed_out) {
         // A bounded hand-off wait expired inside the engine: its 256 workgroups were not co-resident for 20 ms (another kernel on the GPU, a CU mask, a debugger).  The ids
         // of that attempt are not trustworthy -- the SAME utterance is decoded again on the per-operator launches (the encoder output is still in place), the engine is
         // re-armed for the next utterance, and after three strikes it is switched off for the life of the model.
@@ -2342,12 +2411,12 @@ static int32_t transcribe_dev(vox_model* m, const float* d_mel, int T, const flo
         VOXCHK(engine_strike(m));
         fprintf(stderr, "[voxtral_hip] decode engine: %s; this utterance is decoded again on the per-operator path%s\n",
                 engine_timeout_text(e, m->eng_strikes).c_str(), m->eng_strikes >= 3 ? ", the engine is switched off" : "");
-        eng_failed = false; int32_t r; { EngSuspend off(m); r = decode_once(); }
+        int32_t r; { EngSuspend off(m); r = clip_attempt(m, plan, out_ids, logits_host, &timed_out); }
         graphs_destroy(m);      // (the graph captured during the re-run holds the per-operator launches)
         if (r != VOX_OK) return r;
     }
-    m->cache->len = (pfx ? PC : PREFIX_LEN) + steps;
-    *n_ids = n; m->timings.decode_tokens = n;
+    m->cache->len = plan.first_pos + plan.steps;
+    *n_ids = plan.n_ids; m->timings.decode_tokens = plan.n_ids;
     m->timings.decode_ms = now_ms() - t0;
     return VOX_OK;
 }
@@ -2456,7 +2525,7 @@ static int32_t front_end_units(const MelTables& mt, int i0, int nu, const float*
 // prefix tokens (BOS + STREAMING_PAD), first positions (the prefix's last row) and sequence lengths of n utterances up to the device (gguf/model.rs:887-902)
 static int32_t upload_prefix(int n, int tstride, const std::vector<int>& len, int* d_tok, int* d_pos, int* d_len, hipStream_t s) {
     std::vector<int32_t> prefix((size_t)n * tstride, 0); std::vector<int> pos0(n, VOX_PREFIX_TOKENS - 1);
-    for (int i = 0; i < n; i++) { prefix[(size_t)i * tstride] = VOX_TOK_BOS; for (int r = 1; r < VOX_PREFIX_TOKENS; r++) prefix[(size_t)i * tstride + r] = VOX_TOK_STREAMING_PAD; }
+    for (int i = 0; i < n; i++) std::copy(PREFIX_TOKENS.t, PREFIX_TOKENS.t + VOX_PREFIX_TOKENS, prefix.begin() + (size_t)i * tstride);
     HIPCHK(hipMemcpyAsync(d_tok, prefix.data(), prefix.size() * 4, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(d_pos, pos0.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(d_len, len.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipStreamSynchronize(s));      // the host vectors go out of scope
@@ -4014,7 +4083,7 @@ struct vox_stream {
     uint64_t eng_steps = 0, op_steps = 0, verified_eng_steps = 0, verified_op_steps = 0, bytes = 0;
     EngBinding eng;      // the decode engine's layer table for the stream's cache, its argmax partials (256), the pinned host copy of its error word
     float* tap = nullptr; int tap_max = 0, tap_rows = 0;
-    int h_state[STRM_WORDS]; int h_pos_word = 0; std::vector<int32_t> h_prefix;
+    int h_state[STRM_WORDS]; int h_pos_word = 0;
 };
 
 static long stream_spp(int R) { return 640L * R; }      // samples per decoder position: R encoder rows x 4 frames x 160
@@ -4069,8 +4138,7 @@ static int32_t stream_load_initial(vox_stream* st) {
         // the engine's view of THIS cache, in the stream's own binding: no table is rebuilt (and nothing synchronised) when streams, piecewise and offline callers alternate;
         // uploaded here, behind this function's synchronisation, so that the first step finds its cache bound
         HIPCHK(engine_tab_enqueue(m, st->eng, st->dec));
-        st->h_prefix.assign(VOX_PREFIX_TOKENS, VOX_TOK_STREAMING_PAD); st->h_prefix[0] = VOX_TOK_BOS;
-        HIPCHK(hipMemcpyAsync(st->tokens, st->h_prefix.data(), st->h_prefix.size() * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(prefix_tokens_enqueue(st->tokens, s));
         std::memset(st->h_state, 0, sizeof st->h_state);
         st->h_state[STRM_POS] = PC; st->h_state[STRM_ENC_POS] = RC; st->h_state[STRM_FRAME] = 4 * RC; st->h_state[STRM_HEAD] = RC % st->cap;
         HIPCHK(hipMemcpyAsync(st->state, st->h_state, sizeof st->h_state, hipMemcpyHostToDevice, s));
