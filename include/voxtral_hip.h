@@ -410,6 +410,13 @@ int32_t vox_debug_batch_tap_fetch(vox_model* m, float* out, int32_t* rows_per_un
  * encoder rows, w2 split-K slices, wo split-K slices (0 = unsplit), q|k|v launches that ran RoPE in the GEMM's epilogue.  VOX_ERR_INVALID on bad arguments. */
 int32_t vox_debug_encode_batch(vox_model* m, int32_t n, const float* const* mels, const int32_t* T, int32_t layout, float* out, int64_t cap_rows,
                                int32_t* rows_per_clip, int64_t* report);
+/* The sample front ends on their own (tests), through the functions the drivers run.  form 0: the single clip's (vox_transcribe_audio: peak scale, virtual pad, log-mel;
+ * n == 1, norm_group NULL); form 1: the batch drivers' (vox_transcribe_batch / _ex: host samples packed back to back -- with norm_group each unit 16-byte aligned and
+ * the group peaks reduced first --, device samples read where they are).  n <= 128 units; samples[i] host or device (mem_kind), the outputs are always host memory:
+ * out_scales[i] the scale unit i was multiplied by (0.95 / peak of the unit or of its group; 1 for silence or a negative group), out_mels[i] its log-mel [128][out_T[i]]
+ * as the encoder receives it (room for 128 * vox_pad_len(n_samples[i]) / 160 floats), out_T[i] its frame count.  VOX_ERR_INVALID on bad arguments, before any device is touched. */
+int32_t vox_debug_front_end(vox_model* m, int32_t n, const float* const* samples, const size_t* n_samples, const int32_t* norm_group_or_null, int32_t form,
+                            int32_t mem_kind, float* out_scales, float* const* out_mels, int32_t* out_T);
 /* The continuous batch driver's planner on its own (tests): host arithmetic only -- no context, no device.  _step_costs: the per-step cost in ms of 1..8 lock-step
  * groups (index 0 unused, written as 0) the planner prices a call with, from a cost table `base` and the step times `meas` a context has measured (0 = form not seen
  * yet); calib 0: the table alone; shared != 0: a GPU shared with other sessions (the common measured / table ratio only).  _plan_slots: job i needs steps[i] >= 1 decode
@@ -466,6 +473,13 @@ int32_t vox_stream_schedule(size_t n_samples, int32_t finished, int32_t* positio
  * ([min(rows, max_rows)][vocab]; *rows = rows produced since arm) and ends the tap */
 int32_t vox_debug_stream_tap_arm(vox_stream* s, int32_t max_rows);
 int32_t vox_debug_stream_tap_fetch(vox_stream* s, float* out_rows_x_vocab, int32_t* rows);
+/* front-end tap (tests), same rules as the logits tap (an arm drops the rows of an earlier arm, fetch ends the tap, vox_stream_reset starts the count again): while armed
+ * every tick copies, device to device on the stream and without synchronising, its 16 fresh log-mel frames ([16][n_mels], token-major: frames 16 p .. 16 p + 15 of the
+ * tick at decoder position p) and its 4 conv-stem rows ([4][enc_dim], the encoder's input rows 4 p .. 4 p + 3); nothing is launched when no tap is armed.  A decode
+ * engine hand-off re-run repeats decode steps, never ticks, so the tick count and the rows do not depend on it.  _fetch: out_mel [min(ticks, max_ticks)][16][n_mels],
+ * out_conv [min(ticks, max_ticks)][4][enc_dim], *ticks = ticks run since arm. */
+int32_t vox_debug_stream_front_tap_arm(vox_stream* s, int32_t max_ticks);
+int32_t vox_debug_stream_front_tap_fetch(vox_stream* s, float* out_mel, float* out_conv, int32_t* ticks);
 
 #ifdef __cplusplus
 }

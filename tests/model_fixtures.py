@@ -96,6 +96,17 @@ def check_batch_rows(pkg, ctx, model, clips, t_embed, outs, tol):
     return identical
 
 
+def gguf_conv_weights(pkg, path, enc_dim, n_mels):
+    """The conv stem's f32 tensors of a GGUF: (w1 [enc_dim][n_mels][3], b1, w2 [enc_dim][enc_dim][3], b2)."""
+    r = pkg.GgufReader.open(path); pfx = "mm_streams_embeddings.embedding_module.whisper_encoder.conv_layers."
+    try:
+        t = {k: r.tensor_data(pfx + k).view(np.float32) for k in ("0.conv.weight", "0.conv.bias", "1.conv.weight", "1.conv.bias")}
+    finally:
+        r.close()
+    assert t["0.conv.weight"].size == enc_dim * n_mels * 3 and t["1.conv.weight"].size == enc_dim * enc_dim * 3 and t["0.conv.bias"].size == t["1.conv.bias"].size == enc_dim
+    return t["0.conv.weight"].reshape(enc_dim, n_mels, 3), t["0.conv.bias"], t["1.conv.weight"].reshape(enc_dim, enc_dim, 3), t["1.conv.bias"]
+
+
 PREFIX = [1] + [32] * 37      # BOS + 37 x STREAMING_PAD: the decoder's 38-token prefix (gguf/model.rs:887-902)
 
 

@@ -179,6 +179,37 @@ def test_batch_tap_symbols_and_bad_arguments(pkg):
     assert L.vox_debug_batch_tap_fetch(None, out.ctypes.data, rows) == 1
 
 
+def test_front_end_hooks_symbols_and_bad_arguments(pkg):
+    """The front-end hooks (vox_debug_front_end, vox_debug_stream_front_tap_*) are exported and bound, and refuse bad arguments with VOX_ERR_INVALID before they touch a device."""
+    L = pkg.lib()
+    for name in ("vox_debug_front_end", "vox_debug_stream_front_tap_arm", "vox_debug_stream_front_tap_fetch"):
+        assert hasattr(L, name) and name in pkg._lib.SIGNATURES
+    x = np.zeros(1600, np.float32); mel = np.zeros((128, 1024), np.float32)
+    smp = (C.c_void_p * 2)(x.ctypes.data, x.ctypes.data); ns = (C.c_size_t * 2)(1600, 1600); grp = (C.c_int32 * 2)(0, 0)
+    outs = (C.c_void_p * 2)(mel.ctypes.data, mel.ctypes.data); sc = np.zeros(2, np.float32); T = (C.c_int32 * 2)()
+    dummy = C.c_void_p(1)      # a model pointer that must never be dereferenced: every case fails on an argument checked before the model is read
+    cases = [((None, 1, smp, ns, None, 0, 0, sc.ctypes.data, outs, T), "null argument"), ((dummy, 1, None, ns, None, 0, 0, sc.ctypes.data, outs, T), "null argument"),
+             ((dummy, 1, smp, None, None, 0, 0, sc.ctypes.data, outs, T), "null argument"), ((dummy, 1, smp, ns, None, 0, 0, None, outs, T), "null argument"),
+             ((dummy, 1, smp, ns, None, 0, 0, sc.ctypes.data, None, T), "null argument"), ((dummy, 1, smp, ns, None, 0, 0, sc.ctypes.data, outs, None), "null argument"),
+             ((dummy, 1, smp, ns, None, 2, 0, sc.ctypes.data, outs, T), "form"), ((dummy, 1, smp, ns, None, -1, 0, sc.ctypes.data, outs, T), "form"),
+             ((dummy, 1, smp, ns, None, 1, 2, sc.ctypes.data, outs, T), "mem_kind"), ((dummy, 0, smp, ns, None, 1, 0, sc.ctypes.data, outs, T), "out of range"),
+             ((dummy, 129, smp, ns, None, 1, 0, sc.ctypes.data, outs, T), "out of range"), ((dummy, 2, smp, ns, None, 0, 0, sc.ctypes.data, outs, T), "single-clip"),
+             ((dummy, 1, smp, ns, grp, 0, 0, sc.ctypes.data, outs, T), "single-clip"),
+             ((dummy, 2, smp, (C.c_size_t * 2)(1600, 0), None, 1, 0, sc.ctypes.data, outs, T), "slot 1"),
+             ((dummy, 2, (C.c_void_p * 2)(x.ctypes.data, None), ns, None, 1, 0, sc.ctypes.data, outs, T), "slot 1"),
+             ((dummy, 2, smp, ns, None, 1, 0, sc.ctypes.data, (C.c_void_p * 2)(mel.ctypes.data, None), T), "slot 1")]
+    for args, msg in cases:
+        assert L.vox_debug_front_end(*args) == 1, args
+        assert msg in L.vox_last_error().decode(), (args, L.vox_last_error())
+    for mt in (0, -1, 65537):
+        assert L.vox_debug_stream_front_tap_arm(dummy, mt) == 1 and "max_ticks" in L.vox_last_error().decode()
+    assert L.vox_debug_stream_front_tap_arm(None, 4) == 1 and "null stream" in L.vox_last_error().decode()
+    n = C.c_int32()
+    for args in ((None, mel.ctypes.data, mel.ctypes.data, C.byref(n)), (dummy, None, mel.ctypes.data, C.byref(n)), (dummy, mel.ctypes.data, None, C.byref(n)),
+                 (dummy, mel.ctypes.data, mel.ctypes.data, None)):
+        assert L.vox_debug_stream_front_tap_fetch(*args) == 1 and "null argument" in L.vox_last_error().decode()
+
+
 def test_debug_encode_batch_symbol_and_bad_arguments(pkg):
     """The stacked-encoder hook (vox_debug_encode_batch) is exported and bound, and refuses bad arguments with VOX_ERR_INVALID before it touches a device."""
     L = pkg.lib()

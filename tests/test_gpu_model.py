@@ -55,7 +55,8 @@ def test_embed_tokens(tiny):
     assert (m.decoder().embed_tokens_from_ids(ids, 1, 5)[0] == o.embed_tokens(ids)).all()     # exact: pure dequant
 
 
-@pytest.mark.parametrize("T", [64, 250, 1144, 3400])      # 3400 frames -> 850 encoder positions > the 750 sliding window (masking.rs:26-44)
+# 3400 frames -> 850 encoder positions > the 750 sliding window (masking.rs:26-44); 16 .. 19, 65, 67: minimal and odd T / odd T1 of the conv stem's zero-row im2col layout
+@pytest.mark.parametrize("T", [64, 250, 1144, 3400, 16, 17, 18, 19, 65, 67])
 def test_encode_audio(tiny, T):
     m, o, _ = tiny
     mel = fake_mel(T, seed=T)
@@ -74,6 +75,20 @@ def test_encode_audio_conv_valu_cross_check_path(tiny, monkeypatch):
     b = m.encode_audio(mel[None])
     monkeypatch.delenv("VOX_CONV_VALU")
     assert rel_err(b[0], ref) < TOL and rel_err(a[0], b[0]) < TOL, (rel_err(b[0], ref), rel_err(a[0], b[0]))
+
+
+@pytest.mark.parametrize("T", [16, 17, 18, 19, 65, 67])
+def test_encode_audio_conv_valu_odd_frame_counts(tiny, monkeypatch, T):
+    """The same cross-check at minimal and odd frame counts: T odd / even and T1 = (T - 1) // 2 + 1 odd / even, where the im2col layout's last window ends on the zero
+    row behind the frames or one row short of it."""
+    m, o, _ = tiny
+    mel = fake_mel(T, seed=T)
+    ref = o.encode_audio(mel); a = m.encode_audio(mel[None])
+    monkeypatch.setenv("VOX_CONV_VALU", "1")
+    b = m.encode_audio(mel[None])
+    monkeypatch.delenv("VOX_CONV_VALU")
+    assert a.shape == b.shape == (1,) + ref.shape and ref.shape[0] == o.enc_seq_len(T) // 4 >= 1
+    assert rel_err(b[0], ref) < TOL and rel_err(a[0], b[0]) < TOL and rel_err(a[0], ref) < TOL, (rel_err(b[0], ref), rel_err(a[0], b[0]))
 
 
 def test_encode_audio_too_short(tiny):

@@ -422,3 +422,108 @@ def test_steady_ticks_launch_no_prefill_form(pkg, ctx, model):
     assert not {"prefill_small", "prefill_mfma", "prefill_f32"} & set(da)
     assert not {"big", "big_rope", "wide", "skinny", "skinny_mt", "skinny_mt2", "tile_11", "tile_12", "tile_21", "tile_22"} & set(dg)
     assert dg.get("dense2", 0) == 2 * 50      # the conv stem: two small im2col GEMMs per tick
+
+
+# ---- 9. the front end's values: stream_mel_kernel on the sample ring, the conv stem as two GEMMs on the halo buffer -------------------------------------------------
+# (vox_debug_stream_front_tap_*; the float64 reference of tests/frontend_ref.py and the bars of tests/test_gpu_front_end.py; worst errors: DESIGN.md section 4)
+FRONT_SECONDS = 9.0      # 144 000 samples: the 65 536-sample ring wraps twice, frames straddle both wrap points
+
+
+def _front_clip():
+    import frontend_ref as F
+    x = F.make_clip("noise", 9, FRONT_SECONDS)
+    assert len(x) == 144000 and F.pad_len(len(x)) // 2560 == 103
+    return x
+
+
+def _front_tapped(pkg, st, x, cuts):
+    """One utterance with the front tap armed: (log-mel [128][16 ticks] of frames 592 .., conv rows [4 ticks][enc_dim] of rows 148 ..), ticks = positions 37 .. S - 2."""
+    import frontend_ref as F
+    ticks = F.pad_len(len(x)) // 2560 - 1 - 37
+    st.front_tap_arm(ticks + 3)
+    _run(pkg, st, x, cuts)
+    mel, conv = st.front_tap_fetch()
+    assert mel.shape[0] == conv.shape[0] == ticks
+    return np.ascontiguousarray(mel.reshape(ticks * 16, -1).T), conv.reshape(ticks * 4, -1)
+
+
+def _front_mel_check(mel, x, gain, tables, label):
+    import frontend_ref as F
+    ref = F.log_mel(F.pad(np.float64(np.float32(gain)) * x.astype(np.float64)), *tables)[:, 592:592 + mel.shape[1]]
+    inside = F.clip_frames(len(x), 592 + mel.shape[1])[592:]
+    assert ref.shape == mel.shape and (ref[:, inside] > F.FLOOR + 0.05).mean() >= 0.5      # not floor against floor
+    err = np.abs(mel - ref); worst = float(err.max())
+    assert worst <= 1e-4, f"{label}: stream log-mel {worst:.3e} off the float64 reference at (mel bin, frame) {np.unravel_index(np.argmax(err), err.shape)} (+592)"
+    assert (mel[:, ~inside] == np.float32(F.FLOOR)).all()
+    return worst
+
+
+def test_stream_front_end_values(pkg, ctx, model):
+    """The tapped log-mel frames [16 p, 16 p + 16), p = 37 .. S - 2, against log_mel(pad(gain x)) and against the single clip's front end on the same clip (same gain);
+    the tapped conv rows against conv_stem on the TAPPED mel (so the bar covers the conv alone): per row 2e-5 max_j |pre_ij|, carried through the GELU
+    (linear_ref.carry_bound), the bar of tests/test_gpu_linear.py.  The conv weights are read from the GGUF."""
+    import frontend_ref as F
+    from linear_ref import EPI_GELU, carry_bound
+    from model_fixtures import gguf_conv_weights
+    m, size = model
+    tables = (pkg.MelSpectrogram.mel_filterbank(), pkg.MelSpectrogram.hann_window(400))
+    x = _front_clip(); t = _t(pkg, m); gain = _gain(x)
+    st = m.create_stream(t, gain=gain)
+    try:
+        mel, conv = _front_tapped(pkg, st, x, _pieces(len(x), 2560))
+    finally:
+        st.close()
+    assert mel.shape == (128, 16 * 65) and conv.shape == (4 * 65, m.config.enc_dim)
+    worst = _front_mel_check(mel, x, gain, tables, size)
+    sc, mels = m.debug_front_end([x], 0)
+    assert sc[0] == np.float32(gain)
+    off = mels[0][:, 592:592 + mel.shape[1]]
+    d = float(np.abs(mel - off).max())
+    assert d <= 1e-4
+    print(f"{size}: stream log-mel, 65 ticks over two ring wraps: worst error {worst:.2e} vs float64; vs the single clip's front end {d:.2e}, bit-identical: {np.array_equal(mel, off)}")
+    w1, b1, w2, b2 = gguf_conv_weights(pkg, tiny_gguf()[0] if size == "tiny" else _full_path(True), m.config.enc_dim, m.config.n_mels)
+    full = np.full((128, 592 + mel.shape[1]), np.float32(F.FLOOR), np.float32); full[:, 592:] = mel      # frames below 592 see the left pad's zeros alone
+    ref, pre = F.conv_stem(full, w1, b1, w2, b2)
+    ref, pre = ref[148:], pre[148:]
+    assert ref.shape == conv.shape
+    bound = carry_bound(pre, 2e-5 * np.abs(pre).max(axis=1)[:, None], EPI_GELU)
+    err = np.abs(conv - ref); ratio = float((err / bound).max())
+    print(f"{size}: stream conv rows 148 .. {148 + len(conv) - 1}: worst error {err.max():.2e} at max |row| {np.abs(ref).max():.2f}, {ratio:.3f} x the bound")
+    assert (err <= bound).all(), f"{size}: conv row {148 + int(np.argmax((err / bound).max(axis=1)))} is {ratio:.2f} x its bound"
+
+
+def test_stream_front_end_cut_independence(pkg, ctx, model):
+    """The tapped log-mel frames and conv rows do not depend on how the samples were cut into pushes: bit for bit."""
+    m, size = model
+    x = _front_clip(); t = _t(pkg, m); n = len(x)
+    rng = np.random.default_rng(77)
+    rnd = [0]
+    while rnd[-1] < n:
+        rnd.append(min(n, rnd[-1] + int(rng.choice([0, 0, 1, 39, 40, 41, 333, 2559, 2560, 2561, 7000, 30001]))))
+    cuts = {"one push": [(0, n)], "2560": _pieces(n, 2560), "30001": _pieces(n, 30001), "70000 then the rest": [(0, 70000), (70000, n)],
+            "random with empty pushes": list(zip(rnd[:-1], rnd[1:]))}
+    st = m.create_stream(t, gain=_gain(x))
+    try:
+        out = {}
+        for k, c in cuts.items():
+            out[k] = _front_tapped(pkg, st, x, c); st.reset()
+    finally:
+        st.close()
+    ref = out["one push"]
+    for k, v in out.items():
+        assert np.array_equal(v[0], ref[0]), f"{size}: log-mel of '{k}' differs from the one-push run in frames {592 + np.unique(np.nonzero(v[0] != ref[0])[1])[:8]}"
+        assert np.array_equal(v[1], ref[1]), f"{size}: conv rows of '{k}' differ from the one-push run in rows {148 + np.unique(np.nonzero(v[1] != ref[1])[0])[:8]}"
+
+
+def test_stream_gain_reaches_the_mel(pkg, ctx, model):
+    """A gain that is not the clip's own (0.5) appears in the log-mel as the reference says."""
+    m, size = model
+    tables = (pkg.MelSpectrogram.mel_filterbank(), pkg.MelSpectrogram.hann_window(400))
+    x = _front_clip()[:40000]; t = _t(pkg, m)
+    assert abs(_gain(x) - 0.5) > 0.1
+    st = m.create_stream(t, gain=0.5)
+    try:
+        mel, _ = _front_tapped(pkg, st, x, [(0, len(x))])
+    finally:
+        st.close()
+    print(f"{size}: stream log-mel at gain 0.5: worst error {_front_mel_check(mel, x, 0.5, tables, size):.2e}")

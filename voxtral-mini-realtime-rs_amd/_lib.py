@@ -161,6 +161,9 @@ SIGNATURES = {
     "vox_stream_schedule": (i32, [sz, i32, P(i32), P(i32)]),
     "vox_debug_stream_tap_arm": (i32, [vp, i32]),
     "vox_debug_stream_tap_fetch": (i32, [vp, vp, P(i32)]),
+    "vox_debug_stream_front_tap_arm": (i32, [vp, i32]),
+    "vox_debug_stream_front_tap_fetch": (i32, [vp, vp, vp, P(i32)]),
+    "vox_debug_front_end": (i32, [vp, i32, P(vp), P(sz), P(i32), i32, i32, vp, P(vp), P(i32)]),
 }
 
 _LIB = None

@@ -2451,14 +2451,10 @@ extern "C" int32_t vox_transcribe_streaming(vox_model* m, const float* mel, int3
     return VOX_OK;
 }
 
-extern "C" int32_t vox_transcribe_audio(vox_model* m, const float* samples, size_t n, const float* t_embed, int32_t* out_ids, int32_t cap,
-                                        int32_t* n_ids, int32_t mem_kind) {
-    ARGCHK(m && samples && t_embed && out_ids && n_ids, "null argument"); ARGCHK(n > 0, "empty audio"); VOXCHK(ctx_bind(m->ctx));
-    const vox_model_cfg& c = m->cfg; vox_ctx* cx = m->ctx; hipStream_t s = cx->stream;
-    ARGCHK(c.n_mels == 128, "the log-mel front-end produces 128 bins; model expects %d", c.n_mels);
-    m->timings = vox_timings{};
-    VOXCHK(prefix_build(m, t_embed));      // nothing to do once the model holds its prefix state for this t_embed (the first call of a model pays it, outside the stage times)
-    const double t0 = now_ms();
+// the single clip's front end on the context's stream, no synchronisation: samples up (host), peak scale into the context's cell (peak_normalize(0.95), transcribe.rs:207),
+// (virtual) pad + log-mel [128][*T_out] into m->d_mel
+static int32_t clip_front_end(vox_model* m, const float* samples, size_t n, int32_t mem_kind, int* T_out) {
+    vox_ctx* cx = m->ctx; hipStream_t s = cx->stream;
     const float* d_s = samples;
     if (mem_kind == VOX_MEM_HOST) {
         VOXCHK(ensure(&m->d_samples, &m->samples_cap, n));
@@ -2468,11 +2464,23 @@ extern "C" int32_t vox_transcribe_audio(vox_model* m, const float* samples, size
     const size_t left = pad_left(&pc), right = pad_right(&pc, n + left), total = left + n + right, T = total / 160;
     MelTables t; VOXCHK(ctx_mel_tables(cx, &t));
     VOXCHK(ensure(&m->d_mel, &m->mel_cap, (size_t)128 * T));
-    HIPCHK(launch_absmax(d_s, (long)n, 0.95f, cx->d_scale, s));                                  // peak_normalize(0.95), transcribe.rs:207
-    HIPCHK(launch_mel(d_s, (long)n, (long)left, (long)right, cx->d_scale, t, m->d_mel, (int)T, 1, s));   // pad + log-mel, [128][T]
+    HIPCHK(launch_absmax(d_s, (long)n, 0.95f, cx->d_scale, s));
+    HIPCHK(launch_mel(d_s, (long)n, (long)left, (long)right, cx->d_scale, t, m->d_mel, (int)T, 1, s));
+    *T_out = (int)T;
+    return VOX_OK;
+}
+extern "C" int32_t vox_transcribe_audio(vox_model* m, const float* samples, size_t n, const float* t_embed, int32_t* out_ids, int32_t cap,
+                                        int32_t* n_ids, int32_t mem_kind) {
+    ARGCHK(m && samples && t_embed && out_ids && n_ids, "null argument"); ARGCHK(n > 0, "empty audio"); VOXCHK(ctx_bind(m->ctx));
+    const vox_model_cfg& c = m->cfg; hipStream_t s = m->ctx->stream;
+    ARGCHK(c.n_mels == 128, "the log-mel front-end produces 128 bins; model expects %d", c.n_mels);
+    m->timings = vox_timings{};
+    VOXCHK(prefix_build(m, t_embed));      // nothing to do once the model holds its prefix state for this t_embed (the first call of a model pays it, outside the stage times)
+    const double t0 = now_ms();
+    int T = 0; VOXCHK(clip_front_end(m, samples, n, mem_kind, &T));
     HIPCHK(hipStreamSynchronize(s));
     m->timings.preprocess_ms = now_ms() - t0;
-    VOXCHK(transcribe_dev(m, m->d_mel, (int)T, t_embed, out_ids, cap, n_ids, nullptr, true));
+    VOXCHK(transcribe_dev(m, m->d_mel, T, t_embed, out_ids, cap, n_ids, nullptr, true));
     m->timings.total_ms = m->timings.preprocess_ms + m->timings.encode_ms + m->timings.decode_ms;
     return VOX_OK;
 }
@@ -3431,37 +3439,46 @@ extern "C" int32_t vox_transcribe_batch_ex(vox_model* m, int32_t n, const float*
     m->tap.on = false; m->tap.ready = tapped && r == VOX_OK;
     return r;
 }
+// the group peaks of a vox_transcribe_batch_ex call: pooled buffers, per unit (caller's order) its device samples (host samples only) and its device scale cell
+struct GroupScales { DevBuf b_all, b_gmax, b_ugrp, b_uscale; std::vector<const float*> dev_s, scale_of; };
+// every unit's scale = 0.95 / the peak of its norm_group (1: a silent group, a unit with a negative group), reduced on the device; host samples go up once, here, each
+// unit 16-byte aligned (g.dev_s).  Synchronises the stream once: the scales are ready for every session of the call.
+static int32_t group_peak_scales(vox_model* m, int32_t n, const float* const* samples_in, const size_t* n_samples, const int32_t* norm_group, int32_t mem_kind_in, GroupScales& g) {
+    const float* const* samples = samples_in;
+    VOXCHK(ctx_bind(m->ctx)); vox_ctx* cx = m->ctx; hipStream_t s = cx->stream;
+    std::vector<int> ug(n); std::vector<int32_t> ids; ids.reserve(n);      // dense group index per unit
+    {
+        std::vector<int32_t> uniq; for (int i = 0; i < n; i++) if (norm_group[i] >= 0) uniq.push_back(norm_group[i]);
+        std::sort(uniq.begin(), uniq.end()); uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+        for (int i = 0; i < n; i++) ug[i] = norm_group[i] < 0 ? -1 : (int)(std::lower_bound(uniq.begin(), uniq.end(), norm_group[i]) - uniq.begin());
+        ids = uniq;
+    }
+    for (int i = 0; i < n; i++) ARGCHK(samples_in[i] && n_samples[i] > 0, "empty audio in batch slot %d", i);
+    if (mem_kind_in == VOX_MEM_HOST) {      // the peaks are reduced on the device: the whole call's samples go up once, here (4 B per sample: 0.4 GB for a 647-clip corpus)
+        size_t tot = 0; for (int i = 0; i < n; i++) tot += (n_samples[i] + 3) & ~(size_t)3;
+        HIPCHK(g.b_all.alloc_pooled(cx, tot * 4));
+        g.dev_s.resize(n); size_t o = 0;
+        for (int i = 0; i < n; i++) { float* d = g.b_all.as<float>() + o; o += (n_samples[i] + 3) & ~(size_t)3; HIPCHK(hipMemcpyAsync(d, samples_in[i], n_samples[i] * 4, hipMemcpyHostToDevice, s)); g.dev_s[i] = d; }
+        samples = g.dev_s.data();
+    }
+    const size_t ng = std::max<size_t>(ids.size(), 1);
+    HIPCHK(g.b_gmax.alloc_pooled(cx, ng * 4)); HIPCHK(g.b_ugrp.alloc_pooled(cx, (size_t)n * 4)); HIPCHK(g.b_uscale.alloc_pooled(cx, (size_t)n * 4));
+    HIPCHK(hipMemsetAsync(g.b_gmax.p, 0, ng * 4, s)); HIPCHK(hipMemcpyAsync(g.b_ugrp.p, ug.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+    for (int i = 0; i < n; i++) if (ug[i] >= 0) HIPCHK(launch_absmax_group(samples[i], (long)n_samples[i], g.b_gmax.as<unsigned>() + ug[i], s));
+    HIPCHK(launch_group_scale(g.b_gmax.as<unsigned>(), g.b_ugrp.as<int>(), n, 0.95f, g.b_uscale.as<float>(), s));
+    HIPCHK(hipStreamSynchronize(s));      // `ug` (pageable) goes out of scope; the scales are ready for every session below
+    g.scale_of.resize(n); for (int i = 0; i < n; i++) g.scale_of[i] = g.b_uscale.as<float>() + i;
+    return VOX_OK;
+}
 static int32_t transcribe_batch_one_session(vox_model* m, int32_t n, const float* const* samples_in, const size_t* n_samples, const int32_t* norm_group, const float* t_embed,
                                             int32_t* const* out_ids, const int32_t* caps, int32_t* n_ids, int32_t mem_kind_in) {
     const float* const* samples = samples_in; int32_t mem_kind = mem_kind_in;
-    DevBuf b_all, b_gmax, b_ugrp, b_uscale;      // (declared before everything that launches on them; the impls drain the streams before they return)
-    std::vector<const float*> dev_s; std::vector<const float*> scale_of;      // per unit (caller's order): device samples, device scale cell
+    GroupScales gs;      // (declared before everything that launches on its buffers; the impls drain the streams before they return)
     if (norm_group) {
-        VOXCHK(ctx_bind(m->ctx)); vox_ctx* cx = m->ctx; hipStream_t s = cx->stream;
-        std::vector<int> ug(n); std::vector<int32_t> ids; ids.reserve(n);      // dense group index per unit
-        {
-            std::vector<std::pair<int32_t, int>> seen;      // (caller's id, dense index), sorted by id
-            std::vector<int32_t> uniq; for (int i = 0; i < n; i++) if (norm_group[i] >= 0) uniq.push_back(norm_group[i]);
-            std::sort(uniq.begin(), uniq.end()); uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
-            for (int i = 0; i < n; i++) ug[i] = norm_group[i] < 0 ? -1 : (int)(std::lower_bound(uniq.begin(), uniq.end(), norm_group[i]) - uniq.begin());
-            ids = uniq;
-        }
-        for (int i = 0; i < n; i++) ARGCHK(samples_in[i] && n_samples[i] > 0, "empty audio in batch slot %d", i);
-        if (mem_kind_in == VOX_MEM_HOST) {      // the peaks are reduced on the device: the whole call's samples go up once, here (4 B per sample: 0.4 GB for a 647-clip corpus)
-            size_t tot = 0; for (int i = 0; i < n; i++) tot += (n_samples[i] + 3) & ~(size_t)3;
-            HIPCHK(b_all.alloc_pooled(cx, tot * 4));
-            dev_s.resize(n); size_t o = 0;
-            for (int i = 0; i < n; i++) { float* d = b_all.as<float>() + o; o += (n_samples[i] + 3) & ~(size_t)3; HIPCHK(hipMemcpyAsync(d, samples_in[i], n_samples[i] * 4, hipMemcpyHostToDevice, s)); dev_s[i] = d; }
-            samples = dev_s.data(); mem_kind = VOX_MEM_DEVICE;
-        }
-        const size_t ng = std::max<size_t>(ids.size(), 1);
-        HIPCHK(b_gmax.alloc_pooled(cx, ng * 4)); HIPCHK(b_ugrp.alloc_pooled(cx, (size_t)n * 4)); HIPCHK(b_uscale.alloc_pooled(cx, (size_t)n * 4));
-        HIPCHK(hipMemsetAsync(b_gmax.p, 0, ng * 4, s)); HIPCHK(hipMemcpyAsync(b_ugrp.p, ug.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
-        for (int i = 0; i < n; i++) if (ug[i] >= 0) HIPCHK(launch_absmax_group(samples[i], (long)n_samples[i], b_gmax.as<unsigned>() + ug[i], s));
-        HIPCHK(launch_group_scale(b_gmax.as<unsigned>(), b_ugrp.as<int>(), n, 0.95f, b_uscale.as<float>(), s));
-        HIPCHK(hipStreamSynchronize(s));      // `ug` (pageable) goes out of scope; the scales are ready for every session below
-        scale_of.resize(n); for (int i = 0; i < n; i++) scale_of[i] = b_uscale.as<float>() + i;
+        VOXCHK(group_peak_scales(m, n, samples_in, n_samples, norm_group, mem_kind_in, gs));
+        if (!gs.dev_s.empty()) { samples = gs.dev_s.data(); mem_kind = VOX_MEM_DEVICE; }
     }
+    const std::vector<const float*>& scale_of = gs.scale_of;
     struct DrainAll { vox_model* m; bool on; ~DrainAll() { if (on) { (void)hipStreamSynchronize(m->ctx->stream); } } } drain_all{m, norm_group != nullptr};
     std::vector<int> order(n);
     for (int i = 0; i < n; i++) order[i] = i;
@@ -4083,6 +4100,7 @@ struct vox_stream {
     uint64_t eng_steps = 0, op_steps = 0, verified_eng_steps = 0, verified_op_steps = 0, bytes = 0;
     EngBinding eng;      // the decode engine's layer table for the stream's cache, its argmax partials (256), the pinned host copy of its error word
     float* tap = nullptr; int tap_max = 0, tap_rows = 0;
+    float *ftap_mel = nullptr, *ftap_conv = nullptr; int ftap_max = 0, ftap_ticks = 0;      // vox_debug_stream_front_tap_*: per tick its 4 R fresh mel frames and its R conv-stem rows
     int h_state[STRM_WORDS]; int h_pos_word = 0;
 };
 
@@ -4149,7 +4167,7 @@ static int32_t stream_load_initial(vox_stream* st) {
     if (!was_on) { (void)hipStreamSynchronize(s); prefix_release(m); P.on = false; }
     if (r != VOX_OK) return r;
     st->n_pushed = st->n_written = 0; st->pos = st->verified_pos = st->PC; st->ids_out = 0; st->finished = false; st->eng_unverified = false;
-    st->eng_steps = st->op_steps = st->verified_eng_steps = st->verified_op_steps = 0; st->tap_rows = st->verified_tap_rows = 0;
+    st->eng_steps = st->op_steps = st->verified_eng_steps = st->verified_op_steps = 0; st->tap_rows = st->verified_tap_rows = 0; st->ftap_ticks = 0;
     return VOX_OK;
 }
 
@@ -4157,7 +4175,7 @@ static void stream_release(vox_stream* st) {
     if (!st) return;
     (void)hipSetDevice(st->ctx->device); (void)hipStreamSynchronize(st->ctx->stream);      // never dereferences st->m: a stream may not outlive its model, but freeing it late must not crash
     cache_release(st->dec);
-    for (void* p : {(void*)st->kring, (void*)st->vring, (void*)st->samples, (void*)st->audio_keep, (void*)st->ws, (void*)st->tokens, (void*)st->state, (void*)st->tap}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)st->kring, (void*)st->vring, (void*)st->samples, (void*)st->audio_keep, (void*)st->ws, (void*)st->tokens, (void*)st->state, (void*)st->tap, (void*)st->ftap_mel, (void*)st->ftap_conv}) if (p) (void)hipFree(p);
     binding_release(st->eng);
     delete st;
 }
@@ -4205,7 +4223,7 @@ extern "C" int32_t vox_stream_reset(vox_stream* st) {
 extern "C" int32_t vox_stream_info(const vox_stream* st, int64_t out[8]) {
     ARGCHK(st && out, "null argument");
     const int R = st->m->cfg.reshape_factor;
-    const uint64_t dec_b = st->dec ? 2 * (uint64_t)st->m->cfg.dec_layers * st->dec->layer_stride * 4 : 0, tap_b = st->tap ? (uint64_t)st->tap_max * st->m->cfg.vocab * 4 : 0;
+    const uint64_t dec_b = st->dec ? 2 * (uint64_t)st->m->cfg.dec_layers * st->dec->layer_stride * 4 : 0, tap_b = (st->tap ? (uint64_t)st->tap_max * st->m->cfg.vocab * 4 : 0) + (st->ftap_mel ? (uint64_t)st->ftap_max * R * (4 * st->m->cfg.n_mels + st->m->cfg.enc_dim) * 4 : 0);
     out[0] = st->n_pushed; out[1] = st->pos; out[2] = st->ids_out; out[3] = (int64_t)R * st->pos; out[4] = std::min<int64_t>((int64_t)R * st->pos, st->cap);
     out[5] = (int64_t)(st->bytes + dec_b + tap_b); out[6] = (int64_t)st->eng_steps; out[7] = (int64_t)st->op_steps;
     return VOX_OK;
@@ -4288,6 +4306,13 @@ static int32_t stream_tick(vox_stream* st) {
     // conv stem without padding rows, memsets or a transpose: conv1 row i of the tick is the window of halo rows [2 i, 2 i + 2], conv row i the window of conv1 rows [2 i, 2 i + 2]
     { GemmParams g{}; g.w = m->conv1_g; g.x = halo; g.x_stride = 2 * Cm; g.M = N1; g.out = c1; g.out_stride = D; g.bias = m->conv1_b; HIPCHK(launch_dense2_gemm(g, EPI_GELU, s)); }
     { GemmParams g{}; g.w = m->conv2_g; g.x = c1; g.x_stride = 2 * D; g.M = R; g.out = x; g.out_stride = D; g.bias = m->conv2_b; HIPCHK(launch_dense2_gemm(g, EPI_GELU, s)); }
+    if (st->ftap_mel) {      // the front tap (tests): the tick's fresh frames (halo rows 3 ..) and conv rows, copied on the stream; a re-run repeats decode steps, never a tick
+        const int k = st->ftap_ticks++;
+        if (k < st->ftap_max) {
+            HIPCHK(hipMemcpyAsync(st->ftap_mel + (size_t)k * 4 * R * Cm, halo + (size_t)3 * Cm, (size_t)4 * R * Cm * 4, hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(st->ftap_conv + (size_t)k * R * D, x, (size_t)R * D * 4, hipMemcpyDeviceToDevice, s));
+        }
+    }
     for (int l = 0; l < c.enc_layers; l++) {
         const EncLayer& L = m->enc[l];
         HIPCHK(launch_rms_norm(x, D, R, D, L.attn_norm, nullptr, c.norm_eps, xn, D, s));
@@ -4388,5 +4413,71 @@ extern "C" int32_t vox_debug_stream_tap_fetch(vox_stream* st, float* out, int32_
     if (k > 0) HIPCHK(hipMemcpy(out, st->tap, (size_t)k * st->m->cfg.vocab * 4, hipMemcpyDeviceToHost));
     *rows = st->tap_rows;
     (void)hipFree(st->tap); st->tap = nullptr; st->tap_max = 0; st->tap_rows = st->verified_tap_rows = 0;
+    return VOX_OK;
+}
+
+static void stream_front_tap_drop(vox_stream* st) {
+    if (st->ftap_mel) (void)hipFree(st->ftap_mel);
+    if (st->ftap_conv) (void)hipFree(st->ftap_conv);
+    st->ftap_mel = st->ftap_conv = nullptr; st->ftap_max = st->ftap_ticks = 0;
+}
+extern "C" int32_t vox_debug_stream_front_tap_arm(vox_stream* st, int32_t max_ticks) {
+    ARGCHK(st, "null stream"); ARGCHK(max_ticks > 0 && max_ticks <= 65536, "max_ticks %d out of range (1..65536)", max_ticks); VOXCHK(ctx_bind(st->ctx));
+    HIPCHK(hipStreamSynchronize(st->ctx->stream));
+    stream_front_tap_drop(st);
+    const vox_model_cfg& c = st->m->cfg; const size_t R = (size_t)c.reshape_factor;
+    HIPCHK(hipMalloc((void**)&st->ftap_mel, (size_t)max_ticks * 4 * R * c.n_mels * 4));
+    if (hipMalloc((void**)&st->ftap_conv, (size_t)max_ticks * R * c.enc_dim * 4) != hipSuccess) { (void)hipGetLastError(); stream_front_tap_drop(st); return fail(VOX_ERR_HIP, "hipMalloc of the stream front tap failed"); }
+    st->ftap_max = max_ticks;
+    return VOX_OK;
+}
+extern "C" int32_t vox_debug_stream_front_tap_fetch(vox_stream* st, float* out_mel, float* out_conv, int32_t* ticks) {
+    ARGCHK(st && out_mel && out_conv && ticks, "null argument"); ARGCHK(st->ftap_mel, "no stream front tap to fetch (vox_debug_stream_front_tap_arm)"); VOXCHK(ctx_bind(st->ctx));
+    HIPCHK(hipStreamSynchronize(st->ctx->stream));
+    const vox_model_cfg& c = st->m->cfg; const size_t R = (size_t)c.reshape_factor, k = (size_t)std::min(st->ftap_ticks, st->ftap_max);
+    if (k > 0) { HIPCHK(hipMemcpy(out_mel, st->ftap_mel, k * 4 * R * c.n_mels * 4, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out_conv, st->ftap_conv, k * R * c.enc_dim * 4, hipMemcpyDeviceToHost)); }
+    *ticks = st->ftap_ticks;
+    stream_front_tap_drop(st);
+    return VOX_OK;
+}
+
+// ---- debug: the sample front ends on their own (tests).  form 0: the single clip's (clip_front_end); form 1: the batch drivers' (group_peak_scales when norm_group is
+// given, front_end_units with the drivers' host packing and device pointers).  Every unit's scale and [128][T_i] log-mel come back to the host.
+extern "C" int32_t vox_debug_front_end(vox_model* m, int32_t n, const float* const* samples, const size_t* n_samples, const int32_t* norm_group, int32_t form,
+                                       int32_t mem_kind, float* out_scales, float* const* out_mels, int32_t* out_T) {
+    ARGCHK(m && samples && n_samples && out_scales && out_mels && out_T, "null argument");
+    ARGCHK(form == 0 || form == 1, "bad form %d (0 single clip, 1 batch)", form); ARGCHK(mem_kind == VOX_MEM_HOST || mem_kind == VOX_MEM_DEVICE, "bad mem_kind %d", mem_kind);
+    ARGCHK(n > 0 && n <= 128, "unit count %d out of range (1..128)", n);
+    ARGCHK(form == 1 || (n == 1 && !norm_group), "the single-clip front end takes one unit and no norm_group");
+    for (int i = 0; i < n; i++) ARGCHK(samples[i] && n_samples[i] > 0 && n_samples[i] <= ((size_t)1 << 30) && out_mels[i], "empty audio or null output in slot %d", i);
+    ARGCHK(m->cfg.n_mels == 128, "the log-mel front-end produces 128 bins; model expects %d", m->cfg.n_mels);
+    VOXCHK(ctx_bind(m->ctx)); vox_ctx* cx = m->ctx; hipStream_t s = cx->stream;
+    if (form == 0) {
+        int T = 0; VOXCHK(clip_front_end(m, samples[0], n_samples[0], mem_kind, &T));
+        HIPCHK(hipMemcpyAsync(out_scales, cx->d_scale, 4, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(out_mels[0], m->d_mel, (size_t)128 * T * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s)); out_T[0] = T;
+        return VOX_OK;
+    }
+    GroupScales gs; const float* const* smp = samples; int32_t mk = mem_kind;      // as transcribe_batch_one_session hands the units to the drivers
+    if (norm_group) {
+        VOXCHK(group_peak_scales(m, n, samples, n_samples, norm_group, mem_kind, gs));
+        if (!gs.dev_s.empty()) { smp = gs.dev_s.data(); mk = VOX_MEM_DEVICE; }
+    }
+    const float* const* unit_scale = norm_group ? gs.scale_of.data() : nullptr;
+    MelTables mt; VOXCHK(ctx_mel_tables(cx, &mt));
+    std::vector<int> S, T, len, slot_of(n); std::vector<int32_t> caps(n, INT32_MAX); int Smax = 0;
+    for (int i = 0; i < n; i++) slot_of[i] = i;
+    VOXCHK(batch_lengths(m, n, smp, n_samples, caps.data(), slot_of.data(), T, S, len, &Smax));
+    size_t mel_floats = 0, smp_total = 0; for (int i = 0; i < n; i++) { mel_floats += (size_t)128 * T[i]; smp_total += n_samples[i]; }
+    DevBuf b_mel, b_scale, b_smp; BatchDrain drain{cx};
+    HIPCHK(b_mel.alloc_pooled(cx, mel_floats * 4)); HIPCHK(b_scale.alloc_pooled(cx, (size_t)n * 4));
+    if (mk == VOX_MEM_HOST) HIPCHK(b_smp.alloc_pooled(cx, smp_total * 4));
+    std::vector<const float*> d_mels(n);
+    VOXCHK(front_end_units(mt, 0, n, smp, n_samples, T.data(), unit_scale, mk == VOX_MEM_HOST ? b_smp.as<float>() : nullptr, b_mel.as<float>(), b_scale.as<float>(), d_mels.data(), s));
+    for (int i = 0; i < n; i++) {
+        HIPCHK(hipMemcpyAsync(out_scales + i, unit_scale ? unit_scale[i] : b_scale.as<float>() + i, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(out_mels[i], d_mels[i], (size_t)128 * T[i] * 4, hipMemcpyDeviceToHost, s)); out_T[i] = T[i];
+    }
+    HIPCHK(hipStreamSynchronize(s));
     return VOX_OK;
 }

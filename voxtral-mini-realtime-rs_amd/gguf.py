@@ -449,6 +449,18 @@ class LiveStream:
             raise VoxError(1, f"stream tap: {rows.value} rows for a tap of {self._tap_max}")
         return buf[:rows.value].copy()
 
+    def front_tap_arm(self, max_ticks):
+        check(lib().vox_debug_stream_front_tap_arm(self.h, int(max_ticks))); self._ftap_max = int(max_ticks)
+
+    def front_tap_fetch(self):
+        """vox_debug_stream_front_tap_fetch: (log-mel [ticks][16][n_mels], conv-stem rows [ticks][4][enc_dim]) of the ticks run since front_tap_arm."""
+        c = self.model.config; R = c.reshape_factor
+        mel = np.zeros((self._ftap_max, 4 * R, c.n_mels), dtype=np.float32); conv = np.zeros((self._ftap_max, R, c.enc_dim), dtype=np.float32); ticks = C.c_int32()
+        check(lib().vox_debug_stream_front_tap_fetch(self.h, _ptr(mel), _ptr(conv), C.byref(ticks)))
+        if ticks.value > self._ftap_max:
+            raise VoxError(1, f"stream front tap: {ticks.value} ticks for a tap of {self._ftap_max}")
+        return mel[:ticks.value].copy(), conv[:ticks.value].copy()
+
     def close(self):
         if self.h:
             lib().vox_stream_free(self.h); self.h = None
@@ -572,6 +584,25 @@ class Q4VoxtralModel:
         for i in range(n):
             res.append(out[o:o + rows[i]].copy()); o += rows[i]
         return res, {"Mtot": rep[0], "ksp": rep[1], "ksp_wo": rep[2], "fused_rope": rep[3]}
+
+    def debug_front_end(self, samples_list, form, norm_group=None, device_ptrs=None, n_samples=None):
+        """vox_debug_front_end: the sample front end of the single clip (form 0: one unit) or of the batch drivers (form 1) on its own, for float32 sample arrays (or
+        device pointers + lengths) -> (scales [n] f32, list of log-mels [128, T_i] as the encoder receives them)."""
+        from .audio import PadConfig
+        if device_ptrs is None:
+            arrs = [_f32(x).reshape(-1) for x in samples_list]; n = len(arrs)
+            ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in arrs]); lens = [a.size for a in arrs]; kind = 0
+        else:
+            n = len(device_ptrs); ptrs = (C.c_void_p * max(n, 1))(*device_ptrs); lens = [int(v) for v in n_samples]; kind = 1
+        pc = PadConfig.voxtral()
+        Ts = [pc.padded_len(v) // 160 for v in lens]
+        mels = [np.full((128, T), np.nan, dtype=np.float32) for T in Ts]
+        mptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in mels]); scales = np.full(n, np.nan, dtype=np.float32); out_T = (C.c_int32 * max(n, 1))()
+        grp = None if norm_group is None else (C.c_int32 * max(n, 1))(*[int(g) for g in norm_group])
+        check(lib().vox_debug_front_end(self.h, n, ptrs, (C.c_size_t * max(n, 1))(*lens), grp, int(form), kind, _ptr(scales), mptrs, out_T))
+        if [out_T[i] for i in range(n)] != Ts:
+            raise VoxError(1, f"front end: frame counts {[out_T[i] for i in range(n)]}, expected {Ts}")
+        return scales, mels
 
     def create_encoder_cache(self, capacity_rows=0):
         return EncoderCaches(self, capacity_rows)
