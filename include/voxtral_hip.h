@@ -427,7 +427,7 @@ int32_t vox_debug_plan_slots(const int32_t* steps, int32_t n, int32_t force_G, i
                              int32_t* job_qpos, int32_t steps_g[8], int32_t run_g[8], double* cost_ms);
 
 /* ---- live streaming session (no reference counterpart: the reference transcribes finished files, bin/transcribe.rs:112-126) ------------------------------------------
- * A vox_stream is fed 16 kHz samples in pieces of any size and hands back token ids as soon as they are determined.  After vox_stream_finish the concatenation of
+ * A vox_stream is fed 16 kHz samples (or samples at its capture rate: CAPTURE RATE below) in pieces of any size and hands back token ids as soon as they are determined.  After vox_stream_finish the concatenation of
  * everything it handed back is the id sequence vox_transcribe_streaming gives for the log-mel of pad_audio(gain * x) of the concatenated samples x (gain = 0.95 / max|x|:
  * vox_transcribe_audio(x)) -- per step the logits agree to f32 summation-order noise, so the ids agree up to the first near-tie of the offline path's own logits.
  *   Cut-independence: the session advances in TICKS of one decoder position (16 mel frames -> 4 encoder rows -> 1 adapter row -> 1 decode step) however much audio a
@@ -450,25 +450,53 @@ int32_t vox_debug_plan_slots(const int32_t* steps, int32_t n, int32_t force_G, i
  *   for another t_embed, which the next offline call with that t_embed rebuilds; results never depend on it.  As everywhere, a prefix state that cannot be allocated
  *   switches the model's prefix cache off (create / reset then fail with VOX_ERR_HIP).
  * LIMITS: one decoder position = 2560 samples = 160 ms.  A session ends at 16 384 decoder positions (the decoder RoPE table; the encoder's 65 536-position table ends at
- * the same point), about 43 minutes: later pushes are refused until vox_stream_reset.  16 kHz in (no resampling inside the stream).  Q4 (GGUF) models whose conv stem
- * runs as im2col GEMMs (3 n_mels and 3 enc_dim multiples of 128); dense SafeTensors models: VOX_ERR_UNSUPPORTED. */
+ * the same point), about 43 minutes: later pushes are refused until vox_stream_reset.  Input: 16 kHz, or the capture rate of a stream made by vox_stream_create_rate
+ * (every rate pair vox_resample serves), as f32 or as signed 16-bit PCM; mono.  Q4 (GGUF) models whose conv stem
+ * runs as im2col GEMMs (3 n_mels and 3 enc_dim multiples of 128); dense SafeTensors models: VOX_ERR_UNSUPPORTED.
+ *
+ * CAPTURE RATE (vox_stream_create_rate).  A stream created for rate sr and fed x hands back the ids of a 16 kHz stream fed vox_resample(x, sr, 16000) with the same gain:
+ * every 16 kHz sample the session consumes is bit for bit the one vox_resample produces for the concatenated input -- hence the agreement with the offline path that
+ * 16 kHz streams carry.  The ids, and which call returns which id (vox_stream_schedule_rate), are functions of the samples, the rate and the gain alone: not of the cuts,
+ * not of the f32 / s16 mix, not of what else ran on the model or the context in between (vox_resample at other rates included: the stream owns its block matrix).
+ *   Why an exact incremental form exists: the resampler is one fixed matrix applied block by block (fft_in input samples -> fft_out output samples, vox_resample_plan);
+ *   output sample i reads block c = (i + delay) / fft_out in full and the tail of block c - 1, nothing else.  So after n input samples the first
+ *       avail16(n) = max(0, floor(n / fft_in) * fft_out - delay)
+ *   output samples are final; the stream produces exactly those (stream_resample_kernel, from a ring of input samples) and runs the ticks they make due.  At
+ *   vox_stream_finish the rest, up to vox_resample_len(n) = ceil(n * 16000 / sr), is produced with the blocks clipped at n as vox_resample clips them at the end of a file;
+ *   then the right pad follows.
+ *   Added latency, from the plan alone: (fft_in + delay * fft_in / fft_out) / sr seconds --
+ *       48 kHz 16 ms | 44.1 kHz 30 ms | 32 kHz 24 ms | 22.05 kHz 60 ms | 8 kHz 96 ms | 11.025 kHz 120 ms          (a tick has 160 ms)
+ *   State: in addition to a 16 kHz stream's, a ring of input-rate samples (a power of two holding two blocks and a feed chunk) and the rate pair's block matrix
+ *   (2 fft_out x fft_in f32, e.g. 0.7 MB at 48 kHz, 2.3 MB at 44.1 kHz); both are counted in vox_stream_info's bytes.  Still one synchronisation per call.
+ * 16-BIT PCM (vox_stream_push_s16) works on every stream: sample v enters as float(v) / 32768 (exact in f32; the mono 16-bit scale of audio/io.rs:110-113), so a push of v
+ * equals vox_stream_push of those floats, and the two may alternate on one stream. */
 typedef struct vox_stream vox_stream;
 /* gain: every sample is multiplied by it before the mel (a stream has no file peak; 1.0 = as given).
  * enc_capacity_rows: rows of the encoder K / V ring, 0 = enc_window + 8 rounded up to a multiple of 64 (768: 0.4 GB of K / V per stream at full size; a ring needs no
  *   slack, any capacity above enc_window + 4 gives the same bits); must exceed enc_window + 4.
  * max_positions: decoder positions the session can reach, 0 = the decoder RoPE table (16 384). */
 int32_t vox_stream_create(vox_model* m, const float* t_embed, float gain, int32_t enc_capacity_rows, int32_t max_positions, vox_stream** out);
+/* vox_stream_create for input at sample_rate Hz.  16000: vox_stream_create itself.  Any other rate: the stream also owns its input ring and its block matrix (built here;
+ * synchronises).  Rate pairs vox_resample refuses (block matrix above 64 MB: rates without a large common divisor, e.g. 44101 Hz) and blocks that do not fit the input
+ * ring: VOX_ERR_UNSUPPORTED; rate 0: VOX_ERR_INVALID. */
+int32_t vox_stream_create_rate(vox_model* m, const float* t_embed, float gain, int32_t enc_capacity_rows, int32_t max_positions, uint32_t sample_rate, vox_stream** out);
 /* samples host or device (mem_kind), ids host.  cap smaller than the ids the call will produce (known from the schedule before any work), a push after finish, a push
  * that would pass max_positions: VOX_ERR_INVALID BEFORE any state changes -- the call can be repeated. */
 int32_t vox_stream_push(vox_stream* s, const float* samples, size_t n, int32_t mem_kind, int32_t* out_ids, int32_t cap, int32_t* n_ids);
+/* vox_stream_push for signed 16-bit PCM at the stream's rate (host or device memory; host samples pass through a bounded device staging buffer, allocated at the first
+ * such push and counted in vox_stream_info's bytes from then on).  The same refusals, before any state changes. */
+int32_t vox_stream_push_s16(vox_stream* s, const int16_t* samples, size_t n, int32_t mem_kind, int32_t* out_ids, int32_t cap, int32_t* n_ids);
 int32_t vox_stream_finish(vox_stream* s, int32_t* out_ids, int32_t cap, int32_t* n_ids);
 int32_t vox_stream_reset(vox_stream* s);          /* back to the state after create: the next push starts a new utterance */
 int32_t vox_stream_free(vox_stream* s);
-/* samples pushed, decoder positions done, ids handed out, encoder stream position, encoder ring rows in use, device bytes held,
+/* samples pushed (as pushed: at the stream's input rate), decoder positions done, ids handed out, encoder stream position, encoder ring rows in use, device bytes held,
  * decode steps run on the engine, decode steps run per operator */
 int32_t vox_stream_info(const vox_stream* s, int64_t out[8]);
 /* host only: after n_samples pushed (finished = 0) or at the end of an n_samples utterance (finished = 1): decoder positions determined, ids due */
 int32_t vox_stream_schedule(size_t n_samples, int32_t finished, int32_t* positions, int32_t* ids);
+/* the same for a stream fed at sample_rate Hz: *samples_16k = avail16(n_samples) (finished = 0) or vox_resample_len(n_samples) (finished = 1), positions and ids are
+ * vox_stream_schedule's for that many 16 kHz samples.  Rate 16000 gives vox_stream_schedule's answers.  Push and finish check `cap` against this schedule. */
+int32_t vox_stream_schedule_rate(size_t n_samples, uint32_t sample_rate, int32_t finished, int32_t* positions, int32_t* ids, size_t* samples_16k);
 /* test tap, modelled on vox_debug_batch_tap_*: from now on keep the f32 logits row behind each id handed out (up to max_rows); fetch copies them to the host
  * ([min(rows, max_rows)][vocab]; *rows = rows produced since arm) and ends the tap */
 int32_t vox_debug_stream_tap_arm(vox_stream* s, int32_t max_rows);

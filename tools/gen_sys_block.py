@@ -7,7 +7,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = os.path.join(ROOT, "include", "voxtral_hip.h"); DOC = os.path.join(ROOT, "INTEGRATION.md")
 BEGIN, END = "<!-- BEGIN GENERATED -sys (tools/gen_sys_block.py) -->", "<!-- END GENERATED -sys -->"
 PRIM = {"int32_t": "i32", "uint32_t": "u32", "int64_t": "i64", "uint64_t": "u64", "size_t": "usize", "float": "f32", "double": "f64",
-        "uint8_t": "u8", "uint16_t": "u16", "char": "c_char", "void": "c_void", "int": "i32"}
+        "uint8_t": "u8", "uint16_t": "u16", "int16_t": "i16", "char": "c_char", "void": "c_void", "int": "i32"}
 KEYWORDS = {"in": "inp", "type": "ty", "ref": "r", "box": "bx", "move": "mv", "loop": "lp", "match": "m_"}
 
 

@@ -164,6 +164,9 @@ SIGNATURES = {
     "vox_debug_stream_front_tap_arm": (i32, [vp, i32]),
     "vox_debug_stream_front_tap_fetch": (i32, [vp, vp, vp, P(i32)]),
     "vox_debug_front_end": (i32, [vp, i32, P(vp), P(sz), P(i32), i32, i32, vp, P(vp), P(i32)]),
+    "vox_stream_create_rate": (i32, [vp, vp, f32, i32, i32, u32, P(vp)]),
+    "vox_stream_push_s16": (i32, [vp, vp, sz, i32, vp, i32, P(i32)]),
+    "vox_stream_schedule_rate": (i32, [sz, u32, i32, P(i32), P(i32), P(sz)]),
 }
 
 _LIB = None

@@ -71,25 +71,35 @@ def transcribe_one(pkg, path, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed
     return " ".join(texts)
 
 
-def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms):
+def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_rate=False):
     """--live: the file through a live session (vox_stream) in pieces of `chunk_ms` milliseconds, the text so far on stderr whenever ids arrive.  The gain is the
     file's peak scale 0.95 / max|x| (bin/transcribe.rs:207; a file is known in advance -- a microphone caller passes its own), the whole file is one utterance (no
-    --max-mel-frames chunks: the session's state is bounded by its ring), so the line equals the un-chunked path's."""
+    --max-mel-frames chunks: the session's state is bounded by its ring), so the line equals the un-chunked path's.
+    native_rate (--live-native-rate), for a file that is not at 16 kHz: the session is created for the file's rate and pushed the file's own samples -- what a capture
+    device would deliver; it resamples as the samples arrive.  The gain stays the peak scale of the RESAMPLED file (computed here only because the file is known in
+    advance and the line is to be compared), so the line equals the one without the flag."""
     x, sr = load_wav(path)
+    rate = 16000
     if sr != 16000:
-        log(f"  resampling {sr} Hz -> 16 kHz"); x = resample_to_16k(x, sr, mel.ctx, pkg)
+        log(f"  resampling {sr} Hz -> 16 kHz"); x16 = resample_to_16k(x, sr, mel.ctx, pkg)
+        if native_rate:
+            rate = sr; log(f"  live session at {sr} Hz: the resampled file gives the gain alone")
+        else:
+            x = x16
+    else:
+        x16 = x
     x = np.ascontiguousarray(x, dtype=np.float32)
-    peak = np.float32(np.abs(x).max()) if x.size else np.float32(0)
+    peak = np.float32(np.abs(x16).max()) if x16.size else np.float32(0)
     gain = float(np.float32(0.95) / peak) if peak >= 1e-10 else 1.0              # audio/io.rs:59-68
-    step = max(1, int(round(16000 * chunk_ms / 1000.0)))
-    stream = model.create_stream(t_embed, gain=gain)
+    step = max(1, int(round(rate * chunk_ms / 1000.0)))
+    stream = model.create_stream(t_embed, gain=gain, sample_rate=rate)
     try:
         ids = []
         text = lambda: tokenizer.decode([t for t in ids if t >= 1000]).strip()   # :309-318
         for a in range(0, x.size, step):
             new = stream.push(x[a:a + step])
             if new.size:
-                ids.extend(int(t) for t in new); log(f"  [{min(a + step, x.size) / 16000:8.2f} s] {text()}")
+                ids.extend(int(t) for t in new); log(f"  [{min(a + step, x.size) / rate:8.2f} s] {text()}")
         ids.extend(int(t) for t in stream.finish())
         return text()
     finally:
@@ -233,9 +243,13 @@ def main(argv=None):
     ap.add_argument("--live", action="store_true", help="extension: feed every file through a live streaming session (vox_stream) in --live-chunk-ms pieces; the text so far "
                     "goes to stderr as ids arrive, stdout keeps one final line per input, equal to the un-chunked path's (Q4 GGUF, one GPU, no --batch)")
     ap.add_argument("--live-chunk-ms", type=int, default=160, help="with --live: milliseconds of audio per push (one decoder position = 160 ms)")
+    ap.add_argument("--live-native-rate", action="store_true", help="with --live, for a file that is not at 16 kHz: push the file's own-rate samples into a session created "
+                    "for that rate (it resamples as they arrive) instead of resampling the whole file first; the line is the same")
     a = ap.parse_args(argv)
     if a.live and (a.gpus > 1 or a.batch > 1 or a.live_chunk_ms <= 0):
         ap.error("--live runs one file at a time on one GPU (no --gpus / --batch) with --live-chunk-ms > 0")
+    if a.live_native_rate and not a.live:
+        ap.error("--live-native-rate applies with --live")
     if a.live and not a.gguf:
         ap.error("--live needs a Q4 GGUF model (--gguf): live sessions do not serve the f32 SafeTensors path")
     if a.audio_list and a.audio:
@@ -319,7 +333,7 @@ def main(argv=None):
         p = paths[i]
         try:
             t1 = time.time()
-            text = transcribe_live(pkg, p, model, tokenizer, mel, t_embed, a.live_chunk_ms) if a.live else transcribe_one(pkg, p, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed)
+            text = transcribe_live(pkg, p, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_native_rate) if a.live else transcribe_one(pkg, p, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed)
             log(f"{p}: {time.time() - t1:.3f}s")
         except Exception as e:      # per-utterance failure isolates to that line (empty), eval_wer.py:211-223 tolerates it
             log(f"Error transcribing {p}: {e}"); text = ""; rc = 1

@@ -384,10 +384,15 @@ extern "C" int32_t vox_resample_len(size_t n_in, uint32_t sr_in, uint32_t sr_out
     ARGCHK(n_out && sr_in > 0 && sr_out > 0, "bad argument");
     *n_out = sr_in == sr_out ? n_in : (size_t)std::ceil(((double)sr_out / (double)sr_in) * (double)n_in); return VOX_OK;      // rubato: (resample_ratio() * len).ceil()
 }
-static int32_t resample_matrix_ensure(vox_ctx* c, uint32_t sr_in, uint32_t sr_out, const ResamplePlan& p) {
-    if (c->rs_matrix && c->rs_in == sr_in && c->rs_out == sr_out) return VOX_OK;
-    const size_t bytes = (size_t)p.fft_in * 2 * (size_t)p.fft_out * 4;
-    if (bytes > RESAMPLE_MATRIX_MAX) return fail(VOX_ERR_UNSUPPORTED, "resample %u -> %u Hz: FFT blocks of %ld -> %ld samples are not supported (rates must share a large common divisor)", sr_in, sr_out, p.fft_in, p.fft_out);
+// the size of a plan's block matrix, or the refusal of a rate pair whose blocks are too large (shared by vox_resample and the streams fed at their capture rate)
+static int32_t resample_matrix_bytes(uint32_t sr_in, uint32_t sr_out, const ResamplePlan& p, size_t* bytes) {
+    *bytes = (size_t)p.fft_in * 2 * (size_t)p.fft_out * 4;
+    if (*bytes > RESAMPLE_MATRIX_MAX) return fail(VOX_ERR_UNSUPPORTED, "resample %u -> %u Hz: FFT blocks of %ld -> %ld samples are not supported (rates must share a large common divisor)", sr_in, sr_out, p.fft_in, p.fft_out);
+    return VOX_OK;
+}
+// a plan's block matrix At[fft_in][2 fft_out] in a fresh device buffer the caller owns (the context's cache below, a vox_stream): the same taps, spectrum and kernel
+// whoever asks, so the same bits.  Synchronises the context's stream.
+static int32_t resample_matrix_build(vox_ctx* c, const ResamplePlan& p, size_t bytes, float** out) {
     const std::vector<float> h = resample_taps(p);
     const long Pi = 2 * p.fft_in; std::vector<double> ct((size_t)Pi), st((size_t)Pi), H((size_t)p.new_len * 2, 0.0);
     for (long j = 0; j < Pi; j++) { ct[(size_t)j] = std::cos(2.0 * M_PI * (double)j / (double)Pi); st[(size_t)j] = std::sin(2.0 * M_PI * (double)j / (double)Pi); }
@@ -396,13 +401,21 @@ static int32_t resample_matrix_ensure(vox_ctx* c, uint32_t sr_in, uint32_t sr_ou
         for (long n = 0; n < p.fft_in; n++) { const long j = (k * n) % Pi; re += (double)h[(size_t)n] * ct[(size_t)j]; im -= (double)h[(size_t)n] * st[(size_t)j]; }
         H[(size_t)2 * k] = re; H[(size_t)2 * k + 1] = im;
     }
+    float* A = nullptr;
+    DevBuf dH; HIPCHK(dH.alloc(H.size() * 8)); HIPCHK(hipMalloc((void**)&A, bytes));
+    hipError_t e = hipMemcpyAsync(dH.p, H.data(), H.size() * 8, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = launch_resample_matrix(dH.as<double>(), (int)p.new_len, (int)p.fft_in, (int)p.fft_out, A, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { (void)hipFree(A); return fail(VOX_ERR_HIP, "resample matrix: %s", hipGetErrorString(e)); }
+    *out = A;
+    return VOX_OK;
+}
+static int32_t resample_matrix_ensure(vox_ctx* c, uint32_t sr_in, uint32_t sr_out, const ResamplePlan& p) {
+    if (c->rs_matrix && c->rs_in == sr_in && c->rs_out == sr_out) return VOX_OK;
+    size_t bytes; VOXCHK(resample_matrix_bytes(sr_in, sr_out, p, &bytes));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (c->rs_matrix) { (void)hipFree(c->rs_matrix); c->rs_matrix = nullptr; }
-    DevBuf dH; HIPCHK(dH.alloc(H.size() * 8)); HIPCHK(hipMalloc((void**)&c->rs_matrix, bytes));
-    HIPCHK(hipMemcpyAsync(dH.p, H.data(), H.size() * 8, hipMemcpyHostToDevice, c->stream));
-    hipError_t e = launch_resample_matrix(dH.as<double>(), (int)p.new_len, (int)p.fft_in, (int)p.fft_out, c->rs_matrix, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { (void)hipFree(c->rs_matrix); c->rs_matrix = nullptr; return fail(VOX_ERR_HIP, "resample matrix: %s", hipGetErrorString(e)); }
+    VOXCHK(resample_matrix_build(c, p, bytes, &c->rs_matrix));
     c->rs_in = sr_in; c->rs_out = sr_out;
     return VOX_OK;
 }
@@ -4082,9 +4095,14 @@ extern "C" int32_t vox_debug_encode_batch(vox_model* m, int32_t n, const float* 
 //   per tick: stream_mel_kernel (4 R new frames + 3 halo frames, token-major) -> conv stem as two small im2col GEMMs on the halo buffer -> enc_layers x { RMSNorm,
 //   q|k|v GEMV, stream_attn_kernel (RoPE + ring append + windowed attention), wo, RMSNorm, w1|w3, w2 } -> final norm, adapter -> stream_embed_kernel -> one decode step
 //   (engine launch while the stream's decoder cache has <= 1024 rows, per-operator launches after) -> stream_advance_kernel (token, state block).
+// Ingest at the capture rate (vox_stream_create_rate): input-rate samples go into a ring of their own, stream_resample_kernel turns every block that
+// is complete into 16 kHz samples of the ring above (vox_resample's bits: the same matrix, the same sums), the ticks see 16 kHz samples only.  16-bit PCM
+// (vox_stream_push_s16) is converted on the device on its way into whichever ring the stream is fed through.
 // ------------------------------------------------------------------------------------------------
 static const int STREAM_SAMPLE_RING = 1 << 16;      // samples held on the device (a tick reads 160 (4 R + 2) + 400 of them)
 static const int STREAM_KEEP_ROWS = 1024;           // adapter rows kept for the re-run of unverified engine steps; a push verifies at least this often
+static const int STREAM_FEED_CHUNK = 1 << 15;       // input-rate samples a rate stream's ring takes beyond two blocks; 16-bit samples of the host staging buffer
+static const int STREAM_IN_RING_MAX = 1 << 20;      // largest input ring (samples): rate pairs whose two blocks + a feed chunk do not fit are refused at create
 struct vox_stream {
     vox_model* m = nullptr; vox_ctx* ctx = nullptr;
     std::vector<float> t_embed; float gain = 1.0f;
@@ -4094,8 +4112,12 @@ struct vox_stream {
     float *samples = nullptr, *audio_keep = nullptr, *ws = nullptr;
     int *tokens = nullptr, *state = nullptr;
     MelTables mel{};
+    // input at the capture rate (sr != 16000): the plan, the stream's OWN block matrix (the context's is vox_resample's and goes when the rate pair changes), the input ring
+    uint32_t sr = 16000; ResamplePlan rp; float *rs_matrix = nullptr, *in_ring = nullptr; int in_ring_n = 0;
+    int16_t* s16_stage = nullptr;      // host 16-bit pushes: STREAM_FEED_CHUNK samples of device staging, allocated at the first one
     // host mirror of the session
-    int64_t n_pushed = 0, n_written = 0;      // samples the caller gave; samples in the ring (after finish: + the right pad)
+    int64_t n_pushed = 0, n_written = 0;      // samples the caller gave (at the input rate); samples in the 16 kHz ring (after finish: + the right pad)
+    int64_t in_written = 0;                   // rate streams: input samples copied into the input ring so far
     int pos = 0, ids_out = 0, verified_pos = 0, verified_tap_rows = 0; bool finished = false, eng_unverified = false;
     uint64_t eng_steps = 0, op_steps = 0, verified_eng_steps = 0, verified_op_steps = 0, bytes = 0;
     EngBinding eng;      // the decode engine's layer table for the stream's cache, its argmax partials (256), the pinned host copy of its error word
@@ -4108,15 +4130,33 @@ static long stream_spp(int R) { return 640L * R; }      // samples per decoder p
 // decoder positions determined after n samples of an unfinished stream: position p's last frame 4 R p + 4 R - 1 reads padded samples up to 640 R (p + 1) + 40
 static long stream_positions(long left, int R, int64_t n) { const int64_t a = left + n - 40; return a < 0 ? 0 : (long)(a / stream_spp(R)); }
 
-extern "C" int32_t vox_stream_schedule(size_t n_samples, int32_t finished, int32_t* positions, int32_t* ids) {
-    ARGCHK(positions && ids, "null argument"); ARGCHK(n_samples <= ((size_t)1 << 40), "sample count out of range");
+// the 16 kHz samples final after n input samples at the plan's rate: output i reads block (i + delay) / fft_out in full and the tail of the block before, nothing else
+static int64_t stream_avail16(const ResamplePlan& p, int64_t n) { return std::max<int64_t>(0, n / p.fft_in * p.fft_out - p.delay); }
+// the 16 kHz samples a stream at rate sr holds after n input samples (finished: of an n-sample utterance)
+static int32_t stream_samples16(uint32_t sr, const ResamplePlan& p, size_t n, bool finished, size_t* n16) {
+    if (sr == 16000) { *n16 = n; return VOX_OK; }
+    if (finished) return vox_resample_len(n, sr, 16000, n16);
+    *n16 = (size_t)stream_avail16(p, (int64_t)n); return VOX_OK;
+}
+static int32_t stream_schedule16(size_t n16, bool finished, int32_t* positions, int32_t* ids) {
     vox_pad_cfg pc; vox_pad_cfg_voxtral(&pc);
     const long left = (long)pad_left(&pc); const int R = 4;
     long P;
-    if (finished) { size_t total; VOXCHK(vox_pad_len(n_samples, &pc, &total)); P = (long)(total / (size_t)stream_spp(R)); *ids = (int32_t)std::max(P - VOX_PREFIX_TOKENS, 0L); }
-    else { P = stream_positions(left, R, (int64_t)n_samples); *ids = (int32_t)std::max(P - (VOX_PREFIX_TOKENS - 1), 0L); }
+    if (finished) { size_t total; VOXCHK(vox_pad_len(n16, &pc, &total)); P = (long)(total / (size_t)stream_spp(R)); *ids = (int32_t)std::max(P - VOX_PREFIX_TOKENS, 0L); }
+    else { P = stream_positions(left, R, (int64_t)n16); *ids = (int32_t)std::max(P - (VOX_PREFIX_TOKENS - 1), 0L); }
     *positions = (int32_t)P;
     return VOX_OK;
+}
+extern "C" int32_t vox_stream_schedule(size_t n_samples, int32_t finished, int32_t* positions, int32_t* ids) {
+    ARGCHK(positions && ids, "null argument"); ARGCHK(n_samples <= ((size_t)1 << 40), "sample count out of range");
+    return stream_schedule16(n_samples, finished != 0, positions, ids);
+}
+extern "C" int32_t vox_stream_schedule_rate(size_t n_samples, uint32_t sample_rate, int32_t finished, int32_t* positions, int32_t* ids, size_t* samples_16k) {
+    ARGCHK(positions && ids && samples_16k, "null argument"); ARGCHK(sample_rate > 0, "bad sample rate 0"); ARGCHK(n_samples <= ((size_t)1 << 40), "sample count out of range");
+    ResamplePlan p;
+    if (sample_rate != 16000) { p = resample_plan_make(sample_rate, 16000); size_t bytes; VOXCHK(resample_matrix_bytes(sample_rate, 16000, p, &bytes)); }
+    VOXCHK(stream_samples16(sample_rate, p, n_samples, finished != 0, samples_16k));
+    return stream_schedule16(*samples_16k, finished != 0, positions, ids);
 }
 
 static int32_t stream_dec_alloc(vox_stream* st, int rows) {      // a fresh decoder cache of `rows` rows (the old one is freed)
@@ -4166,7 +4206,7 @@ static int32_t stream_load_initial(vox_stream* st) {
     if (r == VOX_OK) r = body();
     if (!was_on) { (void)hipStreamSynchronize(s); prefix_release(m); P.on = false; }
     if (r != VOX_OK) return r;
-    st->n_pushed = st->n_written = 0; st->pos = st->verified_pos = st->PC; st->ids_out = 0; st->finished = false; st->eng_unverified = false;
+    st->n_pushed = st->n_written = st->in_written = 0; st->pos = st->verified_pos = st->PC; st->ids_out = 0; st->finished = false; st->eng_unverified = false;
     st->eng_steps = st->op_steps = st->verified_eng_steps = st->verified_op_steps = 0; st->tap_rows = st->verified_tap_rows = 0; st->ftap_ticks = 0;
     return VOX_OK;
 }
@@ -4175,14 +4215,24 @@ static void stream_release(vox_stream* st) {
     if (!st) return;
     (void)hipSetDevice(st->ctx->device); (void)hipStreamSynchronize(st->ctx->stream);      // never dereferences st->m: a stream may not outlive its model, but freeing it late must not crash
     cache_release(st->dec);
-    for (void* p : {(void*)st->kring, (void*)st->vring, (void*)st->samples, (void*)st->audio_keep, (void*)st->ws, (void*)st->tokens, (void*)st->state, (void*)st->tap, (void*)st->ftap_mel, (void*)st->ftap_conv}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)st->kring, (void*)st->vring, (void*)st->samples, (void*)st->audio_keep, (void*)st->ws, (void*)st->tokens, (void*)st->state, (void*)st->tap, (void*)st->ftap_mel, (void*)st->ftap_conv,
+                    (void*)st->rs_matrix, (void*)st->in_ring, (void*)st->s16_stage}) if (p) (void)hipFree(p);
     binding_release(st->eng);
     delete st;
 }
 
-extern "C" int32_t vox_stream_create(vox_model* m, const float* t_embed, float gain, int32_t enc_capacity_rows, int32_t max_positions, vox_stream** out) {
-    ARGCHK(m && t_embed && out, "null argument"); ARGCHK(std::isfinite(gain), "gain is not finite");
+// sample_rate 16000: the 16 kHz stream, nothing more; any other rate: + the input ring and the stream's own block matrix
+static int32_t stream_create(vox_model* m, const float* t_embed, float gain, int32_t enc_capacity_rows, int32_t max_positions, uint32_t sample_rate, vox_stream** out) {
+    ARGCHK(m && t_embed && out, "null argument"); ARGCHK(std::isfinite(gain), "gain is not finite"); ARGCHK(sample_rate > 0, "bad sample rate 0");
     VOXCHK(ctx_bind(m->ctx));
+    ResamplePlan rp; size_t rs_bytes = 0; int in_ring_n = 0;
+    if (sample_rate != 16000) {
+        rp = resample_plan_make(sample_rate, 16000);
+        VOXCHK(resample_matrix_bytes(sample_rate, 16000, rp, &rs_bytes));
+        if (2 * rp.fft_in + STREAM_FEED_CHUNK > STREAM_IN_RING_MAX)
+            return fail(VOX_ERR_UNSUPPORTED, "a stream at %u Hz: two blocks of %ld samples do not fit its input ring of %d", sample_rate, rp.fft_in, STREAM_IN_RING_MAX);
+        for (in_ring_n = 1; in_ring_n < 2 * rp.fft_in + STREAM_FEED_CHUNK;) in_ring_n <<= 1;
+    }
     const vox_model_cfg& c = m->cfg; vox_ctx* cx = m->ctx;
     if (!m->is_q4) return fail(VOX_ERR_UNSUPPORTED, "live streaming sessions serve Q4 (GGUF) models");
     int RC, PC; prefix_bounds(m, &RC, &PC);
@@ -4197,6 +4247,7 @@ extern "C" int32_t vox_stream_create(vox_model* m, const float* t_embed, float g
     ARGCHK(maxp > VOX_PREFIX_TOKENS && maxp <= pos_limit, "max_positions %d out of range (%d..%d)", maxp, VOX_PREFIX_TOKENS + 1, pos_limit);
     VOXCHK(enc_stream_rope_ensure(m));
     vox_stream* st = new vox_stream(); st->m = m; st->ctx = cx; st->t_embed.assign(t_embed, t_embed + c.dec_dim); st->gain = gain; st->cap = cap; st->max_pos = maxp; st->RC = RC; st->PC = PC;
+    st->sr = sample_rate; st->rp = rp; st->in_ring_n = in_ring_n;
     { vox_pad_cfg pc; vox_pad_cfg_voxtral(&pc); st->left = (long)pad_left(&pc); }
     const int D = c.enc_dim, QD = c.enc_heads * c.enc_head_dim, F = c.enc_ffn, DD = c.dec_dim;
     st->ring_layer = (size_t)c.enc_heads * cap * c.enc_head_dim;
@@ -4207,12 +4258,21 @@ extern "C" int32_t vox_stream_create(vox_model* m, const float* t_embed, float g
     A((void**)&st->kring, ring_b); A((void**)&st->vring, ring_b); A((void**)&st->samples, (size_t)STREAM_SAMPLE_RING * 4); A((void**)&st->audio_keep, keep_b);
     A((void**)&st->ws, ws_f * 4); A((void**)&st->tokens, (size_t)(maxp + 2) * 4); A((void**)&st->state, sizeof(int) * STRM_WORDS);
     if (e == hipSuccess) e = binding_alloc(m, st->eng, &st->bytes);      // (here, not at the first step: the footprint a stream reports does not depend on what it has done)
+    if (in_ring_n) A((void**)&st->in_ring, (size_t)in_ring_n * 4);
     if (e != hipSuccess) { (void)hipGetLastError(); stream_release(st); return fail(VOX_ERR_HIP, "allocating the stream's device state failed: %s", hipGetErrorString(e)); }
     int32_t r = ctx_mel_tables(cx, &st->mel);
     if (r == VOX_OK && hipMemsetAsync(st->samples, 0, (size_t)STREAM_SAMPLE_RING * 4, cx->stream) != hipSuccess) r = fail(VOX_ERR_HIP, "hipMemsetAsync failed");
+    if (r == VOX_OK && in_ring_n) { r = resample_matrix_build(cx, rp, rs_bytes, &st->rs_matrix); if (r == VOX_OK) st->bytes += rs_bytes; }
     if (r == VOX_OK) r = stream_load_initial(st);
     if (r != VOX_OK) { stream_release(st); return r; }
     *out = st; return VOX_OK;
+}
+extern "C" int32_t vox_stream_create(vox_model* m, const float* t_embed, float gain, int32_t enc_capacity_rows, int32_t max_positions, vox_stream** out) {
+    return stream_create(m, t_embed, gain, enc_capacity_rows, max_positions, 16000, out);
+}
+extern "C" int32_t vox_stream_create_rate(vox_model* m, const float* t_embed, float gain, int32_t enc_capacity_rows, int32_t max_positions, uint32_t sample_rate, vox_stream** out) {
+    ARGCHK(sample_rate > 0, "bad sample rate 0");
+    return stream_create(m, t_embed, gain, enc_capacity_rows, max_positions, sample_rate, out);
 }
 extern "C" int32_t vox_stream_free(vox_stream* st) { stream_release(st); return VOX_OK; }
 extern "C" int32_t vox_stream_reset(vox_stream* st) {
@@ -4332,19 +4392,45 @@ static int32_t stream_tick(vox_stream* st) {
     return stream_decode_step(st, h, stream_tap_row(st), R);
 }
 
-// append `n` samples (src null: zeros, the right pad) and run every tick up to position `target` as soon as its samples are in the ring
-static int32_t stream_feed(vox_stream* st, const float* src, size_t n, int32_t mem_kind, int target) {
-    hipStream_t s = st->ctx->stream; const int R = st->m->cfg.reshape_factor;
+// what a call appends: f32 or 16-bit samples in host or device memory; p null: zeros (the right pad)
+struct StreamSrc { const void* p = nullptr; bool s16 = false; int32_t mem_kind = VOX_MEM_DEVICE; };
+// samples [at, at + len) of the source into ring[(w0 + k) & (ring_n - 1)], k < len <= ring_n: f32 and zeros as at most two copies (the ring wraps), 16-bit samples through
+// stream_s16_kernel (which wraps by itself), host ones in pieces of the staging buffer
+static int32_t stream_ring_write(vox_stream* st, float* ring, int ring_n, int64_t w0, const StreamSrc& src, size_t at, size_t len) {
+    hipStream_t s = st->ctx->stream;
+    if (src.p && src.s16) {
+        const int16_t* v = (const int16_t*)src.p + at;
+        if (src.mem_kind == VOX_MEM_DEVICE) { HIPCHK(launch_stream_s16(v, (int)len, ring, ring_n - 1, (long)w0, s)); return VOX_OK; }
+        if (!st->s16_stage) { HIPCHK(hipMalloc((void**)&st->s16_stage, (size_t)STREAM_FEED_CHUNK * 2)); st->bytes += (size_t)STREAM_FEED_CHUNK * 2; }
+        for (size_t w = 0; w < len;) {      // (stream order keeps a piece's conversion ahead of the next piece's upload)
+            const size_t k = std::min(len - w, (size_t)STREAM_FEED_CHUNK);
+            HIPCHK(hipMemcpyAsync(st->s16_stage, v + w, k * 2, hipMemcpyHostToDevice, s));
+            HIPCHK(launch_stream_s16(st->s16_stage, (int)k, ring, ring_n - 1, (long)(w0 + (int64_t)w), s));
+            w += k;
+        }
+        return VOX_OK;
+    }
+    for (size_t w = 0; w < len;) {      // at most two pieces: the ring wraps
+        const size_t off = (size_t)((w0 + (int64_t)w) & (ring_n - 1)), k = std::min(len - w, (size_t)ring_n - off);
+        if (!src.p) HIPCHK(hipMemsetAsync(ring + off, 0, k * 4, s));
+        else HIPCHK(hipMemcpyAsync(ring + off, (const float*)src.p + at + w, k * 4, src.mem_kind == VOX_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+        w += k;
+    }
+    return VOX_OK;
+}
+// 16 kHz samples the ring can take: everything from the oldest sample the next tick reads stays
+static size_t stream_room16(const vox_stream* st) {
+    const int R = st->m->cfg.reshape_factor;
+    const long lo = std::max(0L, (4L * R * st->pos - 3) * 160 - 200 - st->left);
+    return (size_t)STREAM_SAMPLE_RING - (size_t)(st->n_written - lo);
+}
+// append `n` 16 kHz samples and run every tick up to position `target` as soon as its samples are in the ring
+static int32_t stream_feed(vox_stream* st, const StreamSrc& src, size_t n, int target) {
+    const int R = st->m->cfg.reshape_factor;
     size_t done = 0;
     while (done < n || st->pos < target) {
-        const long lo = std::max(0L, (4L * R * st->pos - 3) * 160 - 200 - st->left);      // the oldest sample the next tick reads
-        const size_t room = (size_t)STREAM_SAMPLE_RING - (size_t)(st->n_written - lo), chunk = std::min(n - done, room);
-        for (size_t w = 0; w < chunk;) {      // at most two pieces: the ring wraps
-            const size_t off = (size_t)((st->n_written + (int64_t)w) & (STREAM_SAMPLE_RING - 1)), len = std::min(chunk - w, (size_t)STREAM_SAMPLE_RING - off);
-            if (!src) HIPCHK(hipMemsetAsync(st->samples + off, 0, len * 4, s));
-            else HIPCHK(hipMemcpyAsync(st->samples + off, src + done + w, len * 4, mem_kind == VOX_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-            w += len;
-        }
+        const size_t chunk = std::min(n - done, stream_room16(st));
+        VOXCHK(stream_ring_write(st, st->samples, STREAM_SAMPLE_RING, st->n_written, src, done, chunk));
         st->n_written += (int64_t)chunk; done += chunk;
         const int avail = (int)std::min<long>(target, stream_positions(st->left, R, st->n_written));
         if (chunk == 0 && st->pos >= avail) return fail(VOX_ERR_INVALID, "internal: stream stalled at position %d of %d", st->pos, target);
@@ -4352,14 +4438,43 @@ static int32_t stream_feed(vox_stream* st, const float* src, size_t n, int32_t m
     }
     return VOX_OK;
 }
-// what a push / finish does around its ticks: the stream's own Ada scales, clean accumulators, then the ids of the call behind ONE synchronisation
-static int32_t stream_run(vox_stream* st, const float* src, size_t n, int32_t mem_kind, int target, int32_t* out_ids, int32_t* n_ids) {
+// a stream at its capture rate: append `n` input-rate samples, turn every block that became complete into 16 kHz samples (finish: everything up to vox_resample_len of
+// the utterance, blocks clipped at its end) and run the ticks those make due, in rounds bounded by the two rings -- a push may be larger than both.  The input ring keeps
+// everything from block c_next - 1 on, c_next the block of the next 16 kHz sample to be produced: that sample reads the tail of the block before its own.
+static int32_t stream_feed_rate(vox_stream* st, const StreamSrc& src, size_t n, bool finish, int target) {
+    const int R = st->m->cfg.reshape_factor; const ResamplePlan& p = st->rp; hipStream_t s = st->ctx->stream;
+    size_t goal16; VOXCHK(stream_samples16(st->sr, p, (size_t)st->in_written + n, finish, &goal16));
+    const int tgt = (int)std::min<long>(target, stream_positions(st->left, R, (int64_t)goal16));
+    size_t done = 0;
+    while (done < n || st->n_written < (int64_t)goal16 || st->pos < tgt) {
+        const int64_t c_next = (st->n_written + p.delay) / p.fft_out, keep_from = std::max<int64_t>(0, c_next - 1) * p.fft_in;
+        const size_t chunk = std::min(n - done, (size_t)st->in_ring_n - (size_t)std::max<int64_t>(0, st->in_written - keep_from));      // (past the last block at finish: nothing is appended)
+        VOXCHK(stream_ring_write(st, st->in_ring, st->in_ring_n, st->in_written, src, done, chunk));
+        st->in_written += (int64_t)chunk; done += chunk;
+        const int64_t have16 = finish ? (int64_t)goal16 : stream_avail16(p, st->in_written);
+        const size_t count = std::min((size_t)std::max<int64_t>(0, have16 - st->n_written), stream_room16(st));
+        HIPCHK(launch_stream_resample(st->in_ring, st->in_ring_n - 1, (long)st->in_written, st->rs_matrix, (int)p.fft_in, (int)p.fft_out, (int)p.delay, st->samples, STREAM_SAMPLE_RING - 1,
+                                      (long)st->n_written, (int)count, s));
+        st->n_written += (int64_t)count;
+        const int avail = (int)std::min<long>(tgt, stream_positions(st->left, R, st->n_written));
+        if (chunk == 0 && count == 0 && st->pos >= avail) return fail(VOX_ERR_INVALID, "internal: stream stalled at position %d of %d (%lld of %zu samples at 16 kHz)", st->pos, tgt, (long long)st->n_written, goal16);
+        while (st->pos < avail) VOXCHK(stream_tick(st));
+    }
+    return VOX_OK;
+}
+// what a push / finish does around its ticks: the stream's own Ada scales, clean accumulators, then the ids of the call behind ONE synchronisation.
+// finish: a rate stream first produces the rest of its 16 kHz samples; then `n` zeros follow, the right pad
+static int32_t stream_run(vox_stream* st, const StreamSrc& src, size_t n, bool finish, int target, int32_t* out_ids, int32_t* n_ids) {
     vox_model* m = st->m; hipStream_t s = st->ctx->stream;
     const int due = target - st->pos;
     if (m->pw_pend_rows > 0) VOXCHK(pw_sync(m));      // unverified engine steps of the piecewise surface share the engine's error word: settled first
     VOXCHK(vox_model_set_t_embed(m, st->t_embed.data()));
     if (due > 0) VOXCHK(wo_acc_clear(m, s));
-    VOXCHK(stream_feed(st, src, n, mem_kind, target));
+    if (st->sr != 16000 && !finish) VOXCHK(stream_feed_rate(st, src, n, false, target));
+    else {
+        if (st->sr != 16000) VOXCHK(stream_feed_rate(st, StreamSrc{}, 0, true, target));
+        VOXCHK(stream_feed(st, src, n, target));
+    }
     int32_t* ids_dev = st->tokens + VOX_PREFIX_TOKENS + st->ids_out;
     VOXCHK(stream_verify_enqueue(st));
     if (due > 0) HIPCHK(hipMemcpyAsync(out_ids, ids_dev, (size_t)due * 4, hipMemcpyDeviceToHost, s));
@@ -4370,30 +4485,40 @@ static int32_t stream_run(vox_stream* st, const float* src, size_t n, int32_t me
     return VOX_OK;
 }
 
-extern "C" int32_t vox_stream_push(vox_stream* st, const float* samples, size_t n, int32_t mem_kind, int32_t* out_ids, int32_t cap, int32_t* n_ids) {
+static int32_t stream_push(vox_stream* st, const void* samples, bool s16, size_t n, int32_t mem_kind, int32_t* out_ids, int32_t cap, int32_t* n_ids) {
     ARGCHK(st && n_ids && (samples || n == 0), "null argument"); ARGCHK(cap >= 0 && (out_ids || cap == 0), "bad output buffer"); ARGCHK(n <= ((size_t)1 << 36), "push of %zu samples", n);
     ARGCHK(mem_kind == VOX_MEM_HOST || mem_kind == VOX_MEM_DEVICE, "bad mem_kind %d", mem_kind);
     ARGCHK(!st->finished, "the stream is finished: vox_stream_reset starts the next utterance");
-    const long P = stream_positions(st->left, st->m->cfg.reshape_factor, st->n_pushed + (int64_t)n);
+    size_t n16; VOXCHK(stream_samples16(st->sr, st->rp, (size_t)st->n_pushed + n, false, &n16));
+    const long P = stream_positions(st->left, st->m->cfg.reshape_factor, (int64_t)n16);
     ARGCHK(P <= st->max_pos, "the push would reach decoder position %ld of a stream created for %d (vox_stream_reset starts over)", P, st->max_pos);
     const int target = std::max((int)P, st->pos), due = target - st->pos;
     ARGCHK(cap >= due, "out_ids capacity %d < %d ids due", cap, due);      // BEFORE anything is appended: the call can be repeated
     VOXCHK(ctx_bind(st->ctx));
     st->n_pushed += (int64_t)n;
-    return stream_run(st, samples, n, mem_kind, target, out_ids, n_ids);
+    StreamSrc src; src.p = samples; src.s16 = s16; src.mem_kind = mem_kind;
+    return stream_run(st, src, n, false, target, out_ids, n_ids);
+}
+extern "C" int32_t vox_stream_push(vox_stream* st, const float* samples, size_t n, int32_t mem_kind, int32_t* out_ids, int32_t cap, int32_t* n_ids) {
+    return stream_push(st, samples, false, n, mem_kind, out_ids, cap, n_ids);
+}
+extern "C" int32_t vox_stream_push_s16(vox_stream* st, const int16_t* samples, size_t n, int32_t mem_kind, int32_t* out_ids, int32_t cap, int32_t* n_ids) {
+    ARGCHK(mem_kind == VOX_MEM_HOST || mem_kind == VOX_MEM_DEVICE, "bad mem_kind %d", mem_kind);
+    return stream_push(st, samples, true, n, mem_kind, out_ids, cap, n_ids);
 }
 extern "C" int32_t vox_stream_finish(vox_stream* st, int32_t* out_ids, int32_t cap, int32_t* n_ids) {
     ARGCHK(st && n_ids, "null argument"); ARGCHK(cap >= 0 && (out_ids || cap == 0), "bad output buffer");
     ARGCHK(!st->finished, "the stream is finished already");
     vox_pad_cfg pc; vox_pad_cfg_voxtral(&pc);
-    size_t total; VOXCHK(vox_pad_len((size_t)st->n_pushed, &pc, &total));
+    size_t n16; VOXCHK(stream_samples16(st->sr, st->rp, (size_t)st->n_pushed, true, &n16));
+    size_t total; VOXCHK(vox_pad_len(n16, &pc, &total));
     const int S = (int)(total / (size_t)stream_spp(st->m->cfg.reshape_factor));
     ARGCHK(S - 1 <= st->max_pos, "finishing would reach decoder position %d of a stream created for %d", S - 1, st->max_pos);
     const int target = std::max(S - 1, st->pos), due = target - st->pos;      // the steps at positions 37 .. S - 2 yield the S - 38 ids of the offline path
     ARGCHK(cap >= due, "out_ids capacity %d < %d ids due", cap, due);
     VOXCHK(ctx_bind(st->ctx));
-    const size_t right = total - (size_t)st->left - (size_t)st->n_pushed;
-    VOXCHK(stream_run(st, nullptr, right, VOX_MEM_DEVICE, target, out_ids, n_ids));
+    const size_t right = total - (size_t)st->left - n16;
+    VOXCHK(stream_run(st, StreamSrc{}, right, true, target, out_ids, n_ids));
     st->finished = true;
     return VOX_OK;
 }

@@ -370,6 +370,14 @@ enum StreamWord { STRM_POS = 0,         // decoder position of the next tick (= 
 // conv stem's im2col GEMM reads).  Sample i of the stream lives at ring[i & ring_mask]; every sample a frame reads has been written (the host runs a tick only then),
 // the reflections of mel_kernel never apply (left >= 200, and the right end of a finished stream is its zero pad).
 hipError_t launch_stream_mel(const float* ring, int ring_mask, long left, float gain, MelTables t, const int* state, int halo_back, int n_frames, float* out, hipStream_t s);
+// ingest at the capture rate: the 16 kHz samples [i0, i0 + count) of the stream from its input-rate ring, with resample_apply_kernel's arithmetic (At, fft_in, fft_out, delay:
+// launch_resample's) -- bit for bit vox_resample's samples for the concatenated input.  Input sample k lives at in_ring[k & in_mask], output sample i goes to
+// out_ring[i & out_mask]; n_in: the input samples that exist (written so far, or the utterance's length at its end): blocks are clipped there.  The caller launches it only
+// for samples whose blocks are complete or clipped, and while block (i0 + delay) / fft_out - 1 is still in the input ring.  count <= out_mask + 1.
+hipError_t launch_stream_resample(const float* in_ring, int in_mask, long n_in, const float* At, int fft_in, int fft_out, int delay, float* out_ring, int out_mask, long i0, int count,
+                                  hipStream_t s);
+// 16-bit PCM into a stream's f32 ring: ring[(w0 + k) & mask] = float(src[k]) / 32768 for k < count <= mask + 1 (src: device memory)
+hipError_t launch_stream_s16(const short* src, int count, float* ring, int mask, long w0, hipStream_t s);
 // one encoder layer's attention for the tick's M <= 8 rows against the stream's K / V ring: RoPE on q and k at the absolute stream position, k / v appended at
 // position % cap, query m attends the keys j <= position_m, position_m - j <= window in ascending order of j (the ring changes addresses, not the order).  cap > window + M.
 struct StreamAttnParams {

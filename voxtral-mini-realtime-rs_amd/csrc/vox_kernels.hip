@@ -4210,6 +4210,53 @@ hipError_t launch_stream_mel(const float* ring, int ring_mask, long left, float 
     return hipGetLastError();
 }
 
+// ingest of a stream fed at its capture rate: resample_apply_kernel on rings.  One thread per 16 kHz sample i of [i0, i0 + count): input sample k of the stream lives at
+// in_ring[k & in_mask], output sample i goes to out_ring[i & out_mask] (the ring stream_mel_kernel reads).  The arithmetic is resample_apply_kernel's, term for term --
+// the block's own first half and the previous block's tail as two fmaf chains in ascending n, then a0 + a1, no second chain at c == 0, blocks clipped at n_in -- so every
+// sample has the bits vox_resample gives for the concatenated input; the sums are not reordered.  The host launches it only for samples whose blocks are complete (or,
+// at the end of the utterance, with n_in = its length) and keeps the input ring from block c - 1 of the oldest sample still to be produced.
+// (VOX_NO_PK_F32: a0 / a1 are f32 pair arithmetic in one thread; no packed form is wanted on a stream kernel's lanes, vox_kernels.h.)
+__global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_resample_kernel(const float* __restrict__ in_ring, int in_mask, long n_in, const float* __restrict__ At, int fft_in, int fft_out,
+                                                                            int delay, float* __restrict__ out_ring, int out_mask, long i0, int count) {
+    const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (k >= count) return;
+    const long i = i0 + k;
+    const long j = i + delay, c = j / fft_out; const int m = (int)(j - c * fft_out);
+    const int ld = 2 * fft_out;
+    float a0 = 0.f, a1 = 0.f;
+    {
+        const long base = c * fft_in; const int cnt = (int)max(0L, min((long)fft_in, n_in - base));
+        const float* ap = At + m;
+        for (int n = 0; n < cnt; n++) a0 = fmaf(in_ring[(base + n) & (long)in_mask], ap[(size_t)n * ld], a0);
+    }
+    if (c > 0) {
+        const long base = (c - 1) * fft_in; const int cnt = (int)max(0L, min((long)fft_in, n_in - base));
+        const float* ap = At + fft_out + m;
+        for (int n = 0; n < cnt; n++) a1 = fmaf(in_ring[(base + n) & (long)in_mask], ap[(size_t)n * ld], a1);
+    }
+    out_ring[i & (long)out_mask] = a0 + a1;
+}
+hipError_t launch_stream_resample(const float* in_ring, int in_mask, long n_in, const float* At, int fft_in, int fft_out, int delay, float* out_ring, int out_mask, long i0, int count,
+                                  hipStream_t s) {
+    if (count <= 0) return hipSuccess;
+    if ((in_mask & (in_mask + 1)) || (out_mask & (out_mask + 1)) || in_mask < 0 || out_mask < 0 || fft_in <= 0 || fft_out <= 0 || delay < 0 || i0 < 0 || n_in < 0 || count > out_mask + 1)
+        return hipErrorInvalidValue;
+    stream_resample_kernel<<<dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s>>>(in_ring, in_mask, n_in, At, fft_in, fft_out, delay, out_ring, out_mask, i0, count);
+    return hipGetLastError();
+}
+// 16-bit PCM into a stream's f32 ring: ring[(w0 + k) & mask] = float(src[k]) / 32768 (the mono 16-bit scale of audio/io.rs:110-113; a power of two: exact in f32)
+__global__ __launch_bounds__(256) void stream_s16_kernel(const short* __restrict__ src, int count, float* __restrict__ ring, int mask, long w0) {
+    const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (k >= count) return;
+    ring[(w0 + k) & (long)mask] = (float)src[k] * (1.0f / 32768.0f);
+}
+hipError_t launch_stream_s16(const short* src, int count, float* ring, int mask, long w0, hipStream_t s) {
+    if (count <= 0) return hipSuccess;
+    if ((mask & (mask + 1)) || mask < 0 || w0 < 0 || count > mask + 1) return hipErrorInvalidValue;
+    stream_s16_kernel<<<dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s>>>(src, count, ring, mask, w0);
+    return hipGetLastError();
+}
+
 // RoPE + K / V append + windowed attention of one encoder layer for the tick's rows, one workgroup per (head, query row).  The workgroup rotates the tick's k rows
 // 0 .. m of its head itself (LDS), so no workgroup reads a ring row another one writes in this launch: ring rows are read for positions below the tick's first only, and
 // with cap > window + M the rows written now hold positions no query of the tick sees any more.  Scores: 16 lanes per key (one float4 each at hd 64), the keys in

@@ -397,35 +397,58 @@ def argmax_rows_dev(ctx, logits_ptr, rows, vocab):
     return ids
 
 
-def stream_schedule(n_samples: int, finished: bool = False):
-    """vox_stream_schedule (host arithmetic): (decoder positions determined, ids due) after `n_samples` pushed, or at the end of an n_samples utterance."""
+def stream_schedule_rate(n_samples: int, sample_rate: int, finished: bool = False):
+    """vox_stream_schedule_rate (host arithmetic) for a stream fed at `sample_rate`: (decoder positions determined, ids due, 16 kHz samples the stream holds) after
+    `n_samples` pushed, or at the end of an n_samples utterance."""
+    p = C.c_int32(); i = C.c_int32(); k = C.c_size_t()
+    check(lib().vox_stream_schedule_rate(int(n_samples), int(sample_rate), 1 if finished else 0, C.byref(p), C.byref(i), C.byref(k)))
+    return p.value, i.value, k.value
+
+
+def stream_schedule(n_samples: int, finished: bool = False, sample_rate: int = 16000):
+    """vox_stream_schedule (host arithmetic): (decoder positions determined, ids due) after `n_samples` pushed, or at the end of an n_samples utterance; samples counted
+    at `sample_rate`, the rate of the stream (vox_stream_schedule_rate)."""
+    if int(sample_rate) != 16000:
+        return stream_schedule_rate(n_samples, sample_rate, finished)[:2]
     p = C.c_int32(); i = C.c_int32()
     check(lib().vox_stream_schedule(int(n_samples), 1 if finished else 0, C.byref(p), C.byref(i)))
     return p.value, i.value
 
 
 class LiveStream:
-    """A live streaming session (vox_stream): push 16 kHz samples in pieces of any size, get token ids back as soon as they are determined; after finish() the
-    concatenation equals transcribe_streaming on the log-mel of pad_audio(gain * samples).  One decoder position = 2560 samples = 160 ms."""
+    """A live streaming session (vox_stream): push samples in pieces of any size, get token ids back as soon as they are determined; after finish() the
+    concatenation equals transcribe_streaming on the log-mel of pad_audio(gain * samples).  One decoder position = 2560 samples = 160 ms at 16 kHz.
+    sample_rate: the rate of what is pushed (vox_stream_create_rate); other than 16 kHz the session resamples incrementally and gives the ids of a 16 kHz session
+    fed resample(samples)."""
 
-    def __init__(self, model, t_embed, gain=1.0, enc_capacity_rows=0, max_positions=0):
-        self.model = model; self.h = C.c_void_p()
-        check(lib().vox_stream_create(model.h, _ptr(_f32(t_embed).reshape(-1)), float(gain), int(enc_capacity_rows), int(max_positions), C.byref(self.h)))
+    def __init__(self, model, t_embed, gain=1.0, enc_capacity_rows=0, max_positions=0, sample_rate=16000):
+        self.model = model; self.h = C.c_void_p(); self.sample_rate = int(sample_rate)
+        args = (model.h, _ptr(_f32(t_embed).reshape(-1)), float(gain), int(enc_capacity_rows), int(max_positions))
+        if self.sample_rate == 16000:
+            check(lib().vox_stream_create(*args, C.byref(self.h)))
+        else:
+            check(lib().vox_stream_create_rate(*args, self.sample_rate, C.byref(self.h)))
         model._caches.add(self)
 
     def _ids(self, call, n_new, finished):
-        due = stream_schedule(self.info()["samples"] + n_new, finished)[1] - self.info()["ids"]
+        due = stream_schedule(self.info()["samples"] + n_new, finished, self.sample_rate)[1] - self.info()["ids"]
         ids = np.zeros(max(due, 1), dtype=np.int32); n = C.c_int32()
         check(call(_ptr(ids), ids.size, C.byref(n)))
         return ids[:n.value].copy()
 
-    def push(self, samples=None, device_ptr=None, n_samples=None) -> np.ndarray:
-        """Append samples (a float32 array, or a device pointer + count) -> the ids that became determined (possibly none)."""
+    def push(self, samples=None, device_ptr=None, n_samples=None, dtype=None) -> np.ndarray:
+        """Append samples at the stream's rate -> the ids that became determined (possibly none).  samples: an int16 array (16-bit PCM, vox_stream_push_s16) or
+        anything else as float32; or a device pointer + count, of float32 or, with dtype="s16", of 16-bit PCM."""
         if device_ptr is None:
-            x = _f32(samples).reshape(-1); n_samples = x.size; ptr = _ptr(x) if x.size else None; kind = 0
+            s16 = isinstance(samples, np.ndarray) and samples.dtype == np.int16
+            x = np.ascontiguousarray(samples).reshape(-1) if s16 else _f32(samples).reshape(-1)
+            n_samples = x.size; ptr = _ptr(x) if x.size else None; kind = 0
         else:
-            ptr = C.c_void_p(device_ptr); kind = 1
-        return self._ids(lambda o, c, n: lib().vox_stream_push(self.h, ptr, n_samples, kind, o, c, n), n_samples, False)
+            if dtype not in (None, "f32", "s16"):
+                raise ValueError(f"dtype {dtype!r}: a device pointer holds 'f32' or 's16' samples")
+            s16 = dtype == "s16"; ptr = C.c_void_p(device_ptr); kind = 1
+        fn = lib().vox_stream_push_s16 if s16 else lib().vox_stream_push
+        return self._ids(lambda o, c, n: fn(self.h, ptr, n_samples, kind, o, c, n), n_samples, False)
 
     def finish(self) -> np.ndarray:
         """End of the utterance: the right pad is appended, the remaining ids come back."""
@@ -640,10 +663,10 @@ class Q4VoxtralModel:
         check(lib().vox_transcribe_audio(self.h, ptr, n_samples, _ptr(t), _ptr(ids), cap, C.byref(n), kind))
         return ids[:n.value].copy()
 
-    def create_stream(self, t_embed, gain=1.0, enc_capacity_rows=0, max_positions=0) -> LiveStream:
-        """A live session on this model (vox_stream_create): push(x) -> ids, finish(), reset(), info(), close().  gain multiplies every sample (a stream has no
-        file peak: 0.95 / max|x| of a known file reproduces transcribe_audio)."""
-        return LiveStream(self, t_embed, gain, enc_capacity_rows, max_positions)
+    def create_stream(self, t_embed, gain=1.0, enc_capacity_rows=0, max_positions=0, sample_rate=16000) -> LiveStream:
+        """A live session on this model (vox_stream_create / vox_stream_create_rate): push(x) -> ids, finish(), reset(), info(), close().  gain multiplies every sample
+        (a stream has no file peak: 0.95 / max|x| of a known file reproduces transcribe_audio).  sample_rate: the rate of the samples that will be pushed."""
+        return LiveStream(self, t_embed, gain, enc_capacity_rows, max_positions, sample_rate)
 
     def transcribe_batch(self, samples_list, t_embed, device_ptrs=None, n_samples=None, norm_group=None, tap_units=None):
         """Batched whole-path transcription of independent utterances (<= 4096; wider than 16: continuous batching over decode slots): list of float32 sample arrays
