@@ -509,6 +509,43 @@ int32_t vox_debug_stream_tap_fetch(vox_stream* s, float* out_rows_x_vocab, int32
 int32_t vox_debug_stream_front_tap_arm(vox_stream* s, int32_t max_ticks);
 int32_t vox_debug_stream_front_tap_fetch(vox_stream* s, float* out_mel, float* out_conv, int32_t* ticks);
 
+/* ---- stream group: up to 16 live sessions advanced together (no reference counterpart) ---------------------------------------------------------------------------------
+ * A vox_stream_group holds n_members member sessions on one model and one t_embed, each with its own gain, sample ring, encoder K / V ring and slice of the group's
+ * decoder cache.  vox_stream_group_advance feeds any subset of the members (16 kHz f32 samples, host or device memory: mem_kind holds for the whole call) and advances
+ * them together: every weight matrix is read by ONE launch per tick for all members that have a tick due, and the call synchronises once.
+ *   Contract: a member's schedule is vox_stream_schedule's on that member's own sample count; every call hands each fed member exactly the ids that became due, and a
+ *   member fed with finish = 1 ends its utterance with those samples (right pad, remaining ids: vox_pad_len(n) / 2560 - 38 in all).  A member's ids are those of a solo
+ *   vox_stream with the same gain fed the same samples in the project's usual sense -- its logits stay within f32 summation-order noise (2e-4 of the largest logit) of the
+ *   teacher-forced logits, so its ids change only after a near-tie.  They are NOT claimed bit-identical to the solo stream's: the number of members that tick together
+ *   selects the GEMM kernels (4 rows per member through the encoder, 1 through the decoder), so a member's last bits depend on who else is due.  A solo vox_stream keeps
+ *   its bit-for-bit claims.
+ *   Refusals happen before anything changes (the call can be repeated, vox_stream_group_info is unchanged): cap below the ids due for an entry, a member fed twice in one
+ *   call, a finished member fed before its vox_stream_group_reset, a push past max_positions, a bad member or mem_kind.
+ *   Decode step: the batched step's launch chain on the group's cache slab [layer][member][kv_head][max_positions][head_dim], which does not grow: max_positions = 0
+ *   selects 2048 (5.4 minutes; at full size 0.21 MB per position, 0.44 GB per member) and a member that reaches it is refused until its reset.  Each member also holds an
+ *   encoder ring (enc_capacity_rows as vox_stream_create's: 0.4 GB at full size).  The decode engine is not used.
+ *   Creation refuses (VOX_ERR_UNSUPPORTED) what vox_stream_create refuses and models without tile-ordered Q4 weights; n_members outside 1..16 is invalid.
+ *   16 kHz f32 only (no capture rate, no 16-bit PCM).  gains: one per member, null = 1.0 each. */
+typedef struct vox_stream_group vox_stream_group;
+typedef struct {
+    int32_t member;            /* 0 .. n_members-1, at most one entry per member per call */
+    int32_t finish;            /* 1: after these samples the member's utterance ends (right pad, remaining ids) */
+    const float* samples;      /* 16 kHz f32, mem_kind of the call; may be null when n_samples == 0 */
+    size_t n_samples;
+    int32_t* out_ids; int32_t cap;
+    int32_t n_ids;             /* out */
+} vox_stream_feed;
+int32_t vox_stream_group_create(vox_model* m, const float* t_embed, int32_t n_members, const float* gains /* null: 1.0 */,
+                                int32_t enc_capacity_rows, int32_t max_positions, vox_stream_group** out);
+int32_t vox_stream_group_advance(vox_stream_group* g, vox_stream_feed* feeds, int32_t n_feeds, int32_t mem_kind);
+int32_t vox_stream_group_reset(vox_stream_group* g, int32_t member, float gain);   /* member back to the prefix state: the next connection */
+/* vox_stream_info's eight words for the member; [5] is the member's share of the group's device bytes, [6] is 0 (no engine step), [7] counts the member's ticks */
+int32_t vox_stream_group_info(const vox_stream_group* g, int32_t member, int64_t out[8]);
+int32_t vox_stream_group_free(vox_stream_group* g);
+/* vox_debug_stream_tap_* for one member (the rows are copied by the tick's last kernel; a reset of the member starts the count again) */
+int32_t vox_debug_stream_group_tap_arm(vox_stream_group* g, int32_t member, int32_t max_rows);
+int32_t vox_debug_stream_group_tap_fetch(vox_stream_group* g, int32_t member, float* out, int32_t* rows);
+
 #ifdef __cplusplus
 }
 #endif

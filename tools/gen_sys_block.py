@@ -50,7 +50,7 @@ def parse_header():
             if not decl:
                 continue
             ty, names = decl.rsplit(None, 1)[0], decl
-            mm = re.match(r"((?:const\s+)?[A-Za-z_][A-Za-z0-9_]*)\s+(.*)", decl)
+            mm = re.match(r"((?:const\s+)?[A-Za-z_][A-Za-z0-9_]*\s*\**)\s*(.*)", decl)      # pointer fields: `const float* samples`
             ty, names = mm.group(1), mm.group(2)
             for n in names.split(","):
                 fields.append((n.strip(), rust_type(ty)))
@@ -79,7 +79,7 @@ def generate() -> str:
         out.append(f"#[repr(C)] pub struct {o} {{ _p: [u8; 0] }}")
     out.append("")
     for name, fields in structs:
-        out.append("#[repr(C)] #[derive(Clone, Copy, Debug, Default)]")
+        out.append("#[repr(C)] #[derive(Clone, Copy, Debug%s)]" % ("" if any("*" in t for _, t in fields) else ", Default"))      # (raw pointers have no Default)
         out.append(f"pub struct {name} {{ " + ", ".join(f"pub {KEYWORDS.get(n, n)}: {t}" for n, t in fields) + " }")
     out.append("")
     for n, v, u in consts:

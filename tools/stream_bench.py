@@ -2,6 +2,7 @@
 """Steady-state tick time of a live streaming session (vox_stream) on the full-size Q4 model, next to what a caller could do before it existed.
 
     python tools/stream_bench.py [--gguf PATH] [--ticks 200] [--passes 3] [--out profiles/stream_tick.txt]
+    python tools/stream_bench.py --group 1,2,4,8,16 [--out profiles/stream_group_tick.txt]
 
  * stream: HIP events on the context's stream around ONE push of `ticks` x 2560 samples (a large push is a loop of identical ticks), at encoder positions past the
    750-row window, median of `passes` passes; launches per tick from the library's launch counters plus the fixed launches of a tick; wall time of single 160 ms pushes
@@ -9,6 +10,9 @@
  * baseline, same box, same run, from the public entries a caller had: the same audio's log-mel cut into 16-frame chunks, each through vox_encode_audio_with_cache
    (device mel in, device row out) plus one piecewise decoder step (embed_tokens_from_ids_ex, vox_tensor_add, vox_forward_hidden_with_cache_ex, vox_lm_head_argmax).  It is
    NOT exact at chunk borders (the conv stem zero-pads every chunk) -- it prices the same work, not the same result.
+ * --group N[,N...]: steady ROUNDS of a stream group (vox_stream_group) of N members, every member active and past the 750-row encoder window: HIP events around ONE
+   advance of `ticks` ticks per member (= `ticks` rounds of width N), median of `passes` passes, next to the solo stream's tick in the same run -- a solo pass and a
+   group pass alternate; launches per round from the library's launch counters plus the fixed launches of a round.  No baseline in this mode.
  * derived figures are labelled as derived."""
 import argparse
 import ctypes as C
@@ -56,10 +60,43 @@ def launch_counts(pkg):
     return sum(a), sum(g)
 
 
+def bench_groups(pkg, ctx, m, t, tm, a, widths, lines):
+    """--group: per width N, `passes` x (one solo push of `ticks` ticks, one group advance of `ticks` ticks per member), alternating."""
+    c = m.config; S = pkg.synth; warm = 200
+    n_ticks = warm + a.ticks * a.passes + 8
+    assert 37 + n_ticks < 1024, "every timed solo step stays on the decode engine's 1024-row cache"
+    x = S.synth_audio(n_ticks * 0.16 + 1.0, seed=4242); gain = float(np.float32(0.95) / np.float32(np.abs(x).max()))
+    fixed_enc = 1 + 2 * c.enc_layers + 1      # stream_mel, two RMSNorms per encoder layer, the final norm
+    rows = []
+    for N in widths:
+        st = m.create_stream(t, gain=gain); g = m.create_stream_group(t, N, gains=[gain] * N)
+        pos = 40 + 2560 * warm
+        st.push(x[:pos]); g.advance({k: x[:pos] for k in range(N)})
+        solo, grp = [], []; ks = kg = 0
+        for _ in range(a.passes):
+            seg = x[pos:pos + 2560 * a.ticks]; pos += 2560 * a.ticks
+            k0 = launch_counts(pkg); solo.append(tm.ms(lambda: st.push(seg)) / a.ticks); k1 = launch_counts(pkg)
+            feeds = {k: seg for k in range(N)}
+            grp.append(tm.ms(lambda: g.advance(feeds)) / a.ticks); k2 = launch_counts(pkg)
+            ks += sum(k1) - sum(k0); kg += sum(k2) - sum(k1)
+        assert g.info(N - 1)["positions"] == st.info()["positions"] == 38 + warm + a.ticks * a.passes
+        st.close(); g.close()
+        ticks = a.ticks * a.passes; tick = statistics.median(solo); rnd = statistics.median(grp)
+        ls = ks / ticks + fixed_enc + 2; lg = kg / ticks + fixed_enc + 2      # + embed and advance (the group's compaction of the conv rows is a copy, not a launch)
+        rows.append((N, rnd, tick))
+        lines += [f"group of {N:2d}: round median {rnd:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in grp) + f"   solo tick median {tick:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in solo),
+                  f"  round / ({N} x solo tick) = {rnd / (N * tick):.3f}   per member and tick {rnd / N:.3f} ms   launches per round {lg:.0f} (solo tick {ls:.0f})"]
+    lines.append("derived: members one GPU serves in real time at each width = N x 160 ms / round: " + ", ".join(f"{N}: {N * 160.0 / r:.0f}" for N, r, _ in rows))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gguf"); ap.add_argument("--ticks", type=int, default=200); ap.add_argument("--passes", type=int, default=3); ap.add_argument("--out")
+    ap.add_argument("--group", help="N[,N...]: measure stream-group rounds of these widths next to the solo tick instead of the solo tick and its baseline")
     a = ap.parse_args()
+    widths = [int(v) for v in a.group.split(",")] if a.group else []
+    if any(not 1 <= n <= 16 for n in widths):
+        ap.error("--group takes widths 1..16")
     from __graft_entry__ import load_package
     pkg = load_package(); S = pkg.synth
     path = a.gguf
@@ -70,6 +107,17 @@ def main():
             S.write_synthetic_gguf(path + ".tmp", S.ModelDims(), seed=42); os.replace(path + ".tmp", path)
     ctx = pkg.Context(0); m = pkg.Q4ModelLoader.from_file(path).load(ctx); c = m.config
     t = pkg.TimeEmbedding(c.dec_dim).embed(6.0); tm = Timer(pkg, ctx); L = pkg.lib()
+    if widths:
+        lines = ["# " + " ".join(["python", "tools/stream_bench.py"] + sys.argv[1:]),
+                 f"# model {os.path.basename(path)}: {c.enc_layers} encoder layers, {c.dec_layers} decoder layers; {a.ticks} ticks per pass, {a.passes} passes, all past encoder position {4 * (37 + 200)}"]
+        bench_groups(pkg, ctx, m, t, tm, a, widths, lines)
+        text = "\n".join(lines) + "\n"
+        print(text, end="")
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            open(a.out, "w").write(text)
+        m.close(); ctx.close()
+        return
     warm = 200                                  # ticks before the first timed pass: encoder position 4 (37 + 200) = 948, past the 750-row window
     n_ticks = warm + a.ticks * a.passes + 40
     assert 37 + n_ticks < 1024, "every timed step stays on the decode engine's 1024-row cache"

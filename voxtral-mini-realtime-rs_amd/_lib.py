@@ -28,6 +28,12 @@ class Chunk(C.Structure):
     _fields_ = [("start_sample", C.c_size_t), ("end_sample", C.c_size_t), ("index", C.c_size_t), ("is_last", C.c_int32)]
 
 
+class StreamFeed(C.Structure):
+    """vox_stream_feed: one member's entry of a vox_stream_group_advance call"""
+    _fields_ = [("member", C.c_int32), ("finish", C.c_int32), ("samples", C.c_void_p), ("n_samples", C.c_size_t), ("out_ids", C.c_void_p), ("cap", C.c_int32),
+                ("n_ids", C.c_int32)]
+
+
 class ModelCfg(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("enc_layers", "enc_dim", "enc_heads", "enc_head_dim", "enc_ffn", "enc_window",
                                          "dec_layers", "dec_dim", "dec_heads", "dec_kv_heads", "dec_head_dim", "dec_ffn",
@@ -167,6 +173,13 @@ SIGNATURES = {
     "vox_stream_create_rate": (i32, [vp, vp, f32, i32, i32, u32, P(vp)]),
     "vox_stream_push_s16": (i32, [vp, vp, sz, i32, vp, i32, P(i32)]),
     "vox_stream_schedule_rate": (i32, [sz, u32, i32, P(i32), P(i32), P(sz)]),
+    "vox_stream_group_create": (i32, [vp, vp, i32, vp, i32, i32, P(vp)]),
+    "vox_stream_group_advance": (i32, [vp, vp, i32, i32]),
+    "vox_stream_group_reset": (i32, [vp, i32, f32]),
+    "vox_stream_group_info": (i32, [vp, i32, P(i64 * 8)]),
+    "vox_stream_group_free": (i32, [vp]),
+    "vox_debug_stream_group_tap_arm": (i32, [vp, i32, i32]),
+    "vox_debug_stream_group_tap_fetch": (i32, [vp, i32, vp, P(i32)]),
 }
 
 _LIB = None

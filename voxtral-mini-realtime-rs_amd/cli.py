@@ -106,6 +106,44 @@ def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_
         stream.close()
 
 
+def transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, chunk_ms, n_members):
+    """--live-group N: the files N at a time through one stream group (vox_stream_group) in pieces of `chunk_ms` milliseconds: every call feeds each busy member its
+    next piece, a file that ends (its member fed with finish) frees the member for the next file in input order.  Gains and lines as transcribe_live's (16 kHz: other
+    rates are resampled first).  -> {file index: text}; a file that cannot be read is left out (the one-by-one path reports it)."""
+    step = max(1, int(round(16000 * chunk_ms / 1000.0)))
+    group = model.create_stream_group(t_embed, n_members)
+    text = lambda ids: tokenizer.decode([t for t in ids if t >= 1000]).strip()
+    texts = {}; busy = {}; nxt = 0      # busy: member -> [file index, samples, offset, ids]
+    try:
+        while nxt < len(paths) or busy:
+            for k in range(n_members):
+                while k not in busy and nxt < len(paths):
+                    i = nxt; nxt += 1
+                    try:
+                        x, sr = load_wav(paths[i])
+                        if sr != 16000:
+                            x = resample_to_16k(x, sr, mel.ctx, pkg)
+                    except Exception as e:
+                        log(f"Error reading {paths[i]}: {e}"); continue
+                    x = np.ascontiguousarray(x, dtype=np.float32)
+                    peak = np.float32(np.abs(x).max()) if x.size else np.float32(0)
+                    group.reset(k, float(np.float32(0.95) / peak) if peak >= 1e-10 else 1.0)      # audio/io.rs:59-68
+                    busy[k] = [i, x, 0, []]
+            if not busy:
+                break
+            feeds = {k: b[1][b[2]:b[2] + step] for k, b in busy.items()}
+            last = [k for k, b in busy.items() if b[2] + step >= b[1].size]
+            for k, new in group.advance(feeds, finish=last).items():
+                b = busy[k]; b[2] += step
+                if new.size:
+                    b[3].extend(int(t) for t in new); log(f"  [{paths[b[0]]} {min(b[2], b[1].size) / 16000:8.2f} s] {text(b[3])}")
+            for k in last:
+                b = busy.pop(k); texts[b[0]] = text(b[3])
+        return texts
+    finally:
+        group.close()
+
+
 def file_costs(paths):
     """Decode cost of a file ~ its duration (the reference has no early stop): the file size is the proxy that needs no decode."""
     import os
@@ -245,7 +283,15 @@ def main(argv=None):
     ap.add_argument("--live-chunk-ms", type=int, default=160, help="with --live: milliseconds of audio per push (one decoder position = 160 ms)")
     ap.add_argument("--live-native-rate", action="store_true", help="with --live, for a file that is not at 16 kHz: push the file's own-rate samples into a session created "
                     "for that rate (it resamples as they arrive) instead of resampling the whole file first; the line is the same")
+    ap.add_argument("--live-group", type=int, default=0, metavar="N", help="with --live: feed the files N (2..16) at a time through one stream group (vox_stream_group): every "
+                    "weight matrix is read once per tick for all files that have a tick due; same final lines, in input order")
     a = ap.parse_args(argv)
+    if a.live_group and not a.live:
+        ap.error("--live-group applies with --live")
+    if a.live_group and not 2 <= a.live_group <= 16:
+        ap.error("--live-group takes 2..16 members")
+    if a.live_group and a.live_native_rate:
+        ap.error("--live-group feeds 16 kHz samples: it does not combine with --live-native-rate")
     if a.live and (a.gpus > 1 or a.batch > 1 or a.live_chunk_ms <= 0):
         ap.error("--live runs one file at a time on one GPU (no --gpus / --batch) with --live-chunk-ms > 0")
     if a.live_native_rate and not a.live:
@@ -326,6 +372,11 @@ def main(argv=None):
                 model.set_sessions(1)
         if unit_texts is not None:      # (rank 0, or the only rank)
             texts = join_units(len(paths), units, unit_texts)
+    if a.live_group:
+        try:
+            texts = transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_group)
+        except Exception as e:      # the files fall back to one live session each
+            log(f"Error in the stream group: {e}"); texts = {}
     def one(i):
         nonlocal rc
         if i in texts:

@@ -14,6 +14,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <array>
 #include <cassert>
 #include <chrono>
 #include <cmath>
@@ -21,6 +22,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <map>
 #include <mutex>
 #include <string>
@@ -2215,8 +2217,14 @@ static int32_t prefix_build(vox_model* m, const float* t_embed) {
 static int32_t prefix_rows_into(vox_model* m, vox_cache* kc, hipStream_t s) {
     const vox_model_cfg& c = m->cfg; const PrefixState& P = m->pfx;
     const size_t rows_bytes = (size_t)P.PC * c.dec_head_dim * 4, n_rows = (size_t)c.dec_layers * c.dec_kv_heads, pitch = (size_t)kc->max_seq * c.dec_head_dim * 4;
-    HIPCHK(hipMemcpy2DAsync(kc->k, pitch, P.dec_k, rows_bytes, rows_bytes, n_rows, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpy2DAsync(kc->v, pitch, P.dec_v, rows_bytes, rows_bytes, n_rows, hipMemcpyDeviceToDevice, s));
+    const size_t plane = (size_t)c.dec_kv_heads * kc->max_seq * c.dec_head_dim, src_layer = (size_t)c.dec_kv_heads * P.PC * c.dec_head_dim;
+    if (kc->layer_stride == plane) {      // the layers back to back: one copy per tensor
+        HIPCHK(hipMemcpy2DAsync(kc->k, pitch, P.dec_k, rows_bytes, rows_bytes, n_rows, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpy2DAsync(kc->v, pitch, P.dec_v, rows_bytes, rows_bytes, n_rows, hipMemcpyDeviceToDevice, s));
+    } else for (int l = 0; l < c.dec_layers; l++) {      // one sequence's slice of a slab (a stream group's member)
+        HIPCHK(hipMemcpy2DAsync(kc->k + (size_t)l * kc->layer_stride, pitch, P.dec_k + (size_t)l * src_layer, rows_bytes, rows_bytes, c.dec_kv_heads, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpy2DAsync(kc->v + (size_t)l * kc->layer_stride, pitch, P.dec_v + (size_t)l * src_layer, rows_bytes, rows_bytes, c.dec_kv_heads, hipMemcpyDeviceToDevice, s));
+    }
     kc->len = P.PC; return VOX_OK;
 }
 // Does THIS call run on the prefix?  Only a clip that decodes at least one position behind the prefix tokens (then at least one live adapter row exists).
@@ -4111,6 +4119,7 @@ struct vox_stream {
     vox_cache* dec = nullptr;                                             // decoder cache (grows from ENGINE_MAX_ROWS rows by doubling, up to max_pos)
     float *samples = nullptr, *audio_keep = nullptr, *ws = nullptr;
     int *tokens = nullptr, *state = nullptr;
+    StreamMember* d_mem = nullptr; int* d_order = nullptr;      // the round of one: this stream's descriptor and the order {0} (one allocation)
     MelTables mel{};
     // input at the capture rate (sr != 16000): the plan, the stream's OWN block matrix (the context's is vox_resample's and goes when the rate pair changes), the input ring
     uint32_t sr = 16000; ResamplePlan rp; float *rs_matrix = nullptr, *in_ring = nullptr; int in_ring_n = 0;
@@ -4129,6 +4138,19 @@ struct vox_stream {
 static long stream_spp(int R) { return 640L * R; }      // samples per decoder position: R encoder rows x 4 frames x 160
 // decoder positions determined after n samples of an unfinished stream: position p's last frame 4 R p + 4 R - 1 reads padded samples up to 640 R (p + 1) + 40
 static long stream_positions(long left, int R, int64_t n) { const int64_t a = left + n - 40; return a < 0 ? 0 : (long)(a / stream_spp(R)); }
+
+// the buffers of a round of up to n sessions (n = 1: a solo stream's tick), carved from one allocation; returns its size in floats (base may be null).
+// A slot's mel halo is padded from 4 R + 3 to 4 R + 4 frames and its conv1 block from 2 R + 1 to 2 R + 2 rows, so that slots lie a whole number of window strides
+// apart and each conv is ONE im2col GEMM over all slots (stream_encode_round); h: the decode step's input rows.
+struct StreamWs { float *halo, *c1, *c2, *x, *xn, *qkv, *att, *ffn, *ah, *arow, *h; };
+static size_t stream_ws_carve(const vox_model* m, int n, float* base, StreamWs* w) {
+    const vox_model_cfg& c = m->cfg; const size_t R = (size_t)c.reshape_factor, D = (size_t)c.enc_dim, QD = (size_t)c.enc_heads * c.enc_head_dim, N = (size_t)n;
+    StreamWs t; if (!w) w = &t;
+    size_t o = 0; auto take = [&](float*& q, size_t k) { q = base ? base + o : nullptr; o += (k + 63) / 64 * 64; };      // (256-byte pieces)
+    take(w->halo, N * (4 * R + 4) * c.n_mels); take(w->c1, N * (2 * R + 2) * D); take(w->c2, N * (R + 1) * D); take(w->x, N * R * D); take(w->xn, N * R * D);
+    take(w->qkv, N * R * QD * 3); take(w->att, N * R * QD); take(w->ffn, N * R * c.enc_ffn); take(w->ah, N * m->ad0.w.N); take(w->arow, N * c.dec_dim); take(w->h, N * c.dec_dim);
+    return o;
+}
 
 // the 16 kHz samples final after n input samples at the plan's rate: output i reads block (i + delay) / fft_out in full and the tail of the block before, nothing else
 static int64_t stream_avail16(const ResamplePlan& p, int64_t n) { return std::max<int64_t>(0, n / p.fft_in * p.fft_out - p.delay); }
@@ -4181,31 +4203,37 @@ static int32_t stream_dec_grow(vox_stream* st) {
     return VOX_OK;
 }
 
-// the state after create / reset: the prefix state of the stream's t_embed (built here when the model does not hold it, whatever vox_model_set_prefix_cache says --
-// the model's own setting is restored) copied into the stream's ring, decoder cache and tokens; the stream does not look at the model's copy again
-static int32_t stream_load_initial(vox_stream* st) {
-    vox_model* m = st->m; const vox_model_cfg& c = m->cfg; hipStream_t s = st->ctx->stream; PrefixState& P = m->pfx;
+// the state after create / reset of a session (a solo stream, a group's member): the prefix state of its t_embed (built here when the model does not hold it, whatever
+// vox_model_set_prefix_cache says -- the model's own setting is restored) copied into the session's ring, its decoder cache rows (`dec`: a cache, or a view of a slab's
+// slice), its tokens and its state block; the session does not look at the model's copy again.  `then`: what the caller enqueues behind the copies; ONE synchronisation.
+template <class Then>
+static int32_t stream_seed(vox_model* m, const float* t_embed, int RC, int PC, int cap, float* kring, float* vring, vox_cache* dec, int* tokens, int* state, int* h_state, Then then) {
+    const vox_model_cfg& c = m->cfg; hipStream_t s = m->ctx->stream; PrefixState& P = m->pfx;
     const bool was_on = P.on; P.on = true;
-    int32_t r = prefix_build(m, st->t_embed.data());
-    if (r == VOX_OK && !(P.enc_built && P.dec_built && P.RC == st->RC && P.PC == st->PC)) r = fail(VOX_ERR_HIP, "the prefix state a stream starts from could not be built");
+    int32_t r = prefix_build(m, t_embed);
+    if (r == VOX_OK && !(P.enc_built && P.dec_built && P.RC == RC && P.PC == PC)) r = fail(VOX_ERR_HIP, "the prefix state a stream starts from could not be built");
     auto body = [&]() -> int32_t {
-        VOXCHK(stream_dec_alloc(st, std::min(st->max_pos, ENGINE_MAX_ROWS)));
-        const int H = c.enc_heads, hd = c.enc_head_dim, PC = st->PC, RC = st->RC;      // (== P.PC, P.RC: checked above)
-        HIPCHK(launch_stream_ring_init(P.enc_kv, c.enc_layers, RC, H, hd, st->cap, st->kring, st->vring, s));
-        VOXCHK(prefix_rows_into(m, st->dec, s));
-        // the engine's view of THIS cache, in the stream's own binding: no table is rebuilt (and nothing synchronised) when streams, piecewise and offline callers alternate;
-        // uploaded here, behind this function's synchronisation, so that the first step finds its cache bound
-        HIPCHK(engine_tab_enqueue(m, st->eng, st->dec));
-        HIPCHK(prefix_tokens_enqueue(st->tokens, s));
-        std::memset(st->h_state, 0, sizeof st->h_state);
-        st->h_state[STRM_POS] = PC; st->h_state[STRM_ENC_POS] = RC; st->h_state[STRM_FRAME] = 4 * RC; st->h_state[STRM_HEAD] = RC % st->cap;
-        HIPCHK(hipMemcpyAsync(st->state, st->h_state, sizeof st->h_state, hipMemcpyHostToDevice, s));
+        HIPCHK(launch_stream_ring_init(P.enc_kv, c.enc_layers, RC, c.enc_heads, c.enc_head_dim, cap, kring, vring, s));
+        VOXCHK(prefix_rows_into(m, dec, s));
+        VOXCHK(then());
+        HIPCHK(prefix_tokens_enqueue(tokens, s));
+        std::memset(h_state, 0, sizeof(int) * STRM_WORDS);
+        h_state[STRM_POS] = PC; h_state[STRM_ENC_POS] = RC; h_state[STRM_FRAME] = 4 * RC; h_state[STRM_HEAD] = RC % cap;
+        HIPCHK(hipMemcpyAsync(state, h_state, sizeof(int) * STRM_WORDS, hipMemcpyHostToDevice, s));
         HIPCHK(hipStreamSynchronize(s));
         return VOX_OK;
     };
     if (r == VOX_OK) r = body();
     if (!was_on) { (void)hipStreamSynchronize(s); prefix_release(m); P.on = false; }
-    if (r != VOX_OK) return r;
+    return r;
+}
+static int32_t stream_load_initial(vox_stream* st) {
+    vox_model* m = st->m;
+    VOXCHK(stream_dec_alloc(st, std::min(st->max_pos, ENGINE_MAX_ROWS)));
+    // the engine's view of THIS cache, in the stream's own binding: no table is rebuilt (and nothing synchronised) when streams, piecewise and offline callers alternate;
+    // uploaded behind the seed's copies and in front of its synchronisation, so that the first step finds its cache bound
+    VOXCHK(stream_seed(m, st->t_embed.data(), st->RC, st->PC, st->cap, st->kring, st->vring, st->dec, st->tokens, st->state, st->h_state,
+                       [&]() -> int32_t { HIPCHK(engine_tab_enqueue(m, st->eng, st->dec)); return VOX_OK; }));
     st->n_pushed = st->n_written = st->in_written = 0; st->pos = st->verified_pos = st->PC; st->ids_out = 0; st->finished = false; st->eng_unverified = false;
     st->eng_steps = st->op_steps = st->verified_eng_steps = st->verified_op_steps = 0; st->tap_rows = st->verified_tap_rows = 0; st->ftap_ticks = 0;
     return VOX_OK;
@@ -4216,11 +4244,29 @@ static void stream_release(vox_stream* st) {
     (void)hipSetDevice(st->ctx->device); (void)hipStreamSynchronize(st->ctx->stream);      // never dereferences st->m: a stream may not outlive its model, but freeing it late must not crash
     cache_release(st->dec);
     for (void* p : {(void*)st->kring, (void*)st->vring, (void*)st->samples, (void*)st->audio_keep, (void*)st->ws, (void*)st->tokens, (void*)st->state, (void*)st->tap, (void*)st->ftap_mel, (void*)st->ftap_conv,
-                    (void*)st->rs_matrix, (void*)st->in_ring, (void*)st->s16_stage}) if (p) (void)hipFree(p);
+                    (void*)st->rs_matrix, (void*)st->in_ring, (void*)st->s16_stage, (void*)st->d_mem}) if (p) (void)hipFree(p);
     binding_release(st->eng);
     delete st;
 }
 
+// what create checks about the model and the two sizes, for a solo stream and for a group: the prefix bounds, the ring capacity, the position limit
+struct StreamGeom { int RC = 0, PC = 0, cap = 0, max_pos = 0; long left = 0; };
+static int32_t stream_geometry(vox_model* m, int32_t enc_capacity_rows, int32_t max_positions, int default_positions, StreamGeom* g) {
+    const vox_model_cfg& c = m->cfg;
+    if (!m->is_q4) return fail(VOX_ERR_UNSUPPORTED, "live streaming sessions serve Q4 (GGUF) models");
+    int RC, PC; prefix_bounds(m, &RC, &PC);
+    ARGCHK(RC > 0 && c.reshape_factor == 4 && PC == VOX_PREFIX_TOKENS - 1, "this model geometry has no prefix state for a stream to start from");
+    if (!m->conv1_g.qs || !m->conv2_g.qs) return fail(VOX_ERR_UNSUPPORTED, "the stream's conv stem runs as im2col GEMMs: 3 n_mels and 3 enc_dim must be multiples of 128");
+    ARGCHK(c.enc_window + 1 <= 1024, "encoder window %d exceeds the stream attention's 1023 keys", c.enc_window);
+    int cap = enc_capacity_rows; if (cap == 0) cap = (std::max(c.enc_window + 8, RC) + 63) / 64 * 64;      // a ring needs no slack: anything above window + 4 is exact
+    ARGCHK(cap > c.enc_window + 4 && cap >= RC, "encoder ring capacity %d must exceed the sliding window + 4 (%d)", cap, c.enc_window + 4);
+    const int pos_limit = std::min(m->dec_rope_len, (1 << 16) / c.reshape_factor);      // the decoder RoPE table and the 65 536-position streaming encoder table end together
+    int maxp = max_positions; if (maxp == 0) maxp = std::min(pos_limit, default_positions);
+    ARGCHK(maxp > VOX_PREFIX_TOKENS && maxp <= pos_limit, "max_positions %d out of range (%d..%d)", maxp, VOX_PREFIX_TOKENS + 1, pos_limit);
+    g->RC = RC; g->PC = PC; g->cap = cap; g->max_pos = maxp;
+    { vox_pad_cfg pc; vox_pad_cfg_voxtral(&pc); g->left = (long)pad_left(&pc); }
+    return VOX_OK;
+}
 // sample_rate 16000: the 16 kHz stream, nothing more; any other rate: + the input ring and the stream's own block matrix
 static int32_t stream_create(vox_model* m, const float* t_embed, float gain, int32_t enc_capacity_rows, int32_t max_positions, uint32_t sample_rate, vox_stream** out) {
     ARGCHK(m && t_embed && out, "null argument"); ARGCHK(std::isfinite(gain), "gain is not finite"); ARGCHK(sample_rate > 0, "bad sample rate 0");
@@ -4234,37 +4280,30 @@ static int32_t stream_create(vox_model* m, const float* t_embed, float gain, int
         for (in_ring_n = 1; in_ring_n < 2 * rp.fft_in + STREAM_FEED_CHUNK;) in_ring_n <<= 1;
     }
     const vox_model_cfg& c = m->cfg; vox_ctx* cx = m->ctx;
-    if (!m->is_q4) return fail(VOX_ERR_UNSUPPORTED, "live streaming sessions serve Q4 (GGUF) models");
-    int RC, PC; prefix_bounds(m, &RC, &PC);
-    ARGCHK(RC > 0 && c.reshape_factor == 4 && PC == VOX_PREFIX_TOKENS - 1, "this model geometry has no prefix state for a stream to start from");
-    if (!m->conv1_g.qs || !m->conv2_g.qs) return fail(VOX_ERR_UNSUPPORTED, "the stream's conv stem runs as im2col GEMMs: 3 n_mels and 3 enc_dim must be multiples of 128");
-    ARGCHK(c.enc_window + 1 <= 1024, "encoder window %d exceeds the stream attention's 1023 keys", c.enc_window);
-    const int R = c.reshape_factor;
-    int cap = enc_capacity_rows; if (cap == 0) cap = (std::max(c.enc_window + 8, RC) + 63) / 64 * 64;      // a ring needs no slack: anything above window + 4 is exact
-    ARGCHK(cap > c.enc_window + 4 && cap >= RC, "encoder ring capacity %d must exceed the sliding window + 4 (%d)", cap, c.enc_window + 4);
-    const int pos_limit = std::min(m->dec_rope_len, (1 << 16) / R);      // the decoder RoPE table and the 65 536-position streaming encoder table end together
-    int maxp = max_positions; if (maxp == 0) maxp = pos_limit;
-    ARGCHK(maxp > VOX_PREFIX_TOKENS && maxp <= pos_limit, "max_positions %d out of range (%d..%d)", maxp, VOX_PREFIX_TOKENS + 1, pos_limit);
+    StreamGeom g; VOXCHK(stream_geometry(m, enc_capacity_rows, max_positions, INT32_MAX, &g));
     VOXCHK(enc_stream_rope_ensure(m));
-    vox_stream* st = new vox_stream(); st->m = m; st->ctx = cx; st->t_embed.assign(t_embed, t_embed + c.dec_dim); st->gain = gain; st->cap = cap; st->max_pos = maxp; st->RC = RC; st->PC = PC;
-    st->sr = sample_rate; st->rp = rp; st->in_ring_n = in_ring_n;
-    { vox_pad_cfg pc; vox_pad_cfg_voxtral(&pc); st->left = (long)pad_left(&pc); }
-    const int D = c.enc_dim, QD = c.enc_heads * c.enc_head_dim, F = c.enc_ffn, DD = c.dec_dim;
-    st->ring_layer = (size_t)c.enc_heads * cap * c.enc_head_dim;
-    const size_t ring_b = (size_t)c.enc_layers * st->ring_layer * 4, keep_b = (size_t)STREAM_KEEP_ROWS * DD * 4;
-    const size_t ws_f = (size_t)(4 * R + 3) * c.n_mels + (size_t)(2 * R + 1) * D + (size_t)2 * R * D + (size_t)R * QD * 4 + (size_t)R * F + m->ad0.w.N + (size_t)2 * DD + 256;
+    vox_stream* st = new vox_stream(); st->m = m; st->ctx = cx; st->t_embed.assign(t_embed, t_embed + c.dec_dim); st->gain = gain; st->cap = g.cap; st->max_pos = g.max_pos; st->RC = g.RC; st->PC = g.PC;
+    st->sr = sample_rate; st->rp = rp; st->in_ring_n = in_ring_n; st->left = g.left;
+    const int DD = c.dec_dim, maxp = g.max_pos;
+    st->ring_layer = (size_t)c.enc_heads * g.cap * c.enc_head_dim;
+    const size_t ring_b = (size_t)c.enc_layers * st->ring_layer * 4, keep_b = (size_t)STREAM_KEEP_ROWS * DD * 4, ws_b = stream_ws_carve(m, 1, nullptr, nullptr) * 4;
     hipError_t e = hipSuccess;
     auto A = [&](void** q, size_t n) { if (e == hipSuccess) { e = hipMalloc(q, n); if (e == hipSuccess) st->bytes += n; } };
     A((void**)&st->kring, ring_b); A((void**)&st->vring, ring_b); A((void**)&st->samples, (size_t)STREAM_SAMPLE_RING * 4); A((void**)&st->audio_keep, keep_b);
-    A((void**)&st->ws, ws_f * 4); A((void**)&st->tokens, (size_t)(maxp + 2) * 4); A((void**)&st->state, sizeof(int) * STRM_WORDS);
+    A((void**)&st->ws, ws_b); A((void**)&st->tokens, (size_t)(maxp + 2) * 4); A((void**)&st->state, sizeof(int) * STRM_WORDS); A((void**)&st->d_mem, sizeof(StreamMember) + 16);
     if (e == hipSuccess) e = binding_alloc(m, st->eng, &st->bytes);      // (here, not at the first step: the footprint a stream reports does not depend on what it has done)
     if (in_ring_n) A((void**)&st->in_ring, (size_t)in_ring_n * 4);
     if (e != hipSuccess) { (void)hipGetLastError(); stream_release(st); return fail(VOX_ERR_HIP, "allocating the stream's device state failed: %s", hipGetErrorString(e)); }
+    st->d_order = reinterpret_cast<int*>(st->d_mem + 1);
+    struct { StreamMember me; int order[4]; } desc{};      // the stream's descriptor never changes; uploaded behind stream_load_initial's synchronisation at the latest
+    desc.me.samples = st->samples; desc.me.gain = gain; desc.me.state = st->state; desc.me.kring = st->kring; desc.me.vring = st->vring; desc.me.tokens = st->tokens;
     int32_t r = ctx_mel_tables(cx, &st->mel);
     if (r == VOX_OK && hipMemsetAsync(st->samples, 0, (size_t)STREAM_SAMPLE_RING * 4, cx->stream) != hipSuccess) r = fail(VOX_ERR_HIP, "hipMemsetAsync failed");
+    if (r == VOX_OK && hipMemsetAsync(st->ws, 0, ws_b, cx->stream) != hipSuccess) r = fail(VOX_ERR_HIP, "hipMemsetAsync failed");      // (the pad frame and pad row are read, their products are not)
+    if (r == VOX_OK && hipMemcpyAsync(st->d_mem, &desc, sizeof(StreamMember) + 16, hipMemcpyHostToDevice, cx->stream) != hipSuccess) r = fail(VOX_ERR_HIP, "hipMemcpyAsync failed");
     if (r == VOX_OK && in_ring_n) { r = resample_matrix_build(cx, rp, rs_bytes, &st->rs_matrix); if (r == VOX_OK) st->bytes += rs_bytes; }
     if (r == VOX_OK) r = stream_load_initial(st);
-    if (r != VOX_OK) { stream_release(st); return r; }
+    if (r != VOX_OK) { (void)hipStreamSynchronize(cx->stream); stream_release(st); return r; }
     *out = st; return VOX_OK;
 }
 extern "C" int32_t vox_stream_create(vox_model* m, const float* t_embed, float gain, int32_t enc_capacity_rows, int32_t max_positions, vox_stream** out) {
@@ -4334,7 +4373,7 @@ static int32_t stream_settle(vox_stream* st, bool* reran) {      // behind that 
         st->pos = p0; st->dec->len = p0; st->tap_rows = st->verified_tap_rows; st->h_pos_word = p0;
         HIPCHK(hipMemcpyAsync(st->state + STRM_POS, &st->h_pos_word, 4, hipMemcpyHostToDevice, s));
         VOXCHK(wo_acc_clear(m, s));
-        float* h = st->ws;      // (the tick's buffers are free between ticks)
+        StreamWs w; stream_ws_carve(m, 1, st->ws, &w); float* h = w.h;      // (the tick's buffers are free between ticks)
         EngSuspend off(m);
         int32_t r = VOX_OK;
         for (int p = p0; p < p1 && r == VOX_OK; p++) {
@@ -4354,48 +4393,71 @@ static int32_t stream_verify(vox_stream* st) {      // inside a long push: befor
     return stream_settle(st, nullptr);
 }
 
-static int32_t stream_tick(vox_stream* st) {
-    vox_model* m = st->m; const vox_model_cfg& c = m->cfg; vox_ctx* cx = st->ctx; hipStream_t s = cx->stream;
-    const int D = c.enc_dim, H = c.enc_heads, hd = c.enc_head_dim, QD = H * hd, F = c.enc_ffn, R = c.reshape_factor, DD = c.dec_dim, Cm = c.n_mels;
-    const int NF = 4 * R + 3, N1 = 2 * R + 1;      // mel frames with the halo (conv row s reads frames 4 s - 3 .. 4 s + 3), conv1 rows with theirs (2 s - 1 .. 2 s + 1)
-    if (st->pos - st->verified_pos >= STREAM_KEEP_ROWS) VOXCHK(stream_verify(st));      // the kept adapter rows cover the unverified steps
-    if (st->pos >= st->dec->max_seq) { VOXCHK(stream_verify(st)); VOXCHK(stream_dec_grow(st)); }
-    float* halo = st->ws; float* c1 = halo + (size_t)NF * Cm; float* x = c1 + (size_t)N1 * D; float* xn = x + (size_t)R * D; float* qkv = xn + (size_t)R * D;
-    float* att = qkv + (size_t)R * QD * 3; float* ffn = att + (size_t)R * QD; float* ah = ffn + (size_t)R * F; float* arow = ah + m->ad0.w.N; float* h = arow + DD;
-    HIPCHK(launch_stream_mel(st->samples, STREAM_SAMPLE_RING - 1, st->left, st->gain, st->mel, st->state, 3, NF, halo, s));
-    // conv stem without padding rows, memsets or a transpose: conv1 row i of the tick is the window of halo rows [2 i, 2 i + 2], conv row i the window of conv1 rows [2 i, 2 i + 2]
-    { GemmParams g{}; g.w = m->conv1_g; g.x = halo; g.x_stride = 2 * Cm; g.M = N1; g.out = c1; g.out_stride = D; g.bias = m->conv1_b; HIPCHK(launch_dense2_gemm(g, EPI_GELU, s)); }
-    { GemmParams g{}; g.w = m->conv2_g; g.x = c1; g.x_stride = 2 * D; g.M = R; g.out = x; g.out_stride = D; g.bias = m->conv2_b; HIPCHK(launch_dense2_gemm(g, EPI_GELU, s)); }
-    if (st->ftap_mel) {      // the front tap (tests): the tick's fresh frames (halo rows 3 ..) and conv rows, copied on the stream; a re-run repeats decode steps, never a tick
-        const int k = st->ftap_ticks++;
-        if (k < st->ftap_max) {
-            HIPCHK(hipMemcpyAsync(st->ftap_mel + (size_t)k * 4 * R * Cm, halo + (size_t)3 * Cm, (size_t)4 * R * Cm * 4, hipMemcpyDeviceToDevice, s));
-            HIPCHK(hipMemcpyAsync(st->ftap_conv + (size_t)k * R * D, x, (size_t)R * D * 4, hipMemcpyDeviceToDevice, s));
-        }
+// The encoder half of a tick for a ROUND of r.n sessions (a solo stream: a round of one): mel -> conv stem -> enc_layers x { RMSNorm, q|k|v, ring attention, wo, RMSNorm,
+// w1|w3, w2 } -> final norm -> adapter, every weight matrix in ONE launch for all sessions of the round (4 n rows through q4_linear_dev, which picks the kernel by the row
+// count).  Slot z works for session r.order[z] (device arrays); w.arow[z] is its adapter row.  ftap_*: a solo stream's front tap (null: none).
+struct StreamRound { const StreamMember* mem; const int* order; int n, cap; size_t ring_layer; MelTables mel; long left; };
+static int32_t stream_encode_round(vox_model* m, const StreamWs& w, const StreamRound& r, float* ftap_mel, float* ftap_conv) {
+    const vox_model_cfg& c = m->cfg; vox_ctx* cx = m->ctx; hipStream_t s = cx->stream;
+    const int D = c.enc_dim, H = c.enc_heads, hd = c.enc_head_dim, QD = H * hd, F = c.enc_ffn, R = c.reshape_factor, DD = c.dec_dim, Cm = c.n_mels, n = r.n, M = R * n;
+    const int NF = 4 * R + 3, HS = NF + 1, C1S = 2 * R + 2, C2S = R + 1;      // mel frames with the halo (conv row s reads frames 4 s - 3 .. 4 s + 3); the slot strides in frames, conv1 rows, conv rows
+    HIPCHK(launch_stream_mel(r.mem, r.order, n, STREAM_SAMPLE_RING - 1, r.left, r.mel, 3, NF, w.halo, (long)HS * Cm, s));
+    // conv stem without padding rows, memsets or a transpose: conv1 row i of a slot is the window of its halo rows [2 i, 2 i + 2], conv row i the window of its conv1 rows
+    // [2 i, 2 i + 2].  The slots lie C1S / C2S windows apart, so one GEMM per conv serves them all; its last window of every slot but the last straddles two slots: that
+    // row is computed and never read.  The R valid rows per slot are then packed into the 4 n-row encoder input (one slot: they are packed as they are).
+    float* conv = n == 1 ? w.x : w.c2;
+    { GemmParams g{}; g.w = m->conv1_g; g.x = w.halo; g.x_stride = 2 * Cm; g.M = C1S * n - 1; g.out = w.c1; g.out_stride = D; g.bias = m->conv1_b; HIPCHK(launch_dense2_gemm(g, EPI_GELU, s)); }
+    { GemmParams g{}; g.w = m->conv2_g; g.x = w.c1; g.x_stride = 2 * D; g.M = C2S * n - 1; g.out = conv; g.out_stride = D; g.bias = m->conv2_b; HIPCHK(launch_dense2_gemm(g, EPI_GELU, s)); }
+    if (n > 1) HIPCHK(hipMemcpy2DAsync(w.x, (size_t)R * D * 4, w.c2, (size_t)C2S * D * 4, (size_t)R * D * 4, n, hipMemcpyDeviceToDevice, s));
+    if (ftap_mel) {      // the front tap (tests): the tick's fresh frames (halo rows 3 ..) and conv rows, copied on the stream
+        HIPCHK(hipMemcpyAsync(ftap_mel, w.halo + (size_t)3 * Cm, (size_t)4 * R * Cm * 4, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(ftap_conv, w.x, (size_t)R * D * 4, hipMemcpyDeviceToDevice, s));
     }
+    float *x = w.x, *xn = w.xn;
     for (int l = 0; l < c.enc_layers; l++) {
         const EncLayer& L = m->enc[l];
-        HIPCHK(launch_rms_norm(x, D, R, D, L.attn_norm, nullptr, c.norm_eps, xn, D, s));
-        VOXCHK(q4_linear_dev(cx, L.wqkv.w, L.wqkv.bias, xn, D, R, qkv, 3 * QD));
-        StreamAttnParams ap{}; ap.qkv = qkv; ap.qkv_stride = 3 * QD; ap.kring = st->kring + (size_t)l * st->ring_layer; ap.vring = st->vring + (size_t)l * st->ring_layer; ap.cap = st->cap;
-        ap.cos_t = m->enc_cos_s; ap.sin_t = m->enc_sin_s; ap.state = st->state; ap.out = att; ap.out_stride = QD; ap.M = R; ap.n_heads = H; ap.window = c.enc_window;
+        HIPCHK(launch_rms_norm(x, D, M, D, L.attn_norm, nullptr, c.norm_eps, xn, D, s));
+        VOXCHK(q4_linear_dev(cx, L.wqkv.w, L.wqkv.bias, xn, D, M, w.qkv, 3 * QD));
+        StreamAttnParams ap{}; ap.qkv = w.qkv; ap.qkv_stride = 3 * QD; ap.mem = r.mem; ap.order = r.order; ap.n = n; ap.ring_off = (size_t)l * r.ring_layer; ap.cap = r.cap;
+        ap.cos_t = m->enc_cos_s; ap.sin_t = m->enc_sin_s; ap.out = w.att; ap.out_stride = QD; ap.M = R; ap.n_heads = H; ap.window = c.enc_window;
         HIPCHK(launch_stream_attn(ap, hd, s));
-        VOXCHK(q4_linear_dev(cx, L.wo.w, L.wo.bias, att, QD, R, x, D, EPI_RESID, x, D));
-        HIPCHK(launch_rms_norm(x, D, R, D, L.ffn_norm, nullptr, c.norm_eps, xn, D, s));
-        VOXCHK(q4_linear_dev(cx, L.w13.w, nullptr, xn, D, R, ffn, F, EPI_SWIGLU));
-        VOXCHK(q4_linear_dev(cx, L.w2.w, L.w2.bias, ffn, F, R, x, D, EPI_RESID, x, D));
+        VOXCHK(q4_linear_dev(cx, L.wo.w, L.wo.bias, w.att, QD, M, x, D, EPI_RESID, x, D));
+        HIPCHK(launch_rms_norm(x, D, M, D, L.ffn_norm, nullptr, c.norm_eps, xn, D, s));
+        VOXCHK(q4_linear_dev(cx, L.w13.w, nullptr, xn, D, M, w.ffn, F, EPI_SWIGLU));
+        VOXCHK(q4_linear_dev(cx, L.w2.w, L.w2.bias, w.ffn, F, M, x, D, EPI_RESID, x, D));
     }
-    HIPCHK(launch_rms_norm(x, D, R, D, m->enc_norm, nullptr, c.norm_eps, xn, D, s));
-    VOXCHK(q4_linear_dev(cx, m->ad0.w, nullptr, xn, D * R, 1, ah, m->ad0.w.N, EPI_GELU));      // the R rows viewed as one [R D] row (models/adapter.rs:108-122)
-    VOXCHK(q4_linear_dev(cx, m->ad2.w, nullptr, ah, m->ad0.w.N, 1, arow, DD));
-    HIPCHK(launch_stream_embed(m->tok.w, st->tokens, arow, st->audio_keep, STREAM_KEEP_ROWS, DD, st->state, h, s));
-    return stream_decode_step(st, h, stream_tap_row(st), R);
+    HIPCHK(launch_rms_norm(x, D, M, D, m->enc_norm, nullptr, c.norm_eps, xn, D, s));
+    VOXCHK(q4_linear_dev(cx, m->ad0.w, nullptr, xn, D * R, n, w.ah, m->ad0.w.N, EPI_GELU));      // a slot's R rows viewed as one [R D] row (models/adapter.rs:108-122)
+    VOXCHK(q4_linear_dev(cx, m->ad2.w, nullptr, w.ah, m->ad0.w.N, n, w.arow, DD));
+    return VOX_OK;
+}
+
+// a solo stream's tick: the round of one, then its own decode half -- the engine launch or the per-operator step, with the kept adapter rows behind the re-run
+static int32_t stream_tick(vox_stream* st) {
+    vox_model* m = st->m; const vox_model_cfg& c = m->cfg; hipStream_t s = st->ctx->stream; const int R = c.reshape_factor;
+    if (st->pos - st->verified_pos >= STREAM_KEEP_ROWS) VOXCHK(stream_verify(st));      // the kept adapter rows cover the unverified steps
+    if (st->pos >= st->dec->max_seq) { VOXCHK(stream_verify(st)); VOXCHK(stream_dec_grow(st)); }
+    StreamWs w; stream_ws_carve(m, 1, st->ws, &w);
+    const StreamRound r{st->d_mem, st->d_order, 1, st->cap, st->ring_layer, st->mel, st->left};
+    const int k = st->ftap_mel ? st->ftap_ticks++ : 0; const bool ftap = st->ftap_mel && k < st->ftap_max;      // (a re-run repeats decode steps, never a tick)
+    VOXCHK(stream_encode_round(m, w, r, ftap ? st->ftap_mel + (size_t)k * 4 * R * c.n_mels : nullptr, ftap ? st->ftap_conv + (size_t)k * R * c.enc_dim : nullptr));
+    HIPCHK(launch_stream_embed(m->tok.w, st->tokens, w.arow, st->audio_keep, STREAM_KEEP_ROWS, c.dec_dim, st->state, w.h, s));
+    return stream_decode_step(st, w.h, stream_tap_row(st), R);
 }
 
 // what a call appends: f32 or 16-bit samples in host or device memory; p null: zeros (the right pad)
 struct StreamSrc { const void* p = nullptr; bool s16 = false; int32_t mem_kind = VOX_MEM_DEVICE; };
 // samples [at, at + len) of the source into ring[(w0 + k) & (ring_n - 1)], k < len <= ring_n: f32 and zeros as at most two copies (the ring wraps), 16-bit samples through
 // stream_s16_kernel (which wraps by itself), host ones in pieces of the staging buffer
+static int32_t ring_write_f32(hipStream_t s, float* ring, int ring_n, int64_t w0, const StreamSrc& src, size_t at, size_t len) {      // f32 samples or zeros
+    for (size_t w = 0; w < len;) {      // at most two pieces: the ring wraps
+        const size_t off = (size_t)((w0 + (int64_t)w) & (ring_n - 1)), k = std::min(len - w, (size_t)ring_n - off);
+        if (!src.p) HIPCHK(hipMemsetAsync(ring + off, 0, k * 4, s));
+        else HIPCHK(hipMemcpyAsync(ring + off, (const float*)src.p + at + w, k * 4, src.mem_kind == VOX_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+        w += k;
+    }
+    return VOX_OK;
+}
 static int32_t stream_ring_write(vox_stream* st, float* ring, int ring_n, int64_t w0, const StreamSrc& src, size_t at, size_t len) {
     hipStream_t s = st->ctx->stream;
     if (src.p && src.s16) {
@@ -4410,20 +4472,14 @@ static int32_t stream_ring_write(vox_stream* st, float* ring, int ring_n, int64_
         }
         return VOX_OK;
     }
-    for (size_t w = 0; w < len;) {      // at most two pieces: the ring wraps
-        const size_t off = (size_t)((w0 + (int64_t)w) & (ring_n - 1)), k = std::min(len - w, (size_t)ring_n - off);
-        if (!src.p) HIPCHK(hipMemsetAsync(ring + off, 0, k * 4, s));
-        else HIPCHK(hipMemcpyAsync(ring + off, (const float*)src.p + at + w, k * 4, src.mem_kind == VOX_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-        w += k;
-    }
-    return VOX_OK;
+    return ring_write_f32(s, ring, ring_n, w0, src, at, len);
 }
-// 16 kHz samples the ring can take: everything from the oldest sample the next tick reads stays
-static size_t stream_room16(const vox_stream* st) {
-    const int R = st->m->cfg.reshape_factor;
-    const long lo = std::max(0L, (4L * R * st->pos - 3) * 160 - 200 - st->left);
-    return (size_t)STREAM_SAMPLE_RING - (size_t)(st->n_written - lo);
+// 16 kHz samples a session's ring can take: everything from the oldest sample its next tick (at position pos) reads stays
+static size_t ring_room16(int R, long left, int pos, int64_t n_written) {
+    const long lo = std::max(0L, (4L * R * pos - 3) * 160 - 200 - left);
+    return (size_t)STREAM_SAMPLE_RING - (size_t)(n_written - lo);
 }
+static size_t stream_room16(const vox_stream* st) { return ring_room16(st->m->cfg.reshape_factor, st->left, st->pos, st->n_written); }
 // append `n` 16 kHz samples and run every tick up to position `target` as soon as its samples are in the ring
 static int32_t stream_feed(vox_stream* st, const StreamSrc& src, size_t n, int target) {
     const int R = st->m->cfg.reshape_factor;
@@ -4564,6 +4620,217 @@ extern "C" int32_t vox_debug_stream_front_tap_fetch(vox_stream* st, float* out_m
     *ticks = st->ftap_ticks;
     stream_front_tap_drop(st);
     return VOX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Stream group (vox_stream_group; DESIGN.md section 8, "Stream groups"): N <= 16 member sessions on one model and one t_embed, advanced together.  A call knows every
+// fed member's due tick count d_i before it launches anything: the members sorted by d_i descending, round r runs ONE tick of the first n_r = #{d_i > r} of them --
+// stream_encode_round at 4 n_r rows (the code of a solo stream's tick) and, as the decode half, xf_chain at n_r rows on the group's decoder slab.  One upload (the
+// order) per pass, constant launch arguments within a pass except n_r, one synchronisation per call.  No engine runs here: no kept rows, no re-run, no verification.
+// ------------------------------------------------------------------------------------------------
+static const int GROUP_MAX = 16, GROUP_DEFAULT_POSITIONS = 2048;
+struct GroupMember {
+    int64_t n_pushed = 0, n_written = 0; int pos = 0, ids_out = 0; bool finished = false; uint64_t steps = 0;
+    int h_state[STRM_WORDS];
+};
+struct vox_stream_group {
+    vox_model* m = nullptr; vox_ctx* ctx = nullptr;
+    std::vector<float> t_embed; int n = 0; StreamGeom g;
+    float *kring = nullptr, *vring = nullptr; size_t ring_layer = 0, ring_member = 0;      // encoder K / V rings: [member][enc_layers][enc_heads][cap][hd]
+    float *dec_k = nullptr, *dec_v = nullptr; size_t seq_stride = 0, layer_stride = 0;      // decoder slab: [dec_layers][member][kv_heads][max_pos][hd], the layout xf_chain reads
+    float *samples = nullptr, *ws = nullptr; int *tokens = nullptr, *state = nullptr;       // [member][STREAM_SAMPLE_RING], the round's buffers, [member][max_pos + 2], [member][STRM_WORDS]
+    StreamMember* d_mem = nullptr; int *d_order = nullptr, *d_pos = nullptr, *d_kv_row = nullptr;      // descriptors [n]; the pass's order, the step's positions and cache slices [16] (one allocation)
+    float *qkv = nullptr, *att = nullptr, *logits = nullptr, *ssq = nullptr; uint16_t *xf1 = nullptr, *xf2 = nullptr, *xf3 = nullptr;      // the decode step's rows and XF planes (one 16-row group)
+    MelTables mel{}; uint64_t bytes = 0;
+    std::vector<StreamMember> h_mem; std::vector<GroupMember> mem;
+    std::deque<std::array<int, GROUP_MAX>> orders;      // the orders uploaded by the call in flight (alive until its synchronisation)
+};
+static int32_t group_upload_members(vox_stream_group* g) {      // after a descriptor changed (gain, tap); synchronises
+    HIPCHK(hipMemcpyAsync(g->d_mem, g->h_mem.data(), sizeof(StreamMember) * g->n, hipMemcpyHostToDevice, g->ctx->stream));
+    HIPCHK(hipStreamSynchronize(g->ctx->stream));
+    return VOX_OK;
+}
+static int32_t group_member_seed(vox_stream_group* g, int i) {
+    vox_cache view; view.m = g->m; view.ctx = g->ctx; view.k = g->dec_k + (size_t)i * g->seq_stride; view.v = g->dec_v + (size_t)i * g->seq_stride; view.max_seq = g->g.max_pos;
+    view.layer_stride = g->layer_stride;      // the member's slice of the slab, seen as a cache whose layers lie layer_stride apart
+    GroupMember& me = g->mem[i];
+    VOXCHK(stream_seed(g->m, g->t_embed.data(), g->g.RC, g->g.PC, g->g.cap, g->h_mem[i].kring, g->h_mem[i].vring, &view, g->h_mem[i].tokens, g->h_mem[i].state, me.h_state,
+                       []() -> int32_t { return VOX_OK; }));
+    me.n_pushed = me.n_written = 0; me.pos = g->g.PC; me.ids_out = 0; me.finished = false; me.steps = 0;
+    return VOX_OK;
+}
+static void group_release(vox_stream_group* g) {
+    if (!g) return;
+    (void)hipSetDevice(g->ctx->device); (void)hipStreamSynchronize(g->ctx->stream);      // never dereferences g->m (as stream_release)
+    for (StreamMember& me : g->h_mem) if (me.tap) (void)hipFree(me.tap);
+    for (void* p : {(void*)g->kring, (void*)g->vring, (void*)g->dec_k, (void*)g->dec_v, (void*)g->samples, (void*)g->ws, (void*)g->tokens, (void*)g->state, (void*)g->d_mem, (void*)g->d_order,
+                    (void*)g->qkv, (void*)g->att, (void*)g->logits, (void*)g->ssq, (void*)g->xf1, (void*)g->xf2, (void*)g->xf3}) if (p) (void)hipFree(p);
+    delete g;
+}
+extern "C" int32_t vox_stream_group_create(vox_model* m, const float* t_embed, int32_t n_members, const float* gains, int32_t enc_capacity_rows, int32_t max_positions,
+                                           vox_stream_group** out) {
+    ARGCHK(n_members >= 1 && n_members <= GROUP_MAX, "n_members %d out of range (1..%d)", n_members, GROUP_MAX); ARGCHK(m && t_embed && out, "null argument");
+    for (int i = 0; gains && i < n_members; i++) ARGCHK(std::isfinite(gains[i]), "gain of member %d is not finite", i);
+    VOXCHK(ctx_bind(m->ctx));
+    const vox_model_cfg& c = m->cfg; vox_ctx* cx = m->ctx; hipStream_t s = cx->stream;
+    StreamGeom sg; VOXCHK(stream_geometry(m, enc_capacity_rows, max_positions, GROUP_DEFAULT_POSITIONS, &sg));
+    if (!batch_xf_ok(m)) return fail(VOX_ERR_UNSUPPORTED, "a stream group's decode step runs on the tile-ordered Q4 weights, which this model does not have");
+    VOXCHK(enc_stream_rope_ensure(m));
+    vox_stream_group* g = new vox_stream_group(); g->m = m; g->ctx = cx; g->t_embed.assign(t_embed, t_embed + c.dec_dim); g->n = n_members; g->g = sg;
+    const size_t N = (size_t)n_members; const int D = c.dec_dim, QD = c.dec_heads * c.dec_head_dim, W = QD + 2 * c.dec_kv_heads * c.dec_head_dim, maxp = sg.max_pos;
+    g->ring_layer = (size_t)c.enc_heads * sg.cap * c.enc_head_dim; g->ring_member = (size_t)c.enc_layers * g->ring_layer;
+    g->seq_stride = (size_t)c.dec_kv_heads * maxp * c.dec_head_dim; g->layer_stride = N * g->seq_stride;
+    const size_t ws_b = stream_ws_carve(m, n_members, nullptr, nullptr) * 4, slab_b = (size_t)c.dec_layers * g->layer_stride * 4;
+    hipError_t e = hipSuccess;
+    auto A = [&](void** q, size_t nb, bool zero) { if (e == hipSuccess) { e = hipMalloc(q, nb); if (e == hipSuccess) { g->bytes += nb; if (zero) e = hipMemsetAsync(*q, 0, nb, s); } } };
+    A((void**)&g->kring, N * g->ring_member * 4, false); A((void**)&g->vring, N * g->ring_member * 4, false); A((void**)&g->dec_k, slab_b, true); A((void**)&g->dec_v, slab_b, true);
+    A((void**)&g->samples, N * STREAM_SAMPLE_RING * 4, true); A((void**)&g->ws, ws_b, true); A((void**)&g->tokens, N * (maxp + 2) * 4, true); A((void**)&g->state, N * sizeof(int) * STRM_WORDS, true);
+    A((void**)&g->d_mem, N * sizeof(StreamMember), true); A((void**)&g->d_order, 3 * GROUP_MAX * 4, true);
+    A((void**)&g->qkv, (size_t)GROUP_MAX * W * 4, true); A((void**)&g->att, (size_t)GROUP_MAX * QD * 4, true); A((void**)&g->logits, (size_t)GROUP_MAX * c.vocab * 4, true);
+    A((void**)&g->ssq, (size_t)q4_skinny_resid_xf_parts(D) * 16 * 4, true); A((void**)&g->xf1, xf_bytes(D), true); A((void**)&g->xf2, xf_bytes(QD), true); A((void**)&g->xf3, xf_bytes(c.dec_ffn), true);
+    if (e != hipSuccess) { (void)hipGetLastError(); group_release(g); return fail(VOX_ERR_HIP, "allocating the stream group's device state failed: %s", hipGetErrorString(e)); }
+    g->d_pos = g->d_order + GROUP_MAX; g->d_kv_row = g->d_pos + GROUP_MAX;
+    g->h_mem.resize(N); g->mem.resize(N);
+    for (size_t i = 0; i < N; i++) {
+        StreamMember& me = g->h_mem[i]; me = StreamMember{};
+        me.samples = g->samples + i * STREAM_SAMPLE_RING; me.gain = gains ? gains[i] : 1.0f; me.state = g->state + i * STRM_WORDS;
+        me.kring = g->kring + i * g->ring_member; me.vring = g->vring + i * g->ring_member; me.tokens = g->tokens + i * (size_t)(maxp + 2);
+    }
+    int32_t r = ctx_mel_tables(cx, &g->mel);
+    if (r == VOX_OK) r = group_upload_members(g);
+    for (int i = 0; i < n_members && r == VOX_OK; i++) r = group_member_seed(g, i);
+    if (r != VOX_OK) { group_release(g); return r; }
+    *out = g; return VOX_OK;
+}
+extern "C" int32_t vox_stream_group_free(vox_stream_group* g) { group_release(g); return VOX_OK; }
+extern "C" int32_t vox_stream_group_reset(vox_stream_group* g, int32_t member, float gain) {
+    ARGCHK(g, "null group"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1); ARGCHK(std::isfinite(gain), "gain is not finite");
+    VOXCHK(ctx_bind(g->ctx));
+    HIPCHK(hipStreamSynchronize(g->ctx->stream));
+    g->h_mem[member].gain = gain;
+    VOXCHK(group_upload_members(g));
+    return group_member_seed(g, member);      // (the state block restarts the tap's row count as well)
+}
+extern "C" int32_t vox_stream_group_info(const vox_stream_group* g, int32_t member, int64_t out[8]) {
+    ARGCHK(g && out, "null argument"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1);
+    const GroupMember& me = g->mem[member]; const int R = g->m->cfg.reshape_factor;
+    const uint64_t tap_b = g->h_mem[member].tap ? (uint64_t)g->h_mem[member].tap_max * g->m->cfg.vocab * 4 : 0;
+    out[0] = me.n_pushed; out[1] = me.pos; out[2] = me.ids_out; out[3] = (int64_t)R * me.pos; out[4] = std::min<int64_t>((int64_t)R * me.pos, g->g.cap);
+    out[5] = (int64_t)(g->bytes / (uint64_t)g->n + tap_b);      // the member's share of the group's device state
+    out[6] = 0; out[7] = (int64_t)me.steps;                      // no engine step; the member's ticks, each one row of an xf_chain step
+    return VOX_OK;
+}
+
+// what one entry of a call feeds: the samples, then `right` zeros (the right pad of a finishing member); `done` of the n + right written so far
+struct GroupFeed { int member; const float* p; size_t n, right, done; int target, due; };
+// one round: a tick of the first n_r members of the pass's order
+static int32_t group_round(vox_stream_group* g, const StreamWs& w, int n_r) {
+    vox_model* m = g->m; const vox_model_cfg& c = m->cfg; hipStream_t s = g->ctx->stream; const int R = c.reshape_factor;
+    const StreamRound r{g->d_mem, g->d_order, n_r, g->g.cap, g->ring_layer, g->mel, g->g.left};
+    VOXCHK(stream_encode_round(m, w, r, nullptr, nullptr));
+    XfBufs xb{}; xb.h = w.h; xb.qkv = g->qkv; xb.att = g->att; xb.logits = g->logits; xb.ssq = g->ssq; xb.xf1 = g->xf1; xb.xf2 = g->xf2; xb.xf3 = g->xf3;
+    xb.k = g->dec_k; xb.v = g->dec_v; xb.layer_stride = g->layer_stride; xb.seq_stride = g->seq_stride; xb.max_seq = g->g.max_pos; xb.pos = g->d_pos; xb.kv_row = g->d_kv_row;
+    HIPCHK(launch_stream_group_embed(m->tok.w, g->d_mem, g->d_order, n_r, w.arow, c.dec_dim, w.h, g->xf1, m->dec[0].attn_norm, g->ssq, g->d_pos, g->d_kv_row, s));
+    VOXCHK(xf_chain(m, xb, 0, n_r, 0, 0, true, 0, s));
+    HIPCHK(launch_stream_group_advance(g->logits, c.vocab, g->d_mem, g->d_order, n_r, R, 4 * R, g->g.cap, s));
+    return VOX_OK;
+}
+extern "C" int32_t vox_stream_group_advance(vox_stream_group* g, vox_stream_feed* feeds, int32_t n_feeds, int32_t mem_kind) {
+    ARGCHK(g && (feeds || n_feeds == 0), "null argument"); ARGCHK(n_feeds >= 0 && n_feeds <= g->n, "%d entries for a group of %d members", n_feeds, g->n);
+    ARGCHK(mem_kind == VOX_MEM_HOST || mem_kind == VOX_MEM_DEVICE, "bad mem_kind %d", mem_kind);
+    vox_model* m = g->m; const int R = m->cfg.reshape_factor; const long left = g->g.left; hipStream_t s = g->ctx->stream;
+    // every check before anything changes: a refused call can be repeated
+    std::vector<GroupFeed> fs; fs.reserve((size_t)n_feeds); unsigned seen = 0;
+    for (int k = 0; k < n_feeds; k++) {
+        const vox_stream_feed& f = feeds[k];
+        ARGCHK(f.member >= 0 && f.member < g->n, "entry %d: member %d out of range (0..%d)", k, f.member, g->n - 1);
+        ARGCHK(!((seen >> f.member) & 1u), "entry %d: member %d is fed twice in one call", k, f.member); seen |= 1u << f.member;
+        ARGCHK(f.samples || f.n_samples == 0, "entry %d: null samples", k); ARGCHK(f.n_samples <= ((size_t)1 << 36), "entry %d: push of %zu samples", k, f.n_samples);
+        ARGCHK(f.cap >= 0 && (f.out_ids || f.cap == 0), "entry %d: bad output buffer", k); ARGCHK(f.finish == 0 || f.finish == 1, "entry %d: finish must be 0 or 1", k);
+        const GroupMember& me = g->mem[f.member];
+        ARGCHK(!me.finished, "entry %d: member %d is finished: vox_stream_group_reset starts its next utterance", k, f.member);
+        GroupFeed gf{f.member, f.samples, f.n_samples, 0, 0, 0, 0};
+        const size_t n16 = (size_t)me.n_pushed + f.n_samples;
+        if (f.finish) {
+            vox_pad_cfg pc; vox_pad_cfg_voxtral(&pc); size_t total; VOXCHK(vox_pad_len(n16, &pc, &total));
+            const int S = (int)(total / (size_t)stream_spp(R));
+            ARGCHK(S - 1 <= g->g.max_pos, "entry %d: finishing would reach decoder position %d of a group created for %d", k, S - 1, g->g.max_pos);
+            gf.target = std::max(S - 1, me.pos); gf.right = total - (size_t)left - n16;
+        } else {
+            const long P = stream_positions(left, R, (int64_t)n16);
+            ARGCHK(P <= g->g.max_pos, "entry %d: the push would reach decoder position %ld of a group created for %d (vox_stream_group_reset starts over)", k, P, g->g.max_pos);
+            gf.target = std::max((int)P, me.pos);
+        }
+        gf.due = gf.target - me.pos;
+        ARGCHK(f.cap >= gf.due, "entry %d: out_ids capacity %d < %d ids due", k, f.cap, gf.due);
+        fs.push_back(gf);
+    }
+    VOXCHK(ctx_bind(g->ctx));
+    if (m->pw_pend_rows > 0) VOXCHK(pw_sync(m));
+    VOXCHK(vox_model_set_t_embed(m, g->t_embed.data()));
+    StreamWs w; stream_ws_carve(m, g->n, g->ws, &w);
+    for (GroupFeed& f : fs) g->mem[f.member].n_pushed += (int64_t)f.n;
+    // passes: write what fits into every fed member's sample ring, run the rounds that became due, repeat (a push may be larger than the ring)
+    for (;;) {
+        bool open = false; for (const GroupFeed& f : fs) open |= f.done < f.n + f.right || g->mem[f.member].pos < f.target;
+        if (!open) break;
+        std::vector<std::pair<int, int>> due;      // (ticks due in this pass, member)
+        bool wrote = false;
+        for (GroupFeed& f : fs) {
+            GroupMember& me = g->mem[f.member]; float* ring = g->samples + (size_t)f.member * STREAM_SAMPLE_RING;
+            size_t room = ring_room16(R, left, me.pos, me.n_written);
+            if (f.done < f.n) {
+                const size_t k = std::min(f.n - f.done, room); StreamSrc src; src.p = f.p; src.mem_kind = mem_kind;
+                VOXCHK(ring_write_f32(s, ring, STREAM_SAMPLE_RING, me.n_written, src, f.done, k)); me.n_written += (int64_t)k; f.done += k; room -= k; wrote |= k > 0;
+            }
+            if (f.done >= f.n && f.done < f.n + f.right) {
+                const size_t k = std::min(f.n + f.right - f.done, room);
+                VOXCHK(ring_write_f32(s, ring, STREAM_SAMPLE_RING, me.n_written, StreamSrc{}, 0, k)); me.n_written += (int64_t)k; f.done += k; wrote |= k > 0;
+            }
+            const int avail = (int)std::min<long>(f.target, stream_positions(left, R, me.n_written));
+            if (avail > me.pos) due.emplace_back(avail - me.pos, f.member);
+        }
+        if (!wrote && due.empty()) return fail(VOX_ERR_INVALID, "internal: stream group stalled");
+        if (due.empty()) continue;
+        std::stable_sort(due.begin(), due.end(), [](const std::pair<int, int>& a, const std::pair<int, int>& b) { return a.first > b.first; });
+        g->orders.emplace_back(); std::array<int, GROUP_MAX>& ord = g->orders.back(); ord.fill(0);
+        for (size_t i = 0; i < due.size(); i++) ord[i] = due[i].second;
+        HIPCHK(hipMemcpyAsync(g->d_order, ord.data(), sizeof(int) * GROUP_MAX, hipMemcpyHostToDevice, s));      // the pass's one upload
+        int n_r = (int)due.size();
+        for (int r = 0; r < due[0].first; r++) {
+            while (due[(size_t)n_r - 1].first <= r) n_r--;
+            VOXCHK(group_round(g, w, n_r));
+        }
+        for (const std::pair<int, int>& d : due) { g->mem[d.second].pos += d.first; g->mem[d.second].steps += (uint64_t)d.first; }
+    }
+    for (size_t k = 0; k < fs.size(); k++) if (fs[k].due > 0)
+        HIPCHK(hipMemcpyAsync(feeds[k].out_ids, g->h_mem[fs[k].member].tokens + VOX_PREFIX_TOKENS + g->mem[fs[k].member].ids_out, (size_t)fs[k].due * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));      // the call's one synchronisation: every fed member's ids land
+    g->orders.clear();
+    for (size_t k = 0; k < fs.size(); k++) { GroupMember& me = g->mem[fs[k].member]; me.ids_out += fs[k].due; feeds[k].n_ids = fs[k].due; if (feeds[k].finish) me.finished = true; }
+    return VOX_OK;
+}
+extern "C" int32_t vox_debug_stream_group_tap_arm(vox_stream_group* g, int32_t member, int32_t max_rows) {
+    ARGCHK(g, "null group"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1);
+    ARGCHK(max_rows > 0 && max_rows <= 65536, "max_rows %d out of range (1..65536)", max_rows); VOXCHK(ctx_bind(g->ctx));
+    HIPCHK(hipStreamSynchronize(g->ctx->stream));
+    StreamMember& me = g->h_mem[member];
+    if (me.tap) { (void)hipFree(me.tap); me.tap = nullptr; me.tap_max = 0; }
+    HIPCHK(hipMalloc((void**)&me.tap, (size_t)max_rows * g->m->cfg.vocab * 4)); me.tap_max = max_rows;
+    HIPCHK(hipMemsetAsync(me.state + STRM_TAP_ROWS, 0, 4, g->ctx->stream));
+    return group_upload_members(g);
+}
+extern "C" int32_t vox_debug_stream_group_tap_fetch(vox_stream_group* g, int32_t member, float* out, int32_t* rows) {
+    ARGCHK(g && out && rows, "null argument"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1);
+    StreamMember& me = g->h_mem[member];
+    ARGCHK(me.tap, "no tap to fetch for member %d (vox_debug_stream_group_tap_arm)", member); VOXCHK(ctx_bind(g->ctx));
+    HIPCHK(hipStreamSynchronize(g->ctx->stream));
+    int n = 0; HIPCHK(hipMemcpy(&n, me.state + STRM_TAP_ROWS, 4, hipMemcpyDeviceToHost));
+    const int k = std::min(n, me.tap_max);
+    if (k > 0) HIPCHK(hipMemcpy(out, me.tap, (size_t)k * g->m->cfg.vocab * 4, hipMemcpyDeviceToHost));
+    *rows = n;
+    (void)hipFree(me.tap); me.tap = nullptr; me.tap_max = 0;
+    return group_upload_members(g);
 }
 
 // ---- debug: the sample front ends on their own (tests).  form 0: the single clip's (clip_front_end); form 1: the batch drivers' (group_peak_scales when norm_group is

@@ -358,18 +358,30 @@ hipError_t tl_configure(unsigned long long* buf, int n_slots, int n_waves);   //
 int tl_slots_used();
 void tl_slot_meta(int slot, int out[4]);    // {0 gemv / 1 attention, epi, N, K} of the launch that took `slot`
 
-// ---- live streaming session (vox_stream): the session advances in TICKS of one decoder position (16 mel frames -> 4 encoder rows -> 1 adapter row ->
-// 1 decode step).  The integers a tick depends on live in one device block per stream, advanced by the tick's last kernel, so a tick's launch arguments never change.
+// ---- live streaming session (vox_stream, vox_stream_group): a session advances in TICKS of one decoder position (16 mel frames -> 4 encoder rows ->
+// 1 adapter row -> 1 decode step).  The integers a tick depends on live in one device block per session, advanced by the tick's last kernel, so a tick's launch arguments
+// never change.  A ROUND runs one tick of n sessions at once (n = 1: a solo vox_stream): slot z of the round serves session order[z], whose pointers the kernels read from
+// a device array of StreamMember descriptors.
 enum StreamWord { STRM_POS = 0,         // decoder position of the next tick (= its adapter row, its decoder cache row; the step yields tokens[position + 1])
                   STRM_ENC_POS = 1,     // encoder stream position of the tick's first row (RoPE position, ring row before the modulo)
                   STRM_FRAME = 2,       // first NEW mel frame of the tick (the halo starts halo_back frames before it)
                   STRM_HEAD = 3,        // STRM_ENC_POS modulo the ring capacity
                   STRM_TICKS = 4,       // ticks run since create / reset
-                  STRM_WORDS = 16 };    // block size in ints (the rest is reserved: a later group of N streams holds N such blocks back to back)
-// front end: the log-mel frames STRM_FRAME - halo_back .. + n_frames - 1 of the virtually padded signal zeros(left) + gain * samples, token-major ([n_frames][128]: the layout the
-// conv stem's im2col GEMM reads).  Sample i of the stream lives at ring[i & ring_mask]; every sample a frame reads has been written (the host runs a tick only then),
-// the reflections of mel_kernel never apply (left >= 200, and the right end of a finished stream is its zero pad).
-hipError_t launch_stream_mel(const float* ring, int ring_mask, long left, float gain, MelTables t, const int* state, int halo_back, int n_frames, float* out, hipStream_t s);
+                  STRM_TAP_ROWS = 5,    // group members: logits rows offered to the member's tap since it was armed
+                  STRM_WORDS = 16 };    // block size in ints (a group of N sessions holds N such blocks back to back)
+struct StreamMember {
+    const float* samples; float gain;   // the session's 16 kHz sample ring; every sample is multiplied by gain before the mel
+    int* state;                         // its StreamWord block
+    float *kring, *vring;               // its encoder K / V ring, [enc_layers][n_heads][cap][hd]
+    int* tokens;                        // its token row
+    float* tap; int tap_max;            // group members: [tap_max][vocab] logits rows (null: not armed)
+};
+// front end: for every slot z < n the log-mel frames STRM_FRAME - halo_back .. + n_frames - 1 of the virtually padded signal zeros(left) + gain * samples of session
+// order[z], token-major into out + z * slot_stride ([n_frames][128]: the layout the conv stem's im2col GEMM reads).  Sample i of a session lives at ring[i & ring_mask];
+// every sample a frame reads has been written (the host runs a tick only then), the reflections of mel_kernel never apply (left >= 200, and the right end of a finished
+// session is its zero pad).
+hipError_t launch_stream_mel(const StreamMember* mem, const int* order, int n, int ring_mask, long left, MelTables t, int halo_back, int n_frames, float* out, long slot_stride,
+                             hipStream_t s);
 // ingest at the capture rate: the 16 kHz samples [i0, i0 + count) of the stream from its input-rate ring, with resample_apply_kernel's arithmetic (At, fft_in, fft_out, delay:
 // launch_resample's) -- bit for bit vox_resample's samples for the concatenated input.  Input sample k lives at in_ring[k & in_mask], output sample i goes to
 // out_ring[i & out_mask]; n_in: the input samples that exist (written so far, or the utterance's length at its end): blocks are clipped there.  The caller launches it only
@@ -378,14 +390,15 @@ hipError_t launch_stream_resample(const float* in_ring, int in_mask, long n_in, 
                                   hipStream_t s);
 // 16-bit PCM into a stream's f32 ring: ring[(w0 + k) & mask] = float(src[k]) / 32768 for k < count <= mask + 1 (src: device memory)
 hipError_t launch_stream_s16(const short* src, int count, float* ring, int mask, long w0, hipStream_t s);
-// one encoder layer's attention for the tick's M <= 8 rows against the stream's K / V ring: RoPE on q and k at the absolute stream position, k / v appended at
-// position % cap, query m attends the keys j <= position_m, position_m - j <= window in ascending order of j (the ring changes addresses, not the order).  cap > window + M.
+// one encoder layer's attention for the round's n x M rows (M <= 8 per session, slot z's rows at z * M) against each session's own K / V ring: RoPE on q and k at the
+// session's absolute stream position, k / v appended at position % cap, query m attends the keys j <= position_m, position_m - j <= window in ascending order of j (the
+// ring changes addresses, not the order).  cap > window + M.
 struct StreamAttnParams {
-    const float* qkv; int qkv_stride;        // [M][q | k | v], each n_heads * hd wide, not rotated
-    float* kring; float* vring; int cap;     // this layer's ring, [n_heads][cap][hd]
+    const float* qkv; int qkv_stride;        // [n M][q | k | v], each n_heads * hd wide, not rotated
+    const StreamMember* mem; const int* order; int n;
+    size_t ring_off; int cap;                // this layer's ring inside a session's kring / vring (floats), [n_heads][cap][hd]
     const float* cos_t; const float* sin_t;  // [positions][hd / 2]
-    const int* state;
-    float* out; int out_stride;              // [M][n_heads * hd]
+    float* out; int out_stride;              // [n M][n_heads * hd]
     int M, n_heads, window;
 };
 hipError_t launch_stream_attn(const StreamAttnParams& p, int hd, hipStream_t s);
@@ -398,5 +411,13 @@ hipError_t launch_stream_embed_kept(Q4W tok, const int* tokens, const float* aud
 // tokens[STRM_POS + 1] = argmax over the lm_head partials, then the state advances by one tick (enc_rows encoder rows, frames mel frames;
 // enc_rows = 0: a decode-only re-run moves STRM_POS alone)
 hipError_t launch_stream_advance(const float* part_val, const int* part_idx, int n_parts, int* tokens, int* state, int enc_rows, int frames, int cap, hipStream_t s);
+// ---- the decode half of a group round (vox_stream_group): n <= 16 rows, row r = session order[r], through xf_chain.
+// input rows: h[r] = audio[r] + embed(tokens[STRM_POS]) as f32, as layer 0's XF planes of h * xf_w with the row's sum of squares (what launch_argmax_embed_batch forms),
+// pos[r] = STRM_POS and kv_row[r] = order[r]: the positions and cache slices xf_chain reads
+hipError_t launch_stream_group_embed(Q4W tok, const StreamMember* mem, const int* order, int n, const float* audio, int D, float* h, uint16_t* xf, const float* xf_w,
+                                     float* ssq_out, int* pos, int* kv_row, hipStream_t s);
+// tokens[STRM_POS + 1] = argmax of logits row r (argmax_take / block_argmax: the rule of every decode form), the row copied to the session's tap when one is armed,
+// then the session's state advances by one tick as launch_stream_advance moves it
+hipError_t launch_stream_group_advance(const float* logits, int vocab, const StreamMember* mem, const int* order, int n, int enc_rows, int frames, int cap, hipStream_t s);
 
 }  // namespace vox

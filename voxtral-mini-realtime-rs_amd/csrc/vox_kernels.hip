@@ -4163,18 +4163,22 @@ hipError_t launch_gelu(float* x, long n, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// live streaming session (vox_stream): the kernels of one tick that are not the row-independent operators.  Every per-tick integer comes from the stream's device
-// state block (StreamWord), so the launch arguments of a tick never change.
+// live streaming session (vox_stream, vox_stream_group): the kernels of one tick that are not the row-independent operators.  Every per-tick integer comes from the
+// session's device state block (StreamWord), so the launch arguments of a tick never change.  The kernels serve a ROUND of n sessions (a solo stream: n = 1): slot z of the
+// launch works for session order[z], through that session's StreamMember descriptor.
 // ------------------------------------------------------------------------------------------------
 // front end: mel_kernel's arithmetic (windowed frame, 400-point table DFT, Slaney bank, log10 / floor / scale) on frames of a sample ring, written token-major with
 // the conv stem's halo in front.  No reflection branch: the host guarantees left >= 200 and runs a tick only when every sample its frames read has been written.
-__global__ __launch_bounds__(256) void stream_mel_kernel(const float* __restrict__ ring, int ring_mask, long left, float gain, MelTables t, const int* __restrict__ state,
-                                                         int halo_back, float* __restrict__ out) {
+__global__ __launch_bounds__(256) void stream_mel_kernel(const StreamMember* __restrict__ mem, const int* __restrict__ order, int ring_mask, long left, MelTables t,
+                                                         int halo_back, float* __restrict__ out_all, long slot_stride) {
     __shared__ float fr[400];
     __shared__ float ct[400], st[400];
     __shared__ float pw[201 + 3];
     const int tid = threadIdx.x;
-    const long f = (long)state[STRM_FRAME] - halo_back + blockIdx.x;
+    const StreamMember& me = mem[order[blockIdx.y]];
+    const float* __restrict__ ring = me.samples; const float gain = me.gain;
+    float* __restrict__ out = out_all + (size_t)blockIdx.y * slot_stride;
+    const long f = (long)me.state[STRM_FRAME] - halo_back + blockIdx.x;
     for (int j = tid; j < 400; j += 256) {
         const long ai = f * 160 + j - 200 - left;      // index into the stream's samples; below 0: the silent left pad
         float v = 0.f;
@@ -4204,9 +4208,10 @@ __global__ __launch_bounds__(256) void stream_mel_kernel(const float* __restrict
         out[(size_t)blockIdx.x * 128 + tid] = v;
     }
 }
-hipError_t launch_stream_mel(const float* ring, int ring_mask, long left, float gain, MelTables t, const int* state, int halo_back, int n_frames, float* out, hipStream_t s) {
-    if (n_frames <= 0 || left < 200 || (ring_mask & (ring_mask + 1))) return hipErrorInvalidValue;
-    stream_mel_kernel<<<dim3(n_frames), dim3(256), 0, s>>>(ring, ring_mask, left, gain, t, state, halo_back, out);
+hipError_t launch_stream_mel(const StreamMember* mem, const int* order, int n, int ring_mask, long left, MelTables t, int halo_back, int n_frames, float* out, long slot_stride,
+                             hipStream_t s) {
+    if (n_frames <= 0 || n < 1 || n > 16 || left < 200 || (ring_mask & (ring_mask + 1)) || slot_stride < (long)n_frames * 128) return hipErrorInvalidValue;
+    stream_mel_kernel<<<dim3(n_frames, n), dim3(256), 0, s>>>(mem, order, ring_mask, left, t, halo_back, out, slot_stride);
     return hipGetLastError();
 }
 
@@ -4257,7 +4262,7 @@ hipError_t launch_stream_s16(const short* src, int count, float* ring, int mask,
     return hipGetLastError();
 }
 
-// RoPE + K / V append + windowed attention of one encoder layer for the tick's rows, one workgroup per (head, query row).  The workgroup rotates the tick's k rows
+// RoPE + K / V append + windowed attention of one encoder layer for the round's rows, one workgroup per (head, query row, slot).  The workgroup rotates the tick's k rows
 // 0 .. m of its head itself (LDS), so no workgroup reads a ring row another one writes in this launch: ring rows are read for positions below the tick's first only, and
 // with cap > window + M the rows written now hold positions no query of the tick sees any more.  Scores: 16 lanes per key (one float4 each at hd 64), the keys in
 // ascending position; softmax and the weighted sum in fixed order over the key index relative to the window start -- the ring capacity changes addresses only.
@@ -4272,20 +4277,23 @@ __global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_attn_kernel(const St
     __shared__ float red[G][HD];
     __shared__ float wred[4];
     const int h = blockIdx.x, m = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int enc_pos = p.state[STRM_ENC_POS], qpos = enc_pos + m, QD = p.n_heads * HD;
+    const StreamMember& me = p.mem[p.order[blockIdx.z]];
+    float* __restrict__ kring = me.kring + p.ring_off; float* __restrict__ vring = me.vring + p.ring_off;
+    const float* __restrict__ qkv = p.qkv + (size_t)blockIdx.z * p.M * p.qkv_stride;      // the slot's M rows
+    const int enc_pos = me.state[STRM_ENC_POS], qpos = enc_pos + m, QD = p.n_heads * HD;
     for (int i = tid; i < (m + 2) * HALF; i += 256) {      // k rows 0 .. m, then the query row
         const int r = i / HALF, j = i - r * HALF; const bool isq = r == m + 1; const int row = isq ? m : r;
         const size_t ti = (size_t)(enc_pos + row) * HALF + j;
         const float c = p.cos_t[ti], sn = p.sin_t[ti];
-        const float* src = p.qkv + (size_t)row * p.qkv_stride + (isq ? 0 : QD) + h * HD + 2 * j;
+        const float* src = qkv + (size_t)row * p.qkv_stride + (isq ? 0 : QD) + h * HD + 2 * j;
         const float xr = src[0], xi = src[1];
         float* dst = isq ? qs : kn[r];
         dst[2 * j] = xr * c - xi * sn; dst[2 * j + 1] = xr * sn + xi * c;
     }
-    for (int i = tid; i < (m + 1) * HD; i += 256) { const int r = i / HD, d = i - r * HD; vn[r][d] = p.qkv[(size_t)r * p.qkv_stride + 2 * QD + h * HD + d]; }
+    for (int i = tid; i < (m + 1) * HD; i += 256) { const int r = i / HD, d = i - r * HD; vn[r][d] = qkv[(size_t)r * p.qkv_stride + 2 * QD + h * HD + d]; }
     __syncthreads();
     const size_t hbase = (size_t)h * p.cap * HD;
-    if (tid < HD) { const size_t slot = hbase + (size_t)(qpos % p.cap) * HD + tid; p.kring[slot] = kn[m][tid]; p.vring[slot] = vn[m][tid]; }
+    if (tid < HD) { const size_t slot = hbase + (size_t)(qpos % p.cap) * HD + tid; kring[slot] = kn[m][tid]; vring[slot] = vn[m][tid]; }
     const int j0 = max(0, qpos - p.window), nk = qpos - j0 + 1;      // keys j0 .. qpos (host: window + 1 <= 1024)
     const int g = tid >> 4, li = tid & 15;
     const float scale = HD == 64 ? 0.125f : 0.08838834764831845f;      // head_dim^-0.5
@@ -4295,7 +4303,7 @@ __global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_attn_kernel(const St
 #pragma unroll
         for (int u = 0; u < HD / 64; u++) {
             const int o = (u * 16 + li) * 4;
-            const float4 kv = j < enc_pos ? *reinterpret_cast<const float4*>(p.kring + hbase + (size_t)(j % p.cap) * HD + o) : *reinterpret_cast<const float4*>(&kn[j - enc_pos][o]);
+            const float4 kv = j < enc_pos ? *reinterpret_cast<const float4*>(kring + hbase + (size_t)(j % p.cap) * HD + o) : *reinterpret_cast<const float4*>(&kn[j - enc_pos][o]);
             const float4 qv = *reinterpret_cast<const float4*>(&qs[o]);
             dot = fmaf(qv.x, kv.x, dot); dot = fmaf(qv.y, kv.y, dot); dot = fmaf(qv.z, kv.z, dot); dot = fmaf(qv.w, kv.w, dot);
         }
@@ -4320,7 +4328,7 @@ __global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_attn_kernel(const St
     float acc = 0.f;
     for (int i = kg; i < nk; i += G) {
         const int j = j0 + i;
-        const float vv = j < enc_pos ? p.vring[hbase + (size_t)(j % p.cap) * HD + d] : vn[j - enc_pos][d];
+        const float vv = j < enc_pos ? vring[hbase + (size_t)(j % p.cap) * HD + d] : vn[j - enc_pos][d];
         acc = fmaf(sc[i], vv, acc);
     }
     red[kg][d] = acc;
@@ -4329,14 +4337,15 @@ __global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_attn_kernel(const St
         float o = red[0][tid];
 #pragma unroll
         for (int q = 1; q < G; q++) o += red[q][tid];
-        p.out[(size_t)m * p.out_stride + h * HD + tid] = o / sum;
+        p.out[((size_t)blockIdx.z * p.M + m) * p.out_stride + h * HD + tid] = o / sum;
     }
 }
 hipError_t launch_stream_attn(const StreamAttnParams& p, int hd, hipStream_t s) {
-    if (p.M < 1 || p.M > 8 || p.window < 0 || p.window + 1 > 1024 || p.cap <= p.window + p.M || ((uintptr_t)p.kring & 15) || ((uintptr_t)p.vring & 15)) return hipErrorInvalidValue;      // (the ring rows are read as float4: hd % 4 == 0 holds for 64 / 128)
+    // (the ring rows are read as float4: the sessions' rings are hipMalloc'd, a layer's offset is a multiple of hd, hd % 4 == 0 holds for 64 / 128)
+    if (p.M < 1 || p.M > 8 || p.n < 1 || p.n > 16 || !p.mem || !p.order || p.window < 0 || p.window + 1 > 1024 || p.cap <= p.window + p.M || (p.ring_off & 3)) return hipErrorInvalidValue;
     attn_form_note(ATTN_FORM_STREAM_RING);
-    if (hd == 64) stream_attn_kernel<64><<<dim3(p.n_heads, p.M), dim3(256), 0, s>>>(p);
-    else if (hd == 128) stream_attn_kernel<128><<<dim3(p.n_heads, p.M), dim3(256), 0, s>>>(p);
+    if (hd == 64) stream_attn_kernel<64><<<dim3(p.n_heads, p.M, p.n), dim3(256), 0, s>>>(p);
+    else if (hd == 128) stream_attn_kernel<128><<<dim3(p.n_heads, p.M, p.n), dim3(256), 0, s>>>(p);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
@@ -4376,6 +4385,16 @@ hipError_t launch_stream_embed_kept(Q4W tok, const int* tokens, const float* aud
     return hipGetLastError();
 }
 
+// a session's state block after a tick (one thread): the token, the next position and, for a tick that ran the encoder (enc_rows > 0), the encoder words
+__device__ __forceinline__ void stream_state_step(int* __restrict__ tokens, int* __restrict__ state, int idx, int enc_rows, int frames, int cap) {
+    const int pos = state[STRM_POS];
+    tokens[pos + 1] = idx;
+    state[STRM_POS] = pos + 1;
+    if (enc_rows > 0) {
+        const int e = state[STRM_ENC_POS] + enc_rows;
+        state[STRM_ENC_POS] = e; state[STRM_HEAD] = e % cap; state[STRM_FRAME] += frames; state[STRM_TICKS] += 1;
+    }
+}
 // the tick's last kernel: the argmax over the lm_head partials, as argmax_final_kernel, then the state block moves on
 __global__ __launch_bounds__(256) void stream_advance_kernel(const float* __restrict__ pv, const int* __restrict__ pi, int n_parts, int* __restrict__ tokens, int* __restrict__ state,
                                                              int enc_rows, int frames, int cap) {
@@ -4384,18 +4403,55 @@ __global__ __launch_bounds__(256) void stream_advance_kernel(const float* __rest
     float v; int idx;
     argmax_scan_partials<256>(pv, pi, n_parts, v, idx);
     block_argmax<256>(v, idx, bv, bi);
-    if (threadIdx.x == 0) {
-        const int pos = state[STRM_POS];
-        tokens[pos + 1] = idx;
-        state[STRM_POS] = pos + 1;
-        if (enc_rows > 0) {
-            const int e = state[STRM_ENC_POS] + enc_rows;
-            state[STRM_ENC_POS] = e; state[STRM_HEAD] = e % cap; state[STRM_FRAME] += frames; state[STRM_TICKS] += 1;
-        }
-    }
+    if (threadIdx.x == 0) stream_state_step(tokens, state, idx, enc_rows, frames, cap);
 }
 hipError_t launch_stream_advance(const float* part_val, const int* part_idx, int n_parts, int* tokens, int* state, int enc_rows, int frames, int cap, hipStream_t s) {
     stream_advance_kernel<<<dim3(1), dim3(256), 0, s>>>(part_val, part_idx, n_parts, tokens, state, enc_rows, frames, cap);
+    return hipGetLastError();
+}
+
+
+// ---- the decode half of a group round: one workgroup per row r of the round (session order[r]).  Rows past the round's n are not touched by either kernel: what an
+// earlier, wider round left in h, the XF planes, pos or kv_row there is never read for a cache row, a token or a tap (xf_chain's kernels guard every store by the row count).
+__global__ __launch_bounds__(256) void stream_group_embed_kernel(Q4W tok, const StreamMember* __restrict__ mem, const int* __restrict__ order, const float* __restrict__ audio, int D,
+                                                                 float* __restrict__ h, uint16_t* __restrict__ xf, const float* __restrict__ xf_w, float* __restrict__ ssq_out,
+                                                                 int* __restrict__ pos_out, int* __restrict__ kv_row_out) {
+    __shared__ float wsum[4];
+    const int r = blockIdx.x, member = order[r];
+    const StreamMember& me = mem[member];
+    const int pos = me.state[STRM_POS];
+    float* hrow = h + (size_t)r * D;
+    embed_row(tok, me.tokens[pos], audio + (size_t)r * D, hrow, D);
+    xf_row_ssq(hrow, xf_w, D, xf, r, ssq_out, wsum);
+    if (threadIdx.x == 0) { pos_out[r] = pos; kv_row_out[r] = member; }
+}
+hipError_t launch_stream_group_embed(Q4W tok, const StreamMember* mem, const int* order, int n, const float* audio, int D, float* h, uint16_t* xf, const float* xf_w,
+                                     float* ssq_out, int* pos, int* kv_row, hipStream_t s) {
+    if (n < 1 || n > 16 || !mem || !order || !audio || !h || !xf || !xf_w || !ssq_out || !pos || !kv_row || (D & 127)) return hipErrorInvalidValue;
+    stream_group_embed_kernel<<<dim3(n), dim3(256), 0, s>>>(tok, mem, order, audio, D, h, xf, xf_w, ssq_out, pos, kv_row);
+    return hipGetLastError();
+}
+__global__ __launch_bounds__(1024) void stream_group_advance_kernel(const float* __restrict__ logits, int vocab, const StreamMember* __restrict__ mem, const int* __restrict__ order,
+                                                                   int enc_rows, int frames, int cap) {
+    __shared__ float bv[16];
+    __shared__ int bi[16];
+    __shared__ int s_tap;
+    const StreamMember& me = mem[order[blockIdx.x]];
+    const float* row = logits + (size_t)blockIdx.x * vocab;
+    if (threadIdx.x == 0) s_tap = me.tap ? me.state[STRM_TAP_ROWS] : -1;
+    float v; int idx;
+    argmax_scan_row<1024>(row, vocab, v, idx);
+    block_argmax<1024>(v, idx, bv, bi);      // (its barrier also publishes s_tap)
+    const int k = s_tap;
+    if (k >= 0 && k < me.tap_max) { float* dst = me.tap + (size_t)k * vocab; for (int i = threadIdx.x; i < vocab; i += 1024) dst[i] = row[i]; }
+    if (threadIdx.x == 0) {
+        if (k >= 0) me.state[STRM_TAP_ROWS] = k + 1;      // (a row past tap_max is counted, not stored: the fetch reports it)
+        stream_state_step(me.tokens, me.state, idx, enc_rows, frames, cap);
+    }
+}
+hipError_t launch_stream_group_advance(const float* logits, int vocab, const StreamMember* mem, const int* order, int n, int enc_rows, int frames, int cap, hipStream_t s) {
+    if (n < 1 || n > 16 || !logits || !mem || !order || vocab <= 0 || enc_rows <= 0 || cap <= 0) return hipErrorInvalidValue;
+    stream_group_advance_kernel<<<dim3(n), dim3(1024), 0, s>>>(logits, vocab, mem, order, enc_rows, frames, cap);
     return hipGetLastError();
 }
 

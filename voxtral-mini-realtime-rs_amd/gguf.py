@@ -495,6 +495,73 @@ class LiveStream:
             pass
 
 
+class LiveStreamGroup:
+    """A stream group (vox_stream_group): up to 16 live sessions on one model advanced together, every weight matrix read once per tick for all members that have a tick
+    due.  Members are numbered 0 .. n_members-1; each has its own gain and follows stream_schedule on its own sample count.  16 kHz float32 samples."""
+
+    def __init__(self, model, t_embed, n_members, gains=None, enc_capacity_rows=0, max_positions=0):
+        self.model = model; self.h = C.c_void_p(); self.n_members = int(n_members); self._tap_max = {}
+        g = None if gains is None else _f32(gains).reshape(-1)
+        if g is not None and g.size != self.n_members:
+            raise ValueError(f"{g.size} gains for {self.n_members} members")
+        check(lib().vox_stream_group_create(model.h, _ptr(_f32(t_embed).reshape(-1)), self.n_members, None if g is None else _ptr(g), int(enc_capacity_rows),
+                                            int(max_positions), C.byref(self.h)))
+        model._caches.add(self)
+
+    def advance(self, feeds, finish=(), device=False) -> dict:
+        """One call for any subset of members: feeds {member: samples} (float32 arrays; device=True: {member: (device pointer, count)}), finish: the members whose
+        utterance ends with these samples (a member named there alone is fed no samples) -> {member: the ids that became due}."""
+        fin = set(int(k) for k in finish); entries = {int(k): v for k, v in feeds.items()}
+        for k in fin:
+            entries.setdefault(k, (0, 0) if device else np.zeros(0, np.float32))
+        arr = (_lib.StreamFeed * max(len(entries), 1))(); keep = []
+        for e, (k, v) in zip(arr, entries.items()):
+            if device:
+                ptr, n = int(v[0]) or None, int(v[1])
+            else:
+                x = _f32(v).reshape(-1); keep.append(x); ptr, n = (x.ctypes.data if x.size else None), x.size
+            if not 0 <= k < self.n_members:
+                raise ValueError(f"member {k} of a group of {self.n_members}")
+            inf = self.info(k)
+            due = stream_schedule(inf["samples"] + n, k in fin)[1] - inf["ids"]      # each cap comes from the schedule
+            ids = np.zeros(max(due, 1), dtype=np.int32); keep.append(ids)
+            e.member = k; e.finish = 1 if k in fin else 0; e.samples = ptr; e.n_samples = n; e.out_ids = ids.ctypes.data; e.cap = ids.size; e.n_ids = 0
+        check(lib().vox_stream_group_advance(self.h, arr, len(entries), 1 if device else 0))
+        out = {}
+        for e in arr[:len(entries)]:
+            out[e.member] = np.ctypeslib.as_array((C.c_int32 * max(e.cap, 1)).from_address(e.out_ids))[:e.n_ids].copy()
+        return out
+
+    def reset(self, member, gain=1.0):
+        check(lib().vox_stream_group_reset(self.h, int(member), float(gain)))
+
+    def info(self, member):
+        v = (C.c_int64 * 8)(); check(lib().vox_stream_group_info(self.h, int(member), v))
+        return dict(zip(("samples", "positions", "ids", "encoder_position", "ring_rows", "bytes", "engine_steps", "operator_steps"), (int(x) for x in v)))
+
+    def tap_arm(self, member, max_rows):
+        check(lib().vox_debug_stream_group_tap_arm(self.h, int(member), int(max_rows))); self._tap_max[int(member)] = int(max_rows)
+
+    def tap_fetch(self, member):
+        """The f32 logits rows behind the ids handed to `member` since tap_arm: [rows][vocab]."""
+        mx = self._tap_max[int(member)]
+        buf = np.zeros((mx, self.model.config.vocab), dtype=np.float32); rows = C.c_int32()
+        check(lib().vox_debug_stream_group_tap_fetch(self.h, int(member), _ptr(buf), C.byref(rows)))
+        if rows.value > mx:
+            raise VoxError(1, f"stream group tap: {rows.value} rows for a tap of {mx}")
+        return buf[:rows.value].copy()
+
+    def close(self):
+        if self.h:
+            lib().vox_stream_group_free(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Q4VoxtralModel:
     """gguf/model.rs:759-989"""
 
@@ -667,6 +734,11 @@ class Q4VoxtralModel:
         """A live session on this model (vox_stream_create / vox_stream_create_rate): push(x) -> ids, finish(), reset(), info(), close().  gain multiplies every sample
         (a stream has no file peak: 0.95 / max|x| of a known file reproduces transcribe_audio).  sample_rate: the rate of the samples that will be pushed."""
         return LiveStream(self, t_embed, gain, enc_capacity_rows, max_positions, sample_rate)
+
+    def create_stream_group(self, t_embed, n_members, gains=None, enc_capacity_rows=0, max_positions=0) -> LiveStreamGroup:
+        """Up to 16 live sessions advanced together (vox_stream_group_create): advance({member: samples}, finish=()) -> {member: ids}, reset(member, gain), info(member),
+        close().  gains: one per member (None: 1.0 each); max_positions 0: 2048 decoder positions per member (the group's decoder cache does not grow)."""
+        return LiveStreamGroup(self, t_embed, n_members, gains, enc_capacity_rows, max_positions)
 
     def transcribe_batch(self, samples_list, t_embed, device_ptrs=None, n_samples=None, norm_group=None, tap_units=None):
         """Batched whole-path transcription of independent utterances (<= 4096; wider than 16: continuous batching over decode slots): list of float32 sample arrays
