@@ -368,7 +368,8 @@ int32_t vox_debug_reload_knobs(void);
 /* Test hook: attention launches enqueued by this process so far, by kernel form (host-side counts; the replays of a captured graph are not counted):
  * out[0] short-sequence prefill, [1] MFMA prefill, [2] f32 VALU prefill (VOX_ATTN_F32), [3] single-query decode, [4] its speculative-row form (VOX_ATTN_SPEC),
  * [5] batched GQA decode, [6] fused attention + wo, [7] single-stream decode-engine launches (the whole step), [8] the live stream's ring attention (RoPE + K / V append + windowed
- * attention in one launch: exactly enc_layers per tick of a vox_stream).  Entries past [8] are written as 0. */
+ * attention in one launch: exactly enc_layers per tick of a vox_stream).  Behind them, not attention: [9] a stream group's resampling ingest (one launch per pass for
+ * all fed members), [10] a solo stream's.  Entries past [10] are written as 0. */
 int32_t vox_debug_attn_launches(uint64_t* out, int32_t cap);
 /* Test hook: launches of the linear kernels enqueued by this process so far, by kernel form (host-side counts, as above; nothing is dispatched by them):
  * out[0..2] Q4 GEMV with 1 / 2 / 4 rows per wave, [3] dense GEMV, [4] 5..16-row skinny GEMM, [5] 17..48-row skinny GEMM (one-dimensional form), [6] its split-K form,
@@ -511,8 +512,8 @@ int32_t vox_debug_stream_front_tap_fetch(vox_stream* s, float* out_mel, float* o
 
 /* ---- stream group: up to 16 live sessions advanced together (no reference counterpart) ---------------------------------------------------------------------------------
  * A vox_stream_group holds n_members member sessions on one model and one t_embed, each with its own gain, sample ring, encoder K / V ring and slice of the group's
- * decoder cache.  vox_stream_group_advance feeds any subset of the members (16 kHz f32 samples, host or device memory: mem_kind holds for the whole call) and advances
- * them together: every weight matrix is read by ONE launch per tick for all members that have a tick due, and the call synchronises once.
+ * decoder cache.  vox_stream_group_advance feeds any subset of the members (f32 samples at each member's rate, host or device memory: mem_kind holds for the whole
+ * call; vox_stream_group_advance_s16: signed 16-bit PCM) and advances them together: every weight matrix is read by ONE launch per tick for all members that have a tick due, and the call synchronises once.
  *   Contract: a member's schedule is vox_stream_schedule's on that member's own sample count; every call hands each fed member exactly the ids that became due, and a
  *   member fed with finish = 1 ends its utterance with those samples (right pad, remaining ids: vox_pad_len(n) / 2560 - 38 in all).  A member's ids are those of a solo
  *   vox_stream with the same gain fed the same samples in the project's usual sense -- its logits stay within f32 summation-order noise (2e-4 of the largest logit) of the
@@ -525,20 +526,42 @@ int32_t vox_debug_stream_front_tap_fetch(vox_stream* s, float* out_mel, float* o
  *   selects 2048 (5.4 minutes; at full size 0.21 MB per position, 0.44 GB per member) and a member that reaches it is refused until its reset.  Each member also holds an
  *   encoder ring (enc_capacity_rows as vox_stream_create's: 0.4 GB at full size).  The decode engine is not used.
  *   Creation refuses (VOX_ERR_UNSUPPORTED) what vox_stream_create refuses and models without tile-ordered Q4 weights; n_members outside 1..16 is invalid.
- *   16 kHz f32 only (no capture rate, no 16-bit PCM).  gains: one per member, null = 1.0 each. */
+ *   gains: one per member, null = 1.0 each.
+ * CAPTURE RATE AND 16-BIT PCM.  The rate is member state (vox_stream_group_create_rates, vox_stream_group_reset_rate; 16000 unless set), the sample format belongs to the
+ * call, as mem_kind does: vox_stream_group_advance_s16 reads every entry's samples as int16_t (sample v enters as float(v) / 32768, exact), and the two calls may alternate
+ * on one group.  A member at rate sr follows vox_stream_schedule_rate on its own count of input-rate samples (cap, max_positions and the finish target are checked against
+ * it; vox_stream_group_info [0] counts samples as pushed) and consumes, bit for bit, the 16 kHz samples vox_resample gives for its concatenated input: CAPTURE RATE above
+ * holds for a member unchanged, the added-latency table included.
+ *   Invariant: a call in which every entry fits its rings in one pass runs exactly the rounds -- the same order, the same widths -- that a 16 kHz group runs when fed,
+ *   in the same call, x16[a:b] per member, x16 = vox_resample(x, sr, 16000), a and b the member's 16 kHz sample counts before and after the call (the third value of
+ *   vox_stream_schedule_rate; vox_resample_len at finish).  So such a group equals that 16 kHz group bit for bit, ids and logits.
+ *   How: in every pass all fed members' samples become 16 kHz samples in ONE resampling launch (behind ONE conversion launch when the call is 16-bit), in front of the
+ *   pass's rounds; the call still synchronises once.  Host 16-bit samples pass through a device staging area of the group (65 536 samples per member, allocated at the
+ *   first such call and counted in the bytes from then on); device samples are read in place.
+ *   State per rate != 16000: the group owns ONE block matrix per rate in use (vox_resample's bits, never the context's matrix), shared by the members at that rate and freed
+ *   when the last of them leaves it or with the group; each such member owns an input ring sized as a solo stream's.  vox_stream_group_info [5] counts the member's ring
+ *   and its share of the matrix.  Rates vox_stream_create_rate refuses: VOX_ERR_UNSUPPORTED; rate 0: VOX_ERR_INVALID; a refused vox_stream_group_reset_rate leaves the
+ *   member, its rate and its state as they were. */
 typedef struct vox_stream_group vox_stream_group;
 typedef struct {
     int32_t member;            /* 0 .. n_members-1, at most one entry per member per call */
     int32_t finish;            /* 1: after these samples the member's utterance ends (right pad, remaining ids) */
-    const float* samples;      /* 16 kHz f32, mem_kind of the call; may be null when n_samples == 0 */
+    const float* samples;      /* at the member's rate, mem_kind of the call: f32, or int16_t for vox_stream_group_advance_s16; may be null when n_samples == 0 */
     size_t n_samples;
     int32_t* out_ids; int32_t cap;
     int32_t n_ids;             /* out */
 } vox_stream_feed;
 int32_t vox_stream_group_create(vox_model* m, const float* t_embed, int32_t n_members, const float* gains /* null: 1.0 */,
                                 int32_t enc_capacity_rows, int32_t max_positions, vox_stream_group** out);
+/* vox_stream_group_create with a rate per member (null: 16000 each); a member at another rate also owns its input ring, the group one block matrix per rate */
+int32_t vox_stream_group_create_rates(vox_model* m, const float* t_embed, int32_t n_members, const float* gains /* null: 1.0 */, const uint32_t* rates /* null: 16000 each */,
+                                      int32_t enc_capacity_rows, int32_t max_positions, vox_stream_group** out);
 int32_t vox_stream_group_advance(vox_stream_group* g, vox_stream_feed* feeds, int32_t n_feeds, int32_t mem_kind);
-int32_t vox_stream_group_reset(vox_stream_group* g, int32_t member, float gain);   /* member back to the prefix state: the next connection */
+/* vox_stream_group_advance with every entry's `samples` pointing at int16_t samples at that member's rate; the same refusals, before anything changes */
+int32_t vox_stream_group_advance_s16(vox_stream_group* g, vox_stream_feed* feeds, int32_t n_feeds, int32_t mem_kind);
+int32_t vox_stream_group_reset(vox_stream_group* g, int32_t member, float gain);   /* member back to the prefix state: the next connection, at the member's current rate */
+/* the same for a connection that delivers sample_rate Hz (may build that rate's matrix: synchronises) */
+int32_t vox_stream_group_reset_rate(vox_stream_group* g, int32_t member, float gain, uint32_t sample_rate);
 /* vox_stream_info's eight words for the member; [5] is the member's share of the group's device bytes, [6] is 0 (no engine step), [7] counts the member's ticks */
 int32_t vox_stream_group_info(const vox_stream_group* g, int32_t member, int64_t out[8]);
 int32_t vox_stream_group_free(vox_stream_group* g);

@@ -3,6 +3,7 @@
 
     python tools/stream_bench.py [--gguf PATH] [--ticks 200] [--passes 3] [--out profiles/stream_tick.txt]
     python tools/stream_bench.py --group 1,2,4,8,16 [--out profiles/stream_group_tick.txt]
+    python tools/stream_bench.py --group 1,4,16 --rate 48000 --s16 [--out profiles/stream_group_rate_tick.txt]
 
  * stream: HIP events on the context's stream around ONE push of `ticks` x 2560 samples (a large push is a loop of identical ticks), at encoder positions past the
    750-row window, median of `passes` passes; launches per tick from the library's launch counters plus the fixed launches of a tick; wall time of single 160 ms pushes
@@ -13,6 +14,11 @@
  * --group N[,N...]: steady ROUNDS of a stream group (vox_stream_group) of N members, every member active and past the 750-row encoder window: HIP events around ONE
    advance of `ticks` ticks per member (= `ticks` rounds of width N), median of `passes` passes, next to the solo stream's tick in the same run -- a solo pass and a
    group pass alternate; launches per round from the library's launch counters plus the fixed launches of a round.  No baseline in this mode.
+ * --rate SR [--s16] (with --group): the same run also times a second group whose members are all fed at SR Hz (float32, or 16-bit PCM with --s16), the same way -- a
+   third pass alternating with the other two, one advance of `ticks` ticks' worth of input per member from host memory -- and reports the difference to the 16 kHz f32
+   round of the same run: what the ingest costs (the larger host copies, the conversion and resampling launches, the extra passes of a push larger than the input ring).
+   A fourth pass feeds a third group at SR Hz from device memory, which takes the host copies out of the difference.  A round grows with the decoder position, so
+   all three groups are warmed alike and run one timed pass per loop: pass i of each covers the same positions (the rate groups' to within one tick).
  * derived figures are labelled as derived."""
 import argparse
 import ctypes as C
@@ -67,11 +73,25 @@ def bench_groups(pkg, ctx, m, t, tm, a, widths, lines):
     assert 37 + n_ticks < 1024, "every timed solo step stays on the decode engine's 1024-row cache"
     x = S.synth_audio(n_ticks * 0.16 + 1.0, seed=4242); gain = float(np.float32(0.95) / np.float32(np.abs(x).max()))
     fixed_enc = 1 + 2 * c.enc_layers + 1      # stream_mel, two RMSNorms per encoder layer, the final norm
-    rows = []
+    rows = []; rate_rows = []
+    sr = a.rate; per = sr * 2560 // 16000 if sr else 0      # input samples per tick
+    if sr:
+        assert per * 16000 == sr * 2560, "--rate: a tick must be a whole number of input samples"
+        rng = np.random.default_rng(4242); n_r = per * (n_ticks + 8)
+        xr = (0.1 * rng.standard_normal(n_r) + 0.3 * np.sin(np.arange(n_r) * (0.07 * 16000 / sr))).astype(np.float32)
+        if a.s16:
+            xr = np.round(xr * 16000).astype(np.int16)
+        gr = gain if not a.s16 else 1.0
+        dev = C.c_void_p(); pkg._lib.check(pkg.lib().vox_dev_alloc(ctx.h, xr.nbytes, C.byref(dev))); pkg._lib.check(pkg.lib().vox_dev_upload(ctx.h, dev, xr.ctypes.data, xr.nbytes))
     for N in widths:
         st = m.create_stream(t, gain=gain); g = m.create_stream_group(t, N, gains=[gain] * N)
         pos = 40 + 2560 * warm
         st.push(x[:pos]); g.advance({k: x[:pos] for k in range(N)})
+        if sr:
+            g2, g3 = (m.create_stream_group(t, N, gains=[gr] * N, sample_rates=[sr] * N) for _ in range(2)); rpos = per * (warm + 1)      # fed from host / device memory
+            for gg in (g2, g3):
+                gg.advance({k: xr[:rpos] for k in range(N)})
+            rate, rate_dev = [], []
         solo, grp = [], []; ks = kg = 0
         for _ in range(a.passes):
             seg = x[pos:pos + 2560 * a.ticks]; pos += 2560 * a.ticks
@@ -79,21 +99,49 @@ def bench_groups(pkg, ctx, m, t, tm, a, widths, lines):
             feeds = {k: seg for k in range(N)}
             grp.append(tm.ms(lambda: g.advance(feeds)) / a.ticks); k2 = launch_counts(pkg)
             ks += sum(k1) - sum(k0); kg += sum(k2) - sum(k1)
+            if sr:      # the rate groups: `ticks` ticks' worth of the same input from host memory and from device memory; per tick actually run
+                n = per * a.ticks
+                for gg, out, device in ((g2, rate, False), (g3, rate_dev, True)):
+                    p0 = gg.info(0)["positions"]
+                    assert abs(p0 - (pos // 2560 + 38 - a.ticks)) <= 1      # where the 16 kHz group's pass began, to within the ingest's latency
+                    if device:
+                        fr = {k: (dev.value + rpos * xr.itemsize, n) for k in range(N)}
+                        ms = tm.ms(lambda: gg.advance(fr, device=True, dtype="s16" if a.s16 else "f32"))
+                    else:
+                        fr = {k: xr[rpos:rpos + n] for k in range(N)}
+                        ms = tm.ms(lambda: gg.advance(fr))
+                    done = gg.info(N - 1)["positions"] - p0
+                    assert abs(done - a.ticks) <= 1
+                    out.append(ms / done)
+                rpos += n
         assert g.info(N - 1)["positions"] == st.info()["positions"] == 38 + warm + a.ticks * a.passes
         st.close(); g.close()
+        if sr:
+            g2.close(); g3.close(); rate_rows.append((N, statistics.median(rate), statistics.median(rate_dev), statistics.median(grp), rate, rate_dev))
         ticks = a.ticks * a.passes; tick = statistics.median(solo); rnd = statistics.median(grp)
         ls = ks / ticks + fixed_enc + 2; lg = kg / ticks + fixed_enc + 2      # + embed and advance (the group's compaction of the conv rows is a copy, not a launch)
         rows.append((N, rnd, tick))
         lines += [f"group of {N:2d}: round median {rnd:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in grp) + f"   solo tick median {tick:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in solo),
                   f"  round / ({N} x solo tick) = {rnd / (N * tick):.3f}   per member and tick {rnd / N:.3f} ms   launches per round {lg:.0f} (solo tick {ls:.0f})"]
     lines.append("derived: members one GPU serves in real time at each width = N x 160 ms / round: " + ", ".join(f"{N}: {N * 160.0 / r:.0f}" for N, r, _ in rows))
+    if sr:
+        what = f"{sr} Hz {'s16' if a.s16 else 'f32'}"
+        lines.append(f"# every member fed at {what} ({per} input samples per tick), next to the 16 kHz f32 round above (same run, same passes)")
+        for N, r, rd, base, pr, prd in rate_rows:
+            lines += [f"group of {N:2d} at {what}: round median {r:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in pr) + f"   difference to the 16 kHz f32 round {r - base:+.3f} ms ({100 * (r - base) / base:+.1f} %)",
+                      f"  fed from device memory: round median {rd:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in prd) + f"   difference {rd - base:+.3f} ms ({100 * (rd - base) / base:+.1f} %)"]
+        pkg._lib.check(pkg.lib().vox_dev_free(ctx.h, dev))
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gguf"); ap.add_argument("--ticks", type=int, default=200); ap.add_argument("--passes", type=int, default=3); ap.add_argument("--out")
     ap.add_argument("--group", help="N[,N...]: measure stream-group rounds of these widths next to the solo tick instead of the solo tick and its baseline")
+    ap.add_argument("--rate", type=int, default=0, metavar="SR", help="with --group: also time a group whose members are all fed at SR Hz, next to the 16 kHz f32 round")
+    ap.add_argument("--s16", action="store_true", help="with --rate: feed that group 16-bit PCM")
     a = ap.parse_args()
+    if (a.rate or a.s16) and not a.group or (a.s16 and not a.rate):
+        ap.error("--rate applies with --group, --s16 with --rate")
     widths = [int(v) for v in a.group.split(",")] if a.group else []
     if any(not 1 <= n <= 16 for n in widths):
         ap.error("--group takes widths 1..16")

@@ -180,6 +180,9 @@ SIGNATURES = {
     "vox_stream_group_free": (i32, [vp]),
     "vox_debug_stream_group_tap_arm": (i32, [vp, i32, i32]),
     "vox_debug_stream_group_tap_fetch": (i32, [vp, i32, vp, P(i32)]),
+    "vox_stream_group_create_rates": (i32, [vp, vp, i32, vp, vp, i32, i32, P(vp)]),
+    "vox_stream_group_reset_rate": (i32, [vp, i32, f32, u32]),
+    "vox_stream_group_advance_s16": (i32, [vp, vp, i32, i32]),
 }
 
 _LIB = None

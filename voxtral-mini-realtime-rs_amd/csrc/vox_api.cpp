@@ -4267,18 +4267,23 @@ static int32_t stream_geometry(vox_model* m, int32_t enc_capacity_rows, int32_t 
     { vox_pad_cfg pc; vox_pad_cfg_voxtral(&pc); g->left = (long)pad_left(&pc); }
     return VOX_OK;
 }
+// what a session fed at sample_rate != 16000 needs (a solo stream, a group's member): the plan, the size of its block matrix, the size of its input ring -- a power of
+// two holding two blocks and a feed chunk -- or the refusal of a rate pair vox_resample refuses or whose blocks do not fit the ring
+static int32_t stream_rate_plan(uint32_t sample_rate, ResamplePlan* rp, size_t* rs_bytes, int* in_ring_n) {
+    *rp = resample_plan_make(sample_rate, 16000);
+    VOXCHK(resample_matrix_bytes(sample_rate, 16000, *rp, rs_bytes));
+    if (2 * rp->fft_in + STREAM_FEED_CHUNK > STREAM_IN_RING_MAX)
+        return fail(VOX_ERR_UNSUPPORTED, "a stream at %u Hz: two blocks of %ld samples do not fit its input ring of %d", sample_rate, rp->fft_in, STREAM_IN_RING_MAX);
+    int n = 1; while (n < 2 * rp->fft_in + STREAM_FEED_CHUNK) n <<= 1;
+    *in_ring_n = n;
+    return VOX_OK;
+}
 // sample_rate 16000: the 16 kHz stream, nothing more; any other rate: + the input ring and the stream's own block matrix
 static int32_t stream_create(vox_model* m, const float* t_embed, float gain, int32_t enc_capacity_rows, int32_t max_positions, uint32_t sample_rate, vox_stream** out) {
     ARGCHK(m && t_embed && out, "null argument"); ARGCHK(std::isfinite(gain), "gain is not finite"); ARGCHK(sample_rate > 0, "bad sample rate 0");
     VOXCHK(ctx_bind(m->ctx));
     ResamplePlan rp; size_t rs_bytes = 0; int in_ring_n = 0;
-    if (sample_rate != 16000) {
-        rp = resample_plan_make(sample_rate, 16000);
-        VOXCHK(resample_matrix_bytes(sample_rate, 16000, rp, &rs_bytes));
-        if (2 * rp.fft_in + STREAM_FEED_CHUNK > STREAM_IN_RING_MAX)
-            return fail(VOX_ERR_UNSUPPORTED, "a stream at %u Hz: two blocks of %ld samples do not fit its input ring of %d", sample_rate, rp.fft_in, STREAM_IN_RING_MAX);
-        for (in_ring_n = 1; in_ring_n < 2 * rp.fft_in + STREAM_FEED_CHUNK;) in_ring_n <<= 1;
-    }
+    if (sample_rate != 16000) VOXCHK(stream_rate_plan(sample_rate, &rp, &rs_bytes, &in_ring_n));
     const vox_model_cfg& c = m->cfg; vox_ctx* cx = m->ctx;
     StreamGeom g; VOXCHK(stream_geometry(m, enc_capacity_rows, max_positions, INT32_MAX, &g));
     VOXCHK(enc_stream_rope_ensure(m));
@@ -4627,12 +4632,19 @@ extern "C" int32_t vox_debug_stream_front_tap_fetch(vox_stream* st, float* out_m
 // fed member's due tick count d_i before it launches anything: the members sorted by d_i descending, round r runs ONE tick of the first n_r = #{d_i > r} of them --
 // stream_encode_round at 4 n_r rows (the code of a solo stream's tick) and, as the decode half, xf_chain at n_r rows on the group's decoder slab.  One upload (the
 // order) per pass, constant launch arguments within a pass except n_r, one synchronisation per call.  No engine runs here: no kept rows, no re-run, no verification.
+// A member may be fed at its capture rate, and a call may carry 16-bit PCM (group_advance): the ingest has the member dimension too, one launch per pass.
 // ------------------------------------------------------------------------------------------------
 static const int GROUP_MAX = 16, GROUP_DEFAULT_POSITIONS = 2048;
 struct GroupMember {
-    int64_t n_pushed = 0, n_written = 0; int pos = 0, ids_out = 0; bool finished = false; uint64_t steps = 0;
+    int64_t n_pushed = 0, n_written = 0; int pos = 0, ids_out = 0; bool finished = false; uint64_t steps = 0;      // n_pushed: as pushed, at the member's rate; n_written: 16 kHz
     int h_state[STRM_WORDS];
+    // a member fed at its capture rate (sr != 16000): its slot of the group's rate table, its own input ring, the input samples copied into it so far
+    uint32_t sr = 16000; int rate = -1; float* in_ring = nullptr; int in_ring_n = 0; int64_t in_written = 0;
 };
+// one block matrix per rate in use, shared by the members at that rate (built by resample_matrix_build: vox_resample's bits; never the context's matrix, which goes
+// when vox_resample serves another rate pair).  refs == 0: a free slot
+struct GroupRate { uint32_t sr = 0; ResamplePlan rp; float* At = nullptr; size_t bytes = 0; int refs = 0; };
+struct GroupIngest { StreamIngest rs[16]; StreamS16 pcm[16]; };      // a pass's ingest descriptors, one slot per entry of the call: ONE upload
 struct vox_stream_group {
     vox_model* m = nullptr; vox_ctx* ctx = nullptr;
     std::vector<float> t_embed; int n = 0; StreamGeom g;
@@ -4644,7 +4656,40 @@ struct vox_stream_group {
     MelTables mel{}; uint64_t bytes = 0;
     std::vector<StreamMember> h_mem; std::vector<GroupMember> mem;
     std::deque<std::array<int, GROUP_MAX>> orders;      // the orders uploaded by the call in flight (alive until its synchronisation)
+    std::vector<GroupRate> rates;
+    GroupIngest* d_ingest = nullptr; std::deque<GroupIngest> ingests;      // the pass's ingest descriptors on the device; the ones uploaded by the call in flight, as orders
+    int16_t* s16_stage = nullptr;      // host 16-bit feeds: STREAM_SAMPLE_RING samples of device staging per member, allocated at the first one
 };
+// the member leaves its rate: its input ring and its reference to the rate's matrix go (the matrix with its last reference).  The caller has synchronised.
+static void group_member_drop_rate(vox_stream_group* g, int i) {
+    GroupMember& me = g->mem[i];
+    if (me.in_ring) (void)hipFree(me.in_ring);
+    if (me.rate >= 0) { GroupRate& r = g->rates[(size_t)me.rate]; if (--r.refs == 0) { (void)hipFree(r.At); r = GroupRate{}; } }
+    me.sr = 16000; me.rate = -1; me.in_ring = nullptr; me.in_ring_n = 0; me.in_written = 0;
+}
+// the member's rate from now on.  Everything that can fail happens before anything changes: a refused rate leaves the member as it was.  May synchronise (a new matrix).
+static int32_t group_member_set_rate(vox_stream_group* g, int i, uint32_t sr) {
+    GroupMember& me = g->mem[i];
+    if (sr == me.sr) return VOX_OK;
+    ResamplePlan rp; size_t rs_bytes = 0; int ring_n = 0, slot = -1; float *ring = nullptr, *At = nullptr;
+    if (sr != 16000) {
+        VOXCHK(stream_rate_plan(sr, &rp, &rs_bytes, &ring_n));
+        for (size_t k = 0; k < g->rates.size(); k++) if (g->rates[k].refs > 0 && g->rates[k].sr == sr) slot = (int)k;
+        if (hipMalloc((void**)&ring, (size_t)ring_n * 4) != hipSuccess) { (void)hipGetLastError(); return fail(VOX_ERR_HIP, "hipMalloc of a member's %d-sample input ring failed", ring_n); }
+        if (slot < 0) { const int32_t r = resample_matrix_build(g->ctx, rp, rs_bytes, &At); if (r != VOX_OK) { (void)hipFree(ring); return r; } }
+    }
+    HIPCHK(hipStreamSynchronize(g->ctx->stream));
+    group_member_drop_rate(g, i);
+    if (sr == 16000) return VOX_OK;
+    if (slot < 0) {
+        for (size_t k = 0; k < g->rates.size() && slot < 0; k++) if (g->rates[k].refs == 0) slot = (int)k;
+        if (slot < 0) { g->rates.emplace_back(); slot = (int)g->rates.size() - 1; }
+        GroupRate& r = g->rates[(size_t)slot]; r.sr = sr; r.rp = rp; r.At = At; r.bytes = rs_bytes;
+    }
+    g->rates[(size_t)slot].refs++;
+    me.sr = sr; me.rate = slot; me.in_ring = ring; me.in_ring_n = ring_n; me.in_written = 0;
+    return VOX_OK;
+}
 static int32_t group_upload_members(vox_stream_group* g) {      // after a descriptor changed (gain, tap); synchronises
     HIPCHK(hipMemcpyAsync(g->d_mem, g->h_mem.data(), sizeof(StreamMember) * g->n, hipMemcpyHostToDevice, g->ctx->stream));
     HIPCHK(hipStreamSynchronize(g->ctx->stream));
@@ -4656,21 +4701,26 @@ static int32_t group_member_seed(vox_stream_group* g, int i) {
     GroupMember& me = g->mem[i];
     VOXCHK(stream_seed(g->m, g->t_embed.data(), g->g.RC, g->g.PC, g->g.cap, g->h_mem[i].kring, g->h_mem[i].vring, &view, g->h_mem[i].tokens, g->h_mem[i].state, me.h_state,
                        []() -> int32_t { return VOX_OK; }));
-    me.n_pushed = me.n_written = 0; me.pos = g->g.PC; me.ids_out = 0; me.finished = false; me.steps = 0;
+    me.n_pushed = me.n_written = me.in_written = 0; me.pos = g->g.PC; me.ids_out = 0; me.finished = false; me.steps = 0;
     return VOX_OK;
 }
 static void group_release(vox_stream_group* g) {
     if (!g) return;
     (void)hipSetDevice(g->ctx->device); (void)hipStreamSynchronize(g->ctx->stream);      // never dereferences g->m (as stream_release)
     for (StreamMember& me : g->h_mem) if (me.tap) (void)hipFree(me.tap);
-    for (void* p : {(void*)g->kring, (void*)g->vring, (void*)g->dec_k, (void*)g->dec_v, (void*)g->samples, (void*)g->ws, (void*)g->tokens, (void*)g->state, (void*)g->d_mem, (void*)g->d_order,
+    for (size_t i = 0; i < g->mem.size(); i++) group_member_drop_rate(g, (int)i);
+    for (void* p : {(void*)g->d_ingest, (void*)g->s16_stage, (void*)g->kring, (void*)g->vring, (void*)g->dec_k, (void*)g->dec_v, (void*)g->samples, (void*)g->ws, (void*)g->tokens, (void*)g->state, (void*)g->d_mem, (void*)g->d_order,
                     (void*)g->qkv, (void*)g->att, (void*)g->logits, (void*)g->ssq, (void*)g->xf1, (void*)g->xf2, (void*)g->xf3}) if (p) (void)hipFree(p);
     delete g;
 }
-extern "C" int32_t vox_stream_group_create(vox_model* m, const float* t_embed, int32_t n_members, const float* gains, int32_t enc_capacity_rows, int32_t max_positions,
-                                           vox_stream_group** out) {
+extern "C" int32_t vox_stream_group_create_rates(vox_model* m, const float* t_embed, int32_t n_members, const float* gains, const uint32_t* rates, int32_t enc_capacity_rows,
+                                                 int32_t max_positions, vox_stream_group** out) {
     ARGCHK(n_members >= 1 && n_members <= GROUP_MAX, "n_members %d out of range (1..%d)", n_members, GROUP_MAX); ARGCHK(m && t_embed && out, "null argument");
     for (int i = 0; gains && i < n_members; i++) ARGCHK(std::isfinite(gains[i]), "gain of member %d is not finite", i);
+    for (int i = 0; rates && i < n_members; i++) {      // every rate is checked before anything is allocated
+        ARGCHK(rates[i] > 0, "member %d: bad sample rate 0", i);
+        if (rates[i] != 16000) { ResamplePlan rp; size_t b; int rn; VOXCHK(stream_rate_plan(rates[i], &rp, &b, &rn)); }
+    }
     VOXCHK(ctx_bind(m->ctx));
     const vox_model_cfg& c = m->cfg; vox_ctx* cx = m->ctx; hipStream_t s = cx->stream;
     StreamGeom sg; VOXCHK(stream_geometry(m, enc_capacity_rows, max_positions, GROUP_DEFAULT_POSITIONS, &sg));
@@ -4685,7 +4735,7 @@ extern "C" int32_t vox_stream_group_create(vox_model* m, const float* t_embed, i
     auto A = [&](void** q, size_t nb, bool zero) { if (e == hipSuccess) { e = hipMalloc(q, nb); if (e == hipSuccess) { g->bytes += nb; if (zero) e = hipMemsetAsync(*q, 0, nb, s); } } };
     A((void**)&g->kring, N * g->ring_member * 4, false); A((void**)&g->vring, N * g->ring_member * 4, false); A((void**)&g->dec_k, slab_b, true); A((void**)&g->dec_v, slab_b, true);
     A((void**)&g->samples, N * STREAM_SAMPLE_RING * 4, true); A((void**)&g->ws, ws_b, true); A((void**)&g->tokens, N * (maxp + 2) * 4, true); A((void**)&g->state, N * sizeof(int) * STRM_WORDS, true);
-    A((void**)&g->d_mem, N * sizeof(StreamMember), true); A((void**)&g->d_order, 3 * GROUP_MAX * 4, true);
+    A((void**)&g->d_mem, N * sizeof(StreamMember), true); A((void**)&g->d_order, 3 * GROUP_MAX * 4, true); A((void**)&g->d_ingest, sizeof(GroupIngest), true);
     A((void**)&g->qkv, (size_t)GROUP_MAX * W * 4, true); A((void**)&g->att, (size_t)GROUP_MAX * QD * 4, true); A((void**)&g->logits, (size_t)GROUP_MAX * c.vocab * 4, true);
     A((void**)&g->ssq, (size_t)q4_skinny_resid_xf_parts(D) * 16 * 4, true); A((void**)&g->xf1, xf_bytes(D), true); A((void**)&g->xf2, xf_bytes(QD), true); A((void**)&g->xf3, xf_bytes(c.dec_ffn), true);
     if (e != hipSuccess) { (void)hipGetLastError(); group_release(g); return fail(VOX_ERR_HIP, "allocating the stream group's device state failed: %s", hipGetErrorString(e)); }
@@ -4699,30 +4749,44 @@ extern "C" int32_t vox_stream_group_create(vox_model* m, const float* t_embed, i
     int32_t r = ctx_mel_tables(cx, &g->mel);
     if (r == VOX_OK) r = group_upload_members(g);
     for (int i = 0; i < n_members && r == VOX_OK; i++) r = group_member_seed(g, i);
+    for (int i = 0; rates && i < n_members && r == VOX_OK; i++) r = group_member_set_rate(g, i, rates[i]);
     if (r != VOX_OK) { group_release(g); return r; }
     *out = g; return VOX_OK;
 }
+extern "C" int32_t vox_stream_group_create(vox_model* m, const float* t_embed, int32_t n_members, const float* gains, int32_t enc_capacity_rows, int32_t max_positions,
+                                           vox_stream_group** out) {
+    return vox_stream_group_create_rates(m, t_embed, n_members, gains, nullptr, enc_capacity_rows, max_positions, out);
+}
 extern "C" int32_t vox_stream_group_free(vox_stream_group* g) { group_release(g); return VOX_OK; }
-extern "C" int32_t vox_stream_group_reset(vox_stream_group* g, int32_t member, float gain) {
+// sample_rate 0: the member keeps its rate (vox_stream_group_reset)
+static int32_t group_reset(vox_stream_group* g, int32_t member, float gain, uint32_t sample_rate) {
     ARGCHK(g, "null group"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1); ARGCHK(std::isfinite(gain), "gain is not finite");
     VOXCHK(ctx_bind(g->ctx));
     HIPCHK(hipStreamSynchronize(g->ctx->stream));
+    if (sample_rate) VOXCHK(group_member_set_rate(g, member, sample_rate));      // refused: the member, its rate and its state are as they were
     g->h_mem[member].gain = gain;
     VOXCHK(group_upload_members(g));
     return group_member_seed(g, member);      // (the state block restarts the tap's row count as well)
+}
+extern "C" int32_t vox_stream_group_reset(vox_stream_group* g, int32_t member, float gain) { return group_reset(g, member, gain, 0); }
+extern "C" int32_t vox_stream_group_reset_rate(vox_stream_group* g, int32_t member, float gain, uint32_t sample_rate) {
+    ARGCHK(g, "null group"); ARGCHK(sample_rate > 0, "bad sample rate 0");
+    return group_reset(g, member, gain, sample_rate);
 }
 extern "C" int32_t vox_stream_group_info(const vox_stream_group* g, int32_t member, int64_t out[8]) {
     ARGCHK(g && out, "null argument"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1);
     const GroupMember& me = g->mem[member]; const int R = g->m->cfg.reshape_factor;
     const uint64_t tap_b = g->h_mem[member].tap ? (uint64_t)g->h_mem[member].tap_max * g->m->cfg.vocab * 4 : 0;
+    const uint64_t rate_b = me.rate >= 0 ? (uint64_t)me.in_ring_n * 4 + g->rates[(size_t)me.rate].bytes / (uint64_t)g->rates[(size_t)me.rate].refs : 0;
     out[0] = me.n_pushed; out[1] = me.pos; out[2] = me.ids_out; out[3] = (int64_t)R * me.pos; out[4] = std::min<int64_t>((int64_t)R * me.pos, g->g.cap);
-    out[5] = (int64_t)(g->bytes / (uint64_t)g->n + tap_b);      // the member's share of the group's device state
+    out[5] = (int64_t)(g->bytes / (uint64_t)g->n + tap_b + rate_b);      // the member's share of the group's device state; its own input ring, its share of its rate's matrix
     out[6] = 0; out[7] = (int64_t)me.steps;                      // no engine step; the member's ticks, each one row of an xf_chain step
     return VOX_OK;
 }
 
-// what one entry of a call feeds: the samples, then `right` zeros (the right pad of a finishing member); `done` of the n + right written so far
-struct GroupFeed { int member; const float* p; size_t n, right, done; int target, due; };
+// what one entry of a call feeds: the samples (f32 or 16-bit, at the member's rate), then `right` zeros (the right pad of a finishing member); `done` of the n + right
+// written so far; goal16: the 16 kHz samples the member holds after the call, before the pad
+struct GroupFeed { int member; const void* p; size_t n, right, done; int target, due; bool finish; size_t goal16; };
 // one round: a tick of the first n_r members of the pass's order
 static int32_t group_round(vox_stream_group* g, const StreamWs& w, int n_r) {
     vox_model* m = g->m; const vox_model_cfg& c = m->cfg; hipStream_t s = g->ctx->stream; const int R = c.reshape_factor;
@@ -4735,12 +4799,16 @@ static int32_t group_round(vox_stream_group* g, const StreamWs& w, int n_r) {
     HIPCHK(launch_stream_group_advance(g->logits, c.vocab, g->d_mem, g->d_order, n_r, R, 4 * R, g->g.cap, s));
     return VOX_OK;
 }
-extern "C" int32_t vox_stream_group_advance(vox_stream_group* g, vox_stream_feed* feeds, int32_t n_feeds, int32_t mem_kind) {
+// vox_stream_group_advance and its 16-bit form.  A member at its capture rate follows stream_feed_rate inside the passes: its samples go into its input ring, every
+// block that became complete (finish: everything up to vox_resample_len, blocks clipped at the utterance's end) becomes 16 kHz samples -- ONE stream_group_resample_kernel
+// launch per pass for all fed members, behind ONE stream_group_s16_kernel launch when the samples are 16-bit -- and the rounds see 16 kHz rings only.  A call whose entries
+// fit their rings in one pass runs the rounds of a 16 kHz group fed the resampled pieces.
+static int32_t group_advance(vox_stream_group* g, vox_stream_feed* feeds, int32_t n_feeds, int32_t mem_kind, bool s16) {
     ARGCHK(g && (feeds || n_feeds == 0), "null argument"); ARGCHK(n_feeds >= 0 && n_feeds <= g->n, "%d entries for a group of %d members", n_feeds, g->n);
     ARGCHK(mem_kind == VOX_MEM_HOST || mem_kind == VOX_MEM_DEVICE, "bad mem_kind %d", mem_kind);
     vox_model* m = g->m; const int R = m->cfg.reshape_factor; const long left = g->g.left; hipStream_t s = g->ctx->stream;
     // every check before anything changes: a refused call can be repeated
-    std::vector<GroupFeed> fs; fs.reserve((size_t)n_feeds); unsigned seen = 0;
+    std::vector<GroupFeed> fs; fs.reserve((size_t)n_feeds); unsigned seen = 0; bool any_rate = false;
     for (int k = 0; k < n_feeds; k++) {
         const vox_stream_feed& f = feeds[k];
         ARGCHK(f.member >= 0 && f.member < g->n, "entry %d: member %d out of range (0..%d)", k, f.member, g->n - 1);
@@ -4749,8 +4817,10 @@ extern "C" int32_t vox_stream_group_advance(vox_stream_group* g, vox_stream_feed
         ARGCHK(f.cap >= 0 && (f.out_ids || f.cap == 0), "entry %d: bad output buffer", k); ARGCHK(f.finish == 0 || f.finish == 1, "entry %d: finish must be 0 or 1", k);
         const GroupMember& me = g->mem[f.member];
         ARGCHK(!me.finished, "entry %d: member %d is finished: vox_stream_group_reset starts its next utterance", k, f.member);
-        GroupFeed gf{f.member, f.samples, f.n_samples, 0, 0, 0, 0};
-        const size_t n16 = (size_t)me.n_pushed + f.n_samples;
+        GroupFeed gf{f.member, f.samples, f.n_samples, 0, 0, 0, 0, f.finish != 0, 0};
+        static const ResamplePlan no_plan;
+        size_t n16; VOXCHK(stream_samples16(me.sr, me.rate >= 0 ? g->rates[(size_t)me.rate].rp : no_plan, (size_t)me.n_pushed + f.n_samples, f.finish != 0, &n16));
+        gf.goal16 = n16; any_rate |= me.rate >= 0;
         if (f.finish) {
             vox_pad_cfg pc; vox_pad_cfg_voxtral(&pc); size_t total; VOXCHK(vox_pad_len(n16, &pc, &total));
             const int S = (int)(total / (size_t)stream_spp(R));
@@ -4766,29 +4836,68 @@ extern "C" int32_t vox_stream_group_advance(vox_stream_group* g, vox_stream_feed
         fs.push_back(gf);
     }
     VOXCHK(ctx_bind(g->ctx));
+    const bool staged = s16 && mem_kind == VOX_MEM_HOST;      // host 16-bit samples pass through the group's staging area, STREAM_SAMPLE_RING of them per entry and pass
+    if (staged && !g->s16_stage && !fs.empty()) {
+        const size_t nb = (size_t)g->n * STREAM_SAMPLE_RING * 2;
+        HIPCHK(hipMalloc((void**)&g->s16_stage, nb)); g->bytes += nb;
+    }
     if (m->pw_pend_rows > 0) VOXCHK(pw_sync(m));
     VOXCHK(vox_model_set_t_embed(m, g->t_embed.data()));
     StreamWs w; stream_ws_carve(m, g->n, g->ws, &w);
     for (GroupFeed& f : fs) g->mem[f.member].n_pushed += (int64_t)f.n;
-    // passes: write what fits into every fed member's sample ring, run the rounds that became due, repeat (a push may be larger than the ring)
+    // passes: write what fits into every fed member's rings, run the rounds that became due, repeat (a push may be larger than the rings)
     for (;;) {
-        bool open = false; for (const GroupFeed& f : fs) open |= f.done < f.n + f.right || g->mem[f.member].pos < f.target;
+        bool open = false;
+        for (const GroupFeed& f : fs) open |= f.done < f.n + f.right || g->mem[f.member].n_written < (int64_t)f.goal16 || g->mem[f.member].pos < f.target;
         if (!open) break;
         std::vector<std::pair<int, int>> due;      // (ticks due in this pass, member)
-        bool wrote = false;
-        for (GroupFeed& f : fs) {
-            GroupMember& me = g->mem[f.member]; float* ring = g->samples + (size_t)f.member * STREAM_SAMPLE_RING;
-            size_t room = ring_room16(R, left, me.pos, me.n_written);
-            if (f.done < f.n) {
-                const size_t k = std::min(f.n - f.done, room); StreamSrc src; src.p = f.p; src.mem_kind = mem_kind;
-                VOXCHK(ring_write_f32(s, ring, STREAM_SAMPLE_RING, me.n_written, src, f.done, k)); me.n_written += (int64_t)k; f.done += k; room -= k; wrote |= k > 0;
+        bool wrote = false, any_pcm = false, any_rs = false;
+        GroupIngest* ing = nullptr;
+        if (s16 || any_rate) { g->ingests.emplace_back(); ing = &g->ingests.back(); std::memset((void*)ing, 0, sizeof(GroupIngest)); }
+        // samples [at, at + k) of entry z into ring[(w0 + j) & (ring_n - 1)]: f32 as copies, 16-bit samples as slot z of the pass's conversion launch
+        auto append = [&](size_t z, float* ring, int ring_n, int64_t w0, size_t at, size_t k) -> int32_t {
+            const GroupFeed& f = fs[z];
+            if (!s16) { StreamSrc src; src.p = f.p; src.mem_kind = mem_kind; return ring_write_f32(s, ring, ring_n, w0, src, at, k); }
+            if (k == 0) return VOX_OK;
+            const int16_t* v = (const int16_t*)f.p + at;
+            if (staged) {
+                int16_t* st = g->s16_stage + z * (size_t)STREAM_SAMPLE_RING;
+                HIPCHK(hipMemcpyAsync(st, v, k * 2, hipMemcpyHostToDevice, s)); v = st;
             }
-            if (f.done >= f.n && f.done < f.n + f.right) {
+            ing->pcm[z] = StreamS16{v, (int)k, ring, ring_n - 1, (long)w0}; any_pcm = true;
+            return VOX_OK;
+        };
+        for (size_t z = 0; z < fs.size(); z++) {
+            GroupFeed& f = fs[z]; GroupMember& me = g->mem[f.member]; float* ring = g->samples + (size_t)f.member * STREAM_SAMPLE_RING;
+            size_t room = ring_room16(R, left, me.pos, me.n_written);
+            if (me.rate >= 0) {
+                // the input ring keeps everything from block c_next - 1 on, c_next the block of the next 16 kHz sample to be produced
+                const GroupRate& gr = g->rates[(size_t)me.rate]; const ResamplePlan& p = gr.rp;
+                const int64_t c_next = (me.n_written + p.delay) / p.fft_out, keep_from = std::max<int64_t>(0, c_next - 1) * p.fft_in;
+                size_t k = std::min(f.n - std::min(f.done, f.n), (size_t)me.in_ring_n - (size_t)std::max<int64_t>(0, me.in_written - keep_from));
+                if (staged) k = std::min(k, (size_t)STREAM_SAMPLE_RING);
+                VOXCHK(append(z, me.in_ring, me.in_ring_n, me.in_written, f.done, k)); me.in_written += (int64_t)k; f.done += k; wrote |= k > 0;
+                const int64_t have16 = f.finish && f.done >= f.n ? (int64_t)f.goal16 : stream_avail16(p, me.in_written);
+                const size_t count = std::min((size_t)std::max<int64_t>(0, have16 - me.n_written), room);
+                if (count > 0) {
+                    ing->rs[z] = StreamIngest{me.in_ring, me.in_ring_n - 1, (long)me.in_written, gr.At, (int)p.fft_in, (int)p.fft_out, (int)p.delay, ring, (long)me.n_written, (int)count};
+                    me.n_written += (int64_t)count; room -= count; any_rs = true; wrote = true;
+                }
+            } else if (f.done < f.n) {
+                const size_t k = std::min(f.n - f.done, room);
+                VOXCHK(append(z, ring, STREAM_SAMPLE_RING, me.n_written, f.done, k)); me.n_written += (int64_t)k; f.done += k; room -= k; wrote |= k > 0;
+            }
+            if (f.done >= f.n && f.done < f.n + f.right && me.n_written >= (int64_t)f.goal16) {      // the right pad, behind the utterance's last 16 kHz sample
                 const size_t k = std::min(f.n + f.right - f.done, room);
                 VOXCHK(ring_write_f32(s, ring, STREAM_SAMPLE_RING, me.n_written, StreamSrc{}, 0, k)); me.n_written += (int64_t)k; f.done += k; wrote |= k > 0;
             }
             const int avail = (int)std::min<long>(f.target, stream_positions(left, R, me.n_written));
             if (avail > me.pos) due.emplace_back(avail - me.pos, f.member);
+        }
+        if (any_pcm || any_rs) {      // the pass's ingest, in front of its rounds: one upload, the conversion, then the resampling (which reads what the conversion wrote)
+            HIPCHK(hipMemcpyAsync(g->d_ingest, ing, sizeof(GroupIngest), hipMemcpyHostToDevice, s));
+            if (any_pcm) HIPCHK(launch_stream_group_s16(g->d_ingest->pcm, ing->pcm, (int)fs.size(), s));
+            if (any_rs) HIPCHK(launch_stream_group_resample(g->d_ingest->rs, ing->rs, (int)fs.size(), STREAM_SAMPLE_RING - 1, s));
         }
         if (!wrote && due.empty()) return fail(VOX_ERR_INVALID, "internal: stream group stalled");
         if (due.empty()) continue;
@@ -4806,9 +4915,15 @@ extern "C" int32_t vox_stream_group_advance(vox_stream_group* g, vox_stream_feed
     for (size_t k = 0; k < fs.size(); k++) if (fs[k].due > 0)
         HIPCHK(hipMemcpyAsync(feeds[k].out_ids, g->h_mem[fs[k].member].tokens + VOX_PREFIX_TOKENS + g->mem[fs[k].member].ids_out, (size_t)fs[k].due * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));      // the call's one synchronisation: every fed member's ids land
-    g->orders.clear();
+    g->orders.clear(); g->ingests.clear();
     for (size_t k = 0; k < fs.size(); k++) { GroupMember& me = g->mem[fs[k].member]; me.ids_out += fs[k].due; feeds[k].n_ids = fs[k].due; if (feeds[k].finish) me.finished = true; }
     return VOX_OK;
+}
+extern "C" int32_t vox_stream_group_advance(vox_stream_group* g, vox_stream_feed* feeds, int32_t n_feeds, int32_t mem_kind) {
+    return group_advance(g, feeds, n_feeds, mem_kind, false);
+}
+extern "C" int32_t vox_stream_group_advance_s16(vox_stream_group* g, vox_stream_feed* feeds, int32_t n_feeds, int32_t mem_kind) {
+    return group_advance(g, feeds, n_feeds, mem_kind, true);
 }
 extern "C" int32_t vox_debug_stream_group_tap_arm(vox_stream_group* g, int32_t member, int32_t max_rows) {
     ARGCHK(g, "null group"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1);

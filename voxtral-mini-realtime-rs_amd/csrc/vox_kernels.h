@@ -169,9 +169,10 @@ hipError_t launch_attn_decode(const AttnParams& p, int hd, int max_seq, hipStrea
 // single sequence: attention + the wo linear in one launch; acc[wo.N] (int64, zero on entry) receives the product in 2^-32 fixed point (consumer: PRO_RMS_MUL_SUM)
 bool attn_wo_supported(const AttnParams& p, const Q4W& wo, int hd, int max_seq);
 hipError_t launch_attn_wo(const AttnParams& p, const Q4W& wo, long long* acc, int max_seq, hipStream_t s);
-// host-side launch counts of the attention kernels and of the single-stream decode engine, by form (vox_debug_attn_launches: tests assert which path a call took)
+// host-side launch counts of the attention kernels and of the single-stream decode engine, by form (vox_debug_attn_launches: tests assert which path a call took);
+// behind them, in slots of their own, the two resampling ingest kernels of the live sessions (a group's pass-wide one, a solo stream's)
 enum AttnForm { ATTN_FORM_PREFILL_SMALL, ATTN_FORM_PREFILL_MFMA, ATTN_FORM_PREFILL_F32, ATTN_FORM_DECODE, ATTN_FORM_DECODE_SPEC, ATTN_FORM_DECODE_GQA, ATTN_FORM_WO,
-                ATTN_FORM_ENGINE, ATTN_FORM_STREAM_RING, ATTN_FORM_COUNT };
+                ATTN_FORM_ENGINE, ATTN_FORM_STREAM_RING, ATTN_FORM_GROUP_RESAMPLE, ATTN_FORM_STREAM_RESAMPLE, ATTN_FORM_COUNT };
 void attn_form_note(AttnForm f);
 void attn_form_counts(unsigned long long out[ATTN_FORM_COUNT]);
 // host-side launch counts of the linear kernels, by form (vox_debug_gemm_launches: tests assert which kernel a shape ran; counters only, nothing is dispatched by them).
@@ -390,6 +391,19 @@ hipError_t launch_stream_resample(const float* in_ring, int in_mask, long n_in, 
                                   hipStream_t s);
 // 16-bit PCM into a stream's f32 ring: ring[(w0 + k) & mask] = float(src[k]) / 32768 for k < count <= mask + 1 (src: device memory)
 hipError_t launch_stream_s16(const short* src, int count, float* ring, int mask, long w0, hipStream_t s);
+// ---- the ingest of a stream group's pass: both kernels above with a slot dimension, ONE launch for every fed member.  Slot z reads desc[z] (device array; `host`: the
+// same n <= 16 descriptors on the host, which the launch validates: power-of-two masks, counts within the ring); slots may have count 0, a launch whose counts are all 0
+// is skipped.
+struct StreamIngest {                     // launch_stream_resample's arguments for one member; the 16 kHz ring mask is the launch's
+    const float* in_ring; int in_mask;    // the member's input-rate ring
+    long n_in;                            // input samples that exist (blocks are clipped there)
+    const float* At; int fft_in, fft_out, delay;      // its rate's block matrix and plan
+    float* out_ring;                      // its 16 kHz ring
+    long i0; int count;                   // 16 kHz samples [i0, i0 + count)
+};
+hipError_t launch_stream_group_resample(const StreamIngest* desc, const StreamIngest* host, int n, int out_mask, hipStream_t s);
+struct StreamS16 { const short* src; int count; float* ring; int mask; long w0; };      // launch_stream_s16's arguments for one member
+hipError_t launch_stream_group_s16(const StreamS16* desc, const StreamS16* host, int n, hipStream_t s);
 // one encoder layer's attention for the round's n x M rows (M <= 8 per session, slot z's rows at z * M) against each session's own K / V ring: RoPE on q and k at the
 // session's absolute stream position, k / v appended at position % cap, query m attends the keys j <= position_m, position_m - j <= window in ascending order of j (the
 // ring changes addresses, not the order).  cap > window + M.

@@ -4247,6 +4247,7 @@ hipError_t launch_stream_resample(const float* in_ring, int in_mask, long n_in, 
     if ((in_mask & (in_mask + 1)) || (out_mask & (out_mask + 1)) || in_mask < 0 || out_mask < 0 || fft_in <= 0 || fft_out <= 0 || delay < 0 || i0 < 0 || n_in < 0 || count > out_mask + 1)
         return hipErrorInvalidValue;
     stream_resample_kernel<<<dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s>>>(in_ring, in_mask, n_in, At, fft_in, fft_out, delay, out_ring, out_mask, i0, count);
+    attn_form_note(ATTN_FORM_STREAM_RESAMPLE);
     return hipGetLastError();
 }
 // 16-bit PCM into a stream's f32 ring: ring[(w0 + k) & mask] = float(src[k]) / 32768 (the mono 16-bit scale of audio/io.rs:110-113; a power of two: exact in f32)
@@ -4259,6 +4260,68 @@ hipError_t launch_stream_s16(const short* src, int count, float* ring, int mask,
     if (count <= 0) return hipSuccess;
     if ((mask & (mask + 1)) || mask < 0 || w0 < 0 || count > mask + 1) return hipErrorInvalidValue;
     stream_s16_kernel<<<dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s>>>(src, count, ring, mask, w0);
+    return hipGetLastError();
+}
+// the two ingest kernels with a slot dimension (a stream group's pass): slot blockIdx.y works through desc[blockIdx.y], as the tick kernels work through StreamMember.
+// The grid is sized by the largest count of the pass; lanes beyond their slot's count (a slot with count 0: all of them) do nothing.
+// stream_group_resample_kernel is stream_resample_kernel term for term -- the same two fmaf chains in ascending n, the same a0 + a1, the same clipping at n_in -- so
+// every sample has vox_resample's bits whichever of the two produced it; the plans (At, fft_in, fft_out, delay) differ from slot to slot.
+__global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_group_resample_kernel(const StreamIngest* __restrict__ desc, int out_mask) {
+    const StreamIngest& d = desc[blockIdx.y];
+    const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (k >= d.count) return;
+    const float* __restrict__ in_ring = d.in_ring; const float* __restrict__ At = d.At;
+    const int fft_in = d.fft_in, fft_out = d.fft_out; const long in_mask = (long)d.in_mask, n_in = d.n_in;
+    const long i = d.i0 + k;
+    const long j = i + d.delay, c = j / fft_out; const int m = (int)(j - c * fft_out);
+    const int ld = 2 * fft_out;
+    float a0 = 0.f, a1 = 0.f;
+    {
+        const long base = c * fft_in; const int cnt = (int)max(0L, min((long)fft_in, n_in - base));
+        const float* ap = At + m;
+        for (int n = 0; n < cnt; n++) a0 = fmaf(in_ring[(base + n) & in_mask], ap[(size_t)n * ld], a0);
+    }
+    if (c > 0) {
+        const long base = (c - 1) * fft_in; const int cnt = (int)max(0L, min((long)fft_in, n_in - base));
+        const float* ap = At + fft_out + m;
+        for (int n = 0; n < cnt; n++) a1 = fmaf(in_ring[(base + n) & in_mask], ap[(size_t)n * ld], a1);
+    }
+    d.out_ring[i & (long)out_mask] = a0 + a1;
+}
+hipError_t launch_stream_group_resample(const StreamIngest* desc, const StreamIngest* host, int n, int out_mask, hipStream_t s) {
+    if (!desc || !host || n < 1 || n > 16 || out_mask < 0 || (out_mask & (out_mask + 1))) return hipErrorInvalidValue;
+    int most = 0;
+    for (int z = 0; z < n; z++) {
+        const StreamIngest& d = host[z];
+        if (d.count < 0 || d.count > out_mask + 1) return hipErrorInvalidValue;
+        if (d.count == 0) continue;
+        if (!d.in_ring || !d.At || !d.out_ring || d.in_mask < 0 || (d.in_mask & (d.in_mask + 1)) || d.fft_in <= 0 || d.fft_out <= 0 || d.delay < 0 || d.i0 < 0 || d.n_in < 0)
+            return hipErrorInvalidValue;
+        most = max(most, d.count);
+    }
+    if (most == 0) return hipSuccess;
+    stream_group_resample_kernel<<<dim3((unsigned)((most + 255) / 256), n), dim3(256), 0, s>>>(desc, out_mask);
+    attn_form_note(ATTN_FORM_GROUP_RESAMPLE);
+    return hipGetLastError();
+}
+__global__ __launch_bounds__(256) void stream_group_s16_kernel(const StreamS16* __restrict__ desc) {
+    const StreamS16& d = desc[blockIdx.y];
+    const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (k >= d.count) return;
+    d.ring[(d.w0 + k) & (long)d.mask] = (float)d.src[k] * (1.0f / 32768.0f);
+}
+hipError_t launch_stream_group_s16(const StreamS16* desc, const StreamS16* host, int n, hipStream_t s) {
+    if (!desc || !host || n < 1 || n > 16) return hipErrorInvalidValue;
+    int most = 0;
+    for (int z = 0; z < n; z++) {
+        const StreamS16& d = host[z];
+        if (d.count < 0) return hipErrorInvalidValue;
+        if (d.count == 0) continue;
+        if (!d.src || !d.ring || d.mask < 0 || (d.mask & (d.mask + 1)) || d.w0 < 0 || d.count > d.mask + 1) return hipErrorInvalidValue;
+        most = max(most, d.count);
+    }
+    if (most == 0) return hipSuccess;
+    stream_group_s16_kernel<<<dim3((unsigned)((most + 255) / 256), n), dim3(256), 0, s>>>(desc);
     return hipGetLastError();
 }
 

@@ -497,43 +497,75 @@ class LiveStream:
 
 class LiveStreamGroup:
     """A stream group (vox_stream_group): up to 16 live sessions on one model advanced together, every weight matrix read once per tick for all members that have a tick
-    due.  Members are numbered 0 .. n_members-1; each has its own gain and follows stream_schedule on its own sample count.  16 kHz float32 samples."""
+    due.  Members are numbered 0 .. n_members-1; each has its own gain and its own sample rate (sample_rates, reset(sample_rate=); 16 kHz unless set) and follows
+    stream_schedule(..., sample_rate=its rate) on its own sample count.  Samples are float32 or 16-bit PCM at the member's rate."""
+    _rates = None      # {member: rate} of the members at another rate than 16 kHz; a member without an entry is fed 16 kHz
 
-    def __init__(self, model, t_embed, n_members, gains=None, enc_capacity_rows=0, max_positions=0):
-        self.model = model; self.h = C.c_void_p(); self.n_members = int(n_members); self._tap_max = {}
+    def __init__(self, model, t_embed, n_members, gains=None, enc_capacity_rows=0, max_positions=0, sample_rates=None):
+        self.model = model; self.h = C.c_void_p(); self.n_members = int(n_members); self._tap_max = {}; self._rates = {}
         g = None if gains is None else _f32(gains).reshape(-1)
         if g is not None and g.size != self.n_members:
             raise ValueError(f"{g.size} gains for {self.n_members} members")
-        check(lib().vox_stream_group_create(model.h, _ptr(_f32(t_embed).reshape(-1)), self.n_members, None if g is None else _ptr(g), int(enc_capacity_rows),
-                                            int(max_positions), C.byref(self.h)))
+        args = (model.h, _ptr(_f32(t_embed).reshape(-1)), self.n_members, None if g is None else _ptr(g))
+        if sample_rates is None:
+            check(lib().vox_stream_group_create(*args, int(enc_capacity_rows), int(max_positions), C.byref(self.h)))
+        else:
+            r = np.ascontiguousarray([int(v) for v in sample_rates], dtype=np.uint32)
+            if r.size != self.n_members:
+                raise ValueError(f"{r.size} sample rates for {self.n_members} members")
+            check(lib().vox_stream_group_create_rates(*args, _ptr(r), int(enc_capacity_rows), int(max_positions), C.byref(self.h)))
+            self._rates = {k: int(v) for k, v in enumerate(r) if int(v) != 16000}
         model._caches.add(self)
 
-    def advance(self, feeds, finish=(), device=False) -> dict:
-        """One call for any subset of members: feeds {member: samples} (float32 arrays; device=True: {member: (device pointer, count)}), finish: the members whose
-        utterance ends with these samples (a member named there alone is fed no samples) -> {member: the ids that became due}."""
+    def sample_rate(self, member) -> int:
+        """The rate of what `member` is fed."""
+        return (self._rates or {}).get(int(member), 16000)
+
+    def advance(self, feeds, finish=(), device=False, dtype=None) -> dict:
+        """One call for any subset of members: feeds {member: samples at the member's rate} (arrays; device=True: {member: (device pointer, count)} of float32 or, with
+        dtype="s16", of 16-bit PCM), finish: the members whose utterance ends with these samples (a member named there alone is fed no samples) -> {member: the ids that
+        became due}.  Host arrays: when every fed array is int16 the call is the 16-bit one (vox_stream_group_advance_s16); anything else goes in as float32, int16
+        arrays of a mixed call as v / 32768 (exact)."""
+        if dtype not in (None, "f32", "s16") or (dtype is not None and not device):
+            raise ValueError(f"dtype {dtype!r}: a device pointer holds 'f32' or 's16' samples")
         fin = set(int(k) for k in finish); entries = {int(k): v for k, v in feeds.items()}
+        is16 = lambda v: isinstance(v, np.ndarray) and v.dtype == np.int16
+        s16 = dtype == "s16" if device else bool(entries) and all(is16(v) for v in entries.values())
         for k in fin:
-            entries.setdefault(k, (0, 0) if device else np.zeros(0, np.float32))
+            entries.setdefault(k, (0, 0) if device else np.zeros(0, np.int16 if s16 else np.float32))
         arr = (_lib.StreamFeed * max(len(entries), 1))(); keep = []
         for e, (k, v) in zip(arr, entries.items()):
             if device:
                 ptr, n = int(v[0]) or None, int(v[1])
             else:
-                x = _f32(v).reshape(-1); keep.append(x); ptr, n = (x.ctypes.data if x.size else None), x.size
+                if s16:
+                    x = np.ascontiguousarray(v).reshape(-1)
+                else:
+                    x = (v.astype(np.float32) / np.float32(32768) if is16(v) else _f32(v)).reshape(-1)
+                keep.append(x); ptr, n = (x.ctypes.data if x.size else None), x.size
             if not 0 <= k < self.n_members:
                 raise ValueError(f"member {k} of a group of {self.n_members}")
             inf = self.info(k)
-            due = stream_schedule(inf["samples"] + n, k in fin)[1] - inf["ids"]      # each cap comes from the schedule
+            due = stream_schedule(inf["samples"] + n, k in fin, self.sample_rate(k))[1] - inf["ids"]      # each cap comes from the member's schedule
             ids = np.zeros(max(due, 1), dtype=np.int32); keep.append(ids)
             e.member = k; e.finish = 1 if k in fin else 0; e.samples = ptr; e.n_samples = n; e.out_ids = ids.ctypes.data; e.cap = ids.size; e.n_ids = 0
-        check(lib().vox_stream_group_advance(self.h, arr, len(entries), 1 if device else 0))
+        fn = lib().vox_stream_group_advance_s16 if s16 else lib().vox_stream_group_advance
+        check(fn(self.h, arr, len(entries), 1 if device else 0))
         out = {}
         for e in arr[:len(entries)]:
             out[e.member] = np.ctypeslib.as_array((C.c_int32 * max(e.cap, 1)).from_address(e.out_ids))[:e.n_ids].copy()
         return out
 
-    def reset(self, member, gain=1.0):
-        check(lib().vox_stream_group_reset(self.h, int(member), float(gain)))
+    def reset(self, member, gain=1.0, sample_rate=None):
+        """The member's next connection; sample_rate: what it delivers (None: the member keeps its rate)."""
+        if sample_rate is None:
+            check(lib().vox_stream_group_reset(self.h, int(member), float(gain)))
+            return
+        check(lib().vox_stream_group_reset_rate(self.h, int(member), float(gain), int(sample_rate)))
+        rates = dict(self._rates or {}); rates.pop(int(member), None)
+        if int(sample_rate) != 16000:
+            rates[int(member)] = int(sample_rate)
+        self._rates = rates
 
     def info(self, member):
         v = (C.c_int64 * 8)(); check(lib().vox_stream_group_info(self.h, int(member), v))
@@ -735,10 +767,11 @@ class Q4VoxtralModel:
         (a stream has no file peak: 0.95 / max|x| of a known file reproduces transcribe_audio).  sample_rate: the rate of the samples that will be pushed."""
         return LiveStream(self, t_embed, gain, enc_capacity_rows, max_positions, sample_rate)
 
-    def create_stream_group(self, t_embed, n_members, gains=None, enc_capacity_rows=0, max_positions=0) -> LiveStreamGroup:
+    def create_stream_group(self, t_embed, n_members, gains=None, enc_capacity_rows=0, max_positions=0, sample_rates=None) -> LiveStreamGroup:
         """Up to 16 live sessions advanced together (vox_stream_group_create): advance({member: samples}, finish=()) -> {member: ids}, reset(member, gain), info(member),
-        close().  gains: one per member (None: 1.0 each); max_positions 0: 2048 decoder positions per member (the group's decoder cache does not grow)."""
-        return LiveStreamGroup(self, t_embed, n_members, gains, enc_capacity_rows, max_positions)
+        close().  gains: one per member (None: 1.0 each); max_positions 0: 2048 decoder positions per member (the group's decoder cache does not grow);
+        sample_rates: what each member is fed (None: 16 kHz each; vox_stream_group_create_rates)."""
+        return LiveStreamGroup(self, t_embed, n_members, gains, enc_capacity_rows, max_positions, sample_rates)
 
     def transcribe_batch(self, samples_list, t_embed, device_ptrs=None, n_samples=None, norm_group=None, tap_units=None):
         """Batched whole-path transcription of independent utterances (<= 4096; wider than 16: continuous batching over decode slots): list of float32 sample arrays
