@@ -568,6 +568,13 @@ int32_t vox_stream_group_free(vox_stream_group* g);
 /* vox_debug_stream_tap_* for one member (the rows are copied by the tick's last kernel; a reset of the member starts the count again) */
 int32_t vox_debug_stream_group_tap_arm(vox_stream_group* g, int32_t member, int32_t max_rows);
 int32_t vox_debug_stream_group_tap_fetch(vox_stream_group* g, int32_t member, float* out, int32_t* rows);
+/* The live sessions' feed planner on its own (tests): host arithmetic only -- no context, no device, no model.  A fresh session fed at sample_rate (4 encoder rows per
+ * position, the Voxtral left pad, no position limit to speak of) takes the calls (n_samples[c], finish[c] 0 / 1) exactly as vox_stream_push / _finish and a group's advance
+ * plan and pass them, every due tick taken as run.  One row of five words per pass: call index, input samples appended, 16 kHz samples that entered the 16 kHz ring (a
+ * 16 kHz session: the appended ones), right-pad zeros written, ticks that became due.  pass_cap: most input samples per pass (0: no cap; a group's 16-bit staging: 65536).
+ * A call after a finish, a bad rate or more than max_rows passes are refused. */
+int32_t vox_debug_stream_feed_passes(uint32_t sample_rate, const size_t* n_samples, const int32_t* finish, int32_t n_calls, size_t pass_cap, int64_t* rows, int32_t max_rows,
+                                     int32_t* n_rows);
 
 #ifdef __cplusplus
 }

@@ -183,6 +183,7 @@ SIGNATURES = {
     "vox_stream_group_create_rates": (i32, [vp, vp, i32, vp, vp, i32, i32, P(vp)]),
     "vox_stream_group_reset_rate": (i32, [vp, i32, f32, u32]),
     "vox_stream_group_advance_s16": (i32, [vp, vp, i32, i32]),
+    "vox_debug_stream_feed_passes": (i32, [u32, P(sz), P(i32), i32, sz, P(i64), i32, P(i32)]),
 }
 
 _LIB = None

@@ -4106,11 +4106,21 @@ extern "C" int32_t vox_debug_encode_batch(vox_model* m, int32_t n, const float* 
 // Ingest at the capture rate (vox_stream_create_rate): input-rate samples go into a ring of their own, stream_resample_kernel turns every block that
 // is complete into 16 kHz samples of the ring above (vox_resample's bits: the same matrix, the same sums), the ticks see 16 kHz samples only.  16-bit PCM
 // (vox_stream_push_s16) is converted on the device on its way into whichever ring the stream is fed through.
+// What a call appends, resamples, pads and ticks, pass by pass, is decided by feed_plan / feed_pass on the stream's FeedState -- the planner a group's members share.
 // ------------------------------------------------------------------------------------------------
 static const int STREAM_SAMPLE_RING = 1 << 16;      // samples held on the device (a tick reads 160 (4 R + 2) + 400 of them)
 static const int STREAM_KEEP_ROWS = 1024;           // adapter rows kept for the re-run of unverified engine steps; a push verifies at least this often
 static const int STREAM_FEED_CHUNK = 1 << 15;       // input-rate samples a rate stream's ring takes beyond two blocks; 16-bit samples of the host staging buffer
 static const int STREAM_IN_RING_MAX = 1 << 20;      // largest input ring (samples): rate pairs whose two blocks + a feed chunk do not fit are refused at create
+// The host mirror of ONE live session's feed -- a solo vox_stream's, a group member's: everything feed_plan and feed_pass below read and advance.
+struct FeedState {
+    uint32_t sr = 16000; ResamplePlan rp; float* At = nullptr;      // the rate the caller feeds at; at any rate but 16000 a COPY of its plan and the block matrix in use
+    float* in_ring = nullptr; int in_ring_n = 0;                    // ... and the session's own input-rate ring (a power of two: stream_rate_plan)
+    int64_t n_pushed = 0, n_written = 0;      // samples the caller gave (at sr); samples in the 16 kHz ring (after finish: + the right pad)
+    int64_t in_written = 0;                   // input-rate samples copied into the input ring so far
+    int pos = 0, ids_out = 0; bool finished = false;      // decoder position of the next tick; ids handed to the caller; the utterance has ended (until a reset)
+    void restart(int PC) { n_pushed = n_written = in_written = 0; pos = PC; ids_out = 0; finished = false; }      // create / reset: the session starts behind the prefix
+};
 struct vox_stream {
     vox_model* m = nullptr; vox_ctx* ctx = nullptr;
     std::vector<float> t_embed; float gain = 1.0f;
@@ -4121,13 +4131,9 @@ struct vox_stream {
     int *tokens = nullptr, *state = nullptr;
     StreamMember* d_mem = nullptr; int* d_order = nullptr;      // the round of one: this stream's descriptor and the order {0} (one allocation)
     MelTables mel{};
-    // input at the capture rate (sr != 16000): the plan, the stream's OWN block matrix (the context's is vox_resample's and goes when the rate pair changes), the input ring
-    uint32_t sr = 16000; ResamplePlan rp; float *rs_matrix = nullptr, *in_ring = nullptr; int in_ring_n = 0;
+    FeedState feed;                    // the session's host mirror (rate, rings' fill, position, ids handed out); feed.At is the stream's OWN block matrix (freed with it)
     int16_t* s16_stage = nullptr;      // host 16-bit pushes: STREAM_FEED_CHUNK samples of device staging, allocated at the first one
-    // host mirror of the session
-    int64_t n_pushed = 0, n_written = 0;      // samples the caller gave (at the input rate); samples in the 16 kHz ring (after finish: + the right pad)
-    int64_t in_written = 0;                   // rate streams: input samples copied into the input ring so far
-    int pos = 0, ids_out = 0, verified_pos = 0, verified_tap_rows = 0; bool finished = false, eng_unverified = false;
+    int verified_pos = 0, verified_tap_rows = 0; bool eng_unverified = false;
     uint64_t eng_steps = 0, op_steps = 0, verified_eng_steps = 0, verified_op_steps = 0, bytes = 0;
     EngBinding eng;      // the decode engine's layer table for the stream's cache, its argmax partials (256), the pinned host copy of its error word
     float* tap = nullptr; int tap_max = 0, tap_rows = 0;
@@ -4234,7 +4240,7 @@ static int32_t stream_load_initial(vox_stream* st) {
     // uploaded behind the seed's copies and in front of its synchronisation, so that the first step finds its cache bound
     VOXCHK(stream_seed(m, st->t_embed.data(), st->RC, st->PC, st->cap, st->kring, st->vring, st->dec, st->tokens, st->state, st->h_state,
                        [&]() -> int32_t { HIPCHK(engine_tab_enqueue(m, st->eng, st->dec)); return VOX_OK; }));
-    st->n_pushed = st->n_written = st->in_written = 0; st->pos = st->verified_pos = st->PC; st->ids_out = 0; st->finished = false; st->eng_unverified = false;
+    st->feed.restart(st->PC); st->verified_pos = st->PC; st->eng_unverified = false;
     st->eng_steps = st->op_steps = st->verified_eng_steps = st->verified_op_steps = 0; st->tap_rows = st->verified_tap_rows = 0; st->ftap_ticks = 0;
     return VOX_OK;
 }
@@ -4244,7 +4250,7 @@ static void stream_release(vox_stream* st) {
     (void)hipSetDevice(st->ctx->device); (void)hipStreamSynchronize(st->ctx->stream);      // never dereferences st->m: a stream may not outlive its model, but freeing it late must not crash
     cache_release(st->dec);
     for (void* p : {(void*)st->kring, (void*)st->vring, (void*)st->samples, (void*)st->audio_keep, (void*)st->ws, (void*)st->tokens, (void*)st->state, (void*)st->tap, (void*)st->ftap_mel, (void*)st->ftap_conv,
-                    (void*)st->rs_matrix, (void*)st->in_ring, (void*)st->s16_stage, (void*)st->d_mem}) if (p) (void)hipFree(p);
+                    (void*)st->feed.At, (void*)st->feed.in_ring, (void*)st->s16_stage, (void*)st->d_mem}) if (p) (void)hipFree(p);
     binding_release(st->eng);
     delete st;
 }
@@ -4288,7 +4294,7 @@ static int32_t stream_create(vox_model* m, const float* t_embed, float gain, int
     StreamGeom g; VOXCHK(stream_geometry(m, enc_capacity_rows, max_positions, INT32_MAX, &g));
     VOXCHK(enc_stream_rope_ensure(m));
     vox_stream* st = new vox_stream(); st->m = m; st->ctx = cx; st->t_embed.assign(t_embed, t_embed + c.dec_dim); st->gain = gain; st->cap = g.cap; st->max_pos = g.max_pos; st->RC = g.RC; st->PC = g.PC;
-    st->sr = sample_rate; st->rp = rp; st->in_ring_n = in_ring_n; st->left = g.left;
+    st->feed.sr = sample_rate; st->feed.rp = rp; st->feed.in_ring_n = in_ring_n; st->left = g.left;
     const int DD = c.dec_dim, maxp = g.max_pos;
     st->ring_layer = (size_t)c.enc_heads * g.cap * c.enc_head_dim;
     const size_t ring_b = (size_t)c.enc_layers * st->ring_layer * 4, keep_b = (size_t)STREAM_KEEP_ROWS * DD * 4, ws_b = stream_ws_carve(m, 1, nullptr, nullptr) * 4;
@@ -4297,7 +4303,7 @@ static int32_t stream_create(vox_model* m, const float* t_embed, float gain, int
     A((void**)&st->kring, ring_b); A((void**)&st->vring, ring_b); A((void**)&st->samples, (size_t)STREAM_SAMPLE_RING * 4); A((void**)&st->audio_keep, keep_b);
     A((void**)&st->ws, ws_b); A((void**)&st->tokens, (size_t)(maxp + 2) * 4); A((void**)&st->state, sizeof(int) * STRM_WORDS); A((void**)&st->d_mem, sizeof(StreamMember) + 16);
     if (e == hipSuccess) e = binding_alloc(m, st->eng, &st->bytes);      // (here, not at the first step: the footprint a stream reports does not depend on what it has done)
-    if (in_ring_n) A((void**)&st->in_ring, (size_t)in_ring_n * 4);
+    if (in_ring_n) A((void**)&st->feed.in_ring, (size_t)in_ring_n * 4);
     if (e != hipSuccess) { (void)hipGetLastError(); stream_release(st); return fail(VOX_ERR_HIP, "allocating the stream's device state failed: %s", hipGetErrorString(e)); }
     st->d_order = reinterpret_cast<int*>(st->d_mem + 1);
     struct { StreamMember me; int order[4]; } desc{};      // the stream's descriptor never changes; uploaded behind stream_load_initial's synchronisation at the latest
@@ -4306,7 +4312,7 @@ static int32_t stream_create(vox_model* m, const float* t_embed, float gain, int
     if (r == VOX_OK && hipMemsetAsync(st->samples, 0, (size_t)STREAM_SAMPLE_RING * 4, cx->stream) != hipSuccess) r = fail(VOX_ERR_HIP, "hipMemsetAsync failed");
     if (r == VOX_OK && hipMemsetAsync(st->ws, 0, ws_b, cx->stream) != hipSuccess) r = fail(VOX_ERR_HIP, "hipMemsetAsync failed");      // (the pad frame and pad row are read, their products are not)
     if (r == VOX_OK && hipMemcpyAsync(st->d_mem, &desc, sizeof(StreamMember) + 16, hipMemcpyHostToDevice, cx->stream) != hipSuccess) r = fail(VOX_ERR_HIP, "hipMemcpyAsync failed");
-    if (r == VOX_OK && in_ring_n) { r = resample_matrix_build(cx, rp, rs_bytes, &st->rs_matrix); if (r == VOX_OK) st->bytes += rs_bytes; }
+    if (r == VOX_OK && in_ring_n) { r = resample_matrix_build(cx, rp, rs_bytes, &st->feed.At); if (r == VOX_OK) st->bytes += rs_bytes; }
     if (r == VOX_OK) r = stream_load_initial(st);
     if (r != VOX_OK) { (void)hipStreamSynchronize(cx->stream); stream_release(st); return r; }
     *out = st; return VOX_OK;
@@ -4328,7 +4334,7 @@ extern "C" int32_t vox_stream_info(const vox_stream* st, int64_t out[8]) {
     ARGCHK(st && out, "null argument");
     const int R = st->m->cfg.reshape_factor;
     const uint64_t dec_b = st->dec ? 2 * (uint64_t)st->m->cfg.dec_layers * st->dec->layer_stride * 4 : 0, tap_b = (st->tap ? (uint64_t)st->tap_max * st->m->cfg.vocab * 4 : 0) + (st->ftap_mel ? (uint64_t)st->ftap_max * R * (4 * st->m->cfg.n_mels + st->m->cfg.enc_dim) * 4 : 0);
-    out[0] = st->n_pushed; out[1] = st->pos; out[2] = st->ids_out; out[3] = (int64_t)R * st->pos; out[4] = std::min<int64_t>((int64_t)R * st->pos, st->cap);
+    out[0] = st->feed.n_pushed; out[1] = st->feed.pos; out[2] = st->feed.ids_out; out[3] = (int64_t)R * st->feed.pos; out[4] = std::min<int64_t>((int64_t)R * st->feed.pos, st->cap);
     out[5] = (int64_t)(st->bytes + dec_b + tap_b); out[6] = (int64_t)st->eng_steps; out[7] = (int64_t)st->op_steps;
     return VOX_OK;
 }
@@ -4337,7 +4343,7 @@ extern "C" int32_t vox_stream_info(const vox_stream* st, int64_t out[8]) {
 // words stay).  logits_row: where the step's f32 logits go (the tap), or null.
 static int32_t stream_decode_step(vox_stream* st, float* h, float* logits_row, int enc_rows) {
     vox_model* m = st->m; hipStream_t s = st->ctx->stream; vox_cache* kc = st->dec;
-    ARGCHK(kc->len == st->pos && st->pos < kc->max_seq, "internal: stream decoder cache at %d, position %d of %d", kc->len, st->pos, kc->max_seq);
+    ARGCHK(kc->len == st->feed.pos && st->feed.pos < kc->max_seq, "internal: stream decoder cache at %d, position %d of %d", kc->len, st->feed.pos, kc->max_seq);
     int* pos_word = st->state + STRM_POS;
     if (engine_bind(m, st->eng, kc)) {      // one launch: the layers against the stream's cache + final norm + lm_head (argmax partials, logits on request)
         VOXCHK(engine_take_serials(m, 1, s));
@@ -4350,7 +4356,7 @@ static int32_t stream_decode_step(vox_stream* st, float* h, float* logits_row, i
         HIPCHK(launch_stream_advance(m->d_part_val, m->d_part_idx, m->n_parts, st->tokens, st->state, enc_rows, 4 * enc_rows, st->cap, s));
         st->op_steps++;
     }
-    kc->len = ++st->pos;
+    kc->len = ++st->feed.pos;
     return VOX_OK;
 }
 static float* stream_tap_row(vox_stream* st) {
@@ -4370,12 +4376,12 @@ static int32_t stream_settle(vox_stream* st, bool* reran) {      // behind that 
     st->eng_unverified = false;
     if (e) {
         st->eng.err_word[0] = 0u; VOXCHK(engine_strike(m));
-        const int p0 = st->verified_pos, p1 = st->pos;
+        const int p0 = st->verified_pos, p1 = st->feed.pos;
         fprintf(stderr, "[voxtral_hip] decode engine: %s; the stream's steps %d..%d are decoded again on the per-operator path%s\n",
                 engine_timeout_text(e, m->eng_strikes).c_str(), p0, p1 - 1, m->eng_strikes >= 3 ? ", the engine is switched off" : "");
         ARGCHK(p1 - p0 <= STREAM_KEEP_ROWS, "internal: %d unverified stream steps", p1 - p0);
         st->eng_steps = st->verified_eng_steps; st->op_steps = st->verified_op_steps;      // the re-run below counts every step again, on the path it then takes
-        st->pos = p0; st->dec->len = p0; st->tap_rows = st->verified_tap_rows; st->h_pos_word = p0;
+        st->feed.pos = p0; st->dec->len = p0; st->tap_rows = st->verified_tap_rows; st->h_pos_word = p0;
         HIPCHK(hipMemcpyAsync(st->state + STRM_POS, &st->h_pos_word, 4, hipMemcpyHostToDevice, s));
         VOXCHK(wo_acc_clear(m, s));
         StreamWs w; stream_ws_carve(m, 1, st->ws, &w); float* h = w.h;      // (the tick's buffers are free between ticks)
@@ -4390,7 +4396,7 @@ static int32_t stream_settle(vox_stream* st, bool* reran) {      // behind that 
         HIPCHK(hipStreamSynchronize(s));
         if (reran) *reran = true;
     }
-    st->verified_pos = st->pos; st->verified_tap_rows = st->tap_rows; st->verified_eng_steps = st->eng_steps; st->verified_op_steps = st->op_steps;
+    st->verified_pos = st->feed.pos; st->verified_tap_rows = st->tap_rows; st->verified_eng_steps = st->eng_steps; st->verified_op_steps = st->op_steps;
     return VOX_OK;
 }
 static int32_t stream_verify(vox_stream* st) {      // inside a long push: before the kept rows run out, before the decoder cache moves
@@ -4440,8 +4446,8 @@ static int32_t stream_encode_round(vox_model* m, const StreamWs& w, const Stream
 // a solo stream's tick: the round of one, then its own decode half -- the engine launch or the per-operator step, with the kept adapter rows behind the re-run
 static int32_t stream_tick(vox_stream* st) {
     vox_model* m = st->m; const vox_model_cfg& c = m->cfg; hipStream_t s = st->ctx->stream; const int R = c.reshape_factor;
-    if (st->pos - st->verified_pos >= STREAM_KEEP_ROWS) VOXCHK(stream_verify(st));      // the kept adapter rows cover the unverified steps
-    if (st->pos >= st->dec->max_seq) { VOXCHK(stream_verify(st)); VOXCHK(stream_dec_grow(st)); }
+    if (st->feed.pos - st->verified_pos >= STREAM_KEEP_ROWS) VOXCHK(stream_verify(st));      // the kept adapter rows cover the unverified steps
+    if (st->feed.pos >= st->dec->max_seq) { VOXCHK(stream_verify(st)); VOXCHK(stream_dec_grow(st)); }
     StreamWs w; stream_ws_carve(m, 1, st->ws, &w);
     const StreamRound r{st->d_mem, st->d_order, 1, st->cap, st->ring_layer, st->mel, st->left};
     const int k = st->ftap_mel ? st->ftap_ticks++ : 0; const bool ftap = st->ftap_mel && k < st->ftap_max;      // (a re-run repeats decode steps, never a tick)
@@ -4479,86 +4485,104 @@ static int32_t stream_ring_write(vox_stream* st, float* ring, int ring_n, int64_
     }
     return ring_write_f32(s, ring, ring_n, w0, src, at, len);
 }
+// ---- the feed planner: ONE implementation for a solo stream and for every member of a group ("The feed planner").  feed_plan is what a push / finish /
+// advance entry decides before anything changes; feed_pass is one pass of the call, bounded by the session's two rings -- a call may be larger than both.  Pure host
+// arithmetic: the callers turn a pass's amounts into copies, launches and ticks (stream_run; group_stage_pass), vox_debug_stream_feed_passes into rows of numbers.
 // 16 kHz samples a session's ring can take: everything from the oldest sample its next tick (at position pos) reads stays
 static size_t ring_room16(int R, long left, int pos, int64_t n_written) {
     const long lo = std::max(0L, (4L * R * pos - 3) * 160 - 200 - left);
     return (size_t)STREAM_SAMPLE_RING - (size_t)(n_written - lo);
 }
-static size_t stream_room16(const vox_stream* st) { return ring_room16(st->m->cfg.reshape_factor, st->left, st->pos, st->n_written); }
-// append `n` 16 kHz samples and run every tick up to position `target` as soon as its samples are in the ring
-static int32_t stream_feed(vox_stream* st, const StreamSrc& src, size_t n, int target) {
-    const int R = st->m->cfg.reshape_factor;
-    size_t done = 0;
-    while (done < n || st->pos < target) {
-        const size_t chunk = std::min(n - done, stream_room16(st));
-        VOXCHK(stream_ring_write(st, st->samples, STREAM_SAMPLE_RING, st->n_written, src, done, chunk));
-        st->n_written += (int64_t)chunk; done += chunk;
-        const int avail = (int)std::min<long>(target, stream_positions(st->left, R, st->n_written));
-        if (chunk == 0 && st->pos >= avail) return fail(VOX_ERR_INVALID, "internal: stream stalled at position %d of %d", st->pos, target);
-        while (st->pos < avail) VOXCHK(stream_tick(st));
+// what one call feeds a session: n samples at its rate, then `right` zeros (the right pad of a finishing session); `done` of the n + right written so far; goal16: the
+// 16 kHz samples the session holds after the call, before the pad; the ticks up to position `target` run in this call and yield `due` ids
+struct FeedPlan { size_t n = 0, right = 0, done = 0, goal16 = 0; int target = 0, due = 0; bool finish = false; };
+// every check of a call on one session, nothing changed: a refused call can be repeated.  `who`: the message's subject ("the stream", "entry 2: member 5")
+static int32_t feed_plan(const FeedState& f, int R, long left, int max_pos, size_t n, bool finish, int cap, const char* who, FeedPlan* out) {
+    ARGCHK(!f.finished, "%s is finished: a reset starts its next utterance", who);
+    FeedPlan p; p.n = n; p.finish = finish;
+    VOXCHK(stream_samples16(f.sr, f.rp, (size_t)f.n_pushed + n, finish, &p.goal16));
+    if (finish) {
+        vox_pad_cfg pc; vox_pad_cfg_voxtral(&pc); size_t total; VOXCHK(vox_pad_len(p.goal16, &pc, &total));
+        const int S = (int)(total / (size_t)stream_spp(R));      // the steps at positions 37 .. S - 2 yield the S - 38 ids of the offline path
+        ARGCHK(S - 1 <= max_pos, "%s: finishing would reach decoder position %d of a session created for %d", who, S - 1, max_pos);
+        p.target = std::max(S - 1, f.pos); p.right = total - (size_t)left - p.goal16;
+    } else {
+        const long P = stream_positions(left, R, (int64_t)p.goal16);
+        ARGCHK(P <= max_pos, "%s: the push would reach decoder position %ld of a session created for %d (a reset starts over)", who, P, max_pos);
+        p.target = std::max((int)P, f.pos);
     }
-    return VOX_OK;
+    p.due = p.target - f.pos;
+    ARGCHK(cap >= p.due, "%s: out_ids capacity %d < %d ids due", who, cap, p.due);
+    *out = p; return VOX_OK;
 }
-// a stream at its capture rate: append `n` input-rate samples, turn every block that became complete into 16 kHz samples (finish: everything up to vox_resample_len of
-// the utterance, blocks clipped at its end) and run the ticks those make due, in rounds bounded by the two rings -- a push may be larger than both.  The input ring keeps
-// everything from block c_next - 1 on, c_next the block of the next 16 kHz sample to be produced: that sample reads the tail of the block before its own.
-static int32_t stream_feed_rate(vox_stream* st, const StreamSrc& src, size_t n, bool finish, int target) {
-    const int R = st->m->cfg.reshape_factor; const ResamplePlan& p = st->rp; hipStream_t s = st->ctx->stream;
-    size_t goal16; VOXCHK(stream_samples16(st->sr, p, (size_t)st->in_written + n, finish, &goal16));
-    const int tgt = (int)std::min<long>(target, stream_positions(st->left, R, (int64_t)goal16));
-    size_t done = 0;
-    while (done < n || st->n_written < (int64_t)goal16 || st->pos < tgt) {
-        const int64_t c_next = (st->n_written + p.delay) / p.fft_out, keep_from = std::max<int64_t>(0, c_next - 1) * p.fft_in;
-        const size_t chunk = std::min(n - done, (size_t)st->in_ring_n - (size_t)std::max<int64_t>(0, st->in_written - keep_from));      // (past the last block at finish: nothing is appended)
-        VOXCHK(stream_ring_write(st, st->in_ring, st->in_ring_n, st->in_written, src, done, chunk));
-        st->in_written += (int64_t)chunk; done += chunk;
-        const int64_t have16 = finish ? (int64_t)goal16 : stream_avail16(p, st->in_written);
-        const size_t count = std::min((size_t)std::max<int64_t>(0, have16 - st->n_written), stream_room16(st));
-        HIPCHK(launch_stream_resample(st->in_ring, st->in_ring_n - 1, (long)st->in_written, st->rs_matrix, (int)p.fft_in, (int)p.fft_out, (int)p.delay, st->samples, STREAM_SAMPLE_RING - 1,
-                                      (long)st->n_written, (int)count, s));
-        st->n_written += (int64_t)count;
-        const int avail = (int)std::min<long>(tgt, stream_positions(st->left, R, st->n_written));
-        if (chunk == 0 && count == 0 && st->pos >= avail) return fail(VOX_ERR_INVALID, "internal: stream stalled at position %d of %d (%lld of %zu samples at 16 kHz)", st->pos, tgt, (long long)st->n_written, goal16);
-        while (st->pos < avail) VOXCHK(stream_tick(st));
+static bool feed_open(const FeedState& f, const FeedPlan& p) { return p.done < p.n + p.right || f.n_written < (int64_t)p.goal16 || f.pos < p.target; }
+// one pass: samples [at, at + n_in) of the call go to the session's FIRST ring at in_w0 (a rate session: its input ring; a 16 kHz session: the 16 kHz ring itself, and
+// n16 == n_in, i0 == in_w0); the 16 kHz samples [i0, i0 + n16) exist after it (a rate session: to be resampled, the input ring holding in_written samples by then);
+// `pad` zeros follow at pad_w0; `ticks` ticks became due
+struct FeedPass {
+    size_t at = 0, n_in = 0, n16 = 0, pad = 0; int64_t in_w0 = 0, i0 = 0, pad_w0 = 0; int ticks = 0;
+    bool idle() const { return n_in == 0 && n16 == 0 && pad == 0 && ticks == 0; }      // an open call's pass is never idle: the callers' stall refusal
+};
+// Advances in_written, n_written and p.done; NOT pos -- the caller runs the ticks.  in_cap: most input samples this pass (a group's 16-bit staging slot).
+// A rate session's input ring keeps everything from block c_next - 1 on, c_next the block of the next 16 kHz sample to be produced: that sample reads the tail of the
+// block before its own.  Its 16 kHz samples are the ones whose blocks are complete -- at the end of the utterance (finish, the last input sample in) all goal16, blocks
+// clipped at its length.  The right pad follows the utterance's last 16 kHz sample, in the same pass where the ring has room.
+static FeedPass feed_pass(FeedState& f, FeedPlan& p, int R, long left, size_t in_cap) {
+    FeedPass q; q.at = p.done;
+    size_t room = ring_room16(R, left, f.pos, f.n_written);
+    const size_t rest = std::min(p.n - std::min(p.done, p.n), in_cap);
+    if (f.sr != 16000) {
+        const int64_t c_next = (f.n_written + f.rp.delay) / f.rp.fft_out, keep_from = std::max<int64_t>(0, c_next - 1) * f.rp.fft_in;
+        q.n_in = std::min(rest, (size_t)f.in_ring_n - (size_t)std::max<int64_t>(0, f.in_written - keep_from));
+        q.in_w0 = f.in_written; f.in_written += (int64_t)q.n_in; p.done += q.n_in;
+        const int64_t have16 = p.finish && p.done >= p.n ? (int64_t)p.goal16 : stream_avail16(f.rp, f.in_written);
+        q.n16 = std::min((size_t)std::max<int64_t>(0, have16 - f.n_written), room); q.i0 = f.n_written;
+    } else {
+        q.n_in = q.n16 = std::min(rest, room); q.in_w0 = q.i0 = f.n_written; p.done += q.n_in;
     }
-    return VOX_OK;
+    f.n_written += (int64_t)q.n16; room -= q.n16;
+    if (p.done >= p.n && p.done < p.n + p.right && f.n_written >= (int64_t)p.goal16) {
+        q.pad = std::min(p.n + p.right - p.done, room); q.pad_w0 = f.n_written; f.n_written += (int64_t)q.pad; p.done += q.pad;
+    }
+    q.ticks = std::max(0, (int)std::min<long>(p.target, stream_positions(left, R, f.n_written)) - f.pos);
+    return q;
 }
-// what a push / finish does around its ticks: the stream's own Ada scales, clean accumulators, then the ids of the call behind ONE synchronisation.
-// finish: a rate stream first produces the rest of its 16 kHz samples; then `n` zeros follow, the right pad
-static int32_t stream_run(vox_stream* st, const StreamSrc& src, size_t n, bool finish, int target, int32_t* out_ids, int32_t* n_ids) {
-    vox_model* m = st->m; hipStream_t s = st->ctx->stream;
-    const int due = target - st->pos;
+
+// what a push / finish does around its ticks: the stream's own Ada scales, clean accumulators, the passes of its one session -- input into its first ring, the resampling
+// launch of a rate stream, the pad, then every tick that became due -- then the ids of the call behind ONE synchronisation
+static int32_t stream_run(vox_stream* st, const StreamSrc& src, FeedPlan& plan, int32_t* out_ids, int32_t* n_ids) {
+    vox_model* m = st->m; hipStream_t s = st->ctx->stream; FeedState& f = st->feed; const bool rate = f.sr != 16000;
+    const int due = plan.due, R = m->cfg.reshape_factor;
     if (m->pw_pend_rows > 0) VOXCHK(pw_sync(m));      // unverified engine steps of the piecewise surface share the engine's error word: settled first
     VOXCHK(vox_model_set_t_embed(m, st->t_embed.data()));
     if (due > 0) VOXCHK(wo_acc_clear(m, s));
-    if (st->sr != 16000 && !finish) VOXCHK(stream_feed_rate(st, src, n, false, target));
-    else {
-        if (st->sr != 16000) VOXCHK(stream_feed_rate(st, StreamSrc{}, 0, true, target));
-        VOXCHK(stream_feed(st, src, n, target));
+    while (feed_open(f, plan)) {
+        const FeedPass q = feed_pass(f, plan, R, st->left, SIZE_MAX);
+        if (q.idle()) return fail(VOX_ERR_INVALID, "internal: stream stalled at position %d of %d (%lld of %zu samples at 16 kHz)", f.pos, plan.target, (long long)f.n_written, plan.goal16);
+        VOXCHK(stream_ring_write(st, rate ? f.in_ring : st->samples, rate ? f.in_ring_n : STREAM_SAMPLE_RING, q.in_w0, src, q.at, q.n_in));
+        if (rate) HIPCHK(launch_stream_resample(f.in_ring, f.in_ring_n - 1, (long)f.in_written, f.At, (int)f.rp.fft_in, (int)f.rp.fft_out, (int)f.rp.delay, st->samples, STREAM_SAMPLE_RING - 1,
+                                                (long)q.i0, (int)q.n16, s));
+        VOXCHK(ring_write_f32(s, st->samples, STREAM_SAMPLE_RING, q.pad_w0, StreamSrc{}, 0, q.pad));
+        for (int t = 0; t < q.ticks; t++) VOXCHK(stream_tick(st));
     }
-    int32_t* ids_dev = st->tokens + VOX_PREFIX_TOKENS + st->ids_out;
+    int32_t* ids_dev = st->tokens + VOX_PREFIX_TOKENS + f.ids_out;
     VOXCHK(stream_verify_enqueue(st));
     if (due > 0) HIPCHK(hipMemcpyAsync(out_ids, ids_dev, (size_t)due * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));      // the call's one synchronisation: ids and the engine's verdict land together
     bool reran = false; VOXCHK(stream_settle(st, &reran));
     if (reran && due > 0) { HIPCHK(hipMemcpyAsync(out_ids, ids_dev, (size_t)due * 4, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s)); }
-    st->ids_out += due; *n_ids = due;
+    f.ids_out += due; *n_ids = due;
     return VOX_OK;
 }
 
 static int32_t stream_push(vox_stream* st, const void* samples, bool s16, size_t n, int32_t mem_kind, int32_t* out_ids, int32_t cap, int32_t* n_ids) {
     ARGCHK(st && n_ids && (samples || n == 0), "null argument"); ARGCHK(cap >= 0 && (out_ids || cap == 0), "bad output buffer"); ARGCHK(n <= ((size_t)1 << 36), "push of %zu samples", n);
     ARGCHK(mem_kind == VOX_MEM_HOST || mem_kind == VOX_MEM_DEVICE, "bad mem_kind %d", mem_kind);
-    ARGCHK(!st->finished, "the stream is finished: vox_stream_reset starts the next utterance");
-    size_t n16; VOXCHK(stream_samples16(st->sr, st->rp, (size_t)st->n_pushed + n, false, &n16));
-    const long P = stream_positions(st->left, st->m->cfg.reshape_factor, (int64_t)n16);
-    ARGCHK(P <= st->max_pos, "the push would reach decoder position %ld of a stream created for %d (vox_stream_reset starts over)", P, st->max_pos);
-    const int target = std::max((int)P, st->pos), due = target - st->pos;
-    ARGCHK(cap >= due, "out_ids capacity %d < %d ids due", cap, due);      // BEFORE anything is appended: the call can be repeated
+    FeedPlan plan; VOXCHK(feed_plan(st->feed, st->m->cfg.reshape_factor, st->left, st->max_pos, n, false, cap, "the stream", &plan));      // BEFORE anything is appended: the call can be repeated
     VOXCHK(ctx_bind(st->ctx));
-    st->n_pushed += (int64_t)n;
+    st->feed.n_pushed += (int64_t)n;
     StreamSrc src; src.p = samples; src.s16 = s16; src.mem_kind = mem_kind;
-    return stream_run(st, src, n, false, target, out_ids, n_ids);
+    return stream_run(st, src, plan, out_ids, n_ids);
 }
 extern "C" int32_t vox_stream_push(vox_stream* st, const float* samples, size_t n, int32_t mem_kind, int32_t* out_ids, int32_t cap, int32_t* n_ids) {
     return stream_push(st, samples, false, n, mem_kind, out_ids, cap, n_ids);
@@ -4569,18 +4593,10 @@ extern "C" int32_t vox_stream_push_s16(vox_stream* st, const int16_t* samples, s
 }
 extern "C" int32_t vox_stream_finish(vox_stream* st, int32_t* out_ids, int32_t cap, int32_t* n_ids) {
     ARGCHK(st && n_ids, "null argument"); ARGCHK(cap >= 0 && (out_ids || cap == 0), "bad output buffer");
-    ARGCHK(!st->finished, "the stream is finished already");
-    vox_pad_cfg pc; vox_pad_cfg_voxtral(&pc);
-    size_t n16; VOXCHK(stream_samples16(st->sr, st->rp, (size_t)st->n_pushed, true, &n16));
-    size_t total; VOXCHK(vox_pad_len(n16, &pc, &total));
-    const int S = (int)(total / (size_t)stream_spp(st->m->cfg.reshape_factor));
-    ARGCHK(S - 1 <= st->max_pos, "finishing would reach decoder position %d of a stream created for %d", S - 1, st->max_pos);
-    const int target = std::max(S - 1, st->pos), due = target - st->pos;      // the steps at positions 37 .. S - 2 yield the S - 38 ids of the offline path
-    ARGCHK(cap >= due, "out_ids capacity %d < %d ids due", cap, due);
+    FeedPlan plan; VOXCHK(feed_plan(st->feed, st->m->cfg.reshape_factor, st->left, st->max_pos, 0, true, cap, "the stream", &plan));
     VOXCHK(ctx_bind(st->ctx));
-    const size_t right = total - (size_t)st->left - n16;
-    VOXCHK(stream_run(st, StreamSrc{}, right, true, target, out_ids, n_ids));
-    st->finished = true;
+    VOXCHK(stream_run(st, StreamSrc{}, plan, out_ids, n_ids));
+    st->feed.finished = true;
     return VOX_OK;
 }
 
@@ -4632,14 +4648,14 @@ extern "C" int32_t vox_debug_stream_front_tap_fetch(vox_stream* st, float* out_m
 // fed member's due tick count d_i before it launches anything: the members sorted by d_i descending, round r runs ONE tick of the first n_r = #{d_i > r} of them --
 // stream_encode_round at 4 n_r rows (the code of a solo stream's tick) and, as the decode half, xf_chain at n_r rows on the group's decoder slab.  One upload (the
 // order) per pass, constant launch arguments within a pass except n_r, one synchronisation per call.  No engine runs here: no kept rows, no re-run, no verification.
-// A member may be fed at its capture rate, and a call may carry 16-bit PCM (group_advance): the ingest has the member dimension too, one launch per pass.
+// A member may be fed at its capture rate, and a call may carry 16-bit PCM: every member's passes are feed_plan / feed_pass on its FeedState, the solo stream's planner;
+// the ingest has the member dimension too, one launch per pass (group_stage_pass).
 // ------------------------------------------------------------------------------------------------
 static const int GROUP_MAX = 16, GROUP_DEFAULT_POSITIONS = 2048;
 struct GroupMember {
-    int64_t n_pushed = 0, n_written = 0; int pos = 0, ids_out = 0; bool finished = false; uint64_t steps = 0;      // n_pushed: as pushed, at the member's rate; n_written: 16 kHz
+    FeedState feed;                      // the member's host mirror; at a capture rate: its own input ring, a copy of its rate's plan, the rate's matrix (owned by the rate table)
+    int rate = -1; uint64_t steps = 0;   // its slot of the group's rate table (-1: 16 kHz); its ticks, each one row of an xf_chain step
     int h_state[STRM_WORDS];
-    // a member fed at its capture rate (sr != 16000): its slot of the group's rate table, its own input ring, the input samples copied into it so far
-    uint32_t sr = 16000; int rate = -1; float* in_ring = nullptr; int in_ring_n = 0; int64_t in_written = 0;
 };
 // one block matrix per rate in use, shared by the members at that rate (built by resample_matrix_build: vox_resample's bits; never the context's matrix, which goes
 // when vox_resample serves another rate pair).  refs == 0: a free slot
@@ -4663,14 +4679,15 @@ struct vox_stream_group {
 // the member leaves its rate: its input ring and its reference to the rate's matrix go (the matrix with its last reference).  The caller has synchronised.
 static void group_member_drop_rate(vox_stream_group* g, int i) {
     GroupMember& me = g->mem[i];
-    if (me.in_ring) (void)hipFree(me.in_ring);
+    FeedState& f = me.feed;
+    if (f.in_ring) (void)hipFree(f.in_ring);
     if (me.rate >= 0) { GroupRate& r = g->rates[(size_t)me.rate]; if (--r.refs == 0) { (void)hipFree(r.At); r = GroupRate{}; } }
-    me.sr = 16000; me.rate = -1; me.in_ring = nullptr; me.in_ring_n = 0; me.in_written = 0;
+    f.sr = 16000; f.rp = ResamplePlan{}; f.At = nullptr; f.in_ring = nullptr; f.in_ring_n = 0; f.in_written = 0; me.rate = -1;
 }
 // the member's rate from now on.  Everything that can fail happens before anything changes: a refused rate leaves the member as it was.  May synchronise (a new matrix).
 static int32_t group_member_set_rate(vox_stream_group* g, int i, uint32_t sr) {
     GroupMember& me = g->mem[i];
-    if (sr == me.sr) return VOX_OK;
+    if (sr == me.feed.sr) return VOX_OK;
     ResamplePlan rp; size_t rs_bytes = 0; int ring_n = 0, slot = -1; float *ring = nullptr, *At = nullptr;
     if (sr != 16000) {
         VOXCHK(stream_rate_plan(sr, &rp, &rs_bytes, &ring_n));
@@ -4687,7 +4704,7 @@ static int32_t group_member_set_rate(vox_stream_group* g, int i, uint32_t sr) {
         GroupRate& r = g->rates[(size_t)slot]; r.sr = sr; r.rp = rp; r.At = At; r.bytes = rs_bytes;
     }
     g->rates[(size_t)slot].refs++;
-    me.sr = sr; me.rate = slot; me.in_ring = ring; me.in_ring_n = ring_n; me.in_written = 0;
+    FeedState& f = me.feed; f.sr = sr; f.rp = rp; f.At = g->rates[(size_t)slot].At; f.in_ring = ring; f.in_ring_n = ring_n; f.in_written = 0; me.rate = slot;
     return VOX_OK;
 }
 static int32_t group_upload_members(vox_stream_group* g) {      // after a descriptor changed (gain, tap); synchronises
@@ -4701,7 +4718,7 @@ static int32_t group_member_seed(vox_stream_group* g, int i) {
     GroupMember& me = g->mem[i];
     VOXCHK(stream_seed(g->m, g->t_embed.data(), g->g.RC, g->g.PC, g->g.cap, g->h_mem[i].kring, g->h_mem[i].vring, &view, g->h_mem[i].tokens, g->h_mem[i].state, me.h_state,
                        []() -> int32_t { return VOX_OK; }));
-    me.n_pushed = me.n_written = me.in_written = 0; me.pos = g->g.PC; me.ids_out = 0; me.finished = false; me.steps = 0;
+    me.feed.restart(g->g.PC); me.steps = 0;
     return VOX_OK;
 }
 static void group_release(vox_stream_group* g) {
@@ -4777,16 +4794,14 @@ extern "C" int32_t vox_stream_group_info(const vox_stream_group* g, int32_t memb
     ARGCHK(g && out, "null argument"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1);
     const GroupMember& me = g->mem[member]; const int R = g->m->cfg.reshape_factor;
     const uint64_t tap_b = g->h_mem[member].tap ? (uint64_t)g->h_mem[member].tap_max * g->m->cfg.vocab * 4 : 0;
-    const uint64_t rate_b = me.rate >= 0 ? (uint64_t)me.in_ring_n * 4 + g->rates[(size_t)me.rate].bytes / (uint64_t)g->rates[(size_t)me.rate].refs : 0;
-    out[0] = me.n_pushed; out[1] = me.pos; out[2] = me.ids_out; out[3] = (int64_t)R * me.pos; out[4] = std::min<int64_t>((int64_t)R * me.pos, g->g.cap);
+    const uint64_t rate_b = me.rate >= 0 ? (uint64_t)me.feed.in_ring_n * 4 + g->rates[(size_t)me.rate].bytes / (uint64_t)g->rates[(size_t)me.rate].refs : 0;
+    const FeedState& f = me.feed;
+    out[0] = f.n_pushed; out[1] = f.pos; out[2] = f.ids_out; out[3] = (int64_t)R * f.pos; out[4] = std::min<int64_t>((int64_t)R * f.pos, g->g.cap);
     out[5] = (int64_t)(g->bytes / (uint64_t)g->n + tap_b + rate_b);      // the member's share of the group's device state; its own input ring, its share of its rate's matrix
     out[6] = 0; out[7] = (int64_t)me.steps;                      // no engine step; the member's ticks, each one row of an xf_chain step
     return VOX_OK;
 }
 
-// what one entry of a call feeds: the samples (f32 or 16-bit, at the member's rate), then `right` zeros (the right pad of a finishing member); `done` of the n + right
-// written so far; goal16: the 16 kHz samples the member holds after the call, before the pad
-struct GroupFeed { int member; const void* p; size_t n, right, done; int target, due; bool finish; size_t goal16; };
 // one round: a tick of the first n_r members of the pass's order
 static int32_t group_round(vox_stream_group* g, const StreamWs& w, int n_r) {
     vox_model* m = g->m; const vox_model_cfg& c = m->cfg; hipStream_t s = g->ctx->stream; const int R = c.reshape_factor;
@@ -4799,125 +4814,108 @@ static int32_t group_round(vox_stream_group* g, const StreamWs& w, int n_r) {
     HIPCHK(launch_stream_group_advance(g->logits, c.vocab, g->d_mem, g->d_order, n_r, R, 4 * R, g->g.cap, s));
     return VOX_OK;
 }
-// vox_stream_group_advance and its 16-bit form.  A member at its capture rate follows stream_feed_rate inside the passes: its samples go into its input ring, every
-// block that became complete (finish: everything up to vox_resample_len, blocks clipped at the utterance's end) becomes 16 kHz samples -- ONE stream_group_resample_kernel
-// launch per pass for all fed members, behind ONE stream_group_s16_kernel launch when the samples are 16-bit -- and the rounds see 16 kHz rings only.  A call whose entries
-// fit their rings in one pass runs the rounds of a 16 kHz group fed the resampled pieces.
-static int32_t group_advance(vox_stream_group* g, vox_stream_feed* feeds, int32_t n_feeds, int32_t mem_kind, bool s16) {
-    ARGCHK(g && (feeds || n_feeds == 0), "null argument"); ARGCHK(n_feeds >= 0 && n_feeds <= g->n, "%d entries for a group of %d members", n_feeds, g->n);
-    ARGCHK(mem_kind == VOX_MEM_HOST || mem_kind == VOX_MEM_DEVICE, "bad mem_kind %d", mem_kind);
-    vox_model* m = g->m; const int R = m->cfg.reshape_factor; const long left = g->g.left; hipStream_t s = g->ctx->stream;
-    // every check before anything changes: a refused call can be repeated
-    std::vector<GroupFeed> fs; fs.reserve((size_t)n_feeds); unsigned seen = 0; bool any_rate = false;
+// vox_stream_group_advance and its 16-bit form, in four units: group_plan_entries (every check, nothing changed), then per pass group_stage_pass (feed_pass for every
+// entry: the copies, and the slots of ONE ingest upload and of at most one stream_group_s16_kernel and one stream_group_resample_kernel launch) and group_run_rounds
+// (ONE order upload, the rounds, pos and steps), then group_drain (the id copies behind the call's ONE synchronisation).  The rounds see 16 kHz rings only.
+struct GroupFeed { int member; const void* p; FeedPlan plan; };      // one entry of the call: its member, its samples (f32 or 16-bit, at the member's rate), its plan
+struct GroupCall { std::vector<GroupFeed> fs; int32_t mem_kind = VOX_MEM_HOST; bool s16 = false, staged = false, any_rate = false; };      // staged: host 16-bit samples pass through g->s16_stage
+typedef std::vector<std::pair<int, int>> GroupDue;      // (ticks due in this pass, member)
+static int32_t group_plan_entries(const vox_stream_group* g, const vox_stream_feed* feeds, int32_t n_feeds, GroupCall* call) {
+    unsigned seen = 0; call->fs.reserve((size_t)n_feeds);
     for (int k = 0; k < n_feeds; k++) {
         const vox_stream_feed& f = feeds[k];
         ARGCHK(f.member >= 0 && f.member < g->n, "entry %d: member %d out of range (0..%d)", k, f.member, g->n - 1);
         ARGCHK(!((seen >> f.member) & 1u), "entry %d: member %d is fed twice in one call", k, f.member); seen |= 1u << f.member;
         ARGCHK(f.samples || f.n_samples == 0, "entry %d: null samples", k); ARGCHK(f.n_samples <= ((size_t)1 << 36), "entry %d: push of %zu samples", k, f.n_samples);
         ARGCHK(f.cap >= 0 && (f.out_ids || f.cap == 0), "entry %d: bad output buffer", k); ARGCHK(f.finish == 0 || f.finish == 1, "entry %d: finish must be 0 or 1", k);
-        const GroupMember& me = g->mem[f.member];
-        ARGCHK(!me.finished, "entry %d: member %d is finished: vox_stream_group_reset starts its next utterance", k, f.member);
-        GroupFeed gf{f.member, f.samples, f.n_samples, 0, 0, 0, 0, f.finish != 0, 0};
-        static const ResamplePlan no_plan;
-        size_t n16; VOXCHK(stream_samples16(me.sr, me.rate >= 0 ? g->rates[(size_t)me.rate].rp : no_plan, (size_t)me.n_pushed + f.n_samples, f.finish != 0, &n16));
-        gf.goal16 = n16; any_rate |= me.rate >= 0;
-        if (f.finish) {
-            vox_pad_cfg pc; vox_pad_cfg_voxtral(&pc); size_t total; VOXCHK(vox_pad_len(n16, &pc, &total));
-            const int S = (int)(total / (size_t)stream_spp(R));
-            ARGCHK(S - 1 <= g->g.max_pos, "entry %d: finishing would reach decoder position %d of a group created for %d", k, S - 1, g->g.max_pos);
-            gf.target = std::max(S - 1, me.pos); gf.right = total - (size_t)left - n16;
-        } else {
-            const long P = stream_positions(left, R, (int64_t)n16);
-            ARGCHK(P <= g->g.max_pos, "entry %d: the push would reach decoder position %ld of a group created for %d (vox_stream_group_reset starts over)", k, P, g->g.max_pos);
-            gf.target = std::max((int)P, me.pos);
-        }
-        gf.due = gf.target - me.pos;
-        ARGCHK(f.cap >= gf.due, "entry %d: out_ids capacity %d < %d ids due", k, f.cap, gf.due);
-        fs.push_back(gf);
+        char who[48]; snprintf(who, sizeof who, "entry %d: member %d", k, f.member);
+        GroupFeed gf{f.member, f.samples, FeedPlan{}};
+        VOXCHK(feed_plan(g->mem[f.member].feed, g->m->cfg.reshape_factor, g->g.left, g->g.max_pos, f.n_samples, f.finish != 0, f.cap, who, &gf.plan));
+        call->any_rate |= g->mem[f.member].rate >= 0;
+        call->fs.push_back(gf);
     }
+    return VOX_OK;
+}
+// one pass: what fits into every fed member's rings.  f32 samples and the pad zeros go as copies; 16-bit samples (slot z of the conversion) and the 16 kHz samples a rate
+// member's complete blocks give (slot z of the resampling, which reads what the conversion wrote) as the pass's ingest, in front of its rounds
+static int32_t group_stage_pass(vox_stream_group* g, GroupCall& call, GroupDue* due, bool* idle) {
+    const int R = g->m->cfg.reshape_factor; hipStream_t s = g->ctx->stream;
+    bool any_pcm = false, any_rs = false; *idle = true; due->clear();
+    GroupIngest* ing = nullptr;
+    if (call.s16 || call.any_rate) { g->ingests.emplace_back(); ing = &g->ingests.back(); std::memset((void*)ing, 0, sizeof(GroupIngest)); }
+    for (size_t z = 0; z < call.fs.size(); z++) {
+        GroupFeed& e = call.fs[z]; FeedState& f = g->mem[e.member].feed; const bool rate = f.sr != 16000;
+        float *ring16 = g->samples + (size_t)e.member * STREAM_SAMPLE_RING, *ring = rate ? f.in_ring : ring16; const int ring_n = rate ? f.in_ring_n : STREAM_SAMPLE_RING;
+        const FeedPass q = feed_pass(f, e.plan, R, g->g.left, call.staged ? (size_t)STREAM_SAMPLE_RING : SIZE_MAX);
+        if (!call.s16) { StreamSrc src; src.p = e.p; src.mem_kind = call.mem_kind; VOXCHK(ring_write_f32(s, ring, ring_n, q.in_w0, src, q.at, q.n_in)); }
+        else if (q.n_in > 0) {
+            const int16_t* v = (const int16_t*)e.p + q.at;
+            if (call.staged) { int16_t* st = g->s16_stage + z * (size_t)STREAM_SAMPLE_RING; HIPCHK(hipMemcpyAsync(st, v, q.n_in * 2, hipMemcpyHostToDevice, s)); v = st; }
+            ing->pcm[z] = StreamS16{v, (int)q.n_in, ring, ring_n - 1, (long)q.in_w0}; any_pcm = true;
+        }
+        if (rate && q.n16 > 0) {
+            ing->rs[z] = StreamIngest{f.in_ring, f.in_ring_n - 1, (long)f.in_written, f.At, (int)f.rp.fft_in, (int)f.rp.fft_out, (int)f.rp.delay, ring16, (long)q.i0, (int)q.n16}; any_rs = true;
+        }
+        VOXCHK(ring_write_f32(s, ring16, STREAM_SAMPLE_RING, q.pad_w0, StreamSrc{}, 0, q.pad));
+        if (q.ticks > 0) due->emplace_back(q.ticks, e.member);
+        *idle &= q.idle();
+    }
+    if (any_pcm || any_rs) {
+        HIPCHK(hipMemcpyAsync(g->d_ingest, ing, sizeof(GroupIngest), hipMemcpyHostToDevice, s));
+        if (any_pcm) HIPCHK(launch_stream_group_s16(g->d_ingest->pcm, ing->pcm, (int)call.fs.size(), s));
+        if (any_rs) HIPCHK(launch_stream_group_resample(g->d_ingest->rs, ing->rs, (int)call.fs.size(), STREAM_SAMPLE_RING - 1, s));
+    }
+    return VOX_OK;
+}
+// the pass's rounds: the members sorted by ticks due, descending; round r runs one tick of the first n_r = #{ticks > r} of them
+static int32_t group_run_rounds(vox_stream_group* g, const StreamWs& w, GroupDue& due) {
+    std::stable_sort(due.begin(), due.end(), [](const std::pair<int, int>& a, const std::pair<int, int>& b) { return a.first > b.first; });
+    g->orders.emplace_back(); std::array<int, GROUP_MAX>& ord = g->orders.back(); ord.fill(0);
+    for (size_t i = 0; i < due.size(); i++) ord[i] = due[i].second;
+    HIPCHK(hipMemcpyAsync(g->d_order, ord.data(), sizeof(int) * GROUP_MAX, hipMemcpyHostToDevice, g->ctx->stream));      // the pass's one order upload
+    int n_r = (int)due.size();
+    for (int r = 0; r < due[0].first; r++) {
+        while (due[(size_t)n_r - 1].first <= r) n_r--;
+        VOXCHK(group_round(g, w, n_r));
+    }
+    for (const std::pair<int, int>& d : due) { g->mem[d.second].feed.pos += d.first; g->mem[d.second].steps += (uint64_t)d.first; }
+    return VOX_OK;
+}
+static int32_t group_drain(vox_stream_group* g, vox_stream_feed* feeds, const GroupCall& call) {
+    hipStream_t s = g->ctx->stream;
+    for (size_t k = 0; k < call.fs.size(); k++) if (call.fs[k].plan.due > 0)
+        HIPCHK(hipMemcpyAsync(feeds[k].out_ids, g->h_mem[call.fs[k].member].tokens + VOX_PREFIX_TOKENS + g->mem[call.fs[k].member].feed.ids_out, (size_t)call.fs[k].plan.due * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));      // the call's one synchronisation: every fed member's ids land
+    g->orders.clear(); g->ingests.clear();
+    for (size_t k = 0; k < call.fs.size(); k++) { FeedState& f = g->mem[call.fs[k].member].feed; f.ids_out += call.fs[k].plan.due; feeds[k].n_ids = call.fs[k].plan.due; if (feeds[k].finish) f.finished = true; }
+    return VOX_OK;
+}
+static int32_t group_advance(vox_stream_group* g, vox_stream_feed* feeds, int32_t n_feeds, int32_t mem_kind, bool s16) {
+    ARGCHK(g && (feeds || n_feeds == 0), "null argument"); ARGCHK(n_feeds >= 0 && n_feeds <= g->n, "%d entries for a group of %d members", n_feeds, g->n);
+    ARGCHK(mem_kind == VOX_MEM_HOST || mem_kind == VOX_MEM_DEVICE, "bad mem_kind %d", mem_kind);
+    vox_model* m = g->m;
+    GroupCall call; call.mem_kind = mem_kind; call.s16 = s16; call.staged = s16 && mem_kind == VOX_MEM_HOST;
+    VOXCHK(group_plan_entries(g, feeds, n_feeds, &call));      // every check before anything changes: a refused call can be repeated
     VOXCHK(ctx_bind(g->ctx));
-    const bool staged = s16 && mem_kind == VOX_MEM_HOST;      // host 16-bit samples pass through the group's staging area, STREAM_SAMPLE_RING of them per entry and pass
-    if (staged && !g->s16_stage && !fs.empty()) {
+    if (call.staged && !g->s16_stage && !call.fs.empty()) {      // STREAM_SAMPLE_RING staged samples per entry and pass
         const size_t nb = (size_t)g->n * STREAM_SAMPLE_RING * 2;
         HIPCHK(hipMalloc((void**)&g->s16_stage, nb)); g->bytes += nb;
     }
     if (m->pw_pend_rows > 0) VOXCHK(pw_sync(m));
     VOXCHK(vox_model_set_t_embed(m, g->t_embed.data()));
     StreamWs w; stream_ws_carve(m, g->n, g->ws, &w);
-    for (GroupFeed& f : fs) g->mem[f.member].n_pushed += (int64_t)f.n;
+    for (GroupFeed& e : call.fs) g->mem[e.member].feed.n_pushed += (int64_t)e.plan.n;
     // passes: write what fits into every fed member's rings, run the rounds that became due, repeat (a push may be larger than the rings)
+    GroupDue due;
     for (;;) {
-        bool open = false;
-        for (const GroupFeed& f : fs) open |= f.done < f.n + f.right || g->mem[f.member].n_written < (int64_t)f.goal16 || g->mem[f.member].pos < f.target;
+        bool open = false, idle = false;
+        for (const GroupFeed& e : call.fs) open |= feed_open(g->mem[e.member].feed, e.plan);
         if (!open) break;
-        std::vector<std::pair<int, int>> due;      // (ticks due in this pass, member)
-        bool wrote = false, any_pcm = false, any_rs = false;
-        GroupIngest* ing = nullptr;
-        if (s16 || any_rate) { g->ingests.emplace_back(); ing = &g->ingests.back(); std::memset((void*)ing, 0, sizeof(GroupIngest)); }
-        // samples [at, at + k) of entry z into ring[(w0 + j) & (ring_n - 1)]: f32 as copies, 16-bit samples as slot z of the pass's conversion launch
-        auto append = [&](size_t z, float* ring, int ring_n, int64_t w0, size_t at, size_t k) -> int32_t {
-            const GroupFeed& f = fs[z];
-            if (!s16) { StreamSrc src; src.p = f.p; src.mem_kind = mem_kind; return ring_write_f32(s, ring, ring_n, w0, src, at, k); }
-            if (k == 0) return VOX_OK;
-            const int16_t* v = (const int16_t*)f.p + at;
-            if (staged) {
-                int16_t* st = g->s16_stage + z * (size_t)STREAM_SAMPLE_RING;
-                HIPCHK(hipMemcpyAsync(st, v, k * 2, hipMemcpyHostToDevice, s)); v = st;
-            }
-            ing->pcm[z] = StreamS16{v, (int)k, ring, ring_n - 1, (long)w0}; any_pcm = true;
-            return VOX_OK;
-        };
-        for (size_t z = 0; z < fs.size(); z++) {
-            GroupFeed& f = fs[z]; GroupMember& me = g->mem[f.member]; float* ring = g->samples + (size_t)f.member * STREAM_SAMPLE_RING;
-            size_t room = ring_room16(R, left, me.pos, me.n_written);
-            if (me.rate >= 0) {
-                // the input ring keeps everything from block c_next - 1 on, c_next the block of the next 16 kHz sample to be produced
-                const GroupRate& gr = g->rates[(size_t)me.rate]; const ResamplePlan& p = gr.rp;
-                const int64_t c_next = (me.n_written + p.delay) / p.fft_out, keep_from = std::max<int64_t>(0, c_next - 1) * p.fft_in;
-                size_t k = std::min(f.n - std::min(f.done, f.n), (size_t)me.in_ring_n - (size_t)std::max<int64_t>(0, me.in_written - keep_from));
-                if (staged) k = std::min(k, (size_t)STREAM_SAMPLE_RING);
-                VOXCHK(append(z, me.in_ring, me.in_ring_n, me.in_written, f.done, k)); me.in_written += (int64_t)k; f.done += k; wrote |= k > 0;
-                const int64_t have16 = f.finish && f.done >= f.n ? (int64_t)f.goal16 : stream_avail16(p, me.in_written);
-                const size_t count = std::min((size_t)std::max<int64_t>(0, have16 - me.n_written), room);
-                if (count > 0) {
-                    ing->rs[z] = StreamIngest{me.in_ring, me.in_ring_n - 1, (long)me.in_written, gr.At, (int)p.fft_in, (int)p.fft_out, (int)p.delay, ring, (long)me.n_written, (int)count};
-                    me.n_written += (int64_t)count; room -= count; any_rs = true; wrote = true;
-                }
-            } else if (f.done < f.n) {
-                const size_t k = std::min(f.n - f.done, room);
-                VOXCHK(append(z, ring, STREAM_SAMPLE_RING, me.n_written, f.done, k)); me.n_written += (int64_t)k; f.done += k; room -= k; wrote |= k > 0;
-            }
-            if (f.done >= f.n && f.done < f.n + f.right && me.n_written >= (int64_t)f.goal16) {      // the right pad, behind the utterance's last 16 kHz sample
-                const size_t k = std::min(f.n + f.right - f.done, room);
-                VOXCHK(ring_write_f32(s, ring, STREAM_SAMPLE_RING, me.n_written, StreamSrc{}, 0, k)); me.n_written += (int64_t)k; f.done += k; wrote |= k > 0;
-            }
-            const int avail = (int)std::min<long>(f.target, stream_positions(left, R, me.n_written));
-            if (avail > me.pos) due.emplace_back(avail - me.pos, f.member);
-        }
-        if (any_pcm || any_rs) {      // the pass's ingest, in front of its rounds: one upload, the conversion, then the resampling (which reads what the conversion wrote)
-            HIPCHK(hipMemcpyAsync(g->d_ingest, ing, sizeof(GroupIngest), hipMemcpyHostToDevice, s));
-            if (any_pcm) HIPCHK(launch_stream_group_s16(g->d_ingest->pcm, ing->pcm, (int)fs.size(), s));
-            if (any_rs) HIPCHK(launch_stream_group_resample(g->d_ingest->rs, ing->rs, (int)fs.size(), STREAM_SAMPLE_RING - 1, s));
-        }
-        if (!wrote && due.empty()) return fail(VOX_ERR_INVALID, "internal: stream group stalled");
-        if (due.empty()) continue;
-        std::stable_sort(due.begin(), due.end(), [](const std::pair<int, int>& a, const std::pair<int, int>& b) { return a.first > b.first; });
-        g->orders.emplace_back(); std::array<int, GROUP_MAX>& ord = g->orders.back(); ord.fill(0);
-        for (size_t i = 0; i < due.size(); i++) ord[i] = due[i].second;
-        HIPCHK(hipMemcpyAsync(g->d_order, ord.data(), sizeof(int) * GROUP_MAX, hipMemcpyHostToDevice, s));      // the pass's one upload
-        int n_r = (int)due.size();
-        for (int r = 0; r < due[0].first; r++) {
-            while (due[(size_t)n_r - 1].first <= r) n_r--;
-            VOXCHK(group_round(g, w, n_r));
-        }
-        for (const std::pair<int, int>& d : due) { g->mem[d.second].pos += d.first; g->mem[d.second].steps += (uint64_t)d.first; }
+        VOXCHK(group_stage_pass(g, call, &due, &idle));
+        if (idle) return fail(VOX_ERR_INVALID, "internal: stream group stalled");
+        if (!due.empty()) VOXCHK(group_run_rounds(g, w, due));
     }
-    for (size_t k = 0; k < fs.size(); k++) if (fs[k].due > 0)
-        HIPCHK(hipMemcpyAsync(feeds[k].out_ids, g->h_mem[fs[k].member].tokens + VOX_PREFIX_TOKENS + g->mem[fs[k].member].ids_out, (size_t)fs[k].due * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));      // the call's one synchronisation: every fed member's ids land
-    g->orders.clear(); g->ingests.clear();
-    for (size_t k = 0; k < fs.size(); k++) { GroupMember& me = g->mem[fs[k].member]; me.ids_out += fs[k].due; feeds[k].n_ids = fs[k].due; if (feeds[k].finish) me.finished = true; }
-    return VOX_OK;
+    return group_drain(g, feeds, call);
 }
 extern "C" int32_t vox_stream_group_advance(vox_stream_group* g, vox_stream_feed* feeds, int32_t n_feeds, int32_t mem_kind) {
     return group_advance(g, feeds, n_feeds, mem_kind, false);
@@ -4946,6 +4944,37 @@ extern "C" int32_t vox_debug_stream_group_tap_fetch(vox_stream_group* g, int32_t
     *rows = n;
     (void)hipFree(me.tap); me.tap = nullptr; me.tap_max = 0;
     return group_upload_members(g);
+}
+
+// ---- debug: the feed planner on its own (tests/test_stream_feed_cpu.py).  No device, no model: a fresh session at `sample_rate` (R = 4, the Voxtral left pad, no position
+// limit to speak of) takes the calls (n_samples[c], finish[c]) through feed_plan and feed_pass as the drivers do, every due tick taken as run.  One row of 5 per pass:
+// call index, input samples appended, 16 kHz samples that entered the 16 kHz ring (a 16 kHz session: the appended ones), pad zeros, ticks.  pass_cap: feed_pass's in_cap (0: none).
+extern "C" int32_t vox_debug_stream_feed_passes(uint32_t sample_rate, const size_t* n_samples, const int32_t* finish, int32_t n_calls, size_t pass_cap, int64_t* rows, int32_t max_rows,
+                                                int32_t* n_rows) {
+    ARGCHK(n_rows && (n_calls == 0 || (n_samples && finish)) && (rows || max_rows == 0), "null argument"); ARGCHK(sample_rate > 0, "bad sample rate 0");
+    ARGCHK(n_calls >= 0 && max_rows >= 0, "bad count (%d calls, %d rows)", n_calls, max_rows);
+    FeedState f; f.sr = sample_rate;
+    if (sample_rate != 16000) { size_t bytes; VOXCHK(stream_rate_plan(sample_rate, &f.rp, &bytes, &f.in_ring_n)); }
+    vox_pad_cfg pc; vox_pad_cfg_voxtral(&pc); const long left = (long)pad_left(&pc); const int R = 4;
+    f.restart(VOX_PREFIX_TOKENS - 1);
+    int k = 0;
+    for (int c = 0; c < n_calls; c++) {
+        ARGCHK(finish[c] == 0 || finish[c] == 1, "call %d: finish must be 0 or 1", c); ARGCHK(n_samples[c] <= ((size_t)1 << 36), "call %d: push of %zu samples", c, n_samples[c]);
+        char who[32]; snprintf(who, sizeof who, "call %d: the session", c);
+        FeedPlan plan; VOXCHK(feed_plan(f, R, left, INT32_MAX, n_samples[c], finish[c] != 0, INT32_MAX, who, &plan));
+        f.n_pushed += (int64_t)plan.n;
+        while (feed_open(f, plan)) {
+            const FeedPass q = feed_pass(f, plan, R, left, pass_cap ? pass_cap : SIZE_MAX);
+            if (q.idle()) return fail(VOX_ERR_INVALID, "internal: call %d stalled at position %d of %d", c, f.pos, plan.target);
+            ARGCHK(k < max_rows, "more than %d passes: the output buffer is too small", max_rows);
+            int64_t* r = rows + (size_t)5 * k++;
+            r[0] = c; r[1] = (int64_t)q.n_in; r[2] = (int64_t)q.n16; r[3] = (int64_t)q.pad; r[4] = q.ticks;
+            f.pos += q.ticks;
+        }
+        f.ids_out += plan.due; f.finished = plan.finish;
+    }
+    *n_rows = k;
+    return VOX_OK;
 }
 
 // ---- debug: the sample front ends on their own (tests).  form 0: the single clip's (clip_front_end); form 1: the batch drivers' (group_peak_scales when norm_group is

@@ -383,8 +383,8 @@ struct StreamMember {
 // session is its zero pad).
 hipError_t launch_stream_mel(const StreamMember* mem, const int* order, int n, int ring_mask, long left, MelTables t, int halo_back, int n_frames, float* out, long slot_stride,
                              hipStream_t s);
-// ingest at the capture rate: the 16 kHz samples [i0, i0 + count) of the stream from its input-rate ring, with resample_apply_kernel's arithmetic (At, fft_in, fft_out, delay:
-// launch_resample's) -- bit for bit vox_resample's samples for the concatenated input.  Input sample k lives at in_ring[k & in_mask], output sample i goes to
+// ingest at the capture rate: the 16 kHz samples [i0, i0 + count) of the stream from its input-rate ring, through the device function resample_apply_kernel computes a sample
+// with (vox_kernels.hip resample_sample; At, fft_in, fft_out, delay: launch_resample's) -- bit for bit vox_resample's samples for the concatenated input.  Input sample k lives at in_ring[k & in_mask], output sample i goes to
 // out_ring[i & out_mask]; n_in: the input samples that exist (written so far, or the utterance's length at its end): blocks are clipped there.  The caller launches it only
 // for samples whose blocks are complete or clipped, and while block (i0 + delay) / fft_out - 1 is still in the input ring.  count <= out_mask + 1.
 hipError_t launch_stream_resample(const float* in_ring, int in_mask, long n_in, const float* At, int fft_in, int fft_out, int delay, float* out_ring, int out_mask, long i0, int count,
@@ -392,8 +392,8 @@ hipError_t launch_stream_resample(const float* in_ring, int in_mask, long n_in, 
 // 16-bit PCM into a stream's f32 ring: ring[(w0 + k) & mask] = float(src[k]) / 32768 for k < count <= mask + 1 (src: device memory)
 hipError_t launch_stream_s16(const short* src, int count, float* ring, int mask, long w0, hipStream_t s);
 // ---- the ingest of a stream group's pass: both kernels above with a slot dimension, ONE launch for every fed member.  Slot z reads desc[z] (device array; `host`: the
-// same n <= 16 descriptors on the host, which the launch validates: power-of-two masks, counts within the ring); slots may have count 0, a launch whose counts are all 0
-// is skipped.
+// same n <= 16 descriptors on the host, which the launch validates with the checks of the solo launches: power-of-two masks, counts within the ring, no null pointer);
+// slots may have count 0, a launch whose counts are all 0 is skipped.
 struct StreamIngest {                     // launch_stream_resample's arguments for one member; the 16 kHz ring mask is the launch's
     const float* in_ring; int in_mask;    // the member's input-rate ring
     long n_in;                            // input samples that exist (blocks are clipped there)

@@ -4089,24 +4089,34 @@ __global__ __launch_bounds__(256) void resample_matrix_kernel(const double* __re
     }
     At[e] = (float)acc;
 }
-__global__ __launch_bounds__(256) void resample_apply_kernel(const float* __restrict__ x, long n_in, const float* __restrict__ At, int fft_in, int fft_out, int delay,
-                                                             float* __restrict__ out, long n_out) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_out) return;
+// 16 kHz sample i of the resampler, for every kernel that produces one (the offline one below, the two ingest kernels of the live sessions): load(k) is input sample k,
+// n_in the input samples that exist.  The block's own first half and the previous block's tail as two fmaf chains in ascending n, no second chain at c == 0, blocks
+// clipped at n_in, then a0 + a1: one wording, so a sample has the same bits whichever kernel produced it.  `load` is a functor the compiler inlines (a plain pointer, a
+// masked ring), never a function pointer.
+template <class Load>
+__device__ __forceinline__ float resample_sample(long i, Load load, long n_in, const float* __restrict__ At, int fft_in, int fft_out, int delay) {
     const long j = i + delay, c = j / fft_out; const int m = (int)(j - c * fft_out);
     const int ld = 2 * fft_out;
     float a0 = 0.f, a1 = 0.f;
     {
         const long base = c * fft_in; const int cnt = (int)max(0L, min((long)fft_in, n_in - base));
-        const float* xp = x + base; const float* ap = At + m;
-        for (int n = 0; n < cnt; n++) a0 = fmaf(xp[n], ap[(size_t)n * ld], a0);
+        const float* ap = At + m;
+        for (int n = 0; n < cnt; n++) a0 = fmaf(load(base + n), ap[(size_t)n * ld], a0);
     }
     if (c > 0) {
         const long base = (c - 1) * fft_in; const int cnt = (int)max(0L, min((long)fft_in, n_in - base));
-        const float* xp = x + base; const float* ap = At + fft_out + m;
-        for (int n = 0; n < cnt; n++) a1 = fmaf(xp[n], ap[(size_t)n * ld], a1);
+        const float* ap = At + fft_out + m;
+        for (int n = 0; n < cnt; n++) a1 = fmaf(load(base + n), ap[(size_t)n * ld], a1);
     }
-    out[i] = a0 + a1;
+    return a0 + a1;
+}
+struct LoadPlain { const float* __restrict__ x; __device__ __forceinline__ float operator()(long k) const { return x[k]; } };                       // the whole input in memory
+struct LoadRing { const float* __restrict__ ring; long mask; __device__ __forceinline__ float operator()(long k) const { return ring[k & mask]; } };      // sample k at ring[k & mask]
+__global__ __launch_bounds__(256) void resample_apply_kernel(const float* __restrict__ x, long n_in, const float* __restrict__ At, int fft_in, int fft_out, int delay,
+                                                             float* __restrict__ out, long n_out) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_out) return;
+    out[i] = resample_sample(i, LoadPlain{x}, n_in, At, fft_in, fft_out, delay);
 }
 hipError_t launch_resample_matrix(const double* H, int new_len, int fft_in, int fft_out, float* At, hipStream_t s) {
     const long total = (long)fft_in * 2 * fft_out;
@@ -4216,88 +4226,60 @@ hipError_t launch_stream_mel(const StreamMember* mem, const int* order, int n, i
 }
 
 // ingest of a stream fed at its capture rate: resample_apply_kernel on rings.  One thread per 16 kHz sample i of [i0, i0 + count): input sample k of the stream lives at
-// in_ring[k & in_mask], output sample i goes to out_ring[i & out_mask] (the ring stream_mel_kernel reads).  The arithmetic is resample_apply_kernel's, term for term --
-// the block's own first half and the previous block's tail as two fmaf chains in ascending n, then a0 + a1, no second chain at c == 0, blocks clipped at n_in -- so every
-// sample has the bits vox_resample gives for the concatenated input; the sums are not reordered.  The host launches it only for samples whose blocks are complete (or,
-// at the end of the utterance, with n_in = its length) and keeps the input ring from block c - 1 of the oldest sample still to be produced.
+// in_ring[k & in_mask], output sample i goes to out_ring[i & out_mask] (the ring stream_mel_kernel reads).  The arithmetic is resample_sample's, shared with
+// resample_apply_kernel, so every sample has the bits vox_resample gives for the concatenated input.  The host launches it only for samples whose blocks are complete (or,
+// at the end of the utterance, with n_in = its length) and keeps the input ring from block c - 1 of the oldest sample still to be produced (vox_api.cpp feed_pass).
 // (VOX_NO_PK_F32: a0 / a1 are f32 pair arithmetic in one thread; no packed form is wanted on a stream kernel's lanes, vox_kernels.h.)
 __global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_resample_kernel(const float* __restrict__ in_ring, int in_mask, long n_in, const float* __restrict__ At, int fft_in, int fft_out,
                                                                             int delay, float* __restrict__ out_ring, int out_mask, long i0, int count) {
     const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (k >= count) return;
     const long i = i0 + k;
-    const long j = i + delay, c = j / fft_out; const int m = (int)(j - c * fft_out);
-    const int ld = 2 * fft_out;
-    float a0 = 0.f, a1 = 0.f;
-    {
-        const long base = c * fft_in; const int cnt = (int)max(0L, min((long)fft_in, n_in - base));
-        const float* ap = At + m;
-        for (int n = 0; n < cnt; n++) a0 = fmaf(in_ring[(base + n) & (long)in_mask], ap[(size_t)n * ld], a0);
-    }
-    if (c > 0) {
-        const long base = (c - 1) * fft_in; const int cnt = (int)max(0L, min((long)fft_in, n_in - base));
-        const float* ap = At + fft_out + m;
-        for (int n = 0; n < cnt; n++) a1 = fmaf(in_ring[(base + n) & (long)in_mask], ap[(size_t)n * ld], a1);
-    }
-    out_ring[i & (long)out_mask] = a0 + a1;
+    out_ring[i & (long)out_mask] = resample_sample(i, LoadRing{in_ring, (long)in_mask}, n_in, At, fft_in, fft_out, delay);
 }
+// what the host checks about one resampling descriptor with count > 0, and about one conversion descriptor: power-of-two masks, counts within the ring, no null pointer
+static bool stream_ingest_ok(const StreamIngest& d, int out_mask) {
+    return d.in_ring && d.At && d.out_ring && d.in_mask >= 0 && !(d.in_mask & (d.in_mask + 1)) && out_mask >= 0 && !(out_mask & (out_mask + 1)) && d.fft_in > 0 && d.fft_out > 0 && d.delay >= 0 &&
+           d.i0 >= 0 && d.n_in >= 0 && d.count <= out_mask + 1;
+}
+static bool stream_s16_ok(const StreamS16& d) { return d.src && d.ring && d.mask >= 0 && !(d.mask & (d.mask + 1)) && d.w0 >= 0 && d.count <= d.mask + 1; }
 hipError_t launch_stream_resample(const float* in_ring, int in_mask, long n_in, const float* At, int fft_in, int fft_out, int delay, float* out_ring, int out_mask, long i0, int count,
                                   hipStream_t s) {
     if (count <= 0) return hipSuccess;
-    if ((in_mask & (in_mask + 1)) || (out_mask & (out_mask + 1)) || in_mask < 0 || out_mask < 0 || fft_in <= 0 || fft_out <= 0 || delay < 0 || i0 < 0 || n_in < 0 || count > out_mask + 1)
-        return hipErrorInvalidValue;
+    if (!stream_ingest_ok(StreamIngest{in_ring, in_mask, n_in, At, fft_in, fft_out, delay, out_ring, i0, count}, out_mask)) return hipErrorInvalidValue;
     stream_resample_kernel<<<dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s>>>(in_ring, in_mask, n_in, At, fft_in, fft_out, delay, out_ring, out_mask, i0, count);
     attn_form_note(ATTN_FORM_STREAM_RESAMPLE);
     return hipGetLastError();
 }
 // 16-bit PCM into a stream's f32 ring: ring[(w0 + k) & mask] = float(src[k]) / 32768 (the mono 16-bit scale of audio/io.rs:110-113; a power of two: exact in f32)
+__device__ __forceinline__ float s16_to_f32(short v) { return (float)v * (1.0f / 32768.0f); }
 __global__ __launch_bounds__(256) void stream_s16_kernel(const short* __restrict__ src, int count, float* __restrict__ ring, int mask, long w0) {
     const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (k >= count) return;
-    ring[(w0 + k) & (long)mask] = (float)src[k] * (1.0f / 32768.0f);
+    ring[(w0 + k) & (long)mask] = s16_to_f32(src[k]);
 }
 hipError_t launch_stream_s16(const short* src, int count, float* ring, int mask, long w0, hipStream_t s) {
     if (count <= 0) return hipSuccess;
-    if ((mask & (mask + 1)) || mask < 0 || w0 < 0 || count > mask + 1) return hipErrorInvalidValue;
+    if (!stream_s16_ok(StreamS16{src, count, ring, mask, w0})) return hipErrorInvalidValue;
     stream_s16_kernel<<<dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s>>>(src, count, ring, mask, w0);
     return hipGetLastError();
 }
 // the two ingest kernels with a slot dimension (a stream group's pass): slot blockIdx.y works through desc[blockIdx.y], as the tick kernels work through StreamMember.
-// The grid is sized by the largest count of the pass; lanes beyond their slot's count (a slot with count 0: all of them) do nothing.
-// stream_group_resample_kernel is stream_resample_kernel term for term -- the same two fmaf chains in ascending n, the same a0 + a1, the same clipping at n_in -- so
-// every sample has vox_resample's bits whichever of the two produced it; the plans (At, fft_in, fft_out, delay) differ from slot to slot.
+// The grid is sized by the largest count of the pass; lanes beyond their slot's count (a slot with count 0: all of them) do nothing.  Both call what the solo kernels
+// call (resample_sample, s16_to_f32): a sample has the same bits whichever of the two produced it; the plans (At, fft_in, fft_out, delay) differ from slot to slot.
 __global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_group_resample_kernel(const StreamIngest* __restrict__ desc, int out_mask) {
     const StreamIngest& d = desc[blockIdx.y];
     const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (k >= d.count) return;
-    const float* __restrict__ in_ring = d.in_ring; const float* __restrict__ At = d.At;
-    const int fft_in = d.fft_in, fft_out = d.fft_out; const long in_mask = (long)d.in_mask, n_in = d.n_in;
     const long i = d.i0 + k;
-    const long j = i + d.delay, c = j / fft_out; const int m = (int)(j - c * fft_out);
-    const int ld = 2 * fft_out;
-    float a0 = 0.f, a1 = 0.f;
-    {
-        const long base = c * fft_in; const int cnt = (int)max(0L, min((long)fft_in, n_in - base));
-        const float* ap = At + m;
-        for (int n = 0; n < cnt; n++) a0 = fmaf(in_ring[(base + n) & in_mask], ap[(size_t)n * ld], a0);
-    }
-    if (c > 0) {
-        const long base = (c - 1) * fft_in; const int cnt = (int)max(0L, min((long)fft_in, n_in - base));
-        const float* ap = At + fft_out + m;
-        for (int n = 0; n < cnt; n++) a1 = fmaf(in_ring[(base + n) & in_mask], ap[(size_t)n * ld], a1);
-    }
-    d.out_ring[i & (long)out_mask] = a0 + a1;
+    d.out_ring[i & (long)out_mask] = resample_sample(i, LoadRing{d.in_ring, (long)d.in_mask}, d.n_in, d.At, d.fft_in, d.fft_out, d.delay);
 }
 hipError_t launch_stream_group_resample(const StreamIngest* desc, const StreamIngest* host, int n, int out_mask, hipStream_t s) {
     if (!desc || !host || n < 1 || n > 16 || out_mask < 0 || (out_mask & (out_mask + 1))) return hipErrorInvalidValue;
     int most = 0;
     for (int z = 0; z < n; z++) {
-        const StreamIngest& d = host[z];
-        if (d.count < 0 || d.count > out_mask + 1) return hipErrorInvalidValue;
-        if (d.count == 0) continue;
-        if (!d.in_ring || !d.At || !d.out_ring || d.in_mask < 0 || (d.in_mask & (d.in_mask + 1)) || d.fft_in <= 0 || d.fft_out <= 0 || d.delay < 0 || d.i0 < 0 || d.n_in < 0)
-            return hipErrorInvalidValue;
-        most = max(most, d.count);
+        if (host[z].count < 0 || (host[z].count > 0 && !stream_ingest_ok(host[z], out_mask))) return hipErrorInvalidValue;
+        most = max(most, host[z].count);
     }
     if (most == 0) return hipSuccess;
     stream_group_resample_kernel<<<dim3((unsigned)((most + 255) / 256), n), dim3(256), 0, s>>>(desc, out_mask);
@@ -4308,17 +4290,14 @@ __global__ __launch_bounds__(256) void stream_group_s16_kernel(const StreamS16* 
     const StreamS16& d = desc[blockIdx.y];
     const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (k >= d.count) return;
-    d.ring[(d.w0 + k) & (long)d.mask] = (float)d.src[k] * (1.0f / 32768.0f);
+    d.ring[(d.w0 + k) & (long)d.mask] = s16_to_f32(d.src[k]);
 }
 hipError_t launch_stream_group_s16(const StreamS16* desc, const StreamS16* host, int n, hipStream_t s) {
     if (!desc || !host || n < 1 || n > 16) return hipErrorInvalidValue;
     int most = 0;
     for (int z = 0; z < n; z++) {
-        const StreamS16& d = host[z];
-        if (d.count < 0) return hipErrorInvalidValue;
-        if (d.count == 0) continue;
-        if (!d.src || !d.ring || d.mask < 0 || (d.mask & (d.mask + 1)) || d.w0 < 0 || d.count > d.mask + 1) return hipErrorInvalidValue;
-        most = max(most, d.count);
+        if (host[z].count < 0 || (host[z].count > 0 && !stream_s16_ok(host[z]))) return hipErrorInvalidValue;
+        most = max(most, host[z].count);
     }
     if (most == 0) return hipSuccess;
     stream_group_s16_kernel<<<dim3((unsigned)((most + 255) / 256), n), dim3(256), 0, s>>>(desc);
