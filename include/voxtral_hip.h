@@ -341,6 +341,20 @@ int32_t vox_forward_hidden_with_cache_ex(vox_model* m, const float* x_MxD, int32
 int32_t vox_lm_head_ex(vox_model* m, const float* hidden_MxD, int32_t M, float* logits_MxV, int32_t mem_kind);
 /* `logits.argmax(2)` + the scalar read-back (bin/e2e_bench.rs:219-220; lowest index wins ties): ids_host[M]; synchronises the stream */
 int32_t vox_argmax_rows(vox_ctx* ctx, const float* logits_MxV, int32_t M, int32_t V, int32_t* ids_host, int32_t mem_kind);
+/* ---- scores: what the model thought of an id (no reference counterpart).  For a logits row L[V] (f32) and an id t:
+ *   logprob   = L[t] - (m + log sum_v exp(L[v] - m)), m = max_v L[v]: the id's log-probability under the row's softmax, in f32 with expf / logf;
+ *   runner_up = the argmax over the columns v != t by the rule of every decode form (the largest wins, the lowest index wins a tie, a NaN or -inf never wins); -1 when
+ *               no column can win (V == 1, or nothing but NaN / -inf besides t);
+ *   margin    = L[t] - L[runner_up], one f32 subtraction: 0 on an exact tie, negative when t is not the row's argmax, L[t] + inf (+inf for a finite L[t]) without a
+ *               runner-up;
+ *   id        = t.
+ * A -inf column adds 0 to the sum.  A row that holds a NaN, or whose maximum is not finite (+inf, or all -inf), has logprob = NaN; id and runner_up follow the rule all the
+ * same.  The record is a function of the row's values and V alone -- one scan order and one reduction tree whatever the row's address or alignment, its slot, the rows
+ * next to it or the launch -- so everything a live session claims bit for bit about its ids (cuts, ring wrap, isolation, capture rate) holds for its scores. */
+typedef struct { float logprob; float margin; int32_t runner_up; int32_t id; } vox_token_score;
+/* rows of logits -> one record per row, the piecewise caller's companion to vox_argmax_rows (same mem_kind for the logits).  ids_or_null (host, M entries, each in [0, V)):
+ * the id to score; null: the row's argmax as vox_argmax_rows gives it.  out: host, M records.  Computed on the device either way (host logits are uploaded).  Synchronises. */
+int32_t vox_score_rows(vox_ctx* ctx, const float* logits_MxV, int32_t M, int32_t V, const int32_t* ids_or_null, vox_token_score* out, int32_t mem_kind);
 /* lm_head + argmax + read-back in one call: M token ids come back instead of M x 512 KB of logits; synchronises the stream */
 int32_t vox_lm_head_argmax(vox_model* m, const float* hidden_MxD, int32_t M, int32_t* ids_host, int32_t mem_kind);
 /* Q4VoxtralModel::generate_step_with_cache, gguf/model.rs:857-867 (text tokens only: embed -> decoder against the cache -> final norm -> lm_head) in one call;
@@ -498,6 +512,16 @@ int32_t vox_stream_schedule(size_t n_samples, int32_t finished, int32_t* positio
 /* the same for a stream fed at sample_rate Hz: *samples_16k = avail16(n_samples) (finished = 0) or vox_resample_len(n_samples) (finished = 1), positions and ids are
  * vox_stream_schedule's for that many 16 kHz samples.  Rate 16000 gives vox_stream_schedule's answers.  Push and finish check `cap` against this schedule. */
 int32_t vox_stream_schedule_rate(size_t n_samples, uint32_t sample_rate, int32_t finished, int32_t* positions, int32_t* ids, size_t* samples_16k);
+/* SCORES.  With scores on, every id the stream hands out comes with a vox_token_score (above) computed from the f32 logits row of its decode step: one more launch per
+ * tick behind the tick's last kernel (plus, on the per-operator decode step, the logits row written out) and one more copy in front of the call's one synchronisation;
+ * the ids themselves do not change, and a stream that never turns scores on allocates and launches nothing.  The records are bit for bit a function of what the ids are a
+ * function of.  vox_stream_set_scores: on = 0 / 1, takes effect with the next push / finish, survives vox_stream_reset; the first on = 1 allocates the records (16 bytes
+ * per position the stream was created for) and one logits row on the device, counted in vox_stream_info [5] from then on.
+ * vox_stream_scores: the records of ids [first_id, first_id + n) of the current utterance from a host array the stream keeps (no device is touched); the range must lie
+ * within the ids handed out so far (vox_stream_info [2]), else VOX_ERR_INVALID and nothing is written.  An id handed out while scores were off has logprob = margin = NaN,
+ * runner_up = -1 and its id.  Steps a decode-engine hand-off timeout takes back are scored again from the re-run's logits. */
+int32_t vox_stream_set_scores(vox_stream* s, int32_t on);
+int32_t vox_stream_scores(const vox_stream* s, int32_t first_id, int32_t n, vox_token_score* out);
 /* test tap, modelled on vox_debug_batch_tap_*: from now on keep the f32 logits row behind each id handed out (up to max_rows); fetch copies them to the host
  * ([min(rows, max_rows)][vocab]; *rows = rows produced since arm) and ends the tap */
 int32_t vox_debug_stream_tap_arm(vox_stream* s, int32_t max_rows);
@@ -565,6 +589,10 @@ int32_t vox_stream_group_reset_rate(vox_stream_group* g, int32_t member, float g
 /* vox_stream_info's eight words for the member; [5] is the member's share of the group's device bytes, [6] is 0 (no engine step), [7] counts the member's ticks */
 int32_t vox_stream_group_info(const vox_stream_group* g, int32_t member, int64_t out[8]);
 int32_t vox_stream_group_free(vox_stream_group* g);
+/* vox_stream_set_scores / vox_stream_scores for one member (SCORES above): the flag survives the member's resets; a round launches the score kernel once for all its
+ * slots, and only while some member has scores on; the member's records are counted in vox_stream_group_info [5] */
+int32_t vox_stream_group_set_scores(vox_stream_group* g, int32_t member, int32_t on);
+int32_t vox_stream_group_scores(const vox_stream_group* g, int32_t member, int32_t first_id, int32_t n, vox_token_score* out);
 /* vox_debug_stream_tap_* for one member (the rows are copied by the tick's last kernel; a reset of the member starts the count again) */
 int32_t vox_debug_stream_group_tap_arm(vox_stream_group* g, int32_t member, int32_t max_rows);
 int32_t vox_debug_stream_group_tap_fetch(vox_stream_group* g, int32_t member, float* out, int32_t* rows);

@@ -4,6 +4,7 @@
     python tools/stream_bench.py [--gguf PATH] [--ticks 200] [--passes 3] [--out profiles/stream_tick.txt]
     python tools/stream_bench.py --group 1,2,4,8,16 [--out profiles/stream_group_tick.txt]
     python tools/stream_bench.py --group 1,4,16 --rate 48000 --s16 [--out profiles/stream_group_rate_tick.txt]
+    python tools/stream_bench.py --scores [--group 1,4,16] [--out profiles/stream_scores_tick.txt]
 
  * stream: HIP events on the context's stream around ONE push of `ticks` x 2560 samples (a large push is a loop of identical ticks), at encoder positions past the
    750-row window, median of `passes` passes; launches per tick from the library's launch counters plus the fixed launches of a tick; wall time of single 160 ms pushes
@@ -19,6 +20,9 @@
    round of the same run: what the ingest costs (the larger host copies, the conversion and resampling launches, the extra passes of a push larger than the input ring).
    A fourth pass feeds a third group at SR Hz from device memory, which takes the host copies out of the difference.  A round grows with the decoder position, so
    all three groups are warmed alike and run one timed pass per loop: pass i of each covers the same positions (the rate groups' to within one tick).
+ * --scores: what scores cost (vox_stream_set_scores: one more launch per tick, one logits row written and read per session).  A second solo stream -- with --group
+   also a second group -- runs with scores on, warmed like the first and timed the same way in the same loop: pass i of the scored session follows pass i of the
+   unscored one and covers the same positions.  The unscored figures are the tool's usual ones (comparable with a run without the flag); the difference is reported.
  * derived figures are labelled as derived."""
 import argparse
 import ctypes as C
@@ -87,6 +91,13 @@ def bench_groups(pkg, ctx, m, t, tm, a, widths, lines):
         st = m.create_stream(t, gain=gain); g = m.create_stream_group(t, N, gains=[gain] * N)
         pos = 40 + 2560 * warm
         st.push(x[:pos]); g.advance({k: x[:pos] for k in range(N)})
+        if a.scores:      # the scored twins
+            st_s = m.create_stream(t, gain=gain); g_s = m.create_stream_group(t, N, gains=[gain] * N)
+            st_s.set_scores(True); st_s.push(x[:pos])
+            for k in range(N):
+                g_s.set_scores(k, True)
+            g_s.advance({k: x[:pos] for k in range(N)})
+            solo_s, grp_s = [], []
         if sr:
             g2, g3 = (m.create_stream_group(t, N, gains=[gr] * N, sample_rates=[sr] * N) for _ in range(2)); rpos = per * (warm + 1)      # fed from host / device memory
             for gg in (g2, g3):
@@ -99,6 +110,8 @@ def bench_groups(pkg, ctx, m, t, tm, a, widths, lines):
             feeds = {k: seg for k in range(N)}
             grp.append(tm.ms(lambda: g.advance(feeds)) / a.ticks); k2 = launch_counts(pkg)
             ks += sum(k1) - sum(k0); kg += sum(k2) - sum(k1)
+            if a.scores:
+                solo_s.append(tm.ms(lambda: st_s.push(seg)) / a.ticks); grp_s.append(tm.ms(lambda: g_s.advance(feeds)) / a.ticks)
             if sr:      # the rate groups: `ticks` ticks' worth of the same input from host memory and from device memory; per tick actually run
                 n = per * a.ticks
                 for gg, out, device in ((g2, rate, False), (g3, rate_dev, True)):
@@ -116,6 +129,9 @@ def bench_groups(pkg, ctx, m, t, tm, a, widths, lines):
                 rpos += n
         assert g.info(N - 1)["positions"] == st.info()["positions"] == 38 + warm + a.ticks * a.passes
         st.close(); g.close()
+        if a.scores:
+            assert g_s.info(N - 1)["positions"] == st_s.info()["positions"] == 38 + warm + a.ticks * a.passes and not np.isnan(st_s.scores()["logprob"]).any()
+            st_s.close(); g_s.close()
         if sr:
             g2.close(); g3.close(); rate_rows.append((N, statistics.median(rate), statistics.median(rate_dev), statistics.median(grp), rate, rate_dev))
         ticks = a.ticks * a.passes; tick = statistics.median(solo); rnd = statistics.median(grp)
@@ -123,6 +139,10 @@ def bench_groups(pkg, ctx, m, t, tm, a, widths, lines):
         rows.append((N, rnd, tick))
         lines += [f"group of {N:2d}: round median {rnd:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in grp) + f"   solo tick median {tick:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in solo),
                   f"  round / ({N} x solo tick) = {rnd / (N * tick):.3f}   per member and tick {rnd / N:.3f} ms   launches per round {lg:.0f} (solo tick {ls:.0f})"]
+        if a.scores:
+            ts, rs = statistics.median(solo_s), statistics.median(grp_s)
+            lines += [f"  scores on, group of {N:2d}: round median {rs:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in grp_s) + f"   difference to scores off {rs - rnd:+.3f} ms ({100 * (rs - rnd) / rnd:+.2f} %), per pass " + " ".join(f"{v - w:+.3f}" for v, w in zip(grp_s, grp)),
+                      f"  scores on, solo tick: median {ts:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in solo_s) + f"   difference to scores off {ts - tick:+.3f} ms ({100 * (ts - tick) / tick:+.2f} %), per pass " + " ".join(f"{v - w:+.3f}" for v, w in zip(solo_s, solo))]
     lines.append("derived: members one GPU serves in real time at each width = N x 160 ms / round: " + ", ".join(f"{N}: {N * 160.0 / r:.0f}" for N, r, _ in rows))
     if sr:
         what = f"{sr} Hz {'s16' if a.s16 else 'f32'}"
@@ -139,6 +159,7 @@ def main():
     ap.add_argument("--group", help="N[,N...]: measure stream-group rounds of these widths next to the solo tick instead of the solo tick and its baseline")
     ap.add_argument("--rate", type=int, default=0, metavar="SR", help="with --group: also time a group whose members are all fed at SR Hz, next to the 16 kHz f32 round")
     ap.add_argument("--s16", action="store_true", help="with --rate: feed that group 16-bit PCM")
+    ap.add_argument("--scores", action="store_true", help="also time a stream (with --group: and a group) with scores on, pass by pass next to the unscored one")
     a = ap.parse_args()
     if (a.rate or a.s16) and not a.group or (a.s16 and not a.rate):
         ap.error("--rate applies with --group, --s16 with --rate")
@@ -176,15 +197,19 @@ def main():
     # ---- the stream
     st = m.create_stream(t, gain=gain)
     pos = 40 + 2560 * warm; st.push(x[:pos])
-    k0 = launch_counts(pkg); e0 = st.info()
-    per = []
+    if a.scores:
+        st_s = m.create_stream(t, gain=gain); st_s.set_scores(True); st_s.push(x[:pos])
+    e0 = st.info()
+    per = []; per_s = []; counted = 0
     for _ in range(a.passes):
         seg = x[pos:pos + 2560 * a.ticks]; pos += 2560 * a.ticks
-        per.append(tm.ms(lambda: st.push(seg)) / a.ticks)
-    k1 = launch_counts(pkg); e1 = st.info()
+        k0 = launch_counts(pkg); per.append(tm.ms(lambda: st.push(seg)) / a.ticks); k1 = launch_counts(pkg); counted += sum(k1) - sum(k0)
+        if a.scores:
+            per_s.append(tm.ms(lambda: st_s.push(seg)) / a.ticks)
+    e1 = st.info()
     ticks = a.ticks * a.passes
     eng = (e1["engine_steps"] - e0["engine_steps"]) / ticks
-    counted = ((k1[0] - k0[0]) + (k1[1] - k0[1])) / ticks       # attention forms (ring attention, the engine's whole step) + linear forms
+    counted = counted / ticks                                  # attention forms (ring attention, the engine's whole step) + linear forms
     fixed = 1 + 2 * c.enc_layers + 1 + 1 + 1                   # stream_mel, two RMSNorms per encoder layer, final norm, stream_embed, stream_advance
     wall = []
     for _ in range(30):
@@ -197,6 +222,12 @@ def main():
               f"  conv stem form shipped: dense2 im2col GEMM on the halo buffer (M = 9 and M = 4); a small-M form was not built, so there is no second number",
               f"  split front end / layers / adapter / decode step: not measured (events sit around whole pushes); graph replay: not built, the tick is launched eagerly",
               f"  wall time of a 160 ms host-memory push until its id is back: median {statistics.median(wall):.3f} ms  min {min(wall):.3f}  max {max(wall):.3f}  (30 pushes)"]
+
+    if a.scores:
+        assert not np.isnan(st_s.scores()["logprob"]).any(); st_s.close()
+        ts = statistics.median(per_s)
+        lines.append(f"stream tick with scores on (a second stream, pass i behind pass i above): median {ts:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in per_s) +
+                     f"   difference to scores off {ts - tick:+.3f} ms ({100 * (ts - tick) / tick:+.2f} %), per pass " + " ".join(f"{v - w:+.3f}" for v, w in zip(per_s, per)))
 
     # ---- the baseline: 16-frame chunks through the cached encoder + one piecewise decoder step per chunk
     mel = np.ascontiguousarray(pkg.MelSpectrogram.voxtral(ctx).compute_log(pkg.pad_audio(pkg.peak_normalize(x))).T)      # [128][T]

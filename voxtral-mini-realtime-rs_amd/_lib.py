@@ -34,6 +34,11 @@ class StreamFeed(C.Structure):
                 ("n_ids", C.c_int32)]
 
 
+class TokenScore(C.Structure):
+    """vox_token_score: what a live session knows about one id it handed out"""
+    _fields_ = [("logprob", C.c_float), ("margin", C.c_float), ("runner_up", C.c_int32), ("id", C.c_int32)]
+
+
 class ModelCfg(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("enc_layers", "enc_dim", "enc_heads", "enc_head_dim", "enc_ffn", "enc_window",
                                          "dec_layers", "dec_dim", "dec_heads", "dec_kv_heads", "dec_head_dim", "dec_ffn",
@@ -184,6 +189,11 @@ SIGNATURES = {
     "vox_stream_group_reset_rate": (i32, [vp, i32, f32, u32]),
     "vox_stream_group_advance_s16": (i32, [vp, vp, i32, i32]),
     "vox_debug_stream_feed_passes": (i32, [u32, P(sz), P(i32), i32, sz, P(i64), i32, P(i32)]),
+    "vox_score_rows": (i32, [vp, vp, i32, i32, vp, vp, i32]),
+    "vox_stream_set_scores": (i32, [vp, i32]),
+    "vox_stream_scores": (i32, [vp, i32, i32, vp]),
+    "vox_stream_group_set_scores": (i32, [vp, i32, i32]),
+    "vox_stream_group_scores": (i32, [vp, i32, i32, i32, vp]),
 }
 
 _LIB = None

@@ -71,13 +71,22 @@ def transcribe_one(pkg, path, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed
     return " ".join(texts)
 
 
-def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_rate=False):
+def write_words(out, pkg, path, ids, scores, tokenizer, rate):
+    """--live-words: one JSON line per word of a file that has ended (pkg.words: text, first_id, last_id, due_s, logprob, min_margin) + the file's path."""
+    import json
+    for w in pkg.words(ids, scores, tokenizer, sample_rate=rate):
+        out.write(json.dumps(dict(w, file=path), ensure_ascii=False) + "\n")
+    out.flush()
+
+
+def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_rate=False, words_out=None):
     """--live: the file through a live session (vox_stream) in pieces of `chunk_ms` milliseconds, the text so far on stderr whenever ids arrive.  The gain is the
     file's peak scale 0.95 / max|x| (bin/transcribe.rs:207; a file is known in advance -- a microphone caller passes its own), the whole file is one utterance (no
     --max-mel-frames chunks: the session's state is bounded by its ring), so the line equals the un-chunked path's.
     native_rate (--live-native-rate), for a file that is not at 16 kHz: the session is created for the file's rate and pushed the file's own samples -- what a capture
     device would deliver; it resamples as the samples arrive.  The gain stays the peak scale of the RESAMPLED file (computed here only because the file is known in
-    advance and the line is to be compared), so the line equals the one without the flag."""
+    advance and the line is to be compared), so the line equals the one without the flag.
+    words_out (--live-words): the session runs with scores on and the file's words go there when it ends; the ids, hence the line, are the same."""
     x, sr = load_wav(path)
     rate = 16000
     if sr != 16000:
@@ -94,6 +103,8 @@ def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_
     step = max(1, int(round(rate * chunk_ms / 1000.0)))
     stream = model.create_stream(t_embed, gain=gain, sample_rate=rate)
     try:
+        if words_out is not None:
+            stream.set_scores(True)
         ids = []
         text = lambda: tokenizer.decode([t for t in ids if t >= 1000]).strip()   # :309-318
         for a in range(0, x.size, step):
@@ -101,20 +112,25 @@ def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_
             if new.size:
                 ids.extend(int(t) for t in new); log(f"  [{min(a + step, x.size) / rate:8.2f} s] {text()}")
         ids.extend(int(t) for t in stream.finish())
+        if words_out is not None:
+            write_words(words_out, pkg, path, ids, stream.scores(), tokenizer, rate)
         return text()
     finally:
         stream.close()
 
 
-def transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, chunk_ms, n_members):
+def transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, chunk_ms, n_members, words_out=None):
     """--live-group N: the files N at a time through one stream group (vox_stream_group) in pieces of `chunk_ms` milliseconds: every call feeds each busy member its
     next piece, a file that ends (its member fed with finish) frees the member for the next file in input order.  Gains and lines as transcribe_live's (16 kHz: other
-    rates are resampled first).  -> {file index: text}; a file that cannot be read is left out (the one-by-one path reports it)."""
+    rates are resampled first).  -> {file index: text}; a file that cannot be read is left out (the one-by-one path reports it).  words_out (--live-words): every
+    member runs with scores on, a file's words go there when the file ends."""
     step = max(1, int(round(16000 * chunk_ms / 1000.0)))
     group = model.create_stream_group(t_embed, n_members)
     text = lambda ids: tokenizer.decode([t for t in ids if t >= 1000]).strip()
     texts = {}; busy = {}; nxt = 0      # busy: member -> [file index, samples, offset, ids]
     try:
+        for k in range(n_members if words_out is not None else 0):
+            group.set_scores(k, True)
         while nxt < len(paths) or busy:
             for k in range(n_members):
                 while k not in busy and nxt < len(paths):
@@ -139,6 +155,8 @@ def transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, chunk_ms, 
                     b[3].extend(int(t) for t in new); log(f"  [{paths[b[0]]} {min(b[2], b[1].size) / 16000:8.2f} s] {text(b[3])}")
             for k in last:
                 b = busy.pop(k); texts[b[0]] = text(b[3])
+                if words_out is not None:
+                    write_words(words_out, pkg, paths[b[0]], b[3], group.scores(k), tokenizer, 16000)
         return texts
     finally:
         group.close()
@@ -285,7 +303,12 @@ def main(argv=None):
                     "for that rate (it resamples as they arrive) instead of resampling the whole file first; the line is the same")
     ap.add_argument("--live-group", type=int, default=0, metavar="N", help="with --live: feed the files N (2..16) at a time through one stream group (vox_stream_group): every "
                     "weight matrix is read once per tick for all files that have a tick due; same final lines, in input order")
+    ap.add_argument("--live-words", metavar="PATH", help="with --live: run the sessions with scores on (vox_stream_set_scores) and write one JSON line per word to PATH when "
+                    "a file ends: text, first_id / last_id (indices into the file's ids), due_s (when the session hands the word's last id out, in seconds of pushed audio: "
+                    "not where the word was said), logprob (summed over the word's ids), min_margin (the smallest top-2 margin among them), file; stdout is unchanged")
     a = ap.parse_args(argv)
+    if a.live_words and not a.live:
+        ap.error("--live-words applies with --live")
     if a.live_group and not a.live:
         ap.error("--live-group applies with --live")
     if a.live_group and not 2 <= a.live_group <= 16:
@@ -357,6 +380,7 @@ def main(argv=None):
     chunk_cfg = pkg.ChunkConfig.voxtral().with_max_frames(a.max_mel_frames)
     rc = 0
     texts = {}
+    words_out = open(a.live_words, "w", encoding="utf-8") if a.live_words else None
     if a.batch > 1:
         # every file -> its chunks (transcribe.rs:210-226); ALL units of this rank's share go to vox_transcribe_batch_ex in calls of <= --batch units (continuous batching
         # over decode slots); a file's line = its chunk texts joined by " " (:261-275).  Files with a failed unit fall back to the one-by-one path below.
@@ -374,9 +398,11 @@ def main(argv=None):
             texts = join_units(len(paths), units, unit_texts)
     if a.live_group:
         try:
-            texts = transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_group)
+            texts = transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_group, words_out)
         except Exception as e:      # the files fall back to one live session each
             log(f"Error in the stream group: {e}"); texts = {}
+            if words_out is not None:      # the files' words come again with their lines
+                words_out.seek(0); words_out.truncate()
     def one(i):
         nonlocal rc
         if i in texts:
@@ -384,7 +410,7 @@ def main(argv=None):
         p = paths[i]
         try:
             t1 = time.time()
-            text = transcribe_live(pkg, p, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_native_rate) if a.live else transcribe_one(pkg, p, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed)
+            text = transcribe_live(pkg, p, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_native_rate, words_out) if a.live else transcribe_one(pkg, p, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed)
             log(f"{p}: {time.time() - t1:.3f}s")
         except Exception as e:      # per-utterance failure isolates to that line (empty), eval_wer.py:211-223 tolerates it
             log(f"Error transcribing {p}: {e}"); text = ""; rc = 1
@@ -401,6 +427,8 @@ def main(argv=None):
     else:
         for i in range(len(paths)):
             print(one(i), flush=True)
+    if words_out is not None:
+        words_out.close()
     if own_group:
         import torch.distributed as dist
         dist.barrier(); dist.destroy_process_group()

@@ -3721,6 +3721,26 @@ extern "C" int32_t vox_argmax_rows(vox_ctx* c, const float* logits, int32_t M, i
     return VOX_OK;
 }
 
+// vox_argmax_rows' companion: a vox_token_score per row (launch_score_rows: the kernel the live sessions' scores come from).  Every check before the context is
+// bound; host logits are uploaded -- there is one implementation, the device's.  out host; synchronises.
+static_assert(sizeof(vox_token_score) == 16 && sizeof(TokenScore) == sizeof(vox_token_score), "vox_token_score is TokenScore");
+extern "C" int32_t vox_score_rows(vox_ctx* c, const float* logits, int32_t M, int32_t V, const int32_t* ids, vox_token_score* out, int32_t mem_kind) {
+    ARGCHK(c && logits && out, "null argument"); ARGCHK(M > 0 && V > 0, "bad shape %d x %d", M, V);
+    ARGCHK(mem_kind == VOX_MEM_HOST || mem_kind == VOX_MEM_DEVICE, "bad mem_kind %d", mem_kind);
+    for (int r = 0; ids && r < M; r++) ARGCHK(ids[r] >= 0 && ids[r] < V, "row %d: id %d outside the %d columns", r, ids[r], V);
+    VOXCHK(ctx_bind(c));
+    hipStream_t s = c->stream; DevBuf dx, di, dout;
+    HIPCHK(dout.alloc_pooled(c, (size_t)M * sizeof(TokenScore)));
+    if (mem_kind == VOX_MEM_HOST) {
+        HIPCHK(dx.alloc_pooled(c, (size_t)M * V * 4)); HIPCHK(hipMemcpyAsync(dx.p, logits, (size_t)M * V * 4, hipMemcpyHostToDevice, s)); logits = dx.as<float>();
+    }
+    if (ids) { HIPCHK(di.alloc_pooled(c, (size_t)M * 4)); HIPCHK(hipMemcpyAsync(di.p, ids, (size_t)M * 4, hipMemcpyHostToDevice, s)); }
+    HIPCHK(launch_score_rows(logits, M, V, ids ? di.as<int>() : nullptr, dout.as<TokenScore>(), s));
+    HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)M * sizeof(TokenScore), hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
+    if (c->pw_model) return pw_after_sync(c->pw_model);      // (a synchronising call of the piecewise surface, as vox_argmax_rows)
+    return VOX_OK;
+}
+
 // lm_head + argmax in one call: the token id comes back, not 512 KB of logits per row.  ids host; synchronises.
 extern "C" int32_t vox_lm_head_argmax(vox_model* m, const float* hidden, int32_t M, int32_t* ids, int32_t mem_kind) {
     ARGCHK(m && hidden && ids && M > 0, "bad argument"); VOXCHK(ctx_bind(m->ctx));
@@ -4121,6 +4141,30 @@ struct FeedState {
     int pos = 0, ids_out = 0; bool finished = false;      // decoder position of the next tick; ids handed to the caller; the utterance has ended (until a reset)
     void restart(int PC) { n_pushed = n_written = in_written = 0; pos = PC; ids_out = 0; finished = false; }      // create / reset: the session starts behind the prefix
 };
+// A session's scores (vox_stream_set_scores; DESIGN.md section 8, "Scores"): the device records the score kernel writes, one per id of the utterance, and their host
+// mirror -- one record per id handed out, the ones of a call copied in front of its synchronisation.  Nothing is allocated before the first set(1).
+struct ScoreState {
+    bool on = false; TokenScore* dev = nullptr; int cap = 0;
+    std::vector<vox_token_score> host;
+    size_t bytes() const { return dev ? (size_t)cap * sizeof(TokenScore) : 0; }
+    // in front of the call's synchronisation: room for the call's `due` records behind the `have` handed out so far, their copy enqueued when scores are on
+    int32_t enqueue(int have, int due, hipStream_t s) {
+        host.resize((size_t)have + due);
+        if (on && due > 0) HIPCHK(hipMemcpyAsync(host.data() + have, dev + have, (size_t)due * sizeof(TokenScore), hipMemcpyDeviceToHost, s));
+        return VOX_OK;
+    }
+    // behind it: the ids of a call that ran with scores off get the records that say so
+    void settle(int have, int due, const int32_t* ids) {
+        const float nan = NAN;
+        for (int i = 0; !on && i < due; i++) host[(size_t)have + i] = vox_token_score{nan, nan, -1, ids[i]};
+    }
+    int32_t read(int have, int32_t first_id, int32_t n, vox_token_score* out) const {
+        ARGCHK(first_id >= 0 && n >= 0 && (int64_t)first_id + n <= have, "%d ids from %d on: %d handed out", n, first_id, have);
+        ARGCHK(out || n == 0, "null output");
+        if (n > 0) std::memcpy(out, host.data() + first_id, (size_t)n * sizeof(vox_token_score));
+        return VOX_OK;
+    }
+};
 struct vox_stream {
     vox_model* m = nullptr; vox_ctx* ctx = nullptr;
     std::vector<float> t_embed; float gain = 1.0f;
@@ -4137,6 +4181,7 @@ struct vox_stream {
     uint64_t eng_steps = 0, op_steps = 0, verified_eng_steps = 0, verified_op_steps = 0, bytes = 0;
     EngBinding eng;      // the decode engine's layer table for the stream's cache, its argmax partials (256), the pinned host copy of its error word
     float* tap = nullptr; int tap_max = 0, tap_rows = 0;
+    ScoreState sc; float* score_row = nullptr;      // scores: the records, and the logits row a scored step writes when no tap row takes it
     float *ftap_mel = nullptr, *ftap_conv = nullptr; int ftap_max = 0, ftap_ticks = 0;      // vox_debug_stream_front_tap_*: per tick its 4 R fresh mel frames and its R conv-stem rows
     int h_state[STRM_WORDS]; int h_pos_word = 0;
 };
@@ -4242,6 +4287,7 @@ static int32_t stream_load_initial(vox_stream* st) {
                        [&]() -> int32_t { HIPCHK(engine_tab_enqueue(m, st->eng, st->dec)); return VOX_OK; }));
     st->feed.restart(st->PC); st->verified_pos = st->PC; st->eng_unverified = false;
     st->eng_steps = st->op_steps = st->verified_eng_steps = st->verified_op_steps = 0; st->tap_rows = st->verified_tap_rows = 0; st->ftap_ticks = 0;
+    st->sc.host.clear();      // the utterance's records start over; the flag stays
     return VOX_OK;
 }
 
@@ -4250,7 +4296,7 @@ static void stream_release(vox_stream* st) {
     (void)hipSetDevice(st->ctx->device); (void)hipStreamSynchronize(st->ctx->stream);      // never dereferences st->m: a stream may not outlive its model, but freeing it late must not crash
     cache_release(st->dec);
     for (void* p : {(void*)st->kring, (void*)st->vring, (void*)st->samples, (void*)st->audio_keep, (void*)st->ws, (void*)st->tokens, (void*)st->state, (void*)st->tap, (void*)st->ftap_mel, (void*)st->ftap_conv,
-                    (void*)st->feed.At, (void*)st->feed.in_ring, (void*)st->s16_stage, (void*)st->d_mem}) if (p) (void)hipFree(p);
+                    (void*)st->feed.At, (void*)st->feed.in_ring, (void*)st->s16_stage, (void*)st->d_mem, (void*)st->sc.dev, (void*)st->score_row}) if (p) (void)hipFree(p);
     binding_release(st->eng);
     delete st;
 }
@@ -4340,9 +4386,10 @@ extern "C" int32_t vox_stream_info(const vox_stream* st, int64_t out[8]) {
 }
 
 // the decode step of a tick: input row in the stream's h buffer, position in the state block.  enc_rows = 0: the re-run of an unverified step (the state's encoder
-// words stay).  logits_row: where the step's f32 logits go (the tap), or null.
+// words stay).  logits_row: where the step's f32 logits go (the tap), or null.  With scores on, stream_score_kernel follows the advance kernel.
 static int32_t stream_decode_step(vox_stream* st, float* h, float* logits_row, int enc_rows) {
     vox_model* m = st->m; hipStream_t s = st->ctx->stream; vox_cache* kc = st->dec;
+    if (st->sc.on && !logits_row) logits_row = st->score_row;      // a scored step always leaves its logits: in the tap's row, else in the stream's own
     ARGCHK(kc->len == st->feed.pos && st->feed.pos < kc->max_seq, "internal: stream decoder cache at %d, position %d of %d", kc->len, st->feed.pos, kc->max_seq);
     int* pos_word = st->state + STRM_POS;
     if (engine_bind(m, st->eng, kc)) {      // one launch: the layers against the stream's cache + final norm + lm_head (argmax partials, logits on request)
@@ -4356,6 +4403,8 @@ static int32_t stream_decode_step(vox_stream* st, float* h, float* logits_row, i
         HIPCHK(launch_stream_advance(m->d_part_val, m->d_part_idx, m->n_parts, st->tokens, st->state, enc_rows, 4 * enc_rows, st->cap, s));
         st->op_steps++;
     }
+    // the emitted id's record, behind the advance launch of either path -- and of the re-run's steps, which come through here again
+    if (st->sc.on) HIPCHK(launch_stream_score(logits_row, m->cfg.vocab, st->d_mem, st->d_order, 1, VOX_PREFIX_TOKENS, s));
     kc->len = ++st->feed.pos;
     return VOX_OK;
 }
@@ -4568,9 +4617,11 @@ static int32_t stream_run(vox_stream* st, const StreamSrc& src, FeedPlan& plan, 
     int32_t* ids_dev = st->tokens + VOX_PREFIX_TOKENS + f.ids_out;
     VOXCHK(stream_verify_enqueue(st));
     if (due > 0) HIPCHK(hipMemcpyAsync(out_ids, ids_dev, (size_t)due * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));      // the call's one synchronisation: ids and the engine's verdict land together
+    VOXCHK(st->sc.enqueue(f.ids_out, due, s));      // the records travel with the ids
+    HIPCHK(hipStreamSynchronize(s));      // the call's one synchronisation: ids, their records and the engine's verdict land together
     bool reran = false; VOXCHK(stream_settle(st, &reran));
-    if (reran && due > 0) { HIPCHK(hipMemcpyAsync(out_ids, ids_dev, (size_t)due * 4, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s)); }
+    if (reran && due > 0) { HIPCHK(hipMemcpyAsync(out_ids, ids_dev, (size_t)due * 4, hipMemcpyDeviceToHost, s)); VOXCHK(st->sc.enqueue(f.ids_out, due, s)); HIPCHK(hipStreamSynchronize(s)); }
+    st->sc.settle(f.ids_out, due, out_ids);
     f.ids_out += due; *n_ids = due;
     return VOX_OK;
 }
@@ -4598,6 +4649,32 @@ extern "C" int32_t vox_stream_finish(vox_stream* st, int32_t* out_ids, int32_t c
     VOXCHK(stream_run(st, StreamSrc{}, plan, out_ids, n_ids));
     st->feed.finished = true;
     return VOX_OK;
+}
+
+// scores on / off.  The first on allocates the records and the logits row; the stream's descriptor carries the records' pointer only while scores are on (the kernel's
+// own check), uploaded behind a synchronisation: nothing of an earlier call is in flight then
+extern "C" int32_t vox_stream_set_scores(vox_stream* st, int32_t on) {
+    ARGCHK(st, "null stream"); ARGCHK(on == 0 || on == 1, "on must be 0 or 1"); VOXCHK(ctx_bind(st->ctx));
+    hipStream_t s = st->ctx->stream; ScoreState& sc = st->sc;
+    if (on && !sc.dev) {
+        const int cap = st->max_pos + 2; const size_t row_b = (size_t)st->m->cfg.vocab * 4;
+        TokenScore* d = nullptr; float* row = nullptr;
+        if (hipMalloc((void**)&d, (size_t)cap * sizeof(TokenScore)) != hipSuccess || hipMalloc((void**)&row, row_b) != hipSuccess) {
+            (void)hipGetLastError(); if (d) (void)hipFree(d);
+            return fail(VOX_ERR_HIP, "hipMalloc of the stream's score records failed");
+        }
+        sc.dev = d; sc.cap = cap; st->score_row = row; st->bytes += sc.bytes() + row_b;
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    struct { TokenScore* p; int cap; } w{on ? sc.dev : nullptr, on ? sc.cap : 0};
+    HIPCHK(hipMemcpyAsync(&st->d_mem->scores, &w.p, sizeof w.p, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(&st->d_mem->scores_cap, &w.cap, sizeof w.cap, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    sc.on = on != 0;
+    return VOX_OK;
+}
+extern "C" int32_t vox_stream_scores(const vox_stream* st, int32_t first_id, int32_t n, vox_token_score* out) {
+    ARGCHK(st, "null stream");
+    return st->sc.read(st->feed.ids_out, first_id, n, out);
 }
 
 extern "C" int32_t vox_debug_stream_tap_arm(vox_stream* st, int32_t max_rows) {
@@ -4655,6 +4732,7 @@ static const int GROUP_MAX = 16, GROUP_DEFAULT_POSITIONS = 2048;
 struct GroupMember {
     FeedState feed;                      // the member's host mirror; at a capture rate: its own input ring, a copy of its rate's plan, the rate's matrix (owned by the rate table)
     int rate = -1; uint64_t steps = 0;   // its slot of the group's rate table (-1: 16 kHz); its ticks, each one row of an xf_chain step
+    ScoreState sc;                       // its scores (vox_stream_group_set_scores); h_mem[i].scores is sc.dev while they are on
     int h_state[STRM_WORDS];
 };
 // one block matrix per rate in use, shared by the members at that rate (built by resample_matrix_build: vox_resample's bits; never the context's matrix, which goes
@@ -4675,6 +4753,7 @@ struct vox_stream_group {
     std::vector<GroupRate> rates;
     GroupIngest* d_ingest = nullptr; std::deque<GroupIngest> ingests;      // the pass's ingest descriptors on the device; the ones uploaded by the call in flight, as orders
     int16_t* s16_stage = nullptr;      // host 16-bit feeds: STREAM_SAMPLE_RING samples of device staging per member, allocated at the first one
+    int n_scored = 0;                  // members with scores on: a round launches stream_score_kernel only while there is one
 };
 // the member leaves its rate: its input ring and its reference to the rate's matrix go (the matrix with its last reference).  The caller has synchronised.
 static void group_member_drop_rate(vox_stream_group* g, int i) {
@@ -4718,13 +4797,14 @@ static int32_t group_member_seed(vox_stream_group* g, int i) {
     GroupMember& me = g->mem[i];
     VOXCHK(stream_seed(g->m, g->t_embed.data(), g->g.RC, g->g.PC, g->g.cap, g->h_mem[i].kring, g->h_mem[i].vring, &view, g->h_mem[i].tokens, g->h_mem[i].state, me.h_state,
                        []() -> int32_t { return VOX_OK; }));
-    me.feed.restart(g->g.PC); me.steps = 0;
+    me.feed.restart(g->g.PC); me.steps = 0; me.sc.host.clear();
     return VOX_OK;
 }
 static void group_release(vox_stream_group* g) {
     if (!g) return;
     (void)hipSetDevice(g->ctx->device); (void)hipStreamSynchronize(g->ctx->stream);      // never dereferences g->m (as stream_release)
     for (StreamMember& me : g->h_mem) if (me.tap) (void)hipFree(me.tap);
+    for (GroupMember& me : g->mem) if (me.sc.dev) (void)hipFree(me.sc.dev);
     for (size_t i = 0; i < g->mem.size(); i++) group_member_drop_rate(g, (int)i);
     for (void* p : {(void*)g->d_ingest, (void*)g->s16_stage, (void*)g->kring, (void*)g->vring, (void*)g->dec_k, (void*)g->dec_v, (void*)g->samples, (void*)g->ws, (void*)g->tokens, (void*)g->state, (void*)g->d_mem, (void*)g->d_order,
                     (void*)g->qkv, (void*)g->att, (void*)g->logits, (void*)g->ssq, (void*)g->xf1, (void*)g->xf2, (void*)g->xf3}) if (p) (void)hipFree(p);
@@ -4797,7 +4877,7 @@ extern "C" int32_t vox_stream_group_info(const vox_stream_group* g, int32_t memb
     const uint64_t rate_b = me.rate >= 0 ? (uint64_t)me.feed.in_ring_n * 4 + g->rates[(size_t)me.rate].bytes / (uint64_t)g->rates[(size_t)me.rate].refs : 0;
     const FeedState& f = me.feed;
     out[0] = f.n_pushed; out[1] = f.pos; out[2] = f.ids_out; out[3] = (int64_t)R * f.pos; out[4] = std::min<int64_t>((int64_t)R * f.pos, g->g.cap);
-    out[5] = (int64_t)(g->bytes / (uint64_t)g->n + tap_b + rate_b);      // the member's share of the group's device state; its own input ring, its share of its rate's matrix
+    out[5] = (int64_t)(g->bytes / (uint64_t)g->n + tap_b + rate_b + me.sc.bytes());      // the member's share of the group's device state; its own input ring, its share of its rate's matrix, its score records
     out[6] = 0; out[7] = (int64_t)me.steps;                      // no engine step; the member's ticks, each one row of an xf_chain step
     return VOX_OK;
 }
@@ -4812,6 +4892,7 @@ static int32_t group_round(vox_stream_group* g, const StreamWs& w, int n_r) {
     HIPCHK(launch_stream_group_embed(m->tok.w, g->d_mem, g->d_order, n_r, w.arow, c.dec_dim, w.h, g->xf1, m->dec[0].attn_norm, g->ssq, g->d_pos, g->d_kv_row, s));
     VOXCHK(xf_chain(m, xb, 0, n_r, 0, 0, true, 0, s));
     HIPCHK(launch_stream_group_advance(g->logits, c.vocab, g->d_mem, g->d_order, n_r, R, 4 * R, g->g.cap, s));
+    if (g->n_scored > 0) HIPCHK(launch_stream_score(g->logits, c.vocab, g->d_mem, g->d_order, n_r, VOX_PREFIX_TOKENS, s));      // slots of unscored members return at once
     return VOX_OK;
 }
 // vox_stream_group_advance and its 16-bit form, in four units: group_plan_entries (every check, nothing changed), then per pass group_stage_pass (feed_pass for every
@@ -4885,9 +4966,14 @@ static int32_t group_drain(vox_stream_group* g, vox_stream_feed* feeds, const Gr
     hipStream_t s = g->ctx->stream;
     for (size_t k = 0; k < call.fs.size(); k++) if (call.fs[k].plan.due > 0)
         HIPCHK(hipMemcpyAsync(feeds[k].out_ids, g->h_mem[call.fs[k].member].tokens + VOX_PREFIX_TOKENS + g->mem[call.fs[k].member].feed.ids_out, (size_t)call.fs[k].plan.due * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));      // the call's one synchronisation: every fed member's ids land
+    for (const GroupFeed& e : call.fs) VOXCHK(g->mem[e.member].sc.enqueue(g->mem[e.member].feed.ids_out, e.plan.due, s));      // the records travel with the ids
+    HIPCHK(hipStreamSynchronize(s));      // the call's one synchronisation: every fed member's ids and records land
     g->orders.clear(); g->ingests.clear();
-    for (size_t k = 0; k < call.fs.size(); k++) { FeedState& f = g->mem[call.fs[k].member].feed; f.ids_out += call.fs[k].plan.due; feeds[k].n_ids = call.fs[k].plan.due; if (feeds[k].finish) f.finished = true; }
+    for (size_t k = 0; k < call.fs.size(); k++) {
+        GroupMember& me = g->mem[call.fs[k].member]; FeedState& f = me.feed; const int due = call.fs[k].plan.due;
+        me.sc.settle(f.ids_out, due, feeds[k].out_ids);
+        f.ids_out += due; feeds[k].n_ids = due; if (feeds[k].finish) f.finished = true;
+    }
     return VOX_OK;
 }
 static int32_t group_advance(vox_stream_group* g, vox_stream_feed* feeds, int32_t n_feeds, int32_t mem_kind, bool s16) {
@@ -4922,6 +5008,25 @@ extern "C" int32_t vox_stream_group_advance(vox_stream_group* g, vox_stream_feed
 }
 extern "C" int32_t vox_stream_group_advance_s16(vox_stream_group* g, vox_stream_feed* feeds, int32_t n_feeds, int32_t mem_kind) {
     return group_advance(g, feeds, n_feeds, mem_kind, true);
+}
+extern "C" int32_t vox_stream_group_set_scores(vox_stream_group* g, int32_t member, int32_t on) {
+    ARGCHK(g, "null group"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1); ARGCHK(on == 0 || on == 1, "on must be 0 or 1");
+    VOXCHK(ctx_bind(g->ctx));
+    ScoreState& sc = g->mem[member].sc;
+    if (on && !sc.dev) {      // the group's logits rows are there already: a member needs its records alone
+        const int cap = g->g.max_pos + 2;
+        if (hipMalloc((void**)&sc.dev, (size_t)cap * sizeof(TokenScore)) != hipSuccess) { (void)hipGetLastError(); sc.dev = nullptr; return fail(VOX_ERR_HIP, "hipMalloc of member %d's score records failed", member); }
+        sc.cap = cap;
+    }
+    HIPCHK(hipStreamSynchronize(g->ctx->stream));
+    g->h_mem[member].scores = on ? sc.dev : nullptr; g->h_mem[member].scores_cap = on ? sc.cap : 0;
+    VOXCHK(group_upload_members(g));
+    g->n_scored += (on != 0) - (int)sc.on; sc.on = on != 0;
+    return VOX_OK;
+}
+extern "C" int32_t vox_stream_group_scores(const vox_stream_group* g, int32_t member, int32_t first_id, int32_t n, vox_token_score* out) {
+    ARGCHK(g, "null group"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1);
+    return g->mem[member].sc.read(g->mem[member].feed.ids_out, first_id, n, out);
 }
 extern "C" int32_t vox_debug_stream_group_tap_arm(vox_stream_group* g, int32_t member, int32_t max_rows) {
     ARGCHK(g, "null group"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1);

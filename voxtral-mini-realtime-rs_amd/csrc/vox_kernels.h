@@ -370,12 +370,14 @@ enum StreamWord { STRM_POS = 0,         // decoder position of the next tick (= 
                   STRM_TICKS = 4,       // ticks run since create / reset
                   STRM_TAP_ROWS = 5,    // group members: logits rows offered to the member's tap since it was armed
                   STRM_WORDS = 16 };    // block size in ints (a group of N sessions holds N such blocks back to back)
+struct TokenScore { float logprob, margin; int runner_up, id; };      // vox_token_score (voxtral_hip.h)
 struct StreamMember {
     const float* samples; float gain;   // the session's 16 kHz sample ring; every sample is multiplied by gain before the mel
     int* state;                         // its StreamWord block
     float *kring, *vring;               // its encoder K / V ring, [enc_layers][n_heads][cap][hd]
     int* tokens;                        // its token row
     float* tap; int tap_max;            // group members: [tap_max][vocab] logits rows (null: not armed)
+    struct TokenScore* scores; int scores_cap;      // the session's score records, one per id of the utterance (null: scores off, launch_stream_score skips the slot)
 };
 // front end: for every slot z < n the log-mel frames STRM_FRAME - halo_back .. + n_frames - 1 of the virtually padded signal zeros(left) + gain * samples of session
 // order[z], token-major into out + z * slot_stride ([n_frames][128]: the layout the conv stem's im2col GEMM reads).  Sample i of a session lives at ring[i & ring_mask];
@@ -433,5 +435,14 @@ hipError_t launch_stream_group_embed(Q4W tok, const StreamMember* mem, const int
 // tokens[STRM_POS + 1] = argmax of logits row r (argmax_take / block_argmax: the rule of every decode form), the row copied to the session's tap when one is armed,
 // then the session's state advances by one tick as launch_stream_advance moves it
 hipError_t launch_stream_group_advance(const float* logits, int vocab, const StreamMember* mem, const int* order, int n, int enc_rows, int frames, int cap, hipStream_t s);
+// ---- scores of emitted ids (vox_token_score): for a logits row L[V] and an id t, logprob = L[t] - (m + log sum_v exp(L[v] - m)), m = max L (f32, expf / logf),
+// runner_up = the argmax over v != t by the rule above launch_argmax_final (-1 when no such column can win), margin = L[t] - L[runner_up] (L[t] + inf without one).
+// A row with a NaN or a maximum that is not finite: logprob = NaN.  The record is a function of the row's values and V alone (one scan order for aligned and
+// misaligned rows, a fixed reduction tree): score_row, vox_kernels.hip.
+// out[r] = the record of ids[r] on row r of x [rows][V] (device pointers; ids null: the row's argmax, 0 when nothing wins)
+hipError_t launch_score_rows(const float* x, int rows, int V, const int* ids, TokenScore* out, hipStream_t s);
+// behind launch_stream_advance / launch_stream_group_advance: slot z < n scores the id session order[z] just emitted (tokens[STRM_POS]) on row z of logits [n][vocab],
+// into mem[order[z]].scores[STRM_POS - first_pos]; sessions whose scores pointer is null are skipped
+hipError_t launch_stream_score(const float* logits, int vocab, const StreamMember* mem, const int* order, int n, int first_pos, hipStream_t s);
 
 }  // namespace vox

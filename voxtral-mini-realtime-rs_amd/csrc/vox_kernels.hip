@@ -4497,4 +4497,105 @@ hipError_t launch_stream_group_advance(const float* logits, int vocab, const Str
     return hipGetLastError();
 }
 
+// ---- what a live session knows about an id it emitted (vox_token_score, voxtral_hip.h): its log-probability under the softmax of the step's f32 logits row, its margin
+// over the runner-up, and the runner-up.  ONE device function for every launch form, and ONE scan order: column 4 i + j (j < 4, i < V / 4) belongs to thread i % NT, the
+// V % 4 leftovers to threads 0 .. 2 -- whether the row starts on a 16-byte boundary (float4 loads) or not (the same four columns as single loads), so a thread's chain
+// of adds, the wave's xor tree and thread 0's walk over the per-wave sums are functions of V alone: the record is a function of the row's values and V, never of the
+// row's address, its slot, the grid or the launch's other rows.  Two scans: the argmax over the columns != t by the rule (argmax_take: a NaN and -inf never win) with a
+// NaN flag, then sum exp(L[v] - m), m = max(L[t], the runner-up's value) = the row's maximum whenever the record's logprob is a number.
+//   runner_up = -1 when no column != t can win (V == 1, or only NaN / -inf besides t); margin = L[t] - (-inf) then.
+//   logprob = NaN when the row holds a NaN or its maximum is not finite.  t outside [0, V) (the sentinel a session stores for a row nothing wins on: garbage behind a
+//   timed-out engine step) reads no column: logprob and margin are NaN, runner_up the row's argmax.
+// (VOX_NO_PK_F32 on the kernels: hipcc pairs the f32 adds and subtractions of the float4 scan.)
+struct RowScore { float logprob, margin; int runner_up; };
+template <int NT>
+__device__ __forceinline__ RowScore score_row(const float* __restrict__ row, int V, int t, float* sv, int* si) {
+    __shared__ int s_nan;
+    __shared__ float s_m;
+    const bool al = (reinterpret_cast<uintptr_t>(row) & 15) == 0;
+    const int V4 = V >> 2;
+    if (threadIdx.x == 0) s_nan = 0;
+    float bv = -INFINITY; int bi = 0x7fffffff; bool nan = false;
+    auto see = [&](float x, int i) { nan |= x != x; if (i != t) argmax_take<true>(bv, bi, x, i); };
+    for (int i = threadIdx.x; i < V4; i += NT) {
+        float4 q;
+        if (al) q = reinterpret_cast<const float4*>(row)[i];
+        else { q.x = row[4 * i]; q.y = row[4 * i + 1]; q.z = row[4 * i + 2]; q.w = row[4 * i + 3]; }
+        see(q.x, 4 * i); see(q.y, 4 * i + 1); see(q.z, 4 * i + 2); see(q.w, 4 * i + 3);
+    }
+    for (int i = 4 * V4 + threadIdx.x; i < V; i += NT) see(row[i], i);
+    __syncthreads();                                   // s_nan = 0 is visible; sv / si are free (a caller's earlier block_argmax has been read)
+    if (nan) s_nan = 1;                                // (every writer stores the same value)
+    block_argmax<NT>(bv, bi, sv, si);                  // thread 0: the runner-up; its barrier publishes s_nan
+    const float lt = (t >= 0 && t < V) ? row[t] : __int_as_float(0x7fc00000);
+    if (threadIdx.x == 0) s_m = lt > bv ? lt : bv;     // (a NaN lt leaves bv: the row is flagged anyway)
+    __syncthreads();
+    const float m = s_m;
+    const bool ok = !s_nan && m - m == 0.0f;           // finite maximum, no NaN: otherwise nothing is summed
+    float acc = 0.0f;
+    if (ok) {
+        for (int i = threadIdx.x; i < V4; i += NT) {
+            float4 q;
+            if (al) q = reinterpret_cast<const float4*>(row)[i];
+            else { q.x = row[4 * i]; q.y = row[4 * i + 1]; q.z = row[4 * i + 2]; q.w = row[4 * i + 3]; }
+            acc += expf(q.x - m); acc += expf(q.y - m); acc += expf(q.z - m); acc += expf(q.w - m);
+        }
+        for (int i = 4 * V4 + threadIdx.x; i < V; i += NT) acc += expf(row[i] - m);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    __syncthreads();                                   // thread 0 has read sv in block_argmax
+    if ((threadIdx.x & 63) == 0) sv[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    RowScore r; r.runner_up = bi == 0x7fffffff ? -1 : bi; r.margin = lt - bv; r.logprob = __int_as_float(0x7fc00000);
+    if (threadIdx.x == 0 && ok) {
+        float sum = sv[0];
+        for (int w = 1; w < NT / 64; w++) sum += sv[w];
+        r.logprob = (lt - m) - logf(sum);
+    }
+    return r;                                          // thread 0's is the record
+}
+// the plain form: one workgroup per row of x [rows][V]; ids null: the row's argmax by the rule (0 when nothing wins, as argmax_rows_kernel)
+__global__ __launch_bounds__(1024) VOX_NO_PK_F32 void score_rows_kernel(const float* __restrict__ x, int V, const int* __restrict__ ids, TokenScore* __restrict__ out) {
+    __shared__ float bv[16];
+    __shared__ int bi[16];
+    __shared__ int s_t;
+    const float* row = x + (size_t)blockIdx.x * V;
+    if (ids) { if (threadIdx.x == 0) s_t = ids[blockIdx.x]; }
+    else {
+        float v; int idx;
+        argmax_scan_row<1024>(row, V, v, idx);
+        block_argmax<1024>(v, idx, bv, bi);
+        if (threadIdx.x == 0) s_t = idx == 0x7fffffff ? 0 : idx;
+    }
+    __syncthreads();
+    const int t = s_t;
+    const RowScore r = score_row<1024>(row, V, t, bv, bi);
+    if (threadIdx.x == 0) out[blockIdx.x] = TokenScore{r.logprob, r.margin, r.runner_up, t};
+}
+hipError_t launch_score_rows(const float* x, int rows, int V, const int* ids, TokenScore* out, hipStream_t s) {
+    if (rows <= 0 || V <= 0 || !x || !out) return hipErrorInvalidValue;
+    score_rows_kernel<<<dim3(rows), dim3(1024), 0, s>>>(x, V, ids, out);
+    return hipGetLastError();
+}
+// the session form, behind the tick's advance kernel: slot z scores the id session order[z] just emitted -- tokens[STRM_POS], STRM_POS already moved on -- on logits row
+// z, into record STRM_POS - first_pos of the session's score array; a session without one (scores off) returns at once
+__global__ __launch_bounds__(1024) VOX_NO_PK_F32 void stream_score_kernel(const float* __restrict__ logits, int vocab, const StreamMember* __restrict__ mem, const int* __restrict__ order,
+                                                                         int first_pos) {
+    __shared__ float bv[16];
+    __shared__ int bi[16];
+    const StreamMember& me = mem[order[blockIdx.x]];
+    if (!me.scores) return;
+    const int pos = me.state[STRM_POS], k = pos - first_pos;
+    if (k < 0 || k >= me.scores_cap) return;           // (never: the host sizes the array by the session's position limit)
+    const int t = me.tokens[pos];
+    const RowScore r = score_row<1024>(logits + (size_t)blockIdx.x * vocab, vocab, t, bv, bi);
+    if (threadIdx.x == 0) me.scores[k] = TokenScore{r.logprob, r.margin, r.runner_up, t};
+}
+hipError_t launch_stream_score(const float* logits, int vocab, const StreamMember* mem, const int* order, int n, int first_pos, hipStream_t s) {
+    if (n < 1 || n > 16 || !logits || !mem || !order || vocab <= 0 || first_pos < 0) return hipErrorInvalidValue;
+    stream_score_kernel<<<dim3(n), dim3(1024), 0, s>>>(logits, vocab, mem, order, first_pos);
+    return hipGetLastError();
+}
+
 }  // namespace vox

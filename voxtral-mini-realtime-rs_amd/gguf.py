@@ -397,6 +397,74 @@ def argmax_rows_dev(ctx, logits_ptr, rows, vocab):
     return ids
 
 
+SCORE_DTYPE = np.dtype([("logprob", "<f4"), ("margin", "<f4"), ("runner_up", "<i4"), ("id", "<i4")])      # vox_token_score
+
+
+def score_rows(ctx, logits, ids=None, device_ptr=None, shape=None):
+    """vox_score_rows: one vox_token_score per row of f32 logits [rows][vocab] -> a structured array (logprob, margin, runner_up, id).  ids: the id to score in every
+    row (None: the row's argmax by the project's rule).  logits: a host array, or device_ptr + shape=(rows, vocab).  Computed on the device; synchronises."""
+    if device_ptr is None:
+        x = _f32(logits); x = x.reshape(1, -1) if x.ndim == 1 else x
+        M, V = x.shape; ptr = _ptr(x); kind = 0
+    else:
+        M, V = (int(v) for v in shape); ptr = C.c_void_p(device_ptr); kind = 1
+    t = None if ids is None else np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+    if t is not None and t.size != M:
+        raise ValueError(f"{t.size} ids for {M} rows")
+    out = np.zeros(M, dtype=SCORE_DTYPE)
+    check(lib().vox_score_rows(ctx.h, ptr, M, V, None if t is None else _ptr(t), _ptr(out), kind))
+    return out
+
+
+def stream_id_due(k: int, sample_rate: int = 16000) -> int:
+    """The smallest number of pushed samples (at `sample_rate`) at which a live session hands out id k of its utterance: 2560 k + 40 at 16 kHz, by the schedule; at
+    another rate the smallest n with stream_schedule_rate(n)[1] > k, found by bisection (the schedule is monotone).  This is when the session KNOWS the id, the only time
+    the schedule defines: not where in the audio the word was said."""
+    k = int(k)
+    if k < 0:
+        raise ValueError(f"id index {k}")
+    if int(sample_rate) == 16000:
+        return 2560 * k + 40
+    ids = lambda n: stream_schedule_rate(n, sample_rate)[1]
+    lo, hi = 0, max(1, int(sample_rate))      # ids(lo) <= k < ids(hi)
+    while ids(hi) <= k:
+        lo, hi = hi, 2 * hi
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if ids(mid) > k:
+            hi = mid
+        else:
+            lo = mid
+    return hi
+
+
+def words(ids, scores, tokenizer, sample_rate: int = 16000):
+    """The ids a live session handed out (ids[k] = id k of the utterance) and their records (LiveStream.scores()) as words.  Text ids are those >= 1000 (control and
+    streaming ids are dropped); a word begins at the first text id and at every text id whose bytes begin with ASCII whitespace, so a character split over two ids stays
+    in one word.  -> a list of {text (the word's bytes as lossy UTF-8, its leading whitespace included: the texts joined are the decoded transcript), first_id, last_id
+    (indices into ids), due_s (stream_id_due(last_id) / sample_rate: when a session fed at that rate hands the word's last id out), logprob (the sum over its ids),
+    min_margin (the smallest margin among them)}."""
+    from .tokenizer import TEXT_TOKEN_OFFSET
+    out = []; cur = None
+    for k, t in enumerate(ids):
+        t = int(t)
+        if t < TEXT_TOKEN_OFFSET:
+            continue
+        v = t - TEXT_TOKEN_OFFSET
+        b = tokenizer.vocab_bytes[v] if v < len(tokenizer.vocab_bytes) else None
+        if b is None:      # a control entry, an id past the vocabulary: VoxtralTokenizer.decode skips them
+            continue
+        if cur is None or b[:1] in (b" ", b"\t", b"\n", b"\r", b"\x0b", b"\x0c"):
+            cur = {"bytes": bytearray(), "first_id": k, "last_id": k, "logprob": 0.0, "min_margin": float("inf")}; out.append(cur)
+        cur["bytes"] += b; cur["last_id"] = k
+        cur["logprob"] += float(scores["logprob"][k]); cur["min_margin"] = min(cur["min_margin"], float(scores["margin"][k]))
+    res = []
+    for w in out:
+        res.append({"text": bytes(w["bytes"]).decode("utf-8", errors="replace"), "first_id": w["first_id"], "last_id": w["last_id"],
+                    "due_s": stream_id_due(w["last_id"], sample_rate) / float(sample_rate), "logprob": w["logprob"], "min_margin": w["min_margin"]})
+    return res
+
+
 def stream_schedule_rate(n_samples: int, sample_rate: int, finished: bool = False):
     """vox_stream_schedule_rate (host arithmetic) for a stream fed at `sample_rate`: (decoder positions determined, ids due, 16 kHz samples the stream holds) after
     `n_samples` pushed, or at the end of an n_samples utterance."""
@@ -460,6 +528,18 @@ class LiveStream:
     def info(self):
         v = (C.c_int64 * 8)(); check(lib().vox_stream_info(self.h, v))
         return dict(zip(("samples", "positions", "ids", "encoder_position", "ring_rows", "bytes", "engine_steps", "operator_steps"), (int(x) for x in v)))
+
+    def set_scores(self, on: bool = True):
+        """vox_stream_set_scores: from the next push / finish on, every id comes with its record (scores()); survives reset()."""
+        check(lib().vox_stream_set_scores(self.h, 1 if on else 0))
+
+    def scores(self, first: int = 0, n=None) -> np.ndarray:
+        """vox_stream_scores: the records of ids [first, first + n) of the current utterance (n None: up to the last id handed out) as a structured array (logprob,
+        margin, runner_up, id); an id handed out while scores were off has NaN, NaN, -1 and its id.  Reads host memory only."""
+        n = self.info()["ids"] - int(first) if n is None else int(n)
+        out = np.zeros(max(n, 0), dtype=SCORE_DTYPE)
+        check(lib().vox_stream_scores(self.h, int(first), n, _ptr(out) if out.size else None))
+        return out
 
     def tap_arm(self, max_rows):
         check(lib().vox_debug_stream_tap_arm(self.h, int(max_rows))); self._tap_max = int(max_rows)
@@ -570,6 +650,17 @@ class LiveStreamGroup:
     def info(self, member):
         v = (C.c_int64 * 8)(); check(lib().vox_stream_group_info(self.h, int(member), v))
         return dict(zip(("samples", "positions", "ids", "encoder_position", "ring_rows", "bytes", "engine_steps", "operator_steps"), (int(x) for x in v)))
+
+    def set_scores(self, member, on: bool = True):
+        """vox_stream_group_set_scores: LiveStream.set_scores for one member; survives the member's resets."""
+        check(lib().vox_stream_group_set_scores(self.h, int(member), 1 if on else 0))
+
+    def scores(self, member, first: int = 0, n=None) -> np.ndarray:
+        """vox_stream_group_scores: LiveStream.scores for one member."""
+        n = self.info(member)["ids"] - int(first) if n is None else int(n)
+        out = np.zeros(max(n, 0), dtype=SCORE_DTYPE)
+        check(lib().vox_stream_group_scores(self.h, int(member), int(first), n, _ptr(out) if out.size else None))
+        return out
 
     def tap_arm(self, member, max_rows):
         check(lib().vox_debug_stream_group_tap_arm(self.h, int(member), int(max_rows))); self._tap_max[int(member)] = int(max_rows)
