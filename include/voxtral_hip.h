@@ -522,10 +522,23 @@ int32_t vox_stream_schedule_rate(size_t n_samples, uint32_t sample_rate, int32_t
  * runner_up = -1 and its id.  Steps a decode-engine hand-off timeout takes back are scored again from the re-run's logits. */
 int32_t vox_stream_set_scores(vox_stream* s, int32_t on);
 int32_t vox_stream_scores(const vox_stream* s, int32_t first_id, int32_t n, vox_token_score* out);
+/* PEEK.  vox_stream_peek returns the ids vox_stream_finish would return now -- vox_stream_peek_ids of them: vox_stream_schedule_rate(samples pushed, rate, finished = 1)
+ * minus the ids handed out -- and leaves the stream what it was, bit for bit: the ids and logits of every later call, the decoder cache's size and engine binding,
+ * vox_stream_info [0..4], [6], [7].  It takes no samples: push first, then peek; it may be repeated, and followed by a push, a finish or a reset alike.  The stream runs
+ * finish's ticks (the right pad, the rest of a rate stream's last block) and takes them back: the encoder ring rows they overwrite and the state block are saved in front
+ * of them and restored behind them by one launch each (the save area, 21 MB at full size, is allocated at the first peek and counted in vox_stream_info [5] from
+ * then on), the host takes back its own counters, and a decoder cache that grew inside the tail gets its old planes back.  Still one synchronisation per call.
+ * Refusals are vox_stream_finish's, before anything changes: a finished stream, cap below the count, a tail past max_positions.
+ * scores_or_null: the records of the peeked ids (with scores off: NaN, NaN, -1, id); the stream's own list (vox_stream_scores) is not extended. */
+int32_t vox_stream_peek(vox_stream* s, int32_t* out_ids, int32_t cap, int32_t* n_ids, vox_token_score* scores_or_null);
+/* host only: the ids a peek returns after n_samples pushed at sample_rate Hz with ids_out ids handed out (more than the utterance has: VOX_ERR_INVALID) */
+int32_t vox_stream_peek_ids(size_t n_samples, uint32_t sample_rate, int32_t ids_out, int32_t* n);
 /* test tap, modelled on vox_debug_batch_tap_*: from now on keep the f32 logits row behind each id handed out (up to max_rows); fetch copies them to the host
  * ([min(rows, max_rows)][vocab]; *rows = rows produced since arm) and ends the tap */
 int32_t vox_debug_stream_tap_arm(vox_stream* s, int32_t max_rows);
 int32_t vox_debug_stream_tap_fetch(vox_stream* s, float* out_rows_x_vocab, int32_t* rows);
+/* while a tap is armed: the `rows` logits rows the last vox_stream_peek left behind the tap's position ([rows][vocab]; the tap must have room for them).  The tap goes on. */
+int32_t vox_debug_stream_tap_peeked(vox_stream* s, float* out_rows_x_vocab, int32_t rows);
 /* front-end tap (tests), same rules as the logits tap (an arm drops the rows of an earlier arm, fetch ends the tap, vox_stream_reset starts the count again): while armed
  * every tick copies, device to device on the stream and without synchronising, its 16 fresh log-mel frames ([16][n_mels], token-major: frames 16 p .. 16 p + 15 of the
  * tick at decoder position p) and its 4 conv-stem rows ([4][enc_dim], the encoder's input rows 4 p .. 4 p + 3); nothing is launched when no tap is armed.  A decode
@@ -593,12 +606,18 @@ int32_t vox_stream_group_free(vox_stream_group* g);
  * slots, and only while some member has scores on; the member's records are counted in vox_stream_group_info [5] */
 int32_t vox_stream_group_set_scores(vox_stream_group* g, int32_t member, int32_t on);
 int32_t vox_stream_group_scores(const vox_stream_group* g, int32_t member, int32_t first_id, int32_t n, vox_token_score* out);
+/* vox_stream_peek (PEEK above) for any subset of the members in one call: every entry names a member, out_ids and cap and gets n_ids; its n_samples and finish must be 0.
+ * The entries' ids are those vox_stream_group_advance would hand the same members finishing now, and the group -- the peeked members and the others -- stays what it
+ * was.  One ring save and one restore launch for all entries, one synchronisation, as advance.  Refusals are advance's for finishing entries (and samples or a finish
+ * flag in an entry), before anything changes.  scores_or_null: one array per entry (entries whose pointer is null get none), as vox_stream_peek's.  The save area
+ * holds a slot per entry of the largest peek so far and is counted in the group's device bytes. */
+int32_t vox_stream_group_peek(vox_stream_group* g, vox_stream_feed* feeds, int32_t n_feeds, vox_token_score* const* scores_or_null);
 /* vox_debug_stream_tap_* for one member (the rows are copied by the tick's last kernel; a reset of the member starts the count again) */
 int32_t vox_debug_stream_group_tap_arm(vox_stream_group* g, int32_t member, int32_t max_rows);
 int32_t vox_debug_stream_group_tap_fetch(vox_stream_group* g, int32_t member, float* out, int32_t* rows);
 /* The live sessions' feed planner on its own (tests): host arithmetic only -- no context, no device, no model.  A fresh session fed at sample_rate (4 encoder rows per
  * position, the Voxtral left pad, no position limit to speak of) takes the calls (n_samples[c], finish[c] 0 / 1) exactly as vox_stream_push / _finish and a group's advance
- * plan and pass them, every due tick taken as run.  One row of five words per pass: call index, input samples appended, 16 kHz samples that entered the 16 kHz ring (a
+ * plan and pass them, every due tick taken as run; finish[c] = 2 is a peek (n_samples[c] must be 0): planned as a finish, its one pass emitted, the session as it was.  One row of five words per pass: call index, input samples appended, 16 kHz samples that entered the 16 kHz ring (a
  * 16 kHz session: the appended ones), right-pad zeros written, ticks that became due.  pass_cap: most input samples per pass (0: no cap; a group's 16-bit staging: 65536).
  * A call after a finish, a bad rate or more than max_rows passes are refused. */
 int32_t vox_debug_stream_feed_passes(uint32_t sample_rate, const size_t* n_samples, const int32_t* finish, int32_t n_calls, size_t pass_cap, int64_t* rows, int32_t max_rows,

@@ -5,6 +5,7 @@
     python tools/stream_bench.py --group 1,2,4,8,16 [--out profiles/stream_group_tick.txt]
     python tools/stream_bench.py --group 1,4,16 --rate 48000 --s16 [--out profiles/stream_group_rate_tick.txt]
     python tools/stream_bench.py --scores [--group 1,4,16] [--out profiles/stream_scores_tick.txt]
+    python tools/stream_bench.py --peek [--out profiles/stream_peek.txt]
 
  * stream: HIP events on the context's stream around ONE push of `ticks` x 2560 samples (a large push is a loop of identical ticks), at encoder positions past the
    750-row window, median of `passes` passes; launches per tick from the library's launch counters plus the fixed launches of a tick; wall time of single 160 ms pushes
@@ -23,6 +24,9 @@
  * --scores: what scores cost (vox_stream_set_scores: one more launch per tick, one logits row written and read per session).  A second solo stream -- with --group
    also a second group -- runs with scores on, warmed like the first and timed the same way in the same loop: pass i of the scored session follows pass i of the
    unscored one and covers the same positions.  The unscored figures are the tool's usual ones (comparable with a run without the flag); the difference is reported.
+ * --peek: what a peek costs (vox_stream_peek: finish's T ticks between a ring save and a ring restore, taken back).  One stream past the 750-row window; per pass,
+   HIP events around one peek and, right behind it, around one push of the same T ticks -- the same session, the same positions (the peek left it where it was), the
+   same run.  Median of `passes` passes of each, their ratio, and the launches of both from the library's counters plus the fixed launches of a tick.
  * derived figures are labelled as derived."""
 import argparse
 import ctypes as C
@@ -153,6 +157,32 @@ def bench_groups(pkg, ctx, m, t, tm, a, widths, lines):
         pkg._lib.check(pkg.lib().vox_dev_free(ctx.h, dev))
 
 
+def bench_peek(pkg, ctx, m, t, tm, a, lines):
+    """--peek: per pass one peek and one push of as many ticks, the yardstick, on the same session at the same positions."""
+    c = m.config; S = pkg.synth; warm = 200
+    x = S.synth_audio((warm + 16 * (a.passes + 2)) * 0.16 + 1.0, seed=4242); gain = float(np.float32(0.95) / np.float32(np.abs(x).max()))
+    fixed = 1 + 2 * c.enc_layers + 1 + 1 + 1      # stream_mel, two RMSNorms per encoder layer, final norm, stream_embed, stream_advance
+    st = m.create_stream(t, gain=gain)
+    pos = 40 + 2560 * warm; st.push(x[:pos])
+    b0 = st.info()["bytes"]; T = len(st.peek()); save = st.info()["bytes"] - b0      # the first peek allocates the save area: not timed
+    pk, tk = [], []; lp = lt = 0
+    for _ in range(a.passes):
+        k0 = launch_counts(pkg); ms = tm.ms(lambda: st.peek()); k1 = launch_counts(pkg)
+        seg = x[pos:pos + 2560 * T]; pos += 2560 * T
+        ids = []; ms2 = tm.ms(lambda: ids.append(st.push(seg))); k2 = launch_counts(pkg)
+        assert len(ids[0]) == T and len(st.peek()) == T      # (this peek re-runs nothing timed: it shows the count is steady)
+        pk.append(ms); tk.append(ms2); lp += sum(k1) - sum(k0); lt += sum(k2) - sum(k1)
+    e = st.info(); st.close()
+    assert e["positions"] == 38 + warm + T * a.passes and e["positions"] + T < 1024      # every timed step on the decode engine's 1024-row cache, the tails included
+    p, q = statistics.median(pk), statistics.median(tk)
+    lines += [f"peek of {T} ticks (HIP events around vox_stream_peek): median {p:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in pk),
+              f"the same {T} ticks as one push, same session, same positions, right behind each peek: median {q:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in tk),
+              f"ratio peek / ticks: {p / q:.3f}   per pass " + " ".join(f"{v / w:.3f}" for v, w in zip(pk, tk)) + f"   difference {p - q:+.3f} ms",
+              f"launches: peek {lp / a.passes + T * fixed + 2:.0f} = {T} ticks x {lp / a.passes / T + fixed:.0f} + 2 (ring save, ring restore); push {lt / a.passes + T * fixed:.0f} = {T} ticks x {lt / a.passes / T + fixed:.0f}",
+              f"save area: {save} bytes ({save / 1e6:.1f} MB), allocated by the first peek (not timed)",
+              f"derived: per tick {q / T:.3f} ms; the two keep launches move at most 2 x {save / 1e6:.1f} MB"]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gguf"); ap.add_argument("--ticks", type=int, default=200); ap.add_argument("--passes", type=int, default=3); ap.add_argument("--out")
@@ -160,7 +190,10 @@ def main():
     ap.add_argument("--rate", type=int, default=0, metavar="SR", help="with --group: also time a group whose members are all fed at SR Hz, next to the 16 kHz f32 round")
     ap.add_argument("--s16", action="store_true", help="with --rate: feed that group 16-bit PCM")
     ap.add_argument("--scores", action="store_true", help="also time a stream (with --group: and a group) with scores on, pass by pass next to the unscored one")
+    ap.add_argument("--peek", action="store_true", help="time vox_stream_peek next to the same number of ordinary ticks of the same session (nothing else is measured)")
     a = ap.parse_args()
+    if a.peek and (a.group or a.scores):
+        ap.error("--peek is a mode of its own")
     if (a.rate or a.s16) and not a.group or (a.s16 and not a.rate):
         ap.error("--rate applies with --group, --s16 with --rate")
     widths = [int(v) for v in a.group.split(",")] if a.group else []
@@ -176,6 +209,17 @@ def main():
             S.write_synthetic_gguf(path + ".tmp", S.ModelDims(), seed=42); os.replace(path + ".tmp", path)
     ctx = pkg.Context(0); m = pkg.Q4ModelLoader.from_file(path).load(ctx); c = m.config
     t = pkg.TimeEmbedding(c.dec_dim).embed(6.0); tm = Timer(pkg, ctx); L = pkg.lib()
+    if a.peek:
+        lines = ["# " + " ".join(["python", "tools/stream_bench.py"] + sys.argv[1:]),
+                 f"# model {os.path.basename(path)}: {c.enc_layers} encoder layers, {c.dec_layers} decoder layers; {a.passes} passes, all past encoder position {4 * (37 + 200)}"]
+        bench_peek(pkg, ctx, m, t, tm, a, lines)
+        text = "\n".join(lines) + "\n"
+        print(text, end="")
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            open(a.out, "w").write(text)
+        m.close(); ctx.close()
+        return
     if widths:
         lines = ["# " + " ".join(["python", "tools/stream_bench.py"] + sys.argv[1:]),
                  f"# model {os.path.basename(path)}: {c.enc_layers} encoder layers, {c.dec_layers} decoder layers; {a.ticks} ticks per pass, {a.passes} passes, all past encoder position {4 * (37 + 200)}"]

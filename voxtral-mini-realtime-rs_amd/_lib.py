@@ -194,6 +194,10 @@ SIGNATURES = {
     "vox_stream_scores": (i32, [vp, i32, i32, vp]),
     "vox_stream_group_set_scores": (i32, [vp, i32, i32]),
     "vox_stream_group_scores": (i32, [vp, i32, i32, i32, vp]),
+    "vox_stream_peek": (i32, [vp, vp, i32, P(i32), vp]),
+    "vox_stream_peek_ids": (i32, [sz, u32, i32, P(i32)]),
+    "vox_debug_stream_tap_peeked": (i32, [vp, vp, i32]),
+    "vox_stream_group_peek": (i32, [vp, vp, i32, vp]),
 }
 
 _LIB = None

@@ -79,14 +79,16 @@ def write_words(out, pkg, path, ids, scores, tokenizer, rate):
     out.flush()
 
 
-def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_rate=False, words_out=None):
+def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_rate=False, words_out=None, peek=False):
     """--live: the file through a live session (vox_stream) in pieces of `chunk_ms` milliseconds, the text so far on stderr whenever ids arrive.  The gain is the
     file's peak scale 0.95 / max|x| (bin/transcribe.rs:207; a file is known in advance -- a microphone caller passes its own), the whole file is one utterance (no
     --max-mel-frames chunks: the session's state is bounded by its ring), so the line equals the un-chunked path's.
     native_rate (--live-native-rate), for a file that is not at 16 kHz: the session is created for the file's rate and pushed the file's own samples -- what a capture
     device would deliver; it resamples as the samples arrive.  The gain stays the peak scale of the RESAMPLED file (computed here only because the file is known in
     advance and the line is to be compared), so the line equals the one without the flag.
-    words_out (--live-words): the session runs with scores on and the file's words go there when it ends; the ids, hence the line, are the same."""
+    words_out (--live-words): the session runs with scores on and the file's words go there when it ends; the ids, hence the line, are the same.
+    peek (--live-peek): after every push a "  ~[" line on stderr with the text so far plus the tentative tail -- what the line would be if the file ended here
+    (vox_stream_peek: finish's ticks, taken back); the session, hence everything else, is as without the flag."""
     x, sr = load_wav(path)
     rate = 16000
     if sr != 16000:
@@ -106,11 +108,13 @@ def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_
         if words_out is not None:
             stream.set_scores(True)
         ids = []
-        text = lambda: tokenizer.decode([t for t in ids if t >= 1000]).strip()   # :309-318
+        text = lambda tail=(): tokenizer.decode([t for t in ids + [int(v) for v in tail] if t >= 1000]).strip()   # :309-318
         for a in range(0, x.size, step):
             new = stream.push(x[a:a + step])
             if new.size:
                 ids.extend(int(t) for t in new); log(f"  [{min(a + step, x.size) / rate:8.2f} s] {text()}")
+            if peek:
+                log(f"  ~[{min(a + step, x.size) / rate:8.2f} s] {text(stream.peek())}")
         ids.extend(int(t) for t in stream.finish())
         if words_out is not None:
             write_words(words_out, pkg, path, ids, stream.scores(), tokenizer, rate)
@@ -119,11 +123,12 @@ def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_
         stream.close()
 
 
-def transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, chunk_ms, n_members, words_out=None):
+def transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, chunk_ms, n_members, words_out=None, peek=False):
     """--live-group N: the files N at a time through one stream group (vox_stream_group) in pieces of `chunk_ms` milliseconds: every call feeds each busy member its
     next piece, a file that ends (its member fed with finish) frees the member for the next file in input order.  Gains and lines as transcribe_live's (16 kHz: other
     rates are resampled first).  -> {file index: text}; a file that cannot be read is left out (the one-by-one path reports it).  words_out (--live-words): every
-    member runs with scores on, a file's words go there when the file ends."""
+    member runs with scores on, a file's words go there when the file ends.  peek (--live-peek): after every call one vox_stream_group_peek for the members still
+    busy, a "  ~[" line each: the text so far plus the tentative tail."""
     step = max(1, int(round(16000 * chunk_ms / 1000.0)))
     group = model.create_stream_group(t_embed, n_members)
     text = lambda ids: tokenizer.decode([t for t in ids if t >= 1000]).strip()
@@ -157,6 +162,8 @@ def transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, chunk_ms, 
                 b = busy.pop(k); texts[b[0]] = text(b[3])
                 if words_out is not None:
                     write_words(words_out, pkg, paths[b[0]], b[3], group.scores(k), tokenizer, 16000)
+            for k, tail in (group.peek(sorted(busy)) if peek and busy else {}).items():
+                b = busy[k]; log(f"  ~[{paths[b[0]]} {min(b[2], b[1].size) / 16000:8.2f} s] {text(b[3] + [int(v) for v in tail])}")
         return texts
     finally:
         group.close()
@@ -303,10 +310,15 @@ def main(argv=None):
                     "for that rate (it resamples as they arrive) instead of resampling the whole file first; the line is the same")
     ap.add_argument("--live-group", type=int, default=0, metavar="N", help="with --live: feed the files N (2..16) at a time through one stream group (vox_stream_group): every "
                     "weight matrix is read once per tick for all files that have a tick due; same final lines, in input order")
+    ap.add_argument("--live-peek", action="store_true", help="with --live (also with --live-group, --live-native-rate, --live-words): after every push a line starting with "
+                    "'  ~[' on stderr: the text so far plus the tentative tail, i.e. the line if the file ended here (vox_stream_peek); stdout, the '  [' lines and the "
+                    "words file do not change")
     ap.add_argument("--live-words", metavar="PATH", help="with --live: run the sessions with scores on (vox_stream_set_scores) and write one JSON line per word to PATH when "
                     "a file ends: text, first_id / last_id (indices into the file's ids), due_s (when the session hands the word's last id out, in seconds of pushed audio: "
                     "not where the word was said), logprob (summed over the word's ids), min_margin (the smallest top-2 margin among them), file; stdout is unchanged")
     a = ap.parse_args(argv)
+    if a.live_peek and not a.live:
+        ap.error("--live-peek applies with --live")
     if a.live_words and not a.live:
         ap.error("--live-words applies with --live")
     if a.live_group and not a.live:
@@ -398,7 +410,7 @@ def main(argv=None):
             texts = join_units(len(paths), units, unit_texts)
     if a.live_group:
         try:
-            texts = transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_group, words_out)
+            texts = transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_group, words_out, a.live_peek)
         except Exception as e:      # the files fall back to one live session each
             log(f"Error in the stream group: {e}"); texts = {}
             if words_out is not None:      # the files' words come again with their lines
@@ -410,7 +422,7 @@ def main(argv=None):
         p = paths[i]
         try:
             t1 = time.time()
-            text = transcribe_live(pkg, p, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_native_rate, words_out) if a.live else transcribe_one(pkg, p, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed)
+            text = transcribe_live(pkg, p, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_native_rate, words_out, a.live_peek) if a.live else transcribe_one(pkg, p, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed)
             log(f"{p}: {time.time() - t1:.3f}s")
         except Exception as e:      # per-utterance failure isolates to that line (empty), eval_wer.py:211-223 tolerates it
             log(f"Error transcribing {p}: {e}"); text = ""; rc = 1

@@ -4184,6 +4184,10 @@ struct vox_stream {
     ScoreState sc; float* score_row = nullptr;      // scores: the records, and the logits row a scored step writes when no tap row takes it
     float *ftap_mel = nullptr, *ftap_conv = nullptr; int ftap_max = 0, ftap_ticks = 0;      // vox_debug_stream_front_tap_*: per tick its 4 R fresh mel frames and its R conv-stem rows
     int h_state[STRM_WORDS]; int h_pos_word = 0;
+    // vox_stream_peek: the save area of the ring keep (allocated at the first peek, counted in `bytes`) and the ring rows it holds; while a peek's ticks run, a decoder
+    // cache that grows leaves its old planes here instead of freeing them -- the peek puts them back
+    float* keep = nullptr; int keep_rows = 0; bool peeking = false;
+    float *peek_old_k = nullptr, *peek_old_v = nullptr; int peek_old_rows = 0; size_t peek_old_stride = 0;
 };
 
 static long stream_spp(int R) { return 640L * R; }      // samples per decoder position: R encoder rows x 4 frames x 160
@@ -4249,7 +4253,10 @@ static int32_t stream_dec_grow(vox_stream* st) {
     HIPCHK(hipMemcpy2DAsync(nk, (size_t)rows * hd * 4, kc->k, (size_t)old * hd * 4, (size_t)old * hd * 4, planes, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpy2DAsync(nv, (size_t)rows * hd * 4, kc->v, (size_t)old * hd * 4, (size_t)old * hd * 4, planes, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipStreamSynchronize(s));
-    (void)hipFree(kc->k); (void)hipFree(kc->v);
+    if (st->peeking) {      // a peek undoes the growth: the old planes wait in the stream
+        if (st->peek_old_k) { (void)hipFree(nk); (void)hipFree(nv); return fail(VOX_ERR_INVALID, "internal: the decoder cache grew twice inside one peek"); }
+        st->peek_old_k = kc->k; st->peek_old_v = kc->v; st->peek_old_rows = old; st->peek_old_stride = kc->layer_stride;
+    } else { (void)hipFree(kc->k); (void)hipFree(kc->v); }
     cache_unregister(kc); kc->k = nk; kc->v = nv; kc->max_seq = rows; kc->layer_stride = (size_t)c.dec_kv_heads * rows * hd; cache_register(kc);      // (a new generation: the engine's layer table for the old planes is stale)
     return VOX_OK;
 }
@@ -4296,7 +4303,8 @@ static void stream_release(vox_stream* st) {
     (void)hipSetDevice(st->ctx->device); (void)hipStreamSynchronize(st->ctx->stream);      // never dereferences st->m: a stream may not outlive its model, but freeing it late must not crash
     cache_release(st->dec);
     for (void* p : {(void*)st->kring, (void*)st->vring, (void*)st->samples, (void*)st->audio_keep, (void*)st->ws, (void*)st->tokens, (void*)st->state, (void*)st->tap, (void*)st->ftap_mel, (void*)st->ftap_conv,
-                    (void*)st->feed.At, (void*)st->feed.in_ring, (void*)st->s16_stage, (void*)st->d_mem, (void*)st->sc.dev, (void*)st->score_row}) if (p) (void)hipFree(p);
+                    (void*)st->feed.At, (void*)st->feed.in_ring, (void*)st->s16_stage, (void*)st->d_mem, (void*)st->sc.dev, (void*)st->score_row,
+                    (void*)st->keep, (void*)st->peek_old_k, (void*)st->peek_old_v}) if (p) (void)hipFree(p);
     binding_release(st->eng);
     delete st;
 }
@@ -4599,13 +4607,35 @@ static FeedPass feed_pass(FeedState& f, FeedPlan& p, int R, long left, size_t in
 
 // what a push / finish does around its ticks: the stream's own Ada scales, clean accumulators, the passes of its one session -- input into its first ring, the resampling
 // launch of a rate stream, the pad, then every tick that became due -- then the ids of the call behind ONE synchronisation
-static int32_t stream_run(vox_stream* st, const StreamSrc& src, FeedPlan& plan, int32_t* out_ids, int32_t* n_ids) {
+// the ring keep's launch for a solo stream: the round of one
+static int32_t stream_keep_launch(vox_stream* st, int restore) {
+    const vox_model_cfg& c = st->m->cfg;
+    StreamKeepParams kp{}; kp.mem = st->d_mem; kp.order = st->d_order; kp.n = 1; kp.layers = c.enc_layers; kp.n_heads = c.enc_heads; kp.hd = c.enc_head_dim; kp.cap = st->cap;
+    kp.rows = st->keep_rows; kp.keep = st->keep; kp.slot_stride = stream_keep_floats(c.enc_layers, c.enc_heads, c.enc_head_dim, st->keep_rows);
+    HIPCHK(launch_stream_keep(kp, restore, st->ctx->stream));
+    return VOX_OK;
+}
+// what a call's ids carry when they are not the session's own: a peek's records go to the caller's array, never into the session's list
+struct PeekOut { vox_token_score* scores = nullptr; };
+static int32_t peek_scores_enqueue(const ScoreState& sc, int have, int due, const PeekOut& pk, hipStream_t s) {
+    if (sc.on && pk.scores && due > 0) HIPCHK(hipMemcpyAsync(pk.scores, sc.dev + have, (size_t)due * sizeof(TokenScore), hipMemcpyDeviceToHost, s));
+    return VOX_OK;
+}
+static void peek_scores_settle(const ScoreState& sc, int due, const int32_t* ids, const PeekOut& pk) {
+    const float nan = NAN;
+    for (int i = 0; !sc.on && pk.scores && i < due; i++) pk.scores[i] = vox_token_score{nan, nan, -1, ids[i]};
+}
+// pk: the call is a peek (stream_peek, which saved the ring rows and takes the host state back): ONE pass, the ring rows and the state block go back in front of the
+// call's synchronisation, ids_out stays
+static int32_t stream_run(vox_stream* st, const StreamSrc& src, FeedPlan& plan, int32_t* out_ids, int32_t* n_ids, const PeekOut* pk = nullptr) {
     vox_model* m = st->m; hipStream_t s = st->ctx->stream; FeedState& f = st->feed; const bool rate = f.sr != 16000;
     const int due = plan.due, R = m->cfg.reshape_factor;
     if (m->pw_pend_rows > 0) VOXCHK(pw_sync(m));      // unverified engine steps of the piecewise surface share the engine's error word: settled first
     VOXCHK(vox_model_set_t_embed(m, st->t_embed.data()));
     if (due > 0) VOXCHK(wo_acc_clear(m, s));
-    while (feed_open(f, plan)) {
+    for (int pass = 0; feed_open(f, plan); pass++) {
+        // a second pass would size its room from the advanced position and could overwrite samples the session still reads once it is taken back
+        if (pk && pass > 0) return fail(VOX_ERR_INVALID, "internal: a peek at position %d needs a second pass (%lld of %zu samples at 16 kHz)", f.pos, (long long)f.n_written, plan.goal16);
         const FeedPass q = feed_pass(f, plan, R, st->left, SIZE_MAX);
         if (q.idle()) return fail(VOX_ERR_INVALID, "internal: stream stalled at position %d of %d (%lld of %zu samples at 16 kHz)", f.pos, plan.target, (long long)f.n_written, plan.goal16);
         VOXCHK(stream_ring_write(st, rate ? f.in_ring : st->samples, rate ? f.in_ring_n : STREAM_SAMPLE_RING, q.in_w0, src, q.at, q.n_in));
@@ -4617,13 +4647,60 @@ static int32_t stream_run(vox_stream* st, const StreamSrc& src, FeedPlan& plan, 
     int32_t* ids_dev = st->tokens + VOX_PREFIX_TOKENS + f.ids_out;
     VOXCHK(stream_verify_enqueue(st));
     if (due > 0) HIPCHK(hipMemcpyAsync(out_ids, ids_dev, (size_t)due * 4, hipMemcpyDeviceToHost, s));
-    VOXCHK(st->sc.enqueue(f.ids_out, due, s));      // the records travel with the ids
+    if (pk) { VOXCHK(peek_scores_enqueue(st->sc, f.ids_out, due, *pk, s)); VOXCHK(stream_keep_launch(st, 1)); }
+    else VOXCHK(st->sc.enqueue(f.ids_out, due, s));      // the records travel with the ids
     HIPCHK(hipStreamSynchronize(s));      // the call's one synchronisation: ids, their records and the engine's verdict land together
     bool reran = false; VOXCHK(stream_settle(st, &reran));
-    if (reran && due > 0) { HIPCHK(hipMemcpyAsync(out_ids, ids_dev, (size_t)due * 4, hipMemcpyDeviceToHost, s)); VOXCHK(st->sc.enqueue(f.ids_out, due, s)); HIPCHK(hipStreamSynchronize(s)); }
+    if (reran && pk) {      // the re-run moved STRM_POS again: the saved block goes back once more (the ring rows with it: the same values)
+        if (due > 0) HIPCHK(hipMemcpyAsync(out_ids, ids_dev, (size_t)due * 4, hipMemcpyDeviceToHost, s));
+        VOXCHK(peek_scores_enqueue(st->sc, f.ids_out, due, *pk, s)); VOXCHK(stream_keep_launch(st, 1)); HIPCHK(hipStreamSynchronize(s));
+    } else if (reran && due > 0) { HIPCHK(hipMemcpyAsync(out_ids, ids_dev, (size_t)due * 4, hipMemcpyDeviceToHost, s)); VOXCHK(st->sc.enqueue(f.ids_out, due, s)); HIPCHK(hipStreamSynchronize(s)); }
+    *n_ids = due;
+    if (pk) { peek_scores_settle(st->sc, due, out_ids, *pk); return VOX_OK; }
     st->sc.settle(f.ids_out, due, out_ids);
-    f.ids_out += due; *n_ids = due;
+    f.ids_out += due;
     return VOX_OK;
+}
+// the most ticks a peek (a finish) of this session can have due: what is still to come is the backlog of a rate session -- 16 kHz samples of its unfinished block, at
+// most fft_out + delay of them -- and the right pad, at most one token less a sample + the extra tokens; a tick takes stream_spp samples, and position p needs 40 beyond
+static int peek_max_ticks(const FeedState& f, int R) {
+    vox_pad_cfg pc; vox_pad_cfg_voxtral(&pc);
+    const long spt = (long)pad_spt(&pc), right_max = spt - 1 + (long)pc.extra_right_pad_tokens * spt, backlog = f.sr != 16000 ? f.rp.fft_out + f.rp.delay + 1 : 0;
+    return (int)((backlog + right_max + 40) / stream_spp(R)) + 1;
+}
+// vox_stream_peek behind its checks: finish's ticks, then the session as it was.  The device takes back the encoder ring rows the tail wrote and the state block
+// (stream_keep_kernel, inside stream_run); the host takes back the feed, the step counts and a decoder cache that grew.  Everything else the tail wrote lies past the
+// session's position and is written again before it is read.
+static int32_t stream_peek(vox_stream* st, FeedPlan& plan, int32_t* out_ids, int32_t* n_ids, vox_token_score* scores) {
+    vox_model* m = st->m; const vox_model_cfg& c = m->cfg; hipStream_t s = st->ctx->stream; FeedState& f = st->feed;
+    const int T = peek_max_ticks(f, c.reshape_factor), rows = std::min(st->cap, c.reshape_factor * T);
+    ARGCHK(plan.due <= T, "internal: a peek of %d ticks, %d at the most by the pad and the rate plan", plan.due, T);
+    if (!st->keep) {      // the first peek: the save area, counted in info [5] from now on
+        const size_t nb = stream_keep_floats(c.enc_layers, c.enc_heads, c.enc_head_dim, rows) * 4;
+        if (hipMalloc((void**)&st->keep, nb) != hipSuccess) { (void)hipGetLastError(); st->keep = nullptr; return fail(VOX_ERR_HIP, "hipMalloc of the stream's %zu-byte peek save area failed", nb); }
+        st->keep_rows = rows; st->bytes += nb;
+    }
+    if (m->pw_pend_rows > 0) VOXCHK(pw_sync(m));
+    VOXCHK(stream_verify(st));      // the kept adapter rows cover the tail alone; verified_* are the session's own from here
+    struct { int64_t n_written; int pos, tap_rows, ftap_ticks; uint64_t eng, op; } was{f.n_written, f.pos, st->tap_rows, st->ftap_ticks, st->eng_steps, st->op_steps};
+    int32_t r = stream_keep_launch(st, 0);
+    if (r == VOX_OK) {
+        st->peeking = true;
+        const PeekOut pk{scores};
+        r = stream_run(st, StreamSrc{}, plan, out_ids, n_ids, &pk);
+        st->peeking = false;
+        if (r != VOX_OK) { (void)stream_keep_launch(st, 1); (void)hipStreamSynchronize(s); st->eng_unverified = false; }      // a failed tail is taken back as well
+    }
+    if (st->peek_old_k) {      // the tail crossed the cache's rows: the growth is undone (stream_run has synchronised; engine_bind meets a new generation and rebuilds its table)
+        vox_cache* kc = st->dec;
+        (void)hipFree(kc->k); (void)hipFree(kc->v);
+        cache_unregister(kc); kc->k = st->peek_old_k; kc->v = st->peek_old_v; kc->max_seq = st->peek_old_rows; kc->layer_stride = st->peek_old_stride; cache_register(kc);
+        st->peek_old_k = st->peek_old_v = nullptr;
+    }
+    f.n_written = was.n_written; f.pos = was.pos; f.finished = false; st->dec->len = was.pos;
+    st->tap_rows = st->verified_tap_rows = was.tap_rows; st->ftap_ticks = was.ftap_ticks;
+    st->eng_steps = st->verified_eng_steps = was.eng; st->op_steps = st->verified_op_steps = was.op; st->verified_pos = was.pos;
+    return r;
 }
 
 static int32_t stream_push(vox_stream* st, const void* samples, bool s16, size_t n, int32_t mem_kind, int32_t* out_ids, int32_t cap, int32_t* n_ids) {
@@ -4648,6 +4725,21 @@ extern "C" int32_t vox_stream_finish(vox_stream* st, int32_t* out_ids, int32_t c
     VOXCHK(ctx_bind(st->ctx));
     VOXCHK(stream_run(st, StreamSrc{}, plan, out_ids, n_ids));
     st->feed.finished = true;
+    return VOX_OK;
+}
+
+extern "C" int32_t vox_stream_peek(vox_stream* st, int32_t* out_ids, int32_t cap, int32_t* n_ids, vox_token_score* scores_or_null) {
+    ARGCHK(st && n_ids, "null argument"); ARGCHK(cap >= 0 && (out_ids || cap == 0), "bad output buffer");
+    FeedPlan plan; VOXCHK(feed_plan(st->feed, st->m->cfg.reshape_factor, st->left, st->max_pos, 0, true, cap, "the stream", &plan));      // finish's refusals, nothing changed
+    VOXCHK(ctx_bind(st->ctx));
+    return stream_peek(st, plan, out_ids, n_ids, scores_or_null);
+}
+extern "C" int32_t vox_stream_peek_ids(size_t n_samples, uint32_t sample_rate, int32_t ids_out, int32_t* n) {
+    ARGCHK(n, "null argument"); ARGCHK(ids_out >= 0, "ids_out %d", ids_out);
+    int32_t positions, ids; size_t n16;
+    VOXCHK(vox_stream_schedule_rate(n_samples, sample_rate, 1, &positions, &ids, &n16));
+    ARGCHK(ids_out <= ids, "%d ids handed out of an utterance of %d", ids_out, ids);
+    *n = ids - ids_out;
     return VOX_OK;
 }
 
@@ -4692,6 +4784,14 @@ extern "C" int32_t vox_debug_stream_tap_fetch(vox_stream* st, float* out, int32_
     if (k > 0) HIPCHK(hipMemcpy(out, st->tap, (size_t)k * st->m->cfg.vocab * 4, hipMemcpyDeviceToHost));
     *rows = st->tap_rows;
     (void)hipFree(st->tap); st->tap = nullptr; st->tap_max = 0; st->tap_rows = st->verified_tap_rows = 0;
+    return VOX_OK;
+}
+// the rows a peek left BEHIND the tap's position (tests): the tail's logits rows stay in the tap's buffer until the session's own ticks write over them
+extern "C" int32_t vox_debug_stream_tap_peeked(vox_stream* st, float* out, int32_t rows) {
+    ARGCHK(st && out, "null argument"); ARGCHK(st->tap, "no stream tap armed (vox_debug_stream_tap_arm)"); VOXCHK(ctx_bind(st->ctx));
+    ARGCHK(rows >= 0 && st->tap_rows + rows <= st->tap_max, "%d peeked rows behind %d of a tap of %d", rows, st->tap_rows, st->tap_max);
+    HIPCHK(hipStreamSynchronize(st->ctx->stream));
+    if (rows > 0) HIPCHK(hipMemcpy(out, st->tap + (size_t)st->tap_rows * st->m->cfg.vocab, (size_t)rows * st->m->cfg.vocab * 4, hipMemcpyDeviceToHost));
     return VOX_OK;
 }
 
@@ -4754,6 +4854,7 @@ struct vox_stream_group {
     GroupIngest* d_ingest = nullptr; std::deque<GroupIngest> ingests;      // the pass's ingest descriptors on the device; the ones uploaded by the call in flight, as orders
     int16_t* s16_stage = nullptr;      // host 16-bit feeds: STREAM_SAMPLE_RING samples of device staging per member, allocated at the first one
     int n_scored = 0;                  // members with scores on: a round launches stream_score_kernel only while there is one
+    float* keep = nullptr; size_t keep_floats = 0;      // vox_stream_group_peek: [16 ints: the peeking members, slot by slot][a ring keep area per slot]; grows on demand, counted in `bytes`
 };
 // the member leaves its rate: its input ring and its reference to the rate's matrix go (the matrix with its last reference).  The caller has synchronised.
 static void group_member_drop_rate(vox_stream_group* g, int i) {
@@ -4806,7 +4907,7 @@ static void group_release(vox_stream_group* g) {
     for (StreamMember& me : g->h_mem) if (me.tap) (void)hipFree(me.tap);
     for (GroupMember& me : g->mem) if (me.sc.dev) (void)hipFree(me.sc.dev);
     for (size_t i = 0; i < g->mem.size(); i++) group_member_drop_rate(g, (int)i);
-    for (void* p : {(void*)g->d_ingest, (void*)g->s16_stage, (void*)g->kring, (void*)g->vring, (void*)g->dec_k, (void*)g->dec_v, (void*)g->samples, (void*)g->ws, (void*)g->tokens, (void*)g->state, (void*)g->d_mem, (void*)g->d_order,
+    for (void* p : {(void*)g->keep, (void*)g->d_ingest, (void*)g->s16_stage, (void*)g->kring, (void*)g->vring, (void*)g->dec_k, (void*)g->dec_v, (void*)g->samples, (void*)g->ws, (void*)g->tokens, (void*)g->state, (void*)g->d_mem, (void*)g->d_order,
                     (void*)g->qkv, (void*)g->att, (void*)g->logits, (void*)g->ssq, (void*)g->xf1, (void*)g->xf2, (void*)g->xf3}) if (p) (void)hipFree(p);
     delete g;
 }
@@ -4899,7 +5000,7 @@ static int32_t group_round(vox_stream_group* g, const StreamWs& w, int n_r) {
 // entry: the copies, and the slots of ONE ingest upload and of at most one stream_group_s16_kernel and one stream_group_resample_kernel launch) and group_run_rounds
 // (ONE order upload, the rounds, pos and steps), then group_drain (the id copies behind the call's ONE synchronisation).  The rounds see 16 kHz rings only.
 struct GroupFeed { int member; const void* p; FeedPlan plan; };      // one entry of the call: its member, its samples (f32 or 16-bit, at the member's rate), its plan
-struct GroupCall { std::vector<GroupFeed> fs; int32_t mem_kind = VOX_MEM_HOST; bool s16 = false, staged = false, any_rate = false; };      // staged: host 16-bit samples pass through g->s16_stage
+struct GroupCall { std::vector<GroupFeed> fs; int32_t mem_kind = VOX_MEM_HOST; bool s16 = false, staged = false, any_rate = false, peek = false; };      // staged: host 16-bit samples pass through g->s16_stage; peek: every entry is planned as a finish (vox_stream_group_peek)
 typedef std::vector<std::pair<int, int>> GroupDue;      // (ticks due in this pass, member)
 static int32_t group_plan_entries(const vox_stream_group* g, const vox_stream_feed* feeds, int32_t n_feeds, GroupCall* call) {
     unsigned seen = 0; call->fs.reserve((size_t)n_feeds);
@@ -4909,9 +5010,10 @@ static int32_t group_plan_entries(const vox_stream_group* g, const vox_stream_fe
         ARGCHK(!((seen >> f.member) & 1u), "entry %d: member %d is fed twice in one call", k, f.member); seen |= 1u << f.member;
         ARGCHK(f.samples || f.n_samples == 0, "entry %d: null samples", k); ARGCHK(f.n_samples <= ((size_t)1 << 36), "entry %d: push of %zu samples", k, f.n_samples);
         ARGCHK(f.cap >= 0 && (f.out_ids || f.cap == 0), "entry %d: bad output buffer", k); ARGCHK(f.finish == 0 || f.finish == 1, "entry %d: finish must be 0 or 1", k);
+        if (call->peek) ARGCHK(f.n_samples == 0 && f.finish == 0, "entry %d: a peek takes no samples and no finish flag (push first, then peek)", k);
         char who[48]; snprintf(who, sizeof who, "entry %d: member %d", k, f.member);
         GroupFeed gf{f.member, f.samples, FeedPlan{}};
-        VOXCHK(feed_plan(g->mem[f.member].feed, g->m->cfg.reshape_factor, g->g.left, g->g.max_pos, f.n_samples, f.finish != 0, f.cap, who, &gf.plan));
+        VOXCHK(feed_plan(g->mem[f.member].feed, g->m->cfg.reshape_factor, g->g.left, g->g.max_pos, f.n_samples, call->peek || f.finish != 0, f.cap, who, &gf.plan));
         call->any_rate |= g->mem[f.member].rate >= 0;
         call->fs.push_back(gf);
     }
@@ -5009,6 +5111,73 @@ extern "C" int32_t vox_stream_group_advance(vox_stream_group* g, vox_stream_feed
 extern "C" int32_t vox_stream_group_advance_s16(vox_stream_group* g, vox_stream_feed* feeds, int32_t n_feeds, int32_t mem_kind) {
     return group_advance(g, feeds, n_feeds, mem_kind, true);
 }
+// vox_stream_group_peek: advance's units -- plan the entries (each as a finish), stage ONE pass, run its rounds, drain -- between the two directions of the ring keep,
+// the peeking members as its slots; then every peeking member's feed and tick count as they were.  The restore is enqueued in front of the drain's synchronisation: one
+// synchronisation per call, as advance.  The slab does not grow and a member's tap count lives in its state block: nothing else to undo.
+static int32_t group_keep_launch(vox_stream_group* g, int n, int rows, int restore) {
+    const vox_model_cfg& c = g->m->cfg;
+    StreamKeepParams kp{}; kp.mem = g->d_mem; kp.order = reinterpret_cast<const int*>(g->keep); kp.n = n; kp.layers = c.enc_layers; kp.n_heads = c.enc_heads; kp.hd = c.enc_head_dim;
+    kp.cap = g->g.cap; kp.rows = rows; kp.keep = g->keep + GROUP_MAX; kp.slot_stride = stream_keep_floats(c.enc_layers, c.enc_heads, c.enc_head_dim, rows);
+    HIPCHK(launch_stream_keep(kp, restore, g->ctx->stream));
+    return VOX_OK;
+}
+extern "C" int32_t vox_stream_group_peek(vox_stream_group* g, vox_stream_feed* feeds, int32_t n_feeds, vox_token_score* const* scores_or_null) {
+    ARGCHK(g && (feeds || n_feeds == 0), "null argument"); ARGCHK(n_feeds >= 0 && n_feeds <= g->n, "%d entries for a group of %d members", n_feeds, g->n);
+    vox_model* m = g->m; const vox_model_cfg& c = m->cfg; const int R = c.reshape_factor;
+    GroupCall call; call.peek = true;
+    VOXCHK(group_plan_entries(g, feeds, n_feeds, &call));      // finish's refusals for every entry, nothing changed
+    if (call.fs.empty()) return VOX_OK;
+    int T = 0;
+    for (const GroupFeed& e : call.fs) {
+        const int t = peek_max_ticks(g->mem[e.member].feed, R); T = std::max(T, t);
+        ARGCHK(e.plan.due <= t, "internal: member %d: a peek of %d ticks, %d at the most by the pad and the rate plan", e.member, e.plan.due, t);
+    }
+    VOXCHK(ctx_bind(g->ctx)); hipStream_t s = g->ctx->stream;
+    const int n = (int)call.fs.size(), rows = std::min(g->g.cap, R * T);
+    const size_t need = GROUP_MAX + (size_t)n * stream_keep_floats(c.enc_layers, c.enc_heads, c.enc_head_dim, rows);
+    if (g->keep_floats < need) {      // the save area: a slot per peeking member, allocated at the first peek that needs it
+        HIPCHK(hipStreamSynchronize(s));
+        float* q = nullptr;
+        if (hipMalloc((void**)&q, need * 4) != hipSuccess) { (void)hipGetLastError(); return fail(VOX_ERR_HIP, "hipMalloc of the group's %zu-byte peek save area failed", need * 4); }
+        if (g->keep) (void)hipFree(g->keep);
+        g->bytes += (need - g->keep_floats) * 4; g->keep = q; g->keep_floats = need;
+    }
+    if (m->pw_pend_rows > 0) VOXCHK(pw_sync(m));
+    VOXCHK(vox_model_set_t_embed(m, g->t_embed.data()));
+    StreamWs w; stream_ws_carve(m, g->n, g->ws, &w);
+    struct Was { int64_t n_written; int pos; uint64_t steps; };
+    std::vector<Was> was; for (const GroupFeed& e : call.fs) was.push_back(Was{g->mem[e.member].feed.n_written, g->mem[e.member].feed.pos, g->mem[e.member].steps});
+    bool restored = false;
+    auto body = [&]() -> int32_t {
+        g->orders.emplace_back(); std::array<int, GROUP_MAX>& slots = g->orders.back(); slots.fill(0);      // (alive until the synchronisation, as a pass's order)
+        for (int k = 0; k < n; k++) slots[(size_t)k] = call.fs[(size_t)k].member;
+        HIPCHK(hipMemcpyAsync(g->keep, slots.data(), sizeof(int) * GROUP_MAX, hipMemcpyHostToDevice, s));
+        VOXCHK(group_keep_launch(g, n, rows, 0));
+        GroupDue due; bool idle = false;
+        VOXCHK(group_stage_pass(g, call, &due, &idle));
+        if (!due.empty()) VOXCHK(group_run_rounds(g, w, due));
+        // ONE pass: a second would size its room from the advanced positions and could overwrite samples the members still read once they are taken back
+        for (const GroupFeed& e : call.fs) if (feed_open(g->mem[e.member].feed, e.plan)) return fail(VOX_ERR_INVALID, "internal: member %d: a peek needs a second pass", e.member);
+        for (int k = 0; k < n; k++) {
+            const GroupFeed& e = call.fs[(size_t)k]; const GroupMember& me = g->mem[e.member];
+            if (e.plan.due > 0) HIPCHK(hipMemcpyAsync(feeds[k].out_ids, g->h_mem[e.member].tokens + VOX_PREFIX_TOKENS + me.feed.ids_out, (size_t)e.plan.due * 4, hipMemcpyDeviceToHost, s));
+            if (scores_or_null) VOXCHK(peek_scores_enqueue(me.sc, me.feed.ids_out, e.plan.due, PeekOut{scores_or_null[k]}, s));
+        }
+        VOXCHK(group_keep_launch(g, n, rows, 1)); restored = true;
+        HIPCHK(hipStreamSynchronize(s));      // the call's one synchronisation
+        return VOX_OK;
+    };
+    int32_t r = body();
+    if (r != VOX_OK && !restored) (void)group_keep_launch(g, n, rows, 1);      // a failed tail is taken back as well
+    if (r != VOX_OK) (void)hipStreamSynchronize(s);
+    g->orders.clear(); g->ingests.clear();
+    for (int k = 0; k < n; k++) {
+        const GroupFeed& e = call.fs[(size_t)k]; GroupMember& me = g->mem[e.member];
+        me.feed.n_written = was[(size_t)k].n_written; me.feed.pos = was[(size_t)k].pos; me.feed.finished = false; me.steps = was[(size_t)k].steps;
+        if (r == VOX_OK) { feeds[k].n_ids = e.plan.due; if (scores_or_null) peek_scores_settle(me.sc, e.plan.due, feeds[k].out_ids, PeekOut{scores_or_null[k]}); }
+    }
+    return r;
+}
 extern "C" int32_t vox_stream_group_set_scores(vox_stream_group* g, int32_t member, int32_t on) {
     ARGCHK(g, "null group"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1); ARGCHK(on == 0 || on == 1, "on must be 0 or 1");
     VOXCHK(ctx_bind(g->ctx));
@@ -5064,11 +5233,14 @@ extern "C" int32_t vox_debug_stream_feed_passes(uint32_t sample_rate, const size
     f.restart(VOX_PREFIX_TOKENS - 1);
     int k = 0;
     for (int c = 0; c < n_calls; c++) {
-        ARGCHK(finish[c] == 0 || finish[c] == 1, "call %d: finish must be 0 or 1", c); ARGCHK(n_samples[c] <= ((size_t)1 << 36), "call %d: push of %zu samples", c, n_samples[c]);
+        ARGCHK(finish[c] >= 0 && finish[c] <= 2, "call %d: finish must be 0, 1 or 2 (a peek)", c); ARGCHK(n_samples[c] <= ((size_t)1 << 36), "call %d: push of %zu samples", c, n_samples[c]);
+        const bool peek = finish[c] == 2; ARGCHK(!peek || n_samples[c] == 0, "call %d: finish = 2 (a peek) takes no samples", c);
         char who[32]; snprintf(who, sizeof who, "call %d: the session", c);
         FeedPlan plan; VOXCHK(feed_plan(f, R, left, INT32_MAX, n_samples[c], finish[c] != 0, INT32_MAX, who, &plan));
         f.n_pushed += (int64_t)plan.n;
-        while (feed_open(f, plan)) {
+        const int64_t was_written = f.n_written; const int was_pos = f.pos;
+        for (int pass = 0; feed_open(f, plan); pass++) {
+            if (peek && pass > 0) return fail(VOX_ERR_INVALID, "internal: call %d: a peek needs a second pass", c);
             const FeedPass q = feed_pass(f, plan, R, left, pass_cap ? pass_cap : SIZE_MAX);
             if (q.idle()) return fail(VOX_ERR_INVALID, "internal: call %d stalled at position %d of %d", c, f.pos, plan.target);
             ARGCHK(k < max_rows, "more than %d passes: the output buffer is too small", max_rows);
@@ -5076,6 +5248,7 @@ extern "C" int32_t vox_debug_stream_feed_passes(uint32_t sample_rate, const size
             r[0] = c; r[1] = (int64_t)q.n_in; r[2] = (int64_t)q.n16; r[3] = (int64_t)q.pad; r[4] = q.ticks;
             f.pos += q.ticks;
         }
+        if (peek) { f.n_written = was_written; f.pos = was_pos; continue; }      // the session as it was: the drivers' rollback of the feed
         f.ids_out += plan.due; f.finished = plan.finish;
     }
     *n_rows = k;

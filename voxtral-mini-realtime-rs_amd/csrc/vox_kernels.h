@@ -444,5 +444,17 @@ hipError_t launch_score_rows(const float* x, int rows, int V, const int* ids, To
 // behind launch_stream_advance / launch_stream_group_advance: slot z < n scores the id session order[z] just emitted (tokens[STRM_POS]) on row z of logits [n][vocab],
 // into mem[order[z]].scores[STRM_POS - first_pos]; sessions whose scores pointer is null are skipped
 hipError_t launch_stream_score(const float* logits, int vocab, const StreamMember* mem, const int* order, int n, int first_pos, hipStream_t s);
+// ---- the ring keep of a peek (vox_stream_peek, vox_stream_group_peek): around ticks that are taken back.  Slot z < n works for session order[z] on its own area
+// keep + z * slot_stride (floats, a multiple of 4): [STRM_WORDS ints: the state block][K: layers x n_heads x rows x hd][V: the same].
+// restore = 0 (save, in front of the ticks): the state block, and of every (layer, head) of K and V the `rows` ring rows from STRM_HEAD on, modulo cap -- the slots the
+// next rows / 4 ticks write.  restore = 1 (behind them): the same rows back from where the SAVED block's STRM_HEAD points, then the block itself.  16-byte accesses, no
+// arithmetic on the values; the launch arguments of the two directions of a call are the same.  rows <= cap, hd % 4 == 0.
+struct StreamKeepParams {
+    const StreamMember* mem; const int* order; int n;
+    int layers, n_heads, hd, cap, rows;
+    float* keep; size_t slot_stride;
+};
+size_t stream_keep_floats(int layers, int n_heads, int hd, int rows);      // one slot's area
+hipError_t launch_stream_keep(const StreamKeepParams& p, int restore, hipStream_t s);
 
 }  // namespace vox

@@ -4598,4 +4598,41 @@ hipError_t launch_stream_score(const float* logits, int vocab, const StreamMembe
     return hipGetLastError();
 }
 
+// the ring keep of a peek: slot z = blockIdx.z copies, for session order[z], `rows` ring rows of every (layer, head) of K and V between the ring and the slot's area, and
+// the session's state block.  The ring rows start at STRM_HEAD -- the live block's at save, the SAVED block's at restore (the live one has moved on by then) -- and wrap
+// at cap.  Nobody writes what another thread reads: the save leaves the live block alone, the restore the saved one.
+template <int RESTORE>
+__global__ __launch_bounds__(256) void stream_keep_kernel(StreamKeepParams p) {
+    const StreamMember& me = p.mem[p.order[blockIdx.z]];
+    float* area = p.keep + (size_t)blockIdx.z * p.slot_stride;
+    int* kstate = reinterpret_cast<int*>(area);
+    const int head = RESTORE ? kstate[STRM_HEAD] : me.state[STRM_HEAD];
+    if (head < 0 || head >= p.cap) return;           // (never: the advance kernels keep STRM_HEAD inside the ring)
+    if (blockIdx.x == 0 && threadIdx.x < STRM_WORDS) {
+        if (RESTORE) me.state[threadIdx.x] = kstate[threadIdx.x]; else kstate[threadIdx.x] = me.state[threadIdx.x];
+    }
+    const int hq = p.hd / 4;
+    const long plane = (long)p.layers * p.n_heads * p.rows * hq;      // float4s of K (and of V)
+    float4* kk = reinterpret_cast<float4*>(area + STRM_WORDS);
+    float4* kv = kk + plane;
+    float4* rk = reinterpret_cast<float4*>(me.kring);
+    float4* rv = reinterpret_cast<float4*>(me.vring);
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < plane; i += (long)gridDim.x * blockDim.x) {
+        const int q = (int)(i % hq); const long lr = i / hq; const int r = (int)(lr % p.rows); const long lh = lr / p.rows;
+        int slot = head + r; if (slot >= p.cap) slot -= p.cap;
+        const long ring = (lh * p.cap + slot) * hq + q;
+        if (RESTORE) { rk[ring] = kk[i]; rv[ring] = kv[i]; } else { kk[i] = rk[ring]; kv[i] = rv[ring]; }
+    }
+}
+size_t stream_keep_floats(int layers, int n_heads, int hd, int rows) { return (size_t)STRM_WORDS + 2 * (size_t)layers * n_heads * rows * hd; }
+hipError_t launch_stream_keep(const StreamKeepParams& p, int restore, hipStream_t s) {
+    if (p.n < 1 || p.n > 16 || !p.mem || !p.order || !p.keep || p.layers < 1 || p.n_heads < 1 || p.hd < 4 || (p.hd & 3) || p.rows < 1 || p.rows > p.cap) return hipErrorInvalidValue;
+    if ((p.slot_stride & 3) || p.slot_stride < stream_keep_floats(p.layers, p.n_heads, p.hd, p.rows)) return hipErrorInvalidValue;
+    const long plane = (long)p.layers * p.n_heads * p.rows * (p.hd / 4);
+    int blocks = (int)((plane + 255) / 256); if (blocks > 2048) blocks = 2048;
+    if (restore) stream_keep_kernel<1><<<dim3(blocks, 1, p.n), dim3(256), 0, s>>>(p);
+    else stream_keep_kernel<0><<<dim3(blocks, 1, p.n), dim3(256), 0, s>>>(p);
+    return hipGetLastError();
+}
+
 }  // namespace vox

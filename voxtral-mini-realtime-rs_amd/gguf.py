@@ -483,6 +483,14 @@ def stream_schedule(n_samples: int, finished: bool = False, sample_rate: int = 1
     return p.value, i.value
 
 
+def stream_peek_ids(n_samples: int, ids_out: int, sample_rate: int = 16000) -> int:
+    """vox_stream_peek_ids (host arithmetic): the ids a peek returns after `n_samples` pushed at `sample_rate` with `ids_out` ids handed out -- the finished schedule's
+    count minus those."""
+    n = C.c_int32()
+    check(lib().vox_stream_peek_ids(int(n_samples), int(sample_rate), int(ids_out), C.byref(n)))
+    return n.value
+
+
 class LiveStream:
     """A live streaming session (vox_stream): push samples in pieces of any size, get token ids back as soon as they are determined; after finish() the
     concatenation equals transcribe_streaming on the log-mel of pad_audio(gain * samples).  One decoder position = 2560 samples = 160 ms at 16 kHz.
@@ -522,6 +530,14 @@ class LiveStream:
         """End of the utterance: the right pad is appended, the remaining ids come back."""
         return self._ids(lambda o, c, n: lib().vox_stream_finish(self.h, o, c, n), 0, True)
 
+    def peek(self, return_scores=False):
+        """vox_stream_peek: the ids finish() would return now; the session stays what it was and goes on with the next push (or finish).  return_scores: -> (ids, the
+        records of those ids as scores() gives them; with scores off: NaN, NaN, -1, id).  The session's own record list is not extended."""
+        inf = self.info(); due = stream_peek_ids(inf["samples"], inf["ids"], self.sample_rate)
+        ids = np.zeros(max(due, 1), dtype=np.int32); rec = np.zeros(max(due, 1), dtype=SCORE_DTYPE); n = C.c_int32()
+        check(lib().vox_stream_peek(self.h, _ptr(ids), ids.size, C.byref(n), _ptr(rec) if return_scores else None))
+        return (ids[:n.value].copy(), rec[:n.value].copy()) if return_scores else ids[:n.value].copy()
+
     def reset(self):
         check(lib().vox_stream_reset(self.h))
 
@@ -551,6 +567,12 @@ class LiveStream:
         if rows.value > self._tap_max:
             raise VoxError(1, f"stream tap: {rows.value} rows for a tap of {self._tap_max}")
         return buf[:rows.value].copy()
+
+    def tap_peeked(self, rows):
+        """vox_debug_stream_tap_peeked: the logits rows behind the ids of the last peek(), [rows][vocab]; the tap goes on."""
+        buf = np.zeros((int(rows), self.model.config.vocab), dtype=np.float32)
+        check(lib().vox_debug_stream_tap_peeked(self.h, _ptr(buf), int(rows)))
+        return buf
 
     def front_tap_arm(self, max_ticks):
         check(lib().vox_debug_stream_front_tap_arm(self.h, int(max_ticks))); self._ftap_max = int(max_ticks)
@@ -634,6 +656,24 @@ class LiveStreamGroup:
         out = {}
         for e in arr[:len(entries)]:
             out[e.member] = np.ctypeslib.as_array((C.c_int32 * max(e.cap, 1)).from_address(e.out_ids))[:e.n_ids].copy()
+        return out
+
+    def peek(self, members, return_scores=False) -> dict:
+        """vox_stream_group_peek: {member: the ids advance(finish=[member]) would hand it now} for every member named, in one call; the group stays what it was.
+        return_scores: {member: (ids, records)} as LiveStream.peek."""
+        ms = [int(k) for k in members]
+        arr = (_lib.StreamFeed * max(len(ms), 1))(); keep = []; recs = []
+        for e, k in zip(arr, ms):
+            if not 0 <= k < self.n_members:
+                raise ValueError(f"member {k} of a group of {self.n_members}")
+            inf = self.info(k); due = max(stream_peek_ids(inf["samples"], inf["ids"], self.sample_rate(k)), 1)
+            ids = np.zeros(due, dtype=np.int32); keep.append(ids); recs.append(np.zeros(due, dtype=SCORE_DTYPE))
+            e.member = k; e.finish = 0; e.samples = None; e.n_samples = 0; e.out_ids = ids.ctypes.data; e.cap = ids.size; e.n_ids = 0
+        ptrs = (C.c_void_p * max(len(ms), 1))(*[r.ctypes.data for r in recs])
+        check(lib().vox_stream_group_peek(self.h, arr, len(ms), ptrs if return_scores else None))
+        out = {}
+        for e, ids, rec in zip(arr, keep, recs):
+            out[e.member] = (ids[:e.n_ids].copy(), rec[:e.n_ids].copy()) if return_scores else ids[:e.n_ids].copy()
         return out
 
     def reset(self, member, gain=1.0, sample_rate=None):
