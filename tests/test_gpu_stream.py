@@ -13,21 +13,12 @@ import os
 import numpy as np
 import pytest
 
-from model_fixtures import cache_dir, check_greedy_ids, single_stream_reference, tiny_gguf
+from model_fixtures import check_greedy_ids, single_stream_reference, tiny_gguf
+from stream_helpers import _full_path, _gain, _pieces, _stop, _t
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-4
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "fullsize_16s_peaked_oracle.npz")
-
-
-def _full_path(peaked):
-    name, seed = ("full_q4_peaked_seed44.gguf", 44) if peaked else ("full_q4_seed42.gguf", 42)
-    path = os.path.join(cache_dir(), name)
-    if not os.path.exists(path):
-        from __graft_entry__ import load_package
-        S = load_package().synth
-        S.write_synthetic_gguf(path + ".tmp", S.ModelDims(), seed=seed, **({"peaked": True} if peaked else {})); os.replace(path + ".tmp", path)
-    return path
 
 
 @pytest.fixture(scope="module")
@@ -68,25 +59,6 @@ def _loud(seconds, seed):
     return (0.4 * rng.standard_normal(n) + 0.3 * np.sin(np.arange(n) * 0.07)).astype(np.float32)
 
 
-def _t(pkg, m, delay=6.0):
-    return pkg.TimeEmbedding(m.config.dec_dim).embed(delay)
-
-
-def _gain(x):
-    """peak_normalize(0.95)'s scale (audio/io.rs:59-68): 0.95 / max|x| in f32, 1 for silence."""
-    mx = np.float32(np.abs(x).max()) if x.size else np.float32(0)
-    return float(np.float32(0.95) / mx) if mx >= 1e-10 else 1.0
-
-
-def _stop(lg):
-    srt = np.sort(lg, axis=1); safe = (srt[:, -1] - srt[:, -2]) > 10 * TOL * max(1.0, float(np.abs(lg).max()))
-    return len(safe) if safe.all() else int(np.argmin(safe))
-
-
-def _pieces(n, size):
-    return [(a, min(n, a + size)) for a in range(0, n, size)]
-
-
 def _run(pkg, st, x, cuts, check_schedule=True):
     """Push x[a:b] for every (a, b) of cuts, then finish: (all ids, ids per call).  Every call must return exactly what the schedule says was due."""
     per = []; pushed = 0; had = 0
@@ -123,7 +95,7 @@ def _clips(pkg):
 
 def _compare_with_offline(pkg, ctx, m, x, t, label, condition):
     rids, rlg = _reference(pkg, ctx, m, x, t)
-    stop = _stop(rlg)
+    stop = _stop(rlg, TOL)
     sids = _stream_ids(pkg, m, x, t)
     print(f"{label}: {len(sids)} ids, stream == reference on {int((sids == rids).sum()) if len(sids) == len(rids) else -1}, first near-tie of the reference at {stop}")
     assert len(sids) == len(rids) and len(sids) >= 8
@@ -311,7 +283,7 @@ def test_past_1024_positions_tiny_against_the_oracle(pkg, ctx, orc):
         xn = np.array(x, dtype=np.float32, copy=True); orc.lib().orc_peak_normalize(xn, xn.size, 0.95)
         mel = np.ascontiguousarray(orc.mel_compute_log(orc.pad_audio(xn)).T)
         rids, rlg = om.transcribe_streaming(mel, orc.time_embedding(6.0, m.config.dec_dim), want_logits=True)
-        stop = _stop(rlg)
+        stop = _stop(rlg, TOL)
         st = m.create_stream(t, gain=_gain(x))
         try:
             sids = _run(pkg, st, x, _pieces(len(x), 16000))[0]; info = st.info()
@@ -340,7 +312,7 @@ def test_past_1024_positions_full_engine_then_operators(pkg, ctx, full_model):
         ib = _run(pkg, b, x, _pieces(len(x), 16000))[0]; info_b = b.info(); lg = b.tap_fetch()
     finally:
         b.close()
-    stop = _stop(lg)
+    stop = _stop(lg, TOL)
     print(f"full 170 s: engine stream {info_a['engine_steps']} engine + {info_a['operator_steps']} per-operator steps; first near-tie of the per-operator stream at {stop}; equal on {int((ia == ib).sum())} of 1071")
     assert len(ia) == len(ib) == 1071 and 2 * stop >= 1071
     assert (ia[:stop] == ib[:stop]).all()

@@ -17,22 +17,13 @@ import os
 import numpy as np
 import pytest
 
-from model_fixtures import GEMM_FORMS, cache_dir, check_greedy_ids, teacher_forced_logits, tiny_gguf
+from model_fixtures import GEMM_FORMS, teacher_forced_logits, tiny_gguf
+from stream_helpers import _full_path, _gain, _held, _raw_advance, _stop, _t
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-4
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "fullsize_16s_peaked_oracle.npz")
 ATTN_FORMS = ("prefill_small", "prefill_mfma", "prefill_f32", "decode", "decode_spec", "decode_gqa", "attn_wo", "engine", "stream_ring")
-
-
-def _full_path(peaked):      # as tests/test_gpu_stream.py builds it
-    name, seed = ("full_q4_peaked_seed44.gguf", 44) if peaked else ("full_q4_seed42.gguf", 42)
-    path = os.path.join(cache_dir(), name)
-    if not os.path.exists(path):
-        from __graft_entry__ import load_package
-        S = load_package().synth
-        S.write_synthetic_gguf(path + ".tmp", S.ModelDims(), seed=seed, **({"peaked": True} if peaked else {})); os.replace(path + ".tmp", path)
-    return path
 
 
 @pytest.fixture(scope="module")
@@ -54,20 +45,6 @@ def full_model(pkg, ctx):
     m = pkg.Q4ModelLoader.from_file(_full_path(True)).load(ctx)
     yield m
     m.close()
-
-
-def _t(pkg, m, delay=6.0):
-    return pkg.TimeEmbedding(m.config.dec_dim).embed(delay)
-
-
-def _gain(x):
-    mx = np.float32(np.abs(x).max()) if x.size else np.float32(0)
-    return float(np.float32(0.95) / mx) if mx >= 1e-10 else 1.0
-
-
-def _stop(lg):
-    srt = np.sort(lg, axis=1); safe = (srt[:, -1] - srt[:, -2]) > 10 * TOL * max(1.0, float(np.abs(lg).max()))
-    return len(safe) if safe.all() else int(np.argmin(safe))
 
 
 _SOLO = {}      # clip key -> (ids, logits) of the solo LiveStream: computed once, shared, read-only
@@ -96,20 +73,10 @@ def _clip(pkg, m, t, seconds, seed, n=None, **kw):
             assert len(x) >= n
             x = np.ascontiguousarray(x[:n])
         ids, lg = _solo(m, (id(m), seconds, s, n, tuple(sorted(kw.items()))), x, t, **kw)
-        if 2 * _stop(lg) >= len(ids):
+        if 2 * _stop(lg, TOL) >= len(ids):
             return x, ids, lg
-        print(f"clip {seconds} s seed {s}: first near-tie at {_stop(lg)} of {len(ids)} ids: another seed")
+        print(f"clip {seconds} s seed {s}: first near-tie at {_stop(lg, TOL)} of {len(ids)} ids: another seed")
     raise AssertionError(f"no seed from {seed} on gives a {seconds} s clip that can carry an ids claim")
-
-
-def _held(ids, rids, rlg, label):
-    """The ids rule of this file."""
-    stop = _stop(rlg)
-    assert len(ids) == len(rids) and len(ids) >= 8, (label, len(ids), len(rids))
-    assert 2 * stop >= len(rids), f"{label}: the reference's first near-tie ({stop}) lies in the first half of {len(rids)} ids: the clip cannot carry the claim"
-    assert (ids[:stop] == rids[:stop]).all(), f"{label}: ids differ from the solo stream's at {np.flatnonzero(ids[:stop] != rids[:stop])[:8]} (first near-tie at {stop})"
-    check_greedy_ids(ids, rids, rlg, TOL)
-    return int((ids == rids).sum())
 
 
 def _counts(pkg):
@@ -178,7 +145,7 @@ def test_sixteen_members_equal_solo_streams_across_every_dispatch_edge(pkg, ctx,
     print(f"round widths seen: {sorted(rec['widths'])}; encoder positions of the 16 members in one call: {rec['positions16']}")
     assert {16, 13, 12, 5, 4, 2, 1} <= rec["widths"]      # 64 and 52 encoder rows (tile GEMM), 48 and 20 (17..48 rows), 16 and 8 (5..16), 4 (GEMV)
     assert len(set(rec["positions16"])) >= 8             # the members are spread over the stream, not in lock-step
-    same = [_held(np.array(rec["ids"][k], np.int32), rec["clips"][k][1], rec["clips"][k][2], f"member {k}") for k in range(16)]
+    same = [_held(np.array(rec["ids"][k], np.int32), rec["clips"][k][1], rec["clips"][k][2], f"member {k}", TOL) for k in range(16)]
     print(f"16 members: ids equal to the solo stream's on {same} of {[len(c[1]) for c in rec['clips']]}")
     for k, lg in rec["taps"].items():
         x, rids, _ = rec["clips"][k]; ids = np.array(rec["ids"][k], np.int32)
@@ -253,9 +220,9 @@ def test_ring_wrap_inside_a_group(pkg, ctx, tiny):
         info = g.info(0)
         assert info["encoder_position"] == 4 * info["positions"] and info["ring_rows"] == 760 and info["encoder_position"] > 760
         assert runs == [3, 3, 3] and len(done) == 9
-        print(f"long member next to 9 short runs: {_held(np.array(got, np.int32), lids, llg, 'the 33 s member')} of {len(lids)} ids equal to the solo stream's")
+        print(f"long member next to 9 short runs: {_held(np.array(got, np.int32), lids, llg, 'the 33 s member', TOL)} of {len(lids)} ids equal to the solo stream's")
         for j, r, ids in done:
-            _held(ids, short[j][1], short[j][2], f"short member {j + 1}, run {r}")
+            _held(ids, short[j][1], short[j][2], f"short member {j + 1}, run {r}", TOL)
     finally:
         g.close()
 
@@ -282,11 +249,11 @@ def test_reset_and_reuse_of_a_member(pkg, ctx, tiny):
                 mid_utterance = [0 < g.info(k)["samples"] < len(clips[k]) for k in (1, 2)]
                 assert g.info(0) == {**g.info(0), "samples": 0, "positions": 37, "ids": 0}
         assert mid_utterance == [True, True]
-        _held(first, a[1], a[2], "member 0, first clip")
+        _held(first, a[1], a[2], "member 0, first clip", TOL)
         # the solo reference of the second clip at ITS gain: 0.5 x with twice the gain is the clip the reference saw, to the last bit of the product
-        _held(np.array(ids[0], np.int32), b[1], b[2], "member 0 after its reset, second clip")
+        _held(np.array(ids[0], np.int32), b[1], b[2], "member 0 after its reset, second clip", TOL)
         for k in (1, 2):
-            _held(np.array(ids[k], np.int32), others[k - 1][1], others[k - 1][2], f"member {k}, mid-utterance during the reset")
+            _held(np.array(ids[k], np.int32), others[k - 1][1], others[k - 1][2], f"member {k}, mid-utterance during the reset", TOL)
     finally:
         g.close()
 
@@ -328,16 +295,6 @@ def test_weights_once_per_round(pkg, ctx, tiny):
 
 
 # ---- 7. refusals ------------------------------------------------------------------------------------------------------------------------------------------------------
-def _raw_advance(pkg, g, entries, mem_kind=0):
-    """vox_stream_group_advance with hand-made entries [(member, finish, samples, cap)] -> (code, message, ids per entry)."""
-    L = pkg.lib(); arr = (pkg._lib.StreamFeed * len(entries))(); bufs = []
-    for e, (member, finish, x, cap) in zip(arr, entries):
-        ids = np.zeros(max(cap, 1), np.int32); bufs.append(ids)
-        e.member = member; e.finish = finish; e.samples = x.ctypes.data if x.size else None; e.n_samples = x.size; e.out_ids = ids.ctypes.data; e.cap = cap
-    code = L.vox_stream_group_advance(g.h, arr, len(entries), mem_kind)
-    return code, (L.vox_last_error() or b"").decode(), [b[:e.n_ids].copy() for b, e in zip(bufs, arr)]
-
-
 def test_refusals_leave_the_group_untouched(pkg, ctx, tiny):
     m = tiny; t = _t(pkg, m)
     x, rids, rlg = _clip(pkg, m, t, 3.0, 31)
@@ -346,28 +303,28 @@ def test_refusals_leave_the_group_untouched(pkg, ctx, tiny):
     try:
         infos = lambda: [g.info(k) for k in range(2)]
         half = x[:len(x) // 2]
-        assert _raw_advance(pkg, g, [(1, 0, half, 64)])[0] == 0      # member 1 is mid-utterance throughout
+        assert _raw_advance(pkg, g, [(1, 0, half, half.size, 64)])[0] == 0      # member 1 is mid-utterance throughout
         before = infos()
-        for entries, kind, needle in [([(0, 0, x, due - 1)], 0, "capacity"), ([(1, 0, half, 64), (0, 0, x, due - 1)], 0, "capacity"),
-                                      ([(0, 0, x, due), (0, 0, x, due)], 0, "twice"), ([(2, 0, x, due)], 0, "member"), ([(-1, 0, x, due)], 0, "member"),
-                                      ([(0, 0, x, due)], 7, "mem_kind")]:
-            code, msg, _ = _raw_advance(pkg, g, entries, kind)
+        for entries, kind, needle in [([(0, 0, x, x.size, due - 1)], 0, "capacity"), ([(1, 0, half, half.size, 64), (0, 0, x, x.size, due - 1)], 0, "capacity"),
+                                      ([(0, 0, x, x.size, due), (0, 0, x, x.size, due)], 0, "twice"), ([(2, 0, x, x.size, due)], 0, "member"), ([(-1, 0, x, x.size, due)], 0, "member"),
+                                      ([(0, 0, x, x.size, due)], 7, "mem_kind")]:
+            code, msg, _ = _raw_advance(pkg, g, entries, mem_kind=kind)
             assert code == 1 and needle in msg, (entries[0][:2], msg)
             assert infos() == before
-        code, msg, out = _raw_advance(pkg, g, [(0, 0, x, due)])      # the repeated call with room
+        code, msg, out = _raw_advance(pkg, g, [(0, 0, x, x.size, due)])      # the repeated call with room
         assert code == 0 and np.array_equal(out[0], rids[:due])
         before = infos()
-        code, msg, _ = _raw_advance(pkg, g, [(0, 1, x[:0], 1)])       # finish with too small a buffer
+        code, msg, _ = _raw_advance(pkg, g, [(0, 1, x[:0], 0, 1)])       # finish with too small a buffer
         assert code == 1 and "capacity" in msg and infos() == before
         rest = g.advance({}, finish=[0])[0]
-        _held(np.concatenate([out[0], rest]), rids, rlg, "member 0 after the refused calls")
+        _held(np.concatenate([out[0], rest]), rids, rlg, "member 0 after the refused calls", TOL)
         before = infos()
         for fin in (0, 1):      # a finished member is refused until its reset
-            code, msg, _ = _raw_advance(pkg, g, [(0, fin, x[:100], 64)])
+            code, msg, _ = _raw_advance(pkg, g, [(0, fin, x[:100], 100, 64)])
             assert code == 1 and "finished" in msg and infos() == before
         g.reset(0, _gain(x))
         again = np.concatenate([g.advance({0: x})[0], g.advance({}, finish=[0])[0]])
-        _held(again, rids, rlg, "member 0 after its reset")
+        _held(again, rids, rlg, "member 0 after its reset", TOL)
         rest1 = np.concatenate([g.advance({1: x[len(x) // 2:]})[1], g.advance({}, finish=[1])[1]])
         assert g.info(1)["ids"] == len(rids) and len(rest1) + pkg.stream_schedule(len(half))[1] == len(rids)
     finally:
@@ -383,7 +340,7 @@ def test_refusals_leave_the_group_untouched(pkg, ctx, tiny):
     try:
         a = small.advance({0: x[:2560 * 10 + 40], 1: x[:2560 * 4 + 40]})
         assert len(a[0]) == 11 and np.array_equal(a[0], rids[:11]) and np.array_equal(a[1], rids[:5])      # (11 ids lie before the reference's first near-tie: asserted below)
-        assert _stop(rlg) >= 11
+        assert _stop(rlg, TOL) >= 11
         before = [small.info(k) for k in range(2)]
         with pytest.raises(pkg.VoxError, match="position"):
             small.advance({1: x[2560 * 4 + 40:2560 * 5 + 40], 0: x[2560 * 10 + 40:2560 * 11 + 40]})
@@ -416,8 +373,8 @@ def test_device_and_host_samples_and_a_push_larger_than_the_ring(pkg, ctx, tiny)
                 got_h.extend(g.advance({1: xh[:70000]})[1])      # one host push larger than the 65 536-sample ring, between two device calls
         got_d.extend(g.advance({}, finish=[0], device=True)[0])
         got_h.extend(g.advance({1: xh[70000:]}, finish=[1])[1])
-        _held(np.array(got_d, np.int32), dids, dlg, "the member fed from device memory")
-        _held(np.array(got_h, np.int32), hids, hlg, "the member fed from host memory")
+        _held(np.array(got_d, np.int32), dids, dlg, "the member fed from device memory", TOL)
+        _held(np.array(got_h, np.int32), hids, hlg, "the member fed from host memory", TOL)
     finally:
         pkg._lib.check(pkg.lib().vox_dev_free(ctx.h, dev)); g.close()
 

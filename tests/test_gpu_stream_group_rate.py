@@ -12,7 +12,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from model_fixtures import check_greedy_ids, tiny_gguf
+from model_fixtures import tiny_gguf
+from stream_helpers import _gain, _held, _raw_advance, _stop, _t
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-4
@@ -32,15 +33,6 @@ def model(pkg, ctx):
     m = pkg.Q4ModelLoader.from_file(tiny_gguf()[0]).load(ctx)
     yield m
     m.close()
-
-
-def _t(pkg, m, delay=6.0):
-    return pkg.TimeEmbedding(m.config.dec_dim).embed(delay)
-
-
-def _gain(x):
-    mx = np.float32(np.abs(x).max()) if x.size else np.float32(0)
-    return float(np.float32(0.95) / mx) if mx >= 1e-10 else 1.0
 
 
 def _loud(sr, n, seed):
@@ -214,20 +206,6 @@ def test_s16_equals_f32(pkg, ctx, model):
 
 
 # ---- 4. a push larger than both rings ---------------------------------------------------------------------------------------------------------------------------------
-def _stop(lg):
-    srt = np.sort(lg, axis=1); safe = (srt[:, -1] - srt[:, -2]) > 10 * TOL * max(1.0, float(np.abs(lg).max()))
-    return len(safe) if safe.all() else int(np.argmin(safe))
-
-
-def _held(ids, rids, rlg, label):
-    """The ids rule of tests/test_gpu_stream_group.py."""
-    stop = _stop(rlg)
-    assert len(ids) == len(rids) and len(ids) >= 8, (label, len(ids), len(rids))
-    assert 2 * stop >= len(rids), f"{label}: the reference's first near-tie ({stop}) lies in the first half of {len(rids)} ids: the clip cannot carry the claim"
-    assert (ids[:stop] == rids[:stop]).all(), f"{label}: ids differ from the solo stream's at {np.flatnonzero(ids[:stop] != rids[:stop])[:8]} (first near-tie at {stop})"
-    check_greedy_ids(ids, rids, rlg, TOL)
-
-
 def _solo_clip(pkg, ctx, m, t, sr, n, seed):
     """(x, gain, ids, logits) of a solo stream at sr fed x whole; the seed moved on until the first near-tie lies at or beyond half of the ids."""
     for s in range(seed, seed + 12000, 1000):
@@ -238,9 +216,9 @@ def _solo_clip(pkg, ctx, m, t, sr, n, seed):
         finally:
             st.close()
         assert lg.shape[0] == len(ids)
-        if 2 * _stop(lg) >= len(ids):
+        if 2 * _stop(lg, TOL) >= len(ids):
             return x, gain, ids, lg
-        print(f"{sr} Hz, seed {s}: first near-tie at {_stop(lg)} of {len(ids)} ids: another seed")
+        print(f"{sr} Hz, seed {s}: first near-tie at {_stop(lg, TOL)} of {len(ids)} ids: another seed")
     raise AssertionError("no seed gives a clip that can carry an ids claim")
 
 
@@ -260,8 +238,8 @@ def test_a_push_larger_than_both_rings(pkg, ctx, model):
             assert len(got) + len(ids) == pkg.stream_schedule(b, finished=b == len(xb))[1]
             got.extend(ids)
         assert g.info(0)["samples"] == len(xa) and g.info(1)["samples"] == len(xb)
-        _held(out[0], aids, alg, "the 48 kHz member fed 7 s in one call")
-        _held(np.array(got, np.int32), bids, blg, "the 16 kHz member next to it")
+        _held(out[0], aids, alg, "the 48 kHz member fed 7 s in one call", TOL)
+        _held(np.array(got, np.int32), bids, blg, "the 16 kHz member next to it", TOL)
     finally:
         g.close()
 
@@ -316,16 +294,6 @@ def test_reset_to_another_rate_and_reuse(pkg, ctx, model):
 
 
 # ---- 6. refusals ------------------------------------------------------------------------------------------------------------------------------------------------------
-def _raw_advance(pkg, g, entries, s16=False, mem_kind=0):
-    """vox_stream_group_advance / _s16 with hand-made entries [(member, finish, samples or None, n, cap)] -> (code, message, ids per entry)."""
-    L = pkg.lib(); arr = (pkg._lib.StreamFeed * len(entries))(); bufs = []
-    for e, (member, finish, x, n, cap) in zip(arr, entries):
-        ids = np.zeros(max(cap, 1), np.int32); bufs.append(ids)
-        e.member = member; e.finish = finish; e.samples = None if x is None or not x.size else x.ctypes.data; e.n_samples = n; e.out_ids = ids.ctypes.data; e.cap = cap
-    code = (L.vox_stream_group_advance_s16 if s16 else L.vox_stream_group_advance)(g.h, arr, len(entries), mem_kind)
-    return code, (L.vox_last_error() or b"").decode(), [b[:e.n_ids].copy() for b, e in zip(bufs, arr)]
-
-
 def test_refusals_leave_the_group_untouched(pkg, ctx, model):
     m = model; t = _t(pkg, m); rates = [48000, 16000]
     xa = _loud(48000, int(2.5 * 48000) + 9, 6100); xb = _loud(16000, int(2.5 * 16000) + 4, 6200)

@@ -7,23 +7,14 @@ Every comparison is == on ids, on tapped f32 logits rows and on score records: n
 A solo stream's bits do not depend on how its samples were cut into pushes (tests/test_gpu_stream.py), so a twin may be fed in other pieces; a group's round width
 selects the GEMM kernels, so a group's twins are fed exactly the same calls."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
-from model_fixtures import cache_dir, tiny_gguf
+from model_fixtures import tiny_gguf
+from stream_helpers import _full_path, _gain, _pieces, _t
 
 pytestmark = pytest.mark.gpu
-
-
-def _full_path():      # as tests/test_gpu_stream.py builds it
-    path = os.path.join(cache_dir(), "full_q4_peaked_seed44.gguf")
-    if not os.path.exists(path):
-        from __graft_entry__ import load_package
-        S = load_package().synth
-        S.write_synthetic_gguf(path + ".tmp", S.ModelDims(), seed=44, peaked=True); os.replace(path + ".tmp", path)
-    return path
 
 
 @pytest.fixture(scope="module")
@@ -42,7 +33,7 @@ def tiny(pkg, ctx):
 
 @pytest.fixture(scope="module")
 def full_model(pkg, ctx):
-    m = pkg.Q4ModelLoader.from_file(_full_path()).load(ctx)
+    m = pkg.Q4ModelLoader.from_file(_full_path(True)).load(ctx)
     yield m
     m.close()
 
@@ -50,16 +41,6 @@ def full_model(pkg, ctx):
 @pytest.fixture(scope="module", params=["tiny", "full"])
 def model(request):
     return request.getfixturevalue("tiny" if request.param == "tiny" else "full_model"), request.param
-
-
-def _t(pkg, m, delay=6.0):
-    return pkg.TimeEmbedding(m.config.dec_dim).embed(delay)
-
-
-def _gain(x):
-    x = x.astype(np.float32) / np.float32(32768) if x.dtype == np.int16 else x
-    mx = np.float32(np.abs(x).max()) if x.size else np.float32(0)
-    return float(np.float32(0.95) / mx) if mx >= 1e-10 else 1.0
 
 
 def _words(info):
@@ -117,10 +98,6 @@ def _walk(m, t, x, cuts, peek_after=(), scores=False, tap=256, finish=True, twic
     finally:
         st.close()
     return out
-
-
-def _pieces(n, size, start=0):
-    return [(a, min(n, a + size)) for a in range(start, n, size)]
 
 
 def _same_session(a, b, label):

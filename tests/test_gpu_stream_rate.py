@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from model_fixtures import cache_dir, tiny_gguf
+from stream_helpers import _gain, _pieces, _t
 
 pytestmark = pytest.mark.gpu
 RATES = (48000, 44100, 8000)      # 513 -> 171; 882 -> 320; 512 -> 1024 (up-sampling: fft_in + 1 bins)
@@ -34,19 +35,6 @@ def model(pkg, ctx):
 def _loud(sr, seconds, seed):
     rng = np.random.default_rng(seed); n = int(seconds * sr)
     return (0.4 * rng.standard_normal(n) + 0.3 * np.sin(np.arange(n) * (0.07 * 16000 / sr))).astype(np.float32)
-
-
-def _t(pkg, m, delay=6.0):
-    return pkg.TimeEmbedding(m.config.dec_dim).embed(delay)
-
-
-def _gain(x):
-    mx = np.float32(np.abs(x).max()) if x.size else np.float32(0)
-    return float(np.float32(0.95) / mx) if mx >= 1e-10 else 1.0
-
-
-def _pieces(n, size):
-    return [(a, min(n, a + size)) for a in range(0, n, size)]
 
 
 def _plan(pkg, sr):

@@ -19,7 +19,8 @@ import wave
 import numpy as np
 import pytest
 
-from model_fixtures import cache_dir, tiny_gguf
+from model_fixtures import tiny_gguf
+from stream_helpers import _full_path, _gain, _pieces, _t
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -194,19 +195,6 @@ def _loud(seconds, seed, sr=16000):
     return (0.4 * rng.standard_normal(n) + 0.3 * np.sin(np.arange(n) * (0.07 * 16000 / sr))).astype(F32)
 
 
-def _gain(x):
-    mx = F32(np.abs(x).max()) if x.size else F32(0)
-    return float(F32(0.95) / mx) if mx >= 1e-10 else 1.0
-
-
-def _t(pkg, m):
-    return pkg.TimeEmbedding(m.config.dec_dim).embed(6.0)
-
-
-def _pieces(n, size):
-    return [(a, min(n, a + size)) for a in range(0, n, size)]
-
-
 def _run(st, x, size):
     out = [st.push(x[a:b]) for a, b in _pieces(len(x), size)] + [st.finish()]
     return np.concatenate(out).astype(np.int32)
@@ -274,19 +262,10 @@ def test_solo_tiny_toggling_reset_refusals_and_bytes(pkg, ctx, tiny):
         plain.close(); full.close(); st.close()
 
 
-def _full_peaked_path():      # as tests/test_gpu_stream.py builds it
-    path = os.path.join(cache_dir(), "full_q4_peaked_seed44.gguf")
-    if not os.path.exists(path):
-        from __graft_entry__ import load_package
-        S = load_package().synth
-        S.write_synthetic_gguf(path + ".tmp", S.ModelDims(), seed=44, peaked=True); os.replace(path + ".tmp", path)
-    return path
-
-
 def test_solo_full_size_engine_path(pkg, ctx):
     """The full-size peaked model, 3 s: every decode step is an engine launch, its logits row written on request; the ids are the unscored stream's, the records the
     reference's on the tapped rows at V = 131072."""
-    m = pkg.Q4ModelLoader.from_file(_full_peaked_path()).load(ctx)
+    m = pkg.Q4ModelLoader.from_file(_full_path(True)).load(ctx)
     try:
         t = _t(pkg, m); x = _loud(3.0, 13); g = _gain(x)
         a = m.create_stream(t, gain=g); b = m.create_stream(t, gain=g)

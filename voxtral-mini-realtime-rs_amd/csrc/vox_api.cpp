@@ -4127,6 +4127,8 @@ extern "C" int32_t vox_debug_encode_batch(vox_model* m, int32_t n, const float* 
 // is complete into 16 kHz samples of the ring above (vox_resample's bits: the same matrix, the same sums), the ticks see 16 kHz samples only.  16-bit PCM
 // (vox_stream_push_s16) is converted on the device on its way into whichever ring the stream is fed through.
 // What a call appends, resamples, pads and ticks, pass by pass, is decided by feed_plan / feed_pass on the stream's FeedState -- the planner a group's members share.
+// ONE call path: push, finish and peek are stream_run (a group's advance and peek: group_run), which hands the call's ids and score records back through SessionOut
+// around the call's one synchronisation; a peek is the mode of it that runs between the two directions of the ring keep (ring_keep) and ends in FeedState::rewind.
 // ------------------------------------------------------------------------------------------------
 static const int STREAM_SAMPLE_RING = 1 << 16;      // samples held on the device (a tick reads 160 (4 R + 2) + 400 of them)
 static const int STREAM_KEEP_ROWS = 1024;           // adapter rows kept for the re-run of unverified engine steps; a push verifies at least this often
@@ -4140,6 +4142,9 @@ struct FeedState {
     int64_t in_written = 0;                   // input-rate samples copied into the input ring so far
     int pos = 0, ids_out = 0; bool finished = false;      // decoder position of the next tick; ids handed to the caller; the utterance has ended (until a reset)
     void restart(int PC) { n_pushed = n_written = in_written = 0; pos = PC; ids_out = 0; finished = false; }      // create / reset: the session starts behind the prefix
+    // what a peek takes back: its tail adds no input samples (in_written stays) and hands out no ids of the session's own (ids_out stays)
+    struct Mark { int64_t n_written; int pos; };
+    Mark mark() const { return Mark{n_written, pos}; } void rewind(const Mark& k) { n_written = k.n_written; pos = k.pos; finished = false; }
 };
 // A session's scores (vox_stream_set_scores; DESIGN.md section 8, "Scores"): the device records the score kernel writes, one per id of the utterance, and their host
 // mirror -- one record per id handed out, the ones of a call copied in front of its synchronisation.  Nothing is allocated before the first set(1).
@@ -4147,16 +4152,21 @@ struct ScoreState {
     bool on = false; TokenScore* dev = nullptr; int cap = 0;
     std::vector<vox_token_score> host;
     size_t bytes() const { return dev ? (size_t)cap * sizeof(TokenScore) : 0; }
-    // in front of the call's synchronisation: room for the call's `due` records behind the `have` handed out so far, their copy enqueued when scores are on
-    int32_t enqueue(int have, int due, hipStream_t s) {
-        host.resize((size_t)have + due);
-        if (on && due > 0) HIPCHK(hipMemcpyAsync(host.data() + have, dev + have, (size_t)due * sizeof(TokenScore), hipMemcpyDeviceToHost, s));
+    // the first set(1): the device records of a session of max_pos positions.  `whose`: the message's subject ("the stream's", "member 3's")
+    int32_t alloc(int max_pos, const char* whose) {
+        if (dev) return VOX_OK;
+        if (hipMalloc((void**)&dev, (size_t)(max_pos + 2) * sizeof(TokenScore)) != hipSuccess) { (void)hipGetLastError(); dev = nullptr; return fail(VOX_ERR_HIP, "hipMalloc of %s score records failed", whose); }
+        cap = max_pos + 2; return VOX_OK;
+    }
+    // in front of the call's synchronisation: the copy of the call's `due` records behind the `have` handed out so far, when scores are on and there is a destination
+    int32_t enqueue(int have, int due, vox_token_score* dst, hipStream_t s) const {
+        if (on && dst && due > 0) HIPCHK(hipMemcpyAsync(dst, dev + have, (size_t)due * sizeof(TokenScore), hipMemcpyDeviceToHost, s));
         return VOX_OK;
     }
     // behind it: the ids of a call that ran with scores off get the records that say so
-    void settle(int have, int due, const int32_t* ids) {
+    void settle(int due, const int32_t* ids, vox_token_score* dst) const {
         const float nan = NAN;
-        for (int i = 0; !on && i < due; i++) host[(size_t)have + i] = vox_token_score{nan, nan, -1, ids[i]};
+        for (int i = 0; !on && dst && i < due; i++) dst[i] = vox_token_score{nan, nan, -1, ids[i]};
     }
     int32_t read(int have, int32_t first_id, int32_t n, vox_token_score* out) const {
         ARGCHK(first_id >= 0 && n >= 0 && (int64_t)first_id + n <= have, "%d ids from %d on: %d handed out", n, first_id, have);
@@ -4165,6 +4175,24 @@ struct ScoreState {
         return VOX_OK;
     }
 };
+// One session's share of one call's hand-back -- a solo stream's push / finish / peek, a member's entry of a group's advance / peek: the call's `due` ids from the
+// session's device token array into the caller's out_ids, their records into the session's own list or, in a peek, into the caller's array (null: none wanted).
+namespace {
+struct SessionOut {
+    FeedState* feed; ScoreState* sc; const int* tokens; int32_t* out_ids; int due;
+    bool peek; vox_token_score* peek_scores;      // a peek's records never enter the session's list, and ids_out stays
+    vox_token_score* dst = nullptr;
+    int32_t enqueue(hipStream_t s) {      // in front of the call's synchronisation: the records travel with the ids
+        const int have = feed->ids_out;
+        if (due > 0) HIPCHK(hipMemcpyAsync(out_ids, tokens + VOX_PREFIX_TOKENS + have, (size_t)due * 4, hipMemcpyDeviceToHost, s));
+        if (peek) dst = peek_scores; else { sc->host.resize((size_t)have + due); dst = sc->host.data() + have; }
+        return sc->enqueue(have, due, dst, s);
+    }
+    void settle() { sc->settle(due, out_ids, dst); if (!peek) feed->ids_out += due; }      // behind it
+};
+}  // namespace
+struct DecPlanes { float *k = nullptr, *v = nullptr; int rows = 0; size_t stride = 0; };      // a decoder cache's planes: what a cache that grew inside a peek leaves behind
+struct KeepArea { float* p = nullptr; size_t floats = 0; };      // the ring keep's save area (keep_reserve): allocated at the first peek, counted in its owner's `bytes`
 struct vox_stream {
     vox_model* m = nullptr; vox_ctx* ctx = nullptr;
     std::vector<float> t_embed; float gain = 1.0f;
@@ -4184,10 +4212,8 @@ struct vox_stream {
     ScoreState sc; float* score_row = nullptr;      // scores: the records, and the logits row a scored step writes when no tap row takes it
     float *ftap_mel = nullptr, *ftap_conv = nullptr; int ftap_max = 0, ftap_ticks = 0;      // vox_debug_stream_front_tap_*: per tick its 4 R fresh mel frames and its R conv-stem rows
     int h_state[STRM_WORDS]; int h_pos_word = 0;
-    // vox_stream_peek: the save area of the ring keep (allocated at the first peek, counted in `bytes`) and the ring rows it holds; while a peek's ticks run, a decoder
-    // cache that grows leaves its old planes here instead of freeing them -- the peek puts them back
-    float* keep = nullptr; int keep_rows = 0; bool peeking = false;
-    float *peek_old_k = nullptr, *peek_old_v = nullptr; int peek_old_rows = 0; size_t peek_old_stride = 0;
+    // vox_stream_peek: the ring keep's save area; while a peek's ticks run (active), a decoder cache that grows leaves its planes in `old`: the peek puts them back
+    struct { KeepArea keep; bool active = false; DecPlanes old; } peek;
 };
 
 static long stream_spp(int R) { return 640L * R; }      // samples per decoder position: R encoder rows x 4 frames x 160
@@ -4242,7 +4268,10 @@ static int32_t stream_dec_alloc(vox_stream* st, int rows) {      // a fresh deco
     return cache_alloc(st->m, rows, &st->dec);
 }
 // the cache is full and the session may go on: twice the rows (at most max_pos), the rows so far copied over.  Happens at a position, not at a push: cut-independent.
-static int32_t stream_dec_grow(vox_stream* st) {
+// (a new generation: the engine's layer table for the planes so far is stale)
+static void dec_set_planes(vox_cache* kc, const DecPlanes& p) { cache_unregister(kc); kc->k = p.k; kc->v = p.v; kc->max_seq = p.rows; kc->layer_stride = p.stride; cache_register(kc); }
+// `leave`: where the old planes stay (a peek undoes the growth); null: they are freed
+static int32_t stream_dec_grow(vox_stream* st, DecPlanes* leave) {
     vox_model* m = st->m; const vox_model_cfg& c = m->cfg; hipStream_t s = st->ctx->stream; vox_cache* kc = st->dec;
     const int old = kc->max_seq, rows = std::min(st->max_pos, 2 * old), hd = c.dec_head_dim;
     ARGCHK(rows > old, "internal: decoder cache of %d rows cannot grow", old);
@@ -4253,12 +4282,16 @@ static int32_t stream_dec_grow(vox_stream* st) {
     HIPCHK(hipMemcpy2DAsync(nk, (size_t)rows * hd * 4, kc->k, (size_t)old * hd * 4, (size_t)old * hd * 4, planes, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpy2DAsync(nv, (size_t)rows * hd * 4, kc->v, (size_t)old * hd * 4, (size_t)old * hd * 4, planes, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipStreamSynchronize(s));
-    if (st->peeking) {      // a peek undoes the growth: the old planes wait in the stream
-        if (st->peek_old_k) { (void)hipFree(nk); (void)hipFree(nv); return fail(VOX_ERR_INVALID, "internal: the decoder cache grew twice inside one peek"); }
-        st->peek_old_k = kc->k; st->peek_old_v = kc->v; st->peek_old_rows = old; st->peek_old_stride = kc->layer_stride;
+    if (leave) {
+        if (leave->k) { (void)hipFree(nk); (void)hipFree(nv); return fail(VOX_ERR_INVALID, "internal: the decoder cache grew twice inside one peek"); }
+        *leave = DecPlanes{kc->k, kc->v, old, kc->layer_stride};
     } else { (void)hipFree(kc->k); (void)hipFree(kc->v); }
-    cache_unregister(kc); kc->k = nk; kc->v = nv; kc->max_seq = rows; kc->layer_stride = (size_t)c.dec_kv_heads * rows * hd; cache_register(kc);      // (a new generation: the engine's layer table for the old planes is stale)
+    dec_set_planes(kc, DecPlanes{nk, nv, rows, (size_t)c.dec_kv_heads * rows * hd});
     return VOX_OK;
+}
+// the growth undone: the planes a peek's tail left in `old` go back (nothing in flight: the peek has synchronised), the grown ones are freed
+static void stream_dec_ungrow(vox_stream* st, DecPlanes* old) {
+    if (old->k) { (void)hipFree(st->dec->k); (void)hipFree(st->dec->v); dec_set_planes(st->dec, *old); *old = DecPlanes{}; }
 }
 
 // the state after create / reset of a session (a solo stream, a group's member): the prefix state of its t_embed (built here when the model does not hold it, whatever
@@ -4304,7 +4337,7 @@ static void stream_release(vox_stream* st) {
     cache_release(st->dec);
     for (void* p : {(void*)st->kring, (void*)st->vring, (void*)st->samples, (void*)st->audio_keep, (void*)st->ws, (void*)st->tokens, (void*)st->state, (void*)st->tap, (void*)st->ftap_mel, (void*)st->ftap_conv,
                     (void*)st->feed.At, (void*)st->feed.in_ring, (void*)st->s16_stage, (void*)st->d_mem, (void*)st->sc.dev, (void*)st->score_row,
-                    (void*)st->keep, (void*)st->peek_old_k, (void*)st->peek_old_v}) if (p) (void)hipFree(p);
+                    (void*)st->peek.keep.p, (void*)st->peek.old.k, (void*)st->peek.old.v}) if (p) (void)hipFree(p);
     binding_release(st->eng);
     delete st;
 }
@@ -4384,11 +4417,13 @@ extern "C" int32_t vox_stream_reset(vox_stream* st) {
     HIPCHK(hipStreamSynchronize(st->ctx->stream));
     return stream_load_initial(st);
 }
+// words 0 .. 4 of a session's info: samples pushed, position, ids handed out, encoder rows so far, rows held in its ring
+static void feed_info(const FeedState& f, int R, int cap, int64_t* out) { out[0] = f.n_pushed; out[1] = f.pos; out[2] = f.ids_out; out[3] = (int64_t)R * f.pos; out[4] = std::min<int64_t>(out[3], cap); }
 extern "C" int32_t vox_stream_info(const vox_stream* st, int64_t out[8]) {
     ARGCHK(st && out, "null argument");
     const int R = st->m->cfg.reshape_factor;
     const uint64_t dec_b = st->dec ? 2 * (uint64_t)st->m->cfg.dec_layers * st->dec->layer_stride * 4 : 0, tap_b = (st->tap ? (uint64_t)st->tap_max * st->m->cfg.vocab * 4 : 0) + (st->ftap_mel ? (uint64_t)st->ftap_max * R * (4 * st->m->cfg.n_mels + st->m->cfg.enc_dim) * 4 : 0);
-    out[0] = st->feed.n_pushed; out[1] = st->feed.pos; out[2] = st->feed.ids_out; out[3] = (int64_t)R * st->feed.pos; out[4] = std::min<int64_t>((int64_t)R * st->feed.pos, st->cap);
+    feed_info(st->feed, R, st->cap, out);
     out[5] = (int64_t)(st->bytes + dec_b + tap_b); out[6] = (int64_t)st->eng_steps; out[7] = (int64_t)st->op_steps;
     return VOX_OK;
 }
@@ -4504,7 +4539,7 @@ static int32_t stream_encode_round(vox_model* m, const StreamWs& w, const Stream
 static int32_t stream_tick(vox_stream* st) {
     vox_model* m = st->m; const vox_model_cfg& c = m->cfg; hipStream_t s = st->ctx->stream; const int R = c.reshape_factor;
     if (st->feed.pos - st->verified_pos >= STREAM_KEEP_ROWS) VOXCHK(stream_verify(st));      // the kept adapter rows cover the unverified steps
-    if (st->feed.pos >= st->dec->max_seq) { VOXCHK(stream_verify(st)); VOXCHK(stream_dec_grow(st)); }
+    if (st->feed.pos >= st->dec->max_seq) { VOXCHK(stream_verify(st)); VOXCHK(stream_dec_grow(st, st->peek.active ? &st->peek.old : nullptr)); }
     StreamWs w; stream_ws_carve(m, 1, st->ws, &w);
     const StreamRound r{st->d_mem, st->d_order, 1, st->cap, st->ring_layer, st->mel, st->left};
     const int k = st->ftap_mel ? st->ftap_ticks++ : 0; const bool ftap = st->ftap_mel && k < st->ftap_max;      // (a re-run repeats decode steps, never a tick)
@@ -4553,6 +4588,12 @@ static size_t ring_room16(int R, long left, int pos, int64_t n_written) {
 // what one call feeds a session: n samples at its rate, then `right` zeros (the right pad of a finishing session); `done` of the n + right written so far; goal16: the
 // 16 kHz samples the session holds after the call, before the pad; the ticks up to position `target` run in this call and yield `due` ids
 struct FeedPlan { size_t n = 0, right = 0, done = 0, goal16 = 0; int target = 0, due = 0; bool finish = false; };
+// the checks on one entry's own arguments.  `who`: what the message starts with ("" for a solo stream's call, "entry 2: ")
+static int32_t entry_check(const char* who, const void* samples, size_t n, const int32_t* out_ids, int32_t cap) {
+    ARGCHK(samples || n == 0, "%snull samples", who); ARGCHK(n <= ((size_t)1 << 36), "%spush of %zu samples", who, n);
+    ARGCHK(cap >= 0 && (out_ids || cap == 0), "%sbad output buffer", who);
+    return VOX_OK;
+}
 // every check of a call on one session, nothing changed: a refused call can be repeated.  `who`: the message's subject ("the stream", "entry 2: member 5")
 static int32_t feed_plan(const FeedState& f, int R, long left, int max_pos, size_t n, bool finish, int cap, const char* who, FeedPlan* out) {
     ARGCHK(!f.finished, "%s is finished: a reset starts its next utterance", who);
@@ -4605,37 +4646,49 @@ static FeedPass feed_pass(FeedState& f, FeedPlan& p, int R, long left, size_t in
     return q;
 }
 
-// what a push / finish does around its ticks: the stream's own Ada scales, clean accumulators, the passes of its one session -- input into its first ring, the resampling
-// launch of a rate stream, the pad, then every tick that became due -- then the ids of the call behind ONE synchronisation
-// the ring keep's launch for a solo stream: the round of one
-static int32_t stream_keep_launch(vox_stream* st, int restore) {
-    const vox_model_cfg& c = st->m->cfg;
-    StreamKeepParams kp{}; kp.mem = st->d_mem; kp.order = st->d_order; kp.n = 1; kp.layers = c.enc_layers; kp.n_heads = c.enc_heads; kp.hd = c.enc_head_dim; kp.cap = st->cap;
-    kp.rows = st->keep_rows; kp.keep = st->keep; kp.slot_stride = stream_keep_floats(c.enc_layers, c.enc_heads, c.enc_head_dim, st->keep_rows);
-    HIPCHK(launch_stream_keep(kp, restore, st->ctx->stream));
+// ---- a peek's parts, common to a solo stream and a group ("Peek").
+// A peek is ONE pass: a second would size its room from the advanced position and could overwrite samples the session still reads once it is taken back
+static int32_t peek_second_pass(const char* who) { return fail(VOX_ERR_INVALID, "internal: %s: a peek needs a second pass", who); }
+// the most ticks a peek (a finish) of this session can have due: what is still to come is the backlog of a rate session -- 16 kHz samples of its unfinished block, at
+// most fft_out + delay of them -- and the right pad, at most one token less a sample + the extra tokens; a tick takes stream_spp samples, and position p needs 40 beyond.
+// `due` is checked against it.  `who`: what the message starts with ("", "member 3: ")
+static int32_t peek_max_ticks(const FeedState& f, int R, int due, const char* who, int* T) {
+    vox_pad_cfg pc; vox_pad_cfg_voxtral(&pc);
+    const long spt = (long)pad_spt(&pc), right_max = spt - 1 + (long)pc.extra_right_pad_tokens * spt, backlog = f.sr != 16000 ? f.rp.fft_out + f.rp.delay + 1 : 0;
+    *T = (int)((backlog + right_max + 40) / stream_spp(R)) + 1;
+    ARGCHK(due <= *T, "internal: %sa peek of %d ticks, %d at the most by the pad and the rate plan", who, due, *T);
     return VOX_OK;
 }
-// what a call's ids carry when they are not the session's own: a peek's records go to the caller's array, never into the session's list
-struct PeekOut { vox_token_score* scores = nullptr; };
-static int32_t peek_scores_enqueue(const ScoreState& sc, int have, int due, const PeekOut& pk, hipStream_t s) {
-    if (sc.on && pk.scores && due > 0) HIPCHK(hipMemcpyAsync(pk.scores, sc.dev + have, (size_t)due * sizeof(TokenScore), hipMemcpyDeviceToHost, s));
+// the save area holds `need` floats from here on; its growth is counted in the owner's `bytes`.  `whose`: "stream", "group"
+static int32_t keep_reserve(KeepArea& a, size_t need, uint64_t* bytes, hipStream_t s, const char* whose) {
+    if (a.floats >= need) return VOX_OK;
+    if (a.p) HIPCHK(hipStreamSynchronize(s));      // the area that goes may be in use
+    float* q = nullptr;
+    if (hipMalloc((void**)&q, need * 4) != hipSuccess) { (void)hipGetLastError(); return fail(VOX_ERR_HIP, "hipMalloc of the %s's %zu-byte peek save area failed", whose, need * 4); }
+    if (a.p) (void)hipFree(a.p);
+    *bytes += (need - a.floats) * 4; a.p = q; a.floats = need;
     return VOX_OK;
 }
-static void peek_scores_settle(const ScoreState& sc, int due, const int32_t* ids, const PeekOut& pk) {
-    const float nan = NAN;
-    for (int i = 0; !sc.on && pk.scores && i < due; i++) pk.scores[i] = vox_token_score{nan, nan, -1, ids[i]};
+// a peek's ring keep (launch_stream_keep; restore 0 in front of the tail's ticks, 1 in front of the call's synchronisation): slot z saves or puts back the state block
+// of session order[z] and the `rows` encoder ring rows its tail writes
+static StreamKeepParams ring_keep(const vox_model_cfg& c, const StreamMember* mem, const int* order, int n, int rows, int cap, float* keep) {
+    StreamKeepParams kp{}; kp.mem = mem; kp.order = order; kp.n = n; kp.layers = c.enc_layers; kp.n_heads = c.enc_heads; kp.hd = c.enc_head_dim; kp.cap = cap;
+    kp.rows = rows; kp.keep = keep; kp.slot_stride = stream_keep_floats(c.enc_layers, c.enc_heads, c.enc_head_dim, rows);
+    return kp;
 }
-// pk: the call is a peek (stream_peek, which saved the ring rows and takes the host state back): ONE pass, the ring rows and the state block go back in front of the
-// call's synchronisation, ids_out stays
-static int32_t stream_run(vox_stream* st, const StreamSrc& src, FeedPlan& plan, int32_t* out_ids, int32_t* n_ids, const PeekOut* pk = nullptr) {
-    vox_model* m = st->m; hipStream_t s = st->ctx->stream; FeedState& f = st->feed; const bool rate = f.sr != 16000;
+
+// What a push / finish / peek does around its ticks: the stream's own Ada scales, clean accumulators, the passes of its one session -- input into its first ring, the
+// resampling launch of a rate stream, the pad, then every tick that became due -- then the ids of the call and their records through SessionOut, around ONE synchronisation.
+// keep: the call is a peek (stream_peek, which saved the ring rows and takes the host state back): ONE pass, the ring rows and the state block go back in front of the
+// call's synchronisation, the records go to peek_scores (null: nowhere), ids_out stays
+static int32_t stream_run(vox_stream* st, const StreamSrc& src, FeedPlan& plan, int32_t* out_ids, int32_t* n_ids, const StreamKeepParams* keep = nullptr, vox_token_score* peek_scores = nullptr) {
+    vox_model* m = st->m; hipStream_t s = st->ctx->stream; FeedState& f = st->feed; const bool rate = f.sr != 16000, peek = keep != nullptr;
     const int due = plan.due, R = m->cfg.reshape_factor;
     if (m->pw_pend_rows > 0) VOXCHK(pw_sync(m));      // unverified engine steps of the piecewise surface share the engine's error word: settled first
     VOXCHK(vox_model_set_t_embed(m, st->t_embed.data()));
     if (due > 0) VOXCHK(wo_acc_clear(m, s));
     for (int pass = 0; feed_open(f, plan); pass++) {
-        // a second pass would size its room from the advanced position and could overwrite samples the session still reads once it is taken back
-        if (pk && pass > 0) return fail(VOX_ERR_INVALID, "internal: a peek at position %d needs a second pass (%lld of %zu samples at 16 kHz)", f.pos, (long long)f.n_written, plan.goal16);
+        if (peek && pass > 0) return peek_second_pass("the stream");
         const FeedPass q = feed_pass(f, plan, R, st->left, SIZE_MAX);
         if (q.idle()) return fail(VOX_ERR_INVALID, "internal: stream stalled at position %d of %d (%lld of %zu samples at 16 kHz)", f.pos, plan.target, (long long)f.n_written, plan.goal16);
         VOXCHK(stream_ring_write(st, rate ? f.in_ring : st->samples, rate ? f.in_ring_n : STREAM_SAMPLE_RING, q.in_w0, src, q.at, q.n_in));
@@ -4644,70 +4697,53 @@ static int32_t stream_run(vox_stream* st, const StreamSrc& src, FeedPlan& plan, 
         VOXCHK(ring_write_f32(s, st->samples, STREAM_SAMPLE_RING, q.pad_w0, StreamSrc{}, 0, q.pad));
         for (int t = 0; t < q.ticks; t++) VOXCHK(stream_tick(st));
     }
-    int32_t* ids_dev = st->tokens + VOX_PREFIX_TOKENS + f.ids_out;
+    SessionOut o{&f, &st->sc, st->tokens, out_ids, due, peek, peek_scores};
     VOXCHK(stream_verify_enqueue(st));
-    if (due > 0) HIPCHK(hipMemcpyAsync(out_ids, ids_dev, (size_t)due * 4, hipMemcpyDeviceToHost, s));
-    if (pk) { VOXCHK(peek_scores_enqueue(st->sc, f.ids_out, due, *pk, s)); VOXCHK(stream_keep_launch(st, 1)); }
-    else VOXCHK(st->sc.enqueue(f.ids_out, due, s));      // the records travel with the ids
-    HIPCHK(hipStreamSynchronize(s));      // the call's one synchronisation: ids, their records and the engine's verdict land together
-    bool reran = false; VOXCHK(stream_settle(st, &reran));
-    if (reran && pk) {      // the re-run moved STRM_POS again: the saved block goes back once more (the ring rows with it: the same values)
-        if (due > 0) HIPCHK(hipMemcpyAsync(out_ids, ids_dev, (size_t)due * 4, hipMemcpyDeviceToHost, s));
-        VOXCHK(peek_scores_enqueue(st->sc, f.ids_out, due, *pk, s)); VOXCHK(stream_keep_launch(st, 1)); HIPCHK(hipStreamSynchronize(s));
-    } else if (reran && due > 0) { HIPCHK(hipMemcpyAsync(out_ids, ids_dev, (size_t)due * 4, hipMemcpyDeviceToHost, s)); VOXCHK(st->sc.enqueue(f.ids_out, due, s)); HIPCHK(hipStreamSynchronize(s)); }
-    *n_ids = due;
-    if (pk) { peek_scores_settle(st->sc, due, out_ids, *pk); return VOX_OK; }
-    st->sc.settle(f.ids_out, due, out_ids);
-    f.ids_out += due;
+    bool reran = false;
+    for (int round = 0; round < 2; round++) {      // a second time only behind the engine's re-run, which wrote the call's ids (and moved STRM_POS) again
+        VOXCHK(o.enqueue(s));
+        if (peek) HIPCHK(launch_stream_keep(*keep, 1, s));
+        HIPCHK(hipStreamSynchronize(s));      // the call's one synchronisation: ids, their records and the engine's verdict land together
+        if (round == 0) VOXCHK(stream_settle(st, &reran));
+        if (!reran) break;
+    }
+    *n_ids = due; o.settle();
     return VOX_OK;
 }
-// the most ticks a peek (a finish) of this session can have due: what is still to come is the backlog of a rate session -- 16 kHz samples of its unfinished block, at
-// most fft_out + delay of them -- and the right pad, at most one token less a sample + the extra tokens; a tick takes stream_spp samples, and position p needs 40 beyond
-static int peek_max_ticks(const FeedState& f, int R) {
-    vox_pad_cfg pc; vox_pad_cfg_voxtral(&pc);
-    const long spt = (long)pad_spt(&pc), right_max = spt - 1 + (long)pc.extra_right_pad_tokens * spt, backlog = f.sr != 16000 ? f.rp.fft_out + f.rp.delay + 1 : 0;
-    return (int)((backlog + right_max + 40) / stream_spp(R)) + 1;
-}
 // vox_stream_peek behind its checks: finish's ticks, then the session as it was.  The device takes back the encoder ring rows the tail wrote and the state block
-// (stream_keep_kernel, inside stream_run); the host takes back the feed, the step counts and a decoder cache that grew.  Everything else the tail wrote lies past the
-// session's position and is written again before it is read.
+// (the ring keep, its restore inside stream_run); the host takes back the feed, what StreamMark holds next to it, and a decoder cache that grew.  Everything else the
+// tail wrote lies past the session's position and is written again before it is read.
+struct StreamMark { FeedState::Mark feed; int tap_rows, ftap_ticks; uint64_t eng_steps, op_steps; };      // (the verified counters are set to the same: stream_peek verifies first)
 static int32_t stream_peek(vox_stream* st, FeedPlan& plan, int32_t* out_ids, int32_t* n_ids, vox_token_score* scores) {
     vox_model* m = st->m; const vox_model_cfg& c = m->cfg; hipStream_t s = st->ctx->stream; FeedState& f = st->feed;
-    const int T = peek_max_ticks(f, c.reshape_factor), rows = std::min(st->cap, c.reshape_factor * T);
-    ARGCHK(plan.due <= T, "internal: a peek of %d ticks, %d at the most by the pad and the rate plan", plan.due, T);
-    if (!st->keep) {      // the first peek: the save area, counted in info [5] from now on
-        const size_t nb = stream_keep_floats(c.enc_layers, c.enc_heads, c.enc_head_dim, rows) * 4;
-        if (hipMalloc((void**)&st->keep, nb) != hipSuccess) { (void)hipGetLastError(); st->keep = nullptr; return fail(VOX_ERR_HIP, "hipMalloc of the stream's %zu-byte peek save area failed", nb); }
-        st->keep_rows = rows; st->bytes += nb;
-    }
+    int T; VOXCHK(peek_max_ticks(f, c.reshape_factor, plan.due, "", &T));
+    const int rows = std::min(st->cap, c.reshape_factor * T);      // (a function of the stream's rate and capacity: the area is reserved once)
+    VOXCHK(keep_reserve(st->peek.keep, stream_keep_floats(c.enc_layers, c.enc_heads, c.enc_head_dim, rows), &st->bytes, s, "stream"));
     if (m->pw_pend_rows > 0) VOXCHK(pw_sync(m));
     VOXCHK(stream_verify(st));      // the kept adapter rows cover the tail alone; verified_* are the session's own from here
-    struct { int64_t n_written; int pos, tap_rows, ftap_ticks; uint64_t eng, op; } was{f.n_written, f.pos, st->tap_rows, st->ftap_ticks, st->eng_steps, st->op_steps};
-    int32_t r = stream_keep_launch(st, 0);
-    if (r == VOX_OK) {
-        st->peeking = true;
-        const PeekOut pk{scores};
-        r = stream_run(st, StreamSrc{}, plan, out_ids, n_ids, &pk);
-        st->peeking = false;
-        if (r != VOX_OK) { (void)stream_keep_launch(st, 1); (void)hipStreamSynchronize(s); st->eng_unverified = false; }      // a failed tail is taken back as well
-    }
-    if (st->peek_old_k) {      // the tail crossed the cache's rows: the growth is undone (stream_run has synchronised; engine_bind meets a new generation and rebuilds its table)
-        vox_cache* kc = st->dec;
-        (void)hipFree(kc->k); (void)hipFree(kc->v);
-        cache_unregister(kc); kc->k = st->peek_old_k; kc->v = st->peek_old_v; kc->max_seq = st->peek_old_rows; kc->layer_stride = st->peek_old_stride; cache_register(kc);
-        st->peek_old_k = st->peek_old_v = nullptr;
-    }
-    f.n_written = was.n_written; f.pos = was.pos; f.finished = false; st->dec->len = was.pos;
+    const StreamMark was{f.mark(), st->tap_rows, st->ftap_ticks, st->eng_steps, st->op_steps};
+    const StreamKeepParams keep = ring_keep(c, st->d_mem, st->d_order, 1, rows, st->cap, st->peek.keep.p);      // the round of one
+    HIPCHK(launch_stream_keep(keep, 0, s));
+    st->peek.active = true;
+    const int32_t r = stream_run(st, StreamSrc{}, plan, out_ids, n_ids, &keep, scores);
+    st->peek.active = false;
+    if (r != VOX_OK) { (void)launch_stream_keep(keep, 1, s); (void)hipStreamSynchronize(s); st->eng_unverified = false; }      // a failed tail is taken back as well
+    stream_dec_ungrow(st, &st->peek.old);      // the tail crossed the cache's rows: engine_bind meets a new generation and rebuilds its table
+    f.rewind(was.feed); st->dec->len = st->verified_pos = f.pos;
     st->tap_rows = st->verified_tap_rows = was.tap_rows; st->ftap_ticks = was.ftap_ticks;
-    st->eng_steps = st->verified_eng_steps = was.eng; st->op_steps = st->verified_op_steps = was.op; st->verified_pos = was.pos;
+    st->eng_steps = st->verified_eng_steps = was.eng_steps; st->op_steps = st->verified_op_steps = was.op_steps;
     return r;
 }
 
+// a solo stream's entry -- push, finish, peek: every check, the plan, nothing changed (a refused call can be repeated); then the stream's device
+static int32_t stream_enter(vox_stream* st, const void* samples, size_t n, bool finish, int32_t* out_ids, int32_t cap, int32_t* n_ids, FeedPlan* plan) {
+    ARGCHK(st && n_ids && (samples || n == 0), "null argument"); VOXCHK(entry_check("", samples, n, out_ids, cap));
+    VOXCHK(feed_plan(st->feed, st->m->cfg.reshape_factor, st->left, st->max_pos, n, finish, cap, "the stream", plan));
+    return ctx_bind(st->ctx);
+}
 static int32_t stream_push(vox_stream* st, const void* samples, bool s16, size_t n, int32_t mem_kind, int32_t* out_ids, int32_t cap, int32_t* n_ids) {
-    ARGCHK(st && n_ids && (samples || n == 0), "null argument"); ARGCHK(cap >= 0 && (out_ids || cap == 0), "bad output buffer"); ARGCHK(n <= ((size_t)1 << 36), "push of %zu samples", n);
     ARGCHK(mem_kind == VOX_MEM_HOST || mem_kind == VOX_MEM_DEVICE, "bad mem_kind %d", mem_kind);
-    FeedPlan plan; VOXCHK(feed_plan(st->feed, st->m->cfg.reshape_factor, st->left, st->max_pos, n, false, cap, "the stream", &plan));      // BEFORE anything is appended: the call can be repeated
-    VOXCHK(ctx_bind(st->ctx));
+    FeedPlan plan; VOXCHK(stream_enter(st, samples, n, false, out_ids, cap, n_ids, &plan));
     st->feed.n_pushed += (int64_t)n;
     StreamSrc src; src.p = samples; src.s16 = s16; src.mem_kind = mem_kind;
     return stream_run(st, src, plan, out_ids, n_ids);
@@ -4716,22 +4752,17 @@ extern "C" int32_t vox_stream_push(vox_stream* st, const float* samples, size_t 
     return stream_push(st, samples, false, n, mem_kind, out_ids, cap, n_ids);
 }
 extern "C" int32_t vox_stream_push_s16(vox_stream* st, const int16_t* samples, size_t n, int32_t mem_kind, int32_t* out_ids, int32_t cap, int32_t* n_ids) {
-    ARGCHK(mem_kind == VOX_MEM_HOST || mem_kind == VOX_MEM_DEVICE, "bad mem_kind %d", mem_kind);
     return stream_push(st, samples, true, n, mem_kind, out_ids, cap, n_ids);
 }
 extern "C" int32_t vox_stream_finish(vox_stream* st, int32_t* out_ids, int32_t cap, int32_t* n_ids) {
-    ARGCHK(st && n_ids, "null argument"); ARGCHK(cap >= 0 && (out_ids || cap == 0), "bad output buffer");
-    FeedPlan plan; VOXCHK(feed_plan(st->feed, st->m->cfg.reshape_factor, st->left, st->max_pos, 0, true, cap, "the stream", &plan));
-    VOXCHK(ctx_bind(st->ctx));
+    FeedPlan plan; VOXCHK(stream_enter(st, nullptr, 0, true, out_ids, cap, n_ids, &plan));
     VOXCHK(stream_run(st, StreamSrc{}, plan, out_ids, n_ids));
     st->feed.finished = true;
     return VOX_OK;
 }
 
 extern "C" int32_t vox_stream_peek(vox_stream* st, int32_t* out_ids, int32_t cap, int32_t* n_ids, vox_token_score* scores_or_null) {
-    ARGCHK(st && n_ids, "null argument"); ARGCHK(cap >= 0 && (out_ids || cap == 0), "bad output buffer");
-    FeedPlan plan; VOXCHK(feed_plan(st->feed, st->m->cfg.reshape_factor, st->left, st->max_pos, 0, true, cap, "the stream", &plan));      // finish's refusals, nothing changed
-    VOXCHK(ctx_bind(st->ctx));
+    FeedPlan plan; VOXCHK(stream_enter(st, nullptr, 0, true, out_ids, cap, n_ids, &plan));      // finish's refusals, nothing changed
     return stream_peek(st, plan, out_ids, n_ids, scores_or_null);
 }
 extern "C" int32_t vox_stream_peek_ids(size_t n_samples, uint32_t sample_rate, int32_t ids_out, int32_t* n) {
@@ -4748,14 +4779,13 @@ extern "C" int32_t vox_stream_peek_ids(size_t n_samples, uint32_t sample_rate, i
 extern "C" int32_t vox_stream_set_scores(vox_stream* st, int32_t on) {
     ARGCHK(st, "null stream"); ARGCHK(on == 0 || on == 1, "on must be 0 or 1"); VOXCHK(ctx_bind(st->ctx));
     hipStream_t s = st->ctx->stream; ScoreState& sc = st->sc;
-    if (on && !sc.dev) {
-        const int cap = st->max_pos + 2; const size_t row_b = (size_t)st->m->cfg.vocab * 4;
-        TokenScore* d = nullptr; float* row = nullptr;
-        if (hipMalloc((void**)&d, (size_t)cap * sizeof(TokenScore)) != hipSuccess || hipMalloc((void**)&row, row_b) != hipSuccess) {
-            (void)hipGetLastError(); if (d) (void)hipFree(d);
-            return fail(VOX_ERR_HIP, "hipMalloc of the stream's score records failed");
+    if (on) {      // the first on: the records, and the stream's own logits row
+        const size_t had = sc.bytes(), row_b = (size_t)st->m->cfg.vocab * 4;
+        VOXCHK(sc.alloc(st->max_pos, "the stream's")); st->bytes += sc.bytes() - had;
+        if (!st->score_row) {
+            if (hipMalloc((void**)&st->score_row, row_b) != hipSuccess) { (void)hipGetLastError(); st->score_row = nullptr; return fail(VOX_ERR_HIP, "hipMalloc of the stream's score records failed"); }
+            st->bytes += row_b;
         }
-        sc.dev = d; sc.cap = cap; st->score_row = row; st->bytes += sc.bytes() + row_b;
     }
     HIPCHK(hipStreamSynchronize(s));
     struct { TokenScore* p; int cap; } w{on ? sc.dev : nullptr, on ? sc.cap : 0};
@@ -4827,6 +4857,7 @@ extern "C" int32_t vox_debug_stream_front_tap_fetch(vox_stream* st, float* out_m
 // order) per pass, constant launch arguments within a pass except n_r, one synchronisation per call.  No engine runs here: no kept rows, no re-run, no verification.
 // A member may be fed at its capture rate, and a call may carry 16-bit PCM: every member's passes are feed_plan / feed_pass on its FeedState, the solo stream's planner;
 // the ingest has the member dimension too, one launch per pass (group_stage_pass).
+// ONE call path, as a solo stream's: advance, its 16-bit form and peek are group_run; a peek is its mode between the two directions of the ring keep.
 // ------------------------------------------------------------------------------------------------
 static const int GROUP_MAX = 16, GROUP_DEFAULT_POSITIONS = 2048;
 struct GroupMember {
@@ -4854,7 +4885,7 @@ struct vox_stream_group {
     GroupIngest* d_ingest = nullptr; std::deque<GroupIngest> ingests;      // the pass's ingest descriptors on the device; the ones uploaded by the call in flight, as orders
     int16_t* s16_stage = nullptr;      // host 16-bit feeds: STREAM_SAMPLE_RING samples of device staging per member, allocated at the first one
     int n_scored = 0;                  // members with scores on: a round launches stream_score_kernel only while there is one
-    float* keep = nullptr; size_t keep_floats = 0;      // vox_stream_group_peek: [16 ints: the peeking members, slot by slot][a ring keep area per slot]; grows on demand, counted in `bytes`
+    KeepArea keep;                     // vox_stream_group_peek: [16 ints: the peeking members, slot by slot][a ring keep area per slot]
 };
 // the member leaves its rate: its input ring and its reference to the rate's matrix go (the matrix with its last reference).  The caller has synchronised.
 static void group_member_drop_rate(vox_stream_group* g, int i) {
@@ -4907,7 +4938,7 @@ static void group_release(vox_stream_group* g) {
     for (StreamMember& me : g->h_mem) if (me.tap) (void)hipFree(me.tap);
     for (GroupMember& me : g->mem) if (me.sc.dev) (void)hipFree(me.sc.dev);
     for (size_t i = 0; i < g->mem.size(); i++) group_member_drop_rate(g, (int)i);
-    for (void* p : {(void*)g->keep, (void*)g->d_ingest, (void*)g->s16_stage, (void*)g->kring, (void*)g->vring, (void*)g->dec_k, (void*)g->dec_v, (void*)g->samples, (void*)g->ws, (void*)g->tokens, (void*)g->state, (void*)g->d_mem, (void*)g->d_order,
+    for (void* p : {(void*)g->keep.p, (void*)g->d_ingest, (void*)g->s16_stage, (void*)g->kring, (void*)g->vring, (void*)g->dec_k, (void*)g->dec_v, (void*)g->samples, (void*)g->ws, (void*)g->tokens, (void*)g->state, (void*)g->d_mem, (void*)g->d_order,
                     (void*)g->qkv, (void*)g->att, (void*)g->logits, (void*)g->ssq, (void*)g->xf1, (void*)g->xf2, (void*)g->xf3}) if (p) (void)hipFree(p);
     delete g;
 }
@@ -4976,8 +5007,7 @@ extern "C" int32_t vox_stream_group_info(const vox_stream_group* g, int32_t memb
     const GroupMember& me = g->mem[member]; const int R = g->m->cfg.reshape_factor;
     const uint64_t tap_b = g->h_mem[member].tap ? (uint64_t)g->h_mem[member].tap_max * g->m->cfg.vocab * 4 : 0;
     const uint64_t rate_b = me.rate >= 0 ? (uint64_t)me.feed.in_ring_n * 4 + g->rates[(size_t)me.rate].bytes / (uint64_t)g->rates[(size_t)me.rate].refs : 0;
-    const FeedState& f = me.feed;
-    out[0] = f.n_pushed; out[1] = f.pos; out[2] = f.ids_out; out[3] = (int64_t)R * f.pos; out[4] = std::min<int64_t>((int64_t)R * f.pos, g->g.cap);
+    feed_info(me.feed, R, g->g.cap, out);
     out[5] = (int64_t)(g->bytes / (uint64_t)g->n + tap_b + rate_b + me.sc.bytes());      // the member's share of the group's device state; its own input ring, its share of its rate's matrix, its score records
     out[6] = 0; out[7] = (int64_t)me.steps;                      // no engine step; the member's ticks, each one row of an xf_chain step
     return VOX_OK;
@@ -4996,9 +5026,10 @@ static int32_t group_round(vox_stream_group* g, const StreamWs& w, int n_r) {
     if (g->n_scored > 0) HIPCHK(launch_stream_score(g->logits, c.vocab, g->d_mem, g->d_order, n_r, VOX_PREFIX_TOKENS, s));      // slots of unscored members return at once
     return VOX_OK;
 }
-// vox_stream_group_advance and its 16-bit form, in four units: group_plan_entries (every check, nothing changed), then per pass group_stage_pass (feed_pass for every
-// entry: the copies, and the slots of ONE ingest upload and of at most one stream_group_s16_kernel and one stream_group_resample_kernel launch) and group_run_rounds
-// (ONE order upload, the rounds, pos and steps), then group_drain (the id copies behind the call's ONE synchronisation).  The rounds see 16 kHz rings only.
+// A group's call -- advance, its 16-bit form, peek -- is group_run, in four units: group_plan_entries (every check, nothing changed), then per pass group_stage_pass
+// (feed_pass for every entry: the copies, and the slots of ONE ingest upload and of at most one stream_group_s16_kernel and one stream_group_resample_kernel launch) and
+// group_run_rounds (ONE order upload, the rounds, pos and steps), then group_drain (every entry's SessionOut around the call's ONE synchronisation).  The rounds see
+// 16 kHz rings only.
 struct GroupFeed { int member; const void* p; FeedPlan plan; };      // one entry of the call: its member, its samples (f32 or 16-bit, at the member's rate), its plan
 struct GroupCall { std::vector<GroupFeed> fs; int32_t mem_kind = VOX_MEM_HOST; bool s16 = false, staged = false, any_rate = false, peek = false; };      // staged: host 16-bit samples pass through g->s16_stage; peek: every entry is planned as a finish (vox_stream_group_peek)
 typedef std::vector<std::pair<int, int>> GroupDue;      // (ticks due in this pass, member)
@@ -5008,10 +5039,10 @@ static int32_t group_plan_entries(const vox_stream_group* g, const vox_stream_fe
         const vox_stream_feed& f = feeds[k];
         ARGCHK(f.member >= 0 && f.member < g->n, "entry %d: member %d out of range (0..%d)", k, f.member, g->n - 1);
         ARGCHK(!((seen >> f.member) & 1u), "entry %d: member %d is fed twice in one call", k, f.member); seen |= 1u << f.member;
-        ARGCHK(f.samples || f.n_samples == 0, "entry %d: null samples", k); ARGCHK(f.n_samples <= ((size_t)1 << 36), "entry %d: push of %zu samples", k, f.n_samples);
-        ARGCHK(f.cap >= 0 && (f.out_ids || f.cap == 0), "entry %d: bad output buffer", k); ARGCHK(f.finish == 0 || f.finish == 1, "entry %d: finish must be 0 or 1", k);
+        char who[48]; snprintf(who, sizeof who, "entry %d: ", k);
+        VOXCHK(entry_check(who, f.samples, f.n_samples, f.out_ids, f.cap)); ARGCHK(f.finish == 0 || f.finish == 1, "entry %d: finish must be 0 or 1", k);
         if (call->peek) ARGCHK(f.n_samples == 0 && f.finish == 0, "entry %d: a peek takes no samples and no finish flag (push first, then peek)", k);
-        char who[48]; snprintf(who, sizeof who, "entry %d: member %d", k, f.member);
+        snprintf(who, sizeof who, "entry %d: member %d", k, f.member);
         GroupFeed gf{f.member, f.samples, FeedPlan{}};
         VOXCHK(feed_plan(g->mem[f.member].feed, g->m->cfg.reshape_factor, g->g.left, g->g.max_pos, f.n_samples, call->peek || f.finish != 0, f.cap, who, &gf.plan));
         call->any_rate |= g->mem[f.member].rate >= 0;
@@ -5064,129 +5095,94 @@ static int32_t group_run_rounds(vox_stream_group* g, const StreamWs& w, GroupDue
     for (const std::pair<int, int>& d : due) { g->mem[d.second].feed.pos += d.first; g->mem[d.second].steps += (uint64_t)d.first; }
     return VOX_OK;
 }
-static int32_t group_drain(vox_stream_group* g, vox_stream_feed* feeds, const GroupCall& call) {
+// keep (a peek): the ring rows and the state blocks go back in front of the synchronisation, the records go to peek_scores[k] (null: nowhere)
+static int32_t group_drain(vox_stream_group* g, vox_stream_feed* feeds, const GroupCall& call, const StreamKeepParams* keep, vox_token_score* const* peek_scores) {
     hipStream_t s = g->ctx->stream;
-    for (size_t k = 0; k < call.fs.size(); k++) if (call.fs[k].plan.due > 0)
-        HIPCHK(hipMemcpyAsync(feeds[k].out_ids, g->h_mem[call.fs[k].member].tokens + VOX_PREFIX_TOKENS + g->mem[call.fs[k].member].feed.ids_out, (size_t)call.fs[k].plan.due * 4, hipMemcpyDeviceToHost, s));
-    for (const GroupFeed& e : call.fs) VOXCHK(g->mem[e.member].sc.enqueue(g->mem[e.member].feed.ids_out, e.plan.due, s));      // the records travel with the ids
+    std::vector<SessionOut> outs;
+    for (size_t k = 0; k < call.fs.size(); k++) {
+        GroupMember& me = g->mem[call.fs[k].member];
+        outs.push_back(SessionOut{&me.feed, &me.sc, g->h_mem[call.fs[k].member].tokens, feeds[k].out_ids, call.fs[k].plan.due, call.peek, peek_scores ? peek_scores[k] : nullptr});
+        VOXCHK(outs.back().enqueue(s));
+    }
+    if (keep) HIPCHK(launch_stream_keep(*keep, 1, s));
     HIPCHK(hipStreamSynchronize(s));      // the call's one synchronisation: every fed member's ids and records land
     g->orders.clear(); g->ingests.clear();
     for (size_t k = 0; k < call.fs.size(); k++) {
-        GroupMember& me = g->mem[call.fs[k].member]; FeedState& f = me.feed; const int due = call.fs[k].plan.due;
-        me.sc.settle(f.ids_out, due, feeds[k].out_ids);
-        f.ids_out += due; feeds[k].n_ids = due; if (feeds[k].finish) f.finished = true;
+        outs[k].settle();
+        feeds[k].n_ids = outs[k].due; if (feeds[k].finish) outs[k].feed->finished = true;      // (a peek's entries carry no finish flag)
     }
     return VOX_OK;
 }
-static int32_t group_advance(vox_stream_group* g, vox_stream_feed* feeds, int32_t n_feeds, int32_t mem_kind, bool s16) {
-    ARGCHK(g && (feeds || n_feeds == 0), "null argument"); ARGCHK(n_feeds >= 0 && n_feeds <= g->n, "%d entries for a group of %d members", n_feeds, g->n);
-    ARGCHK(mem_kind == VOX_MEM_HOST || mem_kind == VOX_MEM_DEVICE, "bad mem_kind %d", mem_kind);
-    vox_model* m = g->m;
-    GroupCall call; call.mem_kind = mem_kind; call.s16 = s16; call.staged = s16 && mem_kind == VOX_MEM_HOST;
-    VOXCHK(group_plan_entries(g, feeds, n_feeds, &call));      // every check before anything changes: a refused call can be repeated
-    VOXCHK(ctx_bind(g->ctx));
-    if (call.staged && !g->s16_stage && !call.fs.empty()) {      // STREAM_SAMPLE_RING staged samples per entry and pass
-        const size_t nb = (size_t)g->n * STREAM_SAMPLE_RING * 2;
-        HIPCHK(hipMalloc((void**)&g->s16_stage, nb)); g->bytes += nb;
-    }
-    if (m->pw_pend_rows > 0) VOXCHK(pw_sync(m));
-    VOXCHK(vox_model_set_t_embed(m, g->t_embed.data()));
-    StreamWs w; stream_ws_carve(m, g->n, g->ws, &w);
-    for (GroupFeed& e : call.fs) g->mem[e.member].feed.n_pushed += (int64_t)e.plan.n;
-    // passes: write what fits into every fed member's rings, run the rounds that became due, repeat (a push may be larger than the rings)
-    GroupDue due;
-    for (;;) {
-        bool open = false, idle = false;
-        for (const GroupFeed& e : call.fs) open |= feed_open(g->mem[e.member].feed, e.plan);
-        if (!open) break;
+// the passes: write what fits into every fed member's rings, run the rounds that became due, repeat (a push may be larger than the rings; a peek is one pass)
+static int32_t group_passes(vox_stream_group* g, GroupCall& call) {
+    StreamWs w; stream_ws_carve(g->m, g->n, g->ws, &w); GroupDue due;
+    for (int pass = 0;; pass++) {
+        const GroupFeed* open = nullptr; bool idle = false;
+        for (const GroupFeed& e : call.fs) if (!open && feed_open(g->mem[e.member].feed, e.plan)) open = &e;
+        if (!open) return VOX_OK;
+        if (call.peek && pass > 0) { char who[24]; snprintf(who, sizeof who, "member %d", open->member); return peek_second_pass(who); }
         VOXCHK(group_stage_pass(g, call, &due, &idle));
         if (idle) return fail(VOX_ERR_INVALID, "internal: stream group stalled");
         if (!due.empty()) VOXCHK(group_run_rounds(g, w, due));
     }
-    return group_drain(g, feeds, call);
 }
-extern "C" int32_t vox_stream_group_advance(vox_stream_group* g, vox_stream_feed* feeds, int32_t n_feeds, int32_t mem_kind) {
-    return group_advance(g, feeds, n_feeds, mem_kind, false);
+// behind the checks and the reservations: the save of a peek, the passes, the drain
+static int32_t group_body(vox_stream_group* g, vox_stream_feed* feeds, GroupCall& call, const StreamKeepParams* keep, vox_token_score* const* peek_scores) {
+    if (keep) {
+        g->orders.emplace_back(); std::array<int, GROUP_MAX>& slots = g->orders.back(); slots.fill(0);      // (alive until the synchronisation, as a pass's order)
+        for (size_t k = 0; k < call.fs.size(); k++) slots[k] = call.fs[k].member;
+        HIPCHK(hipMemcpyAsync(g->keep.p, slots.data(), sizeof(int) * GROUP_MAX, hipMemcpyHostToDevice, g->ctx->stream));
+        HIPCHK(launch_stream_keep(*keep, 0, g->ctx->stream));
+    }
+    VOXCHK(group_passes(g, call));
+    return group_drain(g, feeds, call, keep, peek_scores);
 }
-extern "C" int32_t vox_stream_group_advance_s16(vox_stream_group* g, vox_stream_feed* feeds, int32_t n_feeds, int32_t mem_kind) {
-    return group_advance(g, feeds, n_feeds, mem_kind, true);
-}
-// vox_stream_group_peek: advance's units -- plan the entries (each as a finish), stage ONE pass, run its rounds, drain -- between the two directions of the ring keep,
-// the peeking members as its slots; then every peeking member's feed and tick count as they were.  The restore is enqueued in front of the drain's synchronisation: one
-// synchronisation per call, as advance.  The slab does not grow and a member's tap count lives in its state block: nothing else to undo.
-static int32_t group_keep_launch(vox_stream_group* g, int n, int rows, int restore) {
-    const vox_model_cfg& c = g->m->cfg;
-    StreamKeepParams kp{}; kp.mem = g->d_mem; kp.order = reinterpret_cast<const int*>(g->keep); kp.n = n; kp.layers = c.enc_layers; kp.n_heads = c.enc_heads; kp.hd = c.enc_head_dim;
-    kp.cap = g->g.cap; kp.rows = rows; kp.keep = g->keep + GROUP_MAX; kp.slot_stride = stream_keep_floats(c.enc_layers, c.enc_heads, c.enc_head_dim, rows);
-    HIPCHK(launch_stream_keep(kp, restore, g->ctx->stream));
-    return VOX_OK;
-}
-extern "C" int32_t vox_stream_group_peek(vox_stream_group* g, vox_stream_feed* feeds, int32_t n_feeds, vox_token_score* const* scores_or_null) {
+namespace { struct GroupMark { FeedState::Mark feed; uint64_t steps; }; }      // what a peek takes back of a member (the slab does not grow, its tap count lives in its state block)
+static int32_t group_run(vox_stream_group* g, vox_stream_feed* feeds, int32_t n_feeds, GroupCall& call, vox_token_score* const* peek_scores) {
     ARGCHK(g && (feeds || n_feeds == 0), "null argument"); ARGCHK(n_feeds >= 0 && n_feeds <= g->n, "%d entries for a group of %d members", n_feeds, g->n);
-    vox_model* m = g->m; const vox_model_cfg& c = m->cfg; const int R = c.reshape_factor;
-    GroupCall call; call.peek = true;
-    VOXCHK(group_plan_entries(g, feeds, n_feeds, &call));      // finish's refusals for every entry, nothing changed
-    if (call.fs.empty()) return VOX_OK;
-    int T = 0;
-    for (const GroupFeed& e : call.fs) {
-        const int t = peek_max_ticks(g->mem[e.member].feed, R); T = std::max(T, t);
-        ARGCHK(e.plan.due <= t, "internal: member %d: a peek of %d ticks, %d at the most by the pad and the rate plan", e.member, e.plan.due, t);
+    ARGCHK(call.mem_kind == VOX_MEM_HOST || call.mem_kind == VOX_MEM_DEVICE, "bad mem_kind %d", call.mem_kind);
+    vox_model* m = g->m; const vox_model_cfg& c = m->cfg; const int R = c.reshape_factor; hipStream_t s = g->ctx->stream;
+    call.staged = call.s16 && call.mem_kind == VOX_MEM_HOST;
+    VOXCHK(group_plan_entries(g, feeds, n_feeds, &call));      // every check before anything changes: a refused call can be repeated
+    const int n = (int)call.fs.size(); int keep_rows = 0;
+    if (call.peek && n == 0) return VOX_OK;
+    if (call.peek) {      // the bound on every entry's ticks; the keep's rows from the largest
+        int T = 0;
+        for (const GroupFeed& e : call.fs) { char who[24]; snprintf(who, sizeof who, "member %d: ", e.member); int t; VOXCHK(peek_max_ticks(g->mem[e.member].feed, R, e.plan.due, who, &t)); T = std::max(T, t); }
+        keep_rows = std::min(g->g.cap, R * T);
     }
-    VOXCHK(ctx_bind(g->ctx)); hipStream_t s = g->ctx->stream;
-    const int n = (int)call.fs.size(), rows = std::min(g->g.cap, R * T);
-    const size_t need = GROUP_MAX + (size_t)n * stream_keep_floats(c.enc_layers, c.enc_heads, c.enc_head_dim, rows);
-    if (g->keep_floats < need) {      // the save area: a slot per peeking member, allocated at the first peek that needs it
-        HIPCHK(hipStreamSynchronize(s));
-        float* q = nullptr;
-        if (hipMalloc((void**)&q, need * 4) != hipSuccess) { (void)hipGetLastError(); return fail(VOX_ERR_HIP, "hipMalloc of the group's %zu-byte peek save area failed", need * 4); }
-        if (g->keep) (void)hipFree(g->keep);
-        g->bytes += (need - g->keep_floats) * 4; g->keep = q; g->keep_floats = need;
+    VOXCHK(ctx_bind(g->ctx));
+    if (call.staged && !g->s16_stage && n > 0) {      // STREAM_SAMPLE_RING staged samples per entry and pass
+        const size_t nb = (size_t)g->n * STREAM_SAMPLE_RING * 2;
+        HIPCHK(hipMalloc((void**)&g->s16_stage, nb)); g->bytes += nb;
     }
+    if (call.peek) VOXCHK(keep_reserve(g->keep, GROUP_MAX + (size_t)n * stream_keep_floats(c.enc_layers, c.enc_heads, c.enc_head_dim, keep_rows), &g->bytes, s, "group"));
     if (m->pw_pend_rows > 0) VOXCHK(pw_sync(m));
     VOXCHK(vox_model_set_t_embed(m, g->t_embed.data()));
-    StreamWs w; stream_ws_carve(m, g->n, g->ws, &w);
-    struct Was { int64_t n_written; int pos; uint64_t steps; };
-    std::vector<Was> was; for (const GroupFeed& e : call.fs) was.push_back(Was{g->mem[e.member].feed.n_written, g->mem[e.member].feed.pos, g->mem[e.member].steps});
-    bool restored = false;
-    auto body = [&]() -> int32_t {
-        g->orders.emplace_back(); std::array<int, GROUP_MAX>& slots = g->orders.back(); slots.fill(0);      // (alive until the synchronisation, as a pass's order)
-        for (int k = 0; k < n; k++) slots[(size_t)k] = call.fs[(size_t)k].member;
-        HIPCHK(hipMemcpyAsync(g->keep, slots.data(), sizeof(int) * GROUP_MAX, hipMemcpyHostToDevice, s));
-        VOXCHK(group_keep_launch(g, n, rows, 0));
-        GroupDue due; bool idle = false;
-        VOXCHK(group_stage_pass(g, call, &due, &idle));
-        if (!due.empty()) VOXCHK(group_run_rounds(g, w, due));
-        // ONE pass: a second would size its room from the advanced positions and could overwrite samples the members still read once they are taken back
-        for (const GroupFeed& e : call.fs) if (feed_open(g->mem[e.member].feed, e.plan)) return fail(VOX_ERR_INVALID, "internal: member %d: a peek needs a second pass", e.member);
-        for (int k = 0; k < n; k++) {
-            const GroupFeed& e = call.fs[(size_t)k]; const GroupMember& me = g->mem[e.member];
-            if (e.plan.due > 0) HIPCHK(hipMemcpyAsync(feeds[k].out_ids, g->h_mem[e.member].tokens + VOX_PREFIX_TOKENS + me.feed.ids_out, (size_t)e.plan.due * 4, hipMemcpyDeviceToHost, s));
-            if (scores_or_null) VOXCHK(peek_scores_enqueue(me.sc, me.feed.ids_out, e.plan.due, PeekOut{scores_or_null[k]}, s));
-        }
-        VOXCHK(group_keep_launch(g, n, rows, 1)); restored = true;
-        HIPCHK(hipStreamSynchronize(s));      // the call's one synchronisation
-        return VOX_OK;
-    };
-    int32_t r = body();
-    if (r != VOX_OK && !restored) (void)group_keep_launch(g, n, rows, 1);      // a failed tail is taken back as well
-    if (r != VOX_OK) (void)hipStreamSynchronize(s);
-    g->orders.clear(); g->ingests.clear();
-    for (int k = 0; k < n; k++) {
-        const GroupFeed& e = call.fs[(size_t)k]; GroupMember& me = g->mem[e.member];
-        me.feed.n_written = was[(size_t)k].n_written; me.feed.pos = was[(size_t)k].pos; me.feed.finished = false; me.steps = was[(size_t)k].steps;
-        if (r == VOX_OK) { feeds[k].n_ids = e.plan.due; if (scores_or_null) peek_scores_settle(me.sc, e.plan.due, feeds[k].out_ids, PeekOut{scores_or_null[k]}); }
-    }
+    for (GroupFeed& e : call.fs) g->mem[e.member].feed.n_pushed += (int64_t)e.plan.n;
+    if (!call.peek) return group_body(g, feeds, call, nullptr, nullptr);
+    // a peek: the peeking members are the ring keep's slots, their numbers the first 16 ints of the save area
+    const StreamKeepParams keep = ring_keep(c, g->d_mem, reinterpret_cast<const int*>(g->keep.p), n, keep_rows, g->g.cap, g->keep.p + GROUP_MAX);
+    std::vector<GroupMark> was; for (const GroupFeed& e : call.fs) was.push_back(GroupMark{g->mem[e.member].feed.mark(), g->mem[e.member].steps});
+    const int32_t r = group_body(g, feeds, call, &keep, peek_scores);
+    if (r != VOX_OK) { (void)launch_stream_keep(keep, 1, s); (void)hipStreamSynchronize(s); g->orders.clear(); g->ingests.clear(); }      // a failed tail is taken back as well
+    for (int k = 0; k < n; k++) { GroupMember& me = g->mem[call.fs[(size_t)k].member]; me.feed.rewind(was[(size_t)k].feed); me.steps = was[(size_t)k].steps; }
     return r;
+}
+extern "C" int32_t vox_stream_group_advance(vox_stream_group* g, vox_stream_feed* feeds, int32_t n_feeds, int32_t mem_kind) {
+    GroupCall call; call.mem_kind = mem_kind; return group_run(g, feeds, n_feeds, call, nullptr);
+}
+extern "C" int32_t vox_stream_group_advance_s16(vox_stream_group* g, vox_stream_feed* feeds, int32_t n_feeds, int32_t mem_kind) {
+    GroupCall call; call.mem_kind = mem_kind; call.s16 = true; return group_run(g, feeds, n_feeds, call, nullptr);
+}
+extern "C" int32_t vox_stream_group_peek(vox_stream_group* g, vox_stream_feed* feeds, int32_t n_feeds, vox_token_score* const* scores_or_null) {
+    GroupCall call; call.peek = true; return group_run(g, feeds, n_feeds, call, scores_or_null);
 }
 extern "C" int32_t vox_stream_group_set_scores(vox_stream_group* g, int32_t member, int32_t on) {
     ARGCHK(g, "null group"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1); ARGCHK(on == 0 || on == 1, "on must be 0 or 1");
     VOXCHK(ctx_bind(g->ctx));
     ScoreState& sc = g->mem[member].sc;
-    if (on && !sc.dev) {      // the group's logits rows are there already: a member needs its records alone
-        const int cap = g->g.max_pos + 2;
-        if (hipMalloc((void**)&sc.dev, (size_t)cap * sizeof(TokenScore)) != hipSuccess) { (void)hipGetLastError(); sc.dev = nullptr; return fail(VOX_ERR_HIP, "hipMalloc of member %d's score records failed", member); }
-        sc.cap = cap;
-    }
+    if (on) { char whose[24]; snprintf(whose, sizeof whose, "member %d's", member); VOXCHK(sc.alloc(g->g.max_pos, whose)); }      // the group's logits rows are there already: a member needs its records alone
     HIPCHK(hipStreamSynchronize(g->ctx->stream));
     g->h_mem[member].scores = on ? sc.dev : nullptr; g->h_mem[member].scores_cap = on ? sc.cap : 0;
     VOXCHK(group_upload_members(g));
@@ -5238,9 +5234,9 @@ extern "C" int32_t vox_debug_stream_feed_passes(uint32_t sample_rate, const size
         char who[32]; snprintf(who, sizeof who, "call %d: the session", c);
         FeedPlan plan; VOXCHK(feed_plan(f, R, left, INT32_MAX, n_samples[c], finish[c] != 0, INT32_MAX, who, &plan));
         f.n_pushed += (int64_t)plan.n;
-        const int64_t was_written = f.n_written; const int was_pos = f.pos;
+        const FeedState::Mark was = f.mark();
         for (int pass = 0; feed_open(f, plan); pass++) {
-            if (peek && pass > 0) return fail(VOX_ERR_INVALID, "internal: call %d: a peek needs a second pass", c);
+            if (peek && pass > 0) { snprintf(who, sizeof who, "call %d", c); return peek_second_pass(who); }
             const FeedPass q = feed_pass(f, plan, R, left, pass_cap ? pass_cap : SIZE_MAX);
             if (q.idle()) return fail(VOX_ERR_INVALID, "internal: call %d stalled at position %d of %d", c, f.pos, plan.target);
             ARGCHK(k < max_rows, "more than %d passes: the output buffer is too small", max_rows);
@@ -5248,7 +5244,7 @@ extern "C" int32_t vox_debug_stream_feed_passes(uint32_t sample_rate, const size
             r[0] = c; r[1] = (int64_t)q.n_in; r[2] = (int64_t)q.n16; r[3] = (int64_t)q.pad; r[4] = q.ticks;
             f.pos += q.ticks;
         }
-        if (peek) { f.n_written = was_written; f.pos = was_pos; continue; }      // the session as it was: the drivers' rollback of the feed
+        if (peek) { f.rewind(was); continue; }      // the session as it was: the drivers' rollback of the feed
         f.ids_out += plan.due; f.finished = plan.finish;
     }
     *n_rows = k;
