@@ -355,6 +355,24 @@ typedef struct { float logprob; float margin; int32_t runner_up; int32_t id; } v
 /* rows of logits -> one record per row, the piecewise caller's companion to vox_argmax_rows (same mem_kind for the logits).  ids_or_null (host, M entries, each in [0, V)):
  * the id to score; null: the row's argmax as vox_argmax_rows gives it.  out: host, M records.  Computed on the device either way (host logits are uploaded).  Synchronises. */
 int32_t vox_score_rows(vox_ctx* ctx, const float* logits_MxV, int32_t M, int32_t V, const int32_t* ids_or_null, vox_token_score* out, int32_t mem_kind);
+/* ---- alternatives: what else the model weighed at a step, and how spread the step's distribution was (no reference counterpart).  For a logits row L[V] (f32) and
+ * k in 1 .. VOX_MAX_ALTERNATIVES:
+ *   alt[0].id = the row's argmax by the rule of every decode form (the largest wins, the lowest index wins a tie, a NaN or -inf never wins); alt[j].id = the argmax by
+ *               the same rule over the columns not yet taken;
+ *   n         = min(k, the number of columns that can win); the entries j >= n are {-1, NaN} (V < k, rows of -inf or NaN: n < k, possibly 0);
+ *   alt[j].logprob = (L[id_j] - m) - logf(S), with vox_token_score's m and S = sum_v exp(L[v] - m), summed in the same order: when the scored id is the row's argmax,
+ *               alt[0].logprob has the bits of the score record's logprob, and alt[1].id is its runner_up;
+ *   entropy   = max(0, logf(S) - T / S), T = sum_v exp(L[v] - m) (L[v] - m) over the columns above -inf, in f32, summed in S's order: the entropy of the row's softmax
+ *               in nats.
+ * A row that holds a NaN, or whose maximum is not finite, has entropy = NaN and every logprob = NaN; ids and n follow the rule all the same.  The record is a function
+ * of the row's values, V and k alone (never of the row's address or alignment, its slot, the launch or the rows next to it), and the list for k is bit for bit the
+ * first k entries of the list for a larger k: what a live session claims bit for bit about its ids holds for these records too. */
+#define VOX_MAX_ALTERNATIVES 8
+typedef struct { int32_t id; float logprob; } vox_alt;
+typedef struct { float entropy; int32_t n; vox_alt alt[VOX_MAX_ALTERNATIVES]; } vox_token_alts;   /* 72 bytes */
+/* rows of logits -> one record per row, vox_score_rows' companion (same mem_kind for the logits).  k: 1 .. VOX_MAX_ALTERNATIVES.  out: host, M records.  Computed on the
+ * device either way (host logits are uploaded).  Synchronises. */
+int32_t vox_alternatives_rows(vox_ctx* ctx, const float* logits_MxV, int32_t M, int32_t V, int32_t k, vox_token_alts* out, int32_t mem_kind);
 /* lm_head + argmax + read-back in one call: M token ids come back instead of M x 512 KB of logits; synchronises the stream */
 int32_t vox_lm_head_argmax(vox_model* m, const float* hidden_MxD, int32_t M, int32_t* ids_host, int32_t mem_kind);
 /* Q4VoxtralModel::generate_step_with_cache, gguf/model.rs:857-867 (text tokens only: embed -> decoder against the cache -> final norm -> lm_head) in one call;
@@ -533,6 +551,19 @@ int32_t vox_stream_scores(const vox_stream* s, int32_t first_id, int32_t n, vox_
 int32_t vox_stream_peek(vox_stream* s, int32_t* out_ids, int32_t cap, int32_t* n_ids, vox_token_score* scores_or_null);
 /* host only: the ids a peek returns after n_samples pushed at sample_rate Hz with ids_out ids handed out (more than the utterance has: VOX_ERR_INVALID) */
 int32_t vox_stream_peek_ids(size_t n_samples, uint32_t sample_rate, int32_t ids_out, int32_t* n);
+/* ALTERNATIVES.  With k > 0, every id the stream hands out also comes with a vox_token_alts (above) of its decode step's logits row: one more launch per tick, behind the
+ * score launch if there is one, and one more copy in front of the call's one synchronisation; the ids do not change, and a stream that never asks allocates and launches
+ * nothing.  vox_stream_set_alternatives: k = 0 (off, the default) .. VOX_MAX_ALTERNATIVES, takes effect with the next push / finish / peek, survives vox_stream_reset; the
+ * first k > 0 allocates the records (72 bytes per position the stream was created for) and, unless scores did, one logits row, counted in vox_stream_info [5] from then on.
+ * vox_stream_alternatives: the records of ids [first_id, first_id + n) of the current utterance from a host array the stream keeps (no device is touched); the range must
+ * lie within the ids handed out so far, else VOX_ERR_INVALID and nothing is written.  An id handed out while alternatives were off has entropy = NaN, n = 0 and every entry
+ * {-1, NaN}; a record made at k has n <= k whatever k is now.  vox_stream_reset starts the list over.
+ * vox_stream_peeked_alternatives: the records of the ids the LAST vox_stream_peek returned (*n of them; cap < that: VOX_ERR_INVALID), copied in front of that peek's one
+ * synchronisation into a host array of the stream's; they equal bit for bit what finish then appends for the same ids, never enter the stream's own list, and are valid
+ * until the next push / finish / peek / reset -- after that *n = 0. */
+int32_t vox_stream_set_alternatives(vox_stream* s, int32_t k);
+int32_t vox_stream_alternatives(const vox_stream* s, int32_t first_id, int32_t n, vox_token_alts* out);
+int32_t vox_stream_peeked_alternatives(const vox_stream* s, vox_token_alts* out, int32_t cap, int32_t* n);
 /* test tap, modelled on vox_debug_batch_tap_*: from now on keep the f32 logits row behind each id handed out (up to max_rows); fetch copies them to the host
  * ([min(rows, max_rows)][vocab]; *rows = rows produced since arm) and ends the tap */
 int32_t vox_debug_stream_tap_arm(vox_stream* s, int32_t max_rows);
@@ -612,6 +643,11 @@ int32_t vox_stream_group_scores(const vox_stream_group* g, int32_t member, int32
  * flag in an entry), before anything changes.  scores_or_null: one array per entry (entries whose pointer is null get none), as vox_stream_peek's.  The save area
  * holds a slot per entry of the largest peek so far and is counted in the group's device bytes. */
 int32_t vox_stream_group_peek(vox_stream_group* g, vox_stream_feed* feeds, int32_t n_feeds, vox_token_score* const* scores_or_null);
+/* vox_stream_set_alternatives / vox_stream_alternatives / vox_stream_peeked_alternatives for one member (ALTERNATIVES above): k survives the member's resets; a round
+ * launches the alternatives kernel once for all its slots, and only while some member has k > 0; the member's records are counted in vox_stream_group_info [5] */
+int32_t vox_stream_group_set_alternatives(vox_stream_group* g, int32_t member, int32_t k);
+int32_t vox_stream_group_alternatives(const vox_stream_group* g, int32_t member, int32_t first_id, int32_t n, vox_token_alts* out);
+int32_t vox_stream_group_peeked_alternatives(const vox_stream_group* g, int32_t member, vox_token_alts* out, int32_t cap, int32_t* n);
 /* vox_debug_stream_tap_* for one member (the rows are copied by the tick's last kernel; a reset of the member starts the count again) */
 int32_t vox_debug_stream_group_tap_arm(vox_stream_group* g, int32_t member, int32_t max_rows);
 int32_t vox_debug_stream_group_tap_fetch(vox_stream_group* g, int32_t member, float* out, int32_t* rows);

@@ -53,6 +53,9 @@ def parse_header():
             mm = re.match(r"((?:const\s+)?[A-Za-z_][A-Za-z0-9_]*\s*\**)\s*(.*)", decl)      # pointer fields: `const float* samples`
             ty, names = mm.group(1), mm.group(2)
             for n in names.split(","):
+                arr = re.match(r"([A-Za-z_][A-Za-z0-9_]*)\s*\[([A-Za-z0-9_]+)\]$", n.strip())      # an array field: `vox_alt alt[VOX_MAX_ALTERNATIVES]` -> `[vox_alt; VOX_MAX_ALTERNATIVES as usize]`
+                if arr:
+                    fields.append((arr.group(1), f"[{rust_type(ty)}; {arr.group(2)}{'' if arr.group(2).isdigit() else ' as usize'}]")); continue
                 fields.append((n.strip(), rust_type(ty)))
         structs.append((m.group(2), fields))
     funcs = []

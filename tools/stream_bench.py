@@ -5,6 +5,7 @@
     python tools/stream_bench.py --group 1,2,4,8,16 [--out profiles/stream_group_tick.txt]
     python tools/stream_bench.py --group 1,4,16 --rate 48000 --s16 [--out profiles/stream_group_rate_tick.txt]
     python tools/stream_bench.py --scores [--group 1,4,16] [--out profiles/stream_scores_tick.txt]
+    python tools/stream_bench.py --alternatives 8 [--group 1,4,16] [--out profiles/stream_alternatives_tick.txt]
     python tools/stream_bench.py --peek [--out profiles/stream_peek.txt]
 
  * stream: HIP events on the context's stream around ONE push of `ticks` x 2560 samples (a large push is a loop of identical ticks), at encoder positions past the
@@ -24,6 +25,8 @@
  * --scores: what scores cost (vox_stream_set_scores: one more launch per tick, one logits row written and read per session).  A second solo stream -- with --group
    also a second group -- runs with scores on, warmed like the first and timed the same way in the same loop: pass i of the scored session follows pass i of the
    unscored one and covers the same positions.  The unscored figures are the tool's usual ones (comparable with a run without the flag); the difference is reported.
+ * --alternatives K: what alternatives at k = K cost (vox_stream_set_alternatives: one more launch per tick, one logits row written and read twice per session),
+   measured as --scores measures scores: twins with alternatives on, pass i behind pass i of the plain session.  Combines with --scores (a third twin).
  * --peek: what a peek costs (vox_stream_peek: finish's T ticks between a ring save and a ring restore, taken back).  One stream past the 750-row window; per pass,
    HIP events around one peek and, right behind it, around one push of the same T ticks -- the same session, the same positions (the peek left it where it was), the
    same run.  Median of `passes` passes of each, their ratio, and the launches of both from the library's counters plus the fixed launches of a tick.
@@ -74,6 +77,21 @@ def launch_counts(pkg):
     return sum(a), sum(g)
 
 
+def twin_kinds(a):
+    """--scores / --alternatives K: (what is on, how a solo stream turns it on, how a group member does)."""
+    kinds = []
+    if a.scores:
+        kinds.append(("scores on", lambda st: st.set_scores(True), lambda g, k: g.set_scores(k, True)))
+    if a.alternatives:
+        kinds.append((f"alternatives on (k = {a.alternatives})", lambda st: st.set_alternatives(a.alternatives), lambda g, k: g.set_alternatives(k, a.alternatives)))
+    return kinds
+
+
+def twin_recorded(what, st):
+    """Every id of the timed twin got its record."""
+    return not np.isnan(st.scores()["logprob"]).any() if what.startswith("scores") else not np.isnan(st.alternatives()["entropy"]).any()
+
+
 def bench_groups(pkg, ctx, m, t, tm, a, widths, lines):
     """--group: per width N, `passes` x (one solo push of `ticks` ticks, one group advance of `ticks` ticks per member), alternating."""
     c = m.config; S = pkg.synth; warm = 200
@@ -95,13 +113,14 @@ def bench_groups(pkg, ctx, m, t, tm, a, widths, lines):
         st = m.create_stream(t, gain=gain); g = m.create_stream_group(t, N, gains=[gain] * N)
         pos = 40 + 2560 * warm
         st.push(x[:pos]); g.advance({k: x[:pos] for k in range(N)})
-        if a.scores:      # the scored twins
+        twins = []      # (what is on, its solo stream, its group, the solo passes, the group passes): warmed like the plain pair
+        for what, on_solo, on_member in twin_kinds(a):
             st_s = m.create_stream(t, gain=gain); g_s = m.create_stream_group(t, N, gains=[gain] * N)
-            st_s.set_scores(True); st_s.push(x[:pos])
+            on_solo(st_s); st_s.push(x[:pos])
             for k in range(N):
-                g_s.set_scores(k, True)
+                on_member(g_s, k)
             g_s.advance({k: x[:pos] for k in range(N)})
-            solo_s, grp_s = [], []
+            twins.append((what, st_s, g_s, [], []))
         if sr:
             g2, g3 = (m.create_stream_group(t, N, gains=[gr] * N, sample_rates=[sr] * N) for _ in range(2)); rpos = per * (warm + 1)      # fed from host / device memory
             for gg in (g2, g3):
@@ -114,8 +133,9 @@ def bench_groups(pkg, ctx, m, t, tm, a, widths, lines):
             feeds = {k: seg for k in range(N)}
             grp.append(tm.ms(lambda: g.advance(feeds)) / a.ticks); k2 = launch_counts(pkg)
             ks += sum(k1) - sum(k0); kg += sum(k2) - sum(k1)
-            if a.scores:
-                solo_s.append(tm.ms(lambda: st_s.push(seg)) / a.ticks); grp_s.append(tm.ms(lambda: g_s.advance(feeds)) / a.ticks)
+            for what, st_s, g_s, solo_s, grp_s in twins:
+                k3 = launch_counts(pkg); solo_s.append(tm.ms(lambda: st_s.push(seg)) / a.ticks); k4 = launch_counts(pkg); grp_s.append(tm.ms(lambda: g_s.advance(feeds)) / a.ticks); k5 = launch_counts(pkg)
+                assert (sum(k4) - sum(k3), sum(k5) - sum(k4)) == (sum(k1) - sum(k0), sum(k2) - sum(k1))      # the counted launches are the plain pair's (the record kernels are uncounted: one each)
             if sr:      # the rate groups: `ticks` ticks' worth of the same input from host memory and from device memory; per tick actually run
                 n = per * a.ticks
                 for gg, out, device in ((g2, rate, False), (g3, rate_dev, True)):
@@ -133,8 +153,8 @@ def bench_groups(pkg, ctx, m, t, tm, a, widths, lines):
                 rpos += n
         assert g.info(N - 1)["positions"] == st.info()["positions"] == 38 + warm + a.ticks * a.passes
         st.close(); g.close()
-        if a.scores:
-            assert g_s.info(N - 1)["positions"] == st_s.info()["positions"] == 38 + warm + a.ticks * a.passes and not np.isnan(st_s.scores()["logprob"]).any()
+        for what, st_s, g_s, _, _ in twins:
+            assert g_s.info(N - 1)["positions"] == st_s.info()["positions"] == 38 + warm + a.ticks * a.passes and twin_recorded(what, st_s)
             st_s.close(); g_s.close()
         if sr:
             g2.close(); g3.close(); rate_rows.append((N, statistics.median(rate), statistics.median(rate_dev), statistics.median(grp), rate, rate_dev))
@@ -143,10 +163,10 @@ def bench_groups(pkg, ctx, m, t, tm, a, widths, lines):
         rows.append((N, rnd, tick))
         lines += [f"group of {N:2d}: round median {rnd:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in grp) + f"   solo tick median {tick:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in solo),
                   f"  round / ({N} x solo tick) = {rnd / (N * tick):.3f}   per member and tick {rnd / N:.3f} ms   launches per round {lg:.0f} (solo tick {ls:.0f})"]
-        if a.scores:
-            ts, rs = statistics.median(solo_s), statistics.median(grp_s)
-            lines += [f"  scores on, group of {N:2d}: round median {rs:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in grp_s) + f"   difference to scores off {rs - rnd:+.3f} ms ({100 * (rs - rnd) / rnd:+.2f} %), per pass " + " ".join(f"{v - w:+.3f}" for v, w in zip(grp_s, grp)),
-                      f"  scores on, solo tick: median {ts:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in solo_s) + f"   difference to scores off {ts - tick:+.3f} ms ({100 * (ts - tick) / tick:+.2f} %), per pass " + " ".join(f"{v - w:+.3f}" for v, w in zip(solo_s, solo))]
+        for what, _, _, solo_s, grp_s in twins:
+            ts, rs = statistics.median(solo_s), statistics.median(grp_s); off = what.split()[0] + " off"
+            lines += [f"  {what}, group of {N:2d}: round median {rs:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in grp_s) + f"   difference to {off} {rs - rnd:+.3f} ms ({100 * (rs - rnd) / rnd:+.2f} %), per pass " + " ".join(f"{v - w:+.3f}" for v, w in zip(grp_s, grp)),
+                      f"  {what}, solo tick: median {ts:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in solo_s) + f"   difference to {off} {ts - tick:+.3f} ms ({100 * (ts - tick) / tick:+.2f} %), per pass " + " ".join(f"{v - w:+.3f}" for v, w in zip(solo_s, solo))]
     lines.append("derived: members one GPU serves in real time at each width = N x 160 ms / round: " + ", ".join(f"{N}: {N * 160.0 / r:.0f}" for N, r, _ in rows))
     if sr:
         what = f"{sr} Hz {'s16' if a.s16 else 'f32'}"
@@ -190,9 +210,12 @@ def main():
     ap.add_argument("--rate", type=int, default=0, metavar="SR", help="with --group: also time a group whose members are all fed at SR Hz, next to the 16 kHz f32 round")
     ap.add_argument("--s16", action="store_true", help="with --rate: feed that group 16-bit PCM")
     ap.add_argument("--scores", action="store_true", help="also time a stream (with --group: and a group) with scores on, pass by pass next to the unscored one")
+    ap.add_argument("--alternatives", type=int, default=0, metavar="K", help="also time a stream (with --group: and a group) with alternatives on at k = K (1..8), as --scores does")
     ap.add_argument("--peek", action="store_true", help="time vox_stream_peek next to the same number of ordinary ticks of the same session (nothing else is measured)")
     a = ap.parse_args()
-    if a.peek and (a.group or a.scores):
+    if not 0 <= a.alternatives <= 8:
+        ap.error("--alternatives takes 1..8")
+    if a.peek and (a.group or a.scores or a.alternatives):
         ap.error("--peek is a mode of its own")
     if (a.rate or a.s16) and not a.group or (a.s16 and not a.rate):
         ap.error("--rate applies with --group, --s16 with --rate")
@@ -241,15 +264,17 @@ def main():
     # ---- the stream
     st = m.create_stream(t, gain=gain)
     pos = 40 + 2560 * warm; st.push(x[:pos])
-    if a.scores:
-        st_s = m.create_stream(t, gain=gain); st_s.set_scores(True); st_s.push(x[:pos])
+    twins = []
+    for what, on_solo, _ in twin_kinds(a):
+        st_s = m.create_stream(t, gain=gain); on_solo(st_s); st_s.push(x[:pos]); twins.append((what, st_s, []))
     e0 = st.info()
-    per = []; per_s = []; counted = 0
+    per = []; counted = 0
     for _ in range(a.passes):
         seg = x[pos:pos + 2560 * a.ticks]; pos += 2560 * a.ticks
         k0 = launch_counts(pkg); per.append(tm.ms(lambda: st.push(seg)) / a.ticks); k1 = launch_counts(pkg); counted += sum(k1) - sum(k0)
-        if a.scores:
-            per_s.append(tm.ms(lambda: st_s.push(seg)) / a.ticks)
+        for what, st_s, per_s in twins:
+            k2 = launch_counts(pkg); per_s.append(tm.ms(lambda: st_s.push(seg)) / a.ticks)
+            assert sum(launch_counts(pkg)) - sum(k2) == sum(k1) - sum(k0)      # the counted launches are the plain stream's (the record kernel is uncounted: one per tick)
     e1 = st.info()
     ticks = a.ticks * a.passes
     eng = (e1["engine_steps"] - e0["engine_steps"]) / ticks
@@ -267,11 +292,11 @@ def main():
               f"  split front end / layers / adapter / decode step: not measured (events sit around whole pushes); graph replay: not built, the tick is launched eagerly",
               f"  wall time of a 160 ms host-memory push until its id is back: median {statistics.median(wall):.3f} ms  min {min(wall):.3f}  max {max(wall):.3f}  (30 pushes)"]
 
-    if a.scores:
-        assert not np.isnan(st_s.scores()["logprob"]).any(); st_s.close()
+    for what, st_s, per_s in twins:
+        assert twin_recorded(what, st_s); st_s.close()
         ts = statistics.median(per_s)
-        lines.append(f"stream tick with scores on (a second stream, pass i behind pass i above): median {ts:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in per_s) +
-                     f"   difference to scores off {ts - tick:+.3f} ms ({100 * (ts - tick) / tick:+.2f} %), per pass " + " ".join(f"{v - w:+.3f}" for v, w in zip(per_s, per)))
+        lines.append(f"stream tick with {what} (a second stream, pass i behind pass i above): median {ts:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in per_s) +
+                     f"   difference to {what.split()[0]} off {ts - tick:+.3f} ms ({100 * (ts - tick) / tick:+.2f} %), per pass " + " ".join(f"{v - w:+.3f}" for v, w in zip(per_s, per)))
 
     # ---- the baseline: 16-frame chunks through the cached encoder + one piecewise decoder step per chunk
     mel = np.ascontiguousarray(pkg.MelSpectrogram.voxtral(ctx).compute_log(pkg.pad_audio(pkg.peak_normalize(x))).T)      # [128][T]

@@ -39,6 +39,16 @@ class TokenScore(C.Structure):
     _fields_ = [("logprob", C.c_float), ("margin", C.c_float), ("runner_up", C.c_int32), ("id", C.c_int32)]
 
 
+class Alt(C.Structure):
+    """vox_alt: one alternative of a step, its id and log-probability"""
+    _fields_ = [("id", C.c_int32), ("logprob", C.c_float)]
+
+
+class TokenAlts(C.Structure):
+    """vox_token_alts: the k best ids of a step's logits row and the row's entropy"""
+    _fields_ = [("entropy", C.c_float), ("n", C.c_int32), ("alt", Alt * 8)]
+
+
 class ModelCfg(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("enc_layers", "enc_dim", "enc_heads", "enc_head_dim", "enc_ffn", "enc_window",
                                          "dec_layers", "dec_dim", "dec_heads", "dec_kv_heads", "dec_head_dim", "dec_ffn",
@@ -194,6 +204,13 @@ SIGNATURES = {
     "vox_stream_scores": (i32, [vp, i32, i32, vp]),
     "vox_stream_group_set_scores": (i32, [vp, i32, i32]),
     "vox_stream_group_scores": (i32, [vp, i32, i32, i32, vp]),
+    "vox_alternatives_rows": (i32, [vp, vp, i32, i32, i32, vp, i32]),
+    "vox_stream_set_alternatives": (i32, [vp, i32]),
+    "vox_stream_alternatives": (i32, [vp, i32, i32, vp]),
+    "vox_stream_peeked_alternatives": (i32, [vp, vp, i32, P(i32)]),
+    "vox_stream_group_set_alternatives": (i32, [vp, i32, i32]),
+    "vox_stream_group_alternatives": (i32, [vp, i32, i32, i32, vp]),
+    "vox_stream_group_peeked_alternatives": (i32, [vp, i32, vp, i32, P(i32)]),
     "vox_stream_peek": (i32, [vp, vp, i32, P(i32), vp]),
     "vox_stream_peek_ids": (i32, [sz, u32, i32, P(i32)]),
     "vox_debug_stream_tap_peeked": (i32, [vp, vp, i32]),

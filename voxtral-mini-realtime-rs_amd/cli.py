@@ -71,15 +71,16 @@ def transcribe_one(pkg, path, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed
     return " ".join(texts)
 
 
-def write_words(out, pkg, path, ids, scores, tokenizer, rate):
-    """--live-words: one JSON line per word of a file that has ended (pkg.words: text, first_id, last_id, due_s, logprob, min_margin) + the file's path."""
+def write_words(out, pkg, path, ids, scores, tokenizer, rate, alternatives=None):
+    """--live-words: one JSON line per word of a file that has ended (pkg.words: text, first_id, last_id, due_s, logprob, min_margin) + the file's path; with
+    --live-alternatives also the word's entropy and the alternatives of its weakest id."""
     import json
-    for w in pkg.words(ids, scores, tokenizer, sample_rate=rate):
+    for w in pkg.words(ids, scores, tokenizer, sample_rate=rate, alternatives=alternatives):
         out.write(json.dumps(dict(w, file=path), ensure_ascii=False) + "\n")
     out.flush()
 
 
-def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_rate=False, words_out=None, peek=False):
+def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_rate=False, words_out=None, peek=False, alts_k=0):
     """--live: the file through a live session (vox_stream) in pieces of `chunk_ms` milliseconds, the text so far on stderr whenever ids arrive.  The gain is the
     file's peak scale 0.95 / max|x| (bin/transcribe.rs:207; a file is known in advance -- a microphone caller passes its own), the whole file is one utterance (no
     --max-mel-frames chunks: the session's state is bounded by its ring), so the line equals the un-chunked path's.
@@ -87,6 +88,7 @@ def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_
     device would deliver; it resamples as the samples arrive.  The gain stays the peak scale of the RESAMPLED file (computed here only because the file is known in
     advance and the line is to be compared), so the line equals the one without the flag.
     words_out (--live-words): the session runs with scores on and the file's words go there when it ends; the ids, hence the line, are the same.
+    alts_k (--live-alternatives): the session also keeps every id's alts_k best alternatives and the step's entropy, for the words file.
     peek (--live-peek): after every push a "  ~[" line on stderr with the text so far plus the tentative tail -- what the line would be if the file ended here
     (vox_stream_peek: finish's ticks, taken back); the session, hence everything else, is as without the flag."""
     x, sr = load_wav(path)
@@ -107,6 +109,8 @@ def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_
     try:
         if words_out is not None:
             stream.set_scores(True)
+            if alts_k:
+                stream.set_alternatives(alts_k)
         ids = []
         text = lambda tail=(): tokenizer.decode([t for t in ids + [int(v) for v in tail] if t >= 1000]).strip()   # :309-318
         for a in range(0, x.size, step):
@@ -117,17 +121,17 @@ def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_
                 log(f"  ~[{min(a + step, x.size) / rate:8.2f} s] {text(stream.peek())}")
         ids.extend(int(t) for t in stream.finish())
         if words_out is not None:
-            write_words(words_out, pkg, path, ids, stream.scores(), tokenizer, rate)
+            write_words(words_out, pkg, path, ids, stream.scores(), tokenizer, rate, stream.alternatives() if alts_k else None)
         return text()
     finally:
         stream.close()
 
 
-def transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, chunk_ms, n_members, words_out=None, peek=False):
+def transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, chunk_ms, n_members, words_out=None, peek=False, alts_k=0):
     """--live-group N: the files N at a time through one stream group (vox_stream_group) in pieces of `chunk_ms` milliseconds: every call feeds each busy member its
     next piece, a file that ends (its member fed with finish) frees the member for the next file in input order.  Gains and lines as transcribe_live's (16 kHz: other
     rates are resampled first).  -> {file index: text}; a file that cannot be read is left out (the one-by-one path reports it).  words_out (--live-words): every
-    member runs with scores on, a file's words go there when the file ends.  peek (--live-peek): after every call one vox_stream_group_peek for the members still
+    member runs with scores on (and, with alts_k from --live-alternatives, with that many alternatives), a file's words go there when the file ends.  peek (--live-peek): after every call one vox_stream_group_peek for the members still
     busy, a "  ~[" line each: the text so far plus the tentative tail."""
     step = max(1, int(round(16000 * chunk_ms / 1000.0)))
     group = model.create_stream_group(t_embed, n_members)
@@ -136,6 +140,8 @@ def transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, chunk_ms, 
     try:
         for k in range(n_members if words_out is not None else 0):
             group.set_scores(k, True)
+            if alts_k:
+                group.set_alternatives(k, alts_k)
         while nxt < len(paths) or busy:
             for k in range(n_members):
                 while k not in busy and nxt < len(paths):
@@ -161,7 +167,7 @@ def transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, chunk_ms, 
             for k in last:
                 b = busy.pop(k); texts[b[0]] = text(b[3])
                 if words_out is not None:
-                    write_words(words_out, pkg, paths[b[0]], b[3], group.scores(k), tokenizer, 16000)
+                    write_words(words_out, pkg, paths[b[0]], b[3], group.scores(k), tokenizer, 16000, group.alternatives(k) if alts_k else None)
             for k, tail in (group.peek(sorted(busy)) if peek and busy else {}).items():
                 b = busy[k]; log(f"  ~[{paths[b[0]]} {min(b[2], b[1].size) / 16000:8.2f} s] {text(b[3] + [int(v) for v in tail])}")
         return texts
@@ -316,7 +322,15 @@ def main(argv=None):
     ap.add_argument("--live-words", metavar="PATH", help="with --live: run the sessions with scores on (vox_stream_set_scores) and write one JSON line per word to PATH when "
                     "a file ends: text, first_id / last_id (indices into the file's ids), due_s (when the session hands the word's last id out, in seconds of pushed audio: "
                     "not where the word was said), logprob (summed over the word's ids), min_margin (the smallest top-2 margin among them), file; stdout is unchanged")
+    ap.add_argument("--live-alternatives", type=int, default=None, metavar="K", help="with --live-words: also keep every id's K (1..8) best alternatives and its step's entropy "
+                    "(vox_stream_set_alternatives); every word line gains entropy (the largest over the word's ids) and weakest: {k: the index of its smallest-margin id, "
+                    "alternatives: [{id, text, logprob}] of that id}; ids, stdout and the lines of runs without the flag are unchanged")
     a = ap.parse_args(argv)
+    if a.live_alternatives is not None and not a.live_words:
+        ap.error("--live-alternatives applies with --live-words")
+    if a.live_alternatives is not None and not 1 <= a.live_alternatives <= 8:
+        ap.error("--live-alternatives takes 1..8")
+    a.live_alternatives = a.live_alternatives or 0
     if a.live_peek and not a.live:
         ap.error("--live-peek applies with --live")
     if a.live_words and not a.live:
@@ -410,7 +424,7 @@ def main(argv=None):
             texts = join_units(len(paths), units, unit_texts)
     if a.live_group:
         try:
-            texts = transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_group, words_out, a.live_peek)
+            texts = transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_group, words_out, a.live_peek, a.live_alternatives)
         except Exception as e:      # the files fall back to one live session each
             log(f"Error in the stream group: {e}"); texts = {}
             if words_out is not None:      # the files' words come again with their lines
@@ -422,7 +436,7 @@ def main(argv=None):
         p = paths[i]
         try:
             t1 = time.time()
-            text = transcribe_live(pkg, p, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_native_rate, words_out, a.live_peek) if a.live else transcribe_one(pkg, p, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed)
+            text = transcribe_live(pkg, p, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_native_rate, words_out, a.live_peek, a.live_alternatives) if a.live else transcribe_one(pkg, p, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed)
             log(f"{p}: {time.time() - t1:.3f}s")
         except Exception as e:      # per-utterance failure isolates to that line (empty), eval_wer.py:211-223 tolerates it
             log(f"Error transcribing {p}: {e}"); text = ""; rc = 1

@@ -3741,6 +3741,25 @@ extern "C" int32_t vox_score_rows(vox_ctx* c, const float* logits, int32_t M, in
     return VOX_OK;
 }
 
+// vox_score_rows' companion: a vox_token_alts per row (launch_alts_rows: the kernel the live sessions' alternatives come from).  Every check before the context is
+// bound; host logits are uploaded.  out host; synchronises.
+static_assert(sizeof(vox_token_alts) == 72 && sizeof(TokenAlts) == sizeof(vox_token_alts) && VOX_ALTS_MAX == VOX_MAX_ALTERNATIVES, "vox_token_alts is TokenAlts");
+extern "C" int32_t vox_alternatives_rows(vox_ctx* c, const float* logits, int32_t M, int32_t V, int32_t k, vox_token_alts* out, int32_t mem_kind) {
+    ARGCHK(c && logits && out, "null argument"); ARGCHK(M > 0 && V > 0, "bad shape %d x %d", M, V);
+    ARGCHK(k >= 1 && k <= VOX_MAX_ALTERNATIVES, "k %d out of range (1..%d)", k, VOX_MAX_ALTERNATIVES);
+    ARGCHK(mem_kind == VOX_MEM_HOST || mem_kind == VOX_MEM_DEVICE, "bad mem_kind %d", mem_kind);
+    VOXCHK(ctx_bind(c));
+    hipStream_t s = c->stream; DevBuf dx, dout;
+    HIPCHK(dout.alloc_pooled(c, (size_t)M * sizeof(TokenAlts)));
+    if (mem_kind == VOX_MEM_HOST) {
+        HIPCHK(dx.alloc_pooled(c, (size_t)M * V * 4)); HIPCHK(hipMemcpyAsync(dx.p, logits, (size_t)M * V * 4, hipMemcpyHostToDevice, s)); logits = dx.as<float>();
+    }
+    HIPCHK(launch_alts_rows(logits, M, V, k, dout.as<TokenAlts>(), s));
+    HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)M * sizeof(TokenAlts), hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
+    if (c->pw_model) return pw_after_sync(c->pw_model);      // (a synchronising call of the piecewise surface, as vox_score_rows)
+    return VOX_OK;
+}
+
 // lm_head + argmax in one call: the token id comes back, not 512 KB of logits per row.  ids host; synchronises.
 extern "C" int32_t vox_lm_head_argmax(vox_model* m, const float* hidden, int32_t M, int32_t* ids, int32_t mem_kind) {
     ARGCHK(m && hidden && ids && M > 0, "bad argument"); VOXCHK(ctx_bind(m->ctx));
@@ -4175,20 +4194,59 @@ struct ScoreState {
         return VOX_OK;
     }
 };
+// A session's alternatives (vox_stream_set_alternatives; DESIGN.md section 8, "Alternatives"): ScoreState's twin for the 72-byte records, at the session's k (0: off).
+// peeked: the records of the ids the last peek returned -- never part of the session's list, gone with the next push / finish / peek / reset.
+struct AltsState {
+    int k = 0; TokenAlts* dev = nullptr; int cap = 0;
+    std::vector<vox_token_alts> host, peeked;
+    size_t bytes() const { return dev ? (size_t)cap * sizeof(TokenAlts) : 0; }
+    static vox_token_alts off() { vox_token_alts r; r.entropy = NAN; r.n = 0; for (vox_alt& a : r.alt) a = vox_alt{-1, NAN}; return r; }
+    int32_t alloc(int max_pos, const char* whose) {      // the first k > 0
+        if (dev) return VOX_OK;
+        if (hipMalloc((void**)&dev, (size_t)(max_pos + 2) * sizeof(TokenAlts)) != hipSuccess) { (void)hipGetLastError(); dev = nullptr; return fail(VOX_ERR_HIP, "hipMalloc of %s alternatives records failed", whose); }
+        cap = max_pos + 2; return VOX_OK;
+    }
+    void restart() { host.clear(); peeked.clear(); }      // create / reset: the lists start over, k stays
+    // in front of the call's synchronisation: where the call's `due` records go (the session's list behind the `have` handed out, a peek's own array), and their copy
+    // A session that never had k > 0 (dev null) keeps no list: its pushes do no work here, and read hands out off-records for the ids the list does not reach.
+    int32_t enqueue(int have, int due, bool peek, vox_token_alts** dst, hipStream_t s) {
+        if (peek) { peeked.assign((size_t)due, off()); *dst = peeked.data(); }
+        else if (!dev) { peeked.clear(); *dst = nullptr; return VOX_OK; }
+        else { peeked.clear(); host.resize((size_t)have + due, off()); *dst = host.data() + have; }
+        if (k > 0 && due > 0) HIPCHK(hipMemcpyAsync(*dst, dev + have, (size_t)due * sizeof(TokenAlts), hipMemcpyDeviceToHost, s));
+        return VOX_OK;
+    }
+    void settle(int due, vox_token_alts* dst) const { for (int i = 0; k == 0 && dst && i < due; i++) dst[i] = off(); }      // behind it: a call that ran with alternatives off
+    int32_t read(int have, int32_t first_id, int32_t n, vox_token_alts* out) const {
+        ARGCHK(first_id >= 0 && n >= 0 && (int64_t)first_id + n <= have, "%d ids from %d on: %d handed out", n, first_id, have);
+        ARGCHK(out || n == 0, "null output");
+        for (int i = 0; i < n; i++) out[i] = (size_t)(first_id + i) < host.size() ? host[(size_t)(first_id + i)] : off();
+        return VOX_OK;
+    }
+    int32_t read_peeked(vox_token_alts* out, int32_t out_cap, int32_t* n) const {
+        ARGCHK(n, "null argument"); ARGCHK(out_cap >= 0 && (size_t)out_cap >= peeked.size(), "capacity %d for the %zu records of the last peek", out_cap, peeked.size());
+        ARGCHK(out || peeked.empty(), "null output");
+        if (!peeked.empty()) std::memcpy(out, peeked.data(), peeked.size() * sizeof(vox_token_alts));
+        *n = (int32_t)peeked.size();
+        return VOX_OK;
+    }
+};
 // One session's share of one call's hand-back -- a solo stream's push / finish / peek, a member's entry of a group's advance / peek: the call's `due` ids from the
-// session's device token array into the caller's out_ids, their records into the session's own list or, in a peek, into the caller's array (null: none wanted).
+// session's device token array into the caller's out_ids, their records into the session's own list or, in a peek, into the caller's array (null: none wanted); their
+// alternatives records into the session's list or, in a peek, into the array the session keeps for vox_stream_peeked_alternatives.
 namespace {
 struct SessionOut {
-    FeedState* feed; ScoreState* sc; const int* tokens; int32_t* out_ids; int due;
+    FeedState* feed; ScoreState* sc; AltsState* al; const int* tokens; int32_t* out_ids; int due;
     bool peek; vox_token_score* peek_scores;      // a peek's records never enter the session's list, and ids_out stays
-    vox_token_score* dst = nullptr;
+    vox_token_score* dst = nullptr; vox_token_alts* adst = nullptr;
     int32_t enqueue(hipStream_t s) {      // in front of the call's synchronisation: the records travel with the ids
         const int have = feed->ids_out;
         if (due > 0) HIPCHK(hipMemcpyAsync(out_ids, tokens + VOX_PREFIX_TOKENS + have, (size_t)due * 4, hipMemcpyDeviceToHost, s));
         if (peek) dst = peek_scores; else { sc->host.resize((size_t)have + due); dst = sc->host.data() + have; }
-        return sc->enqueue(have, due, dst, s);
+        VOXCHK(sc->enqueue(have, due, dst, s));
+        return al->enqueue(have, due, peek, &adst, s);
     }
-    void settle() { sc->settle(due, out_ids, dst); if (!peek) feed->ids_out += due; }      // behind it
+    void settle() { sc->settle(due, out_ids, dst); al->settle(due, adst); if (!peek) feed->ids_out += due; }      // behind it
 };
 }  // namespace
 struct DecPlanes { float *k = nullptr, *v = nullptr; int rows = 0; size_t stride = 0; };      // a decoder cache's planes: what a cache that grew inside a peek leaves behind
@@ -4210,6 +4268,7 @@ struct vox_stream {
     EngBinding eng;      // the decode engine's layer table for the stream's cache, its argmax partials (256), the pinned host copy of its error word
     float* tap = nullptr; int tap_max = 0, tap_rows = 0;
     ScoreState sc; float* score_row = nullptr;      // scores: the records, and the logits row a scored step writes when no tap row takes it
+    AltsState al;                                   // alternatives: the records (a step with them on writes the same row)
     float *ftap_mel = nullptr, *ftap_conv = nullptr; int ftap_max = 0, ftap_ticks = 0;      // vox_debug_stream_front_tap_*: per tick its 4 R fresh mel frames and its R conv-stem rows
     int h_state[STRM_WORDS]; int h_pos_word = 0;
     // vox_stream_peek: the ring keep's save area; while a peek's ticks run (active), a decoder cache that grows leaves its planes in `old`: the peek puts them back
@@ -4327,7 +4386,7 @@ static int32_t stream_load_initial(vox_stream* st) {
                        [&]() -> int32_t { HIPCHK(engine_tab_enqueue(m, st->eng, st->dec)); return VOX_OK; }));
     st->feed.restart(st->PC); st->verified_pos = st->PC; st->eng_unverified = false;
     st->eng_steps = st->op_steps = st->verified_eng_steps = st->verified_op_steps = 0; st->tap_rows = st->verified_tap_rows = 0; st->ftap_ticks = 0;
-    st->sc.host.clear();      // the utterance's records start over; the flag stays
+    st->sc.host.clear(); st->al.restart();      // the utterance's records start over; the flag and k stay
     return VOX_OK;
 }
 
@@ -4336,7 +4395,7 @@ static void stream_release(vox_stream* st) {
     (void)hipSetDevice(st->ctx->device); (void)hipStreamSynchronize(st->ctx->stream);      // never dereferences st->m: a stream may not outlive its model, but freeing it late must not crash
     cache_release(st->dec);
     for (void* p : {(void*)st->kring, (void*)st->vring, (void*)st->samples, (void*)st->audio_keep, (void*)st->ws, (void*)st->tokens, (void*)st->state, (void*)st->tap, (void*)st->ftap_mel, (void*)st->ftap_conv,
-                    (void*)st->feed.At, (void*)st->feed.in_ring, (void*)st->s16_stage, (void*)st->d_mem, (void*)st->sc.dev, (void*)st->score_row,
+                    (void*)st->feed.At, (void*)st->feed.in_ring, (void*)st->s16_stage, (void*)st->d_mem, (void*)st->sc.dev, (void*)st->score_row, (void*)st->al.dev,
                     (void*)st->peek.keep.p, (void*)st->peek.old.k, (void*)st->peek.old.v}) if (p) (void)hipFree(p);
     binding_release(st->eng);
     delete st;
@@ -4432,7 +4491,7 @@ extern "C" int32_t vox_stream_info(const vox_stream* st, int64_t out[8]) {
 // words stay).  logits_row: where the step's f32 logits go (the tap), or null.  With scores on, stream_score_kernel follows the advance kernel.
 static int32_t stream_decode_step(vox_stream* st, float* h, float* logits_row, int enc_rows) {
     vox_model* m = st->m; hipStream_t s = st->ctx->stream; vox_cache* kc = st->dec;
-    if (st->sc.on && !logits_row) logits_row = st->score_row;      // a scored step always leaves its logits: in the tap's row, else in the stream's own
+    if ((st->sc.on || st->al.k > 0) && !logits_row) logits_row = st->score_row;      // a scored step always leaves its logits: in the tap's row, else in the stream's own
     ARGCHK(kc->len == st->feed.pos && st->feed.pos < kc->max_seq, "internal: stream decoder cache at %d, position %d of %d", kc->len, st->feed.pos, kc->max_seq);
     int* pos_word = st->state + STRM_POS;
     if (engine_bind(m, st->eng, kc)) {      // one launch: the layers against the stream's cache + final norm + lm_head (argmax partials, logits on request)
@@ -4448,6 +4507,7 @@ static int32_t stream_decode_step(vox_stream* st, float* h, float* logits_row, i
     }
     // the emitted id's record, behind the advance launch of either path -- and of the re-run's steps, which come through here again
     if (st->sc.on) HIPCHK(launch_stream_score(logits_row, m->cfg.vocab, st->d_mem, st->d_order, 1, VOX_PREFIX_TOKENS, s));
+    if (st->al.k > 0) HIPCHK(launch_stream_alts(logits_row, m->cfg.vocab, st->d_mem, st->d_order, 1, VOX_PREFIX_TOKENS, s));
     kc->len = ++st->feed.pos;
     return VOX_OK;
 }
@@ -4697,7 +4757,7 @@ static int32_t stream_run(vox_stream* st, const StreamSrc& src, FeedPlan& plan, 
         VOXCHK(ring_write_f32(s, st->samples, STREAM_SAMPLE_RING, q.pad_w0, StreamSrc{}, 0, q.pad));
         for (int t = 0; t < q.ticks; t++) VOXCHK(stream_tick(st));
     }
-    SessionOut o{&f, &st->sc, st->tokens, out_ids, due, peek, peek_scores};
+    SessionOut o{&f, &st->sc, &st->al, st->tokens, out_ids, due, peek, peek_scores};
     VOXCHK(stream_verify_enqueue(st));
     bool reran = false;
     for (int round = 0; round < 2; round++) {      // a second time only behind the engine's re-run, which wrote the call's ids (and moved STRM_POS) again
@@ -4774,18 +4834,23 @@ extern "C" int32_t vox_stream_peek_ids(size_t n_samples, uint32_t sample_rate, i
     return VOX_OK;
 }
 
+// the stream's own logits row, for the steps of a scored stream (scores or alternatives) that no tap row takes: allocated once
+static int32_t stream_own_row(vox_stream* st) {
+    if (st->score_row) return VOX_OK;
+    const size_t row_b = (size_t)st->m->cfg.vocab * 4;
+    if (hipMalloc((void**)&st->score_row, row_b) != hipSuccess) { (void)hipGetLastError(); st->score_row = nullptr; return fail(VOX_ERR_HIP, "hipMalloc of the stream's logits row failed"); }
+    st->bytes += row_b;
+    return VOX_OK;
+}
 // scores on / off.  The first on allocates the records and the logits row; the stream's descriptor carries the records' pointer only while scores are on (the kernel's
 // own check), uploaded behind a synchronisation: nothing of an earlier call is in flight then
 extern "C" int32_t vox_stream_set_scores(vox_stream* st, int32_t on) {
     ARGCHK(st, "null stream"); ARGCHK(on == 0 || on == 1, "on must be 0 or 1"); VOXCHK(ctx_bind(st->ctx));
     hipStream_t s = st->ctx->stream; ScoreState& sc = st->sc;
     if (on) {      // the first on: the records, and the stream's own logits row
-        const size_t had = sc.bytes(), row_b = (size_t)st->m->cfg.vocab * 4;
+        const size_t had = sc.bytes();
         VOXCHK(sc.alloc(st->max_pos, "the stream's")); st->bytes += sc.bytes() - had;
-        if (!st->score_row) {
-            if (hipMalloc((void**)&st->score_row, row_b) != hipSuccess) { (void)hipGetLastError(); st->score_row = nullptr; return fail(VOX_ERR_HIP, "hipMalloc of the stream's score records failed"); }
-            st->bytes += row_b;
-        }
+        VOXCHK(stream_own_row(st));
     }
     HIPCHK(hipStreamSynchronize(s));
     struct { TokenScore* p; int cap; } w{on ? sc.dev : nullptr, on ? sc.cap : 0};
@@ -4797,6 +4862,33 @@ extern "C" int32_t vox_stream_set_scores(vox_stream* st, int32_t on) {
 extern "C" int32_t vox_stream_scores(const vox_stream* st, int32_t first_id, int32_t n, vox_token_score* out) {
     ARGCHK(st, "null stream");
     return st->sc.read(st->feed.ids_out, first_id, n, out);
+}
+
+// alternatives at k (0: off), as scores on / off: the first k > 0 allocates the records and, unless scores did, the logits row; the descriptor carries the records'
+// pointer only while k > 0, and the k, uploaded behind a synchronisation
+extern "C" int32_t vox_stream_set_alternatives(vox_stream* st, int32_t k) {
+    ARGCHK(st, "null stream"); ARGCHK(k >= 0 && k <= VOX_MAX_ALTERNATIVES, "k %d out of range (0..%d)", k, VOX_MAX_ALTERNATIVES); VOXCHK(ctx_bind(st->ctx));
+    hipStream_t s = st->ctx->stream; AltsState& al = st->al;
+    if (k > 0) {
+        const size_t had = al.bytes();
+        VOXCHK(al.alloc(st->max_pos, "the stream's")); st->bytes += al.bytes() - had;
+        VOXCHK(stream_own_row(st));
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    struct { TokenAlts* p; int cap, k; } w{k > 0 ? al.dev : nullptr, k > 0 ? al.cap : 0, k};
+    HIPCHK(hipMemcpyAsync(&st->d_mem->alts, &w.p, sizeof w.p, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(&st->d_mem->alts_cap, &w.cap, sizeof w.cap, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(&st->d_mem->alts_k, &w.k, sizeof w.k, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    al.k = k;
+    return VOX_OK;
+}
+extern "C" int32_t vox_stream_alternatives(const vox_stream* st, int32_t first_id, int32_t n, vox_token_alts* out) {
+    ARGCHK(st, "null stream");
+    return st->al.read(st->feed.ids_out, first_id, n, out);
+}
+extern "C" int32_t vox_stream_peeked_alternatives(const vox_stream* st, vox_token_alts* out, int32_t cap, int32_t* n) {
+    ARGCHK(st, "null stream");
+    return st->al.read_peeked(out, cap, n);
 }
 
 extern "C" int32_t vox_debug_stream_tap_arm(vox_stream* st, int32_t max_rows) {
@@ -4864,6 +4956,7 @@ struct GroupMember {
     FeedState feed;                      // the member's host mirror; at a capture rate: its own input ring, a copy of its rate's plan, the rate's matrix (owned by the rate table)
     int rate = -1; uint64_t steps = 0;   // its slot of the group's rate table (-1: 16 kHz); its ticks, each one row of an xf_chain step
     ScoreState sc;                       // its scores (vox_stream_group_set_scores); h_mem[i].scores is sc.dev while they are on
+    AltsState al;                        // its alternatives (vox_stream_group_set_alternatives); h_mem[i].alts is al.dev while its k > 0
     int h_state[STRM_WORDS];
 };
 // one block matrix per rate in use, shared by the members at that rate (built by resample_matrix_build: vox_resample's bits; never the context's matrix, which goes
@@ -4885,6 +4978,7 @@ struct vox_stream_group {
     GroupIngest* d_ingest = nullptr; std::deque<GroupIngest> ingests;      // the pass's ingest descriptors on the device; the ones uploaded by the call in flight, as orders
     int16_t* s16_stage = nullptr;      // host 16-bit feeds: STREAM_SAMPLE_RING samples of device staging per member, allocated at the first one
     int n_scored = 0;                  // members with scores on: a round launches stream_score_kernel only while there is one
+    int n_alts = 0;                    // members with alternatives on: the same for stream_alts_kernel
     KeepArea keep;                     // vox_stream_group_peek: [16 ints: the peeking members, slot by slot][a ring keep area per slot]
 };
 // the member leaves its rate: its input ring and its reference to the rate's matrix go (the matrix with its last reference).  The caller has synchronised.
@@ -4929,14 +5023,14 @@ static int32_t group_member_seed(vox_stream_group* g, int i) {
     GroupMember& me = g->mem[i];
     VOXCHK(stream_seed(g->m, g->t_embed.data(), g->g.RC, g->g.PC, g->g.cap, g->h_mem[i].kring, g->h_mem[i].vring, &view, g->h_mem[i].tokens, g->h_mem[i].state, me.h_state,
                        []() -> int32_t { return VOX_OK; }));
-    me.feed.restart(g->g.PC); me.steps = 0; me.sc.host.clear();
+    me.feed.restart(g->g.PC); me.steps = 0; me.sc.host.clear(); me.al.restart();
     return VOX_OK;
 }
 static void group_release(vox_stream_group* g) {
     if (!g) return;
     (void)hipSetDevice(g->ctx->device); (void)hipStreamSynchronize(g->ctx->stream);      // never dereferences g->m (as stream_release)
     for (StreamMember& me : g->h_mem) if (me.tap) (void)hipFree(me.tap);
-    for (GroupMember& me : g->mem) if (me.sc.dev) (void)hipFree(me.sc.dev);
+    for (GroupMember& me : g->mem) { if (me.sc.dev) (void)hipFree(me.sc.dev); if (me.al.dev) (void)hipFree(me.al.dev); }
     for (size_t i = 0; i < g->mem.size(); i++) group_member_drop_rate(g, (int)i);
     for (void* p : {(void*)g->keep.p, (void*)g->d_ingest, (void*)g->s16_stage, (void*)g->kring, (void*)g->vring, (void*)g->dec_k, (void*)g->dec_v, (void*)g->samples, (void*)g->ws, (void*)g->tokens, (void*)g->state, (void*)g->d_mem, (void*)g->d_order,
                     (void*)g->qkv, (void*)g->att, (void*)g->logits, (void*)g->ssq, (void*)g->xf1, (void*)g->xf2, (void*)g->xf3}) if (p) (void)hipFree(p);
@@ -5008,7 +5102,7 @@ extern "C" int32_t vox_stream_group_info(const vox_stream_group* g, int32_t memb
     const uint64_t tap_b = g->h_mem[member].tap ? (uint64_t)g->h_mem[member].tap_max * g->m->cfg.vocab * 4 : 0;
     const uint64_t rate_b = me.rate >= 0 ? (uint64_t)me.feed.in_ring_n * 4 + g->rates[(size_t)me.rate].bytes / (uint64_t)g->rates[(size_t)me.rate].refs : 0;
     feed_info(me.feed, R, g->g.cap, out);
-    out[5] = (int64_t)(g->bytes / (uint64_t)g->n + tap_b + rate_b + me.sc.bytes());      // the member's share of the group's device state; its own input ring, its share of its rate's matrix, its score records
+    out[5] = (int64_t)(g->bytes / (uint64_t)g->n + tap_b + rate_b + me.sc.bytes() + me.al.bytes());      // the member's share of the group's device state; its own input ring, its share of its rate's matrix, its score and alternatives records
     out[6] = 0; out[7] = (int64_t)me.steps;                      // no engine step; the member's ticks, each one row of an xf_chain step
     return VOX_OK;
 }
@@ -5024,6 +5118,7 @@ static int32_t group_round(vox_stream_group* g, const StreamWs& w, int n_r) {
     VOXCHK(xf_chain(m, xb, 0, n_r, 0, 0, true, 0, s));
     HIPCHK(launch_stream_group_advance(g->logits, c.vocab, g->d_mem, g->d_order, n_r, R, 4 * R, g->g.cap, s));
     if (g->n_scored > 0) HIPCHK(launch_stream_score(g->logits, c.vocab, g->d_mem, g->d_order, n_r, VOX_PREFIX_TOKENS, s));      // slots of unscored members return at once
+    if (g->n_alts > 0) HIPCHK(launch_stream_alts(g->logits, c.vocab, g->d_mem, g->d_order, n_r, VOX_PREFIX_TOKENS, s));      // (the same)
     return VOX_OK;
 }
 // A group's call -- advance, its 16-bit form, peek -- is group_run, in four units: group_plan_entries (every check, nothing changed), then per pass group_stage_pass
@@ -5101,7 +5196,7 @@ static int32_t group_drain(vox_stream_group* g, vox_stream_feed* feeds, const Gr
     std::vector<SessionOut> outs;
     for (size_t k = 0; k < call.fs.size(); k++) {
         GroupMember& me = g->mem[call.fs[k].member];
-        outs.push_back(SessionOut{&me.feed, &me.sc, g->h_mem[call.fs[k].member].tokens, feeds[k].out_ids, call.fs[k].plan.due, call.peek, peek_scores ? peek_scores[k] : nullptr});
+        outs.push_back(SessionOut{&me.feed, &me.sc, &me.al, g->h_mem[call.fs[k].member].tokens, feeds[k].out_ids, call.fs[k].plan.due, call.peek, peek_scores ? peek_scores[k] : nullptr});
         VOXCHK(outs.back().enqueue(s));
     }
     if (keep) HIPCHK(launch_stream_keep(*keep, 1, s));
@@ -5192,6 +5287,28 @@ extern "C" int32_t vox_stream_group_set_scores(vox_stream_group* g, int32_t memb
 extern "C" int32_t vox_stream_group_scores(const vox_stream_group* g, int32_t member, int32_t first_id, int32_t n, vox_token_score* out) {
     ARGCHK(g, "null group"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1);
     return g->mem[member].sc.read(g->mem[member].feed.ids_out, first_id, n, out);
+}
+extern "C" int32_t vox_stream_group_set_alternatives(vox_stream_group* g, int32_t member, int32_t k) {
+    ARGCHK(g, "null group"); ARGCHK(k >= 0 && k <= VOX_MAX_ALTERNATIVES, "k %d out of range (0..%d)", k, VOX_MAX_ALTERNATIVES);      // (k before the handle is read)
+    ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1);
+    VOXCHK(ctx_bind(g->ctx));
+    AltsState& al = g->mem[member].al;
+    if (k > 0) { char whose[24]; snprintf(whose, sizeof whose, "member %d's", member); VOXCHK(al.alloc(g->g.max_pos, whose)); }      // (the group's logits rows are there already)
+    HIPCHK(hipStreamSynchronize(g->ctx->stream));
+    StreamMember& hm = g->h_mem[member]; const StreamMember was = hm;
+    hm.alts = k > 0 ? al.dev : nullptr; hm.alts_cap = k > 0 ? al.cap : 0; hm.alts_k = k;
+    const int32_t r = group_upload_members(g);
+    if (r != VOX_OK) { hm = was; return r; }      // a failed upload leaves the host descriptor with the counters: n_alts gates the round's launch
+    g->n_alts += (k > 0) - (al.k > 0); al.k = k;
+    return VOX_OK;
+}
+extern "C" int32_t vox_stream_group_alternatives(const vox_stream_group* g, int32_t member, int32_t first_id, int32_t n, vox_token_alts* out) {
+    ARGCHK(g, "null group"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1);
+    return g->mem[member].al.read(g->mem[member].feed.ids_out, first_id, n, out);
+}
+extern "C" int32_t vox_stream_group_peeked_alternatives(const vox_stream_group* g, int32_t member, vox_token_alts* out, int32_t cap, int32_t* n) {
+    ARGCHK(g, "null group"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1);
+    return g->mem[member].al.read_peeked(out, cap, n);
 }
 extern "C" int32_t vox_debug_stream_group_tap_arm(vox_stream_group* g, int32_t member, int32_t max_rows) {
     ARGCHK(g, "null group"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1);

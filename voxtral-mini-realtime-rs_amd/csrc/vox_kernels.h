@@ -371,6 +371,9 @@ enum StreamWord { STRM_POS = 0,         // decoder position of the next tick (= 
                   STRM_TAP_ROWS = 5,    // group members: logits rows offered to the member's tap since it was armed
                   STRM_WORDS = 16 };    // block size in ints (a group of N sessions holds N such blocks back to back)
 struct TokenScore { float logprob, margin; int runner_up, id; };      // vox_token_score (voxtral_hip.h)
+static const int VOX_ALTS_MAX = 8;                                     // VOX_MAX_ALTERNATIVES
+struct TokenAlt { int id; float logprob; };
+struct TokenAlts { float entropy; int n; TokenAlt alt[VOX_ALTS_MAX]; };      // vox_token_alts (voxtral_hip.h)
 struct StreamMember {
     const float* samples; float gain;   // the session's 16 kHz sample ring; every sample is multiplied by gain before the mel
     int* state;                         // its StreamWord block
@@ -378,6 +381,7 @@ struct StreamMember {
     int* tokens;                        // its token row
     float* tap; int tap_max;            // group members: [tap_max][vocab] logits rows (null: not armed)
     struct TokenScore* scores; int scores_cap;      // the session's score records, one per id of the utterance (null: scores off, launch_stream_score skips the slot)
+    struct TokenAlts* alts; int alts_cap, alts_k;   // its alternatives records, one per id, and its k (null: alternatives off, launch_stream_alts skips the slot)
 };
 // front end: for every slot z < n the log-mel frames STRM_FRAME - halo_back .. + n_frames - 1 of the virtually padded signal zeros(left) + gain * samples of session
 // order[z], token-major into out + z * slot_stride ([n_frames][128]: the layout the conv stem's im2col GEMM reads).  Sample i of a session lives at ring[i & ring_mask];
@@ -444,6 +448,15 @@ hipError_t launch_score_rows(const float* x, int rows, int V, const int* ids, To
 // behind launch_stream_advance / launch_stream_group_advance: slot z < n scores the id session order[z] just emitted (tokens[STRM_POS]) on row z of logits [n][vocab],
 // into mem[order[z]].scores[STRM_POS - first_pos]; sessions whose scores pointer is null are skipped
 hipError_t launch_stream_score(const float* logits, int vocab, const StreamMember* mem, const int* order, int n, int first_pos, hipStream_t s);
+// ---- alternatives of emitted ids (vox_token_alts): for a logits row L[V] and k in 1 .. 8, alt[j] = the argmax by the rule over the columns not yet taken (n = how many
+// could win, at most k; the entries behind are {-1, NaN}) with logprob = (L[id] - m) - logf(S), and entropy = max(0, logf(S) - T / S), S = sum exp(L - m) as score_row sums
+// it, T = sum exp(L - m) (L - m) over the columns above -inf.  A row with a NaN or a maximum that is not finite: entropy and every logprob NaN.  A function of the row's
+// values, V and k alone; the list for k is the list for 8 cut short: alts_row, vox_kernels.hip.
+// out[r] = the record of row r of x [rows][V] (device pointers)
+hipError_t launch_alts_rows(const float* x, int rows, int V, int k, TokenAlts* out, hipStream_t s);
+// behind launch_stream_score's place in the tick: slot z < n writes the record of the id session order[z] just emitted from row z of logits [n][vocab] into
+// mem[order[z]].alts[STRM_POS - first_pos] at that session's alts_k; sessions whose alts pointer is null are skipped
+hipError_t launch_stream_alts(const float* logits, int vocab, const StreamMember* mem, const int* order, int n, int first_pos, hipStream_t s);
 // ---- the ring keep of a peek (vox_stream_peek, vox_stream_group_peek): around ticks that are taken back.  Slot z < n works for session order[z] on its own area
 // keep + z * slot_stride (floats, a multiple of 4): [STRM_WORDS ints: the state block][K: layers x n_heads x rows x hd][V: the same].
 // restore = 0 (save, in front of the ticks): the state block, and of every (layer, head) of K and V the `rows` ring rows from STRM_HEAD on, modulo cap -- the slots the

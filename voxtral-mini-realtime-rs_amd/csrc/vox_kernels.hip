@@ -4635,4 +4635,122 @@ hipError_t launch_stream_keep(const StreamKeepParams& p, int restore, hipStream_
     return hipGetLastError();
 }
 
+// ---- what else the model weighed at an id (vox_token_alts, voxtral_hip.h): the row's k best columns by the rule with their log-probabilities, and the row's entropy.
+// ONE device function for every launch form, on score_row's scan order (column 4 i + j -> thread i % NT, leftovers to threads 0 .. 2, float4 loads or the same four
+// columns singly), so the record is a function of the row's values, V and k alone.
+//   Scan 1: every thread keeps its own 8 best (value, column) in registers, sorted: a new column goes in front of the first entry it beats (argmax_beats: the columns
+//   ascend, an equal value never displaces an earlier one; a NaN and -inf beat nothing), the entries behind move down.  Statically indexed throughout: no scratch.
+//   Always 8 deep, whatever k: one thread can own every winner, and the list for k is then the list for 8 cut short by construction.
+//   Merge: k rounds of block_argmax over the threads' heads; the thread that owns the winner pops.  A round nothing wins ends the list: n < k.
+//   Scan 2: S = sum exp(L - m) exactly as score_row sums it (m = the first winner's value = the row's maximum; the same chain of adds, xor tree and walk over the wave
+//   sums, so alt[0].logprob has the bits of the score record's logprob) and, through the same chain and tree, T = sum exp(L - m) (L - m) without the -inf columns.
+//   logprob_j = (L[id_j] - m) - logf(S), entropy = max(0, logf(S) - T / S); a row with a NaN or a maximum that is not finite: NaN for all of them, ids and n by the rule.
+// (VOX_NO_PK_F32 on the kernels: hipcc pairs the f32 arithmetic of the float4 scans.)
+__device__ __forceinline__ bool argmax_beats(float x, float v) {      // would (x, a later column) replace the running best v?  The rule's own test
+    int idx = 0; argmax_take<true>(v, idx, x, 1); return idx != 0;
+}
+template <int NT>
+__device__ __forceinline__ void alts_row(const float* __restrict__ row, int V, int k, TokenAlts* __restrict__ out, float* sv, int* si) {
+    constexpr int K = VOX_ALTS_MAX;
+    __shared__ int s_nan, s_win, s_id[K];
+    __shared__ float s_val[K], s_t[16];
+    const bool al = (reinterpret_cast<uintptr_t>(row) & 15) == 0;
+    const int V4 = V >> 2;
+    k = k < 1 ? 1 : k > K ? K : k;
+    if (threadIdx.x == 0) s_nan = 0;
+    float lv[K]; int li[K]; bool nan = false;
+#pragma unroll
+    for (int j = 0; j < K; j++) { lv[j] = -INFINITY; li[j] = 0x7fffffff; }
+    auto see = [&](float x, int i) {
+        nan |= x != x;
+        bool in = argmax_beats(x, lv[K - 1]);
+#pragma unroll
+        for (int j = K - 1; j > 0; j--) {      // bottom up: entry j takes the old entry j - 1 when x beats that too, x when it beats entry j alone
+            const bool up = argmax_beats(x, lv[j - 1]);
+            lv[j] = in ? (up ? lv[j - 1] : x) : lv[j]; li[j] = in ? (up ? li[j - 1] : i) : li[j];
+            in = up;
+        }
+        lv[0] = in ? x : lv[0]; li[0] = in ? i : li[0];
+    };
+    for (int i = threadIdx.x; i < V4; i += NT) {
+        float4 q;
+        if (al) q = reinterpret_cast<const float4*>(row)[i];
+        else { q.x = row[4 * i]; q.y = row[4 * i + 1]; q.z = row[4 * i + 2]; q.w = row[4 * i + 3]; }
+        see(q.x, 4 * i); see(q.y, 4 * i + 1); see(q.z, 4 * i + 2); see(q.w, 4 * i + 3);
+    }
+    for (int i = 4 * V4 + threadIdx.x; i < V; i += NT) see(row[i], i);
+    __syncthreads();                                   // s_nan = 0 is visible; sv / si are free
+    if (nan) s_nan = 1;                                // (every writer stores the same value)
+    int n = 0;
+    for (; n < k; n++) {
+        float hv = lv[0]; int hi = li[0];
+        block_argmax<NT>(hv, hi, sv, si);              // thread 0: the round's winner; the first round's barrier publishes s_nan
+        if (threadIdx.x == 0) { s_win = hi; s_val[n] = hv; s_id[n] = hi; }
+        __syncthreads();                               // (thread 0 has read sv / si: the next round may write them)
+        const int win = s_win;
+        if (win == 0x7fffffff) break;                  // nothing can win any more (the whole workgroup leaves together)
+        if (li[0] == win) {                            // the owner pops
+#pragma unroll
+            for (int j = 0; j < K - 1; j++) { lv[j] = lv[j + 1]; li[j] = li[j + 1]; }
+            lv[K - 1] = -INFINITY; li[K - 1] = 0x7fffffff;
+        }
+    }
+    const float m = n > 0 ? s_val[0] : -INFINITY;
+    const bool ok = !s_nan && m - m == 0.0f;           // finite maximum, no NaN: otherwise nothing is summed
+    float acc = 0.0f, tac = 0.0f;
+    if (ok) {
+        auto add = [&](float x) { const float d = x - m, e = expf(d); acc += e; tac += d == -INFINITY ? 0.0f : e * d; };      // (a -inf column: e = 0, and no 0 * inf)
+        for (int i = threadIdx.x; i < V4; i += NT) {
+            float4 q;
+            if (al) q = reinterpret_cast<const float4*>(row)[i];
+            else { q.x = row[4 * i]; q.y = row[4 * i + 1]; q.z = row[4 * i + 2]; q.w = row[4 * i + 3]; }
+            add(q.x); add(q.y); add(q.z); add(q.w);
+        }
+        for (int i = 4 * V4 + threadIdx.x; i < V; i += NT) add(row[i]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { acc += __shfl_xor(acc, o); tac += __shfl_xor(tac, o); }
+    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = acc; s_t[threadIdx.x >> 6] = tac; }      // (sv is free: the merge's last barrier lies behind thread 0's read)
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const float qnan = __int_as_float(0x7fc00000);
+    float S = sv[0], T = s_t[0];
+    for (int w = 1; w < NT / 64; w++) { S += sv[w]; T += s_t[w]; }
+    const float lse = logf(S);
+    out->entropy = ok ? fmaxf(0.0f, lse - T / S) : qnan; out->n = n;
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        const bool has = j < n;
+        out->alt[j].id = has ? s_id[j] : -1; out->alt[j].logprob = has && ok ? (s_val[j] - m) - lse : qnan;
+    }
+}
+// the plain form: one workgroup per row of x [rows][V]
+__global__ __launch_bounds__(1024) VOX_NO_PK_F32 void alts_rows_kernel(const float* __restrict__ x, int V, int k, TokenAlts* __restrict__ out) {
+    __shared__ float bv[16];
+    __shared__ int bi[16];
+    alts_row<1024>(x + (size_t)blockIdx.x * V, V, k, out + blockIdx.x, bv, bi);
+}
+hipError_t launch_alts_rows(const float* x, int rows, int V, int k, TokenAlts* out, hipStream_t s) {
+    if (rows <= 0 || V <= 0 || k < 1 || k > VOX_ALTS_MAX || !x || !out) return hipErrorInvalidValue;
+    alts_rows_kernel<<<dim3(rows), dim3(1024), 0, s>>>(x, V, k, out);
+    return hipGetLastError();
+}
+// the session form, behind the tick's advance kernel (and its score launch): slot z writes the record of the id session order[z] just emitted -- STRM_POS already moved
+// on -- from logits row z into record STRM_POS - first_pos of the session's array, at the session's own k; a session without one (alternatives off) returns at once
+__global__ __launch_bounds__(1024) VOX_NO_PK_F32 void stream_alts_kernel(const float* __restrict__ logits, int vocab, const StreamMember* __restrict__ mem, const int* __restrict__ order,
+                                                                        int first_pos) {
+    __shared__ float bv[16];
+    __shared__ int bi[16];
+    const StreamMember& me = mem[order[blockIdx.x]];
+    if (!me.alts) return;
+    const int r = me.state[STRM_POS] - first_pos;
+    if (r < 0 || r >= me.alts_cap) return;             // (never: the host sizes the array by the session's position limit)
+    alts_row<1024>(logits + (size_t)blockIdx.x * vocab, vocab, me.alts_k, me.alts + r, bv, bi);
+}
+hipError_t launch_stream_alts(const float* logits, int vocab, const StreamMember* mem, const int* order, int n, int first_pos, hipStream_t s) {
+    if (n < 1 || n > 16 || !logits || !mem || !order || vocab <= 0 || first_pos < 0) return hipErrorInvalidValue;
+    stream_alts_kernel<<<dim3(n), dim3(1024), 0, s>>>(logits, vocab, mem, order, first_pos);
+    return hipGetLastError();
+}
+
 }  // namespace vox

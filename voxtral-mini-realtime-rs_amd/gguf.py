@@ -416,6 +416,23 @@ def score_rows(ctx, logits, ids=None, device_ptr=None, shape=None):
     return out
 
 
+ALTS_DTYPE = np.dtype([("entropy", "<f4"), ("n", "<i4"), ("alt", np.dtype([("id", "<i4"), ("logprob", "<f4")]), (8,))])      # vox_token_alts
+
+
+def alternatives_rows(ctx, logits, k, device_ptr=None, shape=None):
+    """vox_alternatives_rows: one vox_token_alts per row of f32 logits [rows][vocab] -> a structured array (entropy, n, alt[8] of (id, logprob)): the row's k best ids
+    by the project's argmax rule with their log-probabilities, and the entropy of its softmax.  logits: a host array, or device_ptr + shape=(rows, vocab).  Computed on
+    the device; synchronises."""
+    if device_ptr is None:
+        x = _f32(logits); x = x.reshape(1, -1) if x.ndim == 1 else x
+        M, V = x.shape; ptr = _ptr(x); kind = 0
+    else:
+        M, V = (int(v) for v in shape); ptr = C.c_void_p(device_ptr); kind = 1
+    out = np.zeros(M, dtype=ALTS_DTYPE)
+    check(lib().vox_alternatives_rows(ctx.h, ptr, M, V, int(k), _ptr(out), kind))
+    return out
+
+
 def stream_id_due(k: int, sample_rate: int = 16000) -> int:
     """The smallest number of pushed samples (at `sample_rate`) at which a live session hands out id k of its utterance: 2560 k + 40 at 16 kHz, by the schedule; at
     another rate the smallest n with stream_schedule_rate(n)[1] > k, found by bisection (the schedule is monotone).  This is when the session KNOWS the id, the only time
@@ -438,13 +455,21 @@ def stream_id_due(k: int, sample_rate: int = 16000) -> int:
     return hi
 
 
-def words(ids, scores, tokenizer, sample_rate: int = 16000):
+def words(ids, scores, tokenizer, sample_rate: int = 16000, alternatives=None):
     """The ids a live session handed out (ids[k] = id k of the utterance) and their records (LiveStream.scores()) as words.  Text ids are those >= 1000 (control and
     streaming ids are dropped); a word begins at the first text id and at every text id whose bytes begin with ASCII whitespace, so a character split over two ids stays
     in one word.  -> a list of {text (the word's bytes as lossy UTF-8, its leading whitespace included: the texts joined are the decoded transcript), first_id, last_id
     (indices into ids), due_s (stream_id_due(last_id) / sample_rate: when a session fed at that rate hands the word's last id out), logprob (the sum over its ids),
-    min_margin (the smallest margin among them)}."""
+    min_margin (the smallest margin among them)}.
+    alternatives (LiveStream.alternatives(), one record per id): every word also gets entropy (the largest over its ids; NaN when one of them has none) and weakest =
+    {k: the index of its smallest-margin id (the first of them), alternatives: that id's list as [{id, text, logprob}]}; text is the tokenizer's bytes for the id as
+    lossy UTF-8, "" for control ids and ids past the vocabulary."""
     from .tokenizer import TEXT_TOKEN_OFFSET
+
+    def id_text(t):
+        v = t - TEXT_TOKEN_OFFSET
+        b = tokenizer.vocab_bytes[v] if 0 <= v < len(tokenizer.vocab_bytes) else None
+        return "" if b is None else bytes(b).decode("utf-8", errors="replace")
     out = []; cur = None
     for k, t in enumerate(ids):
         t = int(t)
@@ -455,13 +480,21 @@ def words(ids, scores, tokenizer, sample_rate: int = 16000):
         if b is None:      # a control entry, an id past the vocabulary: VoxtralTokenizer.decode skips them
             continue
         if cur is None or b[:1] in (b" ", b"\t", b"\n", b"\r", b"\x0b", b"\x0c"):
-            cur = {"bytes": bytearray(), "first_id": k, "last_id": k, "logprob": 0.0, "min_margin": float("inf")}; out.append(cur)
-        cur["bytes"] += b; cur["last_id"] = k
-        cur["logprob"] += float(scores["logprob"][k]); cur["min_margin"] = min(cur["min_margin"], float(scores["margin"][k]))
+            cur = {"bytes": bytearray(), "first_id": k, "last_id": k, "logprob": 0.0, "min_margin": float("inf"), "weakest": k, "ks": []}; out.append(cur)
+        cur["bytes"] += b; cur["last_id"] = k; cur["ks"].append(k)
+        cur["logprob"] += float(scores["logprob"][k])
+        if float(scores["margin"][k]) < cur["min_margin"]:
+            cur["min_margin"] = float(scores["margin"][k]); cur["weakest"] = k
     res = []
     for w in out:
         res.append({"text": bytes(w["bytes"]).decode("utf-8", errors="replace"), "first_id": w["first_id"], "last_id": w["last_id"],
                     "due_s": stream_id_due(w["last_id"], sample_rate) / float(sample_rate), "logprob": w["logprob"], "min_margin": w["min_margin"]})
+        if alternatives is not None:
+            ent = [float(alternatives["entropy"][k]) for k in w["ks"]]
+            rec = alternatives[w["weakest"]]
+            res[-1]["entropy"] = float("nan") if any(e != e for e in ent) else max(ent)
+            res[-1]["weakest"] = {"k": w["weakest"], "alternatives": [{"id": int(a["id"]), "text": id_text(int(a["id"])), "logprob": float(a["logprob"])}
+                                                                      for a in rec["alt"][:int(rec["n"])]]}
     return res
 
 
@@ -556,6 +589,26 @@ class LiveStream:
         out = np.zeros(max(n, 0), dtype=SCORE_DTYPE)
         check(lib().vox_stream_scores(self.h, int(first), n, _ptr(out) if out.size else None))
         return out
+
+    def set_alternatives(self, k: int):
+        """vox_stream_set_alternatives: from the next push / finish / peek on, every id comes with its k best alternatives and the step's entropy (alternatives());
+        k = 0: off; survives reset()."""
+        check(lib().vox_stream_set_alternatives(self.h, int(k)))
+
+    def alternatives(self, first: int = 0, n=None) -> np.ndarray:
+        """vox_stream_alternatives: the records of ids [first, first + n) of the current utterance (n None: up to the last id handed out) as a structured array
+        (entropy, n, alt[8] of (id, logprob)); an id handed out while alternatives were off has NaN, 0 and (-1, NaN) throughout.  Reads host memory only."""
+        n = self.info()["ids"] - int(first) if n is None else int(n)
+        out = np.zeros(max(n, 0), dtype=ALTS_DTYPE)
+        check(lib().vox_stream_alternatives(self.h, int(first), n, _ptr(out) if out.size else None))
+        return out
+
+    def peeked_alternatives(self) -> np.ndarray:
+        """vox_stream_peeked_alternatives: the records of the ids the last peek() returned; empty once a push / finish / peek / reset has followed it."""
+        cap = max(stream_peek_ids(self.info()["samples"], 0, self.sample_rate), 1)      # (no peek returns more ids than the whole utterance has)
+        out = np.zeros(cap, dtype=ALTS_DTYPE); n = C.c_int32()
+        check(lib().vox_stream_peeked_alternatives(self.h, _ptr(out), cap, C.byref(n)))
+        return out[:n.value].copy()
 
     def tap_arm(self, max_rows):
         check(lib().vox_debug_stream_tap_arm(self.h, int(max_rows))); self._tap_max = int(max_rows)
@@ -701,6 +754,24 @@ class LiveStreamGroup:
         out = np.zeros(max(n, 0), dtype=SCORE_DTYPE)
         check(lib().vox_stream_group_scores(self.h, int(member), int(first), n, _ptr(out) if out.size else None))
         return out
+
+    def set_alternatives(self, member, k: int):
+        """vox_stream_group_set_alternatives: LiveStream.set_alternatives for one member; survives the member's resets."""
+        check(lib().vox_stream_group_set_alternatives(self.h, int(member), int(k)))
+
+    def alternatives(self, member, first: int = 0, n=None) -> np.ndarray:
+        """vox_stream_group_alternatives: LiveStream.alternatives for one member."""
+        n = self.info(member)["ids"] - int(first) if n is None else int(n)
+        out = np.zeros(max(n, 0), dtype=ALTS_DTYPE)
+        check(lib().vox_stream_group_alternatives(self.h, int(member), int(first), n, _ptr(out) if out.size else None))
+        return out
+
+    def peeked_alternatives(self, member) -> np.ndarray:
+        """vox_stream_group_peeked_alternatives: LiveStream.peeked_alternatives for one member."""
+        cap = max(stream_peek_ids(self.info(member)["samples"], 0, self.sample_rate(member)), 1)
+        out = np.zeros(cap, dtype=ALTS_DTYPE); n = C.c_int32()
+        check(lib().vox_stream_group_peeked_alternatives(self.h, int(member), _ptr(out), cap, C.byref(n)))
+        return out[:n.value].copy()
 
     def tap_arm(self, member, max_rows):
         check(lib().vox_debug_stream_group_tap_arm(self.h, int(member), int(max_rows))); self._tap_max[int(member)] = int(max_rows)
