@@ -401,7 +401,8 @@ int32_t vox_debug_reload_knobs(void);
  * out[0] short-sequence prefill, [1] MFMA prefill, [2] f32 VALU prefill (VOX_ATTN_F32), [3] single-query decode, [4] its speculative-row form (VOX_ATTN_SPEC),
  * [5] batched GQA decode, [6] fused attention + wo, [7] single-stream decode-engine launches (the whole step), [8] the live stream's ring attention (RoPE + K / V append + windowed
  * attention in one launch: exactly enc_layers per tick of a vox_stream).  Behind them, not attention: [9] a stream group's resampling ingest (one launch per pass for
- * all fed members), [10] a solo stream's.  Entries past [10] are written as 0. */
+ * all fed members), [10] a solo stream's.  Behind those, attention again: [11] paged single-query decode, [12] paged batched GQA decode (a paged stream group's step:
+ * PAGED DECODER CACHE below).  Entries past [12] are written as 0. */
 int32_t vox_debug_attn_launches(uint64_t* out, int32_t cap);
 /* Test hook: launches of the linear kernels enqueued by this process so far, by kernel form (host-side counts, as above; nothing is dispatched by them):
  * out[0..2] Q4 GEMV with 1 / 2 / 4 rows per wave, [3] dense GEMV, [4] 5..16-row skinny GEMM, [5] 17..48-row skinny GEMM (one-dimensional form), [6] its split-K form,
@@ -592,7 +593,9 @@ int32_t vox_debug_stream_front_tap_fetch(vox_stream* s, float* out_mel, float* o
  *   call, a finished member fed before its vox_stream_group_reset, a push past max_positions, a bad member or mem_kind.
  *   Decode step: the batched step's launch chain on the group's cache slab [layer][member][kv_head][max_positions][head_dim], which does not grow: max_positions = 0
  *   selects 2048 (5.4 minutes; at full size 0.21 MB per position, 0.44 GB per member) and a member that reaches it is refused until its reset.  Each member also holds an
- *   encoder ring (enc_capacity_rows as vox_stream_create's: 0.4 GB at full size).  The decode engine is not used.
+ *   encoder ring (enc_capacity_rows as vox_stream_create's: 0.4 GB at full size).  The decode engine is not used.  Derived from the code, not run: the slab's GQA
+ *   decode attention needs 16 max_positions bytes of LDS, so at full size a slab group above about 9 900 positions cannot launch it (creation accepts up to 16 384);
+ *   a paged group (PAGED DECODER CACHE below) has no such bound and grows into a pool.
  *   Creation refuses (VOX_ERR_UNSUPPORTED) what vox_stream_create refuses and models without tile-ordered Q4 weights; n_members outside 1..16 is invalid.
  *   gains: one per member, null = 1.0 each.
  * CAPTURE RATE AND 16-BIT PCM.  The rate is member state (vox_stream_group_create_rates, vox_stream_group_reset_rate; 16000 unless set), the sample format belongs to the
@@ -651,6 +654,31 @@ int32_t vox_stream_group_peeked_alternatives(const vox_stream_group* g, int32_t 
 /* vox_debug_stream_tap_* for one member (the rows are copied by the tick's last kernel; a reset of the member starts the count again) */
 int32_t vox_debug_stream_group_tap_arm(vox_stream_group* g, int32_t member, int32_t max_rows);
 int32_t vox_debug_stream_group_tap_fetch(vox_stream_group* g, int32_t member, float* out, int32_t* rows);
+/* PAGED DECODER CACHE.  vox_stream_group_create_paged makes a group whose decoder cache is ONE pool of fixed-size K / V pages instead of a slab slice per member: K and V
+ * pools [layer][pool_pages][kv_head][page_rows][head_dim], page_rows a power of two in 16..1024 (0: 256).  Logical page q of a member holds its cache rows q * page_rows ..
+ * (q + 1) * page_rows - 1.  A member holds only the pages its positions occupy: it takes a page when a call's ticks cross a page boundary, returns every page at its
+ * reset (and takes the seed's), and returns the pages that have fallen out of the decoder's sliding window after each committed call -- for a member at position P the
+ * logical pages below max(0, P - window) / page_rows, which no later step reads.  So a member's memory follows its length and stops growing at the window, and
+ * max_positions may be anything up to the session limit (the RoPE tables: 16 384 positions; 0 selects it); the refusal at max_positions stays per member.
+ *   pool_pages: 0 selects n_members * ceil(2048 / page_rows), the memory of the default slab.  A pool that cannot hold every member's seed (ceil(37 / page_rows) pages
+ *   each) is refused, as are a page_rows that is no power of two in range and a max_positions above the session limit.
+ *   A call is planned before anything changes: the logical pages its entries' ticks enter are counted, and a call that needs more than the pool has free is refused
+ *   (VOX_ERR_INVALID, the message names the pool, the member and both counts); the group is untouched and the call can be repeated, e.g. after another member's reset.
+ *   Pages are not freed inside a call.  A peek takes the pages its tail enters and returns them when the tail is taken back: pool and tables are what they were.
+ *   Contract: the same sequence of calls gives a paged group and a slab group the same ids and the same logits, bit for bit -- the decode step is the slab group's launch
+ *   chain, its attention reading K / V through the members' page tables (one launch per layer, as the slab's) and its q|k|v GEMM appending into the member's page.
+ *   Everything else of a group -- advance, its 16-bit form, peek, reset, info, scores, alternatives, taps -- works on a paged group unchanged.
+ * vox_stream_group_pool: out = page_rows, pool_pages, free pages, the most pages ever in use; held_or_null[member] = the pages each member holds.  A slab group:
+ *   VOX_ERR_UNSUPPORTED.
+ * vox_stream_group_pages_for: host arithmetic only, the allocator's own function: a member whose next tick is at `positions` holds the logical pages *first_page ..
+ *   *first_page + *n_pages - 1 = max(0, positions - window) / page_rows .. ceil(positions / page_rows) - 1 (window -1: no window).  During a call from position a to b a
+ *   member holds pages_for(a).first .. pages_for(b).first + pages_for(b).n - 1: what a pool must have room for.
+ * vox_debug_stream_group_pages (tests): the member's physical pages in logical order, *n of them (at most cap are written). */
+int32_t vox_stream_group_create_paged(vox_model* m, const float* t_embed, int32_t n_members, const float* gains /* null: 1.0 */, const uint32_t* rates /* null: 16000 each */,
+                                      int32_t enc_capacity_rows, int32_t max_positions, int32_t page_rows, int32_t pool_pages, vox_stream_group** out);
+int32_t vox_stream_group_pool(const vox_stream_group* g, int64_t out[4], int32_t* held_or_null);
+int32_t vox_stream_group_pages_for(int64_t positions, int32_t page_rows, int32_t window, int32_t* first_page, int32_t* n_pages);
+int32_t vox_debug_stream_group_pages(const vox_stream_group* g, int32_t member, int32_t* out, int32_t cap, int32_t* n);
 /* The live sessions' feed planner on its own (tests): host arithmetic only -- no context, no device, no model.  A fresh session fed at sample_rate (4 encoder rows per
  * position, the Voxtral left pad, no position limit to speak of) takes the calls (n_samples[c], finish[c] 0 / 1) exactly as vox_stream_push / _finish and a group's advance
  * plan and pass them, every due tick taken as run; finish[c] = 2 is a peek (n_samples[c] must be 0): planned as a finish, its one pass emitted, the session as it was.  One row of five words per pass: call index, input samples appended, 16 kHz samples that entered the 16 kHz ring (a

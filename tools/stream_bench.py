@@ -7,6 +7,7 @@
     python tools/stream_bench.py --scores [--group 1,4,16] [--out profiles/stream_scores_tick.txt]
     python tools/stream_bench.py --alternatives 8 [--group 1,4,16] [--out profiles/stream_alternatives_tick.txt]
     python tools/stream_bench.py --peek [--out profiles/stream_peek.txt]
+    python tools/stream_bench.py --group 1,4,16 --page-rows 256 [--out profiles/stream_group_paged_tick.txt]
 
  * stream: HIP events on the context's stream around ONE push of `ticks` x 2560 samples (a large push is a loop of identical ticks), at encoder positions past the
    750-row window, median of `passes` passes; launches per tick from the library's launch counters plus the fixed launches of a tick; wall time of single 160 ms pushes
@@ -30,6 +31,10 @@
  * --peek: what a peek costs (vox_stream_peek: finish's T ticks between a ring save and a ring restore, taken back).  One stream past the 750-row window; per pass,
    HIP events around one peek and, right behind it, around one push of the same T ticks -- the same session, the same positions (the peek left it where it was), the
    same run.  Median of `passes` passes of each, their ratio, and the launches of both from the library's counters plus the fixed launches of a tick.
+ * --page-rows R (with --group): the same run also times a PAGED group (vox_stream_group_create_paged: pages of R rows, the default pool -- the default slab's memory --
+   and the slab's 2048 positions per member), warmed like the slab group and timed the same way: pass i of the paged group right behind pass i of the slab group, the
+   same positions.  Reports the paged round, its difference to the slab round and both launch counts.  Behind the widths: one run of 16 members of mixed lengths on a
+   paged group, the pool's peak use in bytes next to the bytes of the default slab.
  * derived figures are labelled as derived."""
 import argparse
 import ctypes as C
@@ -72,9 +77,9 @@ class Timer:
 
 
 def launch_counts(pkg):
-    a = (C.c_uint64 * 9)(); g = (C.c_uint64 * 20)()
-    L = pkg.lib(); assert L.vox_debug_attn_launches(a, 9) == 0 and L.vox_debug_gemm_launches(g, 20) == 0
-    return sum(a), sum(g)
+    a = (C.c_uint64 * 13)(); g = (C.c_uint64 * 20)()      # attention forms 0..8 and the paged decode forms 11, 12 (9 and 10 are the resampling ingests: not counted here)
+    L = pkg.lib(); assert L.vox_debug_attn_launches(a, 13) == 0 and L.vox_debug_gemm_launches(g, 20) == 0
+    return sum(a[:9]) + sum(a[11:]), sum(g)
 
 
 def twin_kinds(a):
@@ -121,6 +126,9 @@ def bench_groups(pkg, ctx, m, t, tm, a, widths, lines):
                 on_member(g_s, k)
             g_s.advance({k: x[:pos] for k in range(N)})
             twins.append((what, st_s, g_s, [], []))
+        if a.page_rows:      # the paged twin of the slab group: the same positions per member, the default pool
+            gp = m.create_stream_group(t, N, gains=[gain] * N, max_positions=2048, page_rows=a.page_rows)
+            gp.advance({k: x[:pos] for k in range(N)}); paged = []; kp = 0
         if sr:
             g2, g3 = (m.create_stream_group(t, N, gains=[gr] * N, sample_rates=[sr] * N) for _ in range(2)); rpos = per * (warm + 1)      # fed from host / device memory
             for gg in (g2, g3):
@@ -133,6 +141,8 @@ def bench_groups(pkg, ctx, m, t, tm, a, widths, lines):
             feeds = {k: seg for k in range(N)}
             grp.append(tm.ms(lambda: g.advance(feeds)) / a.ticks); k2 = launch_counts(pkg)
             ks += sum(k1) - sum(k0); kg += sum(k2) - sum(k1)
+            if a.page_rows:
+                k2p = launch_counts(pkg); paged.append(tm.ms(lambda: gp.advance(feeds)) / a.ticks); kp += sum(launch_counts(pkg)) - sum(k2p)
             for what, st_s, g_s, solo_s, grp_s in twins:
                 k3 = launch_counts(pkg); solo_s.append(tm.ms(lambda: st_s.push(seg)) / a.ticks); k4 = launch_counts(pkg); grp_s.append(tm.ms(lambda: g_s.advance(feeds)) / a.ticks); k5 = launch_counts(pkg)
                 assert (sum(k4) - sum(k3), sum(k5) - sum(k4)) == (sum(k1) - sum(k0), sum(k2) - sum(k1))      # the counted launches are the plain pair's (the record kernels are uncounted: one each)
@@ -163,11 +173,25 @@ def bench_groups(pkg, ctx, m, t, tm, a, widths, lines):
         rows.append((N, rnd, tick))
         lines += [f"group of {N:2d}: round median {rnd:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in grp) + f"   solo tick median {tick:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in solo),
                   f"  round / ({N} x solo tick) = {rnd / (N * tick):.3f}   per member and tick {rnd / N:.3f} ms   launches per round {lg:.0f} (solo tick {ls:.0f})"]
+        if a.page_rows:
+            assert gp.info(N - 1)["positions"] == 38 + warm + a.ticks * a.passes
+            pl = gp.pool(); gp.close(); rp = statistics.median(paged)
+            lines += [f"  paged group of {N:2d} (pages of {pl['page_rows']} rows, pool of {pl['pool_pages']}, peak {pl['peak']}): round median {rp:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in paged) +
+                      f"   difference to the slab round {rp - rnd:+.3f} ms ({100 * (rp - rnd) / rnd:+.2f} %), per pass " + " ".join(f"{v - w:+.3f}" for v, w in zip(paged, grp)),
+                      f"  launches per round: paged {kp / ticks + fixed_enc + 2:.0f}, slab {lg:.0f}"]
         for what, _, _, solo_s, grp_s in twins:
             ts, rs = statistics.median(solo_s), statistics.median(grp_s); off = what.split()[0] + " off"
             lines += [f"  {what}, group of {N:2d}: round median {rs:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in grp_s) + f"   difference to {off} {rs - rnd:+.3f} ms ({100 * (rs - rnd) / rnd:+.2f} %), per pass " + " ".join(f"{v - w:+.3f}" for v, w in zip(grp_s, grp)),
                       f"  {what}, solo tick: median {ts:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in solo_s) + f"   difference to {off} {ts - tick:+.3f} ms ({100 * (ts - tick) / tick:+.2f} %), per pass " + " ".join(f"{v - w:+.3f}" for v, w in zip(solo_s, solo))]
     lines.append("derived: members one GPU serves in real time at each width = N x 160 ms / round: " + ", ".join(f"{N}: {N * 160.0 / r:.0f}" for N, r, _ in rows))
+    if a.page_rows:      # memory: 16 members of mixed lengths (20 (k + 1) ticks) on one paged group, next to the default slab every member would hold
+        R = a.page_rows; gp = m.create_stream_group(t, 16, gains=[gain] * 16, max_positions=2048, page_rows=R)
+        for c0 in range(0, 320, 20):
+            gp.advance({k: x[2560 * c0 + (40 if c0 else 0):2560 * (c0 + 20) + 40] for k in range(16) if 20 * (k + 1) > c0})
+        pl = gp.pool(); gp.close()
+        page_b = 2 * c.dec_layers * c.dec_kv_heads * R * c.dec_head_dim * 4; slab_b = 16 * 2 * c.dec_layers * c.dec_kv_heads * 2048 * c.dec_head_dim * 4
+        lines.append(f"memory, 16 members of 20 .. 320 ticks on one paged group: peak {pl['peak']} pages of {R} rows = {pl['peak'] * page_b / 1e9:.3f} GB of K / V held "
+                     f"(pages held at the end {sum(pl['held'])}); the default slab of 16 members x 2048 positions: {slab_b / 1e9:.3f} GB")
     if sr:
         what = f"{sr} Hz {'s16' if a.s16 else 'f32'}"
         lines.append(f"# every member fed at {what} ({per} input samples per tick), next to the 16 kHz f32 round above (same run, same passes)")
@@ -211,12 +235,15 @@ def main():
     ap.add_argument("--s16", action="store_true", help="with --rate: feed that group 16-bit PCM")
     ap.add_argument("--scores", action="store_true", help="also time a stream (with --group: and a group) with scores on, pass by pass next to the unscored one")
     ap.add_argument("--alternatives", type=int, default=0, metavar="K", help="also time a stream (with --group: and a group) with alternatives on at k = K (1..8), as --scores does")
+    ap.add_argument("--page-rows", type=int, default=0, metavar="R", help="with --group: also time a paged group (pages of R rows, the default pool) pass by pass next to the slab group")
     ap.add_argument("--peek", action="store_true", help="time vox_stream_peek next to the same number of ordinary ticks of the same session (nothing else is measured)")
     a = ap.parse_args()
     if not 0 <= a.alternatives <= 8:
         ap.error("--alternatives takes 1..8")
     if a.peek and (a.group or a.scores or a.alternatives):
         ap.error("--peek is a mode of its own")
+    if a.page_rows and not a.group:
+        ap.error("--page-rows applies with --group")
     if (a.rate or a.s16) and not a.group or (a.s16 and not a.rate):
         ap.error("--rate applies with --group, --s16 with --rate")
     widths = [int(v) for v in a.group.split(",")] if a.group else []

@@ -215,6 +215,10 @@ SIGNATURES = {
     "vox_stream_peek_ids": (i32, [sz, u32, i32, P(i32)]),
     "vox_debug_stream_tap_peeked": (i32, [vp, vp, i32]),
     "vox_stream_group_peek": (i32, [vp, vp, i32, vp]),
+    "vox_stream_group_create_paged": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, i32, P(vp)]),
+    "vox_stream_group_pool": (i32, [vp, P(i64 * 4), vp]),
+    "vox_stream_group_pages_for": (i32, [i64, i32, i32, P(i32), P(i32)]),
+    "vox_debug_stream_group_pages": (i32, [vp, i32, vp, i32, P(i32)]),
 }
 
 _LIB = None

@@ -6,6 +6,7 @@
 // src/models/time_embedding.rs.  No code is shared with oracle/ and there is no CPU fallback for compute.
 #include "../../include/voxtral_hip.h"
 #include "vox_kernels.h"
+#include "vox_page_pool.h"
 
 #include <dlfcn.h>
 #include <fcntl.h>
@@ -2619,6 +2620,10 @@ struct XfBufs {
     float *h, *qkv, *att, *logits, *ssq; uint16_t *xf1, *xf2, *xf3; long xf1_gs, xf2_gs, xf3_gs, ssq_gs;
     float *k, *v; size_t layer_stride, seq_stride; int max_seq; const int *pos, *kv_row; bool no_xcd_remap;
     float* ssq_e; void* planes; size_t planes_bytes;
+    // a paged cache (a paged stream group; null / 0 everywhere else, and the code of a contiguous cache runs): k / v are the page pool [layer][page][kv head][page_rows][hd],
+    // page_tab [member][page_tab_stride] its table, kv_row the rows' MEMBERS (attention finds its table row), kv_page / kv_in the rows' physical page and row inside it
+    // (the q|k|v epilogue appends there); score_rows: the attention's LDS score rows per query head
+    const int *page_tab, *kv_page, *kv_in; int page_tab_stride, page_shift, score_rows; long page_floats;
 };
 // the XF planes and ssq blocks of a step over n_grp groups (0: none, the group strides alone): from the pool, zeroed on s, bound to b
 struct XfPlanes {
@@ -2644,6 +2649,7 @@ static int32_t xf_chain(const vox_model* m, const XfBufs& b, int g0i, int ng, in
     const vox_model_cfg& c = m->cfg;
     const int D = c.dec_dim, H = c.dec_heads, KV = c.dec_kv_heads, hd = c.dec_head_dim, QD = H * hd, W = QD + 2 * KV * hd, F = c.dec_ffn, V = c.vocab;
     const int parts_D = q4_skinny_resid_xf_parts(D), max_seq = b.max_seq, M = mtw ? 16 * mtw : ng;
+    ARGCHK(!(b.page_tab && mtw), "internal: a paged cache runs the one-group chain (the wide step has no paged form)");
     const int r0 = g0i * 16;      // the chain's first group: its planes, sums, rows, positions and cache slices (a wide chain's further groups follow at the group strides)
     uint16_t* xf1 = b.xf1 + (size_t)g0i * b.xf1_gs; uint16_t* xf2 = b.xf2 + (size_t)g0i * b.xf2_gs; uint16_t* xf3 = b.xf3 + (size_t)g0i * b.xf3_gs; float* ssq = b.ssq + (size_t)g0i * b.ssq_gs;
     float* hg = b.h + (size_t)r0 * D; float* qg = b.qkv + (size_t)r0 * W; const int* pg = b.pos + r0; const int* rg = b.kv_row ? b.kv_row + r0 : nullptr;
@@ -2662,11 +2668,17 @@ static int32_t xf_chain(const vox_model* m, const XfBufs& b, int g0i, int ng, in
         float* kl = b.k + (size_t)l * b.layer_stride + row0; float* vl = b.v + (size_t)l * b.layer_stride + row0;
         { GemmParams g{}; g.out = qg; g.out_stride = W; g.ssq_part = ssq; g.n_part = l == 0 ? 1 : parts_D; g.pos = pg; g.rope_cos = m->dec_cos; g.rope_sin = m->dec_sin;
           g.hd = hd; g.n_q = QD; g.n_kv = KV; g.kc = kl; g.vc = vl; g.kv_seq_stride = (long)b.seq_stride; g.kv_head_stride = max_seq * hd; g.kv_row = rg;
+          if (b.page_tab) { g.kv_seq_stride = b.page_floats; g.kv_head_stride = (hd << b.page_shift); g.kv_row = b.kv_page + r0; g.kv_pos = b.kv_in + r0; }
           HIPCHK(gemm(g, L.wqkv.w, xf1, D, EPI_ROPE_KV)); }
         AttnParams ap{}; ap.q = qg; ap.k = kl; ap.v = vl; ap.kv_row_stride = hd; ap.kv_head_stride = max_seq * hd; ap.n_heads = H; ap.n_kv_heads = KV;
         ap.offset = 0; ap.window = c.dec_window; ap.pos_ptr = pg; ap.M = 1; ap.pos_per_seq = 1; ap.q_seq_stride = W; ap.out_seq_stride = QD; ap.kv_seq_stride = (long)b.seq_stride;
         ap.kv_row = rg; ap.out_xf = xf2; ap.prefer_gqa = prefer_gqa; ap.no_xcd_remap = b.no_xcd_remap; ap.spec_rows = spec_rows;
         ap.out = b.att; if (mtw) { ap.out = b.att + (size_t)g0i * 16 * QD; ap.out_xf_gstride = b.xf2_gs; }
+        if (b.page_tab) {
+            ap.kv_head_stride = (hd << b.page_shift); ap.page_tab = b.page_tab; ap.page_tab_stride = b.page_tab_stride; ap.page_shift = b.page_shift; ap.page_floats = b.page_floats;
+            ap.score_rows = b.score_rows;
+            HIPCHK(launch_attn_decode_paged(ap, hd, sg, M));
+        } else
         HIPCHK(launch_attn_decode(ap, hd, max_seq, sg, M));
         { GemmParams g{}; g.out = hg; g.out_stride = D; g.resid = hg; g.resid_stride = D; g.xf_out = xf1; g.xf_w = L.ffn_norm; g.xf_w2 = L.ada_mul; g.ssq_out = ssq;
           HIPCHK(gemm(g, L.wo.w, xf2, QD, EPI_RESID_XF)); }
@@ -4364,7 +4376,7 @@ static int32_t stream_seed(vox_model* m, const float* t_embed, int RC, int PC, i
     if (r == VOX_OK && !(P.enc_built && P.dec_built && P.RC == RC && P.PC == PC)) r = fail(VOX_ERR_HIP, "the prefix state a stream starts from could not be built");
     auto body = [&]() -> int32_t {
         HIPCHK(launch_stream_ring_init(P.enc_kv, c.enc_layers, RC, c.enc_heads, c.enc_head_dim, cap, kring, vring, s));
-        VOXCHK(prefix_rows_into(m, dec, s));
+        if (dec) VOXCHK(prefix_rows_into(m, dec, s));      // (null: `then` places the rows -- a paged group's member)
         VOXCHK(then());
         HIPCHK(prefix_tokens_enqueue(tokens, s));
         std::memset(h_state, 0, sizeof(int) * STRM_WORDS);
@@ -4980,7 +4992,17 @@ struct vox_stream_group {
     int n_scored = 0;                  // members with scores on: a round launches stream_score_kernel only while there is one
     int n_alts = 0;                    // members with alternatives on: the same for stream_alts_kernel
     KeepArea keep;                     // vox_stream_group_peek: [16 ints: the peeking members, slot by slot][a ring keep area per slot]
+    // a paged group (vox_stream_group_create_paged): dec_k / dec_v are the page pool [dec_layers][pool_pages][kv_heads][page_rows][hd] (layer_stride = the floats of a
+    // layer's pages), pool the allocator with every member's table mirror, d_tab the device table [n][pool.max_pages], d_kv_page / d_kv_in the step's physical pages and
+    // rows inside them [16] (behind d_kv_row, the same allocation).  A slab group: paged == false, nothing of this is set
+    bool paged = false; PagePool pool; int* d_tab = nullptr; int *d_kv_page = nullptr, *d_kv_in = nullptr; size_t page_floats = 0;
 };
+// entries [q0, q1) of a member's table mirror to the device, on the group's stream (the mirror stays where it is: the tables are sized at create)
+static int32_t group_table_upload(vox_stream_group* g, int member, int q0, int q1) {
+    if (q1 <= q0) return VOX_OK;
+    HIPCHK(hipMemcpyAsync(g->d_tab + (size_t)member * g->pool.max_pages + q0, g->pool.mem[(size_t)member].tab.data() + q0, (size_t)(q1 - q0) * 4, hipMemcpyHostToDevice, g->ctx->stream));
+    return VOX_OK;
+}
 // the member leaves its rate: its input ring and its reference to the rate's matrix go (the matrix with its last reference).  The caller has synchronised.
 static void group_member_drop_rate(vox_stream_group* g, int i) {
     GroupMember& me = g->mem[i];
@@ -5018,6 +5040,20 @@ static int32_t group_upload_members(vox_stream_group* g) {      // after a descr
     return VOX_OK;
 }
 static int32_t group_member_seed(vox_stream_group* g, int i) {
+    if (g->paged) {      // every page the member holds goes back, the prefix rows go into fresh ones (the top of the stack: the pages just returned)
+        const vox_model_cfg& c = g->m->cfg; GroupMember& me = g->mem[i]; int q0, q1, t0, t1;
+        ARGCHK(g->pool.held(i) + g->pool.n_free() >= (g->g.PC + g->pool.page_rows - 1) / g->pool.page_rows, "member %d: the pool has no pages for the seed", i);
+        g->pool.release_all(i, &q0, &q1);
+        if (!g->pool.take(i, g->g.PC, &t0, &t1)) return fail(VOX_ERR_INVALID, "internal: member %d: no pool pages for the seed", i);
+        VOXCHK(stream_seed(g->m, g->t_embed.data(), g->g.RC, g->g.PC, g->g.cap, g->h_mem[i].kring, g->h_mem[i].vring, nullptr, g->h_mem[i].tokens, g->h_mem[i].state, me.h_state,
+                           [&]() -> int32_t {
+                               VOXCHK(group_table_upload(g, i, 0, std::max(q1, t1)));
+                               HIPCHK(launch_stream_pages_seed(g->m->pfx.dec_k, g->m->pfx.dec_v, c.dec_layers, c.dec_kv_heads, g->g.PC, c.dec_head_dim, g->d_tab + (size_t)i * g->pool.max_pages,
+                                                               g->pool.shift, g->layer_stride, g->dec_k, g->dec_v, g->ctx->stream));
+                               return VOX_OK; }));
+        me.feed.restart(g->g.PC); me.steps = 0; me.sc.host.clear(); me.al.restart();
+        return VOX_OK;
+    }
     vox_cache view; view.m = g->m; view.ctx = g->ctx; view.k = g->dec_k + (size_t)i * g->seq_stride; view.v = g->dec_v + (size_t)i * g->seq_stride; view.max_seq = g->g.max_pos;
     view.layer_stride = g->layer_stride;      // the member's slice of the slab, seen as a cache whose layers lie layer_stride apart
     GroupMember& me = g->mem[i];
@@ -5033,11 +5069,12 @@ static void group_release(vox_stream_group* g) {
     for (GroupMember& me : g->mem) { if (me.sc.dev) (void)hipFree(me.sc.dev); if (me.al.dev) (void)hipFree(me.al.dev); }
     for (size_t i = 0; i < g->mem.size(); i++) group_member_drop_rate(g, (int)i);
     for (void* p : {(void*)g->keep.p, (void*)g->d_ingest, (void*)g->s16_stage, (void*)g->kring, (void*)g->vring, (void*)g->dec_k, (void*)g->dec_v, (void*)g->samples, (void*)g->ws, (void*)g->tokens, (void*)g->state, (void*)g->d_mem, (void*)g->d_order,
-                    (void*)g->qkv, (void*)g->att, (void*)g->logits, (void*)g->ssq, (void*)g->xf1, (void*)g->xf2, (void*)g->xf3}) if (p) (void)hipFree(p);
+                    (void*)g->qkv, (void*)g->att, (void*)g->logits, (void*)g->ssq, (void*)g->xf1, (void*)g->xf2, (void*)g->xf3, (void*)g->d_tab}) if (p) (void)hipFree(p);
     delete g;
 }
-extern "C" int32_t vox_stream_group_create_rates(vox_model* m, const float* t_embed, int32_t n_members, const float* gains, const uint32_t* rates, int32_t enc_capacity_rows,
-                                                 int32_t max_positions, vox_stream_group** out) {
+// page_rows < 0: a slab group (pool_pages unread); else a paged one (0: the default page / the default pool)
+static int32_t group_create(vox_model* m, const float* t_embed, int32_t n_members, const float* gains, const uint32_t* rates, int32_t enc_capacity_rows,
+                            int32_t max_positions, int32_t page_rows, int32_t pool_pages, vox_stream_group** out) {
     ARGCHK(n_members >= 1 && n_members <= GROUP_MAX, "n_members %d out of range (1..%d)", n_members, GROUP_MAX); ARGCHK(m && t_embed && out, "null argument");
     for (int i = 0; gains && i < n_members; i++) ARGCHK(std::isfinite(gains[i]), "gain of member %d is not finite", i);
     for (int i = 0; rates && i < n_members; i++) {      // every rate is checked before anything is allocated
@@ -5046,23 +5083,40 @@ extern "C" int32_t vox_stream_group_create_rates(vox_model* m, const float* t_em
     }
     VOXCHK(ctx_bind(m->ctx));
     const vox_model_cfg& c = m->cfg; vox_ctx* cx = m->ctx; hipStream_t s = cx->stream;
-    StreamGeom sg; VOXCHK(stream_geometry(m, enc_capacity_rows, max_positions, GROUP_DEFAULT_POSITIONS, &sg));
+    const bool paged = page_rows >= 0;
+    StreamGeom sg; VOXCHK(stream_geometry(m, enc_capacity_rows, max_positions, paged ? INT32_MAX : GROUP_DEFAULT_POSITIONS, &sg));      // (paged, 0: the session limit)
+    if (paged) {
+        if (page_rows == 0) page_rows = PAGE_ROWS_DEFAULT;
+        ARGCHK(page_rows_ok(page_rows), "page_rows %d is not a power of two in %d..%d", page_rows, PAGE_ROWS_MIN, PAGE_ROWS_MAX);
+        const int seed = (sg.PC + page_rows - 1) / page_rows, most = (sg.max_pos + page_rows - 1) / page_rows;
+        ARGCHK(pool_pages >= 0, "pool_pages %d is negative", pool_pages);
+        if (pool_pages == 0) pool_pages = n_members * std::min(most, std::max(seed, (GROUP_DEFAULT_POSITIONS + page_rows - 1) / page_rows));      // the default slab's memory
+        ARGCHK(pool_pages >= n_members * seed, "a pool of %d pages cannot hold the seeds of %d members (%d pages each)", pool_pages, n_members, seed);
+        ARGCHK(pool_pages <= n_members * most, "a pool of %d pages is more than %d members of %d positions can hold (%d)", pool_pages, n_members, sg.max_pos, n_members * most);
+    }
     if (!batch_xf_ok(m)) return fail(VOX_ERR_UNSUPPORTED, "a stream group's decode step runs on the tile-ordered Q4 weights, which this model does not have");
     VOXCHK(enc_stream_rope_ensure(m));
     vox_stream_group* g = new vox_stream_group(); g->m = m; g->ctx = cx; g->t_embed.assign(t_embed, t_embed + c.dec_dim); g->n = n_members; g->g = sg;
     const size_t N = (size_t)n_members; const int D = c.dec_dim, QD = c.dec_heads * c.dec_head_dim, W = QD + 2 * c.dec_kv_heads * c.dec_head_dim, maxp = sg.max_pos;
     g->ring_layer = (size_t)c.enc_heads * sg.cap * c.enc_head_dim; g->ring_member = (size_t)c.enc_layers * g->ring_layer;
     g->seq_stride = (size_t)c.dec_kv_heads * maxp * c.dec_head_dim; g->layer_stride = N * g->seq_stride;
+    if (paged) {
+        g->paged = true; g->pool.init(n_members, page_rows, c.dec_window, pool_pages, maxp);
+        g->page_floats = (size_t)c.dec_kv_heads * page_rows * c.dec_head_dim; g->seq_stride = g->page_floats; g->layer_stride = (size_t)pool_pages * g->page_floats;
+    }
     const size_t ws_b = stream_ws_carve(m, n_members, nullptr, nullptr) * 4, slab_b = (size_t)c.dec_layers * g->layer_stride * 4;
     hipError_t e = hipSuccess;
     auto A = [&](void** q, size_t nb, bool zero) { if (e == hipSuccess) { e = hipMalloc(q, nb); if (e == hipSuccess) { g->bytes += nb; if (zero) e = hipMemsetAsync(*q, 0, nb, s); } } };
     A((void**)&g->kring, N * g->ring_member * 4, false); A((void**)&g->vring, N * g->ring_member * 4, false); A((void**)&g->dec_k, slab_b, true); A((void**)&g->dec_v, slab_b, true);
     A((void**)&g->samples, N * STREAM_SAMPLE_RING * 4, true); A((void**)&g->ws, ws_b, true); A((void**)&g->tokens, N * (maxp + 2) * 4, true); A((void**)&g->state, N * sizeof(int) * STRM_WORDS, true);
-    A((void**)&g->d_mem, N * sizeof(StreamMember), true); A((void**)&g->d_order, 3 * GROUP_MAX * 4, true); A((void**)&g->d_ingest, sizeof(GroupIngest), true);
+    A((void**)&g->d_mem, N * sizeof(StreamMember), true); A((void**)&g->d_order, 5 * GROUP_MAX * 4, true);
+    if (paged) A((void**)&g->d_tab, N * (size_t)g->pool.max_pages * 4, false); A((void**)&g->d_ingest, sizeof(GroupIngest), true);
     A((void**)&g->qkv, (size_t)GROUP_MAX * W * 4, true); A((void**)&g->att, (size_t)GROUP_MAX * QD * 4, true); A((void**)&g->logits, (size_t)GROUP_MAX * c.vocab * 4, true);
     A((void**)&g->ssq, (size_t)q4_skinny_resid_xf_parts(D) * 16 * 4, true); A((void**)&g->xf1, xf_bytes(D), true); A((void**)&g->xf2, xf_bytes(QD), true); A((void**)&g->xf3, xf_bytes(c.dec_ffn), true);
     if (e != hipSuccess) { (void)hipGetLastError(); group_release(g); return fail(VOX_ERR_HIP, "allocating the stream group's device state failed: %s", hipGetErrorString(e)); }
-    g->d_pos = g->d_order + GROUP_MAX; g->d_kv_row = g->d_pos + GROUP_MAX;
+    g->d_pos = g->d_order + GROUP_MAX; g->d_kv_row = g->d_pos + GROUP_MAX; g->d_kv_page = g->d_kv_row + GROUP_MAX; g->d_kv_in = g->d_kv_page + GROUP_MAX;
+    if (paged) e = hipMemsetAsync(g->d_tab, 0xff, N * (size_t)g->pool.max_pages * 4, s);      // every entry -1
+    if (e != hipSuccess) { (void)hipGetLastError(); group_release(g); return fail(VOX_ERR_HIP, "initialising the stream group's page table failed: %s", hipGetErrorString(e)); }
     g->h_mem.resize(N); g->mem.resize(N);
     for (size_t i = 0; i < N; i++) {
         StreamMember& me = g->h_mem[i]; me = StreamMember{};
@@ -5075,6 +5129,36 @@ extern "C" int32_t vox_stream_group_create_rates(vox_model* m, const float* t_em
     for (int i = 0; rates && i < n_members && r == VOX_OK; i++) r = group_member_set_rate(g, i, rates[i]);
     if (r != VOX_OK) { group_release(g); return r; }
     *out = g; return VOX_OK;
+}
+extern "C" int32_t vox_stream_group_create_rates(vox_model* m, const float* t_embed, int32_t n_members, const float* gains, const uint32_t* rates, int32_t enc_capacity_rows,
+                                                 int32_t max_positions, vox_stream_group** out) {
+    return group_create(m, t_embed, n_members, gains, rates, enc_capacity_rows, max_positions, -1, 0, out);
+}
+extern "C" int32_t vox_stream_group_create_paged(vox_model* m, const float* t_embed, int32_t n_members, const float* gains, const uint32_t* rates, int32_t enc_capacity_rows,
+                                                 int32_t max_positions, int32_t page_rows, int32_t pool_pages, vox_stream_group** out) {
+    ARGCHK(page_rows >= 0, "page_rows %d is negative", page_rows);
+    return group_create(m, t_embed, n_members, gains, rates, enc_capacity_rows, max_positions, page_rows, pool_pages, out);
+}
+extern "C" int32_t vox_stream_group_pool(const vox_stream_group* g, int64_t out[4], int32_t* held_or_null) {
+    ARGCHK(g && out, "null argument");
+    if (!g->paged) return fail(VOX_ERR_UNSUPPORTED, "a slab group has no page pool (vox_stream_group_create_paged makes a paged one)");
+    out[0] = g->pool.page_rows; out[1] = g->pool.pool_pages; out[2] = g->pool.n_free(); out[3] = g->pool.peak;
+    for (int i = 0; held_or_null && i < g->n; i++) held_or_null[i] = g->pool.held(i);
+    return VOX_OK;
+}
+extern "C" int32_t vox_stream_group_pages_for(int64_t positions, int32_t page_rows, int32_t window, int32_t* first_page, int32_t* n_pages) {
+    ARGCHK(first_page && n_pages, "null argument"); ARGCHK(positions >= 0 && positions <= ((int64_t)1 << 30), "positions %lld out of range", (long long)positions);
+    ARGCHK(page_rows_ok(page_rows), "page_rows %d is not a power of two in %d..%d", page_rows, PAGE_ROWS_MIN, PAGE_ROWS_MAX); ARGCHK(window >= -1, "window %d: -1 is none", window);
+    int first, n; pages_held(positions, page_rows, window, &first, &n); *first_page = first; *n_pages = n;
+    return VOX_OK;
+}
+extern "C" int32_t vox_debug_stream_group_pages(const vox_stream_group* g, int32_t member, int32_t* out, int32_t cap, int32_t* n) {
+    ARGCHK(g && n && (out || cap == 0) && cap >= 0, "bad argument"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1);
+    if (!g->paged) return fail(VOX_ERR_UNSUPPORTED, "a slab group has no pages");
+    const PagePool::Member& me = g->pool.mem[(size_t)member];
+    for (int q = me.first; q < me.end && q - me.first < cap; q++) out[q - me.first] = me.tab[(size_t)q];
+    *n = me.end - me.first;
+    return VOX_OK;
 }
 extern "C" int32_t vox_stream_group_create(vox_model* m, const float* t_embed, int32_t n_members, const float* gains, int32_t enc_capacity_rows, int32_t max_positions,
                                            vox_stream_group** out) {
@@ -5114,7 +5198,12 @@ static int32_t group_round(vox_stream_group* g, const StreamWs& w, int n_r) {
     VOXCHK(stream_encode_round(m, w, r, nullptr, nullptr));
     XfBufs xb{}; xb.h = w.h; xb.qkv = g->qkv; xb.att = g->att; xb.logits = g->logits; xb.ssq = g->ssq; xb.xf1 = g->xf1; xb.xf2 = g->xf2; xb.xf3 = g->xf3;
     xb.k = g->dec_k; xb.v = g->dec_v; xb.layer_stride = g->layer_stride; xb.seq_stride = g->seq_stride; xb.max_seq = g->g.max_pos; xb.pos = g->d_pos; xb.kv_row = g->d_kv_row;
-    HIPCHK(launch_stream_group_embed(m->tok.w, g->d_mem, g->d_order, n_r, w.arow, c.dec_dim, w.h, g->xf1, m->dec[0].attn_norm, g->ssq, g->d_pos, g->d_kv_row, s));
+    StreamPages pg{g->d_tab, g->pool.max_pages, g->pool.shift, g->d_kv_page, g->d_kv_in};
+    if (g->paged) {
+        xb.page_tab = g->d_tab; xb.page_tab_stride = g->pool.max_pages; xb.page_shift = g->pool.shift; xb.page_floats = (long)g->page_floats; xb.kv_page = g->d_kv_page; xb.kv_in = g->d_kv_in;
+        xb.score_rows = c.dec_window >= 0 ? std::min(g->g.max_pos, c.dec_window + 1) : g->g.max_pos;
+    }
+    HIPCHK(launch_stream_group_embed(m->tok.w, g->d_mem, g->d_order, n_r, w.arow, c.dec_dim, w.h, g->xf1, m->dec[0].attn_norm, g->ssq, g->d_pos, g->d_kv_row, s, g->paged ? &pg : nullptr));
     VOXCHK(xf_chain(m, xb, 0, n_r, 0, 0, true, 0, s));
     HIPCHK(launch_stream_group_advance(g->logits, c.vocab, g->d_mem, g->d_order, n_r, R, 4 * R, g->g.cap, s));
     if (g->n_scored > 0) HIPCHK(launch_stream_score(g->logits, c.vocab, g->d_mem, g->d_order, n_r, VOX_PREFIX_TOKENS, s));      // slots of unscored members return at once
@@ -5129,7 +5218,7 @@ struct GroupFeed { int member; const void* p; FeedPlan plan; };      // one entr
 struct GroupCall { std::vector<GroupFeed> fs; int32_t mem_kind = VOX_MEM_HOST; bool s16 = false, staged = false, any_rate = false, peek = false; };      // staged: host 16-bit samples pass through g->s16_stage; peek: every entry is planned as a finish (vox_stream_group_peek)
 typedef std::vector<std::pair<int, int>> GroupDue;      // (ticks due in this pass, member)
 static int32_t group_plan_entries(const vox_stream_group* g, const vox_stream_feed* feeds, int32_t n_feeds, GroupCall* call) {
-    unsigned seen = 0; call->fs.reserve((size_t)n_feeds);
+    unsigned seen = 0; int pages = 0; call->fs.reserve((size_t)n_feeds);
     for (int k = 0; k < n_feeds; k++) {
         const vox_stream_feed& f = feeds[k];
         ARGCHK(f.member >= 0 && f.member < g->n, "entry %d: member %d out of range (0..%d)", k, f.member, g->n - 1);
@@ -5142,6 +5231,29 @@ static int32_t group_plan_entries(const vox_stream_group* g, const vox_stream_fe
         VOXCHK(feed_plan(g->mem[f.member].feed, g->m->cfg.reshape_factor, g->g.left, g->g.max_pos, f.n_samples, call->peek || f.finish != 0, f.cap, who, &gf.plan));
         call->any_rate |= g->mem[f.member].rate >= 0;
         call->fs.push_back(gf);
+        if (g->paged) {      // the logical pages the entry's ticks enter: all of the call's are there, or the call is refused
+            const int need = g->pool.need(f.member, gf.plan.target); pages += need;
+            ARGCHK(pages <= g->pool.n_free(), "entry %d: member %d: the call needs %d new pages of the pool (this member %d), %d are free (a reset returns a member's pages)", k, f.member,
+                   pages, need, g->pool.n_free());
+        }
+    }
+    return VOX_OK;
+}
+// behind every check of a paged group's call: the entries' pages are taken, in entry order, and their table entries go up in front of the call's rounds
+static int32_t group_take_pages(vox_stream_group* g, const GroupCall& call) {
+    for (const GroupFeed& e : call.fs) {
+        int q0, q1;
+        if (!g->pool.take(e.member, e.plan.target, &q0, &q1)) return fail(VOX_ERR_INVALID, "internal: member %d: the planned pages are not free", e.member);
+        VOXCHK(group_table_upload(g, e.member, q0, q1));
+    }
+    return VOX_OK;
+}
+// behind a committed call: the pages below each fed member's window go back (no later step reads them); their entries become -1 on the device as well, behind the
+// call's rounds in stream order
+static int32_t group_release_pages(vox_stream_group* g, const GroupCall& call) {
+    for (const GroupFeed& e : call.fs) {
+        int q0, q1; g->pool.release_below_window(e.member, g->mem[e.member].feed.pos, &q0, &q1);
+        VOXCHK(group_table_upload(g, e.member, q0, q1));
     }
     return VOX_OK;
 }
@@ -5255,13 +5367,20 @@ static int32_t group_run(vox_stream_group* g, vox_stream_feed* feeds, int32_t n_
     if (m->pw_pend_rows > 0) VOXCHK(pw_sync(m));
     VOXCHK(vox_model_set_t_embed(m, g->t_embed.data()));
     for (GroupFeed& e : call.fs) g->mem[e.member].feed.n_pushed += (int64_t)e.plan.n;
-    if (!call.peek) return group_body(g, feeds, call, nullptr, nullptr);
+    PagePool::Mark pool_was; std::vector<int> took;
+    if (g->paged) { if (call.peek) { pool_was = g->pool.mark(); for (const GroupFeed& e : call.fs) took.push_back(e.member); } VOXCHK(group_take_pages(g, call)); }
+    if (!call.peek) { VOXCHK(group_body(g, feeds, call, nullptr, nullptr)); return g->paged ? group_release_pages(g, call) : VOX_OK; }
     // a peek: the peeking members are the ring keep's slots, their numbers the first 16 ints of the save area
     const StreamKeepParams keep = ring_keep(c, g->d_mem, reinterpret_cast<const int*>(g->keep.p), n, keep_rows, g->g.cap, g->keep.p + GROUP_MAX);
     std::vector<GroupMark> was; for (const GroupFeed& e : call.fs) was.push_back(GroupMark{g->mem[e.member].feed.mark(), g->mem[e.member].steps});
     const int32_t r = group_body(g, feeds, call, &keep, peek_scores);
     if (r != VOX_OK) { (void)launch_stream_keep(keep, 1, s); (void)hipStreamSynchronize(s); g->orders.clear(); g->ingests.clear(); }      // a failed tail is taken back as well
     for (int k = 0; k < n; k++) { GroupMember& me = g->mem[call.fs[(size_t)k].member]; me.feed.rewind(was[(size_t)k].feed); me.steps = was[(size_t)k].steps; }
+    if (g->paged) {      // the tail's pages go back: the pool, the tables and the peak are what they were (the device entries too, behind the tail in stream order)
+        std::vector<int> ends; for (int member : took) ends.push_back(g->pool.mem[(size_t)member].end);
+        g->pool.undo(pool_was, took);
+        for (size_t k = 0; k < took.size(); k++) (void)group_table_upload(g, took[k], g->pool.mem[(size_t)took[k]].end, ends[k]);
+    }
     return r;
 }
 extern "C" int32_t vox_stream_group_advance(vox_stream_group* g, vox_stream_feed* feeds, int32_t n_feeds, int32_t mem_kind) {

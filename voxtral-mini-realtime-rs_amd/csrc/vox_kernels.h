@@ -32,7 +32,8 @@ enum WFmt { WFMT_Q4_0 = 0, WFMT_BF16 = 1, WFMT_BF16X2 = 2, WFMT_F32 = 3 };
 // plane [N][K] (decode GEMV, embedding lookup), qs / sc = bf16 hi / lo planes (w ~= hi + lo to 2^-17; the MFMA GEMMs for > 4 rows).   // BF16X2: f32 weights as two dense bf16 planes, qs = hi [N][K], sc = lo [N][K] (conv stem)
 
 enum Epi { EPI_STORE = 0, EPI_RESID = 1, EPI_SWIGLU = 2, EPI_ROPE_KV = 3, EPI_ARGMAX = 4, EPI_GELU = 5, EPI_SWIGLU_XF = 6, EPI_RESID_XF = 7,
-           EPI_ROPE_ROWS = 8 };      // launch_q4_gemm only: store, with RoPE (interleaved pairs, rope.rs:77-141) on the first n_q columns, row m at position pos[m] (or m % rope_seq_rows, or m) -- the encoder's q|k|v operator
+           EPI_ROPE_ROWS = 8,        // launch_q4_gemm only: store, with RoPE (interleaved pairs, rope.rs:77-141) on the first n_q columns, row m at position pos[m] (or m % rope_seq_rows, or m) -- the encoder's q|k|v operator
+           EPI_ROPE_KV_PAGED = 9 };  // inside launch_q4_skinny only: EPI_ROPE_KV with GemmParams::kv_pos set runs as this instantiation
 // (M <= 16 only) _SWIGLU_XF: SwiGLU written as XF planes; _RESID_XF: out = acc + resid as f32 AND as XF planes of out * xf_w (* xf_w2) plus
 // per-workgroup partial sums of squares -- the next RMSNorm is folded into its producer and its consumer (GemmParams::ssq_part)
 enum Pro { PRO_NONE = 0, PRO_RMS = 1, PRO_RMS_MUL = 2,      // RMS_MUL: RMSNorm then * mul (the cached Ada scale)
@@ -83,6 +84,8 @@ struct GemmParams {
     // all at position pos[m] of sequence m's cache slice
     const int* pos; const float* rope_cos; const float* rope_sin; int hd, n_q, n_kv; float* kc; float* vc; long kv_seq_stride; int kv_head_stride;
     const int* kv_row;    // EPI_ROPE_KV, optional: row m writes into cache slice kv_row[m] instead of slice m (continuous batching: a SLOT of the step decodes whichever utterance it currently holds)
+    const int* kv_pos;    // EPI_ROPE_KV, optional (the <= 16-row XF form alone, an epilogue instantiation of its own): row m's row INSIDE its slice; null: pos[m], the address of every contiguous cache.  A paged cache
+                          // (a paged stream group) passes kv_row[m] = the physical page, kv_seq_stride = the floats of a page, kv_head_stride = page_rows * hd, kv_pos[m] = pos[m] % page_rows
     int tl_slot;          // timeline slot (measurement builds, -DVOX_TIMELINE)
     // split-K (q4_gemm_kernel only, EPI_STORE): blockIdx.z = K slice; slice z writes its partial product to out + z * M * out_stride (bias in slice 0).
     // The consumer (launch_rms_norm_sumk) adds the slices in a fixed order -- for few-column GEMMs (the encoder's N = 1280 w2: 40 K-steps per workgroup)
@@ -161,18 +164,26 @@ struct AttnParams {
     // prefill, one sequence, MFMA kernel only (attn_prefill_prefix_ok): a second K / V segment in FRONT of k / v.  Key index j < prefix_len is row j of prefix_k / prefix_v
     // ([kvh * prefix_head_stride + j * prefix_row_stride + d]); j >= prefix_len is row j - prefix_len of k / v.  offset = prefix_len, kv_len = prefix_len + M.
     const float* prefix_k; const float* prefix_v; int prefix_len, prefix_row_stride, prefix_head_stride;
+    // paged decode (launch_attn_decode_paged): k / v = the layer's page pool [page][kv head][page_rows][hd] (kv_head_stride = page_rows * hd, kv_row_stride = hd,
+    // page_floats per page); page_tab[kv_row[s] * page_tab_stride + q] = the physical page of logical page q (rows q << page_shift ..) of sequence s, read only for the
+    // pages of the window; score_rows: LDS score rows per query head, >= the most keys a query attends (min(max positions, window + 1))
+    const int* page_tab; int page_tab_stride, page_shift, score_rows; long page_floats;
 };
 hipError_t launch_attn_prefill(const AttnParams& p, int hd, hipStream_t s, int n_seq = 1);     // M > 1, causal (+window)
 bool attn_prefill_prefix_ok(const AttnParams& p, int hd, int n_seq);     // may launch_attn_prefill take p's two K / V segments (prefix_len > 0)?
 bool attn_prefill_small_ok(const AttnParams& p, int hd, int n_seq);      // will launch_attn_prefill take the short-sequence kernel (<= 48 rows from position 0, f32; may write XF tiles: p.out_xf_tiles)?
 hipError_t launch_attn_decode(const AttnParams& p, int hd, int max_seq, hipStream_t s, int n_seq = 1);  // M == 1 per sequence
+// the same attention with K / V read through a page table: the GQA form where n_heads == 4 n_kv_heads and hd == 128, else the per-head form; a row has launch_attn_decode's bits
+hipError_t launch_attn_decode_paged(const AttnParams& p, int hd, hipStream_t s, int n_seq);
 // single sequence: attention + the wo linear in one launch; acc[wo.N] (int64, zero on entry) receives the product in 2^-32 fixed point (consumer: PRO_RMS_MUL_SUM)
 bool attn_wo_supported(const AttnParams& p, const Q4W& wo, int hd, int max_seq);
 hipError_t launch_attn_wo(const AttnParams& p, const Q4W& wo, long long* acc, int max_seq, hipStream_t s);
 // host-side launch counts of the attention kernels and of the single-stream decode engine, by form (vox_debug_attn_launches: tests assert which path a call took);
 // behind them, in slots of their own, the two resampling ingest kernels of the live sessions (a group's pass-wide one, a solo stream's)
 enum AttnForm { ATTN_FORM_PREFILL_SMALL, ATTN_FORM_PREFILL_MFMA, ATTN_FORM_PREFILL_F32, ATTN_FORM_DECODE, ATTN_FORM_DECODE_SPEC, ATTN_FORM_DECODE_GQA, ATTN_FORM_WO,
-                ATTN_FORM_ENGINE, ATTN_FORM_STREAM_RING, ATTN_FORM_GROUP_RESAMPLE, ATTN_FORM_STREAM_RESAMPLE, ATTN_FORM_COUNT };
+                ATTN_FORM_ENGINE, ATTN_FORM_STREAM_RING, ATTN_FORM_GROUP_RESAMPLE, ATTN_FORM_STREAM_RESAMPLE,
+                ATTN_FORM_DECODE_PAGED, ATTN_FORM_DECODE_GQA_PAGED,      // the paged decode forms (launch_attn_decode_paged), behind every earlier slot
+                ATTN_FORM_COUNT };
 void attn_form_note(AttnForm f);
 void attn_form_counts(unsigned long long out[ATTN_FORM_COUNT]);
 // host-side launch counts of the linear kernels, by form (vox_debug_gemm_launches: tests assert which kernel a shape ran; counters only, nothing is dispatched by them).
@@ -434,8 +445,13 @@ hipError_t launch_stream_advance(const float* part_val, const int* part_idx, int
 // ---- the decode half of a group round (vox_stream_group): n <= 16 rows, row r = session order[r], through xf_chain.
 // input rows: h[r] = audio[r] + embed(tokens[STRM_POS]) as f32, as layer 0's XF planes of h * xf_w with the row's sum of squares (what launch_argmax_embed_batch forms),
 // pos[r] = STRM_POS and kv_row[r] = order[r]: the positions and cache slices xf_chain reads
+// pages (a paged group): also page_out[r] = the table entry of the row's position (tab[order[r] * tab_stride + pos >> shift]) and in_page_out[r] = pos % page_rows
+struct StreamPages { const int* tab; int tab_stride, shift; int* page_out; int* in_page_out; };
 hipError_t launch_stream_group_embed(Q4W tok, const StreamMember* mem, const int* order, int n, const float* audio, int D, float* h, uint16_t* xf, const float* xf_w,
-                                     float* ssq_out, int* pos, int* kv_row, hipStream_t s);
+                                     float* ssq_out, int* pos, int* kv_row, hipStream_t s, const StreamPages* pages = nullptr);
+// a paged member's seed: rows 0 .. rows-1 of src_k / src_v [layers][kv_heads][rows][hd] into the pages tab[0 ..] of the pool (layers layer_stride floats apart)
+hipError_t launch_stream_pages_seed(const float* src_k, const float* src_v, int layers, int kv_heads, int rows, int hd, const int* tab, int page_shift, size_t layer_stride,
+                                    float* pool_k, float* pool_v, hipStream_t s);
 // tokens[STRM_POS + 1] = argmax of logits row r (argmax_take / block_argmax: the rule of every decode form), the row copied to the session's tap when one is armed,
 // then the session's state advances by one tick as launch_stream_advance moves it
 hipError_t launch_stream_group_advance(const float* logits, int vocab, const StreamMember* mem, const int* order, int n, int enc_rows, int frames, int cap, hipStream_t s);

@@ -226,8 +226,21 @@ hipError_t launch_q4_dequant(Q4W w, float* out, hipStream_t s) {
 // fused Q4 GEMV
 // ------------------------------------------------------------------------------------------------
 struct NoHook { __device__ __forceinline__ void operator()() const {} };
-template <int HD, bool NT, bool LATE_V, bool SPEC = false, class Hook = NoHook>
-__device__ __forceinline__ float4 attn_decode_core(const float* __restrict__ qh, const float* __restrict__ kb, const float* __restrict__ vb, int kv_row_stride,
+// where a decode attention finds cache row j of its KV head: the one place attn_decode_core and attn_decode_gqa_kernel form a K / V address.  Contiguous rows (a cache, a
+// slab slice): base + j * stride.  Paged rows (a paged stream group's pool): through the sequence's page table, staged in LDS by the kernel
+struct KvRowsFlat {
+    const float* kb; const float* vb; int stride;
+    __device__ __forceinline__ const float* k(int j) const { return kb + (size_t)j * stride; }
+    __device__ __forceinline__ const float* v(int j) const { return vb + (size_t)j * stride; }
+};
+struct KvRowsPaged {      // kb / vb: the layer's pool + the KV head's offset inside a page; tab[i]: the physical page of logical page q0 + i (LDS)
+    const float* kb; const float* vb; const int* tab; int q0, shift, mask, stride; size_t page_floats;
+    __device__ __forceinline__ size_t at(int j) const { return (size_t)tab[(j >> shift) - q0] * page_floats + (size_t)(j & mask) * stride; }
+    __device__ __forceinline__ const float* k(int j) const { return kb + at(j); }
+    __device__ __forceinline__ const float* v(int j) const { return vb + at(j); }
+};
+template <int HD, bool NT, bool LATE_V, bool SPEC = false, class Hook = NoHook, class Rows = KvRowsFlat>
+__device__ __forceinline__ float4 attn_decode_core(const float* __restrict__ qh, const Rows rows,
                                                    int pos, int window, float* __restrict__ sc, float* __restrict__ red, float4* __restrict__ osum, int tl_slot, int tlw,
                                                    int spec_rows = 0, Hook after_issue = Hook());
 
@@ -1119,6 +1132,9 @@ template <int NTW, int EPI, int TILED, int XIN, int PRO, int STEPS = 0>
 __global__ __launch_bounds__(NTW == 3 ? 256 : 512, NTW == 3 ? 3 : 1) void q4_skinny_kernel(const GemmParams p) {
     extern __shared__ __attribute__((aligned(16))) float sred[];      // [KS][NTW][64][4]
     __shared__ float s_rstd[16]; __shared__ float s_pp[32 * 16];
+    // EPI_ROPE_KV_PAGED: EPI_ROPE_KV with the row inside the cache slice taken from p.kv_pos (a paged cache) -- an instantiation of its own, so that the epilogue of
+    // every contiguous cache stays the code it was
+    constexpr bool KVP = EPI == EPI_ROPE_KV_PAGED, ROPE_KV = EPI == EPI_ROPE_KV || KVP;
     const int nb = p.w.nb, N = p.w.N, M = p.M, nq = nb >> 2;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, KS = blockDim.x >> 6;
     const int g = lane >> 4, li = lane & 15;
@@ -1200,7 +1216,7 @@ __global__ __launch_bounds__(NTW == 3 ? 256 : 512, NTW == 3 ? 3 : 1) void q4_ski
     // branch around a load makes hipcc drain vmcnt).  vmcnt retires IN ORDER and these words were written by the previous launches on other XCDs
     // (memory round trips): the straight-line path requests them BEHIND its first K step's operands, so that step does not wait for them.
     float pv[12]; const int prow = tid & 15, pch = tid >> 4, nch = blockDim.x >> 4;
-    float pre_res[4] = {0.f, 0.f, 0.f, 0.f}; float pre_xw = 0.f; int pre_pos[4] = {0, 0, 0, 0}; int pre_row[4] = {0, 0, 0, 0};
+    float pre_res[4] = {0.f, 0.f, 0.f, 0.f}; float pre_xw = 0.f; int pre_pos[4] = {0, 0, 0, 0}; int pre_row[4] = {0, 0, 0, 0}; int pre_kvp[4] = {0, 0, 0, 0};
 #define VOX_PRELOADS                                                                                       \
     {                                                                                                      \
         if (PRO) {                                                                                         \
@@ -1215,9 +1231,10 @@ __global__ __launch_bounds__(NTW == 3 ? 256 : 512, NTW == 3 ? 3 : 1) void q4_ski
             _Pragma("unroll") for (int r = 0; r < 4; r++) pre_res[r] = p.resid[(size_t)min(4 * g + r, M - 1) * p.resid_stride + n0_]; \
         }                                                                                                  \
         if (EPI == EPI_RESID_XF) { pre_xw = p.xf_w[n0_]; if (p.xf_w2) pre_xw *= p.xf_w2[n0_]; }            \
-        if (EPI == EPI_ROPE_KV) {                                                                          \
+        if (ROPE_KV) {                                                                                     \
             _Pragma("unroll") for (int r = 0; r < 4; r++) pre_pos[r] = p.pos[min(4 * g + r, M - 1)];       \
             _Pragma("unroll") for (int r = 0; r < 4; r++) pre_row[r] = p.kv_row ? p.kv_row[min(4 * g + r, M - 1)] : min(4 * g + r, M - 1); \
+            if (KVP) { _Pragma("unroll") for (int r = 0; r < 4; r++) pre_kvp[r] = p.kv_pos[min(4 * g + r, M - 1)]; } \
         }                                                                                                  \
     }
     constexpr bool STRAIGHT = STEPS > 0 && TILED && XIN;
@@ -1336,21 +1353,22 @@ __global__ __launch_bounds__(NTW == 3 ? 256 : 512, NTW == 3 ? 3 : 1) void q4_ski
                     const size_t base = ((size_t)((qq * 4 + jj) * 64 + gg * 16 + m)) * 8 + 2 * half + 4 * (tt & 1);
                     *reinterpret_cast<uint32_t*>(p.xf_out + base) = hi; *reinterpret_cast<uint32_t*>(p.xf_out + (size_t)(N >> 7) * 256 * 8 + base) = lo;
                 }
-            } else if (EPI == EPI_ROPE_KV) {
+            } else if (ROPE_KV) {
                 const float other = dpp_mov<0xB1>(v);          // the pair partner (interleaved RoPE pairs, rope.rs:77-141)
                 if (m < M && nok) {
                     const int ps = pre ? pre_pos[r] : p.pos[m], kd = p.n_kv * p.hd;
                     const int cr = pre ? pre_row[r] : (p.kv_row ? p.kv_row[m] : m);      // cache slice of row m
+                    const int cp = KVP ? (pre ? pre_kvp[r] : p.kv_pos[m]) : ps;      // its row inside the slice: the position, or a paged cache's row inside the page
                     if (n < p.n_q + kd) {
                         const int dd = n % p.hd;
                         const size_t ti = (size_t)ps * (p.hd >> 1) + (dd >> 1);
                         const float c = p.rope_cos[ti], sn = p.rope_sin[ti];
                         const float o = (n & 1) ? other * sn + v * c : v * c - other * sn;
                         if (n < p.n_q) p.out[(size_t)m * p.out_stride + n] = o;
-                        else p.kc[(size_t)cr * p.kv_seq_stride + (size_t)((n - p.n_q) / p.hd) * p.kv_head_stride + (size_t)ps * p.hd + dd] = o;
+                        else p.kc[(size_t)cr * p.kv_seq_stride + (size_t)((n - p.n_q) / p.hd) * p.kv_head_stride + (size_t)cp * p.hd + dd] = o;
                     } else {
                         const int vn = n - p.n_q - kd;
-                        p.vc[(size_t)cr * p.kv_seq_stride + (size_t)(vn / p.hd) * p.kv_head_stride + (size_t)ps * p.hd + (vn % p.hd)] = v;
+                        p.vc[(size_t)cr * p.kv_seq_stride + (size_t)(vn / p.hd) * p.kv_head_stride + (size_t)cp * p.hd + (vn % p.hd)] = v;
                     }
                 }
             } else if (m < M && nok) {
@@ -1647,7 +1665,7 @@ hipError_t launch_q4_wide(const GemmParams& p, int epi_stage, hipStream_t s) {  
     const int epi = epi_stage & 0xff; const bool only_gemm = (epi_stage & 0x100) != 0, only_finish = (epi_stage & 0x200) != 0;
     WidePlan pl;
     const int MT = p.wide_mt;
-    if (!p.xf || p.M != 16 * MT || !q4_wide_plan(p.w, MT, epi, &pl)) return hipErrorInvalidValue;
+    if (!p.xf || p.M != 16 * MT || p.kv_pos || !q4_wide_plan(p.w, MT, epi, &pl)) return hipErrorInvalidValue;
     const bool direct = epi == EPI_STORE;
     if (direct) { if (!p.out || !p.ssq_part || p.n_part < 1) return hipErrorInvalidValue; }
     else if (!p.kz_scratch || p.kz_scratch_bytes < q4_wide_planes_bytes(p.w, MT, pl)) return hipErrorInvalidValue;
@@ -2403,6 +2421,7 @@ hipError_t launch_transpose(const float* in, int R, int C, float* out, hipStream
 
 template <int NTW, int TILED>
 static hipError_t skinny_launch_n(const GemmParams& p, int epi, int ks, hipStream_t s) {
+    if (epi == EPI_ROPE_KV && p.kv_pos) epi = EPI_ROPE_KV_PAGED;      // (launch_q4_gemm_epi admits kv_pos with XF input alone)
     dim3 grid((p.w.N + 16 * NTW - 1) / (16 * NTW));
     const size_t lds = (size_t)ks * NTW * 64 * 4 * sizeof(float);
     if (p.xf) {      // fragment-ordered bf16 hi/lo input (batched decode step); tile-ordered weights only
@@ -2415,7 +2434,7 @@ static hipError_t skinny_launch_n(const GemmParams& p, int epi, int ks, hipStrea
 #define VOX_ST(N_, E_, P_, S_) if (NTW == N_ && epi == E_ && (int)pro == P_ && per == S_) { \
             if (E_ == EPI_RESID_XF && (!p.xf_out || !p.xf_w || !p.ssq_out)) return hipErrorInvalidValue; \
             q4_skinny_kernel<N_, E_, 1, 1, P_, S_><<<grid, dim3(64 * ks), lds, s>>>(p); return hipGetLastError(); }
-            VOX_ST(2, EPI_ROPE_KV, 1, 3) VOX_ST(2, EPI_SWIGLU_XF, 1, 6) VOX_ST(1, EPI_SWIGLU_XF, 1, 6) VOX_ST(1, EPI_RESID_XF, 0, 4) VOX_ST(4, EPI_SWIGLU_XF, 1, 6) VOX_ST(1, EPI_RESID_XF, 0, 9) VOX_ST(4, EPI_STORE, 1, 6)
+            VOX_ST(2, EPI_ROPE_KV, 1, 3) VOX_ST(2, EPI_ROPE_KV_PAGED, 1, 3) VOX_ST(2, EPI_SWIGLU_XF, 1, 6) VOX_ST(1, EPI_SWIGLU_XF, 1, 6) VOX_ST(1, EPI_RESID_XF, 0, 4) VOX_ST(4, EPI_SWIGLU_XF, 1, 6) VOX_ST(1, EPI_RESID_XF, 0, 9) VOX_ST(4, EPI_STORE, 1, 6)
 #undef VOX_ST
         }
         if (epi == EPI_RESID_XF) {
@@ -2425,6 +2444,7 @@ static hipError_t skinny_launch_n(const GemmParams& p, int epi, int ks, hipStrea
             switch (epi) {
             case EPI_STORE: q4_skinny_kernel<NTW, EPI_STORE, 1, 1, 1><<<grid, dim3(64 * ks), lds, s>>>(p); break;
             case EPI_ROPE_KV: q4_skinny_kernel<NTW, EPI_ROPE_KV, 1, 1, 1><<<grid, dim3(64 * ks), lds, s>>>(p); break;
+            case EPI_ROPE_KV_PAGED: q4_skinny_kernel<NTW, EPI_ROPE_KV_PAGED, 1, 1, 1><<<grid, dim3(64 * ks), lds, s>>>(p); break;
             case EPI_SWIGLU_XF: q4_skinny_kernel<NTW, EPI_SWIGLU_XF, 1, 1, 1><<<grid, dim3(64 * ks), lds, s>>>(p); break;
             default: return hipErrorInvalidValue;
             }
@@ -2528,6 +2548,7 @@ hipError_t launch_q4_gemm(const GemmParams& p, int epi, hipStream_t s, bool* fus
 static hipError_t launch_q4_gemm_epi(const GemmParams& p, int epi_in, hipStream_t s, bool* fused_rope) {
     int epi = epi_in == EPI_ROPE_ROWS ? EPI_STORE : epi_in;      // (EPI_ROPE_ROWS: only the large-M kernel below takes it; the others store, the caller ropes)
     if (p.w.K % 32 || p.M <= 0) return hipErrorInvalidValue;
+    if (p.kv_pos && !(p.xf && p.M <= 16)) return hipErrorInvalidValue;      // a row inside the slice: q4_skinny_kernel's epilogue alone takes it
     if (p.ksplit > 1 && (p.M <= 48 || p.xf || p.w.nb % 4 || p.w.fmt == WFMT_F32)) return hipErrorInvalidValue;      // split-K exists in q4_gemm_kernel only
     if (p.w.fmt == WFMT_F32) {      // true-f32 dense weights: bf16 hi + lo planes on the matrix cores (3 MFMAs per product, f32-class like the conv stem)
         if (p.xf) return hipErrorInvalidValue;
@@ -3170,8 +3191,8 @@ __device__ __forceinline__ float4 ldf4(const float* p) {
 // that has started to move (j_lo > 0) re-requests the rows (uniform branch).
 // after_issue(): called once the q / K (/ V) requests of the first NPRE*32 keys are out -- a caller's own loads placed there are YOUNGER in the
 // in-order vmcnt queue, so the waits for K and V do not wait for them (attn_wo_kernel: its block of wo).
-template <int HD, bool NT, bool LATE_V, bool SPEC, class Hook>
-__device__ __forceinline__ float4 attn_decode_core(const float* __restrict__ qh, const float* __restrict__ kb, const float* __restrict__ vb, int kv_row_stride,
+template <int HD, bool NT, bool LATE_V, bool SPEC, class Hook, class Rows>
+__device__ __forceinline__ float4 attn_decode_core(const float* __restrict__ qh, const Rows rows,
                                                    int pos_in, int window, float* __restrict__ sc, float* __restrict__ red, float4* __restrict__ osum, int tl_slot, int tlw,
                                                    int spec_rows, Hook after_issue) {
     // Latency-bound (a few hundred KB of K/V per layer): the structure maximises independent loads in flight.
@@ -3198,14 +3219,14 @@ __device__ __forceinline__ float4 attn_decode_core(const float* __restrict__ qh,
 #define VOX_KPRE(ROW_)                                                                                        \
     _Pragma("unroll") for (int u = 0; u < NPRE; u++) {                                                        \
         const int jc = (ROW_);                                                                                \
-        const float* kr = kb + (size_t)jc * kv_row_stride + part * PER;                                       \
+        const float* kr = rows.k(jc) + part * PER;                                                            \
         _Pragma("unroll") for (int e = 0; e < PER / 4; e++) kpre[u][e] = ldf4<NT>(kr + 4 * e);                \
     }
 #define VOX_VPRE_AT(ROW_)                                                                                     \
     _Pragma("unroll") for (int u = 0; u < NPRE; u++)                                                          \
         _Pragma("unroll") for (int w = 0; w < 4; w++) {                                                       \
             const int iv = u * 4 * GROUPS + grp + w * GROUPS;                                                 \
-            vpre[u][w] = ldf4<NT>(vb + (size_t)(ROW_) * kv_row_stride + col * 4);                             \
+            vpre[u][w] = ldf4<NT>(rows.v(ROW_) + col * 4);                                                    \
         }
 #define VOX_VPRE VOX_VPRE_AT(j_lo + min(iv, n - 1))
     static_assert(!SPEC || !LATE_V, "speculative rows: K and V are both requested up front");
@@ -3251,7 +3272,7 @@ __device__ __forceinline__ float4 attn_decode_core(const float* __restrict__ qh,
 #pragma unroll
         for (int u = 0; u < 2; u++) {
             const int i = i0 + 32 * u + ks, jc = j_lo + min(i, n - 1);
-            const float* kr = kb + (size_t)jc * kv_row_stride + part * PER;
+            const float* kr = rows.k(jc) + part * PER;
             float s = 0.f;
 #pragma unroll
             for (int e = 0; e < PER; e += 4) {
@@ -3301,7 +3322,7 @@ __device__ __forceinline__ float4 attn_decode_core(const float* __restrict__ qh,
 #pragma unroll
         for (int u = 0; u < 4; u++) {
             const int i = i0 + u * GROUPS, ic = min(i, n - 1);
-            vv[u] = ldf4<NT>(vb + (size_t)(j_lo + ic) * kv_row_stride + col * 4);
+            vv[u] = ldf4<NT>(rows.v(j_lo + ic) + col * 4);
             pr[u] = i < n ? sc[ic] : 0.f;
         }
 #pragma unroll
@@ -3355,7 +3376,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const AttnParams p) {
     float* orow = p.out + (size_t)seq * p.out_seq_stride;
     const int tlw = (blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave; (void)tlw;
     VOX_TL(p.tl_slot, tlw, 0);
-    const float4 r4 = attn_decode_core<HD, false, false, SPEC>(qrow + h * HD, kb, vb, p.kv_row_stride, pos, p.window, sc, red, osum, p.tl_slot, tlw, p.spec_rows);
+    const float4 r4 = attn_decode_core<HD, false, false, SPEC>(qrow + h * HD, KvRowsFlat{kb, vb, p.kv_row_stride}, pos, p.window, sc, red, osum, p.tl_slot, tlw, p.spec_rows);
     if (tid < HD / 4) {
         if (p.out_xf) xf_store4(p.out_xf + (size_t)(seq >> 4) * p.out_xf_gstride, p.n_heads * HD, seq & 15, h * HD + tid * 4, r4);       // batched decode: A-fragments of the wo GEMM
         else *reinterpret_cast<float4*>(orow + h * HD + tid * 4) = r4;
@@ -3366,22 +3387,33 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const AttnParams p) {
 // group, so every K / V row is fetched from L2 once instead of G times (512 -> 128 workgroups at 16 sequences, a quarter of the
 // traffic).  Measured: neutral for one group of 16 sequences, +3 % at 64 sequences (four concurrent groups) -- used for wide batches only.  Same structure: all K loads of the
 // first 160 keys up front, softmax through LDS, V loads issued before the softmax, P.V reduced across 8 key groups.
-template <int G>
+// Both row policies are this one kernel.  PAGED (a paged stream group, launch_attn_decode_paged): k / v are the layer's page POOL and the KV head's cache rows are found
+// through the sequence's page table, whose entries for the window are staged in LDS before the first K request (attn_stage_pages); the scores take score_rows per
+// query head.  Else the rows are contiguous.  The arithmetic depends on the logical key index alone: same scan order, same reduction trees, the same bits.
+static const int ATTN_PAGE_TAB_MAX = 1026;      // staged entries: 16 384 positions in pages of 16 rows, + 2
+__device__ __forceinline__ KvRowsPaged attn_stage_pages(const AttnParams& p, int seq, int kvh, int pos, int* __restrict__ ptab);
+template <int G, bool PAGED>
 __global__ __launch_bounds__(256) void attn_decode_gqa_kernel(const AttnParams p) {
     constexpr int HD = 128, PER = HD / 8, NPRE = 5, COLS = HD / 4, GROUPS = 256 / COLS;   // GROUPS = 8
     extern __shared__ __attribute__((aligned(16))) float smem[];      // scores [G][max_seq]
     __shared__ float red[2 * G * 4];
     __shared__ float4 osum[256];
+    __shared__ int ptab[PAGED ? ATTN_PAGE_TAB_MAX : 1];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int kvh = blockIdx.x, seq = blockIdx.y, max_seq = p.kv_head_stride / HD;
+    const int kvh = blockIdx.x, seq = blockIdx.y, max_seq = PAGED ? p.score_rows : p.kv_head_stride / HD;
     const int pos = (p.pos_ptr ? p.pos_ptr[p.pos_per_seq ? seq : 0] : 0) + p.offset;
     const int len = pos + 1;
     const int j_lo = p.window >= 0 ? max(0, pos - p.window) : 0;
     const int n = len - j_lo;
     const float scale = 1.0f / sqrtf((float)HD);
-    const int crow = p.kv_row ? p.kv_row[seq] : seq;      // cache slice of this sequence (continuous batching: the utterance the slot holds)
-    const float* kb = p.k + (size_t)crow * p.kv_seq_stride + (size_t)kvh * p.kv_head_stride;
-    const float* vb = p.v + (size_t)crow * p.kv_seq_stride + (size_t)kvh * p.kv_head_stride;
+    typename std::conditional<PAGED, KvRowsPaged, KvRowsFlat>::type rows;
+    if constexpr (PAGED) rows = attn_stage_pages(p, seq, kvh, pos, ptab);
+    else {
+        const int crow = p.kv_row ? p.kv_row[seq] : seq;      // cache slice of this sequence (continuous batching: the utterance the slot holds)
+        const float* kb = p.k + (size_t)crow * p.kv_seq_stride + (size_t)kvh * p.kv_head_stride;
+        const float* vb = p.v + (size_t)crow * p.kv_seq_stride + (size_t)kvh * p.kv_head_stride;
+        rows = KvRowsFlat{kb, vb, p.kv_row_stride};
+    }
     const float* qrow = p.q + (size_t)seq * p.q_seq_stride + (size_t)kvh * G * HD;
     const int ks = tid >> 3, part = tid & 7;
     const int grp = tid / COLS, col = tid % COLS;
@@ -3389,7 +3421,7 @@ __global__ __launch_bounds__(256) void attn_decode_gqa_kernel(const AttnParams p
 #pragma unroll
     for (int u = 0; u < NPRE; u++) {
         const int jc = j_lo + min(32 * u + ks, n - 1);
-        const float* kr = kb + (size_t)jc * p.kv_row_stride + part * PER;
+        const float* kr = rows.k(jc) + part * PER;
 #pragma unroll
         for (int e = 0; e < PER / 4; e++) kpre[u][e] = *reinterpret_cast<const float4*>(kr + 4 * e);
     }
@@ -3414,7 +3446,7 @@ __global__ __launch_bounds__(256) void attn_decode_gqa_kernel(const AttnParams p
         const int i = i0 + ks, jc = j_lo + min(i, n - 1);
         float4 kr[PER / 4];
 #pragma unroll
-        for (int e = 0; e < PER / 4; e++) kr[e] = *reinterpret_cast<const float4*>(kb + (size_t)jc * p.kv_row_stride + part * PER + 4 * e);
+        for (int e = 0; e < PER / 4; e++) kr[e] = *reinterpret_cast<const float4*>(rows.k(jc) + part * PER + 4 * e);
         VOX_SCORE(kr, i)
     }
 #undef VOX_SCORE
@@ -3425,7 +3457,7 @@ __global__ __launch_bounds__(256) void attn_decode_gqa_kernel(const AttnParams p
 #pragma unroll
         for (int w = 0; w < 4; w++) {
             const int ic = min(u * 32 + grp + w * GROUPS, n - 1);
-            vpre[u][w] = *reinterpret_cast<const float4*>(vb + (size_t)(j_lo + ic) * p.kv_row_stride + col * 4);
+            vpre[u][w] = *reinterpret_cast<const float4*>(rows.v(j_lo + ic) + col * 4);
         }
     __syncthreads();
     float mx[G], sum[G];
@@ -3464,7 +3496,7 @@ __global__ __launch_bounds__(256) void attn_decode_gqa_kernel(const AttnParams p
             }
         }
     for (int i0 = 32 * NPRE + grp; i0 < n; i0 += GROUPS) {
-        const float4 vv = *reinterpret_cast<const float4*>(vb + (size_t)(j_lo + i0) * p.kv_row_stride + col * 4);
+        const float4 vv = *reinterpret_cast<const float4*>(rows.v(j_lo + i0) + col * 4);
 #pragma unroll
         for (int hh = 0; hh < G; hh++) {
             const float pr = smem[hh * max_seq + i0];
@@ -3487,6 +3519,47 @@ __global__ __launch_bounds__(256) void attn_decode_gqa_kernel(const AttnParams p
             else *reinterpret_cast<float4*>(p.out + (size_t)seq * p.out_seq_stride + h * HD + tid * 4) = r4;
         }
     }
+}
+// ---- paged decode attention (a paged stream group: AttnParams::page_tab): k / v are the layer's page POOL, [page][kv head][page_rows][hd]; sequence seq is member
+// kv_row[seq], whose table row names the physical page of each logical page.  The window's entries -- logical pages j_lo >> shift .. pos >> shift, at most
+// (window + 1) / page_rows + 2 of them -- are staged in LDS before the first K request; the bodies are the slab kernels' (attn_decode_core, attn_decode_gqa_kernel) with
+// the paged row policy: same scan order, same reduction trees, so a row has the slab kernel's bits.  Scores: score_rows per query head.  Entries outside the window
+// are never read (released pages hold -1 there).
+__device__ __forceinline__ KvRowsPaged attn_stage_pages(const AttnParams& p, int seq, int kvh, int pos, int* __restrict__ ptab) {
+    const int j_lo = p.window >= 0 ? max(0, pos - p.window) : 0, q0 = j_lo >> p.page_shift, nq = (pos >> p.page_shift) - q0 + 1;
+    const int* tab = p.page_tab + (size_t)(p.kv_row ? p.kv_row[seq] : seq) * p.page_tab_stride + q0;
+    for (int i = threadIdx.x; i < nq; i += 256) ptab[i] = tab[i];
+    __syncthreads();
+    const size_t ho = (size_t)kvh * p.kv_head_stride;
+    return KvRowsPaged{p.k + ho, p.v + ho, ptab, q0, p.page_shift, (1 << p.page_shift) - 1, p.kv_row_stride, (size_t)p.page_floats};
+}
+template <int HD>
+__global__ __launch_bounds__(256) void attn_decode_paged_kernel(const AttnParams p) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];      // scores, score_rows
+    __shared__ float red[8];
+    __shared__ float4 osum[256];
+    __shared__ int ptab[ATTN_PAGE_TAB_MAX];
+    const int tid = threadIdx.x, wave = tid >> 6;
+    int h = blockIdx.x, seq = blockIdx.y;      // the G query heads of a KV head on one XCD, as attn_decode_kernel
+    {
+        const int G_ = p.n_heads / p.n_kv_heads, total = gridDim.x * gridDim.y;
+        if (G_ > 1 && total % (8 * G_) == 0 && !p.no_xcd_remap) {
+            const int lin = blockIdx.y * gridDim.x + blockIdx.x, xcd = lin & 7, slot = lin >> 3;
+            const int pair = xcd * (total / (8 * G_)) + slot / G_;
+            h = (pair % p.n_kv_heads) * G_ + slot % G_; seq = pair / p.n_kv_heads;
+        }
+    }
+    const int kvh = h / (p.n_heads / p.n_kv_heads);
+    const int pos = (p.pos_ptr ? p.pos_ptr[p.pos_per_seq ? seq : 0] : 0) + p.offset;
+    const KvRowsPaged rows = attn_stage_pages(p, seq, kvh, pos, ptab);
+    const int tlw = (blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave; (void)tlw;
+    VOX_TL(p.tl_slot, tlw, 0);
+    const float4 r4 = attn_decode_core<HD, false, false, false, NoHook, KvRowsPaged>(p.q + (size_t)seq * p.q_seq_stride + h * HD, rows, pos, p.window, smem, red, osum, p.tl_slot, tlw, 0);
+    if (tid < HD / 4) {
+        if (p.out_xf) xf_store4(p.out_xf + (size_t)(seq >> 4) * p.out_xf_gstride, p.n_heads * HD, seq & 15, h * HD + tid * 4, r4);
+        else *reinterpret_cast<float4*>(p.out + (size_t)seq * p.out_seq_stride + h * HD + tid * 4) = r4;
+    }
+    VOX_TL(p.tl_slot, tlw, 3);
 }
 // ---- single-stream decode: attention + wo in ONE launch (gguf/model.rs:125-174 + the wo linear of model.rs:230-238), no cross-workgroup wait.
 // Workgroup (h, slice): runs the attention of query head h (redundantly in each of the 8 slices: K / V rows are L2 hits after the first; the
@@ -3521,8 +3594,8 @@ __global__ __launch_bounds__(256) void attn_wo_kernel(const AttnParams p, const 
     };
     // (2) attention of head h; the weight requests go out right behind its q / K / V requests
     const int pos = (p.pos_ptr ? p.pos_ptr[0] : 0) + p.offset;
-    const float4 r4 = attn_decode_core<HD, false, false, false>(p.q + h * HD, p.k + (size_t)kvh * p.kv_head_stride, p.v + (size_t)kvh * p.kv_head_stride,
-                                                                 p.kv_row_stride, pos, p.window, smem, red, osum, p.tl_slot, tlw, 0, load_w);
+    const float4 r4 = attn_decode_core<HD, false, false, false>(p.q + h * HD, KvRowsFlat{p.k + (size_t)kvh * p.kv_head_stride, p.v + (size_t)kvh * p.kv_head_stride, p.kv_row_stride},
+                                                                 pos, p.window, smem, red, osum, p.tl_slot, tlw, 0, load_w);
     if (tid < HD / 4) a_s[tid] = r4;
     __syncthreads();
     VOX_TL(p.tl_slot, tlw, 2);
@@ -3566,7 +3639,7 @@ hipError_t launch_attn_decode(const AttnParams& p_in, int hd, int max_seq, hipSt
     AttnParams p = p_in; p.tl_slot = tl_take_slot(1, 0, p.n_heads, hd);
     const size_t lds = (size_t)max_seq * sizeof(float);
     if (hd == 128 && p.prefer_gqa && p.n_heads == 4 * p.n_kv_heads && p.kv_head_stride == max_seq * 128) {
-        auto kern = attn_decode_gqa_kernel<4>;      // many sequences: one workgroup per (KV head, sequence), K/V fetched once for its 4 query heads
+        auto kern = attn_decode_gqa_kernel<4, false>;      // many sequences: one workgroup per (KV head, sequence), K/V fetched once for its 4 query heads
         static DevOnce attr_done;
         hipError_t e = ensure_dyn_lds(kern, 4 * lds, &attr_done);
         if (e != hipSuccess) return e;
@@ -3596,6 +3669,37 @@ hipError_t launch_attn_decode(const AttnParams& p_in, int hd, int max_seq, hipSt
         auto kern = attn_decode_kernel<64, false>;
         kern<<<dim3(p.n_heads, n_seq), dim3(256), lds, s>>>(p);
         attn_form_note(ATTN_FORM_DECODE);
+    } else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+// the paged forms: launch_attn_decode's choice between the GQA and the per-head kernel for a stream group's step (prefer_gqa, no speculative rows), on the page pool
+hipError_t launch_attn_decode_paged(const AttnParams& p_in, int hd, hipStream_t s, int n_seq) {
+    AttnParams p = p_in; p.tl_slot = tl_take_slot(1, 0, p.n_heads, hd);
+    const int page_rows = 1 << p.page_shift, win = p.window >= 0 ? p.window : p.score_rows - 1;
+    if (!p.page_tab || !p.pos_ptr || !p.pos_per_seq || p.page_shift < 4 || p.page_shift > 10 || p.kv_row_stride != hd || p.kv_head_stride != page_rows * hd || p.score_rows < 1 ||
+        p.page_floats != (long)p.n_kv_heads * page_rows * hd || p.page_tab_stride < 1 || win / page_rows + 2 > ATTN_PAGE_TAB_MAX || n_seq < 1) return hipErrorInvalidValue;
+    const size_t lds = (size_t)p.score_rows * sizeof(float);
+    if (hd == 128 && p.n_heads == 4 * p.n_kv_heads) {
+        auto kern = attn_decode_gqa_kernel<4, true>;
+        static DevOnce attr_done;
+        hipError_t e = ensure_dyn_lds(kern, 4 * lds, &attr_done);
+        if (e != hipSuccess) return e;
+        kern<<<dim3(p.n_kv_heads, n_seq), dim3(256), 4 * lds, s>>>(p);
+        attn_form_note(ATTN_FORM_DECODE_GQA_PAGED);
+    } else if (hd == 128) {
+        auto kern = attn_decode_paged_kernel<128>;
+        static DevOnce attr_done;
+        hipError_t e = ensure_dyn_lds(kern, lds, &attr_done);
+        if (e != hipSuccess) return e;
+        kern<<<dim3(p.n_heads, n_seq), dim3(256), lds, s>>>(p);
+        attn_form_note(ATTN_FORM_DECODE_PAGED);
+    } else if (hd == 64) {
+        auto kern = attn_decode_paged_kernel<64>;
+        static DevOnce attr_done;
+        hipError_t e = ensure_dyn_lds(kern, lds, &attr_done);
+        if (e != hipSuccess) return e;
+        kern<<<dim3(p.n_heads, n_seq), dim3(256), lds, s>>>(p);
+        attn_form_note(ATTN_FORM_DECODE_PAGED);
     } else return hipErrorInvalidValue;
     return hipGetLastError();
 }
@@ -4455,9 +4559,12 @@ hipError_t launch_stream_advance(const float* part_val, const int* part_idx, int
 
 // ---- the decode half of a group round: one workgroup per row r of the round (session order[r]).  Rows past the round's n are not touched by either kernel: what an
 // earlier, wider round left in h, the XF planes, pos or kv_row there is never read for a cache row, a token or a tap (xf_chain's kernels guard every store by the row count).
+// PAGED (a paged group): the row's physical page -- entry pos / page_rows of the member's table row, held since the call was planned -- and its row inside the page
+// go out as well: what the q|k|v GEMM's epilogue appends at (GemmParams::kv_row, kv_pos)
+template <bool PAGED>
 __global__ __launch_bounds__(256) void stream_group_embed_kernel(Q4W tok, const StreamMember* __restrict__ mem, const int* __restrict__ order, const float* __restrict__ audio, int D,
                                                                  float* __restrict__ h, uint16_t* __restrict__ xf, const float* __restrict__ xf_w, float* __restrict__ ssq_out,
-                                                                 int* __restrict__ pos_out, int* __restrict__ kv_row_out) {
+                                                                 int* __restrict__ pos_out, int* __restrict__ kv_row_out, const StreamPages pg) {
     __shared__ float wsum[4];
     const int r = blockIdx.x, member = order[r];
     const StreamMember& me = mem[member];
@@ -4465,12 +4572,38 @@ __global__ __launch_bounds__(256) void stream_group_embed_kernel(Q4W tok, const 
     float* hrow = h + (size_t)r * D;
     embed_row(tok, me.tokens[pos], audio + (size_t)r * D, hrow, D);
     xf_row_ssq(hrow, xf_w, D, xf, r, ssq_out, wsum);
-    if (threadIdx.x == 0) { pos_out[r] = pos; kv_row_out[r] = member; }
+    if (threadIdx.x == 0) {
+        pos_out[r] = pos; kv_row_out[r] = member;
+        if (PAGED) { pg.page_out[r] = pg.tab[(size_t)member * pg.tab_stride + (pos >> pg.shift)]; pg.in_page_out[r] = pos & ((1 << pg.shift) - 1); }
+    }
 }
 hipError_t launch_stream_group_embed(Q4W tok, const StreamMember* mem, const int* order, int n, const float* audio, int D, float* h, uint16_t* xf, const float* xf_w,
-                                     float* ssq_out, int* pos, int* kv_row, hipStream_t s) {
+                                     float* ssq_out, int* pos, int* kv_row, hipStream_t s, const StreamPages* pages) {
     if (n < 1 || n > 16 || !mem || !order || !audio || !h || !xf || !xf_w || !ssq_out || !pos || !kv_row || (D & 127)) return hipErrorInvalidValue;
-    stream_group_embed_kernel<<<dim3(n), dim3(256), 0, s>>>(tok, mem, order, audio, D, h, xf, xf_w, ssq_out, pos, kv_row);
+    if (pages) {
+        if (!pages->tab || !pages->page_out || !pages->in_page_out || pages->tab_stride < 1 || pages->shift < 4 || pages->shift > 10) return hipErrorInvalidValue;
+        stream_group_embed_kernel<true><<<dim3(n), dim3(256), 0, s>>>(tok, mem, order, audio, D, h, xf, xf_w, ssq_out, pos, kv_row, *pages);
+    } else stream_group_embed_kernel<false><<<dim3(n), dim3(256), 0, s>>>(tok, mem, order, audio, D, h, xf, xf_w, ssq_out, pos, kv_row, StreamPages{});
+    return hipGetLastError();
+}
+// seed of a paged member (prefix_rows_into's counterpart): rows 0 .. rows-1 of every (layer, kv head) plane of the prefix state, src [layers][kv heads][rows][hd], into
+// the member's first pages of the pool [layers][pool_pages][kv heads][page_rows][hd]; tab: the member's table row
+__global__ __launch_bounds__(256) void stream_pages_seed_kernel(const float* __restrict__ src_k, const float* __restrict__ src_v, int kv_heads, int rows, int hd4,
+                                                                const int* __restrict__ tab, int shift, size_t layer_stride, size_t page_floats,
+                                                                float* __restrict__ pool_k, float* __restrict__ pool_v, long total) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int d = (int)(i % hd4); long t = i / hd4; const int j = (int)(t % rows); t /= rows; const int kh = (int)(t % kv_heads), l = (int)(t / kv_heads);
+        const size_t dst = (size_t)l * layer_stride + (size_t)tab[j >> shift] * page_floats + ((size_t)kh << shift) * hd4 * 4 + (size_t)(j & ((1 << shift) - 1)) * hd4 * 4 + 4 * d;
+        *reinterpret_cast<float4*>(pool_k + dst) = reinterpret_cast<const float4*>(src_k)[i];
+        *reinterpret_cast<float4*>(pool_v + dst) = reinterpret_cast<const float4*>(src_v)[i];
+    }
+}
+hipError_t launch_stream_pages_seed(const float* src_k, const float* src_v, int layers, int kv_heads, int rows, int hd, const int* tab, int page_shift, size_t layer_stride,
+                                    float* pool_k, float* pool_v, hipStream_t s) {
+    if (!src_k || !src_v || !tab || !pool_k || !pool_v || layers < 1 || kv_heads < 1 || rows < 1 || hd < 4 || (hd & 3) || page_shift < 4 || page_shift > 10) return hipErrorInvalidValue;
+    const long total = (long)layers * kv_heads * rows * (hd / 4);
+    stream_pages_seed_kernel<<<dim3((unsigned)std::min<long>((total + 255) / 256, 1024)), dim3(256), 0, s>>>(src_k, src_v, kv_heads, rows, hd / 4, tab, page_shift, layer_stride,
+                                                                                                              (size_t)kv_heads * hd << page_shift, pool_k, pool_v, total);
     return hipGetLastError();
 }
 __global__ __launch_bounds__(1024) void stream_group_advance_kernel(const float* __restrict__ logits, int vocab, const StreamMember* __restrict__ mem, const int* __restrict__ order,

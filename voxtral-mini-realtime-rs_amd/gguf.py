@@ -506,6 +506,14 @@ def stream_schedule_rate(n_samples: int, sample_rate: int, finished: bool = Fals
     return p.value, i.value, k.value
 
 
+def stream_group_pages_for(positions, page_rows=256, window=8192):
+    """vox_stream_group_pages_for (host arithmetic, the allocator's own function): (first logical page, number of pages) a paged group's member holds when its next tick
+    is at `positions`; window -1: no sliding window."""
+    f = C.c_int32(); n = C.c_int32()
+    check(lib().vox_stream_group_pages_for(int(positions), int(page_rows), int(window), C.byref(f), C.byref(n)))
+    return f.value, n.value
+
+
 def stream_schedule(n_samples: int, finished: bool = False, sample_rate: int = 16000):
     """vox_stream_schedule (host arithmetic): (decoder positions determined, ids due) after `n_samples` pushed, or at the end of an n_samples utterance; samples counted
     at `sample_rate`, the rate of the stream (vox_stream_schedule_rate)."""
@@ -656,19 +664,23 @@ class LiveStreamGroup:
     stream_schedule(..., sample_rate=its rate) on its own sample count.  Samples are float32 or 16-bit PCM at the member's rate."""
     _rates = None      # {member: rate} of the members at another rate than 16 kHz; a member without an entry is fed 16 kHz
 
-    def __init__(self, model, t_embed, n_members, gains=None, enc_capacity_rows=0, max_positions=0, sample_rates=None):
+    def __init__(self, model, t_embed, n_members, gains=None, enc_capacity_rows=0, max_positions=0, sample_rates=None, page_rows=None, pool_pages=None):
         self.model = model; self.h = C.c_void_p(); self.n_members = int(n_members); self._tap_max = {}; self._rates = {}
+        self.paged = page_rows is not None or pool_pages is not None      # either one given: a paged group (vox_stream_group_create_paged; 0 / None: its default)
         g = None if gains is None else _f32(gains).reshape(-1)
         if g is not None and g.size != self.n_members:
             raise ValueError(f"{g.size} gains for {self.n_members} members")
         args = (model.h, _ptr(_f32(t_embed).reshape(-1)), self.n_members, None if g is None else _ptr(g))
-        if sample_rates is None:
+        if sample_rates is None and not self.paged:
             check(lib().vox_stream_group_create(*args, int(enc_capacity_rows), int(max_positions), C.byref(self.h)))
         else:
-            r = np.ascontiguousarray([int(v) for v in sample_rates], dtype=np.uint32)
+            r = np.ascontiguousarray([int(v) for v in (sample_rates if sample_rates is not None else [16000] * self.n_members)], dtype=np.uint32)
             if r.size != self.n_members:
                 raise ValueError(f"{r.size} sample rates for {self.n_members} members")
-            check(lib().vox_stream_group_create_rates(*args, _ptr(r), int(enc_capacity_rows), int(max_positions), C.byref(self.h)))
+            if self.paged:
+                check(lib().vox_stream_group_create_paged(*args, _ptr(r), int(enc_capacity_rows), int(max_positions), int(page_rows or 0), int(pool_pages or 0), C.byref(self.h)))
+            else:
+                check(lib().vox_stream_group_create_rates(*args, _ptr(r), int(enc_capacity_rows), int(max_positions), C.byref(self.h)))
             self._rates = {k: int(v) for k, v in enumerate(r) if int(v) != 16000}
         model._caches.add(self)
 
@@ -743,6 +755,19 @@ class LiveStreamGroup:
     def info(self, member):
         v = (C.c_int64 * 8)(); check(lib().vox_stream_group_info(self.h, int(member), v))
         return dict(zip(("samples", "positions", "ids", "encoder_position", "ring_rows", "bytes", "engine_steps", "operator_steps"), (int(x) for x in v)))
+
+    def pool(self) -> dict:
+        """vox_stream_group_pool of a paged group: page_rows, pool_pages, the free pages, the most pages ever in use, and held: the pages each member holds."""
+        v = (C.c_int64 * 4)(); held = np.zeros(self.n_members, dtype=np.int32)
+        check(lib().vox_stream_group_pool(self.h, v, _ptr(held)))
+        return {"page_rows": int(v[0]), "pool_pages": int(v[1]), "free": int(v[2]), "peak": int(v[3]), "held": [int(x) for x in held]}
+
+    def pages(self, member) -> list:
+        """vox_debug_stream_group_pages: the member's physical pages, in the order of its logical pages."""
+        n = C.c_int32(); check(lib().vox_debug_stream_group_pages(self.h, int(member), None, 0, C.byref(n)))
+        out = np.zeros(max(n.value, 1), dtype=np.int32)
+        check(lib().vox_debug_stream_group_pages(self.h, int(member), _ptr(out), out.size, C.byref(n)))
+        return [int(x) for x in out[:n.value]]
 
     def set_scores(self, member, on: bool = True):
         """vox_stream_group_set_scores: LiveStream.set_scores for one member; survives the member's resets."""
@@ -969,11 +994,13 @@ class Q4VoxtralModel:
         (a stream has no file peak: 0.95 / max|x| of a known file reproduces transcribe_audio).  sample_rate: the rate of the samples that will be pushed."""
         return LiveStream(self, t_embed, gain, enc_capacity_rows, max_positions, sample_rate)
 
-    def create_stream_group(self, t_embed, n_members, gains=None, enc_capacity_rows=0, max_positions=0, sample_rates=None) -> LiveStreamGroup:
+    def create_stream_group(self, t_embed, n_members, gains=None, enc_capacity_rows=0, max_positions=0, sample_rates=None, page_rows=None, pool_pages=None) -> LiveStreamGroup:
         """Up to 16 live sessions advanced together (vox_stream_group_create): advance({member: samples}, finish=()) -> {member: ids}, reset(member, gain), info(member),
         close().  gains: one per member (None: 1.0 each); max_positions 0: 2048 decoder positions per member (the group's decoder cache does not grow);
-        sample_rates: what each member is fed (None: 16 kHz each; vox_stream_group_create_rates)."""
-        return LiveStreamGroup(self, t_embed, n_members, gains, enc_capacity_rows, max_positions, sample_rates)
+        sample_rates: what each member is fed (None: 16 kHz each; vox_stream_group_create_rates).
+        page_rows / pool_pages, either one given: a PAGED group (vox_stream_group_create_paged) -- one pool of pool_pages K / V pages of page_rows rows (0 / None: 256 rows;
+        the default slab's memory) that the members grow into and return pages to; max_positions 0 is then the session limit; pool(), pages(member)."""
+        return LiveStreamGroup(self, t_embed, n_members, gains, enc_capacity_rows, max_positions, sample_rates, page_rows, pool_pages)
 
     def transcribe_batch(self, samples_list, t_embed, device_ptrs=None, n_samples=None, norm_group=None, tap_units=None):
         """Batched whole-path transcription of independent utterances (<= 4096; wider than 16: continuous batching over decode slots): list of float32 sample arrays
