@@ -291,21 +291,25 @@ def test_header_is_valid_c11_and_links(pkg, tmp_path):
 
 
 def test_host_code_under_address_sanitizer(pkg, tmp_path):
-    """vox_api.cpp's host side (GGUF reader, padding / chunk arithmetic, argument checks: ~2 000 lines of pointer arithmetic) rebuilt with -fsanitize=address and driven by
-    tests/abi_smoke.c's host section, including every truncation of a GGUF image.  Host code only: -fno-gpu-sanitize keeps the gfx950 side uninstrumented, and the
-    device objects are linked unchanged."""
-    import os, subprocess
+    """Every host unit (build.py's HOST_SOURCES; GGUF reader, padding / chunk arithmetic, argument checks: ~2 000 lines of pointer arithmetic) rebuilt with
+    -fsanitize=address and driven by tests/abi_smoke.c's host section, including every truncation of a GGUF image.  Host code only: -fno-gpu-sanitize keeps the gfx950
+    side uninstrumented, and the device objects are linked unchanged."""
+    import importlib, os, subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     pkg_dir = os.path.join(root, "voxtral-mini-realtime-rs_amd"); bdir = os.path.join(pkg_dir, "build")
     if not (os.path.exists(os.path.join(bdir, "vox_kernels.o")) and os.path.exists(os.path.join(bdir, "vox_engine.o"))):
         pytest.skip("device objects not built")
+    build = importlib.import_module(pkg.__name__ + ".build")      # HOST_SOURCES: every host unit; HOST_SOURCES_PLAIN: the ones compiled as plain C++
     hipcc = "/opt/rocm/bin/hipcc"; clang = "/opt/rocm/lib/llvm/bin/clang"
     d = str(tmp_path)
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-fPIC", "-fsanitize=address", "-fno-gpu-sanitize", "-fno-omit-frame-pointer", "-x", "hip", "-c",
-                        os.path.join(pkg_dir, "csrc", "vox_api.cpp"), "-o", os.path.join(d, "vox_api.o")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
+    objs = []
+    for src in build.HOST_SOURCES:
+        objs.append(os.path.join(d, src.rsplit(".", 1)[0] + ".o"))
+        r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-fPIC", "-fsanitize=address", "-fno-gpu-sanitize", "-fno-omit-frame-pointer", "-x",
+                            "c++" if src in build.HOST_SOURCES_PLAIN else "hip", "-c", os.path.join(pkg_dir, "csrc", src), "-o", objs[-1]], capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr[-2000:]
     r = subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-fsanitize=address", "-fno-gpu-sanitize", "-o", os.path.join(d, "libvoxtral_hip.so"),
-                        os.path.join(bdir, "vox_kernels.o"), os.path.join(bdir, "vox_engine.o"), os.path.join(d, "vox_api.o")], capture_output=True, text=True)
+                        os.path.join(bdir, "vox_kernels.o"), os.path.join(bdir, "vox_engine.o"), *objs], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
     r = subprocess.run([clang, "-std=c11", "-g", "-fsanitize=address", "-fno-gpu-sanitize", "-I" + os.path.join(root, "include"), os.path.join(root, "tests", "abi_smoke.c"), "-o",
                         os.path.join(d, "abi_smoke_asan"), "-L" + d, "-lvoxtral_hip", "-lm", "-Wl,-rpath," + d], capture_output=True, text=True)

@@ -1,4 +1,4 @@
-"""The continuous batch driver's planner (csrc/vox_api.cpp: step_costs, plan_slots, the retire-slack schedule) against an independent restatement written here.
+"""The continuous batch driver's planner (csrc/vox_batch_plan.cpp: step_costs, plan_slots, the retire-slack schedule) against an independent restatement written here.
 Host arithmetic only: vox_debug_step_costs / vox_debug_plan_slots take no context and touch no device, so nothing in this file needs a GPU."""
 import ctypes as C
 import os

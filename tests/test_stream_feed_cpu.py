@@ -1,4 +1,4 @@
-"""The live sessions' feed planner (feed_plan / feed_pass in vox_api.cpp: one implementation for a solo vox_stream and for every member of a vox_stream_group) through
+"""The live sessions' feed planner (feed_plan / feed_pass in vox_feed_plan.cpp: one implementation for a solo vox_stream and for every member of a vox_stream_group) through
 its host-only view vox_debug_stream_feed_passes.  No GPU, no model; every assertion is == or <=.
 
 A session takes calls (n samples at its rate, finish or not).  A call runs in PASSES, each bounded by the session's two rings: the input-rate ring (a power of two of at

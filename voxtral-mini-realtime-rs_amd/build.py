@@ -8,8 +8,11 @@ from concurrent.futures import ThreadPoolExecutor
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.environ.get("VOX_LIB") or os.path.join(PKG_DIR, "libvoxtral_hip.so")   # VOX_LIB: a measurement build (variant_lib_path)
-SOURCES = ["vox_kernels.hip", "vox_engine.hip", "vox_engine_b16.hip", "vox_api.cpp"]
-HEADERS = ["vox_kernels.h", "vox_engine_common.h", "vox_page_pool.h",os.path.join("..", "..", "include", "voxtral_hip.h")]
+# host units ("Host units"): the device-free ones include no HIP header and are compiled as plain C++
+HOST_SOURCES_PLAIN = ["vox_audio_host.cpp", "vox_gguf.cpp", "vox_batch_plan.cpp", "vox_feed_plan.cpp"]
+HOST_SOURCES = ["vox_api.cpp", *HOST_SOURCES_PLAIN]
+SOURCES = ["vox_kernels.hip", "vox_engine.hip", "vox_engine_b16.hip", *HOST_SOURCES]
+HEADERS = ["vox_kernels.h", "vox_engine_common.h", "vox_page_pool.h", "vox_host_base.h", os.path.join("..", "..", "include", "voxtral_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-result"]
 
@@ -38,7 +41,7 @@ def build_all(verbose: bool = False, force: bool = False, tag: str | None = None
         obj = os.path.join(bdir, src.rsplit(".", 1)[0] + ".o")
         objs.append(obj)
         if force or _stale(obj, [sp] + deps):
-            jobs.append([HIPCC, *FLAGS, *extra_flags, "-x", "hip", "-c", sp, "-o", obj])
+            jobs.append([HIPCC, *FLAGS, *extra_flags, "-x", "c++" if src in HOST_SOURCES_PLAIN else "hip", "-c", sp, "-o", obj])
 
     def run(cmd):
         if verbose:

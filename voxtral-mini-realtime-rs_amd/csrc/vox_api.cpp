@@ -1,12 +1,14 @@
-// vox_api.cpp -- C ABI of libvoxtral_hip.so (include/voxtral_hip.h): context, audio front-end helpers,
-// GGUF reader, Q4 operator boundary, model loader (GGUF -> packed device arena) and the model-forward
-// orchestration (encoder, prefill, hipGraph-captured sync-free decode step).
+// vox_api.cpp -- C ABI of libvoxtral_hip.so (include/voxtral_hip.h): context, the audio front end's device side,
+// Q4 operator boundary, model loader (GGUF -> packed device arena) and the model-forward
+// orchestration (encoder, prefill, hipGraph-captured sync-free decode step).  The host arithmetic of the
+// front end, the GGUF reader and the planners are units of their own (vox_audio_host.cpp, vox_gguf.cpp, vox_batch_plan.cpp, vox_feed_plan.cpp; vox_host_base.h).
 //
 // Reference surface mirrored: src/audio/{io,pad,chunk,mel}.rs, src/gguf/{reader,tensor,op,linear,loader,model}.rs,
 // src/models/time_embedding.rs.  No code is shared with oracle/ and there is no CPU fallback for compute.
 #include "../../include/voxtral_hip.h"
 #include "vox_kernels.h"
 #include "vox_page_pool.h"
+#include "vox_host_base.h"
 
 #include <dlfcn.h>
 #include <fcntl.h>
@@ -32,20 +34,21 @@
 #include <vector>
 
 using namespace vox;
+using namespace vox_host;
 
 // ------------------------------------------------------------------------------------------------
 // errors
 // ------------------------------------------------------------------------------------------------
 static thread_local std::string g_err;
-static int32_t fail(int32_t code, const char* fmt, ...) {
+namespace vox_host {
+int32_t fail(int32_t code, const char* fmt, ...) {
     char buf[1024];
     va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
     g_err = buf;
     return code;
 }
+}  // namespace vox_host
 #define HIPCHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return fail(VOX_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); } while (0)
-#define VOXCHK(expr) do { int32_t _r = (expr); if (_r != VOX_OK) return _r; } while (0)
-#define ARGCHK(cond, ...) do { if (!(cond)) return fail(VOX_ERR_INVALID, __VA_ARGS__); } while (0)
 
 extern "C" const char* vox_last_error(void) { return g_err.c_str(); }
 extern "C" int32_t vox_abi_version(void) { return 1; }
@@ -223,89 +226,6 @@ struct DevBuf {
     template <class T> T* as() { return reinterpret_cast<T*>(p); }
 };
 
-// ------------------------------------------------------------------------------------------------
-// audio front-end: host helpers (caller-side in the reference too)
-// ------------------------------------------------------------------------------------------------
-extern "C" int32_t vox_peak_normalize(float* s, size_t n, float target) {   // audio/io.rs:59-68
-    ARGCHK(s || n == 0, "null samples");
-    float mx = 0.f;
-    for (size_t i = 0; i < n; i++) mx = std::fmax(mx, std::fabs(s[i]));
-    if (mx < 1e-10f) return VOX_OK;
-    const float scale = target / mx;
-    for (size_t i = 0; i < n; i++) s[i] *= scale;
-    return VOX_OK;
-}
-extern "C" int32_t vox_pad_cfg_voxtral(vox_pad_cfg* c) {                     // audio/pad.rs:32-52
-    ARGCHK(c, "null cfg"); c->sample_rate = 16000; c->n_left_pad_tokens = 76; c->frame_rate = 12.5f; c->extra_right_pad_tokens = 17; return VOX_OK;
-}
-static size_t pad_spt(const vox_pad_cfg* c) { return (size_t)((float)c->sample_rate / c->frame_rate); }
-static size_t pad_left(const vox_pad_cfg* c) { return (size_t)c->n_left_pad_tokens * pad_spt(c); }
-static size_t pad_right(const vox_pad_cfg* c, size_t total) {                // audio/pad.rs:68-74
-    const size_t spt = pad_spt(c), rem = total % spt;
-    return (rem ? spt - rem : 0) + (size_t)c->extra_right_pad_tokens * spt;
-}
-extern "C" int32_t vox_pad_len(size_t n, const vox_pad_cfg* c, size_t* out) {
-    ARGCHK(c && out, "null argument"); ARGCHK(c->frame_rate > 0 && pad_spt(c) > 0, "bad pad config");
-    *out = pad_left(c) + n + pad_right(c, n + pad_left(c)); return VOX_OK;
-}
-extern "C" int32_t vox_pad_audio(const float* in, size_t n, const vox_pad_cfg* c, float* out) {   // audio/pad.rs:89-103
-    ARGCHK(c && out && (in || n == 0), "null argument");
-    size_t total; VOXCHK(vox_pad_len(n, c, &total));
-    std::memset(out, 0, total * sizeof(float));
-    if (n) std::memcpy(out + pad_left(c), in, n * sizeof(float));
-    return VOX_OK;
-}
-extern "C" int32_t vox_num_audio_tokens(size_t n, const vox_pad_cfg* c, size_t* out) { ARGCHK(c && out, "null argument"); *out = n / pad_spt(c); return VOX_OK; }
-
-extern "C" int32_t vox_needs_chunking(size_t n, const vox_chunk_cfg* c, int32_t* out) {   // audio/chunk.rs:164-166
-    ARGCHK(c && out, "null argument"); *out = n > (size_t)c->max_mel_frames * c->hop_length; return VOX_OK;
-}
-extern "C" int32_t vox_chunk_plan(size_t n, const vox_chunk_cfg* c, vox_chunk* out, size_t cap, size_t* n_chunks) {  // chunk.rs:120-161
-    ARGCHK(c && n_chunks, "null argument");
-    ARGCHK(c->max_mel_frames > c->overlap_frames && c->hop_length > 0, "overlap_frames must be < max_mel_frames");
-    const size_t max_s = (size_t)c->max_mel_frames * c->hop_length, step = (size_t)(c->max_mel_frames - c->overlap_frames) * c->hop_length;
-    size_t idx = 0;
-    for (size_t pos = 0; pos < n; pos += step, idx++) {
-        const size_t end = std::min(pos + max_s, n);
-        if (out && idx < cap) { out[idx].start_sample = pos; out[idx].end_sample = end; out[idx].index = idx; out[idx].is_last = end >= n; }
-    }
-    *n_chunks = idx; return VOX_OK;
-}
-
-// mel tables (audio/mel.rs:260-349), computed on the host exactly as the reference does (f32 math)
-static float hz_to_mel(float f) {
-    const float F_SP = 200.0f / 3.0f, MIN_LOG_HZ = 1000.0f, MIN_LOG_MEL = MIN_LOG_HZ / F_SP, LOGSTEP = 0.06875174f;
-    return f < MIN_LOG_HZ ? f / F_SP : MIN_LOG_MEL + std::log(f / MIN_LOG_HZ) / LOGSTEP;
-}
-static float mel_to_hz(float m) {
-    const float F_SP = 200.0f / 3.0f, MIN_LOG_HZ = 1000.0f, MIN_LOG_MEL = MIN_LOG_HZ / F_SP, LOGSTEP = 0.06875174f;
-    return m < MIN_LOG_MEL ? m * F_SP : MIN_LOG_HZ * std::exp((m - MIN_LOG_MEL) * LOGSTEP);
-}
-static void build_filterbank(float* fb) {
-    const int n_mels = 128, n_freqs = 201;
-    const float mel_min = hz_to_mel(0.0f), mel_max = hz_to_mel(8000.0f);
-    float hz[130], fr[201];
-    for (int i = 0; i <= n_mels + 1; i++) hz[i] = mel_to_hz(mel_min + (mel_max - mel_min) * (float)i / (float)(n_mels + 1));
-    for (int j = 0; j < n_freqs; j++) fr[j] = (float)j * 16000.0f / 400.0f;
-    std::memset(fb, 0, sizeof(float) * n_mels * n_freqs);
-    for (int i = 0; i < n_mels; i++) {
-        const float lo = hz[i], ce = hz[i + 1], up = hz[i + 2];
-        for (int j = 0; j < n_freqs; j++) {
-            if (fr[j] >= lo && fr[j] <= ce && ce > lo) fb[i * n_freqs + j] = (fr[j] - lo) / (ce - lo);
-            else if (fr[j] > ce && fr[j] <= up && up > ce) fb[i * n_freqs + j] = (up - fr[j]) / (up - ce);
-        }
-        const float bw = hz[i + 2] - hz[i];
-        if (bw > 0.0f) { const float en = 2.0f / bw; for (int j = 0; j < n_freqs; j++) fb[i * n_freqs + j] *= en; }
-    }
-}
-static void build_hann(int len, float* w) {
-    const float PI = 3.14159265358979323846f;
-    for (int i = 0; i < len; i++) w[i] = 0.5f * (1.0f - std::cos(2.0f * PI * (float)i / (float)len));
-}
-extern "C" int32_t vox_mel_num_frames(size_t n, size_t* out) { ARGCHK(out, "null out"); *out = (n + 400 - 400) / 160; return VOX_OK; }   // mel.rs:175-182
-extern "C" int32_t vox_mel_filterbank(float* out) { ARGCHK(out, "null out"); build_filterbank(out); return VOX_OK; }
-extern "C" int32_t vox_hann_window(int32_t len, float* out) { ARGCHK(out && len > 0, "bad argument"); build_hann(len, out); return VOX_OK; }
-
 static int32_t ctx_mel_tables(vox_ctx* c, MelTables* t) {
     if (!c->mel_ready) {
         std::vector<float> win(400), ct(400), st(400), fb(128 * 201);
@@ -344,53 +264,6 @@ extern "C" int32_t vox_mel_compute_log(vox_ctx* c, const float* samples, size_t 
     HIPCHK(launch_mel(din.as<float>(), (long)n, 0, 0, nullptr, t, dout.as<float>(), (int)T, 0, c->stream));
     HIPCHK(hipMemcpyAsync(out, dout.p, T * 128 * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    return VOX_OK;
-}
-
-// ---- sample-rate conversion (audio/resample.rs:16-52).  The reference's whole resampler is two calls into rubato 1.0 (Cargo.toml:41), a third-party crate
-// that is not in the tree: Fft::<f32>::new(sr_in, sr_out, 1024, 2, 1, FixedSync::Input) and process_all_into_buffer.  What is implemented is that crate's
-// published algorithm (synchronous FFT resampler; restated a second time, independently, by the test-side CPU checker; PARITY UNPINNED against the crate itself):
-//   plan    gcd; fft_chunks = ceil(f32(1024) / f32(2) / f32(sr_in / gcd)); fft_in = fft_chunks * sr_in / gcd; fft_out = fft_chunks * sr_out / gcd
-//   filter  fft_in taps, f32 arithmetic: (periodic 4-term Blackman-Harris window)^2 * sinc((x - fft_in / 2) * cutoff), unit sum, / (2 fft_in);
-//           cutoff = 0.4^(16 / fft_in), times fft_out / fft_in when down-sampling
-//   blocks  zero-pad to 2 fft_in, FFT, keep new_len bins (fft_out down, fft_in + 1 up) times the filter spectrum, inverse FFT of length 2 fft_out, overlap-add
-//   output  drop output_delay = fft_out / 2 samples, keep ceil(n_in * (f64(sr_out) / f64(sr_in)))
-// On the device the block pipeline is one fixed matrix (vox_kernels.hip resample_*_kernel), built once per rate pair and kept in the context.
-struct ResamplePlan { long fft_in = 0, fft_out = 0, new_len = 0, delay = 0; float cutoff = 0.f; };
-static long gcd_l(long a, long b) { while (b) { long t = a % b; a = b; b = t; } return a; }
-static ResamplePlan resample_plan_make(uint32_t sr_in, uint32_t sr_out) {
-    ResamplePlan p; const long g = gcd_l(sr_in, sr_out), min_in = sr_in / g, min_out = sr_out / g;
-    const long chunks = (long)std::ceil(1024.0f / 2.0f / (float)min_in);
-    p.fft_in = chunks * min_in; p.fft_out = chunks * min_out;
-    const float base = std::pow(0.4f, 16.0f / (float)p.fft_in);
-    p.cutoff = p.fft_in > p.fft_out ? base * (float)p.fft_out / (float)p.fft_in : base;
-    p.new_len = p.fft_in < p.fft_out ? p.fft_in + 1 : p.fft_out; p.delay = p.fft_out / 2;
-    return p;
-}
-static std::vector<float> resample_taps(const ResamplePlan& p) {
-    const long n = p.fft_in; std::vector<float> h((size_t)n);
-    const float npf = (float)n, pi = (float)M_PI, pi2 = 2.0f * pi, pi4 = 4.0f * pi, pi6 = 6.0f * pi;
-    float sum = 0.f;
-    for (long x = 0; x < n; x++) {
-        const float xf = (float)x;
-        const float bh = 0.35875f - 0.48829f * std::cos(pi2 * xf / npf) + 0.14128f * std::cos(pi4 * xf / npf) - 0.01168f * std::cos(pi6 * xf / npf);
-        const float v = (xf - (float)(n / 2)) * p.cutoff;
-        const float sinc = v == 0.f ? 1.0f : std::sin(v * pi) / (v * pi);
-        h[(size_t)x] = bh * bh * sinc; sum += h[(size_t)x];
-    }
-    for (auto& v : h) v = v / sum / (float)(2 * n);
-    return h;
-}
-// largest block matrix kept on the device (2 fft_out x fft_in f32): every pair of standard audio rates needs <= 9 MB; co-prime rates would need FFTs of sr_in points
-static constexpr size_t RESAMPLE_MATRIX_MAX = (size_t)64 << 20;
-extern "C" int32_t vox_resample_len(size_t n_in, uint32_t sr_in, uint32_t sr_out, size_t* n_out) {
-    ARGCHK(n_out && sr_in > 0 && sr_out > 0, "bad argument");
-    *n_out = sr_in == sr_out ? n_in : (size_t)std::ceil(((double)sr_out / (double)sr_in) * (double)n_in); return VOX_OK;      // rubato: (resample_ratio() * len).ceil()
-}
-// the size of a plan's block matrix, or the refusal of a rate pair whose blocks are too large (shared by vox_resample and the streams fed at their capture rate)
-static int32_t resample_matrix_bytes(uint32_t sr_in, uint32_t sr_out, const ResamplePlan& p, size_t* bytes) {
-    *bytes = (size_t)p.fft_in * 2 * (size_t)p.fft_out * 4;
-    if (*bytes > RESAMPLE_MATRIX_MAX) return fail(VOX_ERR_UNSUPPORTED, "resample %u -> %u Hz: FFT blocks of %ld -> %ld samples are not supported (rates must share a large common divisor)", sr_in, sr_out, p.fft_in, p.fft_out);
     return VOX_OK;
 }
 // a plan's block matrix At[fft_in][2 fft_out] in a fresh device buffer the caller owns (the context's cache below, a vox_stream): the same taps, spectrum and kernel
@@ -443,146 +316,6 @@ extern "C" int32_t vox_resample(vox_ctx* c, const float* in, size_t n_in, uint32
     if (mem_kind != VOX_MEM_DEVICE) HIPCHK(hipMemcpyAsync(out, d_out, no * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return VOX_OK;
-}
-// the plan and the filter taps (host; fft_in floats) -- lets the parity tests check the design independently of the kernels
-extern "C" int32_t vox_resample_plan(uint32_t sr_in, uint32_t sr_out, int32_t* fft_in, int32_t* fft_out, int32_t* delay, float* cutoff, float* taps, size_t cap) {
-    ARGCHK(fft_in && fft_out && delay && cutoff && sr_in > 0 && sr_out > 0, "bad argument");
-    const ResamplePlan p = resample_plan_make(sr_in, sr_out);
-    ARGCHK(p.fft_in <= INT32_MAX && p.fft_out <= INT32_MAX, "rates too far from a common divisor");
-    *fft_in = (int32_t)p.fft_in; *fft_out = (int32_t)p.fft_out; *delay = (int32_t)p.delay; *cutoff = p.cutoff;
-    if (taps) { ARGCHK(cap >= (size_t)p.fft_in, "taps buffer too small (%zu < %ld floats)", cap, p.fft_in); const std::vector<float> h = resample_taps(p); std::memcpy(taps, h.data(), h.size() * 4); }
-    return VOX_OK;
-}
-
-extern "C" int32_t vox_time_embedding(float t, int32_t dim, float* out) {   // models/time_embedding.rs:41-71
-    ARGCHK(out && dim > 0 && dim % 2 == 0, "bad argument");
-    const int half = dim / 2; const float log_theta = std::log(10000.0f);
-    for (int i = 0; i < half; i++) {
-        const float freq = std::exp(-log_theta * (float)i / (float)half), ang = t * freq;
-        out[i] = std::cos(ang); out[half + i] = std::sin(ang);
-    }
-    return VOX_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// GGUF reader (gguf/reader.rs:13-223)
-// ------------------------------------------------------------------------------------------------
-struct GTensor { std::string name; uint32_t ndims = 0; uint64_t dims[4] = {0, 0, 0, 0}; uint32_t dtype = 0; uint64_t offset = 0, nbytes = 0; };
-struct vox_gguf {
-    uint8_t* map = nullptr; size_t size = 0; uint32_t version = 0;
-    int own = 1;                    // 1: mmap'ed file (munmap), 0: borrowed caller memory (from_bytes), 2: heap copy of shards (free)
-    std::vector<GTensor> tensors; std::map<std::string, size_t> index; uint64_t data_off = 0;
-    const GTensor* find(const std::string& n) const { auto it = index.find(n); return it == index.end() ? nullptr : &tensors[it->second]; }
-    const uint8_t* data(const GTensor* t) const { return map + data_off + t->offset; }
-};
-namespace {
-struct Cur {
-    const uint8_t* p; size_t pos, size; bool bad = false;
-    template <class T> T rd() { T v{}; if (pos + sizeof(T) > size) { bad = true; return v; } std::memcpy(&v, p + pos, sizeof(T)); pos += sizeof(T); return v; }
-    std::string str() { uint64_t len = rd<uint64_t>(); if (bad || len > size - pos) { bad = true; return {}; } std::string s((const char*)p + pos, len); pos += len; return s; }
-    void skip(size_t n) { if (n > size - pos) bad = true; else pos += n; }
-    int skip_value(uint32_t ty) {   // gguf/reader.rs:327-376
-        switch (ty) {
-        case 0: case 1: case 7: skip(1); break;
-        case 2: case 3: skip(2); break;
-        case 4: case 5: case 6: skip(4); break;
-        case 8: (void)str(); break;
-        case 9: { uint32_t et = rd<uint32_t>(); uint64_t cnt = rd<uint64_t>(); for (uint64_t i = 0; i < cnt && !bad; i++) if (skip_value(et)) return 1; break; }
-        case 10: case 11: case 12: skip(8); break;
-        default: return 1;
-        }
-        return 0;
-    }
-};
-}  // namespace
-
-extern "C" int32_t vox_gguf_close(vox_gguf* g) {
-    if (g) { if (g->map && g->own == 1) munmap(g->map, g->size); else if (g->map && g->own == 2) std::free(g->map); delete g; }
-    return VOX_OK;
-}
-// parse the header of g->map / g->size (takes ownership of g: closes it on error)
-static int32_t gguf_parse(vox_gguf* g, vox_gguf** out) {
-    Cur c{g->map, 0, g->size};
-    const uint32_t magic = c.rd<uint32_t>();
-    if (c.bad || magic != 0x46554747u) { vox_gguf_close(g); return fail(VOX_ERR_IO, "Invalid GGUF magic: 0x%08X (expected 0x46554747)", magic); }
-    g->version = c.rd<uint32_t>();
-    if (g->version != 2 && g->version != 3) { uint32_t v = g->version; vox_gguf_close(g); return fail(VOX_ERR_IO, "Unsupported GGUF version: %u (expected 2 or 3)", v); }
-    const uint64_t nt = c.rd<uint64_t>(), nkv = c.rd<uint64_t>();
-    for (uint64_t i = 0; i < nkv && !c.bad; i++) {
-        (void)c.str(); const uint32_t ty = c.rd<uint32_t>();
-        if (c.skip_value(ty)) { vox_gguf_close(g); return fail(VOX_ERR_IO, "Unknown GGUF metadata value type"); }
-    }
-    if (c.bad || nt > (1u << 24)) { vox_gguf_close(g); return fail(VOX_ERR_IO, "Failed to parse GGUF metadata"); }
-    g->tensors.resize(nt);
-    for (uint64_t i = 0; i < nt; i++) {
-        GTensor& t = g->tensors[i];
-        t.name = c.str(); t.ndims = c.rd<uint32_t>();
-        if (c.bad || t.ndims > 4) { vox_gguf_close(g); return fail(VOX_ERR_IO, "Failed to read tensor %llu", (unsigned long long)i); }
-        uint64_t ne = 1; bool ovf = false;
-        for (uint32_t d = 0; d < t.ndims; d++) { t.dims[d] = c.rd<uint64_t>(); if (__builtin_mul_overflow(ne, t.dims[d], &ne)) ovf = true; }
-        t.dtype = c.rd<uint32_t>(); t.offset = c.rd<uint64_t>();
-        if (c.bad) { vox_gguf_close(g); return fail(VOX_ERR_IO, "Failed to read tensor %llu", (unsigned long long)i); }
-        if (ovf || ne > (1ull << 60)) { std::string n = t.name; vox_gguf_close(g); return fail(VOX_ERR_IO, "tensor '%s' has an element count that overflows", n.c_str()); }
-        if (t.dtype > 2) { uint32_t d = t.dtype; vox_gguf_close(g); return fail(VOX_ERR_IO, "Unsupported GGML dtype code: %u", d); }
-        t.nbytes = t.dtype == 0 ? ne * 4 : t.dtype == 1 ? ne * 2 : (ne / 32) * 18;     // reader.rs:37-48
-        g->index[t.name] = i;
-    }
-    g->data_off = (c.pos + 31) / 32 * 32;                                                // reader.rs:177-179
-    for (auto& t : g->tensors) {    // checked: a crafted offset / size must not wrap around the bounds test
-        uint64_t end = 0;
-        if (g->data_off > g->size || __builtin_add_overflow(g->data_off, t.offset, &end) || __builtin_add_overflow(end, t.nbytes, &end) || end > g->size) {
-            std::string n = t.name; vox_gguf_close(g); return fail(VOX_ERR_IO, "tensor '%s' exceeds file size", n.c_str());
-        }
-    }
-    *out = g; return VOX_OK;
-}
-extern "C" int32_t vox_gguf_open(const char* path, vox_gguf** out) {
-    ARGCHK(path && out, "null argument");
-    int fd = open(path, O_RDONLY);
-    if (fd < 0) return fail(VOX_ERR_IO, "cannot open %s: %s", path, strerror(errno));
-    struct stat st;
-    if (fstat(fd, &st) != 0 || st.st_size < 24) { close(fd); return fail(VOX_ERR_IO, "%s is not a GGUF file (stat failed or shorter than a header)", path); }
-    void* mp = mmap(nullptr, st.st_size, PROT_READ, MAP_PRIVATE, fd, 0); close(fd);
-    if (mp == MAP_FAILED) return fail(VOX_ERR_IO, "mmap of %s failed", path);
-    vox_gguf* g = new vox_gguf(); g->map = (uint8_t*)mp; g->size = st.st_size; g->own = 1;
-    return gguf_parse(g, out);
-}
-// GgufReader::from_bytes (gguf/reader.rs:98-103): parse a GGUF image that is already in host memory.  The memory is BORROWED: it
-// must stay valid and unchanged until vox_gguf_close.
-extern "C" int32_t vox_gguf_open_memory(const void* data, size_t size, vox_gguf** out) {
-    ARGCHK(data && out, "null argument"); ARGCHK(size >= 24, "GGUF image too small (%zu bytes)", size);
-    vox_gguf* g = new vox_gguf(); g->map = (uint8_t*)const_cast<void*>(data); g->size = size; g->own = 0;
-    return gguf_parse(g, out);
-}
-// Q4ModelLoader::from_shards (gguf/loader.rs:101-107; the reference's ShardedCursor reads <= 512 MB pieces as one stream): the shards
-// are the consecutive pieces of ONE GGUF image; they are concatenated into a private host copy.
-extern "C" int32_t vox_gguf_open_shards(const void* const* shards, const size_t* sizes, int32_t n, vox_gguf** out) {
-    ARGCHK(shards && sizes && out && n > 0, "bad shard list");
-    size_t total = 0; for (int i = 0; i < n; i++) { ARGCHK(shards[i] || sizes[i] == 0, "null shard %d", i); total += sizes[i]; }
-    ARGCHK(total >= 24, "GGUF image too small (%zu bytes)", total);
-    uint8_t* buf = (uint8_t*)std::malloc(total); if (!buf) return fail(VOX_ERR_IO, "out of host memory for %zu bytes of shards", total);
-    size_t o = 0; for (int i = 0; i < n; i++) { std::memcpy(buf + o, shards[i], sizes[i]); o += sizes[i]; }
-    vox_gguf* g = new vox_gguf(); g->map = buf; g->size = total; g->own = 2;
-    return gguf_parse(g, out);
-}
-extern "C" int32_t vox_gguf_version(const vox_gguf* g, uint32_t* out) { ARGCHK(g && out, "null argument"); *out = g->version; return VOX_OK; }
-extern "C" int32_t vox_gguf_tensor_count(const vox_gguf* g, uint64_t* out) { ARGCHK(g && out, "null argument"); *out = g->tensors.size(); return VOX_OK; }
-extern "C" int32_t vox_gguf_tensor_name(const vox_gguf* g, uint64_t i, const char** out) {
-    ARGCHK(g && out, "null argument"); ARGCHK(i < g->tensors.size(), "tensor index out of range"); *out = g->tensors[i].name.c_str(); return VOX_OK;
-}
-extern "C" int32_t vox_gguf_tensor_info(const vox_gguf* g, const char* name, uint64_t dims[4], uint32_t* ndims, uint32_t* dtype, uint64_t* nbytes) {
-    ARGCHK(g && name && dims && ndims && dtype && nbytes, "null argument");
-    const GTensor* t = g->find(name);
-    if (!t) return fail(VOX_ERR_NOTFOUND, "Tensor '%s' not found in GGUF", name);
-    for (uint32_t d = 0; d < 4; d++) dims[d] = d < t->ndims ? t->dims[d] : 0;
-    *ndims = t->ndims; *dtype = t->dtype; *nbytes = t->nbytes; return VOX_OK;
-}
-extern "C" int32_t vox_gguf_tensor_data(const vox_gguf* g, const char* name, void* dst, size_t cap) {
-    ARGCHK(g && name && dst, "null argument");
-    const GTensor* t = g->find(name);
-    if (!t) return fail(VOX_ERR_NOTFOUND, "Tensor '%s' not found in GGUF", name);
-    ARGCHK(cap >= t->nbytes, "destination too small for '%s' (%zu < %llu)", name, cap, (unsigned long long)t->nbytes);
-    std::memcpy(dst, g->data(t), t->nbytes); return VOX_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -817,7 +550,6 @@ struct PrefixState {
     float* capture = nullptr; int capture_rows = 0;      // while the encoder part is being built: encode_batch_dev stores every layer's k | v rows here
     uint64_t enc_bytes = 0, dec_bytes = 0;
 };
-static const int VOX_PREFIX_TOKENS = 38, VOX_TOK_BOS = 1, VOX_TOK_STREAMING_PAD = 32;      // the decoder's fixed prefix: BOS + 37 x STREAMING_PAD (gguf/model.rs:891-892)
 // the prefix itself, built here and nowhere else; static storage, so an upload from it has nothing to keep alive
 static const struct PrefixTokens {
     int32_t t[VOX_PREFIX_TOKENS];
@@ -2912,71 +2644,10 @@ static int32_t transcribe_batch_impl(vox_model* m, int32_t n, const float* const
 // Step cost of G lock-step groups in ms, measured on the FLEURS-like corpus (profiles/r05_continuous_sweep.txt: decode time net of graph captures / steps; 3 interpolated):
 // Five to eight groups (80 .. 128 slots, end of round 6): TWO wide chains per step, ceil(n / 2) and floor(n / 2) groups each -- measured (chains then forked) with tools/wide_probe.py
 // (profiles/r06_wide_split.txt); only on a context that owns its GPU.
-static const int kMaxGroups = 8;
 static const double kStepMs[9] = {0.0, 1.84, 2.08, 2.75, 3.15, 3.55, 3.80, 4.35, 4.70};      // (four groups: the wide step, round 6 -- 3.40 on four forked chains)
 // ... with the batched decode-layer engine serving the steps of <= 2 active groups (one group: decode_engine_b16_kernel<1>, 1.06 ms + tail; two: the two-group launch,
 // 1.60 ms + tail; three and four groups stay on the launch chains -- a two-group launch + a one- or two-group launch back to back: 2.9 / 3.4 ms against 2.75 / 3.40)
 static const double kStepMsEng[9] = {0.0, 1.17, 1.77, 2.75, 3.15, 3.55, 3.80, 4.35, 4.70};      // (four groups: the wide step, round 6)
-// Step costs the planner prices a session with: the table `base`, corrected by what the context has measured (`meas`, 0 = form not seen yet) -- a form seen before costs
-// what it cost (clock, a shared GPU, another geometry), a form not seen yet the table's value times the mean measured / table ratio of the forms that were.  calib off
-// (VOX_BATCH_NO_CALIB=1): the table alone.
-static void step_costs(const double* base, const double* meas, bool calib, bool shared, double* out) {
-    double ratio = 0.0; int nr = 0;
-    for (int g2 = 1; g2 <= kMaxGroups; g2++) if (calib && meas[g2] > 0.0) { ratio += meas[g2] / base[g2]; nr++; }
-    ratio = nr ? std::min(4.0, std::max(0.25, ratio / nr)) : 1.0;
-    // The common factor (clock, a GPU shared with another session) is taken as measured; a form's deviation from it is trusted within +-15 % only, and a step of more
-    // groups never costs less than one of fewer: next to a second session on the GPU (tools/two_sessions_probe.py) the per-form figures scatter (a 3-group step "measured"
-    // at 5.35 ms against 4.18 for four groups made the next session plan 48 slots instead of 64: 4.71 s instead of 3.77 s for the corpus)
-    out[0] = 0.0;
-    for (int g2 = 1; g2 <= kMaxGroups; g2++) {
-        const double common = base[g2] * ratio;
-        out[g2] = (calib && !shared && meas[g2] > 0.0) ? common * std::min(1.15, std::max(0.85, meas[g2] / common)) : common;      // (a shared GPU: the common factor only)
-        out[g2] = std::max(out[g2], out[g2 - 1]);
-    }
-}
-struct SlotPlan { int G = 0; std::vector<std::vector<int>> queue; std::vector<int> steps_g; double cost_ms = 0.0; };
-// jobs: (decode steps, utterance) with steps >= 1.  LPT onto 16 G slots, slots ordered by load (so the groups retire last to first), G by the cost model.
-static SlotPlan plan_slots(const std::vector<std::pair<int, int>>& jobs_in, int force_G, const double* step_ms, int max_groups = 4) {
-    std::vector<std::pair<int, int>> jobs = jobs_in;
-    std::stable_sort(jobs.begin(), jobs.end(), [](const std::pair<int, int>& a, const std::pair<int, int>& b) { return a.first > b.first; });
-    SlotPlan best;
-    const int g_max = std::max(1, std::min(max_groups, ((int)jobs.size() + 15) / 16));
-    for (int G = 1; G <= g_max; G++) {
-        if (force_G > 0 && G != std::min(force_G, g_max)) continue;
-        const int Sl = 16 * G;
-        std::vector<long> load(Sl, 0); std::vector<std::vector<int>> q(Sl);
-        for (auto& j : jobs) { int b = 0; for (int s2 = 1; s2 < Sl; s2++) if (load[s2] < load[b]) b = s2; load[b] += j.first; q[b].push_back(j.second); }
-        std::vector<int> order(Sl); for (int i = 0; i < Sl; i++) order[i] = i;
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return load[a] > load[b]; });
-        SlotPlan pl; pl.G = G; pl.queue.resize(Sl); pl.steps_g.assign(G, 0);
-        for (int i = 0; i < Sl; i++) { pl.queue[i] = q[order[i]]; pl.steps_g[i / 16] = std::max(pl.steps_g[i / 16], (int)load[order[i]]); }
-        for (int k = 0; k < G; k++) pl.cost_ms += (double)(pl.steps_g[k] - (k + 1 < G ? pl.steps_g[k + 1] : 0)) * step_ms[k + 1];
-        if (best.G == 0 || pl.cost_ms <= best.cost_ms) best = pl;
-    }
-    return best;
-}
-// A plan as the decode loop uses it: the slot queues flattened (slot sl's k-th utterance at h_queue[sl q_stride + k], -1 behind its last), the steps of the whole
-// decode, and how long each group RUNS.  A group retires when its queues are empty -- but every distinct set of active groups is a graph capture + instantiation
-// (~10 ms): a group that would retire fewer than kRetireSlack steps before the next longer one keeps running with idle slots instead (harmless: idle rows compute on zeros).
-static const int kRetireSlack = 12;
-struct SlotSchedule {
-    SlotPlan plan; int G = 1, Sl = 16, q_stride = 1, steps = 0; std::vector<int> h_queue; int run_g[kMaxGroups] = {0, 0, 0, 0, 0, 0, 0, 0};
-    uint32_t active_at(int t) const { uint32_t a = 0; for (int gi = 0; gi < G; gi++) if (t < run_g[gi]) a |= 1u << gi; return a; }
-};
-static SlotSchedule slot_schedule(const std::vector<std::pair<int, int>>& jobs, int force_G, const double* step_ms, int max_groups) {
-    SlotSchedule z; z.plan = plan_slots(jobs, force_G, step_ms, max_groups);
-    const SlotPlan& plan = z.plan;
-    z.G = std::max(plan.G, 1); z.Sl = 16 * z.G;
-    for (auto& q : plan.queue) z.q_stride = std::max(z.q_stride, (int)q.size() + 1);
-    z.h_queue.assign((size_t)z.Sl * z.q_stride, -1);
-    for (size_t sl = 0; sl < plan.queue.size(); sl++) for (size_t k = 0; k < plan.queue[sl].size(); k++) z.h_queue[sl * z.q_stride + k] = plan.queue[sl][k];
-    z.steps = plan.steps_g.empty() ? 0 : plan.steps_g[0];
-    for (size_t gi = 0; gi < plan.steps_g.size(); gi++) z.run_g[gi] = plan.steps_g[gi];
-    for (int gi = 1; gi < z.G; gi++) {      // walk from the longest group down: snap a group to the previous one's run length when it is close
-        if (z.run_g[gi - 1] - plan.steps_g[gi] < kRetireSlack) z.run_g[gi] = z.run_g[gi - 1];
-    }
-    return z;
-}
 // the wide step's geometry: every decoder layer the shape of layer 0, tile-ordered Q4 copies, no biases, plans for 2 .. 4 groups per chain
 static bool wide_geom_ok(const vox_model* m) {
     const vox_model_cfg& c = m->cfg;
@@ -3351,24 +3022,6 @@ static int32_t transcribe_continuous_impl(vox_model* m, int32_t n, const float* 
     m->timings.preprocess_ms = z.pre_ms; m->timings.encode_ms = z.enc_ms; m->timings.decode_ms = z.pf_ms + (now_ms() - z.t1); m->timings.total_ms = now_ms() - z.t0;
     m->timings.decode_tokens = total; m->timings.graph_replays = z.replays;
     if (z.pol.verbose) z.report();
-    return VOX_OK;
-}
-extern "C" int32_t vox_debug_step_costs(const double* base, const double* meas, int32_t calib, int32_t shared, double* out) {
-    ARGCHK(base && meas && out, "null argument");
-    step_costs(base, meas, calib != 0, shared != 0, out);
-    return VOX_OK;
-}
-extern "C" int32_t vox_debug_plan_slots(const int32_t* steps, int32_t n, int32_t force_G, int32_t max_groups, const double* step_ms, int32_t* G, int32_t* job_slot,
-                                        int32_t* job_qpos, int32_t* steps_g, int32_t* run_g, double* cost_ms) {
-    ARGCHK(n >= 0 && (steps || n == 0) && step_ms && G && (job_slot || n == 0) && (job_qpos || n == 0) && steps_g && run_g && cost_ms, "null argument");
-    ARGCHK(force_G >= 0 && force_G <= kMaxGroups && max_groups >= 1 && max_groups <= kMaxGroups, "group count out of range");
-    std::vector<std::pair<int, int>> jobs;
-    for (int i = 0; i < n; i++) { ARGCHK(steps[i] >= 1, "job %d: %d steps", i, steps[i]); jobs.emplace_back(steps[i], i); }
-    const SlotSchedule z = slot_schedule(jobs, force_G, step_ms, max_groups);
-    *G = z.G; *cost_ms = z.plan.cost_ms;
-    for (int k = 0; k < kMaxGroups; k++) { steps_g[k] = k < (int)z.plan.steps_g.size() ? z.plan.steps_g[k] : 0; run_g[k] = z.run_g[k]; }
-    for (int sl = 0; sl < z.Sl; sl++)
-        for (int k = 0; k < z.q_stride; k++) { const int j = z.h_queue[(size_t)sl * z.q_stride + k]; if (j >= 0) { job_slot[j] = sl; job_qpos[j] = k; } }
     return VOX_OK;
 }
 
@@ -4161,22 +3814,7 @@ extern "C" int32_t vox_debug_encode_batch(vox_model* m, int32_t n, const float* 
 // ONE call path: push, finish and peek are stream_run (a group's advance and peek: group_run), which hands the call's ids and score records back through SessionOut
 // around the call's one synchronisation; a peek is the mode of it that runs between the two directions of the ring keep (ring_keep) and ends in FeedState::rewind.
 // ------------------------------------------------------------------------------------------------
-static const int STREAM_SAMPLE_RING = 1 << 16;      // samples held on the device (a tick reads 160 (4 R + 2) + 400 of them)
 static const int STREAM_KEEP_ROWS = 1024;           // adapter rows kept for the re-run of unverified engine steps; a push verifies at least this often
-static const int STREAM_FEED_CHUNK = 1 << 15;       // input-rate samples a rate stream's ring takes beyond two blocks; 16-bit samples of the host staging buffer
-static const int STREAM_IN_RING_MAX = 1 << 20;      // largest input ring (samples): rate pairs whose two blocks + a feed chunk do not fit are refused at create
-// The host mirror of ONE live session's feed -- a solo vox_stream's, a group member's: everything feed_plan and feed_pass below read and advance.
-struct FeedState {
-    uint32_t sr = 16000; ResamplePlan rp; float* At = nullptr;      // the rate the caller feeds at; at any rate but 16000 a COPY of its plan and the block matrix in use
-    float* in_ring = nullptr; int in_ring_n = 0;                    // ... and the session's own input-rate ring (a power of two: stream_rate_plan)
-    int64_t n_pushed = 0, n_written = 0;      // samples the caller gave (at sr); samples in the 16 kHz ring (after finish: + the right pad)
-    int64_t in_written = 0;                   // input-rate samples copied into the input ring so far
-    int pos = 0, ids_out = 0; bool finished = false;      // decoder position of the next tick; ids handed to the caller; the utterance has ended (until a reset)
-    void restart(int PC) { n_pushed = n_written = in_written = 0; pos = PC; ids_out = 0; finished = false; }      // create / reset: the session starts behind the prefix
-    // what a peek takes back: its tail adds no input samples (in_written stays) and hands out no ids of the session's own (ids_out stays)
-    struct Mark { int64_t n_written; int pos; };
-    Mark mark() const { return Mark{n_written, pos}; } void rewind(const Mark& k) { n_written = k.n_written; pos = k.pos; finished = false; }
-};
 // A session's scores (vox_stream_set_scores; DESIGN.md section 8, "Scores"): the device records the score kernel writes, one per id of the utterance, and their host
 // mirror -- one record per id handed out, the ones of a call copied in front of its synchronisation.  Nothing is allocated before the first set(1).
 struct ScoreState {
@@ -4287,10 +3925,6 @@ struct vox_stream {
     struct { KeepArea keep; bool active = false; DecPlanes old; } peek;
 };
 
-static long stream_spp(int R) { return 640L * R; }      // samples per decoder position: R encoder rows x 4 frames x 160
-// decoder positions determined after n samples of an unfinished stream: position p's last frame 4 R p + 4 R - 1 reads padded samples up to 640 R (p + 1) + 40
-static long stream_positions(long left, int R, int64_t n) { const int64_t a = left + n - 40; return a < 0 ? 0 : (long)(a / stream_spp(R)); }
-
 // the buffers of a round of up to n sessions (n = 1: a solo stream's tick), carved from one allocation; returns its size in floats (base may be null).
 // A slot's mel halo is padded from 4 R + 3 to 4 R + 4 frames and its conv1 block from 2 R + 1 to 2 R + 2 rows, so that slots lie a whole number of window strides
 // apart and each conv is ONE im2col GEMM over all slots (stream_encode_round); h: the decode step's input rows.
@@ -4302,35 +3936,6 @@ static size_t stream_ws_carve(const vox_model* m, int n, float* base, StreamWs* 
     take(w->halo, N * (4 * R + 4) * c.n_mels); take(w->c1, N * (2 * R + 2) * D); take(w->c2, N * (R + 1) * D); take(w->x, N * R * D); take(w->xn, N * R * D);
     take(w->qkv, N * R * QD * 3); take(w->att, N * R * QD); take(w->ffn, N * R * c.enc_ffn); take(w->ah, N * m->ad0.w.N); take(w->arow, N * c.dec_dim); take(w->h, N * c.dec_dim);
     return o;
-}
-
-// the 16 kHz samples final after n input samples at the plan's rate: output i reads block (i + delay) / fft_out in full and the tail of the block before, nothing else
-static int64_t stream_avail16(const ResamplePlan& p, int64_t n) { return std::max<int64_t>(0, n / p.fft_in * p.fft_out - p.delay); }
-// the 16 kHz samples a stream at rate sr holds after n input samples (finished: of an n-sample utterance)
-static int32_t stream_samples16(uint32_t sr, const ResamplePlan& p, size_t n, bool finished, size_t* n16) {
-    if (sr == 16000) { *n16 = n; return VOX_OK; }
-    if (finished) return vox_resample_len(n, sr, 16000, n16);
-    *n16 = (size_t)stream_avail16(p, (int64_t)n); return VOX_OK;
-}
-static int32_t stream_schedule16(size_t n16, bool finished, int32_t* positions, int32_t* ids) {
-    vox_pad_cfg pc; vox_pad_cfg_voxtral(&pc);
-    const long left = (long)pad_left(&pc); const int R = 4;
-    long P;
-    if (finished) { size_t total; VOXCHK(vox_pad_len(n16, &pc, &total)); P = (long)(total / (size_t)stream_spp(R)); *ids = (int32_t)std::max(P - VOX_PREFIX_TOKENS, 0L); }
-    else { P = stream_positions(left, R, (int64_t)n16); *ids = (int32_t)std::max(P - (VOX_PREFIX_TOKENS - 1), 0L); }
-    *positions = (int32_t)P;
-    return VOX_OK;
-}
-extern "C" int32_t vox_stream_schedule(size_t n_samples, int32_t finished, int32_t* positions, int32_t* ids) {
-    ARGCHK(positions && ids, "null argument"); ARGCHK(n_samples <= ((size_t)1 << 40), "sample count out of range");
-    return stream_schedule16(n_samples, finished != 0, positions, ids);
-}
-extern "C" int32_t vox_stream_schedule_rate(size_t n_samples, uint32_t sample_rate, int32_t finished, int32_t* positions, int32_t* ids, size_t* samples_16k) {
-    ARGCHK(positions && ids && samples_16k, "null argument"); ARGCHK(sample_rate > 0, "bad sample rate 0"); ARGCHK(n_samples <= ((size_t)1 << 40), "sample count out of range");
-    ResamplePlan p;
-    if (sample_rate != 16000) { p = resample_plan_make(sample_rate, 16000); size_t bytes; VOXCHK(resample_matrix_bytes(sample_rate, 16000, p, &bytes)); }
-    VOXCHK(stream_samples16(sample_rate, p, n_samples, finished != 0, samples_16k));
-    return stream_schedule16(*samples_16k, finished != 0, positions, ids);
 }
 
 static int32_t stream_dec_alloc(vox_stream* st, int rows) {      // a fresh decoder cache of `rows` rows (the old one is freed)
@@ -4429,17 +4034,6 @@ static int32_t stream_geometry(vox_model* m, int32_t enc_capacity_rows, int32_t 
     ARGCHK(maxp > VOX_PREFIX_TOKENS && maxp <= pos_limit, "max_positions %d out of range (%d..%d)", maxp, VOX_PREFIX_TOKENS + 1, pos_limit);
     g->RC = RC; g->PC = PC; g->cap = cap; g->max_pos = maxp;
     { vox_pad_cfg pc; vox_pad_cfg_voxtral(&pc); g->left = (long)pad_left(&pc); }
-    return VOX_OK;
-}
-// what a session fed at sample_rate != 16000 needs (a solo stream, a group's member): the plan, the size of its block matrix, the size of its input ring -- a power of
-// two holding two blocks and a feed chunk -- or the refusal of a rate pair vox_resample refuses or whose blocks do not fit the ring
-static int32_t stream_rate_plan(uint32_t sample_rate, ResamplePlan* rp, size_t* rs_bytes, int* in_ring_n) {
-    *rp = resample_plan_make(sample_rate, 16000);
-    VOXCHK(resample_matrix_bytes(sample_rate, 16000, *rp, rs_bytes));
-    if (2 * rp->fft_in + STREAM_FEED_CHUNK > STREAM_IN_RING_MAX)
-        return fail(VOX_ERR_UNSUPPORTED, "a stream at %u Hz: two blocks of %ld samples do not fit its input ring of %d", sample_rate, rp->fft_in, STREAM_IN_RING_MAX);
-    int n = 1; while (n < 2 * rp->fft_in + STREAM_FEED_CHUNK) n <<= 1;
-    *in_ring_n = n;
     return VOX_OK;
 }
 // sample_rate 16000: the 16 kHz stream, nothing more; any other rate: + the input ring and the stream's own block matrix
@@ -4649,86 +4243,10 @@ static int32_t stream_ring_write(vox_stream* st, float* ring, int ring_n, int64_
     }
     return ring_write_f32(s, ring, ring_n, w0, src, at, len);
 }
-// ---- the feed planner: ONE implementation for a solo stream and for every member of a group ("The feed planner").  feed_plan is what a push / finish /
-// advance entry decides before anything changes; feed_pass is one pass of the call, bounded by the session's two rings -- a call may be larger than both.  Pure host
-// arithmetic: the callers turn a pass's amounts into copies, launches and ticks (stream_run; group_stage_pass), vox_debug_stream_feed_passes into rows of numbers.
-// 16 kHz samples a session's ring can take: everything from the oldest sample its next tick (at position pos) reads stays
-static size_t ring_room16(int R, long left, int pos, int64_t n_written) {
-    const long lo = std::max(0L, (4L * R * pos - 3) * 160 - 200 - left);
-    return (size_t)STREAM_SAMPLE_RING - (size_t)(n_written - lo);
-}
-// what one call feeds a session: n samples at its rate, then `right` zeros (the right pad of a finishing session); `done` of the n + right written so far; goal16: the
-// 16 kHz samples the session holds after the call, before the pad; the ticks up to position `target` run in this call and yield `due` ids
-struct FeedPlan { size_t n = 0, right = 0, done = 0, goal16 = 0; int target = 0, due = 0; bool finish = false; };
 // the checks on one entry's own arguments.  `who`: what the message starts with ("" for a solo stream's call, "entry 2: ")
 static int32_t entry_check(const char* who, const void* samples, size_t n, const int32_t* out_ids, int32_t cap) {
     ARGCHK(samples || n == 0, "%snull samples", who); ARGCHK(n <= ((size_t)1 << 36), "%spush of %zu samples", who, n);
     ARGCHK(cap >= 0 && (out_ids || cap == 0), "%sbad output buffer", who);
-    return VOX_OK;
-}
-// every check of a call on one session, nothing changed: a refused call can be repeated.  `who`: the message's subject ("the stream", "entry 2: member 5")
-static int32_t feed_plan(const FeedState& f, int R, long left, int max_pos, size_t n, bool finish, int cap, const char* who, FeedPlan* out) {
-    ARGCHK(!f.finished, "%s is finished: a reset starts its next utterance", who);
-    FeedPlan p; p.n = n; p.finish = finish;
-    VOXCHK(stream_samples16(f.sr, f.rp, (size_t)f.n_pushed + n, finish, &p.goal16));
-    if (finish) {
-        vox_pad_cfg pc; vox_pad_cfg_voxtral(&pc); size_t total; VOXCHK(vox_pad_len(p.goal16, &pc, &total));
-        const int S = (int)(total / (size_t)stream_spp(R));      // the steps at positions 37 .. S - 2 yield the S - 38 ids of the offline path
-        ARGCHK(S - 1 <= max_pos, "%s: finishing would reach decoder position %d of a session created for %d", who, S - 1, max_pos);
-        p.target = std::max(S - 1, f.pos); p.right = total - (size_t)left - p.goal16;
-    } else {
-        const long P = stream_positions(left, R, (int64_t)p.goal16);
-        ARGCHK(P <= max_pos, "%s: the push would reach decoder position %ld of a session created for %d (a reset starts over)", who, P, max_pos);
-        p.target = std::max((int)P, f.pos);
-    }
-    p.due = p.target - f.pos;
-    ARGCHK(cap >= p.due, "%s: out_ids capacity %d < %d ids due", who, cap, p.due);
-    *out = p; return VOX_OK;
-}
-static bool feed_open(const FeedState& f, const FeedPlan& p) { return p.done < p.n + p.right || f.n_written < (int64_t)p.goal16 || f.pos < p.target; }
-// one pass: samples [at, at + n_in) of the call go to the session's FIRST ring at in_w0 (a rate session: its input ring; a 16 kHz session: the 16 kHz ring itself, and
-// n16 == n_in, i0 == in_w0); the 16 kHz samples [i0, i0 + n16) exist after it (a rate session: to be resampled, the input ring holding in_written samples by then);
-// `pad` zeros follow at pad_w0; `ticks` ticks became due
-struct FeedPass {
-    size_t at = 0, n_in = 0, n16 = 0, pad = 0; int64_t in_w0 = 0, i0 = 0, pad_w0 = 0; int ticks = 0;
-    bool idle() const { return n_in == 0 && n16 == 0 && pad == 0 && ticks == 0; }      // an open call's pass is never idle: the callers' stall refusal
-};
-// Advances in_written, n_written and p.done; NOT pos -- the caller runs the ticks.  in_cap: most input samples this pass (a group's 16-bit staging slot).
-// A rate session's input ring keeps everything from block c_next - 1 on, c_next the block of the next 16 kHz sample to be produced: that sample reads the tail of the
-// block before its own.  Its 16 kHz samples are the ones whose blocks are complete -- at the end of the utterance (finish, the last input sample in) all goal16, blocks
-// clipped at its length.  The right pad follows the utterance's last 16 kHz sample, in the same pass where the ring has room.
-static FeedPass feed_pass(FeedState& f, FeedPlan& p, int R, long left, size_t in_cap) {
-    FeedPass q; q.at = p.done;
-    size_t room = ring_room16(R, left, f.pos, f.n_written);
-    const size_t rest = std::min(p.n - std::min(p.done, p.n), in_cap);
-    if (f.sr != 16000) {
-        const int64_t c_next = (f.n_written + f.rp.delay) / f.rp.fft_out, keep_from = std::max<int64_t>(0, c_next - 1) * f.rp.fft_in;
-        q.n_in = std::min(rest, (size_t)f.in_ring_n - (size_t)std::max<int64_t>(0, f.in_written - keep_from));
-        q.in_w0 = f.in_written; f.in_written += (int64_t)q.n_in; p.done += q.n_in;
-        const int64_t have16 = p.finish && p.done >= p.n ? (int64_t)p.goal16 : stream_avail16(f.rp, f.in_written);
-        q.n16 = std::min((size_t)std::max<int64_t>(0, have16 - f.n_written), room); q.i0 = f.n_written;
-    } else {
-        q.n_in = q.n16 = std::min(rest, room); q.in_w0 = q.i0 = f.n_written; p.done += q.n_in;
-    }
-    f.n_written += (int64_t)q.n16; room -= q.n16;
-    if (p.done >= p.n && p.done < p.n + p.right && f.n_written >= (int64_t)p.goal16) {
-        q.pad = std::min(p.n + p.right - p.done, room); q.pad_w0 = f.n_written; f.n_written += (int64_t)q.pad; p.done += q.pad;
-    }
-    q.ticks = std::max(0, (int)std::min<long>(p.target, stream_positions(left, R, f.n_written)) - f.pos);
-    return q;
-}
-
-// ---- a peek's parts, common to a solo stream and a group ("Peek").
-// A peek is ONE pass: a second would size its room from the advanced position and could overwrite samples the session still reads once it is taken back
-static int32_t peek_second_pass(const char* who) { return fail(VOX_ERR_INVALID, "internal: %s: a peek needs a second pass", who); }
-// the most ticks a peek (a finish) of this session can have due: what is still to come is the backlog of a rate session -- 16 kHz samples of its unfinished block, at
-// most fft_out + delay of them -- and the right pad, at most one token less a sample + the extra tokens; a tick takes stream_spp samples, and position p needs 40 beyond.
-// `due` is checked against it.  `who`: what the message starts with ("", "member 3: ")
-static int32_t peek_max_ticks(const FeedState& f, int R, int due, const char* who, int* T) {
-    vox_pad_cfg pc; vox_pad_cfg_voxtral(&pc);
-    const long spt = (long)pad_spt(&pc), right_max = spt - 1 + (long)pc.extra_right_pad_tokens * spt, backlog = f.sr != 16000 ? f.rp.fft_out + f.rp.delay + 1 : 0;
-    *T = (int)((backlog + right_max + 40) / stream_spp(R)) + 1;
-    ARGCHK(due <= *T, "internal: %sa peek of %d ticks, %d at the most by the pad and the rate plan", who, due, *T);
     return VOX_OK;
 }
 // the save area holds `need` floats from here on; its growth is counted in the owner's `bytes`.  `whose`: "stream", "group"
@@ -4836,14 +4354,6 @@ extern "C" int32_t vox_stream_finish(vox_stream* st, int32_t* out_ids, int32_t c
 extern "C" int32_t vox_stream_peek(vox_stream* st, int32_t* out_ids, int32_t cap, int32_t* n_ids, vox_token_score* scores_or_null) {
     FeedPlan plan; VOXCHK(stream_enter(st, nullptr, 0, true, out_ids, cap, n_ids, &plan));      // finish's refusals, nothing changed
     return stream_peek(st, plan, out_ids, n_ids, scores_or_null);
-}
-extern "C" int32_t vox_stream_peek_ids(size_t n_samples, uint32_t sample_rate, int32_t ids_out, int32_t* n) {
-    ARGCHK(n, "null argument"); ARGCHK(ids_out >= 0, "ids_out %d", ids_out);
-    int32_t positions, ids; size_t n16;
-    VOXCHK(vox_stream_schedule_rate(n_samples, sample_rate, 1, &positions, &ids, &n16));
-    ARGCHK(ids_out <= ids, "%d ids handed out of an utterance of %d", ids_out, ids);
-    *n = ids - ids_out;
-    return VOX_OK;
 }
 
 // the stream's own logits row, for the steps of a scored stream (scores or alternatives) that no tap row takes: allocated once
@@ -5146,12 +4656,6 @@ extern "C" int32_t vox_stream_group_pool(const vox_stream_group* g, int64_t out[
     for (int i = 0; held_or_null && i < g->n; i++) held_or_null[i] = g->pool.held(i);
     return VOX_OK;
 }
-extern "C" int32_t vox_stream_group_pages_for(int64_t positions, int32_t page_rows, int32_t window, int32_t* first_page, int32_t* n_pages) {
-    ARGCHK(first_page && n_pages, "null argument"); ARGCHK(positions >= 0 && positions <= ((int64_t)1 << 30), "positions %lld out of range", (long long)positions);
-    ARGCHK(page_rows_ok(page_rows), "page_rows %d is not a power of two in %d..%d", page_rows, PAGE_ROWS_MIN, PAGE_ROWS_MAX); ARGCHK(window >= -1, "window %d: -1 is none", window);
-    int first, n; pages_held(positions, page_rows, window, &first, &n); *first_page = first; *n_pages = n;
-    return VOX_OK;
-}
 extern "C" int32_t vox_debug_stream_group_pages(const vox_stream_group* g, int32_t member, int32_t* out, int32_t cap, int32_t* n) {
     ARGCHK(g && n && (out || cap == 0) && cap >= 0, "bad argument"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1);
     if (!g->paged) return fail(VOX_ERR_UNSUPPORTED, "a slab group has no pages");
@@ -5450,41 +4954,6 @@ extern "C" int32_t vox_debug_stream_group_tap_fetch(vox_stream_group* g, int32_t
     *rows = n;
     (void)hipFree(me.tap); me.tap = nullptr; me.tap_max = 0;
     return group_upload_members(g);
-}
-
-// ---- debug: the feed planner on its own (tests/test_stream_feed_cpu.py).  No device, no model: a fresh session at `sample_rate` (R = 4, the Voxtral left pad, no position
-// limit to speak of) takes the calls (n_samples[c], finish[c]) through feed_plan and feed_pass as the drivers do, every due tick taken as run.  One row of 5 per pass:
-// call index, input samples appended, 16 kHz samples that entered the 16 kHz ring (a 16 kHz session: the appended ones), pad zeros, ticks.  pass_cap: feed_pass's in_cap (0: none).
-extern "C" int32_t vox_debug_stream_feed_passes(uint32_t sample_rate, const size_t* n_samples, const int32_t* finish, int32_t n_calls, size_t pass_cap, int64_t* rows, int32_t max_rows,
-                                                int32_t* n_rows) {
-    ARGCHK(n_rows && (n_calls == 0 || (n_samples && finish)) && (rows || max_rows == 0), "null argument"); ARGCHK(sample_rate > 0, "bad sample rate 0");
-    ARGCHK(n_calls >= 0 && max_rows >= 0, "bad count (%d calls, %d rows)", n_calls, max_rows);
-    FeedState f; f.sr = sample_rate;
-    if (sample_rate != 16000) { size_t bytes; VOXCHK(stream_rate_plan(sample_rate, &f.rp, &bytes, &f.in_ring_n)); }
-    vox_pad_cfg pc; vox_pad_cfg_voxtral(&pc); const long left = (long)pad_left(&pc); const int R = 4;
-    f.restart(VOX_PREFIX_TOKENS - 1);
-    int k = 0;
-    for (int c = 0; c < n_calls; c++) {
-        ARGCHK(finish[c] >= 0 && finish[c] <= 2, "call %d: finish must be 0, 1 or 2 (a peek)", c); ARGCHK(n_samples[c] <= ((size_t)1 << 36), "call %d: push of %zu samples", c, n_samples[c]);
-        const bool peek = finish[c] == 2; ARGCHK(!peek || n_samples[c] == 0, "call %d: finish = 2 (a peek) takes no samples", c);
-        char who[32]; snprintf(who, sizeof who, "call %d: the session", c);
-        FeedPlan plan; VOXCHK(feed_plan(f, R, left, INT32_MAX, n_samples[c], finish[c] != 0, INT32_MAX, who, &plan));
-        f.n_pushed += (int64_t)plan.n;
-        const FeedState::Mark was = f.mark();
-        for (int pass = 0; feed_open(f, plan); pass++) {
-            if (peek && pass > 0) { snprintf(who, sizeof who, "call %d", c); return peek_second_pass(who); }
-            const FeedPass q = feed_pass(f, plan, R, left, pass_cap ? pass_cap : SIZE_MAX);
-            if (q.idle()) return fail(VOX_ERR_INVALID, "internal: call %d stalled at position %d of %d", c, f.pos, plan.target);
-            ARGCHK(k < max_rows, "more than %d passes: the output buffer is too small", max_rows);
-            int64_t* r = rows + (size_t)5 * k++;
-            r[0] = c; r[1] = (int64_t)q.n_in; r[2] = (int64_t)q.n16; r[3] = (int64_t)q.pad; r[4] = q.ticks;
-            f.pos += q.ticks;
-        }
-        if (peek) { f.rewind(was); continue; }      // the session as it was: the drivers' rollback of the feed
-        f.ids_out += plan.due; f.finished = plan.finish;
-    }
-    *n_rows = k;
-    return VOX_OK;
 }
 
 // ---- debug: the sample front ends on their own (tests).  form 0: the single clip's (clip_front_end); form 1: the batch drivers' (group_peak_scales when norm_group is

@@ -4168,7 +4168,7 @@ hipError_t launch_batch_tap(const BatchTapParams& p, int n_rows, hipStream_t s) 
 // Sample-rate conversion (audio/resample.rs:16-52 `resample`).  The reference calls rubato 1.0's synchronous FFT resampler (`Fft`, FixedSync::Input,
 // chunk 1024, 2 sub-chunks): blocks of fft_in samples, zero-padded to 2 fft_in, real FFT, times the FFT of a Blackman-Harris^2 windowed sinc, the
 // low new_len bins re-synthesised by an unnormalised inverse real FFT of length 2 fft_out, overlap-added, minus fft_out / 2 samples of delay (plan
-// and filter taps: vox_api.cpp resample_plan_make).  Every step is linear and identical for every block, so one block is a fixed
+// and filter taps: vox_audio_host.cpp resample_plan_make).  Every step is linear and identical for every block, so one block is a fixed
 // (2 fft_out) x fft_in matrix applied to the block's samples:
 //     out_buf[m] = sum_n x[n] * A[m][n],   A[m][n] = sum_{k < new_len} w_k Re(H[k] e^{2 pi i k (m fft_in - n fft_out) / (2 fft_in fft_out)}),  w_0 = 1, w_k = 2
 // (H = the filter's spectrum; the inverse transform ignores the imaginary part of bin 0; new_len <= fft_out so the Nyquist bin never carries data).
@@ -4332,7 +4332,7 @@ hipError_t launch_stream_mel(const StreamMember* mem, const int* order, int n, i
 // ingest of a stream fed at its capture rate: resample_apply_kernel on rings.  One thread per 16 kHz sample i of [i0, i0 + count): input sample k of the stream lives at
 // in_ring[k & in_mask], output sample i goes to out_ring[i & out_mask] (the ring stream_mel_kernel reads).  The arithmetic is resample_sample's, shared with
 // resample_apply_kernel, so every sample has the bits vox_resample gives for the concatenated input.  The host launches it only for samples whose blocks are complete (or,
-// at the end of the utterance, with n_in = its length) and keeps the input ring from block c - 1 of the oldest sample still to be produced (vox_api.cpp feed_pass).
+// at the end of the utterance, with n_in = its length) and keeps the input ring from block c - 1 of the oldest sample still to be produced (vox_feed_plan.cpp feed_pass).
 // (VOX_NO_PK_F32: a0 / a1 are f32 pair arithmetic in one thread; no packed form is wanted on a stream kernel's lanes, vox_kernels.h.)
 __global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_resample_kernel(const float* __restrict__ in_ring, int in_mask, long n_in, const float* __restrict__ At, int fft_in, int fft_out,
                                                                             int delay, float* __restrict__ out_ring, int out_mask, long i0, int count) {
