@@ -373,6 +373,30 @@ typedef struct { float entropy; int32_t n; vox_alt alt[VOX_MAX_ALTERNATIVES]; } 
 /* rows of logits -> one record per row, vox_score_rows' companion (same mem_kind for the logits).  k: 1 .. VOX_MAX_ALTERNATIVES.  out: host, M records.  Computed on the
  * device either way (host logits are uploaded).  Synchronises. */
 int32_t vox_alternatives_rows(vox_ctx* ctx, const float* logits_MxV, int32_t M, int32_t V, int32_t k, vox_token_alts* out, int32_t mem_kind);
+/* ---- both records of a row from ONE launch, scored on the row's own argmax (vox_score_rows with ids_or_null == NULL): the kernel the offline and batch paths below
+ * take their records from.  k == 0: scores alone (alts_or_null must be NULL, scores_or_null given); k in 1 .. VOX_MAX_ALTERNATIVES: alts_or_null is required,
+ * scores_or_null optional -- both records then come from the two scans of the alternatives (id = alt[0].id, runner_up = alt[1].id, margin = L[id] - L[runner_up],
+ * logprob = alt[0].logprob) instead of four.  The records are bit for bit vox_score_rows' and vox_alternatives_rows' on the same row.  Records: host, M each.
+ * Computed on the device either way (host logits are uploaded).  Synchronises. */
+int32_t vox_records_rows(vox_ctx* ctx, const float* logits_MxV, int32_t M, int32_t V, int32_t k, vox_token_score* scores_or_null, vox_token_alts* alts_or_null,
+                         int32_t mem_kind);
+/* ---- offline and batch transcription with a record per id (no reference counterpart): vox_transcribe_audio / vox_transcribe_batch_ex and, besides the ids, for id j of
+ * a unit the vox_token_score and / or vox_token_alts of the f32 logits row the id was taken from -- bit for bit what vox_score_rows(row, id) and
+ * vox_alternatives_rows(row, k) return for that row, and record j's id (alt[0].id) is out_ids[j].  k == 0: scores alone (alts must be NULL); k in 1 ..
+ * VOX_MAX_ALTERNATIVES: alts is required, scores optional; both NULL is refused (VOX_ERR_INVALID: the unscored calls serve that).  The record arrays are host memory:
+ * `cap` entries (single clip), caps[i] entries for unit i (batch: scores[i] / alts[i]); the entries from n_ids on are left untouched.  Every argument is checked before
+ * a device is touched.
+ *   batch: the ids are those of vox_transcribe_batch_ex under the same slot plan; the records are written by one more launch per decode step (and one per prefill
+ *   stack), in front of the step's argmax, into device arrays that come down once behind the call's last synchronisation.  Every step form, calls split by
+ *   vox_model_set_sessions and a call with the debug tap armed are served.  A call of the unscored entry points launches and allocates nothing for this.
+ *   single clip: the clip is decoded as vox_transcribe_streaming decodes it with its logits tap (the full prefill, a logits row per step kept on the device), and
+ *   vox_records_rows' kernel runs once over all rows; the ids are vox_transcribe_audio's.
+ * (A row nothing can win on -- NaN and -inf only, never seen from a model -- has record id 0 where the ids hold the argmax sentinel.) */
+int32_t vox_transcribe_audio_scored(vox_model* m, const float* samples, size_t n, const float* t_embed, int32_t* out_ids, int32_t cap, int32_t* n_ids,
+                                    vox_token_score* scores_or_null, vox_token_alts* alts_or_null, int32_t k, int32_t mem_kind);
+int32_t vox_transcribe_batch_scored(vox_model* m, int32_t n, const float* const* samples, const size_t* n_samples, const int32_t* norm_group_or_null, const float* t_embed,
+                                    int32_t* const* out_ids, const int32_t* caps, int32_t* n_ids, vox_token_score* const* scores_or_null,
+                                    vox_token_alts* const* alts_or_null, int32_t k, int32_t mem_kind);
 /* lm_head + argmax + read-back in one call: M token ids come back instead of M x 512 KB of logits; synchronises the stream */
 int32_t vox_lm_head_argmax(vox_model* m, const float* hidden_MxD, int32_t M, int32_t* ids_host, int32_t mem_kind);
 /* Q4VoxtralModel::generate_step_with_cache, gguf/model.rs:857-867 (text tokens only: embed -> decoder against the cache -> final norm -> lm_head) in one call;

@@ -219,6 +219,9 @@ SIGNATURES = {
     "vox_stream_group_pool": (i32, [vp, P(i64 * 4), vp]),
     "vox_stream_group_pages_for": (i32, [i64, i32, i32, P(i32), P(i32)]),
     "vox_debug_stream_group_pages": (i32, [vp, i32, vp, i32, P(i32)]),
+    "vox_records_rows": (i32, [vp, vp, i32, i32, i32, vp, vp, i32]),
+    "vox_transcribe_audio_scored": (i32, [vp, vp, sz, vp, vp, i32, P(i32), vp, vp, i32, i32]),
+    "vox_transcribe_batch_scored": (i32, [vp, i32, P(vp), P(sz), vp, vp, P(vp), P(i32), P(i32), vp, vp, i32, i32]),
 }
 
 _LIB = None

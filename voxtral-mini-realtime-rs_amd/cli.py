@@ -49,14 +49,36 @@ def resample_to_16k(x, sr, ctx=None, pkg=None):
     return pkg.resample_to_16k(ctx, x, sr)
 
 
-def transcribe_one(pkg, path, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed):
-    """bin/transcribe.rs:187-276"""
+def unit_words(pkg, path, chunk, ids, scores, tokenizer, alternatives=None):
+    """--words: the words of one unit of work (a file, or chunk `chunk` of a chunked file; None: the file is one unit) as dicts: pkg.words' text, first_id, last_id
+    (indices into the UNIT's ids), logprob, min_margin, with alternatives also entropy and weakest; + file and, for a chunk, chunk.  No due_s: that is when a live
+    session hands an id out."""
+    res = []
+    for w in pkg.words(ids, scores, tokenizer, alternatives=alternatives):
+        w = {k: v for k, v in w.items() if k != "due_s"}; w["file"] = path
+        if chunk is not None:
+            w["chunk"] = int(chunk)
+        res.append(w)
+    return res
+
+
+def write_word_lines(out, lines):
+    """one JSON line per word dict"""
+    import json
+    for w in lines:
+        out.write(json.dumps(w, ensure_ascii=False) + "\n")
+    out.flush()
+
+
+def transcribe_one(pkg, path, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed, words_out=None, alts_k=0):
+    """bin/transcribe.rs:187-276.  words_out (--words): every chunk's logits rows come back with its ids and vox_records_rows' kernel gives every id its record
+    (alts_k: --alternatives); the ids, hence the line, are the same."""
     x, sr = load_wav(path)
     if sr != 16000:
         log(f"  resampling {sr} Hz -> 16 kHz"); x = resample_to_16k(x, sr, mel.ctx, pkg)
     x = pkg.peak_normalize(x, 0.95)                                              # :207
     chunks = pkg.chunk_audio(x, chunk_cfg) if pkg.needs_chunking(x.size, chunk_cfg) else [None]
-    texts = []
+    texts = []; words = []
     for i, ch in enumerate(chunks):
         samples = x if ch is None else ch.samples
         if len(chunks) > 1:
@@ -64,10 +86,18 @@ def transcribe_one(pkg, path, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed
         m = mel.compute_log(pkg.pad_audio(samples, pad_cfg))                     # :279-306
         if m.shape[0] == 0:
             raise RuntimeError("Audio too short to produce mel frames")
-        ids = model.transcribe_streaming(np.ascontiguousarray(m.T)[None], t_embed)
+        if words_out is None:
+            ids = model.transcribe_streaming(np.ascontiguousarray(m.T)[None], t_embed)
+        else:
+            ids, lg = model.transcribe_streaming(np.ascontiguousarray(m.T)[None], t_embed, return_logits=True)
+            if len(ids):
+                sc, al = pkg.records_rows(mel.ctx, lg, alts_k)
+                words.extend(unit_words(pkg, path, i if len(chunks) > 1 else None, ids, sc, tokenizer, al))
         text = tokenizer.decode([t for t in ids if t >= 1000]).strip()           # :309-318
         if text:
             texts.append(text)
+    if words_out is not None:      # (a file that failed half way writes nothing)
+        write_word_lines(words_out, words)
     return " ".join(texts)
 
 
@@ -205,11 +235,13 @@ def unit_table(pkg, paths, chunk_cfg):
 class UnitRunner:
     """Transcribes units (file, chunk, start, end) through vox_transcribe_batch_ex.  A file is loaded, resampled and peak-normalised ONCE, as a file
     (bin/transcribe.rs:197-207); its chunks are views into it handed over as already normalised (norm_group < 0), so a file's chunks may sit in different calls or
-    on different ranks and still carry the file's scale.  Returns the text of every unit (None = failed: the file falls back to the one-by-one path)."""
+    on different ranks and still carry the file's scale.  Returns the text of every unit (None = failed: the file falls back to the one-by-one path).
+    alts_k (--words: 0 = scores alone, 1..8 with --alternatives; None: off): the units go through vox_transcribe_batch_scored and self.words[(file, chunk)] holds
+    every unit's word dicts (unit_words), for the caller to write once the file's line stands."""
 
-    def __init__(self, pkg, ctx, model, tokenizer, paths, t_embed):
+    def __init__(self, pkg, ctx, model, tokenizer, paths, t_embed, alts_k=None, chunked=()):
         self.pkg, self.ctx, self.model, self.tok, self.paths, self.t_embed = pkg, ctx, model, tokenizer, paths, t_embed
-        self.files = {}
+        self.files = {}; self.alts_k = alts_k; self.chunked = set(chunked); self.words = {}
 
     def samples(self, i):
         if i not in self.files:
@@ -232,10 +264,17 @@ class UnitRunner:
         if not views:
             return out
         try:
-            t1 = time.time(); ids = self.model.transcribe_batch(views, self.t_embed, norm_group=[-1] * len(views))
+            t1 = time.time()
+            if self.alts_k is None:
+                ids = self.model.transcribe_batch(views, self.t_embed, norm_group=[-1] * len(views))
+            else:
+                ids, scs, als = self.model.transcribe_batch_scored(views, self.t_embed, alternatives=self.alts_k, norm_group=[-1] * len(views))
             log(f"batch of {len(views)}: {time.time() - t1:.3f}s")
-            for u, r in zip(keep, ids):
+            for j, (u, r) in enumerate(zip(keep, ids)):
                 out[u] = self.tok.decode([t for t in r if t >= 1000]).strip()           # :309-318, per chunk
+                if self.alts_k is not None:
+                    i, k = units[u][0], units[u][1]
+                    self.words[(i, k)] = unit_words(self.pkg, self.paths[i], k if i in self.chunked else None, r, scs[j], self.tok, None if als is None else als[j])
         except Exception as e:
             log(f"batched path failed ({e}); falling back to one by one")
         for i in {units[u][0] for u in keep}:      # a file whose units are all done is dropped from memory
@@ -329,7 +368,21 @@ def main(argv=None):
     ap.add_argument("--live-alternatives", type=int, default=None, metavar="K", help="with --live-words: also keep every id's K (1..8) best alternatives and its step's entropy "
                     "(vox_stream_set_alternatives); every word line gains entropy (the largest over the word's ids) and weakest: {k: the index of its smallest-margin id, "
                     "alternatives: [{id, text, logprob}] of that id}; ids, stdout and the lines of runs without the flag are unchanged")
+    ap.add_argument("--words", metavar="PATH", help="extension, without --live (one by one, --audio-list, --batch): every id comes with its score record "
+                    "(vox_transcribe_batch_scored; one by one: vox_records_rows on the chunk's logits rows) and one JSON line per word goes to PATH: text, first_id / last_id "
+                    "(indices into the ids of the file, or of the chunk for a file split by --max-mel-frames), logprob (summed over the word's ids), min_margin (the smallest "
+                    "top-2 margin among them), file and, for a chunked file, chunk; stdout is unchanged")
+    ap.add_argument("--alternatives", type=int, default=None, metavar="K", help="with --words: also every id's K (1..8) best alternatives and its step's entropy; every word "
+                    "line gains entropy and weakest, as with --live-alternatives")
     a = ap.parse_args(argv)
+    if a.alternatives is not None and not a.words:
+        ap.error("--alternatives applies with --words")
+    if a.alternatives is not None and not 1 <= a.alternatives <= 8:
+        ap.error("--alternatives takes 1..8")
+    if a.words and a.live:
+        ap.error("--words serves the offline and batch paths: with --live use --live-words")
+    if a.words and a.gpus > 1:
+        ap.error("--words runs on one GPU (no --gpus): the ranks' records are not gathered")
     if a.live_alternatives is not None and not a.live_words:
         ap.error("--live-alternatives applies with --live-words")
     if a.live_alternatives is not None and not 1 <= a.live_alternatives <= 8:
@@ -417,6 +470,7 @@ def main(argv=None):
     rc = 0
     texts = {}
     words_out = open(a.live_words, "w", encoding="utf-8") if a.live_words else None
+    rec_out = open(a.words, "w", encoding="utf-8") if a.words else None      # --words (never with --live: checked above)
     if a.batch > 1:
         # every file -> its chunks (transcribe.rs:210-226); ALL units of this rank's share go to vox_transcribe_batch_ex in calls of <= --batch units (continuous batching
         # over decode slots); a file's line = its chunk texts joined by " " (:261-275).  Files with a failed unit fall back to the one-by-one path below.
@@ -424,7 +478,11 @@ def main(argv=None):
         if a.sessions_per_gpu > 1 and a.gguf:      # vox_model_set_sessions: calls with >= 128 units per session run as that many concurrent sessions on this GPU
             model.set_sessions(a.sessions_per_gpu)
             log(f"{a.sessions_per_gpu} sessions on this GPU (model replicated device to device)")
-        runner = UnitRunner(pkg, ctx, model, tokenizer, paths, t_embed)
+        n_units_of = {}
+        for i, _, _, _ in units:
+            n_units_of[i] = n_units_of.get(i, 0) + 1
+        runner = UnitRunner(pkg, ctx, model, tokenizer, paths, t_embed, alts_k=(a.alternatives or 0) if rec_out is not None else None,
+                            chunked=[i for i, c in n_units_of.items() if c > 1])
         try:
             unit_texts = sharded_units(pkg, units, runner, a.batch, rank, world) if units else []
         finally:
@@ -432,6 +490,10 @@ def main(argv=None):
                 model.set_sessions(1)
         if unit_texts is not None:      # (rank 0, or the only rank)
             texts = join_units(len(paths), units, unit_texts)
+            if rec_out is not None:      # the words of the files whose line stands, file-major; the others' come from the one-by-one path with their line
+                for i, k, _, _ in units:
+                    if i in texts:
+                        write_word_lines(rec_out, runner.words.get((i, k), []))
     if a.live_group:
         try:
             texts = transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_group, words_out, a.live_peek, a.live_alternatives, a.live_page_rows, a.live_pool_pages)
@@ -446,7 +508,7 @@ def main(argv=None):
         p = paths[i]
         try:
             t1 = time.time()
-            text = transcribe_live(pkg, p, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_native_rate, words_out, a.live_peek, a.live_alternatives) if a.live else transcribe_one(pkg, p, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed)
+            text = transcribe_live(pkg, p, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_native_rate, words_out, a.live_peek, a.live_alternatives) if a.live else transcribe_one(pkg, p, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed, rec_out, a.alternatives or 0)
             log(f"{p}: {time.time() - t1:.3f}s")
         except Exception as e:      # per-utterance failure isolates to that line (empty), eval_wer.py:211-223 tolerates it
             log(f"Error transcribing {p}: {e}"); text = ""; rc = 1
@@ -465,6 +527,8 @@ def main(argv=None):
             print(one(i), flush=True)
     if words_out is not None:
         words_out.close()
+    if rec_out is not None:
+        rec_out.close()
     if own_group:
         import torch.distributed as dist
         dist.barrier(); dist.destroy_process_group()

@@ -2117,7 +2117,9 @@ static int32_t run_decode_steps(vox_model* m, const ClipPlan& plan, bool eng, fl
 // One attempt at the plan on the model's own cache: decode state, engine binding and launch serials, seed_clip, run_decode_steps, ids (and logits) on their way to the
 // caller, the engine's error word behind them, ONE synchronisation.  *eng_timed_out: a bounded hand-off wait expired inside the engine -- the ids of this attempt are
 // not trustworthy (m->eng_offline.err_word holds the code); what happens then is the caller's.
-static int32_t clip_attempt(vox_model* m, const ClipPlan& plan, int32_t* out_ids, float* logits_host, bool* eng_timed_out) {
+// rec: also a record per id from the kept logits rows (launch_records_rows, once over all rows), into the caller's host arrays behind the same synchronisation.
+struct ClipRecords { vox_token_score* scores; vox_token_alts* alts; int k; };      // what a scored call asked for: host arrays (either may be null) and k
+static int32_t clip_attempt(vox_model* m, const ClipPlan& plan, int32_t* out_ids, float* logits_host, const ClipRecords* rec, bool* eng_timed_out) {
     const vox_model_cfg& c = m->cfg; hipStream_t s = m->ctx->stream;
     *eng_timed_out = false;
     VOXCHK(ensure_decode_state(m, plan.S));
@@ -2128,7 +2130,15 @@ static int32_t clip_attempt(vox_model* m, const ClipPlan& plan, int32_t* out_ids
     stage.begin("decode");
     VOXCHK(run_decode_steps(m, plan, eng, d_logits_all));
     HIPCHK(hipMemcpyAsync(out_ids, m->d_tokens + VOX_PREFIX_TOKENS, (size_t)plan.n_ids * 4, hipMemcpyDeviceToHost, s));
-    if (plan.want_logits) HIPCHK(hipMemcpyAsync(logits_host, d_logits_all, (size_t)plan.n_ids * c.vocab * 4, hipMemcpyDeviceToHost, s));
+    if (logits_host) HIPCHK(hipMemcpyAsync(logits_host, d_logits_all, (size_t)plan.n_ids * c.vocab * 4, hipMemcpyDeviceToHost, s));
+    DevBuf dsc, dal;
+    if (rec) {
+        if (rec->scores) HIPCHK(dsc.alloc((size_t)plan.n_ids * sizeof(TokenScore)));
+        if (rec->alts) HIPCHK(dal.alloc((size_t)plan.n_ids * sizeof(TokenAlts)));
+        HIPCHK(launch_records_rows(d_logits_all, plan.n_ids, c.vocab, rec->k, dsc.as<TokenScore>(), dal.as<TokenAlts>(), s));
+        if (rec->scores) HIPCHK(hipMemcpyAsync(rec->scores, dsc.p, (size_t)plan.n_ids * sizeof(TokenScore), hipMemcpyDeviceToHost, s));
+        if (rec->alts) HIPCHK(hipMemcpyAsync(rec->alts, dal.p, (size_t)plan.n_ids * sizeof(TokenAlts), hipMemcpyDeviceToHost, s));
+    }
     const bool eng_used = eng && plan.steps > 0;
     if (eng_used) VOXCHK(engine_err_enqueue(m, m->eng_offline.err_word, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -2141,9 +2151,9 @@ static int32_t clip_attempt(vox_model* m, const ClipPlan& plan, int32_t* out_ids
 // from_padded_samples: d_mel is the log-mel of samples the library itself padded (vox_transcribe_audio) -- the only case in which the model's prefix state stands for the
 // first encoder rows and decoder positions (a caller's own mel may hold anything there).
 static int32_t transcribe_dev(vox_model* m, const float* d_mel, int T, const float* t_embed, int32_t* out_ids, int32_t cap, int32_t* n_ids,
-                              float* logits_host, bool from_padded_samples = false) {
+                              float* logits_host, bool from_padded_samples = false, const ClipRecords* rec = nullptr) {
     VOXCHK(vox_model_set_t_embed(m, t_embed));
-    const bool pfx = from_padded_samples && !logits_host && prefix_usable(m, T);      // (prefix_build ran before the mel was made: vox_transcribe_audio)
+    const bool pfx = from_padded_samples && !logits_host && !rec && prefix_usable(m, T);      // (prefix_build ran before the mel was made: vox_transcribe_audio; records are taken from the kept logits rows: the tap's plan)
     double t0 = now_ms();
     RoctxScope whole("transcribe_streaming");
     int S = 0; RoctxStage stage; stage.begin("encode_audio");
@@ -2152,11 +2162,11 @@ static int32_t transcribe_dev(vox_model* m, const float* d_mel, int T, const flo
     stage.end();
     m->timings.encode_ms = now_ms() - t0; t0 = now_ms();
     *n_ids = 0; m->timings.decode_tokens = 0; m->timings.graph_replays = 0;
-    const ClipPlan plan = plan_clip(S, pfx, m->pfx.PC, logits_host != nullptr);
+    const ClipPlan plan = plan_clip(S, pfx, m->pfx.PC, logits_host != nullptr || rec != nullptr);
     if (plan.n_ids == 0) { m->timings.decode_ms = 0; return VOX_OK; }
     ARGCHK(cap >= plan.n_ids, "out_ids capacity %d < %d", cap, plan.n_ids);
     bool timed_out = false;
-    VOXCHK(clip_attempt(m, plan, out_ids, logits_host, &timed_out));
+    VOXCHK(clip_attempt(m, plan, out_ids, logits_host, rec, &timed_out));
     if (timed_out) {
         // A bounded hand-off wait expired inside the engine: its 256 workgroups were not co-resident for 20 ms (another kernel on the GPU, a CU mask, a debugger).  The ids
         // of that attempt are not trustworthy -- the SAME utterance is decoded again on the per-operator launches (the encoder output is still in place), the engine is
@@ -2165,7 +2175,7 @@ static int32_t transcribe_dev(vox_model* m, const float* d_mel, int T, const flo
         VOXCHK(engine_strike(m));
         fprintf(stderr, "[voxtral_hip] decode engine: %s; this utterance is decoded again on the per-operator path%s\n",
                 engine_timeout_text(e, m->eng_strikes).c_str(), m->eng_strikes >= 3 ? ", the engine is switched off" : "");
-        int32_t r; { EngSuspend off(m); r = clip_attempt(m, plan, out_ids, logits_host, &timed_out); }
+        int32_t r; { EngSuspend off(m); r = clip_attempt(m, plan, out_ids, logits_host, rec, &timed_out); }
         graphs_destroy(m);      // (the graph captured during the re-run holds the per-operator launches)
         if (r != VOX_OK) return r;
     }
@@ -2223,8 +2233,30 @@ static int32_t clip_front_end(vox_model* m, const float* samples, size_t n, int3
     *T_out = (int)T;
     return VOX_OK;
 }
+// what the scored entry points check of their record arguments, before a device is touched: k in 0 .. 8, alts exactly when k >= 1, at least one array
+static int32_t records_args_check(const void* scores, const void* alts, int32_t k) {
+    ARGCHK(k >= 0 && k <= VOX_MAX_ALTERNATIVES, "k %d out of range (0..%d)", k, VOX_MAX_ALTERNATIVES);
+    ARGCHK(k > 0 || !alts, "alts given with k == 0: k in 1..%d asks for alternatives", VOX_MAX_ALTERNATIVES);
+    ARGCHK(k == 0 || alts, "k %d needs the alts array", k);
+    ARGCHK(scores || alts, "scores and alts are both null: the unscored call serves that");
+    return VOX_OK;
+}
+static int32_t transcribe_audio_impl(vox_model* m, const float* samples, size_t n, const float* t_embed, int32_t* out_ids, int32_t cap,
+                                     int32_t* n_ids, int32_t mem_kind, const ClipRecords* rec);
 extern "C" int32_t vox_transcribe_audio(vox_model* m, const float* samples, size_t n, const float* t_embed, int32_t* out_ids, int32_t cap,
                                         int32_t* n_ids, int32_t mem_kind) {
+    return transcribe_audio_impl(m, samples, n, t_embed, out_ids, cap, n_ids, mem_kind, nullptr);
+}
+extern "C" int32_t vox_transcribe_audio_scored(vox_model* m, const float* samples, size_t n, const float* t_embed, int32_t* out_ids, int32_t cap, int32_t* n_ids,
+                                               vox_token_score* scores, vox_token_alts* alts, int32_t k, int32_t mem_kind) {
+    ARGCHK(m, "null model"); ARGCHK(samples && t_embed && out_ids, "null argument"); ARGCHK(n_ids, "null n_ids"); ARGCHK(n > 0, "empty audio");
+    VOXCHK(records_args_check(scores, alts, k));
+    ARGCHK(mem_kind == VOX_MEM_HOST || mem_kind == VOX_MEM_DEVICE, "bad mem_kind %d", mem_kind);
+    const ClipRecords rec{scores, alts, k};
+    return transcribe_audio_impl(m, samples, n, t_embed, out_ids, cap, n_ids, mem_kind, &rec);
+}
+static int32_t transcribe_audio_impl(vox_model* m, const float* samples, size_t n, const float* t_embed, int32_t* out_ids, int32_t cap,
+                                     int32_t* n_ids, int32_t mem_kind, const ClipRecords* rec) {
     ARGCHK(m && samples && t_embed && out_ids && n_ids, "null argument"); ARGCHK(n > 0, "empty audio"); VOXCHK(ctx_bind(m->ctx));
     const vox_model_cfg& c = m->cfg; hipStream_t s = m->ctx->stream;
     ARGCHK(c.n_mels == 128, "the log-mel front-end produces 128 bins; model expects %d", c.n_mels);
@@ -2234,7 +2266,7 @@ extern "C" int32_t vox_transcribe_audio(vox_model* m, const float* samples, size
     int T = 0; VOXCHK(clip_front_end(m, samples, n, mem_kind, &T));
     HIPCHK(hipStreamSynchronize(s));
     m->timings.preprocess_ms = now_ms() - t0;
-    VOXCHK(transcribe_dev(m, m->d_mel, T, t_embed, out_ids, cap, n_ids, nullptr, true));
+    VOXCHK(transcribe_dev(m, m->d_mel, T, t_embed, out_ids, cap, n_ids, nullptr, true, rec));
     m->timings.total_ms = m->timings.preprocess_ms + m->timings.encode_ms + m->timings.decode_ms;
     return VOX_OK;
 }
@@ -2468,6 +2500,53 @@ struct BatchTapCall {
         return VOX_OK;
     }
 };
+// What a scored batch call asked for (vox_transcribe_batch_scored): per-unit host arrays in the order of the call's units (either may be null; unit i's hold caps[i]
+// entries) and k.  The drivers permute and slice these as they do out_ids.
+struct RecordsOut { vox_token_score* const* scores; vox_token_alts* const* alts; int k; };
+// The records of one driver call (launch_batch_records): utterance i's record j lives at rec_off[i] + j of one device array per kind, rec_off = the prefix sum of the
+// planned id counts (batch_lengths: a pure function of the sample counts).  Off (no RecordsOut): no buffer, no launch.  rows(...) enqueues the records of the rows the
+// next argmax launch reads, inside a capture as well as eagerly, at BatchTapCall::rows' three sites; download(...) goes in front of the call's last synchronisation
+// (copy_out_ids'), scatter() behind it: the first n_ids records of every unit into the caller's arrays, nothing past them.
+struct BatchRecordsCall {
+    vox_model* m = nullptr; const RecordsOut* out = nullptr; int n = 0;
+    DevBuf off, sc, al; std::vector<int> h_off; std::vector<TokenScore> h_sc; std::vector<TokenAlts> h_al;
+    bool on() const { return out != nullptr; }
+    int total() const { return h_off.empty() ? 0 : h_off.back(); }
+    int32_t init(vox_model* mm, int nn, const std::vector<int>& S, const RecordsOut* o, hipStream_t s) {
+        m = mm; n = nn; out = o;
+        if (!on()) return VOX_OK;
+        h_off.assign((size_t)n + 1, 0);
+        for (int i = 0; i < n; i++) h_off[(size_t)i + 1] = h_off[i] + (S[i] >= VOX_PREFIX_TOKENS ? std::max(S[i] - VOX_PREFIX_TOKENS, 1) : 0);      // copy_out_ids' counts
+        HIPCHK(off.alloc_pooled(m->ctx, h_off.size() * 4));
+        HIPCHK(hipMemcpyAsync(off.p, h_off.data(), h_off.size() * 4, hipMemcpyHostToDevice, s));
+        if (out->scores) HIPCHK(sc.alloc_pooled(m->ctx, (size_t)total() * sizeof(TokenScore)));
+        if (out->alts) HIPCHK(al.alloc_pooled(m->ctx, (size_t)total() * sizeof(TokenAlts)));
+        HIPCHK(hipStreamSynchronize(s));      // (no pageable copy may sit behind the stages that follow)
+        return VOX_OK;
+    }
+    int32_t rows(const float* logits, int n_rows, const int* slot_clip, int clip0, const int* pos, const int* seq_len, hipStream_t s) const {
+        if (!on() || total() == 0) return VOX_OK;
+        BatchRecordsParams p{}; p.logits = logits; p.vocab = m->cfg.vocab; p.slot_clip = slot_clip; p.clip0 = clip0; p.pos = pos; p.seq_len = seq_len;
+        p.rec_off = (const int*)off.p; p.n_clips = n; p.n_records = total(); p.first_pos = VOX_PREFIX_TOKENS;
+        p.scores = (TokenScore*)sc.p; p.alts = (TokenAlts*)al.p; p.k = out->k;
+        HIPCHK(launch_batch_records(p, n_rows, s));
+        return VOX_OK;
+    }
+    int32_t download(hipStream_t s) {
+        if (!on() || total() == 0) return VOX_OK;
+        if (out->scores) { h_sc.resize((size_t)total()); HIPCHK(hipMemcpyAsync(h_sc.data(), sc.p, h_sc.size() * sizeof(TokenScore), hipMemcpyDeviceToHost, s)); }
+        if (out->alts) { h_al.resize((size_t)total()); HIPCHK(hipMemcpyAsync(h_al.data(), al.p, h_al.size() * sizeof(TokenAlts), hipMemcpyDeviceToHost, s)); }
+        return VOX_OK;
+    }
+    void scatter() const {
+        if (!on() || total() == 0) return;
+        for (int i = 0; i < n; i++) {
+            const size_t o = (size_t)h_off[i], cnt = (size_t)(h_off[(size_t)i + 1] - h_off[i]);
+            if (cnt && out->scores) std::memcpy(out->scores[i], h_sc.data() + o, cnt * sizeof(TokenScore));
+            if (cnt && out->alts) std::memcpy(out->alts[i], h_al.data() + o, cnt * sizeof(TokenAlts));
+        }
+    }
+};
 // Stacked 38-token prefill of nc utterances (gguf/model.rs:887-919) on s: x0[i][r] = audio[aoff[i]][r] + embed(tok[i][r]) into px, the decoder over all nc x 38 rows
 // against the cache slices k / v (utterance i's at + i seq_stride), then the logits of every utterance's last prefix row (RMSNorm -> xn, lm_head -> logits): what its
 // first generated token is taken from.  Utterances shorter than the prefix emit nothing (model.rs:887-889) -- they ride along as idle rows.
@@ -2507,7 +2586,7 @@ static int32_t f32_batch_layers(const vox_model* m, const XfBufs& b, int n, floa
 }
 static int32_t transcribe_batch_impl(vox_model* m, int32_t n, const float* const* samples, const size_t* n_samples, const float* t_embed,
                                      int32_t* const* out_ids, const int32_t* caps, int32_t* n_ids, int32_t mem_kind, const int* slot_of, bool allow_engine = true,
-                                     const float* const* unit_scale = nullptr) {
+                                     const float* const* unit_scale = nullptr, const RecordsOut* rec_out = nullptr) {
     // unit_scale[i]: device float the front-end multiplies unit i by (vox_transcribe_batch_ex: the peak scale of the unit's FILE); null = every unit normalises itself
     // slot_of[i]: the caller's slot of row i (error messages)
     VOXCHK(ctx_bind(m->ctx));
@@ -2526,6 +2605,7 @@ static int32_t transcribe_batch_impl(vox_model* m, int32_t n, const float* const
     size_t mel_floats = 0; for (int i = 0; i < n; i++) mel_floats += (size_t)128 * T[i];
     DevBuf b_audio, b_k, b_v, b_tok, b_pos, b_len, b_h, b_xn, b_qkv, b_att, b_act, b_logits, b_px, b_mel, b_scale, b_smp; XfPlanes xfp;
     BatchTapCall tap; VOXCHK(tap.init(m, n, slot_of, s));
+    BatchRecordsCall rec; VOXCHK(rec.init(m, n, S, rec_out, s));
     BatchDrain drain{cx};
     HIPCHK(b_audio.alloc_pooled(cx, (size_t)n * audio_rows * D * 4)); HIPCHK(b_k.alloc_pooled(cx, layer_stride * c.dec_layers * 4)); HIPCHK(b_v.alloc_pooled(cx, layer_stride * c.dec_layers * 4));
     HIPCHK(b_tok.alloc_pooled(cx, (size_t)n * tstride * 4)); HIPCHK(b_pos.alloc_pooled(cx, (size_t)n * 4)); HIPCHK(b_len.alloc_pooled(cx, (size_t)n * 4));
@@ -2581,6 +2661,7 @@ static int32_t transcribe_batch_impl(vox_model* m, int32_t n, const float* const
     const bool gqa = n_grp > 1 || knob_str("VOX_ATTN_GQA");
     auto next_input = [&](bool xf_in, bool first = false) -> int32_t {
         VOXCHK(tap.rows(logits, n, nullptr, 0, d_pos, d_len, s));
+        VOXCHK(rec.rows(logits, n, nullptr, 0, d_pos, d_len, s));
         if (!xf_in && !first) HIPCHK(launch_argmax_embed_batch(logits, n, V, d_tok, tstride, d_pos, d_len, m->tok.w, d_audio, (long)audio_rows * D, D, xb.h, s));
         else HIPCHK(launch_argmax_embed_batch(logits, n, V, d_tok, tstride, d_pos, d_len, m->tok.w, d_audio, (long)audio_rows * D, D, xb.h, s,
                                               xf_in ? xb.xf1 : nullptr, xf_in ? m->dec[0].attn_norm : nullptr, xf_in ? xb.ssq : nullptr, xb.xf1_gs, (int)xb.ssq_gs));
@@ -2623,7 +2704,9 @@ static int32_t transcribe_batch_impl(vox_model* m, int32_t n, const float* const
     }
     VOXCHK(engb_timeout_check(m, use_eng ? n_grp : 0, false, s));
     int total = 0;
+    VOXCHK(rec.download(s));
     VOXCHK(copy_out_ids(n, S, tstride, d_tok, out_ids, n_ids, &total, s));
+    rec.scatter();
     m->timings.preprocess_ms = pre_ms; m->timings.encode_ms = enc_ms; m->timings.decode_ms = now_ms() - t1; m->timings.total_ms = now_ms() - t0;
     m->timings.decode_tokens = total; m->timings.graph_replays = replays;
     if (knob_str("VOX_BATCH_VERBOSE"))
@@ -2760,7 +2843,7 @@ struct ContSession {
     bool fe_overlap = false; size_t mel_half = 1, smp_half = 1; int ncm = 0;      // front-end buffers: halves of the ping-pong, ncm = utterances of the largest chunk
     DevBuf b_audio, b_k, b_v, b_tok, b_posc, b_len, b_h0, b_aoff, b_px, b_xn, b_lg0, b_mel, b_scale, b_smp;
     DevBuf b_queue, b_sclip, b_sqpos, b_pos, b_kvrow, b_h, b_qkv, b_att, b_logits, b_ssq_e, b_planes; XfPlanes xfp; XfBufs xb{}; SlotStepParams sp{};      // the decode step's
-    BatchTapCall tap; BatchDrain drain;
+    BatchTapCall tap; BatchRecordsCall rec; BatchDrain drain;
     double pre_ms = 0.0, enc_ms = 0.0, pf_ms = 0.0, t0 = 0.0, t1 = 0.0, capture_ms = 0.0; int replays = 0, n_captures = 0;
     int form_steps[5] = {0, 0, 0, 0, 0};      // VOX_BATCH_VERBOSE: decode steps on the launch chains, the one- / two-group engine, one wide chain, two or more wide chains
     explicit ContSession(vox_model* mm) : m(mm), cx(mm->ctx), s(mm->ctx->stream), drain{mm->ctx} {}
@@ -2832,6 +2915,7 @@ struct ContSession {
         VOXCHK(prefill_first_logits(m, nc, d_tok + (size_t)c0 * tstride, tstride, d_audio, lay.audio_off.data() + c0, b_px.as<float>(), b_k.as<float>() + (size_t)c0 * seq_stride,
                                     b_v.as<float>() + (size_t)c0 * seq_stride, max_seq, layer_stride, seq_stride, b_xn.as<float>(), b_lg0.as<float>(), s));
         VOXCHK(tap.rows(b_lg0.as<float>(), nc, nullptr, c0, b_posc.as<int>() + c0, b_len.as<int>() + c0, s));
+        VOXCHK(rec.rows(b_lg0.as<float>(), nc, nullptr, c0, b_posc.as<int>() + c0, b_len.as<int>() + c0, s));
         HIPCHK(launch_argmax_embed_batch(b_lg0.as<float>(), nc, V, d_tok + (size_t)c0 * tstride, tstride, b_posc.as<int>() + c0, b_len.as<int>() + c0, m->tok.w, d_audio, 0, D,
                                          b_h0.as<float>() + (size_t)c0 * D, s, nullptr, nullptr, nullptr, 0, 0, b_aoff.as<long>() + c0));
         // (the last chunk's prefill is not waited for here when a decode follows: the decode's buffers are set up and its graphs captured -- host work, ~6-10 ms per
@@ -2888,6 +2972,7 @@ struct ContSession {
                 if ((active >> gi) & 1u) VOXCHK(xf_chain(m, xb, gi, 16, 0, 0, true, 0, s));
         }
         VOXCHK(tap.rows(xb.logits, sch.Sl, b_sclip.as<int>(), 0, xb.pos, nullptr, s));
+        VOXCHK(rec.rows(xb.logits, sch.Sl, b_sclip.as<int>(), 0, xb.pos, nullptr, s));
         HIPCHK(launch_argmax_embed_slots(sp, sch.Sl, s));      // (retired groups' slots are idle: slot_clip < 0)
         return VOX_OK;
     }
@@ -2987,7 +3072,7 @@ struct ContSession {
 // lengths -> plan -> buffers -> stage chunks -> decode -> copy out -> timings
 static int32_t transcribe_continuous_impl(vox_model* m, int32_t n, const float* const* samples, const size_t* n_samples, const float* t_embed,
                                           int32_t* const* out_ids, const int32_t* caps, int32_t* n_ids, int32_t mem_kind, const int* slot_of, bool allow_engine,
-                                          const float* const* unit_scale = nullptr) {
+                                          const float* const* unit_scale = nullptr, const RecordsOut* rec_out = nullptr) {
     VOXCHK(ctx_bind(m->ctx));
     const vox_model_cfg& c = m->cfg; const int PREFIX_LEN = VOX_PREFIX_TOKENS;
     ARGCHK(c.n_mels == 128, "the log-mel front-end produces 128 bins; model expects %d", c.n_mels);
@@ -3011,6 +3096,7 @@ static int32_t transcribe_continuous_impl(vox_model* m, int32_t n, const float* 
     z.sch = slot_schedule(jobs, z.pol.force_G, z.step_cost, z.pol.max_groups);
     cont_policy_groups(z.pol, m, z.sch.G);
     VOXCHK(z.tap.init(m, n, slot_of, z.s));
+    VOXCHK(z.rec.init(m, n, z.S, rec_out, z.s));
     VOXCHK(z.alloc());
     z.t0 = now_ms();
     std::vector<const float*> mels_cur, mels_next;
@@ -3018,7 +3104,9 @@ static int32_t transcribe_continuous_impl(vox_model* m, int32_t n, const float* 
     z.t1 = now_ms();
     if (z.sch.steps > 0) VOXCHK(z.decode());
     int total = 0;
+    VOXCHK(z.rec.download(z.s));
     VOXCHK(copy_out_ids(n, z.S, z.tstride, z.b_tok.as<int>(), out_ids, n_ids, &total, z.s));
+    z.rec.scatter();
     m->timings.preprocess_ms = z.pre_ms; m->timings.encode_ms = z.enc_ms; m->timings.decode_ms = z.pf_ms + (now_ms() - z.t1); m->timings.total_ms = now_ms() - z.t0;
     m->timings.decode_tokens = total; m->timings.graph_replays = z.replays;
     if (z.pol.verbose) z.report();
@@ -3035,7 +3123,7 @@ extern "C" int32_t vox_transcribe_batch(vox_model* m, int32_t n, const float* co
 // of work from there on (:231-265).  Units that name the same group >= 0 share ONE peak scale = 0.95 / max|x| over all of them (chunks tile their file, so that is the
 // file's peak); group < 0: the unit is used as handed over (already normalised by the caller); norm_group == NULL: every unit normalises itself (un-chunked e2e-bench).
 static int32_t transcribe_batch_one_session(vox_model* m, int32_t n, const float* const* samples_in, const size_t* n_samples, const int32_t* norm_group, const float* t_embed,
-                                            int32_t* const* out_ids, const int32_t* caps, int32_t* n_ids, int32_t mem_kind_in);
+                                            int32_t* const* out_ids, const int32_t* caps, int32_t* n_ids, int32_t mem_kind_in, const RecordsOut* rec = nullptr);
 // vox_model_set_sessions(m, S): batch calls with enough units run as S concurrent sessions on the model's GPU -- the calling thread on the model's own context, S - 1
 // library threads on hidden contexts with replicas of the model (vox_model_replicate, device to device) -- see the header.  Units of one normalisation group stay in one
 // session (the group's peak is reduced over the units of ONE session); LPT by sample count; every context involved is marked shared for the duration of the call.
@@ -3062,7 +3150,7 @@ extern "C" int32_t vox_model_set_sessions(vox_model* m, int32_t sessions) {
     return ctx_bind(m->ctx);
 }
 static int32_t transcribe_batch_sessions(vox_model* m, int S, int32_t n, const float* const* samples, const size_t* n_samples, const int32_t* norm_group, const float* t_embed,
-                                         int32_t* const* out_ids, const int32_t* caps, int32_t* n_ids, int32_t mem_kind) {
+                                         int32_t* const* out_ids, const int32_t* caps, int32_t* n_ids, int32_t mem_kind, const RecordsOut* rec) {
     const double t0 = now_ms();
     // groups of units (a normalisation group, or a unit on its own), heaviest first onto the least loaded session
     std::vector<std::vector<int>> members; { std::map<int32_t, int> by_id;
@@ -3074,13 +3162,17 @@ static int32_t transcribe_batch_sessions(vox_model* m, int S, int32_t n, const f
     std::vector<std::vector<int>> part(S); std::vector<double> load(S, 0.0);
     for (int g : gi) { int k = 0; for (int j = 1; j < S; j++) if (load[j] < load[k]) k = j; load[k] += w[g]; for (int i : members[g]) part[k].push_back(i); }
     for (auto& p : part) std::sort(p.begin(), p.end());
-    struct Sub { std::vector<const float*> s; std::vector<size_t> ns; std::vector<int32_t> grp; std::vector<int32_t*> out; std::vector<int32_t> caps, nid; int32_t rc = VOX_OK; std::string err; vox_timings tm{}; };
+    struct Sub { std::vector<const float*> s; std::vector<size_t> ns; std::vector<int32_t> grp; std::vector<int32_t*> out; std::vector<int32_t> caps, nid; int32_t rc = VOX_OK; std::string err; vox_timings tm{};
+                 std::vector<vox_token_score*> rs; std::vector<vox_token_alts*> ra; };      // (rs / ra: the session's units' record arrays of a scored call)
     std::vector<Sub> sub(S);
-    for (int k = 0; k < S; k++) for (int i : part[k]) { Sub& u = sub[k]; u.s.push_back(samples[i]); u.ns.push_back(n_samples[i]); if (norm_group) u.grp.push_back(norm_group[i]); u.out.push_back(out_ids[i]); u.caps.push_back(caps[i]); u.nid.push_back(0); }
+    for (int k = 0; k < S; k++) for (int i : part[k]) { Sub& u = sub[k]; u.s.push_back(samples[i]); u.ns.push_back(n_samples[i]); if (norm_group) u.grp.push_back(norm_group[i]); u.out.push_back(out_ids[i]); u.caps.push_back(caps[i]); u.nid.push_back(0);
+                                                  if (rec && rec->scores) u.rs.push_back(rec->scores[i]); if (rec && rec->alts) u.ra.push_back(rec->alts[i]); }
     auto run = [&](int k) {
         Sub& u = sub[k]; vox_model* mk = k == 0 ? m : m->twins[(size_t)k - 1];
         if (u.s.empty()) return;
-        u.rc = transcribe_batch_one_session(mk, (int32_t)u.s.size(), u.s.data(), u.ns.data(), norm_group ? u.grp.data() : nullptr, t_embed, u.out.data(), u.caps.data(), u.nid.data(), mem_kind);
+        const RecordsOut sub_rec{u.rs.empty() ? nullptr : u.rs.data(), u.ra.empty() ? nullptr : u.ra.data(), rec ? rec->k : 0};      // every session writes its own units' records
+        u.rc = transcribe_batch_one_session(mk, (int32_t)u.s.size(), u.s.data(), u.ns.data(), norm_group ? u.grp.data() : nullptr, t_embed, u.out.data(), u.caps.data(), u.nid.data(), mem_kind,
+                                            rec ? &sub_rec : nullptr);
         if (u.rc != VOX_OK) u.err = g_err;      // (thread-local: read on the thread that failed)
         u.tm = mk->timings;
     };
@@ -3102,8 +3194,29 @@ static int32_t transcribe_batch_sessions(vox_model* m, int S, int32_t n, const f
     tm.decode_tokens = total; tm.total_ms = now_ms() - t0; m->timings = tm;
     return VOX_OK;
 }
+static int32_t transcribe_batch_entry(vox_model* m, int32_t n, const float* const* samples_in, const size_t* n_samples, const int32_t* norm_group, const float* t_embed,
+                                      int32_t* const* out_ids, const int32_t* caps, int32_t* n_ids, int32_t mem_kind_in, const RecordsOut* rec);
 extern "C" int32_t vox_transcribe_batch_ex(vox_model* m, int32_t n, const float* const* samples_in, const size_t* n_samples, const int32_t* norm_group, const float* t_embed,
                                            int32_t* const* out_ids, const int32_t* caps, int32_t* n_ids, int32_t mem_kind_in) {
+    return transcribe_batch_entry(m, n, samples_in, n_samples, norm_group, t_embed, out_ids, caps, n_ids, mem_kind_in, nullptr);
+}
+// the same call with a record per id (see the header): every argument is checked here, before a device is touched
+extern "C" int32_t vox_transcribe_batch_scored(vox_model* m, int32_t n, const float* const* samples, const size_t* n_samples, const int32_t* norm_group, const float* t_embed,
+                                               int32_t* const* out_ids, const int32_t* caps, int32_t* n_ids, vox_token_score* const* scores, vox_token_alts* const* alts,
+                                               int32_t k, int32_t mem_kind) {
+    ARGCHK(m, "null model"); ARGCHK(samples && n_samples && t_embed && out_ids, "null argument"); ARGCHK(caps, "null caps"); ARGCHK(n_ids, "null n_ids");
+    ARGCHK(n > 0 && n <= 4096, "batch size %d out of range (1..4096)", n);
+    VOXCHK(records_args_check(scores, alts, k));
+    ARGCHK(mem_kind == VOX_MEM_HOST || mem_kind == VOX_MEM_DEVICE, "bad mem_kind %d", mem_kind);
+    for (int i = 0; i < n; i++) {
+        ARGCHK(out_ids[i] || caps[i] <= 0, "null out_ids[%d]", i);
+        ARGCHK(!scores || scores[i] || caps[i] <= 0, "null scores[%d]", i); ARGCHK(!alts || alts[i] || caps[i] <= 0, "null alts[%d]", i);
+    }
+    const RecordsOut rec{scores, alts, k};
+    return transcribe_batch_entry(m, n, samples, n_samples, norm_group, t_embed, out_ids, caps, n_ids, mem_kind, &rec);
+}
+static int32_t transcribe_batch_entry(vox_model* m, int32_t n, const float* const* samples_in, const size_t* n_samples, const int32_t* norm_group, const float* t_embed,
+                                      int32_t* const* out_ids, const int32_t* caps, int32_t* n_ids, int32_t mem_kind_in, const RecordsOut* rec) {
     ARGCHK(m, "null model");
     const bool tapped = m->tap.armed; m->tap.armed = false;      // an armed tap is consumed by this call, whatever its outcome
     ARGCHK(samples_in && n_samples && t_embed && out_ids && caps && n_ids, "null argument"); ARGCHK(n > 0 && n <= 4096, "batch size %d out of range (1..4096)", n);
@@ -3118,10 +3231,10 @@ extern "C" int32_t vox_transcribe_batch_ex(vox_model* m, int32_t n, const float*
         const int S = std::min((int)m->twins.size() + 1, n / kMinUnitsPerSession);
         if (S > 1 && tapped) return fail(VOX_ERR_UNSUPPORTED, "the batch logits tap covers one session: this call would run as %d (vox_model_set_sessions)", S);
         if (S > 1) { for (int i = 0; i < n; i++) ARGCHK(samples_in[i] && n_samples[i] > 0, "empty audio in batch slot %d", i);
-                     return transcribe_batch_sessions(m, S, n, samples_in, n_samples, norm_group, t_embed, out_ids, caps, n_ids, mem_kind_in); }
+                     return transcribe_batch_sessions(m, S, n, samples_in, n_samples, norm_group, t_embed, out_ids, caps, n_ids, mem_kind_in, rec); }
     }
     m->tap.on = tapped;
-    const int32_t r = transcribe_batch_one_session(m, n, samples_in, n_samples, norm_group, t_embed, out_ids, caps, n_ids, mem_kind_in);
+    const int32_t r = transcribe_batch_one_session(m, n, samples_in, n_samples, norm_group, t_embed, out_ids, caps, n_ids, mem_kind_in, rec);
     m->tap.on = false; m->tap.ready = tapped && r == VOX_OK;
     return r;
 }
@@ -3157,7 +3270,7 @@ static int32_t group_peak_scales(vox_model* m, int32_t n, const float* const* sa
     return VOX_OK;
 }
 static int32_t transcribe_batch_one_session(vox_model* m, int32_t n, const float* const* samples_in, const size_t* n_samples, const int32_t* norm_group, const float* t_embed,
-                                            int32_t* const* out_ids, const int32_t* caps, int32_t* n_ids, int32_t mem_kind_in) {
+                                            int32_t* const* out_ids, const int32_t* caps, int32_t* n_ids, int32_t mem_kind_in, const RecordsOut* rec) {
     const float* const* samples = samples_in; int32_t mem_kind = mem_kind_in;
     GroupScales gs;      // (declared before everything that launches on its buffers; the impls drain the streams before they return)
     if (norm_group) {
@@ -3172,6 +3285,9 @@ static int32_t transcribe_batch_one_session(vox_model* m, int32_t n, const float
         std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return n_samples[a] > n_samples[b]; });
     std::vector<const float*> p_s(n), p_sc(n, nullptr); std::vector<size_t> p_n(n); std::vector<int32_t*> p_o(n); std::vector<int32_t> p_c(n), p_k(n, 0);
     for (int i = 0; i < n; i++) { const int o = order[i]; p_s[i] = samples[o]; p_n[i] = n_samples[o]; p_o[i] = out_ids[o]; p_c[i] = caps[o]; if (norm_group) p_sc[i] = scale_of[o]; }
+    std::vector<vox_token_score*> p_rs; std::vector<vox_token_alts*> p_ra;      // the record arrays in the same order
+    if (rec && rec->scores) { p_rs.resize(n); for (int i = 0; i < n; i++) p_rs[i] = rec->scores[order[i]]; }
+    if (rec && rec->alts) { p_ra.resize(n); for (int i = 0; i < n; i++) p_ra[i] = rec->alts[order[i]]; }
     const float* const* usc = norm_group ? p_sc.data() : nullptr;
     // <= 16 rows: one group (the batched decode-layer engine).  Wider: continuous batching over slots, in sessions whose resident K / V stays under 64 GB (212 992 B per
     // position and utterance: 54 MB at 256 positions -> 1 174 utterances; every session pays its own tail and graph captures, so the 647-clip corpus is ONE session);
@@ -3200,9 +3316,10 @@ static int32_t transcribe_batch_one_session(vox_model* m, int32_t n, const float
     for (int pi = 0, a = 0; pi < n_parts && r == VOX_OK; pi++) {
         const int b = a + (n - a) / (n_parts - pi);      // equal contiguous parts of the sorted order
         const int np = b - a;
+        const RecordsOut part_rec{p_rs.empty() ? nullptr : p_rs.data() + a, p_ra.empty() ? nullptr : p_ra.data() + a, rec ? rec->k : 0};
         r = retry_on_launches([&](bool engine) {
             return (cont ? transcribe_continuous_impl : transcribe_batch_impl)(m, np, p_s.data() + a, p_n.data() + a, t_embed, p_o.data() + a, p_c.data() + a, p_k.data() + a, mem_kind,
-                                                                               order.data() + a, engine, usc ? usc + a : nullptr);
+                                                                               order.data() + a, engine, usc ? usc + a : nullptr, rec ? &part_rec : nullptr);
         });
         acc.preprocess_ms += m->timings.preprocess_ms; acc.encode_ms += m->timings.encode_ms; acc.decode_ms += m->timings.decode_ms; acc.total_ms += m->timings.total_ms;
         acc.decode_tokens += m->timings.decode_tokens; acc.graph_replays += m->timings.graph_replays;
@@ -3421,6 +3538,28 @@ extern "C" int32_t vox_alternatives_rows(vox_ctx* c, const float* logits, int32_
     }
     HIPCHK(launch_alts_rows(logits, M, V, k, dout.as<TokenAlts>(), s));
     HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)M * sizeof(TokenAlts), hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
+    if (c->pw_model) return pw_after_sync(c->pw_model);      // (a synchronising call of the piecewise surface, as vox_score_rows)
+    return VOX_OK;
+}
+
+// both records from one launch (launch_records_rows: the kernel the scored offline and batch calls take theirs from).  Every check before the context is bound; host
+// logits are uploaded.  Records host; synchronises.
+extern "C" int32_t vox_records_rows(vox_ctx* c, const float* logits, int32_t M, int32_t V, int32_t k, vox_token_score* scores, vox_token_alts* alts, int32_t mem_kind) {
+    ARGCHK(c, "null context"); ARGCHK(logits, "null logits"); ARGCHK(M > 0 && V > 0, "bad shape %d x %d", M, V);
+    VOXCHK(records_args_check(scores, alts, k));
+    ARGCHK(k > 0 || scores, "k == 0 needs the scores array");
+    ARGCHK(mem_kind == VOX_MEM_HOST || mem_kind == VOX_MEM_DEVICE, "bad mem_kind %d", mem_kind);
+    VOXCHK(ctx_bind(c));
+    hipStream_t s = c->stream; DevBuf dx, dsc, dal;
+    if (scores) HIPCHK(dsc.alloc_pooled(c, (size_t)M * sizeof(TokenScore)));
+    if (alts) HIPCHK(dal.alloc_pooled(c, (size_t)M * sizeof(TokenAlts)));
+    if (mem_kind == VOX_MEM_HOST) {
+        HIPCHK(dx.alloc_pooled(c, (size_t)M * V * 4)); HIPCHK(hipMemcpyAsync(dx.p, logits, (size_t)M * V * 4, hipMemcpyHostToDevice, s)); logits = dx.as<float>();
+    }
+    HIPCHK(launch_records_rows(logits, M, V, k, dsc.as<TokenScore>(), dal.as<TokenAlts>(), s));
+    if (scores) HIPCHK(hipMemcpyAsync(scores, dsc.p, (size_t)M * sizeof(TokenScore), hipMemcpyDeviceToHost, s));
+    if (alts) HIPCHK(hipMemcpyAsync(alts, dal.p, (size_t)M * sizeof(TokenAlts), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
     if (c->pw_model) return pw_after_sync(c->pw_model);      // (a synchronising call of the piecewise surface, as vox_score_rows)
     return VOX_OK;
 }

@@ -473,6 +473,20 @@ hipError_t launch_alts_rows(const float* x, int rows, int V, int k, TokenAlts* o
 // behind launch_stream_score's place in the tick: slot z < n writes the record of the id session order[z] just emitted from row z of logits [n][vocab] into
 // mem[order[z]].alts[STRM_POS - first_pos] at that session's alts_k; sessions whose alts pointer is null are skipped
 hipError_t launch_stream_alts(const float* logits, int vocab, const StreamMember* mem, const int* order, int n, int first_pos, hipStream_t s);
+// ---- both records in one launch (the offline and batch paths: records_row, vox_kernels.hip).  The scored id is the row's own argmax by the rule (0 when nothing wins).
+// k == 0: scores[r] alone (alts null), launch_score_rows' arithmetic.  k in 1 .. 8: alts[r] and, when scores is given, scores[r] from the same two scans of the row.
+// Bit for bit the records of launch_score_rows(ids = null) and launch_alts_rows on the same row.
+hipError_t launch_records_rows(const float* x, int rows, int V, int k, TokenScore* scores, TokenAlts* alts, hipStream_t s);
+// the batch drivers' form, in front of the argmax launch of a step (which moves pos, slot_clip and the queues).  Rows are addressed as BatchTapParams addresses them;
+// utterance c's id j = pos[r] + 1 - first_pos goes to record rec_off[c] + j of scores / alts (rec_off [n_clips + 1]: the prefix sum of the utterances' id counts,
+// n_records = rec_off[n_clips]; a j outside the utterance's count writes nothing).  scores / alts / k as launch_records_rows.
+struct BatchRecordsParams {
+    const float* logits; int vocab;                    // [n_rows][vocab]
+    const int* slot_clip; int clip0; const int* pos; const int* seq_len;      // per row (slot_clip, seq_len may be null)
+    const int* rec_off; int n_clips, n_records, first_pos;
+    TokenScore* scores; TokenAlts* alts; int k;
+};
+hipError_t launch_batch_records(const BatchRecordsParams& p, int n_rows, hipStream_t s);
 // ---- the ring keep of a peek (vox_stream_peek, vox_stream_group_peek): around ticks that are taken back.  Slot z < n works for session order[z] on its own area
 // keep + z * slot_stride (floats, a multiple of 4): [STRM_WORDS ints: the state block][K: layers x n_heads x rows x hd][V: the same].
 // restore = 0 (save, in front of the ticks): the state block, and of every (layer, head) of K and V the `rows` ring rows from STRM_HEAD on, modulo cap -- the slots the

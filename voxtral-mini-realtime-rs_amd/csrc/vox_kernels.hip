@@ -4782,14 +4782,17 @@ hipError_t launch_stream_keep(const StreamKeepParams& p, int restore, hipStream_
 __device__ __forceinline__ bool argmax_beats(float x, float v) {      // would (x, a later column) replace the running best v?  The rule's own test
     int idx = 0; argmax_take<true>(v, idx, x, 1); return idx != 0;
 }
+// alts_merge: the two scans and the merge, `rounds` rounds of it (1 .. 8).  Thread 0 gets what the records are written from -- n, the winners in s_val / s_id (the
+// caller's LDS, VOX_ALTS_MAX entries each), whether the row sums (ok), its maximum m, logf(S) and the entropy; the other threads' return value means nothing.
+struct AltsMerge { int n; bool ok; float m, lse, entropy; };
 template <int NT>
-__device__ __forceinline__ void alts_row(const float* __restrict__ row, int V, int k, TokenAlts* __restrict__ out, float* sv, int* si) {
+__device__ __forceinline__ AltsMerge alts_merge(const float* __restrict__ row, int V, int rounds, float* sv, int* si, float* s_val, int* s_id) {
     constexpr int K = VOX_ALTS_MAX;
-    __shared__ int s_nan, s_win, s_id[K];
-    __shared__ float s_val[K], s_t[16];
+    __shared__ int s_nan, s_win;
+    __shared__ float s_t[16];
     const bool al = (reinterpret_cast<uintptr_t>(row) & 15) == 0;
     const int V4 = V >> 2;
-    k = k < 1 ? 1 : k > K ? K : k;
+    const int k = rounds < 1 ? 1 : rounds > K ? K : rounds;
     if (threadIdx.x == 0) s_nan = 0;
     float lv[K]; int li[K]; bool nan = false;
 #pragma unroll
@@ -4845,17 +4848,31 @@ __device__ __forceinline__ void alts_row(const float* __restrict__ row, int V, i
     for (int o = 32; o > 0; o >>= 1) { acc += __shfl_xor(acc, o); tac += __shfl_xor(tac, o); }
     if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = acc; s_t[threadIdx.x >> 6] = tac; }      // (sv is free: the merge's last barrier lies behind thread 0's read)
     __syncthreads();
-    if (threadIdx.x != 0) return;
-    const float qnan = __int_as_float(0x7fc00000);
+    AltsMerge r; r.n = n; r.ok = ok; r.m = m; r.lse = 0.0f; r.entropy = __int_as_float(0x7fc00000);
+    if (threadIdx.x != 0) return r;
     float S = sv[0], T = s_t[0];
     for (int w = 1; w < NT / 64; w++) { S += sv[w]; T += s_t[w]; }
-    const float lse = logf(S);
-    out->entropy = ok ? fmaxf(0.0f, lse - T / S) : qnan; out->n = n;
+    r.lse = logf(S);
+    if (ok) r.entropy = fmaxf(0.0f, r.lse - T / S);
+    return r;
+}
+// thread 0: the record of a merge, its first n <= a.n winners
+__device__ __forceinline__ void alts_write(TokenAlts* __restrict__ out, const AltsMerge& a, int n, const float* s_val, const int* s_id) {
+    constexpr int K = VOX_ALTS_MAX;
+    const float qnan = __int_as_float(0x7fc00000);
+    out->entropy = a.entropy; out->n = n;
 #pragma unroll
     for (int j = 0; j < K; j++) {
         const bool has = j < n;
-        out->alt[j].id = has ? s_id[j] : -1; out->alt[j].logprob = has && ok ? (s_val[j] - m) - lse : qnan;
+        out->alt[j].id = has ? s_id[j] : -1; out->alt[j].logprob = has && a.ok ? (s_val[j] - a.m) - a.lse : qnan;
     }
+}
+template <int NT>
+__device__ __forceinline__ void alts_row(const float* __restrict__ row, int V, int k, TokenAlts* __restrict__ out, float* sv, int* si) {
+    __shared__ int s_id[VOX_ALTS_MAX];
+    __shared__ float s_val[VOX_ALTS_MAX];
+    const AltsMerge a = alts_merge<NT>(row, V, k, sv, si, s_val, s_id);
+    if (threadIdx.x == 0) alts_write(out, a, a.n, s_val, s_id);
 }
 // the plain form: one workgroup per row of x [rows][V]
 __global__ __launch_bounds__(1024) VOX_NO_PK_F32 void alts_rows_kernel(const float* __restrict__ x, int V, int k, TokenAlts* __restrict__ out) {
@@ -4883,6 +4900,72 @@ __global__ __launch_bounds__(1024) VOX_NO_PK_F32 void stream_alts_kernel(const f
 hipError_t launch_stream_alts(const float* logits, int vocab, const StreamMember* mem, const int* order, int n, int first_pos, hipStream_t s) {
     if (n < 1 || n > 16 || !logits || !mem || !order || vocab <= 0 || first_pos < 0) return hipErrorInvalidValue;
     stream_alts_kernel<<<dim3(n), dim3(1024), 0, s>>>(logits, vocab, mem, order, first_pos);
+    return hipGetLastError();
+}
+
+// ---- both records of a row in one launch (the offline and batch paths: vox_records_rows, vox_transcribe_*_scored).  The scored id is the row's own argmax by the rule
+// (0 when nothing wins, as launch_score_rows without ids).  Two forms, chosen per call:
+//   k == 0 (scores only): the argmax, then score_row on it -- launch_score_rows' kernel body.
+//   k in 1 .. 8: ONE alts_merge, max(k, 2) rounds of it, yields both records.  The alternatives record is the merge's first k winners (the list for k is the list for more
+//   rounds cut short).  The score record follows from the same pass: id = winner 0, runner_up = winner 1 (the argmax over the columns != id by the rule; -1 without one),
+//   margin = L[id] - L[runner_up] (- (-inf) without one), logprob = alt[0].logprob, whose chain of adds, tree and walk are score_row's.  Nothing wins (n == 0): id 0,
+//   margin = L[0] - (-inf) as score_row forms it on t = 0.  Two scans of the row instead of the four of score_row + alts_row.
+// The records are bit for bit launch_score_rows' and launch_alts_rows' on the same row.
+template <int NT>
+__device__ __forceinline__ void records_row(const float* __restrict__ row, int V, int k, TokenScore* __restrict__ sc, TokenAlts* __restrict__ al, float* sv, int* si) {
+    if (k < 1 || !al) {      // (uniform per launch)
+        if (!sc) return;
+        __shared__ int s_t;
+        float v; int idx;
+        argmax_scan_row<NT>(row, V, v, idx);
+        block_argmax<NT>(v, idx, sv, si);
+        if (threadIdx.x == 0) s_t = idx == 0x7fffffff ? 0 : idx;
+        __syncthreads();
+        const int t = s_t;
+        const RowScore r = score_row<NT>(row, V, t, sv, si);
+        if (threadIdx.x == 0) *sc = TokenScore{r.logprob, r.margin, r.runner_up, t};
+        return;
+    }
+    __shared__ int s_id[VOX_ALTS_MAX];
+    __shared__ float s_val[VOX_ALTS_MAX];
+    const AltsMerge a = alts_merge<NT>(row, V, sc && k < 2 ? 2 : k, sv, si, s_val, s_id);
+    if (threadIdx.x != 0) return;
+    alts_write(al, a, a.n < k ? a.n : k, s_val, s_id);
+    if (!sc) return;
+    const float lt = a.n > 0 ? s_val[0] : row[0], bv = a.n > 1 ? s_val[1] : -INFINITY;
+    TokenScore r;
+    r.logprob = a.n > 0 && a.ok ? (s_val[0] - a.m) - a.lse : __int_as_float(0x7fc00000);
+    r.margin = lt - bv; r.runner_up = a.n > 1 ? s_id[1] : -1; r.id = a.n > 0 ? s_id[0] : 0;
+    *sc = r;
+}
+// the plain form: one workgroup per row of x [rows][V], record r of either array
+__global__ __launch_bounds__(1024) VOX_NO_PK_F32 void records_rows_kernel(const float* __restrict__ x, int V, int k, TokenScore* __restrict__ sc, TokenAlts* __restrict__ al) {
+    __shared__ float bv[16];
+    __shared__ int bi[16];
+    records_row<1024>(x + (size_t)blockIdx.x * V, V, k, sc ? sc + blockIdx.x : nullptr, al ? al + blockIdx.x : nullptr, bv, bi);
+}
+hipError_t launch_records_rows(const float* x, int rows, int V, int k, TokenScore* scores, TokenAlts* alts, hipStream_t s) {
+    if (rows <= 0 || V <= 0 || k < 0 || k > VOX_ALTS_MAX || !x || (k == 0 ? (!scores || alts) : !alts)) return hipErrorInvalidValue;
+    records_rows_kernel<<<dim3(rows), dim3(1024), 0, s>>>(x, V, k, scores, alts);
+    return hipGetLastError();
+}
+// the batch drivers' form, in front of the step's argmax launch (see BatchRecordsParams): every index is checked before anything is read or written
+__global__ __launch_bounds__(1024) VOX_NO_PK_F32 void batch_records_kernel(const BatchRecordsParams p) {
+    __shared__ float bv[16];
+    __shared__ int bi[16];
+    const int r = blockIdx.x;
+    const int c = p.slot_clip ? p.slot_clip[r] : p.clip0 + r;
+    if (c < 0 || c >= p.n_clips) return;               // an idle slot
+    const int cur = p.pos[r] + 1;
+    if (p.seq_len && cur >= p.seq_len[r]) return;      // the argmax launch writes no token for this row
+    const int j = cur - p.first_pos, o0 = p.rec_off[c], cnt = p.rec_off[c + 1] - o0;
+    if (j < 0 || j >= cnt || o0 < 0 || o0 + j >= p.n_records) return;
+    records_row<1024>(p.logits + (size_t)r * p.vocab, p.vocab, p.k, p.scores ? p.scores + o0 + j : nullptr, p.alts ? p.alts + o0 + j : nullptr, bv, bi);
+}
+hipError_t launch_batch_records(const BatchRecordsParams& p, int n_rows, hipStream_t s) {
+    if (n_rows <= 0 || !p.logits || !p.pos || !p.rec_off || p.vocab <= 0 || p.n_clips <= 0 || p.n_records < 0 || p.k < 0 || p.k > VOX_ALTS_MAX ||
+        (p.k == 0 ? (!p.scores || p.alts) : !p.alts)) return hipErrorInvalidValue;
+    batch_records_kernel<<<dim3(n_rows), dim3(1024), 0, s>>>(p);
     return hipGetLastError();
 }
 

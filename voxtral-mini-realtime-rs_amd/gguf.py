@@ -433,6 +433,21 @@ def alternatives_rows(ctx, logits, k, device_ptr=None, shape=None):
     return out
 
 
+def records_rows(ctx, logits, k=0, device_ptr=None, shape=None):
+    """vox_records_rows: both records of every row of f32 logits [rows][vocab] from one launch, scored on the row's own argmax -> (scores, alts): the structured arrays
+    of score_rows(ctx, logits) and alternatives_rows(ctx, logits, k), bit for bit; k = 0: scores alone, alts is None.  logits: a host array, or device_ptr +
+    shape=(rows, vocab).  Computed on the device; synchronises."""
+    if device_ptr is None:
+        x = _f32(logits); x = x.reshape(1, -1) if x.ndim == 1 else x
+        M, V = x.shape; ptr = _ptr(x); kind = 0
+    else:
+        M, V = (int(v) for v in shape); ptr = C.c_void_p(device_ptr); kind = 1
+    k = int(k)
+    sc = np.zeros(M, dtype=SCORE_DTYPE); al = np.zeros(M, dtype=ALTS_DTYPE) if k != 0 else None
+    check(lib().vox_records_rows(ctx.h, ptr, M, V, k, _ptr(sc), None if al is None else _ptr(al), kind))
+    return sc, al
+
+
 def stream_id_due(k: int, sample_rate: int = 16000) -> int:
     """The smallest number of pushed samples (at `sample_rate`) at which a live session hands out id k of its utterance: 2560 k + 40 at 16 kHz, by the schedule; at
     another rate the smallest n with stream_schedule_rate(n)[1] > k, found by bisection (the schedule is monotone).  This is when the session KNOWS the id, the only time
@@ -989,6 +1004,21 @@ class Q4VoxtralModel:
         check(lib().vox_transcribe_audio(self.h, ptr, n_samples, _ptr(t), _ptr(ids), cap, C.byref(n), kind))
         return ids[:n.value].copy()
 
+    def transcribe_audio_scored(self, samples, t_embed, alternatives=0, device_ptr=None, n_samples=None):
+        """transcribe_audio with a record per id (vox_transcribe_audio_scored) -> (ids, scores, alts): scores[j] / alts[j] are score_rows / alternatives_rows of the f32
+        logits row ids[j] was the argmax of, as SCORE_DTYPE / ALTS_DTYPE arrays; alternatives = 0: scores alone, alts is None; 1..8: that many alternatives per id."""
+        t = _f32(t_embed).reshape(-1)
+        if device_ptr is None:
+            x = _f32(samples); n_samples = x.size; ptr = _ptr(x); kind = 0
+        else:
+            ptr = C.c_void_p(device_ptr); kind = 1
+        k = int(alternatives)
+        cap = n_samples // 1280 + 128
+        ids = np.zeros(cap, dtype=np.int32); n = C.c_int32()
+        sc = np.zeros(cap, dtype=SCORE_DTYPE); al = np.zeros(cap, dtype=ALTS_DTYPE) if k != 0 else None
+        check(lib().vox_transcribe_audio_scored(self.h, ptr, n_samples, _ptr(t), _ptr(ids), cap, C.byref(n), _ptr(sc), None if al is None else _ptr(al), k, kind))
+        return ids[:n.value].copy(), sc[:n.value].copy(), None if al is None else al[:n.value].copy()
+
     def create_stream(self, t_embed, gain=1.0, enc_capacity_rows=0, max_positions=0, sample_rate=16000) -> LiveStream:
         """A live session on this model (vox_stream_create / vox_stream_create_rate): push(x) -> ids, finish(), reset(), info(), close().  gain multiplies every sample
         (a stream has no file peak: 0.95 / max|x| of a known file reproduces transcribe_audio).  sample_rate: the rate of the samples that will be pushed."""
@@ -1009,6 +1039,16 @@ class Q4VoxtralModel:
         bin/transcribe.rs:207-226); < 0 = use the unit as it is; None = every unit normalises itself.
         tap_units (vox_debug_batch_tap_*): unit indices whose logits rows are tapped -> (outs, taps), taps[j] [len(outs[tap_units[j]])][vocab] f32: row k is the row
         out_ids[tap_units[j]][k] was the argmax of."""
+        return self._transcribe_batch(samples_list, t_embed, device_ptrs, n_samples, norm_group, tap_units, None)
+
+    def transcribe_batch_scored(self, samples_list, t_embed, alternatives=0, norm_group=None, tap_units=None, device_ptrs=None, n_samples=None):
+        """transcribe_batch with a record per id (vox_transcribe_batch_scored) -> (ids, scores, alts_or_None[, taps]): per unit, scores[i][j] / alts[i][j] are score_rows /
+        alternatives_rows of the f32 logits row ids[i][j] was the argmax of (SCORE_DTYPE / ALTS_DTYPE arrays, one per unit, as long as the unit's ids).
+        alternatives = 0: scores alone and None for the alternatives; 1..8: that many alternatives per id.  The ids are transcribe_batch's; tap_units as there."""
+        return self._transcribe_batch(samples_list, t_embed, device_ptrs, n_samples, norm_group, tap_units, int(alternatives))
+
+    def _transcribe_batch(self, samples_list, t_embed, device_ptrs, n_samples, norm_group, tap_units, alternatives):
+        """the two calls above; alternatives None: the unscored entry points"""
         t = _f32(t_embed).reshape(-1)
         if device_ptrs is None:
             arrs = [_f32(x) for x in samples_list]; n = len(arrs)
@@ -1026,16 +1066,22 @@ class Q4VoxtralModel:
             pc = PadConfig.voxtral()
             max_rows = max(1, max(pc.padded_len(int(lens[u])) // 2560 - 35 for u in units))      # >= max(S - 38, 1): S <= padded / 2560 + 1 decoder positions
             check(lib().vox_debug_batch_tap_arm(self.h, (C.c_int32 * len(units))(*units), len(units), max_rows))
-        if norm_group is None:
+        if norm_group is not None and len(norm_group) != n:
+            raise ValueError("norm_group needs one entry per unit")
+        grp = None if norm_group is None else (C.c_int32 * n)(*[int(g) for g in norm_group])
+        if alternatives is not None:
+            scs = [np.zeros(cp, dtype=SCORE_DTYPE) for cp in caps]; als = [np.zeros(cp, dtype=ALTS_DTYPE) for cp in caps] if alternatives != 0 else None
+            sptrs = (C.c_void_p * n)(*[a.ctypes.data for a in scs]); aptrs = None if als is None else (C.c_void_p * n)(*[a.ctypes.data for a in als])
+            check(lib().vox_transcribe_batch_scored(self.h, n, ptrs, lens, grp, _ptr(t), optrs, ccaps, nids, sptrs, aptrs, alternatives, kind))
+        elif norm_group is None:
             check(lib().vox_transcribe_batch(self.h, n, ptrs, lens, _ptr(t), optrs, ccaps, nids, kind))
         else:
-            if len(norm_group) != n:
-                raise ValueError("norm_group needs one entry per unit")
-            grp = (C.c_int32 * n)(*[int(g) for g in norm_group])
             check(lib().vox_transcribe_batch_ex(self.h, n, ptrs, lens, grp, _ptr(t), optrs, ccaps, nids, kind))
         res = [outs[i][:nids[i]].copy() for i in range(n)]
+        if alternatives is not None:
+            recs = ([scs[i][:nids[i]].copy() for i in range(n)], None if als is None else [als[i][:nids[i]].copy() for i in range(n)])
         if tap_units is None:
-            return res
+            return res if alternatives is None else (res, *recs)
         V = self.config.vocab
         buf = np.zeros((len(units), max_rows, V), dtype=np.float32); rows = (C.c_int32 * len(units))()
         check(lib().vox_debug_batch_tap_fetch(self.h, buf.ctypes.data, rows))
@@ -1044,7 +1090,7 @@ class Q4VoxtralModel:
             if rows[j] != len(res[u]):
                 raise VoxError(1, f"batch tap: unit {u} has {rows[j]} tapped rows for {len(res[u])} ids (max_rows {max_rows})")
             taps.append(buf[j, :rows[j]].copy())
-        return res, taps
+        return (res, taps) if alternatives is None else (res, *recs, taps)
 
     def timings(self):
         t = _lib.Timings(); check(lib().vox_get_stage_timings(self.h, C.byref(t)))
