@@ -428,6 +428,31 @@ int32_t vox_debug_reload_knobs(void);
  * all fed members), [10] a solo stream's.  Behind those, attention again: [11] paged single-query decode, [12] paged batched GQA decode (a paged stream group's step:
  * PAGED DECODER CACHE below).  Entries past [12] are written as 0. */
 int32_t vox_debug_attn_launches(uint64_t* out, int32_t cap);
+/* One decode attention launch on its own (tests): one query row per sequence against a decoder cache, through the launcher and with the parameters of the batched decode
+ * steps -- exactly ONE launch; which kernel ran is the launcher's choice and is read from vox_debug_attn_launches ([3] [4] [5] slab, [11] [12] paged).
+ *   Geometry: n_seq sequences, n_heads query heads over n_kv_heads KV heads, head_dim 128 (anything else is refused), window (-1: none): sequence s at position pos[s]
+ *   attends the keys max(0, pos[s] - window) .. pos[s].  q: host [n_seq][n_heads * 128].
+ *   Slab cache (page_rows == 0): k / v host [n_slices][n_kv_heads][max_seq][128]; sequence s reads slice s, or slice kv_row[s] (n_slices >= n_seq without kv_row).
+ *   Paged cache (page_rows a power of two in 16..1024; max_seq 0): k / v host [pool_pages][n_kv_heads][page_rows][128], page_tab host [n_slices][page_tab_stride]:
+ *   entry q of row s (row kv_row[s] with kv_row) = the physical page of that sequence's rows q * page_rows ..; score_rows >= the most keys any sequence attends.
+ *   Only the entries of a sequence's window are read, and they are checked against the pool here; the others may hold anything.
+ *   Forms: prefer_gqa: the batched steps' flag (slab; the paged launcher takes the GQA form whenever n_heads == 4 n_kv_heads).  spec (slab): offer the speculative
+ *   rows (spec_rows = max_seq) -- the launcher takes that form only with VOX_ATTN_SPEC=1, as in the product.  no_xcd_remap: the measurement knob of the per-head kernels.
+ *   out: out_xf == 0: host float [n_seq][n_heads * 128] (a row the launch did not write comes back NaN); out_xf != 0: host uint16_t, the raw XF planes the wo GEMM reads,
+ *   ceil(n_seq / 16) groups of 2 * (n_heads * 128 / 128) * 256 * 8 uint16_t each (hi plane, then lo plane; sequence s = row s % 16 of group s / 16).
+ * Every argument is checked before the context is bound (VOX_ERR_INVALID); a slab call that would take the GQA form with max_seq above vox_debug_attn_gqa_max_seq is
+ * refused before the launch.  vox_debug_attn_gqa_max_seq: the most rows per KV head the slab GQA form serves on the context's device (SLAB LIMIT below). */
+typedef struct {
+    int32_t n_seq, n_heads, n_kv_heads, head_dim, window;
+    int32_t n_slices, max_seq;
+    int32_t page_rows, pool_pages, page_tab_stride, score_rows;
+    int32_t prefer_gqa, spec, no_xcd_remap, out_xf;
+    const int32_t* pos;
+    const int32_t* kv_row;       /* may be NULL */
+    const int32_t* page_tab;     /* paged calls only */
+} vox_attn_decode_desc;
+int32_t vox_debug_attn_decode(vox_ctx* ctx, const vox_attn_decode_desc* desc, const float* q, const float* k, const float* v, void* out);
+int32_t vox_debug_attn_gqa_max_seq(vox_ctx* ctx, int32_t* out);
 /* Test hook: launches of the linear kernels enqueued by this process so far, by kernel form (host-side counts, as above; nothing is dispatched by them):
  * out[0..2] Q4 GEMV with 1 / 2 / 4 rows per wave, [3] dense GEMV, [4] 5..16-row skinny GEMM, [5] 17..48-row skinny GEMM (one-dimensional form), [6] its split-K form,
  * [7] rows -> XF tiles (helper of [5] / [6]), [8] split-K finishing sum (helper of [6]), [9..12] 16 x 64, 16 x 128, 32 x 64, 32 x 128 tile GEMM, [13] [14] the 32 x 64 and
@@ -617,8 +642,10 @@ int32_t vox_debug_stream_front_tap_fetch(vox_stream* s, float* out_mel, float* o
  *   call, a finished member fed before its vox_stream_group_reset, a push past max_positions, a bad member or mem_kind.
  *   Decode step: the batched step's launch chain on the group's cache slab [layer][member][kv_head][max_positions][head_dim], which does not grow: max_positions = 0
  *   selects 2048 (5.4 minutes; at full size 0.21 MB per position, 0.44 GB per member) and a member that reaches it is refused until its reset.  Each member also holds an
- *   encoder ring (enc_capacity_rows as vox_stream_create's: 0.4 GB at full size).  The decode engine is not used.  Derived from the code, not run: the slab's GQA
- *   decode attention needs 16 max_positions bytes of LDS, so at full size a slab group above about 9 900 positions cannot launch it (creation accepts up to 16 384);
+ *   encoder ring (enc_capacity_rows as vox_stream_create's: 0.4 GB at full size).  The decode engine is not used.  SLAB LIMIT: on a model whose step takes the GQA
+ *   decode attention (head_dim 128, dec_heads == 4 dec_kv_heads: the full-size model) that kernel keeps 16 max_positions bytes of scores in LDS, of which a workgroup
+ *   may ask for 160 KB less the kernel's static share: creation refuses (VOX_ERR_INVALID, nothing allocated) a slab group above that many positions -- 9 976 with this
+ *   build; the message names the limit, vox_debug_attn_gqa_max_seq returns it.  Other models' slab groups take up to the session limit (16 384), and
  *   a paged group (PAGED DECODER CACHE below) has no such bound and grows into a pool.
  *   Creation refuses (VOX_ERR_UNSUPPORTED) what vox_stream_create refuses and models without tile-ordered Q4 weights; n_members outside 1..16 is invalid.
  *   gains: one per member, null = 1.0 each.

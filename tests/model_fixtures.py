@@ -256,13 +256,18 @@ def fill_edge_caches(caches, n_layers, n_kv, hd, lo, hi, edge_rows, seed=2026, s
                 upd(l, a, k, v)
 
 
+# every slot of vox_debug_attn_launches, in the order of include/voxtral_hip.h (AttnForm, csrc/vox_kernels.h)
+ATTN_FORMS = ("prefill_small", "prefill_mfma", "prefill_f32", "decode", "decode_spec", "decode_gqa", "attn_wo", "engine", "stream_ring", "group_resample", "stream_resample",
+              "decode_paged", "decode_gqa_paged")
+
+
 def attn_launches(pkg):
     """Attention launches of this process so far by kernel form (vox_debug_attn_launches)."""
     import ctypes
-    out = (ctypes.c_uint64 * 8)()
-    assert pkg.lib().vox_debug_attn_launches(out, 8) == 0
-    names = ("prefill_small", "prefill_mfma", "prefill_f32", "decode", "decode_spec", "decode_gqa", "attn_wo", "engine")
-    return dict(zip(names, (int(x) for x in out)))
+    out = (ctypes.c_uint64 * (len(ATTN_FORMS) + 1))()
+    assert pkg.lib().vox_debug_attn_launches(out, len(ATTN_FORMS) + 1) == 0
+    assert out[len(ATTN_FORMS)] == 0      # (entries past the last form are written as 0)
+    return dict(zip(ATTN_FORMS, (int(x) for x in out)))
 
 
 def launches_since(pkg, before):

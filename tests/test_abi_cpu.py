@@ -230,6 +230,54 @@ def test_debug_encode_batch_symbol_and_bad_arguments(pkg):
     assert L.vox_abi_version() == 1
 
 
+def test_debug_attn_decode_symbol_and_bad_arguments(pkg):
+    """The decode-attention hook (vox_debug_attn_decode) is exported and bound, its descriptor has the header's layout, and every bad argument -- a position outside
+    the cache, a cache slice outside n_slices, a table entry of a window outside the pool included -- is refused with VOX_ERR_INVALID before the context is bound."""
+    from importlib import import_module
+    L = pkg.lib(); gg = import_module(pkg.__name__ + ".gguf")
+    for name in ("vox_debug_attn_decode", "vox_debug_attn_gqa_max_seq"):
+        assert hasattr(L, name) and name in pkg._lib.SIGNATURES
+    D = gg.AttnDecodeDesc
+    assert C.sizeof(D) == 15 * 4 + 4 + 3 * 8 and D.pos.offset == 64 and D.kv_row.offset == 72 and D.page_tab.offset == 80 and D.out_xf.offset == 56
+    dummy = C.c_void_p(1)      # a context pointer that must never be dereferenced: every case fails on an argument checked before the context is bound
+    q = np.zeros((2, 512), np.float32); k = np.zeros((2, 1, 64, 128), np.float32); out = np.zeros((2, 512), np.float32)
+    pos = np.array([63, 5], np.int32); rows = np.array([1, 0], np.int32); tab = np.zeros((2, 4), np.int32)
+
+    def call(ctx=dummy, qq=q, kk=k, vv=k, oo=out, **kw):
+        base = dict(n_seq=2, n_heads=4, n_kv_heads=1, head_dim=128, window=-1, n_slices=2, max_seq=64, pos=pos.ctypes.data)
+        base.update(kw)
+        d = D(**base)
+        return L.vox_debug_attn_decode(ctx, C.byref(d), None if qq is None else qq.ctypes.data, None if kk is None else kk.ctypes.data,
+                                       None if vv is None else vv.ctypes.data, None if oo is None else oo.ctypes.data)
+
+    paged = dict(max_seq=0, page_rows=16, pool_pages=4, page_tab_stride=4, score_rows=64, page_tab=tab.ctypes.data)
+    bad_tab = tab.copy(); bad_tab[0, 3] = 4
+    row_hi, row_neg, pos_neg = np.array([0, 2], np.int32), np.array([-1, 0], np.int32), np.array([0, -1], np.int32)
+    gone_tab = tab.copy(); gone_tab[1, 0] = -1
+    cases = [(dict(ctx=None), "null argument"), (dict(qq=None), "null argument"), (dict(kk=None), "null argument"), (dict(vv=None), "null argument"),
+             (dict(oo=None), "null argument"), (dict(pos=None), "null argument"),
+             (dict(head_dim=64), "head_dim"), (dict(head_dim=0), "head_dim"), (dict(n_seq=0), "n_seq"), (dict(n_seq=4097), "n_seq"),
+             (dict(n_heads=4, n_kv_heads=3), "head counts"), (dict(n_kv_heads=0), "head counts"), (dict(window=-2), "window"),
+             (dict(n_slices=1), "n_slices"), (dict(n_slices=0), "n_slices"),
+             (dict(kv_row=row_hi.ctypes.data), "kv_row[1]"), (dict(kv_row=row_neg.ctypes.data), "kv_row[0]"), (dict(kv_row=rows.ctypes.data, max_seq=60), "outside the cache"),
+             (dict(max_seq=0), "max_seq"), (dict(max_seq=16385), "max_seq"), (dict(max_seq=63), "pos[0] = 63 outside the cache"),
+             (dict(pos=pos_neg.ctypes.data), "pos[1] = -1"), (dict(score_rows=8), "paged field"),
+             (dict(paged, page_rows=48), "page_rows"), (dict(paged, page_rows=8), "page_rows"), (dict(paged, page_rows=2048), "page_rows"),
+             (dict(paged, page_tab=None), "page_tab"), (dict(paged, max_seq=64), "no max_seq"), (dict(paged, spec=1), "speculative"),
+             (dict(paged, pool_pages=0), "pool_pages"), (dict(paged, page_tab_stride=0), "page_tab_stride"), (dict(paged, page_tab_stride=3), "pos[0] = 63 outside the table"),
+             (dict(paged, score_rows=0), "score_rows"), (dict(paged, score_rows=63), "attends 64 keys"), (dict(paged, window=10, score_rows=10), "attends 11 keys"),
+             (dict(paged, page_tab=bad_tab.ctypes.data), "table entry 3 of its window is 4"),
+             (dict(paged, page_tab=gone_tab.ctypes.data), "sequence 1: table entry 0 of its window is -1")]
+    for kw, msg in cases:
+        assert call(**kw) == 1, kw
+        assert msg in L.vox_last_error().decode(), (kw, L.vox_last_error())
+    n = C.c_int32()
+    assert L.vox_debug_attn_gqa_max_seq(None, C.byref(n)) == 1 and L.vox_debug_attn_gqa_max_seq(dummy, None) == 1
+    with pytest.raises(pkg.VoxError):      # the Python wrapper's own shape checks
+        gg.attn_decode(None, q, k[:, :, :, :64], k[:, :, :, :64], pos, 4, 1)
+    assert L.vox_abi_version() == 1
+
+
 def test_integration_md_sys_block_is_complete_and_current(pkg):
     """INTEGRATION.md section 2 is generated from the header: every declared symbol has its Rust declaration and the block is not stale."""
     import subprocess, sys

@@ -165,6 +165,8 @@ SIGNATURES = {
     "vox_bench_decode_gemv": (i32, [vp, i32, i32, P(C.c_double), P(C.c_double), P(C.c_char_p)]),
     "vox_bench_wide": (i32, [vp, i32, i32, i32, P(C.c_double)]),
     "vox_debug_attn_launches": (i32, [P(C.c_uint64), i32]),
+    "vox_debug_attn_decode": (i32, [vp, vp, vp, vp, vp, vp]),
+    "vox_debug_attn_gqa_max_seq": (i32, [vp, P(i32)]),
     "vox_debug_gemm_launches": (i32, [P(C.c_uint64), i32]),
     "vox_debug_timeline_start": (i32, [vp, i32, i32]),
     "vox_debug_timeline_fetch": (i32, [vp, vp, sz, P(i32), vp]),

@@ -2377,6 +2377,83 @@ struct StepGraphs {
 };
 // XF planes of one 16-row group over K columns: bf16 hi + lo in MFMA A-operand order
 static size_t xf_bytes(int K) { return (size_t)2 * (K / 128) * 256 * 16; }
+
+// ---- one decode attention launch on host buffers (tests): the AttnParams of the batched steps (xf_chain; the lock-step per-operator step; n_seq == 1: the single-row
+// step's with the position per sequence), ONE launch through launch_attn_decode (slab) or launch_attn_decode_paged (page_rows > 0).  Which kernel ran is the launchers'
+// choice alone (vox_debug_attn_launches).  Every argument is checked before the context is bound -- the positions against the cache, the cache slices against n_slices,
+// every table entry of a sequence's window against the pool: nothing a kernel reads lies outside the uploaded buffers.
+extern "C" int32_t vox_debug_attn_gqa_max_seq(vox_ctx* c, int32_t* out) {
+    ARGCHK(c && out, "null argument"); VOXCHK(ctx_bind(c));
+    int most = 0; HIPCHK(attn_decode_gqa_max_seq(&most));
+    *out = most; return VOX_OK;
+}
+extern "C" int32_t vox_debug_attn_decode(vox_ctx* c, const vox_attn_decode_desc* d, const float* q, const float* k, const float* v, void* out) {
+    ARGCHK(c && d && q && k && v && out, "null argument"); ARGCHK(d->pos, "null argument (pos)");
+    ARGCHK(d->head_dim == 128, "head_dim %d: the decoder's decode attention serves head_dim 128 alone", d->head_dim);
+    ARGCHK(d->n_seq >= 1 && d->n_seq <= 4096, "n_seq %d out of range (1..4096)", d->n_seq);
+    ARGCHK(d->n_heads >= 1 && d->n_kv_heads >= 1 && d->n_heads <= 64 && d->n_heads % d->n_kv_heads == 0, "bad head counts (%d query heads, %d KV heads)", d->n_heads, d->n_kv_heads);
+    ARGCHK(d->window >= -1, "window %d (-1: none)", d->window);
+    ARGCHK(d->n_slices >= 1 && d->n_slices <= 4096 && (d->kv_row || d->n_slices >= d->n_seq), "n_slices %d: without kv_row every sequence reads its own slice (n_seq %d)", d->n_slices, d->n_seq);
+    for (int i = 0; d->kv_row && i < d->n_seq; i++) ARGCHK(d->kv_row[i] >= 0 && d->kv_row[i] < d->n_slices, "kv_row[%d] = %d outside the %d slices", i, d->kv_row[i], d->n_slices);
+    const bool paged = d->page_rows != 0;
+    const int hd = 128, H = d->n_heads, KV = d->n_kv_heads, QD = H * hd, W = QD + 2 * KV * hd, n = d->n_seq;
+    int shift = 0;
+    if (!paged) {
+        ARGCHK(d->max_seq >= 1 && d->max_seq <= 16384, "max_seq %d out of range (1..16384)", d->max_seq);
+        ARGCHK(!d->pool_pages && !d->page_tab && !d->page_tab_stride && !d->score_rows, "a slab call takes no paged field");
+        for (int i = 0; i < n; i++) ARGCHK(d->pos[i] >= 0 && d->pos[i] < d->max_seq, "pos[%d] = %d outside the cache's %d rows", i, d->pos[i], d->max_seq);
+    } else {
+        ARGCHK(d->page_rows >= 16 && d->page_rows <= 1024 && !(d->page_rows & (d->page_rows - 1)), "page_rows %d is not a power of two in 16..1024", d->page_rows);
+        while ((1 << shift) < d->page_rows) shift++;
+        ARGCHK(d->page_tab, "null argument (page_tab)"); ARGCHK(!d->max_seq && !d->spec, "a paged call takes no max_seq and has no speculative form");
+        ARGCHK(d->pool_pages >= 1 && d->pool_pages <= (1 << 20), "pool_pages %d out of range", d->pool_pages);
+        ARGCHK(d->page_tab_stride >= 1 && d->page_tab_stride <= 1024, "page_tab_stride %d out of range (1..1024)", d->page_tab_stride);
+        ARGCHK(d->score_rows >= 1 && d->score_rows <= 16384, "score_rows %d out of range (1..16384)", d->score_rows);
+        for (int i = 0; i < n; i++) {
+            const int pos = d->pos[i], row = d->kv_row ? d->kv_row[i] : i;
+            ARGCHK(pos >= 0 && (pos >> shift) < d->page_tab_stride, "pos[%d] = %d outside the table's %d pages of %d rows", i, pos, d->page_tab_stride, d->page_rows);
+            const int j_lo = d->window >= 0 ? std::max(0, pos - d->window) : 0;
+            ARGCHK(pos - j_lo + 1 <= d->score_rows, "pos[%d] = %d attends %d keys, score_rows is %d", i, pos, pos - j_lo + 1, d->score_rows);
+            for (int pg = j_lo >> shift; pg <= (pos >> shift); pg++) {
+                const int e = d->page_tab[(size_t)row * d->page_tab_stride + pg];
+                ARGCHK(e >= 0 && e < d->pool_pages, "sequence %d: table entry %d of its window is %d, outside the pool's %d pages", i, pg, e, d->pool_pages);
+            }
+        }
+    }
+    VOXCHK(ctx_bind(c));
+    if (!paged && d->prefer_gqa && attn_decode_takes_gqa(hd, H, KV)) {      // (the one check that needs the device: the kernel's attributes)
+        int most = 0; HIPCHK(attn_decode_gqa_max_seq(&most));
+        ARGCHK(d->max_seq <= most, "max_seq %d: the slab GQA form serves at most %d rows per KV head", d->max_seq, most);
+    }
+    hipStream_t s = c->stream;
+    const size_t slice_f = paged ? (size_t)KV * d->page_rows * hd : (size_t)KV * d->max_seq * hd, kv_f = slice_f * (paged ? d->pool_pages : d->n_slices);
+    const int n_grp = (n + 15) / 16; const size_t xf_b = xf_bytes(QD);
+    DevBuf dq, dk, dv, dout, dxf, dint;
+    const size_t tab_n = paged ? (size_t)d->n_slices * d->page_tab_stride : 0;
+    HIPCHK(dq.alloc((size_t)n * W * 4)); HIPCHK(dk.alloc(kv_f * 4)); HIPCHK(dv.alloc(kv_f * 4)); HIPCHK(dout.alloc((size_t)n * QD * 4)); HIPCHK(dxf.alloc(xf_b * n_grp));
+    HIPCHK(dint.alloc((2 * (size_t)n + tab_n) * 4));
+    int* d_pos = dint.as<int>(); int* d_row = d_pos + n; int* d_tab = d_row + n;
+    HIPCHK(hipMemsetAsync(dq.p, 0, (size_t)n * W * 4, s));
+    HIPCHK(hipMemcpy2DAsync(dq.p, (size_t)W * 4, q, (size_t)QD * 4, (size_t)QD * 4, n, hipMemcpyHostToDevice, s));      // q rows at the q|k|v row stride, as the steps hold them
+    HIPCHK(hipMemcpyAsync(dk.p, k, kv_f * 4, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(dv.p, v, kv_f * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_pos, d->pos, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    if (d->kv_row) HIPCHK(hipMemcpyAsync(d_row, d->kv_row, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    if (paged) HIPCHK(hipMemcpyAsync(d_tab, d->page_tab, tab_n * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(dout.p, 0xff, (size_t)n * QD * 4, s));      // a row the launch does not write stays NaN
+    HIPCHK(hipMemsetAsync(dxf.p, 0, xf_b * n_grp, s));                 // (the planes of a step start zeroed: XfPlanes)
+    AttnParams ap{}; ap.q = dq.as<float>(); ap.k = dk.as<float>(); ap.v = dv.as<float>(); ap.kv_row_stride = hd; ap.kv_head_stride = d->max_seq * hd; ap.n_heads = H; ap.n_kv_heads = KV;
+    ap.offset = 0; ap.window = d->window; ap.pos_ptr = d_pos; ap.M = 1; ap.pos_per_seq = 1; ap.q_seq_stride = W; ap.out_seq_stride = QD; ap.kv_seq_stride = (long)slice_f;
+    ap.kv_row = d->kv_row ? d_row : nullptr; ap.prefer_gqa = d->prefer_gqa != 0; ap.no_xcd_remap = d->no_xcd_remap != 0; ap.spec_rows = d->spec ? d->max_seq : 0;
+    ap.out = dout.as<float>(); if (d->out_xf) { ap.out_xf = dxf.as<uint16_t>(); ap.out_xf_gstride = (long)(xf_b / 2); }
+    if (paged) {
+        ap.kv_head_stride = (hd << shift); ap.page_tab = d_tab; ap.page_tab_stride = d->page_tab_stride; ap.page_shift = shift; ap.page_floats = (long)slice_f; ap.score_rows = d->score_rows;
+        HIPCHK(launch_attn_decode_paged(ap, hd, s, n));
+    } else HIPCHK(launch_attn_decode(ap, hd, d->max_seq, s, n));
+    if (d->out_xf) HIPCHK(hipMemcpyAsync(out, dxf.p, xf_b * n_grp, hipMemcpyDeviceToHost, s));
+    else HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)n * QD * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return VOX_OK;
+}
 // What a batched XF decode step works on.  f32 rows (h, qkv, logits; att unread), XF planes and partial sums of squares one block per 16-row group, `*_gs` elements apart.
 // k / v: layer 0's cache slab (layer l at + l layer_stride), row r's slice at + r seq_stride, or, with kv_row, the slice kv_row[r] names; pos: the rows' positions.
 // ssq_e: the batched engine's sums of squares (one block of 256 + 16 rows per group); planes: the wide step's K-split scratch, planes_bytes per chain.
@@ -4744,6 +4821,11 @@ static int32_t group_create(vox_model* m, const float* t_embed, int32_t n_member
         ARGCHK(pool_pages <= n_members * most, "a pool of %d pages is more than %d members of %d positions can hold (%d)", pool_pages, n_members, sg.max_pos, n_members * most);
     }
     if (!batch_xf_ok(m)) return fail(VOX_ERR_UNSUPPORTED, "a stream group's decode step runs on the tile-ordered Q4 weights, which this model does not have");
+    if (!paged && attn_decode_takes_gqa(c.dec_head_dim, c.dec_heads, c.dec_kv_heads)) {      // the slab's step is xf_chain with prefer_gqa: its attention keeps 16 bytes of LDS per slab row
+        int most = 0; HIPCHK(attn_decode_gqa_max_seq(&most));
+        ARGCHK(sg.max_pos <= most, "max_positions %d: a slab group of this model serves at most %d positions (its GQA decode attention keeps 16 bytes of LDS per position); "
+                                   "a paged group (vox_stream_group_create_paged) has no such limit", sg.max_pos, most);
+    }
     VOXCHK(enc_stream_rope_ensure(m));
     vox_stream_group* g = new vox_stream_group(); g->m = m; g->ctx = cx; g->t_embed.assign(t_embed, t_embed + c.dec_dim); g->n = n_members; g->g = sg;
     const size_t N = (size_t)n_members; const int D = c.dec_dim, QD = c.dec_heads * c.dec_head_dim, W = QD + 2 * c.dec_kv_heads * c.dec_head_dim, maxp = sg.max_pos;

@@ -147,7 +147,7 @@ struct AttnParams {
     const int* pos_ptr;                      // decode: position = *pos_ptr + offset, kv_len = position+1
     // batched decode (gridDim.y = sequences): sequence s reads pos_ptr[s] and its own q / out rows and KV-cache slice
     int pos_per_seq; int q_seq_stride, out_seq_stride; long kv_seq_stride;
-    const int* kv_row;    // batched decode, optional: sequence s reads cache slice kv_row[s] instead of slice s (attn_decode_gqa_kernel only: launch_attn_decode forces that kernel)
+    const int* kv_row;    // batched decode, optional: sequence s reads cache slice kv_row[s] instead of slice s (attn_decode_kernel and attn_decode_gqa_kernel alike; the paged forms: table row kv_row[s])
     // stacked prefill (gridDim.z = sequences): sequence z has seq_len[z] query rows (kv_len = offset + seq_len[z]); p.M = the maximum;
     // q / out / k / v of sequence z start q_seq_stride / out_seq_stride / kv_seq_stride floats after those of z-1
     const int* seq_len;
@@ -172,7 +172,12 @@ struct AttnParams {
 hipError_t launch_attn_prefill(const AttnParams& p, int hd, hipStream_t s, int n_seq = 1);     // M > 1, causal (+window)
 bool attn_prefill_prefix_ok(const AttnParams& p, int hd, int n_seq);     // may launch_attn_prefill take p's two K / V segments (prefix_len > 0)?
 bool attn_prefill_small_ok(const AttnParams& p, int hd, int n_seq);      // will launch_attn_prefill take the short-sequence kernel (<= 48 rows from position 0, f32; may write XF tiles: p.out_xf_tiles)?
-hipError_t launch_attn_decode(const AttnParams& p, int hd, int max_seq, hipStream_t s, int n_seq = 1);  // M == 1 per sequence
+hipError_t launch_attn_decode(const AttnParams& p, int hd, int max_seq, hipStream_t s, int n_seq = 1);  // M == 1 per sequence; hipErrorInvalidValue, nothing launched: the GQA form with max_seq above attn_decode_gqa_max_seq
+// does launch_attn_decode take the GQA form for this geometry when AttnParams::prefer_gqa is set (one workgroup per KV head and sequence, 4 query heads each)?
+bool attn_decode_takes_gqa(int hd, int n_heads, int n_kv_heads);
+// the most cache rows per KV head (max_seq) that form can serve: the dynamic LDS a workgroup of the current device may ask for (160 KB less the kernel's static LDS,
+// as launch_attn_decode raises the limit) / 16 bytes of scores per row.  The per-head form and the paged forms (score_rows <= window + 1) are not bound by it.
+hipError_t attn_decode_gqa_max_seq(int* out);
 // the same attention with K / V read through a page table: the GQA form where n_heads == 4 n_kv_heads and hd == 128, else the per-head form; a row has launch_attn_decode's bits
 hipError_t launch_attn_decode_paged(const AttnParams& p, int hd, hipStream_t s, int n_seq);
 // single sequence: attention + the wo linear in one launch; acc[wo.N] (int64, zero on entry) receives the product in 2^-32 fixed point (consumer: PRO_RMS_MUL_SUM)

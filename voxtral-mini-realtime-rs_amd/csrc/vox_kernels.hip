@@ -3635,11 +3635,42 @@ hipError_t launch_attn_wo(const AttnParams& p_in, const Q4W& wo, long long* acc,
     return hipGetLastError();
 }
 
+// the dynamic LDS ensure_dyn_lds grants a kernel: the 160 KB of a CU less the kernel's static LDS (the same arithmetic, the same clamp)
+template <class Kern>
+static hipError_t dyn_lds_granted(Kern kern, size_t* out) {
+    hipFuncAttributes fa;
+    hipError_t e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kern));
+    if (e != hipSuccess) { (void)hipGetLastError(); return e; }
+    *out = (size_t)160 * 1024 - std::min<size_t>(fa.sharedSizeBytes, 96 * 1024);
+    return hipSuccess;
+}
+// the slab GQA form keeps 4 query heads' scores, 16 bytes of dynamic LDS per cache row: the most rows per KV head it can serve on the current device
+hipError_t attn_decode_gqa_max_seq(int* out) {
+    static std::atomic<int> known{0};      // the kernel's static LDS is the code object's: asked for once per process, not on every launch
+    int most = known.load(std::memory_order_acquire);
+    if (!most) {
+        size_t lds = 0;
+        hipError_t e = dyn_lds_granted(attn_decode_gqa_kernel<4, false>, &lds);
+        if (e != hipSuccess) return e;
+        most = (int)(lds / (4 * sizeof(float)));
+        known.store(most, std::memory_order_release);
+    }
+    *out = most;
+    return hipSuccess;
+}
+bool attn_decode_takes_gqa(int hd, int n_heads, int n_kv_heads) { return hd == 128 && n_kv_heads > 0 && n_heads == 4 * n_kv_heads; }
+
 hipError_t launch_attn_decode(const AttnParams& p_in, int hd, int max_seq, hipStream_t s, int n_seq) {
     AttnParams p = p_in; p.tl_slot = tl_take_slot(1, 0, p.n_heads, hd);
     const size_t lds = (size_t)max_seq * sizeof(float);
-    if (hd == 128 && p.prefer_gqa && p.n_heads == 4 * p.n_kv_heads && p.kv_head_stride == max_seq * 128) {
+    if (p.prefer_gqa && attn_decode_takes_gqa(hd, p.n_heads, p.n_kv_heads) && p.kv_head_stride == max_seq * 128) {
         auto kern = attn_decode_gqa_kernel<4, false>;      // many sequences: one workgroup per (KV head, sequence), K/V fetched once for its 4 query heads
+        if (4 * lds > 48 * 1024) {      // (below that every device serves it; above, the scores of a longer slab do not fit: refused here, not by the launch)
+            int most = 0;
+            hipError_t el = attn_decode_gqa_max_seq(&most);
+            if (el != hipSuccess) return el;
+            if (max_seq > most) return hipErrorInvalidValue;
+        }
         static DevOnce attr_done;
         hipError_t e = ensure_dyn_lds(kern, 4 * lds, &attr_done);
         if (e != hipSuccess) return e;

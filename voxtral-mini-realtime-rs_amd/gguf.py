@@ -261,6 +261,50 @@ def attention(ctx, q, k, v, n_heads, n_kv_heads, offset=0, window=-1):
     return out
 
 
+class AttnDecodeDesc(C.Structure):
+    """vox_attn_decode_desc (include/voxtral_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("n_seq", "n_heads", "n_kv_heads", "head_dim", "window", "n_slices", "max_seq", "page_rows", "pool_pages", "page_tab_stride",
+                                         "score_rows", "prefer_gqa", "spec", "no_xcd_remap", "out_xf")] + [(n, C.c_void_p) for n in ("pos", "kv_row", "page_tab")]
+
+
+def attn_decode(ctx, q, k, v, pos, n_heads, n_kv_heads, window=-1, kv_row=None, page_tab=None, score_rows=0, prefer_gqa=False, spec=False, no_xcd_remap=False,
+                out_xf=False, head_dim=128):
+    """vox_debug_attn_decode: ONE decode attention launch.  q [n_seq, n_heads*128], pos [n_seq]; slab: k / v [n_slices, n_kv_heads, max_seq, 128]; paged (page_tab
+    [n_slices, stride] int32 given): k / v [pool_pages, n_kv_heads, page_rows, 128].  Returns float32 [n_seq, n_heads*128], or with out_xf the raw XF planes as uint16
+    [ceil(n_seq / 16), 2, n_heads*128 / 128 * 256 * 8] (hi plane, lo plane)."""
+    q, k, v = _f32(q), _f32(k), _f32(v)
+    pos = np.ascontiguousarray(pos, dtype=np.int32)
+    if q.ndim != 2 or k.ndim != 4 or k.shape != v.shape or pos.shape != (q.shape[0],):
+        raise VoxError(1, "attn_decode: bad shapes")
+    d = AttnDecodeDesc(n_seq=q.shape[0], n_heads=n_heads, n_kv_heads=n_kv_heads, head_dim=head_dim, window=window, prefer_gqa=int(prefer_gqa), spec=int(spec),
+                       no_xcd_remap=int(no_xcd_remap), out_xf=int(out_xf), pos=pos.ctypes.data)
+    if kv_row is not None:
+        kv_row = np.ascontiguousarray(kv_row, dtype=np.int32)
+        if kv_row.shape != pos.shape:
+            raise VoxError(1, "attn_decode: bad shapes")
+        d.kv_row = kv_row.ctypes.data
+    if page_tab is None:
+        d.n_slices, d.max_seq = k.shape[0], k.shape[2]
+    else:
+        page_tab = np.ascontiguousarray(page_tab, dtype=np.int32)
+        if page_tab.ndim != 2:
+            raise VoxError(1, "attn_decode: bad shapes")
+        d.n_slices, d.page_tab_stride = page_tab.shape
+        d.pool_pages, d.page_rows, d.score_rows, d.page_tab = k.shape[0], k.shape[2], score_rows, page_tab.ctypes.data
+    if k.shape[1] != n_kv_heads or k.shape[3] != 128 or q.shape[1] != n_heads * 128:
+        raise VoxError(1, "attn_decode: q / k / v widths do not match the head counts")
+    QD = n_heads * 128
+    out = np.empty(((q.shape[0] + 15) // 16, 2, QD // 128 * 256 * 8), np.uint16) if out_xf else np.empty((q.shape[0], QD), np.float32)
+    check(lib().vox_debug_attn_decode(ctx.h, C.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(out)))
+    return out
+
+
+def attn_gqa_max_seq(ctx):
+    """vox_debug_attn_gqa_max_seq: the most rows per KV head the slab GQA decode attention serves (a slab stream group's max_positions on a 4:1 model)."""
+    n = C.c_int32(); check(lib().vox_debug_attn_gqa_max_seq(ctx.h, C.byref(n)))
+    return n.value
+
+
 class Q4Linear:
     """gguf/linear.rs:17-40"""
 
