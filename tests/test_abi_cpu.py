@@ -366,3 +366,14 @@ def test_host_code_under_address_sanitizer(pkg, tmp_path):
     r = subprocess.run([os.path.join(d, "abi_smoke_asan")], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0 and "AddressSanitizer" not in r.stderr, r.stdout + r.stderr[-3000:]
     assert "gguf reader ok" in r.stdout
+
+
+def test_every_source_in_csrc_is_built(pkg):
+    """A unit cannot sit in csrc/ unbuilt, and a header cannot go unwatched: the *.cpp / *.hip files directly under csrc/ (names that begin with `_` aside) are exactly
+    build.py's SOURCES, and the *.h files there are exactly the csrc entries of its HEADERS (the public header lives under include/)."""
+    import importlib
+    build = importlib.import_module(pkg.__name__ + ".build")
+    names = [n for n in os.listdir(build.CSRC) if not n.startswith("_") and os.path.isfile(os.path.join(build.CSRC, n))]
+    assert sorted(n for n in names if n.endswith((".cpp", ".hip"))) == sorted(build.SOURCES)
+    assert len(set(build.SOURCES)) == len(build.SOURCES) and set(build.HOST_SOURCES) <= set(build.SOURCES)
+    assert sorted(n for n in names if n.endswith(".h")) == sorted(h for h in build.HEADERS if os.sep not in h and "/" not in h)

@@ -10,9 +10,9 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.environ.get("VOX_LIB") or os.path.join(PKG_DIR, "libvoxtral_hip.so")   # VOX_LIB: a measurement build (variant_lib_path)
 # host units ("Host units"): the device-free ones include no HIP header and are compiled as plain C++
 HOST_SOURCES_PLAIN = ["vox_audio_host.cpp", "vox_gguf.cpp", "vox_batch_plan.cpp", "vox_feed_plan.cpp"]
-HOST_SOURCES = ["vox_api.cpp", *HOST_SOURCES_PLAIN]
+HOST_SOURCES = ["vox_api.cpp", "vox_ctx.cpp", "vox_tensor.cpp", "vox_cache.cpp", *HOST_SOURCES_PLAIN]
 SOURCES = ["vox_kernels.hip", "vox_engine.hip", "vox_engine_b16.hip", *HOST_SOURCES]
-HEADERS = ["vox_kernels.h", "vox_engine_common.h", "vox_page_pool.h", "vox_host_base.h", os.path.join("..", "..", "include", "voxtral_hip.h")]
+HEADERS = ["vox_kernels.h", "vox_engine_common.h", "vox_page_pool.h", "vox_host_base.h", "vox_dev_base.h", os.path.join("..", "..", "include", "voxtral_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-result"]
 
@@ -48,7 +48,7 @@ def build_all(verbose: bool = False, force: bool = False, tag: str | None = None
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)
 
-    with ThreadPoolExecutor(max_workers=max(1, len(jobs))) as ex:
+    with ThreadPoolExecutor(max_workers=max(1, min(len(jobs), 16))) as ex:
         list(ex.map(run, jobs))
     if jobs or force or _stale(lib_path, objs):
         run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib_path, *objs])

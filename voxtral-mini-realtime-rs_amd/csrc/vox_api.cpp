@@ -1,16 +1,13 @@
-// vox_api.cpp -- C ABI of libvoxtral_hip.so (include/voxtral_hip.h): context, the audio front end's device side,
-// Q4 operator boundary, model loader (GGUF -> packed device arena) and the model-forward
-// orchestration (encoder, prefill, hipGraph-captured sync-free decode step).  The host arithmetic of the
-// front end, the GGUF reader and the planners are units of their own (vox_audio_host.cpp, vox_gguf.cpp, vox_batch_plan.cpp, vox_feed_plan.cpp; vox_host_base.h).
+// vox_api.cpp -- C ABI of libvoxtral_hip.so (include/voxtral_hip.h): model loader (GGUF -> packed device arena) and the model-forward
+// orchestration (encoder, prefill, hipGraph-captured sync-free decode step), the batch drivers, the piecewise surface, the live streams.  Units of their own:
+// the context and the audio front end's device side (vox_ctx.cpp), the Q4 operator boundary (vox_tensor.cpp), the decoder cache (vox_cache.cpp; vox_dev_base.h),
+// the host arithmetic of the front end, the GGUF reader and the planners (vox_audio_host.cpp, vox_gguf.cpp, vox_batch_plan.cpp, vox_feed_plan.cpp; vox_host_base.h).
 //
 // Reference surface mirrored: src/audio/{io,pad,chunk,mel}.rs, src/gguf/{reader,tensor,op,linear,loader,model}.rs,
 // src/models/time_embedding.rs.  No code is shared with oracle/ and there is no CPU fallback for compute.
-#include "../../include/voxtral_hip.h"
-#include "vox_kernels.h"
 #include "vox_page_pool.h"
-#include "vox_host_base.h"
+#include "vox_dev_base.h"
 
-#include <dlfcn.h>
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -19,9 +16,7 @@
 #include <algorithm>
 #include <array>
 #include <cassert>
-#include <chrono>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -37,590 +32,32 @@ using namespace vox;
 using namespace vox_host;
 
 // ------------------------------------------------------------------------------------------------
-// errors
-// ------------------------------------------------------------------------------------------------
-static thread_local std::string g_err;
-namespace vox_host {
-int32_t fail(int32_t code, const char* fmt, ...) {
-    char buf[1024];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-    g_err = buf;
-    return code;
-}
-}  // namespace vox_host
-#define HIPCHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return fail(VOX_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); } while (0)
-
-extern "C" const char* vox_last_error(void) { return g_err.c_str(); }
-extern "C" int32_t vox_abi_version(void) { return 1; }
-extern "C" int32_t vox_device_count(int32_t* n) {
-    ARGCHK(n, "null out pointer");
-    int c = 0; hipError_t e = hipGetDeviceCount(&c);
-    if (e != hipSuccess) { *n = 0; (void)hipGetLastError(); return VOX_OK; }
-    *n = c; return VOX_OK;
-}
-
-// ---- roctx ranges with the reference's tracing span names (gguf/model.rs:784 "encode_audio", :878 "transcribe_streaming", :909 "prefill",
-// :936-937 "decode"): librocprofiler-sdk-roctx is resolved lazily so the library has no hard dependency on the profiler; without it the
-// calls are no-ops.  Under `rocprofv3 --marker-trace` the ranges attribute the kernel trace to the pipeline stages.
-namespace {
-struct Roctx {
-    int (*push)(const char*) = nullptr; int (*pop)() = nullptr;
-    Roctx() {
-        if (knob_str("VOX_NO_ROCTX")) return;
-        void* h = dlopen("librocprofiler-sdk-roctx.so", RTLD_LAZY | RTLD_LOCAL);
-        if (!h) h = dlopen("librocprofiler-sdk-roctx.so.1", RTLD_LAZY | RTLD_LOCAL);
-        if (!h) return;
-        push = reinterpret_cast<int (*)(const char*)>(dlsym(h, "roctxRangePushA")); pop = reinterpret_cast<int (*)()>(dlsym(h, "roctxRangePop"));
-        if (!push || !pop) { push = nullptr; pop = nullptr; }
-    }
-};
-}  // namespace
-static Roctx& roctx() { static Roctx r; return r; }
-static void roctx_push(const char* name) { Roctx& r = roctx(); if (r.push) (void)r.push(name); }
-static void roctx_pop() { Roctx& r = roctx(); if (r.pop) (void)r.pop(); }
-struct RoctxScope { explicit RoctxScope(const char* n) { roctx_push(n); } ~RoctxScope() { roctx_pop(); } };
-// consecutive stages of one function: begin() closes the previous stage; every exit path (error returns included) closes the open one
-struct RoctxStage { bool open = false; void begin(const char* n) { end(); roctx_push(n); open = true; } void end() { if (open) { roctx_pop(); open = false; } } ~RoctxStage() { end(); } };
-
-static double now_ms() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-// ------------------------------------------------------------------------------------------------
-// context
-// ------------------------------------------------------------------------------------------------
-struct vox_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    // mel tables (device)
-    float *d_window = nullptr, *d_cos = nullptr, *d_sin = nullptr, *d_fb = nullptr;
-    int *d_fb_lo = nullptr, *d_fb_hi = nullptr;
-    float* d_scale = nullptr;   // peak-normalise scale scratch
-    bool mel_ready = false;
-    // grow-only pool of per-call device workspaces (batched transcription): hipMalloc/hipFree of a few hundred MB per call cost
-    // tens of ms and serialise the device; buffers are handed back after the call's final stream synchronisation
-    struct PoolEntry { void* p; size_t cap; bool used; };
-    std::vector<PoolEntry> pool;
-    hipStream_t occupy_stream = nullptr;      // vox_debug_occupy's busy kernel (a batched decode step runs all its chains on `stream`)
-    hipStream_t fe_stream = nullptr; hipEvent_t ev_fe[2] = {nullptr, nullptr}, ev_enc[2] = {nullptr, nullptr};      // continuous batch: the next chunk's upload + log-mel under this chunk's encoder
-    // continuous batch, self-calibration of the planner (the step costs were constants measured on one box): milliseconds per step of 1..4 active groups as
-    // MEASURED on this context (HIP events around the runs of equal active sets of earlier sessions, exponentially averaged; [0] = engine forms on, [1] = off), 0 = not seen yet
-    double step_ms_meas[2][9] = {{0, 0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0, 0, 0}}; hipEvent_t ev_seg[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    uint32_t warm_forms = 0;      // continuous batch: step chains whose kernels have run once on this context's device (bit 0 launch chains, bit 1 one-group engine, bit 2 two-group engine, bits 3..5 wide chains of 2 / 3 / 4 groups)
-    // XF tiles of a 17..48-row GEMM input (the 38-token prefill): 3 tiles x K columns x 64 B; sized once for K <= 16384, reused by every such GEMM of the stream
-    static constexpr size_t XF_SCRATCH_BYTES = (size_t)3 * 16384 * 64; uint16_t* xf_scratch = nullptr; size_t xf_scratch_bytes = 0;
-    bool shared = false;      // vox_ctx_set_shared: other sessions run on this GPU (no batched engines, planner on the scaled table)
-    static constexpr size_t KZ_SCRATCH_BYTES = (size_t)8 * 48 * 18432 * 4; float* kz_scratch = nullptr; size_t kz_scratch_bytes = 0;      // K-slice planes of the 17..48-row GEMMs (q4_skinny_mt2_kernel): 8 x 48 x 18432 floats
-    // The one owner of the two buffers above: allocates those asked for that are not there yet.  A failed allocation is not an error: the buffer stays null, size 0 (the caller takes a form without it)
-    void want_scratch(bool xf, bool kz) {
-        auto get = [](void** p, size_t* bytes, size_t want) { if (*p) return; *bytes = want; if (hipMalloc(p, want) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; *bytes = 0; } };
-        if (xf) get(reinterpret_cast<void**>(&xf_scratch), &xf_scratch_bytes, XF_SCRATCH_BYTES);
-        if (kz) get(reinterpret_cast<void**>(&kz_scratch), &kz_scratch_bytes, KZ_SCRATCH_BYTES);
-    }
-    float* rs_matrix = nullptr; uint32_t rs_in = 0, rs_out = 0;    // block matrix of the last resampled rate pair (vox_resample)
-    struct vox_model* pw_model = nullptr;      // the model with decode-engine steps of the piecewise surface enqueued on `stream` and not yet verified (see pw_after_sync)
-};
-
-static int32_t ctx_bind(const vox_ctx* c) { HIPCHK(hipSetDevice(c->device)); return VOX_OK; }
-
-extern "C" int32_t vox_ctx_create(int32_t device, vox_ctx** out) {
-    ARGCHK(out, "null out pointer");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { (void)hipGetLastError(); return fail(VOX_ERR_HIP, "no HIP device available (libvoxtral_hip has no CPU fallback)"); }
-    ARGCHK(device >= 0 && device < n, "device %d out of range (have %d)", device, n);
-    HIPCHK(hipSetDevice(device));
-    knobs_load_once();      // the VOX_* measurement knobs are snapshotted ONCE per process (std::call_once): no launch path calls getenv, and a second context created
-                            // while another thread transcribes does not touch the table (vox_debug_reload_knobs replaces it: tests only)
-    vox_ctx* c = new vox_ctx(); c->device = device;
-    hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { delete c; return fail(VOX_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e)); }
-    *out = c; return VOX_OK;
-}
-extern "C" int32_t vox_debug_reload_knobs(void) { knobs_reload(); return VOX_OK; }
-extern "C" int32_t vox_debug_attn_launches(uint64_t* out, int32_t cap) {
-    ARGCHK(out && cap > 0, "bad argument");
-    unsigned long long n[ATTN_FORM_COUNT]; attn_form_counts(n);
-    for (int i = 0; i < cap; i++) out[i] = i < ATTN_FORM_COUNT ? (uint64_t)n[i] : 0;
-    return VOX_OK;
-}
-extern "C" int32_t vox_debug_gemm_launches(uint64_t* out, int32_t cap) {
-    ARGCHK(out && cap > 0, "bad argument");
-    unsigned long long n[GEMM_FORM_COUNT]; gemm_form_counts(n);
-    for (int i = 0; i < cap; i++) out[i] = i < GEMM_FORM_COUNT ? (uint64_t)n[i] : 0;
-    return VOX_OK;
-}
-extern "C" int32_t vox_debug_occupy(vox_ctx* c, int32_t workgroups, int32_t micros) {
-    ARGCHK(c && workgroups > 0 && workgroups <= 4096 && micros > 0 && micros <= 2000000, "bad argument"); VOXCHK(ctx_bind(c));
-    if (!c->occupy_stream) HIPCHK(hipStreamCreateWithFlags(&c->occupy_stream, hipStreamNonBlocking));
-    HIPCHK(launch_occupy(workgroups, micros, c->occupy_stream));
-    return VOX_OK;
-}
-extern "C" int32_t vox_ctx_destroy(vox_ctx* c) {
-    if (!c) return VOX_OK;
-    (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
-    for (void* p : {(void*)c->d_window, (void*)c->d_cos, (void*)c->d_sin, (void*)c->d_fb, (void*)c->d_fb_lo, (void*)c->d_fb_hi, (void*)c->d_scale})
-        if (p) (void)hipFree(p);
-    for (auto& e : c->pool) (void)hipFree(e.p);
-    if (c->xf_scratch) (void)hipFree(c->xf_scratch);
-    if (c->kz_scratch) (void)hipFree(c->kz_scratch);
-    if (c->rs_matrix) (void)hipFree(c->rs_matrix);
-    if (c->occupy_stream) (void)hipStreamDestroy(c->occupy_stream);
-    for (auto e : c->ev_seg) if (e) (void)hipEventDestroy(e);
-    if (c->fe_stream) { (void)hipStreamSynchronize(c->fe_stream); (void)hipStreamDestroy(c->fe_stream); }
-    for (auto e : c->ev_fe) if (e) (void)hipEventDestroy(e);
-    for (auto e : c->ev_enc) if (e) (void)hipEventDestroy(e);
-    (void)hipStreamDestroy(c->stream);
-    delete c; return VOX_OK;
-}
-static int32_t pw_after_sync(struct vox_model* m);      // (piecewise decoder surface, below)
-extern "C" int32_t vox_ctx_synchronize(vox_ctx* c) {
-    ARGCHK(c, "null ctx"); VOXCHK(ctx_bind(c)); HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->pw_model) return pw_after_sync(c->pw_model);      // unverified decode-engine steps of the piecewise surface: their verdict is due at every synchronisation
-    return VOX_OK;
-}
-extern "C" int32_t vox_ctx_set_shared(vox_ctx* c, int32_t shared) { ARGCHK(c, "null context"); c->shared = shared != 0; return VOX_OK; }
-extern "C" int32_t vox_ctx_stream(vox_ctx* c, void** s) { ARGCHK(c && s, "null argument"); *s = (void*)c->stream; return VOX_OK; }
-extern "C" int32_t vox_dev_alloc(vox_ctx* c, size_t nbytes, void** out) { ARGCHK(c && out, "null argument"); VOXCHK(ctx_bind(c)); HIPCHK(hipMalloc(out, nbytes ? nbytes : 1)); return VOX_OK; }
-extern "C" int32_t vox_dev_free(vox_ctx* c, void* p) { ARGCHK(c, "null ctx"); VOXCHK(ctx_bind(c)); if (p) { HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipFree(p)); } return VOX_OK; }
-extern "C" int32_t vox_dev_upload(vox_ctx* c, void* dst, const void* src, size_t n) {
-    ARGCHK(c && dst && src, "null argument"); VOXCHK(ctx_bind(c));
-    HIPCHK(hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, c->stream)); HIPCHK(hipStreamSynchronize(c->stream)); return VOX_OK;
-}
-extern "C" int32_t vox_dev_download(vox_ctx* c, void* dst, const void* src, size_t n) {
-    ARGCHK(c && dst && src, "null argument"); VOXCHK(ctx_bind(c));
-    HIPCHK(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, c->stream)); HIPCHK(hipStreamSynchronize(c->stream)); return VOX_OK;
-}
-
-extern "C" int32_t vox_dev_copy(vox_ctx* c, void* dst, const void* src, size_t n) {
-    ARGCHK(c && dst && src, "null argument"); VOXCHK(ctx_bind(c));
-    HIPCHK(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToDevice, c->stream)); HIPCHK(hipStreamSynchronize(c->stream)); return VOX_OK;
-}
-
-// small RAII device buffer for host-pointer entry points
-struct DevBuf {
-    void* p = nullptr; vox_ctx* pool_ctx = nullptr;
-    ~DevBuf() {
-        if (!p) return;
-        if (pool_ctx) { for (auto& e : pool_ctx->pool) if (e.p == p) { e.used = false; return; } }
-        (void)hipFree(p);
-    }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 1); }
-    // from the context's workspace pool (best fit, at most 2x oversize); the caller must have synchronised the stream before the
-    // buffer goes out of scope
-    hipError_t alloc_pooled(vox_ctx* c, size_t n) {
-        n = n ? n : 1;
-        int best = -1;
-        for (size_t i = 0; i < c->pool.size(); i++) {
-            const auto& e = c->pool[i];
-            if (!e.used && e.cap >= n && e.cap <= 2 * n + (1u << 20) && (best < 0 || e.cap < c->pool[best].cap)) best = (int)i;
-        }
-        if (best >= 0) { c->pool[best].used = true; p = c->pool[best].p; pool_ctx = c; return hipSuccess; }
-        if (c->pool.size() >= 96) {          // bound the pool: drop idle entries
-            for (size_t i = 0; i < c->pool.size();) { if (!c->pool[i].used) { (void)hipFree(c->pool[i].p); c->pool.erase(c->pool.begin() + i); } else i++; }
-        }
-        hipError_t e = hipMalloc(&p, n);
-        if (e == hipSuccess) { c->pool.push_back({p, n, true}); pool_ctx = c; }
-        return e;
-    }
-    template <class T> T* as() { return reinterpret_cast<T*>(p); }
-};
-
-static int32_t ctx_mel_tables(vox_ctx* c, MelTables* t) {
-    if (!c->mel_ready) {
-        std::vector<float> win(400), ct(400), st(400), fb(128 * 201);
-        std::vector<int> lo(128), hi(128);
-        build_hann(400, win.data()); build_filterbank(fb.data());
-        for (int m = 0; m < 400; m++) { ct[m] = (float)std::cos(2.0 * M_PI * m / 400.0); st[m] = (float)std::sin(2.0 * M_PI * m / 400.0); }
-        for (int i = 0; i < 128; i++) {
-            int a = 201, b = 0;
-            for (int j = 0; j < 201; j++) if (fb[i * 201 + j] != 0.0f) { a = std::min(a, j); b = std::max(b, j + 1); }
-            if (a > b) { a = 0; b = 0; }
-            lo[i] = a; hi[i] = b;
-        }
-        HIPCHK(hipMalloc((void**)&c->d_window, 400 * 4)); HIPCHK(hipMalloc((void**)&c->d_cos, 400 * 4)); HIPCHK(hipMalloc((void**)&c->d_sin, 400 * 4));
-        HIPCHK(hipMalloc((void**)&c->d_fb, 128 * 201 * 4)); HIPCHK(hipMalloc((void**)&c->d_fb_lo, 128 * 4)); HIPCHK(hipMalloc((void**)&c->d_fb_hi, 128 * 4));
-        HIPCHK(hipMalloc((void**)&c->d_scale, 16));
-        HIPCHK(hipMemcpy(c->d_window, win.data(), 400 * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(c->d_cos, ct.data(), 400 * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(c->d_sin, st.data(), 400 * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(c->d_fb, fb.data(), 128 * 201 * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(c->d_fb_lo, lo.data(), 128 * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(c->d_fb_hi, hi.data(), 128 * 4, hipMemcpyHostToDevice));
-        c->mel_ready = true;
-    }
-    t->window = c->d_window; t->cos_t = c->d_cos; t->sin_t = c->d_sin; t->fb = c->d_fb; t->fb_lo = c->d_fb_lo; t->fb_hi = c->d_fb_hi;
-    return VOX_OK;
-}
-
-extern "C" int32_t vox_mel_compute_log(vox_ctx* c, const float* samples, size_t n, float* out, int32_t mem_kind) {
-    ARGCHK(c && out && (samples || n == 0), "null argument"); VOXCHK(ctx_bind(c));
-    const size_t T = n / 160;
-    if (T == 0) return VOX_OK;
-    MelTables t; VOXCHK(ctx_mel_tables(c, &t));
-    if (mem_kind == VOX_MEM_DEVICE) {
-        HIPCHK(launch_mel(samples, (long)n, 0, 0, nullptr, t, out, (int)T, 0, c->stream));
-        return VOX_OK;
-    }
-    DevBuf din, dout; HIPCHK(din.alloc(n * 4)); HIPCHK(dout.alloc(T * 128 * 4));
-    HIPCHK(hipMemcpyAsync(din.p, samples, n * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(launch_mel(din.as<float>(), (long)n, 0, 0, nullptr, t, dout.as<float>(), (int)T, 0, c->stream));
-    HIPCHK(hipMemcpyAsync(out, dout.p, T * 128 * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return VOX_OK;
-}
-// a plan's block matrix At[fft_in][2 fft_out] in a fresh device buffer the caller owns (the context's cache below, a vox_stream): the same taps, spectrum and kernel
-// whoever asks, so the same bits.  Synchronises the context's stream.
-static int32_t resample_matrix_build(vox_ctx* c, const ResamplePlan& p, size_t bytes, float** out) {
-    const std::vector<float> h = resample_taps(p);
-    const long Pi = 2 * p.fft_in; std::vector<double> ct((size_t)Pi), st((size_t)Pi), H((size_t)p.new_len * 2, 0.0);
-    for (long j = 0; j < Pi; j++) { ct[(size_t)j] = std::cos(2.0 * M_PI * (double)j / (double)Pi); st[(size_t)j] = std::sin(2.0 * M_PI * (double)j / (double)Pi); }
-    for (long k = 0; k < p.new_len; k++) {                                           // filter_f = FFT of the zero-padded taps (only the bins that are kept)
-        double re = 0.0, im = 0.0;
-        for (long n = 0; n < p.fft_in; n++) { const long j = (k * n) % Pi; re += (double)h[(size_t)n] * ct[(size_t)j]; im -= (double)h[(size_t)n] * st[(size_t)j]; }
-        H[(size_t)2 * k] = re; H[(size_t)2 * k + 1] = im;
-    }
-    float* A = nullptr;
-    DevBuf dH; HIPCHK(dH.alloc(H.size() * 8)); HIPCHK(hipMalloc((void**)&A, bytes));
-    hipError_t e = hipMemcpyAsync(dH.p, H.data(), H.size() * 8, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = launch_resample_matrix(dH.as<double>(), (int)p.new_len, (int)p.fft_in, (int)p.fft_out, A, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { (void)hipFree(A); return fail(VOX_ERR_HIP, "resample matrix: %s", hipGetErrorString(e)); }
-    *out = A;
-    return VOX_OK;
-}
-static int32_t resample_matrix_ensure(vox_ctx* c, uint32_t sr_in, uint32_t sr_out, const ResamplePlan& p) {
-    if (c->rs_matrix && c->rs_in == sr_in && c->rs_out == sr_out) return VOX_OK;
-    size_t bytes; VOXCHK(resample_matrix_bytes(sr_in, sr_out, p, &bytes));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->rs_matrix) { (void)hipFree(c->rs_matrix); c->rs_matrix = nullptr; }
-    VOXCHK(resample_matrix_build(c, p, bytes, &c->rs_matrix));
-    c->rs_in = sr_in; c->rs_out = sr_out;
-    return VOX_OK;
-}
-extern "C" int32_t vox_resample(vox_ctx* c, const float* in, size_t n_in, uint32_t sr_in, uint32_t sr_out, float* out, size_t cap, size_t* n_out, int32_t mem_kind) {
-    ARGCHK(c && out && n_out && (in || n_in == 0), "null argument"); ARGCHK(sr_in > 0 && sr_out > 0, "bad sample rate"); VOXCHK(ctx_bind(c));
-    size_t no; VOXCHK(vox_resample_len(n_in, sr_in, sr_out, &no));
-    ARGCHK(cap >= no, "output capacity %zu < %zu samples", cap, no);
-    *n_out = no; if (no == 0) return VOX_OK;
-    hipStream_t s = c->stream;
-    if (sr_in == sr_out) {                                                     // resample.rs:17-19: same rate -> clone
-        HIPCHK(hipMemcpyAsync(out, in, n_in * 4, mem_kind == VOX_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToHost, s)); HIPCHK(hipStreamSynchronize(s)); return VOX_OK;
-    }
-    const ResamplePlan p = resample_plan_make(sr_in, sr_out);
-    VOXCHK(resample_matrix_ensure(c, sr_in, sr_out, p));
-    DevBuf din, dout;
-    const float* d_in = in; float* d_out = out;
-    if (mem_kind != VOX_MEM_DEVICE) {
-        HIPCHK(din.alloc(n_in * 4)); HIPCHK(dout.alloc(no * 4));
-        HIPCHK(hipMemcpyAsync(din.p, in, n_in * 4, hipMemcpyHostToDevice, s)); d_in = din.as<float>(); d_out = dout.as<float>();
-    }
-    HIPCHK(launch_resample(d_in, (long)n_in, c->rs_matrix, (int)p.fft_in, (int)p.fft_out, (int)p.delay, d_out, (long)no, s));
-    if (mem_kind != VOX_MEM_DEVICE) HIPCHK(hipMemcpyAsync(out, d_out, no * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return VOX_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Q4 tensor + operator (gguf/tensor.rs, op.rs, linear.rs)
-// ------------------------------------------------------------------------------------------------
-struct vox_q4 { vox_ctx* ctx; Q4W w; void* qs_mem; void* sc_mem; void* qt_mem = nullptr; void* st_mem = nullptr; };
-
-// upload raw 18-byte blocks and re-pack into (qs, sc) planes at [dst_row0 ..) of the destination planes
-static int32_t upload_repack(vox_ctx* c, const uint8_t* raw, int64_t n_blocks, int nb, uint4* qs, uint16_t* sc, int row_mul, int row_add,
-                             void* staging, size_t staging_cap) {
-    const size_t bytes = (size_t)n_blocks * 18;
-    DevBuf tmp; uint8_t* d_raw = (uint8_t*)staging;
-    if (!staging || staging_cap < bytes) { HIPCHK(tmp.alloc(bytes)); d_raw = tmp.as<uint8_t>(); }
-    HIPCHK(hipMemcpyAsync(d_raw, raw, bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(launch_q4_repack(d_raw, qs, sc, n_blocks, nb, row_mul, row_add, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return VOX_OK;
-}
-
-extern "C" int32_t vox_q4_tensor_from_bytes(vox_ctx* c, const uint8_t* raw, size_t nbytes, int64_t N, int64_t K, vox_q4** out) {
-    ARGCHK(c && raw && out, "null argument"); ARGCHK(N > 0 && K > 0, "bad shape"); VOXCHK(ctx_bind(c));
-    const int64_t ne = N * K;
-    ARGCHK(ne % 32 == 0, "Q4_0 requires element count divisible by 32, got %lld", (long long)ne);           // tensor.rs:38-41
-    const int64_t nblk = ne / 32;
-    ARGCHK((int64_t)nbytes == nblk * 18, "Q4_0 byte count mismatch: expected %lld for %lld blocks, got %zu", (long long)(nblk * 18), (long long)nblk, nbytes);
-    ARGCHK(K % 32 == 0, "Q4_0 rows must be a whole number of 32-element blocks (K=%lld)", (long long)K);
-    vox_q4* q = new vox_q4(); q->ctx = c; q->qs_mem = q->sc_mem = nullptr;
-    if (hipMalloc(&q->qs_mem, (size_t)nblk * 16) != hipSuccess || hipMalloc(&q->sc_mem, (size_t)nblk * 2) != hipSuccess) {
-        if (q->qs_mem) (void)hipFree(q->qs_mem); delete q; return fail(VOX_ERR_HIP, "hipMalloc failed for Q4 tensor");
-    }
-    q->w = Q4W{(const uint4*)q->qs_mem, (const uint16_t*)q->sc_mem, (int)N, (int)K, (int)(K / 32)};
-    int32_t r = upload_repack(c, raw, nblk, (int)(K / 32), (uint4*)q->qs_mem, (uint16_t*)q->sc_mem, 1, 0, nullptr, 0);
-    if (r != VOX_OK) { (void)hipFree(q->qs_mem); (void)hipFree(q->sc_mem); delete q; return r; }
-    if ((K / 32) % 4 == 0) {     // MFMA tile-order copy (skinny / large-M kernels); same bits, different order
-        const size_t n_tiles = (size_t)(N + 15) / 16, nq = (size_t)(K / 128);
-        if (hipMalloc(&q->qt_mem, n_tiles * nq * 64 * 16) == hipSuccess && hipMalloc(&q->st_mem, n_tiles * nq * 64 * 2) == hipSuccess &&
-            launch_q4_tile_build(q->w, (uint4*)q->qt_mem, (uint16_t*)q->st_mem, c->stream) == hipSuccess && hipStreamSynchronize(c->stream) == hipSuccess) {
-            q->w.qt = (const uint4*)q->qt_mem; q->w.st = (const uint16_t*)q->st_mem;
-        } else { (void)hipFree(q->qt_mem); (void)hipFree(q->st_mem); (void)hipFree(q->qs_mem); (void)hipFree(q->sc_mem); delete q; return fail(VOX_ERR_HIP, "tile copy of Q4 tensor failed"); }
-    }
-    *out = q; return VOX_OK;
-}
-extern "C" int32_t vox_q4_tensor_shape(const vox_q4* q, int64_t* N, int64_t* K) { ARGCHK(q && N && K, "null argument"); *N = q->w.N; *K = q->w.K; return VOX_OK; }
-extern "C" int32_t vox_q4_tensor_num_blocks(const vox_q4* q, int64_t* out) { ARGCHK(q && out, "null argument"); *out = (int64_t)q->w.N * q->w.nb; return VOX_OK; }
-extern "C" int32_t vox_q4_tensor_free(vox_q4* q) {
-    if (!q) return VOX_OK;
-    (void)hipSetDevice(q->ctx->device); (void)hipStreamSynchronize(q->ctx->stream);
-    (void)hipFree(q->qs_mem); (void)hipFree(q->sc_mem); (void)hipFree(q->qt_mem); (void)hipFree(q->st_mem); delete q; return VOX_OK;
-}
-extern "C" int32_t vox_q4_tensor_dequantize(vox_ctx* c, const vox_q4* q, float* out) {
-    ARGCHK(c && q && out, "null argument"); VOXCHK(ctx_bind(c));
-    const size_t ne = (size_t)q->w.N * q->w.K;
-    DevBuf d; HIPCHK(d.alloc(ne * 4));
-    HIPCHK(launch_q4_dequant(q->w, d.as<float>(), c->stream));
-    HIPCHK(hipMemcpyAsync(out, d.p, ne * 4, hipMemcpyDeviceToHost, c->stream)); HIPCHK(hipStreamSynchronize(c->stream));
-    return VOX_OK;
-}
-
-// out[rows][N] = x[rows][K] * W^T (+bias), device pointers.  rows <= 4 -> fused GEMV, else MFMA GEMM (op.rs:144-150)
-static int32_t q4_linear_dev(vox_ctx* c, const Q4W& w, const float* bias, const float* x, int x_stride, int rows, float* out, int out_stride,
-                             int epi = EPI_STORE, const float* resid = nullptr, int resid_stride = 0, int ksplit = 0) {
-    if (rows <= 4) {
-        GemvParams p{}; p.w = w; p.x = x; p.x_stride = x_stride; p.out = out; p.out_stride = out_stride; p.bias = bias;
-        p.resid = resid; p.resid_stride = resid_stride;
-        HIPCHK(launch_q4_gemv(p, rows, PRO_NONE, epi, q4_gemv_default_R(w.N, w.K, epi), c->stream));
-    } else {
-        GemmParams p{}; p.w = w; p.x = x; p.x_stride = x_stride; p.M = rows; p.out = out; p.out_stride = out_stride; p.bias = bias;
-        p.resid = resid; p.resid_stride = resid_stride; p.ksplit = ksplit;
-        if (rows > 16 && rows <= 48 && w.fmt == WFMT_Q4_0 && w.K <= 16384) {      // the prefill GEMMs: rows -> XF tiles once (launch_q4_skinny_mt)
-            c->want_scratch(true, true);
-            p.xf_scratch = c->xf_scratch; p.xf_scratch_bytes = c->xf_scratch_bytes;
-            p.kz_scratch = c->kz_scratch; p.kz_scratch_bytes = c->kz_scratch_bytes;
-        }
-        HIPCHK(launch_q4_gemm(p, epi, c->stream));
-    }
-    return VOX_OK;
-}
-
-extern "C" int32_t vox_q4_linear_forward(vox_ctx* c, const vox_q4* w, const float* bias, const float* x, int32_t B, int32_t M, float* out, int32_t mem_kind) {
-    ARGCHK(c && w && x && out, "null argument"); ARGCHK(B > 0 && M > 0, "bad batch/rows"); VOXCHK(ctx_bind(c));
-    const int rows = B * M, K = w->w.K, N = w->w.N;
-    if (mem_kind == VOX_MEM_DEVICE) return q4_linear_dev(c, w->w, bias, x, K, rows, out, N);
-    DevBuf dx, dy, db; HIPCHK(dx.alloc((size_t)rows * K * 4)); HIPCHK(dy.alloc((size_t)rows * N * 4));
-    HIPCHK(hipMemcpyAsync(dx.p, x, (size_t)rows * K * 4, hipMemcpyHostToDevice, c->stream));
-    if (bias) { HIPCHK(db.alloc((size_t)N * 4)); HIPCHK(hipMemcpyAsync(db.p, bias, (size_t)N * 4, hipMemcpyHostToDevice, c->stream)); }
-    VOXCHK(q4_linear_dev(c, w->w, bias ? db.as<float>() : nullptr, dx.as<float>(), K, rows, dy.as<float>(), N));
-    HIPCHK(hipMemcpyAsync(out, dy.p, (size_t)rows * N * 4, hipMemcpyDeviceToHost, c->stream)); HIPCHK(hipStreamSynchronize(c->stream));
-    return VOX_OK;
-}
-extern "C" int32_t vox_q4_matmul(vox_ctx* c, const vox_q4* w, const float* x, int32_t B, int32_t M, float* out, int32_t mem_kind) {
-    return vox_q4_linear_forward(c, w, nullptr, x, B, M, out, mem_kind);
-}
-
-// ---- dense (f32-path) operators of models/layers on their own: what the f32 SafeTensors model runs, reachable per operator so that the reference's own
-// per-component vectors (scripts/reference_forward.py; models/layers/swiglu.rs:101, conv.rs, rms_norm.rs tests) go through the HIP kernels, not only through the oracle
-static uint16_t bf16_rne(float f) { uint32_t u; std::memcpy(&u, &f, 4); return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16); }
-static void bf16_split(const float* w, size_t n, uint16_t* hi, uint16_t* lo) {
-    for (size_t e = 0; e < n; e++) { const uint16_t hb = bf16_rne(w[e]); const uint32_t hu = (uint32_t)hb << 16; float hf; std::memcpy(&hf, &hu, 4); hi[e] = hb; lo[e] = bf16_rne(w[e] - hf); }
-}
-extern "C" int32_t vox_dense_tensor_from_f32(vox_ctx* c, const float* w, const float* w_other, int64_t N, int64_t K, vox_q4** out) {
-    ARGCHK(c && w && out, "null argument"); ARGCHK(N > 0 && K > 0 && K % 32 == 0, "dense tensor [%lld][%lld]: K must be a positive multiple of 32", (long long)N, (long long)K);
-    VOXCHK(ctx_bind(c));
-    const int64_t Ntot = w_other ? 2 * N : N; const size_t ne = (size_t)Ntot * K;
-    std::vector<float> host(ne);
-    for (int64_t r = 0; r < N; r++) {
-        std::memcpy(host.data() + (size_t)(w_other ? 2 * r : r) * K, w + (size_t)r * K, (size_t)K * 4);
-        if (w_other) std::memcpy(host.data() + (size_t)(2 * r + 1) * K, w_other + (size_t)r * K, (size_t)K * 4);      // interleaved gate / up rows (the fused w1|w3 operand)
-    }
-    std::vector<uint16_t> h2(ne), l2(ne); bf16_split(host.data(), ne, h2.data(), l2.data());
-    vox_q4* q = new vox_q4{c, Q4W{}, nullptr, nullptr};
-    auto bail = [&](hipError_t e) { (void)hipGetLastError(); (void)hipFree(q->qs_mem); (void)hipFree(q->sc_mem); (void)hipFree(q->qt_mem); delete q; return fail(VOX_ERR_HIP, "dense tensor upload: %s", hipGetErrorString(e)); };
-    hipError_t e = hipMalloc(&q->qs_mem, ne * 2); if (e == hipSuccess) e = hipMalloc(&q->sc_mem, ne * 2); if (e == hipSuccess) e = hipMalloc(&q->qt_mem, ne * 4);
-    if (e == hipSuccess) e = hipMemcpy(q->qs_mem, h2.data(), ne * 2, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(q->sc_mem, l2.data(), ne * 2, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(q->qt_mem, host.data(), ne * 4, hipMemcpyHostToDevice);
-    if (e != hipSuccess) return bail(e);
-    q->w = Q4W{(const uint4*)q->qs_mem, (const uint16_t*)q->sc_mem, (int)Ntot, (int)K, (int)(K / 32), WFMT_F32}; q->w.qt = (const uint4*)q->qt_mem;      // the f32 model's WFMT_F32 operand (Loader::linear)
-    *out = q; return VOX_OK;
-}
-extern "C" int32_t vox_linear_forward_ex(vox_ctx* c, const vox_q4* w, const float* bias, const float* x, int32_t B, int32_t M, float* out, int32_t epilogue, int32_t mem_kind) {
-    ARGCHK(c && w && x && out, "null argument"); ARGCHK(B > 0 && M > 0, "bad batch/rows"); VOXCHK(ctx_bind(c));
-    ARGCHK(epilogue == 0 || epilogue == 1 || epilogue == 2, "epilogue %d: 0 none, 1 GELU, 2 SwiGLU over interleaved gate / up rows", epilogue);
-    const int epi = epilogue == 1 ? EPI_GELU : epilogue == 2 ? EPI_SWIGLU : EPI_STORE;
-    const int rows = B * M, K = w->w.K, N = w->w.N, No = epilogue == 2 ? N / 2 : N;
-    ARGCHK(epilogue != 2 || (N % 2 == 0 && !bias), "SwiGLU epilogue needs an even number of interleaved rows and no bias");
-    if (mem_kind == VOX_MEM_DEVICE) return q4_linear_dev(c, w->w, bias, x, K, rows, out, No, epi);
-    DevBuf dx, dy, db; HIPCHK(dx.alloc((size_t)rows * K * 4)); HIPCHK(dy.alloc((size_t)rows * No * 4));
-    HIPCHK(hipMemcpyAsync(dx.p, x, (size_t)rows * K * 4, hipMemcpyHostToDevice, c->stream));
-    if (bias) { HIPCHK(db.alloc((size_t)N * 4)); HIPCHK(hipMemcpyAsync(db.p, bias, (size_t)N * 4, hipMemcpyHostToDevice, c->stream)); }
-    VOXCHK(q4_linear_dev(c, w->w, bias ? db.as<float>() : nullptr, dx.as<float>(), K, rows, dy.as<float>(), No, epi));
-    HIPCHK(hipMemcpyAsync(out, dy.p, (size_t)rows * No * 4, hipMemcpyDeviceToHost, c->stream)); HIPCHK(hipStreamSynchronize(c->stream));
-    return VOX_OK;
-}
-// ConvDownsampler::forward (models/layers/conv.rs:78-83): gelu(conv1d k3 s2 p1) twice, x [C][L] -> [O][L2], on the product's im2col MFMA path (conv_stem_dev)
-extern "C" int32_t vox_conv_downsample(vox_ctx* c, const float* x, int32_t C, int32_t L, const float* w1, const float* b1, const float* w2, const float* b2, int32_t O, float* out) {
-    ARGCHK(c && x && w1 && b1 && w2 && b2 && out && C > 0 && L > 0 && O > 0, "bad argument"); ARGCHK((3 * C) % 128 == 0 && (3 * O) % 128 == 0, "3 * channels must be a multiple of 128");
-    VOXCHK(ctx_bind(c)); hipStream_t s = c->stream;
-    const int T1 = (L + 2 - 3) / 2 + 1, S = (T1 + 2 - 3) / 2 + 1;      // models/layers/conv.rs:47-48
-    auto planes = [&](const float* w, int Co, int Ci, DevBuf& hi, DevBuf& lo, Q4W* q) -> int32_t {      // W'[co][kk * Ci + ci] = w[co][ci][kk] as bf16 hi + lo (Loader::conv_planes)
-        const size_t K = (size_t)3 * Ci; std::vector<float> r((size_t)Co * K);
-        for (int co = 0; co < Co; co++) for (int ci = 0; ci < Ci; ci++) for (int kk = 0; kk < 3; kk++) r[(size_t)co * K + (size_t)kk * Ci + ci] = w[((size_t)co * Ci + ci) * 3 + kk];
-        std::vector<uint16_t> h(r.size()), l(r.size()); bf16_split(r.data(), r.size(), h.data(), l.data());
-        HIPCHK(hi.alloc(h.size() * 2)); HIPCHK(lo.alloc(l.size() * 2));
-        HIPCHK(hipMemcpy(hi.p, h.data(), h.size() * 2, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(lo.p, l.data(), l.size() * 2, hipMemcpyHostToDevice));
-        *q = Q4W{(const uint4*)hi.p, (const uint16_t*)lo.p, Co, (int)K, (int)(K / 32), WFMT_BF16X2}; return VOX_OK;
-    };
-    DevBuf h1, l1, h2, l2, dx, dm, d1, dy, dyt, db1, db2; Q4W g1{}, g2{};
-    VOXCHK(planes(w1, O, C, h1, l1, &g1)); VOXCHK(planes(w2, O, O, h2, l2, &g2));
-    HIPCHK(dx.alloc((size_t)C * L * 4)); HIPCHK(dm.alloc((size_t)(L + 2) * C * 4)); HIPCHK(d1.alloc((size_t)(T1 + 2) * O * 4)); HIPCHK(dy.alloc((size_t)S * O * 4)); HIPCHK(dyt.alloc((size_t)S * O * 4));
-    HIPCHK(db1.alloc((size_t)O * 4)); HIPCHK(db2.alloc((size_t)O * 4));
-    HIPCHK(hipMemcpyAsync(dx.p, x, (size_t)C * L * 4, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(db1.p, b1, (size_t)O * 4, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(db2.p, b2, (size_t)O * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(dm.p, 0, (size_t)(L + 2) * C * 4, s)); HIPCHK(hipMemsetAsync(d1.p, 0, (size_t)(T1 + 2) * O * 4, s));
-    HIPCHK(launch_transpose(dx.as<float>(), C, L, dm.as<float>() + C, s));      // [C][L] -> token-major, one zero row either side
-    { GemmParams g{}; g.w = g1; g.x = dm.as<float>(); g.x_stride = 2 * C; g.M = T1; g.out = d1.as<float>() + O; g.out_stride = O; g.bias = db1.as<float>(); HIPCHK(launch_dense2_gemm(g, EPI_GELU, s)); }
-    { GemmParams g{}; g.w = g2; g.x = d1.as<float>(); g.x_stride = 2 * O; g.M = S; g.out = dy.as<float>(); g.out_stride = O; g.bias = db2.as<float>(); HIPCHK(launch_dense2_gemm(g, EPI_GELU, s)); }
-    HIPCHK(launch_transpose(dy.as<float>(), S, O, dyt.as<float>(), s));      // token-major [S][O] -> the layer's [O][S]
-    HIPCHK(hipMemcpyAsync(out, dyt.p, (size_t)S * O * 4, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
-    return VOX_OK;
-}
-
-// causal (+ sliding-window) multi-head / grouped-query attention core on host or device buffers
-// (gguf/model.rs:100-120,125-198; masking.rs:9-107).  q [M][n_heads*hd], k/v [kv_len][n_kv*hd] (token-major), query m at
-// position offset+m sees keys j <= offset+m with offset+m-j <= window (window < 0: no window).  out [M][n_heads*hd].
-extern "C" int32_t vox_attention(vox_ctx* c, const float* q, const float* k, const float* v, int32_t M, int32_t kv_len, int32_t n_heads,
-                                 int32_t n_kv_heads, int32_t head_dim, int32_t offset, int32_t window, float* out, int32_t mem_kind) {
-    ARGCHK(c && q && k && v && out, "null argument");
-    ARGCHK(M > 0 && kv_len > 0 && n_heads > 0 && n_kv_heads > 0 && n_heads % n_kv_heads == 0, "bad attention shape");
-    ARGCHK(head_dim == 64 || head_dim == 128, "head_dim must be 64 (encoder) or 128 (decoder)");
-    ARGCHK(offset >= 0 && offset + M <= kv_len, "queries must lie inside the key range (offset + M <= kv_len)");
-    VOXCHK(ctx_bind(c));
-    const size_t qn = (size_t)M * n_heads * head_dim, kn = (size_t)kv_len * n_kv_heads * head_dim;
-    DevBuf dq, dk, dv, dout;
-    const float *pq = q, *pk = k, *pv = v; float* po = out;
-    if (mem_kind != VOX_MEM_DEVICE) {
-        HIPCHK(dq.alloc(qn * 4)); HIPCHK(dk.alloc(kn * 4)); HIPCHK(dv.alloc(kn * 4)); HIPCHK(dout.alloc(qn * 4));
-        HIPCHK(hipMemcpyAsync(dq.p, q, qn * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(dk.p, k, kn * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(dv.p, v, kn * 4, hipMemcpyHostToDevice, c->stream));
-        pq = dq.as<float>(); pk = dk.as<float>(); pv = dv.as<float>(); po = dout.as<float>();
-    }
-    AttnParams ap{}; ap.q = pq; ap.q_stride = n_heads * head_dim; ap.k = pk; ap.v = pv; ap.kv_row_stride = n_kv_heads * head_dim; ap.kv_head_stride = head_dim;
-    ap.out = po; ap.out_stride = n_heads * head_dim; ap.M = M; ap.kv_len = kv_len; ap.n_heads = n_heads; ap.n_kv_heads = n_kv_heads; ap.offset = offset; ap.window = window;
-    HIPCHK(launch_attn_prefill(ap, head_dim, c->stream));
-    if (mem_kind != VOX_MEM_DEVICE) { HIPCHK(hipMemcpyAsync(out, po, qn * 4, hipMemcpyDeviceToHost, c->stream)); HIPCHK(hipStreamSynchronize(c->stream)); }
-    return VOX_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
 // model
 // ------------------------------------------------------------------------------------------------
-struct Lin { Q4W w{}; const float* bias = nullptr; };
-struct EncLayer { const float *attn_norm = nullptr, *ffn_norm = nullptr; Lin wqkv, wo, w13, w2; };
-struct DecLayer { const float *attn_norm = nullptr, *ffn_norm = nullptr; Lin wqkv, wo, w13, w2, ada0, ada2; float* ada_mul = nullptr; };
-
-struct vox_cache { vox_model* m; vox_ctx* ctx = nullptr; float *k = nullptr, *v = nullptr; int max_seq = 0, len = 0; size_t layer_stride = 0;
-                   int kind = 0, abs_pos = 0; uint64_t gen = 0; };   // kind 0: decoder cache, 1: encoder (streaming) cache; abs_pos: positions seen so far (RoPE offset of the next chunk)   // layer_stride in floats   // per layer: [n_kv][max_seq][hd]
 
 // Every caller-visible cache carries a generation number from one process-wide counter and is listed while it lives: code that remembers a cache across calls (the
 // piecewise engine's layer table, the record of unverified engine steps) keys on (address, generation) -- a freed cache's address may be handed out again by the
 // allocator, with another max_seq behind the same K base -- and asks cache_alive() before it dereferences one it did not receive in the current call.
 static std::mutex g_cache_mu; static std::unordered_map<const vox_cache*, uint64_t> g_cache_live; static uint64_t g_cache_gen = 0;
-static void cache_register(vox_cache* k) { std::lock_guard<std::mutex> l(g_cache_mu); k->gen = ++g_cache_gen; g_cache_live[k] = k->gen; }
+namespace vox_host {
+void cache_register(vox_cache* k) { std::lock_guard<std::mutex> l(g_cache_mu); k->gen = ++g_cache_gen; g_cache_live[k] = k->gen; }
+}  // namespace vox_host
 static void cache_unregister(const vox_cache* k) { std::lock_guard<std::mutex> l(g_cache_mu); g_cache_live.erase(k); }
 static bool cache_alive(const vox_cache* k, uint64_t gen) { std::lock_guard<std::mutex> l(g_cache_mu); auto it = g_cache_live.find(k); return it != g_cache_live.end() && it->second == gen; }
 // frees a cache nothing on the GPU reads any more: synchronising first, and dropping whatever remembers it, is the caller's
-static void cache_release(vox_cache*& k) { if (!k) return; cache_unregister(k); (void)hipFree(k->k); (void)hipFree(k->v); delete k; k = nullptr; }
-
-// What one client of the single-stream decode engine (the offline path, the piecewise decoder surface, a live stream) holds of it: the device layer table for ITS cache,
-// where the launch leaves its 256 argmax partials, and the pinned host word the engine's error word is copied to.  `host` is what `tab` holds, valid for exactly
-// (cache, gen): engine_bind rebuilds it for another cache or generation and leaves it alone otherwise, so clients that alternate on one model never disturb each other.
-struct EngBinding {
-    EngLayerTab* tab = nullptr; float* part_val = nullptr; int* part_idx = nullptr; unsigned* err_word = nullptr; const vox_cache* cache = nullptr; uint64_t gen = 0; std::vector<EngLayerTab> host;
-};
+namespace vox_host {
+void cache_release(vox_cache*& k) { if (!k) return; cache_unregister(k); (void)hipFree(k->k); (void)hipFree(k->v); delete k; k = nullptr; }
+}  // namespace vox_host
 static void binding_release(EngBinding& b) {
     for (void* p : {(void*)b.tab, (void*)b.part_val, (void*)b.part_idx}) if (p) (void)hipFree(p);
     if (b.err_word) (void)hipHostFree(b.err_word);
     b = EngBinding{};
 }
-
-struct TensorMeta { std::vector<uint64_t> shape; int dtype = 0; uint64_t nbytes = 0; };
-// What vox_transcribe_audio computes identically for EVERY utterance, held once per model.  The library itself pads every utterance on the left
-// with silence (vox_pad_cfg_voxtral), the log-mel of silence is the constant floor, the conv stem is local, the encoder attention causal, and the decoder's prefix tokens
-// are fixed: encoder rows [0, RC) and decoder positions [0, PC) are functions of the weights (and of t_embed) alone.  Built from a silent mel, never from a caller's clip.
-struct PrefixState {
-    bool on = true;                        // vox_model_set_prefix_cache
-    int RC = 0, PC = 0;                    // encoder rows / decoder positions held; 0: this geometry has no prefix (prefix_bounds)
-    float* enc_kv = nullptr;               // [enc_layers][RC][k row | v row]: the RoPE'd keys and the values of rows 0 .. RC-1 of every encoder layer
-    float* audio = nullptr;                // [PC][dec_dim]: adapter rows 0 .. PC-1
-    float *dec_k = nullptr, *dec_v = nullptr;      // [dec_layers * dec_kv_heads][PC][head_dim]: decoder cache rows 0 .. PC-1 for the t_embed below
-    bool enc_built = false, dec_built = false;
-    std::vector<float> t_embed;            // the t_embed the decoder part was built with
-    float* capture = nullptr; int capture_rows = 0;      // while the encoder part is being built: encode_batch_dev stores every layer's k | v rows here
-    uint64_t enc_bytes = 0, dec_bytes = 0;
-};
 // the prefix itself, built here and nowhere else; static storage, so an upload from it has nothing to keep alive
 static const struct PrefixTokens {
     int32_t t[VOX_PREFIX_TOKENS];
     PrefixTokens() { std::fill(t, t + VOX_PREFIX_TOKENS, VOX_TOK_STREAMING_PAD); t[0] = VOX_TOK_BOS; }
 } PREFIX_TOKENS;
-// What decode_step_enqueue launches.  StepAndArgmax: the step and the launch that turns its argmax partials into the next token + input (every path).  Engine only --
-// EngineAlone: the engine launch, its partials left for whoever comes next; EngineArgmaxFirst: an engine launch that BEGINS with the argmax of the previous launch's partials
-// (flags 65536): [EngineAlone] [EngineArgmaxFirst] ... [EngineArgmaxFirst] [argmax_final] is the token sequence of StepAndArgmax steps with one launch per token, not two.
-enum class StepLaunch { StepAndArgmax, EngineAlone, EngineArgmaxFirst };
-// the single-clip decode graphs: [0] = one step, [1] = key.unroll steps (fewer graph boundaries).  Both bake the key's cache / audio (and the model's token) pointers
-// and its launch form in: graphs_for re-keys them, graphs_destroy drops them (the key stays: the next graphs_for with it captures afresh)
-struct DecodeGraphs {
-    struct Key { const vox_cache* cache; const float* audio; int unroll; StepLaunch launch; } key{nullptr, nullptr, 0, StepLaunch::StepAndArgmax};
-    hipGraph_t graph[2] = {nullptr, nullptr}; hipGraphExec_t exec[2] = {nullptr, nullptr};
-};
-struct vox_model {
-    PrefixState pfx;
-    vox_ctx* ctx = nullptr; vox_model_cfg cfg{};
-    std::vector<vox_model*> twins;      // vox_model_set_sessions: replicas on hidden contexts of the same device (owned: freed with the model)
-    std::map<std::string, TensorMeta> manifest; bool is_q4 = false;      // name -> shape / dtype of every tensor the loader looked up (vox_model_replicate lays a second arena out from it, without the file)
-    uint8_t* arena = nullptr; uint64_t arena_bytes = 0, arena_primary_bytes = 0;      // [0, primary): everything parsed from the file; [primary, bytes): copies derived from it on the GPU
-    std::vector<Q4W*> tiled;                                 // Q4 linears that own a tile-ordered copy in the derived part
-    const float *conv1_w = nullptr, *conv1_b = nullptr, *conv2_w = nullptr, *conv2_b = nullptr, *enc_norm = nullptr, *dec_norm = nullptr;
-    Q4W conv1_g{}, conv2_g{};                               // conv weights as im2col GEMM operands (two bf16 planes), optional
-    const float *enc_cos = nullptr, *enc_sin = nullptr, *dec_cos = nullptr, *dec_sin = nullptr;
-    int enc_rope_len = 4096, dec_rope_len = 16384;                         // gguf/loader.rs:196-198,284-286
-    std::vector<EncLayer> enc; std::vector<DecLayer> dec; Lin ad0, ad2, tok;
-    // derived (not in the arena)
-    float* ada_mul = nullptr; bool t_embed_set = false; std::vector<float> t_embed_host;
-    // workspaces
-    float* ws = nullptr; size_t ws_floats = 0;            // encoder / prefill workspace
-    float *d_audio = nullptr; int audio_cap = 0;          // [S][dec_dim]
-    float *d_mel = nullptr; size_t mel_cap = 0;           // [128][T]
-    float *d_samples = nullptr; size_t samples_cap = 0;
-    // decode state
-    vox_cache* cache = nullptr;                           // internal cache for transcribe_streaming
-    int *d_tokens = nullptr, *d_pos = nullptr; int tokens_cap = 0;
-    float* d_prefix = nullptr;                            // [38][dec_dim] prefill inputs (prefill_prefix_rows)
-    float *enc_cos_s = nullptr, *enc_sin_s = nullptr; int enc_rope_s_len = 0;   // RoPE tables for the streaming encoder (positions beyond the 4096-row load-time table)
-    int* d_seq_len = nullptr; std::vector<int> h_seq_len;  // per-utterance encoder rows of a stacked batch
-    int *d_seq_off = nullptr, *d_row_pos = nullptr; size_t row_pos_cap = 0; std::vector<int> h_seq_off, h_row_pos;      // packed stack: start row per utterance, position per row
-    float *d_h = nullptr, *d_q = nullptr, *d_att = nullptr, *d_act = nullptr, *d_logits = nullptr, *d_part_val = nullptr; int* d_part_idx = nullptr;
-    float* d_h2 = nullptr; long long* d_wo_acc = nullptr;      // fused attention + wo decode launch: residual stream after wo; per-layer fixed-point accumulators [dec_layers][dec_dim]
-    int n_parts = 0, argmax_R = 8;
-    // persistent decode-step engine (vox_engine.hip): one launch per token for the real decoder geometry; eng_ok = eligible, eng_ready = stream packed + state allocated
-    bool eng_ok = false, eng_on = true, eng_ready = false; unsigned char* eng_stream = nullptr; unsigned char* eng_state = nullptr; unsigned long long eng_launches = 0;
-    EngBinding eng_offline, eng_pw;      // the engine against the model's own cache (partials: d_part_val / d_part_idx, not owned) and against a piecewise caller's cache
-    int eng_flags = 128 | 512 | 1, eng_pace = 50;      // XCD-local edges; probe-less all-gather, swept 0.5 us after the CU's own rows went out; one LDS-DMA packet in flight while the CU polls memory
-    int eng_strikes = 0; bool eng_suspended = false;      // hand-off timeouts so far (3: the engine is switched off for good); suspended: the current utterance is being re-run on the per-operator path
-    // batched decode-layer engine (vox_engine_b16.hip): one launch per 16-row group and step on the same packet stream; per-group edge buffers + layer tables
-    unsigned char* eng_wob = nullptr;      // the batched engine's wo stream (XCD-group K split, launch_eng_pack op 5): 7 MB per layer
-    bool engb_ok = false; unsigned char* engb_state[4] = {nullptr, nullptr, nullptr, nullptr}; EngLayerTab* engb_tab[4] = {nullptr, nullptr, nullptr, nullptr};
-    bool engb_on = true; unsigned long long engb_launches = 0; int engb_strikes = 0;
-    int batch_sessions = 0;      // parts the last vox_transcribe_batch call ran in
-    int engb_flags = 128 | 1 | 64 | 2048;
-    int engb_flags2 = 128 | 1024;      // two-group launch: loader depth 2, never paused or thinned -- with two chains interleaved the stream is what a phase waits for (profiles/r05_b32_engine.txt: 61.4 us per layer against 65.4 with the one-group flags)
-    unsigned engb_err_host[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
-    DecodeGraphs graphs;
-    // piecewise decoder surface (embed_tokens_from_ids / forward_hidden_with_cache / lm_head on caller-owned caches): model-owned workspaces, and the decode engine's
-    // layer table for the caller's cache (eng_pw).  pw_memo: row 0 of pw_hidden is the final norm's output of an engine launch that ALSO produced that row's logits (pw_logits)
-    // and argmax partials (eng_pw.part_*): lm_head on that very buffer has nothing left to compute.  eng_pw.err_word is refreshed (async) behind every engine launch: no round trip.
-    float *pw_x = nullptr, *pw_hidden = nullptr, *pw_logits = nullptr; size_t pw_x_cap = 0, pw_hidden_cap = 0, pw_logits_cap = 0;
-    int* pw_ids = nullptr; int pw_ids_cap = 0; int* pw_zero = nullptr;
-    bool pw_memo = false, pw_eng_used = false;
-    // rows appended to a caller's cache by engine steps (and by anything run behind them) whose error word has not been read behind a stream synchronisation yet: a
-    // hand-off timeout found later takes exactly these rows back (cache length -= pw_pend_rows), so "repeat the step" appends at the failed position again
-    vox_cache* pw_pend_cache = nullptr; uint64_t pw_pend_gen = 0; int pw_pend_rows = 0; bool pw_verdict_failed = false;
-    vox_timings timings{};
-    // vox_debug_batch_tap_*: units (caller indices) armed for the next batch call; `on` during that call; out / rows hold the call's rows until fetched
-    struct { std::vector<int> units; int max_rows = 0; bool armed = false, on = false, ready = false; float* out = nullptr; int* rows = nullptr; } tap;
-};
 
 // arena layout planner: pass 1 (base == nullptr) only sizes, pass 2 hands out pointers
 struct Arena {
@@ -828,7 +265,7 @@ struct Loader {
                 for (size_t i = 0; i < ts.size(); i++) {
                     const int64_t nn = (int64_t)ts[i].shape[0];
                     const int mul = interleave ? (int)ts.size() : 1, add = interleave ? (int)i : (int)row0;
-                    if (upload_repack(m->ctx, ts[i].data, nn * nb, nb, qs, sc, mul, add, staging, staging_cap) != VOX_OK) return setfail(g_err);
+                    if (upload_repack(m->ctx, ts[i].data, nn * nb, nb, qs, sc, mul, add, staging, staging_cap) != VOX_OK) return setfail(vox_last_error());
                     row0 += nn;
                 }
             }
@@ -1342,65 +779,6 @@ static int32_t encode_dev(vox_model* m, const float* d_mel, int T, int* S4_out, 
     const int S4 = enc_rows(T) / m->cfg.reshape_factor;
     if (S4 > 0) { size_t cap = (size_t)m->audio_cap * m->cfg.dec_dim; VOXCHK(ensure(&m->d_audio, &cap, (size_t)S4 * m->cfg.dec_dim)); m->audio_cap = (int)(cap / m->cfg.dec_dim); }
     return encode_batch_dev(m, 1, &d_mel, &T, m->d_audio, S4, S4_out, nullptr, nullptr, prefix_rows);
-}
-
-// ---- KV cache (models/layers/kv_cache.rs:52-65,221-234)
-static int32_t cache_alloc(vox_model* m, int max_seq, vox_cache** out) {
-    const vox_model_cfg& c = m->cfg;
-    ARGCHK(max_seq > 0 && max_seq <= m->dec_rope_len, "max_seq %d out of range (1..%d)", max_seq, m->dec_rope_len);
-    vox_cache* k = new vox_cache(); k->m = m; k->ctx = m->ctx; k->max_seq = max_seq;
-    const size_t n = (size_t)c.dec_layers * c.dec_kv_heads * max_seq * c.dec_head_dim * 4;
-    if (hipMalloc((void**)&k->k, n) != hipSuccess || hipMalloc((void**)&k->v, n) != hipSuccess) { if (k->k) (void)hipFree(k->k); delete k; return fail(VOX_ERR_HIP, "hipMalloc of KV cache failed"); }
-    HIPCHK(hipMemsetAsync(k->k, 0, n, m->ctx->stream)); HIPCHK(hipMemsetAsync(k->v, 0, n, m->ctx->stream));
-    k->layer_stride = (size_t)c.dec_kv_heads * max_seq * c.dec_head_dim;
-    cache_register(k);
-    *out = k; return VOX_OK;
-}
-extern "C" int32_t vox_decoder_cache_create(vox_model* m, int32_t max_seq, vox_cache** out) { ARGCHK(m && out, "null argument"); VOXCHK(ctx_bind(m->ctx)); return cache_alloc(m, max_seq, out); }
-extern "C" int32_t vox_cache_free(vox_cache* k) {
-    if (!k) return VOX_OK;
-    (void)hipSetDevice(k->ctx->device); (void)hipStreamSynchronize(k->ctx->stream);   // never dereferences k->m: the model may be gone
-    cache_release(k); return VOX_OK;
-}
-// KVCache::update on one layer of a pre-allocated cache (kv_cache.rs:116-136: slice_assign of k / v [1][heads][new_seq][hd] at rows pos .. pos + new_seq) -- for callers
-// that own their K / V (and for tests that need a cache at a position no prefill has reached).  The length shared by all layers (LayerCaches::seq_len,
-// kv_cache.rs:242-244) becomes max(len, pos + n_rows).
-// The piecewise decoder surface remembers the rows of a cache it has not verified yet (engine steps since the last synchronisation; see pw_note_pending below).  An entry
-// point that moves the cache's length by hand settles them first: a hand-off timeout found LATER would otherwise subtract a stale row count from the new length.
-// A failure found here is reported by this call (VOX_ERR_HIP; the cache is back at the length before the failed step, nothing else was changed).
-static int32_t pw_sync(vox_model* m);
-static int32_t cache_settle_pending(vox_cache* kc) {
-    vox_model* m = kc->m;
-    if (m && m->pw_pend_rows > 0 && m->pw_pend_cache == kc) { VOXCHK(ctx_bind(kc->ctx)); VOXCHK(pw_sync(m)); }
-    return VOX_OK;
-}
-extern "C" int32_t vox_cache_update(vox_cache* kc, int32_t layer, int32_t pos, const float* k, const float* v, int32_t n_rows, int32_t mem_kind) {
-    ARGCHK(kc && k && v && n_rows > 0 && pos >= 0, "bad argument"); VOXCHK(ctx_bind(kc->ctx)); VOXCHK(cache_settle_pending(kc));
-    const vox_model_cfg& c = kc->m->cfg;
-    const int L = kc->kind == 1 ? c.enc_layers : c.dec_layers, H = kc->kind == 1 ? c.enc_heads : c.dec_kv_heads, hd = kc->kind == 1 ? c.enc_head_dim : c.dec_head_dim;
-    ARGCHK(layer >= 0 && layer < L, "layer %d out of range (0..%d)", layer, L - 1);
-    ARGCHK(pos + n_rows <= kc->max_seq, "KV cache overflow: %d + %d > %d", pos, n_rows, kc->max_seq);
-    hipStream_t s = kc->ctx->stream; const hipMemcpyKind kind = mem_kind == VOX_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    for (int h = 0; h < H; h++) {
-        const size_t dst = (size_t)layer * kc->layer_stride + ((size_t)h * kc->max_seq + pos) * hd, src = (size_t)h * n_rows * hd, nb = (size_t)n_rows * hd * 4;
-        HIPCHK(hipMemcpyAsync(kc->k + dst, k + src, nb, kind, s)); HIPCHK(hipMemcpyAsync(kc->v + dst, v + src, nb, kind, s));
-    }
-    if (mem_kind != VOX_MEM_DEVICE) HIPCHK(hipStreamSynchronize(s));      // the host buffers may be reused when the call returns
-    kc->len = std::max(kc->len, pos + n_rows);
-    return VOX_OK;
-}
-// forget every row from `len` on (0 <= len <= seq_len): the next forward appends at `len` again.  What a caller of the device-resident entries does after ITS OWN failed step;
-// the library's own engine timeouts roll the length back themselves (see vox_forward_hidden_with_cache_ex).
-extern "C" int32_t vox_cache_truncate(vox_cache* kc, int32_t len) {
-    ARGCHK(kc, "null cache"); VOXCHK(cache_settle_pending(kc)); ARGCHK(len >= 0 && len <= kc->len, "truncate to %d: the cache holds %d rows", len, kc->len);
-    if (kc->kind == 1) kc->abs_pos -= kc->len - len;
-    kc->len = len; return VOX_OK;
-}
-extern "C" int32_t vox_cache_seq_len(const vox_cache* k, int32_t* out) { ARGCHK(k && out, "null argument"); *out = k->len; return VOX_OK; }
-extern "C" int32_t vox_cache_reset(vox_cache* k) {
-    ARGCHK(k, "null cache");
-    (void)cache_settle_pending(k);      // (a failed verdict only shortens a cache that is being emptied anyway: the strike is counted, the reset goes through)
-    k->len = 0; k->abs_pos = 0; return VOX_OK;
 }
 
 // ---- streaming encoder: Q4AudioEncoder::create_cache / forward_with_cache (gguf/model.rs:437-459), Q4EncoderLayer::forward_with_cache
@@ -3221,7 +2599,7 @@ extern "C" int32_t vox_model_set_sessions(vox_model* m, int32_t sessions) {
     while ((int)m->twins.size() < sessions - 1) {
         vox_ctx* tc = nullptr; VOXCHK(vox_ctx_create(m->ctx->device, &tc)); tc->shared = true; ctx_own_queue(tc);
         vox_model* t = nullptr; const int32_t r = vox_model_replicate(m, tc, &t);
-        if (r != VOX_OK) { std::string e = g_err; (void)vox_ctx_destroy(tc); return fail(r, "%s", e.c_str()); }
+        if (r != VOX_OK) { std::string e = vox_last_error(); (void)vox_ctx_destroy(tc); return fail(r, "%s", e.c_str()); }
         m->twins.push_back(t);
     }
     return ctx_bind(m->ctx);
@@ -3250,7 +2628,7 @@ static int32_t transcribe_batch_sessions(vox_model* m, int S, int32_t n, const f
         const RecordsOut sub_rec{u.rs.empty() ? nullptr : u.rs.data(), u.ra.empty() ? nullptr : u.ra.data(), rec ? rec->k : 0};      // every session writes its own units' records
         u.rc = transcribe_batch_one_session(mk, (int32_t)u.s.size(), u.s.data(), u.ns.data(), norm_group ? u.grp.data() : nullptr, t_embed, u.out.data(), u.caps.data(), u.nid.data(), mem_kind,
                                             rec ? &sub_rec : nullptr);
-        if (u.rc != VOX_OK) u.err = g_err;      // (thread-local: read on the thread that failed)
+        if (u.rc != VOX_OK) u.err = vox_last_error();      // (thread-local: read on the thread that failed)
         u.tm = mk->timings;
     };
     const bool was_shared = m->ctx->shared; m->ctx->shared = true;      // (the twins' contexts always are)
@@ -3450,16 +2828,18 @@ static int32_t pw_engine_verdict(vox_model* m) {
                 len_now, m->eng_strikes >= 3 ? " (the engine is now switched off, the per-operator launches serve it)" : "");
 }
 // behind a synchronisation of the stream: the pinned error word of every engine launch enqueued so far has landed -- read the verdict; clean: every pending row is verified
-static int32_t pw_after_sync(vox_model* m) {
+namespace vox_host {
+int32_t pw_after_sync(vox_model* m) {
     m->pw_eng_used = false;
     const int32_t r = pw_engine_verdict(m);
     if (r == VOX_OK) { m->pw_pend_rows = 0; m->pw_pend_cache = nullptr; if (m->ctx->pw_model == m) m->ctx->pw_model = nullptr; }
     return r;
 }
-static int32_t pw_sync(vox_model* m) {      // synchronise the stream (the pinned error word of an outstanding engine launch lands with the same wait), then the verdict
+int32_t pw_sync(vox_model* m) {      // synchronise the stream (the pinned error word of an outstanding engine launch lands with the same wait), then the verdict
     HIPCHK(hipStreamSynchronize(m->ctx->stream));
     return pw_after_sync(m);
 }
+}  // namespace vox_host
 // rows appended to `kc` by a step that cannot be verified yet (an engine launch, or anything behind one): remembered until the next synchronisation
 static int32_t pw_note_pending(vox_model* m, vox_cache* kc, int rows) {
     if (m->pw_pend_rows > 0 && (m->pw_pend_cache != kc || m->pw_pend_gen != kc->gen)) VOXCHK(pw_sync(m));      // another cache's steps are outstanding: settle them first

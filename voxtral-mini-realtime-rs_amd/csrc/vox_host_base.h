@@ -14,7 +14,7 @@
 #include <vector>
 
 namespace vox_host {
-// ---- vox_api.cpp
+// ---- vox_ctx.cpp
 int32_t fail(int32_t code, const char* fmt, ...);
 }  // namespace vox_host
 
