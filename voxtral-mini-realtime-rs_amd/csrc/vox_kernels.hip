@@ -947,7 +947,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void q
 // TB: Q4 weights come from the tile-ordered copy (one coalesced dwordx4 per lane per n-tile per K step = the lane's dword of the four blocks)
 // instead of four strided dword loads from the row planes -- used for the 33..48-row prefill tile (MT = 3), where the weight stream is the bound.
 template <int MT, int NT, int EPI, int FMT, int TB = 0>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void q4_gemm_kernel(const GemmParams p) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MT == 2 && NT == 2 && FMT == WFMT_Q4_0 && TB == 1 ? 3 : 2))) void q4_gemm_kernel(const GemmParams p) {
     extern __shared__ __attribute__((aligned(16))) uint4 glds[];      // [buf 2][hi/lo 2][j 4][MT][64]
     constexpr int PLANE = 4 * MT * 64, BUF = 2 * PLANE;
     const int nb = p.w.nb, N = p.w.N, M = p.M, nq = nb >> 2;
@@ -1011,58 +1011,89 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void q
         uint4 hi_, lo_; split_bf16x8(sxa[i], sxb[i], hi_, lo_);                                                \
         glds[(BUF_) * BUF + slot[i]] = hi_; glds[(BUF_) * BUF + PLANE + slot[i]] = lo_;                        \
     }
-    VOX_GLOAD(qb)
+#define VOX_MMA                                                                                                \
+        _Pragma("unroll") for (int j = 0; j < 4; j++) {                                                                \
+            _Pragma("unroll") for (int t = 0; t < NT; t++) {                                                           \
+                const bf16x8 bw = as_bf16x8(FMT == WFMT_Q4_0 ? q4_dword_to_bf16x8(cwd[t][j]) : cwdv[t][j]);            \
+                float d = 1.0f;                                                                                        \
+                if (FMT == WFMT_Q4_0) {                                                                                \
+                    const uint32_t pr = (j & 2) ? csc[t].y : csc[t].x;                                                 \
+                    d = f16_bits_to_f32((uint16_t)((j & 1) ? (pr >> 16) : (pr & 0xFFFFu)));                            \
+                }                                                                                                      \
+                _Pragma("unroll") for (int i = 0; i < MT; i++) {                                                       \
+                    const bf16x8 ah = as_bf16x8(glds[buf * BUF + (j * MT + i) * 64 + rdl[j]]);                         \
+                    const bf16x8 al = as_bf16x8(glds[buf * BUF + PLANE + (j * MT + i) * 64 + rdl[j]]);                 \
+                    f32x4 tt = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bw, (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);  \
+                    tt = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bw, tt, 0, 0, 0);                                 \
+                    acc[t][i][0] = fmaf(d, tt[0], acc[t][i][0]); acc[t][i][1] = fmaf(d, tt[1], acc[t][i][1]);          \
+                    acc[t][i][2] = fmaf(d, tt[2], acc[t][i][2]); acc[t][i][3] = fmaf(d, tt[3], acc[t][i][3]);          \
+                }                                                                                                      \
+            }                                                                                                          \
+        }
     float4 sxa[MT], sxb[MT];
-#pragma unroll
-    for (int i = 0; i < MT; i++) { sxa[i] = xa[i]; sxb[i] = xb[i]; }
-    VOX_STAGE(0)
     uint32_t cwd[NT][4]; uint2 csc[NT]; uint4 cwdv[NT][4];
+    if constexpr (MT == 2 && NT == 2 && FMT == WFMT_Q4_0 && TB == 1) {
+        // the 32 x 128 Q4 tile of the encoder's q|k|v, wo and w2 (672 / 560 workgroups): TWO weight / scale / activation register sets instead of three -- k-step q + 1 is loaded
+        // at the top of step q and is in flight while step q is multiplied -- bring the kernel to <= 168 VGPRs, so that three workgroups share a CU (768 resident: one round).
+        // Every accumulator sees the same MFMAs and FMAs in the same order: the same bits.
+        VOX_GLOAD(qb)
 #pragma unroll
-    for (int t = 0; t < NT; t++) { csc[t] = wsc[t];
+        for (int i = 0; i < MT; i++) { sxa[i] = xa[i]; sxb[i] = xb[i]; }
+        VOX_STAGE(0)
 #pragma unroll
-        for (int j = 0; j < 4; j++) { cwd[t][j] = wd[t][j]; cwdv[t][j] = wdv[t][j]; } }
-    { const int q1 = min(qb + 1, qe - 1); VOX_GLOAD(q1) }
-    __syncthreads();
-    for (int q = qb; q < qe; q++) {
-        const int buf = (q - qb) & 1;
+        for (int t = 0; t < NT; t++) { csc[t] = wsc[t];
 #pragma unroll
-        for (int i = 0; i < MT; i++) { sxa[i] = xa[i]; sxb[i] = xb[i]; }          // k-step q+1 (in flight since last iteration)
-        uint32_t nwd[NT][4]; uint2 nsc[NT]; uint4 nwdv[NT][4];
-#pragma unroll
-        for (int t = 0; t < NT; t++) { nsc[t] = wsc[t];
-#pragma unroll
-            for (int j = 0; j < 4; j++) { nwd[t][j] = wd[t][j]; nwdv[t][j] = wdv[t][j]; } }
-        { const int q2 = min(q + 2, qe - 1); VOX_GLOAD(q2) }                      // unconditional (clamped) prefetch
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-#pragma unroll
-            for (int t = 0; t < NT; t++) {
-                const bf16x8 bw = as_bf16x8(FMT == WFMT_Q4_0 ? q4_dword_to_bf16x8(cwd[t][j]) : cwdv[t][j]);
-                float d = 1.0f;
-                if (FMT == WFMT_Q4_0) {
-                    const uint32_t pr = (j & 2) ? csc[t].y : csc[t].x;
-                    d = f16_bits_to_f32((uint16_t)((j & 1) ? (pr >> 16) : (pr & 0xFFFFu)));
-                }
-#pragma unroll
-                for (int i = 0; i < MT; i++) {
-                    const bf16x8 ah = as_bf16x8(glds[buf * BUF + (j * MT + i) * 64 + rdl[j]]);
-                    const bf16x8 al = as_bf16x8(glds[buf * BUF + PLANE + (j * MT + i) * 64 + rdl[j]]);
-                    f32x4 tt = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bw, (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-                    tt = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bw, tt, 0, 0, 0);
-                    acc[t][i][0] = fmaf(d, tt[0], acc[t][i][0]); acc[t][i][1] = fmaf(d, tt[1], acc[t][i][1]);
-                    acc[t][i][2] = fmaf(d, tt[2], acc[t][i][2]); acc[t][i][3] = fmaf(d, tt[3], acc[t][i][3]);
-                }
-            }
-        }
-        if (q + 1 < qe) {
-            VOX_STAGE(buf ^ 1)
-#pragma unroll
-            for (int t = 0; t < NT; t++) { csc[t] = nsc[t];
-#pragma unroll
-                for (int j = 0; j < 4; j++) { cwd[t][j] = nwd[t][j]; cwdv[t][j] = nwdv[t][j]; } }
-        }
+            for (int j = 0; j < 4; j++) cwd[t][j] = wd[t][j]; }
         __syncthreads();
+        for (int q = qb; q < qe; q++) {
+            const int buf = (q - qb) & 1;
+            { const int q1 = min(q + 1, qe - 1); VOX_GLOAD(q1) }                      // unconditional (clamped) prefetch
+            __builtin_amdgcn_sched_barrier(0);                                        // (the loads stay in front of the multiplies)
+            VOX_MMA
+            if (q + 1 < qe) {
+#pragma unroll
+                for (int i = 0; i < MT; i++) { sxa[i] = xa[i]; sxb[i] = xb[i]; }
+                VOX_STAGE(buf ^ 1)
+#pragma unroll
+                for (int t = 0; t < NT; t++) { csc[t] = wsc[t];
+#pragma unroll
+                    for (int j = 0; j < 4; j++) cwd[t][j] = wd[t][j]; }
+            }
+            __syncthreads();
+        }
+    } else {      // every other instantiation: three register sets, k-step q + 2 in flight
+        VOX_GLOAD(qb)
+#pragma unroll
+        for (int i = 0; i < MT; i++) { sxa[i] = xa[i]; sxb[i] = xb[i]; }
+        VOX_STAGE(0)
+#pragma unroll
+        for (int t = 0; t < NT; t++) { csc[t] = wsc[t];
+#pragma unroll
+            for (int j = 0; j < 4; j++) { cwd[t][j] = wd[t][j]; cwdv[t][j] = wdv[t][j]; } }
+        { const int q1 = min(qb + 1, qe - 1); VOX_GLOAD(q1) }
+        __syncthreads();
+        for (int q = qb; q < qe; q++) {
+            const int buf = (q - qb) & 1;
+#pragma unroll
+            for (int i = 0; i < MT; i++) { sxa[i] = xa[i]; sxb[i] = xb[i]; }          // k-step q+1 (in flight since last iteration)
+            uint32_t nwd[NT][4]; uint2 nsc[NT]; uint4 nwdv[NT][4];
+#pragma unroll
+            for (int t = 0; t < NT; t++) { nsc[t] = wsc[t];
+#pragma unroll
+                for (int j = 0; j < 4; j++) { nwd[t][j] = wd[t][j]; nwdv[t][j] = wdv[t][j]; } }
+            { const int q2 = min(q + 2, qe - 1); VOX_GLOAD(q2) }                      // unconditional (clamped) prefetch
+            VOX_MMA
+            if (q + 1 < qe) {
+                VOX_STAGE(buf ^ 1)
+#pragma unroll
+                for (int t = 0; t < NT; t++) { csc[t] = nsc[t];
+#pragma unroll
+                    for (int j = 0; j < 4; j++) { cwd[t][j] = nwd[t][j]; cwdv[t][j] = nwdv[t][j]; } }
+            }
+            __syncthreads();
+        }
     }
+#undef VOX_MMA
 #undef VOX_GLOAD
 #undef VOX_STAGE
 #pragma unroll
