@@ -2,8 +2,23 @@
 // (one unit of the C ABI of libvoxtral_hip.so, include/voxtral_hip.h; the host units: DESIGN.md, "Host units")
 #include "vox_dev_base.h"
 
+#include <mutex>
+#include <unordered_map>
+
 using namespace vox;
 using namespace vox_host;
+
+// Every caller-visible cache carries a generation number from one process-wide counter and is listed while it lives: code that remembers a cache across calls (the
+// piecewise engine's layer table, the record of unverified engine steps) keys on (address, generation) -- a freed cache's address may be handed out again by the
+// allocator, with another max_seq behind the same K base -- and asks cache_alive() before it dereferences one it did not receive in the current call.
+static std::mutex g_cache_mu; static std::unordered_map<const vox_cache*, uint64_t> g_cache_live; static uint64_t g_cache_gen = 0;
+namespace vox_host {
+void cache_register(vox_cache* k) { std::lock_guard<std::mutex> l(g_cache_mu); k->gen = ++g_cache_gen; g_cache_live[k] = k->gen; }
+void cache_unregister(const vox_cache* k) { std::lock_guard<std::mutex> l(g_cache_mu); g_cache_live.erase(k); }
+bool cache_alive(const vox_cache* k, uint64_t gen) { std::lock_guard<std::mutex> l(g_cache_mu); auto it = g_cache_live.find(k); return it != g_cache_live.end() && it->second == gen; }
+// frees a cache nothing on the GPU reads any more: synchronising first, and dropping whatever remembers it, is the caller's
+void cache_release(vox_cache*& k) { if (!k) return; cache_unregister(k); (void)hipFree(k->k); (void)hipFree(k->v); delete k; k = nullptr; }
+}  // namespace vox_host
 
 // ---- KV cache (models/layers/kv_cache.rs:52-65,221-234)
 namespace vox_host {

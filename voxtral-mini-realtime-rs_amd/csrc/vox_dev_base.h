@@ -176,11 +176,18 @@ int32_t upload_repack(vox_ctx* c, const uint8_t* raw, int64_t n_blocks, int nb, 
 int32_t q4_linear_dev(vox_ctx* c, const vox::Q4W& w, const float* bias, const float* x, int x_stride, int rows, float* out, int out_stride,
                              int epi = vox::EPI_STORE, const float* resid = nullptr, int resid_stride = 0, int ksplit = 0);
 // ---- vox_api.cpp
-void cache_register(vox_cache* k);
-void cache_release(vox_cache*& k);
+void binding_release(EngBinding& b);
+void prefix_release(vox_model* m);
+void graphs_destroy(vox_model* m);
 int32_t pw_after_sync(vox_model* m);
 int32_t pw_sync(vox_model* m);
+// ---- vox_model.cpp (the loader; of vox_api.cpp it calls only the three release functions above)
+void model_release(vox_model* m);
 // ---- vox_cache.cpp
+void cache_register(vox_cache* k);
+void cache_unregister(const vox_cache* k);
+bool cache_alive(const vox_cache* k, uint64_t gen);
+void cache_release(vox_cache*& k);
 int32_t cache_alloc(vox_model* m, int max_seq, vox_cache** out);
 struct RoctxScope { explicit RoctxScope(const char* n) { roctx_push(n); } ~RoctxScope() { roctx_pop(); } };
 // consecutive stages of one function: begin() closes the previous stage; every exit path (error returns included) closes the open one
