@@ -426,7 +426,7 @@ int32_t vox_debug_reload_knobs(void);
  * [5] batched GQA decode, [6] fused attention + wo, [7] single-stream decode-engine launches (the whole step), [8] the live stream's ring attention (RoPE + K / V append + windowed
  * attention in one launch: exactly enc_layers per tick of a vox_stream).  Behind them, not attention: [9] a stream group's resampling ingest (one launch per pass for
  * all fed members), [10] a solo stream's.  Behind those, attention again: [11] paged single-query decode, [12] paged batched GQA decode (a paged stream group's step:
- * PAGED DECODER CACHE below).  Entries past [12] are written as 0. */
+ * PAGED DECODER CACHE below).  [13] ring single-query decode (vox_debug_attn_decode_ring below): 0 unless a ring launch ran.  Entries past [13] are written as 0. */
 int32_t vox_debug_attn_launches(uint64_t* out, int32_t cap);
 /* One decode attention launch on its own (tests): one query row per sequence against a decoder cache, through the launcher and with the parameters of the batched decode
  * steps -- exactly ONE launch; which kernel ran is the launcher's choice and is read from vox_debug_attn_launches ([3] [4] [5] slab, [11] [12] paged).
@@ -453,6 +453,20 @@ typedef struct {
 } vox_attn_decode_desc;
 int32_t vox_debug_attn_decode(vox_ctx* ctx, const vox_attn_decode_desc* desc, const float* q, const float* k, const float* v, void* out);
 int32_t vox_debug_attn_gqa_max_seq(vox_ctx* ctx, int32_t* out);
+/* One RING decode attention launch on its own (tests): vox_debug_attn_decode's slab call with every cache slice used as a ring.  max_seq is the ring capacity (any
+ * value in 1..16384, a power of two or not); k / v host [n_slices][n_kv_heads][max_seq][128]; row j of a sequence lives at ring row j % max_seq; pos[s] may be any
+ * value below 2^24; window >= 0 and window + 1 <= max_seq (a key outside the window may have been overwritten: without a window a ring has no meaning).  Sequence s
+ * attends the logical rows max(0, pos[s] - window) .. pos[s] in that order -- the flat kernel's scan order and reduction trees, so the output has the bits of
+ * vox_debug_attn_decode on the same keys laid out from row 0; ring rows outside the window are never read.  The per-head kernel, f32 rows out: prefer_gqa, spec,
+ * out_xf and the paged fields must be 0.  Exactly ONE launch, counted in vox_debug_attn_launches [13].  Every argument is checked before the context is bound. */
+int32_t vox_debug_attn_decode_ring(vox_ctx* ctx, const vox_attn_decode_desc* desc, const float* q, const float* k, const float* v, void* out);
+/* RoPE rows on their own (tests; host arithmetic, no device): rows first_pos .. first_pos + n - 1 (positions below 2^24) of the tables the kernels read, cos_out /
+ * sin_out [n][head_dim / 2], and in inv_out [head_dim / 2] the f32 factors 1 / theta^(2 j / head_dim) they were made from.  The ONE function that produces RoPE rows:
+ * the load-time tables and the streaming encoder's table are filled by it.  head_dim 128 is the decoder's geometry, whose load-time table has 16 384 rows; any other
+ * head_dim is taken as the encoder's, whose streaming table has 65 536.  Below that length a row has the table's bits (f32 product pos * inv, f32 cos / sin); from
+ * there on cos / sin are taken of double(pos) * double(inv) and rounded to f32 -- the f32 product loses the angle at large positions (its spacing is about 0.5 rad
+ * at position 4 M). */
+int32_t vox_debug_rope_rows(int32_t head_dim, float theta, int64_t first_pos, int32_t n, float* inv_out, float* cos_out, float* sin_out);
 /* Test hook: launches of the linear kernels enqueued by this process so far, by kernel form (host-side counts, as above; nothing is dispatched by them):
  * out[0..2] Q4 GEMV with 1 / 2 / 4 rows per wave, [3] dense GEMV, [4] 5..16-row skinny GEMM, [5] 17..48-row skinny GEMM (one-dimensional form), [6] its split-K form,
  * [7] rows -> XF tiles (helper of [5] / [6]), [8] split-K finishing sum (helper of [6]), [9..12] 16 x 64, 16 x 128, 32 x 64, 32 x 128 tile GEMM, [13] [14] the 32 x 64 and
@@ -533,7 +547,7 @@ int32_t vox_debug_plan_slots(const int32_t* steps, int32_t n, int32_t force_G, i
  *   for another t_embed, which the next offline call with that t_embed rebuilds; results never depend on it.  As everywhere, a prefix state that cannot be allocated
  *   switches the model's prefix cache off (create / reset then fail with VOX_ERR_HIP).
  * LIMITS: one decoder position = 2560 samples = 160 ms.  A session ends at 16 384 decoder positions (the decoder RoPE table; the encoder's 65 536-position table ends at
- * the same point), about 43 minutes: later pushes are refused until vox_stream_reset.  Input: 16 kHz, or the capture rate of a stream made by vox_stream_create_rate
+ * the same point), about 43 minutes: later pushes are refused until vox_stream_reset -- an ENDLESS session (vox_stream_create_endless below) goes on to 2^24.  Input: 16 kHz, or the capture rate of a stream made by vox_stream_create_rate
  * (every rate pair vox_resample serves), as f32 or as signed 16-bit PCM; mono.  Q4 (GGUF) models whose conv stem
  * runs as im2col GEMMs (3 n_mels and 3 enc_dim multiples of 128); dense SafeTensors models: VOX_ERR_UNSUPPORTED.
  *
@@ -563,6 +577,28 @@ int32_t vox_stream_create(vox_model* m, const float* t_embed, float gain, int32_
  * synchronises).  Rate pairs vox_resample refuses (block matrix above 64 MB: rates without a large common divisor, e.g. 44101 Hz) and blocks that do not fit the input
  * ring: VOX_ERR_UNSUPPORTED; rate 0: VOX_ERR_INVALID. */
 int32_t vox_stream_create_rate(vox_model* m, const float* t_embed, float gain, int32_t enc_capacity_rows, int32_t max_positions, uint32_t sample_rate, vox_stream** out);
+/* ENDLESS SESSIONS.  vox_stream_create_rate for a session whose limit is 2^24 decoder positions (31 days) instead of 16 384: its decoder cache is a RING of dec_ring_rows
+ * rows and its RoPE rows are made for the positions it is at, so device memory stops growing once the ring is full.  Every other vox_stream_* call works on it unchanged
+ * (push, push_s16, finish, peek, reset, info, scores, alternatives, the taps); everything vox_stream_create_rate refuses is refused here; a push that would pass 2^24
+ * positions is refused before anything changes.
+ *   dec_ring_rows: 0 = dec_window + 1 + TAIL rounded up to a multiple of 64 (8256 rows: 1.7 GB of K / V at full size, against the 3.4 GB of a 16 384-row flat cache).
+ *   TAIL = 63 is the most ticks one finish / peek tail may run: the backlog of the rate's unfinished block plus the right pad (vox_stream_peek_ids' arithmetic), computed
+ *   for the session's rate at create -- a rate whose tail is longer: VOX_ERR_UNSUPPORTED.  A given value must be at least dec_window + 1 + TAIL (VOX_ERR_INVALID, the
+ *   message names the minimum) and at most 16 384; it need not be a power of two.
+ *   Up to position dec_ring_rows the session runs a bounded session's code -- the engine up to 1024 rows, then the per-operator step on a flat cache that doubles up to
+ *   dec_ring_rows rows, the load-time RoPE tables -- and its logits are a bounded session's, bit for bit.  From position dec_ring_rows on, position p lives at cache row
+ *   p % dec_ring_rows: the q|k|v GEMV appends there and takes its RoPE row from the session's ring, the per-head ring attention follows, then the wo GEMV; the encoder's
+ *   ring attention reads its RoPE rows from the session's ring as well.  The fused attention + wo launch has no ring form: on the full-size model the step changes from
+ *   fused to unfused sums at the wrap, so logits stay within the 2e-4 bound there and are not bit-equal; geometries that never fuse stay bit-equal throughout.
+ *   RoPE rows: two device rings per session (1024 decoder rows, 4096 encoder rows), refilled by the host in front of each pass for exactly the positions the pass
+ *   runs; below the load-time table lengths a row has the table's bits, beyond them the angle is formed in double (vox_debug_rope_rows).
+ *   Peek: past the wrap a peek's tail overwrites ring rows that lay outside the window of every later position -- what the TAIL rows are for; nothing is saved.
+ *   Memory: vox_stream_info [5] is constant once the ring is full, apart from the position-indexed device lists -- the tokens (4 bytes per position) and, when on,
+ *   the score (16) and alternatives (72) records -- which GROW BY DOUBLING (from dec_ring_rows positions, at a verification point: one more synchronisation per
+ *   doubling) and are counted as they are.  The host record lists behind vox_stream_scores / vox_stream_alternatives grow with the utterance, 88 bytes per id, and are
+ *   not trimmed.  vox_stream_info [1] keeps counting positions.
+ *   Not served: stream groups (slab or paged), a ring form of the fused attention + wo launch, paging for a solo stream, trimming the host record lists. */
+int32_t vox_stream_create_endless(vox_model* m, const float* t_embed, float gain, int32_t enc_capacity_rows, int32_t dec_ring_rows, uint32_t sample_rate, vox_stream** out);
 /* samples host or device (mem_kind), ids host.  cap smaller than the ids the call will produce (known from the schedule before any work), a push after finish, a push
  * that would pass max_positions: VOX_ERR_INVALID BEFORE any state changes -- the call can be repeated. */
 int32_t vox_stream_push(vox_stream* s, const float* samples, size_t n, int32_t mem_kind, int32_t* out_ids, int32_t cap, int32_t* n_ids);

@@ -8,6 +8,7 @@
     python tools/stream_bench.py --alternatives 8 [--group 1,4,16] [--out profiles/stream_alternatives_tick.txt]
     python tools/stream_bench.py --peek [--out profiles/stream_peek.txt]
     python tools/stream_bench.py --group 1,4,16 --page-rows 256 [--out profiles/stream_group_paged_tick.txt]
+    python tools/stream_bench.py --endless [--out profiles/stream_endless_tick.txt]
 
  * stream: HIP events on the context's stream around ONE push of `ticks` x 2560 samples (a large push is a loop of identical ticks), at encoder positions past the
    750-row window, median of `passes` passes; launches per tick from the library's launch counters plus the fixed launches of a tick; wall time of single 160 ms pushes
@@ -35,6 +36,10 @@
    and the slab's 2048 positions per member), warmed like the slab group and timed the same way: pass i of the paged group right behind pass i of the slab group, the
    same positions.  Reports the paged round, its difference to the slab round and both launch counts.  Behind the widths: one run of 16 members of mixed lengths on a
    paged group, the pool's peak use in bytes next to the bytes of the default slab.
+ * --endless: the tick of an ENDLESS session (vox_stream_create_endless) past the wrap of its decoder ring, next to a bounded session (max_positions 16 384) at the
+   same positions: both are fed the same device-resident samples up to a few ticks past the ring's rows (not timed), then per pass one push of `ticks` ticks each,
+   the endless session's right behind the bounded one's.  Medians, their difference, the launches per tick of both (the ring form runs attention and wo as two
+   launches per decoder layer) and the device bytes each session holds.  Nothing else is measured in this mode.
  * derived figures are labelled as derived."""
 import argparse
 import ctypes as C
@@ -77,8 +82,8 @@ class Timer:
 
 
 def launch_counts(pkg):
-    a = (C.c_uint64 * 13)(); g = (C.c_uint64 * 20)()      # attention forms 0..8 and the paged decode forms 11, 12 (9 and 10 are the resampling ingests: not counted here)
-    L = pkg.lib(); assert L.vox_debug_attn_launches(a, 13) == 0 and L.vox_debug_gemm_launches(g, 20) == 0
+    a = (C.c_uint64 * 14)(); g = (C.c_uint64 * 20)()      # attention forms 0..8, the paged decode forms 11, 12 and the ring decode form 13 (9 and 10 are the resampling ingests: not counted here)
+    L = pkg.lib(); assert L.vox_debug_attn_launches(a, 14) == 0 and L.vox_debug_gemm_launches(g, 20) == 0
     return sum(a[:9]) + sum(a[11:]), sum(g)
 
 
@@ -227,6 +232,43 @@ def bench_peek(pkg, ctx, m, t, tm, a, lines):
               f"derived: per tick {q / T:.3f} ms; the two keep launches move at most 2 x {save / 1e6:.1f} MB"]
 
 
+def bench_endless(pkg, ctx, m, t, tm, a, lines):
+    """--endless: per pass one push of `ticks` ticks of a bounded session, then of an endless session past its wrap, at the same positions."""
+    c = m.config; S = pkg.synth; L = pkg.lib()
+    ring = (c.dec_window + 1 + 63 + 63) // 64 * 64      # the default dec_ring_rows
+    warm = ring + 8 - 37                                 # ticks that take both sessions a few positions past the wrap
+    n_ticks = warm + a.ticks * a.passes + 8
+    assert 38 + n_ticks <= 16384, "the bounded session ends at 16 384 positions"
+    base = S.synth_audio(40.0, seed=4242); gain = float(np.float32(0.95) / np.float32(np.abs(base).max()))
+    n = 40 + 2560 * n_ticks
+    x = np.tile(base, n // len(base) + 1)[:n].copy()
+    dev = C.c_void_p(); pkg._lib.check(L.vox_dev_alloc(ctx.h, x.nbytes, C.byref(dev))); pkg._lib.check(L.vox_dev_upload(ctx.h, dev, x.ctypes.data, x.nbytes))
+    fixed = 1 + 2 * c.enc_layers + 1 + 1 + 1      # stream_mel, two RMSNorms per encoder layer, final norm, stream_embed, stream_advance
+    sb = m.create_stream(t, gain=gain, max_positions=16384); se = m.create_stream(t, gain=gain, endless=True)
+    pos = 40 + 2560 * warm
+    for st in (sb, se):
+        for a0 in range(0, pos, 2560 * 1024):
+            st.push(device_ptr=dev.value + 4 * a0, n_samples=min(pos, a0 + 2560 * 1024) - a0)
+    assert sb.info()["positions"] == se.info()["positions"] == 38 + warm > ring
+    pb, pe = [], []; kb = ke = 0; idb, ide = [], []
+    for _ in range(a.passes):
+        ptr, cnt = dev.value + 4 * pos, 2560 * a.ticks; pos += cnt
+        k0 = launch_counts(pkg); pb.append(tm.ms(lambda: idb.append(sb.push(device_ptr=ptr, n_samples=cnt))) / a.ticks); k1 = launch_counts(pkg)
+        pe.append(tm.ms(lambda: ide.append(se.push(device_ptr=ptr, n_samples=cnt))) / a.ticks); k2 = launch_counts(pkg)
+        kb += sum(k1) - sum(k0); ke += sum(k2) - sum(k1)
+    ib, ie = sb.info(), se.info()
+    assert ib["positions"] == ie["positions"] == 38 + warm + a.ticks * a.passes
+    sb.close(); se.close(); pkg._lib.check(L.vox_dev_free(ctx.h, dev))
+    ticks = a.ticks * a.passes; b, e = statistics.median(pb), statistics.median(pe)
+    idb, ide = np.concatenate(idb), np.concatenate(ide)
+    lines += [f"bounded session (max_positions 16384), positions {38 + warm} .. {ib['positions'] - 1}: tick median {b:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in pb),
+              f"endless session (decoder ring of {ring} rows), the same positions, each pass right behind the bounded one's: tick median {e:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in pe),
+              f"difference endless - bounded: {e - b:+.3f} ms ({100 * (e - b) / b:+.2f} %), per pass " + " ".join(f"{v - w:+.3f}" for v, w in zip(pe, pb)),
+              f"launches per tick: bounded {kb / ticks + fixed:.0f}, endless {ke / ticks + fixed:.0f} (difference {(ke - kb) / ticks:+.0f}; {c.dec_layers} decoder layers)",
+              f"device bytes held at the end: bounded {ib['bytes'] / 1e9:.3f} GB, endless {ie['bytes'] / 1e9:.3f} GB",
+              f"ids of the timed passes: {int((idb == ide).sum())} of {len(idb)} equal (the bounded step fuses attention + wo where the model allows it, the ring step does not: equal bits are not promised there)"]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gguf"); ap.add_argument("--ticks", type=int, default=200); ap.add_argument("--passes", type=int, default=3); ap.add_argument("--out")
@@ -237,7 +279,10 @@ def main():
     ap.add_argument("--alternatives", type=int, default=0, metavar="K", help="also time a stream (with --group: and a group) with alternatives on at k = K (1..8), as --scores does")
     ap.add_argument("--page-rows", type=int, default=0, metavar="R", help="with --group: also time a paged group (pages of R rows, the default pool) pass by pass next to the slab group")
     ap.add_argument("--peek", action="store_true", help="time vox_stream_peek next to the same number of ordinary ticks of the same session (nothing else is measured)")
+    ap.add_argument("--endless", action="store_true", help="time the tick of an endless session past the wrap of its decoder ring next to a bounded session at the same positions (nothing else is measured)")
     a = ap.parse_args()
+    if a.endless and (a.group or a.scores or a.alternatives or a.peek):
+        ap.error("--endless is a mode of its own")
     if not 0 <= a.alternatives <= 8:
         ap.error("--alternatives takes 1..8")
     if a.peek and (a.group or a.scores or a.alternatives):
@@ -259,6 +304,17 @@ def main():
             S.write_synthetic_gguf(path + ".tmp", S.ModelDims(), seed=42); os.replace(path + ".tmp", path)
     ctx = pkg.Context(0); m = pkg.Q4ModelLoader.from_file(path).load(ctx); c = m.config
     t = pkg.TimeEmbedding(c.dec_dim).embed(6.0); tm = Timer(pkg, ctx); L = pkg.lib()
+    if a.endless:
+        lines = ["# " + " ".join(["python", "tools/stream_bench.py"] + sys.argv[1:]),
+                 f"# model {os.path.basename(path)}: {c.enc_layers} encoder layers, {c.dec_layers} decoder layers; {a.ticks} ticks per pass, {a.passes} passes"]
+        bench_endless(pkg, ctx, m, t, tm, a, lines)
+        text = "\n".join(lines) + "\n"
+        print(text, end="")
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            open(a.out, "w").write(text)
+        m.close(); ctx.close()
+        return
     if a.peek:
         lines = ["# " + " ".join(["python", "tools/stream_bench.py"] + sys.argv[1:]),
                  f"# model {os.path.basename(path)}: {c.enc_layers} encoder layers, {c.dec_layers} decoder layers; {a.passes} passes, all past encoder position {4 * (37 + 200)}"]

@@ -166,6 +166,8 @@ SIGNATURES = {
     "vox_bench_wide": (i32, [vp, i32, i32, i32, P(C.c_double)]),
     "vox_debug_attn_launches": (i32, [P(C.c_uint64), i32]),
     "vox_debug_attn_decode": (i32, [vp, vp, vp, vp, vp, vp]),
+    "vox_debug_attn_decode_ring": (i32, [vp, vp, vp, vp, vp, vp]),
+    "vox_debug_rope_rows": (i32, [i32, C.c_float, C.c_int64, i32, vp, vp, vp]),
     "vox_debug_attn_gqa_max_seq": (i32, [vp, P(i32)]),
     "vox_debug_gemm_launches": (i32, [P(C.c_uint64), i32]),
     "vox_debug_timeline_start": (i32, [vp, i32, i32]),
@@ -188,6 +190,7 @@ SIGNATURES = {
     "vox_debug_stream_front_tap_fetch": (i32, [vp, vp, vp, P(i32)]),
     "vox_debug_front_end": (i32, [vp, i32, P(vp), P(sz), P(i32), i32, i32, vp, P(vp), P(i32)]),
     "vox_stream_create_rate": (i32, [vp, vp, f32, i32, i32, u32, P(vp)]),
+    "vox_stream_create_endless": (i32, [vp, vp, f32, i32, i32, u32, P(vp)]),
     "vox_stream_push_s16": (i32, [vp, vp, sz, i32, vp, i32, P(i32)]),
     "vox_stream_schedule_rate": (i32, [sz, u32, i32, P(i32), P(i32), P(sz)]),
     "vox_stream_group_create": (i32, [vp, vp, i32, vp, i32, i32, P(vp)]),

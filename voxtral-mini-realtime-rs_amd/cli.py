@@ -110,7 +110,7 @@ def write_words(out, pkg, path, ids, scores, tokenizer, rate, alternatives=None)
     out.flush()
 
 
-def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_rate=False, words_out=None, peek=False, alts_k=0):
+def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_rate=False, words_out=None, peek=False, alts_k=0, endless=False):
     """--live: the file through a live session (vox_stream) in pieces of `chunk_ms` milliseconds, the text so far on stderr whenever ids arrive.  The gain is the
     file's peak scale 0.95 / max|x| (bin/transcribe.rs:207; a file is known in advance -- a microphone caller passes its own), the whole file is one utterance (no
     --max-mel-frames chunks: the session's state is bounded by its ring), so the line equals the un-chunked path's.
@@ -120,7 +120,8 @@ def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_
     words_out (--live-words): the session runs with scores on and the file's words go there when it ends; the ids, hence the line, are the same.
     alts_k (--live-alternatives): the session also keeps every id's alts_k best alternatives and the step's entropy, for the words file.
     peek (--live-peek): after every push a "  ~[" line on stderr with the text so far plus the tentative tail -- what the line would be if the file ended here
-    (vox_stream_peek: finish's ticks, taken back); the session, hence everything else, is as without the flag."""
+    (vox_stream_peek: finish's ticks, taken back); the session, hence everything else, is as without the flag.
+    endless (--live-endless): the session is an endless one (vox_stream_create_endless: no 43-minute limit, the decoder cache a ring); the line is the same."""
     x, sr = load_wav(path)
     rate = 16000
     if sr != 16000:
@@ -135,7 +136,7 @@ def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_
     peak = np.float32(np.abs(x16).max()) if x16.size else np.float32(0)
     gain = float(np.float32(0.95) / peak) if peak >= 1e-10 else 1.0              # audio/io.rs:59-68
     step = max(1, int(round(rate * chunk_ms / 1000.0)))
-    stream = model.create_stream(t_embed, gain=gain, sample_rate=rate)
+    stream = model.create_stream(t_embed, gain=gain, sample_rate=rate, endless=endless)
     try:
         if words_out is not None:
             stream.set_scores(True)
@@ -359,6 +360,8 @@ def main(argv=None):
     ap.add_argument("--live-page-rows", type=int, default=None, metavar="R", help="with --live-group: a paged group (vox_stream_group_create_paged) whose decoder cache is one pool "
                     "of K / V pages of R rows (a power of two in 16..1024; 0: 256) that the files grow into, instead of a 2048-position slab slice per member; same lines")
     ap.add_argument("--live-pool-pages", type=int, default=None, metavar="P", help="with --live-group: a paged group with a pool of P pages (0: the default slab's memory)")
+    ap.add_argument("--live-endless", action="store_true", help="with --live (one file at a time, not --live-group): an endless session (vox_stream_create_endless) -- no limit at "
+                    "16 384 decoder positions (about 43 minutes); the decoder cache is a ring of a little more than one window and stops growing there")
     ap.add_argument("--live-peek", action="store_true", help="with --live (also with --live-group, --live-native-rate, --live-words): after every push a line starting with "
                     "'  ~[' on stderr: the text so far plus the tentative tail, i.e. the line if the file ended here (vox_stream_peek); stdout, the '  [' lines and the "
                     "words file do not change")
@@ -406,6 +409,8 @@ def main(argv=None):
         ap.error("--live-group feeds 16 kHz samples: it does not combine with --live-native-rate")
     if a.live and (a.gpus > 1 or a.batch > 1 or a.live_chunk_ms <= 0):
         ap.error("--live runs one file at a time on one GPU (no --gpus / --batch) with --live-chunk-ms > 0")
+    if a.live_endless and (not a.live or a.live_group):
+        ap.error("--live-endless applies with --live, one file at a time (stream groups have no endless form)")
     if a.live_native_rate and not a.live:
         ap.error("--live-native-rate applies with --live")
     if a.live and not a.gguf:
@@ -508,7 +513,7 @@ def main(argv=None):
         p = paths[i]
         try:
             t1 = time.time()
-            text = transcribe_live(pkg, p, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_native_rate, words_out, a.live_peek, a.live_alternatives) if a.live else transcribe_one(pkg, p, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed, rec_out, a.alternatives or 0)
+            text = transcribe_live(pkg, p, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_native_rate, words_out, a.live_peek, a.live_alternatives, a.live_endless) if a.live else transcribe_one(pkg, p, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed, rec_out, a.alternatives or 0)
             log(f"{p}: {time.time() - t1:.3f}s")
         except Exception as e:      # per-utterance failure isolates to that line (empty), eval_wer.py:211-223 tolerates it
             log(f"Error transcribing {p}: {e}"); text = ""; rc = 1

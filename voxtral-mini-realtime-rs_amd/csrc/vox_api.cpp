@@ -253,8 +253,8 @@ extern "C" int32_t vox_encoder_cache_apply_sliding_window(vox_cache* kc, int32_t
 static int32_t enc_stream_rope_ensure(vox_model* m) {
     if (m->enc_cos_s) return VOX_OK;
     const vox_model_cfg& c = m->cfg; const int hd = c.enc_head_dim;
-    const int len = 1 << 16, half = hd / 2; std::vector<float> ct((size_t)len * half), st((size_t)len * half);
-    for (int i = 0; i < len; i++) for (int j = 0; j < half; j++) { const float inv = 1.0f / std::pow(c.rope_theta, (float)(2 * j) / (float)hd), fr = (float)i * inv; ct[(size_t)i * half + j] = std::cos(fr); st[(size_t)i * half + j] = std::sin(fr); }
+    const int len = ROPE_ENC_STREAM_TABLE_LEN, half = hd / 2; std::vector<float> ct((size_t)len * half), st((size_t)len * half);
+    rope_rows_fill(hd, c.rope_theta, 0, len, len, nullptr, ct.data(), st.data());
     HIPCHK(hipMalloc((void**)&m->enc_cos_s, ct.size() * 4)); HIPCHK(hipMalloc((void**)&m->enc_sin_s, st.size() * 4));
     HIPCHK(hipMemcpy(m->enc_cos_s, ct.data(), ct.size() * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(m->enc_sin_s, st.data(), st.size() * 4, hipMemcpyHostToDevice));
     m->enc_rope_s_len = len;
@@ -477,7 +477,10 @@ static bool decode_layer_fuses_attn_wo(const vox_model* m, const DecLayer& L, co
 // attn_wo accumulators: every step leaves them cleared (w2 does it); clearing them outright before a run of steps keeps a call that failed half-way through a layer from
 // leaking into the next one
 static int32_t wo_acc_clear(vox_model* m, hipStream_t s) { if (m->d_wo_acc) HIPCHK(hipMemsetAsync(m->d_wo_acc, 0, (size_t)m->cfg.dec_layers * m->cfg.dec_dim * 8, s)); return VOX_OK; }
-static int32_t decoder_step_dev(vox_model* m, float* h, vox_cache* kc, const int* pos_ptr, int pos_off) {
+// ring (an endless session's step from its wrap on): the cache is a RING of kc->max_seq rows -- the q|k|v GEMV appends at row position % max_seq and reads its RoPE row
+// from the session's ring (EPI_ROPE_KV_RING), the per-head ring attention follows, then the wo GEMV: the fused attention + wo launch has no ring form
+struct DecRingStep { const float* rope; int mask; };      // the session's decoder RoPE ring [mask + 1][cos hd/2 | sin hd/2]
+static int32_t decoder_step_dev(vox_model* m, float* h, vox_cache* kc, const int* pos_ptr, int pos_off, const DecRingStep* ring = nullptr) {
     const vox_model_cfg& c = m->cfg; hipStream_t s = m->ctx->stream;
     const int D = c.dec_dim, H = c.dec_heads, KV = c.dec_kv_heads, hd = c.dec_head_dim, QD = H * hd, KD = KV * hd, F = c.dec_ffn;
     const size_t lf = kc->layer_stride;
@@ -487,14 +490,15 @@ static int32_t decoder_step_dev(vox_model* m, float* h, vox_cache* kc, const int
         p.w = L.wqkv.w; p.x = h; p.x_stride = D; p.out = m->d_q; p.out_stride = QD; p.gamma = L.attn_norm; p.eps = c.norm_eps;
         p.pos_ptr = pos_ptr; p.pos_off = pos_off; p.rope_cos = m->dec_cos; p.rope_sin = m->dec_sin; p.hd = hd; p.n_q = QD; p.n_k = KD;
         p.kcache = kl; p.vcache = vl; p.cache_head_stride = kc->max_seq * hd;
+        if (ring) { p.rope_cos = ring->rope; p.rope_sin = ring->rope + hd / 2; p.rope_mask = ring->mask; }
         {
-            HIPCHK(launch_q4_gemv(p, 1, PRO_RMS, EPI_ROPE_KV, q4_gemv_default_R(p.w.N, p.w.K, EPI_ROPE_KV), s));
+            HIPCHK(launch_q4_gemv(p, 1, PRO_RMS, ring ? EPI_ROPE_KV_RING : EPI_ROPE_KV, q4_gemv_default_R(p.w.N, p.w.K, EPI_ROPE_KV), s));
             AttnParams ap{}; ap.q = m->d_q; ap.k = kl; ap.v = vl; ap.kv_row_stride = hd; ap.kv_head_stride = kc->max_seq * hd; ap.out = m->d_att;
             ap.n_heads = H; ap.n_kv_heads = KV; ap.offset = pos_off; ap.window = c.dec_window; ap.pos_ptr = pos_ptr; ap.M = 1; ap.spec_rows = kc->max_seq;
             // four launches per layer: attention + wo in one (32-way K split, one partial product per head, combined with int64 fixed-point atomics);
             // w1|w3's prologue adds the sum to the residual and writes the new residual stream (d_h2) for w2's epilogue
             const int R13 = q4_gemv_default_R(L.w13.w.N, L.w13.w.K, EPI_SWIGLU);
-            if (decode_layer_fuses_attn_wo(m, L, ap, kc) && h != m->d_h2) {
+            if (!ring && decode_layer_fuses_attn_wo(m, L, ap, kc) && h != m->d_h2) {
                 long long* acc = m->d_wo_acc + (size_t)l * D;      // zero on entry: cleared at allocation, and by w2 below after every use
                 HIPCHK(launch_attn_wo(ap, L.wo.w, acc, kc->max_seq, s));
                 GemvParams f{}; f.w = L.w13.w; f.x = h; f.x_stride = D; f.out = m->d_act; f.out_stride = F; f.gamma = L.ffn_norm; f.mul = L.ada_mul; f.eps = c.norm_eps;
@@ -505,7 +509,7 @@ static int32_t decoder_step_dev(vox_model* m, float* h, vox_cache* kc, const int
                 HIPCHK(launch_q4_gemv(d, 1, PRO_NONE, EPI_RESID, q4_gemv_default_R(d.w.N, d.w.K, EPI_RESID), s));
                 continue;
             }
-            HIPCHK(launch_attn_decode(ap, hd, kc->max_seq, s));
+            HIPCHK(ring ? launch_attn_decode_ring(ap, hd, kc->max_seq, s) : launch_attn_decode(ap, hd, kc->max_seq, s));
         }
         GemvParams o{}; o.w = L.wo.w; o.x = m->d_att; o.x_stride = QD; o.out = h; o.out_stride = D; o.resid = h; o.resid_stride = D;
         HIPCHK(launch_q4_gemv(o, 1, PRO_NONE, EPI_RESID, q4_gemv_default_R(o.w.N, o.w.K, EPI_RESID), s));
@@ -1209,7 +1213,8 @@ extern "C" int32_t vox_debug_attn_gqa_max_seq(vox_ctx* c, int32_t* out) {
     int most = 0; HIPCHK(attn_decode_gqa_max_seq(&most));
     *out = most; return VOX_OK;
 }
-extern "C" int32_t vox_debug_attn_decode(vox_ctx* c, const vox_attn_decode_desc* d, const float* q, const float* k, const float* v, void* out) {
+// ring: vox_debug_attn_decode_ring -- the slab call's buffers with the cache slices used as rings of max_seq rows (launch_attn_decode_ring)
+static int32_t attn_decode_debug(vox_ctx* c, const vox_attn_decode_desc* d, const float* q, const float* k, const float* v, void* out, bool ring) {
     ARGCHK(c && d && q && k && v && out, "null argument"); ARGCHK(d->pos, "null argument (pos)");
     ARGCHK(d->head_dim == 128, "head_dim %d: the decoder's decode attention serves head_dim 128 alone", d->head_dim);
     ARGCHK(d->n_seq >= 1 && d->n_seq <= 4096, "n_seq %d out of range (1..4096)", d->n_seq);
@@ -1220,7 +1225,13 @@ extern "C" int32_t vox_debug_attn_decode(vox_ctx* c, const vox_attn_decode_desc*
     const bool paged = d->page_rows != 0;
     const int hd = 128, H = d->n_heads, KV = d->n_kv_heads, QD = H * hd, W = QD + 2 * KV * hd, n = d->n_seq;
     int shift = 0;
-    if (!paged) {
+    if (ring) {
+        ARGCHK(d->max_seq >= 1 && d->max_seq <= 16384, "max_seq %d (the ring capacity) out of range (1..16384)", d->max_seq);
+        ARGCHK(!paged && !d->pool_pages && !d->page_tab && !d->page_tab_stride && !d->score_rows, "a ring call takes no paged field");
+        ARGCHK(!d->prefer_gqa && !d->spec && !d->out_xf, "the ring form is the per-head kernel writing f32 rows: prefer_gqa, spec and out_xf must be 0");
+        ARGCHK(d->window >= 0 && d->window + 1 <= d->max_seq, "window %d: a ring of %d rows serves windows 0..%d", d->window, d->max_seq, d->max_seq - 1);
+        for (int i = 0; i < n; i++) ARGCHK(d->pos[i] >= 0 && d->pos[i] < (1 << 24), "pos[%d] = %d outside 0..2^24 - 1", i, d->pos[i]);
+    } else if (!paged) {
         ARGCHK(d->max_seq >= 1 && d->max_seq <= 16384, "max_seq %d out of range (1..16384)", d->max_seq);
         ARGCHK(!d->pool_pages && !d->page_tab && !d->page_tab_stride && !d->score_rows, "a slab call takes no paged field");
         for (int i = 0; i < n; i++) ARGCHK(d->pos[i] >= 0 && d->pos[i] < d->max_seq, "pos[%d] = %d outside the cache's %d rows", i, d->pos[i], d->max_seq);
@@ -1270,11 +1281,18 @@ extern "C" int32_t vox_debug_attn_decode(vox_ctx* c, const vox_attn_decode_desc*
     if (paged) {
         ap.kv_head_stride = (hd << shift); ap.page_tab = d_tab; ap.page_tab_stride = d->page_tab_stride; ap.page_shift = shift; ap.page_floats = (long)slice_f; ap.score_rows = d->score_rows;
         HIPCHK(launch_attn_decode_paged(ap, hd, s, n));
-    } else HIPCHK(launch_attn_decode(ap, hd, d->max_seq, s, n));
+    } else if (ring) HIPCHK(launch_attn_decode_ring(ap, hd, d->max_seq, s, n));
+    else HIPCHK(launch_attn_decode(ap, hd, d->max_seq, s, n));
     if (d->out_xf) HIPCHK(hipMemcpyAsync(out, dxf.p, xf_b * n_grp, hipMemcpyDeviceToHost, s));
     else HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)n * QD * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return VOX_OK;
+}
+extern "C" int32_t vox_debug_attn_decode(vox_ctx* c, const vox_attn_decode_desc* d, const float* q, const float* k, const float* v, void* out) {
+    return attn_decode_debug(c, d, q, k, v, out, false);
+}
+extern "C" int32_t vox_debug_attn_decode_ring(vox_ctx* c, const vox_attn_decode_desc* d, const float* q, const float* k, const float* v, void* out) {
+    return attn_decode_debug(c, d, q, k, v, out, true);
 }
 // What a batched XF decode step works on.  f32 rows (h, qkv, logits; att unread), XF planes and partial sums of squares one block per 16-row group, `*_gs` elements apart.
 // k / v: layer 0's cache slab (layer l at + l layer_stride), row r's slice at + r seq_stride, or, with kv_row, the slice kv_row[r] names; pos: the rows' positions.
@@ -2857,6 +2875,17 @@ extern "C" int32_t vox_debug_encode_batch(vox_model* m, int32_t n, const float* 
 static const int STREAM_KEEP_ROWS = 1024;           // adapter rows kept for the re-run of unverified engine steps; a push verifies at least this often
 // A session's scores (vox_stream_set_scores; DESIGN.md section 8, "Scores"): the device records the score kernel writes, one per id of the utterance, and their host
 // mirror -- one record per id handed out, the ones of a call copied in front of its synchronisation.  Nothing is allocated before the first set(1).
+// a position-indexed device list of `*cap` records of `rec` bytes grows to `rows` records: a new array, the old records copied on the stream, the old array freed behind
+// a synchronisation (nothing may still read it)
+static int32_t list_grow(void** dev, int* cap, int rows, size_t rec, hipStream_t s) {
+    void* q = nullptr;
+    if (hipMalloc(&q, (size_t)rows * rec) != hipSuccess) { (void)hipGetLastError(); return fail(VOX_ERR_HIP, "hipMalloc of a session's %d-record list failed", rows); }
+    hipError_t e = hipMemcpyAsync(q, *dev, (size_t)*cap * rec, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { (void)hipFree(q); return fail(VOX_ERR_HIP, "growing a session's list failed: %s", hipGetErrorString(e)); }
+    (void)hipFree(*dev); *dev = q; *cap = rows;
+    return VOX_OK;
+}
 struct ScoreState {
     bool on = false; TokenScore* dev = nullptr; int cap = 0;
     std::vector<vox_token_score> host;
@@ -2867,6 +2896,8 @@ struct ScoreState {
         if (hipMalloc((void**)&dev, (size_t)(max_pos + 2) * sizeof(TokenScore)) != hipSuccess) { (void)hipGetLastError(); dev = nullptr; return fail(VOX_ERR_HIP, "hipMalloc of %s score records failed", whose); }
         cap = max_pos + 2; return VOX_OK;
     }
+    // an endless session's records outgrow their array: `rows` records from here on, the old ones copied over (the caller synchronises and points its descriptor at dev)
+    int32_t grow(int rows, hipStream_t s) { return list_grow((void**)&dev, &cap, rows, sizeof(TokenScore), s); }
     // in front of the call's synchronisation: the copy of the call's `due` records behind the `have` handed out so far, when scores are on and there is a destination
     int32_t enqueue(int have, int due, vox_token_score* dst, hipStream_t s) const {
         if (on && dst && due > 0) HIPCHK(hipMemcpyAsync(dst, dev + have, (size_t)due * sizeof(TokenScore), hipMemcpyDeviceToHost, s));
@@ -2896,6 +2927,7 @@ struct AltsState {
         if (hipMalloc((void**)&dev, (size_t)(max_pos + 2) * sizeof(TokenAlts)) != hipSuccess) { (void)hipGetLastError(); dev = nullptr; return fail(VOX_ERR_HIP, "hipMalloc of %s alternatives records failed", whose); }
         cap = max_pos + 2; return VOX_OK;
     }
+    int32_t grow(int rows, hipStream_t s) { return list_grow((void**)&dev, &cap, rows, sizeof(TokenAlts), s); }      // as ScoreState::grow
     void restart() { host.clear(); peeked.clear(); }      // create / reset: the lists start over, k stays
     // in front of the call's synchronisation: where the call's `due` records go (the session's list behind the `have` handed out, a peek's own array), and their copy
     // A session that never had k > 0 (dev null) keeps no list: its pushes do no work here, and read hands out off-records for the ids the list does not reach.
@@ -2963,7 +2995,17 @@ struct vox_stream {
     int h_state[STRM_WORDS]; int h_pos_word = 0;
     // vox_stream_peek: the ring keep's save area; while a peek's ticks run (active), a decoder cache that grows leaves its planes in `old`: the peek puts them back
     struct { KeepArea keep; bool active = false; DecPlanes old; } peek;
+    // An ENDLESS session (vox_stream_create_endless; DESIGN.md section 8, "Endless sessions"): max_pos is 2^24, the decoder cache stops growing at ring_rows rows and is a
+    // ring from position ring_rows on (dec_limit: where the cache's growth ends -- ring_rows, or a bounded session's max_pos); the position-indexed device lists
+    // (tokens, score and alternatives records) start at lists_cap positions and grow by doubling at a verification point.  rope: the session's two device RoPE rings
+    // ([rows][cos hd/2 | sin hd/2], rows a power of two), their pinned host images, and the event behind the last copy out of those images.
+    bool endless = false; int ring_rows = 0, dec_limit = 0, lists_cap = 0;
+    struct { float *dec = nullptr, *enc = nullptr, *h_dec = nullptr, *h_enc = nullptr; hipEvent_t copied = nullptr; bool pending = false; } rope;
 };
+static const int STREAM_TAIL_TICKS = 63;            // the most ticks a finish / peek tail of an endless session may run (peek_max_ticks at the session's rate, asserted at create and in every peek)
+static const int STREAM_ROPE_DEC_ROWS = 1024;       // rows of an endless session's decoder RoPE ring = the most ticks of one pass; the encoder's ring has reshape_factor times as many
+static const int STREAM_POS_LIMIT = 1 << 24;        // an endless session's position limit (31 days)
+static bool stream_in_ring(const vox_stream* st) { return st->endless && st->feed.pos >= st->ring_rows; }      // is the next tick's decoder cache row a ring row?
 
 // the buffers of a round of up to n sessions (n = 1: a solo stream's tick), carved from one allocation; returns its size in floats (base may be null).
 // A slot's mel halo is padded from 4 R + 3 to 4 R + 4 frames and its conv1 block from 2 R + 1 to 2 R + 2 rows, so that slots lie a whole number of window strides
@@ -2989,7 +3031,7 @@ static void dec_set_planes(vox_cache* kc, const DecPlanes& p) { cache_unregister
 // `leave`: where the old planes stay (a peek undoes the growth); null: they are freed
 static int32_t stream_dec_grow(vox_stream* st, DecPlanes* leave) {
     vox_model* m = st->m; const vox_model_cfg& c = m->cfg; hipStream_t s = st->ctx->stream; vox_cache* kc = st->dec;
-    const int old = kc->max_seq, rows = std::min(st->max_pos, 2 * old), hd = c.dec_head_dim;
+    const int old = kc->max_seq, rows = std::min(st->dec_limit, 2 * old), hd = c.dec_head_dim;
     ARGCHK(rows > old, "internal: decoder cache of %d rows cannot grow", old);
     const size_t planes = (size_t)c.dec_layers * c.dec_kv_heads, nb = planes * rows * hd * 4;
     float *nk = nullptr, *nv = nullptr;
@@ -3036,7 +3078,7 @@ static int32_t stream_seed(vox_model* m, const float* t_embed, int RC, int PC, i
 }
 static int32_t stream_load_initial(vox_stream* st) {
     vox_model* m = st->m;
-    VOXCHK(stream_dec_alloc(st, std::min(st->max_pos, ENGINE_MAX_ROWS)));
+    VOXCHK(stream_dec_alloc(st, std::min(st->dec_limit, ENGINE_MAX_ROWS)));
     // the engine's view of THIS cache, in the stream's own binding: no table is rebuilt (and nothing synchronised) when streams, piecewise and offline callers alternate;
     // uploaded behind the seed's copies and in front of its synchronisation, so that the first step finds its cache bound
     VOXCHK(stream_seed(m, st->t_embed.data(), st->RC, st->PC, st->cap, st->kring, st->vring, st->dec, st->tokens, st->state, st->h_state,
@@ -3053,7 +3095,9 @@ static void stream_release(vox_stream* st) {
     cache_release(st->dec);
     for (void* p : {(void*)st->kring, (void*)st->vring, (void*)st->samples, (void*)st->audio_keep, (void*)st->ws, (void*)st->tokens, (void*)st->state, (void*)st->tap, (void*)st->ftap_mel, (void*)st->ftap_conv,
                     (void*)st->feed.At, (void*)st->feed.in_ring, (void*)st->s16_stage, (void*)st->d_mem, (void*)st->sc.dev, (void*)st->score_row, (void*)st->al.dev,
-                    (void*)st->peek.keep.p, (void*)st->peek.old.k, (void*)st->peek.old.v}) if (p) (void)hipFree(p);
+                    (void*)st->peek.keep.p, (void*)st->peek.old.k, (void*)st->peek.old.v, (void*)st->rope.dec, (void*)st->rope.enc}) if (p) (void)hipFree(p);
+    if (st->rope.h_dec) (void)hipHostFree(st->rope.h_dec); if (st->rope.h_enc) (void)hipHostFree(st->rope.h_enc);
+    if (st->rope.copied) (void)hipEventDestroy(st->rope.copied);
     binding_release(st->eng);
     delete st;
 }
@@ -3077,17 +3121,35 @@ static int32_t stream_geometry(vox_model* m, int32_t enc_capacity_rows, int32_t 
     return VOX_OK;
 }
 // sample_rate 16000: the 16 kHz stream, nothing more; any other rate: + the input ring and the stream's own block matrix
-static int32_t stream_create(vox_model* m, const float* t_embed, float gain, int32_t enc_capacity_rows, int32_t max_positions, uint32_t sample_rate, vox_stream** out) {
+// endless: max_positions is ignored (the limit is 2^24); dec_ring_rows: the decoder ring's rows (0: the default), checked here
+static int32_t stream_create(vox_model* m, const float* t_embed, float gain, int32_t enc_capacity_rows, int32_t max_positions, uint32_t sample_rate, vox_stream** out,
+                             bool endless = false, int32_t dec_ring_rows = 0) {
     ARGCHK(m && t_embed && out, "null argument"); ARGCHK(std::isfinite(gain), "gain is not finite"); ARGCHK(sample_rate > 0, "bad sample rate 0");
     VOXCHK(ctx_bind(m->ctx));
     ResamplePlan rp; size_t rs_bytes = 0; int in_ring_n = 0;
     if (sample_rate != 16000) VOXCHK(stream_rate_plan(sample_rate, &rp, &rs_bytes, &in_ring_n));
     const vox_model_cfg& c = m->cfg; vox_ctx* cx = m->ctx;
-    StreamGeom g; VOXCHK(stream_geometry(m, enc_capacity_rows, max_positions, INT32_MAX, &g));
+    StreamGeom g; VOXCHK(stream_geometry(m, enc_capacity_rows, endless ? 0 : max_positions, INT32_MAX, &g));
+    int ring_rows = 0;
+    if (endless) {
+        // the ring holds a window, the position itself and the rows a finish / peek tail may overwrite ahead of the session: window + 1 + TAIL.  TAIL bounds
+        // peek_max_ticks -- vox_stream_peek_ids' arithmetic: the backlog of the rate's unfinished block + the right pad -- at this session's rate
+        const int need = c.dec_window + 1 + STREAM_TAIL_TICKS;
+        FeedState f; f.sr = sample_rate; f.rp = rp;
+        int T; VOXCHK(peek_max_ticks(f, c.reshape_factor, 0, "", &T));
+        if (T > STREAM_TAIL_TICKS) return fail(VOX_ERR_UNSUPPORTED, "an endless stream at %u Hz: a finish may run %d ticks, the decoder ring's slack covers %d", sample_rate, T, STREAM_TAIL_TICKS);
+        ARGCHK(c.dec_window >= 0, "an endless session needs a sliding decoder window");
+        ring_rows = dec_ring_rows ? dec_ring_rows : (need + 63) / 64 * 64;
+        ARGCHK(ring_rows >= need, "dec_ring_rows %d: the decoder ring needs at least %d rows (dec_window %d + 1 + %d for a finish / peek tail)", dec_ring_rows, need, c.dec_window, STREAM_TAIL_TICKS);
+        const int most = std::min(m->dec_rope_len, ROPE_ENC_STREAM_TABLE_LEN / c.reshape_factor);
+        ARGCHK(ring_rows <= most, "dec_ring_rows %d: at most %d (up to the wrap the session reads the load-time RoPE tables)", ring_rows, most);
+    }
     VOXCHK(enc_stream_rope_ensure(m));
     vox_stream* st = new vox_stream(); st->m = m; st->ctx = cx; st->t_embed.assign(t_embed, t_embed + c.dec_dim); st->gain = gain; st->cap = g.cap; st->max_pos = g.max_pos; st->RC = g.RC; st->PC = g.PC;
     st->feed.sr = sample_rate; st->feed.rp = rp; st->feed.in_ring_n = in_ring_n; st->left = g.left;
-    const int DD = c.dec_dim, maxp = g.max_pos;
+    st->endless = endless; st->ring_rows = ring_rows; st->dec_limit = endless ? ring_rows : g.max_pos; if (endless) st->max_pos = STREAM_POS_LIMIT;
+    st->lists_cap = endless ? ring_rows : g.max_pos;
+    const int DD = c.dec_dim, maxp = st->lists_cap;
     st->ring_layer = (size_t)c.enc_heads * g.cap * c.enc_head_dim;
     const size_t ring_b = (size_t)c.enc_layers * st->ring_layer * 4, keep_b = (size_t)STREAM_KEEP_ROWS * DD * 4, ws_b = stream_ws_carve(m, 1, nullptr, nullptr) * 4;
     hipError_t e = hipSuccess;
@@ -3096,6 +3158,13 @@ static int32_t stream_create(vox_model* m, const float* t_embed, float gain, int
     A((void**)&st->ws, ws_b); A((void**)&st->tokens, (size_t)(maxp + 2) * 4); A((void**)&st->state, sizeof(int) * STRM_WORDS); A((void**)&st->d_mem, sizeof(StreamMember) + 16);
     if (e == hipSuccess) e = binding_alloc(m, st->eng, &st->bytes);      // (here, not at the first step: the footprint a stream reports does not depend on what it has done)
     if (in_ring_n) A((void**)&st->feed.in_ring, (size_t)in_ring_n * 4);
+    if (endless) {      // the RoPE rings and their pinned host images (stream_rope_refill)
+        const size_t db = (size_t)STREAM_ROPE_DEC_ROWS * c.dec_head_dim * 4, eb = (size_t)STREAM_ROPE_DEC_ROWS * c.reshape_factor * c.enc_head_dim * 4;
+        A((void**)&st->rope.dec, db); A((void**)&st->rope.enc, eb);
+        if (e == hipSuccess) e = hipHostMalloc((void**)&st->rope.h_dec, db, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void**)&st->rope.h_enc, eb, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&st->rope.copied, hipEventDisableTiming);
+    }
     if (e != hipSuccess) { (void)hipGetLastError(); stream_release(st); return fail(VOX_ERR_HIP, "allocating the stream's device state failed: %s", hipGetErrorString(e)); }
     st->d_order = reinterpret_cast<int*>(st->d_mem + 1);
     struct { StreamMember me; int order[4]; } desc{};      // the stream's descriptor never changes; uploaded behind stream_load_initial's synchronisation at the latest
@@ -3115,6 +3184,10 @@ extern "C" int32_t vox_stream_create(vox_model* m, const float* t_embed, float g
 extern "C" int32_t vox_stream_create_rate(vox_model* m, const float* t_embed, float gain, int32_t enc_capacity_rows, int32_t max_positions, uint32_t sample_rate, vox_stream** out) {
     ARGCHK(sample_rate > 0, "bad sample rate 0");
     return stream_create(m, t_embed, gain, enc_capacity_rows, max_positions, sample_rate, out);
+}
+extern "C" int32_t vox_stream_create_endless(vox_model* m, const float* t_embed, float gain, int32_t enc_capacity_rows, int32_t dec_ring_rows, uint32_t sample_rate, vox_stream** out) {
+    ARGCHK(m && t_embed && out, "null argument"); ARGCHK(sample_rate > 0, "bad sample rate 0"); ARGCHK(dec_ring_rows >= 0, "dec_ring_rows %d (0: the default)", dec_ring_rows);
+    return stream_create(m, t_embed, gain, enc_capacity_rows, 0, sample_rate, out, true, dec_ring_rows);
 }
 extern "C" int32_t vox_stream_free(vox_stream* st) { stream_release(st); return VOX_OK; }
 extern "C" int32_t vox_stream_reset(vox_stream* st) {
@@ -3138,15 +3211,17 @@ extern "C" int32_t vox_stream_info(const vox_stream* st, int64_t out[8]) {
 static int32_t stream_decode_step(vox_stream* st, float* h, float* logits_row, int enc_rows) {
     vox_model* m = st->m; hipStream_t s = st->ctx->stream; vox_cache* kc = st->dec;
     if ((st->sc.on || st->al.k > 0) && !logits_row) logits_row = st->score_row;      // a scored step always leaves its logits: in the tap's row, else in the stream's own
-    ARGCHK(kc->len == st->feed.pos && st->feed.pos < kc->max_seq, "internal: stream decoder cache at %d, position %d of %d", kc->len, st->feed.pos, kc->max_seq);
+    const bool ring = stream_in_ring(st);      // (a ring row: the cache is full at ring_rows rows and stays)
+    ARGCHK(kc->len == st->feed.pos && (ring ? kc->max_seq == st->ring_rows : st->feed.pos < kc->max_seq), "internal: stream decoder cache at %d, position %d of %d", kc->len, st->feed.pos, kc->max_seq);
     int* pos_word = st->state + STRM_POS;
-    if (engine_bind(m, st->eng, kc)) {      // one launch: the layers against the stream's cache + final norm + lm_head (argmax partials, logits on request)
+    if (!ring && engine_bind(m, st->eng, kc)) {      // one launch: the layers against the stream's cache + final norm + lm_head (argmax partials, logits on request)
         VOXCHK(engine_take_serials(m, 1, s));
         HIPCHK(launch_decode_engine(engine_params(m, st->eng, kc, h, pos_word, 0, logits_row), s));
         HIPCHK(launch_stream_advance(st->eng.part_val, st->eng.part_idx, 256, st->tokens, st->state, enc_rows, 4 * enc_rows, st->cap, s));
         st->eng_steps++; st->eng_unverified = true;
     } else {
-        VOXCHK(decoder_step_dev(m, h, kc, pos_word, 0));
+        const DecRingStep rs{st->rope.dec, STREAM_ROPE_DEC_ROWS - 1};
+        VOXCHK(decoder_step_dev(m, h, kc, pos_word, 0, ring ? &rs : nullptr));
         VOXCHK(lm_head_argmax_dev(m, h, logits_row));
         HIPCHK(launch_stream_advance(m->d_part_val, m->d_part_idx, m->n_parts, st->tokens, st->state, enc_rows, 4 * enc_rows, st->cap, s));
         st->op_steps++;
@@ -3205,7 +3280,8 @@ static int32_t stream_verify(vox_stream* st) {      // inside a long push: befor
 // The encoder half of a tick for a ROUND of r.n sessions (a solo stream: a round of one): mel -> conv stem -> enc_layers x { RMSNorm, q|k|v, ring attention, wo, RMSNorm,
 // w1|w3, w2 } -> final norm -> adapter, every weight matrix in ONE launch for all sessions of the round (4 n rows through q4_linear_dev, which picks the kernel by the row
 // count).  Slot z works for session r.order[z] (device arrays); w.arow[z] is its adapter row.  ftap_*: a solo stream's front tap (null: none).
-struct StreamRound { const StreamMember* mem; const int* order; int n, cap; size_t ring_layer; MelTables mel; long left; };
+// rope (null: the model's streaming table): a solo endless session's encoder RoPE ring, rows = position & rope_mask (StreamAttnParams::rope_mask)
+struct StreamRound { const StreamMember* mem; const int* order; int n, cap; size_t ring_layer; MelTables mel; long left; const float* rope = nullptr; int rope_mask = 0; };
 static int32_t stream_encode_round(vox_model* m, const StreamWs& w, const StreamRound& r, float* ftap_mel, float* ftap_conv) {
     const vox_model_cfg& c = m->cfg; vox_ctx* cx = m->ctx; hipStream_t s = cx->stream;
     const int D = c.enc_dim, H = c.enc_heads, hd = c.enc_head_dim, QD = H * hd, F = c.enc_ffn, R = c.reshape_factor, DD = c.dec_dim, Cm = c.n_mels, n = r.n, M = R * n;
@@ -3228,7 +3304,8 @@ static int32_t stream_encode_round(vox_model* m, const StreamWs& w, const Stream
         HIPCHK(launch_rms_norm(x, D, M, D, L.attn_norm, nullptr, c.norm_eps, xn, D, s));
         VOXCHK(q4_linear_dev(cx, L.wqkv.w, L.wqkv.bias, xn, D, M, w.qkv, 3 * QD));
         StreamAttnParams ap{}; ap.qkv = w.qkv; ap.qkv_stride = 3 * QD; ap.mem = r.mem; ap.order = r.order; ap.n = n; ap.ring_off = (size_t)l * r.ring_layer; ap.cap = r.cap;
-        ap.cos_t = m->enc_cos_s; ap.sin_t = m->enc_sin_s; ap.out = w.att; ap.out_stride = QD; ap.M = R; ap.n_heads = H; ap.window = c.enc_window;
+        ap.cos_t = m->enc_cos_s; ap.sin_t = m->enc_sin_s; ap.out = w.att;
+        if (r.rope) { ap.cos_t = r.rope; ap.sin_t = r.rope + hd / 2; ap.rope_mask = r.rope_mask; } ap.out_stride = QD; ap.M = R; ap.n_heads = H; ap.window = c.enc_window;
         HIPCHK(launch_stream_attn(ap, hd, s));
         VOXCHK(q4_linear_dev(cx, L.wo.w, L.wo.bias, w.att, QD, M, x, D, EPI_RESID, x, D));
         HIPCHK(launch_rms_norm(x, D, M, D, L.ffn_norm, nullptr, c.norm_eps, xn, D, s));
@@ -3241,13 +3318,61 @@ static int32_t stream_encode_round(vox_model* m, const StreamWs& w, const Stream
     return VOX_OK;
 }
 
+// An endless session's position-indexed device lists -- the tokens, and the score and alternatives records it has -- are full: twice the positions (at most the
+// session's limit), behind a verification (nothing unverified refers to the old arrays), the descriptor pointed at the new ones behind a synchronisation.  They GROW BY
+// DOUBLING and are never trimmed: vox_stream_info[5] counts them as they are.
+static int32_t stream_lists_grow(vox_stream* st) {
+    hipStream_t s = st->ctx->stream;
+    VOXCHK(stream_verify(st));
+    const int rows = (int)std::min<int64_t>(2LL * st->lists_cap, st->max_pos);
+    ARGCHK(rows > st->lists_cap, "internal: the stream's lists of %d positions cannot grow", st->lists_cap);
+    const uint64_t had = st->sc.bytes() + st->al.bytes();
+    int tcap = st->lists_cap + 2;
+    VOXCHK(list_grow((void**)&st->tokens, &tcap, rows + 2, 4, s)); st->bytes += (uint64_t)(rows - st->lists_cap) * 4;
+    if (st->sc.dev) VOXCHK(st->sc.grow(rows + 2, s));
+    if (st->al.dev) VOXCHK(st->al.grow(rows + 2, s));
+    st->bytes += st->sc.bytes() + st->al.bytes() - had; st->lists_cap = rows;
+    struct { int* tok; TokenScore* sp; int scap; TokenAlts* ap; int acap; } w{st->tokens, st->sc.on ? st->sc.dev : nullptr, st->sc.on ? st->sc.cap : 0, st->al.k > 0 ? st->al.dev : nullptr, st->al.k > 0 ? st->al.cap : 0};
+    HIPCHK(hipMemcpyAsync(&st->d_mem->tokens, &w.tok, sizeof w.tok, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(&st->d_mem->scores, &w.sp, sizeof w.sp, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(&st->d_mem->scores_cap, &w.scap, sizeof w.scap, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(&st->d_mem->alts, &w.ap, sizeof w.ap, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(&st->d_mem->alts_cap, &w.acap, sizeof w.acap, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return VOX_OK;
+}
+// An endless session's RoPE rows for the n ticks a pass is about to run from position pos0 (some of them at or past the wrap): decoder rows pos0 .. pos0 + n - 1 into row
+// position & mask of the decoder ring, the R n encoder rows of those ticks likewise -- made by rope_rows_fill, the tables' own function, in the rings' pinned host
+// images and copied with one hipMemcpyAsync per ring (two where the span wraps), in stream order in front of the pass's ticks.
+static int32_t stream_rope_refill(vox_stream* st, int pos0, int n) {
+    const vox_model_cfg& c = st->m->cfg; hipStream_t s = st->ctx->stream; const int R = c.reshape_factor;
+    ARGCHK(n >= 1 && n <= STREAM_ROPE_DEC_ROWS, "internal: a pass of %d ticks, the RoPE rings hold %d", n, STREAM_ROPE_DEC_ROWS);
+    // The host images are pinned, so a copy out of them runs when the stream gets to it, long after hipMemcpyAsync has returned -- and positions one ring length apart
+    // share a row.  The images must not be rewritten while the last pass's copy may still be in flight: wait for THAT copy (its event, recorded right behind it), not
+    // for the ticks queued behind it.  The host so runs at most one pass ahead of the copies.
+    if (st->rope.pending) { HIPCHK(hipEventSynchronize(st->rope.copied)); st->rope.pending = false; }
+    auto fill = [&](float* host, float* dev, int rows, int hd, int64_t first, int cnt, int64_t table_len) -> int32_t {
+        const int half = hd / 2; const int64_t mask = rows - 1;
+        for (int i = 0; i < cnt; i++) { float* row = host + (size_t)((first + i) & mask) * hd; rope_rows_fill(hd, c.rope_theta, first + i, 1, table_len, nullptr, row, row + half); }
+        const int r0 = (int)(first & mask), k = std::min(cnt, rows - r0);
+        HIPCHK(hipMemcpyAsync(dev + (size_t)r0 * hd, host + (size_t)r0 * hd, (size_t)k * hd * 4, hipMemcpyHostToDevice, s));
+        if (cnt > k) HIPCHK(hipMemcpyAsync(dev, host, (size_t)(cnt - k) * hd * 4, hipMemcpyHostToDevice, s));      // the span wrapped
+        return VOX_OK;
+    };
+    VOXCHK(fill(st->rope.h_dec, st->rope.dec, STREAM_ROPE_DEC_ROWS, c.dec_head_dim, pos0, n, ROPE_DEC_TABLE_LEN));
+    VOXCHK(fill(st->rope.h_enc, st->rope.enc, STREAM_ROPE_DEC_ROWS * R, c.enc_head_dim, (int64_t)st->RC + (int64_t)R * (pos0 - st->PC), R * n, ROPE_ENC_STREAM_TABLE_LEN));
+    HIPCHK(hipEventRecord(st->rope.copied, s)); st->rope.pending = true;
+    return VOX_OK;
+}
+
 // a solo stream's tick: the round of one, then its own decode half -- the engine launch or the per-operator step, with the kept adapter rows behind the re-run
 static int32_t stream_tick(vox_stream* st) {
     vox_model* m = st->m; const vox_model_cfg& c = m->cfg; hipStream_t s = st->ctx->stream; const int R = c.reshape_factor;
     if (st->feed.pos - st->verified_pos >= STREAM_KEEP_ROWS) VOXCHK(stream_verify(st));      // the kept adapter rows cover the unverified steps
-    if (st->feed.pos >= st->dec->max_seq) { VOXCHK(stream_verify(st)); VOXCHK(stream_dec_grow(st, st->peek.active ? &st->peek.old : nullptr)); }
+    const bool ring = stream_in_ring(st);      // from the wrap on the cache stays as it is: position p lives at row p % ring_rows
+    if (!ring && st->feed.pos >= st->dec->max_seq) { VOXCHK(stream_verify(st)); VOXCHK(stream_dec_grow(st, st->peek.active ? &st->peek.old : nullptr)); }
+    if (st->endless && st->feed.pos >= st->lists_cap) VOXCHK(stream_lists_grow(st));      // (a bounded session's lists hold its max_pos positions)
     StreamWs w; stream_ws_carve(m, 1, st->ws, &w);
-    const StreamRound r{st->d_mem, st->d_order, 1, st->cap, st->ring_layer, st->mel, st->left};
+    StreamRound r{st->d_mem, st->d_order, 1, st->cap, st->ring_layer, st->mel, st->left};
+    if (ring) { r.rope = st->rope.enc; r.rope_mask = STREAM_ROPE_DEC_ROWS * R - 1; }
     const int k = st->ftap_mel ? st->ftap_ticks++ : 0; const bool ftap = st->ftap_mel && k < st->ftap_max;      // (a re-run repeats decode steps, never a tick)
     VOXCHK(stream_encode_round(m, w, r, ftap ? st->ftap_mel + (size_t)k * 4 * R * c.n_mels : nullptr, ftap ? st->ftap_conv + (size_t)k * R * c.enc_dim : nullptr));
     HIPCHK(launch_stream_embed(m->tok.w, st->tokens, w.arow, st->audio_keep, STREAM_KEEP_ROWS, c.dec_dim, st->state, w.h, s));
@@ -3325,6 +3450,7 @@ static int32_t stream_run(vox_stream* st, const StreamSrc& src, FeedPlan& plan, 
         if (rate) HIPCHK(launch_stream_resample(f.in_ring, f.in_ring_n - 1, (long)f.in_written, f.At, (int)f.rp.fft_in, (int)f.rp.fft_out, (int)f.rp.delay, st->samples, STREAM_SAMPLE_RING - 1,
                                                 (long)q.i0, (int)q.n16, s));
         VOXCHK(ring_write_f32(s, st->samples, STREAM_SAMPLE_RING, q.pad_w0, StreamSrc{}, 0, q.pad));
+        if (st->endless && q.ticks > 0 && f.pos + q.ticks > st->ring_rows) VOXCHK(stream_rope_refill(st, f.pos, q.ticks));      // the pass reaches the ring: its RoPE rows first
         for (int t = 0; t < q.ticks; t++) VOXCHK(stream_tick(st));
     }
     SessionOut o{&f, &st->sc, &st->al, st->tokens, out_ids, due, peek, peek_scores};
@@ -3347,6 +3473,9 @@ struct StreamMark { FeedState::Mark feed; int tap_rows, ftap_ticks; uint64_t eng
 static int32_t stream_peek(vox_stream* st, FeedPlan& plan, int32_t* out_ids, int32_t* n_ids, vox_token_score* scores) {
     vox_model* m = st->m; const vox_model_cfg& c = m->cfg; hipStream_t s = st->ctx->stream; FeedState& f = st->feed;
     int T; VOXCHK(peek_max_ticks(f, c.reshape_factor, plan.due, "", &T));
+    // An endless session past its wrap needs no decoder save: the tail's T ticks overwrite ring rows (pos .. pos + T - 1) % ring_rows, which held positions at most
+    // pos + T - 1 - ring_rows < pos - dec_window -- outside the window of every later position.  That is what the ring's TAIL rows of slack buy
+    ARGCHK(!st->endless || (T <= STREAM_TAIL_TICKS && st->ring_rows >= c.dec_window + 1 + T), "internal: a peek of %d ticks against a decoder ring with %d rows of slack", T, st->ring_rows - c.dec_window - 1);
     const int rows = std::min(st->cap, c.reshape_factor * T);      // (a function of the stream's rate and capacity: the area is reserved once)
     VOXCHK(keep_reserve(st->peek.keep, stream_keep_floats(c.enc_layers, c.enc_heads, c.enc_head_dim, rows), &st->bytes, s, "stream"));
     if (m->pw_pend_rows > 0) VOXCHK(pw_sync(m));
@@ -3411,7 +3540,7 @@ extern "C" int32_t vox_stream_set_scores(vox_stream* st, int32_t on) {
     hipStream_t s = st->ctx->stream; ScoreState& sc = st->sc;
     if (on) {      // the first on: the records, and the stream's own logits row
         const size_t had = sc.bytes();
-        VOXCHK(sc.alloc(st->max_pos, "the stream's")); st->bytes += sc.bytes() - had;
+        VOXCHK(sc.alloc(st->lists_cap, "the stream's")); st->bytes += sc.bytes() - had;
         VOXCHK(stream_own_row(st));
     }
     HIPCHK(hipStreamSynchronize(s));
@@ -3433,7 +3562,7 @@ extern "C" int32_t vox_stream_set_alternatives(vox_stream* st, int32_t k) {
     hipStream_t s = st->ctx->stream; AltsState& al = st->al;
     if (k > 0) {
         const size_t had = al.bytes();
-        VOXCHK(al.alloc(st->max_pos, "the stream's")); st->bytes += al.bytes() - had;
+        VOXCHK(al.alloc(st->lists_cap, "the stream's")); st->bytes += al.bytes() - had;
         VOXCHK(stream_own_row(st));
     }
     HIPCHK(hipStreamSynchronize(s));

@@ -175,3 +175,16 @@ extern "C" int32_t vox_debug_stream_feed_passes(uint32_t sample_rate, const size
     *n_rows = k;
     return VOX_OK;
 }
+
+// ---- debug: RoPE rows on their own (tests/test_stream_endless_cpu.py).  No device: rope_rows_fill (vox_host_base.h), the function behind every RoPE table, for rows
+// first_pos .. first_pos + n - 1.  head_dim 128 is the decoder's geometry (its load-time table has 16 384 rows), any other the encoder's (the streaming encoder's
+// table has 65 536): below that length a row has the table's bits, from there on the double-precision angle.
+extern "C" int32_t vox_debug_rope_rows(int32_t head_dim, float theta, int64_t first_pos, int32_t n, float* inv_out, float* cos_out, float* sin_out) {
+    ARGCHK(inv_out && cos_out && sin_out, "null argument");
+    ARGCHK(head_dim >= 2 && head_dim <= 256 && head_dim % 2 == 0, "head_dim %d out of range (even, 2..256)", head_dim);
+    ARGCHK(std::isfinite(theta) && theta > 1.0f, "theta %g must be finite and above 1", (double)theta);
+    ARGCHK(n >= 0 && n <= (1 << 20), "%d rows out of range (0..%d)", n, 1 << 20);
+    ARGCHK(first_pos >= 0 && first_pos + n <= ((int64_t)1 << 24), "rows %lld .. %lld: positions end at 2^24", (long long)first_pos, (long long)(first_pos + n));
+    rope_rows_fill(head_dim, theta, first_pos, n, head_dim == 128 ? ROPE_DEC_TABLE_LEN : ROPE_ENC_STREAM_TABLE_LEN, inv_out, cos_out, sin_out);
+    return VOX_OK;
+}

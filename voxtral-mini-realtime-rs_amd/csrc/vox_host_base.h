@@ -23,6 +23,27 @@ namespace vox_host {
 #define ARGCHK(cond, ...) do { if (!(cond)) return fail(VOX_ERR_INVALID, __VA_ARGS__); } while (0)
 
 struct ResamplePlan { long fft_in = 0, fft_out = 0, new_len = 0, delay = 0; float cutoff = 0.f; };
+
+// RoPE rows (models/layers/rope.rs:35-64), the ONE implementation: the load-time tables (vox_model.cpp), the streaming encoder's table (vox_api.cpp) and
+// vox_debug_rope_rows are filled here.  Rows first .. first + n - 1 of cos / sin [n][hd / 2] (either may be null); inv (hd / 2 floats, may be null): the f32 factors.
+// Positions below table_len take the tables' formula -- the f32 product pos * inv, then f32 cos / sin: the bits every table has had.  From table_len on the angle is
+// double(pos) * double(inv), cos / sin in double, rounded to f32: the f32 product loses the angle at large positions (its spacing is about 0.5 rad at 4 M).
+inline const int ROPE_DEC_TABLE_LEN = 16384, ROPE_ENC_STREAM_TABLE_LEN = 1 << 16;
+inline void rope_rows_fill(int hd, float theta, int64_t first, int64_t n, int64_t table_len, float* inv_out, float* cos_out, float* sin_out) {
+    const int half = hd / 2;
+    for (int j = 0; j < half && inv_out; j++) inv_out[j] = 1.0f / std::pow(theta, (float)(2 * j) / (float)hd);
+    for (int64_t r = 0; r < n; r++) {
+        const int64_t i = first + r;
+        for (int j = 0; j < half; j++) {
+            const float inv = 1.0f / std::pow(theta, (float)(2 * j) / (float)hd);
+            float cv, sv;
+            if (i < table_len) { const float fr = (float)i * inv; cv = std::cos(fr); sv = std::sin(fr); }
+            else { const double fr = (double)i * (double)inv; cv = (float)std::cos(fr); sv = (float)std::sin(fr); }
+            if (cos_out) cos_out[(size_t)r * half + j] = cv;
+            if (sin_out) sin_out[(size_t)r * half + j] = sv;
+        }
+    }
+}
 }  // namespace vox_host
 
 struct GTensor { std::string name; uint32_t ndims = 0; uint64_t dims[4] = {0, 0, 0, 0}; uint32_t dtype = 0; uint64_t offset = 0, nbytes = 0; };

@@ -33,7 +33,10 @@ enum WFmt { WFMT_Q4_0 = 0, WFMT_BF16 = 1, WFMT_BF16X2 = 2, WFMT_F32 = 3 };
 
 enum Epi { EPI_STORE = 0, EPI_RESID = 1, EPI_SWIGLU = 2, EPI_ROPE_KV = 3, EPI_ARGMAX = 4, EPI_GELU = 5, EPI_SWIGLU_XF = 6, EPI_RESID_XF = 7,
            EPI_ROPE_ROWS = 8,        // launch_q4_gemm only: store, with RoPE (interleaved pairs, rope.rs:77-141) on the first n_q columns, row m at position pos[m] (or m % rope_seq_rows, or m) -- the encoder's q|k|v operator
-           EPI_ROPE_KV_PAGED = 9 };  // inside launch_q4_skinny only: EPI_ROPE_KV with GemmParams::kv_pos set runs as this instantiation
+           EPI_ROPE_KV_PAGED = 9,    // inside launch_q4_skinny only: EPI_ROPE_KV with GemmParams::kv_pos set runs as this instantiation
+           EPI_ROPE_KV_RING = 10 };  // launch_q4_gemv only (Q4 weights): EPI_ROPE_KV on a cache used as a RING of cache_head_stride / hd rows per KV head -- k / v go to cache row
+                                     // pos % that -- with the RoPE row read from a session's RoPE ring: row pos & rope_mask of [rope_mask + 1][cos hd/2 | sin hd/2] (rope_cos = the ring,
+                                     // rope_sin = the ring + hd / 2: rows are hd floats apart, not hd / 2).  An epilogue instantiation of its own: EPI_ROPE_KV compiles as it did
 // (M <= 16 only) _SWIGLU_XF: SwiGLU written as XF planes; _RESID_XF: out = acc + resid as f32 AND as XF planes of out * xf_w (* xf_w2) plus
 // per-workgroup partial sums of squares -- the next RMSNorm is folded into its producer and its consumer (GemmParams::ssq_part)
 enum Pro { PRO_NONE = 0, PRO_RMS = 1, PRO_RMS_MUL = 2,      // RMS_MUL: RMSNorm then * mul (the cached Ada scale)
@@ -55,6 +58,7 @@ struct GemvParams {
     float* kcache; float* vcache; int cache_head_stride;    // [kv_head][max_seq][hd]
     float* part_val; int* part_idx;      // EPI_ARGMAX: per-workgroup (max, argmax)
     int tl_slot;                         // timeline slot (measurement builds, -DVOX_TIMELINE; assigned by the launcher, -1 = off)
+    int rope_mask;                       // EPI_ROPE_KV_RING: rows of the RoPE ring - 1 (a power of two - 1)
 };
 // rows_per_wave R in {1,2,4,8}; K tiles of 2048 chosen from K. Returns hipError_t.
 hipError_t launch_q4_gemv(const GemvParams& p, int n_rows_x, int pro, int epi, int R, hipStream_t s);
@@ -180,6 +184,10 @@ bool attn_decode_takes_gqa(int hd, int n_heads, int n_kv_heads);
 hipError_t attn_decode_gqa_max_seq(int* out);
 // the same attention with K / V read through a page table: the GQA form where n_heads == 4 n_kv_heads and hd == 128, else the per-head form; a row has launch_attn_decode's bits
 hipError_t launch_attn_decode_paged(const AttnParams& p, int hd, hipStream_t s, int n_seq);
+// the same attention on a cache used as a RING of `cap` rows per KV head ([kv head][cap][hd]; kv_head_stride = cap * hd, kv_row_stride = hd): row j of a sequence lives
+// at ring row j % cap, positions are not bound by cap; window >= 0 and window + 1 <= cap (hipErrorInvalidValue otherwise, nothing launched).  The per-head kernel with
+// the ring row policy: a row has launch_attn_decode's bits
+hipError_t launch_attn_decode_ring(const AttnParams& p, int hd, int cap, hipStream_t s, int n_seq = 1);
 // single sequence: attention + the wo linear in one launch; acc[wo.N] (int64, zero on entry) receives the product in 2^-32 fixed point (consumer: PRO_RMS_MUL_SUM)
 bool attn_wo_supported(const AttnParams& p, const Q4W& wo, int hd, int max_seq);
 hipError_t launch_attn_wo(const AttnParams& p, const Q4W& wo, long long* acc, int max_seq, hipStream_t s);
@@ -188,6 +196,7 @@ hipError_t launch_attn_wo(const AttnParams& p, const Q4W& wo, long long* acc, in
 enum AttnForm { ATTN_FORM_PREFILL_SMALL, ATTN_FORM_PREFILL_MFMA, ATTN_FORM_PREFILL_F32, ATTN_FORM_DECODE, ATTN_FORM_DECODE_SPEC, ATTN_FORM_DECODE_GQA, ATTN_FORM_WO,
                 ATTN_FORM_ENGINE, ATTN_FORM_STREAM_RING, ATTN_FORM_GROUP_RESAMPLE, ATTN_FORM_STREAM_RESAMPLE,
                 ATTN_FORM_DECODE_PAGED, ATTN_FORM_DECODE_GQA_PAGED,      // the paged decode forms (launch_attn_decode_paged), behind every earlier slot
+                ATTN_FORM_DECODE_RING,                                   // the ring decode form (launch_attn_decode_ring)
                 ATTN_FORM_COUNT };
 void attn_form_note(AttnForm f);
 void attn_form_counts(unsigned long long out[ATTN_FORM_COUNT]);
@@ -436,6 +445,8 @@ struct StreamAttnParams {
     const float* cos_t; const float* sin_t;  // [positions][hd / 2]
     float* out; int out_stride;              // [n M][n_heads * hd]
     int M, n_heads, window;
+    int rope_mask;                           // 0 (the default): cos_t / sin_t are tables, row = the position.  > 0 (an endless session past its wrap): cos_t is a RoPE ring of
+                                             // rope_mask + 1 rows [cos hd/2 | sin hd/2] (sin_t = cos_t + hd / 2), row = position & rope_mask, refilled by the host for the tick's positions
 };
 hipError_t launch_stream_attn(const StreamAttnParams& p, int hd, hipStream_t s);
 // rows 0 .. rows-1 of every layer's ring from token-major k | v rows (the model's prefix state: [layers][rows][k row | v row])

@@ -239,6 +239,15 @@ struct KvRowsPaged {      // kb / vb: the layer's pool + the KV head's offset in
     __device__ __forceinline__ const float* k(int j) const { return kb + at(j); }
     __device__ __forceinline__ const float* v(int j) const { return vb + at(j); }
 };
+// Ring rows (an endless session's decoder cache, launch_attn_decode_ring): logical row j lives at ring row j % cap.  Built once per workgroup from the ring row of the
+// window's first key (r_lo = j_lo % cap: the only division); a window holds at most cap keys, so every key of it is r_lo + (j - j_lo) less at most one cap -- no
+// division per key.  Called with j_lo <= j < j_lo + cap alone (attn_decode_core asks for the window's rows and nothing else).
+struct KvRowsRing {
+    const float* kb; const float* vb; int r_lo, j_lo, cap, stride;
+    __device__ __forceinline__ size_t at(int j) const { int t = r_lo + (j - j_lo); t -= t >= cap ? cap : 0; return (size_t)t * stride; }
+    __device__ __forceinline__ const float* k(int j) const { return kb + at(j); }
+    __device__ __forceinline__ const float* v(int j) const { return vb + at(j); }
+};
 template <int HD, bool NT, bool LATE_V, bool SPEC = false, class Hook = NoHook, class Rows = KvRowsFlat>
 __device__ __forceinline__ float4 attn_decode_core(const float* __restrict__ qh, const Rows rows,
                                                    int pos, int window, float* __restrict__ sc, float* __restrict__ red, float4* __restrict__ osum, int tl_slot, int tlw,
@@ -370,8 +379,10 @@ __global__ __launch_bounds__(64 * NWV, 1) void q4_gemv_kernel(const GemvParams p
     const float rstd = PRO != PRO_NONE ? 1.0f / sqrtf(ssq / (float)K + p.eps) : 1.0f;
 
     int best_i = 0x7fffffff; float best = -INFINITY;   // EPI_ARGMAX running (max, first index) of this wave
-    constexpr bool ROPE = EPI == EPI_ROPE_KV;
+    constexpr bool RINGE = EPI == EPI_ROPE_KV_RING, ROPE = EPI == EPI_ROPE_KV || RINGE;
     const int pos = ROPE ? (p.pos_ptr ? *p.pos_ptr : 0) + p.pos_off : 0;
+    // EPI_ROPE_KV_RING: the cache row and the RoPE row of the position, once per workgroup (the flat form: both are the position, the table's rows hd / 2 floats apart)
+    const int crow = RINGE ? pos % (p.cache_head_stride / p.hd) : pos, prow = RINGE ? (pos & p.rope_mask) : pos, pstride = RINGE ? p.hd : p.hd >> 1;
 
     // (4)+(5) consume one row group from registers (Q_, D_) and run its epilogue
 #define VOX_GROUP(Q_, D_, G_)                                                                                          \
@@ -409,23 +420,23 @@ __global__ __launch_bounds__(64 * NWV, 1) void q4_gemv_kernel(const GemvParams p
                 if (lane == (r >> 1)) p.out[(size_t)y * p.out_stride + (n >> 1)] = silu_f(acc[r]) * acc[r + 1];        \
             }                                                                                                          \
         } else if (ROPE) { /* [wq|wk|wv]: RoPE pairs (rope.rs:99-141), k/v into the cache slot */                      \
-            const int hd = p.hd, half = hd >> 1;                                                                       \
+            const int hd = p.hd;                                                                                       \
             _Pragma("unroll") for (int r = 0; r + 1 < R; r += 2) {                                                     \
                 const int n = row0 + r;                                                                                \
                 if (lane == (r >> 1)) {                                                                                \
                     const float a = acc[r], b = acc[r + 1];                                                            \
                     if (n < p.n_q + p.n_k) {                                                                           \
                         const int dd = n % hd;                                                                         \
-                        const float c = p.rope_cos[(size_t)pos * half + (dd >> 1)], sn = p.rope_sin[(size_t)pos * half + (dd >> 1)]; \
+                        const float c = p.rope_cos[(size_t)prow * pstride + (dd >> 1)], sn = p.rope_sin[(size_t)prow * pstride + (dd >> 1)]; \
                         const float ra = a * c - b * sn, rb = a * sn + b * c;                                          \
                         if (n < p.n_q) st_pair(p.out + n, ra, rb);                                                 \
                         else {                                                                                         \
                             const int kn = n - p.n_q, kh = kn / hd;                                                    \
-                            st_pair(p.kcache + (size_t)kh * p.cache_head_stride + (size_t)pos * hd + dd, ra, rb);  \
+                            st_pair(p.kcache + (size_t)kh * p.cache_head_stride + (size_t)crow * hd + dd, ra, rb);  \
                         }                                                                                              \
                     } else {                                                                                           \
                         const int vn = n - p.n_q - p.n_k, vh = vn / hd, dd = vn % hd;                                  \
-                        st_pair(p.vcache + (size_t)vh * p.cache_head_stride + (size_t)pos * hd + dd, a, b);        \
+                        st_pair(p.vcache + (size_t)vh * p.cache_head_stride + (size_t)crow * hd + dd, a, b);        \
                     }                                                                                                  \
                 }                                                                                                      \
             }                                                                                                          \
@@ -517,7 +528,7 @@ static inline int passes_for(int K, int R) { return (R * (K / 32) + 63) / 64; }
 
 // rows per wave. Prefers the R that fills every pass exactly (R*nb % 64 == 0).
 int q4_gemv_default_R(int N, int K, int epi) {
-    const bool pair = (epi == EPI_SWIGLU || epi == EPI_ROPE_KV);
+    const bool pair = (epi == EPI_SWIGLU || epi == EPI_ROPE_KV || epi == EPI_ROPE_KV_RING);
     const int nb = K / 32;
     const int order_exact[3] = {pair ? 2 : 1, pair ? 4 : 2, 4};
     for (int i = 0; i < 3; i++) {   // exact fit, unless it needs so many passes that the register file halves occupancy
@@ -539,7 +550,7 @@ int dense_gemv_grid(int N);
 // vector is long or the kernel is long enough to amortise the bigger barrier -- wo (K = 4096) 4.93 -> 4.68 us, w2 (K = 9216) 8.31 -> 7.89 us,
 // w1|w3 9.58 -> 9.25 us -- and lose on q|k|v (RoPE / cache epilogue; 6.08 -> 6.16) and lm_head (38.9 -> 41.1).
 int q4_gemv_nwv(int K, int epi) {
-    if (epi == EPI_ARGMAX || epi == EPI_ROPE_KV) return 4;
+    if (epi == EPI_ARGMAX || epi == EPI_ROPE_KV || epi == EPI_ROPE_KV_RING) return 4;
     return (K >= 4096 || epi == EPI_SWIGLU) ? 12 : 4;
 }
 static int q4_gemv_grid_w(int N, int R, int nwv) {
@@ -596,6 +607,10 @@ static hipError_t gemv_dispatch_pe(const GemvParams& p, int ny, int pro, int epi
         if (pro == PRO_RMS_MUL_SUM && epi == EPI_SWIGLU && P == 3 && R == 2) return gemv_launch_t<3, 2, PRO_RMS_MUL_SUM, EPI_SWIGLU>(p, ny, s);
         if (pro == PRO_NONE && epi == EPI_SWIGLU) return gemv_launch_t<P, R2, PRO_NONE, EPI_SWIGLU>(p, ny, s);
         if (pro == PRO_RMS && epi == EPI_ROPE_KV) return gemv_launch_t<P, R2, PRO_RMS, EPI_ROPE_KV>(p, ny, s);
+        if (pro == PRO_RMS && epi == EPI_ROPE_KV_RING) {      // the ring append: a ring of whole rows, a RoPE ring of a power of two rows, one input row
+            if (ny != 1 || p.hd < 2 || p.cache_head_stride < p.hd || p.cache_head_stride % p.hd || p.rope_mask < 0 || (p.rope_mask & (p.rope_mask + 1)) || !p.pos_ptr) return hipErrorInvalidValue;
+            return gemv_launch_t<P, R2, PRO_RMS, EPI_ROPE_KV_RING>(p, ny, s);
+        }
     }
 #undef VOX_CASE
     return hipErrorInvalidValue;
@@ -603,6 +618,7 @@ static hipError_t gemv_dispatch_pe(const GemvParams& p, int ny, int pro, int epi
 
 hipError_t launch_q4_gemv(const GemvParams& p_in, int ny, int pro, int epi, int R, hipStream_t s) {
     GemvParams p = p_in; p.tl_slot = tl_take_slot(0, epi, p.w.N, p.w.K);
+    if ((p.w.fmt == WFMT_BF16 || p.w.fmt == WFMT_F32) && epi == EPI_ROPE_KV_RING) return hipErrorInvalidValue;      // (live sessions serve Q4 models)
     if (p.w.fmt == WFMT_BF16 || p.w.fmt == WFMT_F32) return launch_dense_gemv(p, ny, pro, epi, s);
     if (p.w.K % 32 || p.w.K <= 0 || p.w.N <= 0 || R <= 0 || p.w.N % R) return hipErrorInvalidValue;
     const int P = passes_for(p.w.K, R);
@@ -3374,10 +3390,13 @@ __device__ __forceinline__ float4 attn_decode_core(const float* __restrict__ qh,
     return r4;
 }
 
-template <int HD, bool SPEC>
+// RING (launch_attn_decode_ring): the KV head's rows are a ring of kv_head_stride / kv_row_stride rows, logical row j at ring row j % that (KvRowsRing); the position
+// may be any value.  The arithmetic depends on the logical key index alone: the flat kernel's scan order and reduction trees, the same bits.
+template <int HD, bool SPEC, bool RING = false>
 __global__ __launch_bounds__(256) void attn_decode_kernel(const AttnParams p) {
+    static_assert(!(SPEC && RING), "speculative rows are rows 0 .. 159 of a flat cache");
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* sc = smem;                 // scores / probabilities, up to max_seq
+    float* sc = smem;                 // scores / probabilities, up to max_seq (RING: up to window + 1)
     __shared__ float red[8];
     __shared__ float4 osum[256];
     const int tid = threadIdx.x, wave = tid >> 6;
@@ -3407,7 +3426,11 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const AttnParams p) {
     float* orow = p.out + (size_t)seq * p.out_seq_stride;
     const int tlw = (blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave; (void)tlw;
     VOX_TL(p.tl_slot, tlw, 0);
-    const float4 r4 = attn_decode_core<HD, false, false, SPEC>(qrow + h * HD, KvRowsFlat{kb, vb, p.kv_row_stride}, pos, p.window, sc, red, osum, p.tl_slot, tlw, p.spec_rows);
+    float4 r4;
+    if constexpr (RING) {
+        const int cap = p.kv_head_stride / p.kv_row_stride, j_lo = max(0, pos - p.window);      // (the launcher: window >= 0, window + 1 <= cap)
+        r4 = attn_decode_core<HD, false, false, false, NoHook, KvRowsRing>(qrow + h * HD, KvRowsRing{kb, vb, j_lo % cap, j_lo, cap, p.kv_row_stride}, pos, p.window, sc, red, osum, p.tl_slot, tlw, 0);
+    } else r4 = attn_decode_core<HD, false, false, SPEC>(qrow + h * HD, KvRowsFlat{kb, vb, p.kv_row_stride}, pos, p.window, sc, red, osum, p.tl_slot, tlw, p.spec_rows);
     if (tid < HD / 4) {
         if (p.out_xf) xf_store4(p.out_xf + (size_t)(seq >> 4) * p.out_xf_gstride, p.n_heads * HD, seq & 15, h * HD + tid * 4, r4);       // batched decode: A-fragments of the wo GEMM
         else *reinterpret_cast<float4*>(orow + h * HD + tid * 4) = r4;
@@ -3732,6 +3755,29 @@ hipError_t launch_attn_decode(const AttnParams& p_in, int hd, int max_seq, hipSt
         kern<<<dim3(p.n_heads, n_seq), dim3(256), lds, s>>>(p);
         attn_form_note(ATTN_FORM_DECODE);
     } else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+// the ring form: the per-head kernel on a head-major cache of `cap` rows per KV head used as a ring (row j of a sequence at ring row j % cap); positions are not bound
+// by cap.  A window is required and fits the ring (window + 1 <= cap): a key outside it may have been overwritten.  Scores: window + 1 LDS rows.
+hipError_t launch_attn_decode_ring(const AttnParams& p_in, int hd, int cap, hipStream_t s, int n_seq) {
+    AttnParams p = p_in; p.tl_slot = tl_take_slot(1, 0, p.n_heads, hd); p.spec_rows = 0;
+    if (!p.pos_ptr || cap < 1 || p.window < 0 || p.window + 1 > cap || p.kv_row_stride != hd || p.kv_head_stride != cap * hd || p.n_kv_heads < 1 || p.n_heads % p.n_kv_heads || n_seq < 1)
+        return hipErrorInvalidValue;
+    const size_t lds = (size_t)(p.window + 1) * sizeof(float);
+    if (hd == 128) {
+        auto kern = attn_decode_kernel<128, false, true>;
+        static DevOnce attr_done;
+        hipError_t e = ensure_dyn_lds(kern, lds, &attr_done);
+        if (e != hipSuccess) return e;
+        kern<<<dim3(p.n_heads, n_seq), dim3(256), lds, s>>>(p);
+    } else if (hd == 64) {
+        auto kern = attn_decode_kernel<64, false, true>;
+        static DevOnce attr_done;
+        hipError_t e = ensure_dyn_lds(kern, lds, &attr_done);
+        if (e != hipSuccess) return e;
+        kern<<<dim3(p.n_heads, n_seq), dim3(256), lds, s>>>(p);
+    } else return hipErrorInvalidValue;
+    attn_form_note(ATTN_FORM_DECODE_RING);
     return hipGetLastError();
 }
 // the paged forms: launch_attn_decode's choice between the GQA and the per-head kernel for a stream group's step (prefer_gqa, no speculative rows), on the page pool
@@ -4491,7 +4537,7 @@ __global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_attn_kernel(const St
     const int enc_pos = me.state[STRM_ENC_POS], qpos = enc_pos + m, QD = p.n_heads * HD;
     for (int i = tid; i < (m + 2) * HALF; i += 256) {      // k rows 0 .. m, then the query row
         const int r = i / HALF, j = i - r * HALF; const bool isq = r == m + 1; const int row = isq ? m : r;
-        const size_t ti = (size_t)(enc_pos + row) * HALF + j;
+        const size_t ti = p.rope_mask ? (size_t)((enc_pos + row) & p.rope_mask) * HD + j : (size_t)(enc_pos + row) * HALF + j;      // (a RoPE ring's rows: cos | sin, HD floats apart)
         const float c = p.cos_t[ti], sn = p.sin_t[ti];
         const float* src = qkv + (size_t)row * p.qkv_stride + (isq ? 0 : QD) + h * HD + 2 * j;
         const float xr = src[0], xi = src[1];
@@ -4550,7 +4596,8 @@ __global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_attn_kernel(const St
 }
 hipError_t launch_stream_attn(const StreamAttnParams& p, int hd, hipStream_t s) {
     // (the ring rows are read as float4: the sessions' rings are hipMalloc'd, a layer's offset is a multiple of hd, hd % 4 == 0 holds for 64 / 128)
-    if (p.M < 1 || p.M > 8 || p.n < 1 || p.n > 16 || !p.mem || !p.order || p.window < 0 || p.window + 1 > 1024 || p.cap <= p.window + p.M || (p.ring_off & 3)) return hipErrorInvalidValue;
+    if (p.M < 1 || p.M > 8 || p.n < 1 || p.n > 16 || !p.mem || !p.order || p.window < 0 || p.window + 1 > 1024 || p.cap <= p.window + p.M || (p.ring_off & 3) || p.rope_mask < 0 ||
+        (p.rope_mask & (p.rope_mask + 1)) || (p.rope_mask && p.rope_mask + 1 < p.M)) return hipErrorInvalidValue;
     attn_form_note(ATTN_FORM_STREAM_RING);
     if (hd == 64) stream_attn_kernel<64><<<dim3(p.n_heads, p.M, p.n), dim3(256), 0, s>>>(p);
     else if (hd == 128) stream_attn_kernel<128><<<dim3(p.n_heads, p.M, p.n), dim3(256), 0, s>>>(p);

@@ -320,11 +320,7 @@ struct Loader {
         const int half = hd / 2; float* dst = ar.take<float>((size_t)len * half);
         if (fill) {
             std::vector<float> t((size_t)len * half);
-            for (int i = 0; i < len; i++)
-                for (int j = 0; j < half; j++) {
-                    const float inv = 1.0f / std::pow(theta, (float)(2 * j) / (float)hd), fr = (float)i * inv;
-                    t[(size_t)i * half + j] = sine ? std::sin(fr) : std::cos(fr);
-                }
+            rope_rows_fill(hd, theta, 0, len, len, nullptr, sine ? nullptr : t.data(), sine ? t.data() : nullptr);      // (every row by the tables' f32 formula)
             if (hipMemcpy(dst, t.data(), t.size() * 4, hipMemcpyHostToDevice) != hipSuccess) setfail("hipMemcpy failed for rope table");
         }
         return dst;

@@ -299,6 +299,29 @@ def attn_decode(ctx, q, k, v, pos, n_heads, n_kv_heads, window=-1, kv_row=None, 
     return out
 
 
+def attn_decode_ring(ctx, q, k, v, pos, n_heads, n_kv_heads, window):
+    """vox_debug_attn_decode_ring: ONE ring decode attention launch.  q [n_seq, n_heads*128], pos [n_seq] (any value below 2^24); k / v [n_slices, n_kv_heads, cap, 128]
+    with row j of a sequence at ring row j % cap; 0 <= window < cap.  Returns float32 [n_seq, n_heads*128]."""
+    q, k, v = _f32(q), _f32(k), _f32(v)
+    pos = np.ascontiguousarray(pos, dtype=np.int32)
+    if q.ndim != 2 or k.ndim != 4 or k.shape != v.shape or pos.shape != (q.shape[0],):
+        raise VoxError(1, "attn_decode_ring: bad shapes")
+    if k.shape[1] != n_kv_heads or k.shape[3] != 128 or q.shape[1] != n_heads * 128:
+        raise VoxError(1, "attn_decode_ring: q / k / v widths do not match the head counts")
+    d = AttnDecodeDesc(n_seq=q.shape[0], n_heads=n_heads, n_kv_heads=n_kv_heads, head_dim=128, window=window, n_slices=k.shape[0], max_seq=k.shape[2], pos=pos.ctypes.data)
+    out = np.empty((q.shape[0], n_heads * 128), np.float32)
+    check(lib().vox_debug_attn_decode_ring(ctx.h, C.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(out)))
+    return out
+
+
+def rope_rows(head_dim, theta, first_pos, n):
+    """vox_debug_rope_rows (host arithmetic, no device): (inv [head_dim/2], cos [n, head_dim/2], sin [n, head_dim/2]) float32 for positions first_pos .. first_pos + n - 1."""
+    half = max(int(head_dim) // 2, 0)
+    inv = np.empty(half, np.float32); cos = np.empty((max(int(n), 0), half), np.float32); sin = np.empty_like(cos)
+    check(lib().vox_debug_rope_rows(int(head_dim), float(theta), int(first_pos), int(n), _ptr(inv), _ptr(cos), _ptr(sin)))
+    return inv, cos, sin
+
+
 def attn_gqa_max_seq(ctx):
     """vox_debug_attn_gqa_max_seq: the most rows per KV head the slab GQA decode attention serves (a slab stream group's max_positions on a 4:1 model)."""
     n = C.c_int32(); check(lib().vox_debug_attn_gqa_max_seq(ctx.h, C.byref(n)))
@@ -595,12 +618,20 @@ class LiveStream:
     """A live streaming session (vox_stream): push samples in pieces of any size, get token ids back as soon as they are determined; after finish() the
     concatenation equals transcribe_streaming on the log-mel of pad_audio(gain * samples).  One decoder position = 2560 samples = 160 ms at 16 kHz.
     sample_rate: the rate of what is pushed (vox_stream_create_rate); other than 16 kHz the session resamples incrementally and gives the ids of a 16 kHz session
-    fed resample(samples)."""
+    fed resample(samples).
+    endless (vox_stream_create_endless): the session goes on past 16 384 positions, up to 2^24: its decoder cache is a ring of dec_ring_rows rows (0: a little more
+    than one window) and max_positions does not apply."""
 
-    def __init__(self, model, t_embed, gain=1.0, enc_capacity_rows=0, max_positions=0, sample_rate=16000):
-        self.model = model; self.h = C.c_void_p(); self.sample_rate = int(sample_rate)
+    def __init__(self, model, t_embed, gain=1.0, enc_capacity_rows=0, max_positions=0, sample_rate=16000, endless=False, dec_ring_rows=0):
+        self.model = model; self.h = C.c_void_p(); self.sample_rate = int(sample_rate); self.endless = bool(endless)
         args = (model.h, _ptr(_f32(t_embed).reshape(-1)), float(gain), int(enc_capacity_rows), int(max_positions))
-        if self.sample_rate == 16000:
+        if self.endless:
+            if max_positions:
+                raise VoxError(1, "create_stream: an endless session takes no max_positions")
+            check(lib().vox_stream_create_endless(*args[:4], int(dec_ring_rows), self.sample_rate, C.byref(self.h)))
+        elif dec_ring_rows:
+            raise VoxError(1, "create_stream: dec_ring_rows applies with endless=True")
+        elif self.sample_rate == 16000:
             check(lib().vox_stream_create(*args, C.byref(self.h)))
         else:
             check(lib().vox_stream_create_rate(*args, self.sample_rate, C.byref(self.h)))
@@ -1063,10 +1094,11 @@ class Q4VoxtralModel:
         check(lib().vox_transcribe_audio_scored(self.h, ptr, n_samples, _ptr(t), _ptr(ids), cap, C.byref(n), _ptr(sc), None if al is None else _ptr(al), k, kind))
         return ids[:n.value].copy(), sc[:n.value].copy(), None if al is None else al[:n.value].copy()
 
-    def create_stream(self, t_embed, gain=1.0, enc_capacity_rows=0, max_positions=0, sample_rate=16000) -> LiveStream:
+    def create_stream(self, t_embed, gain=1.0, enc_capacity_rows=0, max_positions=0, sample_rate=16000, endless=False, dec_ring_rows=0) -> LiveStream:
         """A live session on this model (vox_stream_create / vox_stream_create_rate): push(x) -> ids, finish(), reset(), info(), close().  gain multiplies every sample
-        (a stream has no file peak: 0.95 / max|x| of a known file reproduces transcribe_audio).  sample_rate: the rate of the samples that will be pushed."""
-        return LiveStream(self, t_embed, gain, enc_capacity_rows, max_positions, sample_rate)
+        (a stream has no file peak: 0.95 / max|x| of a known file reproduces transcribe_audio).  sample_rate: the rate of the samples that will be pushed.
+        endless (vox_stream_create_endless): no 16 384-position limit -- the decoder cache is a ring of dec_ring_rows rows (0: the default, a little more than one window)."""
+        return LiveStream(self, t_embed, gain, enc_capacity_rows, max_positions, sample_rate, endless, dec_ring_rows)
 
     def create_stream_group(self, t_embed, n_members, gains=None, enc_capacity_rows=0, max_positions=0, sample_rates=None, page_rows=None, pool_pages=None) -> LiveStreamGroup:
         """Up to 16 live sessions advanced together (vox_stream_group_create): advance({member: samples}, finish=()) -> {member: ids}, reset(member, gain), info(member),
