@@ -426,7 +426,9 @@ int32_t vox_debug_reload_knobs(void);
  * [5] batched GQA decode, [6] fused attention + wo, [7] single-stream decode-engine launches (the whole step), [8] the live stream's ring attention (RoPE + K / V append + windowed
  * attention in one launch: exactly enc_layers per tick of a vox_stream).  Behind them, not attention: [9] a stream group's resampling ingest (one launch per pass for
  * all fed members), [10] a solo stream's.  Behind those, attention again: [11] paged single-query decode, [12] paged batched GQA decode (a paged stream group's step:
- * PAGED DECODER CACHE below).  [13] ring single-query decode (vox_debug_attn_decode_ring below): 0 unless a ring launch ran.  Entries past [13] are written as 0. */
+ * PAGED DECODER CACHE below).  [13] ring single-query decode (vox_debug_attn_decode_ring below): 0 unless a ring launch ran.  [14] paged single-query decode on a RING page table, [15] paged batched
+ * GQA decode on one (an endless paged group's step, ENDLESS PAGED GROUPS below; vox_debug_attn_decode_paged_ring): such a launch counts here and not in [11] [12].
+ * Entries past [15] are written as 0. */
 int32_t vox_debug_attn_launches(uint64_t* out, int32_t cap);
 /* One decode attention launch on its own (tests): one query row per sequence against a decoder cache, through the launcher and with the parameters of the batched decode
  * steps -- exactly ONE launch; which kernel ran is the launcher's choice and is read from vox_debug_attn_launches ([3] [4] [5] slab, [11] [12] paged).
@@ -460,6 +462,13 @@ int32_t vox_debug_attn_gqa_max_seq(vox_ctx* ctx, int32_t* out);
  * vox_debug_attn_decode on the same keys laid out from row 0; ring rows outside the window are never read.  The per-head kernel, f32 rows out: prefer_gqa, spec,
  * out_xf and the paged fields must be 0.  Exactly ONE launch, counted in vox_debug_attn_launches [13].  Every argument is checked before the context is bound. */
 int32_t vox_debug_attn_decode_ring(vox_ctx* ctx, const vox_attn_decode_desc* desc, const float* q, const float* k, const float* v, void* out);
+/* One paged decode attention launch on a RING page table (tests): vox_debug_attn_decode's paged call, the descriptor's layout and meaning unchanged, with every table
+ * row used as a ring of page_tab_len entries (1..1024, <= page_tab_stride, a power of two or not): logical page q of a sequence is entry q % page_tab_len of its row.
+ * pos[s] may be any value below 2^24; window >= 0; page_tab_len >= window / page_rows + 4 -- the window / page_rows + 2 pages a window's keys can touch, + 2 -- is
+ * required, a smaller table is refused.  The entries of every sequence's window are checked against the pool; the others may hold anything (-1) and are never read.
+ * The paged kernels with the ring index in their staging loop alone: the output has the bits of vox_debug_attn_decode on a flat table naming the same pages.
+ * Exactly ONE launch, counted in vox_debug_attn_launches [14] (per-head) or [15] (GQA), never in [11] [12].  Every argument is checked before the context is bound. */
+int32_t vox_debug_attn_decode_paged_ring(vox_ctx* ctx, const vox_attn_decode_desc* desc, int32_t page_tab_len, const float* q, const float* k, const float* v, void* out);
 /* RoPE rows on their own (tests; host arithmetic, no device): rows first_pos .. first_pos + n - 1 (positions below 2^24) of the tables the kernels read, cos_out /
  * sin_out [n][head_dim / 2], and in inv_out [head_dim / 2] the f32 factors 1 / theta^(2 j / head_dim) they were made from.  The ONE function that produces RoPE rows:
  * the load-time tables and the streaming encoder's table are filled by it.  head_dim 128 is the decoder's geometry, whose load-time table has 16 384 rows; any other
@@ -766,6 +775,20 @@ int32_t vox_stream_group_create_paged(vox_model* m, const float* t_embed, int32_
 int32_t vox_stream_group_pool(const vox_stream_group* g, int64_t out[4], int32_t* held_or_null);
 int32_t vox_stream_group_pages_for(int64_t positions, int32_t page_rows, int32_t window, int32_t* first_page, int32_t* n_pages);
 int32_t vox_debug_stream_group_pages(const vox_stream_group* g, int32_t member, int32_t* out, int32_t cap, int32_t* n);
+/* ENDLESS PAGED GROUPS.  vox_stream_group_create_endless makes a paged group (everything of PAGED DECODER CACHE above holds) whose members are not refused at 16 384
+ * positions: every member may go on to 2^24 decoder positions (31 days), the limit of an endless solo session, and still gives back its pages as they leave the
+ * decoder window -- so a member's K / V memory stops growing at the window as before.  There is no max_positions.  rates may be null (16 kHz each); page_rows and
+ * pool_pages take 0 for the paged group's defaults.  A model without a sliding decoder window is refused (VOX_ERR_INVALID), as by vox_stream_create_endless.
+ *   What differs inside: a member's page table is a RING of pool_pages entries (logical page q at entry q % pool_pages; a member never holds more pages than the pool
+ *   has, so its pages never collide -- a call that would make it hold more is the pool refusal itself); the RoPE rows of the positions each pass runs are computed on
+ *   the host by the function behind the load-time tables and copied into per-member device rings in front of the pass, at EVERY position (one code path: below the
+ *   tables' lengths the rows have the tables' bits by construction); the per-member token row and the score / alternatives records start at 2048 positions and
+ *   grow by doubling (a doubling synchronises up to four times: once per list and once for the descriptor), are never trimmed, and are counted in vox_stream_group_info[5] as they are.
+ *   Contract: up to the bounded limit, the same sequence of calls gives an endless group and a bounded paged group the same ids, logits, records and pool() -- bit for
+ *   bit.  Everything else of a group -- advance, its 16-bit form, peek, reset, info, scores, alternatives, taps, capture rates, pool, pages_for -- works unchanged.
+ *   Not served: endless slab groups, freeing pages inside a call, more than 16 members. */
+int32_t vox_stream_group_create_endless(vox_model* m, const float* t_embed, int32_t n_members, const float* gains /* null: 1.0 */, const uint32_t* rates /* null: 16000 each */,
+                                        int32_t enc_capacity_rows, int32_t page_rows /* 0: 256 */, int32_t pool_pages /* 0: the default */, vox_stream_group** out);
 /* The live sessions' feed planner on its own (tests): host arithmetic only -- no context, no device, no model.  A fresh session fed at sample_rate (4 encoder rows per
  * position, the Voxtral left pad, no position limit to speak of) takes the calls (n_samples[c], finish[c] 0 / 1) exactly as vox_stream_push / _finish and a group's advance
  * plan and pass them, every due tick taken as run; finish[c] = 2 is a peek (n_samples[c] must be 0): planned as a finish, its one pass emitted, the session as it was.  One row of five words per pass: call index, input samples appended, 16 kHz samples that entered the 16 kHz ring (a

@@ -36,7 +36,12 @@
    and the slab's 2048 positions per member), warmed like the slab group and timed the same way: pass i of the paged group right behind pass i of the slab group, the
    same positions.  Reports the paged round, its difference to the slab round and both launch counts.  Behind the widths: one run of 16 members of mixed lengths on a
    paged group, the pool's peak use in bytes next to the bytes of the default slab.
- * --endless: the tick of an ENDLESS session (vox_stream_create_endless) past the wrap of its decoder ring, next to a bounded session (max_positions 16 384) at the
+ * --group ... --page-rows R --endless: the same run also times an ENDLESS paged group (vox_stream_group_create_endless) of the paged group's pages and pool, each pass right
+   behind the bounded paged group's over the same positions: round medians, their difference, launches per round, and the host wall time per round of both (the endless
+   group fills its members' RoPE rows on the host in front of every pass).
+ * --memory-past-window --page-rows R: nothing is timed; 16 members of an endless paged group and of a bounded paged group with max_positions 16 384 are run past the
+   decoder window by the same calls, and what they hold is read from pool() and info().
+ * --endless (without --group): the tick of an ENDLESS session (vox_stream_create_endless) past the wrap of its decoder ring, next to a bounded session (max_positions 16 384) at the
    same positions: both are fed the same device-resident samples up to a few ticks past the ring's rows (not timed), then per pass one push of `ticks` ticks each,
    the endless session's right behind the bounded one's.  Medians, their difference, the launches per tick of both (the ring form runs attention and wo as two
    launches per decoder layer) and the device bytes each session holds.  Nothing else is measured in this mode.
@@ -82,8 +87,8 @@ class Timer:
 
 
 def launch_counts(pkg):
-    a = (C.c_uint64 * 14)(); g = (C.c_uint64 * 20)()      # attention forms 0..8, the paged decode forms 11, 12 and the ring decode form 13 (9 and 10 are the resampling ingests: not counted here)
-    L = pkg.lib(); assert L.vox_debug_attn_launches(a, 14) == 0 and L.vox_debug_gemm_launches(g, 20) == 0
+    a = (C.c_uint64 * 16)(); g = (C.c_uint64 * 20)()      # attention forms 0..8, the paged decode forms 11, 12, the ring decode form 13 and the ring-table paged forms 14, 15 (9 and 10 are the resampling ingests: not counted here)
+    L = pkg.lib(); assert L.vox_debug_attn_launches(a, 16) == 0 and L.vox_debug_gemm_launches(g, 20) == 0
     return sum(a[:9]) + sum(a[11:]), sum(g)
 
 
@@ -133,7 +138,10 @@ def bench_groups(pkg, ctx, m, t, tm, a, widths, lines):
             twins.append((what, st_s, g_s, [], []))
         if a.page_rows:      # the paged twin of the slab group: the same positions per member, the default pool
             gp = m.create_stream_group(t, N, gains=[gain] * N, max_positions=2048, page_rows=a.page_rows)
-            gp.advance({k: x[:pos] for k in range(N)}); paged = []; kp = 0
+            gp.advance({k: x[:pos] for k in range(N)}); paged = []; kp = 0; wall_p = []
+            if a.endless:      # the endless twin of the paged group (vox_stream_group_create_endless): the same pages, the same pool, the same positions
+                ge = m.create_stream_group(t, N, gains=[gain] * N, page_rows=a.page_rows, pool_pages=gp.pool()["pool_pages"], endless=True)
+                ge.advance({k: x[:pos] for k in range(N)}); endl = []; ke = 0; wall_e = []
         if sr:
             g2, g3 = (m.create_stream_group(t, N, gains=[gr] * N, sample_rates=[sr] * N) for _ in range(2)); rpos = per * (warm + 1)      # fed from host / device memory
             for gg in (g2, g3):
@@ -147,7 +155,11 @@ def bench_groups(pkg, ctx, m, t, tm, a, widths, lines):
             grp.append(tm.ms(lambda: g.advance(feeds)) / a.ticks); k2 = launch_counts(pkg)
             ks += sum(k1) - sum(k0); kg += sum(k2) - sum(k1)
             if a.page_rows:
-                k2p = launch_counts(pkg); paged.append(tm.ms(lambda: gp.advance(feeds)) / a.ticks); kp += sum(launch_counts(pkg)) - sum(k2p)
+                k2p = launch_counts(pkg); w0 = time.perf_counter(); paged.append(tm.ms(lambda: gp.advance(feeds)) / a.ticks); wall_p.append(1e3 * (time.perf_counter() - w0) / a.ticks)
+                kp += sum(launch_counts(pkg)) - sum(k2p)
+                if a.endless:      # right behind the bounded paged pass, over the same positions
+                    k2e = launch_counts(pkg); w0 = time.perf_counter(); endl.append(tm.ms(lambda: ge.advance(feeds)) / a.ticks); wall_e.append(1e3 * (time.perf_counter() - w0) / a.ticks)
+                    ke += sum(launch_counts(pkg)) - sum(k2e)
             for what, st_s, g_s, solo_s, grp_s in twins:
                 k3 = launch_counts(pkg); solo_s.append(tm.ms(lambda: st_s.push(seg)) / a.ticks); k4 = launch_counts(pkg); grp_s.append(tm.ms(lambda: g_s.advance(feeds)) / a.ticks); k5 = launch_counts(pkg)
                 assert (sum(k4) - sum(k3), sum(k5) - sum(k4)) == (sum(k1) - sum(k0), sum(k2) - sum(k1))      # the counted launches are the plain pair's (the record kernels are uncounted: one each)
@@ -184,6 +196,13 @@ def bench_groups(pkg, ctx, m, t, tm, a, widths, lines):
             lines += [f"  paged group of {N:2d} (pages of {pl['page_rows']} rows, pool of {pl['pool_pages']}, peak {pl['peak']}): round median {rp:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in paged) +
                       f"   difference to the slab round {rp - rnd:+.3f} ms ({100 * (rp - rnd) / rnd:+.2f} %), per pass " + " ".join(f"{v - w:+.3f}" for v, w in zip(paged, grp)),
                       f"  launches per round: paged {kp / ticks + fixed_enc + 2:.0f}, slab {lg:.0f}"]
+            if a.endless:
+                assert ge.info(N - 1)["positions"] == 38 + warm + a.ticks * a.passes
+                ie = ge.info(0); ge.close(); re_ = statistics.median(endl); we, wp = statistics.median(wall_e), statistics.median(wall_p)
+                lines += [f"  endless paged group of {N:2d}, the same positions, each pass right behind the bounded paged one's: round median {re_:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in endl) +
+                          f"   difference to the bounded paged round {re_ - rp:+.3f} ms ({100 * (re_ - rp) / rp:+.2f} %), per pass " + " ".join(f"{v - w:+.3f}" for v, w in zip(endl, paged)),
+                          f"  launches per round: endless {ke / ticks + fixed_enc + 2:.0f}, bounded paged {kp / ticks + fixed_enc + 2:.0f}; host wall time per round (the call, its synchronisation included): "
+                          f"endless {we:.3f} ms, bounded paged {wp:.3f} ms (the call is GPU-bound and the host runs ahead of the device: this does NOT isolate the host cost of the RoPE rows' fill); a member's device bytes {ie['bytes'] / 1e6:.1f} MB"]
         for what, _, _, solo_s, grp_s in twins:
             ts, rs = statistics.median(solo_s), statistics.median(grp_s); off = what.split()[0] + " off"
             lines += [f"  {what}, group of {N:2d}: round median {rs:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in grp_s) + f"   difference to {off} {rs - rnd:+.3f} ms ({100 * (rs - rnd) / rnd:+.2f} %), per pass " + " ".join(f"{v - w:+.3f}" for v, w in zip(grp_s, grp)),
@@ -204,6 +223,39 @@ def bench_groups(pkg, ctx, m, t, tm, a, widths, lines):
             lines += [f"group of {N:2d} at {what}: round median {r:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in pr) + f"   difference to the 16 kHz f32 round {r - base:+.3f} ms ({100 * (r - base) / base:+.1f} %)",
                       f"  fed from device memory: round median {rd:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in prd) + f"   difference {rd - base:+.3f} ms ({100 * (rd - base) / base:+.1f} %)"]
         pkg._lib.check(pkg.lib().vox_dev_free(ctx.h, dev))
+
+
+def bench_group_memory(pkg, ctx, m, t, a, lines):
+    """--memory-past-window: what 16 members hold once every one of them is past the decoder window -- an endless paged group next to a bounded paged group with
+    max_positions 16 384, the same pages, the same pool, the same calls (64 ticks for every member, device-resident samples), scores and k = 3 alternatives on: pool()
+    and info() of both, the K / V bytes of the held pages from the pool's shape."""
+    L = pkg.lib(); c = m.config; N = 16; R = a.page_rows; W = c.dec_window; per = 64 * 2560; n_var = 8
+    base = pkg.synth.synth_audio(per * n_var / 16000.0, seed=961); mx = float(np.abs(base).max()); gain = 0.95 / mx
+    dev = C.c_void_p(); pkg._lib.check(L.vox_dev_alloc(ctx.h, base.nbytes, C.byref(dev))); pkg._lib.check(L.vox_dev_upload(ctx.h, dev, base.ctypes.data, base.nbytes))
+    pos = [37]; total = 0
+    while pos[-1] < W + 264:
+        total += per; pos.append(pkg.stream_schedule(total)[0])
+    held = []
+    for p0, p1 in zip(pos, pos[1:]):
+        f0, _ = pkg.stream_group_pages_for(p0, R, W); f1, n1 = pkg.stream_group_pages_for(p1, R, W); held.append(f1 + n1 - f0)
+    pool_pages = N * max(held); page_bytes = 2 * c.dec_layers * c.dec_kv_heads * R * 128 * 4
+    lines.append(f"memory past the window: {N} members to position {pos[-1]} (window {W}) in {len(pos) - 1} calls of 64 ticks, pages of {R} rows ({page_bytes / 1e6:.1f} MB of K + V each), "
+                 f"pool of {pool_pages} pages ({pool_pages * page_bytes / 1e9:.2f} GB), scores and 3 alternatives on")
+    for what, kw in (("bounded paged group, max_positions 16384", {"max_positions": 16384}), ("endless paged group", {"endless": True})):
+        g = m.create_stream_group(t, N, gains=[gain] * N, page_rows=R, pool_pages=pool_pages, **kw)
+        for k in range(N):
+            g.set_scores(k, True); g.set_alternatives(k, 3)
+        i0 = g.info(0)["bytes"]; t0 = time.perf_counter()
+        for cidx in range(len(pos) - 1):
+            g.advance({k: (dev.value + 4 * per * (cidx % n_var), per) for k in range(N)}, device=True)
+        secs = time.perf_counter() - t0
+        pl = g.pool(); inf = [g.info(k) for k in range(N)]
+        assert all(i["positions"] == pos[-1] for i in inf)
+        lines.append(f"  {what}: pool() held {pl['held'][0]} pages per member ({sum(pl['held'])} of {pl['pool_pages']}, peak {pl['peak']}) = {sum(pl['held']) * page_bytes / 1e9:.3f} GB of K / V in use; "
+                     f"info bytes per member {inf[0]['bytes'] / 1e6:.3f} MB at the end, {i0 / 1e6:.3f} MB at create (a member's share of the group's allocations, the whole pool among them, "
+                     f"+ its lists); all members {sum(i['bytes'] for i in inf) / 1e9:.3f} GB; {secs:.0f} s")
+        g.close()
+    pkg._lib.check(L.vox_dev_free(ctx.h, dev))
 
 
 def bench_peek(pkg, ctx, m, t, tm, a, lines):
@@ -280,14 +332,20 @@ def main():
     ap.add_argument("--page-rows", type=int, default=0, metavar="R", help="with --group: also time a paged group (pages of R rows, the default pool) pass by pass next to the slab group")
     ap.add_argument("--peek", action="store_true", help="time vox_stream_peek next to the same number of ordinary ticks of the same session (nothing else is measured)")
     ap.add_argument("--endless", action="store_true", help="time the tick of an endless session past the wrap of its decoder ring next to a bounded session at the same positions (nothing else is measured)")
+    ap.add_argument("--memory-past-window", action="store_true", help="with --page-rows R: what 16 members of an endless paged group and of a bounded paged group (max_positions 16384) hold past "
+                    "the decoder window, from pool() and info() (a mode of its own: nothing is timed)")
     a = ap.parse_args()
-    if a.endless and (a.group or a.scores or a.alternatives or a.peek):
-        ap.error("--endless is a mode of its own")
+    if a.memory_past_window and (not a.page_rows or a.group or a.endless or a.peek or a.scores or a.alternatives):
+        ap.error("--memory-past-window takes --page-rows and nothing else")
+    if a.endless and a.group and not a.page_rows:
+        ap.error("--endless with --group times an endless PAGED group: give --page-rows")
+    if a.endless and not a.group and (a.scores or a.alternatives or a.peek):
+        ap.error("--endless without --group is a mode of its own")
     if not 0 <= a.alternatives <= 8:
         ap.error("--alternatives takes 1..8")
     if a.peek and (a.group or a.scores or a.alternatives):
         ap.error("--peek is a mode of its own")
-    if a.page_rows and not a.group:
+    if a.page_rows and not a.group and not a.memory_past_window:
         ap.error("--page-rows applies with --group")
     if (a.rate or a.s16) and not a.group or (a.s16 and not a.rate):
         ap.error("--rate applies with --group, --s16 with --rate")
@@ -304,7 +362,16 @@ def main():
             S.write_synthetic_gguf(path + ".tmp", S.ModelDims(), seed=42); os.replace(path + ".tmp", path)
     ctx = pkg.Context(0); m = pkg.Q4ModelLoader.from_file(path).load(ctx); c = m.config
     t = pkg.TimeEmbedding(c.dec_dim).embed(6.0); tm = Timer(pkg, ctx); L = pkg.lib()
-    if a.endless:
+    if a.memory_past_window:
+        lines = ["# " + " ".join(["python", "tools/stream_bench.py"] + sys.argv[1:]), f"# model {os.path.basename(path)}: {c.enc_layers} encoder layers, {c.dec_layers} decoder layers"]
+        bench_group_memory(pkg, ctx, m, t, a, lines)
+        text = "\n".join(lines) + "\n"
+        print(text, end="")
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            open(a.out, "w").write(text)
+        return
+    if a.endless and not a.group:
         lines = ["# " + " ".join(["python", "tools/stream_bench.py"] + sys.argv[1:]),
                  f"# model {os.path.basename(path)}: {c.enc_layers} encoder layers, {c.dec_layers} decoder layers; {a.ticks} ticks per pass, {a.passes} passes"]
         bench_endless(pkg, ctx, m, t, tm, a, lines)

@@ -167,6 +167,7 @@ SIGNATURES = {
     "vox_debug_attn_launches": (i32, [P(C.c_uint64), i32]),
     "vox_debug_attn_decode": (i32, [vp, vp, vp, vp, vp, vp]),
     "vox_debug_attn_decode_ring": (i32, [vp, vp, vp, vp, vp, vp]),
+    "vox_debug_attn_decode_paged_ring": (i32, [vp, vp, i32, vp, vp, vp, vp]),      # a paged launch on a ring page table of page_tab_len entries
     "vox_debug_rope_rows": (i32, [i32, C.c_float, C.c_int64, i32, vp, vp, vp]),
     "vox_debug_attn_gqa_max_seq": (i32, [vp, P(i32)]),
     "vox_debug_gemm_launches": (i32, [P(C.c_uint64), i32]),
@@ -221,6 +222,8 @@ SIGNATURES = {
     "vox_debug_stream_tap_peeked": (i32, [vp, vp, i32]),
     "vox_stream_group_peek": (i32, [vp, vp, i32, vp]),
     "vox_stream_group_create_paged": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, i32, P(vp)]),
+    # an endless paged group: (model, t_embed, n_members, gains, rates or null, enc_capacity_rows, page_rows or 0, pool_pages or 0, out) -- no max_positions
+    "vox_stream_group_create_endless": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, P(vp)]),
     "vox_stream_group_pool": (i32, [vp, P(i64 * 4), vp]),
     "vox_stream_group_pages_for": (i32, [i64, i32, i32, P(i32), P(i32)]),
     "vox_debug_stream_group_pages": (i32, [vp, i32, vp, i32, P(i32)]),

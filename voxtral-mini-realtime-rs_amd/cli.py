@@ -158,15 +158,16 @@ def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_
         stream.close()
 
 
-def transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, chunk_ms, n_members, words_out=None, peek=False, alts_k=0, page_rows=None, pool_pages=None):
+def transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, chunk_ms, n_members, words_out=None, peek=False, alts_k=0, page_rows=None, pool_pages=None, endless=False):
     """--live-group N: the files N at a time through one stream group (vox_stream_group) in pieces of `chunk_ms` milliseconds: every call feeds each busy member its
     next piece, a file that ends (its member fed with finish) frees the member for the next file in input order.  Gains and lines as transcribe_live's (16 kHz: other
     rates are resampled first).  -> {file index: text}; a file that cannot be read is left out (the one-by-one path reports it).  words_out (--live-words): every
     member runs with scores on (and, with alts_k from --live-alternatives, with that many alternatives), a file's words go there when the file ends.  peek (--live-peek): after every call one vox_stream_group_peek for the members still
     busy, a "  ~[" line each: the text so far plus the tentative tail.  page_rows / pool_pages (--live-page-rows, --live-pool-pages): either one given makes the group a
-    paged one (vox_stream_group_create_paged); the lines are the same."""
+    paged one (vox_stream_group_create_paged); the lines are the same.  endless (--live-endless): the group is an endless paged one (vox_stream_group_create_endless: no
+    member is refused at 43 minutes); the lines are the same."""
     step = max(1, int(round(16000 * chunk_ms / 1000.0)))
-    group = model.create_stream_group(t_embed, n_members, page_rows=page_rows, pool_pages=pool_pages)
+    group = model.create_stream_group(t_embed, n_members, page_rows=page_rows, pool_pages=pool_pages, endless=endless)
     text = lambda ids: tokenizer.decode([t for t in ids if t >= 1000]).strip()
     texts = {}; busy = {}; nxt = 0      # busy: member -> [file index, samples, offset, ids]
     try:
@@ -360,8 +361,9 @@ def main(argv=None):
     ap.add_argument("--live-page-rows", type=int, default=None, metavar="R", help="with --live-group: a paged group (vox_stream_group_create_paged) whose decoder cache is one pool "
                     "of K / V pages of R rows (a power of two in 16..1024; 0: 256) that the files grow into, instead of a 2048-position slab slice per member; same lines")
     ap.add_argument("--live-pool-pages", type=int, default=None, metavar="P", help="with --live-group: a paged group with a pool of P pages (0: the default slab's memory)")
-    ap.add_argument("--live-endless", action="store_true", help="with --live (one file at a time, not --live-group): an endless session (vox_stream_create_endless) -- no limit at "
-                    "16 384 decoder positions (about 43 minutes); the decoder cache is a ring of a little more than one window and stops growing there")
+    ap.add_argument("--live-endless", action="store_true", help="with --live: an endless session (vox_stream_create_endless) -- no limit at "
+                    "16 384 decoder positions (about 43 minutes); the decoder cache is a ring of a little more than one window and stops growing there.  With --live-group: "
+                    "an endless paged group (vox_stream_group_create_endless; --live-page-rows / --live-pool-pages apply), no member refused at 43 minutes; same lines")
     ap.add_argument("--live-peek", action="store_true", help="with --live (also with --live-group, --live-native-rate, --live-words): after every push a line starting with "
                     "'  ~[' on stderr: the text so far plus the tentative tail, i.e. the line if the file ended here (vox_stream_peek); stdout, the '  [' lines and the "
                     "words file do not change")
@@ -409,8 +411,8 @@ def main(argv=None):
         ap.error("--live-group feeds 16 kHz samples: it does not combine with --live-native-rate")
     if a.live and (a.gpus > 1 or a.batch > 1 or a.live_chunk_ms <= 0):
         ap.error("--live runs one file at a time on one GPU (no --gpus / --batch) with --live-chunk-ms > 0")
-    if a.live_endless and (not a.live or a.live_group):
-        ap.error("--live-endless applies with --live, one file at a time (stream groups have no endless form)")
+    if a.live_endless and not a.live:
+        ap.error("--live-endless applies with --live")
     if a.live_native_rate and not a.live:
         ap.error("--live-native-rate applies with --live")
     if a.live and not a.gguf:
@@ -501,7 +503,7 @@ def main(argv=None):
                         write_word_lines(rec_out, runner.words.get((i, k), []))
     if a.live_group:
         try:
-            texts = transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_group, words_out, a.live_peek, a.live_alternatives, a.live_page_rows, a.live_pool_pages)
+            texts = transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_group, words_out, a.live_peek, a.live_alternatives, a.live_page_rows, a.live_pool_pages, a.live_endless)
         except Exception as e:      # the files fall back to one live session each
             log(f"Error in the stream group: {e}"); texts = {}
             if words_out is not None:      # the files' words come again with their lines

@@ -1214,7 +1214,8 @@ extern "C" int32_t vox_debug_attn_gqa_max_seq(vox_ctx* c, int32_t* out) {
     *out = most; return VOX_OK;
 }
 // ring: vox_debug_attn_decode_ring -- the slab call's buffers with the cache slices used as rings of max_seq rows (launch_attn_decode_ring)
-static int32_t attn_decode_debug(vox_ctx* c, const vox_attn_decode_desc* d, const float* q, const float* k, const float* v, void* out, bool ring) {
+// tab_len > 0: vox_debug_attn_decode_paged_ring -- the paged call with every table row used as a ring of tab_len entries (AttnParams::page_tab_len), positions to 2^24 - 1
+static int32_t attn_decode_debug(vox_ctx* c, const vox_attn_decode_desc* d, const float* q, const float* k, const float* v, void* out, bool ring, int tab_len = 0) {
     ARGCHK(c && d && q && k && v && out, "null argument"); ARGCHK(d->pos, "null argument (pos)");
     ARGCHK(d->head_dim == 128, "head_dim %d: the decoder's decode attention serves head_dim 128 alone", d->head_dim);
     ARGCHK(d->n_seq >= 1 && d->n_seq <= 4096, "n_seq %d out of range (1..4096)", d->n_seq);
@@ -1242,13 +1243,21 @@ static int32_t attn_decode_debug(vox_ctx* c, const vox_attn_decode_desc* d, cons
         ARGCHK(d->pool_pages >= 1 && d->pool_pages <= (1 << 20), "pool_pages %d out of range", d->pool_pages);
         ARGCHK(d->page_tab_stride >= 1 && d->page_tab_stride <= 1024, "page_tab_stride %d out of range (1..1024)", d->page_tab_stride);
         ARGCHK(d->score_rows >= 1 && d->score_rows <= 16384, "score_rows %d out of range (1..16384)", d->score_rows);
+        if (tab_len) {      // the window's keys touch at most window / page_rows + 2 pages; a ring table also holds the two a call may enter ahead of a release
+            ARGCHK(d->window >= 0, "a ring table needs a sliding window (window %d)", d->window);
+            ARGCHK(tab_len <= d->page_tab_stride, "page_tab_len %d exceeds page_tab_stride %d", tab_len, d->page_tab_stride);
+            ARGCHK(tab_len >= d->window / d->page_rows + 2 + 2, "page_tab_len %d: a window of %d in pages of %d rows needs a ring table of at least %d entries (the window's %d pages + 2)", tab_len,
+                   d->window, d->page_rows, d->window / d->page_rows + 4, d->window / d->page_rows + 2);
+        }
         for (int i = 0; i < n; i++) {
             const int pos = d->pos[i], row = d->kv_row ? d->kv_row[i] : i;
+            if (tab_len) ARGCHK(pos >= 0 && pos < (1 << 24), "pos[%d] = %d outside 0..2^24 - 1", i, pos);
+            else
             ARGCHK(pos >= 0 && (pos >> shift) < d->page_tab_stride, "pos[%d] = %d outside the table's %d pages of %d rows", i, pos, d->page_tab_stride, d->page_rows);
             const int j_lo = d->window >= 0 ? std::max(0, pos - d->window) : 0;
             ARGCHK(pos - j_lo + 1 <= d->score_rows, "pos[%d] = %d attends %d keys, score_rows is %d", i, pos, pos - j_lo + 1, d->score_rows);
             for (int pg = j_lo >> shift; pg <= (pos >> shift); pg++) {
-                const int e = d->page_tab[(size_t)row * d->page_tab_stride + pg];
+                const int e = d->page_tab[(size_t)row * d->page_tab_stride + (tab_len ? pg % tab_len : pg)];
                 ARGCHK(e >= 0 && e < d->pool_pages, "sequence %d: table entry %d of its window is %d, outside the pool's %d pages", i, pg, e, d->pool_pages);
             }
         }
@@ -1280,6 +1289,7 @@ static int32_t attn_decode_debug(vox_ctx* c, const vox_attn_decode_desc* d, cons
     ap.out = dout.as<float>(); if (d->out_xf) { ap.out_xf = dxf.as<uint16_t>(); ap.out_xf_gstride = (long)(xf_b / 2); }
     if (paged) {
         ap.kv_head_stride = (hd << shift); ap.page_tab = d_tab; ap.page_tab_stride = d->page_tab_stride; ap.page_shift = shift; ap.page_floats = (long)slice_f; ap.score_rows = d->score_rows;
+        ap.page_tab_len = tab_len;
         HIPCHK(launch_attn_decode_paged(ap, hd, s, n));
     } else if (ring) HIPCHK(launch_attn_decode_ring(ap, hd, d->max_seq, s, n));
     else HIPCHK(launch_attn_decode(ap, hd, d->max_seq, s, n));
@@ -1294,6 +1304,11 @@ extern "C" int32_t vox_debug_attn_decode(vox_ctx* c, const vox_attn_decode_desc*
 extern "C" int32_t vox_debug_attn_decode_ring(vox_ctx* c, const vox_attn_decode_desc* d, const float* q, const float* k, const float* v, void* out) {
     return attn_decode_debug(c, d, q, k, v, out, true);
 }
+extern "C" int32_t vox_debug_attn_decode_paged_ring(vox_ctx* c, const vox_attn_decode_desc* d, int32_t page_tab_len, const float* q, const float* k, const float* v, void* out) {
+    ARGCHK(d, "null argument"); ARGCHK(d->page_rows != 0, "a ring table belongs to a paged call (page_rows 0)");
+    ARGCHK(page_tab_len >= 1 && page_tab_len <= 1024, "page_tab_len %d out of range (1..1024)", page_tab_len);
+    return attn_decode_debug(c, d, q, k, v, out, false, page_tab_len);
+}
 // What a batched XF decode step works on.  f32 rows (h, qkv, logits; att unread), XF planes and partial sums of squares one block per 16-row group, `*_gs` elements apart.
 // k / v: layer 0's cache slab (layer l at + l layer_stride), row r's slice at + r seq_stride, or, with kv_row, the slice kv_row[r] names; pos: the rows' positions.
 // ssq_e: the batched engine's sums of squares (one block of 256 + 16 rows per group); planes: the wide step's K-split scratch, planes_bytes per chain.
@@ -1305,6 +1320,9 @@ struct XfBufs {
     // page_tab [member][page_tab_stride] its table, kv_row the rows' MEMBERS (attention finds its table row), kv_page / kv_in the rows' physical page and row inside it
     // (the q|k|v epilogue appends there); score_rows: the attention's LDS score rows per query head
     const int *page_tab, *kv_page, *kv_in; int page_tab_stride, page_shift, score_rows; long page_floats;
+    // an endless paged group: the table rows are rings of page_tab_len entries, and the q|k|v epilogue reads its RoPE rows from the group's member-strided decoder
+    // RoPE ring (rope_ring [members][rope_mask + 1][cos | sin]; the row's member: kv_row).  0 / null everywhere else
+    int page_tab_len; const float* rope_ring; int rope_mask;
 };
 // the XF planes and ssq blocks of a step over n_grp groups (0: none, the group strides alone): from the pool, zeroed on s, bound to b
 struct XfPlanes {
@@ -1350,6 +1368,7 @@ static int32_t xf_chain(const vox_model* m, const XfBufs& b, int g0i, int ng, in
         { GemmParams g{}; g.out = qg; g.out_stride = W; g.ssq_part = ssq; g.n_part = l == 0 ? 1 : parts_D; g.pos = pg; g.rope_cos = m->dec_cos; g.rope_sin = m->dec_sin;
           g.hd = hd; g.n_q = QD; g.n_kv = KV; g.kc = kl; g.vc = vl; g.kv_seq_stride = (long)b.seq_stride; g.kv_head_stride = max_seq * hd; g.kv_row = rg;
           if (b.page_tab) { g.kv_seq_stride = b.page_floats; g.kv_head_stride = (hd << b.page_shift); g.kv_row = b.kv_page + r0; g.kv_pos = b.kv_in + r0; }
+          if (b.page_tab && b.rope_ring) { g.rope_cos = b.rope_ring; g.rope_sin = b.rope_ring + hd / 2; g.rope_member = rg; g.rope_mask = b.rope_mask; }
           HIPCHK(gemm(g, L.wqkv.w, xf1, D, EPI_ROPE_KV)); }
         AttnParams ap{}; ap.q = qg; ap.k = kl; ap.v = vl; ap.kv_row_stride = hd; ap.kv_head_stride = max_seq * hd; ap.n_heads = H; ap.n_kv_heads = KV;
         ap.offset = 0; ap.window = c.dec_window; ap.pos_ptr = pg; ap.M = 1; ap.pos_per_seq = 1; ap.q_seq_stride = W; ap.out_seq_stride = QD; ap.kv_seq_stride = (long)b.seq_stride;
@@ -1357,7 +1376,7 @@ static int32_t xf_chain(const vox_model* m, const XfBufs& b, int g0i, int ng, in
         ap.out = b.att; if (mtw) { ap.out = b.att + (size_t)g0i * 16 * QD; ap.out_xf_gstride = b.xf2_gs; }
         if (b.page_tab) {
             ap.kv_head_stride = (hd << b.page_shift); ap.page_tab = b.page_tab; ap.page_tab_stride = b.page_tab_stride; ap.page_shift = b.page_shift; ap.page_floats = b.page_floats;
-            ap.score_rows = b.score_rows;
+            ap.score_rows = b.score_rows; ap.page_tab_len = b.page_tab_len;
             HIPCHK(launch_attn_decode_paged(ap, hd, sg, M));
         } else
         HIPCHK(launch_attn_decode(ap, hd, max_seq, sg, M));
@@ -3281,7 +3300,7 @@ static int32_t stream_verify(vox_stream* st) {      // inside a long push: befor
 // w1|w3, w2 } -> final norm -> adapter, every weight matrix in ONE launch for all sessions of the round (4 n rows through q4_linear_dev, which picks the kernel by the row
 // count).  Slot z works for session r.order[z] (device arrays); w.arow[z] is its adapter row.  ftap_*: a solo stream's front tap (null: none).
 // rope (null: the model's streaming table): a solo endless session's encoder RoPE ring, rows = position & rope_mask (StreamAttnParams::rope_mask)
-struct StreamRound { const StreamMember* mem; const int* order; int n, cap; size_t ring_layer; MelTables mel; long left; const float* rope = nullptr; int rope_mask = 0; };
+struct StreamRound { const StreamMember* mem; const int* order; int n, cap; size_t ring_layer; MelTables mel; long left; const float* rope = nullptr; int rope_mask = 0, rope_stride = 0; };      // rope_stride > 0: an endless group's rings, one per member
 static int32_t stream_encode_round(vox_model* m, const StreamWs& w, const StreamRound& r, float* ftap_mel, float* ftap_conv) {
     const vox_model_cfg& c = m->cfg; vox_ctx* cx = m->ctx; hipStream_t s = cx->stream;
     const int D = c.enc_dim, H = c.enc_heads, hd = c.enc_head_dim, QD = H * hd, F = c.enc_ffn, R = c.reshape_factor, DD = c.dec_dim, Cm = c.n_mels, n = r.n, M = R * n;
@@ -3305,7 +3324,7 @@ static int32_t stream_encode_round(vox_model* m, const StreamWs& w, const Stream
         VOXCHK(q4_linear_dev(cx, L.wqkv.w, L.wqkv.bias, xn, D, M, w.qkv, 3 * QD));
         StreamAttnParams ap{}; ap.qkv = w.qkv; ap.qkv_stride = 3 * QD; ap.mem = r.mem; ap.order = r.order; ap.n = n; ap.ring_off = (size_t)l * r.ring_layer; ap.cap = r.cap;
         ap.cos_t = m->enc_cos_s; ap.sin_t = m->enc_sin_s; ap.out = w.att;
-        if (r.rope) { ap.cos_t = r.rope; ap.sin_t = r.rope + hd / 2; ap.rope_mask = r.rope_mask; } ap.out_stride = QD; ap.M = R; ap.n_heads = H; ap.window = c.enc_window;
+        if (r.rope) { ap.cos_t = r.rope; ap.sin_t = r.rope + hd / 2; ap.rope_mask = r.rope_mask; ap.rope_stride = r.rope_stride; } ap.out_stride = QD; ap.M = R; ap.n_heads = H; ap.window = c.enc_window;
         HIPCHK(launch_stream_attn(ap, hd, s));
         VOXCHK(q4_linear_dev(cx, L.wo.w, L.wo.bias, w.att, QD, M, x, D, EPI_RESID, x, D));
         HIPCHK(launch_rms_norm(x, D, M, D, L.ffn_norm, nullptr, c.norm_eps, xn, D, s));
@@ -3649,6 +3668,9 @@ struct GroupMember {
     ScoreState sc;                       // its scores (vox_stream_group_set_scores); h_mem[i].scores is sc.dev while they are on
     AltsState al;                        // its alternatives (vox_stream_group_set_alternatives); h_mem[i].alts is al.dev while its k > 0
     int h_state[STRM_WORDS];
+    // an endless group's member: its own position-indexed token row of lists_cap + 2 entries (its score and alternatives records have lists_cap + 2 as well), grown
+    // by doubling (group_lists_grow).  A bounded group's members share g->tokens and keep 0 / null here
+    int* tokens = nullptr; int lists_cap = 0;
 };
 // one block matrix per rate in use, shared by the members at that rate (built by resample_matrix_build: vox_resample's bits; never the context's matrix, which goes
 // when vox_resample serves another rate pair).  refs == 0: a free slot
@@ -3675,11 +3697,25 @@ struct vox_stream_group {
     // layer's pages), pool the allocator with every member's table mirror, d_tab the device table [n][pool.max_pages], d_kv_page / d_kv_in the step's physical pages and
     // rows inside them [16] (behind d_kv_row, the same allocation).  A slab group: paged == false, nothing of this is set
     bool paged = false; PagePool pool; int* d_tab = nullptr; int *d_kv_page = nullptr, *d_kv_in = nullptr; size_t page_floats = 0;
+    // An ENDLESS paged group (vox_stream_group_create_endless; DESIGN.md section 8, "Endless paged groups"): g.max_pos is 2^24; the pool's tables are rings of pool_pages
+    // entries (d_tab [n][pool.tab_len]); every member has its own token row and record lists (GroupMember::tokens, lists_cap), grown by doubling; and the group owns
+    // two member-strided device RoPE rings -- decoder [n][GROUP_ROPE_ROWS][cos hd/2 | sin hd/2], encoder [n][R GROUP_ROPE_ROWS][..] -- with their pinned host images,
+    // the event behind the last copy out of those images, and the f32 factors of both head dims (rope_inv_fill, computed once).  The rounds of an endless
+    // group read the rings at EVERY position: one code path below and above the load-time tables' lengths.
+    bool endless = false;
+    struct { float *dec = nullptr, *enc = nullptr, *h_dec = nullptr, *h_enc = nullptr; hipEvent_t copied = nullptr; bool pending = false; std::vector<float> inv_d, inv_e; } rope;
 };
+static const int GROUP_ROPE_ROWS = 64;         // rows per member of an endless group's decoder RoPE ring: a power of two >= the most ticks of one pass (feed_pass_max_ticks, asserted at create and per pass)
+static const int GROUP_LISTS_START = 2048;     // positions an endless group's member lists start with
 // entries [q0, q1) of a member's table mirror to the device, on the group's stream (the mirror stays where it is: the tables are sized at create)
-static int32_t group_table_upload(vox_stream_group* g, int member, int q0, int q1) {
+// (a ring table: logical pages q0 .. q1 - 1 live at entries q % tab_len -- at most tab_len of them, two copies where the range wraps)
+static int32_t group_table_upload(vox_stream_group* g, int member, int64_t q0, int64_t q1) {
     if (q1 <= q0) return VOX_OK;
-    HIPCHK(hipMemcpyAsync(g->d_tab + (size_t)member * g->pool.max_pages + q0, g->pool.mem[(size_t)member].tab.data() + q0, (size_t)(q1 - q0) * 4, hipMemcpyHostToDevice, g->ctx->stream));
+    const int L = g->pool.tab_len; int* dev = g->d_tab + (size_t)member * L; const int* host = g->pool.mem[(size_t)member].tab.data();
+    ARGCHK(q1 - q0 <= L, "internal: member %d: %lld changed table entries, the table has %d", member, (long long)(q1 - q0), L);
+    const int e0 = (int)g->pool.slot(q0), cnt = (int)(q1 - q0), k = std::min(cnt, L - e0);
+    HIPCHK(hipMemcpyAsync(dev + e0, host + e0, (size_t)k * 4, hipMemcpyHostToDevice, g->ctx->stream));
+    if (cnt > k) HIPCHK(hipMemcpyAsync(dev, host, (size_t)(cnt - k) * 4, hipMemcpyHostToDevice, g->ctx->stream));      // the range wrapped (a ring table alone)
     return VOX_OK;
 }
 // the member leaves its rate: its input ring and its reference to the rate's matrix go (the matrix with its last reference).  The caller has synchronised.
@@ -3720,14 +3756,15 @@ static int32_t group_upload_members(vox_stream_group* g) {      // after a descr
 }
 static int32_t group_member_seed(vox_stream_group* g, int i) {
     if (g->paged) {      // every page the member holds goes back, the prefix rows go into fresh ones (the top of the stack: the pages just returned)
-        const vox_model_cfg& c = g->m->cfg; GroupMember& me = g->mem[i]; int q0, q1, t0, t1;
+        const vox_model_cfg& c = g->m->cfg; GroupMember& me = g->mem[i]; int64_t q0, q1, t0, t1;
         ARGCHK(g->pool.held(i) + g->pool.n_free() >= (g->g.PC + g->pool.page_rows - 1) / g->pool.page_rows, "member %d: the pool has no pages for the seed", i);
         g->pool.release_all(i, &q0, &q1);
         if (!g->pool.take(i, g->g.PC, &t0, &t1)) return fail(VOX_ERR_INVALID, "internal: member %d: no pool pages for the seed", i);
         VOXCHK(stream_seed(g->m, g->t_embed.data(), g->g.RC, g->g.PC, g->g.cap, g->h_mem[i].kring, g->h_mem[i].vring, nullptr, g->h_mem[i].tokens, g->h_mem[i].state, me.h_state,
                            [&]() -> int32_t {
-                               VOXCHK(group_table_upload(g, i, 0, std::max(q1, t1)));
-                               HIPCHK(launch_stream_pages_seed(g->m->pfx.dec_k, g->m->pfx.dec_v, c.dec_layers, c.dec_kv_heads, g->g.PC, c.dec_head_dim, g->d_tab + (size_t)i * g->pool.max_pages,
+                               if (g->endless) { VOXCHK(group_table_upload(g, i, q0, q1)); VOXCHK(group_table_upload(g, i, t0, t1)); }      // (the returned pages may lie anywhere in the ring; the seed's are entries 0 ..)
+                               else VOXCHK(group_table_upload(g, i, 0, std::max(q1, t1)));
+                               HIPCHK(launch_stream_pages_seed(g->m->pfx.dec_k, g->m->pfx.dec_v, c.dec_layers, c.dec_kv_heads, g->g.PC, c.dec_head_dim, g->d_tab + (size_t)i * g->pool.tab_len,
                                                                g->pool.shift, g->layer_stride, g->dec_k, g->dec_v, g->ctx->stream));
                                return VOX_OK; }));
         me.feed.restart(g->g.PC); me.steps = 0; me.sc.host.clear(); me.al.restart();
@@ -3745,15 +3782,19 @@ static void group_release(vox_stream_group* g) {
     if (!g) return;
     (void)hipSetDevice(g->ctx->device); (void)hipStreamSynchronize(g->ctx->stream);      // never dereferences g->m (as stream_release)
     for (StreamMember& me : g->h_mem) if (me.tap) (void)hipFree(me.tap);
-    for (GroupMember& me : g->mem) { if (me.sc.dev) (void)hipFree(me.sc.dev); if (me.al.dev) (void)hipFree(me.al.dev); }
+    for (GroupMember& me : g->mem) { if (me.sc.dev) (void)hipFree(me.sc.dev); if (me.al.dev) (void)hipFree(me.al.dev); if (me.tokens) (void)hipFree(me.tokens); }
+    for (void* p : {(void*)g->rope.dec, (void*)g->rope.enc}) if (p) (void)hipFree(p);
+    if (g->rope.h_dec) (void)hipHostFree(g->rope.h_dec); if (g->rope.h_enc) (void)hipHostFree(g->rope.h_enc);
+    if (g->rope.copied) (void)hipEventDestroy(g->rope.copied);
     for (size_t i = 0; i < g->mem.size(); i++) group_member_drop_rate(g, (int)i);
     for (void* p : {(void*)g->keep.p, (void*)g->d_ingest, (void*)g->s16_stage, (void*)g->kring, (void*)g->vring, (void*)g->dec_k, (void*)g->dec_v, (void*)g->samples, (void*)g->ws, (void*)g->tokens, (void*)g->state, (void*)g->d_mem, (void*)g->d_order,
                     (void*)g->qkv, (void*)g->att, (void*)g->logits, (void*)g->ssq, (void*)g->xf1, (void*)g->xf2, (void*)g->xf3, (void*)g->d_tab}) if (p) (void)hipFree(p);
     delete g;
 }
 // page_rows < 0: a slab group (pool_pages unread); else a paged one (0: the default page / the default pool)
+// endless (a paged group alone): max_positions is unread, the limit is the session limit 2^24
 static int32_t group_create(vox_model* m, const float* t_embed, int32_t n_members, const float* gains, const uint32_t* rates, int32_t enc_capacity_rows,
-                            int32_t max_positions, int32_t page_rows, int32_t pool_pages, vox_stream_group** out) {
+                            int32_t max_positions, int32_t page_rows, int32_t pool_pages, vox_stream_group** out, bool endless = false) {
     ARGCHK(n_members >= 1 && n_members <= GROUP_MAX, "n_members %d out of range (1..%d)", n_members, GROUP_MAX); ARGCHK(m && t_embed && out, "null argument");
     for (int i = 0; gains && i < n_members; i++) ARGCHK(std::isfinite(gains[i]), "gain of member %d is not finite", i);
     for (int i = 0; rates && i < n_members; i++) {      // every rate is checked before anything is allocated
@@ -3763,7 +3804,14 @@ static int32_t group_create(vox_model* m, const float* t_embed, int32_t n_member
     VOXCHK(ctx_bind(m->ctx));
     const vox_model_cfg& c = m->cfg; vox_ctx* cx = m->ctx; hipStream_t s = cx->stream;
     const bool paged = page_rows >= 0;
-    StreamGeom sg; VOXCHK(stream_geometry(m, enc_capacity_rows, max_positions, paged ? INT32_MAX : GROUP_DEFAULT_POSITIONS, &sg));      // (paged, 0: the session limit)
+    ARGCHK(!endless || paged, "internal: an endless group is a paged one");
+    StreamGeom sg; VOXCHK(stream_geometry(m, enc_capacity_rows, endless ? 0 : max_positions, paged ? INT32_MAX : GROUP_DEFAULT_POSITIONS, &sg));      // (paged, 0: the session limit)
+    if (endless) {
+        ARGCHK(c.dec_window >= 0, "an endless group needs a sliding decoder window");
+        // a pass runs at most the ticks whose samples the 65 536-sample ring holds: each of them has a row of its own in the member's RoPE rings
+        ARGCHK(feed_pass_max_ticks(c.reshape_factor) <= GROUP_ROPE_ROWS, "internal: a pass may run %d ticks, the RoPE rings hold %d rows per member", feed_pass_max_ticks(c.reshape_factor), GROUP_ROPE_ROWS);
+        sg.max_pos = STREAM_POS_LIMIT;
+    }
     if (paged) {
         if (page_rows == 0) page_rows = PAGE_ROWS_DEFAULT;
         ARGCHK(page_rows_ok(page_rows), "page_rows %d is not a power of two in %d..%d", page_rows, PAGE_ROWS_MIN, PAGE_ROWS_MAX);
@@ -3780,32 +3828,46 @@ static int32_t group_create(vox_model* m, const float* t_embed, int32_t n_member
                                    "a paged group (vox_stream_group_create_paged) has no such limit", sg.max_pos, most);
     }
     VOXCHK(enc_stream_rope_ensure(m));
-    vox_stream_group* g = new vox_stream_group(); g->m = m; g->ctx = cx; g->t_embed.assign(t_embed, t_embed + c.dec_dim); g->n = n_members; g->g = sg;
+    vox_stream_group* g = new vox_stream_group(); g->m = m; g->ctx = cx; g->t_embed.assign(t_embed, t_embed + c.dec_dim); g->n = n_members; g->g = sg; g->endless = endless;
     const size_t N = (size_t)n_members; const int D = c.dec_dim, QD = c.dec_heads * c.dec_head_dim, W = QD + 2 * c.dec_kv_heads * c.dec_head_dim, maxp = sg.max_pos;
     g->ring_layer = (size_t)c.enc_heads * sg.cap * c.enc_head_dim; g->ring_member = (size_t)c.enc_layers * g->ring_layer;
     g->seq_stride = (size_t)c.dec_kv_heads * maxp * c.dec_head_dim; g->layer_stride = N * g->seq_stride;
     if (paged) {
-        g->paged = true; g->pool.init(n_members, page_rows, c.dec_window, pool_pages, maxp);
+        g->paged = true;
+        if (endless) g->pool.init_ring(n_members, page_rows, c.dec_window, pool_pages, STREAM_POS_LIMIT); else g->pool.init(n_members, page_rows, c.dec_window, pool_pages, maxp);
         g->page_floats = (size_t)c.dec_kv_heads * page_rows * c.dec_head_dim; g->seq_stride = g->page_floats; g->layer_stride = (size_t)pool_pages * g->page_floats;
     }
     const size_t ws_b = stream_ws_carve(m, n_members, nullptr, nullptr) * 4, slab_b = (size_t)c.dec_layers * g->layer_stride * 4;
     hipError_t e = hipSuccess;
     auto A = [&](void** q, size_t nb, bool zero) { if (e == hipSuccess) { e = hipMalloc(q, nb); if (e == hipSuccess) { g->bytes += nb; if (zero) e = hipMemsetAsync(*q, 0, nb, s); } } };
     A((void**)&g->kring, N * g->ring_member * 4, false); A((void**)&g->vring, N * g->ring_member * 4, false); A((void**)&g->dec_k, slab_b, true); A((void**)&g->dec_v, slab_b, true);
-    A((void**)&g->samples, N * STREAM_SAMPLE_RING * 4, true); A((void**)&g->ws, ws_b, true); A((void**)&g->tokens, N * (maxp + 2) * 4, true); A((void**)&g->state, N * sizeof(int) * STRM_WORDS, true);
+    A((void**)&g->samples, N * STREAM_SAMPLE_RING * 4, true); A((void**)&g->ws, ws_b, true); if (!endless) A((void**)&g->tokens, N * (maxp + 2) * 4, true); A((void**)&g->state, N * sizeof(int) * STRM_WORDS, true);
     A((void**)&g->d_mem, N * sizeof(StreamMember), true); A((void**)&g->d_order, 5 * GROUP_MAX * 4, true);
-    if (paged) A((void**)&g->d_tab, N * (size_t)g->pool.max_pages * 4, false); A((void**)&g->d_ingest, sizeof(GroupIngest), true);
+    if (paged) A((void**)&g->d_tab, N * (size_t)g->pool.tab_len * 4, false); A((void**)&g->d_ingest, sizeof(GroupIngest), true);
     A((void**)&g->qkv, (size_t)GROUP_MAX * W * 4, true); A((void**)&g->att, (size_t)GROUP_MAX * QD * 4, true); A((void**)&g->logits, (size_t)GROUP_MAX * c.vocab * 4, true);
     A((void**)&g->ssq, (size_t)q4_skinny_resid_xf_parts(D) * 16 * 4, true); A((void**)&g->xf1, xf_bytes(D), true); A((void**)&g->xf2, xf_bytes(QD), true); A((void**)&g->xf3, xf_bytes(c.dec_ffn), true);
+    g->h_mem.resize(N); g->mem.resize(N);
+    if (endless) {      // the members' own token rows (counted per member: vox_stream_group_info), the RoPE rings and their pinned host images (group_rope_refill)
+        const size_t db = N * GROUP_ROPE_ROWS * c.dec_head_dim * 4, eb = N * GROUP_ROPE_ROWS * c.reshape_factor * c.enc_head_dim * 4;
+        for (size_t i = 0; i < N && e == hipSuccess; i++) {
+            g->mem[i].lists_cap = GROUP_LISTS_START; e = hipMalloc((void**)&g->mem[i].tokens, (size_t)(GROUP_LISTS_START + 2) * 4);
+            if (e == hipSuccess) e = hipMemsetAsync(g->mem[i].tokens, 0, (size_t)(GROUP_LISTS_START + 2) * 4, s);
+        }
+        A((void**)&g->rope.dec, db, true); A((void**)&g->rope.enc, eb, true);
+        if (e == hipSuccess) e = hipHostMalloc((void**)&g->rope.h_dec, db, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void**)&g->rope.h_enc, eb, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&g->rope.copied, hipEventDisableTiming);
+        g->rope.inv_d.resize((size_t)c.dec_head_dim / 2); g->rope.inv_e.resize((size_t)c.enc_head_dim / 2);
+        rope_inv_fill(c.dec_head_dim, c.rope_theta, g->rope.inv_d.data()); rope_inv_fill(c.enc_head_dim, c.rope_theta, g->rope.inv_e.data());
+    }
     if (e != hipSuccess) { (void)hipGetLastError(); group_release(g); return fail(VOX_ERR_HIP, "allocating the stream group's device state failed: %s", hipGetErrorString(e)); }
     g->d_pos = g->d_order + GROUP_MAX; g->d_kv_row = g->d_pos + GROUP_MAX; g->d_kv_page = g->d_kv_row + GROUP_MAX; g->d_kv_in = g->d_kv_page + GROUP_MAX;
-    if (paged) e = hipMemsetAsync(g->d_tab, 0xff, N * (size_t)g->pool.max_pages * 4, s);      // every entry -1
+    if (paged) e = hipMemsetAsync(g->d_tab, 0xff, N * (size_t)g->pool.tab_len * 4, s);      // every entry -1
     if (e != hipSuccess) { (void)hipGetLastError(); group_release(g); return fail(VOX_ERR_HIP, "initialising the stream group's page table failed: %s", hipGetErrorString(e)); }
-    g->h_mem.resize(N); g->mem.resize(N);
     for (size_t i = 0; i < N; i++) {
         StreamMember& me = g->h_mem[i]; me = StreamMember{};
         me.samples = g->samples + i * STREAM_SAMPLE_RING; me.gain = gains ? gains[i] : 1.0f; me.state = g->state + i * STRM_WORDS;
-        me.kring = g->kring + i * g->ring_member; me.vring = g->vring + i * g->ring_member; me.tokens = g->tokens + i * (size_t)(maxp + 2);
+        me.kring = g->kring + i * g->ring_member; me.vring = g->vring + i * g->ring_member; me.tokens = endless ? g->mem[i].tokens : g->tokens + i * (size_t)(maxp + 2);
     }
     int32_t r = ctx_mel_tables(cx, &g->mel);
     if (r == VOX_OK) r = group_upload_members(g);
@@ -3823,6 +3885,11 @@ extern "C" int32_t vox_stream_group_create_paged(vox_model* m, const float* t_em
     ARGCHK(page_rows >= 0, "page_rows %d is negative", page_rows);
     return group_create(m, t_embed, n_members, gains, rates, enc_capacity_rows, max_positions, page_rows, pool_pages, out);
 }
+extern "C" int32_t vox_stream_group_create_endless(vox_model* m, const float* t_embed, int32_t n_members, const float* gains, const uint32_t* rates, int32_t enc_capacity_rows,
+                                                   int32_t page_rows, int32_t pool_pages, vox_stream_group** out) {
+    ARGCHK(page_rows >= 0, "page_rows %d is negative", page_rows);
+    return group_create(m, t_embed, n_members, gains, rates, enc_capacity_rows, 0, page_rows, pool_pages, out, true);
+}
 extern "C" int32_t vox_stream_group_pool(const vox_stream_group* g, int64_t out[4], int32_t* held_or_null) {
     ARGCHK(g && out, "null argument");
     if (!g->paged) return fail(VOX_ERR_UNSUPPORTED, "a slab group has no page pool (vox_stream_group_create_paged makes a paged one)");
@@ -3834,8 +3901,8 @@ extern "C" int32_t vox_debug_stream_group_pages(const vox_stream_group* g, int32
     ARGCHK(g && n && (out || cap == 0) && cap >= 0, "bad argument"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1);
     if (!g->paged) return fail(VOX_ERR_UNSUPPORTED, "a slab group has no pages");
     const PagePool::Member& me = g->pool.mem[(size_t)member];
-    for (int q = me.first; q < me.end && q - me.first < cap; q++) out[q - me.first] = me.tab[(size_t)q];
-    *n = me.end - me.first;
+    for (int64_t q = me.first; q < me.end && q - me.first < cap; q++) out[q - me.first] = g->pool.at(member, q);
+    *n = (int32_t)(me.end - me.first);
     return VOX_OK;
 }
 extern "C" int32_t vox_stream_group_create(vox_model* m, const float* t_embed, int32_t n_members, const float* gains, int32_t enc_capacity_rows, int32_t max_positions,
@@ -3864,7 +3931,8 @@ extern "C" int32_t vox_stream_group_info(const vox_stream_group* g, int32_t memb
     const uint64_t tap_b = g->h_mem[member].tap ? (uint64_t)g->h_mem[member].tap_max * g->m->cfg.vocab * 4 : 0;
     const uint64_t rate_b = me.rate >= 0 ? (uint64_t)me.feed.in_ring_n * 4 + g->rates[(size_t)me.rate].bytes / (uint64_t)g->rates[(size_t)me.rate].refs : 0;
     feed_info(me.feed, R, g->g.cap, out);
-    out[5] = (int64_t)(g->bytes / (uint64_t)g->n + tap_b + rate_b + me.sc.bytes() + me.al.bytes());      // the member's share of the group's device state; its own input ring, its share of its rate's matrix, its score and alternatives records
+    const uint64_t tok_b = me.tokens ? (uint64_t)(me.lists_cap + 2) * 4 : 0;      // (an endless group's member: its own token row, as it is)
+    out[5] = (int64_t)(g->bytes / (uint64_t)g->n + tap_b + rate_b + tok_b + me.sc.bytes() + me.al.bytes());      // the member's share of the group's device state; its own input ring, its share of its rate's matrix, its score and alternatives records
     out[6] = 0; out[7] = (int64_t)me.steps;                      // no engine step; the member's ticks, each one row of an xf_chain step
     return VOX_OK;
 }
@@ -3872,13 +3940,15 @@ extern "C" int32_t vox_stream_group_info(const vox_stream_group* g, int32_t memb
 // one round: a tick of the first n_r members of the pass's order
 static int32_t group_round(vox_stream_group* g, const StreamWs& w, int n_r) {
     vox_model* m = g->m; const vox_model_cfg& c = m->cfg; hipStream_t s = g->ctx->stream; const int R = c.reshape_factor;
-    const StreamRound r{g->d_mem, g->d_order, n_r, g->g.cap, g->ring_layer, g->mel, g->g.left};
+    StreamRound r{g->d_mem, g->d_order, n_r, g->g.cap, g->ring_layer, g->mel, g->g.left};
+    if (g->endless) { r.rope = g->rope.enc; r.rope_stride = GROUP_ROPE_ROWS * R; r.rope_mask = r.rope_stride - 1; }      // every position: the member's ring row (group_rope_refill)
     VOXCHK(stream_encode_round(m, w, r, nullptr, nullptr));
     XfBufs xb{}; xb.h = w.h; xb.qkv = g->qkv; xb.att = g->att; xb.logits = g->logits; xb.ssq = g->ssq; xb.xf1 = g->xf1; xb.xf2 = g->xf2; xb.xf3 = g->xf3;
-    xb.k = g->dec_k; xb.v = g->dec_v; xb.layer_stride = g->layer_stride; xb.seq_stride = g->seq_stride; xb.max_seq = g->g.max_pos; xb.pos = g->d_pos; xb.kv_row = g->d_kv_row;
-    StreamPages pg{g->d_tab, g->pool.max_pages, g->pool.shift, g->d_kv_page, g->d_kv_in};
+    xb.k = g->dec_k; xb.v = g->dec_v; xb.layer_stride = g->layer_stride; xb.seq_stride = g->seq_stride; xb.max_seq = g->endless ? 0 : g->g.max_pos; xb.pos = g->d_pos; xb.kv_row = g->d_kv_row;      // (a paged step never reads max_seq)
+    StreamPages pg{g->d_tab, g->pool.tab_len, g->pool.shift, g->d_kv_page, g->d_kv_in, g->endless ? g->pool.tab_len : 0};
+    if (g->endless) { xb.page_tab_len = g->pool.tab_len; xb.rope_ring = g->rope.dec; xb.rope_mask = GROUP_ROPE_ROWS - 1; }
     if (g->paged) {
-        xb.page_tab = g->d_tab; xb.page_tab_stride = g->pool.max_pages; xb.page_shift = g->pool.shift; xb.page_floats = (long)g->page_floats; xb.kv_page = g->d_kv_page; xb.kv_in = g->d_kv_in;
+        xb.page_tab = g->d_tab; xb.page_tab_stride = g->pool.tab_len; xb.page_shift = g->pool.shift; xb.page_floats = (long)g->page_floats; xb.kv_page = g->d_kv_page; xb.kv_in = g->d_kv_in;
         xb.score_rows = c.dec_window >= 0 ? std::min(g->g.max_pos, c.dec_window + 1) : g->g.max_pos;
     }
     HIPCHK(launch_stream_group_embed(m->tok.w, g->d_mem, g->d_order, n_r, w.arow, c.dec_dim, w.h, g->xf1, m->dec[0].attn_norm, g->ssq, g->d_pos, g->d_kv_row, s, g->paged ? &pg : nullptr));
@@ -3913,6 +3983,9 @@ static int32_t group_plan_entries(const vox_stream_group* g, const vox_stream_fe
             const int need = g->pool.need(f.member, gf.plan.target); pages += need;
             ARGCHK(pages <= g->pool.n_free(), "entry %d: member %d: the call needs %d new pages of the pool (this member %d), %d are free (a reset returns a member's pages)", k, f.member,
                    pages, need, g->pool.n_free());
+            // a ring table has pool_pages entries: a member that would hold more than that needs more pages than the pool has -- the refusal above.  Stated here, and kept so
+            ARGCHK(!g->endless || g->pool.held(f.member) + need <= g->pool.tab_len, "entry %d: member %d would hold %d pages, its table has %d entries", k, f.member, g->pool.held(f.member) + need,
+                   g->pool.tab_len);
         }
     }
     return VOX_OK;
@@ -3920,7 +3993,7 @@ static int32_t group_plan_entries(const vox_stream_group* g, const vox_stream_fe
 // behind every check of a paged group's call: the entries' pages are taken, in entry order, and their table entries go up in front of the call's rounds
 static int32_t group_take_pages(vox_stream_group* g, const GroupCall& call) {
     for (const GroupFeed& e : call.fs) {
-        int q0, q1;
+        int64_t q0, q1;
         if (!g->pool.take(e.member, e.plan.target, &q0, &q1)) return fail(VOX_ERR_INVALID, "internal: member %d: the planned pages are not free", e.member);
         VOXCHK(group_table_upload(g, e.member, q0, q1));
     }
@@ -3930,7 +4003,7 @@ static int32_t group_take_pages(vox_stream_group* g, const GroupCall& call) {
 // call's rounds in stream order
 static int32_t group_release_pages(vox_stream_group* g, const GroupCall& call) {
     for (const GroupFeed& e : call.fs) {
-        int q0, q1; g->pool.release_below_window(e.member, g->mem[e.member].feed.pos, &q0, &q1);
+        int64_t q0, q1; g->pool.release_below_window(e.member, g->mem[e.member].feed.pos, &q0, &q1);
         VOXCHK(group_table_upload(g, e.member, q0, q1));
     }
     return VOX_OK;
@@ -3967,7 +4040,58 @@ static int32_t group_stage_pass(vox_stream_group* g, GroupCall& call, GroupDue* 
     return VOX_OK;
 }
 // the pass's rounds: the members sorted by ticks due, descending; round r runs one tick of the first n_r = #{ticks > r} of them
+// An endless group's member lists -- its token row, and the score and alternatives records it has -- hold fewer positions than the pass will reach: twice the positions
+// until they do (at most the session limit), the old entries copied over, the descriptor pointed at the new arrays (stream_lists_grow's rule; a group runs no engine,
+// so every point between two passes is a verification point).  A doubling synchronises once per list it has (list_grow: the token row, the score records, the
+// alternatives records) and once for the descriptor upload -- up to four times, 12 doublings at the most in a session's life.  Never trimmed:
+// vox_stream_group_info[5] counts them.
+static int32_t group_lists_grow(vox_stream_group* g, int member, int need_pos) {
+    GroupMember& me = g->mem[member]; hipStream_t s = g->ctx->stream;
+    while (need_pos > me.lists_cap) {
+        const int rows = (int)std::min<int64_t>(2LL * me.lists_cap, g->g.max_pos);
+        ARGCHK(rows > me.lists_cap, "internal: member %d's lists of %d positions cannot grow", member, me.lists_cap);
+        int tcap = me.lists_cap + 2;
+        VOXCHK(list_grow((void**)&me.tokens, &tcap, rows + 2, 4, s));
+        if (me.sc.dev) VOXCHK(me.sc.grow(rows + 2, s));
+        if (me.al.dev) VOXCHK(me.al.grow(rows + 2, s));
+        me.lists_cap = rows;
+        StreamMember& hm = g->h_mem[member]; hm.tokens = me.tokens;
+        if (hm.scores) { hm.scores = me.sc.dev; hm.scores_cap = me.sc.cap; }
+        if (hm.alts) { hm.alts = me.al.dev; hm.alts_cap = me.al.cap; }
+        VOXCHK(group_upload_members(g));      // synchronises
+    }
+    return VOX_OK;
+}
+// An endless group's RoPE rows for the ticks a pass is about to run: for every due member the decoder rows of positions pos .. pos + ticks - 1 into rows position & mask
+// of ITS decoder ring, the R ticks encoder rows likewise -- made by rope_row_fill (vox_host_base.h: the row function of rope_rows_fill and so of every table and of
+// vox_debug_rope_rows) from the factors computed once per group, in the rings'
+// pinned host images, copied on the group's stream in front of the pass's rounds (two copies where a span wraps).  The images are not rewritten while the last pass's
+// copies may be in flight: the event recorded behind them is waited for first (stream_rope_refill's rule) -- the host runs at most one pass ahead of the copies.
+static int32_t group_rope_refill(vox_stream_group* g, const GroupDue& due) {
+    const vox_model_cfg& c = g->m->cfg; hipStream_t s = g->ctx->stream; const int R = c.reshape_factor;
+    if (g->rope.pending) { HIPCHK(hipEventSynchronize(g->rope.copied)); g->rope.pending = false; }
+    auto fill = [&](float* host, float* dev, int member, int rows, int hd, const float* inv, int64_t first, int cnt, int64_t table_len) -> int32_t {
+        const int half = hd / 2; const int64_t mask = rows - 1; const size_t base = (size_t)member * rows * hd;
+        for (int i = 0; i < cnt; i++) { float* row = host + base + (size_t)((first + i) & mask) * hd; rope_row_fill(inv, half, first + i, table_len, row, row + half); }
+        const int r0 = (int)(first & mask), k = std::min(cnt, rows - r0);
+        HIPCHK(hipMemcpyAsync(dev + base + (size_t)r0 * hd, host + base + (size_t)r0 * hd, (size_t)k * hd * 4, hipMemcpyHostToDevice, s));
+        if (cnt > k) HIPCHK(hipMemcpyAsync(dev + base, host + base, (size_t)(cnt - k) * hd * 4, hipMemcpyHostToDevice, s));      // the span wrapped
+        return VOX_OK;
+    };
+    for (const std::pair<int, int>& d : due) {
+        const int pos0 = g->mem[d.second].feed.pos, n = d.first;
+        ARGCHK(n >= 1 && n <= GROUP_ROPE_ROWS, "internal: member %d: a pass of %d ticks, the RoPE rings hold %d rows per member", d.second, n, GROUP_ROPE_ROWS);
+        VOXCHK(fill(g->rope.h_dec, g->rope.dec, d.second, GROUP_ROPE_ROWS, c.dec_head_dim, g->rope.inv_d.data(), pos0, n, ROPE_DEC_TABLE_LEN));
+        VOXCHK(fill(g->rope.h_enc, g->rope.enc, d.second, GROUP_ROPE_ROWS * R, c.enc_head_dim, g->rope.inv_e.data(), (int64_t)g->g.RC + (int64_t)R * (pos0 - g->g.PC), R * n, ROPE_ENC_STREAM_TABLE_LEN));
+    }
+    HIPCHK(hipEventRecord(g->rope.copied, s)); g->rope.pending = true;
+    return VOX_OK;
+}
 static int32_t group_run_rounds(vox_stream_group* g, const StreamWs& w, GroupDue& due) {
+    if (g->endless) {
+        for (const std::pair<int, int>& d : due) VOXCHK(group_lists_grow(g, d.second, g->mem[d.second].feed.pos + d.first));
+        VOXCHK(group_rope_refill(g, due));
+    }
     std::stable_sort(due.begin(), due.end(), [](const std::pair<int, int>& a, const std::pair<int, int>& b) { return a.first > b.first; });
     g->orders.emplace_back(); std::array<int, GROUP_MAX>& ord = g->orders.back(); ord.fill(0);
     for (size_t i = 0; i < due.size(); i++) ord[i] = due[i].second;
@@ -4055,7 +4179,7 @@ static int32_t group_run(vox_stream_group* g, vox_stream_feed* feeds, int32_t n_
     if (r != VOX_OK) { (void)launch_stream_keep(keep, 1, s); (void)hipStreamSynchronize(s); g->orders.clear(); g->ingests.clear(); }      // a failed tail is taken back as well
     for (int k = 0; k < n; k++) { GroupMember& me = g->mem[call.fs[(size_t)k].member]; me.feed.rewind(was[(size_t)k].feed); me.steps = was[(size_t)k].steps; }
     if (g->paged) {      // the tail's pages go back: the pool, the tables and the peak are what they were (the device entries too, behind the tail in stream order)
-        std::vector<int> ends; for (int member : took) ends.push_back(g->pool.mem[(size_t)member].end);
+        std::vector<int64_t> ends; for (int member : took) ends.push_back(g->pool.mem[(size_t)member].end);
         g->pool.undo(pool_was, took);
         for (size_t k = 0; k < took.size(); k++) (void)group_table_upload(g, took[k], g->pool.mem[(size_t)took[k]].end, ends[k]);
     }
@@ -4074,7 +4198,7 @@ extern "C" int32_t vox_stream_group_set_scores(vox_stream_group* g, int32_t memb
     ARGCHK(g, "null group"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1); ARGCHK(on == 0 || on == 1, "on must be 0 or 1");
     VOXCHK(ctx_bind(g->ctx));
     ScoreState& sc = g->mem[member].sc;
-    if (on) { char whose[24]; snprintf(whose, sizeof whose, "member %d's", member); VOXCHK(sc.alloc(g->g.max_pos, whose)); }      // the group's logits rows are there already: a member needs its records alone
+    if (on) { char whose[24]; snprintf(whose, sizeof whose, "member %d's", member); VOXCHK(sc.alloc(g->endless ? g->mem[member].lists_cap : g->g.max_pos, whose)); }      // the group's logits rows are there already: a member needs its records alone
     HIPCHK(hipStreamSynchronize(g->ctx->stream));
     g->h_mem[member].scores = on ? sc.dev : nullptr; g->h_mem[member].scores_cap = on ? sc.cap : 0;
     VOXCHK(group_upload_members(g));
@@ -4090,7 +4214,7 @@ extern "C" int32_t vox_stream_group_set_alternatives(vox_stream_group* g, int32_
     ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1);
     VOXCHK(ctx_bind(g->ctx));
     AltsState& al = g->mem[member].al;
-    if (k > 0) { char whose[24]; snprintf(whose, sizeof whose, "member %d's", member); VOXCHK(al.alloc(g->g.max_pos, whose)); }      // (the group's logits rows are there already)
+    if (k > 0) { char whose[24]; snprintf(whose, sizeof whose, "member %d's", member); VOXCHK(al.alloc(g->endless ? g->mem[member].lists_cap : g->g.max_pos, whose)); }      // (the group's logits rows are there already)
     HIPCHK(hipStreamSynchronize(g->ctx->stream));
     StreamMember& hm = g->h_mem[member]; const StreamMember was = hm;
     hm.alts = k > 0 ? al.dev : nullptr; hm.alts_cap = k > 0 ? al.cap : 0; hm.alts_k = k;

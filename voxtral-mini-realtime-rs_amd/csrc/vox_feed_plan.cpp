@@ -80,6 +80,8 @@ int32_t feed_plan(const FeedState& f, int R, long left, int max_pos, size_t n, b
     ARGCHK(cap >= p.due, "%s: out_ids capacity %d < %d ids due", who, cap, p.due);
     *out = p; return VOX_OK;
 }
+// the most ticks one pass can have due: the ticks whose samples the 16 kHz ring holds at once, and the one a pass's first samples complete
+int feed_pass_max_ticks(int R) { return (int)(STREAM_SAMPLE_RING / stream_spp(R)) + 2; }
 bool feed_open(const FeedState& f, const FeedPlan& p) { return p.done < p.n + p.right || f.n_written < (int64_t)p.goal16 || f.pos < p.target; }
 }  // namespace vox_host
 // Advances in_written, n_written and p.done; NOT pos -- the caller runs the ticks.  in_cap: most input samples this pass (a group's 16-bit staging slot).

@@ -24,25 +24,28 @@ namespace vox_host {
 
 struct ResamplePlan { long fft_in = 0, fft_out = 0, new_len = 0, delay = 0; float cutoff = 0.f; };
 
-// RoPE rows (models/layers/rope.rs:35-64), the ONE implementation: the load-time tables (vox_model.cpp), the streaming encoder's table (vox_api.cpp) and
+// RoPE rows (models/layers/rope.rs:35-64), the ONE implementation (rope_row_fill, the row; rope_rows_fill, rows of it): the load-time tables (vox_model.cpp), the streaming encoder's table (vox_api.cpp) and
 // vox_debug_rope_rows are filled here.  Rows first .. first + n - 1 of cos / sin [n][hd / 2] (either may be null); inv (hd / 2 floats, may be null): the f32 factors.
 // Positions below table_len take the tables' formula -- the f32 product pos * inv, then f32 cos / sin: the bits every table has had.  From table_len on the angle is
 // double(pos) * double(inv), cos / sin in double, rounded to f32: the f32 product loses the angle at large positions (its spacing is about 0.5 rad at 4 M).
 inline const int ROPE_DEC_TABLE_LEN = 16384, ROPE_ENC_STREAM_TABLE_LEN = 1 << 16;
+// one row: cos / sin [half] of position pos from the f32 factors inv [half] (rope_inv_fill) -- the row arithmetic of every caller: rope_rows_fill below, and the
+// per-pass fill of an endless group's member rings (group_rope_refill, which computes inv once per group)
+inline void rope_inv_fill(int hd, float theta, float* inv_out) { for (int j = 0; j < hd / 2; j++) inv_out[j] = 1.0f / std::pow(theta, (float)(2 * j) / (float)hd); }
+inline void rope_row_fill(const float* inv, int half, int64_t pos, int64_t table_len, float* cos_out, float* sin_out) {
+    for (int j = 0; j < half; j++) {
+        float cv, sv;
+        if (pos < table_len) { const float fr = (float)pos * inv[j]; cv = std::cos(fr); sv = std::sin(fr); }
+        else { const double fr = (double)pos * (double)inv[j]; cv = (float)std::cos(fr); sv = (float)std::sin(fr); }
+        if (cos_out) cos_out[j] = cv;
+        if (sin_out) sin_out[j] = sv;
+    }
+}
 inline void rope_rows_fill(int hd, float theta, int64_t first, int64_t n, int64_t table_len, float* inv_out, float* cos_out, float* sin_out) {
     const int half = hd / 2;
-    for (int j = 0; j < half && inv_out; j++) inv_out[j] = 1.0f / std::pow(theta, (float)(2 * j) / (float)hd);
-    for (int64_t r = 0; r < n; r++) {
-        const int64_t i = first + r;
-        for (int j = 0; j < half; j++) {
-            const float inv = 1.0f / std::pow(theta, (float)(2 * j) / (float)hd);
-            float cv, sv;
-            if (i < table_len) { const float fr = (float)i * inv; cv = std::cos(fr); sv = std::sin(fr); }
-            else { const double fr = (double)i * (double)inv; cv = (float)std::cos(fr); sv = (float)std::sin(fr); }
-            if (cos_out) cos_out[(size_t)r * half + j] = cv;
-            if (sin_out) sin_out[(size_t)r * half + j] = sv;
-        }
-    }
+    std::vector<float> inv((size_t)half); rope_inv_fill(hd, theta, inv.data());      // (the factors once per call: the expression, and so the bits, of every table so far)
+    if (inv_out) std::memcpy(inv_out, inv.data(), (size_t)half * sizeof(float));
+    for (int64_t r = 0; r < n; r++) rope_row_fill(inv.data(), half, first + r, table_len, cos_out ? cos_out + (size_t)r * half : nullptr, sin_out ? sin_out + (size_t)r * half : nullptr);
 }
 }  // namespace vox_host
 
@@ -105,6 +108,7 @@ SlotSchedule slot_schedule(const std::vector<std::pair<int, int>>& jobs, int for
 int32_t stream_rate_plan(uint32_t sample_rate, ResamplePlan* rp, size_t* rs_bytes, int* in_ring_n);
 int32_t feed_plan(const FeedState& f, int R, long left, int max_pos, size_t n, bool finish, int cap, const char* who, FeedPlan* out);
 bool feed_open(const FeedState& f, const FeedPlan& p);
+int feed_pass_max_ticks(int R);
 FeedPass feed_pass(FeedState& f, FeedPlan& p, int R, long left, size_t in_cap);
 int32_t peek_second_pass(const char* who);
 int32_t peek_max_ticks(const FeedState& f, int R, int due, const char* who, int* T);

@@ -34,9 +34,12 @@ enum WFmt { WFMT_Q4_0 = 0, WFMT_BF16 = 1, WFMT_BF16X2 = 2, WFMT_F32 = 3 };
 enum Epi { EPI_STORE = 0, EPI_RESID = 1, EPI_SWIGLU = 2, EPI_ROPE_KV = 3, EPI_ARGMAX = 4, EPI_GELU = 5, EPI_SWIGLU_XF = 6, EPI_RESID_XF = 7,
            EPI_ROPE_ROWS = 8,        // launch_q4_gemm only: store, with RoPE (interleaved pairs, rope.rs:77-141) on the first n_q columns, row m at position pos[m] (or m % rope_seq_rows, or m) -- the encoder's q|k|v operator
            EPI_ROPE_KV_PAGED = 9,    // inside launch_q4_skinny only: EPI_ROPE_KV with GemmParams::kv_pos set runs as this instantiation
-           EPI_ROPE_KV_RING = 10 };  // launch_q4_gemv only (Q4 weights): EPI_ROPE_KV on a cache used as a RING of cache_head_stride / hd rows per KV head -- k / v go to cache row
+           EPI_ROPE_KV_RING = 10,    // launch_q4_gemv only (Q4 weights): EPI_ROPE_KV on a cache used as a RING of cache_head_stride / hd rows per KV head -- k / v go to cache row
                                      // pos % that -- with the RoPE row read from a session's RoPE ring: row pos & rope_mask of [rope_mask + 1][cos hd/2 | sin hd/2] (rope_cos = the ring,
                                      // rope_sin = the ring + hd / 2: rows are hd floats apart, not hd / 2).  An epilogue instantiation of its own: EPI_ROPE_KV compiles as it did
+           EPI_ROPE_KV_PAGED_RING = 11 };  // inside launch_q4_skinny only: EPI_ROPE_KV_PAGED with GemmParams::rope_member set (an endless paged group) -- the RoPE row is read from the
+                                     // group's member-strided RoPE ring: row rope_member[m] * (rope_mask + 1) + (pos[m] & rope_mask) of [members][rope_mask + 1][cos hd/2 | sin hd/2]
+                                     // (rope_cos = the ring, rope_sin = the ring + hd / 2).  An epilogue instantiation of its own: the other two compile as they did
 // (M <= 16 only) _SWIGLU_XF: SwiGLU written as XF planes; _RESID_XF: out = acc + resid as f32 AND as XF planes of out * xf_w (* xf_w2) plus
 // per-workgroup partial sums of squares -- the next RMSNorm is folded into its producer and its consumer (GemmParams::ssq_part)
 enum Pro { PRO_NONE = 0, PRO_RMS = 1, PRO_RMS_MUL = 2,      // RMS_MUL: RMSNorm then * mul (the cached Ada scale)
@@ -90,6 +93,7 @@ struct GemmParams {
     const int* kv_row;    // EPI_ROPE_KV, optional: row m writes into cache slice kv_row[m] instead of slice m (continuous batching: a SLOT of the step decodes whichever utterance it currently holds)
     const int* kv_pos;    // EPI_ROPE_KV, optional (the <= 16-row XF form alone, an epilogue instantiation of its own): row m's row INSIDE its slice; null: pos[m], the address of every contiguous cache.  A paged cache
                           // (a paged stream group) passes kv_row[m] = the physical page, kv_seq_stride = the floats of a page, kv_head_stride = page_rows * hd, kv_pos[m] = pos[m] % page_rows
+    const int* rope_member; int rope_mask;      // EPI_ROPE_KV with kv_pos, optional (EPI_ROPE_KV_PAGED_RING): row m's member of a member-strided RoPE ring of rope_mask + 1 rows (a power of two) per member
     int tl_slot;          // timeline slot (measurement builds, -DVOX_TIMELINE)
     // split-K (q4_gemm_kernel only, EPI_STORE): blockIdx.z = K slice; slice z writes its partial product to out + z * M * out_stride (bias in slice 0).
     // The consumer (launch_rms_norm_sumk) adds the slices in a fixed order -- for few-column GEMMs (the encoder's N = 1280 w2: 40 K-steps per workgroup)
@@ -172,6 +176,9 @@ struct AttnParams {
     // page_floats per page); page_tab[kv_row[s] * page_tab_stride + q] = the physical page of logical page q (rows q << page_shift ..) of sequence s, read only for the
     // pages of the window; score_rows: LDS score rows per query head, >= the most keys a query attends (min(max positions, window + 1))
     const int* page_tab; int page_tab_stride, page_shift, score_rows; long page_floats;
+    // 0: the table row is flat, entry q = logical page q.  L > 0 (an endless paged group): the row is a RING of L entries, logical page q at entry q % L -- a sequence
+    // holds at most L pages at a time, so the window's pages never collide; L <= page_tab_stride, any L >= 1 (no power of two)
+    int page_tab_len;
 };
 hipError_t launch_attn_prefill(const AttnParams& p, int hd, hipStream_t s, int n_seq = 1);     // M > 1, causal (+window)
 bool attn_prefill_prefix_ok(const AttnParams& p, int hd, int n_seq);     // may launch_attn_prefill take p's two K / V segments (prefix_len > 0)?
@@ -197,6 +204,7 @@ enum AttnForm { ATTN_FORM_PREFILL_SMALL, ATTN_FORM_PREFILL_MFMA, ATTN_FORM_PREFI
                 ATTN_FORM_ENGINE, ATTN_FORM_STREAM_RING, ATTN_FORM_GROUP_RESAMPLE, ATTN_FORM_STREAM_RESAMPLE,
                 ATTN_FORM_DECODE_PAGED, ATTN_FORM_DECODE_GQA_PAGED,      // the paged decode forms (launch_attn_decode_paged), behind every earlier slot
                 ATTN_FORM_DECODE_RING,                                   // the ring decode form (launch_attn_decode_ring)
+                ATTN_FORM_DECODE_PAGED_RING, ATTN_FORM_DECODE_GQA_PAGED_RING,      // the paged decode forms on a ring table (AttnParams::page_tab_len > 0)
                 ATTN_FORM_COUNT };
 void attn_form_note(AttnForm f);
 void attn_form_counts(unsigned long long out[ATTN_FORM_COUNT]);
@@ -447,6 +455,8 @@ struct StreamAttnParams {
     int M, n_heads, window;
     int rope_mask;                           // 0 (the default): cos_t / sin_t are tables, row = the position.  > 0 (an endless session past its wrap): cos_t is a RoPE ring of
                                              // rope_mask + 1 rows [cos hd/2 | sin hd/2] (sin_t = cos_t + hd / 2), row = position & rope_mask, refilled by the host for the tick's positions
+    int rope_stride;                         // with rope_mask > 0: 0 (the default) one ring for every slot; > 0 (an endless group): a ring per session, rope_stride rows apart --
+                                             // slot z reads row order[z] * rope_stride + (position & rope_mask)
 };
 hipError_t launch_stream_attn(const StreamAttnParams& p, int hd, hipStream_t s);
 // rows 0 .. rows-1 of every layer's ring from token-major k | v rows (the model's prefix state: [layers][rows][k row | v row])
@@ -462,7 +472,8 @@ hipError_t launch_stream_advance(const float* part_val, const int* part_idx, int
 // input rows: h[r] = audio[r] + embed(tokens[STRM_POS]) as f32, as layer 0's XF planes of h * xf_w with the row's sum of squares (what launch_argmax_embed_batch forms),
 // pos[r] = STRM_POS and kv_row[r] = order[r]: the positions and cache slices xf_chain reads
 // pages (a paged group): also page_out[r] = the table entry of the row's position (tab[order[r] * tab_stride + pos >> shift]) and in_page_out[r] = pos % page_rows
-struct StreamPages { const int* tab; int tab_stride, shift; int* page_out; int* in_page_out; };
+// tab_len > 0 (an endless group): the table row is a ring of tab_len entries, the entry is (pos >> shift) % tab_len (AttnParams::page_tab_len)
+struct StreamPages { const int* tab; int tab_stride, shift; int* page_out; int* in_page_out; int tab_len; };
 hipError_t launch_stream_group_embed(Q4W tok, const StreamMember* mem, const int* order, int n, const float* audio, int D, float* h, uint16_t* xf, const float* xf_w,
                                      float* ssq_out, int* pos, int* kv_row, hipStream_t s, const StreamPages* pages = nullptr);
 // a paged member's seed: rows 0 .. rows-1 of src_k / src_v [layers][kv_heads][rows][hd] into the pages tab[0 ..] of the pool (layers layer_stride floats apart)

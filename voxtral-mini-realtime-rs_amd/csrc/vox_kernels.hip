@@ -1181,7 +1181,8 @@ __global__ __launch_bounds__(NTW == 3 ? 256 : 512, NTW == 3 ? 3 : 1) void q4_ski
     __shared__ float s_rstd[16]; __shared__ float s_pp[32 * 16];
     // EPI_ROPE_KV_PAGED: EPI_ROPE_KV with the row inside the cache slice taken from p.kv_pos (a paged cache) -- an instantiation of its own, so that the epilogue of
     // every contiguous cache stays the code it was
-    constexpr bool KVP = EPI == EPI_ROPE_KV_PAGED, ROPE_KV = EPI == EPI_ROPE_KV || KVP;
+    // EPI_ROPE_KV_PAGED_RING: the paged epilogue with the RoPE row read from a member-strided RoPE ring (p.rope_member, p.rope_mask; rows hd floats apart: cos | sin)
+    constexpr bool KVR = EPI == EPI_ROPE_KV_PAGED_RING, KVP = EPI == EPI_ROPE_KV_PAGED || KVR, ROPE_KV = EPI == EPI_ROPE_KV || KVP;
     const int nb = p.w.nb, N = p.w.N, M = p.M, nq = nb >> 2;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, KS = blockDim.x >> 6;
     const int g = lane >> 4, li = lane & 15;
@@ -1263,8 +1264,8 @@ __global__ __launch_bounds__(NTW == 3 ? 256 : 512, NTW == 3 ? 3 : 1) void q4_ski
     // branch around a load makes hipcc drain vmcnt).  vmcnt retires IN ORDER and these words were written by the previous launches on other XCDs
     // (memory round trips): the straight-line path requests them BEHIND its first K step's operands, so that step does not wait for them.
     float pv[12]; const int prow = tid & 15, pch = tid >> 4, nch = blockDim.x >> 4;
-    float pre_res[4] = {0.f, 0.f, 0.f, 0.f}; float pre_xw = 0.f; int pre_pos[4] = {0, 0, 0, 0}; int pre_row[4] = {0, 0, 0, 0}; int pre_kvp[4] = {0, 0, 0, 0};
-#define VOX_PRELOADS                                                                                       \
+    float pre_res[4] = {0.f, 0.f, 0.f, 0.f}; float pre_xw = 0.f; int pre_pos[4] = {0, 0, 0, 0}; int pre_row[4] = {0, 0, 0, 0}; int pre_kvp[4] = {0, 0, 0, 0}; int pre_mem[4] = {0, 0, 0, 0};
+#define VOX_PRELOADS                                                                                      \
     {                                                                                                      \
         if (PRO) {                                                                                         \
             _Pragma("unroll") for (int u = 0; u < 12; u++) {                                               \
@@ -1282,6 +1283,7 @@ __global__ __launch_bounds__(NTW == 3 ? 256 : 512, NTW == 3 ? 3 : 1) void q4_ski
             _Pragma("unroll") for (int r = 0; r < 4; r++) pre_pos[r] = p.pos[min(4 * g + r, M - 1)];       \
             _Pragma("unroll") for (int r = 0; r < 4; r++) pre_row[r] = p.kv_row ? p.kv_row[min(4 * g + r, M - 1)] : min(4 * g + r, M - 1); \
             if (KVP) { _Pragma("unroll") for (int r = 0; r < 4; r++) pre_kvp[r] = p.kv_pos[min(4 * g + r, M - 1)]; } \
+            if (KVR) { _Pragma("unroll") for (int r = 0; r < 4; r++) pre_mem[r] = p.rope_member[min(4 * g + r, M - 1)]; } \
         }                                                                                                  \
     }
     constexpr bool STRAIGHT = STEPS > 0 && TILED && XIN;
@@ -1408,7 +1410,9 @@ __global__ __launch_bounds__(NTW == 3 ? 256 : 512, NTW == 3 ? 3 : 1) void q4_ski
                     const int cp = KVP ? (pre ? pre_kvp[r] : p.kv_pos[m]) : ps;      // its row inside the slice: the position, or a paged cache's row inside the page
                     if (n < p.n_q + kd) {
                         const int dd = n % p.hd;
-                        const size_t ti = (size_t)ps * (p.hd >> 1) + (dd >> 1);
+                        // the RoPE row: the table's row of the position, or the member's ring row of it (ring rows hold cos | sin: hd floats apart)
+                        const size_t ti = KVR ? ((size_t)(pre ? pre_mem[r] : p.rope_member[m]) * (size_t)(p.rope_mask + 1) + (size_t)(ps & p.rope_mask)) * p.hd + (dd >> 1)
+                                              : (size_t)ps * (p.hd >> 1) + (dd >> 1);
                         const float c = p.rope_cos[ti], sn = p.rope_sin[ti];
                         const float o = (n & 1) ? other * sn + v * c : v * c - other * sn;
                         if (n < p.n_q) p.out[(size_t)m * p.out_stride + n] = o;
@@ -2468,7 +2472,7 @@ hipError_t launch_transpose(const float* in, int R, int C, float* out, hipStream
 
 template <int NTW, int TILED>
 static hipError_t skinny_launch_n(const GemmParams& p, int epi, int ks, hipStream_t s) {
-    if (epi == EPI_ROPE_KV && p.kv_pos) epi = EPI_ROPE_KV_PAGED;      // (launch_q4_gemm_epi admits kv_pos with XF input alone)
+    if (epi == EPI_ROPE_KV && p.kv_pos) epi = p.rope_member ? EPI_ROPE_KV_PAGED_RING : EPI_ROPE_KV_PAGED;      // (launch_q4_gemm_epi admits kv_pos with XF input alone, rope_member with kv_pos alone)
     dim3 grid((p.w.N + 16 * NTW - 1) / (16 * NTW));
     const size_t lds = (size_t)ks * NTW * 64 * 4 * sizeof(float);
     if (p.xf) {      // fragment-ordered bf16 hi/lo input (batched decode step); tile-ordered weights only
@@ -2481,7 +2485,7 @@ static hipError_t skinny_launch_n(const GemmParams& p, int epi, int ks, hipStrea
 #define VOX_ST(N_, E_, P_, S_) if (NTW == N_ && epi == E_ && (int)pro == P_ && per == S_) { \
             if (E_ == EPI_RESID_XF && (!p.xf_out || !p.xf_w || !p.ssq_out)) return hipErrorInvalidValue; \
             q4_skinny_kernel<N_, E_, 1, 1, P_, S_><<<grid, dim3(64 * ks), lds, s>>>(p); return hipGetLastError(); }
-            VOX_ST(2, EPI_ROPE_KV, 1, 3) VOX_ST(2, EPI_ROPE_KV_PAGED, 1, 3) VOX_ST(2, EPI_SWIGLU_XF, 1, 6) VOX_ST(1, EPI_SWIGLU_XF, 1, 6) VOX_ST(1, EPI_RESID_XF, 0, 4) VOX_ST(4, EPI_SWIGLU_XF, 1, 6) VOX_ST(1, EPI_RESID_XF, 0, 9) VOX_ST(4, EPI_STORE, 1, 6)
+            VOX_ST(2, EPI_ROPE_KV, 1, 3) VOX_ST(2, EPI_ROPE_KV_PAGED, 1, 3) VOX_ST(2, EPI_ROPE_KV_PAGED_RING, 1, 3) VOX_ST(2, EPI_SWIGLU_XF, 1, 6) VOX_ST(1, EPI_SWIGLU_XF, 1, 6) VOX_ST(1, EPI_RESID_XF, 0, 4) VOX_ST(4, EPI_SWIGLU_XF, 1, 6) VOX_ST(1, EPI_RESID_XF, 0, 9) VOX_ST(4, EPI_STORE, 1, 6)
 #undef VOX_ST
         }
         if (epi == EPI_RESID_XF) {
@@ -2492,6 +2496,7 @@ static hipError_t skinny_launch_n(const GemmParams& p, int epi, int ks, hipStrea
             case EPI_STORE: q4_skinny_kernel<NTW, EPI_STORE, 1, 1, 1><<<grid, dim3(64 * ks), lds, s>>>(p); break;
             case EPI_ROPE_KV: q4_skinny_kernel<NTW, EPI_ROPE_KV, 1, 1, 1><<<grid, dim3(64 * ks), lds, s>>>(p); break;
             case EPI_ROPE_KV_PAGED: q4_skinny_kernel<NTW, EPI_ROPE_KV_PAGED, 1, 1, 1><<<grid, dim3(64 * ks), lds, s>>>(p); break;
+            case EPI_ROPE_KV_PAGED_RING: q4_skinny_kernel<NTW, EPI_ROPE_KV_PAGED_RING, 1, 1, 1><<<grid, dim3(64 * ks), lds, s>>>(p); break;
             case EPI_SWIGLU_XF: q4_skinny_kernel<NTW, EPI_SWIGLU_XF, 1, 1, 1><<<grid, dim3(64 * ks), lds, s>>>(p); break;
             default: return hipErrorInvalidValue;
             }
@@ -2596,6 +2601,7 @@ static hipError_t launch_q4_gemm_epi(const GemmParams& p, int epi_in, hipStream_
     int epi = epi_in == EPI_ROPE_ROWS ? EPI_STORE : epi_in;      // (EPI_ROPE_ROWS: only the large-M kernel below takes it; the others store, the caller ropes)
     if (p.w.K % 32 || p.M <= 0) return hipErrorInvalidValue;
     if (p.kv_pos && !(p.xf && p.M <= 16)) return hipErrorInvalidValue;      // a row inside the slice: q4_skinny_kernel's epilogue alone takes it
+    if (p.rope_member && (!p.kv_pos || p.rope_mask < 0 || (p.rope_mask & (p.rope_mask + 1)))) return hipErrorInvalidValue;      // a member RoPE ring: the paged epilogue's, a power of two rows per member
     if (p.ksplit > 1 && (p.M <= 48 || p.xf || p.w.nb % 4 || p.w.fmt == WFMT_F32)) return hipErrorInvalidValue;      // split-K exists in q4_gemm_kernel only
     if (p.w.fmt == WFMT_F32) {      // true-f32 dense weights: bf16 hi + lo planes on the matrix cores (3 MFMAs per product, f32-class like the conv stem)
         if (p.xf) return hipErrorInvalidValue;
@@ -3581,8 +3587,14 @@ __global__ __launch_bounds__(256) void attn_decode_gqa_kernel(const AttnParams p
 // are never read (released pages hold -1 there).
 __device__ __forceinline__ KvRowsPaged attn_stage_pages(const AttnParams& p, int seq, int kvh, int pos, int* __restrict__ ptab) {
     const int j_lo = p.window >= 0 ? max(0, pos - p.window) : 0, q0 = j_lo >> p.page_shift, nq = (pos >> p.page_shift) - q0 + 1;
-    const int* tab = p.page_tab + (size_t)(p.kv_row ? p.kv_row[seq] : seq) * p.page_tab_stride + q0;
-    for (int i = threadIdx.x; i < nq; i += 256) ptab[i] = tab[i];
+    const int* tab = p.page_tab + (size_t)(p.kv_row ? p.kv_row[seq] : seq) * p.page_tab_stride;
+    if (p.page_tab_len > 0) {      // a ring table: logical page q at entry q % L.  s0 = q0 % L is the only division; nq <= L (the member holds no more), so s0 + i is less at most one L
+        const int L = p.page_tab_len, s0 = q0 % L;
+        for (int i = threadIdx.x; i < nq; i += 256) { int t = s0 + i; t -= t >= L ? L : 0; ptab[i] = tab[t]; }
+    } else {
+        tab += q0;
+        for (int i = threadIdx.x; i < nq; i += 256) ptab[i] = tab[i];
+    }
     __syncthreads();
     const size_t ho = (size_t)kvh * p.kv_head_stride;
     return KvRowsPaged{p.k + ho, p.v + ho, ptab, q0, p.page_shift, (1 << p.page_shift) - 1, p.kv_row_stride, (size_t)p.page_floats};
@@ -3786,6 +3798,10 @@ hipError_t launch_attn_decode_paged(const AttnParams& p_in, int hd, hipStream_t 
     const int page_rows = 1 << p.page_shift, win = p.window >= 0 ? p.window : p.score_rows - 1;
     if (!p.page_tab || !p.pos_ptr || !p.pos_per_seq || p.page_shift < 4 || p.page_shift > 10 || p.kv_row_stride != hd || p.kv_head_stride != page_rows * hd || p.score_rows < 1 ||
         p.page_floats != (long)p.n_kv_heads * page_rows * hd || p.page_tab_stride < 1 || win / page_rows + 2 > ATTN_PAGE_TAB_MAX || n_seq < 1) return hipErrorInvalidValue;
+    // a ring table: its entries lie inside the row.  (That a sequence's window spans at most page_tab_len pages is the table owner's invariant -- a member of an endless
+    // group holds no more pages than its table has entries -- and vox_debug_attn_decode_paged_ring's check.)
+    const bool tab_ring = p.page_tab_len != 0;
+    if (tab_ring && (p.page_tab_len < 1 || p.page_tab_len > p.page_tab_stride || p.window < 0)) return hipErrorInvalidValue;
     const size_t lds = (size_t)p.score_rows * sizeof(float);
     if (hd == 128 && p.n_heads == 4 * p.n_kv_heads) {
         auto kern = attn_decode_gqa_kernel<4, true>;
@@ -3793,21 +3809,21 @@ hipError_t launch_attn_decode_paged(const AttnParams& p_in, int hd, hipStream_t 
         hipError_t e = ensure_dyn_lds(kern, 4 * lds, &attr_done);
         if (e != hipSuccess) return e;
         kern<<<dim3(p.n_kv_heads, n_seq), dim3(256), 4 * lds, s>>>(p);
-        attn_form_note(ATTN_FORM_DECODE_GQA_PAGED);
+        attn_form_note(tab_ring ? ATTN_FORM_DECODE_GQA_PAGED_RING : ATTN_FORM_DECODE_GQA_PAGED);
     } else if (hd == 128) {
         auto kern = attn_decode_paged_kernel<128>;
         static DevOnce attr_done;
         hipError_t e = ensure_dyn_lds(kern, lds, &attr_done);
         if (e != hipSuccess) return e;
         kern<<<dim3(p.n_heads, n_seq), dim3(256), lds, s>>>(p);
-        attn_form_note(ATTN_FORM_DECODE_PAGED);
+        attn_form_note(tab_ring ? ATTN_FORM_DECODE_PAGED_RING : ATTN_FORM_DECODE_PAGED);
     } else if (hd == 64) {
         auto kern = attn_decode_paged_kernel<64>;
         static DevOnce attr_done;
         hipError_t e = ensure_dyn_lds(kern, lds, &attr_done);
         if (e != hipSuccess) return e;
         kern<<<dim3(p.n_heads, n_seq), dim3(256), lds, s>>>(p);
-        attn_form_note(ATTN_FORM_DECODE_PAGED);
+        attn_form_note(tab_ring ? ATTN_FORM_DECODE_PAGED_RING : ATTN_FORM_DECODE_PAGED);
     } else return hipErrorInvalidValue;
     return hipGetLastError();
 }
@@ -4537,7 +4553,8 @@ __global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_attn_kernel(const St
     const int enc_pos = me.state[STRM_ENC_POS], qpos = enc_pos + m, QD = p.n_heads * HD;
     for (int i = tid; i < (m + 2) * HALF; i += 256) {      // k rows 0 .. m, then the query row
         const int r = i / HALF, j = i - r * HALF; const bool isq = r == m + 1; const int row = isq ? m : r;
-        const size_t ti = p.rope_mask ? (size_t)((enc_pos + row) & p.rope_mask) * HD + j : (size_t)(enc_pos + row) * HALF + j;      // (a RoPE ring's rows: cos | sin, HD floats apart)
+        // (a RoPE ring's rows: cos | sin, HD floats apart; rope_stride > 0: the session's own ring, rope_stride rows after the one before)
+        const size_t ti = p.rope_mask ? ((size_t)p.order[blockIdx.z] * p.rope_stride + (size_t)((enc_pos + row) & p.rope_mask)) * HD + j : (size_t)(enc_pos + row) * HALF + j;
         const float c = p.cos_t[ti], sn = p.sin_t[ti];
         const float* src = qkv + (size_t)row * p.qkv_stride + (isq ? 0 : QD) + h * HD + 2 * j;
         const float xr = src[0], xi = src[1];
@@ -4597,7 +4614,7 @@ __global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_attn_kernel(const St
 hipError_t launch_stream_attn(const StreamAttnParams& p, int hd, hipStream_t s) {
     // (the ring rows are read as float4: the sessions' rings are hipMalloc'd, a layer's offset is a multiple of hd, hd % 4 == 0 holds for 64 / 128)
     if (p.M < 1 || p.M > 8 || p.n < 1 || p.n > 16 || !p.mem || !p.order || p.window < 0 || p.window + 1 > 1024 || p.cap <= p.window + p.M || (p.ring_off & 3) || p.rope_mask < 0 ||
-        (p.rope_mask & (p.rope_mask + 1)) || (p.rope_mask && p.rope_mask + 1 < p.M)) return hipErrorInvalidValue;
+        (p.rope_mask & (p.rope_mask + 1)) || (p.rope_mask && p.rope_mask + 1 < p.M) || (p.rope_stride && (!p.rope_mask || p.rope_stride < p.rope_mask + 1))) return hipErrorInvalidValue;
     attn_form_note(ATTN_FORM_STREAM_RING);
     if (hd == 64) stream_attn_kernel<64><<<dim3(p.n_heads, p.M, p.n), dim3(256), 0, s>>>(p);
     else if (hd == 128) stream_attn_kernel<128><<<dim3(p.n_heads, p.M, p.n), dim3(256), 0, s>>>(p);
@@ -4683,14 +4700,17 @@ __global__ __launch_bounds__(256) void stream_group_embed_kernel(Q4W tok, const 
     xf_row_ssq(hrow, xf_w, D, xf, r, ssq_out, wsum);
     if (threadIdx.x == 0) {
         pos_out[r] = pos; kv_row_out[r] = member;
-        if (PAGED) { pg.page_out[r] = pg.tab[(size_t)member * pg.tab_stride + (pos >> pg.shift)]; pg.in_page_out[r] = pos & ((1 << pg.shift) - 1); }
+        if (PAGED) {      // (a ring table: the entry of logical page q is q % tab_len -- one thread, one division)
+            const int q = pos >> pg.shift;
+            pg.page_out[r] = pg.tab[(size_t)member * pg.tab_stride + (pg.tab_len > 0 ? q % pg.tab_len : q)]; pg.in_page_out[r] = pos & ((1 << pg.shift) - 1);
+        }
     }
 }
 hipError_t launch_stream_group_embed(Q4W tok, const StreamMember* mem, const int* order, int n, const float* audio, int D, float* h, uint16_t* xf, const float* xf_w,
                                      float* ssq_out, int* pos, int* kv_row, hipStream_t s, const StreamPages* pages) {
     if (n < 1 || n > 16 || !mem || !order || !audio || !h || !xf || !xf_w || !ssq_out || !pos || !kv_row || (D & 127)) return hipErrorInvalidValue;
     if (pages) {
-        if (!pages->tab || !pages->page_out || !pages->in_page_out || pages->tab_stride < 1 || pages->shift < 4 || pages->shift > 10) return hipErrorInvalidValue;
+        if (!pages->tab || !pages->page_out || !pages->in_page_out || pages->tab_stride < 1 || pages->shift < 4 || pages->shift > 10 || pages->tab_len < 0 || pages->tab_len > pages->tab_stride) return hipErrorInvalidValue;
         stream_group_embed_kernel<true><<<dim3(n), dim3(256), 0, s>>>(tok, mem, order, audio, D, h, xf, xf_w, ssq_out, pos, kv_row, *pages);
     } else stream_group_embed_kernel<false><<<dim3(n), dim3(256), 0, s>>>(tok, mem, order, audio, D, h, xf, xf_w, ssq_out, pos, kv_row, StreamPages{});
     return hipGetLastError();
