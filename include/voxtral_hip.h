@@ -424,7 +424,7 @@ int32_t vox_debug_reload_knobs(void);
 /* Test hook: attention launches enqueued by this process so far, by kernel form (host-side counts; the replays of a captured graph are not counted):
  * out[0] short-sequence prefill, [1] MFMA prefill, [2] f32 VALU prefill (VOX_ATTN_F32), [3] single-query decode, [4] its speculative-row form (VOX_ATTN_SPEC),
  * [5] batched GQA decode, [6] fused attention + wo, [7] single-stream decode-engine launches (the whole step), [8] the live stream's ring attention (RoPE + K / V append + windowed
- * attention in one launch: exactly enc_layers per tick of a vox_stream).  Behind them, not attention: [9] a stream group's resampling ingest (one launch per pass for
+ * attention in one launch: exactly enc_layers per tick of a vox_stream, one per vox_debug_stream_attn call; a refused launch counts nothing).  Behind them, not attention: [9] a stream group's resampling ingest (one launch per pass for
  * all fed members), [10] a solo stream's.  Behind those, attention again: [11] paged single-query decode, [12] paged batched GQA decode (a paged stream group's step:
  * PAGED DECODER CACHE below).  [13] ring single-query decode (vox_debug_attn_decode_ring below): 0 unless a ring launch ran.  [14] paged single-query decode on a RING page table, [15] paged batched
  * GQA decode on one (an endless paged group's step, ENDLESS PAGED GROUPS below; vox_debug_attn_decode_paged_ring): such a launch counts here and not in [11] [12].
@@ -476,6 +476,39 @@ int32_t vox_debug_attn_decode_paged_ring(vox_ctx* ctx, const vox_attn_decode_des
  * there on cos / sin are taken of double(pos) * double(inv) and rounded to f32 -- the f32 product loses the angle at large positions (its spacing is about 0.5 rad
  * at position 4 M). */
 int32_t vox_debug_rope_rows(int32_t head_dim, float theta, int64_t first_pos, int32_t n, float* inv_out, float* cos_out, float* sin_out);
+/* One launch of the live sessions' encoder ring attention on its own (tests): RoPE on q and k, the K / V append into each served session's ring and the windowed
+ * softmax, as every tick of a vox_stream or a stream group runs it once per encoder layer -- exactly ONE launch, counted in vox_debug_attn_launches [8]; nothing of a
+ * model is needed.
+ *   Geometry: n_slots (1..16) slots serve the DISTINCT members order[z] of n_members (n_slots..64) sessions; member c stands at encoder position enc_pos[c] and slot
+ *   z's `rows` (1..8) new rows are the positions enc_pos[order[z]] + m.  n_heads (1..32) heads of head_dim 64 or 128; row m attends the keys
+ *   max(0, p - window) .. p of its position p, window 0..1023; every ring holds cap rows per head, window + rows < cap <= 16384; the launch works on layer `layer` of
+ *   `layers` (1..8): the ring offset layer * n_heads * cap * head_dim.
+ *   qkv: host [n_slots * rows][q | k | v], each n_heads * head_dim wide, NOT rotated.  kring / vring: host [n_members][layers][n_heads][cap][head_dim], in and out:
+ *   position j of a member lives at ring row j % cap; after the launch rows (enc_pos + r) % cap, r < rows, of the served members' layer hold the rotated k and the
+ *   raw v, every other word its bits from before.  out: host [n_slots * rows][n_heads * head_dim]; it is NaN before the launch, so an unwritten row shows.
+ *   RoPE rows (theta; made by the function behind vox_debug_rope_rows, so they have that call's bits for the same head_dim):
+ *     rope_rows == 0: a flat table of the rows 0 .. the largest position; enc_pos[c] + rows <= 65536, the streaming encoder's table length, for every member.
+ *     rope_rows == R (a power of two, rows <= R <= 4096): a RoPE ring of R rows holding the rows (enc_pos[c] + r) & (R - 1), r < rows, of every SERVED member and
+ *       NaN everywhere else -- what an endless session's refill writes; positions below 2^24 (enc_pos[c] + rows <= 2^24); two served members that need one ring row
+ *       for different positions are refused.  rope_per_member != 0: one such ring per member, R rows apart, indexed by the member and not by the slot (an endless
+ *       group's rings).
+ * Every argument is checked before the context is bound (VOX_ERR_INVALID with a message): what the launcher would refuse -- rows 0 or 9, 17 slots, window + 1 >
+ * 1024, cap <= window + rows, head_dim 32, a RoPE ring shorter than `rows` or no power of two -- never reaches it, and nothing the kernel reads or writes lies outside
+ * the uploaded buffers. */
+typedef struct {
+    int32_t n_slots, n_members, rows, n_heads, head_dim, window, cap;
+    int32_t layers, layer;
+    int32_t rope_rows, rope_per_member;
+    float theta;
+    const int32_t* order;        /* [n_slots] */
+    const int32_t* enc_pos;      /* [n_members] */
+} vox_stream_attn_desc;
+int32_t vox_debug_stream_attn(vox_ctx* ctx, const vox_stream_attn_desc* desc, const float* qkv, float* kring, float* vring, float* out);
+/* The seeding of a session's encoder rings from the model's prefix state, on its own (tests): kv host [layers][rows][k row | v row], token-major, each row n_heads *
+ * head_dim wide; kring / vring host [layers][n_heads][cap][head_dim], in and out: ring rows 0 .. rows - 1 of every layer and head receive the input's bits, every
+ * other word keeps its own.  layers 1..64, n_heads 1..64, head_dim 64 | 128, cap 1..16384; rows <= 0 and rows > cap are refused, like every argument, before the
+ * context is bound. */
+int32_t vox_debug_stream_ring_init(vox_ctx* ctx, int32_t layers, int32_t rows, int32_t n_heads, int32_t head_dim, int32_t cap, const float* kv, float* kring, float* vring);
 /* Test hook: launches of the linear kernels enqueued by this process so far, by kernel form (host-side counts, as above; nothing is dispatched by them):
  * out[0..2] Q4 GEMV with 1 / 2 / 4 rows per wave, [3] dense GEMV, [4] 5..16-row skinny GEMM, [5] 17..48-row skinny GEMM (one-dimensional form), [6] its split-K form,
  * [7] rows -> XF tiles (helper of [5] / [6]), [8] split-K finishing sum (helper of [6]), [9..12] 16 x 64, 16 x 128, 32 x 64, 32 x 128 tile GEMM, [13] [14] the 32 x 64 and

@@ -16,7 +16,9 @@ Rows behind a position are NaN, rows in front of a window hold V = 1e6, unread s
 
 UNREACHABLE: the head_dim-64 instantiations (attn_decode_kernel<64, false>, attn_decode_paged_kernel<64>) have no caller -- dec_head_dim is the constant 128 -- and
 the entry refuses head_dim != 128; attn_wo_kernel needs a Q4 weight and is held to the oracle at full size, window edge included (tests/test_gpu_fullsize.py).  The
-paged per-head kernel cannot see a 4:1 geometry: launch_attn_decode_paged takes the GQA form there.
+paged per-head kernel cannot see a 4:1 geometry: launch_attn_decode_paged takes the GQA form there.  The live sessions' ring attention (`stream_ring`:
+stream_attn_kernel, RoPE + K / V append + windowed softmax in one launch) is no decode attention launch and has no entry here; it is held to its own float64
+reference, one launch at a time through vox_debug_stream_attn, by tests/test_gpu_stream_attn.py (both head sizes, the three RoPE modes, the ring seeding too).
 
 That the table can fail was checked once on an MI355X with four temporary mutations of attn_decode_gqa_kernel alone (the paged == slab tests cannot see them: both
 sides are that kernel), each changing a value or reading FEWER rows, no address or bound widened:
@@ -49,7 +51,7 @@ FORMS = {"decode": Form(False, False, False, R.HEAD_GEOS, None),
          "decode_paged": Form(True, False, False, ((4, 2), (2, 2)), "decode"),
          "decode_gqa_paged": Form(True, True, False, R.GQA_GEOS, "decode_gqa")}
 REACHABLE = set(FORMS)
-UNREACHABLE = set(ATTN_FORMS) - REACHABLE      # no decode attention launch: prefill, attn_wo, engines, the streams' ring attention and resamplers (module docstring: hd 64)
+UNREACHABLE = set(ATTN_FORMS) - REACHABLE      # no decode attention launch: prefill, attn_wo, engines, the resamplers, and the streams' ring attention, which tests/test_gpu_stream_attn.py holds (module docstring: hd 64)
 PAGE_ROWS = 64                                 # the paged runs of the 1024-row cases: 16 pages per slice
 REAL_PAGE_ROWS = 256                           # the default page of a paged group
 

@@ -169,6 +169,8 @@ SIGNATURES = {
     "vox_debug_attn_decode_ring": (i32, [vp, vp, vp, vp, vp, vp]),
     "vox_debug_attn_decode_paged_ring": (i32, [vp, vp, i32, vp, vp, vp, vp]),      # a paged launch on a ring page table of page_tab_len entries
     "vox_debug_rope_rows": (i32, [i32, C.c_float, C.c_int64, i32, vp, vp, vp]),
+    "vox_debug_stream_attn": (i32, [vp, vp, vp, vp, vp, vp]),      # (ctx, vox_stream_attn_desc, qkv, kring, vring, out): ONE launch of the streams' ring attention
+    "vox_debug_stream_ring_init": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp]),      # (ctx, layers, rows, n_heads, head_dim, cap, kv, kring, vring)
     "vox_debug_attn_gqa_max_seq": (i32, [vp, P(i32)]),
     "vox_debug_gemm_launches": (i32, [P(C.c_uint64), i32]),
     "vox_debug_timeline_start": (i32, [vp, i32, i32]),

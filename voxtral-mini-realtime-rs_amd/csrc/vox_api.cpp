@@ -1309,6 +1309,101 @@ extern "C" int32_t vox_debug_attn_decode_paged_ring(vox_ctx* c, const vox_attn_d
     ARGCHK(page_tab_len >= 1 && page_tab_len <= 1024, "page_tab_len %d out of range (1..1024)", page_tab_len);
     return attn_decode_debug(c, d, q, k, v, out, false, page_tab_len);
 }
+// ---- one launch of the live sessions' encoder ring attention on host buffers (tests): the StreamAttnParams of stream_encode_round -- StreamMember descriptors on the
+// device with state[STRM_ENC_POS], kring and vring alone filled in, the order array, the caller's q|k|v rows, the RoPE rows as a flat table (the model's streaming
+// table), one RoPE ring (a solo endless session's: stream_rope_refill) or a ring per member (an endless group's: group_rope_refill) -- and ONE launch_stream_attn.  The
+// RoPE rows come from rope_rows_fill with vox_debug_rope_rows' table length, so a test holds the identical f32 rows; in the ring modes only the rows the served members'
+// positions need are written, every other ring row is NaN.  Every argument is checked before the context is bound: what launch_stream_attn refuses never reaches it, and
+// nothing the kernel reads or writes lies outside the uploaded buffers (order against n_members, the positions against the table or 2^24, the ring offset against layers).
+extern "C" int32_t vox_debug_stream_attn(vox_ctx* c, const vox_stream_attn_desc* d, const float* qkv, float* kring, float* vring, float* out) {
+    ARGCHK(c && d && qkv && kring && vring && out, "null argument"); ARGCHK(d->order && d->enc_pos, "null argument (order, enc_pos)");
+    ARGCHK(d->head_dim == 64 || d->head_dim == 128, "head_dim %d: the ring attention serves head_dim 64 and 128", d->head_dim);
+    ARGCHK(d->rows >= 1 && d->rows <= 8, "rows %d out of range (1..8)", d->rows);
+    ARGCHK(d->n_slots >= 1 && d->n_slots <= 16, "n_slots %d out of range (1..16)", d->n_slots);
+    ARGCHK(d->n_members >= d->n_slots && d->n_members <= 64, "n_members %d out of range (n_slots = %d .. 64)", d->n_members, d->n_slots);
+    ARGCHK(d->n_heads >= 1 && d->n_heads <= 32, "n_heads %d out of range (1..32)", d->n_heads);
+    ARGCHK(d->window >= 0 && d->window + 1 <= 1024, "window %d: the kernel holds 1024 scores, windows 0..1023", d->window);
+    ARGCHK(d->cap > d->window + d->rows && d->cap <= 16384, "cap %d: a ring holds window + rows < cap <= 16384 rows (window %d, rows %d)", d->cap, d->window, d->rows);
+    ARGCHK(d->layers >= 1 && d->layers <= 8 && d->layer >= 0 && d->layer < d->layers, "layer %d of %d layers (1..8)", d->layer, d->layers);
+    ARGCHK(std::isfinite(d->theta) && d->theta > 1.0f, "theta %g must be finite and above 1", (double)d->theta);
+    const int R = d->rope_rows, M = d->rows, n = d->n_slots, NM = d->n_members;
+    // (a ring of one row would have the mask 0, which the kernel reads as "a flat table")
+    ARGCHK(R == 0 || (R >= 2 && R >= M && R <= 4096 && !(R & (R - 1))), "rope_rows %d: a RoPE ring has a power of two of rows, at least `rows` (%d) and 2, at most 4096", R, M);
+    ARGCHK(R || !d->rope_per_member, "rope_per_member without a RoPE ring (rope_rows 0)");
+    const int64_t pos_end = R ? ((int64_t)1 << 24) : (int64_t)ROPE_ENC_STREAM_TABLE_LEN;
+    for (int i = 0; i < NM; i++)
+        ARGCHK(d->enc_pos[i] >= 0 && (int64_t)d->enc_pos[i] + M <= pos_end, "enc_pos[%d] = %d: the %d rows of a tick end at position %lld here", i, d->enc_pos[i], M, (long long)pos_end);
+    bool served[64] = {};
+    for (int z = 0; z < n; z++) {
+        ARGCHK(d->order[z] >= 0 && d->order[z] < NM, "order[%d] = %d outside the %d members", z, d->order[z], NM);
+        ARGCHK(!served[d->order[z]], "order[%d] = %d: a member is served by one slot", z, d->order[z]);
+        served[d->order[z]] = true;
+    }
+    const bool per_member = R && d->rope_per_member;
+    const int hd = d->head_dim, half = hd / 2, H = d->n_heads, QD = H * hd;
+    const int64_t table_len = rope_debug_table_len(hd);
+    // the RoPE rows, on the host
+    std::vector<float> rope; size_t sin_at = 0;
+    if (!R) {
+        int64_t T = 0; for (int z = 0; z < n; z++) T = std::max<int64_t>(T, (int64_t)d->enc_pos[d->order[z]] + M);
+        rope.resize((size_t)2 * T * half); sin_at = (size_t)T * half;
+        rope_rows_fill(hd, d->theta, 0, T, table_len, nullptr, rope.data(), rope.data() + sin_at);
+    } else {
+        rope.assign((size_t)(per_member ? NM : 1) * R * hd, std::nanf("")); sin_at = (size_t)half;
+        std::vector<int64_t> holds((size_t)(per_member ? NM : 1) * R, -1);
+        for (int z = 0; z < n; z++) for (int r = 0; r < M; r++) {
+            const int64_t p = (int64_t)d->enc_pos[d->order[z]] + r; const size_t row = (per_member ? (size_t)d->order[z] * R : 0) + (size_t)(p & (R - 1));
+            ARGCHK(holds[row] < 0 || holds[row] == p, "one RoPE ring of %d rows cannot hold positions %lld and %lld (slot %d): rope_per_member gives every member its own", R, (long long)holds[row], (long long)p, z);
+            holds[row] = p;
+            rope_rows_fill(hd, d->theta, p, 1, table_len, nullptr, rope.data() + row * hd, rope.data() + row * hd + half);
+        }
+    }
+    VOXCHK(ctx_bind(c));
+    hipStream_t s = c->stream;
+    const size_t layer_f = (size_t)H * d->cap * hd, mem_f = (size_t)d->layers * layer_f, ring_f = (size_t)NM * mem_f, qkv_f = (size_t)n * M * 3 * QD, out_f = (size_t)n * M * QD;
+    DevBuf dqkv, dk, dv, dout, drope, dint, dmem;
+    HIPCHK(dqkv.alloc(qkv_f * 4)); HIPCHK(dk.alloc(ring_f * 4)); HIPCHK(dv.alloc(ring_f * 4)); HIPCHK(dout.alloc(out_f * 4)); HIPCHK(drope.alloc(rope.size() * 4));
+    HIPCHK(dint.alloc(((size_t)NM * STRM_WORDS + n) * 4)); HIPCHK(dmem.alloc((size_t)NM * sizeof(StreamMember)));
+    int* d_state = dint.as<int>(); int* d_order = d_state + (size_t)NM * STRM_WORDS;
+    std::vector<int> state((size_t)NM * STRM_WORDS, 0); std::vector<StreamMember> mem((size_t)NM, StreamMember{});
+    for (int i = 0; i < NM; i++) {
+        state[(size_t)i * STRM_WORDS + STRM_ENC_POS] = d->enc_pos[i];
+        mem[i].state = d_state + (size_t)i * STRM_WORDS; mem[i].kring = dk.as<float>() + (size_t)i * mem_f; mem[i].vring = dv.as<float>() + (size_t)i * mem_f;
+    }
+    HIPCHK(hipMemcpyAsync(dqkv.p, qkv, qkv_f * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dk.p, kring, ring_f * 4, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(dv.p, vring, ring_f * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(drope.p, rope.data(), rope.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_state, state.data(), state.size() * 4, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(d_order, d->order, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dmem.p, mem.data(), mem.size() * sizeof(StreamMember), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(dout.p, 0xff, out_f * 4, s));      // a row the launch does not write stays NaN
+    StreamAttnParams ap{}; ap.qkv = dqkv.as<float>(); ap.qkv_stride = 3 * QD; ap.mem = dmem.as<StreamMember>(); ap.order = d_order; ap.n = n; ap.ring_off = (size_t)d->layer * layer_f; ap.cap = d->cap;
+    ap.cos_t = drope.as<float>(); ap.sin_t = drope.as<float>() + sin_at; ap.out = dout.as<float>(); ap.out_stride = QD; ap.M = M; ap.n_heads = H; ap.window = d->window;
+    ap.rope_mask = R ? R - 1 : 0; ap.rope_stride = per_member ? R : 0;
+    HIPCHK(launch_stream_attn(ap, hd, s));
+    HIPCHK(hipMemcpyAsync(out, dout.p, out_f * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(kring, dk.p, ring_f * 4, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(vring, dv.p, ring_f * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return VOX_OK;
+}
+// the seeding of a session's rings from the prefix state on host buffers (tests): ONE launch_stream_ring_init into the caller's rings
+extern "C" int32_t vox_debug_stream_ring_init(vox_ctx* c, int32_t layers, int32_t rows, int32_t n_heads, int32_t head_dim, int32_t cap, const float* kv, float* kring, float* vring) {
+    ARGCHK(c && kv && kring && vring, "null argument");
+    ARGCHK(head_dim == 64 || head_dim == 128, "head_dim %d: the encoder rings hold head_dim 64 or 128", head_dim);
+    ARGCHK(layers >= 1 && layers <= 64 && n_heads >= 1 && n_heads <= 64, "%d layers of %d heads out of range (1..64 each)", layers, n_heads);
+    ARGCHK(cap >= 1 && cap <= 16384, "cap %d out of range (1..16384)", cap);
+    ARGCHK(rows >= 1 && rows <= cap, "rows %d: a ring of %d rows is seeded with 1..%d rows", rows, cap, cap);
+    VOXCHK(ctx_bind(c));
+    hipStream_t s = c->stream;
+    const size_t kv_f = (size_t)layers * rows * 2 * n_heads * head_dim, ring_f = (size_t)layers * n_heads * cap * head_dim;
+    DevBuf dkv, dk, dv;
+    HIPCHK(dkv.alloc(kv_f * 4)); HIPCHK(dk.alloc(ring_f * 4)); HIPCHK(dv.alloc(ring_f * 4));
+    HIPCHK(hipMemcpyAsync(dkv.p, kv, kv_f * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dk.p, kring, ring_f * 4, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(dv.p, vring, ring_f * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(launch_stream_ring_init(dkv.as<float>(), layers, rows, n_heads, head_dim, cap, dk.as<float>(), dv.as<float>(), s));
+    HIPCHK(hipMemcpyAsync(kring, dk.p, ring_f * 4, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(vring, dv.p, ring_f * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return VOX_OK;
+}
 // What a batched XF decode step works on.  f32 rows (h, qkv, logits; att unread), XF planes and partial sums of squares one block per 16-row group, `*_gs` elements apart.
 // k / v: layer 0's cache slab (layer l at + l layer_stride), row r's slice at + r seq_stride, or, with kv_row, the slice kv_row[r] names; pos: the rows' positions.
 // ssq_e: the batched engine's sums of squares (one block of 256 + 16 rows per group); planes: the wide step's K-split scratch, planes_bytes per chain.

@@ -187,6 +187,6 @@ extern "C" int32_t vox_debug_rope_rows(int32_t head_dim, float theta, int64_t fi
     ARGCHK(std::isfinite(theta) && theta > 1.0f, "theta %g must be finite and above 1", (double)theta);
     ARGCHK(n >= 0 && n <= (1 << 20), "%d rows out of range (0..%d)", n, 1 << 20);
     ARGCHK(first_pos >= 0 && first_pos + n <= ((int64_t)1 << 24), "rows %lld .. %lld: positions end at 2^24", (long long)first_pos, (long long)(first_pos + n));
-    rope_rows_fill(head_dim, theta, first_pos, n, head_dim == 128 ? ROPE_DEC_TABLE_LEN : ROPE_ENC_STREAM_TABLE_LEN, inv_out, cos_out, sin_out);
+    rope_rows_fill(head_dim, theta, first_pos, n, rope_debug_table_len(head_dim), inv_out, cos_out, sin_out);
     return VOX_OK;
 }

@@ -29,6 +29,8 @@ struct ResamplePlan { long fft_in = 0, fft_out = 0, new_len = 0, delay = 0; floa
 // Positions below table_len take the tables' formula -- the f32 product pos * inv, then f32 cos / sin: the bits every table has had.  From table_len on the angle is
 // double(pos) * double(inv), cos / sin in double, rounded to f32: the f32 product loses the angle at large positions (its spacing is about 0.5 rad at 4 M).
 inline const int ROPE_DEC_TABLE_LEN = 16384, ROPE_ENC_STREAM_TABLE_LEN = 1 << 16;
+// the table length the debug entries take a head_dim for (vox_debug_rope_rows, vox_debug_stream_attn): 128 is the decoder's geometry, any other the streaming encoder's
+inline int64_t rope_debug_table_len(int hd) { return hd == 128 ? ROPE_DEC_TABLE_LEN : ROPE_ENC_STREAM_TABLE_LEN; }
 // one row: cos / sin [half] of position pos from the f32 factors inv [half] (rope_inv_fill) -- the row arithmetic of every caller: rope_rows_fill below, and the
 // per-pass fill of an endless group's member rings (group_rope_refill, which computes inv once per group)
 inline void rope_inv_fill(int hd, float theta, float* inv_out) { for (int j = 0; j < hd / 2; j++) inv_out[j] = 1.0f / std::pow(theta, (float)(2 * j) / (float)hd); }

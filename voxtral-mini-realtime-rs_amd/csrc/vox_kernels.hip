@@ -4613,12 +4613,11 @@ __global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_attn_kernel(const St
 }
 hipError_t launch_stream_attn(const StreamAttnParams& p, int hd, hipStream_t s) {
     // (the ring rows are read as float4: the sessions' rings are hipMalloc'd, a layer's offset is a multiple of hd, hd % 4 == 0 holds for 64 / 128)
-    if (p.M < 1 || p.M > 8 || p.n < 1 || p.n > 16 || !p.mem || !p.order || p.window < 0 || p.window + 1 > 1024 || p.cap <= p.window + p.M || (p.ring_off & 3) || p.rope_mask < 0 ||
+    if ((hd != 64 && hd != 128) || p.M < 1 || p.M > 8 || p.n < 1 || p.n > 16 || !p.mem || !p.order || p.window < 0 || p.window + 1 > 1024 || p.cap <= p.window + p.M || (p.ring_off & 3) || p.rope_mask < 0 ||
         (p.rope_mask & (p.rope_mask + 1)) || (p.rope_mask && p.rope_mask + 1 < p.M) || (p.rope_stride && (!p.rope_mask || p.rope_stride < p.rope_mask + 1))) return hipErrorInvalidValue;
-    attn_form_note(ATTN_FORM_STREAM_RING);
+    attn_form_note(ATTN_FORM_STREAM_RING);      // (behind every refusal: a refused call counts no launch)
     if (hd == 64) stream_attn_kernel<64><<<dim3(p.n_heads, p.M, p.n), dim3(256), 0, s>>>(p);
-    else if (hd == 128) stream_attn_kernel<128><<<dim3(p.n_heads, p.M, p.n), dim3(256), 0, s>>>(p);
-    else return hipErrorInvalidValue;
+    else stream_attn_kernel<128><<<dim3(p.n_heads, p.M, p.n), dim3(256), 0, s>>>(p);
     return hipGetLastError();
 }
 

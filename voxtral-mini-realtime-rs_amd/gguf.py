@@ -318,6 +318,42 @@ def attn_decode_ring(ctx, q, k, v, pos, n_heads, n_kv_heads, window):
     return out
 
 
+class StreamAttnDesc(C.Structure):
+    """vox_stream_attn_desc (include/voxtral_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("n_slots", "n_members", "rows", "n_heads", "head_dim", "window", "cap", "layers", "layer", "rope_rows", "rope_per_member")] + \
+               [("theta", C.c_float), ("order", C.c_void_p), ("enc_pos", C.c_void_p)]
+
+
+def stream_attn(ctx, qkv, kring, vring, order, enc_pos, rows, window, theta, layer=0, rope_rows=0, rope_per_member=False):
+    """vox_debug_stream_attn: ONE launch of the live sessions' encoder ring attention (RoPE on q and k, K / V append, windowed softmax).  qkv [n_slots * rows,
+    3 * n_heads * hd] not rotated; kring / vring [n_members, layers, n_heads, cap, hd] (hd 64 | 128); order [n_slots] distinct members; enc_pos [n_members].
+    rope_rows 0: a flat RoPE table; R: a RoPE ring of R rows, with rope_per_member one per member.  Returns (out [n_slots * rows, n_heads * hd], kring, vring after
+    the launch); the arguments are left as they are."""
+    qkv = _f32(qkv); kring = _f32(kring).copy(); vring = _f32(vring).copy()
+    order = np.ascontiguousarray(order, dtype=np.int32); enc_pos = np.ascontiguousarray(enc_pos, dtype=np.int32)
+    if qkv.ndim != 2 or kring.ndim != 5 or kring.shape != vring.shape or order.ndim != 1 or enc_pos.shape != (kring.shape[0],):
+        raise VoxError(1, "stream_attn: bad shapes")
+    n_members, layers, n_heads, cap, hd = kring.shape
+    if qkv.shape != (len(order) * max(int(rows), 0), 3 * n_heads * hd):
+        raise VoxError(1, "stream_attn: qkv is not [n_slots * rows][3 * n_heads * head_dim]")
+    d = StreamAttnDesc(n_slots=len(order), n_members=n_members, rows=int(rows), n_heads=n_heads, head_dim=hd, window=int(window), cap=cap, layers=layers, layer=int(layer),
+                       rope_rows=int(rope_rows), rope_per_member=int(bool(rope_per_member)), theta=float(theta), order=order.ctypes.data, enc_pos=enc_pos.ctypes.data)
+    out = np.empty((qkv.shape[0], n_heads * hd), np.float32)
+    check(lib().vox_debug_stream_attn(ctx.h, C.byref(d), _ptr(qkv), _ptr(kring), _ptr(vring), _ptr(out)))
+    return out, kring, vring
+
+
+def stream_ring_init(ctx, kv, kring, vring):
+    """vox_debug_stream_ring_init: the rings' seeding from token-major rows.  kv [layers, rows, 2 * n_heads * hd] (k row | v row); kring / vring [layers, n_heads, cap,
+    hd].  Returns (kring, vring) after the launch; the arguments are left as they are."""
+    kv = _f32(kv); kring = _f32(kring).copy(); vring = _f32(vring).copy()
+    if kv.ndim != 3 or kring.ndim != 4 or kring.shape != vring.shape or kv.shape[0] != kring.shape[0] or kv.shape[2] != 2 * kring.shape[1] * kring.shape[3]:
+        raise VoxError(1, "stream_ring_init: bad shapes")
+    layers, n_heads, cap, hd = kring.shape
+    check(lib().vox_debug_stream_ring_init(ctx.h, layers, kv.shape[1], n_heads, hd, cap, _ptr(kv), _ptr(kring), _ptr(vring)))
+    return kring, vring
+
+
 def rope_rows(head_dim, theta, first_pos, n):
     """vox_debug_rope_rows (host arithmetic, no device): (inv [head_dim/2], cos [n, head_dim/2], sin [n, head_dim/2]) float32 for positions first_pos .. first_pos + n - 1."""
     half = max(int(head_dim) // 2, 0)
