@@ -509,6 +509,27 @@ int32_t vox_debug_stream_attn(vox_ctx* ctx, const vox_stream_attn_desc* desc, co
  * other word keeps its own.  layers 1..64, n_heads 1..64, head_dim 64 | 128, cap 1..16384; rows <= 0 and rows > cap are refused, like every argument, before the
  * context is bound. */
 int32_t vox_debug_stream_ring_init(vox_ctx* ctx, int32_t layers, int32_t rows, int32_t n_heads, int32_t head_dim, int32_t cap, const float* kv, float* kring, float* vring);
+/* One launch of the session blob's K / V kernel on its own (tests; SNAPSHOT AND RESUME below): the logical rows lo .. hi - 1 of every (layer, head) of K and V
+ * between the blob's dense layout and a cache in one of the four layouts a session's K / V can have -- exactly ONE launch (none when lo == hi), host arrays in and out.
+ *   blob: host [2][layers][n_heads][hi - lo][head_dim], K then V.  restore == 0 packs the cache's rows into it, restore != 0 unpacks it into the cache; cache_k /
+ *   cache_v are copied back in both directions (a pack leaves them as they were; after an unpack every word outside the named rows has its bits from before).
+ *   layout 0, flat: cache host [layers][layer_rows][...]: layer l starts at l * layer_stride floats, head h of it at h * rows * head_dim, row r at r * head_dim;
+ *     layer_stride >= n_heads * rows * head_dim, a multiple of 4; hi <= rows.
+ *   layout 1, ring: the same planes with row r at (r % rows) * head_dim -- rows is the ring's capacity, any value (a power of two or not); hi - lo <= rows, hi < 2^24.
+ *   layout 2, page table: cache host [layers][pool_pages][n_heads][page_rows][head_dim] (layer_stride = pool_pages * n_heads * page_rows * head_dim, given as 0 or as
+ *     that), page_rows a power of two in 16..1024, page_tab host [page_tab_len]: row r lives in page page_tab[r / page_rows]; (hi - 1) / page_rows < page_tab_len.
+ *   layout 3, ring table: the same with page_tab[(r / page_rows) % page_tab_len]; the range touches at most page_tab_len pages; hi < 2^24.
+ *   The table entries the range touches are checked against pool_pages here, on the host; the others may hold anything and are never read.
+ * head_dim 64 | 128, layers 1..64, n_heads 1..64.  Every argument is checked before the context is bound (VOX_ERR_INVALID with a message): hi < lo, head_dim 32, a
+ * ring shorter than hi - lo, an entry outside the pool never reach a launch, and nothing the kernel reads or writes lies outside the uploaded buffers. */
+typedef struct {
+    int32_t layers, n_heads, head_dim, lo, hi;
+    int32_t layout, rows;
+    int32_t page_rows, pool_pages, page_tab_len;
+    int64_t layer_stride;
+    const int32_t* page_tab;     /* layouts 2 and 3 only */
+} vox_snapshot_kv_desc;
+int32_t vox_debug_snapshot_kv(vox_ctx* ctx, const vox_snapshot_kv_desc* desc, float* cache_k, float* cache_v, float* blob, int32_t restore);
 /* Test hook: launches of the linear kernels enqueued by this process so far, by kernel form (host-side counts, as above; nothing is dispatched by them):
  * out[0..2] Q4 GEMV with 1 / 2 / 4 rows per wave, [3] dense GEMV, [4] 5..16-row skinny GEMM, [5] 17..48-row skinny GEMM (one-dimensional form), [6] its split-K form,
  * [7] rows -> XF tiles (helper of [5] / [6]), [8] split-K finishing sum (helper of [6]), [9..12] 16 x 64, 16 x 128, 32 x 64, 32 x 128 tile GEMM, [13] [14] the 32 x 64 and
@@ -706,6 +727,69 @@ int32_t vox_debug_stream_tap_peeked(vox_stream* s, float* out_rows_x_vocab, int3
 int32_t vox_debug_stream_front_tap_arm(vox_stream* s, int32_t max_ticks);
 int32_t vox_debug_stream_front_tap_fetch(vox_stream* s, float* out_mel, float* out_conv, int32_t* ticks);
 
+/* ---- SNAPSHOT AND RESUME (no reference counterpart): a live session taken off the GPU as one byte string and put back into any stream of the same model -----------------
+ * Between two calls a session is a closed set of device arrays and a small host mirror.  vox_stream_snapshot writes what a LATER TICK CAN STILL READ of them, in logical
+ * order, into one contiguous, position-independent blob; vox_stream_restore makes a stream continue from it.  The stream that restores need not be the one that
+ * snapshotted, nor have its encoder ring capacity, its max_positions or its kind (bounded / endless): a parked session holds no device memory at all (free the
+ * stream), a session can move to another process or GPU with the same model file, survive a restart, or be forked into two.
+ *   Blob: a header of VOX_SNAPSHOT_HEADER_BYTES, then up to VOX_SNAPSHOT_SECTIONS sections, each at a 16-byte boundary, the padding zero:
+ *     [0] [1] encoder K, V   [enc_layers][enc_heads][We][enc_head_dim] f32, the rows E - We .. E - 1 of the encoder stream position E, We = min(E, enc_window): the keys
+ *                            the next query row attends;
+ *     [2] [3] decoder K, V   [dec_layers][dec_kv_heads][Wd][dec_head_dim] f32, the rows D - Wd .. D - 1 of the decoder position D, Wd = min(D, dec_window) (no window: D);
+ *     [4] the 16 kHz sample ring in logical order: the last min(samples written, 65 536) samples;  [5] a rate stream's input-rate ring likewise (empty at 16 kHz);
+ *     [6] the utterance's tokens 0 .. D (i32);  [7] the vox_token_score records of the ids handed out, when scores are on;  [8] the vox_token_alts records, when k > 0.
+ *   The header holds: magic, format version (VOX_SNAPSHOT_VERSION), total bytes; a model fingerprint and a hash of the bits of the session's t_embed; gain, sample
+ *   rate, samples pushed and the other feed counters a later call depends on; D and E; the ids handed out, the scores flag and the alternatives k; the token at
+ *   position D; the model geometry the K / V sections are laid out by; offset and length of every section.  Byte order and float format are the writing machine's.
+ *   NOT in the blob (rebuilt, or simply absent after a restore): test taps, the peek save area, the decode engine's binding, RoPE rings, staging buffers, the kept
+ *   adapter rows (a snapshot is taken at a verification point), K / V rows outside the windows.  Two snapshots of an untouched session are byte-identical.
+ *   The model fingerprint covers the vox_model_cfg words, the byte count of the weights as parsed from the file and a 64-bit hash of a few KB of them (read back once
+ *   per model, at its first snapshot or restore).  It is there to stop a blob from going into the WRONG MODEL BY MISTAKE; it proves nothing about integrity, and a blob
+ *   is not inspected beyond its header's arithmetic.
+ * vox_stream_snapshot_size: the bytes vox_stream_snapshot would write now (host arithmetic: vox_snapshot_bytes_for on the session's counters).
+ * vox_stream_snapshot: leaves the stream exactly as it was (nothing of it is written; a finished stream is refused: a reset starts its next utterance).  mem_kind
+ *   VOX_MEM_DEVICE: the K / V sections are packed straight into the caller's device buffer (16-byte aligned) by one kernel launch per stack, everything else by copies;
+ *   VOX_MEM_HOST: the K / V sections pass through a device staging area of at most 64 MB -- two halves used alternately, each packed by one launch and then downloaded
+ *   -- allocated for the call and freed at its end: vox_stream_info[5] is afterwards what it was.  Synchronisations: one at the start (the token at D), one at the end.
+ *   cap < the size is refused.
+ * vox_stream_restore: replaces the target's utterance, as vox_stream_reset followed by a replay of the blob's samples would; takes the blob's gain; keeps the target's
+ *   own scores / alternatives settings (records the blob does not hold read as "off" records).  Everything is checked before anything changes -- a refused call leaves
+ *   the target bit for bit what it was: the header's magic, version, length and section table (vox_snapshot_describe's refusals), the fingerprint, the t_embed hash, a
+ *   sample rate other than the stream's, D at or beyond the target's max_positions, a token outside the vocabulary.  With a device blob the header is downloaded and
+ *   checked first.  After the payload copies the header's VALIDATED token is written at tokens[D]: the embedding lookup never reads an unchecked index.
+ *   Placement: a bounded target gets the decoder cache size the doubling rule gives an uninterrupted session at D (the decode engine serves exactly the positions it
+ *   would have served); an endless target places the rows at row % dec_ring_rows (flat below the wrap) and grows its lists as its own rule would have; the encoder
+ *   rows go to row % capacity of the target's ring.  Everything after a restore into a stream of the same kind is bit for bit what the uninterrupted session gives
+ *   (an endless target past its wrap: the relation ENDLESS SESSIONS documents).
+ * Members of a stream group (vox_stream_group_snapshot_size / _snapshot / _restore, declared behind the group's own entries): the same three calls with (group,
+ *   member) in front, on slab, paged and endless paged groups.  The format does not know the difference: a solo stream's blob restores into a member and the other
+ *   way round.  A restore sets the member's rate from the blob, as vox_stream_group_reset_rate does (so a rate mismatch is no refusal here), and takes the blob's
+ *   gain.  A paged restore is planned like an advance: the pages the member holds now count as free, the pages vox_stream_group_pages_for(D) names are needed; a pool
+ *   without room refuses (the message names the member, the pages needed and the pages free) and the group is untouched.  A slab member refuses a blob at or beyond
+ *   the slab's max_positions.  A member restored into the SAME slot of a group fed the same calls continues bit for bit (ids, logits, records, pool counts and pages
+ *   held; the physical page numbers may differ); across slots or kinds the continuation is the session's up to f32 summation order (the round width selects the GEMM
+ *   kernels), as between a group and a solo stream anyway.
+ * Out of scope: blobs across model geometries or t_embeds, compression or a narrower dtype in the blob, the offline and batch paths, incremental snapshots.
+ * vox_snapshot_describe (host arithmetic, no device): validates the header at the start of a blob of nbytes bytes -- reads at most VOX_SNAPSHOT_HEADER_BYTES of it;
+ *   a caller that holds only the header of a longer blob passes the blob's length -- and decodes it.  vox_snapshot_bytes_for: the blob size of a session of this
+ *   geometry at decoder position `positions` (>= 37) after n_samples pushed samples at sample_rate, with (1) or without (0) its score / alternatives records: what a
+ *   server budgets its host memory by. */
+#define VOX_SNAPSHOT_VERSION 1
+#define VOX_SNAPSHOT_HEADER_BYTES 288
+#define VOX_SNAPSHOT_SECTIONS 9
+typedef struct {
+    int32_t version; uint32_t sample_rate; float gain; int32_t token;
+    uint64_t total_bytes, fingerprint, t_embed_hash;
+    int64_t samples_pushed, samples_16k, samples_in;
+    int32_t positions, enc_position, ids, scores, alternatives, n_scores, n_alts, enc_rows, dec_rows, reserved;
+    uint64_t section_offset[VOX_SNAPSHOT_SECTIONS], section_bytes[VOX_SNAPSHOT_SECTIONS];
+} vox_snapshot_info;
+int32_t vox_snapshot_describe(const void* blob, size_t nbytes, vox_snapshot_info* out);
+int32_t vox_snapshot_bytes_for(const vox_model_cfg* cfg, int64_t positions, uint32_t sample_rate, size_t n_samples, int32_t scores, int32_t alternatives, size_t* out);
+int32_t vox_stream_snapshot_size(const vox_stream* s, size_t* nbytes);
+int32_t vox_stream_snapshot(vox_stream* s, void* blob, size_t cap, size_t* nbytes, int32_t mem_kind);
+int32_t vox_stream_restore(vox_stream* s, const void* blob, size_t nbytes, int32_t mem_kind);
+
 /* ---- stream group: up to 16 live sessions advanced together (no reference counterpart) ---------------------------------------------------------------------------------
  * A vox_stream_group holds n_members member sessions on one model and one t_embed, each with its own gain, sample ring, encoder K / V ring and slice of the group's
  * decoder cache.  vox_stream_group_advance feeds any subset of the members (f32 samples at each member's rate, host or device memory: mem_kind holds for the whole
@@ -822,6 +906,11 @@ int32_t vox_debug_stream_group_pages(const vox_stream_group* g, int32_t member, 
  *   Not served: endless slab groups, freeing pages inside a call, more than 16 members. */
 int32_t vox_stream_group_create_endless(vox_model* m, const float* t_embed, int32_t n_members, const float* gains /* null: 1.0 */, const uint32_t* rates /* null: 16000 each */,
                                         int32_t enc_capacity_rows, int32_t page_rows /* 0: 256 */, int32_t pool_pages /* 0: the default */, vox_stream_group** out);
+/* Snapshot and resume of a member (SNAPSHOT AND RESUME above: the format, the refusals, the contracts): vox_stream_snapshot_size / _snapshot / _restore for member
+ * `member` of a slab, paged or endless paged group.  Only that member is read or changed. */
+int32_t vox_stream_group_snapshot_size(const vox_stream_group* g, int32_t member, size_t* nbytes);
+int32_t vox_stream_group_snapshot(vox_stream_group* g, int32_t member, void* blob, size_t cap, size_t* nbytes, int32_t mem_kind);
+int32_t vox_stream_group_restore(vox_stream_group* g, int32_t member, const void* blob, size_t nbytes, int32_t mem_kind);
 /* The live sessions' feed planner on its own (tests): host arithmetic only -- no context, no device, no model.  A fresh session fed at sample_rate (4 encoder rows per
  * position, the Voxtral left pad, no position limit to speak of) takes the calls (n_samples[c], finish[c] 0 / 1) exactly as vox_stream_push / _finish and a group's advance
  * plan and pass them, every due tick taken as run; finish[c] = 2 is a peek (n_samples[c] must be 0): planned as a finish, its one pass emitted, the session as it was.  One row of five words per pass: call index, input samples appended, 16 kHz samples that entered the 16 kHz ring (a

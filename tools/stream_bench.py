@@ -9,6 +9,7 @@
     python tools/stream_bench.py --peek [--out profiles/stream_peek.txt]
     python tools/stream_bench.py --group 1,4,16 --page-rows 256 [--out profiles/stream_group_paged_tick.txt]
     python tools/stream_bench.py --endless [--out profiles/stream_endless_tick.txt]
+    python tools/stream_bench.py --snapshot [--out profiles/stream_snapshot.txt]
 
  * stream: HIP events on the context's stream around ONE push of `ticks` x 2560 samples (a large push is a loop of identical ticks), at encoder positions past the
    750-row window, median of `passes` passes; launches per tick from the library's launch counters plus the fixed launches of a tick; wall time of single 160 ms pushes
@@ -45,6 +46,9 @@
    same positions: both are fed the same device-resident samples up to a few ticks past the ring's rows (not timed), then per pass one push of `ticks` ticks each,
    the endless session's right behind the bounded one's.  Medians, their difference, the launches per tick of both (the ring form runs attention and wo as two
    launches per decoder layer) and the device bytes each session holds.  Nothing else is measured in this mode.
+ * --snapshot: vox_stream_snapshot and vox_stream_restore of one endless solo session at three positions (about 300; past 1024; a few positions past the wrap of its
+   decoder ring, i.e. past the decoder window), each with a device blob and with a host blob, and a device-to-device copy (vox_dev_copy) of the blob's byte count in
+   the same run: HIP events on the context's stream around each call, median of `passes`; bytes, ms and GB/s of each.  Nothing else is measured in this mode.
  * derived figures are labelled as derived."""
 import argparse
 import ctypes as C
@@ -321,6 +325,44 @@ def bench_endless(pkg, ctx, m, t, tm, a, lines):
               f"ids of the timed passes: {int((idb == ide).sum())} of {len(idb)} equal (the bounded step fuses attention + wo where the model allows it, the ring step does not: equal bits are not promised there)"]
 
 
+def bench_snapshot(pkg, ctx, m, t, tm, a, lines):
+    """--snapshot: vox_stream_snapshot / vox_stream_restore of one endless solo session at three positions (about 300, past 1024, past the decoder window), with a
+    device blob and with a host blob, next to a device-to-device copy of the same byte count in the same run."""
+    c = m.config; S = pkg.synth; L = pkg.lib()
+    ring = (c.dec_window + 1 + 63 + 63) // 64 * 64
+    stops = [300, 1030, ring + 8]
+    base = S.synth_audio(40.0, seed=4242); gain = float(np.float32(0.95) / np.float32(np.abs(base).max()))
+    n = 40 + 2560 * (stops[-1] - 37)
+    x = np.tile(base, n // len(base) + 1)[:n].copy()
+    dev = ctx.upload(x)
+    src = m.create_stream(t, gain=gain, endless=True); dst = m.create_stream(t, gain=gain, endless=True)
+    pos = 0
+    for stop in stops:
+        end = 40 + 2560 * (stop - 37)
+        for a0 in range(pos, end, 2560 * 1024):
+            src.push(device_ptr=dev + 4 * a0, n_samples=min(end, a0 + 2560 * 1024) - a0)
+        pos = end
+        assert src.info()["positions"] == stop + 1, src.info()
+        nb = C.c_size_t(); pkg._lib.check(L.vox_stream_snapshot_size(src.h, C.byref(nb))); nb = nb.value
+        d1 = ctx.alloc(nb); d2 = ctx.alloc(nb); host = np.zeros(nb, np.uint8); w = C.c_size_t()
+        snap_d = lambda: pkg._lib.check(L.vox_stream_snapshot(src.h, C.c_void_p(d1), nb, C.byref(w), 1))
+        rest_d = lambda: pkg._lib.check(L.vox_stream_restore(dst.h, C.c_void_p(d1), nb, 1))
+        snap_h = lambda: pkg._lib.check(L.vox_stream_snapshot(src.h, host.ctypes.data_as(C.c_void_p), nb, C.byref(w), 0))
+        rest_h = lambda: pkg._lib.check(L.vox_stream_restore(dst.h, host.ctypes.data_as(C.c_void_p), nb, 0))
+        copy = lambda: ctx.copy(d2, d1, nb)
+        snap_d(); rest_d(); copy()      # warm: the kernels' first launch, the fingerprint, the target's cache of the rule's size
+        res = {}
+        for name, fn in (("snapshot, device blob", snap_d), ("restore, device blob", rest_d), ("device-to-device copy", copy), ("snapshot, host blob", snap_h), ("restore, host blob", rest_h)):
+            ms = [tm.ms(fn) for _ in range(a.passes)]; res[name] = statistics.median(ms)
+            lines.append(f"position {stop + 1}: {name}: {nb} bytes, median {res[name]:.3f} ms ({nb / res[name] / 1e6:.1f} GB/s)  passes " + " ".join(f"{v:.3f}" for v in ms))
+        assert dst.info()["positions"] == stop + 1
+        lines.append(f"position {stop + 1}: derived: snapshot to a device blob is {100 * res['snapshot, device blob'] / res['snapshot, host blob']:.1f} % of a snapshot to a host blob (the pack kernels and "
+                     f"the small copies against the same plus staging and download); pack at {100 * res['device-to-device copy'] / res['snapshot, device blob']:.0f} %, unpack at "
+                     f"{100 * res['device-to-device copy'] / res['restore, device blob']:.0f} % of the copy's rate")
+        ctx.free(d1); ctx.free(d2)
+    src.close(); dst.close(); ctx.free(dev)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gguf"); ap.add_argument("--ticks", type=int, default=200); ap.add_argument("--passes", type=int, default=3); ap.add_argument("--out")
@@ -334,7 +376,10 @@ def main():
     ap.add_argument("--endless", action="store_true", help="time the tick of an endless session past the wrap of its decoder ring next to a bounded session at the same positions (nothing else is measured)")
     ap.add_argument("--memory-past-window", action="store_true", help="with --page-rows R: what 16 members of an endless paged group and of a bounded paged group (max_positions 16384) hold past "
                     "the decoder window, from pool() and info() (a mode of its own: nothing is timed)")
+    ap.add_argument("--snapshot", action="store_true", help="time vox_stream_snapshot / vox_stream_restore (device and host blobs) at three positions next to a device copy of the same size (nothing else is measured)")
     a = ap.parse_args()
+    if a.snapshot and (a.group or a.endless or a.peek or a.scores or a.alternatives or a.page_rows or a.memory_past_window):
+        ap.error("--snapshot is a mode of its own")
     if a.memory_past_window and (not a.page_rows or a.group or a.endless or a.peek or a.scores or a.alternatives):
         ap.error("--memory-past-window takes --page-rows and nothing else")
     if a.endless and a.group and not a.page_rows:
@@ -370,6 +415,17 @@ def main():
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             open(a.out, "w").write(text)
+        return
+    if a.snapshot:
+        lines = ["# " + " ".join(["python", "tools/stream_bench.py"] + sys.argv[1:]),
+                 f"# model {os.path.basename(path)}: {c.enc_layers} encoder layers, {c.dec_layers} decoder layers; HIP events around each call, median of {a.passes} passes"]
+        bench_snapshot(pkg, ctx, m, t, tm, a, lines)
+        text = "\n".join(lines) + "\n"
+        print(text, end="")
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            open(a.out, "w").write(text)
+        m.close(); ctx.close()
         return
     if a.endless and not a.group:
         lines = ["# " + " ".join(["python", "tools/stream_bench.py"] + sys.argv[1:]),

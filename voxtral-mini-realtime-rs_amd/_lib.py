@@ -56,6 +56,15 @@ class ModelCfg(C.Structure):
                [("rope_theta", C.c_float), ("norm_eps", C.c_float)]
 
 
+class SnapshotInfo(C.Structure):
+    """vox_snapshot_info: a session blob's decoded header"""
+    _fields_ = [("version", C.c_int32), ("sample_rate", C.c_uint32), ("gain", C.c_float), ("token", C.c_int32),
+                ("total_bytes", C.c_uint64), ("fingerprint", C.c_uint64), ("t_embed_hash", C.c_uint64),
+                ("samples_pushed", C.c_int64), ("samples_16k", C.c_int64), ("samples_in", C.c_int64)] + \
+               [(n, C.c_int32) for n in ("positions", "enc_position", "ids", "scores", "alternatives", "n_scores", "n_alts", "enc_rows", "dec_rows", "reserved")] + \
+               [("section_offset", C.c_uint64 * 9), ("section_bytes", C.c_uint64 * 9)]
+
+
 class Timings(C.Structure):
     _fields_ = [("preprocess_ms", C.c_double), ("encode_ms", C.c_double), ("decode_ms", C.c_double), ("total_ms", C.c_double),
                 ("decode_tokens", C.c_int32), ("graph_replays", C.c_int32)]
@@ -230,6 +239,16 @@ SIGNATURES = {
     "vox_stream_group_pages_for": (i32, [i64, i32, i32, P(i32), P(i32)]),
     "vox_debug_stream_group_pages": (i32, [vp, i32, vp, i32, P(i32)]),
     "vox_records_rows": (i32, [vp, vp, i32, i32, i32, vp, vp, i32]),
+    # snapshot and resume: (blob, nbytes, vox_snapshot_info); (cfg, positions, sample_rate, n_samples, scores, alternatives, out); the streams' three calls
+    "vox_snapshot_describe": (i32, [vp, sz, P(SnapshotInfo)]),
+    "vox_snapshot_bytes_for": (i32, [P(ModelCfg), i64, u32, sz, i32, i32, P(sz)]),
+    "vox_stream_snapshot_size": (i32, [vp, P(sz)]),
+    "vox_stream_snapshot": (i32, [vp, vp, sz, P(sz), i32]),
+    "vox_stream_restore": (i32, [vp, vp, sz, i32]),
+    "vox_stream_group_snapshot_size": (i32, [vp, i32, P(sz)]),
+    "vox_stream_group_snapshot": (i32, [vp, i32, vp, sz, P(sz), i32]),
+    "vox_stream_group_restore": (i32, [vp, i32, vp, sz, i32]),
+    "vox_debug_snapshot_kv": (i32, [vp, vp, vp, vp, vp, i32]),      # (ctx, vox_snapshot_kv_desc, cache_k, cache_v, blob, restore): ONE launch of the blob's K / V kernel
     "vox_transcribe_audio_scored": (i32, [vp, vp, sz, vp, vp, i32, P(i32), vp, vp, i32, i32]),
     "vox_transcribe_batch_scored": (i32, [vp, i32, P(vp), P(sz), vp, vp, P(vp), P(i32), P(i32), vp, vp, i32, i32]),
 }

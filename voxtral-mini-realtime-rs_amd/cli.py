@@ -110,7 +110,7 @@ def write_words(out, pkg, path, ids, scores, tokenizer, rate, alternatives=None)
     out.flush()
 
 
-def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_rate=False, words_out=None, peek=False, alts_k=0, endless=False):
+def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_rate=False, words_out=None, peek=False, alts_k=0, endless=False, suspend_every=0):
     """--live: the file through a live session (vox_stream) in pieces of `chunk_ms` milliseconds, the text so far on stderr whenever ids arrive.  The gain is the
     file's peak scale 0.95 / max|x| (bin/transcribe.rs:207; a file is known in advance -- a microphone caller passes its own), the whole file is one utterance (no
     --max-mel-frames chunks: the session's state is bounded by its ring), so the line equals the un-chunked path's.
@@ -121,7 +121,9 @@ def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_
     alts_k (--live-alternatives): the session also keeps every id's alts_k best alternatives and the step's entropy, for the words file.
     peek (--live-peek): after every push a "  ~[" line on stderr with the text so far plus the tentative tail -- what the line would be if the file ended here
     (vox_stream_peek: finish's ticks, taken back); the session, hence everything else, is as without the flag.
-    endless (--live-endless): the session is an endless one (vox_stream_create_endless: no 43-minute limit, the decoder cache a ring); the line is the same."""
+    endless (--live-endless): the session is an endless one (vox_stream_create_endless: no 43-minute limit, the decoder cache a ring); the line is the same.
+    suspend_every (--live-suspend-every N): after every N pushes the session is snapshotted to host memory (vox_stream_snapshot), the stream is freed, and a fresh one
+    is restored from the blob (vox_stream_restore) -- what a server does with a caller on hold; the line is the same."""
     x, sr = load_wav(path)
     rate = 16000
     if sr != 16000:
@@ -136,12 +138,15 @@ def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_
     peak = np.float32(np.abs(x16).max()) if x16.size else np.float32(0)
     gain = float(np.float32(0.95) / peak) if peak >= 1e-10 else 1.0              # audio/io.rs:59-68
     step = max(1, int(round(rate * chunk_ms / 1000.0)))
-    stream = model.create_stream(t_embed, gain=gain, sample_rate=rate, endless=endless)
-    try:
+    def create():
+        st = model.create_stream(t_embed, gain=gain, sample_rate=rate, endless=endless)
         if words_out is not None:
-            stream.set_scores(True)
+            st.set_scores(True)
             if alts_k:
-                stream.set_alternatives(alts_k)
+                st.set_alternatives(alts_k)
+        return st
+    stream = create()
+    try:
         ids = []
         text = lambda tail=(): tokenizer.decode([t for t in ids + [int(v) for v in tail] if t >= 1000]).strip()   # :309-318
         for a in range(0, x.size, step):
@@ -150,6 +155,10 @@ def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_
                 ids.extend(int(t) for t in new); log(f"  [{min(a + step, x.size) / rate:8.2f} s] {text()}")
             if peek:
                 log(f"  ~[{min(a + step, x.size) / rate:8.2f} s] {text(stream.peek())}")
+            if suspend_every and (a // step + 1) % suspend_every == 0:
+                blob = stream.snapshot(); stream.close()
+                stream = create(); stream.restore(blob)
+                log(f"  *[{min(a + step, x.size) / rate:8.2f} s] suspended to {blob.size} bytes and resumed in a fresh stream")
         ids.extend(int(t) for t in stream.finish())
         if words_out is not None:
             write_words(words_out, pkg, path, ids, stream.scores(), tokenizer, rate, stream.alternatives() if alts_k else None)
@@ -158,18 +167,20 @@ def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_
         stream.close()
 
 
-def transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, chunk_ms, n_members, words_out=None, peek=False, alts_k=0, page_rows=None, pool_pages=None, endless=False):
+def transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, chunk_ms, n_members, words_out=None, peek=False, alts_k=0, page_rows=None, pool_pages=None, endless=False,
+                          suspend_every=0):
     """--live-group N: the files N at a time through one stream group (vox_stream_group) in pieces of `chunk_ms` milliseconds: every call feeds each busy member its
     next piece, a file that ends (its member fed with finish) frees the member for the next file in input order.  Gains and lines as transcribe_live's (16 kHz: other
     rates are resampled first).  -> {file index: text}; a file that cannot be read is left out (the one-by-one path reports it).  words_out (--live-words): every
     member runs with scores on (and, with alts_k from --live-alternatives, with that many alternatives), a file's words go there when the file ends.  peek (--live-peek): after every call one vox_stream_group_peek for the members still
     busy, a "  ~[" line each: the text so far plus the tentative tail.  page_rows / pool_pages (--live-page-rows, --live-pool-pages): either one given makes the group a
     paged one (vox_stream_group_create_paged); the lines are the same.  endless (--live-endless): the group is an endless paged one (vox_stream_group_create_endless: no
-    member is refused at 43 minutes); the lines are the same."""
+    member is refused at 43 minutes); the lines are the same.  suspend_every (--live-suspend-every N): after every N calls each busy member is snapshotted to host
+    memory, reset, and restored from its blob (vox_stream_group_snapshot / _restore); the lines are the same."""
     step = max(1, int(round(16000 * chunk_ms / 1000.0)))
     group = model.create_stream_group(t_embed, n_members, page_rows=page_rows, pool_pages=pool_pages, endless=endless)
     text = lambda ids: tokenizer.decode([t for t in ids if t >= 1000]).strip()
-    texts = {}; busy = {}; nxt = 0      # busy: member -> [file index, samples, offset, ids]
+    texts = {}; busy = {}; nxt = 0; calls = 0      # busy: member -> [file index, samples, offset, ids]
     try:
         for k in range(n_members if words_out is not None else 0):
             group.set_scores(k, True)
@@ -203,6 +214,9 @@ def transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, chunk_ms, 
                     write_words(words_out, pkg, paths[b[0]], b[3], group.scores(k), tokenizer, 16000, group.alternatives(k) if alts_k else None)
             for k, tail in (group.peek(sorted(busy)) if peek and busy else {}).items():
                 b = busy[k]; log(f"  ~[{paths[b[0]]} {min(b[2], b[1].size) / 16000:8.2f} s] {text(b[3] + [int(v) for v in tail])}")
+            calls += 1
+            for k in (sorted(busy) if suspend_every and calls % suspend_every == 0 else []):
+                blob = group.snapshot(k); group.reset(k, 1.0); group.restore(k, blob)
         return texts
     finally:
         group.close()
@@ -364,6 +378,8 @@ def main(argv=None):
     ap.add_argument("--live-endless", action="store_true", help="with --live: an endless session (vox_stream_create_endless) -- no limit at "
                     "16 384 decoder positions (about 43 minutes); the decoder cache is a ring of a little more than one window and stops growing there.  With --live-group: "
                     "an endless paged group (vox_stream_group_create_endless; --live-page-rows / --live-pool-pages apply), no member refused at 43 minutes; same lines")
+    ap.add_argument("--live-suspend-every", type=int, default=0, metavar="N", help="with --live (also with --live-group): after every N pushes the session is snapshotted to "
+                    "host memory, its stream freed (its member reset), and a fresh one restored from the blob; the output is unchanged")
     ap.add_argument("--live-peek", action="store_true", help="with --live (also with --live-group, --live-native-rate, --live-words): after every push a line starting with "
                     "'  ~[' on stderr: the text so far plus the tentative tail, i.e. the line if the file ended here (vox_stream_peek); stdout, the '  [' lines and the "
                     "words file do not change")
@@ -395,6 +411,8 @@ def main(argv=None):
     a.live_alternatives = a.live_alternatives or 0
     if a.live_peek and not a.live:
         ap.error("--live-peek applies with --live")
+    if a.live_suspend_every and (not a.live or a.live_suspend_every < 0):
+        ap.error("--live-suspend-every N (N >= 1) applies with --live")
     if a.live_words and not a.live:
         ap.error("--live-words applies with --live")
     if a.live_group and not a.live:
@@ -503,7 +521,7 @@ def main(argv=None):
                         write_word_lines(rec_out, runner.words.get((i, k), []))
     if a.live_group:
         try:
-            texts = transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_group, words_out, a.live_peek, a.live_alternatives, a.live_page_rows, a.live_pool_pages, a.live_endless)
+            texts = transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_group, words_out, a.live_peek, a.live_alternatives, a.live_page_rows, a.live_pool_pages, a.live_endless, a.live_suspend_every)
         except Exception as e:      # the files fall back to one live session each
             log(f"Error in the stream group: {e}"); texts = {}
             if words_out is not None:      # the files' words come again with their lines
@@ -515,7 +533,7 @@ def main(argv=None):
         p = paths[i]
         try:
             t1 = time.time()
-            text = transcribe_live(pkg, p, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_native_rate, words_out, a.live_peek, a.live_alternatives, a.live_endless) if a.live else transcribe_one(pkg, p, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed, rec_out, a.alternatives or 0)
+            text = transcribe_live(pkg, p, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_native_rate, words_out, a.live_peek, a.live_alternatives, a.live_endless, a.live_suspend_every) if a.live else transcribe_one(pkg, p, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed, rec_out, a.alternatives or 0)
             log(f"{p}: {time.time() - t1:.3f}s")
         except Exception as e:      # per-utterance failure isolates to that line (empty), eval_wer.py:211-223 tolerates it
             log(f"Error transcribing {p}: {e}"); text = ""; rc = 1

@@ -8,6 +8,7 @@
 // src/models/time_embedding.rs.  No code is shared with oracle/ and there is no CPU fallback for compute.
 #include "vox_page_pool.h"
 #include "vox_dev_base.h"
+#include "vox_snapshot.h"
 
 #include <algorithm>
 #include <array>
@@ -3748,6 +3749,319 @@ extern "C" int32_t vox_debug_stream_front_tap_fetch(vox_stream* st, float* out_m
 }
 
 // ------------------------------------------------------------------------------------------------
+// Snapshot and resume (vox_stream_snapshot, vox_stream_restore; DESIGN.md section 8, "Snapshot and resume"; the blob's format: vox_snapshot.h).  Between two calls
+// nothing of a session is in flight or unverified, so the session IS its device arrays and its host mirror; the blob holds the part of them a later tick can read:
+// the K / V rows inside the two windows (launch_snapshot_kv gathers them from, and scatters them into, whatever layout the container has), the two sample rings in
+// logical order, the tokens, the host record lists.  The state block is not stored: its words follow from D (STRM_ENC_POS = R D, STRM_FRAME = 4 R D, STRM_TICKS =
+// D - PC) and from the target's ring capacity (STRM_HEAD).
+// ------------------------------------------------------------------------------------------------
+static const size_t SNAP_STAGE_MAX = (size_t)64 << 20;      // a host blob's K / V sections pass through at most this much device staging, in two halves
+// the model's fingerprint, computed once: the configuration, the parsed weights' byte count, and a hash of three 4 KB pieces of them (start, middle, end) read back here
+static int32_t model_fingerprint(vox_model* m, uint64_t* out) {
+    if (!m->snap_fingerprint_set) {
+        const uint64_t n = m->arena_primary_bytes ? m->arena_primary_bytes : m->arena_bytes, piece = std::min<uint64_t>(4096, n);
+        std::vector<unsigned char> buf((size_t)(3 * piece));
+        const uint64_t at[3] = {0, (n - piece) / 2 & ~(uint64_t)15, n - piece};
+        HIPCHK(hipStreamSynchronize(m->ctx->stream));
+        for (int i = 0; i < 3 && piece; i++) HIPCHK(hipMemcpy(buf.data() + (size_t)i * piece, m->arena + at[i], (size_t)piece, hipMemcpyDeviceToHost));
+        m->snap_fingerprint = vox_snap::snap_fingerprint(m->cfg, n, vox_snap::fnv1a(buf.data(), buf.size())); m->snap_fingerprint_set = true;
+    }
+    *out = m->snap_fingerprint; return VOX_OK;
+}
+// one stack's K / V sections between a cache (kp: everything but the blob pointers and the planes) and the blob's two sections.  A device blob: one launch straight on
+// the caller's buffer.  A host blob: pieces of whole planes through the staging area's halves in turn ([K piece | V piece] each), every piece one launch and two copies,
+// all in stream order -- the copy out of a half is queued ahead of the next launch into it.
+static int32_t snap_move_stack(hipStream_t s, vox::SnapshotKvParams kp, char* blob_k, char* blob_v, int32_t mem_kind, int restore, float* stage, size_t stage_bytes, int* half) {
+    const int rows = kp.hi - kp.lo, all = kp.layers * kp.heads;
+    if (rows <= 0) return VOX_OK;
+    const size_t plane_b = (size_t)rows * kp.hd * 4;
+    if (mem_kind == VOX_MEM_DEVICE) {
+        for (int p0 = 0; p0 < all; p0 += 32768) {
+            kp.plane0 = p0; kp.n_planes = std::min(32768, all - p0); kp.blob_k = reinterpret_cast<float*>(blob_k + (size_t)p0 * plane_b); kp.blob_v = reinterpret_cast<float*>(blob_v + (size_t)p0 * plane_b);
+            HIPCHK(launch_snapshot_kv(kp, restore, s));
+        }
+        return VOX_OK;
+    }
+    const size_t half_b = stage_bytes / 2; const int per = (int)std::min<size_t>((size_t)std::min(all, 32768), half_b / 2 / plane_b);
+    ARGCHK(stage && per >= 1, "internal: a %zu-byte plane does not fit the snapshot staging area of %zu bytes", plane_b, stage_bytes);
+    for (int p0 = 0; p0 < all; p0 += per, *half ^= 1) {
+        const int n = std::min(per, all - p0); const size_t piece_b = (size_t)n * plane_b;
+        char* hk = reinterpret_cast<char*>(stage) + (size_t)*half * half_b; char* hv = hk + piece_b;
+        kp.plane0 = p0; kp.n_planes = n; kp.blob_k = reinterpret_cast<float*>(hk); kp.blob_v = reinterpret_cast<float*>(hv);
+        if (restore) {
+            HIPCHK(hipMemcpyAsync(hk, blob_k + (size_t)p0 * plane_b, piece_b, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(hv, blob_v + (size_t)p0 * plane_b, piece_b, hipMemcpyHostToDevice, s));
+            HIPCHK(launch_snapshot_kv(kp, 1, s));
+        } else {
+            HIPCHK(launch_snapshot_kv(kp, 0, s));
+            HIPCHK(hipMemcpyAsync(blob_k + (size_t)p0 * plane_b, hk, piece_b, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(blob_v + (size_t)p0 * plane_b, hv, piece_b, hipMemcpyDeviceToHost, s));
+        }
+    }
+    return VOX_OK;
+}
+// the staging a host blob of this header needs: both halves of the larger stack, at most SNAP_STAGE_MAX (a multiple of 64 bytes, so both halves stay 16-byte aligned)
+static size_t snap_stage_bytes(const vox_snap::SnapHeader& h) {
+    const uint64_t most = 2 * std::max(h.sec_len[vox_snap::SEC_ENC_K], h.sec_len[vox_snap::SEC_DEC_K]);
+    return (size_t)((std::min<uint64_t>(2 * most, SNAP_STAGE_MAX) + 63) & ~(uint64_t)63);
+}
+// What snapshot and restore see of ONE session, whatever holds it -- a solo stream, a member of a slab, paged or endless group: its host mirror and record lists, its
+// device arrays, and its two K / V stacks as launch_snapshot_kv addresses them (everything but the rows and the blob pointers).  The container fills it in; the two
+// functions below never look at the container again.
+struct SnapSession {
+    vox_model* m; vox_ctx* ctx; const std::vector<float>* t_embed; FeedState* feed; ScoreState* sc; AltsState* al; float gain;
+    int* tokens; float* samples; int* state; int* h_state;
+    int cap, PC, max_pos;      // its encoder ring's capacity, the prefix positions, its position limit
+    vox::SnapshotKvParams enc, dec;
+    const char* who;           // the messages' subject: "the stream", "member 3"
+};
+static void snap_rows(vox::SnapshotKvParams* enc, vox::SnapshotKvParams* dec, const vox_snap::SnapHeader& h) { enc->lo = h.E - h.We; enc->hi = h.E; dec->lo = h.D - h.Wd; dec->hi = h.D; }
+// the header of the session as it stands (host arithmetic; token and fingerprint are the caller's)
+static void session_snap_header(const SnapSession& ss, vox_snap::SnapHeader* h) {
+    using namespace vox_snap;
+    const FeedState& f = *ss.feed; const vox_model_cfg& c = ss.m->cfg;
+    *h = SnapHeader{}; h->magic = SNAP_MAGIC; h->version = VOX_SNAPSHOT_VERSION;
+    h->t_embed_hash = fnv1a(ss.t_embed->data(), ss.t_embed->size() * 4);
+    h->gain = ss.gain; h->sample_rate = f.sr; h->n_pushed = f.n_pushed; h->n_written = f.n_written; h->in_written = f.in_written;
+    h->D = f.pos; h->E = c.reshape_factor * f.pos; h->ids_out = f.ids_out; h->scores_on = ss.sc->on ? 1 : 0; h->alts_k = ss.al->k;
+    SnapShape s; s.D = h->D; s.E = h->E; s.n_written = f.n_written; s.in_samples = f.sr != 16000 ? std::min<int64_t>(f.in_written, f.in_ring_n) : 0;
+    s.n_scores = ss.sc->on ? f.ids_out : 0; s.n_alts = ss.al->k > 0 ? f.ids_out : 0;
+    h->total_bytes = snap_layout(c, s, h);
+}
+// the last `n` samples of a ring of ring_n (a power of two) whose next write goes to `end`, in logical order, to dst: at most two copies
+static int32_t snap_ring_out(hipStream_t s, const float* ring, int ring_n, int64_t end, size_t n, char* dst, hipMemcpyKind kind) {
+    const int64_t first = end - (int64_t)n;
+    for (size_t w = 0; w < n;) {
+        const size_t off = (size_t)((first + (int64_t)w) & (ring_n - 1)), k = std::min(n - w, (size_t)ring_n - off);
+        HIPCHK(hipMemcpyAsync(dst + w * 4, ring + off, k * 4, kind, s)); w += k;
+    }
+    return VOX_OK;
+}
+// vox_stream_snapshot / vox_stream_group_snapshot behind the container: nothing of the session is written.  Two synchronisations: the token at D, the finished blob.
+static int32_t session_snapshot(const SnapSession& ss, void* blob, size_t cap, size_t* nbytes, int32_t mem_kind) {
+    using namespace vox_snap;
+    ARGCHK(blob && nbytes, "null argument"); ARGCHK(mem_kind == VOX_MEM_HOST || mem_kind == VOX_MEM_DEVICE, "bad mem_kind %d", mem_kind);
+    ARGCHK(!ss.feed->finished, "%s is finished: a reset starts its next utterance", ss.who);
+    ARGCHK(mem_kind == VOX_MEM_HOST || !(reinterpret_cast<uintptr_t>(blob) & 15), "a device blob must be 16-byte aligned");
+    SnapHeader h; session_snap_header(ss, &h);
+    ARGCHK(cap >= h.total_bytes, "snapshot: capacity %zu < the %llu bytes of the blob", cap, (unsigned long long)h.total_bytes);
+    vox_model* m = ss.m; hipStream_t s = ss.ctx->stream; const bool dev = mem_kind == VOX_MEM_DEVICE; char* b = static_cast<char*>(blob); const FeedState& f = *ss.feed;
+    VOXCHK(model_fingerprint(m, &h.fingerprint));
+    HIPCHK(hipMemcpyAsync(&h.token, ss.tokens + h.D, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));      // the first of the call's two synchronisations: the token at D (nothing of the session is in flight between calls)
+    ARGCHK(h.token >= 0 && h.token < m->cfg.vocab, "internal: %s: token %d at position %d is outside the vocabulary", ss.who, h.token, h.D);
+    DevBuf stage; const size_t stage_b = dev ? 0 : snap_stage_bytes(h);
+    if (stage_b && hipMalloc(&stage.p, stage_b) != hipSuccess) { (void)hipGetLastError(); stage.p = nullptr; return fail(VOX_ERR_HIP, "hipMalloc of the snapshot's %zu-byte staging area failed", stage_b); }
+    const hipMemcpyKind out = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    auto put = [&](uint64_t off, const void* src, size_t n) -> int32_t {      // host data into the blob (a device blob: read at the call's last synchronisation at the latest)
+        if (dev) HIPCHK(hipMemcpyAsync(b + off, src, n, hipMemcpyHostToDevice, s)); else std::memcpy(b + off, src, n);
+        return VOX_OK;
+    };
+    std::vector<vox_token_alts> alts;      // (lives until the call's last synchronisation: a device blob's copy reads it)
+    auto body = [&]() -> int32_t {
+        for (int i = 0; i < SEC_COUNT; i++) {      // the padding behind every section
+            const uint64_t end = h.sec_off[i] + h.sec_len[i], next = i + 1 < SEC_COUNT ? h.sec_off[i + 1] : h.total_bytes;
+            if (next > end) { if (dev) HIPCHK(hipMemsetAsync(b + end, 0, (size_t)(next - end), s)); else std::memset(b + end, 0, (size_t)(next - end)); }
+        }
+        int half = 0; vox::SnapshotKvParams enc = ss.enc, dec = ss.dec; snap_rows(&enc, &dec, h);
+        VOXCHK(snap_move_stack(s, enc, b + h.sec_off[SEC_ENC_K], b + h.sec_off[SEC_ENC_V], mem_kind, 0, stage.as<float>(), stage_b, &half));
+        VOXCHK(snap_move_stack(s, dec, b + h.sec_off[SEC_DEC_K], b + h.sec_off[SEC_DEC_V], mem_kind, 0, stage.as<float>(), stage_b, &half));
+        VOXCHK(snap_ring_out(s, ss.samples, STREAM_SAMPLE_RING, h.n_written, (size_t)(h.sec_len[SEC_SAMPLES] / 4), b + h.sec_off[SEC_SAMPLES], out));
+        if (h.sec_len[SEC_IN_SAMPLES]) VOXCHK(snap_ring_out(s, f.in_ring, f.in_ring_n, h.in_written, (size_t)(h.sec_len[SEC_IN_SAMPLES] / 4), b + h.sec_off[SEC_IN_SAMPLES], out));
+        HIPCHK(hipMemcpyAsync(b + h.sec_off[SEC_TOKENS], ss.tokens, (size_t)h.sec_len[SEC_TOKENS], out, s));
+        if (h.n_scores) {
+            ARGCHK(ss.sc->host.size() == (size_t)h.n_scores, "internal: %zu score records for %d ids", ss.sc->host.size(), h.n_scores);
+            VOXCHK(put(h.sec_off[SEC_SCORES], ss.sc->host.data(), (size_t)h.sec_len[SEC_SCORES]));
+        }
+        if (h.n_alts) {      // the list as vox_stream_alternatives reads it: "off" records where it does not reach
+            alts.assign((size_t)h.n_alts, AltsState::off());
+            std::copy(ss.al->host.begin(), ss.al->host.begin() + std::min(ss.al->host.size(), alts.size()), alts.begin());
+            VOXCHK(put(h.sec_off[SEC_ALTS], alts.data(), (size_t)h.sec_len[SEC_ALTS]));
+        }
+        VOXCHK(put(0, &h, sizeof h));
+        HIPCHK(hipStreamSynchronize(s));      // the second: the blob is complete, the staging area may go
+        return VOX_OK;
+    };
+    const int32_t r = body();
+    if (r != VOX_OK) (void)hipStreamSynchronize(s);      // (the staging area is freed behind whatever was queued)
+    else *nbytes = (size_t)h.total_bytes;
+    return r;
+}
+// every check of a restore, nothing changed: the header (a device blob's is downloaded first), the model, the t_embed, the position limit.  The rate is the
+// container's to check (a solo stream refuses another rate, a member takes the blob's).
+static int32_t session_restore_check(const SnapSession& ss, const void* blob, size_t nbytes, int32_t mem_kind, vox_snap::SnapHeader* out) {
+    using namespace vox_snap;
+    ARGCHK(blob, "null argument"); ARGCHK(mem_kind == VOX_MEM_HOST || mem_kind == VOX_MEM_DEVICE, "bad mem_kind %d", mem_kind);
+    ARGCHK(mem_kind == VOX_MEM_HOST || !(reinterpret_cast<uintptr_t>(blob) & 15), "a device blob must be 16-byte aligned");
+    const vox_model_cfg& c = ss.m->cfg;
+    SnapHeader h; char msg[256]; unsigned char head[sizeof(SnapHeader)];
+    ARGCHK(nbytes >= sizeof head, "snapshot: %zu bytes are shorter than the %zu-byte header", nbytes, sizeof head);
+    if (mem_kind == VOX_MEM_DEVICE) HIPCHK(hipMemcpy(head, blob, sizeof head, hipMemcpyDeviceToHost)); else std::memcpy(head, blob, sizeof head);      // a device blob: the header first
+    if (!snap_parse(head, nbytes, &h, msg, sizeof msg)) return fail(VOX_ERR_INVALID, "%s", msg);
+    uint64_t fp; VOXCHK(model_fingerprint(ss.m, &fp));
+    ARGCHK(h.fingerprint == fp, "snapshot: the blob was taken from another model (fingerprint %016llx, this model %016llx)", (unsigned long long)h.fingerprint, (unsigned long long)fp);
+    ARGCHK(h.enc_layers == c.enc_layers && h.enc_heads == c.enc_heads && h.enc_head_dim == c.enc_head_dim && h.enc_window == c.enc_window && h.dec_layers == c.dec_layers &&
+           h.dec_kv_heads == c.dec_kv_heads && h.dec_head_dim == c.dec_head_dim && h.dec_window == c.dec_window && h.vocab == c.vocab && h.reshape_factor == c.reshape_factor,
+           "snapshot: the blob's model geometry is not this model's");
+    ARGCHK(h.t_embed_hash == fnv1a(ss.t_embed->data(), ss.t_embed->size() * 4), "snapshot: the blob's session ran with another t_embed than %s", ss.who);
+    ARGCHK(h.D >= ss.PC && h.ids_out == h.D - ss.PC, "snapshot: position %d with %d ids handed out (the prefix ends at %d)", h.D, h.ids_out, ss.PC);
+    ARGCHK(h.D < ss.max_pos, "snapshot: the blob stands at decoder position %d, %s was created for %d", h.D, ss.who, ss.max_pos);
+    ARGCHK(h.We <= ss.cap, "internal: the blob's %d encoder rows exceed the ring of %d", h.We, ss.cap);
+    *out = h; return VOX_OK;
+}
+// the input ring section against the ring the session has at the blob's rate (behind the container's rate step)
+static int32_t session_restore_check_ring(const SnapSession& ss, const vox_snap::SnapHeader& h) {
+    const FeedState& f = *ss.feed;
+    ARGCHK(h.sample_rate == f.sr, "snapshot: the blob's session was fed at %u Hz, %s at %u Hz", h.sample_rate, ss.who, f.sr);
+    ARGCHK(h.sec_len[vox_snap::SEC_IN_SAMPLES] == (f.sr != 16000 ? (uint64_t)std::min<int64_t>(h.in_written, f.in_ring_n) * 4 : 0), "snapshot: an input ring section of %llu bytes for a ring of %d samples",
+           (unsigned long long)h.sec_len[vox_snap::SEC_IN_SAMPLES], f.in_ring_n);
+    return VOX_OK;
+}
+// the blob's payload into the session's arrays (the container has made room: cache rows or pages, lists), its state block, its host mirror and record lists; ends in
+// the call's synchronisation.  `dec` of ss addresses the cache as it is NOW.
+static int32_t session_restore_payload(const SnapSession& ss, const vox_snap::SnapHeader& h, const void* blob, int32_t mem_kind) {
+    using namespace vox_snap;
+    hipStream_t s = ss.ctx->stream; const bool dev = mem_kind == VOX_MEM_DEVICE; FeedState& f = *ss.feed; const char* b = static_cast<const char*>(blob);
+    DevBuf stage; const size_t stage_b = dev ? 0 : snap_stage_bytes(h);
+    if (stage_b && hipMalloc(&stage.p, stage_b) != hipSuccess) { (void)hipGetLastError(); stage.p = nullptr; return fail(VOX_ERR_HIP, "hipMalloc of the restore's %zu-byte staging area failed", stage_b); }
+    std::vector<int32_t> ids((size_t)h.ids_out);
+    auto body = [&]() -> int32_t {
+        int half = 0; char* wb = const_cast<char*>(b); vox::SnapshotKvParams enc = ss.enc, dec = ss.dec; snap_rows(&enc, &dec, h);
+        VOXCHK(snap_move_stack(s, enc, wb + h.sec_off[SEC_ENC_K], wb + h.sec_off[SEC_ENC_V], mem_kind, 1, stage.as<float>(), stage_b, &half));
+        VOXCHK(snap_move_stack(s, dec, wb + h.sec_off[SEC_DEC_K], wb + h.sec_off[SEC_DEC_V], mem_kind, 1, stage.as<float>(), stage_b, &half));
+        StreamSrc src; src.mem_kind = mem_kind;
+        const size_t n16 = (size_t)(h.sec_len[SEC_SAMPLES] / 4), nin = (size_t)(h.sec_len[SEC_IN_SAMPLES] / 4);
+        src.p = b + h.sec_off[SEC_SAMPLES]; if (n16) VOXCHK(ring_write_f32(s, ss.samples, STREAM_SAMPLE_RING, h.n_written - (int64_t)n16, src, 0, n16));
+        src.p = b + h.sec_off[SEC_IN_SAMPLES]; if (nin) VOXCHK(ring_write_f32(s, f.in_ring, f.in_ring_n, h.in_written - (int64_t)nin, src, 0, nin));
+        HIPCHK(hipMemcpyAsync(ss.tokens, b + h.sec_off[SEC_TOKENS], (size_t)h.sec_len[SEC_TOKENS], dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(ss.tokens + h.D, &h.token, 4, hipMemcpyHostToDevice, s));      // the header's validated token: the embedding lookup never reads an unchecked index
+        std::memset(ss.h_state, 0, sizeof(int) * STRM_WORDS);
+        ss.h_state[STRM_POS] = h.D; ss.h_state[STRM_ENC_POS] = h.E; ss.h_state[STRM_FRAME] = 4 * h.E; ss.h_state[STRM_HEAD] = h.E % ss.cap; ss.h_state[STRM_TICKS] = h.D - ss.PC;
+        HIPCHK(hipMemcpyAsync(ss.state, ss.h_state, sizeof(int) * STRM_WORDS, hipMemcpyHostToDevice, s));
+        // the records: the blob's lists, or the records of ids handed out with the feature off (the ids: the blob's tokens)
+        if (h.ids_out) { const char* t = b + h.sec_off[SEC_TOKENS] + (size_t)VOX_PREFIX_TOKENS * 4; if (dev) HIPCHK(hipMemcpyAsync(ids.data(), t, ids.size() * 4, hipMemcpyDeviceToHost, s)); else std::memcpy(ids.data(), t, ids.size() * 4); }
+        ss.sc->host.assign((size_t)h.ids_out, vox_token_score{NAN, NAN, -1, 0}); ss.al->host.clear(); ss.al->peeked.clear();
+        if (h.n_alts) ss.al->host.resize((size_t)h.n_alts);
+        if (dev) {
+            if (h.n_scores) HIPCHK(hipMemcpyAsync(ss.sc->host.data(), b + h.sec_off[SEC_SCORES], (size_t)h.sec_len[SEC_SCORES], hipMemcpyDeviceToHost, s));
+            if (h.n_alts) HIPCHK(hipMemcpyAsync(ss.al->host.data(), b + h.sec_off[SEC_ALTS], (size_t)h.sec_len[SEC_ALTS], hipMemcpyDeviceToHost, s));
+        } else {
+            if (h.n_scores) std::memcpy(ss.sc->host.data(), b + h.sec_off[SEC_SCORES], (size_t)h.sec_len[SEC_SCORES]);
+            if (h.n_alts) std::memcpy(ss.al->host.data(), b + h.sec_off[SEC_ALTS], (size_t)h.sec_len[SEC_ALTS]);
+        }
+        HIPCHK(hipStreamSynchronize(s));
+        for (int i = 0; !h.n_scores && i < h.ids_out; i++) ss.sc->host[(size_t)i].id = ids[(size_t)i];
+        return VOX_OK;
+    };
+    const int32_t r = body();
+    if (r != VOX_OK) { (void)hipStreamSynchronize(s); return r; }
+    f.n_pushed = h.n_pushed; f.n_written = h.n_written; f.in_written = h.in_written; f.pos = h.D; f.ids_out = h.ids_out; f.finished = false;
+    return VOX_OK;
+}
+
+// ---- a solo stream as a SnapSession.  An endless session's cache is addressed as the ring it becomes: below the wrap row % rows is the row
+static SnapSession stream_session(vox_stream* st) {
+    const vox_model_cfg& c = st->m->cfg; const vox_cache* kc = st->dec;
+    SnapSession ss{}; ss.m = st->m; ss.ctx = st->ctx; ss.t_embed = &st->t_embed; ss.feed = &st->feed; ss.sc = &st->sc; ss.al = &st->al; ss.gain = st->gain;
+    ss.tokens = st->tokens; ss.samples = st->samples; ss.state = st->state; ss.h_state = st->h_state; ss.cap = st->cap; ss.PC = st->PC; ss.max_pos = st->max_pos; ss.who = "the stream";
+    ss.enc.cache_k = st->kring; ss.enc.cache_v = st->vring; ss.enc.layers = c.enc_layers; ss.enc.heads = c.enc_heads; ss.enc.hd = c.enc_head_dim;
+    ss.enc.layout = vox::SNAP_RING; ss.enc.cap = st->cap; ss.enc.layer_stride = st->ring_layer; ss.enc.head_stride = (size_t)st->cap * c.enc_head_dim;
+    ss.dec.cache_k = kc->k; ss.dec.cache_v = kc->v; ss.dec.layers = c.dec_layers; ss.dec.heads = c.dec_kv_heads; ss.dec.hd = c.dec_head_dim;
+    ss.dec.layout = st->endless ? vox::SNAP_RING : vox::SNAP_FLAT; ss.dec.cap = kc->max_seq; ss.dec.layer_stride = kc->layer_stride; ss.dec.head_stride = (size_t)kc->max_seq * c.dec_head_dim;
+    return ss;
+}
+extern "C" int32_t vox_stream_snapshot_size(const vox_stream* st, size_t* nbytes) {
+    ARGCHK(st && nbytes, "null argument"); ARGCHK(!st->feed.finished, "the stream is finished: a reset starts its next utterance");
+    vox_snap::SnapHeader h; session_snap_header(stream_session(const_cast<vox_stream*>(st)), &h);
+    *nbytes = (size_t)h.total_bytes; return VOX_OK;
+}
+extern "C" int32_t vox_stream_snapshot(vox_stream* st, void* blob, size_t cap, size_t* nbytes, int32_t mem_kind) {
+    ARGCHK(st, "null stream"); VOXCHK(ctx_bind(st->ctx));
+    return session_snapshot(stream_session(st), blob, cap, nbytes, mem_kind);
+}
+// the decoder cache rows the doubling rule gives an uninterrupted session that stands at position D (stream_load_initial, stream_tick)
+static int stream_dec_rows_at(const vox_stream* st, int D) {
+    int rows = std::min(st->dec_limit, ENGINE_MAX_ROWS);
+    while (rows < D && rows < st->dec_limit) rows = std::min(st->dec_limit, 2 * rows);
+    return rows;
+}
+extern "C" int32_t vox_stream_restore(vox_stream* st, const void* blob, size_t nbytes, int32_t mem_kind) {
+    ARGCHK(st, "null stream"); VOXCHK(ctx_bind(st->ctx));
+    vox_model* m = st->m; hipStream_t s = st->ctx->stream;
+    // ---- every check, nothing changed
+    vox_snap::SnapHeader h; VOXCHK(session_restore_check(stream_session(st), blob, nbytes, mem_kind, &h)); VOXCHK(session_restore_check_ring(stream_session(st), h));
+    // ---- allocations (a failure leaves the session what it was): the decoder cache of the rule's size, an endless target's lists
+    HIPCHK(hipStreamSynchronize(s));
+    const int rows = stream_dec_rows_at(st, h.D);
+    vox_cache* fresh = nullptr;
+    if (st->dec->max_seq != rows) VOXCHK(cache_alloc(m, rows, &fresh));
+    while (st->endless && st->lists_cap < h.D) { const int32_t r = stream_lists_grow(st); if (r != VOX_OK) { (void)hipStreamSynchronize(s); cache_release(fresh); return r; } }
+    // ---- from here on the target is the blob's session
+    if (fresh) { HIPCHK(hipStreamSynchronize(s)); stream_dec_ungrow(st, &st->peek.old); cache_release(st->dec); st->dec = fresh; }
+    st->gain = h.gain;
+    int32_t r = VOX_OK;
+    if (engine_tab_enqueue(m, st->eng, st->dec) != hipSuccess) r = fail(VOX_ERR_HIP, "uploading the decode engine's layer table failed");      // as stream_load_initial: the first step finds its cache bound
+    if (r == VOX_OK && hipMemcpyAsync(&st->d_mem->gain, &st->gain, sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess) r = fail(VOX_ERR_HIP, "hipMemcpyAsync failed");
+    if (r == VOX_OK) r = session_restore_payload(stream_session(st), h, blob, mem_kind);
+    if (r != VOX_OK) { (void)hipStreamSynchronize(s); (void)stream_load_initial(st); return r; }      // a device failure half way: the target is a fresh session, not half of two
+    st->dec->len = st->verified_pos = h.D; st->eng_unverified = false;
+    st->eng_steps = st->op_steps = st->verified_eng_steps = st->verified_op_steps = 0; st->tap_rows = st->verified_tap_rows = 0; st->ftap_ticks = 0;
+    return VOX_OK;
+}
+
+// ---- one launch of the session blob's K / V kernel on host buffers (tests): vox_snapshot_kv_desc's layouts as SnapshotKvParams, ONE launch_snapshot_kv (none when
+// lo == hi).  Every argument is checked before the context is bound -- the range against the cache's rows, the ring or the table, every table entry the range touches
+// against the pool: nothing the kernel reads or writes lies outside the uploaded buffers.
+extern "C" int32_t vox_debug_snapshot_kv(vox_ctx* c, const vox_snapshot_kv_desc* d, float* cache_k, float* cache_v, float* blob, int32_t restore) {
+    ARGCHK(c && d && cache_k && cache_v && blob, "null argument");
+    ARGCHK(d->head_dim == 64 || d->head_dim == 128, "head_dim %d: the snapshot kernel serves head_dim 64 and 128", d->head_dim);
+    ARGCHK(d->layers >= 1 && d->layers <= 64 && d->n_heads >= 1 && d->n_heads <= 64, "bad geometry (%d layers, %d heads)", d->layers, d->n_heads);
+    ARGCHK(d->lo >= 0 && d->hi < (1 << 24), "rows %d .. %d outside 0 .. 2^24 - 1", d->lo, d->hi); ARGCHK(d->hi >= d->lo, "hi %d < lo %d", d->hi, d->lo);
+    ARGCHK(d->layout >= 0 && d->layout <= 3, "layout %d (0 flat, 1 ring, 2 page table, 3 ring table)", d->layout);
+    const int hd = d->head_dim, H = d->n_heads, n = d->hi - d->lo; const bool paged = d->layout >= 2;
+    SnapshotKvParams kp{}; kp.layers = d->layers; kp.heads = H; kp.hd = hd; kp.lo = d->lo; kp.hi = d->hi; kp.layout = d->layout;
+    size_t cache_f = 0;
+    if (!paged) {
+        ARGCHK(d->rows >= 1 && d->rows <= 16384, "rows %d out of range (1..16384)", d->rows);
+        ARGCHK(!d->page_rows && !d->pool_pages && !d->page_tab_len && !d->page_tab, "a flat or ring call takes no paged field");
+        ARGCHK(d->layer_stride >= (int64_t)H * d->rows * hd && d->layer_stride <= ((int64_t)1 << 28) && d->layer_stride % 4 == 0, "layer_stride %lld: a multiple of 4, at least the %lld floats of a layer's rows",
+               (long long)d->layer_stride, (long long)H * d->rows * hd);
+        if (d->layout == 0) ARGCHK(d->hi <= d->rows, "rows %d .. %d outside the cache's %d rows", d->lo, d->hi, d->rows);
+        else ARGCHK(n <= d->rows, "a ring of %d rows is shorter than the %d rows %d .. %d", d->rows, n, d->lo, d->hi);
+        kp.cap = d->rows; kp.layer_stride = (size_t)d->layer_stride; kp.head_stride = (size_t)d->rows * hd; cache_f = (size_t)d->layers * kp.layer_stride;
+    } else {
+        ARGCHK(d->page_rows >= 16 && d->page_rows <= 1024 && !(d->page_rows & (d->page_rows - 1)), "page_rows %d is not a power of two in 16..1024", d->page_rows);
+        ARGCHK(!d->rows, "a paged call takes no rows"); ARGCHK(d->page_tab, "null argument (page_tab)");
+        ARGCHK(d->pool_pages >= 1 && d->pool_pages <= (1 << 16), "pool_pages %d out of range", d->pool_pages); ARGCHK(d->page_tab_len >= 1 && d->page_tab_len <= 1024, "page_tab_len %d out of range (1..1024)", d->page_tab_len);
+        while ((1 << kp.shift) < d->page_rows) kp.shift++;
+        kp.page_floats = (size_t)H * d->page_rows * hd; kp.head_stride = (size_t)d->page_rows * hd; kp.layer_stride = kp.page_floats * d->pool_pages; kp.tab_len = d->page_tab_len;
+        ARGCHK(d->layer_stride == 0 || (size_t)d->layer_stride == kp.layer_stride, "layer_stride %lld: a paged cache's layers are %zu floats apart", (long long)d->layer_stride, kp.layer_stride);
+        if (n > 0) {
+            const int pages = ((d->hi - 1) >> kp.shift) - (d->lo >> kp.shift) + 1;
+            if (d->layout == 2) ARGCHK(((d->hi - 1) >> kp.shift) < d->page_tab_len, "row %d lies in page %d of a table of %d entries", d->hi - 1, (d->hi - 1) >> kp.shift, d->page_tab_len);
+            else ARGCHK(pages <= d->page_tab_len, "rows %d .. %d touch %d pages, the ring table has %d entries", d->lo, d->hi, pages, d->page_tab_len);
+            int bad = 0;
+            if (!snapshot_kv_pages_ok(d->page_tab, d->layout, kp.shift, d->page_tab_len, d->lo, d->hi, d->pool_pages, &bad))
+                return fail(VOX_ERR_INVALID, "table entry %d of the range is %d, outside the pool's %d pages", bad, d->page_tab[d->layout == 3 ? bad % d->page_tab_len : bad], d->pool_pages);
+        }
+        cache_f = (size_t)d->layers * kp.layer_stride;
+    }
+    ARGCHK(cache_f <= ((size_t)1 << 28), "a cache of %zu floats is more than this entry uploads", cache_f);
+    if (n == 0) return VOX_OK;      // nothing to move: no launch, the arrays stay untouched
+    VOXCHK(ctx_bind(c));
+    hipStream_t s = c->stream; const size_t plane_f = (size_t)d->layers * H * n * hd;
+    DevBuf dk, dv, db, dt;
+    HIPCHK(dk.alloc(cache_f * 4)); HIPCHK(dv.alloc(cache_f * 4)); HIPCHK(db.alloc(2 * plane_f * 4)); HIPCHK(dt.alloc(paged ? (size_t)d->page_tab_len * 4 : 4));
+    HIPCHK(hipMemcpyAsync(dk.p, cache_k, cache_f * 4, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(dv.p, cache_v, cache_f * 4, hipMemcpyHostToDevice, s));
+    if (restore) HIPCHK(hipMemcpyAsync(db.p, blob, 2 * plane_f * 4, hipMemcpyHostToDevice, s)); else HIPCHK(hipMemsetAsync(db.p, 0xff, 2 * plane_f * 4, s));      // a word the pack does not write comes back NaN
+    if (paged) { HIPCHK(hipMemcpyAsync(dt.p, d->page_tab, (size_t)d->page_tab_len * 4, hipMemcpyHostToDevice, s)); kp.tab = dt.as<int>(); }
+    kp.cache_k = dk.as<float>(); kp.cache_v = dv.as<float>(); kp.blob_k = db.as<float>(); kp.blob_v = db.as<float>() + plane_f;
+    HIPCHK(launch_snapshot_kv(kp, restore != 0, s));
+    HIPCHK(hipMemcpyAsync(cache_k, dk.p, cache_f * 4, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(cache_v, dv.p, cache_f * 4, hipMemcpyDeviceToHost, s));
+    if (!restore) HIPCHK(hipMemcpyAsync(blob, db.p, 2 * plane_f * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return VOX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Stream group (vox_stream_group; DESIGN.md section 8, "Stream groups"): N <= 16 member sessions on one model and one t_embed, advanced together.  A call knows every
 // fed member's due tick count d_i before it launches anything: the members sorted by d_i descending, round r runs ONE tick of the first n_r = #{d_i > r} of them --
 // stream_encode_round at 4 n_r rows (the code of a solo stream's tick) and, as the decode half, xf_chain at n_r rows on the group's decoder slab.  One upload (the
@@ -4347,6 +4661,87 @@ extern "C" int32_t vox_debug_stream_group_tap_fetch(vox_stream_group* g, int32_t
     *rows = n;
     (void)hipFree(me.tap); me.tap = nullptr; me.tap_max = 0;
     return group_upload_members(g);
+}
+
+// ---- snapshot and resume of a member (vox_stream_group_snapshot, vox_stream_group_restore): the solo stream's two functions on the member seen as a SnapSession --
+// its slice of the slab as flat planes, or its row of the page table (a ring table in an endless group).  The blob does not know where it came from.
+static SnapSession group_session(vox_stream_group* g, int i) {
+    const vox_model_cfg& c = g->m->cfg; GroupMember& me = g->mem[(size_t)i]; const StreamMember& hm = g->h_mem[(size_t)i];
+    static thread_local char who[32]; snprintf(who, sizeof who, "member %d", i);
+    SnapSession ss{}; ss.m = g->m; ss.ctx = g->ctx; ss.t_embed = &g->t_embed; ss.feed = &me.feed; ss.sc = &me.sc; ss.al = &me.al; ss.gain = hm.gain;
+    ss.tokens = hm.tokens; ss.samples = const_cast<float*>(hm.samples); ss.state = hm.state; ss.h_state = me.h_state; ss.cap = g->g.cap; ss.PC = g->g.PC; ss.max_pos = g->g.max_pos; ss.who = who;
+    ss.enc.cache_k = hm.kring; ss.enc.cache_v = hm.vring; ss.enc.layers = c.enc_layers; ss.enc.heads = c.enc_heads; ss.enc.hd = c.enc_head_dim;
+    ss.enc.layout = vox::SNAP_RING; ss.enc.cap = g->g.cap; ss.enc.layer_stride = g->ring_layer; ss.enc.head_stride = (size_t)g->g.cap * c.enc_head_dim;
+    ss.dec.layers = c.dec_layers; ss.dec.heads = c.dec_kv_heads; ss.dec.hd = c.dec_head_dim; ss.dec.layer_stride = g->layer_stride;
+    if (g->paged) {
+        ss.dec.cache_k = g->dec_k; ss.dec.cache_v = g->dec_v; ss.dec.layout = g->endless ? vox::SNAP_PAGED_RING : vox::SNAP_PAGED; ss.dec.head_stride = (size_t)g->pool.page_rows * c.dec_head_dim;
+        ss.dec.tab = g->d_tab + (size_t)i * g->pool.tab_len; ss.dec.shift = g->pool.shift; ss.dec.tab_len = g->pool.tab_len; ss.dec.page_floats = g->page_floats;
+    } else {
+        ss.dec.cache_k = g->dec_k + (size_t)i * g->seq_stride; ss.dec.cache_v = g->dec_v + (size_t)i * g->seq_stride; ss.dec.layout = vox::SNAP_FLAT; ss.dec.head_stride = (size_t)g->g.max_pos * c.dec_head_dim;
+    }
+    return ss;
+}
+// in front of a launch on a paged member: every table entry the blob's decoder rows touch names a page of the pool (the host mirror of the member's table)
+static int32_t group_snap_pages_check(const vox_stream_group* g, int i, const vox_snap::SnapHeader& h) {
+    if (!g->paged) return VOX_OK;
+    int bad = 0;
+    if (!snapshot_kv_pages_ok(g->pool.mem[(size_t)i].tab.data(), g->endless ? vox::SNAP_PAGED_RING : vox::SNAP_PAGED, g->pool.shift, g->pool.tab_len, h.D - h.Wd, h.D, g->pool.pool_pages, &bad))
+        return fail(VOX_ERR_INVALID, "internal: member %d: logical page %d of its window is %d, outside the pool's %d pages", i, bad, g->pool.at(i, bad), g->pool.pool_pages);
+    return VOX_OK;
+}
+extern "C" int32_t vox_stream_group_snapshot_size(const vox_stream_group* g, int32_t member, size_t* nbytes) {
+    ARGCHK(g && nbytes, "null argument"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1);
+    ARGCHK(!g->mem[(size_t)member].feed.finished, "member %d is finished: a reset starts its next utterance", member);
+    vox_snap::SnapHeader h; session_snap_header(group_session(const_cast<vox_stream_group*>(g), member), &h);
+    *nbytes = (size_t)h.total_bytes; return VOX_OK;
+}
+extern "C" int32_t vox_stream_group_snapshot(vox_stream_group* g, int32_t member, void* blob, size_t cap, size_t* nbytes, int32_t mem_kind) {
+    ARGCHK(g, "null group"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1);
+    VOXCHK(ctx_bind(g->ctx));
+    const SnapSession ss = group_session(g, member);
+    vox_snap::SnapHeader h; session_snap_header(ss, &h); VOXCHK(group_snap_pages_check(g, member, h));
+    return session_snapshot(ss, blob, cap, nbytes, mem_kind);
+}
+// The member becomes the blob's session: its rate from the blob (as vox_stream_group_reset_rate sets it), the blob's gain.  A paged member is planned like an advance:
+// the pages it holds now count as free, the pages vox_stream_group_pages_for(D) names are needed -- a pool without room refuses, and the group is untouched.
+extern "C" int32_t vox_stream_group_restore(vox_stream_group* g, int32_t member, const void* blob, size_t nbytes, int32_t mem_kind) {
+    ARGCHK(g, "null group"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1);
+    VOXCHK(ctx_bind(g->ctx));
+    GroupMember& me = g->mem[(size_t)member]; hipStream_t s = g->ctx->stream;
+    // ---- every check, nothing changed
+    vox_snap::SnapHeader h; VOXCHK(session_restore_check(group_session(g, member), blob, nbytes, mem_kind, &h));
+    int ring_n = 0;
+    if (h.sample_rate != 16000) { ResamplePlan rp; size_t rs_bytes; VOXCHK(stream_rate_plan(h.sample_rate, &rp, &rs_bytes, &ring_n)); }
+    ARGCHK(h.sec_len[vox_snap::SEC_IN_SAMPLES] == (uint64_t)std::min<int64_t>(h.in_written, ring_n) * 4, "snapshot: an input ring section of %llu bytes for a ring of %d samples",
+           (unsigned long long)h.sec_len[vox_snap::SEC_IN_SAMPLES], ring_n);
+    int first = 0, n_pages = 0;
+    if (g->paged) {
+        pages_held(h.D, g->pool.page_rows, g->pool.window, &first, &n_pages);
+        ARGCHK(n_pages <= g->pool.held(member) + g->pool.n_free(), "member %d: the restore needs %d pages of the pool, %d are free (the %d the member holds now included; a reset returns a member's pages)",
+               member, n_pages, g->pool.held(member) + g->pool.n_free(), g->pool.held(member));
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    VOXCHK(group_member_set_rate(g, member, h.sample_rate));      // refused: the member, its rate and its state are as they were
+    // ---- from here on the member is the blob's session
+    int32_t r = VOX_OK;
+    auto body = [&]() -> int32_t {
+        if (g->endless) VOXCHK(group_lists_grow(g, member, h.D));
+        if (g->paged) {
+            int64_t q0, q1, t0, t1;
+            g->pool.release_all(member, &q0, &q1); g->pool.start_at(member, first);
+            if (!g->pool.take(member, h.D, &t0, &t1)) return fail(VOX_ERR_INVALID, "internal: member %d: the planned pages are not free", member);
+            VOXCHK(group_table_upload(g, member, q0, q1)); VOXCHK(group_table_upload(g, member, t0, t1));
+            VOXCHK(group_snap_pages_check(g, member, h));
+        }
+        g->h_mem[(size_t)member].gain = h.gain;
+        VOXCHK(group_upload_members(g));
+        VOXCHK(session_restore_check_ring(group_session(g, member), h));
+        return session_restore_payload(group_session(g, member), h, blob, mem_kind);
+    };
+    r = body();
+    if (r != VOX_OK) { (void)hipStreamSynchronize(s); (void)group_member_seed(g, member); return r; }      // a failure half way: the member is a fresh session, not half of two
+    me.steps = 0;
+    return VOX_OK;
 }
 
 // ---- debug: the sample front ends on their own (tests).  form 0: the single clip's (clip_front_end); form 1: the batch drivers' (group_peak_scales when norm_group is

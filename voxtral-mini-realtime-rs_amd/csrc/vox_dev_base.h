@@ -160,6 +160,7 @@ struct vox_model {
     // hand-off timeout found later takes exactly these rows back (cache length -= pw_pend_rows), so "repeat the step" appends at the failed position again
     vox_cache* pw_pend_cache = nullptr; uint64_t pw_pend_gen = 0; int pw_pend_rows = 0; bool pw_verdict_failed = false;
     vox_timings timings{};
+    uint64_t snap_fingerprint = 0; bool snap_fingerprint_set = false;      // the session blobs' model fingerprint (vox_snapshot.h), computed at the first snapshot or restore
     // vox_debug_batch_tap_*: units (caller indices) armed for the next batch call; `on` during that call; out / rows hold the call's rows until fetched
     struct { std::vector<int> units; int max_rows = 0; bool armed = false, on = false, ready = false; float* out = nullptr; int* rows = nullptr; } tap;
 };

@@ -526,5 +526,29 @@ struct StreamKeepParams {
 };
 size_t stream_keep_floats(int layers, int n_heads, int hd, int rows);      // one slot's area
 hipError_t launch_stream_keep(const StreamKeepParams& p, int restore, hipStream_t s);
+// ---- a session blob's K / V sections (vox_stream_snapshot / vox_stream_restore; DESIGN.md section 8, "Snapshot and resume"): ONE launch moves the logical rows
+// lo .. hi - 1 of the planes plane0 .. plane0 + n_planes - 1 (plane = layer * heads + head) of K and of V between the blob's dense layout -- blob_k / blob_v
+// [n_planes][hi - lo][hd], the first plane of the launch at the pointer -- and a cache addressed in one of the project's four layouts.  Row r of (layer, head) lives at
+//   SNAP_FLAT        cache + layer * layer_stride + head * head_stride + r * hd                          (a solo cache, a slab slice: head_stride = rows * hd)
+//   SNAP_RING        ... + (r % cap) * hd                                                                  (the encoder ring, an endless session's decoder ring; any cap)
+//   SNAP_PAGED       cache + layer * layer_stride + tab[r >> shift] * page_floats + head * head_stride + (r & (page_rows - 1)) * hd     (head_stride = page_rows * hd)
+//   SNAP_PAGED_RING  the same with tab[(r >> shift) % tab_len]
+// restore = 0 packs (cache -> blob), 1 unpacks (blob -> cache), on the same arguments.  16-byte accesses, no arithmetic on the values; cache rows outside lo .. hi - 1
+// keep their bits.  hd 64 | 128; a ring holds the range (hi - lo <= cap; the range's pages <= tab_len), so no slot is named twice.  lo == hi launches nothing.  The
+// table entries are the CALLER's to validate against the pool (snapshot_kv_pages_ok): the kernel reads tab[] as it is.
+enum SnapLayout { SNAP_FLAT = 0, SNAP_RING = 1, SNAP_PAGED = 2, SNAP_PAGED_RING = 3 };
+struct SnapshotKvParams {
+    float *cache_k, *cache_v; float *blob_k, *blob_v;
+    int layers, heads, hd, lo, hi;
+    int plane0, n_planes;                   // the launch's planes (a host blob passes through staging in pieces of whole planes); n_planes 0: all of them
+    int layout;                             // SnapLayout
+    size_t layer_stride, head_stride;       // floats
+    int cap;                                // SNAP_RING
+    const int* tab; int shift, tab_len;     // SNAP_PAGED / SNAP_PAGED_RING: device table of the session, log2(page_rows); tab_len: SNAP_PAGED the entries the table has, SNAP_PAGED_RING the ring's
+    size_t page_floats;                     // floats between two pages of one layer
+};
+// host: every table entry the range lo .. hi - 1 touches lies in 0 .. pool_pages - 1 (tab: the HOST copy of the table); *bad_page: the first logical page that does not
+bool snapshot_kv_pages_ok(const int* tab, int layout, int shift, int tab_len, int lo, int hi, int pool_pages, int* bad_page);
+hipError_t launch_snapshot_kv(const SnapshotKvParams& p, int restore, hipStream_t s);
 
 }  // namespace vox

@@ -4896,6 +4896,84 @@ hipError_t launch_stream_keep(const StreamKeepParams& p, int restore, hipStream_
     return hipGetLastError();
 }
 
+// ---- a session blob's K / V sections (SnapshotKvParams, vox_kernels.h).  blockIdx.y is the launch's plane, the x dimension strides over the plane's
+// (hi - lo) * hd / 4 float4s in blob order: a wave's 64 lanes cover 1 KB of the blob in one piece and, on the cache side, whole rows of 256 or 512 bytes that follow
+// each other except where a ring wraps or a page ends.  Two float4s of K and two of V are in flight per thread and trip.  The ring forms take no modulo per row:
+// the host's checks (the ring holds the range) leave one conditional subtraction from the slot of row lo.
+template <int HD, int LAYOUT, int RESTORE>
+__global__ __launch_bounds__(256) void snapshot_kv_kernel(SnapshotKvParams p) {
+    constexpr int HQ_SHIFT = HD == 64 ? 4 : 5, HQ = 1 << HQ_SHIFT;      // float4s per row
+    const int plane = p.plane0 + (int)blockIdx.y, layer = plane / p.heads, head = plane - layer * p.heads;
+    const long n = (long)(p.hi - p.lo) << HQ_SHIFT;
+    const size_t base = (size_t)layer * p.layer_stride + (size_t)head * p.head_stride;
+    float4* __restrict__ ck = reinterpret_cast<float4*>(p.cache_k + base);
+    float4* __restrict__ cv = reinterpret_cast<float4*>(p.cache_v + base);
+    float4* __restrict__ bk = reinterpret_cast<float4*>(p.blob_k) + (long)blockIdx.y * n;
+    float4* __restrict__ bv = reinterpret_cast<float4*>(p.blob_v) + (long)blockIdx.y * n;
+    const int lo_slot = LAYOUT == SNAP_RING ? p.lo % p.cap : 0;
+    const int pg0 = LAYOUT >= SNAP_PAGED ? p.lo >> p.shift : 0, e0 = LAYOUT == SNAP_PAGED_RING ? pg0 % p.tab_len : pg0;
+    const long page_q = (long)(p.page_floats >> 2);
+    auto at = [&](long i) -> long {      // the cache's float4 of the blob's float4 i
+        const int r = (int)(i >> HQ_SHIFT), q = (int)(i & (HQ - 1));
+        if (LAYOUT == SNAP_FLAT) return ((long)(p.lo + r) << HQ_SHIFT) + q;
+        if (LAYOUT == SNAP_RING) { int slot = lo_slot + r; if (slot >= p.cap) slot -= p.cap; return ((long)slot << HQ_SHIFT) + q; }
+        const int row = p.lo + r; int e = e0 + ((row >> p.shift) - pg0);
+        if (LAYOUT == SNAP_PAGED_RING && e >= p.tab_len) e -= p.tab_len;
+        return (long)p.tab[e] * page_q + ((long)(row & ((1 << p.shift) - 1)) << HQ_SHIFT) + q;
+    };
+    const long step = (long)gridDim.x * 256;
+    long i = (long)blockIdx.x * 256 + threadIdx.x;
+    for (; i + step < n; i += 2 * step) {
+        const long a0 = at(i), a1 = at(i + step);
+        if (RESTORE) { const float4 k0 = bk[i], v0 = bv[i], k1 = bk[i + step], v1 = bv[i + step]; ck[a0] = k0; cv[a0] = v0; ck[a1] = k1; cv[a1] = v1; }
+        else { const float4 k0 = ck[a0], v0 = cv[a0], k1 = ck[a1], v1 = cv[a1]; bk[i] = k0; bv[i] = v0; bk[i + step] = k1; bv[i + step] = v1; }
+    }
+    if (i < n) {
+        const long a0 = at(i);
+        if (RESTORE) { const float4 k0 = bk[i], v0 = bv[i]; ck[a0] = k0; cv[a0] = v0; }
+        else { const float4 k0 = ck[a0], v0 = cv[a0]; bk[i] = k0; bv[i] = v0; }
+    }
+}
+bool snapshot_kv_pages_ok(const int* tab, int layout, int shift, int tab_len, int lo, int hi, int pool_pages, int* bad_page) {
+    if (layout < SNAP_PAGED || lo >= hi) return true;
+    for (int pg = lo >> shift; pg <= ((hi - 1) >> shift); pg++) {
+        const int e = tab[layout == SNAP_PAGED_RING ? pg % tab_len : pg];
+        if (e < 0 || e >= pool_pages) { if (bad_page) *bad_page = pg; return false; }
+    }
+    return true;
+}
+hipError_t launch_snapshot_kv(const SnapshotKvParams& p, int restore, hipStream_t s) {
+    const int all = p.layers * p.heads, n_planes = p.n_planes ? p.n_planes : all - p.plane0;
+    if (p.layers < 1 || p.heads < 1 || (p.hd != 64 && p.hd != 128) || p.lo < 0 || p.hi < p.lo || p.plane0 < 0 || n_planes < 1 || p.plane0 + n_planes > all || n_planes > 65535) return hipErrorInvalidValue;
+    if (p.layout < SNAP_FLAT || p.layout > SNAP_PAGED_RING || (p.layer_stride & 3) || (p.head_stride & 3)) return hipErrorInvalidValue;
+    if (p.hi == p.lo) return hipSuccess;      // nothing to move: no launch
+    if (!p.cache_k || !p.cache_v || !p.blob_k || !p.blob_v) return hipErrorInvalidValue;
+    if ((reinterpret_cast<uintptr_t>(p.cache_k) | reinterpret_cast<uintptr_t>(p.cache_v) | reinterpret_cast<uintptr_t>(p.blob_k) | reinterpret_cast<uintptr_t>(p.blob_v)) & 15) return hipErrorInvalidValue;
+    if (p.layout == SNAP_RING && (p.cap < 1 || p.hi - p.lo > p.cap)) return hipErrorInvalidValue;
+    if (p.layout >= SNAP_PAGED) {
+        const int page_rows = 1 << p.shift, pages = ((p.hi - 1) >> p.shift) - (p.lo >> p.shift) + 1;
+        if (!p.tab || p.shift < 0 || p.shift > 20 || p.tab_len < 1 || (p.page_floats & 3) || p.head_stride < (size_t)page_rows * p.hd) return hipErrorInvalidValue;
+        if (p.layout == SNAP_PAGED ? ((p.hi - 1) >> p.shift) >= p.tab_len : pages > p.tab_len) return hipErrorInvalidValue;
+    }
+    const long n = (long)(p.hi - p.lo) * (p.hd / 4);
+    // about 8 workgroups per CU over the launch (256 CUs), each thread with at least two trips' worth where the plane is that long
+    int bx = (int)std::min<long>((n + 511) / 512, std::max(1, 2048 / n_planes));
+    if (bx < 1) bx = 1;
+    SnapshotKvParams q = p; q.n_planes = n_planes;
+    const dim3 grid(bx, n_planes), block(256);
+#define SNAP_GO(HD, L) do { if (restore) snapshot_kv_kernel<HD, L, 1><<<grid, block, 0, s>>>(q); else snapshot_kv_kernel<HD, L, 0><<<grid, block, 0, s>>>(q); } while (0)
+#define SNAP_HD(L) do { if (p.hd == 64) SNAP_GO(64, L); else SNAP_GO(128, L); } while (0)
+    switch (p.layout) {
+        case SNAP_FLAT: SNAP_HD(SNAP_FLAT); break;
+        case SNAP_RING: SNAP_HD(SNAP_RING); break;
+        case SNAP_PAGED: SNAP_HD(SNAP_PAGED); break;
+        default: SNAP_HD(SNAP_PAGED_RING); break;
+    }
+#undef SNAP_HD
+#undef SNAP_GO
+    return hipGetLastError();
+}
+
 // ---- what else the model weighed at an id (vox_token_alts, voxtral_hip.h): the row's k best columns by the rule with their log-probabilities, and the row's entropy.
 // ONE device function for every launch form, on score_row's scan order (column 4 i + j -> thread i % NT, leftovers to threads 0 .. 2, float4 loads or the same four
 // columns singly), so the record is a function of the row's values, V and k alone.

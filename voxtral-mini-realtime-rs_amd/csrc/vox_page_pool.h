@@ -83,6 +83,8 @@ struct PagePool {
         for (int64_t q = m.first; q < m.end; q++) { free_.push_back(m.tab[slot(q)]); m.tab[slot(q)] = -1; }
         m.first = m.end = 0;
     }
+    // restore (vox_stream_group_restore): a member that holds nothing (release_all) starts at logical page q -- the first page of the window it is about to take
+    void start_at(int member, int64_t q) { Member& m = mem[(size_t)member]; if (m.first == m.end) m.first = m.end = q; }
     Mark mark() const { Mark k; k.peak = peak; for (const Member& m : mem) k.end.push_back(m.end); return k; }
     // the pages taken since the mark go back in the reverse order of their taking, last member first: the stack, the tables and the peak are what they were,
     // PROVIDED the members took their pages in ascending member-slot order `order` (the order given here) and nothing was released in between

@@ -362,6 +362,57 @@ def rope_rows(head_dim, theta, first_pos, n):
     return inv, cos, sin
 
 
+class SnapshotKvDesc(C.Structure):
+    """vox_snapshot_kv_desc (include/voxtral_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("layers", "n_heads", "head_dim", "lo", "hi", "layout", "rows", "page_rows", "pool_pages", "page_tab_len")] + \
+               [("layer_stride", C.c_int64), ("page_tab", C.c_void_p)]
+
+
+def snapshot_kv(ctx, cache_k, cache_v, lo, hi, n_heads, head_dim, layout="flat", rows=0, page_tab=None, page_rows=0, blob=None):
+    """vox_debug_snapshot_kv: ONE launch of the session blob's K / V kernel over the logical rows lo .. hi - 1.  layout "flat" | "ring": cache_k / cache_v
+    [layers, layer_floats] with head h of a layer at h * rows * head_dim (ring: row r at r % rows); "paged" | "paged_ring": [layers, pool_pages, n_heads, page_rows,
+    head_dim] with page_tab [entries] int32.  blob None: pack -> the blob [2, layers, n_heads, hi - lo, head_dim]; blob given: unpack it -> (cache_k, cache_v) after the
+    launch.  The arguments are left as they are."""
+    ck = _f32(cache_k).copy(); cv = _f32(cache_v).copy()
+    code = {"flat": 0, "ring": 1, "paged": 2, "paged_ring": 3}[layout]
+    if ck.shape != cv.shape or ck.ndim != (2 if code < 2 else 5):
+        raise VoxError(1, "snapshot_kv: bad shapes")
+    d = SnapshotKvDesc(layers=ck.shape[0], n_heads=int(n_heads), head_dim=int(head_dim), lo=int(lo), hi=int(hi), layout=code)
+    if code < 2:
+        d.rows, d.layer_stride = int(rows), ck.shape[1]
+    else:
+        page_tab = np.ascontiguousarray(page_tab, dtype=np.int32)
+        if page_tab.ndim != 1 or ck.shape[2] != n_heads or ck.shape[4] != head_dim or ck.shape[3] != page_rows:
+            raise VoxError(1, "snapshot_kv: bad shapes")
+        d.page_rows, d.pool_pages, d.page_tab_len, d.page_tab = int(page_rows), ck.shape[1], page_tab.size, page_tab.ctypes.data
+    shape = (2, ck.shape[0], int(n_heads), max(int(hi) - int(lo), 0), int(head_dim))
+    if blob is None:
+        out = np.zeros(shape, np.float32)
+        check(lib().vox_debug_snapshot_kv(ctx.h, C.byref(d), _ptr(ck), _ptr(cv), _ptr(out), 0))
+        return out
+    blob = _f32(blob)
+    if blob.shape != shape:
+        raise VoxError(1, "snapshot_kv: the blob is not [2, layers, n_heads, hi - lo, head_dim]")
+    check(lib().vox_debug_snapshot_kv(ctx.h, C.byref(d), _ptr(ck), _ptr(cv), _ptr(blob), 1))
+    return ck, cv
+
+
+def snapshot_info(blob) -> dict:
+    """vox_snapshot_describe (host arithmetic, no device): validates the header of a session blob (a numpy uint8 array) and returns it as a dict."""
+    blob = np.ascontiguousarray(blob, dtype=np.uint8).reshape(-1)
+    v = _lib.SnapshotInfo(); check(lib().vox_snapshot_describe(_ptr(blob) if blob.size else None, blob.size, C.byref(v)))
+    out = {n: getattr(v, n) for n, _ in _lib.SnapshotInfo._fields_ if n not in ("reserved", "section_offset", "section_bytes")}
+    out["section_offset"] = [int(x) for x in v.section_offset]; out["section_bytes"] = [int(x) for x in v.section_bytes]
+    return out
+
+
+def snapshot_bytes_for(config, positions, sample_rate=16000, n_samples=0, scores=False, alternatives=False) -> int:
+    """vox_snapshot_bytes_for: the blob size of a session of this model geometry (a model's .config) at decoder position `positions` after n_samples pushed samples."""
+    n = C.c_size_t()
+    check(lib().vox_snapshot_bytes_for(C.byref(config), int(positions), int(sample_rate), int(n_samples), int(bool(scores)), int(bool(alternatives)), C.byref(n)))
+    return n.value
+
+
 def attn_gqa_max_seq(ctx):
     """vox_debug_attn_gqa_max_seq: the most rows per KV head the slab GQA decode attention serves (a slab stream group's max_positions on a 4:1 model)."""
     n = C.c_int32(); check(lib().vox_debug_attn_gqa_max_seq(ctx.h, C.byref(n)))
@@ -712,6 +763,25 @@ class LiveStream:
     def reset(self):
         check(lib().vox_stream_reset(self.h))
 
+    def snapshot(self, device_ptr=None, cap=None):
+        """vox_stream_snapshot: the session as one position-independent blob (a numpy uint8 array); the stream stays exactly what it was.  With a device pointer
+        (16-byte aligned, cap bytes) the blob is written there and its size is returned."""
+        n = C.c_size_t(); check(lib().vox_stream_snapshot_size(self.h, C.byref(n)))
+        if device_ptr is not None:
+            w = C.c_size_t(); check(lib().vox_stream_snapshot(self.h, C.c_void_p(device_ptr), n.value if cap is None else int(cap), C.byref(w), 1))
+            return w.value
+        blob = np.zeros(n.value if cap is None else int(cap), dtype=np.uint8); w = C.c_size_t()
+        check(lib().vox_stream_snapshot(self.h, _ptr(blob), blob.size, C.byref(w), 0))
+        return blob[:w.value]
+
+    def restore(self, blob=None, device_ptr=None, nbytes=None):
+        """vox_stream_restore: this stream continues the session of the blob (a numpy uint8 array, or a device pointer + size) in place of its own utterance; a
+        refused blob leaves the stream untouched."""
+        if device_ptr is not None:
+            check(lib().vox_stream_restore(self.h, C.c_void_p(device_ptr), int(nbytes), 1)); return
+        blob = np.ascontiguousarray(blob, dtype=np.uint8).reshape(-1)
+        check(lib().vox_stream_restore(self.h, _ptr(blob), blob.size, 0))
+
     def info(self):
         v = (C.c_int64 * 8)(); check(lib().vox_stream_info(self.h, v))
         return dict(zip(("samples", "positions", "ids", "encoder_position", "ring_rows", "bytes", "engine_steps", "operator_steps"), (int(x) for x in v)))
@@ -885,6 +955,23 @@ class LiveStreamGroup:
         rates = dict(self._rates or {}); rates.pop(int(member), None)
         if int(sample_rate) != 16000:
             rates[int(member)] = int(sample_rate)
+        self._rates = rates
+
+    def snapshot(self, member) -> np.ndarray:
+        """vox_stream_group_snapshot: the member's session as one blob (LiveStream.snapshot); the group stays exactly what it was."""
+        n = C.c_size_t(); check(lib().vox_stream_group_snapshot_size(self.h, int(member), C.byref(n)))
+        blob = np.zeros(n.value, dtype=np.uint8); w = C.c_size_t()
+        check(lib().vox_stream_group_snapshot(self.h, int(member), _ptr(blob), blob.size, C.byref(w), 0))
+        return blob[:w.value]
+
+    def restore(self, member, blob):
+        """vox_stream_group_restore: the member continues the session of the blob -- a member's or a solo stream's -- at the blob's rate and gain; a refused blob
+        leaves the group untouched."""
+        blob = np.ascontiguousarray(blob, dtype=np.uint8).reshape(-1)
+        check(lib().vox_stream_group_restore(self.h, int(member), _ptr(blob), blob.size, 0))
+        rates = dict(self._rates or {}); rates.pop(int(member), None); sr = snapshot_info(blob)["sample_rate"]
+        if sr != 16000:
+            rates[int(member)] = sr
         self._rates = rates
 
     def info(self, member):
