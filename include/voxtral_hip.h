@@ -428,7 +428,8 @@ int32_t vox_debug_reload_knobs(void);
  * all fed members), [10] a solo stream's.  Behind those, attention again: [11] paged single-query decode, [12] paged batched GQA decode (a paged stream group's step:
  * PAGED DECODER CACHE below).  [13] ring single-query decode (vox_debug_attn_decode_ring below): 0 unless a ring launch ran.  [14] paged single-query decode on a RING page table, [15] paged batched
  * GQA decode on one (an endless paged group's step, ENDLESS PAGED GROUPS below; vox_debug_attn_decode_paged_ring): such a launch counts here and not in [11] [12].
- * Entries past [15] are written as 0. */
+ * [16] paged single-query decode on a bf16 pool, [17] paged batched GQA decode on one, [18] [19] their ring-table forms (a bf16 paged group's step, A BF16 K/V POOL
+ * below; vox_debug_attn_decode_paged_bf16): a bf16 launch counts there and never in [11] [12] [14] [15].  Entries past [19] are written as 0. */
 int32_t vox_debug_attn_launches(uint64_t* out, int32_t cap);
 /* One decode attention launch on its own (tests): one query row per sequence against a decoder cache, through the launcher and with the parameters of the batched decode
  * steps -- exactly ONE launch; which kernel ran is the launcher's choice and is read from vox_debug_attn_launches ([3] [4] [5] slab, [11] [12] paged).
@@ -469,6 +470,13 @@ int32_t vox_debug_attn_decode_ring(vox_ctx* ctx, const vox_attn_decode_desc* des
  * The paged kernels with the ring index in their staging loop alone: the output has the bits of vox_debug_attn_decode on a flat table naming the same pages.
  * Exactly ONE launch, counted in vox_debug_attn_launches [14] (per-head) or [15] (GQA), never in [11] [12].  Every argument is checked before the context is bound. */
 int32_t vox_debug_attn_decode_paged_ring(vox_ctx* ctx, const vox_attn_decode_desc* desc, int32_t page_tab_len, const float* q, const float* k, const float* v, void* out);
+/* One paged decode attention launch on a bf16 pool (tests): vox_debug_attn_decode's paged call, the descriptor's layout and meaning unchanged, with k_bf16 / v_bf16 host
+ * uint16_t [pool_pages][n_kv_heads][page_rows][128] -- the upper halves of f32 values (vox_kv_round_bf16).  page_tab_len 0: a flat table, as vox_debug_attn_decode;
+ * page_tab_len 1..1024: a ring table under vox_debug_attn_decode_paged_ring's conditions (window >= 0, page_tab_len <= page_tab_stride and >= window / page_rows + 4,
+ * pos below 2^24).  The kernels load 16-bit rows (16 bytes of K, 8 of V per load), widen them in registers and run the f32 forms' arithmetic in the f32 forms' order:
+ * the output has the bits of vox_debug_attn_decode / _paged_ring on the same pages holding the widened f32 values.  Exactly ONE launch, counted in
+ * vox_debug_attn_launches [16] (per-head) / [17] (GQA), on a ring table [18] / [19], in no other slot.  Every argument is checked before the context is bound. */
+int32_t vox_debug_attn_decode_paged_bf16(vox_ctx* ctx, const vox_attn_decode_desc* desc, int32_t page_tab_len, const float* q, const uint16_t* k_bf16, const uint16_t* v_bf16, void* out);
 /* RoPE rows on their own (tests; host arithmetic, no device): rows first_pos .. first_pos + n - 1 (positions below 2^24) of the tables the kernels read, cos_out /
  * sin_out [n][head_dim / 2], and in inv_out [head_dim / 2] the f32 factors 1 / theta^(2 j / head_dim) they were made from.  The ONE function that produces RoPE rows:
  * the load-time tables and the streaming encoder's table are filled by it.  head_dim 128 is the decoder's geometry, whose load-time table has 16 384 rows; any other
@@ -906,6 +914,27 @@ int32_t vox_debug_stream_group_pages(const vox_stream_group* g, int32_t member, 
  *   Not served: endless slab groups, freeing pages inside a call, more than 16 members. */
 int32_t vox_stream_group_create_endless(vox_model* m, const float* t_embed, int32_t n_members, const float* gains /* null: 1.0 */, const uint32_t* rates /* null: 16000 each */,
                                         int32_t enc_capacity_rows, int32_t page_rows /* 0: 256 */, int32_t pool_pages /* 0: the default */, vox_stream_group** out);
+/* A BF16 K/V POOL.  vox_stream_group_create_kv makes a paged (endless == 0) or endless paged (endless == 1, max_positions must be 0) group whose decoder K / V pool
+ * holds kv_dtype elements.  VOX_KV_F32: exactly vox_stream_group_create_paged / _create_endless -- the same checks, the same refusals, the same object.  VOX_KV_BF16: the
+ * K and V pools are [layer][pool_pages][kv_head][page_rows][head_dim] of uint16_t, half the memory per page (vox_stream_group_info [5] follows), half the bytes the decode
+ * attention reads at every tick.  Any other kv_dtype is refused (VOX_ERR_INVALID) before anything is allocated.  Everything of PAGED DECODER CACHE and ENDLESS PAGED
+ * GROUPS holds: the allocator, the tables, pool_pages' default, every refusal, the peek's borrowed pages -- the same calls give a bf16 group and an f32 paged group the
+ * same vox_stream_group_pool and the same pages per member.
+ *   The rounding: f32 -> bf16, round to nearest even on the upper 16 bits, (u + 0x7fff + ((u >> 16) & 1)) >> 16; a NaN stays a quiet NaN, a value that rounds past
+ *   the largest finite becomes inf, the sign of zero and denormals are kept.  bf16 has f32's range: no finite value of a checkpoint overflows.  Widening is u << 16.
+ *   ONE function (csrc/vox_kv_bf16.h) serves the append, the seed, the restore and vox_kv_round_bf16, which is host arithmetic: no context, no device.
+ *   Invariants: (1) a group not made with VOX_KV_BF16 runs the launches and allocations it ran before.  (2) The bf16 decode attention is the f32 attention on the
+ *   widened values, bit for bit (vox_debug_attn_decode_paged_bf16).  (3) Rows are rounded where they are appended (the q|k|v epilogue, after RoPE in f32; the seed of
+ *   the prefix rows) and nowhere else: while the ids agree, a bf16 member's layer-0 rows are the rounded layer-0 rows of the f32 member, exactly.  (4) A session blob
+ *   holds f32 rows whatever its container: a bf16 member packs its rows widened (exact); a restore rounds (exact for a blob of a bf16 member) -- bf16 to bf16 of the
+ *   same kind continues bit for bit.  (5) A bf16 group's ids and logits are NOT the f32 group's; how far apart they are is measured (profiles/stream_group_kv_bf16.txt),
+ *   not promised.  Not served: bf16 for slab groups and solo streams, the encoder ring, the offline caches, f16 / fp8, mixed dtypes in one group. */
+#define VOX_KV_F32 0
+#define VOX_KV_BF16 1
+int32_t vox_stream_group_create_kv(vox_model* m, const float* t_embed, int32_t n_members, const float* gains /* null: 1.0 */, const uint32_t* rates /* null: 16000 each */,
+                                   int32_t enc_capacity_rows, int32_t max_positions /* endless: 0 */, int32_t page_rows /* 0: 256 */, int32_t pool_pages /* 0: the default */,
+                                   int32_t endless, int32_t kv_dtype, vox_stream_group** out);
+int32_t vox_kv_round_bf16(const float* in, int64_t n, uint16_t* out);
 /* Snapshot and resume of a member (SNAPSHOT AND RESUME above: the format, the refusals, the contracts): vox_stream_snapshot_size / _snapshot / _restore for member
  * `member` of a slab, paged or endless paged group.  Only that member is read or changed. */
 int32_t vox_stream_group_snapshot_size(const vox_stream_group* g, int32_t member, size_t* nbytes);

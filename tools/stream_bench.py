@@ -40,6 +40,9 @@
  * --group ... --page-rows R --endless: the same run also times an ENDLESS paged group (vox_stream_group_create_endless) of the paged group's pages and pool, each pass right
    behind the bounded paged group's over the same positions: round medians, their difference, launches per round, and the host wall time per round of both (the endless
    group fills its members' RoPE rows on the host in front of every pass).
+ * --group ... --page-rows R --kv bf16: the same run also times a paged group with a bf16 K/V pool (vox_stream_group_create_kv, VOX_KV_BF16) of the paged group's pages,
+   pool and positions, each pass right behind the f32 paged group's: round medians, their difference per pass, launches per round, the growth of both rounds per pass
+   (per `ticks` positions), and the bytes a member holds in both.
  * --memory-past-window --page-rows R: nothing is timed; 16 members of an endless paged group and of a bounded paged group with max_positions 16 384 are run past the
    decoder window by the same calls, and what they hold is read from pool() and info().
  * --endless (without --group): the tick of an ENDLESS session (vox_stream_create_endless) past the wrap of its decoder ring, next to a bounded session (max_positions 16 384) at the
@@ -91,8 +94,8 @@ class Timer:
 
 
 def launch_counts(pkg):
-    a = (C.c_uint64 * 16)(); g = (C.c_uint64 * 20)()      # attention forms 0..8, the paged decode forms 11, 12, the ring decode form 13 and the ring-table paged forms 14, 15 (9 and 10 are the resampling ingests: not counted here)
-    L = pkg.lib(); assert L.vox_debug_attn_launches(a, 16) == 0 and L.vox_debug_gemm_launches(g, 20) == 0
+    a = (C.c_uint64 * 20)(); g = (C.c_uint64 * 20)()      # attention forms 0..8, the paged decode forms 11, 12, the ring decode form 13, the ring-table paged forms 14, 15 and the bf16 paged forms 16..19 (9 and 10 are the resampling ingests: not counted here)
+    L = pkg.lib(); assert L.vox_debug_attn_launches(a, 20) == 0 and L.vox_debug_gemm_launches(g, 20) == 0
     return sum(a[:9]) + sum(a[11:]), sum(g)
 
 
@@ -143,6 +146,9 @@ def bench_groups(pkg, ctx, m, t, tm, a, widths, lines):
         if a.page_rows:      # the paged twin of the slab group: the same positions per member, the default pool
             gp = m.create_stream_group(t, N, gains=[gain] * N, max_positions=2048, page_rows=a.page_rows)
             gp.advance({k: x[:pos] for k in range(N)}); paged = []; kp = 0; wall_p = []
+            if a.kv == "bf16":      # the bf16 twin of the paged group (vox_stream_group_create_kv): the same pages, the same pool, the same positions
+                gb = m.create_stream_group(t, N, gains=[gain] * N, max_positions=2048, page_rows=a.page_rows, pool_pages=gp.pool()["pool_pages"], kv_dtype="bf16")
+                gb.advance({k: x[:pos] for k in range(N)}); bf = []; kb = 0
             if a.endless:      # the endless twin of the paged group (vox_stream_group_create_endless): the same pages, the same pool, the same positions
                 ge = m.create_stream_group(t, N, gains=[gain] * N, page_rows=a.page_rows, pool_pages=gp.pool()["pool_pages"], endless=True)
                 ge.advance({k: x[:pos] for k in range(N)}); endl = []; ke = 0; wall_e = []
@@ -161,6 +167,8 @@ def bench_groups(pkg, ctx, m, t, tm, a, widths, lines):
             if a.page_rows:
                 k2p = launch_counts(pkg); w0 = time.perf_counter(); paged.append(tm.ms(lambda: gp.advance(feeds)) / a.ticks); wall_p.append(1e3 * (time.perf_counter() - w0) / a.ticks)
                 kp += sum(launch_counts(pkg)) - sum(k2p)
+                if a.kv == "bf16":      # right behind the f32 paged pass, over the same positions
+                    k2b = launch_counts(pkg); bf.append(tm.ms(lambda: gb.advance(feeds)) / a.ticks); kb += sum(launch_counts(pkg)) - sum(k2b)
                 if a.endless:      # right behind the bounded paged pass, over the same positions
                     k2e = launch_counts(pkg); w0 = time.perf_counter(); endl.append(tm.ms(lambda: ge.advance(feeds)) / a.ticks); wall_e.append(1e3 * (time.perf_counter() - w0) / a.ticks)
                     ke += sum(launch_counts(pkg)) - sum(k2e)
@@ -196,10 +204,18 @@ def bench_groups(pkg, ctx, m, t, tm, a, widths, lines):
                   f"  round / ({N} x solo tick) = {rnd / (N * tick):.3f}   per member and tick {rnd / N:.3f} ms   launches per round {lg:.0f} (solo tick {ls:.0f})"]
         if a.page_rows:
             assert gp.info(N - 1)["positions"] == 38 + warm + a.ticks * a.passes
-            pl = gp.pool(); gp.close(); rp = statistics.median(paged)
+            pl = gp.pool(); ip = gp.info(0); gp.close(); rp = statistics.median(paged)
             lines += [f"  paged group of {N:2d} (pages of {pl['page_rows']} rows, pool of {pl['pool_pages']}, peak {pl['peak']}): round median {rp:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in paged) +
                       f"   difference to the slab round {rp - rnd:+.3f} ms ({100 * (rp - rnd) / rnd:+.2f} %), per pass " + " ".join(f"{v - w:+.3f}" for v, w in zip(paged, grp)),
                       f"  launches per round: paged {kp / ticks + fixed_enc + 2:.0f}, slab {lg:.0f}"]
+            if a.kv == "bf16":
+                assert gb.info(N - 1)["positions"] == 38 + warm + a.ticks * a.passes and gb.pool()["peak"] == pl["peak"]
+                ib = gb.info(0); gb.close(); rb = statistics.median(bf)
+                grow = lambda v: (v[-1] - v[0]) / (len(v) - 1) if len(v) > 1 else float("nan")
+                lines += [f"  bf16 paged group of {N:2d}, the same pages, pool and positions, each pass right behind the f32 paged one's: round median {rb:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in bf) +
+                          f"   difference to the f32 paged round {rb - rp:+.3f} ms ({100 * (rb - rp) / rp:+.2f} %), per pass " + " ".join(f"{v - w:+.3f}" for v, w in zip(bf, paged)),
+                          f"  launches per round: bf16 {kb / ticks + fixed_enc + 2:.0f}, f32 paged {kp / ticks + fixed_enc + 2:.0f}; growth of the round per {a.ticks} positions (last pass - first pass, per pass): "
+                          f"bf16 {grow(bf):+.3f} ms, f32 paged {grow(paged):+.3f} ms; a member's device bytes: bf16 {ib['bytes'] / 1e6:.1f} MB, f32 paged {ip['bytes'] / 1e6:.1f} MB"]
             if a.endless:
                 assert ge.info(N - 1)["positions"] == 38 + warm + a.ticks * a.passes
                 ie = ge.info(0); ge.close(); re_ = statistics.median(endl); we, wp = statistics.median(wall_e), statistics.median(wall_p)
@@ -372,6 +388,7 @@ def main():
     ap.add_argument("--scores", action="store_true", help="also time a stream (with --group: and a group) with scores on, pass by pass next to the unscored one")
     ap.add_argument("--alternatives", type=int, default=0, metavar="K", help="also time a stream (with --group: and a group) with alternatives on at k = K (1..8), as --scores does")
     ap.add_argument("--page-rows", type=int, default=0, metavar="R", help="with --group: also time a paged group (pages of R rows, the default pool) pass by pass next to the slab group")
+    ap.add_argument("--kv", choices=("f32", "bf16"), default="f32", help="with --group and --page-rows: bf16 also times a paged group with a bf16 K/V pool pass by pass behind the f32 paged group")
     ap.add_argument("--peek", action="store_true", help="time vox_stream_peek next to the same number of ordinary ticks of the same session (nothing else is measured)")
     ap.add_argument("--endless", action="store_true", help="time the tick of an endless session past the wrap of its decoder ring next to a bounded session at the same positions (nothing else is measured)")
     ap.add_argument("--memory-past-window", action="store_true", help="with --page-rows R: what 16 members of an endless paged group and of a bounded paged group (max_positions 16384) hold past "
@@ -390,6 +407,8 @@ def main():
         ap.error("--alternatives takes 1..8")
     if a.peek and (a.group or a.scores or a.alternatives):
         ap.error("--peek is a mode of its own")
+    if a.kv != "f32" and not (a.group and a.page_rows):
+        ap.error("--kv bf16 times a bf16 PAGED group: give --group and --page-rows")
     if a.page_rows and not a.group and not a.memory_past_window:
         ap.error("--page-rows applies with --group")
     if (a.rate or a.s16) and not a.group or (a.s16 and not a.rate):

@@ -177,6 +177,7 @@ SIGNATURES = {
     "vox_debug_attn_decode": (i32, [vp, vp, vp, vp, vp, vp]),
     "vox_debug_attn_decode_ring": (i32, [vp, vp, vp, vp, vp, vp]),
     "vox_debug_attn_decode_paged_ring": (i32, [vp, vp, i32, vp, vp, vp, vp]),      # a paged launch on a ring page table of page_tab_len entries
+    "vox_debug_attn_decode_paged_bf16": (i32, [vp, vp, i32, vp, vp, vp, vp]),      # the paged launch (flat table: page_tab_len 0) on uint16_t pools
     "vox_debug_rope_rows": (i32, [i32, C.c_float, C.c_int64, i32, vp, vp, vp]),
     "vox_debug_stream_attn": (i32, [vp, vp, vp, vp, vp, vp]),      # (ctx, vox_stream_attn_desc, qkv, kring, vring, out): ONE launch of the streams' ring attention
     "vox_debug_stream_ring_init": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp]),      # (ctx, layers, rows, n_heads, head_dim, cap, kv, kring, vring)
@@ -235,6 +236,9 @@ SIGNATURES = {
     "vox_stream_group_create_paged": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, i32, P(vp)]),
     # an endless paged group: (model, t_embed, n_members, gains, rates or null, enc_capacity_rows, page_rows or 0, pool_pages or 0, out) -- no max_positions
     "vox_stream_group_create_endless": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, P(vp)]),
+    # a paged / endless paged group with a K/V pool dtype: (model, t_embed, n_members, gains, rates, enc_capacity_rows, max_positions, page_rows, pool_pages, endless, kv_dtype, out)
+    "vox_stream_group_create_kv": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, P(vp)]),
+    "vox_kv_round_bf16": (i32, [vp, i64, vp]),      # (f32 in, n, uint16 out): the pool's rounding as host arithmetic
     "vox_stream_group_pool": (i32, [vp, P(i64 * 4), vp]),
     "vox_stream_group_pages_for": (i32, [i64, i32, i32, P(i32), P(i32)]),
     "vox_debug_stream_group_pages": (i32, [vp, i32, vp, i32, P(i32)]),

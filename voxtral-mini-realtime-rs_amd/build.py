@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get("VOX_LIB") or os.path.join(PKG_DIR, "libvoxtral_hip.so
 HOST_SOURCES_PLAIN = ["vox_audio_host.cpp", "vox_gguf.cpp", "vox_batch_plan.cpp", "vox_feed_plan.cpp", "vox_snapshot_plan.cpp"]
 HOST_SOURCES = ["vox_api.cpp", "vox_model.cpp", "vox_ctx.cpp", "vox_tensor.cpp", "vox_cache.cpp", *HOST_SOURCES_PLAIN]
 SOURCES = ["vox_kernels.hip", "vox_engine.hip", "vox_engine_b16.hip", *HOST_SOURCES]
-HEADERS = ["vox_kernels.h", "vox_engine_common.h", "vox_page_pool.h", "vox_snapshot.h", "vox_host_base.h", "vox_dev_base.h", os.path.join("..", "..", "include", "voxtral_hip.h")]
+HEADERS = ["vox_kernels.h", "vox_engine_common.h", "vox_page_pool.h", "vox_kv_bf16.h", "vox_snapshot.h", "vox_host_base.h", "vox_dev_base.h", os.path.join("..", "..", "include", "voxtral_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-result"]
 

@@ -168,8 +168,9 @@ def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_
 
 
 def transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, chunk_ms, n_members, words_out=None, peek=False, alts_k=0, page_rows=None, pool_pages=None, endless=False,
-                          suspend_every=0):
-    """--live-group N: the files N at a time through one stream group (vox_stream_group) in pieces of `chunk_ms` milliseconds: every call feeds each busy member its
+                          suspend_every=0, kv_dtype=None):
+    """(kv_dtype, --live-kv f32 | bf16: the paged group's K/V pool dtype, vox_stream_group_create_kv; the lines have the same form.)
+    --live-group N: the files N at a time through one stream group (vox_stream_group) in pieces of `chunk_ms` milliseconds: every call feeds each busy member its
     next piece, a file that ends (its member fed with finish) frees the member for the next file in input order.  Gains and lines as transcribe_live's (16 kHz: other
     rates are resampled first).  -> {file index: text}; a file that cannot be read is left out (the one-by-one path reports it).  words_out (--live-words): every
     member runs with scores on (and, with alts_k from --live-alternatives, with that many alternatives), a file's words go there when the file ends.  peek (--live-peek): after every call one vox_stream_group_peek for the members still
@@ -178,7 +179,7 @@ def transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, chunk_ms, 
     member is refused at 43 minutes); the lines are the same.  suspend_every (--live-suspend-every N): after every N calls each busy member is snapshotted to host
     memory, reset, and restored from its blob (vox_stream_group_snapshot / _restore); the lines are the same."""
     step = max(1, int(round(16000 * chunk_ms / 1000.0)))
-    group = model.create_stream_group(t_embed, n_members, page_rows=page_rows, pool_pages=pool_pages, endless=endless)
+    group = model.create_stream_group(t_embed, n_members, page_rows=page_rows, pool_pages=pool_pages, endless=endless, kv_dtype=kv_dtype)
     text = lambda ids: tokenizer.decode([t for t in ids if t >= 1000]).strip()
     texts = {}; busy = {}; nxt = 0; calls = 0      # busy: member -> [file index, samples, offset, ids]
     try:
@@ -375,6 +376,9 @@ def main(argv=None):
     ap.add_argument("--live-page-rows", type=int, default=None, metavar="R", help="with --live-group: a paged group (vox_stream_group_create_paged) whose decoder cache is one pool "
                     "of K / V pages of R rows (a power of two in 16..1024; 0: 256) that the files grow into, instead of a 2048-position slab slice per member; same lines")
     ap.add_argument("--live-pool-pages", type=int, default=None, metavar="P", help="with --live-group: a paged group with a pool of P pages (0: the default slab's memory)")
+    ap.add_argument("--live-kv", choices=("f32", "bf16"), default=None, help="with --live-group: what the group's decoder K/V pool holds (vox_stream_group_create_kv; makes the "
+                    "group a paged one).  bf16: 16-bit pages, half the memory per page and half the bytes the decode attention reads; the text may differ from an f32 group's "
+                    "where the model's choice between two tokens is close")
     ap.add_argument("--live-endless", action="store_true", help="with --live: an endless session (vox_stream_create_endless) -- no limit at "
                     "16 384 decoder positions (about 43 minutes); the decoder cache is a ring of a little more than one window and stops growing there.  With --live-group: "
                     "an endless paged group (vox_stream_group_create_endless; --live-page-rows / --live-pool-pages apply), no member refused at 43 minutes; same lines")
@@ -421,6 +425,8 @@ def main(argv=None):
         ap.error("--live-group takes 2..16 members")
     if (a.live_page_rows is not None or a.live_pool_pages is not None) and not a.live_group:
         ap.error("--live-page-rows / --live-pool-pages apply with --live-group")
+    if a.live_kv is not None and not a.live_group:
+        ap.error("--live-kv applies with --live-group")
     if a.live_page_rows not in (None, 0) and not (16 <= a.live_page_rows <= 1024 and a.live_page_rows & (a.live_page_rows - 1) == 0):
         ap.error("--live-page-rows takes a power of two in 16..1024 (0: 256)")
     if a.live_pool_pages is not None and a.live_pool_pages < 0:
@@ -521,7 +527,7 @@ def main(argv=None):
                         write_word_lines(rec_out, runner.words.get((i, k), []))
     if a.live_group:
         try:
-            texts = transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_group, words_out, a.live_peek, a.live_alternatives, a.live_page_rows, a.live_pool_pages, a.live_endless, a.live_suspend_every)
+            texts = transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_group, words_out, a.live_peek, a.live_alternatives, a.live_page_rows, a.live_pool_pages, a.live_endless, a.live_suspend_every, a.live_kv)
         except Exception as e:      # the files fall back to one live session each
             log(f"Error in the stream group: {e}"); texts = {}
             if words_out is not None:      # the files' words come again with their lines

@@ -9,6 +9,7 @@
 #include "vox_page_pool.h"
 #include "vox_dev_base.h"
 #include "vox_snapshot.h"
+#include "vox_kv_bf16.h"
 
 #include <algorithm>
 #include <array>
@@ -1216,7 +1217,8 @@ extern "C" int32_t vox_debug_attn_gqa_max_seq(vox_ctx* c, int32_t* out) {
 }
 // ring: vox_debug_attn_decode_ring -- the slab call's buffers with the cache slices used as rings of max_seq rows (launch_attn_decode_ring)
 // tab_len > 0: vox_debug_attn_decode_paged_ring -- the paged call with every table row used as a ring of tab_len entries (AttnParams::page_tab_len), positions to 2^24 - 1
-static int32_t attn_decode_debug(vox_ctx* c, const vox_attn_decode_desc* d, const float* q, const float* k, const float* v, void* out, bool ring, int tab_len = 0) {
+// bf16: vox_debug_attn_decode_paged_bf16 -- the paged call (flat or ring table) on uint16_t pools of the same layout (AttnParams::kv_bf16)
+static int32_t attn_decode_debug(vox_ctx* c, const vox_attn_decode_desc* d, const float* q, const void* k, const void* v, void* out, bool ring, int tab_len = 0, bool bf16 = false) {
     ARGCHK(c && d && q && k && v && out, "null argument"); ARGCHK(d->pos, "null argument (pos)");
     ARGCHK(d->head_dim == 128, "head_dim %d: the decoder's decode attention serves head_dim 128 alone", d->head_dim);
     ARGCHK(d->n_seq >= 1 && d->n_seq <= 4096, "n_seq %d out of range (1..4096)", d->n_seq);
@@ -1273,12 +1275,13 @@ static int32_t attn_decode_debug(vox_ctx* c, const vox_attn_decode_desc* d, cons
     const int n_grp = (n + 15) / 16; const size_t xf_b = xf_bytes(QD);
     DevBuf dq, dk, dv, dout, dxf, dint;
     const size_t tab_n = paged ? (size_t)d->n_slices * d->page_tab_stride : 0;
-    HIPCHK(dq.alloc((size_t)n * W * 4)); HIPCHK(dk.alloc(kv_f * 4)); HIPCHK(dv.alloc(kv_f * 4)); HIPCHK(dout.alloc((size_t)n * QD * 4)); HIPCHK(dxf.alloc(xf_b * n_grp));
+    const size_t kv_b = kv_f * (bf16 ? 2 : 4);
+    HIPCHK(dq.alloc((size_t)n * W * 4)); HIPCHK(dk.alloc(kv_b)); HIPCHK(dv.alloc(kv_b)); HIPCHK(dout.alloc((size_t)n * QD * 4)); HIPCHK(dxf.alloc(xf_b * n_grp));
     HIPCHK(dint.alloc((2 * (size_t)n + tab_n) * 4));
     int* d_pos = dint.as<int>(); int* d_row = d_pos + n; int* d_tab = d_row + n;
     HIPCHK(hipMemsetAsync(dq.p, 0, (size_t)n * W * 4, s));
     HIPCHK(hipMemcpy2DAsync(dq.p, (size_t)W * 4, q, (size_t)QD * 4, (size_t)QD * 4, n, hipMemcpyHostToDevice, s));      // q rows at the q|k|v row stride, as the steps hold them
-    HIPCHK(hipMemcpyAsync(dk.p, k, kv_f * 4, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(dv.p, v, kv_f * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dk.p, k, kv_b, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(dv.p, v, kv_b, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(d_pos, d->pos, (size_t)n * 4, hipMemcpyHostToDevice, s));
     if (d->kv_row) HIPCHK(hipMemcpyAsync(d_row, d->kv_row, (size_t)n * 4, hipMemcpyHostToDevice, s));
     if (paged) HIPCHK(hipMemcpyAsync(d_tab, d->page_tab, tab_n * 4, hipMemcpyHostToDevice, s));
@@ -1290,7 +1293,7 @@ static int32_t attn_decode_debug(vox_ctx* c, const vox_attn_decode_desc* d, cons
     ap.out = dout.as<float>(); if (d->out_xf) { ap.out_xf = dxf.as<uint16_t>(); ap.out_xf_gstride = (long)(xf_b / 2); }
     if (paged) {
         ap.kv_head_stride = (hd << shift); ap.page_tab = d_tab; ap.page_tab_stride = d->page_tab_stride; ap.page_shift = shift; ap.page_floats = (long)slice_f; ap.score_rows = d->score_rows;
-        ap.page_tab_len = tab_len;
+        ap.page_tab_len = tab_len; ap.kv_bf16 = bf16 ? 1 : 0;
         HIPCHK(launch_attn_decode_paged(ap, hd, s, n));
     } else if (ring) HIPCHK(launch_attn_decode_ring(ap, hd, d->max_seq, s, n));
     else HIPCHK(launch_attn_decode(ap, hd, d->max_seq, s, n));
@@ -1309,6 +1312,17 @@ extern "C" int32_t vox_debug_attn_decode_paged_ring(vox_ctx* c, const vox_attn_d
     ARGCHK(d, "null argument"); ARGCHK(d->page_rows != 0, "a ring table belongs to a paged call (page_rows 0)");
     ARGCHK(page_tab_len >= 1 && page_tab_len <= 1024, "page_tab_len %d out of range (1..1024)", page_tab_len);
     return attn_decode_debug(c, d, q, k, v, out, false, page_tab_len);
+}
+extern "C" int32_t vox_debug_attn_decode_paged_bf16(vox_ctx* c, const vox_attn_decode_desc* d, int32_t page_tab_len, const float* q, const uint16_t* k, const uint16_t* v, void* out) {
+    ARGCHK(d, "null argument"); ARGCHK(d->page_rows != 0, "a bf16 pool belongs to a paged call (page_rows 0)");
+    ARGCHK(page_tab_len >= 0 && page_tab_len <= 1024, "page_tab_len %d out of range (0: a flat table; 1..1024: a ring table)", page_tab_len);
+    ARGCHK(d->page_rows >= 16 && d->page_rows <= 1024 && !(d->page_rows & (d->page_rows - 1)), "page_rows %d is not a power of two in 16..1024", d->page_rows);
+    if (page_tab_len) {      // (attn_decode_debug's ring-table conditions, stated here as well: they hold whatever else the call passes)
+        ARGCHK(d->window >= 0, "a ring table needs a sliding window (window %d)", d->window);
+        ARGCHK(page_tab_len >= d->window / d->page_rows + 4, "page_tab_len %d: a window of %d in pages of %d rows needs a ring table of at least %d entries", page_tab_len, d->window, d->page_rows,
+               d->window / d->page_rows + 4);
+    }
+    return attn_decode_debug(c, d, q, k, v, out, false, page_tab_len, true);
 }
 // ---- one launch of the live sessions' encoder ring attention on host buffers (tests): the StreamAttnParams of stream_encode_round -- StreamMember descriptors on the
 // device with state[STRM_ENC_POS], kring and vring alone filled in, the order array, the caller's q|k|v rows, the RoPE rows as a flat table (the model's streaming
@@ -1419,6 +1433,8 @@ struct XfBufs {
     // an endless paged group: the table rows are rings of page_tab_len entries, and the q|k|v epilogue reads its RoPE rows from the group's member-strided decoder
     // RoPE ring (rope_ring [members][rope_mask + 1][cos | sin]; the row's member: kv_row).  0 / null everywhere else
     int page_tab_len; const float* rope_ring; int rope_mask;
+    // a bf16 pool (a bf16 paged group): k / v point at uint16_t pools, layer_stride and page_floats count 16-bit elements.  0 everywhere else
+    int kv_bf16;
 };
 // the XF planes and ssq blocks of a step over n_grp groups (0: none, the group strides alone): from the pool, zeroed on s, bound to b
 struct XfPlanes {
@@ -1445,6 +1461,7 @@ static int32_t xf_chain(const vox_model* m, const XfBufs& b, int g0i, int ng, in
     const int D = c.dec_dim, H = c.dec_heads, KV = c.dec_kv_heads, hd = c.dec_head_dim, QD = H * hd, W = QD + 2 * KV * hd, F = c.dec_ffn, V = c.vocab;
     const int parts_D = q4_skinny_resid_xf_parts(D), max_seq = b.max_seq, M = mtw ? 16 * mtw : ng;
     ARGCHK(!(b.page_tab && mtw), "internal: a paged cache runs the one-group chain (the wide step has no paged form)");
+    ARGCHK(!b.kv_bf16 || b.page_tab, "internal: a bf16 K/V pool is a paged cache's");
     const int r0 = g0i * 16;      // the chain's first group: its planes, sums, rows, positions and cache slices (a wide chain's further groups follow at the group strides)
     uint16_t* xf1 = b.xf1 + (size_t)g0i * b.xf1_gs; uint16_t* xf2 = b.xf2 + (size_t)g0i * b.xf2_gs; uint16_t* xf3 = b.xf3 + (size_t)g0i * b.xf3_gs; float* ssq = b.ssq + (size_t)g0i * b.ssq_gs;
     float* hg = b.h + (size_t)r0 * D; float* qg = b.qkv + (size_t)r0 * W; const int* pg = b.pos + r0; const int* rg = b.kv_row ? b.kv_row + r0 : nullptr;
@@ -1461,9 +1478,12 @@ static int32_t xf_chain(const vox_model* m, const XfBufs& b, int g0i, int ng, in
     for (int l = 0; l < c.dec_layers; l++) {
         const DecLayer& L = m->dec[l];
         float* kl = b.k + (size_t)l * b.layer_stride + row0; float* vl = b.v + (size_t)l * b.layer_stride + row0;
+        if (b.kv_bf16) {      // (a paged pool: row0 is 0) the layer's pages, in 16-bit elements
+            kl = reinterpret_cast<float*>(reinterpret_cast<uint16_t*>(b.k) + (size_t)l * b.layer_stride); vl = reinterpret_cast<float*>(reinterpret_cast<uint16_t*>(b.v) + (size_t)l * b.layer_stride);
+        }
         { GemmParams g{}; g.out = qg; g.out_stride = W; g.ssq_part = ssq; g.n_part = l == 0 ? 1 : parts_D; g.pos = pg; g.rope_cos = m->dec_cos; g.rope_sin = m->dec_sin;
           g.hd = hd; g.n_q = QD; g.n_kv = KV; g.kc = kl; g.vc = vl; g.kv_seq_stride = (long)b.seq_stride; g.kv_head_stride = max_seq * hd; g.kv_row = rg;
-          if (b.page_tab) { g.kv_seq_stride = b.page_floats; g.kv_head_stride = (hd << b.page_shift); g.kv_row = b.kv_page + r0; g.kv_pos = b.kv_in + r0; }
+          if (b.page_tab) { g.kv_seq_stride = b.page_floats; g.kv_head_stride = (hd << b.page_shift); g.kv_row = b.kv_page + r0; g.kv_pos = b.kv_in + r0; g.kv_bf16 = b.kv_bf16; }
           if (b.page_tab && b.rope_ring) { g.rope_cos = b.rope_ring; g.rope_sin = b.rope_ring + hd / 2; g.rope_member = rg; g.rope_mask = b.rope_mask; }
           HIPCHK(gemm(g, L.wqkv.w, xf1, D, EPI_ROPE_KV)); }
         AttnParams ap{}; ap.q = qg; ap.k = kl; ap.v = vl; ap.kv_row_stride = hd; ap.kv_head_stride = max_seq * hd; ap.n_heads = H; ap.n_kv_heads = KV;
@@ -1472,7 +1492,7 @@ static int32_t xf_chain(const vox_model* m, const XfBufs& b, int g0i, int ng, in
         ap.out = b.att; if (mtw) { ap.out = b.att + (size_t)g0i * 16 * QD; ap.out_xf_gstride = b.xf2_gs; }
         if (b.page_tab) {
             ap.kv_head_stride = (hd << b.page_shift); ap.page_tab = b.page_tab; ap.page_tab_stride = b.page_tab_stride; ap.page_shift = b.page_shift; ap.page_floats = b.page_floats;
-            ap.score_rows = b.score_rows; ap.page_tab_len = b.page_tab_len;
+            ap.score_rows = b.score_rows; ap.page_tab_len = b.page_tab_len; ap.kv_bf16 = b.kv_bf16;
             HIPCHK(launch_attn_decode_paged(ap, hd, sg, M));
         } else
         HIPCHK(launch_attn_decode(ap, hd, max_seq, sg, M));
@@ -4106,6 +4126,9 @@ struct vox_stream_group {
     // layer's pages), pool the allocator with every member's table mirror, d_tab the device table [n][pool.max_pages], d_kv_page / d_kv_in the step's physical pages and
     // rows inside them [16] (behind d_kv_row, the same allocation).  A slab group: paged == false, nothing of this is set
     bool paged = false; PagePool pool; int* d_tab = nullptr; int *d_kv_page = nullptr, *d_kv_in = nullptr; size_t page_floats = 0;
+    // a bf16 paged group (vox_stream_group_create_kv with VOX_KV_BF16; DESIGN.md section 8, "A bf16 K/V pool"): dec_k / dec_v point at uint16_t pools of the same layout
+    // -- page_floats, seq_stride and layer_stride then count 16-bit elements.  The allocator, the tables and every refusal are the f32 paged group's
+    bool kv_bf16 = false;
     // An ENDLESS paged group (vox_stream_group_create_endless; DESIGN.md section 8, "Endless paged groups"): g.max_pos is 2^24; the pool's tables are rings of pool_pages
     // entries (d_tab [n][pool.tab_len]); every member has its own token row and record lists (GroupMember::tokens, lists_cap), grown by doubling; and the group owns
     // two member-strided device RoPE rings -- decoder [n][GROUP_ROPE_ROWS][cos hd/2 | sin hd/2], encoder [n][R GROUP_ROPE_ROWS][..] -- with their pinned host images,
@@ -4174,7 +4197,7 @@ static int32_t group_member_seed(vox_stream_group* g, int i) {
                                if (g->endless) { VOXCHK(group_table_upload(g, i, q0, q1)); VOXCHK(group_table_upload(g, i, t0, t1)); }      // (the returned pages may lie anywhere in the ring; the seed's are entries 0 ..)
                                else VOXCHK(group_table_upload(g, i, 0, std::max(q1, t1)));
                                HIPCHK(launch_stream_pages_seed(g->m->pfx.dec_k, g->m->pfx.dec_v, c.dec_layers, c.dec_kv_heads, g->g.PC, c.dec_head_dim, g->d_tab + (size_t)i * g->pool.tab_len,
-                                                               g->pool.shift, g->layer_stride, g->dec_k, g->dec_v, g->ctx->stream));
+                                                               g->pool.shift, g->layer_stride, g->dec_k, g->dec_v, g->ctx->stream, g->kv_bf16));
                                return VOX_OK; }));
         me.feed.restart(g->g.PC); me.steps = 0; me.sc.host.clear(); me.al.restart();
         return VOX_OK;
@@ -4203,7 +4226,7 @@ static void group_release(vox_stream_group* g) {
 // page_rows < 0: a slab group (pool_pages unread); else a paged one (0: the default page / the default pool)
 // endless (a paged group alone): max_positions is unread, the limit is the session limit 2^24
 static int32_t group_create(vox_model* m, const float* t_embed, int32_t n_members, const float* gains, const uint32_t* rates, int32_t enc_capacity_rows,
-                            int32_t max_positions, int32_t page_rows, int32_t pool_pages, vox_stream_group** out, bool endless = false) {
+                            int32_t max_positions, int32_t page_rows, int32_t pool_pages, vox_stream_group** out, bool endless = false, bool kv_bf16 = false) {
     ARGCHK(n_members >= 1 && n_members <= GROUP_MAX, "n_members %d out of range (1..%d)", n_members, GROUP_MAX); ARGCHK(m && t_embed && out, "null argument");
     for (int i = 0; gains && i < n_members; i++) ARGCHK(std::isfinite(gains[i]), "gain of member %d is not finite", i);
     for (int i = 0; rates && i < n_members; i++) {      // every rate is checked before anything is allocated
@@ -4213,7 +4236,7 @@ static int32_t group_create(vox_model* m, const float* t_embed, int32_t n_member
     VOXCHK(ctx_bind(m->ctx));
     const vox_model_cfg& c = m->cfg; vox_ctx* cx = m->ctx; hipStream_t s = cx->stream;
     const bool paged = page_rows >= 0;
-    ARGCHK(!endless || paged, "internal: an endless group is a paged one");
+    ARGCHK(!endless || paged, "internal: an endless group is a paged one"); ARGCHK(!kv_bf16 || paged, "internal: a bf16 K/V pool belongs to a paged group");
     StreamGeom sg; VOXCHK(stream_geometry(m, enc_capacity_rows, endless ? 0 : max_positions, paged ? INT32_MAX : GROUP_DEFAULT_POSITIONS, &sg));      // (paged, 0: the session limit)
     if (endless) {
         ARGCHK(c.dec_window >= 0, "an endless group needs a sliding decoder window");
@@ -4237,7 +4260,7 @@ static int32_t group_create(vox_model* m, const float* t_embed, int32_t n_member
                                    "a paged group (vox_stream_group_create_paged) has no such limit", sg.max_pos, most);
     }
     VOXCHK(enc_stream_rope_ensure(m));
-    vox_stream_group* g = new vox_stream_group(); g->m = m; g->ctx = cx; g->t_embed.assign(t_embed, t_embed + c.dec_dim); g->n = n_members; g->g = sg; g->endless = endless;
+    vox_stream_group* g = new vox_stream_group(); g->m = m; g->ctx = cx; g->t_embed.assign(t_embed, t_embed + c.dec_dim); g->n = n_members; g->g = sg; g->endless = endless; g->kv_bf16 = kv_bf16;
     const size_t N = (size_t)n_members; const int D = c.dec_dim, QD = c.dec_heads * c.dec_head_dim, W = QD + 2 * c.dec_kv_heads * c.dec_head_dim, maxp = sg.max_pos;
     g->ring_layer = (size_t)c.enc_heads * sg.cap * c.enc_head_dim; g->ring_member = (size_t)c.enc_layers * g->ring_layer;
     g->seq_stride = (size_t)c.dec_kv_heads * maxp * c.dec_head_dim; g->layer_stride = N * g->seq_stride;
@@ -4246,7 +4269,7 @@ static int32_t group_create(vox_model* m, const float* t_embed, int32_t n_member
         if (endless) g->pool.init_ring(n_members, page_rows, c.dec_window, pool_pages, STREAM_POS_LIMIT); else g->pool.init(n_members, page_rows, c.dec_window, pool_pages, maxp);
         g->page_floats = (size_t)c.dec_kv_heads * page_rows * c.dec_head_dim; g->seq_stride = g->page_floats; g->layer_stride = (size_t)pool_pages * g->page_floats;
     }
-    const size_t ws_b = stream_ws_carve(m, n_members, nullptr, nullptr) * 4, slab_b = (size_t)c.dec_layers * g->layer_stride * 4;
+    const size_t ws_b = stream_ws_carve(m, n_members, nullptr, nullptr) * 4, slab_b = (size_t)c.dec_layers * g->layer_stride * (kv_bf16 ? 2 : 4);
     hipError_t e = hipSuccess;
     auto A = [&](void** q, size_t nb, bool zero) { if (e == hipSuccess) { e = hipMalloc(q, nb); if (e == hipSuccess) { g->bytes += nb; if (zero) e = hipMemsetAsync(*q, 0, nb, s); } } };
     A((void**)&g->kring, N * g->ring_member * 4, false); A((void**)&g->vring, N * g->ring_member * 4, false); A((void**)&g->dec_k, slab_b, true); A((void**)&g->dec_v, slab_b, true);
@@ -4298,6 +4321,14 @@ extern "C" int32_t vox_stream_group_create_endless(vox_model* m, const float* t_
                                                    int32_t page_rows, int32_t pool_pages, vox_stream_group** out) {
     ARGCHK(page_rows >= 0, "page_rows %d is negative", page_rows);
     return group_create(m, t_embed, n_members, gains, rates, enc_capacity_rows, 0, page_rows, pool_pages, out, true);
+}
+extern "C" int32_t vox_stream_group_create_kv(vox_model* m, const float* t_embed, int32_t n_members, const float* gains, const uint32_t* rates, int32_t enc_capacity_rows,
+                                              int32_t max_positions, int32_t page_rows, int32_t pool_pages, int32_t endless, int32_t kv_dtype, vox_stream_group** out) {
+    ARGCHK(kv_dtype == VOX_KV_F32 || kv_dtype == VOX_KV_BF16, "kv_dtype %d is neither VOX_KV_F32 (0) nor VOX_KV_BF16 (1)", kv_dtype);
+    ARGCHK(endless == 0 || endless == 1, "endless %d is neither 0 nor 1", endless);
+    ARGCHK(!endless || max_positions == 0, "an endless group takes no max_positions (%d): its members go on to the session limit", max_positions);
+    ARGCHK(page_rows >= 0, "page_rows %d is negative", page_rows);
+    return group_create(m, t_embed, n_members, gains, rates, enc_capacity_rows, endless ? 0 : max_positions, page_rows, pool_pages, out, endless != 0, kv_dtype == VOX_KV_BF16);
 }
 extern "C" int32_t vox_stream_group_pool(const vox_stream_group* g, int64_t out[4], int32_t* held_or_null) {
     ARGCHK(g && out, "null argument");
@@ -4356,6 +4387,7 @@ static int32_t group_round(vox_stream_group* g, const StreamWs& w, int n_r) {
     xb.k = g->dec_k; xb.v = g->dec_v; xb.layer_stride = g->layer_stride; xb.seq_stride = g->seq_stride; xb.max_seq = g->endless ? 0 : g->g.max_pos; xb.pos = g->d_pos; xb.kv_row = g->d_kv_row;      // (a paged step never reads max_seq)
     StreamPages pg{g->d_tab, g->pool.tab_len, g->pool.shift, g->d_kv_page, g->d_kv_in, g->endless ? g->pool.tab_len : 0};
     if (g->endless) { xb.page_tab_len = g->pool.tab_len; xb.rope_ring = g->rope.dec; xb.rope_mask = GROUP_ROPE_ROWS - 1; }
+    xb.kv_bf16 = g->kv_bf16 ? 1 : 0;
     if (g->paged) {
         xb.page_tab = g->d_tab; xb.page_tab_stride = g->pool.tab_len; xb.page_shift = g->pool.shift; xb.page_floats = (long)g->page_floats; xb.kv_page = g->d_kv_page; xb.kv_in = g->d_kv_in;
         xb.score_rows = c.dec_window >= 0 ? std::min(g->g.max_pos, c.dec_window + 1) : g->g.max_pos;
@@ -4675,7 +4707,7 @@ static SnapSession group_session(vox_stream_group* g, int i) {
     ss.dec.layers = c.dec_layers; ss.dec.heads = c.dec_kv_heads; ss.dec.hd = c.dec_head_dim; ss.dec.layer_stride = g->layer_stride;
     if (g->paged) {
         ss.dec.cache_k = g->dec_k; ss.dec.cache_v = g->dec_v; ss.dec.layout = g->endless ? vox::SNAP_PAGED_RING : vox::SNAP_PAGED; ss.dec.head_stride = (size_t)g->pool.page_rows * c.dec_head_dim;
-        ss.dec.tab = g->d_tab + (size_t)i * g->pool.tab_len; ss.dec.shift = g->pool.shift; ss.dec.tab_len = g->pool.tab_len; ss.dec.page_floats = g->page_floats;
+        ss.dec.tab = g->d_tab + (size_t)i * g->pool.tab_len; ss.dec.shift = g->pool.shift; ss.dec.tab_len = g->pool.tab_len; ss.dec.page_floats = g->page_floats; ss.dec.kv_bf16 = g->kv_bf16 ? 1 : 0;
     } else {
         ss.dec.cache_k = g->dec_k + (size_t)i * g->seq_stride; ss.dec.cache_v = g->dec_v + (size_t)i * g->seq_stride; ss.dec.layout = vox::SNAP_FLAT; ss.dec.head_stride = (size_t)g->g.max_pos * c.dec_head_dim;
     }

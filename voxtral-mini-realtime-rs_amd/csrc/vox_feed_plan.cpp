@@ -2,6 +2,7 @@
 // (one unit of the C ABI of libvoxtral_hip.so, include/voxtral_hip.h; the device-free host units: DESIGN.md, "Host units")
 #include "vox_host_base.h"
 #include "vox_page_pool.h"
+#include "vox_kv_bf16.h"
 
 using namespace vox_host;
 
@@ -146,6 +147,12 @@ extern "C" int32_t vox_stream_group_pages_for(int64_t positions, int32_t page_ro
 // ---- debug: the feed planner on its own (tests/test_stream_feed_cpu.py).  No device, no model: a fresh session at `sample_rate` (R = 4, the Voxtral left pad, no position
 // limit to speak of) takes the calls (n_samples[c], finish[c]) through feed_plan and feed_pass as the drivers do, every due tick taken as run.  One row of 5 per pass:
 // call index, input samples appended, 16 kHz samples that entered the 16 kHz ring (a 16 kHz session: the appended ones), pad zeros, ticks.  pass_cap: feed_pass's in_cap (0: none).
+// the rounding of a bf16 K/V pool (vox_kv_bf16.h: the function the append, the seed and the restore call on the device), as host arithmetic
+extern "C" int32_t vox_kv_round_bf16(const float* in, int64_t n, uint16_t* out) {
+    ARGCHK(n >= 0, "n %lld is negative", (long long)n); ARGCHK(n == 0 || (in && out), "null argument");
+    for (int64_t i = 0; i < n; i++) out[i] = vox::kv_bf16_round(in[i]);
+    return VOX_OK;
+}
 extern "C" int32_t vox_debug_stream_feed_passes(uint32_t sample_rate, const size_t* n_samples, const int32_t* finish, int32_t n_calls, size_t pass_cap, int64_t* rows, int32_t max_rows,
                                                 int32_t* n_rows) {
     ARGCHK(n_rows && (n_calls == 0 || (n_samples && finish)) && (rows || max_rows == 0), "null argument"); ARGCHK(sample_rate > 0, "bad sample rate 0");

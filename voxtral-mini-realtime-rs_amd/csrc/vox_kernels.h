@@ -37,6 +37,8 @@ enum Epi { EPI_STORE = 0, EPI_RESID = 1, EPI_SWIGLU = 2, EPI_ROPE_KV = 3, EPI_AR
            EPI_ROPE_KV_RING = 10,    // launch_q4_gemv only (Q4 weights): EPI_ROPE_KV on a cache used as a RING of cache_head_stride / hd rows per KV head -- k / v go to cache row
                                      // pos % that -- with the RoPE row read from a session's RoPE ring: row pos & rope_mask of [rope_mask + 1][cos hd/2 | sin hd/2] (rope_cos = the ring,
                                      // rope_sin = the ring + hd / 2: rows are hd floats apart, not hd / 2).  An epilogue instantiation of its own: EPI_ROPE_KV compiles as it did
+           EPI_ROPE_KV_PAGED_BF16 = 12, EPI_ROPE_KV_PAGED_RING_BF16 = 13,      // inside launch_q4_skinny only: the two paged epilogues on a bf16 pool (GemmParams::kv_bf16) -- RoPE in f32 as
+                                     // below, then K and V rounded by kv_bf16_round (vox_kv_bf16.h) and stored as 16-bit values; q is untouched.  Instantiations of their own
            EPI_ROPE_KV_PAGED_RING = 11 };  // inside launch_q4_skinny only: EPI_ROPE_KV_PAGED with GemmParams::rope_member set (an endless paged group) -- the RoPE row is read from the
                                      // group's member-strided RoPE ring: row rope_member[m] * (rope_mask + 1) + (pos[m] & rope_mask) of [members][rope_mask + 1][cos hd/2 | sin hd/2]
                                      // (rope_cos = the ring, rope_sin = the ring + hd / 2).  An epilogue instantiation of its own: the other two compile as they did
@@ -104,6 +106,7 @@ struct GemmParams {
     int rope_seq_rows;    // EPI_ROPE_ROWS without a position table: stacked sequences of this many rows restart at position 0 (0: row m sits at position m)
     int wide_mt; long xf_gstride /* uint4 */, xf_out_gstride /* uint16 */, ssq_part_gstride, ssq_out_gstride /* floats */;
     int wide_rows;        // > 0: q4_wide_kernel stores its K-slice planes ROW-MAJOR, [slice][wide_rows][N] f32 (rows < wide_rows only): the layout the 38-token prefill's finishing kernels read
+    int kv_bf16;          // EPI_ROPE_KV with kv_pos (a bf16 paged group): kc / vc point at uint16_t pools, every K / V stride counts 16-bit elements, the values are rounded by kv_bf16_round
 };
 // ---- wide decode step (round 6): 32 / 48 / 64 rows (2..4 slot groups of a continuous batch) through ONE weight fetch and ONE nibble -> bf16 conversion per K step.
 // GEMM (q4_wide_kernel: the groups' XF planes staged through LDS once per workgroup, K split over workgroups into planes) + a finishing launch that sums the planes in a
@@ -179,6 +182,9 @@ struct AttnParams {
     // 0: the table row is flat, entry q = logical page q.  L > 0 (an endless paged group): the row is a RING of L entries, logical page q at entry q % L -- a sequence
     // holds at most L pages at a time, so the window's pages never collide; L <= page_tab_stride, any L >= 1 (no power of two)
     int page_tab_len;
+    // paged decode on a bf16 pool (a bf16 paged group, VOX_KV_BF16): k / v point at uint16_t pools of the same layout, every K / V stride above counts 16-bit elements;
+    // the kernels widen the rows in registers (kv_bf16_widen) and run the f32 forms' arithmetic in their order
+    int kv_bf16;
 };
 hipError_t launch_attn_prefill(const AttnParams& p, int hd, hipStream_t s, int n_seq = 1);     // M > 1, causal (+window)
 bool attn_prefill_prefix_ok(const AttnParams& p, int hd, int n_seq);     // may launch_attn_prefill take p's two K / V segments (prefix_len > 0)?
@@ -205,6 +211,8 @@ enum AttnForm { ATTN_FORM_PREFILL_SMALL, ATTN_FORM_PREFILL_MFMA, ATTN_FORM_PREFI
                 ATTN_FORM_DECODE_PAGED, ATTN_FORM_DECODE_GQA_PAGED,      // the paged decode forms (launch_attn_decode_paged), behind every earlier slot
                 ATTN_FORM_DECODE_RING,                                   // the ring decode form (launch_attn_decode_ring)
                 ATTN_FORM_DECODE_PAGED_RING, ATTN_FORM_DECODE_GQA_PAGED_RING,      // the paged decode forms on a ring table (AttnParams::page_tab_len > 0)
+                ATTN_FORM_DECODE_PAGED_BF16, ATTN_FORM_DECODE_GQA_PAGED_BF16,      // the paged decode forms on a bf16 pool (AttnParams::kv_bf16): counted here and in no slot above
+                ATTN_FORM_DECODE_PAGED_RING_BF16, ATTN_FORM_DECODE_GQA_PAGED_RING_BF16,      // ... on a ring table
                 ATTN_FORM_COUNT };
 void attn_form_note(AttnForm f);
 void attn_form_counts(unsigned long long out[ATTN_FORM_COUNT]);
@@ -477,8 +485,9 @@ struct StreamPages { const int* tab; int tab_stride, shift; int* page_out; int* 
 hipError_t launch_stream_group_embed(Q4W tok, const StreamMember* mem, const int* order, int n, const float* audio, int D, float* h, uint16_t* xf, const float* xf_w,
                                      float* ssq_out, int* pos, int* kv_row, hipStream_t s, const StreamPages* pages = nullptr);
 // a paged member's seed: rows 0 .. rows-1 of src_k / src_v [layers][kv_heads][rows][hd] into the pages tab[0 ..] of the pool (layers layer_stride floats apart)
+// kv_bf16: pool_k / pool_v point at uint16_t pools (layer_stride in 16-bit elements), the rows are rounded by kv_bf16_round
 hipError_t launch_stream_pages_seed(const float* src_k, const float* src_v, int layers, int kv_heads, int rows, int hd, const int* tab, int page_shift, size_t layer_stride,
-                                    float* pool_k, float* pool_v, hipStream_t s);
+                                    float* pool_k, float* pool_v, hipStream_t s, bool kv_bf16 = false);
 // tokens[STRM_POS + 1] = argmax of logits row r (argmax_take / block_argmax: the rule of every decode form), the row copied to the session's tap when one is armed,
 // then the session's state advances by one tick as launch_stream_advance moves it
 hipError_t launch_stream_group_advance(const float* logits, int vocab, const StreamMember* mem, const int* order, int n, int enc_rows, int frames, int cap, hipStream_t s);
@@ -546,6 +555,9 @@ struct SnapshotKvParams {
     int cap;                                // SNAP_RING
     const int* tab; int shift, tab_len;     // SNAP_PAGED / SNAP_PAGED_RING: device table of the session, log2(page_rows); tab_len: SNAP_PAGED the entries the table has, SNAP_PAGED_RING the ring's
     size_t page_floats;                     // floats between two pages of one layer
+    // SNAP_PAGED / SNAP_PAGED_RING on a bf16 pool: cache_k / cache_v point at uint16_t pools, the three strides count 16-bit elements.  Pack widens (exact), restore
+    // rounds by kv_bf16_round (exact for a blob packed from a bf16 pool); the blob holds f32 rows either way
+    int kv_bf16;
 };
 // host: every table entry the range lo .. hi - 1 touches lies in 0 .. pool_pages - 1 (tab: the HOST copy of the table); *bad_page: the first logical page that does not
 bool snapshot_kv_pages_ok(const int* tab, int layout, int shift, int tab_len, int lo, int hi, int pool_pages, int* bad_page);

@@ -19,6 +19,7 @@
 //  * attention, conv, mel, norm, rope, resampler: wave64 shuffle / LDS kernels, f32.
 // vmcnt retires loads IN ORDER: every pipeline here requests its operands in consumption order.
 #include "vox_kernels.h"
+#include "vox_kv_bf16.h"
 
 #include <hip/hip_fp16.h>
 
@@ -228,21 +229,28 @@ hipError_t launch_q4_dequant(Q4W w, float* out, hipStream_t s) {
 struct NoHook { __device__ __forceinline__ void operator()() const {} };
 // where a decode attention finds cache row j of its KV head: the one place attn_decode_core and attn_decode_gqa_kernel form a K / V address.  Contiguous rows (a cache, a
 // slab slice): base + j * stride.  Paged rows (a paged stream group's pool): through the sequence's page table, staged in LDS by the kernel
+// A policy's element type says how a row is loaded (KvElem, below ldf4): float rows as float4s; uint16_t rows -- a bf16 pool -- as 16-byte pieces of 8 values (K) and
+// 8-byte pieces of 4 (V), widened in registers.  Everything behind the load is the same code.
 struct KvRowsFlat {
+    using elem = float;
     const float* kb; const float* vb; int stride;
     __device__ __forceinline__ const float* k(int j) const { return kb + (size_t)j * stride; }
     __device__ __forceinline__ const float* v(int j) const { return vb + (size_t)j * stride; }
 };
-struct KvRowsPaged {      // kb / vb: the layer's pool + the KV head's offset inside a page; tab[i]: the physical page of logical page q0 + i (LDS)
-    const float* kb; const float* vb; const int* tab; int q0, shift, mask, stride; size_t page_floats;
+template <class T>
+struct KvRowsPagedT {      // kb / vb: the layer's pool + the KV head's offset inside a page; tab[i]: the physical page of logical page q0 + i (LDS); strides in elements
+    using elem = T;
+    const T* kb; const T* vb; const int* tab; int q0, shift, mask, stride; size_t page_floats;
     __device__ __forceinline__ size_t at(int j) const { return (size_t)tab[(j >> shift) - q0] * page_floats + (size_t)(j & mask) * stride; }
-    __device__ __forceinline__ const float* k(int j) const { return kb + at(j); }
-    __device__ __forceinline__ const float* v(int j) const { return vb + at(j); }
+    __device__ __forceinline__ const T* k(int j) const { return kb + at(j); }
+    __device__ __forceinline__ const T* v(int j) const { return vb + at(j); }
 };
+using KvRowsPaged = KvRowsPagedT<float>;
 // Ring rows (an endless session's decoder cache, launch_attn_decode_ring): logical row j lives at ring row j % cap.  Built once per workgroup from the ring row of the
 // window's first key (r_lo = j_lo % cap: the only division); a window holds at most cap keys, so every key of it is r_lo + (j - j_lo) less at most one cap -- no
 // division per key.  Called with j_lo <= j < j_lo + cap alone (attn_decode_core asks for the window's rows and nothing else).
 struct KvRowsRing {
+    using elem = float;
     const float* kb; const float* vb; int r_lo, j_lo, cap, stride;
     __device__ __forceinline__ size_t at(int j) const { int t = r_lo + (j - j_lo); t -= t >= cap ? cap : 0; return (size_t)t * stride; }
     __device__ __forceinline__ const float* k(int j) const { return kb + at(j); }
@@ -1182,7 +1190,9 @@ __global__ __launch_bounds__(NTW == 3 ? 256 : 512, NTW == 3 ? 3 : 1) void q4_ski
     // EPI_ROPE_KV_PAGED: EPI_ROPE_KV with the row inside the cache slice taken from p.kv_pos (a paged cache) -- an instantiation of its own, so that the epilogue of
     // every contiguous cache stays the code it was
     // EPI_ROPE_KV_PAGED_RING: the paged epilogue with the RoPE row read from a member-strided RoPE ring (p.rope_member, p.rope_mask; rows hd floats apart: cos | sin)
-    constexpr bool KVR = EPI == EPI_ROPE_KV_PAGED_RING, KVP = EPI == EPI_ROPE_KV_PAGED || KVR, ROPE_KV = EPI == EPI_ROPE_KV || KVP;
+    // EPI_ROPE_KV_PAGED_BF16 / _PAGED_RING_BF16: the two paged epilogues on a bf16 pool -- K (after its f32 RoPE) and V rounded by kv_bf16_round, 16-bit stores
+    constexpr bool KVB = EPI == EPI_ROPE_KV_PAGED_BF16 || EPI == EPI_ROPE_KV_PAGED_RING_BF16;
+    constexpr bool KVR = EPI == EPI_ROPE_KV_PAGED_RING || EPI == EPI_ROPE_KV_PAGED_RING_BF16, KVP = EPI == EPI_ROPE_KV_PAGED || KVR || KVB, ROPE_KV = EPI == EPI_ROPE_KV || KVP;
     const int nb = p.w.nb, N = p.w.N, M = p.M, nq = nb >> 2;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, KS = blockDim.x >> 6;
     const int g = lane >> 4, li = lane & 15;
@@ -1416,10 +1426,12 @@ __global__ __launch_bounds__(NTW == 3 ? 256 : 512, NTW == 3 ? 3 : 1) void q4_ski
                         const float c = p.rope_cos[ti], sn = p.rope_sin[ti];
                         const float o = (n & 1) ? other * sn + v * c : v * c - other * sn;
                         if (n < p.n_q) p.out[(size_t)m * p.out_stride + n] = o;
+                        else if (KVB) reinterpret_cast<uint16_t*>(p.kc)[(size_t)cr * p.kv_seq_stride + (size_t)((n - p.n_q) / p.hd) * p.kv_head_stride + (size_t)cp * p.hd + dd] = kv_bf16_round(o);
                         else p.kc[(size_t)cr * p.kv_seq_stride + (size_t)((n - p.n_q) / p.hd) * p.kv_head_stride + (size_t)cp * p.hd + dd] = o;
                     } else {
                         const int vn = n - p.n_q - kd;
-                        p.vc[(size_t)cr * p.kv_seq_stride + (size_t)(vn / p.hd) * p.kv_head_stride + (size_t)cp * p.hd + (vn % p.hd)] = v;
+                        if (KVB) reinterpret_cast<uint16_t*>(p.vc)[(size_t)cr * p.kv_seq_stride + (size_t)(vn / p.hd) * p.kv_head_stride + (size_t)cp * p.hd + (vn % p.hd)] = kv_bf16_round(v);
+                        else p.vc[(size_t)cr * p.kv_seq_stride + (size_t)(vn / p.hd) * p.kv_head_stride + (size_t)cp * p.hd + (vn % p.hd)] = v;
                     }
                 }
             } else if (m < M && nok) {
@@ -2472,7 +2484,8 @@ hipError_t launch_transpose(const float* in, int R, int C, float* out, hipStream
 
 template <int NTW, int TILED>
 static hipError_t skinny_launch_n(const GemmParams& p, int epi, int ks, hipStream_t s) {
-    if (epi == EPI_ROPE_KV && p.kv_pos) epi = p.rope_member ? EPI_ROPE_KV_PAGED_RING : EPI_ROPE_KV_PAGED;      // (launch_q4_gemm_epi admits kv_pos with XF input alone, rope_member with kv_pos alone)
+    if (epi == EPI_ROPE_KV && p.kv_pos && p.kv_bf16) epi = p.rope_member ? EPI_ROPE_KV_PAGED_RING_BF16 : EPI_ROPE_KV_PAGED_BF16;      // (a bf16 pool: the same two forms, 16-bit stores)
+    else if (epi == EPI_ROPE_KV && p.kv_pos) epi = p.rope_member ? EPI_ROPE_KV_PAGED_RING : EPI_ROPE_KV_PAGED;      // (launch_q4_gemm_epi admits kv_pos with XF input alone, rope_member with kv_pos alone)
     dim3 grid((p.w.N + 16 * NTW - 1) / (16 * NTW));
     const size_t lds = (size_t)ks * NTW * 64 * 4 * sizeof(float);
     if (p.xf) {      // fragment-ordered bf16 hi/lo input (batched decode step); tile-ordered weights only
@@ -2485,7 +2498,7 @@ static hipError_t skinny_launch_n(const GemmParams& p, int epi, int ks, hipStrea
 #define VOX_ST(N_, E_, P_, S_) if (NTW == N_ && epi == E_ && (int)pro == P_ && per == S_) { \
             if (E_ == EPI_RESID_XF && (!p.xf_out || !p.xf_w || !p.ssq_out)) return hipErrorInvalidValue; \
             q4_skinny_kernel<N_, E_, 1, 1, P_, S_><<<grid, dim3(64 * ks), lds, s>>>(p); return hipGetLastError(); }
-            VOX_ST(2, EPI_ROPE_KV, 1, 3) VOX_ST(2, EPI_ROPE_KV_PAGED, 1, 3) VOX_ST(2, EPI_ROPE_KV_PAGED_RING, 1, 3) VOX_ST(2, EPI_SWIGLU_XF, 1, 6) VOX_ST(1, EPI_SWIGLU_XF, 1, 6) VOX_ST(1, EPI_RESID_XF, 0, 4) VOX_ST(4, EPI_SWIGLU_XF, 1, 6) VOX_ST(1, EPI_RESID_XF, 0, 9) VOX_ST(4, EPI_STORE, 1, 6)
+            VOX_ST(2, EPI_ROPE_KV, 1, 3) VOX_ST(2, EPI_ROPE_KV_PAGED, 1, 3) VOX_ST(2, EPI_ROPE_KV_PAGED_RING, 1, 3) VOX_ST(2, EPI_ROPE_KV_PAGED_BF16, 1, 3) VOX_ST(2, EPI_ROPE_KV_PAGED_RING_BF16, 1, 3) VOX_ST(2, EPI_SWIGLU_XF, 1, 6) VOX_ST(1, EPI_SWIGLU_XF, 1, 6) VOX_ST(1, EPI_RESID_XF, 0, 4) VOX_ST(4, EPI_SWIGLU_XF, 1, 6) VOX_ST(1, EPI_RESID_XF, 0, 9) VOX_ST(4, EPI_STORE, 1, 6)
 #undef VOX_ST
         }
         if (epi == EPI_RESID_XF) {
@@ -2497,6 +2510,8 @@ static hipError_t skinny_launch_n(const GemmParams& p, int epi, int ks, hipStrea
             case EPI_ROPE_KV: q4_skinny_kernel<NTW, EPI_ROPE_KV, 1, 1, 1><<<grid, dim3(64 * ks), lds, s>>>(p); break;
             case EPI_ROPE_KV_PAGED: q4_skinny_kernel<NTW, EPI_ROPE_KV_PAGED, 1, 1, 1><<<grid, dim3(64 * ks), lds, s>>>(p); break;
             case EPI_ROPE_KV_PAGED_RING: q4_skinny_kernel<NTW, EPI_ROPE_KV_PAGED_RING, 1, 1, 1><<<grid, dim3(64 * ks), lds, s>>>(p); break;
+            case EPI_ROPE_KV_PAGED_BF16: q4_skinny_kernel<NTW, EPI_ROPE_KV_PAGED_BF16, 1, 1, 1><<<grid, dim3(64 * ks), lds, s>>>(p); break;
+            case EPI_ROPE_KV_PAGED_RING_BF16: q4_skinny_kernel<NTW, EPI_ROPE_KV_PAGED_RING_BF16, 1, 1, 1><<<grid, dim3(64 * ks), lds, s>>>(p); break;
             case EPI_SWIGLU_XF: q4_skinny_kernel<NTW, EPI_SWIGLU_XF, 1, 1, 1><<<grid, dim3(64 * ks), lds, s>>>(p); break;
             default: return hipErrorInvalidValue;
             }
@@ -2601,6 +2616,7 @@ static hipError_t launch_q4_gemm_epi(const GemmParams& p, int epi_in, hipStream_
     int epi = epi_in == EPI_ROPE_ROWS ? EPI_STORE : epi_in;      // (EPI_ROPE_ROWS: only the large-M kernel below takes it; the others store, the caller ropes)
     if (p.w.K % 32 || p.M <= 0) return hipErrorInvalidValue;
     if (p.kv_pos && !(p.xf && p.M <= 16)) return hipErrorInvalidValue;      // a row inside the slice: q4_skinny_kernel's epilogue alone takes it
+    if (p.kv_bf16 && (!p.kv_pos || p.kv_bf16 != 1)) return hipErrorInvalidValue;      // a bf16 pool is a paged cache's
     if (p.rope_member && (!p.kv_pos || p.rope_mask < 0 || (p.rope_mask & (p.rope_mask + 1)))) return hipErrorInvalidValue;      // a member RoPE ring: the paged epilogue's, a power of two rows per member
     if (p.ksplit > 1 && (p.M <= 48 || p.xf || p.w.nb % 4 || p.w.fmt == WFMT_F32)) return hipErrorInvalidValue;      // split-K exists in q4_gemm_kernel only
     if (p.w.fmt == WFMT_F32) {      // true-f32 dense weights: bf16 hi + lo planes on the matrix cores (3 MFMAs per product, f32-class like the conv stem)
@@ -3235,6 +3251,31 @@ __device__ __forceinline__ float4 ldf4(const float* p) {
     if (NT) { const u32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p)); return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w)); }
     return *reinterpret_cast<const float4*>(p);
 }
+// The loads of a cache row by its element type (a row policy's `elem`).  One K load covers KQ float4s of the lane's run and stays as it arrived (KRaw) until the
+// score loop takes float4 t of it (wk); one V load is the 4 values of a column group (VRaw, wv).  float: the float4 itself, through ldf4 / plain loads as ever.
+// uint16_t (a bf16 pool): 8 values in 16 bytes, 4 in 8, widened by kv_bf16_widen where they are used -- the registers of the 160 prefetched keys hold the 16-bit pairs.
+template <class T> struct KvElem;
+template <> struct KvElem<float> {
+    static constexpr int KQ = 1;
+    using KRaw = float4; using VRaw = float4;      // (loaded and used by the statements the kernels always had: the F32 branches below)
+};
+__device__ __forceinline__ float4 kv_bf16_widen4(unsigned a, unsigned b) {      // the 4 values of two 16-bit pairs (little endian: the low half is the earlier element)
+    return make_float4(kv_bf16_widen((uint16_t)a), kv_bf16_widen((uint16_t)(a >> 16)), kv_bf16_widen((uint16_t)b), kv_bf16_widen((uint16_t)(b >> 16)));
+}
+template <> struct KvElem<uint16_t> {
+    static constexpr int KQ = 2;
+    using KRaw = u32x4_t; using VRaw = u32x2_t;
+    template <bool NT> static __device__ __forceinline__ KRaw ldk(const uint16_t* p) {
+        if (NT) return __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p));
+        return *reinterpret_cast<const u32x4_t*>(p);
+    }
+    template <bool NT> static __device__ __forceinline__ VRaw ldv(const uint16_t* p) {
+        if (NT) return __builtin_nontemporal_load(reinterpret_cast<const u32x2_t*>(p));
+        return *reinterpret_cast<const u32x2_t*>(p);
+    }
+    static __device__ __forceinline__ float4 wk(const KRaw& r, int t) { return t ? kv_bf16_widen4(r.z, r.w) : kv_bf16_widen4(r.x, r.y); }
+    static __device__ __forceinline__ float4 wv(const VRaw& r) { return kv_bf16_widen4(r.x, r.y); }
+};
 // LATE_V: the V rows of the first NPRE*32 keys are requested only after their K rows have been consumed (the K registers are reused:
 // ~half the VGPRs, one more round trip that overlaps the softmax) -- for callers that need 3 waves per SIMD (none today).
 // SPEC: the K / V rows of the first NPRE*32 keys are requested at rows 0 .. NPRE*32-1 of the cache (clamped to its spec_rows rows) WITHOUT
@@ -3268,18 +3309,23 @@ __device__ __forceinline__ float4 attn_decode_core(const float* __restrict__ qh,
     constexpr int NPRE = LATE_V ? 4 : 5, COLS = HD / 4, GROUPS = 256 / COLS;      // LATE_V: 128 keys up front
     static_assert(4 * GROUPS == 32 || HD != 128, "prefetch tiling assumes 32 keys per P.V iteration for HD = 128");
     const int grp = tid / COLS, col = tid % COLS;
-    float4 kpre[NPRE][PER / 4], vpre[NPRE][4];
+    using E = KvElem<typename Rows::elem>;      // the rows' loads: float4s, or a bf16 pool's 16- and 8-byte pieces
+    constexpr int KQ = E::KQ;                   // float4s of the lane's K run per load
+    constexpr bool F32 = KQ == 1;               // (float rows keep the statements they always had, word for word: their instantiations compile as they did)
+    typename E::KRaw kpre[NPRE][PER / (4 * KQ)]; typename E::VRaw vpre[NPRE][4];
 #define VOX_KPRE(ROW_)                                                                                        \
     _Pragma("unroll") for (int u = 0; u < NPRE; u++) {                                                        \
         const int jc = (ROW_);                                                                                \
-        const float* kr = rows.k(jc) + part * PER;                                                            \
-        _Pragma("unroll") for (int e = 0; e < PER / 4; e++) kpre[u][e] = ldf4<NT>(kr + 4 * e);                \
+        const auto* kr = rows.k(jc) + part * PER;                                                             \
+        if constexpr (F32) { _Pragma("unroll") for (int e = 0; e < PER / 4; e++) kpre[u][e] = ldf4<NT>(kr + 4 * e); } \
+        else { _Pragma("unroll") for (int e = 0; e < PER / 8; e++) kpre[u][e] = E::template ldk<NT>(kr + 8 * e); }    \
     }
 #define VOX_VPRE_AT(ROW_)                                                                                     \
     _Pragma("unroll") for (int u = 0; u < NPRE; u++)                                                          \
         _Pragma("unroll") for (int w = 0; w < 4; w++) {                                                       \
             const int iv = u * 4 * GROUPS + grp + w * GROUPS;                                                 \
-            vpre[u][w] = ldf4<NT>(rows.v(ROW_) + col * 4);                                                    \
+            if constexpr (F32) vpre[u][w] = ldf4<NT>(rows.v(ROW_) + col * 4);                                 \
+            else vpre[u][w] = E::template ldv<NT>(rows.v(ROW_) + col * 4);                                    \
         }
 #define VOX_VPRE VOX_VPRE_AT(j_lo + min(iv, n - 1))
     static_assert(!SPEC || !LATE_V, "speculative rows: K and V are both requested up front");
@@ -3310,7 +3356,8 @@ __device__ __forceinline__ float4 attn_decode_core(const float* __restrict__ qh,
         float s = 0.f;
 #pragma unroll
         for (int e = 0; e < PER / 4; e++) {
-            const float4 kv = kpre[u][e];
+            float4 kv;
+            if constexpr (F32) kv = kpre[u][e]; else kv = E::wk(kpre[u][e / KQ], e % KQ);
             s = fmaf(qv[4 * e], kv.x, s); s = fmaf(qv[4 * e + 1], kv.y, s); s = fmaf(qv[4 * e + 2], kv.z, s); s = fmaf(qv[4 * e + 3], kv.w, s);
         }
         s = group8_sum(s);
@@ -3325,12 +3372,25 @@ __device__ __forceinline__ float4 attn_decode_core(const float* __restrict__ qh,
 #pragma unroll
         for (int u = 0; u < 2; u++) {
             const int i = i0 + 32 * u + ks, jc = j_lo + min(i, n - 1);
-            const float* kr = rows.k(jc) + part * PER;
+            const auto* kr = rows.k(jc) + part * PER;
             float s = 0.f;
+            if constexpr (F32) {
 #pragma unroll
-            for (int e = 0; e < PER; e += 4) {
-                const float4 kv = ldf4<NT>(kr + e);
-                s = fmaf(qv[e], kv.x, s); s = fmaf(qv[e + 1], kv.y, s); s = fmaf(qv[e + 2], kv.z, s); s = fmaf(qv[e + 3], kv.w, s);
+                for (int e = 0; e < PER; e += 4) {
+                    const float4 kv = ldf4<NT>(kr + e);
+                    s = fmaf(qv[e], kv.x, s); s = fmaf(qv[e + 1], kv.y, s); s = fmaf(qv[e + 2], kv.z, s); s = fmaf(qv[e + 3], kv.w, s);
+                }
+            } else {      // the same chain of fmas on a run that arrives 8 values per load
+#pragma unroll
+                for (int e0 = 0; e0 < PER; e0 += 8) {
+                    const typename E::KRaw kw = E::template ldk<NT>(kr + e0);
+#pragma unroll
+                    for (int t = 0; t < 2; t++) {
+                        const int e = e0 + 4 * t;
+                        const float4 kv = E::wk(kw, t);
+                        s = fmaf(qv[e], kv.x, s); s = fmaf(qv[e + 1], kv.y, s); s = fmaf(qv[e + 2], kv.z, s); s = fmaf(qv[e + 3], kv.w, s);
+                    }
+                }
             }
             s2[u] = s;
         }
@@ -3365,18 +3425,31 @@ __device__ __forceinline__ float4 attn_decode_core(const float* __restrict__ qh,
             for (int w = 0; w < 4; w++) {
                 const int i = u * 32 + grp + w * GROUPS;
                 const float pr = i < n ? sc[min(i, n - 1)] : 0.f;
-                float4 vv = vpre[u][w];
+                float4 vv;
+                if constexpr (F32) vv = vpre[u][w]; else vv = E::wv(vpre[u][w]);
                 if (SPEC && i >= n) vv = make_float4(0.f, 0.f, 0.f, 0.f);      // a row past pos: 0 * (stale bits, possibly NaN) must stay 0
                 o.x = fmaf(pr, vv.x, o.x); o.y = fmaf(pr, vv.y, o.y); o.z = fmaf(pr, vv.z, o.z); o.w = fmaf(pr, vv.w, o.w);
             }
     }
     for (int i0 = (4 * GROUPS == 32 ? 32 * NPRE : 0) + grp; i0 < n; i0 += 4 * GROUPS) {
         float4 vv[4]; float pr[4];
+        if constexpr (F32) {
 #pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const int i = i0 + u * GROUPS, ic = min(i, n - 1);
-            vv[u] = ldf4<NT>(rows.v(j_lo + ic) + col * 4);
-            pr[u] = i < n ? sc[ic] : 0.f;
+            for (int u = 0; u < 4; u++) {
+                const int i = i0 + u * GROUPS, ic = min(i, n - 1);
+                vv[u] = ldf4<NT>(rows.v(j_lo + ic) + col * 4);
+                pr[u] = i < n ? sc[ic] : 0.f;
+            }
+        } else {      // the four loads out first, as above; widened once they are all requested
+            typename E::VRaw vr[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const int i = i0 + u * GROUPS, ic = min(i, n - 1);
+                vr[u] = E::template ldv<NT>(rows.v(j_lo + ic) + col * 4);
+                pr[u] = i < n ? sc[ic] : 0.f;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++) vv[u] = E::wv(vr[u]);
         }
 #pragma unroll
         for (int u = 0; u < 4; u++) {
@@ -3451,11 +3524,14 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const AttnParams p) {
 // through the sequence's page table, whose entries for the window are staged in LDS before the first K request (attn_stage_pages); the scores take score_rows per
 // query head.  Else the rows are contiguous.  The arithmetic depends on the logical key index alone: same scan order, same reduction trees, the same bits.
 static const int ATTN_PAGE_TAB_MAX = 1026;      // staged entries: 16 384 positions in pages of 16 rows, + 2
-__device__ __forceinline__ KvRowsPaged attn_stage_pages(const AttnParams& p, int seq, int kvh, int pos, int* __restrict__ ptab);
-template <int G, bool PAGED>
-__global__ __launch_bounds__(256) void attn_decode_gqa_kernel(const AttnParams p) {
+// T: the rows' element (KvElem): float, or uint16_t for a paged bf16 pool (attn_decode_gqa_bf16_kernel) -- the loads differ, nothing behind them does.
+template <class T>
+__device__ __forceinline__ KvRowsPagedT<T> attn_stage_pages(const AttnParams& p, int seq, int kvh, int pos, int* __restrict__ ptab);
+template <int G, bool PAGED, class T>
+__device__ __forceinline__ void attn_decode_gqa_body(const AttnParams p, float* __restrict__ smem) {      // smem: the kernel's dynamic LDS, scores [G][max_seq]
     constexpr int HD = 128, PER = HD / 8, NPRE = 5, COLS = HD / 4, GROUPS = 256 / COLS;   // GROUPS = 8
-    extern __shared__ __attribute__((aligned(16))) float smem[];      // scores [G][max_seq]
+    using E = KvElem<T>; constexpr int KQ = E::KQ;
+    constexpr bool F32 = KQ == 1;      // (float rows keep the statements they always had, word for word)
     __shared__ float red[2 * G * 4];
     __shared__ float4 osum[256];
     __shared__ int ptab[PAGED ? ATTN_PAGE_TAB_MAX : 1];
@@ -3466,8 +3542,8 @@ __global__ __launch_bounds__(256) void attn_decode_gqa_kernel(const AttnParams p
     const int j_lo = p.window >= 0 ? max(0, pos - p.window) : 0;
     const int n = len - j_lo;
     const float scale = 1.0f / sqrtf((float)HD);
-    typename std::conditional<PAGED, KvRowsPaged, KvRowsFlat>::type rows;
-    if constexpr (PAGED) rows = attn_stage_pages(p, seq, kvh, pos, ptab);
+    typename std::conditional<PAGED, KvRowsPagedT<T>, KvRowsFlat>::type rows;
+    if constexpr (PAGED) rows = attn_stage_pages<T>(p, seq, kvh, pos, ptab);
     else {
         const int crow = p.kv_row ? p.kv_row[seq] : seq;      // cache slice of this sequence (continuous batching: the utterance the slot holds)
         const float* kb = p.k + (size_t)crow * p.kv_seq_stride + (size_t)kvh * p.kv_head_stride;
@@ -3477,13 +3553,18 @@ __global__ __launch_bounds__(256) void attn_decode_gqa_kernel(const AttnParams p
     const float* qrow = p.q + (size_t)seq * p.q_seq_stride + (size_t)kvh * G * HD;
     const int ks = tid >> 3, part = tid & 7;
     const int grp = tid / COLS, col = tid % COLS;
-    float4 kpre[NPRE][PER / 4];
+    typename E::KRaw kpre[NPRE][PER / (4 * KQ)];
 #pragma unroll
     for (int u = 0; u < NPRE; u++) {
         const int jc = j_lo + min(32 * u + ks, n - 1);
-        const float* kr = rows.k(jc) + part * PER;
+        const auto* kr = rows.k(jc) + part * PER;
+        if constexpr (F32) {
 #pragma unroll
-        for (int e = 0; e < PER / 4; e++) kpre[u][e] = *reinterpret_cast<const float4*>(kr + 4 * e);
+            for (int e = 0; e < PER / 4; e++) kpre[u][e] = *reinterpret_cast<const float4*>(kr + 4 * e);
+        } else {
+#pragma unroll
+            for (int e = 0; e < PER / 8; e++) kpre[u][e] = E::template ldk<false>(kr + 8 * e);
+        }
     }
     float4 qv[G][PER / 4];
 #pragma unroll
@@ -3494,7 +3575,8 @@ __global__ __launch_bounds__(256) void attn_decode_gqa_kernel(const AttnParams p
     _Pragma("unroll") for (int hh = 0; hh < G; hh++) {                                                          \
         float s_ = 0.f;                                                                                         \
         _Pragma("unroll") for (int e = 0; e < PER / 4; e++) {                                                   \
-            const float4 kv = KR_[e], qq = qv[hh][e];                                                           \
+            float4 kv; const float4 qq = qv[hh][e];                                                             \
+            if constexpr (F32) kv = KR_[e]; else kv = E::wk(KR_[e / KQ], e % KQ);                               \
             s_ = fmaf(qq.x, kv.x, s_); s_ = fmaf(qq.y, kv.y, s_); s_ = fmaf(qq.z, kv.z, s_); s_ = fmaf(qq.w, kv.w, s_); \
         }                                                                                                       \
         s_ = group8_sum(s_);                                                                                    \
@@ -3504,20 +3586,26 @@ __global__ __launch_bounds__(256) void attn_decode_gqa_kernel(const AttnParams p
     for (int u = 0; u < NPRE; u++) { const int i = 32 * u + ks; VOX_SCORE(kpre[u], i) }
     for (int i0 = 32 * NPRE; i0 < n; i0 += 32) {
         const int i = i0 + ks, jc = j_lo + min(i, n - 1);
-        float4 kr[PER / 4];
+        typename E::KRaw kr[PER / (4 * KQ)];
+        if constexpr (F32) {
 #pragma unroll
-        for (int e = 0; e < PER / 4; e++) kr[e] = *reinterpret_cast<const float4*>(rows.k(jc) + part * PER + 4 * e);
+            for (int e = 0; e < PER / 4; e++) kr[e] = *reinterpret_cast<const float4*>(rows.k(jc) + part * PER + 4 * e);
+        } else {
+#pragma unroll
+            for (int e = 0; e < PER / 8; e++) kr[e] = E::template ldk<false>(rows.k(jc) + part * PER + 8 * e);
+        }
         VOX_SCORE(kr, i)
     }
 #undef VOX_SCORE
     // V rows of the first NPRE*32 keys: in flight while the softmax runs
-    float4 vpre[NPRE][4];
+    typename E::VRaw vpre[NPRE][4];
 #pragma unroll
     for (int u = 0; u < NPRE; u++)
 #pragma unroll
         for (int w = 0; w < 4; w++) {
             const int ic = min(u * 32 + grp + w * GROUPS, n - 1);
-            vpre[u][w] = *reinterpret_cast<const float4*>(rows.v(j_lo + ic) + col * 4);
+            if constexpr (F32) vpre[u][w] = *reinterpret_cast<const float4*>(rows.v(j_lo + ic) + col * 4);
+            else vpre[u][w] = E::template ldv<false>(rows.v(j_lo + ic) + col * 4);
         }
     __syncthreads();
     float mx[G], sum[G];
@@ -3548,7 +3636,8 @@ __global__ __launch_bounds__(256) void attn_decode_gqa_kernel(const AttnParams p
 #pragma unroll
         for (int w = 0; w < 4; w++) {
             const int i = u * 32 + grp + w * GROUPS, ic = min(i, n - 1);
-            const float4 vv = vpre[u][w];
+            float4 vv;
+            if constexpr (F32) vv = vpre[u][w]; else vv = E::wv(vpre[u][w]);
 #pragma unroll
             for (int hh = 0; hh < G; hh++) {
                 const float pr = i < n ? smem[hh * max_seq + ic] : 0.f;
@@ -3556,7 +3645,9 @@ __global__ __launch_bounds__(256) void attn_decode_gqa_kernel(const AttnParams p
             }
         }
     for (int i0 = 32 * NPRE + grp; i0 < n; i0 += GROUPS) {
-        const float4 vv = *reinterpret_cast<const float4*>(rows.v(j_lo + i0) + col * 4);
+        float4 vv;
+        if constexpr (F32) vv = *reinterpret_cast<const float4*>(rows.v(j_lo + i0) + col * 4);
+        else vv = E::wv(E::template ldv<false>(rows.v(j_lo + i0) + col * 4));
 #pragma unroll
         for (int hh = 0; hh < G; hh++) {
             const float pr = smem[hh * max_seq + i0];
@@ -3580,12 +3671,23 @@ __global__ __launch_bounds__(256) void attn_decode_gqa_kernel(const AttnParams p
         }
     }
 }
+template <int G, bool PAGED>
+__global__ __launch_bounds__(256) void attn_decode_gqa_kernel(const AttnParams p) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    attn_decode_gqa_body<G, PAGED, float>(p, smem);
+}
+template <int G>      // the paged form on a bf16 pool (AttnParams::kv_bf16)
+__global__ __launch_bounds__(256) void attn_decode_gqa_bf16_kernel(const AttnParams p) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    attn_decode_gqa_body<G, true, uint16_t>(p, smem);
+}
 // ---- paged decode attention (a paged stream group: AttnParams::page_tab): k / v are the layer's page POOL, [page][kv head][page_rows][hd]; sequence seq is member
 // kv_row[seq], whose table row names the physical page of each logical page.  The window's entries -- logical pages j_lo >> shift .. pos >> shift, at most
 // (window + 1) / page_rows + 2 of them -- are staged in LDS before the first K request; the bodies are the slab kernels' (attn_decode_core, attn_decode_gqa_kernel) with
 // the paged row policy: same scan order, same reduction trees, so a row has the slab kernel's bits.  Scores: score_rows per query head.  Entries outside the window
 // are never read (released pages hold -1 there).
-__device__ __forceinline__ KvRowsPaged attn_stage_pages(const AttnParams& p, int seq, int kvh, int pos, int* __restrict__ ptab) {
+template <class T>
+__device__ __forceinline__ KvRowsPagedT<T> attn_stage_pages(const AttnParams& p, int seq, int kvh, int pos, int* __restrict__ ptab) {
     const int j_lo = p.window >= 0 ? max(0, pos - p.window) : 0, q0 = j_lo >> p.page_shift, nq = (pos >> p.page_shift) - q0 + 1;
     const int* tab = p.page_tab + (size_t)(p.kv_row ? p.kv_row[seq] : seq) * p.page_tab_stride;
     if (p.page_tab_len > 0) {      // a ring table: logical page q at entry q % L.  s0 = q0 % L is the only division; nq <= L (the member holds no more), so s0 + i is less at most one L
@@ -3597,11 +3699,10 @@ __device__ __forceinline__ KvRowsPaged attn_stage_pages(const AttnParams& p, int
     }
     __syncthreads();
     const size_t ho = (size_t)kvh * p.kv_head_stride;
-    return KvRowsPaged{p.k + ho, p.v + ho, ptab, q0, p.page_shift, (1 << p.page_shift) - 1, p.kv_row_stride, (size_t)p.page_floats};
+    return KvRowsPagedT<T>{reinterpret_cast<const T*>(p.k) + ho, reinterpret_cast<const T*>(p.v) + ho, ptab, q0, p.page_shift, (1 << p.page_shift) - 1, p.kv_row_stride, (size_t)p.page_floats};
 }
-template <int HD>
-__global__ __launch_bounds__(256) void attn_decode_paged_kernel(const AttnParams p) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];      // scores, score_rows
+template <int HD, class T>
+__device__ __forceinline__ void attn_decode_paged_body(const AttnParams p, float* __restrict__ smem) {      // smem: the kernel's dynamic LDS, score_rows scores
     __shared__ float red[8];
     __shared__ float4 osum[256];
     __shared__ int ptab[ATTN_PAGE_TAB_MAX];
@@ -3617,15 +3718,25 @@ __global__ __launch_bounds__(256) void attn_decode_paged_kernel(const AttnParams
     }
     const int kvh = h / (p.n_heads / p.n_kv_heads);
     const int pos = (p.pos_ptr ? p.pos_ptr[p.pos_per_seq ? seq : 0] : 0) + p.offset;
-    const KvRowsPaged rows = attn_stage_pages(p, seq, kvh, pos, ptab);
+    const KvRowsPagedT<T> rows = attn_stage_pages<T>(p, seq, kvh, pos, ptab);
     const int tlw = (blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave; (void)tlw;
     VOX_TL(p.tl_slot, tlw, 0);
-    const float4 r4 = attn_decode_core<HD, false, false, false, NoHook, KvRowsPaged>(p.q + (size_t)seq * p.q_seq_stride + h * HD, rows, pos, p.window, smem, red, osum, p.tl_slot, tlw, 0);
+    const float4 r4 = attn_decode_core<HD, false, false, false, NoHook, KvRowsPagedT<T>>(p.q + (size_t)seq * p.q_seq_stride + h * HD, rows, pos, p.window, smem, red, osum, p.tl_slot, tlw, 0);
     if (tid < HD / 4) {
         if (p.out_xf) xf_store4(p.out_xf + (size_t)(seq >> 4) * p.out_xf_gstride, p.n_heads * HD, seq & 15, h * HD + tid * 4, r4);
         else *reinterpret_cast<float4*>(p.out + (size_t)seq * p.out_seq_stride + h * HD + tid * 4) = r4;
     }
     VOX_TL(p.tl_slot, tlw, 3);
+}
+template <int HD>
+__global__ __launch_bounds__(256) void attn_decode_paged_kernel(const AttnParams p) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    attn_decode_paged_body<HD, float>(p, smem);
+}
+template <int HD>      // on a bf16 pool (AttnParams::kv_bf16)
+__global__ __launch_bounds__(256) void attn_decode_paged_bf16_kernel(const AttnParams p) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    attn_decode_paged_body<HD, uint16_t>(p, smem);
 }
 // ---- single-stream decode: attention + wo in ONE launch (gguf/model.rs:125-174 + the wo linear of model.rs:230-238), no cross-workgroup wait.
 // Workgroup (h, slice): runs the attention of query head h (redundantly in each of the 8 slices: K / V rows are L2 hits after the first; the
@@ -3803,6 +3914,32 @@ hipError_t launch_attn_decode_paged(const AttnParams& p_in, int hd, hipStream_t 
     const bool tab_ring = p.page_tab_len != 0;
     if (tab_ring && (p.page_tab_len < 1 || p.page_tab_len > p.page_tab_stride || p.window < 0)) return hipErrorInvalidValue;
     const size_t lds = (size_t)p.score_rows * sizeof(float);
+    if (p.kv_bf16) {      // a bf16 pool: the same choice of form, the kernels' bf16 instantiations, counters of their own
+        if (p.kv_bf16 != 1 || ((reinterpret_cast<uintptr_t>(p.k) | reinterpret_cast<uintptr_t>(p.v)) & 15)) return hipErrorInvalidValue;
+        if (hd == 128 && p.n_heads == 4 * p.n_kv_heads) {
+            auto kern = attn_decode_gqa_bf16_kernel<4>;
+            static DevOnce attr_done;
+            hipError_t e = ensure_dyn_lds(kern, 4 * lds, &attr_done);
+            if (e != hipSuccess) return e;
+            kern<<<dim3(p.n_kv_heads, n_seq), dim3(256), 4 * lds, s>>>(p);
+            attn_form_note(tab_ring ? ATTN_FORM_DECODE_GQA_PAGED_RING_BF16 : ATTN_FORM_DECODE_GQA_PAGED_BF16);
+        } else if (hd == 128) {
+            auto kern = attn_decode_paged_bf16_kernel<128>;
+            static DevOnce attr_done;
+            hipError_t e = ensure_dyn_lds(kern, lds, &attr_done);
+            if (e != hipSuccess) return e;
+            kern<<<dim3(p.n_heads, n_seq), dim3(256), lds, s>>>(p);
+            attn_form_note(tab_ring ? ATTN_FORM_DECODE_PAGED_RING_BF16 : ATTN_FORM_DECODE_PAGED_BF16);
+        } else if (hd == 64) {
+            auto kern = attn_decode_paged_bf16_kernel<64>;
+            static DevOnce attr_done;
+            hipError_t e = ensure_dyn_lds(kern, lds, &attr_done);
+            if (e != hipSuccess) return e;
+            kern<<<dim3(p.n_heads, n_seq), dim3(256), lds, s>>>(p);
+            attn_form_note(tab_ring ? ATTN_FORM_DECODE_PAGED_RING_BF16 : ATTN_FORM_DECODE_PAGED_BF16);
+        } else return hipErrorInvalidValue;
+        return hipGetLastError();
+    }
     if (hd == 128 && p.n_heads == 4 * p.n_kv_heads) {
         auto kern = attn_decode_gqa_kernel<4, true>;
         static DevOnce attr_done;
@@ -4716,20 +4853,40 @@ hipError_t launch_stream_group_embed(Q4W tok, const StreamMember* mem, const int
 }
 // seed of a paged member (prefix_rows_into's counterpart): rows 0 .. rows-1 of every (layer, kv head) plane of the prefix state, src [layers][kv heads][rows][hd], into
 // the member's first pages of the pool [layers][pool_pages][kv heads][page_rows][hd]; tab: the member's table row
-__global__ __launch_bounds__(256) void stream_pages_seed_kernel(const float* __restrict__ src_k, const float* __restrict__ src_v, int kv_heads, int rows, int hd4,
-                                                                const int* __restrict__ tab, int shift, size_t layer_stride, size_t page_floats,
-                                                                float* __restrict__ pool_k, float* __restrict__ pool_v, long total) {
+// 4 values of a pool row as they are stored: a float4, or -- a bf16 pool -- the 4 values rounded by kv_bf16_round, 8 bytes
+__device__ __forceinline__ void kv_pool_store4(float* dst, const float4& v) { *reinterpret_cast<float4*>(dst) = v; }
+__device__ __forceinline__ u32x2_t kv_pool_round4(const float4& v);
+__device__ __forceinline__ void kv_pool_store4(uint16_t* dst, const float4& v) { *reinterpret_cast<u32x2_t*>(dst) = kv_pool_round4(v); }
+template <class T>
+__device__ __forceinline__ void stream_pages_seed_body(const float* __restrict__ src_k, const float* __restrict__ src_v, int kv_heads, int rows, int hd4,
+                                                       const int* __restrict__ tab, int shift, size_t layer_stride, size_t page_floats,
+                                                       T* __restrict__ pool_k, T* __restrict__ pool_v, long total) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const int d = (int)(i % hd4); long t = i / hd4; const int j = (int)(t % rows); t /= rows; const int kh = (int)(t % kv_heads), l = (int)(t / kv_heads);
         const size_t dst = (size_t)l * layer_stride + (size_t)tab[j >> shift] * page_floats + ((size_t)kh << shift) * hd4 * 4 + (size_t)(j & ((1 << shift) - 1)) * hd4 * 4 + 4 * d;
-        *reinterpret_cast<float4*>(pool_k + dst) = reinterpret_cast<const float4*>(src_k)[i];
-        *reinterpret_cast<float4*>(pool_v + dst) = reinterpret_cast<const float4*>(src_v)[i];
+        kv_pool_store4(pool_k + dst, reinterpret_cast<const float4*>(src_k)[i]);
+        kv_pool_store4(pool_v + dst, reinterpret_cast<const float4*>(src_v)[i]);
     }
 }
+__global__ __launch_bounds__(256) void stream_pages_seed_kernel(const float* __restrict__ src_k, const float* __restrict__ src_v, int kv_heads, int rows, int hd4,
+                                                                const int* __restrict__ tab, int shift, size_t layer_stride, size_t page_floats,
+                                                                float* __restrict__ pool_k, float* __restrict__ pool_v, long total) {
+    stream_pages_seed_body<float>(src_k, src_v, kv_heads, rows, hd4, tab, shift, layer_stride, page_floats, pool_k, pool_v, total);
+}
+__global__ __launch_bounds__(256) void stream_pages_seed_bf16_kernel(const float* __restrict__ src_k, const float* __restrict__ src_v, int kv_heads, int rows, int hd4,
+                                                                     const int* __restrict__ tab, int shift, size_t layer_stride, size_t page_floats,
+                                                                     uint16_t* __restrict__ pool_k, uint16_t* __restrict__ pool_v, long total) {
+    stream_pages_seed_body<uint16_t>(src_k, src_v, kv_heads, rows, hd4, tab, shift, layer_stride, page_floats, pool_k, pool_v, total);
+}
 hipError_t launch_stream_pages_seed(const float* src_k, const float* src_v, int layers, int kv_heads, int rows, int hd, const int* tab, int page_shift, size_t layer_stride,
-                                    float* pool_k, float* pool_v, hipStream_t s) {
+                                    float* pool_k, float* pool_v, hipStream_t s, bool kv_bf16) {
     if (!src_k || !src_v || !tab || !pool_k || !pool_v || layers < 1 || kv_heads < 1 || rows < 1 || hd < 4 || (hd & 3) || page_shift < 4 || page_shift > 10) return hipErrorInvalidValue;
     const long total = (long)layers * kv_heads * rows * (hd / 4);
+    if (kv_bf16) {
+        stream_pages_seed_bf16_kernel<<<dim3((unsigned)std::min<long>((total + 255) / 256, 1024)), dim3(256), 0, s>>>(src_k, src_v, kv_heads, rows, hd / 4, tab, page_shift, layer_stride,
+            (size_t)kv_heads * hd << page_shift, reinterpret_cast<uint16_t*>(pool_k), reinterpret_cast<uint16_t*>(pool_v), total);
+        return hipGetLastError();
+    }
     stream_pages_seed_kernel<<<dim3((unsigned)std::min<long>((total + 255) / 256, 1024)), dim3(256), 0, s>>>(src_k, src_v, kv_heads, rows, hd / 4, tab, page_shift, layer_stride,
                                                                                                               (size_t)kv_heads * hd << page_shift, pool_k, pool_v, total);
     return hipGetLastError();
@@ -4934,6 +5091,46 @@ __global__ __launch_bounds__(256) void snapshot_kv_kernel(SnapshotKvParams p) {
         else { const float4 k0 = ck[a0], v0 = cv[a0]; bk[i] = k0; bv[i] = v0; }
     }
 }
+// The paged layouts on a bf16 pool (SnapshotKvParams::kv_bf16; RING: SNAP_PAGED_RING): the blob side moves the float4s of the kernel above, the cache side the same 4
+// values as 8 bytes -- pack widens them (kv_bf16_widen, exact), restore rounds them (kv_bf16_round: exact for a blob packed from a bf16 pool).  The strides count
+// 16-bit elements; `at` counts 4-value pieces, as above.
+__device__ __forceinline__ float4 kv_pool_widen4(const u32x2_t& r) { return kv_bf16_widen4(r.x, r.y); }
+__device__ __forceinline__ u32x2_t kv_pool_round4(const float4& v) {
+    u32x2_t r;
+    r.x = (unsigned)kv_bf16_round(v.x) | ((unsigned)kv_bf16_round(v.y) << 16); r.y = (unsigned)kv_bf16_round(v.z) | ((unsigned)kv_bf16_round(v.w) << 16);
+    return r;
+}
+template <int HD, bool RING, int RESTORE>
+__global__ __launch_bounds__(256) void snapshot_kv_bf16_kernel(SnapshotKvParams p) {
+    constexpr int HQ_SHIFT = HD == 64 ? 4 : 5, HQ = 1 << HQ_SHIFT;      // 4-value pieces per row
+    const int plane = p.plane0 + (int)blockIdx.y, layer = plane / p.heads, head = plane - layer * p.heads;
+    const long n = (long)(p.hi - p.lo) << HQ_SHIFT;
+    const size_t base = (size_t)layer * p.layer_stride + (size_t)head * p.head_stride;
+    u32x2_t* __restrict__ ck = reinterpret_cast<u32x2_t*>(reinterpret_cast<uint16_t*>(p.cache_k) + base);
+    u32x2_t* __restrict__ cv = reinterpret_cast<u32x2_t*>(reinterpret_cast<uint16_t*>(p.cache_v) + base);
+    float4* __restrict__ bk = reinterpret_cast<float4*>(p.blob_k) + (long)blockIdx.y * n;
+    float4* __restrict__ bv = reinterpret_cast<float4*>(p.blob_v) + (long)blockIdx.y * n;
+    const int pg0 = p.lo >> p.shift, e0 = RING ? pg0 % p.tab_len : pg0;
+    const long page_q = (long)(p.page_floats >> 2);
+    auto at = [&](long i) -> long {      // the cache's piece of the blob's float4 i
+        const int r = (int)(i >> HQ_SHIFT), q = (int)(i & (HQ - 1));
+        const int row = p.lo + r; int e = e0 + ((row >> p.shift) - pg0);
+        if (RING && e >= p.tab_len) e -= p.tab_len;
+        return (long)p.tab[e] * page_q + ((long)(row & ((1 << p.shift) - 1)) << HQ_SHIFT) + q;
+    };
+    const long step = (long)gridDim.x * 256;
+    long i = (long)blockIdx.x * 256 + threadIdx.x;
+    for (; i + step < n; i += 2 * step) {
+        const long a0 = at(i), a1 = at(i + step);
+        if (RESTORE) { const float4 k0 = bk[i], v0 = bv[i], k1 = bk[i + step], v1 = bv[i + step]; ck[a0] = kv_pool_round4(k0); cv[a0] = kv_pool_round4(v0); ck[a1] = kv_pool_round4(k1); cv[a1] = kv_pool_round4(v1); }
+        else { const u32x2_t k0 = ck[a0], v0 = cv[a0], k1 = ck[a1], v1 = cv[a1]; bk[i] = kv_pool_widen4(k0); bv[i] = kv_pool_widen4(v0); bk[i + step] = kv_pool_widen4(k1); bv[i + step] = kv_pool_widen4(v1); }
+    }
+    if (i < n) {
+        const long a0 = at(i);
+        if (RESTORE) { const float4 k0 = bk[i], v0 = bv[i]; ck[a0] = kv_pool_round4(k0); cv[a0] = kv_pool_round4(v0); }
+        else { const u32x2_t k0 = ck[a0], v0 = cv[a0]; bk[i] = kv_pool_widen4(k0); bv[i] = kv_pool_widen4(v0); }
+    }
+}
 bool snapshot_kv_pages_ok(const int* tab, int layout, int shift, int tab_len, int lo, int hi, int pool_pages, int* bad_page) {
     if (layout < SNAP_PAGED || lo >= hi) return true;
     for (int pg = lo >> shift; pg <= ((hi - 1) >> shift); pg++) {
@@ -4946,6 +5143,7 @@ hipError_t launch_snapshot_kv(const SnapshotKvParams& p, int restore, hipStream_
     const int all = p.layers * p.heads, n_planes = p.n_planes ? p.n_planes : all - p.plane0;
     if (p.layers < 1 || p.heads < 1 || (p.hd != 64 && p.hd != 128) || p.lo < 0 || p.hi < p.lo || p.plane0 < 0 || n_planes < 1 || p.plane0 + n_planes > all || n_planes > 65535) return hipErrorInvalidValue;
     if (p.layout < SNAP_FLAT || p.layout > SNAP_PAGED_RING || (p.layer_stride & 3) || (p.head_stride & 3)) return hipErrorInvalidValue;
+    if (p.kv_bf16 && (p.kv_bf16 != 1 || p.layout < SNAP_PAGED || (p.layer_stride & 7) || (p.head_stride & 7) || (p.page_floats & 7))) return hipErrorInvalidValue;      // a bf16 pool is a paged cache's; 16-byte rows
     if (p.hi == p.lo) return hipSuccess;      // nothing to move: no launch
     if (!p.cache_k || !p.cache_v || !p.blob_k || !p.blob_v) return hipErrorInvalidValue;
     if ((reinterpret_cast<uintptr_t>(p.cache_k) | reinterpret_cast<uintptr_t>(p.cache_v) | reinterpret_cast<uintptr_t>(p.blob_k) | reinterpret_cast<uintptr_t>(p.blob_v)) & 15) return hipErrorInvalidValue;
@@ -4963,12 +5161,18 @@ hipError_t launch_snapshot_kv(const SnapshotKvParams& p, int restore, hipStream_
     const dim3 grid(bx, n_planes), block(256);
 #define SNAP_GO(HD, L) do { if (restore) snapshot_kv_kernel<HD, L, 1><<<grid, block, 0, s>>>(q); else snapshot_kv_kernel<HD, L, 0><<<grid, block, 0, s>>>(q); } while (0)
 #define SNAP_HD(L) do { if (p.hd == 64) SNAP_GO(64, L); else SNAP_GO(128, L); } while (0)
+#define SNAP_GO_B(HD, L) do { if (restore) snapshot_kv_bf16_kernel<HD, L, 1><<<grid, block, 0, s>>>(q); else snapshot_kv_bf16_kernel<HD, L, 0><<<grid, block, 0, s>>>(q); } while (0)
+    if (p.kv_bf16) {
+        if (p.layout == SNAP_PAGED) { if (p.hd == 64) SNAP_GO_B(64, false); else SNAP_GO_B(128, false); }
+        else { if (p.hd == 64) SNAP_GO_B(64, true); else SNAP_GO_B(128, true); }
+    } else
     switch (p.layout) {
         case SNAP_FLAT: SNAP_HD(SNAP_FLAT); break;
         case SNAP_RING: SNAP_HD(SNAP_RING); break;
         case SNAP_PAGED: SNAP_HD(SNAP_PAGED); break;
         default: SNAP_HD(SNAP_PAGED_RING); break;
     }
+#undef SNAP_GO_B
 #undef SNAP_HD
 #undef SNAP_GO
     return hipGetLastError();

@@ -261,6 +261,13 @@ def attention(ctx, q, k, v, n_heads, n_kv_heads, offset=0, window=-1):
     return out
 
 
+def kv_round_bf16(x) -> np.ndarray:
+    """vox_kv_round_bf16 (host arithmetic): the bf16 K/V pool's rounding of float32 values -- round to nearest even on the upper 16 bits -- as uint16 of x's shape."""
+    x = _f32(x); out = np.empty(x.shape, np.uint16)
+    check(lib().vox_kv_round_bf16(_ptr(x), x.size, _ptr(out)))
+    return out
+
+
 class AttnDecodeDesc(C.Structure):
     """vox_attn_decode_desc (include/voxtral_hip.h)."""
     _fields_ = [(n, C.c_int32) for n in ("n_seq", "n_heads", "n_kv_heads", "head_dim", "window", "n_slices", "max_seq", "page_rows", "pool_pages", "page_tab_stride",
@@ -268,12 +275,18 @@ class AttnDecodeDesc(C.Structure):
 
 
 def attn_decode(ctx, q, k, v, pos, n_heads, n_kv_heads, window=-1, kv_row=None, page_tab=None, score_rows=0, prefer_gqa=False, spec=False, no_xcd_remap=False,
-                out_xf=False, head_dim=128, page_tab_len=None):
+                out_xf=False, head_dim=128, page_tab_len=None, bf16=False):
     """vox_debug_attn_decode: ONE decode attention launch.  q [n_seq, n_heads*128], pos [n_seq]; slab: k / v [n_slices, n_kv_heads, max_seq, 128]; paged (page_tab
     [n_slices, stride] int32 given): k / v [pool_pages, n_kv_heads, page_rows, 128].  Returns float32 [n_seq, n_heads*128], or with out_xf the raw XF planes as uint16
     [ceil(n_seq / 16), 2, n_heads*128 / 128 * 256 * 8] (hi plane, lo plane).
-    page_tab_len (a paged call): vox_debug_attn_decode_paged_ring -- every table row is a ring of page_tab_len entries, logical page q at entry q % page_tab_len."""
-    q, k, v = _f32(q), _f32(k), _f32(v)
+    page_tab_len (a paged call): vox_debug_attn_decode_paged_ring -- every table row is a ring of page_tab_len entries, logical page q at entry q % page_tab_len.
+    bf16 (a paged call): vox_debug_attn_decode_paged_bf16 -- k / v are uint16 pools of bf16 values (kv_round_bf16); page_tab_len None: a flat table."""
+    if bf16:
+        q, k, v = _f32(q), np.ascontiguousarray(k, dtype=np.uint16), np.ascontiguousarray(v, dtype=np.uint16)
+        if page_tab is None:
+            raise VoxError(1, "attn_decode: a bf16 pool belongs to a paged call")
+    else:
+        q, k, v = _f32(q), _f32(k), _f32(v)
     pos = np.ascontiguousarray(pos, dtype=np.int32)
     if q.ndim != 2 or k.ndim != 4 or k.shape != v.shape or pos.shape != (q.shape[0],):
         raise VoxError(1, "attn_decode: bad shapes")
@@ -296,7 +309,9 @@ def attn_decode(ctx, q, k, v, pos, n_heads, n_kv_heads, window=-1, kv_row=None, 
         raise VoxError(1, "attn_decode: q / k / v widths do not match the head counts")
     QD = n_heads * 128
     out = np.empty(((q.shape[0] + 15) // 16, 2, QD // 128 * 256 * 8), np.uint16) if out_xf else np.empty((q.shape[0], QD), np.float32)
-    if page_tab_len is not None:
+    if bf16:
+        check(lib().vox_debug_attn_decode_paged_bf16(ctx.h, C.byref(d), int(page_tab_len or 0), _ptr(q), _ptr(k), _ptr(v), _ptr(out)))
+    elif page_tab_len is not None:
         check(lib().vox_debug_attn_decode_paged_ring(ctx.h, C.byref(d), int(page_tab_len), _ptr(q), _ptr(k), _ptr(v), _ptr(out)))
     else:
         check(lib().vox_debug_attn_decode(ctx.h, C.byref(d), _ptr(q), _ptr(k), _ptr(v), _ptr(out)))
@@ -864,12 +879,18 @@ class LiveStreamGroup:
     stream_schedule(..., sample_rate=its rate) on its own sample count.  Samples are float32 or 16-bit PCM at the member's rate."""
     _rates = None      # {member: rate} of the members at another rate than 16 kHz; a member without an entry is fed 16 kHz
 
-    def __init__(self, model, t_embed, n_members, gains=None, enc_capacity_rows=0, max_positions=0, sample_rates=None, page_rows=None, pool_pages=None, endless=False):
+    KV_DTYPES = {"f32": 0, "bf16": 1}      # VOX_KV_F32, VOX_KV_BF16
+
+    def __init__(self, model, t_embed, n_members, gains=None, enc_capacity_rows=0, max_positions=0, sample_rates=None, page_rows=None, pool_pages=None, endless=False,
+                 kv_dtype=None):
         self.model = model; self.h = C.c_void_p(); self.n_members = int(n_members); self._tap_max = {}; self._rates = {}
+        if kv_dtype is not None and kv_dtype not in self.KV_DTYPES:
+            raise ValueError(f"kv_dtype {kv_dtype!r}: a stream group's K/V pool holds 'f32' or 'bf16'")
+        self.kv_dtype = kv_dtype      # given: a paged group made by vox_stream_group_create_kv, whose pool() names the dtype; None: the group the other arguments make
         self.endless = bool(endless)      # an endless paged group (vox_stream_group_create_endless): no max_positions, every member goes on to 2^24 positions
         if self.endless and max_positions:
             raise ValueError(f"an endless stream group has no max_positions (got {max_positions}): every member may go on to 2^24 positions")
-        self.paged = self.endless or page_rows is not None or pool_pages is not None      # either one given: a paged group (vox_stream_group_create_paged; 0 / None: its default)
+        self.paged = self.endless or page_rows is not None or pool_pages is not None or kv_dtype is not None      # either one given: a paged group (vox_stream_group_create_paged; 0 / None: its default)
         g = None if gains is None else _f32(gains).reshape(-1)
         if g is not None and g.size != self.n_members:
             raise ValueError(f"{g.size} gains for {self.n_members} members")
@@ -880,7 +901,10 @@ class LiveStreamGroup:
             r = np.ascontiguousarray([int(v) for v in (sample_rates if sample_rates is not None else [16000] * self.n_members)], dtype=np.uint32)
             if r.size != self.n_members:
                 raise ValueError(f"{r.size} sample rates for {self.n_members} members")
-            if self.endless:
+            if kv_dtype is not None:
+                check(lib().vox_stream_group_create_kv(*args, _ptr(r), int(enc_capacity_rows), int(max_positions), int(page_rows or 0), int(pool_pages or 0), int(self.endless),
+                                                       self.KV_DTYPES[kv_dtype], C.byref(self.h)))
+            elif self.endless:
                 check(lib().vox_stream_group_create_endless(*args, _ptr(r), int(enc_capacity_rows), int(page_rows or 0), int(pool_pages or 0), C.byref(self.h)))
             elif self.paged:
                 check(lib().vox_stream_group_create_paged(*args, _ptr(r), int(enc_capacity_rows), int(max_positions), int(page_rows or 0), int(pool_pages or 0), C.byref(self.h)))
@@ -982,7 +1006,10 @@ class LiveStreamGroup:
         """vox_stream_group_pool of a paged group: page_rows, pool_pages, the free pages, the most pages ever in use, and held: the pages each member holds."""
         v = (C.c_int64 * 4)(); held = np.zeros(self.n_members, dtype=np.int32)
         check(lib().vox_stream_group_pool(self.h, v, _ptr(held)))
-        return {"page_rows": int(v[0]), "pool_pages": int(v[1]), "free": int(v[2]), "peak": int(v[3]), "held": [int(x) for x in held]}
+        out = {"page_rows": int(v[0]), "pool_pages": int(v[1]), "free": int(v[2]), "peak": int(v[3]), "held": [int(x) for x in held]}
+        if self.kv_dtype is not None:      # (a group made with kv_dtype= alone: the dicts of every other group are what they were)
+            out["kv_dtype"] = self.kv_dtype
+        return out
 
     def pages(self, member) -> list:
         """vox_debug_stream_group_pages: the member's physical pages, in the order of its logical pages."""
@@ -1233,15 +1260,17 @@ class Q4VoxtralModel:
         return LiveStream(self, t_embed, gain, enc_capacity_rows, max_positions, sample_rate, endless, dec_ring_rows)
 
     def create_stream_group(self, t_embed, n_members, gains=None, enc_capacity_rows=0, max_positions=0, sample_rates=None, page_rows=None, pool_pages=None,
-                            endless=False) -> LiveStreamGroup:
+                            endless=False, kv_dtype=None) -> LiveStreamGroup:
         """Up to 16 live sessions advanced together (vox_stream_group_create): advance({member: samples}, finish=()) -> {member: ids}, reset(member, gain), info(member),
         close().  gains: one per member (None: 1.0 each); max_positions 0: 2048 decoder positions per member (the group's decoder cache does not grow);
         sample_rates: what each member is fed (None: 16 kHz each; vox_stream_group_create_rates).
         page_rows / pool_pages, either one given: a PAGED group (vox_stream_group_create_paged) -- one pool of pool_pages K / V pages of page_rows rows (0 / None: 256 rows;
         the default slab's memory) that the members grow into and return pages to; max_positions 0 is then the session limit; pool(), pages(member).
         endless (vox_stream_group_create_endless): a paged group (page_rows / pool_pages as above, both optional) whose members are not refused at 16 384 positions
-        but go on to 2^24; max_positions must not be given (ValueError).  Everything of a paged group works unchanged."""
-        return LiveStreamGroup(self, t_embed, n_members, gains, enc_capacity_rows, max_positions, sample_rates, page_rows, pool_pages, endless)
+        but go on to 2^24; max_positions must not be given (ValueError).  Everything of a paged group works unchanged.
+        kv_dtype "f32" | "bf16" (vox_stream_group_create_kv; implies paged, as endless does; anything else: ValueError): what the K / V pool holds.  "bf16": 16-bit
+        pages, half the memory and half the bytes the decode attention reads; ids and logits are close to, not equal to, the f32 group's.  pool() then names it."""
+        return LiveStreamGroup(self, t_embed, n_members, gains, enc_capacity_rows, max_positions, sample_rates, page_rows, pool_pages, endless, kv_dtype)
 
     def transcribe_batch(self, samples_list, t_embed, device_ptrs=None, n_samples=None, norm_group=None, tap_units=None):
         """Batched whole-path transcription of independent utterances (<= 4096; wider than 16: continuous batching over decode slots): list of float32 sample arrays
