@@ -512,6 +512,14 @@ typedef struct {
     const int32_t* enc_pos;      /* [n_members] */
 } vox_stream_attn_desc;
 int32_t vox_debug_stream_attn(vox_ctx* ctx, const vox_stream_attn_desc* desc, const float* qkv, float* kring, float* vring, float* out);
+/* The BURST form of the same attention (a burst stream's encoder layers: vox_stream_create_burst), on its own: vox_debug_stream_attn's arguments and checks with `rows`
+ * 1..64 (b ticks' 4 b rows at enc_pos + m; window + rows < cap; a RoPE ring of at least `rows` rows) -- exactly ONE launch of the burst kernel, counted in
+ * vox_debug_stream_attn_burst_launches and in no slot of vox_debug_attn_launches; a refused call counts nothing.  One workgroup serves a head and a tile of 4 query
+ * rows and reads every ring row once for the tile.  One call with rows = 4 b leaves the bits in `out`, kring and vring that b successive vox_debug_stream_attn calls
+ * with rows = 4 leave when enc_pos moves by 4 between them. */
+int32_t vox_debug_stream_attn_burst(vox_ctx* ctx, const vox_stream_attn_desc* desc, const float* qkv, float* kring, float* vring, float* out);
+/* launches of the burst kernel enqueued by the host so far (a burst stream: enc_layers per burst with b >= 2) */
+int32_t vox_debug_stream_attn_burst_launches(uint64_t* out);
 /* The seeding of a session's encoder rings from the model's prefix state, on its own (tests): kv host [layers][rows][k row | v row], token-major, each row n_heads *
  * head_dim wide; kring / vring host [layers][n_heads][cap][head_dim], in and out: ring rows 0 .. rows - 1 of every layer and head receive the input's bits, every
  * other word keeps its own.  layers 1..64, n_heads 1..64, head_dim 64 | 128, cap 1..16384; rows <= 0 and rows > cap are refused, like every argument, before the
@@ -670,6 +678,26 @@ int32_t vox_stream_create_rate(vox_model* m, const float* t_embed, float gain, i
  *   not trimmed.  vox_stream_info [1] keeps counting positions.
  *   Not served: stream groups (slab or paged), a ring form of the fused attention + wo launch, paging for a solo stream, trimming the host record lists. */
 int32_t vox_stream_create_endless(vox_model* m, const float* t_embed, float gain, int32_t enc_capacity_rows, int32_t dec_ring_rows, uint32_t sample_rate, vox_stream** out);
+/* A BURST stream ("Bursts"): a stream that runs a backlog's ticks in bursts of up to burst_ticks (1..VOX_STREAM_BURST_MAX; 1: exactly the stream
+ * the creators above make -- the same launches and allocations).  When one pass of a push / finish / peek has several ticks due (a chunked feed, a file, a session
+ * that fell behind or was restored with audio waiting), the encoder of b of them runs as ONE pass of 4 b rows -- every weight matrix read once, the ring attention
+ * in its burst form (vox_debug_stream_attn_burst) -- followed by the b decode steps, one by one as in a tick.  A burst is the smallest of the ticks still due, burst_ticks
+ * and the distance to the next position where the host acts between ticks (decoder cache growth, an endless session's wrap, list growth, the verification limit:
+ * vox_stream_burst_len); a burst of 1 is a plain tick, so a burst stream fed one tick per call has a plain stream's bits.  In a burst the row count selects other GEMM
+ * kernels than a tick's 4 rows do (as in a stream group): ids equal a plain stream's up to near-ties, and so depend on how the samples were cut, up to near-ties.
+ *   endless (0 / 1), dec_ring_rows: vox_stream_create_endless's (dec_ring_rows 0 unless endless); max_positions: a bounded stream's, ignored when endless.
+ *   enc_capacity_rows: 0 = max(window + 4 burst_ticks + 4, prefix rows) rounded up to 64 (832 rows at 16 for the 750 window); a given value must exceed window +
+ *   4 burst_ticks (VOX_ERR_INVALID before anything is allocated; the message names the bound).
+ * Scores, alternatives, taps, peek, reset, snapshot and restore work as on any stream (a blob does not know its ring capacity).  Not served: bursts in stream groups. */
+#define VOX_STREAM_BURST_MAX 16
+int32_t vox_stream_create_burst(vox_model* m, const float* t_embed, float gain, int32_t enc_capacity_rows, int32_t max_positions, uint32_t sample_rate, int32_t endless,
+                                int32_t dec_ring_rows, int32_t burst_ticks, vox_stream** out);
+/* burst_ticks of the stream (1: a plain stream), the bursts run with b >= 2 since create / reset / restore, the ticks inside them, the ticks run one by one (a peek's
+ * tail is not counted: the peek takes it back) */
+int32_t vox_stream_burst_info(const vox_stream* s, int64_t out[4]);
+/* host only, a pure function: the length of the next burst of a pass with `due` ticks still to run, at decoder position pos, of a stream with burst_ticks = burst, when
+ * next_stop is the nearest position above pos where the host must act between ticks: max(1, min(due, burst, next_stop - pos)).  A burst never spans next_stop. */
+int32_t vox_stream_burst_len(int64_t due, int32_t burst, int64_t pos, int64_t next_stop);
 /* samples host or device (mem_kind), ids host.  cap smaller than the ids the call will produce (known from the schedule before any work), a push after finish, a push
  * that would pass max_positions: VOX_ERR_INVALID BEFORE any state changes -- the call can be repeated. */
 int32_t vox_stream_push(vox_stream* s, const float* samples, size_t n, int32_t mem_kind, int32_t* out_ids, int32_t cap, int32_t* n_ids);

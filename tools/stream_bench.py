@@ -10,6 +10,7 @@
     python tools/stream_bench.py --group 1,4,16 --page-rows 256 [--out profiles/stream_group_paged_tick.txt]
     python tools/stream_bench.py --endless [--out profiles/stream_endless_tick.txt]
     python tools/stream_bench.py --snapshot [--out profiles/stream_snapshot.txt]
+    python tools/stream_bench.py --burst 1,4,16 [--out profiles/stream_burst.txt]
 
  * stream: HIP events on the context's stream around ONE push of `ticks` x 2560 samples (a large push is a loop of identical ticks), at encoder positions past the
    750-row window, median of `passes` passes; launches per tick from the library's launch counters plus the fixed launches of a tick; wall time of single 160 ms pushes
@@ -52,6 +53,12 @@
  * --snapshot: vox_stream_snapshot and vox_stream_restore of one endless solo session at three positions (about 300; past 1024; a few positions past the wrap of its
    decoder ring, i.e. past the decoder window), each with a device blob and with a host blob, and a device-to-device copy (vox_dev_copy) of the blob's byte count in
    the same run: HIP events on the context's stream around each call, median of `passes`; bytes, ms and GB/s of each.  Nothing else is measured in this mode.
+ * --burst B[,B...]: a BACKLOG of `ticks` (default 64) ticks pushed in ONE call, past the 750-row encoder window: a plain stream (vox_stream_create) and one burst stream
+   per B (vox_stream_create_burst; B = 1 runs the plain stream's code) are warmed alike and alternate pass by pass -- pass i of every stream covers the same positions,
+   the plain stream's first: HIP events around the one push from host memory (the default mode's method: its figure with --ticks 64 is the same measurement), median of
+   `passes`.  Per stream: the call's ms, ms per tick, the speed-up over the plain stream of the same run, the bursts and ticks from vox_stream_burst_info, the launches
+   per call from the library's counters (the burst attention has a counter of its own) plus the fixed launches, and how many of the timed ids equal the plain stream's.
+   Nothing else is measured in this mode.
  * derived figures are labelled as derived."""
 import argparse
 import ctypes as C
@@ -341,6 +348,44 @@ def bench_endless(pkg, ctx, m, t, tm, a, lines):
               f"ids of the timed passes: {int((idb == ide).sum())} of {len(idb)} equal (the bounded step fuses attention + wo where the model allows it, the ring step does not: equal bits are not promised there)"]
 
 
+def bench_burst(pkg, ctx, m, t, tm, a, bursts, lines):
+    """--burst: per pass one push of `ticks` ticks into the plain stream, then into every burst stream, all at the same positions."""
+    from importlib import import_module
+    gg = import_module(pkg.__name__ + ".gguf")
+    c = m.config; S = pkg.synth; warm = 200
+    n_ticks = warm + a.ticks * a.passes + 8
+    assert 38 + n_ticks < 1024, "every timed step stays on the decode engine's 1024-row cache"
+    x = S.synth_audio(n_ticks * 0.16 + 1.0, seed=4242); gain = float(np.float32(0.95) / np.float32(np.abs(x).max()))
+    streams = [("plain stream", m.create_stream(t, gain=gain))] + [(f"burst stream, B = {b}", m.create_stream(t, gain=gain, burst=b)) for b in bursts]
+    pos = 40 + 2560 * warm
+    for _, st in streams:
+        for a0 in range(0, pos, 2560):      # warmed tick by tick: every stream reaches the timed passes with the plain stream's bits
+            st.push(x[a0:min(pos, a0 + 2560)] if a0 else x[:2560])
+        assert st.info()["positions"] == 38 + warm and st.burst_info()["bursts"] == 0
+    ms = [[] for _ in streams]; ids = [[] for _ in streams]; counted = [0] * len(streams); battn = [0] * len(streams)
+    for _ in range(a.passes):
+        seg = x[pos:pos + 2560 * a.ticks]; pos += 2560 * a.ticks
+        for i, (_, st) in enumerate(streams):
+            k0 = launch_counts(pkg); b0 = gg.stream_attn_burst_launches()
+            ms[i].append(tm.ms(lambda: ids[i].append(st.push(seg))))
+            counted[i] += sum(launch_counts(pkg)) - sum(k0); battn[i] += gg.stream_attn_burst_launches() - b0
+    ref = np.concatenate(ids[0]); base = statistics.median(ms[0])
+    assert len(ref) == a.ticks * a.passes
+    for i, (name, st) in enumerate(streams):
+        bi = st.burst_info(); inf = st.info(); st.close()
+        assert inf["positions"] == 38 + warm + a.ticks * a.passes
+        med = statistics.median(ms[i]); got = np.concatenate(ids[i])
+        rounds = (bi["bursts"] + bi["single_ticks"] - (warm + 1)) / a.passes      # encoder passes per call: bursts + single ticks (the warm-up's warm + 1 ticks were single)
+        fixed = rounds * (1 + 2 * c.enc_layers + 1) + a.ticks * 2            # per encoder pass: stream_mel, two RMSNorms per layer, the final norm; per tick: stream_embed, stream_advance
+        lines += [f"{name}: {a.ticks}-tick backlog in one push (HIP events around the call): median {med:.3f} ms = {med / a.ticks:.3f} ms per tick  passes " + " ".join(f"{v:.3f}" for v in ms[i]) +
+                  (f"   plain / this = {base / med:.2f} x, per pass " + " ".join(f"{w / v:.2f}" for v, w in zip(ms[i], ms[0])) if i else ""),
+                  f"  per call: {bi['bursts'] / a.passes:.1f} bursts holding {bi['burst_ticks'] / a.passes:.1f} ticks, {(bi['single_ticks'] - warm - 1) / a.passes:.1f} single ticks; launches "
+                  f"{(counted[i] + battn[i]) / a.passes + fixed:.0f} = {counted[i] / a.passes:.0f} counted + {battn[i] / a.passes:.0f} burst attention + {fixed:.0f} uncounted (front end, norms, embed, advance)",
+                  f"  ids of the timed passes equal to the plain stream's: {int((got == ref).sum())} of {len(ref)}"]
+    lines.append(f"derived: 60 s of audio are 375 ticks: at the plain stream's {base / a.ticks:.3f} ms per tick {375 * base / a.ticks / 1e3:.2f} s" +
+                 "".join(f", at B = {b} {375 * statistics.median(ms[i + 1]) / a.ticks / 1e3:.2f} s" for i, b in enumerate(bursts)))
+
+
 def bench_snapshot(pkg, ctx, m, t, tm, a, lines):
     """--snapshot: vox_stream_snapshot / vox_stream_restore of one endless solo session at three positions (about 300, past 1024, past the decoder window), with a
     device blob and with a host blob, next to a device-to-device copy of the same byte count in the same run."""
@@ -393,8 +438,17 @@ def main():
     ap.add_argument("--endless", action="store_true", help="time the tick of an endless session past the wrap of its decoder ring next to a bounded session at the same positions (nothing else is measured)")
     ap.add_argument("--memory-past-window", action="store_true", help="with --page-rows R: what 16 members of an endless paged group and of a bounded paged group (max_positions 16384) hold past "
                     "the decoder window, from pool() and info() (a mode of its own: nothing is timed)")
+    ap.add_argument("--burst", help="B[,B...]: time a backlog of --ticks ticks (default 64 in this mode) pushed in one call into a plain stream and into burst streams of these burst_ticks, "
+                    "pass by pass in one run (nothing else is measured)")
     ap.add_argument("--snapshot", action="store_true", help="time vox_stream_snapshot / vox_stream_restore (device and host blobs) at three positions next to a device copy of the same size (nothing else is measured)")
     a = ap.parse_args()
+    bursts = [int(v) for v in a.burst.split(",")] if a.burst else []
+    if bursts and (a.group or a.endless or a.peek or a.scores or a.alternatives or a.page_rows or a.memory_past_window or a.snapshot):
+        ap.error("--burst is a mode of its own")
+    if any(not 1 <= b <= 16 for b in bursts):
+        ap.error("--burst takes burst_ticks 1..16")
+    if bursts and "--ticks" not in " ".join(sys.argv):
+        a.ticks = 64
     if a.snapshot and (a.group or a.endless or a.peek or a.scores or a.alternatives or a.page_rows or a.memory_past_window):
         ap.error("--snapshot is a mode of its own")
     if a.memory_past_window and (not a.page_rows or a.group or a.endless or a.peek or a.scores or a.alternatives):
@@ -434,6 +488,17 @@ def main():
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             open(a.out, "w").write(text)
+        return
+    if bursts:
+        lines = ["# " + " ".join(["python", "tools/stream_bench.py"] + sys.argv[1:]),
+                 f"# model {os.path.basename(path)}: {c.enc_layers} encoder layers, {c.dec_layers} decoder layers; a backlog of {a.ticks} ticks per call, {a.passes} passes, all past encoder position {4 * (37 + 200)}"]
+        bench_burst(pkg, ctx, m, t, tm, a, bursts, lines)
+        text = "\n".join(lines) + "\n"
+        print(text, end="")
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            open(a.out, "w").write(text)
+        m.close(); ctx.close()
         return
     if a.snapshot:
         lines = ["# " + " ".join(["python", "tools/stream_bench.py"] + sys.argv[1:]),

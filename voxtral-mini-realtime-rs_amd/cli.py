@@ -110,7 +110,7 @@ def write_words(out, pkg, path, ids, scores, tokenizer, rate, alternatives=None)
     out.flush()
 
 
-def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_rate=False, words_out=None, peek=False, alts_k=0, endless=False, suspend_every=0):
+def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_rate=False, words_out=None, peek=False, alts_k=0, endless=False, suspend_every=0, burst=0):
     """--live: the file through a live session (vox_stream) in pieces of `chunk_ms` milliseconds, the text so far on stderr whenever ids arrive.  The gain is the
     file's peak scale 0.95 / max|x| (bin/transcribe.rs:207; a file is known in advance -- a microphone caller passes its own), the whole file is one utterance (no
     --max-mel-frames chunks: the session's state is bounded by its ring), so the line equals the un-chunked path's.
@@ -123,7 +123,9 @@ def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_
     (vox_stream_peek: finish's ticks, taken back); the session, hence everything else, is as without the flag.
     endless (--live-endless): the session is an endless one (vox_stream_create_endless: no 43-minute limit, the decoder cache a ring); the line is the same.
     suspend_every (--live-suspend-every N): after every N pushes the session is snapshotted to host memory (vox_stream_snapshot), the stream is freed, and a fresh one
-    is restored from the blob (vox_stream_restore) -- what a server does with a caller on hold; the line is the same."""
+    is restored from the blob (vox_stream_restore) -- what a server does with a caller on hold; the line is the same.
+    burst (--live-burst B): the session is a burst stream (vox_stream_create_burst): a chunk longer than a tick runs its ticks in bursts of up to B; the line is the
+    same up to near-ties, and depends on --live-chunk-ms up to near-ties."""
     x, sr = load_wav(path)
     rate = 16000
     if sr != 16000:
@@ -139,7 +141,7 @@ def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_
     gain = float(np.float32(0.95) / peak) if peak >= 1e-10 else 1.0              # audio/io.rs:59-68
     step = max(1, int(round(rate * chunk_ms / 1000.0)))
     def create():
-        st = model.create_stream(t_embed, gain=gain, sample_rate=rate, endless=endless)
+        st = model.create_stream(t_embed, gain=gain, sample_rate=rate, endless=endless, burst=burst or None)
         if words_out is not None:
             st.set_scores(True)
             if alts_k:
@@ -379,6 +381,8 @@ def main(argv=None):
     ap.add_argument("--live-kv", choices=("f32", "bf16"), default=None, help="with --live-group: what the group's decoder K/V pool holds (vox_stream_group_create_kv; makes the "
                     "group a paged one).  bf16: 16-bit pages, half the memory per page and half the bytes the decode attention reads; the text may differ from an f32 group's "
                     "where the model's choice between two tokens is close")
+    ap.add_argument("--live-burst", type=int, default=0, metavar="B", help="with --live: a burst stream (vox_stream_create_burst) -- a chunk that makes several ticks due (--live-chunk-ms "
+                    "above 160) runs them in bursts of up to B (1..16): one encoder pass for the burst, then its decode steps")
     ap.add_argument("--live-endless", action="store_true", help="with --live: an endless session (vox_stream_create_endless) -- no limit at "
                     "16 384 decoder positions (about 43 minutes); the decoder cache is a ring of a little more than one window and stops growing there.  With --live-group: "
                     "an endless paged group (vox_stream_group_create_endless; --live-page-rows / --live-pool-pages apply), no member refused at 43 minutes; same lines")
@@ -437,6 +441,10 @@ def main(argv=None):
         ap.error("--live runs one file at a time on one GPU (no --gpus / --batch) with --live-chunk-ms > 0")
     if a.live_endless and not a.live:
         ap.error("--live-endless applies with --live")
+    if a.live_burst and (not a.live or a.live_group):
+        ap.error("--live-burst applies with --live (a solo session; stream groups run no bursts)")
+    if a.live_burst and not 1 <= a.live_burst <= 16:
+        ap.error("--live-burst takes 1..16")
     if a.live_native_rate and not a.live:
         ap.error("--live-native-rate applies with --live")
     if a.live and not a.gguf:
@@ -539,7 +547,7 @@ def main(argv=None):
         p = paths[i]
         try:
             t1 = time.time()
-            text = transcribe_live(pkg, p, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_native_rate, words_out, a.live_peek, a.live_alternatives, a.live_endless, a.live_suspend_every) if a.live else transcribe_one(pkg, p, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed, rec_out, a.alternatives or 0)
+            text = transcribe_live(pkg, p, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_native_rate, words_out, a.live_peek, a.live_alternatives, a.live_endless, a.live_suspend_every, a.live_burst) if a.live else transcribe_one(pkg, p, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed, rec_out, a.alternatives or 0)
             log(f"{p}: {time.time() - t1:.3f}s")
         except Exception as e:      # per-utterance failure isolates to that line (empty), eval_wer.py:211-223 tolerates it
             log(f"Error transcribing {p}: {e}"); text = ""; rc = 1

@@ -1330,10 +1330,12 @@ extern "C" int32_t vox_debug_attn_decode_paged_bf16(vox_ctx* c, const vox_attn_d
 // RoPE rows come from rope_rows_fill with vox_debug_rope_rows' table length, so a test holds the identical f32 rows; in the ring modes only the rows the served members'
 // positions need are written, every other ring row is NaN.  Every argument is checked before the context is bound: what launch_stream_attn refuses never reaches it, and
 // nothing the kernel reads or writes lies outside the uploaded buffers (order against n_members, the positions against the table or 2^24, the ring offset against layers).
-extern "C" int32_t vox_debug_stream_attn(vox_ctx* c, const vox_stream_attn_desc* d, const float* qkv, float* kring, float* vring, float* out) {
+// burst: vox_debug_stream_attn_burst -- rows up to 64, and the ONE launch is launch_stream_attn_burst
+static int32_t stream_attn_debug(vox_ctx* c, const vox_stream_attn_desc* d, const float* qkv, float* kring, float* vring, float* out, bool burst) {
     ARGCHK(c && d && qkv && kring && vring && out, "null argument"); ARGCHK(d->order && d->enc_pos, "null argument (order, enc_pos)");
     ARGCHK(d->head_dim == 64 || d->head_dim == 128, "head_dim %d: the ring attention serves head_dim 64 and 128", d->head_dim);
-    ARGCHK(d->rows >= 1 && d->rows <= 8, "rows %d out of range (1..8)", d->rows);
+    const int max_rows = burst ? 64 : 8;
+    ARGCHK(d->rows >= 1 && d->rows <= max_rows, "rows %d out of range (1..%d)", d->rows, max_rows);
     ARGCHK(d->n_slots >= 1 && d->n_slots <= 16, "n_slots %d out of range (1..16)", d->n_slots);
     ARGCHK(d->n_members >= d->n_slots && d->n_members <= 64, "n_members %d out of range (n_slots = %d .. 64)", d->n_members, d->n_slots);
     ARGCHK(d->n_heads >= 1 && d->n_heads <= 32, "n_heads %d out of range (1..32)", d->n_heads);
@@ -1394,10 +1396,22 @@ extern "C" int32_t vox_debug_stream_attn(vox_ctx* c, const vox_stream_attn_desc*
     StreamAttnParams ap{}; ap.qkv = dqkv.as<float>(); ap.qkv_stride = 3 * QD; ap.mem = dmem.as<StreamMember>(); ap.order = d_order; ap.n = n; ap.ring_off = (size_t)d->layer * layer_f; ap.cap = d->cap;
     ap.cos_t = drope.as<float>(); ap.sin_t = drope.as<float>() + sin_at; ap.out = dout.as<float>(); ap.out_stride = QD; ap.M = M; ap.n_heads = H; ap.window = d->window;
     ap.rope_mask = R ? R - 1 : 0; ap.rope_stride = per_member ? R : 0;
-    HIPCHK(launch_stream_attn(ap, hd, s));
+    HIPCHK(burst ? launch_stream_attn_burst(ap, hd, s) : launch_stream_attn(ap, hd, s));
     HIPCHK(hipMemcpyAsync(out, dout.p, out_f * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(kring, dk.p, ring_f * 4, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(vring, dv.p, ring_f * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
+    return VOX_OK;
+}
+extern "C" int32_t vox_debug_stream_attn(vox_ctx* c, const vox_stream_attn_desc* d, const float* qkv, float* kring, float* vring, float* out) {
+    return stream_attn_debug(c, d, qkv, kring, vring, out, false);
+}
+// the burst form of the same attention (a burst stream's encoder layers, b >= 2): vox_debug_stream_attn's arguments and checks with rows 1..64, ONE launch_stream_attn_burst
+extern "C" int32_t vox_debug_stream_attn_burst(vox_ctx* c, const vox_stream_attn_desc* d, const float* qkv, float* kring, float* vring, float* out) {
+    return stream_attn_debug(c, d, qkv, kring, vring, out, true);
+}
+extern "C" int32_t vox_debug_stream_attn_burst_launches(uint64_t* out) {
+    ARGCHK(out, "null argument");
+    *out = (uint64_t)stream_attn_burst_launches();
     return VOX_OK;
 }
 // the seeding of a session's rings from the prefix state on host buffers (tests): ONE launch_stream_ring_init into the caller's rings
@@ -3135,6 +3149,9 @@ struct vox_stream {
     // (tokens, score and alternatives records) start at lists_cap positions and grow by doubling at a verification point.  rope: the session's two device RoPE rings
     // ([rows][cos hd/2 | sin hd/2], rows a power of two), their pinned host images, and the event behind the last copy out of those images.
     bool endless = false; int ring_rows = 0, dec_limit = 0, lists_cap = 0;
+    // A BURST stream (vox_stream_create_burst; DESIGN.md section 8, "Bursts"): up to `burst` due ticks of a pass run as one encoder pass of 4 b rows and b decode steps
+    // (stream_burst); 1: every tick is stream_tick.  bursts / burst_ticks: the bursts run with b >= 2 and the ticks inside them; single_ticks: the ticks run one by one
+    int burst = 1; uint64_t bursts = 0, burst_ticks = 0, single_ticks = 0;
     struct { float *dec = nullptr, *enc = nullptr, *h_dec = nullptr, *h_enc = nullptr; hipEvent_t copied = nullptr; bool pending = false; } rope;
 };
 static const int STREAM_TAIL_TICKS = 63;            // the most ticks a finish / peek tail of an endless session may run (peek_max_ticks at the session's rate, asserted at create and in every peek)
@@ -3145,9 +3162,11 @@ static bool stream_in_ring(const vox_stream* st) { return st->endless && st->fee
 // the buffers of a round of up to n sessions (n = 1: a solo stream's tick), carved from one allocation; returns its size in floats (base may be null).
 // A slot's mel halo is padded from 4 R + 3 to 4 R + 4 frames and its conv1 block from 2 R + 1 to 2 R + 2 rows, so that slots lie a whole number of window strides
 // apart and each conv is ONE im2col GEMM over all slots (stream_encode_round); h: the decode step's input rows.
+// b > 1 (a solo burst stream, n = 1): the buffers of b ticks in one pass -- 16 b + 3 halo frames, 8 b + 1 and 4 b conv rows, 4 b encoder rows, b adapter rows --
+// which the sizes of a round of b slots cover
 struct StreamWs { float *halo, *c1, *c2, *x, *xn, *qkv, *att, *ffn, *ah, *arow, *h; };
-static size_t stream_ws_carve(const vox_model* m, int n, float* base, StreamWs* w) {
-    const vox_model_cfg& c = m->cfg; const size_t R = (size_t)c.reshape_factor, D = (size_t)c.enc_dim, QD = (size_t)c.enc_heads * c.enc_head_dim, N = (size_t)n;
+static size_t stream_ws_carve(const vox_model* m, int n, float* base, StreamWs* w, int b = 1) {
+    const vox_model_cfg& c = m->cfg; const size_t R = (size_t)c.reshape_factor, D = (size_t)c.enc_dim, QD = (size_t)c.enc_heads * c.enc_head_dim, N = (size_t)n * (size_t)b;
     StreamWs t; if (!w) w = &t;
     size_t o = 0; auto take = [&](float*& q, size_t k) { q = base ? base + o : nullptr; o += (k + 63) / 64 * 64; };      // (256-byte pieces)
     take(w->halo, N * (4 * R + 4) * c.n_mels); take(w->c1, N * (2 * R + 2) * D); take(w->c2, N * (R + 1) * D); take(w->x, N * R * D); take(w->xn, N * R * D);
@@ -3220,6 +3239,7 @@ static int32_t stream_load_initial(vox_stream* st) {
                        [&]() -> int32_t { HIPCHK(engine_tab_enqueue(m, st->eng, st->dec)); return VOX_OK; }));
     st->feed.restart(st->PC); st->verified_pos = st->PC; st->eng_unverified = false;
     st->eng_steps = st->op_steps = st->verified_eng_steps = st->verified_op_steps = 0; st->tap_rows = st->verified_tap_rows = 0; st->ftap_ticks = 0;
+    st->bursts = st->burst_ticks = st->single_ticks = 0;
     st->sc.host.clear(); st->al.restart();      // the utterance's records start over; the flag and k stay
     return VOX_OK;
 }
@@ -3239,14 +3259,16 @@ static void stream_release(vox_stream* st) {
 
 // what create checks about the model and the two sizes, for a solo stream and for a group: the prefix bounds, the ring capacity, the position limit
 struct StreamGeom { int RC = 0, PC = 0, cap = 0, max_pos = 0; long left = 0; };
-static int32_t stream_geometry(vox_model* m, int32_t enc_capacity_rows, int32_t max_positions, int default_positions, StreamGeom* g) {
+// burst: a solo stream's burst_ticks B (1: none) -- a burst appends 4 B rows in one launch, the ring holds window + 4 B rows and more
+static int32_t stream_geometry(vox_model* m, int32_t enc_capacity_rows, int32_t max_positions, int default_positions, StreamGeom* g, int burst = 1) {
     const vox_model_cfg& c = m->cfg;
     if (!m->is_q4) return fail(VOX_ERR_UNSUPPORTED, "live streaming sessions serve Q4 (GGUF) models");
     int RC, PC; prefix_bounds(m, &RC, &PC);
     ARGCHK(RC > 0 && c.reshape_factor == 4 && PC == VOX_PREFIX_TOKENS - 1, "this model geometry has no prefix state for a stream to start from");
     if (!m->conv1_g.qs || !m->conv2_g.qs) return fail(VOX_ERR_UNSUPPORTED, "the stream's conv stem runs as im2col GEMMs: 3 n_mels and 3 enc_dim must be multiples of 128");
     ARGCHK(c.enc_window + 1 <= 1024, "encoder window %d exceeds the stream attention's 1023 keys", c.enc_window);
-    int cap = enc_capacity_rows; if (cap == 0) cap = (std::max(c.enc_window + 8, RC) + 63) / 64 * 64;      // a ring needs no slack: anything above window + 4 is exact
+    int cap = enc_capacity_rows; if (cap == 0) cap = (std::max(c.enc_window + 4 * burst + 4, RC) + 63) / 64 * 64;      // a ring needs no slack: anything above window + 4 is exact
+    if (burst > 1) ARGCHK(cap > c.enc_window + 4 * burst, "encoder ring capacity %d must exceed the sliding window + 4 burst_ticks (%d + 4 x %d = %d)", cap, c.enc_window, burst, c.enc_window + 4 * burst);
     ARGCHK(cap > c.enc_window + 4 && cap >= RC, "encoder ring capacity %d must exceed the sliding window + 4 (%d)", cap, c.enc_window + 4);
     const int pos_limit = std::min(m->dec_rope_len, (1 << 16) / c.reshape_factor);      // the decoder RoPE table and the 65 536-position streaming encoder table end together
     int maxp = max_positions; if (maxp == 0) maxp = std::min(pos_limit, default_positions);
@@ -3258,13 +3280,14 @@ static int32_t stream_geometry(vox_model* m, int32_t enc_capacity_rows, int32_t 
 // sample_rate 16000: the 16 kHz stream, nothing more; any other rate: + the input ring and the stream's own block matrix
 // endless: max_positions is ignored (the limit is 2^24); dec_ring_rows: the decoder ring's rows (0: the default), checked here
 static int32_t stream_create(vox_model* m, const float* t_embed, float gain, int32_t enc_capacity_rows, int32_t max_positions, uint32_t sample_rate, vox_stream** out,
-                             bool endless = false, int32_t dec_ring_rows = 0) {
+                             bool endless = false, int32_t dec_ring_rows = 0, int32_t burst = 1) {
     ARGCHK(m && t_embed && out, "null argument"); ARGCHK(std::isfinite(gain), "gain is not finite"); ARGCHK(sample_rate > 0, "bad sample rate 0");
+    ARGCHK(burst >= 1 && burst <= VOX_STREAM_BURST_MAX, "burst_ticks %d out of range (1..%d)", burst, VOX_STREAM_BURST_MAX);
     VOXCHK(ctx_bind(m->ctx));
     ResamplePlan rp; size_t rs_bytes = 0; int in_ring_n = 0;
     if (sample_rate != 16000) VOXCHK(stream_rate_plan(sample_rate, &rp, &rs_bytes, &in_ring_n));
     const vox_model_cfg& c = m->cfg; vox_ctx* cx = m->ctx;
-    StreamGeom g; VOXCHK(stream_geometry(m, enc_capacity_rows, endless ? 0 : max_positions, INT32_MAX, &g));
+    StreamGeom g; VOXCHK(stream_geometry(m, enc_capacity_rows, endless ? 0 : max_positions, INT32_MAX, &g, burst));
     int ring_rows = 0;
     if (endless) {
         // the ring holds a window, the position itself and the rows a finish / peek tail may overwrite ahead of the session: window + 1 + TAIL.  TAIL bounds
@@ -3283,10 +3306,10 @@ static int32_t stream_create(vox_model* m, const float* t_embed, float gain, int
     vox_stream* st = new vox_stream(); st->m = m; st->ctx = cx; st->t_embed.assign(t_embed, t_embed + c.dec_dim); st->gain = gain; st->cap = g.cap; st->max_pos = g.max_pos; st->RC = g.RC; st->PC = g.PC;
     st->feed.sr = sample_rate; st->feed.rp = rp; st->feed.in_ring_n = in_ring_n; st->left = g.left;
     st->endless = endless; st->ring_rows = ring_rows; st->dec_limit = endless ? ring_rows : g.max_pos; if (endless) st->max_pos = STREAM_POS_LIMIT;
-    st->lists_cap = endless ? ring_rows : g.max_pos;
+    st->lists_cap = endless ? ring_rows : g.max_pos; st->burst = burst;
     const int DD = c.dec_dim, maxp = st->lists_cap;
     st->ring_layer = (size_t)c.enc_heads * g.cap * c.enc_head_dim;
-    const size_t ring_b = (size_t)c.enc_layers * st->ring_layer * 4, keep_b = (size_t)STREAM_KEEP_ROWS * DD * 4, ws_b = stream_ws_carve(m, 1, nullptr, nullptr) * 4;
+    const size_t ring_b = (size_t)c.enc_layers * st->ring_layer * 4, keep_b = (size_t)STREAM_KEEP_ROWS * DD * 4, ws_b = stream_ws_carve(m, 1, nullptr, nullptr, burst) * 4;
     hipError_t e = hipSuccess;
     auto A = [&](void** q, size_t n) { if (e == hipSuccess) { e = hipMalloc(q, n); if (e == hipSuccess) st->bytes += n; } };
     A((void**)&st->kring, ring_b); A((void**)&st->vring, ring_b); A((void**)&st->samples, (size_t)STREAM_SAMPLE_RING * 4); A((void**)&st->audio_keep, keep_b);
@@ -3323,6 +3346,18 @@ extern "C" int32_t vox_stream_create_rate(vox_model* m, const float* t_embed, fl
 extern "C" int32_t vox_stream_create_endless(vox_model* m, const float* t_embed, float gain, int32_t enc_capacity_rows, int32_t dec_ring_rows, uint32_t sample_rate, vox_stream** out) {
     ARGCHK(m && t_embed && out, "null argument"); ARGCHK(sample_rate > 0, "bad sample rate 0"); ARGCHK(dec_ring_rows >= 0, "dec_ring_rows %d (0: the default)", dec_ring_rows);
     return stream_create(m, t_embed, gain, enc_capacity_rows, 0, sample_rate, out, true, dec_ring_rows);
+}
+extern "C" int32_t vox_stream_create_burst(vox_model* m, const float* t_embed, float gain, int32_t enc_capacity_rows, int32_t max_positions, uint32_t sample_rate, int32_t endless,
+                                           int32_t dec_ring_rows, int32_t burst_ticks, vox_stream** out) {
+    ARGCHK(m && t_embed && out, "null argument"); ARGCHK(sample_rate > 0, "bad sample rate 0"); ARGCHK(endless == 0 || endless == 1, "endless must be 0 or 1");
+    ARGCHK(burst_ticks >= 1 && burst_ticks <= VOX_STREAM_BURST_MAX, "burst_ticks %d out of range (1..%d)", burst_ticks, VOX_STREAM_BURST_MAX);
+    ARGCHK(dec_ring_rows >= 0 && (endless || dec_ring_rows == 0), "dec_ring_rows %d (0: the default; an endless session's alone)", dec_ring_rows);
+    return stream_create(m, t_embed, gain, enc_capacity_rows, endless ? 0 : max_positions, sample_rate, out, endless != 0, dec_ring_rows, burst_ticks);
+}
+extern "C" int32_t vox_stream_burst_info(const vox_stream* st, int64_t out[4]) {
+    ARGCHK(st && out, "null argument");
+    out[0] = st->burst; out[1] = (int64_t)st->bursts; out[2] = (int64_t)st->burst_ticks; out[3] = (int64_t)st->single_ticks;
+    return VOX_OK;
 }
 extern "C" int32_t vox_stream_free(vox_stream* st) { stream_release(st); return VOX_OK; }
 extern "C" int32_t vox_stream_reset(vox_stream* st) {
@@ -3417,10 +3452,14 @@ static int32_t stream_verify(vox_stream* st) {      // inside a long push: befor
 // count).  Slot z works for session r.order[z] (device arrays); w.arow[z] is its adapter row.  ftap_*: a solo stream's front tap (null: none).
 // rope (null: the model's streaming table): a solo endless session's encoder RoPE ring, rows = position & rope_mask (StreamAttnParams::rope_mask)
 struct StreamRound { const StreamMember* mem; const int* order; int n, cap; size_t ring_layer; MelTables mel; long left; const float* rope = nullptr; int rope_mask = 0, rope_stride = 0; };      // rope_stride > 0: an endless group's rings, one per member
-static int32_t stream_encode_round(vox_model* m, const StreamWs& w, const StreamRound& r, float* ftap_mel, float* ftap_conv) {
+// b > 1 (a solo burst stream's round of one, n == 1): the encoder of b ticks in one pass.  Everything the b ticks would read is there before the first (the pass's
+// samples, the state block at the burst's first tick), and tick t's rows are rows 4 t .. of every buffer: 16 b + 3 halo frames, 8 b + 1 and 4 b conv windows, 4 b rows
+// through the layers with the burst attention, b adapter rows (w.arow[t]: tick t's).  ftap_*: room for ftap_b of the burst's ticks, in the per-tick layout.
+static int32_t stream_encode_round(vox_model* m, const StreamWs& w, const StreamRound& r, float* ftap_mel, float* ftap_conv, int b = 1, int ftap_b = 1) {
     const vox_model_cfg& c = m->cfg; vox_ctx* cx = m->ctx; hipStream_t s = cx->stream;
-    const int D = c.enc_dim, H = c.enc_heads, hd = c.enc_head_dim, QD = H * hd, F = c.enc_ffn, R = c.reshape_factor, DD = c.dec_dim, Cm = c.n_mels, n = r.n, M = R * n;
-    const int NF = 4 * R + 3, HS = NF + 1, C1S = 2 * R + 2, C2S = R + 1;      // mel frames with the halo (conv row s reads frames 4 s - 3 .. 4 s + 3); the slot strides in frames, conv1 rows, conv rows
+    ARGCHK(b >= 1 && b <= VOX_STREAM_BURST_MAX && (b == 1 || r.n == 1), "internal: a burst of %d ticks in a round of %d", b, r.n);
+    const int D = c.enc_dim, H = c.enc_heads, hd = c.enc_head_dim, QD = H * hd, F = c.enc_ffn, R = c.reshape_factor, DD = c.dec_dim, Cm = c.n_mels, n = r.n, M = R * n * b;
+    const int NF = 4 * R * b + 3, HS = NF + 1, C1S = 2 * R * b + 2, C2S = R * b + 1;      // mel frames with the halo (conv row s reads frames 4 s - 3 .. 4 s + 3); the slot strides in frames, conv1 rows, conv rows
     HIPCHK(launch_stream_mel(r.mem, r.order, n, STREAM_SAMPLE_RING - 1, r.left, r.mel, 3, NF, w.halo, (long)HS * Cm, s));
     // conv stem without padding rows, memsets or a transpose: conv1 row i of a slot is the window of its halo rows [2 i, 2 i + 2], conv row i the window of its conv1 rows
     // [2 i, 2 i + 2].  The slots lie C1S / C2S windows apart, so one GEMM per conv serves them all; its last window of every slot but the last straddles two slots: that
@@ -3430,8 +3469,8 @@ static int32_t stream_encode_round(vox_model* m, const StreamWs& w, const Stream
     { GemmParams g{}; g.w = m->conv2_g; g.x = w.c1; g.x_stride = 2 * D; g.M = C2S * n - 1; g.out = conv; g.out_stride = D; g.bias = m->conv2_b; HIPCHK(launch_dense2_gemm(g, EPI_GELU, s)); }
     if (n > 1) HIPCHK(hipMemcpy2DAsync(w.x, (size_t)R * D * 4, w.c2, (size_t)C2S * D * 4, (size_t)R * D * 4, n, hipMemcpyDeviceToDevice, s));
     if (ftap_mel) {      // the front tap (tests): the tick's fresh frames (halo rows 3 ..) and conv rows, copied on the stream
-        HIPCHK(hipMemcpyAsync(ftap_mel, w.halo + (size_t)3 * Cm, (size_t)4 * R * Cm * 4, hipMemcpyDeviceToDevice, s));
-        HIPCHK(hipMemcpyAsync(ftap_conv, w.x, (size_t)R * D * 4, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(ftap_mel, w.halo + (size_t)3 * Cm, (size_t)ftap_b * 4 * R * Cm * 4, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(ftap_conv, w.x, (size_t)ftap_b * R * D * 4, hipMemcpyDeviceToDevice, s));
     }
     float *x = w.x, *xn = w.xn;
     for (int l = 0; l < c.enc_layers; l++) {
@@ -3440,16 +3479,16 @@ static int32_t stream_encode_round(vox_model* m, const StreamWs& w, const Stream
         VOXCHK(q4_linear_dev(cx, L.wqkv.w, L.wqkv.bias, xn, D, M, w.qkv, 3 * QD));
         StreamAttnParams ap{}; ap.qkv = w.qkv; ap.qkv_stride = 3 * QD; ap.mem = r.mem; ap.order = r.order; ap.n = n; ap.ring_off = (size_t)l * r.ring_layer; ap.cap = r.cap;
         ap.cos_t = m->enc_cos_s; ap.sin_t = m->enc_sin_s; ap.out = w.att;
-        if (r.rope) { ap.cos_t = r.rope; ap.sin_t = r.rope + hd / 2; ap.rope_mask = r.rope_mask; ap.rope_stride = r.rope_stride; } ap.out_stride = QD; ap.M = R; ap.n_heads = H; ap.window = c.enc_window;
-        HIPCHK(launch_stream_attn(ap, hd, s));
+        if (r.rope) { ap.cos_t = r.rope; ap.sin_t = r.rope + hd / 2; ap.rope_mask = r.rope_mask; ap.rope_stride = r.rope_stride; } ap.out_stride = QD; ap.M = R * b; ap.n_heads = H; ap.window = c.enc_window;
+        HIPCHK(b >= 2 ? launch_stream_attn_burst(ap, hd, s) : launch_stream_attn(ap, hd, s));
         VOXCHK(q4_linear_dev(cx, L.wo.w, L.wo.bias, w.att, QD, M, x, D, EPI_RESID, x, D));
         HIPCHK(launch_rms_norm(x, D, M, D, L.ffn_norm, nullptr, c.norm_eps, xn, D, s));
         VOXCHK(q4_linear_dev(cx, L.w13.w, nullptr, xn, D, M, w.ffn, F, EPI_SWIGLU));
         VOXCHK(q4_linear_dev(cx, L.w2.w, L.w2.bias, w.ffn, F, M, x, D, EPI_RESID, x, D));
     }
     HIPCHK(launch_rms_norm(x, D, M, D, m->enc_norm, nullptr, c.norm_eps, xn, D, s));
-    VOXCHK(q4_linear_dev(cx, m->ad0.w, nullptr, xn, D * R, n, w.ah, m->ad0.w.N, EPI_GELU));      // a slot's R rows viewed as one [R D] row (models/adapter.rs:108-122)
-    VOXCHK(q4_linear_dev(cx, m->ad2.w, nullptr, w.ah, m->ad0.w.N, n, w.arow, DD));
+    VOXCHK(q4_linear_dev(cx, m->ad0.w, nullptr, xn, D * R, n * b, w.ah, m->ad0.w.N, EPI_GELU));      // a slot's R rows viewed as one [R D] row (models/adapter.rs:108-122)
+    VOXCHK(q4_linear_dev(cx, m->ad2.w, nullptr, w.ah, m->ad0.w.N, n * b, w.arow, DD));
     return VOX_OK;
 }
 
@@ -3499,12 +3538,27 @@ static int32_t stream_rope_refill(vox_stream* st, int pos0, int n) {
 }
 
 // a solo stream's tick: the round of one, then its own decode half -- the engine launch or the per-operator step, with the kept adapter rows behind the re-run
-static int32_t stream_tick(vox_stream* st) {
-    vox_model* m = st->m; const vox_model_cfg& c = m->cfg; hipStream_t s = st->ctx->stream; const int R = c.reshape_factor;
+// what the host does in front of the tick at the session's position, where that position asks for it: a verification, the decoder cache's growth, the lists' growth
+static int32_t stream_tick_prepare(vox_stream* st) {
     if (st->feed.pos - st->verified_pos >= STREAM_KEEP_ROWS) VOXCHK(stream_verify(st));      // the kept adapter rows cover the unverified steps
     const bool ring = stream_in_ring(st);      // from the wrap on the cache stays as it is: position p lives at row p % ring_rows
     if (!ring && st->feed.pos >= st->dec->max_seq) { VOXCHK(stream_verify(st)); VOXCHK(stream_dec_grow(st, st->peek.active ? &st->peek.old : nullptr)); }
     if (st->endless && st->feed.pos >= st->lists_cap) VOXCHK(stream_lists_grow(st));      // (a bounded session's lists hold its max_pos positions)
+    return VOX_OK;
+}
+// behind stream_tick_prepare: the nearest position above the session's at whose tick the host acts again (or where the encoder's RoPE source changes) -- no burst spans it
+static int64_t stream_next_stop(const vox_stream* st) {
+    const int pos = st->feed.pos;
+    int64_t stop = (int64_t)st->verified_pos + STREAM_KEEP_ROWS;      // the verification limit
+    if (!stream_in_ring(st)) stop = std::min<int64_t>(stop, st->dec->max_seq);      // the decoder cache's growth
+    if (st->endless && pos < st->ring_rows) stop = std::min<int64_t>(stop, st->ring_rows);      // the wrap into the ring
+    if (st->endless) stop = std::min<int64_t>(stop, st->lists_cap);      // the lists' growth
+    return stop;
+}
+static int32_t stream_tick(vox_stream* st) {
+    vox_model* m = st->m; const vox_model_cfg& c = m->cfg; hipStream_t s = st->ctx->stream; const int R = c.reshape_factor;
+    VOXCHK(stream_tick_prepare(st));
+    const bool ring = stream_in_ring(st);
     StreamWs w; stream_ws_carve(m, 1, st->ws, &w);
     StreamRound r{st->d_mem, st->d_order, 1, st->cap, st->ring_layer, st->mel, st->left};
     if (ring) { r.rope = st->rope.enc; r.rope_mask = STREAM_ROPE_DEC_ROWS * R - 1; }
@@ -3512,6 +3566,26 @@ static int32_t stream_tick(vox_stream* st) {
     VOXCHK(stream_encode_round(m, w, r, ftap ? st->ftap_mel + (size_t)k * 4 * R * c.n_mels : nullptr, ftap ? st->ftap_conv + (size_t)k * R * c.enc_dim : nullptr));
     HIPCHK(launch_stream_embed(m->tok.w, st->tokens, w.arow, st->audio_keep, STREAM_KEEP_ROWS, c.dec_dim, st->state, w.h, s));
     return stream_decode_step(st, w.h, stream_tap_row(st), R);
+}
+// a burst: b >= 2 ticks of a burst stream's pass as ONE encoder pass of R b rows, then the b decode steps of stream_tick, one by one -- the kept adapter rows, the
+// tap rows, the records and the engine's verification are per step, as in a tick.  The caller ran stream_tick_prepare and cut b by stream_burst_len: no position of
+// the burst asks for the host.  The encoder reads the state block as the burst's first tick finds it; the b advance launches leave it as b ticks would.
+static int32_t stream_burst(vox_stream* st, int b) {
+    vox_model* m = st->m; const vox_model_cfg& c = m->cfg; hipStream_t s = st->ctx->stream; const int R = c.reshape_factor;
+    ARGCHK(b >= 2 && b <= st->burst && st->feed.pos + b <= stream_next_stop(st), "internal: a burst of %d ticks at position %d (burst_ticks %d, next stop %lld)", b, st->feed.pos, st->burst, (long long)stream_next_stop(st));
+    const bool ring = stream_in_ring(st);
+    StreamWs w; stream_ws_carve(m, 1, st->ws, &w, st->burst);
+    StreamRound r{st->d_mem, st->d_order, 1, st->cap, st->ring_layer, st->mel, st->left};
+    if (ring) { r.rope = st->rope.enc; r.rope_mask = STREAM_ROPE_DEC_ROWS * R - 1; }
+    const int k = st->ftap_ticks, fb = st->ftap_mel ? std::max(0, std::min(b, st->ftap_max - k)) : 0;      // the burst's ticks the front tap still has room for
+    if (st->ftap_mel) st->ftap_ticks += b;
+    VOXCHK(stream_encode_round(m, w, r, fb ? st->ftap_mel + (size_t)k * 4 * R * c.n_mels : nullptr, fb ? st->ftap_conv + (size_t)k * R * c.enc_dim : nullptr, b, fb));
+    for (int t = 0; t < b; t++) {
+        HIPCHK(launch_stream_embed(m->tok.w, st->tokens, w.arow + (size_t)t * c.dec_dim, st->audio_keep, STREAM_KEEP_ROWS, c.dec_dim, st->state, w.h, s));
+        VOXCHK(stream_decode_step(st, w.h, stream_tap_row(st), R));
+    }
+    st->bursts++; st->burst_ticks += (uint64_t)b;
+    return VOX_OK;
 }
 
 // what a call appends: f32 or 16-bit samples in host or device memory; p null: zeros (the right pad)
@@ -3586,7 +3660,12 @@ static int32_t stream_run(vox_stream* st, const StreamSrc& src, FeedPlan& plan, 
                                                 (long)q.i0, (int)q.n16, s));
         VOXCHK(ring_write_f32(s, st->samples, STREAM_SAMPLE_RING, q.pad_w0, StreamSrc{}, 0, q.pad));
         if (st->endless && q.ticks > 0 && f.pos + q.ticks > st->ring_rows) VOXCHK(stream_rope_refill(st, f.pos, q.ticks));      // the pass reaches the ring: its RoPE rows first
-        for (int t = 0; t < q.ticks; t++) VOXCHK(stream_tick(st));
+        for (int t = 0; t < q.ticks;) {      // a burst stream: the pass's ticks in bursts, cut where the host must act between ticks; a burst of 1 is a tick
+            int b = 1;
+            if (st->burst > 1 && q.ticks - t > 1) { VOXCHK(stream_tick_prepare(st)); b = stream_burst_len(q.ticks - t, st->burst, f.pos, stream_next_stop(st)); }
+            if (b >= 2) VOXCHK(stream_burst(st, b)); else { VOXCHK(stream_tick(st)); st->single_ticks++; }
+            t += b;
+        }
     }
     SessionOut o{&f, &st->sc, &st->al, st->tokens, out_ids, due, peek, peek_scores};
     VOXCHK(stream_verify_enqueue(st));
@@ -3604,7 +3683,7 @@ static int32_t stream_run(vox_stream* st, const StreamSrc& src, FeedPlan& plan, 
 // vox_stream_peek behind its checks: finish's ticks, then the session as it was.  The device takes back the encoder ring rows the tail wrote and the state block
 // (the ring keep, its restore inside stream_run); the host takes back the feed, what StreamMark holds next to it, and a decoder cache that grew.  Everything else the
 // tail wrote lies past the session's position and is written again before it is read.
-struct StreamMark { FeedState::Mark feed; int tap_rows, ftap_ticks; uint64_t eng_steps, op_steps; };      // (the verified counters are set to the same: stream_peek verifies first)
+struct StreamMark { FeedState::Mark feed; int tap_rows, ftap_ticks; uint64_t eng_steps, op_steps, bursts, burst_ticks, single_ticks; };      // (the verified counters are set to the same: stream_peek verifies first)
 static int32_t stream_peek(vox_stream* st, FeedPlan& plan, int32_t* out_ids, int32_t* n_ids, vox_token_score* scores) {
     vox_model* m = st->m; const vox_model_cfg& c = m->cfg; hipStream_t s = st->ctx->stream; FeedState& f = st->feed;
     int T; VOXCHK(peek_max_ticks(f, c.reshape_factor, plan.due, "", &T));
@@ -3615,7 +3694,7 @@ static int32_t stream_peek(vox_stream* st, FeedPlan& plan, int32_t* out_ids, int
     VOXCHK(keep_reserve(st->peek.keep, stream_keep_floats(c.enc_layers, c.enc_heads, c.enc_head_dim, rows), &st->bytes, s, "stream"));
     if (m->pw_pend_rows > 0) VOXCHK(pw_sync(m));
     VOXCHK(stream_verify(st));      // the kept adapter rows cover the tail alone; verified_* are the session's own from here
-    const StreamMark was{f.mark(), st->tap_rows, st->ftap_ticks, st->eng_steps, st->op_steps};
+    const StreamMark was{f.mark(), st->tap_rows, st->ftap_ticks, st->eng_steps, st->op_steps, st->bursts, st->burst_ticks, st->single_ticks};
     const StreamKeepParams keep = ring_keep(c, st->d_mem, st->d_order, 1, rows, st->cap, st->peek.keep.p);      // the round of one
     HIPCHK(launch_stream_keep(keep, 0, s));
     st->peek.active = true;
@@ -3626,6 +3705,7 @@ static int32_t stream_peek(vox_stream* st, FeedPlan& plan, int32_t* out_ids, int
     f.rewind(was.feed); st->dec->len = st->verified_pos = f.pos;
     st->tap_rows = st->verified_tap_rows = was.tap_rows; st->ftap_ticks = was.ftap_ticks;
     st->eng_steps = st->verified_eng_steps = was.eng_steps; st->op_steps = st->verified_op_steps = was.op_steps;
+    st->bursts = was.bursts; st->burst_ticks = was.burst_ticks; st->single_ticks = was.single_ticks;
     return r;
 }
 
@@ -4024,6 +4104,7 @@ extern "C" int32_t vox_stream_restore(vox_stream* st, const void* blob, size_t n
     if (r != VOX_OK) { (void)hipStreamSynchronize(s); (void)stream_load_initial(st); return r; }      // a device failure half way: the target is a fresh session, not half of two
     st->dec->len = st->verified_pos = h.D; st->eng_unverified = false;
     st->eng_steps = st->op_steps = st->verified_eng_steps = st->verified_op_steps = 0; st->tap_rows = st->verified_tap_rows = 0; st->ftap_ticks = 0;
+    st->bursts = st->burst_ticks = st->single_ticks = 0;
     return VOX_OK;
 }
 

@@ -137,6 +137,13 @@ extern "C" int32_t vox_stream_peek_ids(size_t n_samples, uint32_t sample_rate, i
     *n = ids - ids_out;
     return VOX_OK;
 }
+// ---- where a burst stream cuts a backlog ("Bursts"): the next burst of a pass with `due` ticks still to run, at position pos, of a stream
+// created with burst_ticks = burst.  next_stop: the nearest position > pos at whose tick the host must act first (decoder cache growth, an endless session's wrap, list
+// growth, the verification limit).  The smallest of the three, and at least 1: a burst never spans a stop, and a tick is always a burst of 1.
+namespace vox_host {
+int stream_burst_len(int64_t due, int burst, int64_t pos, int64_t next_stop) { return (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(due, burst), next_stop - pos)); }
+}  // namespace vox_host
+extern "C" int32_t vox_stream_burst_len(int64_t due, int32_t burst, int64_t pos, int64_t next_stop) { return stream_burst_len(due, burst, pos, next_stop); }
 extern "C" int32_t vox_stream_group_pages_for(int64_t positions, int32_t page_rows, int32_t window, int32_t* first_page, int32_t* n_pages) {
     ARGCHK(first_page && n_pages, "null argument"); ARGCHK(positions >= 0 && positions <= ((int64_t)1 << 30), "positions %lld out of range", (long long)positions);
     ARGCHK(page_rows_ok(page_rows), "page_rows %d is not a power of two in %d..%d", page_rows, PAGE_ROWS_MIN, PAGE_ROWS_MAX); ARGCHK(window >= -1, "window %d: -1 is none", window);

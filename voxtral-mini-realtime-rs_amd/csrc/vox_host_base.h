@@ -114,4 +114,5 @@ int feed_pass_max_ticks(int R);
 FeedPass feed_pass(FeedState& f, FeedPlan& p, int R, long left, size_t in_cap);
 int32_t peek_second_pass(const char* who);
 int32_t peek_max_ticks(const FeedState& f, int R, int due, const char* who, int* T);
+int stream_burst_len(int64_t due, int burst, int64_t pos, int64_t next_stop);
 }  // namespace vox_host

@@ -467,6 +467,12 @@ struct StreamAttnParams {
                                              // slot z reads row order[z] * rope_stride + (position & rope_mask)
 };
 hipError_t launch_stream_attn(const StreamAttnParams& p, int hd, hipStream_t s);
+// the same attention for a burst of ticks: 1 <= M <= 64 rows per session (b ticks' 4 b rows, all at STRM_ENC_POS + m), cap > window + M, and with a RoPE ring
+// rope_mask + 1 >= M.  One workgroup per (head, tile of 4 query rows, slot) reads every ring row once for its tile.  One launch with M = 4 b leaves the bits in `out`
+// and in every ring word that b launches of launch_stream_attn with M = 4 leave when STRM_ENC_POS moves by 4 between them (stream_attn_burst_kernel, vox_kernels.hip).
+hipError_t launch_stream_attn_burst(const StreamAttnParams& p, int hd, hipStream_t s);
+// launches enqueued by launch_stream_attn_burst (vox_debug_stream_attn_burst_launches); attn_form_counts does not count them
+unsigned long long stream_attn_burst_launches();
 // rows 0 .. rows-1 of every layer's ring from token-major k | v rows (the model's prefix state: [layers][rows][k row | v row])
 hipError_t launch_stream_ring_init(const float* kv, int layers, int rows, int n_heads, int hd, int cap, float* kring, float* vring, hipStream_t s);
 // h = audio_row + embed(tokens[STRM_POS]); the adapter row is also kept in audio_keep[STRM_POS % keep_rows] (an engine hand-off timeout re-runs the decode steps from there)

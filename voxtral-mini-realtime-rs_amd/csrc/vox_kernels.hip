@@ -4758,6 +4758,130 @@ hipError_t launch_stream_attn(const StreamAttnParams& p, int hd, hipStream_t s) 
     return hipGetLastError();
 }
 
+// the same attention for a BURST of ticks: M <= 64 rows per slot (b ticks of 4 rows whose samples were all there before the first), one workgroup per (head, tile of 4
+// query rows, slot).  Per query the arithmetic is stream_attn_kernel's, operation for operation -- the rotation's expression, the 16-lane dot with row16_sum, the
+// 256-thread strided max and sum with their (w0 + w1) + (w2 + w3) combination, the G strided V sums added in order -- so one launch leaves the bits in `out` and in the
+// rings that b launches of stream_attn_kernel with M = 4 leave (what an earlier tick appended to the ring is what this kernel rotates into LDS: one expression).  The
+// blocking is new: the workgroup walks the union of its tile's windows once, and every ring k and v row it loads serves the tile's four queries.
+//   keys: 16 lanes per key as above; a key's float4s feed four dots, each stored to its query's score row at the key's index relative to that query's window start
+//   values: thread (d, kg) loads the rows j = jlo + kg, + G, ...; for query q such a row always falls into ONE of the query's G strided sums (the class
+//     (jlo - j0_q + kg) mod G, since the window starts of a tile differ by constants), and it meets that sum's rows in ascending order: the thread carries that sum
+// The burst's own k rows 0 .. last row of the tile are rotated into LDS by the workgroup itself and its v rows are read from qkv (the bits the ring receives), so no
+// workgroup reads a ring row another one writes in this launch: with cap > window + M the rows written now held positions below every window of the burst.
+template <int HD>
+__global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_attn_burst_kernel(const StreamAttnParams p) {
+    constexpr int HALF = HD / 2, G = 256 / HD, TQ = 4;
+    __shared__ __attribute__((aligned(16))) float qs[TQ][HD];
+    __shared__ __attribute__((aligned(16))) float kn[64][HD];
+    __shared__ float sc[TQ][1024];
+    __shared__ float red[TQ][G][HD];
+    __shared__ float wred[TQ][4];
+    const int h = blockIdx.x, m0 = blockIdx.y * TQ, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int T = min(TQ, p.M - m0);      // the tile's query rows m0 .. m0 + T - 1
+    const StreamMember& me = p.mem[p.order[blockIdx.z]];
+    float* __restrict__ kring = me.kring + p.ring_off; float* __restrict__ vring = me.vring + p.ring_off;
+    const float* __restrict__ qkv = p.qkv + (size_t)blockIdx.z * p.M * p.qkv_stride;      // the slot's M rows
+    const int enc_pos = me.state[STRM_ENC_POS], QD = p.n_heads * HD, nkr = m0 + T;       // k rows 0 .. nkr - 1, then the T query rows
+    for (int i = tid; i < (nkr + T) * HALF; i += 256) {
+        const int r = i / HALF, j = i - r * HALF; const bool isq = r >= nkr; const int row = isq ? m0 + (r - nkr) : r;
+        const size_t ti = p.rope_mask ? ((size_t)p.order[blockIdx.z] * p.rope_stride + (size_t)((enc_pos + row) & p.rope_mask)) * HD + j : (size_t)(enc_pos + row) * HALF + j;
+        const float c = p.cos_t[ti], sn = p.sin_t[ti];
+        const float* src = qkv + (size_t)row * p.qkv_stride + (isq ? 0 : QD) + h * HD + 2 * j;
+        const float xr = src[0], xi = src[1];
+        float* dst = isq ? qs[r - nkr] : kn[r];
+        dst[2 * j] = xr * c - xi * sn; dst[2 * j + 1] = xr * sn + xi * c;
+    }
+    __syncthreads();
+    const size_t hbase = (size_t)h * p.cap * HD;
+    for (int i = tid; i < T * HD; i += 256) {
+        const int q = i / HD, d = i - q * HD, m = m0 + q;
+        const size_t slot = hbase + (size_t)((enc_pos + m) % p.cap) * HD + d;
+        kring[slot] = kn[m][d]; vring[slot] = qkv[(size_t)m * p.qkv_stride + 2 * QD + h * HD + d];
+    }
+    // query q: position enc_pos + m0 + q, keys j0[q] .. that position; the tile's union is jlo = j0[0] .. the last query's position
+    int j0[TQ], nk[TQ];
+#pragma unroll
+    for (int q = 0; q < TQ; q++) { const int qpos = enc_pos + m0 + q; j0[q] = max(0, qpos - p.window); nk[q] = q < T ? qpos - j0[q] + 1 : 0; }
+    const int jlo = j0[0], nu = enc_pos + m0 + T - jlo;
+    const int g = tid >> 4, li = tid & 15;
+    const float scale = HD == 64 ? 0.125f : 0.08838834764831845f;      // head_dim^-0.5
+    for (int i0 = 0; i0 < nu; i0 += 16) {      // uniform trip count: the row sums below need every lane
+        const int j = jlo + min(i0 + g, nu - 1);
+        float dot[TQ] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int u = 0; u < HD / 64; u++) {
+            const int o = (u * 16 + li) * 4;
+            const float4 kv = j < enc_pos ? *reinterpret_cast<const float4*>(kring + hbase + (size_t)(j % p.cap) * HD + o) : *reinterpret_cast<const float4*>(&kn[j - enc_pos][o]);
+#pragma unroll
+            for (int q = 0; q < TQ; q++) {
+                const float4 qv = *reinterpret_cast<const float4*>(&qs[q][o]);
+                dot[q] = fmaf(qv.x, kv.x, dot[q]); dot[q] = fmaf(qv.y, kv.y, dot[q]); dot[q] = fmaf(qv.z, kv.z, dot[q]); dot[q] = fmaf(qv.w, kv.w, dot[q]);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < TQ; q++) {
+            const float dq = row16_sum(dot[q]);
+            const int i = j - j0[q];
+            if (li == 0 && i0 + g < nu && i >= 0 && i < nk[q]) sc[q][i] = dq * scale;
+        }
+    }
+    __syncthreads();
+    float mx[TQ], sum[TQ];
+#pragma unroll
+    for (int q = 0; q < TQ; q++) {
+        float v = -INFINITY;
+        for (int i = tid; i < nk[q]; i += 256) v = fmaxf(v, sc[q][i]);
+        v = wave_max(v);
+        if (lane == 0) wred[q][wave] = v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < TQ; q++) mx[q] = fmaxf(fmaxf(wred[q][0], wred[q][1]), fmaxf(wred[q][2], wred[q][3]));
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < TQ; q++) {
+        float v = 0.f;
+        for (int i = tid; i < nk[q]; i += 256) { const float e = expf(sc[q][i] - mx[q]); sc[q][i] = e; v += e; }
+        v = wave_sum(v);
+        if (lane == 0) wred[q][wave] = v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < TQ; q++) sum[q] = (wred[q][0] + wred[q][1]) + (wred[q][2] + wred[q][3]);
+    const int d = tid % HD, kg = tid / HD;
+    float acc[TQ] = {0.f, 0.f, 0.f, 0.f};
+    for (int u = kg; u < nu; u += G) {
+        const int j = jlo + u;
+        const float vv = j < enc_pos ? vring[hbase + (size_t)(j % p.cap) * HD + d] : qkv[(size_t)(j - enc_pos) * p.qkv_stride + 2 * QD + h * HD + d];
+#pragma unroll
+        for (int q = 0; q < TQ; q++) {
+            const int i = j - j0[q];
+            if (i >= 0 && i < nk[q]) acc[q] = fmaf(sc[q][i], vv, acc[q]);
+        }
+    }
+    // (u = kg + G t and i = u - (j0[q] - jlo): the thread's rows of query q are those of the strided sum (kg - (j0[q] - jlo)) mod G)
+#pragma unroll
+    for (int q = 0; q < TQ; q++) red[q][(((kg - (j0[q] - jlo)) % G) + G) % G][d] = acc[q];
+    __syncthreads();
+    for (int i = tid; i < T * HD; i += 256) {
+        const int q = i / HD, dd = i - q * HD;
+        float o = red[q][0][dd];
+#pragma unroll
+        for (int c = 1; c < G; c++) o += red[q][c][dd];
+        p.out[((size_t)blockIdx.z * p.M + m0 + q) * p.out_stride + h * HD + dd] = o / sum[q];
+    }
+}
+static std::atomic<unsigned long long> g_stream_attn_burst_launches;      // a counter of its own: the slots of attn_form_counts keep their numbers
+unsigned long long stream_attn_burst_launches() { return g_stream_attn_burst_launches.load(std::memory_order_relaxed); }
+hipError_t launch_stream_attn_burst(const StreamAttnParams& p, int hd, hipStream_t s) {
+    if ((hd != 64 && hd != 128) || p.M < 1 || p.M > 64 || p.n < 1 || p.n > 16 || !p.mem || !p.order || p.window < 0 || p.window + 1 > 1024 || p.cap <= p.window + p.M || (p.ring_off & 3) || p.rope_mask < 0 ||
+        (p.rope_mask & (p.rope_mask + 1)) || (p.rope_mask && p.rope_mask + 1 < p.M) || (p.rope_stride && (!p.rope_mask || p.rope_stride < p.rope_mask + 1))) return hipErrorInvalidValue;
+    g_stream_attn_burst_launches.fetch_add(1, std::memory_order_relaxed);      // (behind every refusal: a refused call counts no launch)
+    if (hd == 64) stream_attn_burst_kernel<64><<<dim3(p.n_heads, (p.M + 3) / 4, p.n), dim3(256), 0, s>>>(p);
+    else stream_attn_burst_kernel<128><<<dim3(p.n_heads, (p.M + 3) / 4, p.n), dim3(256), 0, s>>>(p);
+    return hipGetLastError();
+}
+
 __global__ void stream_ring_init_kernel(const float* __restrict__ kv, int layers, int rows, int n_heads, int hd, int cap, float* __restrict__ kring, float* __restrict__ vring) {
     const int QD = n_heads * hd;
     const long total = (long)layers * rows * QD;

@@ -339,7 +339,7 @@ class StreamAttnDesc(C.Structure):
                [("theta", C.c_float), ("order", C.c_void_p), ("enc_pos", C.c_void_p)]
 
 
-def stream_attn(ctx, qkv, kring, vring, order, enc_pos, rows, window, theta, layer=0, rope_rows=0, rope_per_member=False):
+def stream_attn(ctx, qkv, kring, vring, order, enc_pos, rows, window, theta, layer=0, rope_rows=0, rope_per_member=False, _entry="vox_debug_stream_attn"):
     """vox_debug_stream_attn: ONE launch of the live sessions' encoder ring attention (RoPE on q and k, K / V append, windowed softmax).  qkv [n_slots * rows,
     3 * n_heads * hd] not rotated; kring / vring [n_members, layers, n_heads, cap, hd] (hd 64 | 128); order [n_slots] distinct members; enc_pos [n_members].
     rope_rows 0: a flat RoPE table; R: a RoPE ring of R rows, with rope_per_member one per member.  Returns (out [n_slots * rows, n_heads * hd], kring, vring after
@@ -354,8 +354,28 @@ def stream_attn(ctx, qkv, kring, vring, order, enc_pos, rows, window, theta, lay
     d = StreamAttnDesc(n_slots=len(order), n_members=n_members, rows=int(rows), n_heads=n_heads, head_dim=hd, window=int(window), cap=cap, layers=layers, layer=int(layer),
                        rope_rows=int(rope_rows), rope_per_member=int(bool(rope_per_member)), theta=float(theta), order=order.ctypes.data, enc_pos=enc_pos.ctypes.data)
     out = np.empty((qkv.shape[0], n_heads * hd), np.float32)
-    check(lib().vox_debug_stream_attn(ctx.h, C.byref(d), _ptr(qkv), _ptr(kring), _ptr(vring), _ptr(out)))
+    check(getattr(lib(), _entry)(ctx.h, C.byref(d), _ptr(qkv), _ptr(kring), _ptr(vring), _ptr(out)))
     return out, kring, vring
+
+
+def stream_attn_burst(ctx, qkv, kring, vring, order, enc_pos, rows, window, theta, layer=0, rope_rows=0, rope_per_member=False):
+    """vox_debug_stream_attn_burst: stream_attn's arguments with rows up to 64 (a burst's 4 b rows) -- ONE launch of the burst kernel, which leaves the bits b
+    chained stream_attn launches of 4 rows leave."""
+    return stream_attn(ctx, qkv, kring, vring, order, enc_pos, rows, window, theta, layer, rope_rows, rope_per_member, _entry="vox_debug_stream_attn_burst")
+
+
+def stream_attn_burst_launches() -> int:
+    """vox_debug_stream_attn_burst_launches: launches of the burst kernel so far (a counter of its own, in no slot of attn_launches)."""
+    v = C.c_uint64(); check(lib().vox_debug_stream_attn_burst_launches(C.byref(v)))
+    return int(v.value)
+
+
+STREAM_BURST_MAX = 16      # VOX_STREAM_BURST_MAX
+
+
+def stream_burst_len(due: int, burst: int, pos: int, next_stop: int) -> int:
+    """vox_stream_burst_len: the next burst of a pass with `due` ticks still to run at position pos -- max(1, min(due, burst, next_stop - pos))."""
+    return int(lib().vox_stream_burst_len(int(due), int(burst), int(pos), int(next_stop)))
 
 
 def stream_ring_init(ctx, kv, kring, vring):
@@ -726,14 +746,22 @@ class LiveStream:
     sample_rate: the rate of what is pushed (vox_stream_create_rate); other than 16 kHz the session resamples incrementally and gives the ids of a 16 kHz session
     fed resample(samples).
     endless (vox_stream_create_endless): the session goes on past 16 384 positions, up to 2^24: its decoder cache is a ring of dec_ring_rows rows (0: a little more
-    than one window) and max_positions does not apply."""
+    than one window) and max_positions does not apply.
+    burst (vox_stream_create_burst; None: a plain stream): 1..16 -- a backlog's ticks run in bursts of up to that many (one encoder pass of 4 b rows, then b decode
+    steps); ids equal a plain stream's up to near-ties, and bit for bit when the stream is fed one tick per call.  burst_info() counts the bursts."""
 
-    def __init__(self, model, t_embed, gain=1.0, enc_capacity_rows=0, max_positions=0, sample_rate=16000, endless=False, dec_ring_rows=0):
+    def __init__(self, model, t_embed, gain=1.0, enc_capacity_rows=0, max_positions=0, sample_rate=16000, endless=False, dec_ring_rows=0, burst=None):
+        if burst is not None and (isinstance(burst, bool) or not isinstance(burst, (int, np.integer)) or not 1 <= int(burst) <= STREAM_BURST_MAX):
+            raise VoxError(1, f"create_stream: burst {burst!r} is not an integer in 1..{STREAM_BURST_MAX}")
         self.model = model; self.h = C.c_void_p(); self.sample_rate = int(sample_rate); self.endless = bool(endless)
         args = (model.h, _ptr(_f32(t_embed).reshape(-1)), float(gain), int(enc_capacity_rows), int(max_positions))
-        if self.endless:
-            if max_positions:
-                raise VoxError(1, "create_stream: an endless session takes no max_positions")
+        if self.endless and max_positions:
+            raise VoxError(1, "create_stream: an endless session takes no max_positions")
+        if burst is not None:
+            if dec_ring_rows and not self.endless:
+                raise VoxError(1, "create_stream: dec_ring_rows applies with endless=True")
+            check(lib().vox_stream_create_burst(*args, self.sample_rate, int(self.endless), int(dec_ring_rows), int(burst), C.byref(self.h)))
+        elif self.endless:
             check(lib().vox_stream_create_endless(*args[:4], int(dec_ring_rows), self.sample_rate, C.byref(self.h)))
         elif dec_ring_rows:
             raise VoxError(1, "create_stream: dec_ring_rows applies with endless=True")
@@ -800,6 +828,11 @@ class LiveStream:
     def info(self):
         v = (C.c_int64 * 8)(); check(lib().vox_stream_info(self.h, v))
         return dict(zip(("samples", "positions", "ids", "encoder_position", "ring_rows", "bytes", "engine_steps", "operator_steps"), (int(x) for x in v)))
+
+    def burst_info(self):
+        """vox_stream_burst_info: burst_ticks (1: a plain stream), the bursts run with b >= 2, the ticks inside them, the ticks run one by one."""
+        v = (C.c_int64 * 4)(); check(lib().vox_stream_burst_info(self.h, v))
+        return dict(zip(("burst", "bursts", "burst_ticks", "single_ticks"), (int(x) for x in v)))
 
     def set_scores(self, on: bool = True):
         """vox_stream_set_scores: from the next push / finish on, every id comes with its record (scores()); survives reset()."""
@@ -1253,11 +1286,12 @@ class Q4VoxtralModel:
         check(lib().vox_transcribe_audio_scored(self.h, ptr, n_samples, _ptr(t), _ptr(ids), cap, C.byref(n), _ptr(sc), None if al is None else _ptr(al), k, kind))
         return ids[:n.value].copy(), sc[:n.value].copy(), None if al is None else al[:n.value].copy()
 
-    def create_stream(self, t_embed, gain=1.0, enc_capacity_rows=0, max_positions=0, sample_rate=16000, endless=False, dec_ring_rows=0) -> LiveStream:
+    def create_stream(self, t_embed, gain=1.0, enc_capacity_rows=0, max_positions=0, sample_rate=16000, endless=False, dec_ring_rows=0, burst=None) -> LiveStream:
         """A live session on this model (vox_stream_create / vox_stream_create_rate): push(x) -> ids, finish(), reset(), info(), close().  gain multiplies every sample
         (a stream has no file peak: 0.95 / max|x| of a known file reproduces transcribe_audio).  sample_rate: the rate of the samples that will be pushed.
-        endless (vox_stream_create_endless): no 16 384-position limit -- the decoder cache is a ring of dec_ring_rows rows (0: the default, a little more than one window)."""
-        return LiveStream(self, t_embed, gain, enc_capacity_rows, max_positions, sample_rate, endless, dec_ring_rows)
+        endless (vox_stream_create_endless): no 16 384-position limit -- the decoder cache is a ring of dec_ring_rows rows (0: the default, a little more than one window).
+        burst (vox_stream_create_burst): 1..16 -- a backlog's ticks run in bursts of up to that many; None: a plain stream."""
+        return LiveStream(self, t_embed, gain, enc_capacity_rows, max_positions, sample_rate, endless, dec_ring_rows, burst)
 
     def create_stream_group(self, t_embed, n_members, gains=None, enc_capacity_rows=0, max_positions=0, sample_rates=None, page_rows=None, pool_pages=None,
                             endless=False, kv_dtype=None) -> LiveStreamGroup:
