@@ -520,6 +520,13 @@ int32_t vox_debug_stream_attn(vox_ctx* ctx, const vox_stream_attn_desc* desc, co
 int32_t vox_debug_stream_attn_burst(vox_ctx* ctx, const vox_stream_attn_desc* desc, const float* qkv, float* kring, float* vring, float* out);
 /* launches of the burst kernel enqueued by the host so far (a burst stream: enc_layers per burst with b >= 2) */
 int32_t vox_debug_stream_attn_burst_launches(uint64_t* out);
+/* The RAGGED burst form (a burst group's round: vox_stream_group_create_burst), on its own: vox_debug_stream_attn_burst's arguments and checks, plus
+ * rows_per_slot[n_slots] -- slot z has rows_per_slot[z] rows (a multiple of 4 in 4..64: its b_z ticks), desc->rows is the largest of them (window + rows < cap), and qkv
+ * [sum rows][3 n_heads hd] and out [sum rows][n_heads hd] hold the slots' rows back to back, slot after slot.  Exactly ONE launch of the ragged burst kernel (grid:
+ * heads x ceil(rows / 4) x n_slots; tiles beyond a slot's rows leave at once), counted in vox_debug_stream_attn_burst_launches; a refused call counts nothing.  For
+ * every slot the launch leaves in out and in every word of that member's K and V ring the bits rows_per_slot[z] / 4 successive vox_debug_stream_attn calls with rows = 4
+ * leave (enc_pos moving by 4); members not in `order` keep every ring word. */
+int32_t vox_debug_stream_attn_group_burst(vox_ctx* ctx, const vox_stream_attn_desc* desc, const int32_t* rows_per_slot, const float* qkv, float* kring, float* vring, float* out);
 /* The seeding of a session's encoder rings from the model's prefix state, on its own (tests): kv host [layers][rows][k row | v row], token-major, each row n_heads *
  * head_dim wide; kring / vring host [layers][n_heads][cap][head_dim], in and out: ring rows 0 .. rows - 1 of every layer and head receive the input's bits, every
  * other word keeps its own.  layers 1..64, n_heads 1..64, head_dim 64 | 128, cap 1..16384; rows <= 0 and rows > cap are refused, like every argument, before the
@@ -688,7 +695,7 @@ int32_t vox_stream_create_endless(vox_model* m, const float* t_embed, float gain
  *   endless (0 / 1), dec_ring_rows: vox_stream_create_endless's (dec_ring_rows 0 unless endless); max_positions: a bounded stream's, ignored when endless.
  *   enc_capacity_rows: 0 = max(window + 4 burst_ticks + 4, prefix rows) rounded up to 64 (832 rows at 16 for the 750 window); a given value must exceed window +
  *   4 burst_ticks (VOX_ERR_INVALID before anything is allocated; the message names the bound).
- * Scores, alternatives, taps, peek, reset, snapshot and restore work as on any stream (a blob does not know its ring capacity).  Not served: bursts in stream groups. */
+ * Scores, alternatives, taps, peek, reset, snapshot and restore work as on any stream (a blob does not know its ring capacity).  Stream groups have bursts of their own: vox_stream_group_create_burst.  Not served: burst_ticks above 16. */
 #define VOX_STREAM_BURST_MAX 16
 int32_t vox_stream_create_burst(vox_model* m, const float* t_embed, float gain, int32_t enc_capacity_rows, int32_t max_positions, uint32_t sample_rate, int32_t endless,
                                 int32_t dec_ring_rows, int32_t burst_ticks, vox_stream** out);
@@ -963,6 +970,30 @@ int32_t vox_stream_group_create_kv(vox_model* m, const float* t_embed, int32_t n
                                    int32_t enc_capacity_rows, int32_t max_positions /* endless: 0 */, int32_t page_rows /* 0: 256 */, int32_t pool_pages /* 0: the default */,
                                    int32_t endless, int32_t kv_dtype, vox_stream_group** out);
 int32_t vox_kv_round_bf16(const float* in, int64_t n, uint16_t* out);
+/* BURST GROUPS ("Bursts in stream groups").  vox_stream_group_create_burst makes any group kind the creators above make -- paged 0: a slab group
+ * (page_rows, pool_pages, endless 0 and kv_dtype VOX_KV_F32 required); paged 1: a paged group with the arguments of vox_stream_group_create_kv -- with burst_ticks B in
+ * 1..VOX_STREAM_BURST_MAX fixed for its life.  B = 1 is exactly the group the other creators make.  With B >= 2 a pass no longer runs one round per due tick: round k of
+ * a pass runs every due member's next b_z = min(ticks still due to it, B) ticks as ONE encoder pass of 4 sum b_z rows -- every encoder weight matrix read once, the
+ * attention in its ragged burst form (vox_debug_stream_attn_group_burst) -- followed by max b_z decode rounds, decode round t serving the members with b_z > t
+ * (vox_stream_group_burst_rounds is the schedule).  A round whose b_z are all 1 is a plain group round, launch for launch; the host never acts between the ticks of a
+ * pass, so a pass is never cut anywhere else.
+ *   enc_capacity_rows: 0 = max(window + 4 B + 4, prefix rows) rounded up to 64; a given value must exceed window + 4 B (VOX_ERR_INVALID before anything is allocated).
+ *   Memory: the round buffers hold n_members x B ticks instead of n_members.
+ * Contract: fed so that no member ever has two ticks due in a pass, a burst group is bit for bit the plain group of the same ring capacity (ids, logits, records, the
+ * pool).  With backlogs a member's ids are the solo plain stream's up to near-ties: the row count of the encoder pass selects the GEMM kernels, so how the samples were
+ * cut can decide an id whose two best logits nearly tie (the solo burst stream's caveat).  A paged and a slab burst group given the same calls agree bit for bit, and so
+ * do an endless and a bounded paged one up to the bounded limit.  Peek, reset, snapshot and restore, scores, alternatives, taps, capture rates and 16-bit PCM work as in
+ * any group.  Not served: burst_ticks above 16; overlapping a round's decode rounds with the next round's encoder pass. */
+int32_t vox_stream_group_create_burst(vox_model* m, const float* t_embed, int32_t n_members, const float* gains /* null: 1.0 */, const uint32_t* rates /* null: 16000 each */,
+                                      int32_t enc_capacity_rows, int32_t max_positions /* endless: 0 */, int32_t paged, int32_t page_rows /* 0: 256 */,
+                                      int32_t pool_pages /* 0: the default */, int32_t endless, int32_t kv_dtype, int32_t burst_ticks, vox_stream_group** out);
+/* burst_ticks of the group (1: a plain group), the burst rounds run since create (rounds in which some member ran 2 or more ticks), the member-ticks inside them, the
+ * plain rounds run (every group counts those); a peek's rounds are not counted */
+int32_t vox_stream_group_burst_info(const vox_stream_group* g, int64_t out[4]);
+/* host only, a pure function: the rounds of a burst group's pass.  due[n]: the ticks due to the pass's n members (1..16 of them, each >= 1, sorted descending); burst:
+ * burst_ticks (1..16).  Row k of out ([max_rounds][17]: n_r, b_0 .. b_15, zeros behind b_{n_r - 1}) is round k: the first n_r = #{due_z > k burst} members run
+ * b_z = min(due_z - k burst, burst) ticks.  *n_rounds = ceil(due[0] / burst); more than max_rounds: VOX_ERR_INVALID, nothing written. */
+int32_t vox_stream_group_burst_rounds(const int32_t* due, int32_t n, int32_t burst, int32_t* out, int32_t max_rounds, int32_t* n_rounds);
 /* Snapshot and resume of a member (SNAPSHOT AND RESUME above: the format, the refusals, the contracts): vox_stream_snapshot_size / _snapshot / _restore for member
  * `member` of a slab, paged or endless paged group.  Only that member is read or changed. */
 int32_t vox_stream_group_snapshot_size(const vox_stream_group* g, int32_t member, size_t* nbytes);

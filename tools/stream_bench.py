@@ -11,6 +11,7 @@
     python tools/stream_bench.py --endless [--out profiles/stream_endless_tick.txt]
     python tools/stream_bench.py --snapshot [--out profiles/stream_snapshot.txt]
     python tools/stream_bench.py --burst 1,4,16 [--out profiles/stream_burst.txt]
+    python tools/stream_bench.py --group 16 --burst 4,16 [--out profiles/stream_group_burst.txt]
 
  * stream: HIP events on the context's stream around ONE push of `ticks` x 2560 samples (a large push is a loop of identical ticks), at encoder positions past the
    750-row window, median of `passes` passes; launches per tick from the library's launch counters plus the fixed launches of a tick; wall time of single 160 ms pushes
@@ -59,6 +60,11 @@
    `passes`.  Per stream: the call's ms, ms per tick, the speed-up over the plain stream of the same run, the bursts and ticks from vox_stream_burst_info, the launches
    per call from the library's counters (the burst attention has a counter of its own) plus the fixed launches, and how many of the timed ids equal the plain stream's.
    Nothing else is measured in this mode.
+ * --group N --burst B[,B...]: BACKLOGS in a stream group of N members, past the 750-row encoder window: a plain group and one burst group per B
+   (vox_stream_group_create_burst) are warmed tick by tick and alternate pass by pass over the same samples.  Two workloads per pass: (a) every member with `ticks`
+   (default 64) ticks due in one call, (b) member 0 with `ticks` ticks due and every other member with one.  Per group: the call's ms, the speed-up over the plain
+   group of the same run, burst rounds / member-ticks / plain rounds per call from vox_stream_group_burst_info, the counted launches per call, and how many of the
+   timed ids equal the plain group's.  --burst 0 times the plain group alone (a build without burst groups).
  * derived figures are labelled as derived."""
 import argparse
 import ctypes as C
@@ -386,6 +392,51 @@ def bench_burst(pkg, ctx, m, t, tm, a, bursts, lines):
                  "".join(f", at B = {b} {375 * statistics.median(ms[i + 1]) / a.ticks / 1e3:.2f} s" for i, b in enumerate(bursts)))
 
 
+def bench_group_burst(pkg, ctx, m, t, tm, a, N, bursts, lines):
+    """--group N --burst B[,B...]: two backlog workloads on a plain group of N members and on one burst group per B, all warmed tick by tick to the same positions and
+    alternating pass by pass: (a) every member with `ticks` ticks due in one call, (b) member 0 with `ticks` ticks due and every other member with one."""
+    from importlib import import_module
+    gg = import_module(pkg.__name__ + ".gguf")
+    S = pkg.synth; warm = 200
+    n_ticks = warm + 2 * a.ticks * a.passes + 8
+    assert 38 + n_ticks < 2048, "every member stays inside the default slab's 2048 positions"
+    x = S.synth_audio(n_ticks * 0.16 + 1.0, seed=4242); gain = float(np.float32(0.95) / np.float32(np.abs(x).max()))
+    groups = [("plain group", m.create_stream_group(t, N, gains=[gain] * N))] + [(f"burst group, B = {b}", m.create_stream_group(t, N, gains=[gain] * N, burst=b)) for b in bursts]
+    start = 40 + 2560 * warm
+    for _, g in groups:
+        for a0 in range(0, start, 2560):      # warmed tick by tick: every group reaches the timed passes with the plain group's bits
+            seg = x[a0:min(start, a0 + 2560)] if a0 else x[:2560]
+            g.advance({k: seg for k in range(N)})
+        assert all(g.info(k)["positions"] == 38 + warm for k in range(N))
+    info = lambda g: (g.burst_info() if hasattr(g, "burst_info") else {"burst_rounds": 0, "burst_member_ticks": 0, "plain_rounds": 0})      # (a build without burst groups: the plain group alone)
+    res = {w: {"ms": [[] for _ in groups], "ids": [[] for _ in groups], "counted": [0] * len(groups), "battn": [0] * len(groups), "bi": [[0, 0, 0] for _ in groups]} for w in "ab"}
+    at = [start] * N      # every member's next sample: the same in every group
+    for _ in range(a.passes):
+        for w in "ab":
+            n = [2560 * a.ticks if (w == "a" or k == 0) else 2560 for k in range(N)]
+            feeds = {k: x[at[k]:at[k] + n[k]] for k in range(N)}
+            for i, (_, g) in enumerate(groups):
+                r = res[w]; k0 = launch_counts(pkg); b0 = gg.stream_attn_burst_launches() if hasattr(gg, "stream_attn_burst_launches") else 0; i0 = info(g)
+                out = {}
+                r["ms"][i].append(tm.ms(lambda: out.update(g.advance(feeds))))
+                r["counted"][i] += sum(launch_counts(pkg)) - sum(k0); r["battn"][i] += (gg.stream_attn_burst_launches() if hasattr(gg, "stream_attn_burst_launches") else 0) - b0
+                i1 = info(g)
+                for j, key in enumerate(("burst_rounds", "burst_member_ticks", "plain_rounds")):
+                    r["bi"][i][j] += i1[key] - i0[key]
+                r["ids"][i].append(np.concatenate([out[k] for k in range(N)]))
+            at = [at[k] + n[k] for k in range(N)]
+    for w, what in (("a", f"(a) every one of the {N} members with a {a.ticks}-tick backlog in one call"), ("b", f"(b) member 0 with a {a.ticks}-tick backlog, the other {N - 1} members with one tick due")):
+        r = res[w]; ref = np.concatenate(r["ids"][0]); base = statistics.median(r["ms"][0])
+        lines.append(what + f" ({len(ref) // a.passes} member-ticks per call; HIP events around the call):")
+        for i, (name, g) in enumerate(groups):
+            med = statistics.median(r["ms"][i]); got = np.concatenate(r["ids"][i]); bi = [v / a.passes for v in r["bi"][i]]
+            lines += [f"  {name}: median {med:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in r["ms"][i]) + (f"   plain / this = {base / med:.2f} x, per pass " + " ".join(f"{q / v:.2f}" for v, q in zip(r["ms"][i], r["ms"][0])) if i else ""),
+                      f"    per call: {bi[0]:.1f} burst rounds holding {bi[1]:.1f} member-ticks, {bi[2]:.1f} plain rounds; counted launches (GEMM and attention forms) {r['counted'][i] / a.passes:.0f} + burst attention {r['battn'][i] / a.passes:.0f}",
+                      f"    ids of the timed calls equal to the plain group's: {int((got == ref).sum())} of {len(ref)}"]
+    for _, g in groups:
+        g.close()
+
+
 def bench_snapshot(pkg, ctx, m, t, tm, a, lines):
     """--snapshot: vox_stream_snapshot / vox_stream_restore of one endless solo session at three positions (about 300, past 1024, past the decoder window), with a
     device blob and with a host blob, next to a device-to-device copy of the same byte count in the same run."""
@@ -443,11 +494,15 @@ def main():
     ap.add_argument("--snapshot", action="store_true", help="time vox_stream_snapshot / vox_stream_restore (device and host blobs) at three positions next to a device copy of the same size (nothing else is measured)")
     a = ap.parse_args()
     bursts = [int(v) for v in a.burst.split(",")] if a.burst else []
-    if bursts and (a.group or a.endless or a.peek or a.scores or a.alternatives or a.page_rows or a.memory_past_window or a.snapshot):
+    if bursts and a.group:      # --group N --burst B[,B...]: the burst groups' mode (B = 0 alone: the plain group by itself, for a build without burst groups)
+        if a.endless or a.peek or a.scores or a.alternatives or a.page_rows or a.memory_past_window or a.snapshot or a.rate or "," in a.group:
+            ap.error("--group N --burst B[,B...] is a mode of its own, with one width")
+        bursts = [b for b in bursts if b != 0]
+    elif bursts and (a.endless or a.peek or a.scores or a.alternatives or a.page_rows or a.memory_past_window or a.snapshot):
         ap.error("--burst is a mode of its own")
     if any(not 1 <= b <= 16 for b in bursts):
         ap.error("--burst takes burst_ticks 1..16")
-    if bursts and "--ticks" not in " ".join(sys.argv):
+    if a.burst and "--ticks" not in " ".join(sys.argv):
         a.ticks = 64
     if a.snapshot and (a.group or a.endless or a.peek or a.scores or a.alternatives or a.page_rows or a.memory_past_window):
         ap.error("--snapshot is a mode of its own")
@@ -489,10 +544,13 @@ def main():
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             open(a.out, "w").write(text)
         return
-    if bursts:
+    if a.burst:
         lines = ["# " + " ".join(["python", "tools/stream_bench.py"] + sys.argv[1:]),
                  f"# model {os.path.basename(path)}: {c.enc_layers} encoder layers, {c.dec_layers} decoder layers; a backlog of {a.ticks} ticks per call, {a.passes} passes, all past encoder position {4 * (37 + 200)}"]
-        bench_burst(pkg, ctx, m, t, tm, a, bursts, lines)
+        if a.group:
+            bench_group_burst(pkg, ctx, m, t, tm, a, widths[0], bursts, lines)
+        else:
+            bench_burst(pkg, ctx, m, t, tm, a, bursts, lines)
         text = "\n".join(lines) + "\n"
         print(text, end="")
         if a.out:

@@ -182,6 +182,7 @@ SIGNATURES = {
     "vox_debug_stream_attn": (i32, [vp, vp, vp, vp, vp, vp]),      # (ctx, vox_stream_attn_desc, qkv, kring, vring, out): ONE launch of the streams' ring attention
     "vox_debug_stream_attn_burst": (i32, [vp, vp, vp, vp, vp, vp]),      # the same arguments, rows up to 64: ONE launch of the burst kernel
     "vox_debug_stream_attn_burst_launches": (i32, [P(C.c_uint64)]),
+    "vox_debug_stream_attn_group_burst": (i32, [vp, vp, vp, vp, vp, vp, vp]),      # (ctx, desc, rows_per_slot, qkv, kring, vring, out): ONE launch of the ragged burst kernel
     "vox_debug_stream_ring_init": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp]),      # (ctx, layers, rows, n_heads, head_dim, cap, kv, kring, vring)
     "vox_debug_attn_gqa_max_seq": (i32, [vp, P(i32)]),
     "vox_debug_gemm_launches": (i32, [P(C.c_uint64), i32]),
@@ -209,6 +210,9 @@ SIGNATURES = {
     "vox_stream_create_burst": (i32, [vp, vp, f32, i32, i32, u32, i32, i32, i32, P(vp)]),      # (..., sample_rate, endless, dec_ring_rows, burst_ticks, out)
     "vox_stream_burst_info": (i32, [vp, P(i64 * 4)]),
     "vox_stream_burst_len": (i32, [i64, i32, i64, i64]),      # returns the length itself (a pure function)
+    "vox_stream_group_burst_rounds": (i32, [vp, i32, i32, vp, i32, P(i32)]),      # (due, n, burst, out [max_rounds][17], max_rounds, n_rounds)
+    "vox_stream_group_create_burst": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, P(vp)]),      # (..., rates, cap, max_pos, paged, page_rows, pool_pages, endless, kv_dtype, burst_ticks, out)
+    "vox_stream_group_burst_info": (i32, [vp, P(i64 * 4)]),
     "vox_stream_push_s16": (i32, [vp, vp, sz, i32, vp, i32, P(i32)]),
     "vox_stream_schedule_rate": (i32, [sz, u32, i32, P(i32), P(i32), P(sz)]),
     "vox_stream_group_create": (i32, [vp, vp, i32, vp, i32, i32, P(vp)]),

@@ -442,7 +442,7 @@ def main(argv=None):
     if a.live_endless and not a.live:
         ap.error("--live-endless applies with --live")
     if a.live_burst and (not a.live or a.live_group):
-        ap.error("--live-burst applies with --live (a solo session; stream groups run no bursts)")
+        ap.error("--live-burst applies with --live (a solo session; --live-group runs a plain group: burst groups are create_stream_group(burst=B))")
     if a.live_burst and not 1 <= a.live_burst <= 16:
         ap.error("--live-burst takes 1..16")
     if a.live_native_rate and not a.live:

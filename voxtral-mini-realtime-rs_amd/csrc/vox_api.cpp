@@ -1331,7 +1331,9 @@ extern "C" int32_t vox_debug_attn_decode_paged_bf16(vox_ctx* c, const vox_attn_d
 // positions need are written, every other ring row is NaN.  Every argument is checked before the context is bound: what launch_stream_attn refuses never reaches it, and
 // nothing the kernel reads or writes lies outside the uploaded buffers (order against n_members, the positions against the table or 2^24, the ring offset against layers).
 // burst: vox_debug_stream_attn_burst -- rows up to 64, and the ONE launch is launch_stream_attn_burst
-static int32_t stream_attn_debug(vox_ctx* c, const vox_stream_attn_desc* d, const float* qkv, float* kring, float* vring, float* out, bool burst) {
+// rows_per_slot (vox_debug_stream_attn_group_burst; null: every slot has d->rows rows): slot z has rows_per_slot[z] rows, a multiple of 4 in 4..64, d->rows is the
+// largest of them; qkv and out hold the slots' rows back to back, and the ONE launch is launch_stream_attn_group_burst with rpt = 4
+static int32_t stream_attn_debug(vox_ctx* c, const vox_stream_attn_desc* d, const float* qkv, float* kring, float* vring, float* out, bool burst, const int32_t* rows_per_slot = nullptr) {
     ARGCHK(c && d && qkv && kring && vring && out, "null argument"); ARGCHK(d->order && d->enc_pos, "null argument (order, enc_pos)");
     ARGCHK(d->head_dim == 64 || d->head_dim == 128, "head_dim %d: the ring attention serves head_dim 64 and 128", d->head_dim);
     const int max_rows = burst ? 64 : 8;
@@ -1344,6 +1346,17 @@ static int32_t stream_attn_debug(vox_ctx* c, const vox_stream_attn_desc* d, cons
     ARGCHK(d->layers >= 1 && d->layers <= 8 && d->layer >= 0 && d->layer < d->layers, "layer %d of %d layers (1..8)", d->layer, d->layers);
     ARGCHK(std::isfinite(d->theta) && d->theta > 1.0f, "theta %g must be finite and above 1", (double)d->theta);
     const int R = d->rope_rows, M = d->rows, n = d->n_slots, NM = d->n_members;
+    StreamBurstDesc bd{}; int rows_all = n * M, slot_rows[16];      // the rows of qkv / out, and of every slot
+    for (int z = 0; z < n; z++) slot_rows[z] = M;
+    if (rows_per_slot) {
+        int most = 0; rows_all = 0;
+        for (int z = 0; z < n; z++) {
+            const int mz = rows_per_slot[z];
+            ARGCHK(mz >= 4 && mz <= 64 && mz % 4 == 0, "rows_per_slot[%d] = %d: a slot of a burst round has 4 b rows, b in 1..16", z, mz);
+            slot_rows[z] = mz; bd.tick0[z] = rows_all / 4; bd.b[z] = mz / 4; rows_all += mz; most = std::max(most, mz);
+        }
+        ARGCHK(most == M, "rows %d is not the largest of rows_per_slot (%d)", M, most);
+    }
     // (a ring of one row would have the mask 0, which the kernel reads as "a flat table")
     ARGCHK(R == 0 || (R >= 2 && R >= M && R <= 4096 && !(R & (R - 1))), "rope_rows %d: a RoPE ring has a power of two of rows, at least `rows` (%d) and 2, at most 4096", R, M);
     ARGCHK(R || !d->rope_per_member, "rope_per_member without a RoPE ring (rope_rows 0)");
@@ -1368,7 +1381,7 @@ static int32_t stream_attn_debug(vox_ctx* c, const vox_stream_attn_desc* d, cons
     } else {
         rope.assign((size_t)(per_member ? NM : 1) * R * hd, std::nanf("")); sin_at = (size_t)half;
         std::vector<int64_t> holds((size_t)(per_member ? NM : 1) * R, -1);
-        for (int z = 0; z < n; z++) for (int r = 0; r < M; r++) {
+        for (int z = 0; z < n; z++) for (int r = 0; r < slot_rows[z]; r++) {
             const int64_t p = (int64_t)d->enc_pos[d->order[z]] + r; const size_t row = (per_member ? (size_t)d->order[z] * R : 0) + (size_t)(p & (R - 1));
             ARGCHK(holds[row] < 0 || holds[row] == p, "one RoPE ring of %d rows cannot hold positions %lld and %lld (slot %d): rope_per_member gives every member its own", R, (long long)holds[row], (long long)p, z);
             holds[row] = p;
@@ -1377,8 +1390,8 @@ static int32_t stream_attn_debug(vox_ctx* c, const vox_stream_attn_desc* d, cons
     }
     VOXCHK(ctx_bind(c));
     hipStream_t s = c->stream;
-    const size_t layer_f = (size_t)H * d->cap * hd, mem_f = (size_t)d->layers * layer_f, ring_f = (size_t)NM * mem_f, qkv_f = (size_t)n * M * 3 * QD, out_f = (size_t)n * M * QD;
-    DevBuf dqkv, dk, dv, dout, drope, dint, dmem;
+    const size_t layer_f = (size_t)H * d->cap * hd, mem_f = (size_t)d->layers * layer_f, ring_f = (size_t)NM * mem_f, qkv_f = (size_t)rows_all * 3 * QD, out_f = (size_t)rows_all * QD;
+    DevBuf dqkv, dk, dv, dout, drope, dint, dmem, ddesc;
     HIPCHK(dqkv.alloc(qkv_f * 4)); HIPCHK(dk.alloc(ring_f * 4)); HIPCHK(dv.alloc(ring_f * 4)); HIPCHK(dout.alloc(out_f * 4)); HIPCHK(drope.alloc(rope.size() * 4));
     HIPCHK(dint.alloc(((size_t)NM * STRM_WORDS + n) * 4)); HIPCHK(dmem.alloc((size_t)NM * sizeof(StreamMember)));
     int* d_state = dint.as<int>(); int* d_order = d_state + (size_t)NM * STRM_WORDS;
@@ -1396,7 +1409,10 @@ static int32_t stream_attn_debug(vox_ctx* c, const vox_stream_attn_desc* d, cons
     StreamAttnParams ap{}; ap.qkv = dqkv.as<float>(); ap.qkv_stride = 3 * QD; ap.mem = dmem.as<StreamMember>(); ap.order = d_order; ap.n = n; ap.ring_off = (size_t)d->layer * layer_f; ap.cap = d->cap;
     ap.cos_t = drope.as<float>(); ap.sin_t = drope.as<float>() + sin_at; ap.out = dout.as<float>(); ap.out_stride = QD; ap.M = M; ap.n_heads = H; ap.window = d->window;
     ap.rope_mask = R ? R - 1 : 0; ap.rope_stride = per_member ? R : 0;
-    HIPCHK(burst ? launch_stream_attn_burst(ap, hd, s) : launch_stream_attn(ap, hd, s));
+    if (rows_per_slot) {
+        HIPCHK(ddesc.alloc(sizeof(StreamBurstDesc))); HIPCHK(hipMemcpyAsync(ddesc.p, &bd, sizeof(StreamBurstDesc), hipMemcpyHostToDevice, s));
+        HIPCHK(launch_stream_attn_group_burst(ap, ddesc.as<StreamBurstDesc>(), bd, 4, hd, s));
+    } else HIPCHK(burst ? launch_stream_attn_burst(ap, hd, s) : launch_stream_attn(ap, hd, s));
     HIPCHK(hipMemcpyAsync(out, dout.p, out_f * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(kring, dk.p, ring_f * 4, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(vring, dv.p, ring_f * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -1408,6 +1424,11 @@ extern "C" int32_t vox_debug_stream_attn(vox_ctx* c, const vox_stream_attn_desc*
 // the burst form of the same attention (a burst stream's encoder layers, b >= 2): vox_debug_stream_attn's arguments and checks with rows 1..64, ONE launch_stream_attn_burst
 extern "C" int32_t vox_debug_stream_attn_burst(vox_ctx* c, const vox_stream_attn_desc* d, const float* qkv, float* kring, float* vring, float* out) {
     return stream_attn_debug(c, d, qkv, kring, vring, out, true);
+}
+// the RAGGED burst form (a burst group's round): the same arguments and checks, plus rows_per_slot[n_slots] -- ONE launch_stream_attn_group_burst
+extern "C" int32_t vox_debug_stream_attn_group_burst(vox_ctx* c, const vox_stream_attn_desc* d, const int32_t* rows_per_slot, const float* qkv, float* kring, float* vring, float* out) {
+    ARGCHK(rows_per_slot, "null argument");
+    return stream_attn_debug(c, d, qkv, kring, vring, out, true, rows_per_slot);
 }
 extern "C" int32_t vox_debug_stream_attn_burst_launches(uint64_t* out) {
     ARGCHK(out, "null argument");
@@ -3455,10 +3476,15 @@ struct StreamRound { const StreamMember* mem; const int* order; int n, cap; size
 // b > 1 (a solo burst stream's round of one, n == 1): the encoder of b ticks in one pass.  Everything the b ticks would read is there before the first (the pass's
 // samples, the state block at the burst's first tick), and tick t's rows are rows 4 t .. of every buffer: 16 b + 3 halo frames, 8 b + 1 and 4 b conv windows, 4 b rows
 // through the layers with the burst attention, b adapter rows (w.arow[t]: tick t's).  ftap_*: room for ftap_b of the burst's ticks, in the per-tick layout.
-static int32_t stream_encode_round(vox_model* m, const StreamWs& w, const StreamRound& r, float* ftap_mel, float* ftap_conv, int b = 1, int ftap_b = 1) {
+// rg (a burst group's round, group_burst_round): slot z runs rg->host->b[z] <= b ticks.  The front end runs with every slot laid out at the stride of b ticks, the rows
+// of the ticks a slot does not run are computed and never read; one pack launch puts each slot's valid R b_z conv rows behind the slots before it, and from there on the
+// pass has R rg->ticks rows, slot z's at row R tick0[z] -- the ragged burst attention, rg->ticks adapter rows (w.arow[tick0[z] + t]: tick t of slot z).
+struct StreamRagged { const StreamBurstDesc* dev; const StreamBurstDesc* host; int ticks; };      // the round's descriptor on the device and on the host; the sum of its b
+static int32_t stream_encode_round(vox_model* m, const StreamWs& w, const StreamRound& r, float* ftap_mel, float* ftap_conv, int b = 1, int ftap_b = 1, const StreamRagged* rg = nullptr) {
     const vox_model_cfg& c = m->cfg; vox_ctx* cx = m->ctx; hipStream_t s = cx->stream;
-    ARGCHK(b >= 1 && b <= VOX_STREAM_BURST_MAX && (b == 1 || r.n == 1), "internal: a burst of %d ticks in a round of %d", b, r.n);
-    const int D = c.enc_dim, H = c.enc_heads, hd = c.enc_head_dim, QD = H * hd, F = c.enc_ffn, R = c.reshape_factor, DD = c.dec_dim, Cm = c.n_mels, n = r.n, M = R * n * b;
+    ARGCHK(b >= 1 && b <= VOX_STREAM_BURST_MAX && (b == 1 || r.n == 1 || rg), "internal: a burst of %d ticks in a round of %d", b, r.n);
+    ARGCHK(!rg || (rg->dev && rg->host && rg->ticks >= r.n && rg->ticks <= r.n * b && !ftap_mel), "internal: a ragged round of %d ticks in %d slots of %d", rg ? rg->ticks : 0, r.n, b);
+    const int D = c.enc_dim, H = c.enc_heads, hd = c.enc_head_dim, QD = H * hd, F = c.enc_ffn, R = c.reshape_factor, DD = c.dec_dim, Cm = c.n_mels, n = r.n, NT = rg ? rg->ticks : n * b, M = R * NT;
     const int NF = 4 * R * b + 3, HS = NF + 1, C1S = 2 * R * b + 2, C2S = R * b + 1;      // mel frames with the halo (conv row s reads frames 4 s - 3 .. 4 s + 3); the slot strides in frames, conv1 rows, conv rows
     HIPCHK(launch_stream_mel(r.mem, r.order, n, STREAM_SAMPLE_RING - 1, r.left, r.mel, 3, NF, w.halo, (long)HS * Cm, s));
     // conv stem without padding rows, memsets or a transpose: conv1 row i of a slot is the window of its halo rows [2 i, 2 i + 2], conv row i the window of its conv1 rows
@@ -3467,7 +3493,8 @@ static int32_t stream_encode_round(vox_model* m, const StreamWs& w, const Stream
     float* conv = n == 1 ? w.x : w.c2;
     { GemmParams g{}; g.w = m->conv1_g; g.x = w.halo; g.x_stride = 2 * Cm; g.M = C1S * n - 1; g.out = w.c1; g.out_stride = D; g.bias = m->conv1_b; HIPCHK(launch_dense2_gemm(g, EPI_GELU, s)); }
     { GemmParams g{}; g.w = m->conv2_g; g.x = w.c1; g.x_stride = 2 * D; g.M = C2S * n - 1; g.out = conv; g.out_stride = D; g.bias = m->conv2_b; HIPCHK(launch_dense2_gemm(g, EPI_GELU, s)); }
-    if (n > 1) HIPCHK(hipMemcpy2DAsync(w.x, (size_t)R * D * 4, w.c2, (size_t)C2S * D * 4, (size_t)R * D * 4, n, hipMemcpyDeviceToDevice, s));
+    if (n > 1 && rg) HIPCHK(launch_stream_burst_pack(w.c2, C2S, rg->dev, n, R, b, D, w.x, s));
+    else if (n > 1) HIPCHK(hipMemcpy2DAsync(w.x, (size_t)R * D * 4, w.c2, (size_t)C2S * D * 4, (size_t)R * D * 4, n, hipMemcpyDeviceToDevice, s));
     if (ftap_mel) {      // the front tap (tests): the tick's fresh frames (halo rows 3 ..) and conv rows, copied on the stream
         HIPCHK(hipMemcpyAsync(ftap_mel, w.halo + (size_t)3 * Cm, (size_t)ftap_b * 4 * R * Cm * 4, hipMemcpyDeviceToDevice, s));
         HIPCHK(hipMemcpyAsync(ftap_conv, w.x, (size_t)ftap_b * R * D * 4, hipMemcpyDeviceToDevice, s));
@@ -3480,15 +3507,16 @@ static int32_t stream_encode_round(vox_model* m, const StreamWs& w, const Stream
         StreamAttnParams ap{}; ap.qkv = w.qkv; ap.qkv_stride = 3 * QD; ap.mem = r.mem; ap.order = r.order; ap.n = n; ap.ring_off = (size_t)l * r.ring_layer; ap.cap = r.cap;
         ap.cos_t = m->enc_cos_s; ap.sin_t = m->enc_sin_s; ap.out = w.att;
         if (r.rope) { ap.cos_t = r.rope; ap.sin_t = r.rope + hd / 2; ap.rope_mask = r.rope_mask; ap.rope_stride = r.rope_stride; } ap.out_stride = QD; ap.M = R * b; ap.n_heads = H; ap.window = c.enc_window;
-        HIPCHK(b >= 2 ? launch_stream_attn_burst(ap, hd, s) : launch_stream_attn(ap, hd, s));
+        if (rg) HIPCHK(launch_stream_attn_group_burst(ap, rg->dev, *rg->host, R, hd, s));
+        else HIPCHK(b >= 2 ? launch_stream_attn_burst(ap, hd, s) : launch_stream_attn(ap, hd, s));
         VOXCHK(q4_linear_dev(cx, L.wo.w, L.wo.bias, w.att, QD, M, x, D, EPI_RESID, x, D));
         HIPCHK(launch_rms_norm(x, D, M, D, L.ffn_norm, nullptr, c.norm_eps, xn, D, s));
         VOXCHK(q4_linear_dev(cx, L.w13.w, nullptr, xn, D, M, w.ffn, F, EPI_SWIGLU));
         VOXCHK(q4_linear_dev(cx, L.w2.w, L.w2.bias, w.ffn, F, M, x, D, EPI_RESID, x, D));
     }
     HIPCHK(launch_rms_norm(x, D, M, D, m->enc_norm, nullptr, c.norm_eps, xn, D, s));
-    VOXCHK(q4_linear_dev(cx, m->ad0.w, nullptr, xn, D * R, n * b, w.ah, m->ad0.w.N, EPI_GELU));      // a slot's R rows viewed as one [R D] row (models/adapter.rs:108-122)
-    VOXCHK(q4_linear_dev(cx, m->ad2.w, nullptr, w.ah, m->ad0.w.N, n * b, w.arow, DD));
+    VOXCHK(q4_linear_dev(cx, m->ad0.w, nullptr, xn, D * R, NT, w.ah, m->ad0.w.N, EPI_GELU));      // a slot's R rows viewed as one [R D] row (models/adapter.rs:108-122)
+    VOXCHK(q4_linear_dev(cx, m->ad2.w, nullptr, w.ah, m->ad0.w.N, NT, w.arow, DD));
     return VOX_OK;
 }
 
@@ -4217,6 +4245,11 @@ struct vox_stream_group {
     // group read the rings at EVERY position: one code path below and above the load-time tables' lengths.
     bool endless = false;
     struct { float *dec = nullptr, *enc = nullptr, *h_dec = nullptr, *h_enc = nullptr; hipEvent_t copied = nullptr; bool pending = false; std::vector<float> inv_d, inv_e; } rope;
+    // A BURST group (vox_stream_group_create_burst; DESIGN.md section 8, "Bursts in stream groups"): burst > 1 -- a pass runs every due member's next
+    // b_z = min(ticks still due, burst) ticks as ONE encoder pass of 4 sum b_z rows and max b_z decode rounds (group_burst_round); its round buffers hold n burst ticks.
+    // d_bdesc: the round's descriptor on the device (a burst group alone), bdescs the ones uploaded by the call in flight, as orders.  burst_rounds / burst_member_ticks:
+    // the rounds run with some b_z >= 2 and the member-ticks inside them; plain_rounds: the rounds run as group_round (every group counts them); since create
+    int burst = 1; StreamBurstDesc* d_bdesc = nullptr; std::deque<StreamBurstDesc> bdescs; uint64_t burst_rounds = 0, burst_member_ticks = 0, plain_rounds = 0;
 };
 static const int GROUP_ROPE_ROWS = 64;         // rows per member of an endless group's decoder RoPE ring: a power of two >= the most ticks of one pass (feed_pass_max_ticks, asserted at create and per pass)
 static const int GROUP_LISTS_START = 2048;     // positions an endless group's member lists start with
@@ -4301,13 +4334,14 @@ static void group_release(vox_stream_group* g) {
     if (g->rope.copied) (void)hipEventDestroy(g->rope.copied);
     for (size_t i = 0; i < g->mem.size(); i++) group_member_drop_rate(g, (int)i);
     for (void* p : {(void*)g->keep.p, (void*)g->d_ingest, (void*)g->s16_stage, (void*)g->kring, (void*)g->vring, (void*)g->dec_k, (void*)g->dec_v, (void*)g->samples, (void*)g->ws, (void*)g->tokens, (void*)g->state, (void*)g->d_mem, (void*)g->d_order,
-                    (void*)g->qkv, (void*)g->att, (void*)g->logits, (void*)g->ssq, (void*)g->xf1, (void*)g->xf2, (void*)g->xf3, (void*)g->d_tab}) if (p) (void)hipFree(p);
+                    (void*)g->qkv, (void*)g->att, (void*)g->logits, (void*)g->ssq, (void*)g->xf1, (void*)g->xf2, (void*)g->xf3, (void*)g->d_tab, (void*)g->d_bdesc}) if (p) (void)hipFree(p);
     delete g;
 }
 // page_rows < 0: a slab group (pool_pages unread); else a paged one (0: the default page / the default pool)
 // endless (a paged group alone): max_positions is unread, the limit is the session limit 2^24
 static int32_t group_create(vox_model* m, const float* t_embed, int32_t n_members, const float* gains, const uint32_t* rates, int32_t enc_capacity_rows,
-                            int32_t max_positions, int32_t page_rows, int32_t pool_pages, vox_stream_group** out, bool endless = false, bool kv_bf16 = false) {
+                            int32_t max_positions, int32_t page_rows, int32_t pool_pages, vox_stream_group** out, bool endless = false, bool kv_bf16 = false, int burst = 1) {
+    ARGCHK(burst >= 1 && burst <= VOX_STREAM_BURST_MAX, "burst_ticks %d out of range (1..%d)", burst, VOX_STREAM_BURST_MAX);
     ARGCHK(n_members >= 1 && n_members <= GROUP_MAX, "n_members %d out of range (1..%d)", n_members, GROUP_MAX); ARGCHK(m && t_embed && out, "null argument");
     for (int i = 0; gains && i < n_members; i++) ARGCHK(std::isfinite(gains[i]), "gain of member %d is not finite", i);
     for (int i = 0; rates && i < n_members; i++) {      // every rate is checked before anything is allocated
@@ -4318,11 +4352,13 @@ static int32_t group_create(vox_model* m, const float* t_embed, int32_t n_member
     const vox_model_cfg& c = m->cfg; vox_ctx* cx = m->ctx; hipStream_t s = cx->stream;
     const bool paged = page_rows >= 0;
     ARGCHK(!endless || paged, "internal: an endless group is a paged one"); ARGCHK(!kv_bf16 || paged, "internal: a bf16 K/V pool belongs to a paged group");
-    StreamGeom sg; VOXCHK(stream_geometry(m, enc_capacity_rows, endless ? 0 : max_positions, paged ? INT32_MAX : GROUP_DEFAULT_POSITIONS, &sg));      // (paged, 0: the session limit)
+    StreamGeom sg; VOXCHK(stream_geometry(m, enc_capacity_rows, endless ? 0 : max_positions, paged ? INT32_MAX : GROUP_DEFAULT_POSITIONS, &sg, burst));      // (paged, 0: the session limit)
     if (endless) {
         ARGCHK(c.dec_window >= 0, "an endless group needs a sliding decoder window");
         // a pass runs at most the ticks whose samples the 65 536-sample ring holds: each of them has a row of its own in the member's RoPE rings
         ARGCHK(feed_pass_max_ticks(c.reshape_factor) <= GROUP_ROPE_ROWS, "internal: a pass may run %d ticks, the RoPE rings hold %d rows per member", feed_pass_max_ticks(c.reshape_factor), GROUP_ROPE_ROWS);
+        // a burst round's attention reads the R b RoPE rows of a member's next b ticks in one launch: the pass's refill has written them, and they are distinct ring rows
+        ARGCHK(GROUP_ROPE_ROWS * c.reshape_factor >= 4 * burst, "internal: a burst of %d ticks reads %d encoder RoPE rows, a member's ring holds %d", burst, 4 * burst, GROUP_ROPE_ROWS * c.reshape_factor);
         sg.max_pos = STREAM_POS_LIMIT;
     }
     if (paged) {
@@ -4341,7 +4377,7 @@ static int32_t group_create(vox_model* m, const float* t_embed, int32_t n_member
                                    "a paged group (vox_stream_group_create_paged) has no such limit", sg.max_pos, most);
     }
     VOXCHK(enc_stream_rope_ensure(m));
-    vox_stream_group* g = new vox_stream_group(); g->m = m; g->ctx = cx; g->t_embed.assign(t_embed, t_embed + c.dec_dim); g->n = n_members; g->g = sg; g->endless = endless; g->kv_bf16 = kv_bf16;
+    vox_stream_group* g = new vox_stream_group(); g->m = m; g->ctx = cx; g->t_embed.assign(t_embed, t_embed + c.dec_dim); g->n = n_members; g->g = sg; g->endless = endless; g->kv_bf16 = kv_bf16; g->burst = burst;
     const size_t N = (size_t)n_members; const int D = c.dec_dim, QD = c.dec_heads * c.dec_head_dim, W = QD + 2 * c.dec_kv_heads * c.dec_head_dim, maxp = sg.max_pos;
     g->ring_layer = (size_t)c.enc_heads * sg.cap * c.enc_head_dim; g->ring_member = (size_t)c.enc_layers * g->ring_layer;
     g->seq_stride = (size_t)c.dec_kv_heads * maxp * c.dec_head_dim; g->layer_stride = N * g->seq_stride;
@@ -4350,13 +4386,14 @@ static int32_t group_create(vox_model* m, const float* t_embed, int32_t n_member
         if (endless) g->pool.init_ring(n_members, page_rows, c.dec_window, pool_pages, STREAM_POS_LIMIT); else g->pool.init(n_members, page_rows, c.dec_window, pool_pages, maxp);
         g->page_floats = (size_t)c.dec_kv_heads * page_rows * c.dec_head_dim; g->seq_stride = g->page_floats; g->layer_stride = (size_t)pool_pages * g->page_floats;
     }
-    const size_t ws_b = stream_ws_carve(m, n_members, nullptr, nullptr) * 4, slab_b = (size_t)c.dec_layers * g->layer_stride * (kv_bf16 ? 2 : 4);
+    const size_t ws_b = stream_ws_carve(m, n_members, nullptr, nullptr, burst) * 4, slab_b = (size_t)c.dec_layers * g->layer_stride * (kv_bf16 ? 2 : 4);
     hipError_t e = hipSuccess;
     auto A = [&](void** q, size_t nb, bool zero) { if (e == hipSuccess) { e = hipMalloc(q, nb); if (e == hipSuccess) { g->bytes += nb; if (zero) e = hipMemsetAsync(*q, 0, nb, s); } } };
     A((void**)&g->kring, N * g->ring_member * 4, false); A((void**)&g->vring, N * g->ring_member * 4, false); A((void**)&g->dec_k, slab_b, true); A((void**)&g->dec_v, slab_b, true);
     A((void**)&g->samples, N * STREAM_SAMPLE_RING * 4, true); A((void**)&g->ws, ws_b, true); if (!endless) A((void**)&g->tokens, N * (maxp + 2) * 4, true); A((void**)&g->state, N * sizeof(int) * STRM_WORDS, true);
     A((void**)&g->d_mem, N * sizeof(StreamMember), true); A((void**)&g->d_order, 5 * GROUP_MAX * 4, true);
     if (paged) A((void**)&g->d_tab, N * (size_t)g->pool.tab_len * 4, false); A((void**)&g->d_ingest, sizeof(GroupIngest), true);
+    if (burst > 1) A((void**)&g->d_bdesc, sizeof(StreamBurstDesc), true);
     A((void**)&g->qkv, (size_t)GROUP_MAX * W * 4, true); A((void**)&g->att, (size_t)GROUP_MAX * QD * 4, true); A((void**)&g->logits, (size_t)GROUP_MAX * c.vocab * 4, true);
     A((void**)&g->ssq, (size_t)q4_skinny_resid_xf_parts(D) * 16 * 4, true); A((void**)&g->xf1, xf_bytes(D), true); A((void**)&g->xf2, xf_bytes(QD), true); A((void**)&g->xf3, xf_bytes(c.dec_ffn), true);
     g->h_mem.resize(N); g->mem.resize(N);
@@ -4411,6 +4448,23 @@ extern "C" int32_t vox_stream_group_create_kv(vox_model* m, const float* t_embed
     ARGCHK(page_rows >= 0, "page_rows %d is negative", page_rows);
     return group_create(m, t_embed, n_members, gains, rates, enc_capacity_rows, endless ? 0 : max_positions, page_rows, pool_pages, out, endless != 0, kv_dtype == VOX_KV_BF16);
 }
+extern "C" int32_t vox_stream_group_create_burst(vox_model* m, const float* t_embed, int32_t n_members, const float* gains, const uint32_t* rates, int32_t enc_capacity_rows,
+                                                 int32_t max_positions, int32_t paged, int32_t page_rows, int32_t pool_pages, int32_t endless, int32_t kv_dtype, int32_t burst_ticks,
+                                                 vox_stream_group** out) {
+    ARGCHK(m && t_embed && out, "null argument");
+    ARGCHK(burst_ticks >= 1 && burst_ticks <= VOX_STREAM_BURST_MAX, "burst_ticks %d out of range (1..%d)", burst_ticks, VOX_STREAM_BURST_MAX);
+    ARGCHK(paged == 0 || paged == 1, "paged %d is neither 0 nor 1", paged); ARGCHK(endless == 0 || endless == 1, "endless %d is neither 0 nor 1", endless);
+    ARGCHK(kv_dtype == VOX_KV_F32 || kv_dtype == VOX_KV_BF16, "kv_dtype %d is neither VOX_KV_F32 (0) nor VOX_KV_BF16 (1)", kv_dtype);
+    ARGCHK(paged || (!page_rows && !pool_pages && !endless && kv_dtype == VOX_KV_F32), "a slab group (paged 0) takes no page_rows, pool_pages, endless or bf16 pool");
+    ARGCHK(page_rows >= 0, "page_rows %d is negative", page_rows);
+    ARGCHK(!endless || max_positions == 0, "an endless group takes no max_positions (%d): its members go on to the session limit", max_positions);
+    return group_create(m, t_embed, n_members, gains, rates, enc_capacity_rows, endless ? 0 : max_positions, paged ? page_rows : -1, pool_pages, out, endless != 0, kv_dtype == VOX_KV_BF16, burst_ticks);
+}
+extern "C" int32_t vox_stream_group_burst_info(const vox_stream_group* g, int64_t out[4]) {
+    ARGCHK(g && out, "null argument");
+    out[0] = g->burst; out[1] = (int64_t)g->burst_rounds; out[2] = (int64_t)g->burst_member_ticks; out[3] = (int64_t)g->plain_rounds;
+    return VOX_OK;
+}
 extern "C" int32_t vox_stream_group_pool(const vox_stream_group* g, int64_t out[4], int32_t* held_or_null) {
     ARGCHK(g && out, "null argument");
     if (!g->paged) return fail(VOX_ERR_UNSUPPORTED, "a slab group has no page pool (vox_stream_group_create_paged makes a paged one)");
@@ -4458,12 +4512,15 @@ extern "C" int32_t vox_stream_group_info(const vox_stream_group* g, int32_t memb
     return VOX_OK;
 }
 
-// one round: a tick of the first n_r members of the pass's order
-static int32_t group_round(vox_stream_group* g, const StreamWs& w, int n_r) {
-    vox_model* m = g->m; const vox_model_cfg& c = m->cfg; hipStream_t s = g->ctx->stream; const int R = c.reshape_factor;
+static StreamRound group_stream_round(const vox_stream_group* g, int n_r) {
     StreamRound r{g->d_mem, g->d_order, n_r, g->g.cap, g->ring_layer, g->mel, g->g.left};
-    if (g->endless) { r.rope = g->rope.enc; r.rope_stride = GROUP_ROPE_ROWS * R; r.rope_mask = r.rope_stride - 1; }      // every position: the member's ring row (group_rope_refill)
-    VOXCHK(stream_encode_round(m, w, r, nullptr, nullptr));
+    if (g->endless) { r.rope = g->rope.enc; r.rope_stride = GROUP_ROPE_ROWS * g->m->cfg.reshape_factor; r.rope_mask = r.rope_stride - 1; }      // every position: the member's ring row (group_rope_refill)
+    return r;
+}
+// the decode half of a round for the first n_r members of the pass's order: the embed (row r's adapter row is w.arow[r]; bd: decode round t of a burst round, the row is
+// w.arow[bd->tick0[r] + t]), xf_chain on the group's decoder cache, the advance, the records
+static int32_t group_decode_round(vox_stream_group* g, const StreamWs& w, int n_r, const StreamBurstDesc* bd = nullptr, int t = 0) {
+    vox_model* m = g->m; const vox_model_cfg& c = m->cfg; hipStream_t s = g->ctx->stream; const int R = c.reshape_factor;
     XfBufs xb{}; xb.h = w.h; xb.qkv = g->qkv; xb.att = g->att; xb.logits = g->logits; xb.ssq = g->ssq; xb.xf1 = g->xf1; xb.xf2 = g->xf2; xb.xf3 = g->xf3;
     xb.k = g->dec_k; xb.v = g->dec_v; xb.layer_stride = g->layer_stride; xb.seq_stride = g->seq_stride; xb.max_seq = g->endless ? 0 : g->g.max_pos; xb.pos = g->d_pos; xb.kv_row = g->d_kv_row;      // (a paged step never reads max_seq)
     StreamPages pg{g->d_tab, g->pool.tab_len, g->pool.shift, g->d_kv_page, g->d_kv_in, g->endless ? g->pool.tab_len : 0};
@@ -4473,11 +4530,38 @@ static int32_t group_round(vox_stream_group* g, const StreamWs& w, int n_r) {
         xb.page_tab = g->d_tab; xb.page_tab_stride = g->pool.tab_len; xb.page_shift = g->pool.shift; xb.page_floats = (long)g->page_floats; xb.kv_page = g->d_kv_page; xb.kv_in = g->d_kv_in;
         xb.score_rows = c.dec_window >= 0 ? std::min(g->g.max_pos, c.dec_window + 1) : g->g.max_pos;
     }
-    HIPCHK(launch_stream_group_embed(m->tok.w, g->d_mem, g->d_order, n_r, w.arow, c.dec_dim, w.h, g->xf1, m->dec[0].attn_norm, g->ssq, g->d_pos, g->d_kv_row, s, g->paged ? &pg : nullptr));
+    if (bd) HIPCHK(launch_stream_group_embed_burst(m->tok.w, g->d_mem, g->d_order, n_r, w.arow, bd, t, c.dec_dim, w.h, g->xf1, m->dec[0].attn_norm, g->ssq, g->d_pos, g->d_kv_row, s, g->paged ? &pg : nullptr));
+    else HIPCHK(launch_stream_group_embed(m->tok.w, g->d_mem, g->d_order, n_r, w.arow, c.dec_dim, w.h, g->xf1, m->dec[0].attn_norm, g->ssq, g->d_pos, g->d_kv_row, s, g->paged ? &pg : nullptr));
     VOXCHK(xf_chain(m, xb, 0, n_r, 0, 0, true, 0, s));
     HIPCHK(launch_stream_group_advance(g->logits, c.vocab, g->d_mem, g->d_order, n_r, R, 4 * R, g->g.cap, s));
     if (g->n_scored > 0) HIPCHK(launch_stream_score(g->logits, c.vocab, g->d_mem, g->d_order, n_r, VOX_PREFIX_TOKENS, s));      // slots of unscored members return at once
     if (g->n_alts > 0) HIPCHK(launch_stream_alts(g->logits, c.vocab, g->d_mem, g->d_order, n_r, VOX_PREFIX_TOKENS, s));      // (the same)
+    return VOX_OK;
+}
+// one round: a tick of the first n_r members of the pass's order
+static int32_t group_round(vox_stream_group* g, const StreamWs& w, int n_r) {
+    VOXCHK(stream_encode_round(g->m, w, group_stream_round(g, n_r), nullptr, nullptr));
+    g->plain_rounds++;
+    return group_decode_round(g, w, n_r);
+}
+// one BURST round of a burst group: the first n_r members of the pass's order run b[z] ticks each (descending, b[0] >= 2) -- ONE encoder pass of R sum b rows
+// (stream_encode_round's ragged form; the round's descriptor goes up once and stays alive until the call's synchronisation), then the b[0] decode rounds one by one:
+// decode round t serves the members with b[z] > t, a prefix of the order.  The encoder reads every member's state block as its first tick of the round finds it; the
+// b[z] advance launches leave it as b[z] ticks would.
+static int32_t group_burst_round(vox_stream_group* g, const StreamWs& w, int n_r, const int* b) {
+    ARGCHK(g->burst > 1 && g->d_bdesc && n_r >= 1 && n_r <= GROUP_MAX && b[0] >= 2 && b[0] <= g->burst, "internal: a burst round of %d members, %d ticks at most (burst_ticks %d)", n_r, b[0], g->burst);
+    g->bdescs.emplace_back(); StreamBurstDesc& d = g->bdescs.back(); std::memset(&d, 0, sizeof d);
+    int ticks = 0;
+    for (int z = 0; z < n_r; z++) { ARGCHK(b[z] >= 1 && (z == 0 || b[z] <= b[z - 1]), "internal: slot %d of a burst round runs %d ticks", z, b[z]); d.tick0[z] = ticks; d.b[z] = b[z]; ticks += b[z]; }
+    HIPCHK(hipMemcpyAsync(g->d_bdesc, &d, sizeof d, hipMemcpyHostToDevice, g->ctx->stream));      // the round's one descriptor upload
+    const StreamRagged rg{g->d_bdesc, &d, ticks};
+    VOXCHK(stream_encode_round(g->m, w, group_stream_round(g, n_r), nullptr, nullptr, b[0], 1, &rg));
+    int n_t = n_r;
+    for (int t = 0; t < b[0]; t++) {
+        while (b[n_t - 1] <= t) n_t--;
+        VOXCHK(group_decode_round(g, w, n_t, g->d_bdesc, t));
+    }
+    g->burst_rounds++; g->burst_member_ticks += (uint64_t)ticks;
     return VOX_OK;
 }
 // A group's call -- advance, its 16-bit form, peek -- is group_run, in four units: group_plan_entries (every check, nothing changed), then per pass group_stage_pass
@@ -4619,7 +4703,13 @@ static int32_t group_run_rounds(vox_stream_group* g, const StreamWs& w, GroupDue
     for (size_t i = 0; i < due.size(); i++) ord[i] = due[i].second;
     HIPCHK(hipMemcpyAsync(g->d_order, ord.data(), sizeof(int) * GROUP_MAX, hipMemcpyHostToDevice, g->ctx->stream));      // the pass's one order upload
     int n_r = (int)due.size();
-    for (int r = 0; r < due[0].first; r++) {
+    if (g->burst > 1) {      // a burst group: round k runs the next min(ticks still due, burst) ticks of every member that has one (group_burst_rounds); all ones: a plain round
+        int dues[GROUP_MAX], b[GROUP_MAX];
+        for (size_t i = 0; i < due.size(); i++) dues[i] = due[i].first;
+        for (int k = 0; (n_r = group_burst_rounds(dues, (int)due.size(), g->burst, k, b)) > 0; k++) {
+            if (b[0] == 1) VOXCHK(group_round(g, w, n_r)); else VOXCHK(group_burst_round(g, w, n_r, b));
+        }
+    } else for (int r = 0; r < due[0].first; r++) {
         while (due[(size_t)n_r - 1].first <= r) n_r--;
         VOXCHK(group_round(g, w, n_r));
     }
@@ -4637,7 +4727,7 @@ static int32_t group_drain(vox_stream_group* g, vox_stream_feed* feeds, const Gr
     }
     if (keep) HIPCHK(launch_stream_keep(*keep, 1, s));
     HIPCHK(hipStreamSynchronize(s));      // the call's one synchronisation: every fed member's ids and records land
-    g->orders.clear(); g->ingests.clear();
+    g->orders.clear(); g->ingests.clear(); g->bdescs.clear();
     for (size_t k = 0; k < call.fs.size(); k++) {
         outs[k].settle();
         feeds[k].n_ids = outs[k].due; if (feeds[k].finish) outs[k].feed->finished = true;      // (a peek's entries carry no finish flag)
@@ -4646,7 +4736,7 @@ static int32_t group_drain(vox_stream_group* g, vox_stream_feed* feeds, const Gr
 }
 // the passes: write what fits into every fed member's rings, run the rounds that became due, repeat (a push may be larger than the rings; a peek is one pass)
 static int32_t group_passes(vox_stream_group* g, GroupCall& call) {
-    StreamWs w; stream_ws_carve(g->m, g->n, g->ws, &w); GroupDue due;
+    StreamWs w; stream_ws_carve(g->m, g->n, g->ws, &w, g->burst); GroupDue due;
     for (int pass = 0;; pass++) {
         const GroupFeed* open = nullptr; bool idle = false;
         for (const GroupFeed& e : call.fs) if (!open && feed_open(g->mem[e.member].feed, e.plan)) open = &e;
@@ -4697,8 +4787,10 @@ static int32_t group_run(vox_stream_group* g, vox_stream_feed* feeds, int32_t n_
     // a peek: the peeking members are the ring keep's slots, their numbers the first 16 ints of the save area
     const StreamKeepParams keep = ring_keep(c, g->d_mem, reinterpret_cast<const int*>(g->keep.p), n, keep_rows, g->g.cap, g->keep.p + GROUP_MAX);
     std::vector<GroupMark> was; for (const GroupFeed& e : call.fs) was.push_back(GroupMark{g->mem[e.member].feed.mark(), g->mem[e.member].steps});
+    const uint64_t rounds_was[3] = {g->burst_rounds, g->burst_member_ticks, g->plain_rounds};      // (a peek's rounds are not counted, as a solo burst stream's)
     const int32_t r = group_body(g, feeds, call, &keep, peek_scores);
-    if (r != VOX_OK) { (void)launch_stream_keep(keep, 1, s); (void)hipStreamSynchronize(s); g->orders.clear(); g->ingests.clear(); }      // a failed tail is taken back as well
+    g->burst_rounds = rounds_was[0]; g->burst_member_ticks = rounds_was[1]; g->plain_rounds = rounds_was[2];
+    if (r != VOX_OK) { (void)launch_stream_keep(keep, 1, s); (void)hipStreamSynchronize(s); g->orders.clear(); g->ingests.clear(); g->bdescs.clear(); }      // a failed tail is taken back as well
     for (int k = 0; k < n; k++) { GroupMember& me = g->mem[call.fs[(size_t)k].member]; me.feed.rewind(was[(size_t)k].feed); me.steps = was[(size_t)k].steps; }
     if (g->paged) {      // the tail's pages go back: the pool, the tables and the peak are what they were (the device entries too, behind the tail in stream order)
         std::vector<int64_t> ends; for (int member : took) ends.push_back(g->pool.mem[(size_t)member].end);

@@ -142,7 +142,31 @@ extern "C" int32_t vox_stream_peek_ids(size_t n_samples, uint32_t sample_rate, i
 // growth, the verification limit).  The smallest of the three, and at least 1: a burst never spans a stop, and a tick is always a burst of 1.
 namespace vox_host {
 int stream_burst_len(int64_t due, int burst, int64_t pos, int64_t next_stop) { return (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(due, burst), next_stop - pos)); }
+// ---- the rounds of a burst group's pass ("Bursts in stream groups"): from the members' ticks due in the pass, sorted descending, round k gives
+// the first n_r = #{due_z > k B} members b_z = min(due_z - k B, B) ticks; returns n_r (0: the pass is over), b[0 .. n_r) descending.  ceil(max due / B) rounds.  A group's
+// host never acts between the ticks of a pass (list growth, the RoPE refill, the pages and the position limits are settled in front of it): there is no next_stop cut.
+int group_burst_rounds(const int* due, int n, int burst, int k, int* b) {
+    int n_r = 0;
+    for (int z = 0; z < n; z++) { const int64_t left = (int64_t)due[z] - (int64_t)k * burst; if (left <= 0) break; b[n_r++] = (int)std::min<int64_t>(left, burst); }
+    return n_r;
+}
 }  // namespace vox_host
+extern "C" int32_t vox_stream_group_burst_rounds(const int32_t* due, int32_t n, int32_t burst, int32_t* out, int32_t max_rounds, int32_t* n_rounds) {
+    ARGCHK(due && n_rounds && (out || max_rounds == 0), "null argument"); ARGCHK(n >= 1 && n <= 16, "n %d out of range (1..16)", n);
+    ARGCHK(burst >= 1 && burst <= VOX_STREAM_BURST_MAX, "burst_ticks %d out of range (1..%d)", burst, VOX_STREAM_BURST_MAX); ARGCHK(max_rounds >= 0, "max_rounds %d is negative", max_rounds);
+    for (int z = 0; z < n; z++) {
+        ARGCHK(due[z] >= 1 && due[z] <= 65536, "due[%d] = %d out of range (1..65536: a member of a pass has a tick due)", z, due[z]);
+        ARGCHK(z == 0 || due[z] <= due[z - 1], "due[%d] = %d above due[%d] = %d: the pass's members are sorted by ticks due, descending", z, due[z], z - 1, due[z - 1]);
+    }
+    const int rounds = (due[0] + burst - 1) / burst;
+    ARGCHK(rounds <= max_rounds, "%d rounds: the output buffer holds %d", rounds, max_rounds);
+    for (int k = 0; k < rounds; k++) {
+        int32_t* row = out + (size_t)17 * k; std::fill(row, row + 17, 0);
+        row[0] = group_burst_rounds(due, n, burst, k, row + 1);
+    }
+    *n_rounds = rounds;
+    return VOX_OK;
+}
 extern "C" int32_t vox_stream_burst_len(int64_t due, int32_t burst, int64_t pos, int64_t next_stop) { return stream_burst_len(due, burst, pos, next_stop); }
 extern "C" int32_t vox_stream_group_pages_for(int64_t positions, int32_t page_rows, int32_t window, int32_t* first_page, int32_t* n_pages) {
     ARGCHK(first_page && n_pages, "null argument"); ARGCHK(positions >= 0 && positions <= ((int64_t)1 << 30), "positions %lld out of range", (long long)positions);

@@ -115,4 +115,5 @@ FeedPass feed_pass(FeedState& f, FeedPlan& p, int R, long left, size_t in_cap);
 int32_t peek_second_pass(const char* who);
 int32_t peek_max_ticks(const FeedState& f, int R, int due, const char* who, int* T);
 int stream_burst_len(int64_t due, int burst, int64_t pos, int64_t next_stop);
+int group_burst_rounds(const int* due, int n, int burst, int k, int* b);
 }  // namespace vox_host

@@ -473,6 +473,20 @@ hipError_t launch_stream_attn(const StreamAttnParams& p, int hd, hipStream_t s);
 hipError_t launch_stream_attn_burst(const StreamAttnParams& p, int hd, hipStream_t s);
 // launches enqueued by launch_stream_attn_burst (vox_debug_stream_attn_burst_launches); attn_form_counts does not count them
 unsigned long long stream_attn_burst_launches();
+// ---- a BURST ROUND of a stream group ("Bursts in stream groups"): slot z of the round runs b[z] ticks (1 .. 16, descending over z), its rows
+// packed behind the slots before it -- its first tick is tick0[z] = b[0] + .. + b[z - 1], its encoder rows start at row rpt * tick0[z].  One descriptor per round,
+// uploaded once; the kernels below read it on the device.
+struct StreamBurstDesc { int tick0[16]; int b[16]; };
+// the RAGGED burst attention: launch_stream_attn_burst with a row count per slot.  Slot z's M_z = rpt * b[z] rows of qkv and out start at row rpt * tick0[z]; grid
+// (heads, ceil(max M_z / 4), n), tiles at or beyond M_z leave at once.  For every slot the launch leaves in `out` and in every word of that session's rings the bits
+// b[z] launches of launch_stream_attn with M = 4 leave; sessions outside `order[0 .. n)` keep every ring word.  a.M is unread.  host: the descriptor's host copy, checked
+// before the launch (b 1 .. 16, tick0 the running sum, rpt * b <= 64, cap > window + max M_z, a RoPE ring of at least max M_z rows): a refused call launches nothing.
+// Counted by stream_attn_burst_launches.
+struct StreamAttnGroupParams : StreamAttnParams { const StreamBurstDesc* desc; int rpt; };
+hipError_t launch_stream_attn_group_burst(const StreamAttnParams& a, const StreamBurstDesc* desc, const StreamBurstDesc& host, int rpt, int hd, hipStream_t s);
+// the pack of a burst round's conv rows: slot z's first rpt * b[z] rows of src (slots src_slot_rows rows apart, D floats per row, D % 4 == 0) to rows rpt * tick0[z] ..
+// of dst -- the encoder input, slot after slot.  max_b: the largest b of the round (the grid)
+hipError_t launch_stream_burst_pack(const float* src, int src_slot_rows, const StreamBurstDesc* desc, int n, int rpt, int max_b, int D, float* dst, hipStream_t s);
 // rows 0 .. rows-1 of every layer's ring from token-major k | v rows (the model's prefix state: [layers][rows][k row | v row])
 hipError_t launch_stream_ring_init(const float* kv, int layers, int rows, int n_heads, int hd, int cap, float* kring, float* vring, hipStream_t s);
 // h = audio_row + embed(tokens[STRM_POS]); the adapter row is also kept in audio_keep[STRM_POS % keep_rows] (an engine hand-off timeout re-runs the decode steps from there)
@@ -490,6 +504,9 @@ hipError_t launch_stream_advance(const float* part_val, const int* part_idx, int
 struct StreamPages { const int* tab; int tab_stride, shift; int* page_out; int* in_page_out; int tab_len; };
 hipError_t launch_stream_group_embed(Q4W tok, const StreamMember* mem, const int* order, int n, const float* audio, int D, float* h, uint16_t* xf, const float* xf_w,
                                      float* ssq_out, int* pos, int* kv_row, hipStream_t s, const StreamPages* pages = nullptr);
+// launch_stream_group_embed for decode round t of a burst round: row r's audio row is row desc->tick0[r] + t of `audio` (tick t of slot r); everything else as above
+hipError_t launch_stream_group_embed_burst(Q4W tok, const StreamMember* mem, const int* order, int n, const float* audio, const StreamBurstDesc* desc, int t, int D, float* h, uint16_t* xf,
+                                           const float* xf_w, float* ssq_out, int* pos, int* kv_row, hipStream_t s, const StreamPages* pages = nullptr);
 // a paged member's seed: rows 0 .. rows-1 of src_k / src_v [layers][kv_heads][rows][hd] into the pages tab[0 ..] of the pool (layers layer_stride floats apart)
 // kv_bf16: pool_k / pool_v point at uint16_t pools (layer_stride in 16-bit elements), the rows are rounded by kv_bf16_round
 hipError_t launch_stream_pages_seed(const float* src_k, const float* src_v, int layers, int kv_heads, int rows, int hd, const int* tab, int page_shift, size_t layer_stride,

@@ -31,6 +31,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <mutex>
 #include <unordered_map>
 
@@ -4768,8 +4769,11 @@ hipError_t launch_stream_attn(const StreamAttnParams& p, int hd, hipStream_t s) 
 //     (jlo - j0_q + kg) mod G, since the window starts of a tile differ by constants), and it meets that sum's rows in ascending order: the thread carries that sum
 // The burst's own k rows 0 .. last row of the tile are rotated into LDS by the workgroup itself and its v rows are read from qkv (the bits the ring receives), so no
 // workgroup reads a ring row another one writes in this launch: with cap > window + M the rows written now held positions below every window of the burst.
-template <int HD>
-__global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_attn_burst_kernel(const StreamAttnParams p) {
+// P = StreamAttnGroupParams: the RAGGED form (a burst group's round, launch_stream_attn_group_burst) -- slot z has its own row count M_z = rpt * b[z] and its rows start
+// at row rpt * tick0[z] of qkv and out (the device descriptor p.desc); a tile at or beyond M_z leaves at once.  Everything behind those two integers is the code above.
+template <int HD, class P = StreamAttnParams>
+__global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_attn_burst_kernel(const P p) {
+    constexpr bool RAGGED = !std::is_same<P, StreamAttnParams>::value;
     constexpr int HALF = HD / 2, G = 256 / HD, TQ = 4;
     __shared__ __attribute__((aligned(16))) float qs[TQ][HD];
     __shared__ __attribute__((aligned(16))) float kn[64][HD];
@@ -4777,10 +4781,13 @@ __global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_attn_burst_kernel(co
     __shared__ float red[TQ][G][HD];
     __shared__ float wred[TQ][4];
     const int h = blockIdx.x, m0 = blockIdx.y * TQ, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int T = min(TQ, p.M - m0);      // the tile's query rows m0 .. m0 + T - 1
+    int M, row0;      // the slot's row count and its first row in qkv / out
+    if constexpr (RAGGED) { M = p.rpt * p.desc->b[blockIdx.z]; row0 = p.rpt * p.desc->tick0[blockIdx.z]; if (m0 >= M) return; }      // (uniform over the workgroup, in front of every barrier)
+    else { M = p.M; row0 = blockIdx.z * p.M; }
+    const int T = min(TQ, M - m0);      // the tile's query rows m0 .. m0 + T - 1
     const StreamMember& me = p.mem[p.order[blockIdx.z]];
     float* __restrict__ kring = me.kring + p.ring_off; float* __restrict__ vring = me.vring + p.ring_off;
-    const float* __restrict__ qkv = p.qkv + (size_t)blockIdx.z * p.M * p.qkv_stride;      // the slot's M rows
+    const float* __restrict__ qkv = p.qkv + (size_t)row0 * p.qkv_stride;      // the slot's M rows
     const int enc_pos = me.state[STRM_ENC_POS], QD = p.n_heads * HD, nkr = m0 + T;       // k rows 0 .. nkr - 1, then the T query rows
     for (int i = tid; i < (nkr + T) * HALF; i += 256) {
         const int r = i / HALF, j = i - r * HALF; const bool isq = r >= nkr; const int row = isq ? m0 + (r - nkr) : r;
@@ -4868,7 +4875,7 @@ __global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_attn_burst_kernel(co
         float o = red[q][0][dd];
 #pragma unroll
         for (int c = 1; c < G; c++) o += red[q][c][dd];
-        p.out[((size_t)blockIdx.z * p.M + m0 + q) * p.out_stride + h * HD + dd] = o / sum[q];
+        p.out[((size_t)row0 + m0 + q) * p.out_stride + h * HD + dd] = o / sum[q];
     }
 }
 static std::atomic<unsigned long long> g_stream_attn_burst_launches;      // a counter of its own: the slots of attn_form_counts keep their numbers
@@ -4879,6 +4886,41 @@ hipError_t launch_stream_attn_burst(const StreamAttnParams& p, int hd, hipStream
     g_stream_attn_burst_launches.fetch_add(1, std::memory_order_relaxed);      // (behind every refusal: a refused call counts no launch)
     if (hd == 64) stream_attn_burst_kernel<64><<<dim3(p.n_heads, (p.M + 3) / 4, p.n), dim3(256), 0, s>>>(p);
     else stream_attn_burst_kernel<128><<<dim3(p.n_heads, (p.M + 3) / 4, p.n), dim3(256), 0, s>>>(p);
+    return hipGetLastError();
+}
+// a burst round's descriptor as the host holds it: n slots, b in 1 .. 16, tick0 the running sum of the b before it.  *max_b: the largest b
+static bool stream_burst_desc_ok(const StreamBurstDesc& d, int n, int* max_b) {
+    if (n < 1 || n > 16) return false;
+    int sum = 0, most = 0;
+    for (int z = 0; z < n; z++) { if (d.b[z] < 1 || d.b[z] > 16 || d.tick0[z] != sum) return false; sum += d.b[z]; most = max(most, d.b[z]); }
+    *max_b = most; return true;
+}
+hipError_t launch_stream_attn_group_burst(const StreamAttnParams& a, const StreamBurstDesc* desc, const StreamBurstDesc& host, int rpt, int hd, hipStream_t s) {
+    int max_b = 0;
+    if (!desc || rpt < 1 || !stream_burst_desc_ok(host, a.n, &max_b)) return hipErrorInvalidValue;
+    const int Mx = rpt * max_b;      // the largest M_z
+    if ((hd != 64 && hd != 128) || Mx > 64 || !a.mem || !a.order || a.window < 0 || a.window + 1 > 1024 || a.cap <= a.window + Mx || (a.ring_off & 3) || a.rope_mask < 0 ||
+        (a.rope_mask & (a.rope_mask + 1)) || (a.rope_mask && a.rope_mask + 1 < Mx) || (a.rope_stride && (!a.rope_mask || a.rope_stride < a.rope_mask + 1))) return hipErrorInvalidValue;
+    StreamAttnGroupParams p{}; static_cast<StreamAttnParams&>(p) = a; p.M = 0; p.desc = desc; p.rpt = rpt;
+    g_stream_attn_burst_launches.fetch_add(1, std::memory_order_relaxed);      // (behind every refusal: a refused call counts no launch)
+    if (hd == 64) stream_attn_burst_kernel<64, StreamAttnGroupParams><<<dim3(a.n_heads, (Mx + 3) / 4, a.n), dim3(256), 0, s>>>(p);
+    else stream_attn_burst_kernel<128, StreamAttnGroupParams><<<dim3(a.n_heads, (Mx + 3) / 4, a.n), dim3(256), 0, s>>>(p);
+    return hipGetLastError();
+}
+// the pack of a burst round: one workgroup column per slot, float4 copies of the slot's valid rows (rows past rpt * b[z] of a slot are never read)
+__global__ __launch_bounds__(256) void stream_burst_pack_kernel(const float* __restrict__ src, long src_slot_floats, const StreamBurstDesc* __restrict__ desc, int row_floats4, int rpt,
+                                                                float* __restrict__ dst) {
+    const int z = blockIdx.y;
+    const long n4 = (long)rpt * desc->b[z] * row_floats4, i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n4) return;
+    const float4* from = reinterpret_cast<const float4*>(src + (size_t)z * src_slot_floats);
+    float4* to = reinterpret_cast<float4*>(dst) + (size_t)rpt * desc->tick0[z] * row_floats4;
+    to[i] = from[i];
+}
+hipError_t launch_stream_burst_pack(const float* src, int src_slot_rows, const StreamBurstDesc* desc, int n, int rpt, int max_b, int D, float* dst, hipStream_t s) {
+    if (!src || !desc || !dst || n < 1 || n > 16 || rpt < 1 || max_b < 1 || max_b > 16 || D < 4 || (D & 3) || src_slot_rows < rpt * max_b) return hipErrorInvalidValue;
+    const long most4 = (long)rpt * max_b * (D / 4);
+    stream_burst_pack_kernel<<<dim3((unsigned)((most4 + 255) / 256), n), dim3(256), 0, s>>>(src, (long)src_slot_rows * D, desc, D / 4, rpt, dst);
     return hipGetLastError();
 }
 
@@ -4973,6 +5015,36 @@ hipError_t launch_stream_group_embed(Q4W tok, const StreamMember* mem, const int
         if (!pages->tab || !pages->page_out || !pages->in_page_out || pages->tab_stride < 1 || pages->shift < 4 || pages->shift > 10 || pages->tab_len < 0 || pages->tab_len > pages->tab_stride) return hipErrorInvalidValue;
         stream_group_embed_kernel<true><<<dim3(n), dim3(256), 0, s>>>(tok, mem, order, audio, D, h, xf, xf_w, ssq_out, pos, kv_row, *pages);
     } else stream_group_embed_kernel<false><<<dim3(n), dim3(256), 0, s>>>(tok, mem, order, audio, D, h, xf, xf_w, ssq_out, pos, kv_row, StreamPages{});
+    return hipGetLastError();
+}
+// the same row for decode round t of a BURST round: slot r's audio row is the adapter row of its tick t, row desc->tick0[r] + t of the round's packed adapter rows
+template <bool PAGED>
+__global__ __launch_bounds__(256) void stream_group_embed_burst_kernel(Q4W tok, const StreamMember* __restrict__ mem, const int* __restrict__ order, const float* __restrict__ audio,
+                                                                       const StreamBurstDesc* __restrict__ desc, int t, int D, float* __restrict__ h, uint16_t* __restrict__ xf,
+                                                                       const float* __restrict__ xf_w, float* __restrict__ ssq_out, int* __restrict__ pos_out, int* __restrict__ kv_row_out,
+                                                                       const StreamPages pg) {
+    __shared__ float wsum[4];
+    const int r = blockIdx.x, member = order[r];
+    const StreamMember& me = mem[member];
+    const int pos = me.state[STRM_POS];
+    float* hrow = h + (size_t)r * D;
+    embed_row(tok, me.tokens[pos], audio + (size_t)(desc->tick0[r] + t) * D, hrow, D);
+    xf_row_ssq(hrow, xf_w, D, xf, r, ssq_out, wsum);
+    if (threadIdx.x == 0) {
+        pos_out[r] = pos; kv_row_out[r] = member;
+        if (PAGED) {
+            const int q = pos >> pg.shift;
+            pg.page_out[r] = pg.tab[(size_t)member * pg.tab_stride + (pg.tab_len > 0 ? q % pg.tab_len : q)]; pg.in_page_out[r] = pos & ((1 << pg.shift) - 1);
+        }
+    }
+}
+hipError_t launch_stream_group_embed_burst(Q4W tok, const StreamMember* mem, const int* order, int n, const float* audio, const StreamBurstDesc* desc, int t, int D, float* h, uint16_t* xf,
+                                           const float* xf_w, float* ssq_out, int* pos, int* kv_row, hipStream_t s, const StreamPages* pages) {
+    if (n < 1 || n > 16 || !mem || !order || !audio || !desc || t < 0 || t > 15 || !h || !xf || !xf_w || !ssq_out || !pos || !kv_row || (D & 127)) return hipErrorInvalidValue;
+    if (pages) {
+        if (!pages->tab || !pages->page_out || !pages->in_page_out || pages->tab_stride < 1 || pages->shift < 4 || pages->shift > 10 || pages->tab_len < 0 || pages->tab_len > pages->tab_stride) return hipErrorInvalidValue;
+        stream_group_embed_burst_kernel<true><<<dim3(n), dim3(256), 0, s>>>(tok, mem, order, audio, desc, t, D, h, xf, xf_w, ssq_out, pos, kv_row, *pages);
+    } else stream_group_embed_burst_kernel<false><<<dim3(n), dim3(256), 0, s>>>(tok, mem, order, audio, desc, t, D, h, xf, xf_w, ssq_out, pos, kv_row, StreamPages{});
     return hipGetLastError();
 }
 // seed of a paged member (prefix_rows_into's counterpart): rows 0 .. rows-1 of every (layer, kv head) plane of the prefix state, src [layers][kv heads][rows][hd], into

@@ -364,6 +364,24 @@ def stream_attn_burst(ctx, qkv, kring, vring, order, enc_pos, rows, window, thet
     return stream_attn(ctx, qkv, kring, vring, order, enc_pos, rows, window, theta, layer, rope_rows, rope_per_member, _entry="vox_debug_stream_attn_burst")
 
 
+def stream_attn_group_burst(ctx, qkv, kring, vring, order, enc_pos, rows_per_slot, window, theta, layer=0, rope_rows=0, rope_per_member=False):
+    """vox_debug_stream_attn_group_burst: the RAGGED burst attention of a burst group's round -- slot z has rows_per_slot[z] rows (multiples of 4 in 4..64: its b_z
+    ticks), qkv [sum rows, 3 * n_heads * hd] and out hold the slots' rows back to back.  ONE launch; for every slot it leaves the bits rows_per_slot[z] / 4 chained
+    stream_attn launches of 4 rows leave, and members outside `order` keep their rings.  Returns (out [sum rows, n_heads * hd], kring, vring)."""
+    qkv = _f32(qkv); kring = _f32(kring).copy(); vring = _f32(vring).copy()
+    order = np.ascontiguousarray(order, dtype=np.int32); enc_pos = np.ascontiguousarray(enc_pos, dtype=np.int32); rps = np.ascontiguousarray(rows_per_slot, dtype=np.int32)
+    if qkv.ndim != 2 or kring.ndim != 5 or kring.shape != vring.shape or order.ndim != 1 or rps.shape != order.shape or enc_pos.shape != (kring.shape[0],):
+        raise VoxError(1, "stream_attn_group_burst: bad shapes")
+    n_members, layers, n_heads, cap, hd = kring.shape
+    if qkv.shape != (int(np.maximum(rps, 0).sum()), 3 * n_heads * hd):
+        raise VoxError(1, "stream_attn_group_burst: qkv is not [sum rows_per_slot][3 * n_heads * head_dim]")
+    d = StreamAttnDesc(n_slots=len(order), n_members=n_members, rows=int(rps.max()) if rps.size else 0, n_heads=n_heads, head_dim=hd, window=int(window), cap=cap, layers=layers,
+                       layer=int(layer), rope_rows=int(rope_rows), rope_per_member=int(bool(rope_per_member)), theta=float(theta), order=order.ctypes.data, enc_pos=enc_pos.ctypes.data)
+    out = np.empty((qkv.shape[0], n_heads * hd), np.float32)
+    check(lib().vox_debug_stream_attn_group_burst(ctx.h, C.byref(d), _ptr(rps), _ptr(qkv), _ptr(kring), _ptr(vring), _ptr(out)))
+    return out, kring, vring
+
+
 def stream_attn_burst_launches() -> int:
     """vox_debug_stream_attn_burst_launches: launches of the burst kernel so far (a counter of its own, in no slot of attn_launches)."""
     v = C.c_uint64(); check(lib().vox_debug_stream_attn_burst_launches(C.byref(v)))
@@ -376,6 +394,17 @@ STREAM_BURST_MAX = 16      # VOX_STREAM_BURST_MAX
 def stream_burst_len(due: int, burst: int, pos: int, next_stop: int) -> int:
     """vox_stream_burst_len: the next burst of a pass with `due` ticks still to run at position pos -- max(1, min(due, burst, next_stop - pos))."""
     return int(lib().vox_stream_burst_len(int(due), int(burst), int(pos), int(next_stop)))
+
+
+def stream_group_burst_rounds(due, burst: int) -> list:
+    """vox_stream_group_burst_rounds: the rounds of a burst group's pass whose members have `due` ticks due (sorted descending, 1..16 of them) at burst_ticks = burst --
+    one tuple of b_z per round: round k gives the first #{due_z > k burst} members min(due_z - k burst, burst) ticks.  ceil(max due / burst) rounds; a round of
+    ones is a plain group round."""
+    d = np.ascontiguousarray([int(v) for v in due], dtype=np.int32)
+    cap = max(1, -(-int(d.max()) // max(int(burst), 1))) if d.size else 1
+    out = np.zeros((cap, 17), dtype=np.int32); n = C.c_int32()
+    check(lib().vox_stream_group_burst_rounds(_ptr(d), int(d.size), int(burst), _ptr(out), cap, C.byref(n)))
+    return [tuple(int(x) for x in row[1:1 + row[0]]) for row in out[:n.value]]
 
 
 def stream_ring_init(ctx, kv, kring, vring):
@@ -915,8 +944,11 @@ class LiveStreamGroup:
     KV_DTYPES = {"f32": 0, "bf16": 1}      # VOX_KV_F32, VOX_KV_BF16
 
     def __init__(self, model, t_embed, n_members, gains=None, enc_capacity_rows=0, max_positions=0, sample_rates=None, page_rows=None, pool_pages=None, endless=False,
-                 kv_dtype=None):
+                 kv_dtype=None, burst=None):
+        if burst is not None and (isinstance(burst, bool) or not isinstance(burst, (int, np.integer)) or not 1 <= int(burst) <= STREAM_BURST_MAX):
+            raise VoxError(1, f"create_stream_group: burst {burst!r} is not an integer in 1..{STREAM_BURST_MAX}")
         self.model = model; self.h = C.c_void_p(); self.n_members = int(n_members); self._tap_max = {}; self._rates = {}
+        self.burst = None if burst is None else int(burst)      # given: a burst group (vox_stream_group_create_burst) of whatever kind the other arguments make
         if kv_dtype is not None and kv_dtype not in self.KV_DTYPES:
             raise ValueError(f"kv_dtype {kv_dtype!r}: a stream group's K/V pool holds 'f32' or 'bf16'")
         self.kv_dtype = kv_dtype      # given: a paged group made by vox_stream_group_create_kv, whose pool() names the dtype; None: the group the other arguments make
@@ -928,7 +960,14 @@ class LiveStreamGroup:
         if g is not None and g.size != self.n_members:
             raise ValueError(f"{g.size} gains for {self.n_members} members")
         args = (model.h, _ptr(_f32(t_embed).reshape(-1)), self.n_members, None if g is None else _ptr(g))
-        if sample_rates is None and not self.paged:
+        if burst is not None:
+            r = np.ascontiguousarray([int(v) for v in (sample_rates if sample_rates is not None else [16000] * self.n_members)], dtype=np.uint32)
+            if r.size != self.n_members:
+                raise ValueError(f"{r.size} sample rates for {self.n_members} members")
+            check(lib().vox_stream_group_create_burst(*args, _ptr(r), int(enc_capacity_rows), int(max_positions), int(self.paged), int(page_rows or 0), int(pool_pages or 0),
+                                                      int(self.endless), self.KV_DTYPES[kv_dtype or "f32"], int(burst), C.byref(self.h)))
+            self._rates = {k: int(v) for k, v in enumerate(r) if int(v) != 16000}
+        elif sample_rates is None and not self.paged:
             check(lib().vox_stream_group_create(*args, int(enc_capacity_rows), int(max_positions), C.byref(self.h)))
         else:
             r = np.ascontiguousarray([int(v) for v in (sample_rates if sample_rates is not None else [16000] * self.n_members)], dtype=np.uint32)
@@ -1034,6 +1073,12 @@ class LiveStreamGroup:
     def info(self, member):
         v = (C.c_int64 * 8)(); check(lib().vox_stream_group_info(self.h, int(member), v))
         return dict(zip(("samples", "positions", "ids", "encoder_position", "ring_rows", "bytes", "engine_steps", "operator_steps"), (int(x) for x in v)))
+
+    def burst_info(self):
+        """vox_stream_group_burst_info: burst_ticks (1: a plain group), the burst rounds run (rounds in which some member ran 2 or more ticks), the member-ticks inside
+        them, the plain rounds run -- since create; a peek's rounds are not counted."""
+        v = (C.c_int64 * 4)(); check(lib().vox_stream_group_burst_info(self.h, v))
+        return dict(zip(("burst", "burst_rounds", "burst_member_ticks", "plain_rounds"), (int(x) for x in v)))
 
     def pool(self) -> dict:
         """vox_stream_group_pool of a paged group: page_rows, pool_pages, the free pages, the most pages ever in use, and held: the pages each member holds."""
@@ -1294,7 +1339,7 @@ class Q4VoxtralModel:
         return LiveStream(self, t_embed, gain, enc_capacity_rows, max_positions, sample_rate, endless, dec_ring_rows, burst)
 
     def create_stream_group(self, t_embed, n_members, gains=None, enc_capacity_rows=0, max_positions=0, sample_rates=None, page_rows=None, pool_pages=None,
-                            endless=False, kv_dtype=None) -> LiveStreamGroup:
+                            endless=False, kv_dtype=None, burst=None) -> LiveStreamGroup:
         """Up to 16 live sessions advanced together (vox_stream_group_create): advance({member: samples}, finish=()) -> {member: ids}, reset(member, gain), info(member),
         close().  gains: one per member (None: 1.0 each); max_positions 0: 2048 decoder positions per member (the group's decoder cache does not grow);
         sample_rates: what each member is fed (None: 16 kHz each; vox_stream_group_create_rates).
@@ -1304,7 +1349,7 @@ class Q4VoxtralModel:
         but go on to 2^24; max_positions must not be given (ValueError).  Everything of a paged group works unchanged.
         kv_dtype "f32" | "bf16" (vox_stream_group_create_kv; implies paged, as endless does; anything else: ValueError): what the K / V pool holds.  "bf16": 16-bit
         pages, half the memory and half the bytes the decode attention reads; ids and logits are close to, not equal to, the f32 group's.  pool() then names it."""
-        return LiveStreamGroup(self, t_embed, n_members, gains, enc_capacity_rows, max_positions, sample_rates, page_rows, pool_pages, endless, kv_dtype)
+        return LiveStreamGroup(self, t_embed, n_members, gains, enc_capacity_rows, max_positions, sample_rates, page_rows, pool_pages, endless, kv_dtype, burst)
 
     def transcribe_batch(self, samples_list, t_embed, device_ptrs=None, n_samples=None, norm_group=None, tap_units=None):
         """Batched whole-path transcription of independent utterances (<= 4096; wider than 16: continuous batching over decode slots): list of float32 sample arrays
