@@ -834,7 +834,8 @@ int32_t vox_stream_snapshot(vox_stream* s, void* blob, size_t cap, size_t* nbyte
 int32_t vox_stream_restore(vox_stream* s, const void* blob, size_t nbytes, int32_t mem_kind);
 
 /* ---- stream group: up to 16 live sessions advanced together (no reference counterpart) ---------------------------------------------------------------------------------
- * A vox_stream_group holds n_members member sessions on one model and one t_embed, each with its own gain, sample ring, encoder K / V ring and slice of the group's
+ * A vox_stream_group holds n_members member sessions on one model -- at one t_embed for all, or, made by vox_stream_group_create_t_embeds, each at its own (A DELAY PER
+ * MEMBER below) --, each with its own gain, sample ring, encoder K / V ring and slice of the group's
  * decoder cache.  vox_stream_group_advance feeds any subset of the members (f32 samples at each member's rate, host or device memory: mem_kind holds for the whole
  * call; vox_stream_group_advance_s16: signed 16-bit PCM) and advances them together: every weight matrix is read by ONE launch per tick for all members that have a tick due, and the call synchronises once.
  *   Contract: a member's schedule is vox_stream_schedule's on that member's own sample count; every call hands each fed member exactly the ids that became due, and a
@@ -999,6 +1000,39 @@ int32_t vox_stream_group_burst_rounds(const int32_t* due, int32_t n, int32_t bur
 int32_t vox_stream_group_snapshot_size(const vox_stream_group* g, int32_t member, size_t* nbytes);
 int32_t vox_stream_group_snapshot(vox_stream_group* g, int32_t member, void* blob, size_t cap, size_t* nbytes, int32_t mem_kind);
 int32_t vox_stream_group_restore(vox_stream_group* g, int32_t member, const void* blob, size_t nbytes, int32_t mem_kind);
+/* A DELAY PER MEMBER ("A delay per member").  The delay enters the computation through t_embed alone: the decoder's Ada scales
+ * 1 + w2(gelu(w0 t_embed)), one [dec_dim] vector per decoder layer, and the decoder half of the prefix state a member starts from.  Every other creator gives the group
+ * ONE t_embed; vox_stream_group_create_t_embeds takes vox_stream_group_create_burst's argument list with t_embeds [n_members][dec_dim], member i's t_embed in row i, and
+ * makes any group kind (slab, paged, endless paged, bf16 pool; burst_ticks 1: a plain group).  The group owns a device block [n_members][dec_layers][dec_dim] of Ada
+ * scales (dec_layers x dec_dim x 4 bytes per member, counted in vox_stream_group_info's bytes), filled per member at create and at reset with the bits
+ * vox_model_set_t_embed computes for the member's t_embed; the decode round's wo GEMM multiplies row r by the scales of the member in row r (one epilogue instantiation;
+ * no launch is added), and a member is seeded from the prefix state of its own t_embed.
+ *   Contract: member k's ids, logits and records are bit for bit those of member k of a group made by vox_stream_group_create_burst at member k's t_embed and given the
+ *   same calls; with n_members equal t_embeds the group IS that group, bit for bit.  advance and peek never select the model's t_embed: offline calls with their own
+ *   t_embed may be interleaved freely, and after create / reset the model's current t_embed and prefix state are those of the member seeded last (the side effect every
+ *   stream's create has).  Members with bit-equal t_embeds seeded one after another share one computation of the scales and of the prefix state.
+ *   vox_stream_group_reset_t_embed: the member's next utterance at another delay; gain as vox_stream_group_reset, sample_rate 0: the member keeps its rate, else as
+ *   vox_stream_group_reset_rate.  A refused call (null t_embed, member out of range, a rate vox_stream_create_rate refuses, a group of one t_embed:
+ *   VOX_ERR_UNSUPPORTED) leaves the member, its delay and its state as they were.  vox_stream_group_t_embed: the member's t_embed (any group; cap >= dec_dim floats).
+ *   Snapshot / restore: a member's blob carries the hash of the MEMBER's t_embed; a restore into a member at another t_embed is refused (VOX_ERR_INVALID, the message
+ *   names the member) before anything changes.  The blob format and VOX_SNAPSHOT_VERSION are unchanged.
+ * Not served: solo vox_stream sessions (they select the model's t_embed per call), the offline and batch paths, a change of delay inside an utterance, more than 16
+ * members, the batched persistent engine. */
+int32_t vox_stream_group_create_t_embeds(vox_model* m, const float* t_embeds /* [n_members][dec_dim] */, int32_t n_members, const float* gains /* null: 1.0 */,
+                                         const uint32_t* rates /* null: 16000 each */, int32_t enc_capacity_rows, int32_t max_positions /* endless: 0 */, int32_t paged,
+                                         int32_t page_rows /* 0: 256 */, int32_t pool_pages /* 0: the default */, int32_t endless, int32_t kv_dtype, int32_t burst_ticks,
+                                         vox_stream_group** out);
+int32_t vox_stream_group_reset_t_embed(vox_stream_group* g, int32_t member, float gain, uint32_t sample_rate /* 0: keep */, const float* t_embed);
+int32_t vox_stream_group_t_embed(const vox_stream_group* g, int32_t member, float* out, int32_t cap);
+/* debug (tests): ONE launch of the decode round's wo operator on caller data -- out [M][N] = x [M][K] W^T + resid [M][N] as f32 rows, xf_out the XF planes
+ * (2 (N / 128) 256 8 16-bit values) of out * xf_w [N] * scale, ssq_out [(N / 16)][16] the per-tile sums of squares of out.  scales holds n_sets vectors of N floats.
+ * order null: the per-column form, every row multiplied by scale set `set`; order [M] given: the per-row form of a group with a delay per member, row m multiplied by
+ * scale set order[m] (0 .. n_sets - 1, checked).  w: a Q4 tensor with K and N multiples of 128; M 1..16; host pointers. */
+typedef struct {
+    int32_t M, n_sets, set, reserved;
+} vox_resid_xf_desc;
+int32_t vox_debug_resid_xf(vox_ctx* ctx, const vox_q4* w, const vox_resid_xf_desc* desc, const float* x, const float* resid, const float* xf_w, const float* scales,
+                           const int32_t* order_or_null, float* out, uint16_t* xf_out, float* ssq_out);
 /* The live sessions' feed planner on its own (tests): host arithmetic only -- no context, no device, no model.  A fresh session fed at sample_rate (4 encoder rows per
  * position, the Voxtral left pad, no position limit to speak of) takes the calls (n_samples[c], finish[c] 0 / 1) exactly as vox_stream_push / _finish and a group's advance
  * plan and pass them, every due tick taken as run; finish[c] = 2 is a peek (n_samples[c] must be 0): planned as a finish, its one pass emitted, the session as it was.  One row of five words per pass: call index, input samples appended, 16 kHz samples that entered the 16 kHz ring (a

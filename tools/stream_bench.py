@@ -45,6 +45,9 @@
  * --group ... --page-rows R --kv bf16: the same run also times a paged group with a bf16 K/V pool (vox_stream_group_create_kv, VOX_KV_BF16) of the paged group's pages,
    pool and positions, each pass right behind the f32 paged group's: round medians, their difference per pass, launches per round, the growth of both rounds per pass
    (per `ticks` positions), and the bytes a member holds in both.
+ * --group ... --delays mixed: the same run also times a group with a DELAY PER MEMBER (vox_stream_group_create_t_embeds: member z at delay 2 + z), warmed like the
+   uniform group and timed the same way, pass i right behind the uniform group's pass i over the same positions: round medians, their difference per pass, launches
+   per round of both, and the device bytes the Ada block adds per member (dec_layers x dec_dim x 4, computed).
  * --memory-past-window --page-rows R: nothing is timed; 16 members of an endless paged group and of a bounded paged group with max_positions 16 384 are run past the
    decoder window by the same calls, and what they hold is read from pool() and info().
  * --endless (without --group): the tick of an ENDLESS session (vox_stream_create_endless) past the wrap of its decoder ring, next to a bounded session (max_positions 16 384) at the
@@ -165,6 +168,9 @@ def bench_groups(pkg, ctx, m, t, tm, a, widths, lines):
             if a.endless:      # the endless twin of the paged group (vox_stream_group_create_endless): the same pages, the same pool, the same positions
                 ge = m.create_stream_group(t, N, gains=[gain] * N, page_rows=a.page_rows, pool_pages=gp.pool()["pool_pages"], endless=True)
                 ge.advance({k: x[:pos] for k in range(N)}); endl = []; ke = 0; wall_e = []
+        if a.delays:      # the mixed twin of the uniform group: member z at delay 2 + z, the same samples
+            gd = m.create_stream_group(None, N, gains=[gain] * N, delays=[2 + z for z in range(N)])
+            gd.advance({k: x[:pos] for k in range(N)}); mixed = []; kd = 0
         if sr:
             g2, g3 = (m.create_stream_group(t, N, gains=[gr] * N, sample_rates=[sr] * N) for _ in range(2)); rpos = per * (warm + 1)      # fed from host / device memory
             for gg in (g2, g3):
@@ -177,6 +183,8 @@ def bench_groups(pkg, ctx, m, t, tm, a, widths, lines):
             feeds = {k: seg for k in range(N)}
             grp.append(tm.ms(lambda: g.advance(feeds)) / a.ticks); k2 = launch_counts(pkg)
             ks += sum(k1) - sum(k0); kg += sum(k2) - sum(k1)
+            if a.delays:      # right behind the uniform pass, over the same positions
+                mixed.append(tm.ms(lambda: gd.advance(feeds)) / a.ticks); kd += sum(launch_counts(pkg)) - sum(k2)
             if a.page_rows:
                 k2p = launch_counts(pkg); w0 = time.perf_counter(); paged.append(tm.ms(lambda: gp.advance(feeds)) / a.ticks); wall_p.append(1e3 * (time.perf_counter() - w0) / a.ticks)
                 kp += sum(launch_counts(pkg)) - sum(k2p)
@@ -215,6 +223,12 @@ def bench_groups(pkg, ctx, m, t, tm, a, widths, lines):
         rows.append((N, rnd, tick))
         lines += [f"group of {N:2d}: round median {rnd:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in grp) + f"   solo tick median {tick:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in solo),
                   f"  round / ({N} x solo tick) = {rnd / (N * tick):.3f}   per member and tick {rnd / N:.3f} ms   launches per round {lg:.0f} (solo tick {ls:.0f})"]
+        if a.delays:
+            assert gd.info(N - 1)["positions"] == 38 + warm + a.ticks * a.passes
+            gd.close(); rd_ = statistics.median(mixed)
+            lines += [f"  mixed delays 2 .. {1 + N}, group of {N:2d}, each pass right behind the uniform one's: round median {rd_:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in mixed) +
+                      f"   difference to the uniform round {rd_ - rnd:+.3f} ms ({100 * (rd_ - rnd) / rnd:+.2f} %), per pass " + " ".join(f"{v - w:+.3f}" for v, w in zip(mixed, grp)),
+                      f"  launches per round: mixed {kd / ticks + fixed_enc + 2:.0f}, uniform {lg:.0f}; the Ada block adds {c.dec_layers * c.dec_dim * 4} device bytes per member (dec_layers x dec_dim x 4, computed)"]
         if a.page_rows:
             assert gp.info(N - 1)["positions"] == 38 + warm + a.ticks * a.passes
             pl = gp.pool(); ip = gp.info(0); gp.close(); rp = statistics.median(paged)
@@ -485,6 +499,7 @@ def main():
     ap.add_argument("--alternatives", type=int, default=0, metavar="K", help="also time a stream (with --group: and a group) with alternatives on at k = K (1..8), as --scores does")
     ap.add_argument("--page-rows", type=int, default=0, metavar="R", help="with --group: also time a paged group (pages of R rows, the default pool) pass by pass next to the slab group")
     ap.add_argument("--kv", choices=("f32", "bf16"), default="f32", help="with --group and --page-rows: bf16 also times a paged group with a bf16 K/V pool pass by pass behind the f32 paged group")
+    ap.add_argument("--delays", choices=("mixed",), default=None, help="with --group: also time a group with a delay per member (member z at delay 2 + z) pass by pass behind the uniform group")
     ap.add_argument("--peek", action="store_true", help="time vox_stream_peek next to the same number of ordinary ticks of the same session (nothing else is measured)")
     ap.add_argument("--endless", action="store_true", help="time the tick of an endless session past the wrap of its decoder ring next to a bounded session at the same positions (nothing else is measured)")
     ap.add_argument("--memory-past-window", action="store_true", help="with --page-rows R: what 16 members of an endless paged group and of a bounded paged group (max_positions 16384) hold past "
@@ -518,6 +533,8 @@ def main():
         ap.error("--peek is a mode of its own")
     if a.kv != "f32" and not (a.group and a.page_rows):
         ap.error("--kv bf16 times a bf16 PAGED group: give --group and --page-rows")
+    if a.delays and (not a.group or bursts):
+        ap.error("--delays mixed applies with --group N[,N...]")
     if a.page_rows and not a.group and not a.memory_past_window:
         ap.error("--page-rows applies with --group")
     if (a.rate or a.s16) and not a.group or (a.s16 and not a.rate):

@@ -262,6 +262,13 @@ SIGNATURES = {
     "vox_stream_group_snapshot": (i32, [vp, i32, vp, sz, P(sz), i32]),
     "vox_stream_group_restore": (i32, [vp, i32, vp, sz, i32]),
     "vox_debug_snapshot_kv": (i32, [vp, vp, vp, vp, vp, i32]),      # (ctx, vox_snapshot_kv_desc, cache_k, cache_v, blob, restore): ONE launch of the blob's K / V kernel
+    # a delay per member: (model, t_embeds [n][dec_dim], n_members, gains, rates, cap, max_pos, paged, page_rows, pool_pages, endless, kv_dtype, burst_ticks, out);
+    # (group, member, gain, sample_rate or 0, t_embed); (group, member, out, cap)
+    "vox_stream_group_create_t_embeds": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, P(vp)]),
+    "vox_stream_group_reset_t_embed": (i32, [vp, i32, f32, u32, vp]),
+    "vox_stream_group_t_embed": (i32, [vp, i32, vp, i32]),
+    # (ctx, w, vox_resid_xf_desc, x, resid, xf_w, scales, order or null, out, xf_out, ssq_out): ONE launch of the wo GEMM's EPI_RESID_XF epilogue
+    "vox_debug_resid_xf": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "vox_transcribe_audio_scored": (i32, [vp, vp, sz, vp, vp, i32, P(i32), vp, vp, i32, i32]),
     "vox_transcribe_batch_scored": (i32, [vp, i32, P(vp), P(sz), vp, vp, P(vp), P(i32), P(i32), vp, vp, i32, i32]),
 }

@@ -101,12 +101,13 @@ def transcribe_one(pkg, path, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed
     return " ".join(texts)
 
 
-def write_words(out, pkg, path, ids, scores, tokenizer, rate, alternatives=None):
+def write_words(out, pkg, path, ids, scores, tokenizer, rate, alternatives=None, delay=None):
     """--live-words: one JSON line per word of a file that has ended (pkg.words: text, first_id, last_id, due_s, logprob, min_margin) + the file's path; with
-    --live-alternatives also the word's entropy and the alternatives of its weakest id."""
+    --live-alternatives also the word's entropy and the alternatives of its weakest id; delay (--live-delays): the delay of the member that ran the file."""
     import json
     for w in pkg.words(ids, scores, tokenizer, sample_rate=rate, alternatives=alternatives):
-        out.write(json.dumps(dict(w, file=path), ensure_ascii=False) + "\n")
+        w = dict(w, file=path) if delay is None else dict(w, file=path, delay=int(delay))
+        out.write(json.dumps(w, ensure_ascii=False) + "\n")
     out.flush()
 
 
@@ -169,9 +170,26 @@ def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_
         stream.close()
 
 
+def parse_live_delays(text, n_members):
+    """--live-delays: "6,10,..." -> one integer delay (>= 0) per member; a single value serves every member.  ValueError when a value is no such integer or the count
+    is neither 1 nor n_members."""
+    parts = [p.strip() for p in str(text).split(",")]
+    try:
+        delays = [int(p) for p in parts]
+    except ValueError:
+        raise ValueError(f"--live-delays takes integers separated by commas, got {text!r}") from None
+    if any(d < 0 for d in delays):
+        raise ValueError(f"--live-delays takes delays >= 0, got {text!r}")
+    if len(delays) not in (1, n_members):
+        raise ValueError(f"--live-delays names {len(delays)} delays for {n_members} members: one per member, or one for all")
+    return delays * n_members if len(delays) == 1 else delays
+
+
 def transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, chunk_ms, n_members, words_out=None, peek=False, alts_k=0, page_rows=None, pool_pages=None, endless=False,
-                          suspend_every=0, kv_dtype=None):
-    """(kv_dtype, --live-kv f32 | bf16: the paged group's K/V pool dtype, vox_stream_group_create_kv; the lines have the same form.)
+                          suspend_every=0, kv_dtype=None, delays=None):
+    """(delays, --live-delays: one delay per member -- the group is made by vox_stream_group_create_t_embeds, member k's files run at delays[k], and every --live-words
+    line gains "delay"; None: every member at t_embed.)
+    (kv_dtype, --live-kv f32 | bf16: the paged group's K/V pool dtype, vox_stream_group_create_kv; the lines have the same form.)
     --live-group N: the files N at a time through one stream group (vox_stream_group) in pieces of `chunk_ms` milliseconds: every call feeds each busy member its
     next piece, a file that ends (its member fed with finish) frees the member for the next file in input order.  Gains and lines as transcribe_live's (16 kHz: other
     rates are resampled first).  -> {file index: text}; a file that cannot be read is left out (the one-by-one path reports it).  words_out (--live-words): every
@@ -181,7 +199,7 @@ def transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, chunk_ms, 
     member is refused at 43 minutes); the lines are the same.  suspend_every (--live-suspend-every N): after every N calls each busy member is snapshotted to host
     memory, reset, and restored from its blob (vox_stream_group_snapshot / _restore); the lines are the same."""
     step = max(1, int(round(16000 * chunk_ms / 1000.0)))
-    group = model.create_stream_group(t_embed, n_members, page_rows=page_rows, pool_pages=pool_pages, endless=endless, kv_dtype=kv_dtype)
+    group = model.create_stream_group(None if delays else t_embed, n_members, page_rows=page_rows, pool_pages=pool_pages, endless=endless, kv_dtype=kv_dtype, delays=delays)
     text = lambda ids: tokenizer.decode([t for t in ids if t >= 1000]).strip()
     texts = {}; busy = {}; nxt = 0; calls = 0      # busy: member -> [file index, samples, offset, ids]
     try:
@@ -214,7 +232,7 @@ def transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, chunk_ms, 
             for k in last:
                 b = busy.pop(k); texts[b[0]] = text(b[3])
                 if words_out is not None:
-                    write_words(words_out, pkg, paths[b[0]], b[3], group.scores(k), tokenizer, 16000, group.alternatives(k) if alts_k else None)
+                    write_words(words_out, pkg, paths[b[0]], b[3], group.scores(k), tokenizer, 16000, group.alternatives(k) if alts_k else None, delay=delays[k] if delays else None)
             for k, tail in (group.peek(sorted(busy)) if peek and busy else {}).items():
                 b = busy[k]; log(f"  ~[{paths[b[0]]} {min(b[2], b[1].size) / 16000:8.2f} s] {text(b[3] + [int(v) for v in tail])}")
             calls += 1
@@ -381,6 +399,9 @@ def main(argv=None):
     ap.add_argument("--live-kv", choices=("f32", "bf16"), default=None, help="with --live-group: what the group's decoder K/V pool holds (vox_stream_group_create_kv; makes the "
                     "group a paged one).  bf16: 16-bit pages, half the memory per page and half the bytes the decode attention reads; the text may differ from an f32 group's "
                     "where the model's choice between two tokens is close")
+    ap.add_argument("--live-delays", metavar="D,D,...", help="with --live-group: one delay per member (N values; a single value serves all), overriding --delay: the group is "
+                    "made with a t_embed per member (vox_stream_group_create_t_embeds), member k's files run at the k-th delay, and every --live-words line gains the "
+                    "member's delay")
     ap.add_argument("--live-burst", type=int, default=0, metavar="B", help="with --live: a burst stream (vox_stream_create_burst) -- a chunk that makes several ticks due (--live-chunk-ms "
                     "above 160) runs them in bursts of up to B (1..16): one encoder pass for the burst, then its decode steps")
     ap.add_argument("--live-endless", action="store_true", help="with --live: an endless session (vox_stream_create_endless) -- no limit at "
@@ -431,6 +452,13 @@ def main(argv=None):
         ap.error("--live-page-rows / --live-pool-pages apply with --live-group")
     if a.live_kv is not None and not a.live_group:
         ap.error("--live-kv applies with --live-group")
+    if a.live_delays is not None and not a.live_group:
+        ap.error("--live-delays applies with --live-group")
+    if a.live_delays is not None:
+        try:
+            a.live_delays = parse_live_delays(a.live_delays, a.live_group)
+        except ValueError as e:
+            ap.error(str(e))
     if a.live_page_rows not in (None, 0) and not (16 <= a.live_page_rows <= 1024 and a.live_page_rows & (a.live_page_rows - 1) == 0):
         ap.error("--live-page-rows takes a power of two in 16..1024 (0: 256)")
     if a.live_pool_pages is not None and a.live_pool_pages < 0:
@@ -535,7 +563,7 @@ def main(argv=None):
                         write_word_lines(rec_out, runner.words.get((i, k), []))
     if a.live_group:
         try:
-            texts = transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_group, words_out, a.live_peek, a.live_alternatives, a.live_page_rows, a.live_pool_pages, a.live_endless, a.live_suspend_every, a.live_kv)
+            texts = transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_group, words_out, a.live_peek, a.live_alternatives, a.live_page_rows, a.live_pool_pages, a.live_endless, a.live_suspend_every, a.live_kv, a.live_delays)
         except Exception as e:      # the files fall back to one live session each
             log(f"Error in the stream group: {e}"); texts = {}
             if words_out is not None:      # the files' words come again with their lines

@@ -1470,6 +1470,9 @@ struct XfBufs {
     int page_tab_len; const float* rope_ring; int rope_mask;
     // a bf16 pool (a bf16 paged group): k / v point at uint16_t pools, layer_stride and page_floats count 16-bit elements.  0 everywhere else
     int kv_bf16;
+    // a stream group with a delay per member: ada_rows [member][dec_layers][dec_dim] every member's Ada scales (ada_stride floats per member), ada_order the rows' members --
+    // the wo GEMM's epilogue multiplies row r by member ada_order[r]'s scales (EPI_RESID_XF_ROWS).  null everywhere else: the model's one set, per column
+    const float* ada_rows; const int* ada_order; long ada_stride;
 };
 // the XF planes and ssq blocks of a step over n_grp groups (0: none, the group strides alone): from the pool, zeroed on s, bound to b
 struct XfPlanes {
@@ -1497,6 +1500,7 @@ static int32_t xf_chain(const vox_model* m, const XfBufs& b, int g0i, int ng, in
     const int parts_D = q4_skinny_resid_xf_parts(D), max_seq = b.max_seq, M = mtw ? 16 * mtw : ng;
     ARGCHK(!(b.page_tab && mtw), "internal: a paged cache runs the one-group chain (the wide step has no paged form)");
     ARGCHK(!b.kv_bf16 || b.page_tab, "internal: a bf16 K/V pool is a paged cache's");
+    ARGCHK(!b.ada_rows || (!mtw && b.ada_order), "internal: Ada scales per row run the one-group chain, with the rows' members");
     const int r0 = g0i * 16;      // the chain's first group: its planes, sums, rows, positions and cache slices (a wide chain's further groups follow at the group strides)
     uint16_t* xf1 = b.xf1 + (size_t)g0i * b.xf1_gs; uint16_t* xf2 = b.xf2 + (size_t)g0i * b.xf2_gs; uint16_t* xf3 = b.xf3 + (size_t)g0i * b.xf3_gs; float* ssq = b.ssq + (size_t)g0i * b.ssq_gs;
     float* hg = b.h + (size_t)r0 * D; float* qg = b.qkv + (size_t)r0 * W; const int* pg = b.pos + r0; const int* rg = b.kv_row ? b.kv_row + r0 : nullptr;
@@ -1532,6 +1536,7 @@ static int32_t xf_chain(const vox_model* m, const XfBufs& b, int g0i, int ng, in
         } else
         HIPCHK(launch_attn_decode(ap, hd, max_seq, sg, M));
         { GemmParams g{}; g.out = hg; g.out_stride = D; g.resid = hg; g.resid_stride = D; g.xf_out = xf1; g.xf_w = L.ffn_norm; g.xf_w2 = L.ada_mul; g.ssq_out = ssq;
+          if (b.ada_rows) { g.xf_w2 = b.ada_rows + (size_t)l * D; g.xf_w2_row = b.ada_order; g.xf_w2_stride = b.ada_stride; }      // every row its member's scales
           HIPCHK(gemm(g, L.wo.w, xf2, QD, EPI_RESID_XF)); }
         { GemmParams g{}; g.out = (float*)xf3; g.out_stride = F; g.ssq_part = ssq; g.n_part = parts_D; HIPCHK(gemm(g, L.w13.w, xf1, D, EPI_SWIGLU_XF)); }
         { GemmParams g{}; g.out = hg; g.out_stride = D; g.resid = hg; g.resid_stride = D; g.xf_out = xf1; g.ssq_out = ssq;
@@ -4191,7 +4196,7 @@ extern "C" int32_t vox_debug_snapshot_kv(vox_ctx* c, const vox_snapshot_kv_desc*
 }
 
 // ------------------------------------------------------------------------------------------------
-// Stream group (vox_stream_group; DESIGN.md section 8, "Stream groups"): N <= 16 member sessions on one model and one t_embed, advanced together.  A call knows every
+// Stream group (vox_stream_group; DESIGN.md section 8, "Stream groups"): N <= 16 member sessions on one model, at one t_embed or each at its own, advanced together.  A call knows every
 // fed member's due tick count d_i before it launches anything: the members sorted by d_i descending, round r runs ONE tick of the first n_r = #{d_i > r} of them --
 // stream_encode_round at 4 n_r rows (the code of a solo stream's tick) and, as the decode half, xf_chain at n_r rows on the group's decoder slab.  One upload (the
 // order) per pass, constant launch arguments within a pass except n_r, one synchronisation per call.  No engine runs here: no kept rows, no re-run, no verification.
@@ -4250,7 +4255,13 @@ struct vox_stream_group {
     // d_bdesc: the round's descriptor on the device (a burst group alone), bdescs the ones uploaded by the call in flight, as orders.  burst_rounds / burst_member_ticks:
     // the rounds run with some b_z >= 2 and the member-ticks inside them; plain_rounds: the rounds run as group_round (every group counts them); since create
     int burst = 1; StreamBurstDesc* d_bdesc = nullptr; std::deque<StreamBurstDesc> bdescs; uint64_t burst_rounds = 0, burst_member_ticks = 0, plain_rounds = 0;
+    // A group with a DELAY PER MEMBER (vox_stream_group_create_t_embeds; DESIGN.md section 8, "A delay per member"): member_te[i] is member i's t_embed (t_embed above is
+    // unread) and ada [n][dec_layers][dec_dim] holds every member's Ada scales -- the model's block as vox_model_set_t_embed(member i's t_embed) fills it, copied device
+    // to device when the member is seeded.  The decode round's wo epilogue reads row r's scales through the pass's order; a call never selects the model's t_embed.
+    // Every other group: ada == nullptr, member_te empty, and the rounds read the model's one set
+    float* ada = nullptr; std::vector<std::vector<float>> member_te;
 };
+static const std::vector<float>& group_t_embed(const vox_stream_group* g, int i) { return g->ada ? g->member_te[(size_t)i] : g->t_embed; }
 static const int GROUP_ROPE_ROWS = 64;         // rows per member of an endless group's decoder RoPE ring: a power of two >= the most ticks of one pass (feed_pass_max_ticks, asserted at create and per pass)
 static const int GROUP_LISTS_START = 2048;     // positions an endless group's member lists start with
 // entries [q0, q1) of a member's table mirror to the device, on the group's stream (the mirror stays where it is: the tables are sized at create)
@@ -4300,13 +4311,22 @@ static int32_t group_upload_members(vox_stream_group* g) {      // after a descr
     HIPCHK(hipStreamSynchronize(g->ctx->stream));
     return VOX_OK;
 }
+// (a group with a delay per member) member i's Ada scales: the model's block for the member's t_embed -- what the seed has just selected, or selects here -- device to device
+static int32_t group_member_ada(vox_stream_group* g, int i) {
+    if (!g->ada) return VOX_OK;
+    const vox_model_cfg& c = g->m->cfg; const size_t n = (size_t)c.dec_layers * c.dec_dim;
+    VOXCHK(vox_model_set_t_embed(g->m, g->member_te[(size_t)i].data()));      // (equal bits: returns at once)
+    HIPCHK(hipMemcpyAsync(g->ada + (size_t)i * n, g->m->ada_mul, n * 4, hipMemcpyDeviceToDevice, g->ctx->stream));
+    HIPCHK(hipStreamSynchronize(g->ctx->stream));
+    return VOX_OK;
+}
 static int32_t group_member_seed(vox_stream_group* g, int i) {
     if (g->paged) {      // every page the member holds goes back, the prefix rows go into fresh ones (the top of the stack: the pages just returned)
         const vox_model_cfg& c = g->m->cfg; GroupMember& me = g->mem[i]; int64_t q0, q1, t0, t1;
         ARGCHK(g->pool.held(i) + g->pool.n_free() >= (g->g.PC + g->pool.page_rows - 1) / g->pool.page_rows, "member %d: the pool has no pages for the seed", i);
         g->pool.release_all(i, &q0, &q1);
         if (!g->pool.take(i, g->g.PC, &t0, &t1)) return fail(VOX_ERR_INVALID, "internal: member %d: no pool pages for the seed", i);
-        VOXCHK(stream_seed(g->m, g->t_embed.data(), g->g.RC, g->g.PC, g->g.cap, g->h_mem[i].kring, g->h_mem[i].vring, nullptr, g->h_mem[i].tokens, g->h_mem[i].state, me.h_state,
+        VOXCHK(stream_seed(g->m, group_t_embed(g, i).data(), g->g.RC, g->g.PC, g->g.cap, g->h_mem[i].kring, g->h_mem[i].vring, nullptr, g->h_mem[i].tokens, g->h_mem[i].state, me.h_state,
                            [&]() -> int32_t {
                                if (g->endless) { VOXCHK(group_table_upload(g, i, q0, q1)); VOXCHK(group_table_upload(g, i, t0, t1)); }      // (the returned pages may lie anywhere in the ring; the seed's are entries 0 ..)
                                else VOXCHK(group_table_upload(g, i, 0, std::max(q1, t1)));
@@ -4314,15 +4334,15 @@ static int32_t group_member_seed(vox_stream_group* g, int i) {
                                                                g->pool.shift, g->layer_stride, g->dec_k, g->dec_v, g->ctx->stream, g->kv_bf16));
                                return VOX_OK; }));
         me.feed.restart(g->g.PC); me.steps = 0; me.sc.host.clear(); me.al.restart();
-        return VOX_OK;
+        return group_member_ada(g, i);
     }
     vox_cache view; view.m = g->m; view.ctx = g->ctx; view.k = g->dec_k + (size_t)i * g->seq_stride; view.v = g->dec_v + (size_t)i * g->seq_stride; view.max_seq = g->g.max_pos;
     view.layer_stride = g->layer_stride;      // the member's slice of the slab, seen as a cache whose layers lie layer_stride apart
     GroupMember& me = g->mem[i];
-    VOXCHK(stream_seed(g->m, g->t_embed.data(), g->g.RC, g->g.PC, g->g.cap, g->h_mem[i].kring, g->h_mem[i].vring, &view, g->h_mem[i].tokens, g->h_mem[i].state, me.h_state,
+    VOXCHK(stream_seed(g->m, group_t_embed(g, i).data(), g->g.RC, g->g.PC, g->g.cap, g->h_mem[i].kring, g->h_mem[i].vring, &view, g->h_mem[i].tokens, g->h_mem[i].state, me.h_state,
                        []() -> int32_t { return VOX_OK; }));
     me.feed.restart(g->g.PC); me.steps = 0; me.sc.host.clear(); me.al.restart();
-    return VOX_OK;
+    return group_member_ada(g, i);
 }
 static void group_release(vox_stream_group* g) {
     if (!g) return;
@@ -4334,13 +4354,15 @@ static void group_release(vox_stream_group* g) {
     if (g->rope.copied) (void)hipEventDestroy(g->rope.copied);
     for (size_t i = 0; i < g->mem.size(); i++) group_member_drop_rate(g, (int)i);
     for (void* p : {(void*)g->keep.p, (void*)g->d_ingest, (void*)g->s16_stage, (void*)g->kring, (void*)g->vring, (void*)g->dec_k, (void*)g->dec_v, (void*)g->samples, (void*)g->ws, (void*)g->tokens, (void*)g->state, (void*)g->d_mem, (void*)g->d_order,
-                    (void*)g->qkv, (void*)g->att, (void*)g->logits, (void*)g->ssq, (void*)g->xf1, (void*)g->xf2, (void*)g->xf3, (void*)g->d_tab, (void*)g->d_bdesc}) if (p) (void)hipFree(p);
+                    (void*)g->qkv, (void*)g->att, (void*)g->logits, (void*)g->ssq, (void*)g->xf1, (void*)g->xf2, (void*)g->xf3, (void*)g->d_tab, (void*)g->d_bdesc, (void*)g->ada}) if (p) (void)hipFree(p);
     delete g;
 }
 // page_rows < 0: a slab group (pool_pages unread); else a paged one (0: the default page / the default pool)
 // endless (a paged group alone): max_positions is unread, the limit is the session limit 2^24
+// per_member: t_embed holds [n_members][dec_dim], one delay per member (vox_stream_group_create_t_embeds); else one [dec_dim] vector for all
 static int32_t group_create(vox_model* m, const float* t_embed, int32_t n_members, const float* gains, const uint32_t* rates, int32_t enc_capacity_rows,
-                            int32_t max_positions, int32_t page_rows, int32_t pool_pages, vox_stream_group** out, bool endless = false, bool kv_bf16 = false, int burst = 1) {
+                            int32_t max_positions, int32_t page_rows, int32_t pool_pages, vox_stream_group** out, bool endless = false, bool kv_bf16 = false, int burst = 1,
+                            bool per_member = false) {
     ARGCHK(burst >= 1 && burst <= VOX_STREAM_BURST_MAX, "burst_ticks %d out of range (1..%d)", burst, VOX_STREAM_BURST_MAX);
     ARGCHK(n_members >= 1 && n_members <= GROUP_MAX, "n_members %d out of range (1..%d)", n_members, GROUP_MAX); ARGCHK(m && t_embed && out, "null argument");
     for (int i = 0; gains && i < n_members; i++) ARGCHK(std::isfinite(gains[i]), "gain of member %d is not finite", i);
@@ -4377,7 +4399,10 @@ static int32_t group_create(vox_model* m, const float* t_embed, int32_t n_member
                                    "a paged group (vox_stream_group_create_paged) has no such limit", sg.max_pos, most);
     }
     VOXCHK(enc_stream_rope_ensure(m));
-    vox_stream_group* g = new vox_stream_group(); g->m = m; g->ctx = cx; g->t_embed.assign(t_embed, t_embed + c.dec_dim); g->n = n_members; g->g = sg; g->endless = endless; g->kv_bf16 = kv_bf16; g->burst = burst;
+    vox_stream_group* g = new vox_stream_group(); g->m = m; g->ctx = cx; g->n = n_members;
+    if (per_member) for (int i = 0; i < n_members; i++) g->member_te.emplace_back(t_embed + (size_t)i * c.dec_dim, t_embed + (size_t)(i + 1) * c.dec_dim);
+    else g->t_embed.assign(t_embed, t_embed + c.dec_dim);
+    g->g = sg; g->endless = endless; g->kv_bf16 = kv_bf16; g->burst = burst;
     const size_t N = (size_t)n_members; const int D = c.dec_dim, QD = c.dec_heads * c.dec_head_dim, W = QD + 2 * c.dec_kv_heads * c.dec_head_dim, maxp = sg.max_pos;
     g->ring_layer = (size_t)c.enc_heads * sg.cap * c.enc_head_dim; g->ring_member = (size_t)c.enc_layers * g->ring_layer;
     g->seq_stride = (size_t)c.dec_kv_heads * maxp * c.dec_head_dim; g->layer_stride = N * g->seq_stride;
@@ -4394,6 +4419,7 @@ static int32_t group_create(vox_model* m, const float* t_embed, int32_t n_member
     A((void**)&g->d_mem, N * sizeof(StreamMember), true); A((void**)&g->d_order, 5 * GROUP_MAX * 4, true);
     if (paged) A((void**)&g->d_tab, N * (size_t)g->pool.tab_len * 4, false); A((void**)&g->d_ingest, sizeof(GroupIngest), true);
     if (burst > 1) A((void**)&g->d_bdesc, sizeof(StreamBurstDesc), true);
+    if (per_member) A((void**)&g->ada, N * c.dec_layers * c.dec_dim * 4, true);
     A((void**)&g->qkv, (size_t)GROUP_MAX * W * 4, true); A((void**)&g->att, (size_t)GROUP_MAX * QD * 4, true); A((void**)&g->logits, (size_t)GROUP_MAX * c.vocab * 4, true);
     A((void**)&g->ssq, (size_t)q4_skinny_resid_xf_parts(D) * 16 * 4, true); A((void**)&g->xf1, xf_bytes(D), true); A((void**)&g->xf2, xf_bytes(QD), true); A((void**)&g->xf3, xf_bytes(c.dec_ffn), true);
     g->h_mem.resize(N); g->mem.resize(N);
@@ -4460,6 +4486,27 @@ extern "C" int32_t vox_stream_group_create_burst(vox_model* m, const float* t_em
     ARGCHK(!endless || max_positions == 0, "an endless group takes no max_positions (%d): its members go on to the session limit", max_positions);
     return group_create(m, t_embed, n_members, gains, rates, enc_capacity_rows, endless ? 0 : max_positions, paged ? page_rows : -1, pool_pages, out, endless != 0, kv_dtype == VOX_KV_BF16, burst_ticks);
 }
+// the full-argument creator with a t_embed per member: every kind of group (burst_ticks 1: a plain one)
+extern "C" int32_t vox_stream_group_create_t_embeds(vox_model* m, const float* t_embeds, int32_t n_members, const float* gains, const uint32_t* rates, int32_t enc_capacity_rows,
+                                                    int32_t max_positions, int32_t paged, int32_t page_rows, int32_t pool_pages, int32_t endless, int32_t kv_dtype, int32_t burst_ticks,
+                                                    vox_stream_group** out) {
+    ARGCHK(m && t_embeds && out, "null argument");
+    ARGCHK(n_members >= 1 && n_members <= GROUP_MAX, "n_members %d out of range (1..%d)", n_members, GROUP_MAX);      // (before t_embeds is read as n_members rows)
+    ARGCHK(burst_ticks >= 1 && burst_ticks <= VOX_STREAM_BURST_MAX, "burst_ticks %d out of range (1..%d)", burst_ticks, VOX_STREAM_BURST_MAX);
+    ARGCHK(paged == 0 || paged == 1, "paged %d is neither 0 nor 1", paged); ARGCHK(endless == 0 || endless == 1, "endless %d is neither 0 nor 1", endless);
+    ARGCHK(kv_dtype == VOX_KV_F32 || kv_dtype == VOX_KV_BF16, "kv_dtype %d is neither VOX_KV_F32 (0) nor VOX_KV_BF16 (1)", kv_dtype);
+    ARGCHK(paged || (!page_rows && !pool_pages && !endless && kv_dtype == VOX_KV_F32), "a slab group (paged 0) takes no page_rows, pool_pages, endless or bf16 pool");
+    ARGCHK(page_rows >= 0, "page_rows %d is negative", page_rows);
+    ARGCHK(!endless || max_positions == 0, "an endless group takes no max_positions (%d): its members go on to the session limit", max_positions);
+    return group_create(m, t_embeds, n_members, gains, rates, enc_capacity_rows, endless ? 0 : max_positions, paged ? page_rows : -1, pool_pages, out, endless != 0, kv_dtype == VOX_KV_BF16, burst_ticks, true);
+}
+extern "C" int32_t vox_stream_group_t_embed(const vox_stream_group* g, int32_t member, float* out, int32_t cap) {
+    ARGCHK(g && out, "null argument"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1);
+    const std::vector<float>& te = group_t_embed(g, member);
+    ARGCHK(cap >= (int32_t)te.size(), "cap %d: a t_embed of this model has %d values", cap, (int)te.size());
+    std::memcpy(out, te.data(), te.size() * 4);
+    return VOX_OK;
+}
 extern "C" int32_t vox_stream_group_burst_info(const vox_stream_group* g, int64_t out[4]) {
     ARGCHK(g && out, "null argument");
     out[0] = g->burst; out[1] = (int64_t)g->burst_rounds; out[2] = (int64_t)g->burst_member_ticks; out[3] = (int64_t)g->plain_rounds;
@@ -4500,6 +4547,19 @@ extern "C" int32_t vox_stream_group_reset_rate(vox_stream_group* g, int32_t memb
     ARGCHK(g, "null group"); ARGCHK(sample_rate > 0, "bad sample rate 0");
     return group_reset(g, member, gain, sample_rate);
 }
+// the member's next utterance at another delay (a group with a delay per member alone).  Everything that can refuse comes first: the member, its delay and its state
+// are then as they were.  Behind the checks: the host copy, then the ordinary reset, whose seed starts from the prefix state of the new t_embed and copies its scales
+extern "C" int32_t vox_stream_group_reset_t_embed(vox_stream_group* g, int32_t member, float gain, uint32_t sample_rate, const float* t_embed) {
+    ARGCHK(g, "null group"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1); ARGCHK(std::isfinite(gain), "gain is not finite");
+    ARGCHK(t_embed, "member %d: null t_embed", member);
+    if (!g->ada) return fail(VOX_ERR_UNSUPPORTED, "member %d: this group runs every member at one t_embed (vox_stream_group_create_t_embeds makes one with a delay per member)", member);
+    if (sample_rate && sample_rate != 16000) { ResamplePlan rp; size_t b; int rn; VOXCHK(stream_rate_plan(sample_rate, &rp, &b, &rn)); }
+    VOXCHK(ctx_bind(g->ctx));
+    HIPCHK(hipStreamSynchronize(g->ctx->stream));
+    if (sample_rate) VOXCHK(group_member_set_rate(g, member, sample_rate));      // refused: nothing has changed
+    g->member_te[(size_t)member].assign(t_embed, t_embed + g->m->cfg.dec_dim);
+    return group_reset(g, member, gain, 0);
+}
 extern "C" int32_t vox_stream_group_info(const vox_stream_group* g, int32_t member, int64_t out[8]) {
     ARGCHK(g && out, "null argument"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1);
     const GroupMember& me = g->mem[member]; const int R = g->m->cfg.reshape_factor;
@@ -4526,6 +4586,7 @@ static int32_t group_decode_round(vox_stream_group* g, const StreamWs& w, int n_
     StreamPages pg{g->d_tab, g->pool.tab_len, g->pool.shift, g->d_kv_page, g->d_kv_in, g->endless ? g->pool.tab_len : 0};
     if (g->endless) { xb.page_tab_len = g->pool.tab_len; xb.rope_ring = g->rope.dec; xb.rope_mask = GROUP_ROPE_ROWS - 1; }
     xb.kv_bf16 = g->kv_bf16 ? 1 : 0;
+    if (g->ada) { xb.ada_rows = g->ada; xb.ada_order = g->d_order; xb.ada_stride = (long)c.dec_layers * c.dec_dim; }      // row r is member order[r]: a prefix of the pass's order in a burst's late rounds too
     if (g->paged) {
         xb.page_tab = g->d_tab; xb.page_tab_stride = g->pool.tab_len; xb.page_shift = g->pool.shift; xb.page_floats = (long)g->page_floats; xb.kv_page = g->d_kv_page; xb.kv_in = g->d_kv_in;
         xb.score_rows = c.dec_window >= 0 ? std::min(g->g.max_pos, c.dec_window + 1) : g->g.max_pos;
@@ -4779,7 +4840,7 @@ static int32_t group_run(vox_stream_group* g, vox_stream_feed* feeds, int32_t n_
     }
     if (call.peek) VOXCHK(keep_reserve(g->keep, GROUP_MAX + (size_t)n * stream_keep_floats(c.enc_layers, c.enc_heads, c.enc_head_dim, keep_rows), &g->bytes, s, "group"));
     if (m->pw_pend_rows > 0) VOXCHK(pw_sync(m));
-    VOXCHK(vox_model_set_t_embed(m, g->t_embed.data()));
+    if (!g->ada) VOXCHK(vox_model_set_t_embed(m, g->t_embed.data()));      // (a delay per member: the round reads the group's own scales, the model's t_embed stays what it is)
     for (GroupFeed& e : call.fs) g->mem[e.member].feed.n_pushed += (int64_t)e.plan.n;
     PagePool::Mark pool_was; std::vector<int> took;
     if (g->paged) { if (call.peek) { pool_was = g->pool.mark(); for (const GroupFeed& e : call.fs) took.push_back(e.member); } VOXCHK(group_take_pages(g, call)); }
@@ -4873,7 +4934,7 @@ extern "C" int32_t vox_debug_stream_group_tap_fetch(vox_stream_group* g, int32_t
 static SnapSession group_session(vox_stream_group* g, int i) {
     const vox_model_cfg& c = g->m->cfg; GroupMember& me = g->mem[(size_t)i]; const StreamMember& hm = g->h_mem[(size_t)i];
     static thread_local char who[32]; snprintf(who, sizeof who, "member %d", i);
-    SnapSession ss{}; ss.m = g->m; ss.ctx = g->ctx; ss.t_embed = &g->t_embed; ss.feed = &me.feed; ss.sc = &me.sc; ss.al = &me.al; ss.gain = hm.gain;
+    SnapSession ss{}; ss.m = g->m; ss.ctx = g->ctx; ss.t_embed = &group_t_embed(g, i); ss.feed = &me.feed; ss.sc = &me.sc; ss.al = &me.al; ss.gain = hm.gain;
     ss.tokens = hm.tokens; ss.samples = const_cast<float*>(hm.samples); ss.state = hm.state; ss.h_state = me.h_state; ss.cap = g->g.cap; ss.PC = g->g.PC; ss.max_pos = g->g.max_pos; ss.who = who;
     ss.enc.cache_k = hm.kring; ss.enc.cache_v = hm.vring; ss.enc.layers = c.enc_layers; ss.enc.heads = c.enc_heads; ss.enc.hd = c.enc_head_dim;
     ss.enc.layout = vox::SNAP_RING; ss.enc.cap = g->g.cap; ss.enc.layer_stride = g->ring_layer; ss.enc.head_stride = (size_t)g->g.cap * c.enc_head_dim;

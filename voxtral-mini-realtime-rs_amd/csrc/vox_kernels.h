@@ -39,6 +39,8 @@ enum Epi { EPI_STORE = 0, EPI_RESID = 1, EPI_SWIGLU = 2, EPI_ROPE_KV = 3, EPI_AR
                                      // rope_sin = the ring + hd / 2: rows are hd floats apart, not hd / 2).  An epilogue instantiation of its own: EPI_ROPE_KV compiles as it did
            EPI_ROPE_KV_PAGED_BF16 = 12, EPI_ROPE_KV_PAGED_RING_BF16 = 13,      // inside launch_q4_skinny only: the two paged epilogues on a bf16 pool (GemmParams::kv_bf16) -- RoPE in f32 as
                                      // below, then K and V rounded by kv_bf16_round (vox_kv_bf16.h) and stored as 16-bit values; q is untouched.  Instantiations of their own
+           EPI_RESID_XF_ROWS = 14,   // inside launch_q4_skinny only: EPI_RESID_XF with GemmParams::xf_w2_row set (a stream group with a delay per member) -- row m's second scale is read
+                                     // from scale set xf_w2_row[m]: xw = xf_w[n] * xf_w2[xf_w2_row[m] * xf_w2_stride + n], the per-column form's product.  An instantiation of its own
            EPI_ROPE_KV_PAGED_RING = 11 };  // inside launch_q4_skinny only: EPI_ROPE_KV_PAGED with GemmParams::rope_member set (an endless paged group) -- the RoPE row is read from the
                                      // group's member-strided RoPE ring: row rope_member[m] * (rope_mask + 1) + (pos[m] & rope_mask) of [members][rope_mask + 1][cos hd/2 | sin hd/2]
                                      // (rope_cos = the ring, rope_sin = the ring + hd / 2).  An epilogue instantiation of its own: the other two compile as they did
@@ -91,8 +93,11 @@ struct GemmParams {
     uint16_t* xf_out; const float* xf_w; const float* xf_w2; float* ssq_out;
     // EPI_ROPE_KV (M <= 16, one row per sequence): columns [0, n_q) -> RoPE -> out; [n_q, n_q + n_kv*hd) -> RoPE -> K cache; rest -> V cache,
     // all at position pos[m] of sequence m's cache slice
-    const int* pos; const float* rope_cos; const float* rope_sin; int hd, n_q, n_kv; float* kc; float* vc; long kv_seq_stride; int kv_head_stride;
-    const int* kv_row;    // EPI_ROPE_KV, optional: row m writes into cache slice kv_row[m] instead of slice m (continuous batching: a SLOT of the step decodes whichever utterance it currently holds)
+    const int* pos; const float* rope_cos; const float* rope_sin; int hd, n_q, n_kv; float* kc; float* vc; union { long kv_seq_stride; long xf_w2_stride; }; int kv_head_stride;
+    // EPI_RESID_XF, optional (the <= 16-row XF form alone, an epilogue instantiation of its own): xf_w2 holds scale SETS xf_w2_stride floats apart and row m multiplies
+    // by set xf_w2_row[m] (a stream group's row -> member map: every member's Ada scales); null: xf_w2 is one [N] vector for all rows.  The two words share the storage
+    // of kv_row and kv_seq_stride, which only EPI_ROPE_KV reads: the argument block keeps its size and layout, and every other instantiation the code it had
+    union { const int* xf_w2_row; const int* kv_row; };    // kv_row: EPI_ROPE_KV, optional: row m writes into cache slice kv_row[m] instead of slice m (continuous batching: a SLOT of the step decodes whichever utterance it currently holds)
     const int* kv_pos;    // EPI_ROPE_KV, optional (the <= 16-row XF form alone, an epilogue instantiation of its own): row m's row INSIDE its slice; null: pos[m], the address of every contiguous cache.  A paged cache
                           // (a paged stream group) passes kv_row[m] = the physical page, kv_seq_stride = the floats of a page, kv_head_stride = page_rows * hd, kv_pos[m] = pos[m] % page_rows
     const int* rope_member; int rope_mask;      // EPI_ROPE_KV with kv_pos, optional (EPI_ROPE_KV_PAGED_RING): row m's member of a member-strided RoPE ring of rope_mask + 1 rows (a power of two) per member

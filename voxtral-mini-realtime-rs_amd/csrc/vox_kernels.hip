@@ -1194,6 +1194,9 @@ __global__ __launch_bounds__(NTW == 3 ? 256 : 512, NTW == 3 ? 3 : 1) void q4_ski
     // EPI_ROPE_KV_PAGED_BF16 / _PAGED_RING_BF16: the two paged epilogues on a bf16 pool -- K (after its f32 RoPE) and V rounded by kv_bf16_round, 16-bit stores
     constexpr bool KVB = EPI == EPI_ROPE_KV_PAGED_BF16 || EPI == EPI_ROPE_KV_PAGED_RING_BF16;
     constexpr bool KVR = EPI == EPI_ROPE_KV_PAGED_RING || EPI == EPI_ROPE_KV_PAGED_RING_BF16, KVP = EPI == EPI_ROPE_KV_PAGED || KVR || KVB, ROPE_KV = EPI == EPI_ROPE_KV || KVP;
+    // EPI_RESID_XF_ROWS: EPI_RESID_XF with the second scale read per ROW, from the scale set p.xf_w2_row[m] names (a stream group's members at their own delays) -- an
+    // instantiation of its own, so that the per-column epilogue stays the code it was; the product xf_w[n] * xf_w2[.] and everything behind it are the per-column form's
+    constexpr bool XROWS = EPI == EPI_RESID_XF_ROWS, RXF = EPI == EPI_RESID_XF || XROWS;
     const int nb = p.w.nb, N = p.w.N, M = p.M, nq = nb >> 2;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, KS = blockDim.x >> 6;
     const int g = lane >> 4, li = lane & 15;
@@ -1275,7 +1278,7 @@ __global__ __launch_bounds__(NTW == 3 ? 256 : 512, NTW == 3 ? 3 : 1) void q4_ski
     // branch around a load makes hipcc drain vmcnt).  vmcnt retires IN ORDER and these words were written by the previous launches on other XCDs
     // (memory round trips): the straight-line path requests them BEHIND its first K step's operands, so that step does not wait for them.
     float pv[12]; const int prow = tid & 15, pch = tid >> 4, nch = blockDim.x >> 4;
-    float pre_res[4] = {0.f, 0.f, 0.f, 0.f}; float pre_xw = 0.f; int pre_pos[4] = {0, 0, 0, 0}; int pre_row[4] = {0, 0, 0, 0}; int pre_kvp[4] = {0, 0, 0, 0}; int pre_mem[4] = {0, 0, 0, 0};
+    float pre_res[4] = {0.f, 0.f, 0.f, 0.f}; float pre_xw = 0.f; float pre_xwr[4] = {0.f, 0.f, 0.f, 0.f}; int pre_pos[4] = {0, 0, 0, 0}; int pre_row[4] = {0, 0, 0, 0}; int pre_kvp[4] = {0, 0, 0, 0}; int pre_mem[4] = {0, 0, 0, 0};
 #define VOX_PRELOADS                                                                                      \
     {                                                                                                      \
         if (PRO) {                                                                                         \
@@ -1286,10 +1289,14 @@ __global__ __launch_bounds__(NTW == 3 ? 256 : 512, NTW == 3 ? 3 : 1) void q4_ski
             }                                                                                              \
         }                                                                                                  \
         const int n0_ = min(nbase + min(wave, NTW - 1) * 16 + li, N - 1);                                  \
-        if (EPI == EPI_RESID_XF || EPI == EPI_RESID) {                                                     \
+        if (RXF || EPI == EPI_RESID) {                                                                     \
             _Pragma("unroll") for (int r = 0; r < 4; r++) pre_res[r] = p.resid[(size_t)min(4 * g + r, M - 1) * p.resid_stride + n0_]; \
         }                                                                                                  \
         if (EPI == EPI_RESID_XF) { pre_xw = p.xf_w[n0_]; if (p.xf_w2) pre_xw *= p.xf_w2[n0_]; }            \
+        if (XROWS) {                                                                                       \
+            const float w1_ = p.xf_w[n0_];                                                                 \
+            _Pragma("unroll") for (int r = 0; r < 4; r++) pre_xwr[r] = w1_ * p.xf_w2[(size_t)p.xf_w2_row[min(4 * g + r, M - 1)] * p.xf_w2_stride + n0_]; \
+        }                                                                                                  \
         if (ROPE_KV) {                                                                                     \
             _Pragma("unroll") for (int r = 0; r < 4; r++) pre_pos[r] = p.pos[min(4 * g + r, M - 1)];       \
             _Pragma("unroll") for (int r = 0; r < 4; r++) pre_row[r] = p.kv_row ? p.kv_row[min(4 * g + r, M - 1)] : min(4 * g + r, M - 1); \
@@ -1379,6 +1386,11 @@ __global__ __launch_bounds__(NTW == 3 ? 256 : 512, NTW == 3 ? 3 : 1) void q4_ski
         float xw = 0.f;
         const bool pre = t == wave;                         // operands prefetched at kernel start
         if (EPI == EPI_RESID_XF && nok) { if (pre) xw = pre_xw; else { xw = p.xf_w[n]; if (p.xf_w2) xw *= p.xf_w2[n]; } }
+        float xwr[4] = {0.f, 0.f, 0.f, 0.f};              // EPI_RESID_XF_ROWS: the scale of each of the lane's four rows
+        if (XROWS && nok) {
+#pragma unroll
+            for (int r = 0; r < 4; r++) xwr[r] = pre ? pre_xwr[r] : p.xf_w[n] * p.xf_w2[(size_t)p.xf_w2_row[min(4 * g + r, M - 1)] * p.xf_w2_stride + n];
+        }
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             const int m = 4 * g + r;
@@ -1399,14 +1411,14 @@ __global__ __launch_bounds__(NTW == 3 ? 256 : 512, NTW == 3 ? 3 : 1) void q4_ski
                     uint16_t* xo = reinterpret_cast<uint16_t*>(p.out);
                     *reinterpret_cast<uint32_t*>(xo + base) = hi; *reinterpret_cast<uint32_t*>(xo + (size_t)(K2 >> 7) * 256 * 8 + base) = lo;
                 }
-            } else if (EPI == EPI_RESID_XF) {
+            } else if (RXF) {
                 // residual stream as f32 + the next RMSNorm folded in: XF planes of v * gamma (K-slot pair (k, k+2) = lanes li, li+2)
                 // and this workgroup's partial sum of squares per row
                 const bool ok = m < M && nok;
                 if (ok) { v = v + (pre ? pre_res[r] : p.resid[(size_t)m * p.resid_stride + n]); p.out[(size_t)m * p.out_stride + n] = v; } else v = 0.f;
                 const float ss = row16_sum(v * v);
                 if (li == 0) p.ssq_out[(size_t)blockIdx.x * 16 + m] = ss;
-                const float a = v * xw, b = dpp_mov<0x4E>(a);
+                const float a = v * (XROWS ? xwr[r] : xw), b = dpp_mov<0x4E>(a);
                 if (ok && !(li & 2)) {
                     uint32_t hi, lo; split_pair(a, b, hi, lo);
                     const int qq = n >> 7, jj = (n >> 5) & 3, e = n & 31, half = e >> 4, gg = (e & 15) >> 2, tt = e & 3;
@@ -1729,7 +1741,7 @@ hipError_t launch_q4_wide(const GemmParams& p, int epi_stage, hipStream_t s) {  
     const int epi = epi_stage & 0xff; const bool only_gemm = (epi_stage & 0x100) != 0, only_finish = (epi_stage & 0x200) != 0;
     WidePlan pl;
     const int MT = p.wide_mt;
-    if (!p.xf || p.M != 16 * MT || p.kv_pos || !q4_wide_plan(p.w, MT, epi, &pl)) return hipErrorInvalidValue;
+    if (!p.xf || p.M != 16 * MT || p.kv_pos || (epi == EPI_RESID_XF && p.xf_w2_row) || !q4_wide_plan(p.w, MT, epi, &pl)) return hipErrorInvalidValue;
     const bool direct = epi == EPI_STORE;
     if (direct) { if (!p.out || !p.ssq_part || p.n_part < 1) return hipErrorInvalidValue; }
     else if (!p.kz_scratch || p.kz_scratch_bytes < q4_wide_planes_bytes(p.w, MT, pl)) return hipErrorInvalidValue;
@@ -2487,6 +2499,7 @@ template <int NTW, int TILED>
 static hipError_t skinny_launch_n(const GemmParams& p, int epi, int ks, hipStream_t s) {
     if (epi == EPI_ROPE_KV && p.kv_pos && p.kv_bf16) epi = p.rope_member ? EPI_ROPE_KV_PAGED_RING_BF16 : EPI_ROPE_KV_PAGED_BF16;      // (a bf16 pool: the same two forms, 16-bit stores)
     else if (epi == EPI_ROPE_KV && p.kv_pos) epi = p.rope_member ? EPI_ROPE_KV_PAGED_RING : EPI_ROPE_KV_PAGED;      // (launch_q4_gemm_epi admits kv_pos with XF input alone, rope_member with kv_pos alone)
+    if (epi == EPI_RESID_XF && p.xf_w2_row) epi = EPI_RESID_XF_ROWS;      // (launch_q4_gemm_epi admits xf_w2_row with XF input and xf_w2 alone)
     dim3 grid((p.w.N + 16 * NTW - 1) / (16 * NTW));
     const size_t lds = (size_t)ks * NTW * 64 * 4 * sizeof(float);
     if (p.xf) {      // fragment-ordered bf16 hi/lo input (batched decode step); tile-ordered weights only
@@ -2497,14 +2510,16 @@ static hipError_t skinny_launch_n(const GemmParams& p, int epi, int ks, hipStrea
         const int nq = p.w.nb / 4, per = nq % ks == 0 ? nq / ks : 0;
         if (per) {
 #define VOX_ST(N_, E_, P_, S_) if (NTW == N_ && epi == E_ && (int)pro == P_ && per == S_) { \
-            if (E_ == EPI_RESID_XF && (!p.xf_out || !p.xf_w || !p.ssq_out)) return hipErrorInvalidValue; \
+            if ((E_ == EPI_RESID_XF || E_ == EPI_RESID_XF_ROWS) && (!p.xf_out || !p.xf_w || !p.ssq_out)) return hipErrorInvalidValue; \
             q4_skinny_kernel<N_, E_, 1, 1, P_, S_><<<grid, dim3(64 * ks), lds, s>>>(p); return hipGetLastError(); }
             VOX_ST(2, EPI_ROPE_KV, 1, 3) VOX_ST(2, EPI_ROPE_KV_PAGED, 1, 3) VOX_ST(2, EPI_ROPE_KV_PAGED_RING, 1, 3) VOX_ST(2, EPI_ROPE_KV_PAGED_BF16, 1, 3) VOX_ST(2, EPI_ROPE_KV_PAGED_RING_BF16, 1, 3) VOX_ST(2, EPI_SWIGLU_XF, 1, 6) VOX_ST(1, EPI_SWIGLU_XF, 1, 6) VOX_ST(1, EPI_RESID_XF, 0, 4) VOX_ST(4, EPI_SWIGLU_XF, 1, 6) VOX_ST(1, EPI_RESID_XF, 0, 9) VOX_ST(4, EPI_STORE, 1, 6)
+            VOX_ST(1, EPI_RESID_XF_ROWS, 0, 4) VOX_ST(1, EPI_RESID_XF_ROWS, 0, 9)      // the per-row wo epilogue: a form for each of EPI_RESID_XF's
 #undef VOX_ST
         }
-        if (epi == EPI_RESID_XF) {
+        if (epi == EPI_RESID_XF || epi == EPI_RESID_XF_ROWS) {
             if (NTW != 1 || pro || !p.xf_out || !p.xf_w || !p.ssq_out) return hipErrorInvalidValue;
-            q4_skinny_kernel<1, EPI_RESID_XF, 1, 1, 0><<<grid, dim3(64 * ks), lds, s>>>(p);
+            if (epi == EPI_RESID_XF_ROWS) q4_skinny_kernel<1, EPI_RESID_XF_ROWS, 1, 1, 0><<<grid, dim3(64 * ks), lds, s>>>(p);
+            else q4_skinny_kernel<1, EPI_RESID_XF, 1, 1, 0><<<grid, dim3(64 * ks), lds, s>>>(p);
         } else if (pro) {
             switch (epi) {
             case EPI_STORE: q4_skinny_kernel<NTW, EPI_STORE, 1, 1, 1><<<grid, dim3(64 * ks), lds, s>>>(p); break;
@@ -2618,6 +2633,7 @@ static hipError_t launch_q4_gemm_epi(const GemmParams& p, int epi_in, hipStream_
     if (p.w.K % 32 || p.M <= 0) return hipErrorInvalidValue;
     if (p.kv_pos && !(p.xf && p.M <= 16)) return hipErrorInvalidValue;      // a row inside the slice: q4_skinny_kernel's epilogue alone takes it
     if (p.kv_bf16 && (!p.kv_pos || p.kv_bf16 != 1)) return hipErrorInvalidValue;      // a bf16 pool is a paged cache's
+    if (epi == EPI_RESID_XF && p.xf_w2_row && !(p.xf && p.M <= 16 && p.xf_w2 && p.xf_w2_stride >= p.w.N)) return hipErrorInvalidValue;      // scale sets per row: q4_skinny_kernel's epilogue alone takes them
     if (p.rope_member && (!p.kv_pos || p.rope_mask < 0 || (p.rope_mask & (p.rope_mask + 1)))) return hipErrorInvalidValue;      // a member RoPE ring: the paged epilogue's, a power of two rows per member
     if (p.ksplit > 1 && (p.M <= 48 || p.xf || p.w.nb % 4 || p.w.fmt == WFMT_F32)) return hipErrorInvalidValue;      // split-K exists in q4_gemm_kernel only
     if (p.w.fmt == WFMT_F32) {      // true-f32 dense weights: bf16 hi + lo planes on the matrix cores (3 MFMAs per product, f32-class like the conv stem)

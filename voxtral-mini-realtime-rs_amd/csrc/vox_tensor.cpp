@@ -140,6 +140,35 @@ extern "C" int32_t vox_linear_forward_ex(vox_ctx* c, const vox_q4* w, const floa
     HIPCHK(hipMemcpyAsync(out, dy.p, (size_t)rows * No * 4, hipMemcpyDeviceToHost, c->stream)); HIPCHK(hipStreamSynchronize(c->stream));
     return VOX_OK;
 }
+// ---- debug: ONE launch of the decode round's wo operator (tests): out = x W^T + resid as f32 rows, the XF planes of out * xf_w * scale and the per-tile sums of squares
+// (launch_q4_gemm's EPI_RESID_XF on the XF tile of x).  order == null: the per-column form, every row multiplied by scale set d->set; order given: the per-row form
+// (EPI_RESID_XF_ROWS), row m by scale set order[m].  Host pointers; xf_out holds 2 (N / 128) 256 8 16-bit values, ssq_out (N / 16) 16 floats; rows >= M stay 0.
+extern "C" int32_t vox_debug_resid_xf(vox_ctx* c, const vox_q4* w, const vox_resid_xf_desc* d, const float* x, const float* resid, const float* xf_w, const float* scales,
+                                      const int32_t* order, float* out, uint16_t* xf_out, float* ssq_out) {
+    ARGCHK(c && w && d && x && resid && xf_w && scales && out && xf_out && ssq_out, "null argument");
+    const int M = d->M, K = w->w.K, N = w->w.N, S = d->n_sets;
+    ARGCHK(M >= 1 && M <= 16, "M %d out of range (1..16)", M); ARGCHK(S >= 1 && S <= 16, "n_sets %d out of range (1..16)", S);
+    ARGCHK(w->w.fmt == WFMT_Q4_0 && w->w.qt && w->w.st && K % 128 == 0 && N % 128 == 0, "the XF step takes a tile-ordered Q4 weight with K and N multiples of 128 (K %d, N %d)", K, N);
+    if (order) { for (int m = 0; m < M; m++) ARGCHK(order[m] >= 0 && order[m] < S, "order[%d] = %d names no scale set (0..%d)", m, order[m], S - 1); }
+    else ARGCHK(d->set >= 0 && d->set < S, "set %d out of range (0..%d)", d->set, S - 1);
+    VOXCHK(ctx_bind(c)); hipStream_t s = c->stream;
+    const size_t xin_b = (size_t)2 * (K / 128) * 256 * 16, xout_b = (size_t)2 * (N / 128) * 256 * 16, ssq_b = (size_t)q4_skinny_resid_xf_parts(N) * 16 * 4;
+    DevBuf dx, dxf, dres, dw1, dsc, dord, dout, dxo, dss;
+    HIPCHK(dx.alloc((size_t)M * K * 4)); HIPCHK(dxf.alloc(xin_b)); HIPCHK(dres.alloc((size_t)M * N * 4)); HIPCHK(dw1.alloc((size_t)N * 4)); HIPCHK(dsc.alloc((size_t)S * N * 4));
+    HIPCHK(dord.alloc(16 * 4)); HIPCHK(dout.alloc((size_t)M * N * 4)); HIPCHK(dxo.alloc(xout_b)); HIPCHK(dss.alloc(ssq_b));
+    HIPCHK(hipMemcpyAsync(dx.p, x, (size_t)M * K * 4, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(dres.p, resid, (size_t)M * N * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dw1.p, xf_w, (size_t)N * 4, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(dsc.p, scales, (size_t)S * N * 4, hipMemcpyHostToDevice, s));
+    if (order) HIPCHK(hipMemcpyAsync(dord.p, order, (size_t)M * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(dxf.p, 0, xin_b, s)); HIPCHK(hipMemsetAsync(dxo.p, 0, xout_b, s)); HIPCHK(hipMemsetAsync(dss.p, 0, ssq_b, s));
+    HIPCHK(launch_xf_rows(dx.as<float>(), K, M, K, dxf.as<uint16_t>(), s));
+    GemmParams g{}; g.w = w->w; g.xf = (const uint4*)dxf.p; g.M = M; g.out = dout.as<float>(); g.out_stride = N; g.resid = dres.as<float>(); g.resid_stride = N;
+    g.xf_out = dxo.as<uint16_t>(); g.xf_w = dw1.as<float>(); g.ssq_out = dss.as<float>();
+    if (order) { g.xf_w2 = dsc.as<float>(); g.xf_w2_row = (const int*)dord.p; g.xf_w2_stride = N; } else g.xf_w2 = dsc.as<float>() + (size_t)d->set * N;
+    HIPCHK(launch_q4_gemm(g, EPI_RESID_XF, s));
+    HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)M * N * 4, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(xf_out, dxo.p, xout_b, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(ssq_out, dss.p, ssq_b, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
+    return VOX_OK;
+}
 // ConvDownsampler::forward (models/layers/conv.rs:78-83): gelu(conv1d k3 s2 p1) twice, x [C][L] -> [O][L2], on the product's im2col MFMA path (conv_stem_dev)
 extern "C" int32_t vox_conv_downsample(vox_ctx* c, const float* x, int32_t C, int32_t L, const float* w1, const float* b1, const float* w2, const float* b2, int32_t O, float* out) {
     ARGCHK(c && x && w1 && b1 && w2 && b2 && out && C > 0 && L > 0 && O > 0, "bad argument"); ARGCHK((3 * C) % 128 == 0 && (3 * O) % 128 == 0, "3 * channels must be a multiple of 128");

@@ -944,7 +944,7 @@ class LiveStreamGroup:
     KV_DTYPES = {"f32": 0, "bf16": 1}      # VOX_KV_F32, VOX_KV_BF16
 
     def __init__(self, model, t_embed, n_members, gains=None, enc_capacity_rows=0, max_positions=0, sample_rates=None, page_rows=None, pool_pages=None, endless=False,
-                 kv_dtype=None, burst=None):
+                 kv_dtype=None, burst=None, t_embeds=None):
         if burst is not None and (isinstance(burst, bool) or not isinstance(burst, (int, np.integer)) or not 1 <= int(burst) <= STREAM_BURST_MAX):
             raise VoxError(1, f"create_stream_group: burst {burst!r} is not an integer in 1..{STREAM_BURST_MAX}")
         self.model = model; self.h = C.c_void_p(); self.n_members = int(n_members); self._tap_max = {}; self._rates = {}
@@ -959,6 +959,20 @@ class LiveStreamGroup:
         g = None if gains is None else _f32(gains).reshape(-1)
         if g is not None and g.size != self.n_members:
             raise ValueError(f"{g.size} gains for {self.n_members} members")
+        self.per_member = t_embeds is not None      # a delay per member (vox_stream_group_create_t_embeds): t_embeds [n_members][dec_dim], t_embed unread
+        if self.per_member:
+            te = _f32(t_embeds)
+            if te.ndim != 2 or te.shape[0] != self.n_members:
+                raise ValueError(f"t_embeds of shape {tuple(te.shape)} for {self.n_members} members: one row per member")
+            r = np.ascontiguousarray([int(v) for v in (sample_rates if sample_rates is not None else [16000] * self.n_members)], dtype=np.uint32)
+            if r.size != self.n_members:
+                raise ValueError(f"{r.size} sample rates for {self.n_members} members")
+            check(lib().vox_stream_group_create_t_embeds(model.h, _ptr(te), self.n_members, None if g is None else _ptr(g), _ptr(r), int(enc_capacity_rows), int(max_positions),
+                                                         int(self.paged), int(page_rows or 0), int(pool_pages or 0), int(self.endless), self.KV_DTYPES[kv_dtype or "f32"],
+                                                         int(burst or 1), C.byref(self.h)))
+            self._rates = {k: int(v) for k, v in enumerate(r) if int(v) != 16000}
+            model._caches.add(self)
+            return
         args = (model.h, _ptr(_f32(t_embed).reshape(-1)), self.n_members, None if g is None else _ptr(g))
         if burst is not None:
             r = np.ascontiguousarray([int(v) for v in (sample_rates if sample_rates is not None else [16000] * self.n_members)], dtype=np.uint32)
@@ -1042,16 +1056,36 @@ class LiveStreamGroup:
             out[e.member] = (ids[:e.n_ids].copy(), rec[:e.n_ids].copy()) if return_scores else ids[:e.n_ids].copy()
         return out
 
-    def reset(self, member, gain=1.0, sample_rate=None):
-        """The member's next connection; sample_rate: what it delivers (None: the member keeps its rate)."""
-        if sample_rate is None:
+    def reset(self, member, gain=1.0, sample_rate=None, delay=None, t_embed=None):
+        """The member's next connection; sample_rate: what it delivers (None: the member keeps its rate).  delay / t_embed (one of them; a group made with t_embeds= or
+        delays= alone): the delay its next utterance runs at (vox_stream_group_reset_t_embed); a refused call leaves the member as it was."""
+        if delay is not None and t_embed is not None:
+            raise ValueError("reset: delay and t_embed name the same thing, give one")
+        if delay is not None:
+            from .audio import TimeEmbedding
+            t_embed = TimeEmbedding(self.model.config.dec_dim).embed(float(delay))
+        if t_embed is not None:
+            te = _f32(t_embed).reshape(-1)
+            if te.size != self.model.config.dec_dim:
+                raise ValueError(f"a t_embed of {te.size} values for a model of dec_dim {self.model.config.dec_dim}")
+            check(lib().vox_stream_group_reset_t_embed(self.h, int(member), float(gain), int(sample_rate or 0), _ptr(te)))
+            if sample_rate is None:
+                return
+        elif sample_rate is None:
             check(lib().vox_stream_group_reset(self.h, int(member), float(gain)))
             return
-        check(lib().vox_stream_group_reset_rate(self.h, int(member), float(gain), int(sample_rate)))
+        else:
+            check(lib().vox_stream_group_reset_rate(self.h, int(member), float(gain), int(sample_rate)))
         rates = dict(self._rates or {}); rates.pop(int(member), None)
         if int(sample_rate) != 16000:
             rates[int(member)] = int(sample_rate)
         self._rates = rates
+
+    def t_embed(self, member) -> np.ndarray:
+        """vox_stream_group_t_embed: the t_embed the member runs at (every group: a group of one delay returns that one for every member)."""
+        out = np.zeros(self.model.config.dec_dim, dtype=np.float32)
+        check(lib().vox_stream_group_t_embed(self.h, int(member), _ptr(out), out.size))
+        return out
 
     def snapshot(self, member) -> np.ndarray:
         """vox_stream_group_snapshot: the member's session as one blob (LiveStream.snapshot); the group stays exactly what it was."""
@@ -1339,7 +1373,7 @@ class Q4VoxtralModel:
         return LiveStream(self, t_embed, gain, enc_capacity_rows, max_positions, sample_rate, endless, dec_ring_rows, burst)
 
     def create_stream_group(self, t_embed, n_members, gains=None, enc_capacity_rows=0, max_positions=0, sample_rates=None, page_rows=None, pool_pages=None,
-                            endless=False, kv_dtype=None, burst=None) -> LiveStreamGroup:
+                            endless=False, kv_dtype=None, burst=None, t_embeds=None, delays=None) -> LiveStreamGroup:
         """Up to 16 live sessions advanced together (vox_stream_group_create): advance({member: samples}, finish=()) -> {member: ids}, reset(member, gain), info(member),
         close().  gains: one per member (None: 1.0 each); max_positions 0: 2048 decoder positions per member (the group's decoder cache does not grow);
         sample_rates: what each member is fed (None: 16 kHz each; vox_stream_group_create_rates).
@@ -1348,8 +1382,20 @@ class Q4VoxtralModel:
         endless (vox_stream_group_create_endless): a paged group (page_rows / pool_pages as above, both optional) whose members are not refused at 16 384 positions
         but go on to 2^24; max_positions must not be given (ValueError).  Everything of a paged group works unchanged.
         kv_dtype "f32" | "bf16" (vox_stream_group_create_kv; implies paged, as endless does; anything else: ValueError): what the K / V pool holds.  "bf16": 16-bit
-        pages, half the memory and half the bytes the decode attention reads; ids and logits are close to, not equal to, the f32 group's.  pool() then names it."""
-        return LiveStreamGroup(self, t_embed, n_members, gains, enc_capacity_rows, max_positions, sample_rates, page_rows, pool_pages, endless, kv_dtype, burst)
+        pages, half the memory and half the bytes the decode attention reads; ids and logits are close to, not equal to, the f32 group's.  pool() then names it.
+        t_embeds [n_members][dec_dim] or delays [n_members] (through TimeEmbedding; vox_stream_group_create_t_embeds, any kind of group): a delay PER MEMBER -- t_embed
+        is then unread (None); member k's ids are those of member k in a group whose members all run at its delay.  reset(member, delay=) moves a member to another,
+        t_embed(member) reads it back."""
+        if delays is not None and t_embeds is not None:
+            raise ValueError("create_stream_group: delays and t_embeds name the same thing, give one")
+        if delays is not None:
+            from .audio import TimeEmbedding
+            te = TimeEmbedding(self.config.dec_dim); t_embeds = [te.embed(float(d)) for d in delays]
+        if t_embeds is not None:
+            t_embeds = _f32(np.stack([_f32(t).reshape(-1) for t in t_embeds])) if len(t_embeds) else np.zeros((0, self.config.dec_dim), np.float32)
+            if t_embeds.shape != (int(n_members), self.config.dec_dim):
+                raise ValueError(f"{t_embeds.shape[0]} t_embeds of {t_embeds.shape[1]} values for {int(n_members)} members of dec_dim {self.config.dec_dim}: one per member")
+        return LiveStreamGroup(self, t_embed, n_members, gains, enc_capacity_rows, max_positions, sample_rates, page_rows, pool_pages, endless, kv_dtype, burst, t_embeds)
 
     def transcribe_batch(self, samples_list, t_embed, device_ptrs=None, n_samples=None, norm_group=None, tap_units=None):
         """Batched whole-path transcription of independent utterances (<= 4096; wider than 16: continuous batching over decode slots): list of float32 sample arrays
