@@ -355,6 +355,21 @@ typedef struct { float logprob; float margin; int32_t runner_up; int32_t id; } v
 /* rows of logits -> one record per row, the piecewise caller's companion to vox_argmax_rows (same mem_kind for the logits).  ids_or_null (host, M entries, each in [0, V)):
  * the id to score; null: the row's argmax as vox_argmax_rows gives it.  out: host, M records.  Computed on the device either way (host logits are uploaded).  Synchronises. */
 int32_t vox_score_rows(vox_ctx* ctx, const float* logits_MxV, int32_t M, int32_t V, const int32_t* ids_or_null, vox_token_score* out, int32_t mem_kind);
+/* ---- levels: what the model had just heard when it chose an id (live sessions only; no reference counterpart).  Record k of an utterance goes with id k and describes
+ * the 2560 samples at 16 kHz that are new to the tick that chose it: the window [2560 (k - 1), 2560 k) of the utterance's own 16 kHz sample index (vox_level_window).
+ * Each sample is taken as the mel front end reads it -- v = gain * sample in f32, 0 below index 0 (the silent left pad; record 0 is (0, 0)), behind the utterance whatever
+ * a finish or a peek put there (its zero pad) -- so a rate stream's records are taken on the 16 kHz samples its resampler produced.
+ *   peak        = max |v| over the window: exact;
+ *   mean_square = (sum v * v) / 2560 in f32, by ONE scan order and ONE reduction tree ("Levels"): every square rounds once, 18 additions lie on
+ *                 every path from a sample to the root, one division follows -- within (1 + 2^-24)^20 - 1 < 2^-19 relative of the float64 value on the same f32 v
+ *                 while no square underflows; a square below 2^-126 rounds on the subnormal grid, which adds at most 2^-149 (absolute) to the record.
+ * A window with a non-finite sample has a non-finite mean_square; nothing else is promised of it -- in particular a NaN sample is dropped from the peak, which stays
+ * the largest of the other samples, and vox_stream_quiet counts such a record by that peak.  The record is a function of the window's samples and the gain alone:
+ * bit for bit independent of how the samples were cut into pushes, of solo stream versus group member, of the other members, of the ring and of burst versus plain. */
+typedef struct { float peak; float mean_square; } vox_tick_level;
+/* host arithmetic, no device: the window of record k >= 0 as [*first_sample, *end_sample) -- first_sample is -2560 for k = 0.  Id k is due at 2560 k + 40 pushed samples
+ * (vox_stream_schedule), so every sample of its window has been pushed when the id is handed out. */
+int32_t vox_level_window(int32_t k, int64_t* first_sample, int64_t* end_sample);
 /* ---- alternatives: what else the model weighed at a step, and how spread the step's distribution was (no reference counterpart).  For a logits row L[V] (f32) and
  * k in 1 .. VOX_MAX_ALTERNATIVES:
  *   alt[0].id = the row's argmax by the rule of every decode form (the largest wins, the lowest index wins a tie, a NaN or -inf never wins); alt[j].id = the argmax by
@@ -532,6 +547,15 @@ int32_t vox_debug_stream_attn_group_burst(vox_ctx* ctx, const vox_stream_attn_de
  * other word keeps its own.  layers 1..64, n_heads 1..64, head_dim 64 | 128, cap 1..16384; rows <= 0 and rows > cap are refused, like every argument, before the
  * context is bound. */
 int32_t vox_debug_stream_ring_init(vox_ctx* ctx, int32_t layers, int32_t rows, int32_t n_heads, int32_t head_dim, int32_t cap, const float* kv, float* kring, float* vring);
+/* The sessions' level kernel on its own, without a model (tests): ONE launch for n_slots slots of n_members hand-made sessions.  rings: host [n_members][ring_n] f32
+ * (ring_n a power of two, 4096 .. 2^20; sample i of a session lives at ring[i & (ring_n - 1)]); gains [n_members]; pos and frame [n_members]: each session's
+ * STRM_POS (>= 37, the prefix positions) and STRM_FRAME (>= 0) words; order [n_slots]: the member slot z works for (distinct).  ticks 1 .. 16: the grid's tick
+ * dimension; burst_b null: every slot runs `ticks` ticks (1: the plain form, more: a solo burst's); burst_b [n_slots]: the ragged form, slot z runs burst_b[z] ticks,
+ * 1 .. ticks, descending.  Block (t, z) writes record pos - 37 + t of its session from the window starting at 160 frame - 97280 + 2560 t (the product's left pad
+ * and first position).  out: host [n_members][list_len] records, list_len 1 .. 65536 -- every record the launch does not write comes back as (NaN, NaN), an index
+ * outside the list is not written.  Every check before the context is bound. */
+int32_t vox_debug_stream_level(vox_ctx* ctx, int32_t n_members, const float* rings, int32_t ring_n, const float* gains, const int32_t* pos, const int32_t* frame,
+                               const int32_t* order, int32_t n_slots, int32_t ticks, const int32_t* burst_b, int32_t list_len, vox_tick_level* out);
 /* One launch of the session blob's K / V kernel on its own (tests; SNAPSHOT AND RESUME below): the logical rows lo .. hi - 1 of every (layer, head) of K and V
  * between the blob's dense layout and a cache in one of the four layouts a session's K / V can have -- exactly ONE launch (none when lo == hi), host arrays in and out.
  *   blob: host [2][layers][n_heads][hi - lo][head_dim], K then V.  restore == 0 packs the cache's rows into it, restore != 0 unpacks it into the cache; cache_k /
@@ -756,6 +780,22 @@ int32_t vox_stream_peek_ids(size_t n_samples, uint32_t sample_rate, int32_t ids_
 int32_t vox_stream_set_alternatives(vox_stream* s, int32_t k);
 int32_t vox_stream_alternatives(const vox_stream* s, int32_t first_id, int32_t n, vox_token_alts* out);
 int32_t vox_stream_peeked_alternatives(const vox_stream* s, vox_token_alts* out, int32_t cap, int32_t* n);
+/* LEVELS.  With levels on, every id the stream hands out also comes with a vox_tick_level (above): one more launch per tick -- per burst, with a block per tick -- in
+ * front of the tick's mel launch, reading the tick's 2560 new samples (10 KB), and one more copy in front of the call's one synchronisation; the ids and logits do not
+ * change, and a stream that never turns levels on allocates and launches nothing.  vox_stream_set_levels: on = 0 / 1, takes effect with the next push / finish / peek,
+ * survives vox_stream_reset (which starts the records over); the first on = 1 allocates the records (8 bytes per position the stream was created for; an endless
+ * stream's list grows with its others), counted in vox_stream_info [5] from then on.
+ * vox_stream_levels: the records of ids [first_id, first_id + n) of the current utterance from a host array the stream keeps (no device is touched); the range must lie
+ * within the ids handed out so far, else VOX_ERR_INVALID and nothing is written; while levels are off: VOX_ERR_INVALID.  An id handed out while levels were
+ * off has (NaN, NaN).  A decode-engine hand-off timeout repeats decode steps, never a tick: level records are not computed again.  A peek's tail ticks write their
+ * records behind the stream's position, where the stream's own ticks overwrite them; the stream's list is not extended and there is no call for a peek's records (a
+ * tail is mostly pad).  A session blob carries no level records: after vox_stream_restore the ids handed out so far have (NaN, NaN), later ids the records of the
+ * uninterrupted session; the restored stream's own flag is what counts.
+ * vox_stream_quiet: the end-of-speech hint -- *ticks = the number of trailing records of the ids handed out in the current utterance whose peak < peak_below (finite,
+ * > 0); a NaN record ends the run.  Host memory only.  ticks x 160 ms is the quiet time as of the last id k handed out, that is as of sample 2560 k. */
+int32_t vox_stream_set_levels(vox_stream* s, int32_t on);
+int32_t vox_stream_levels(const vox_stream* s, int32_t first_id, int32_t n, vox_tick_level* out);
+int32_t vox_stream_quiet(const vox_stream* s, float peak_below, int32_t* ticks);
 /* test tap, modelled on vox_debug_batch_tap_*: from now on keep the f32 logits row behind each id handed out (up to max_rows); fetch copies them to the host
  * ([min(rows, max_rows)][vocab]; *rows = rows produced since arm) and ends the tap */
 int32_t vox_debug_stream_tap_arm(vox_stream* s, int32_t max_rows);
@@ -908,6 +948,12 @@ int32_t vox_stream_group_peek(vox_stream_group* g, vox_stream_feed* feeds, int32
 int32_t vox_stream_group_set_alternatives(vox_stream_group* g, int32_t member, int32_t k);
 int32_t vox_stream_group_alternatives(const vox_stream_group* g, int32_t member, int32_t first_id, int32_t n, vox_token_alts* out);
 int32_t vox_stream_group_peeked_alternatives(const vox_stream_group* g, int32_t member, vox_token_alts* out, int32_t cap, int32_t* n);
+/* vox_stream_set_levels / vox_stream_levels / vox_stream_quiet for one member (LEVELS above): the flag survives the member's resets; a round -- a burst round with a
+ * block per tick and slot -- launches the level kernel once for all its slots, and only while some member has levels on; the member's records have the bits a solo
+ * stream fed the same samples at the same gain has, and are counted in vox_stream_group_info [5] */
+int32_t vox_stream_group_set_levels(vox_stream_group* g, int32_t member, int32_t on);
+int32_t vox_stream_group_levels(const vox_stream_group* g, int32_t member, int32_t first_id, int32_t n, vox_tick_level* out);
+int32_t vox_stream_group_quiet(const vox_stream_group* g, int32_t member, float peak_below, int32_t* ticks);
 /* vox_debug_stream_tap_* for one member (the rows are copied by the tick's last kernel; a reset of the member starts the count again) */
 int32_t vox_debug_stream_group_tap_arm(vox_stream_group* g, int32_t member, int32_t max_rows);
 int32_t vox_debug_stream_group_tap_fetch(vox_stream_group* g, int32_t member, float* out, int32_t* rows);

@@ -5,6 +5,7 @@
     python tools/stream_bench.py --group 1,2,4,8,16 [--out profiles/stream_group_tick.txt]
     python tools/stream_bench.py --group 1,4,16 --rate 48000 --s16 [--out profiles/stream_group_rate_tick.txt]
     python tools/stream_bench.py --scores [--group 1,4,16] [--out profiles/stream_scores_tick.txt]
+    python tools/stream_bench.py --levels [--group 1,4,16] [--out profiles/stream_levels_tick.txt]
     python tools/stream_bench.py --alternatives 8 [--group 1,4,16] [--out profiles/stream_alternatives_tick.txt]
     python tools/stream_bench.py --peek [--out profiles/stream_peek.txt]
     python tools/stream_bench.py --group 1,4,16 --page-rows 256 [--out profiles/stream_group_paged_tick.txt]
@@ -27,6 +28,8 @@
    round of the same run: what the ingest costs (the larger host copies, the conversion and resampling launches, the extra passes of a push larger than the input ring).
    A fourth pass feeds a third group at SR Hz from device memory, which takes the host copies out of the difference.  A round grows with the decoder position, so
    all three groups are warmed alike and run one timed pass per loop: pass i of each covers the same positions (the rate groups' to within one tick).
+ * --levels: what levels cost (vox_stream_set_levels: one more launch per tick or round, 10 KB of samples read per member), measured as --scores measures scores: twins
+   with levels on, pass i behind pass i of the plain session.  Combines with --scores and --alternatives.
  * --scores: what scores cost (vox_stream_set_scores: one more launch per tick, one logits row written and read per session).  A second solo stream -- with --group
    also a second group -- runs with scores on, warmed like the first and timed the same way in the same loop: pass i of the scored session follows pass i of the
    unscored one and covers the same positions.  The unscored figures are the tool's usual ones (comparable with a run without the flag); the difference is reported.
@@ -116,8 +119,10 @@ def launch_counts(pkg):
 
 
 def twin_kinds(a):
-    """--scores / --alternatives K: (what is on, how a solo stream turns it on, how a group member does)."""
+    """--scores / --alternatives K / --levels: (what is on, how a solo stream turns it on, how a group member does)."""
     kinds = []
+    if a.levels:
+        kinds.append(("levels on", lambda st: st.set_levels(True), lambda g, k: g.set_levels(k, True)))
     if a.scores:
         kinds.append(("scores on", lambda st: st.set_scores(True), lambda g, k: g.set_scores(k, True)))
     if a.alternatives:
@@ -127,6 +132,8 @@ def twin_kinds(a):
 
 def twin_recorded(what, st):
     """Every id of the timed twin got its record."""
+    if what.startswith("levels"):      # (the ids of the warm-up push included: the twin had levels on from its first tick)
+        return not np.isnan(st.levels()["peak"]).any()
     return not np.isnan(st.scores()["logprob"]).any() if what.startswith("scores") else not np.isnan(st.alternatives()["entropy"]).any()
 
 
@@ -497,6 +504,8 @@ def main():
     ap.add_argument("--s16", action="store_true", help="with --rate: feed that group 16-bit PCM")
     ap.add_argument("--scores", action="store_true", help="also time a stream (with --group: and a group) with scores on, pass by pass next to the unscored one")
     ap.add_argument("--alternatives", type=int, default=0, metavar="K", help="also time a stream (with --group: and a group) with alternatives on at k = K (1..8), as --scores does")
+    ap.add_argument("--levels", action="store_true", help="also time a stream (with --group: and a group) with levels on (vox_stream_set_levels: one more launch per tick, in front of the "
+                    "mel launch), as --scores does; combines with --scores and --alternatives")
     ap.add_argument("--page-rows", type=int, default=0, metavar="R", help="with --group: also time a paged group (pages of R rows, the default pool) pass by pass next to the slab group")
     ap.add_argument("--kv", choices=("f32", "bf16"), default="f32", help="with --group and --page-rows: bf16 also times a paged group with a bf16 K/V pool pass by pass behind the f32 paged group")
     ap.add_argument("--delays", choices=("mixed",), default=None, help="with --group: also time a group with a delay per member (member z at delay 2 + z) pass by pass behind the uniform group")
@@ -510,26 +519,26 @@ def main():
     a = ap.parse_args()
     bursts = [int(v) for v in a.burst.split(",")] if a.burst else []
     if bursts and a.group:      # --group N --burst B[,B...]: the burst groups' mode (B = 0 alone: the plain group by itself, for a build without burst groups)
-        if a.endless or a.peek or a.scores or a.alternatives or a.page_rows or a.memory_past_window or a.snapshot or a.rate or "," in a.group:
+        if a.endless or a.peek or a.scores or a.alternatives or a.levels or a.page_rows or a.memory_past_window or a.snapshot or a.rate or "," in a.group:
             ap.error("--group N --burst B[,B...] is a mode of its own, with one width")
         bursts = [b for b in bursts if b != 0]
-    elif bursts and (a.endless or a.peek or a.scores or a.alternatives or a.page_rows or a.memory_past_window or a.snapshot):
+    elif bursts and (a.endless or a.peek or a.scores or a.alternatives or a.levels or a.page_rows or a.memory_past_window or a.snapshot):
         ap.error("--burst is a mode of its own")
     if any(not 1 <= b <= 16 for b in bursts):
         ap.error("--burst takes burst_ticks 1..16")
     if a.burst and "--ticks" not in " ".join(sys.argv):
         a.ticks = 64
-    if a.snapshot and (a.group or a.endless or a.peek or a.scores or a.alternatives or a.page_rows or a.memory_past_window):
+    if a.snapshot and (a.group or a.endless or a.peek or a.scores or a.alternatives or a.levels or a.page_rows or a.memory_past_window):
         ap.error("--snapshot is a mode of its own")
-    if a.memory_past_window and (not a.page_rows or a.group or a.endless or a.peek or a.scores or a.alternatives):
+    if a.memory_past_window and (not a.page_rows or a.group or a.endless or a.peek or a.scores or a.alternatives or a.levels):
         ap.error("--memory-past-window takes --page-rows and nothing else")
     if a.endless and a.group and not a.page_rows:
         ap.error("--endless with --group times an endless PAGED group: give --page-rows")
-    if a.endless and not a.group and (a.scores or a.alternatives or a.peek):
+    if a.endless and not a.group and (a.scores or a.alternatives or a.levels or a.peek):
         ap.error("--endless without --group is a mode of its own")
     if not 0 <= a.alternatives <= 8:
         ap.error("--alternatives takes 1..8")
-    if a.peek and (a.group or a.scores or a.alternatives):
+    if a.peek and (a.group or a.scores or a.alternatives or a.levels):
         ap.error("--peek is a mode of its own")
     if a.kv != "f32" and not (a.group and a.page_rows):
         ap.error("--kv bf16 times a bf16 PAGED group: give --group and --page-rows")

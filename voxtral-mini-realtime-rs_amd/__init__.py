@@ -15,4 +15,4 @@ from . import export  # noqa: F401  (SafeTensors -> Q4_0 GGUF)
 from . import shard  # noqa: F401  (multi-GPU: LPT sharding of independent utterances; torch imported lazily)
 from .models import VoxtralModel, VoxtralModelLoader  # noqa: F401
 from .gguf import (Context, device_count, GgufReader, Q4Tensor, Q4Linear, q4_matmul, Q4ModelLoader, Q4VoxtralModel, tensor_add_dev, argmax_rows_dev, linear_forward, conv_downsample,
-                   LiveStream, LiveStreamGroup, stream_schedule, stream_schedule_rate, stream_peek_ids, stream_group_pages_for, score_rows, stream_id_due, words, SCORE_DTYPE, alternatives_rows, ALTS_DTYPE, records_rows, snapshot_info, snapshot_bytes_for, stream_burst_len, stream_group_burst_rounds)  # noqa: F401
+                   LiveStream, LiveStreamGroup, stream_schedule, stream_schedule_rate, stream_peek_ids, stream_group_pages_for, score_rows, stream_id_due, words, SCORE_DTYPE, alternatives_rows, ALTS_DTYPE, records_rows, snapshot_info, snapshot_bytes_for, stream_burst_len, stream_group_burst_rounds, level_window, level_db, quiet_ticks, LEVEL_DTYPE)  # noqa: F401

@@ -269,6 +269,16 @@ SIGNATURES = {
     "vox_stream_group_t_embed": (i32, [vp, i32, vp, i32]),
     # (ctx, w, vox_resid_xf_desc, x, resid, xf_w, scales, order or null, out, xf_out, ssq_out): ONE launch of the wo GEMM's EPI_RESID_XF epilogue
     "vox_debug_resid_xf": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    # levels: (stream, on); (stream, first_id, n, out); (stream, peak_below, ticks); the same with a member; (k, first, end);
+    # (ctx, n_members, rings, ring_n, gains, pos, frame, order, n_slots, ticks, burst_b or null, list_len, out): ONE launch of the level kernel
+    "vox_stream_set_levels": (i32, [vp, i32]),
+    "vox_stream_levels": (i32, [vp, i32, i32, vp]),
+    "vox_stream_quiet": (i32, [vp, f32, P(i32)]),
+    "vox_stream_group_set_levels": (i32, [vp, i32, i32]),
+    "vox_stream_group_levels": (i32, [vp, i32, i32, i32, vp]),
+    "vox_stream_group_quiet": (i32, [vp, i32, f32, P(i32)]),
+    "vox_level_window": (i32, [i32, P(i64), P(i64)]),
+    "vox_debug_stream_level": (i32, [vp, i32, vp, i32, vp, vp, vp, vp, i32, i32, vp, i32, vp]),
     "vox_transcribe_audio_scored": (i32, [vp, vp, sz, vp, vp, i32, P(i32), vp, vp, i32, i32]),
     "vox_transcribe_batch_scored": (i32, [vp, i32, P(vp), P(sz), vp, vp, P(vp), P(i32), P(i32), vp, vp, i32, i32]),
 }

@@ -101,17 +101,38 @@ def transcribe_one(pkg, path, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed
     return " ".join(texts)
 
 
-def write_words(out, pkg, path, ids, scores, tokenizer, rate, alternatives=None, delay=None):
+def write_words(out, pkg, path, ids, scores, tokenizer, rate, alternatives=None, delay=None, levels=None):
     """--live-words: one JSON line per word of a file that has ended (pkg.words: text, first_id, last_id, due_s, logprob, min_margin) + the file's path; with
-    --live-alternatives also the word's entropy and the alternatives of its weakest id; delay (--live-delays): the delay of the member that ran the file."""
+    --live-alternatives also the word's entropy and the alternatives of its weakest id; delay (--live-delays): the delay of the member that ran the file; with
+    --live-levels also peak_db and rms_db -- null where the level has no finite dB figure: digital silence (a level of 0 is -inf dB) or an id without a record, so that
+    every line stays strict JSON."""
     import json
-    for w in pkg.words(ids, scores, tokenizer, sample_rate=rate, alternatives=alternatives):
+    import math
+    for w in pkg.words(ids, scores, tokenizer, sample_rate=rate, alternatives=alternatives, levels=levels):
+        if levels is not None:
+            w = dict(w, peak_db=w["peak_db"] if math.isfinite(w["peak_db"]) else None, rms_db=w["rms_db"] if math.isfinite(w["rms_db"]) else None)
         w = dict(w, file=path) if delay is None else dict(w, file=path, delay=int(delay))
         out.write(json.dumps(w, ensure_ascii=False) + "\n")
     out.flush()
 
 
-def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_rate=False, words_out=None, peek=False, alts_k=0, endless=False, suspend_every=0, burst=0):
+class Endpoint:
+    """--live-endpoint-ms MS [--live-endpoint-db DB]: one session's end-of-speech trigger on its quiet_ticks.  due(ids_out, quiet) is True once per quiet run -- the
+    maximal run of quiet records that ends at the last id -- when the run has reached MS; a non-quiet (or missing) record starts the next run, which re-arms it."""
+
+    def __init__(self, ms, db):
+        self.ms, self.db, self.fired = ms, db, None
+
+    def due(self, ids_out, quiet):
+        run = ids_out - quiet      # the id the run began at
+        if quiet == 0 or quiet * 160 < self.ms or self.fired == run:
+            return False
+        self.fired = run
+        return True
+
+
+def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_rate=False, words_out=None, peek=False, alts_k=0, endless=False, suspend_every=0, burst=0, levels=False,
+                    endpoint_ms=0, endpoint_db=-50.0):
     """--live: the file through a live session (vox_stream) in pieces of `chunk_ms` milliseconds, the text so far on stderr whenever ids arrive.  The gain is the
     file's peak scale 0.95 / max|x| (bin/transcribe.rs:207; a file is known in advance -- a microphone caller passes its own), the whole file is one utterance (no
     --max-mel-frames chunks: the session's state is bounded by its ring), so the line equals the un-chunked path's.
@@ -126,7 +147,10 @@ def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_
     suspend_every (--live-suspend-every N): after every N pushes the session is snapshotted to host memory (vox_stream_snapshot), the stream is freed, and a fresh one
     is restored from the blob (vox_stream_restore) -- what a server does with a caller on hold; the line is the same.
     burst (--live-burst B): the session is a burst stream (vox_stream_create_burst): a chunk longer than a tick runs its ticks in bursts of up to B; the line is the
-    same up to near-ties, and depends on --live-chunk-ms up to near-ties."""
+    same up to near-ties, and depends on --live-chunk-ms up to near-ties.
+    levels (--live-levels): the session runs with levels on (vox_stream_set_levels) and every --live-words line carries peak_db and rms_db.
+    endpoint_ms / endpoint_db (--live-endpoint-ms, --live-endpoint-db; levels are on): after a push whose quiet time (quiet_ticks x 160 ms below endpoint_db) has reached
+    endpoint_ms, ONE peek per quiet run prints the tentative "  ~[" line as --live-peek does; the session goes on, the next non-quiet record re-arms the trigger."""
     x, sr = load_wav(path)
     rate = 16000
     if sr != 16000:
@@ -147,8 +171,11 @@ def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_
             st.set_scores(True)
             if alts_k:
                 st.set_alternatives(alts_k)
+        if levels:
+            st.set_levels(True)
         return st
     stream = create()
+    endpoint = Endpoint(endpoint_ms, endpoint_db) if endpoint_ms else None
     try:
         ids = []
         text = lambda tail=(): tokenizer.decode([t for t in ids + [int(v) for v in tail] if t >= 1000]).strip()   # :309-318
@@ -158,13 +185,15 @@ def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_
                 ids.extend(int(t) for t in new); log(f"  [{min(a + step, x.size) / rate:8.2f} s] {text()}")
             if peek:
                 log(f"  ~[{min(a + step, x.size) / rate:8.2f} s] {text(stream.peek())}")
+            elif endpoint is not None and endpoint.due(len(ids), stream.quiet_ticks(endpoint.db)):
+                log(f"  ~[{min(a + step, x.size) / rate:8.2f} s] {text(stream.peek())}")
             if suspend_every and (a // step + 1) % suspend_every == 0:
                 blob = stream.snapshot(); stream.close()
                 stream = create(); stream.restore(blob)
                 log(f"  *[{min(a + step, x.size) / rate:8.2f} s] suspended to {blob.size} bytes and resumed in a fresh stream")
         ids.extend(int(t) for t in stream.finish())
         if words_out is not None:
-            write_words(words_out, pkg, path, ids, stream.scores(), tokenizer, rate, stream.alternatives() if alts_k else None)
+            write_words(words_out, pkg, path, ids, stream.scores(), tokenizer, rate, stream.alternatives() if alts_k else None, levels=stream.levels() if levels else None)
         return text()
     finally:
         stream.close()
@@ -186,8 +215,9 @@ def parse_live_delays(text, n_members):
 
 
 def transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, chunk_ms, n_members, words_out=None, peek=False, alts_k=0, page_rows=None, pool_pages=None, endless=False,
-                          suspend_every=0, kv_dtype=None, delays=None):
-    """(delays, --live-delays: one delay per member -- the group is made by vox_stream_group_create_t_embeds, member k's files run at delays[k], and every --live-words
+                          suspend_every=0, kv_dtype=None, delays=None, levels=False, endpoint_ms=0, endpoint_db=-50.0):
+    """(levels / endpoint_ms / endpoint_db: as transcribe_live's, per member -- the members whose trigger is due after a call share one group peek.)
+    (delays, --live-delays: one delay per member -- the group is made by vox_stream_group_create_t_embeds, member k's files run at delays[k], and every --live-words
     line gains "delay"; None: every member at t_embed.)
     (kv_dtype, --live-kv f32 | bf16: the paged group's K/V pool dtype, vox_stream_group_create_kv; the lines have the same form.)
     --live-group N: the files N at a time through one stream group (vox_stream_group) in pieces of `chunk_ms` milliseconds: every call feeds each busy member its
@@ -202,7 +232,10 @@ def transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, chunk_ms, 
     group = model.create_stream_group(None if delays else t_embed, n_members, page_rows=page_rows, pool_pages=pool_pages, endless=endless, kv_dtype=kv_dtype, delays=delays)
     text = lambda ids: tokenizer.decode([t for t in ids if t >= 1000]).strip()
     texts = {}; busy = {}; nxt = 0; calls = 0      # busy: member -> [file index, samples, offset, ids]
+    endpoints = {}      # member -> its file's Endpoint
     try:
+        for k in range(n_members if levels else 0):
+            group.set_levels(k, True)
         for k in range(n_members if words_out is not None else 0):
             group.set_scores(k, True)
             if alts_k:
@@ -221,6 +254,8 @@ def transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, chunk_ms, 
                     peak = np.float32(np.abs(x).max()) if x.size else np.float32(0)
                     group.reset(k, float(np.float32(0.95) / peak) if peak >= 1e-10 else 1.0)      # audio/io.rs:59-68
                     busy[k] = [i, x, 0, []]
+                    if endpoint_ms:
+                        endpoints[k] = Endpoint(endpoint_ms, endpoint_db)
             if not busy:
                 break
             feeds = {k: b[1][b[2]:b[2] + step] for k, b in busy.items()}
@@ -232,8 +267,10 @@ def transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, chunk_ms, 
             for k in last:
                 b = busy.pop(k); texts[b[0]] = text(b[3])
                 if words_out is not None:
-                    write_words(words_out, pkg, paths[b[0]], b[3], group.scores(k), tokenizer, 16000, group.alternatives(k) if alts_k else None, delay=delays[k] if delays else None)
-            for k, tail in (group.peek(sorted(busy)) if peek and busy else {}).items():
+                    write_words(words_out, pkg, paths[b[0]], b[3], group.scores(k), tokenizer, 16000, group.alternatives(k) if alts_k else None, delay=delays[k] if delays else None,
+                                levels=group.levels(k) if levels else None)
+            ended = [] if peek or not endpoint_ms else [k for k in sorted(busy) if endpoints[k].due(len(busy[k][3]), group.quiet_ticks(k, endpoint_db))]
+            for k, tail in (group.peek(sorted(busy)) if peek and busy else group.peek(ended) if ended else {}).items():
                 b = busy[k]; log(f"  ~[{paths[b[0]]} {min(b[2], b[1].size) / 16000:8.2f} s] {text(b[3] + [int(v) for v in tail])}")
             calls += 1
             for k in (sorted(busy) if suspend_every and calls % suspend_every == 0 else []):
@@ -412,6 +449,12 @@ def main(argv=None):
     ap.add_argument("--live-peek", action="store_true", help="with --live (also with --live-group, --live-native-rate, --live-words): after every push a line starting with "
                     "'  ~[' on stderr: the text so far plus the tentative tail, i.e. the line if the file ended here (vox_stream_peek); stdout, the '  [' lines and the "
                     "words file do not change")
+    ap.add_argument("--live-levels", action="store_true", help="with --live (also with --live-group): run the sessions with levels on (vox_stream_set_levels): every "
+                    "--live-words line also carries peak_db and rms_db, the level of the audio the model had just heard while it chose the word's ids")
+    ap.add_argument("--live-endpoint-ms", type=int, default=None, metavar="MS", help="with --live (implies --live-levels): the end-of-speech hint -- after a push whose quiet time "
+                    "(trailing 160 ms ticks with a peak below --live-endpoint-db) has reached MS, peek once per quiet run and print the tentative \"  ~[\" line as "
+                    "--live-peek prints it, then go on; the next non-quiet tick re-arms it")
+    ap.add_argument("--live-endpoint-db", type=float, default=-50.0, metavar="DB", help="with --live-endpoint-ms: the quiet threshold in dBFS of the gained samples (default -50)")
     ap.add_argument("--live-words", metavar="PATH", help="with --live: run the sessions with scores on (vox_stream_set_scores) and write one JSON line per word to PATH when "
                     "a file ends: text, first_id / last_id (indices into the file's ids), due_s (when the session hands the word's last id out, in seconds of pushed audio: "
                     "not where the word was said), logprob (summed over the word's ids), min_margin (the smallest top-2 margin among them), file; stdout is unchanged")
@@ -438,6 +481,12 @@ def main(argv=None):
     if a.live_alternatives is not None and not 1 <= a.live_alternatives <= 8:
         ap.error("--live-alternatives takes 1..8")
     a.live_alternatives = a.live_alternatives or 0
+    if a.live_endpoint_ms is not None and (not a.live or a.live_endpoint_ms <= 0):
+        ap.error("--live-endpoint-ms MS (MS > 0) applies with --live")
+    if a.live_levels and not a.live:
+        ap.error("--live-levels applies with --live")
+    a.live_endpoint_ms = a.live_endpoint_ms or 0
+    a.live_levels = a.live_levels or bool(a.live_endpoint_ms)
     if a.live_peek and not a.live:
         ap.error("--live-peek applies with --live")
     if a.live_suspend_every and (not a.live or a.live_suspend_every < 0):
@@ -563,7 +612,7 @@ def main(argv=None):
                         write_word_lines(rec_out, runner.words.get((i, k), []))
     if a.live_group:
         try:
-            texts = transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_group, words_out, a.live_peek, a.live_alternatives, a.live_page_rows, a.live_pool_pages, a.live_endless, a.live_suspend_every, a.live_kv, a.live_delays)
+            texts = transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_group, words_out, a.live_peek, a.live_alternatives, a.live_page_rows, a.live_pool_pages, a.live_endless, a.live_suspend_every, a.live_kv, a.live_delays, a.live_levels, a.live_endpoint_ms, a.live_endpoint_db)
         except Exception as e:      # the files fall back to one live session each
             log(f"Error in the stream group: {e}"); texts = {}
             if words_out is not None:      # the files' words come again with their lines
@@ -575,7 +624,7 @@ def main(argv=None):
         p = paths[i]
         try:
             t1 = time.time()
-            text = transcribe_live(pkg, p, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_native_rate, words_out, a.live_peek, a.live_alternatives, a.live_endless, a.live_suspend_every, a.live_burst) if a.live else transcribe_one(pkg, p, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed, rec_out, a.alternatives or 0)
+            text = transcribe_live(pkg, p, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_native_rate, words_out, a.live_peek, a.live_alternatives, a.live_endless, a.live_suspend_every, a.live_burst, a.live_levels, a.live_endpoint_ms, a.live_endpoint_db) if a.live else transcribe_one(pkg, p, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed, rec_out, a.alternatives or 0)
             log(f"{p}: {time.time() - t1:.3f}s")
         except Exception as e:      # per-utterance failure isolates to that line (empty), eval_wer.py:211-223 tolerates it
             log(f"Error transcribing {p}: {e}"); text = ""; rc = 1

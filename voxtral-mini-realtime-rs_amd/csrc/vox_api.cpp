@@ -1454,6 +1454,48 @@ extern "C" int32_t vox_debug_stream_ring_init(vox_ctx* c, int32_t layers, int32_
     HIPCHK(hipStreamSynchronize(s));
     return VOX_OK;
 }
+// the sessions' level kernel on hand-made sessions (tests): ONE launch_stream_level -- the plain form, a solo burst's or a burst round's ragged one -- on uploaded
+// rings and state words; every list comes back, the records the launch did not write as (NaN, NaN)
+extern "C" int32_t vox_debug_stream_level(vox_ctx* c, int32_t n_members, const float* rings, int32_t ring_n, const float* gains, const int32_t* pos, const int32_t* frame,
+                                          const int32_t* order, int32_t n_slots, int32_t ticks, const int32_t* burst_b, int32_t list_len, vox_tick_level* out) {
+    ARGCHK(c && rings && gains && pos && frame && order && out, "null argument");
+    ARGCHK(n_members >= 1 && n_members <= 16 && n_slots >= 1 && n_slots <= n_members, "%d slots of %d members (1..16, slots <= members)", n_slots, n_members);
+    ARGCHK(ring_n >= 4096 && ring_n <= (1 << 20) && !(ring_n & (ring_n - 1)), "ring_n %d: a power of two in 4096 .. 2^20", ring_n);
+    ARGCHK(ticks >= 1 && ticks <= VOX_STREAM_BURST_MAX, "ticks %d out of range (1..%d)", ticks, VOX_STREAM_BURST_MAX);
+    ARGCHK(list_len >= 1 && list_len <= 65536, "list_len %d out of range (1..65536)", list_len);
+    unsigned seen = 0;
+    for (int z = 0; z < n_slots; z++) {
+        ARGCHK(order[z] >= 0 && order[z] < n_members && !(seen >> order[z] & 1u), "order[%d] = %d: members 0..%d, each once", z, order[z], n_members - 1);
+        seen |= 1u << order[z];
+        if (burst_b) ARGCHK(burst_b[z] >= 1 && burst_b[z] <= ticks && (z == 0 || burst_b[z] <= burst_b[z - 1]), "burst_b[%d] = %d: 1..%d, descending", z, burst_b[z], ticks);
+    }
+    for (int i = 0; i < n_members; i++) {
+        ARGCHK(pos[i] >= VOX_PREFIX_TOKENS - 1 && pos[i] <= (1 << 24) && frame[i] >= 0 && frame[i] <= (1 << 28), "member %d: position %d, frame %d", i, pos[i], frame[i]);
+        ARGCHK(std::isfinite(gains[i]), "member %d: gain is not finite", i);
+    }
+    VOXCHK(ctx_bind(c));
+    hipStream_t s = c->stream;
+    vox_pad_cfg pc; vox_pad_cfg_voxtral(&pc); const long left = (long)pad_left(&pc);
+    const size_t NM = (size_t)n_members, ring_b = NM * ring_n * 4, list_b = NM * list_len * sizeof(TickLevel);
+    DevBuf drings, dstate, dlists, dmem, dorder, ddesc;
+    HIPCHK(drings.alloc(ring_b)); HIPCHK(dstate.alloc(NM * STRM_WORDS * 4)); HIPCHK(dlists.alloc(list_b)); HIPCHK(dmem.alloc(NM * sizeof(StreamMember))); HIPCHK(dorder.alloc(16 * 4));
+    std::vector<int> state(NM * STRM_WORDS, 0); std::vector<StreamMember> mem(NM, StreamMember{}); int h_order[16] = {0};
+    for (size_t i = 0; i < NM; i++) {
+        state[i * STRM_WORDS + STRM_POS] = pos[i]; state[i * STRM_WORDS + STRM_FRAME] = frame[i];
+        mem[i].samples = drings.as<float>() + i * ring_n; mem[i].gain = gains[i]; mem[i].state = dstate.as<int>() + i * STRM_WORDS;
+        mem[i].levels = dlists.as<TickLevel>() + i * list_len; mem[i].levels_cap = list_len;
+    }
+    for (int z = 0; z < n_slots; z++) h_order[z] = order[z];
+    StreamBurstDesc bd; std::memset(&bd, 0, sizeof bd);
+    if (burst_b) { int t0 = 0; for (int z = 0; z < n_slots; z++) { bd.tick0[z] = t0; bd.b[z] = burst_b[z]; t0 += burst_b[z]; } HIPCHK(ddesc.alloc(sizeof bd)); HIPCHK(hipMemcpyAsync(ddesc.p, &bd, sizeof bd, hipMemcpyHostToDevice, s)); }
+    HIPCHK(hipMemcpyAsync(drings.p, rings, ring_b, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(dstate.p, state.data(), NM * STRM_WORDS * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dmem.p, mem.data(), NM * sizeof(StreamMember), hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(dorder.p, h_order, sizeof h_order, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(dlists.p, 0xFF, list_b, s));      // every record (NaN, NaN)
+    HIPCHK(launch_stream_level(dmem.as<StreamMember>(), dorder.as<int>(), n_slots, ring_n - 1, left, VOX_PREFIX_TOKENS - 1, ticks, burst_b ? ddesc.as<StreamBurstDesc>() : nullptr, burst_b ? &bd : nullptr, s));
+    HIPCHK(hipMemcpyAsync(out, dlists.p, list_b, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return VOX_OK;
+}
 // What a batched XF decode step works on.  f32 rows (h, qkv, logits; att unread), XF planes and partial sums of squares one block per 16-row group, `*_gs` elements apart.
 // k / v: layer 0's cache slab (layer l at + l layer_stride), row r's slice at + r seq_stride, or, with kv_row, the slice kv_row[r] names; pos: the rows' positions.
 // ssq_e: the batched engine's sums of squares (one block of 256 + 16 rows per group); planes: the wide step's K-split scratch, planes_bytes per chain.
@@ -3128,12 +3170,52 @@ struct AltsState {
         return VOX_OK;
     }
 };
+// A session's levels (vox_stream_set_levels; DESIGN.md section 8, "Levels"): ScoreState's twin for the 8-byte records stream_level_kernel writes in front of a tick's
+// mel launch.  An engine hand-off timeout repeats decode steps, never a tick (stream_settle comes back through stream_decode_step alone), so level records are never
+// computed again.  A peek's tail writes its records behind the session's position and hands none out: the host list is the session's own.  A session that never had
+// levels on (dev null) keeps no list.
+static_assert(sizeof(vox_tick_level) == 8 && sizeof(TickLevel) == sizeof(vox_tick_level), "vox_tick_level is TickLevel");
+struct LevelState {
+    bool on = false; TickLevel* dev = nullptr; int cap = 0;
+    std::vector<vox_tick_level> host;
+    size_t bytes() const { return dev ? (size_t)cap * sizeof(TickLevel) : 0; }
+    static vox_tick_level off() { return vox_tick_level{NAN, NAN}; }
+    int32_t alloc(int max_pos, const char* whose) {      // the first set(1)
+        if (dev) return VOX_OK;
+        if (hipMalloc((void**)&dev, (size_t)(max_pos + 2) * sizeof(TickLevel)) != hipSuccess) { (void)hipGetLastError(); dev = nullptr; return fail(VOX_ERR_HIP, "hipMalloc of %s level records failed", whose); }
+        cap = max_pos + 2; return VOX_OK;
+    }
+    int32_t grow(int rows, hipStream_t s) { return list_grow((void**)&dev, &cap, rows, sizeof(TickLevel), s); }      // as ScoreState::grow
+    void restart() { host.clear(); }      // create / reset: the list starts over, the flag stays
+    // in front of the call's synchronisation: the call's `due` records behind the `have` handed out go to the session's list (a peek: nowhere); off: the records that say so
+    int32_t enqueue(int have, int due, bool peek, hipStream_t s) {
+        if (peek || !dev) return VOX_OK;
+        host.resize((size_t)have + due, off());
+        if (on && due > 0) HIPCHK(hipMemcpyAsync(host.data() + have, dev + have, (size_t)due * sizeof(TickLevel), hipMemcpyDeviceToHost, s));
+        return VOX_OK;
+    }
+    int32_t read(int have, int32_t first_id, int32_t n, vox_tick_level* out) const {
+        ARGCHK(on, "levels are off (vox_stream_set_levels)");
+        ARGCHK(first_id >= 0 && n >= 0 && (int64_t)first_id + n <= have, "%d ids from %d on: %d handed out", n, first_id, have);
+        ARGCHK(out || n == 0, "null output");
+        for (int i = 0; i < n; i++) out[i] = (size_t)(first_id + i) < host.size() ? host[(size_t)(first_id + i)] : off();
+        return VOX_OK;
+    }
+    // the end-of-speech hint: the trailing records of the `have` ids handed out whose peak < peak_below; a NaN record (a comparison with it is false) ends the run
+    int32_t quiet(int have, float peak_below, int32_t* ticks) const {
+        ARGCHK(ticks, "null argument"); ARGCHK(std::isfinite(peak_below) && peak_below > 0.0f, "peak_below must be finite and > 0");
+        ARGCHK(on, "levels are off (vox_stream_set_levels)");
+        int n = 0;
+        for (int k = have - 1; k >= 0 && (size_t)k < host.size() && host[(size_t)k].peak < peak_below; k--) n++;
+        *ticks = n; return VOX_OK;
+    }
+};
 // One session's share of one call's hand-back -- a solo stream's push / finish / peek, a member's entry of a group's advance / peek: the call's `due` ids from the
 // session's device token array into the caller's out_ids, their records into the session's own list or, in a peek, into the caller's array (null: none wanted); their
 // alternatives records into the session's list or, in a peek, into the array the session keeps for vox_stream_peeked_alternatives.
 namespace {
 struct SessionOut {
-    FeedState* feed; ScoreState* sc; AltsState* al; const int* tokens; int32_t* out_ids; int due;
+    FeedState* feed; ScoreState* sc; AltsState* al; LevelState* lv; const int* tokens; int32_t* out_ids; int due;
     bool peek; vox_token_score* peek_scores;      // a peek's records never enter the session's list, and ids_out stays
     vox_token_score* dst = nullptr; vox_token_alts* adst = nullptr;
     int32_t enqueue(hipStream_t s) {      // in front of the call's synchronisation: the records travel with the ids
@@ -3141,6 +3223,7 @@ struct SessionOut {
         if (due > 0) HIPCHK(hipMemcpyAsync(out_ids, tokens + VOX_PREFIX_TOKENS + have, (size_t)due * 4, hipMemcpyDeviceToHost, s));
         if (peek) dst = peek_scores; else { sc->host.resize((size_t)have + due); dst = sc->host.data() + have; }
         VOXCHK(sc->enqueue(have, due, dst, s));
+        VOXCHK(lv->enqueue(have, due, peek, s));
         return al->enqueue(have, due, peek, &adst, s);
     }
     void settle() { sc->settle(due, out_ids, dst); al->settle(due, adst); if (!peek) feed->ids_out += due; }      // behind it
@@ -3166,6 +3249,7 @@ struct vox_stream {
     float* tap = nullptr; int tap_max = 0, tap_rows = 0;
     ScoreState sc; float* score_row = nullptr;      // scores: the records, and the logits row a scored step writes when no tap row takes it
     AltsState al;                                   // alternatives: the records (a step with them on writes the same row)
+    LevelState lv;                                  // levels: the records (stream_level_kernel, in front of a tick's mel launch)
     float *ftap_mel = nullptr, *ftap_conv = nullptr; int ftap_max = 0, ftap_ticks = 0;      // vox_debug_stream_front_tap_*: per tick its 4 R fresh mel frames and its R conv-stem rows
     int h_state[STRM_WORDS]; int h_pos_word = 0;
     // vox_stream_peek: the ring keep's save area; while a peek's ticks run (active), a decoder cache that grows leaves its planes in `old`: the peek puts them back
@@ -3266,7 +3350,7 @@ static int32_t stream_load_initial(vox_stream* st) {
     st->feed.restart(st->PC); st->verified_pos = st->PC; st->eng_unverified = false;
     st->eng_steps = st->op_steps = st->verified_eng_steps = st->verified_op_steps = 0; st->tap_rows = st->verified_tap_rows = 0; st->ftap_ticks = 0;
     st->bursts = st->burst_ticks = st->single_ticks = 0;
-    st->sc.host.clear(); st->al.restart();      // the utterance's records start over; the flag and k stay
+    st->sc.host.clear(); st->al.restart(); st->lv.restart();      // the utterance's records start over; the flags and k stay
     return VOX_OK;
 }
 
@@ -3275,7 +3359,7 @@ static void stream_release(vox_stream* st) {
     (void)hipSetDevice(st->ctx->device); (void)hipStreamSynchronize(st->ctx->stream);      // never dereferences st->m: a stream may not outlive its model, but freeing it late must not crash
     cache_release(st->dec);
     for (void* p : {(void*)st->kring, (void*)st->vring, (void*)st->samples, (void*)st->audio_keep, (void*)st->ws, (void*)st->tokens, (void*)st->state, (void*)st->tap, (void*)st->ftap_mel, (void*)st->ftap_conv,
-                    (void*)st->feed.At, (void*)st->feed.in_ring, (void*)st->s16_stage, (void*)st->d_mem, (void*)st->sc.dev, (void*)st->score_row, (void*)st->al.dev,
+                    (void*)st->feed.At, (void*)st->feed.in_ring, (void*)st->s16_stage, (void*)st->d_mem, (void*)st->sc.dev, (void*)st->score_row, (void*)st->al.dev, (void*)st->lv.dev,
                     (void*)st->peek.keep.p, (void*)st->peek.old.k, (void*)st->peek.old.v, (void*)st->rope.dec, (void*)st->rope.enc}) if (p) (void)hipFree(p);
     if (st->rope.h_dec) (void)hipHostFree(st->rope.h_dec); if (st->rope.h_enc) (void)hipHostFree(st->rope.h_enc);
     if (st->rope.copied) (void)hipEventDestroy(st->rope.copied);
@@ -3477,7 +3561,7 @@ static int32_t stream_verify(vox_stream* st) {      // inside a long push: befor
 // w1|w3, w2 } -> final norm -> adapter, every weight matrix in ONE launch for all sessions of the round (4 n rows through q4_linear_dev, which picks the kernel by the row
 // count).  Slot z works for session r.order[z] (device arrays); w.arow[z] is its adapter row.  ftap_*: a solo stream's front tap (null: none).
 // rope (null: the model's streaming table): a solo endless session's encoder RoPE ring, rows = position & rope_mask (StreamAttnParams::rope_mask)
-struct StreamRound { const StreamMember* mem; const int* order; int n, cap; size_t ring_layer; MelTables mel; long left; const float* rope = nullptr; int rope_mask = 0, rope_stride = 0; };      // rope_stride > 0: an endless group's rings, one per member
+struct StreamRound { const StreamMember* mem; const int* order; int n, cap; size_t ring_layer; MelTables mel; long left; const float* rope = nullptr; int rope_mask = 0, rope_stride = 0; bool levels = false; };      // rope_stride > 0: an endless group's rings, one per member; levels: some session of the round has levels on
 // b > 1 (a solo burst stream's round of one, n == 1): the encoder of b ticks in one pass.  Everything the b ticks would read is there before the first (the pass's
 // samples, the state block at the burst's first tick), and tick t's rows are rows 4 t .. of every buffer: 16 b + 3 halo frames, 8 b + 1 and 4 b conv windows, 4 b rows
 // through the layers with the burst attention, b adapter rows (w.arow[t]: tick t's).  ftap_*: room for ftap_b of the burst's ticks, in the per-tick layout.
@@ -3491,6 +3575,10 @@ static int32_t stream_encode_round(vox_model* m, const StreamWs& w, const Stream
     ARGCHK(!rg || (rg->dev && rg->host && rg->ticks >= r.n && rg->ticks <= r.n * b && !ftap_mel), "internal: a ragged round of %d ticks in %d slots of %d", rg ? rg->ticks : 0, r.n, b);
     const int D = c.enc_dim, H = c.enc_heads, hd = c.enc_head_dim, QD = H * hd, F = c.enc_ffn, R = c.reshape_factor, DD = c.dec_dim, Cm = c.n_mels, n = r.n, NT = rg ? rg->ticks : n * b, M = R * NT;
     const int NF = 4 * R * b + 3, HS = NF + 1, C1S = 2 * R * b + 2, C2S = R * b + 1;      // mel frames with the halo (conv row s reads frames 4 s - 3 .. 4 s + 3); the slot strides in frames, conv1 rows, conv rows
+    // the level records of every tick of the pass, in front of the mel launch: the state block is the one the pass's first tick finds (nothing has advanced it), and the
+    // samples are the ones the mel launch is about to read -- whichever of the two comes first pulls them in for the other.  Behind the mel it would sit between two
+    // dependent launches of the encoder's chain for no gain.
+    if (r.levels) HIPCHK(launch_stream_level(r.mem, r.order, n, STREAM_SAMPLE_RING - 1, r.left, VOX_PREFIX_TOKENS - 1, b, rg ? rg->dev : nullptr, rg ? rg->host : nullptr, s));
     HIPCHK(launch_stream_mel(r.mem, r.order, n, STREAM_SAMPLE_RING - 1, r.left, r.mel, 3, NF, w.halo, (long)HS * Cm, s));
     // conv stem without padding rows, memsets or a transpose: conv1 row i of a slot is the window of its halo rows [2 i, 2 i + 2], conv row i the window of its conv1 rows
     // [2 i, 2 i + 2].  The slots lie C1S / C2S windows apart, so one GEMM per conv serves them all; its last window of every slot but the last straddles two slots: that
@@ -3533,16 +3621,19 @@ static int32_t stream_lists_grow(vox_stream* st) {
     VOXCHK(stream_verify(st));
     const int rows = (int)std::min<int64_t>(2LL * st->lists_cap, st->max_pos);
     ARGCHK(rows > st->lists_cap, "internal: the stream's lists of %d positions cannot grow", st->lists_cap);
-    const uint64_t had = st->sc.bytes() + st->al.bytes();
+    const uint64_t had = st->sc.bytes() + st->al.bytes() + st->lv.bytes();
     int tcap = st->lists_cap + 2;
     VOXCHK(list_grow((void**)&st->tokens, &tcap, rows + 2, 4, s)); st->bytes += (uint64_t)(rows - st->lists_cap) * 4;
     if (st->sc.dev) VOXCHK(st->sc.grow(rows + 2, s));
     if (st->al.dev) VOXCHK(st->al.grow(rows + 2, s));
-    st->bytes += st->sc.bytes() + st->al.bytes() - had; st->lists_cap = rows;
+    if (st->lv.dev) VOXCHK(st->lv.grow(rows + 2, s));
+    st->bytes += st->sc.bytes() + st->al.bytes() + st->lv.bytes() - had; st->lists_cap = rows;
     struct { int* tok; TokenScore* sp; int scap; TokenAlts* ap; int acap; } w{st->tokens, st->sc.on ? st->sc.dev : nullptr, st->sc.on ? st->sc.cap : 0, st->al.k > 0 ? st->al.dev : nullptr, st->al.k > 0 ? st->al.cap : 0};
     HIPCHK(hipMemcpyAsync(&st->d_mem->tokens, &w.tok, sizeof w.tok, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(&st->d_mem->scores, &w.sp, sizeof w.sp, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(&st->d_mem->scores_cap, &w.scap, sizeof w.scap, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(&st->d_mem->alts, &w.ap, sizeof w.ap, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(&st->d_mem->alts_cap, &w.acap, sizeof w.acap, hipMemcpyHostToDevice, s));
+    struct { TickLevel* p; int cap; } lw{st->lv.on ? st->lv.dev : nullptr, st->lv.on ? st->lv.cap : 0};
+    HIPCHK(hipMemcpyAsync(&st->d_mem->levels, &lw.p, sizeof lw.p, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(&st->d_mem->levels_cap, &lw.cap, sizeof lw.cap, hipMemcpyHostToDevice, s));
     HIPCHK(hipStreamSynchronize(s));
     return VOX_OK;
 }
@@ -3593,7 +3684,7 @@ static int32_t stream_tick(vox_stream* st) {
     VOXCHK(stream_tick_prepare(st));
     const bool ring = stream_in_ring(st);
     StreamWs w; stream_ws_carve(m, 1, st->ws, &w);
-    StreamRound r{st->d_mem, st->d_order, 1, st->cap, st->ring_layer, st->mel, st->left};
+    StreamRound r{st->d_mem, st->d_order, 1, st->cap, st->ring_layer, st->mel, st->left}; r.levels = st->lv.on;
     if (ring) { r.rope = st->rope.enc; r.rope_mask = STREAM_ROPE_DEC_ROWS * R - 1; }
     const int k = st->ftap_mel ? st->ftap_ticks++ : 0; const bool ftap = st->ftap_mel && k < st->ftap_max;      // (a re-run repeats decode steps, never a tick)
     VOXCHK(stream_encode_round(m, w, r, ftap ? st->ftap_mel + (size_t)k * 4 * R * c.n_mels : nullptr, ftap ? st->ftap_conv + (size_t)k * R * c.enc_dim : nullptr));
@@ -3608,7 +3699,7 @@ static int32_t stream_burst(vox_stream* st, int b) {
     ARGCHK(b >= 2 && b <= st->burst && st->feed.pos + b <= stream_next_stop(st), "internal: a burst of %d ticks at position %d (burst_ticks %d, next stop %lld)", b, st->feed.pos, st->burst, (long long)stream_next_stop(st));
     const bool ring = stream_in_ring(st);
     StreamWs w; stream_ws_carve(m, 1, st->ws, &w, st->burst);
-    StreamRound r{st->d_mem, st->d_order, 1, st->cap, st->ring_layer, st->mel, st->left};
+    StreamRound r{st->d_mem, st->d_order, 1, st->cap, st->ring_layer, st->mel, st->left}; r.levels = st->lv.on;
     if (ring) { r.rope = st->rope.enc; r.rope_mask = STREAM_ROPE_DEC_ROWS * R - 1; }
     const int k = st->ftap_ticks, fb = st->ftap_mel ? std::max(0, std::min(b, st->ftap_max - k)) : 0;      // the burst's ticks the front tap still has room for
     if (st->ftap_mel) st->ftap_ticks += b;
@@ -3700,7 +3791,7 @@ static int32_t stream_run(vox_stream* st, const StreamSrc& src, FeedPlan& plan, 
             t += b;
         }
     }
-    SessionOut o{&f, &st->sc, &st->al, st->tokens, out_ids, due, peek, peek_scores};
+    SessionOut o{&f, &st->sc, &st->al, &st->lv, st->tokens, out_ids, due, peek, peek_scores};
     VOXCHK(stream_verify_enqueue(st));
     bool reran = false;
     for (int round = 0; round < 2; round++) {      // a second time only behind the engine's re-run, which wrote the call's ids (and moved STRM_POS) again
@@ -3801,6 +3892,33 @@ extern "C" int32_t vox_stream_set_scores(vox_stream* st, int32_t on) {
 extern "C" int32_t vox_stream_scores(const vox_stream* st, int32_t first_id, int32_t n, vox_token_score* out) {
     ARGCHK(st, "null stream");
     return st->sc.read(st->feed.ids_out, first_id, n, out);
+}
+
+// levels on / off, as scores: the first on allocates the records; the descriptor carries their pointer only while levels are on, uploaded behind a synchronisation
+extern "C" int32_t vox_stream_set_levels(vox_stream* st, int32_t on) {
+    ARGCHK(st, "null stream"); ARGCHK(on == 0 || on == 1, "on must be 0 or 1"); VOXCHK(ctx_bind(st->ctx));
+    hipStream_t s = st->ctx->stream; LevelState& lv = st->lv;
+    if (on) { const size_t had = lv.bytes(); VOXCHK(lv.alloc(st->lists_cap, "the stream's")); st->bytes += lv.bytes() - had; }
+    HIPCHK(hipStreamSynchronize(s));
+    struct { TickLevel* p; int cap; } w{on ? lv.dev : nullptr, on ? lv.cap : 0};
+    HIPCHK(hipMemcpyAsync(&st->d_mem->levels, &w.p, sizeof w.p, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(&st->d_mem->levels_cap, &w.cap, sizeof w.cap, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    lv.on = on != 0;
+    return VOX_OK;
+}
+extern "C" int32_t vox_stream_levels(const vox_stream* st, int32_t first_id, int32_t n, vox_tick_level* out) {
+    ARGCHK(st, "null stream");
+    return st->lv.read(st->feed.ids_out, first_id, n, out);
+}
+extern "C" int32_t vox_stream_quiet(const vox_stream* st, float peak_below, int32_t* ticks) {
+    ARGCHK(st, "null stream");
+    return st->lv.quiet(st->feed.ids_out, peak_below, ticks);
+}
+// the arithmetic of a record's window (host only): [2560 (k - 1), 2560 k) of the utterance's 16 kHz samples
+extern "C" int32_t vox_level_window(int32_t k, int64_t* first_sample, int64_t* end_sample) {
+    ARGCHK(first_sample && end_sample, "null argument"); ARGCHK(k >= 0, "record index %d", k);
+    *first_sample = (int64_t)LEVEL_TICK * ((int64_t)k - 1); *end_sample = (int64_t)LEVEL_TICK * k;
+    return VOX_OK;
 }
 
 // alternatives at k (0: off), as scores on / off: the first k > 0 allocates the records and, unless scores did, the logits row; the descriptor carries the records'
@@ -3940,7 +4058,7 @@ static size_t snap_stage_bytes(const vox_snap::SnapHeader& h) {
 // device arrays, and its two K / V stacks as launch_snapshot_kv addresses them (everything but the rows and the blob pointers).  The container fills it in; the two
 // functions below never look at the container again.
 struct SnapSession {
-    vox_model* m; vox_ctx* ctx; const std::vector<float>* t_embed; FeedState* feed; ScoreState* sc; AltsState* al; float gain;
+    vox_model* m; vox_ctx* ctx; const std::vector<float>* t_embed; FeedState* feed; ScoreState* sc; AltsState* al; LevelState* lv; float gain;
     int* tokens; float* samples; int* state; int* h_state;
     int cap, PC, max_pos;      // its encoder ring's capacity, the prefix positions, its position limit
     vox::SnapshotKvParams enc, dec;
@@ -4072,6 +4190,7 @@ static int32_t session_restore_payload(const SnapSession& ss, const vox_snap::Sn
         // the records: the blob's lists, or the records of ids handed out with the feature off (the ids: the blob's tokens)
         if (h.ids_out) { const char* t = b + h.sec_off[SEC_TOKENS] + (size_t)VOX_PREFIX_TOKENS * 4; if (dev) HIPCHK(hipMemcpyAsync(ids.data(), t, ids.size() * 4, hipMemcpyDeviceToHost, s)); else std::memcpy(ids.data(), t, ids.size() * 4); }
         ss.sc->host.assign((size_t)h.ids_out, vox_token_score{NAN, NAN, -1, 0}); ss.al->host.clear(); ss.al->peeked.clear();
+        ss.lv->host.clear(); if (ss.lv->dev) ss.lv->host.assign((size_t)h.ids_out, LevelState::off());      // level records are not carried over: the ids so far have none
         if (h.n_alts) ss.al->host.resize((size_t)h.n_alts);
         if (dev) {
             if (h.n_scores) HIPCHK(hipMemcpyAsync(ss.sc->host.data(), b + h.sec_off[SEC_SCORES], (size_t)h.sec_len[SEC_SCORES], hipMemcpyDeviceToHost, s));
@@ -4093,7 +4212,7 @@ static int32_t session_restore_payload(const SnapSession& ss, const vox_snap::Sn
 // ---- a solo stream as a SnapSession.  An endless session's cache is addressed as the ring it becomes: below the wrap row % rows is the row
 static SnapSession stream_session(vox_stream* st) {
     const vox_model_cfg& c = st->m->cfg; const vox_cache* kc = st->dec;
-    SnapSession ss{}; ss.m = st->m; ss.ctx = st->ctx; ss.t_embed = &st->t_embed; ss.feed = &st->feed; ss.sc = &st->sc; ss.al = &st->al; ss.gain = st->gain;
+    SnapSession ss{}; ss.m = st->m; ss.ctx = st->ctx; ss.t_embed = &st->t_embed; ss.feed = &st->feed; ss.sc = &st->sc; ss.al = &st->al; ss.lv = &st->lv; ss.gain = st->gain;
     ss.tokens = st->tokens; ss.samples = st->samples; ss.state = st->state; ss.h_state = st->h_state; ss.cap = st->cap; ss.PC = st->PC; ss.max_pos = st->max_pos; ss.who = "the stream";
     ss.enc.cache_k = st->kring; ss.enc.cache_v = st->vring; ss.enc.layers = c.enc_layers; ss.enc.heads = c.enc_heads; ss.enc.hd = c.enc_head_dim;
     ss.enc.layout = vox::SNAP_RING; ss.enc.cap = st->cap; ss.enc.layer_stride = st->ring_layer; ss.enc.head_stride = (size_t)st->cap * c.enc_head_dim;
@@ -4210,6 +4329,7 @@ struct GroupMember {
     int rate = -1; uint64_t steps = 0;   // its slot of the group's rate table (-1: 16 kHz); its ticks, each one row of an xf_chain step
     ScoreState sc;                       // its scores (vox_stream_group_set_scores); h_mem[i].scores is sc.dev while they are on
     AltsState al;                        // its alternatives (vox_stream_group_set_alternatives); h_mem[i].alts is al.dev while its k > 0
+    LevelState lv;                       // its levels (vox_stream_group_set_levels); h_mem[i].levels is lv.dev while they are on
     int h_state[STRM_WORDS];
     // an endless group's member: its own position-indexed token row of lists_cap + 2 entries (its score and alternatives records have lists_cap + 2 as well), grown
     // by doubling (group_lists_grow).  A bounded group's members share g->tokens and keep 0 / null here
@@ -4235,6 +4355,7 @@ struct vox_stream_group {
     int16_t* s16_stage = nullptr;      // host 16-bit feeds: STREAM_SAMPLE_RING samples of device staging per member, allocated at the first one
     int n_scored = 0;                  // members with scores on: a round launches stream_score_kernel only while there is one
     int n_alts = 0;                    // members with alternatives on: the same for stream_alts_kernel
+    int n_leveled = 0;                 // members with levels on: the same for stream_level_kernel, in front of the round's mel launch
     KeepArea keep;                     // vox_stream_group_peek: [16 ints: the peeking members, slot by slot][a ring keep area per slot]
     // a paged group (vox_stream_group_create_paged): dec_k / dec_v are the page pool [dec_layers][pool_pages][kv_heads][page_rows][hd] (layer_stride = the floats of a
     // layer's pages), pool the allocator with every member's table mirror, d_tab the device table [n][pool.max_pages], d_kv_page / d_kv_in the step's physical pages and
@@ -4333,7 +4454,7 @@ static int32_t group_member_seed(vox_stream_group* g, int i) {
                                HIPCHK(launch_stream_pages_seed(g->m->pfx.dec_k, g->m->pfx.dec_v, c.dec_layers, c.dec_kv_heads, g->g.PC, c.dec_head_dim, g->d_tab + (size_t)i * g->pool.tab_len,
                                                                g->pool.shift, g->layer_stride, g->dec_k, g->dec_v, g->ctx->stream, g->kv_bf16));
                                return VOX_OK; }));
-        me.feed.restart(g->g.PC); me.steps = 0; me.sc.host.clear(); me.al.restart();
+        me.feed.restart(g->g.PC); me.steps = 0; me.sc.host.clear(); me.al.restart(); me.lv.restart();
         return group_member_ada(g, i);
     }
     vox_cache view; view.m = g->m; view.ctx = g->ctx; view.k = g->dec_k + (size_t)i * g->seq_stride; view.v = g->dec_v + (size_t)i * g->seq_stride; view.max_seq = g->g.max_pos;
@@ -4341,14 +4462,14 @@ static int32_t group_member_seed(vox_stream_group* g, int i) {
     GroupMember& me = g->mem[i];
     VOXCHK(stream_seed(g->m, group_t_embed(g, i).data(), g->g.RC, g->g.PC, g->g.cap, g->h_mem[i].kring, g->h_mem[i].vring, &view, g->h_mem[i].tokens, g->h_mem[i].state, me.h_state,
                        []() -> int32_t { return VOX_OK; }));
-    me.feed.restart(g->g.PC); me.steps = 0; me.sc.host.clear(); me.al.restart();
+    me.feed.restart(g->g.PC); me.steps = 0; me.sc.host.clear(); me.al.restart(); me.lv.restart();
     return group_member_ada(g, i);
 }
 static void group_release(vox_stream_group* g) {
     if (!g) return;
     (void)hipSetDevice(g->ctx->device); (void)hipStreamSynchronize(g->ctx->stream);      // never dereferences g->m (as stream_release)
     for (StreamMember& me : g->h_mem) if (me.tap) (void)hipFree(me.tap);
-    for (GroupMember& me : g->mem) { if (me.sc.dev) (void)hipFree(me.sc.dev); if (me.al.dev) (void)hipFree(me.al.dev); if (me.tokens) (void)hipFree(me.tokens); }
+    for (GroupMember& me : g->mem) { if (me.sc.dev) (void)hipFree(me.sc.dev); if (me.al.dev) (void)hipFree(me.al.dev); if (me.lv.dev) (void)hipFree(me.lv.dev); if (me.tokens) (void)hipFree(me.tokens); }
     for (void* p : {(void*)g->rope.dec, (void*)g->rope.enc}) if (p) (void)hipFree(p);
     if (g->rope.h_dec) (void)hipHostFree(g->rope.h_dec); if (g->rope.h_enc) (void)hipHostFree(g->rope.h_enc);
     if (g->rope.copied) (void)hipEventDestroy(g->rope.copied);
@@ -4567,13 +4688,13 @@ extern "C" int32_t vox_stream_group_info(const vox_stream_group* g, int32_t memb
     const uint64_t rate_b = me.rate >= 0 ? (uint64_t)me.feed.in_ring_n * 4 + g->rates[(size_t)me.rate].bytes / (uint64_t)g->rates[(size_t)me.rate].refs : 0;
     feed_info(me.feed, R, g->g.cap, out);
     const uint64_t tok_b = me.tokens ? (uint64_t)(me.lists_cap + 2) * 4 : 0;      // (an endless group's member: its own token row, as it is)
-    out[5] = (int64_t)(g->bytes / (uint64_t)g->n + tap_b + rate_b + tok_b + me.sc.bytes() + me.al.bytes());      // the member's share of the group's device state; its own input ring, its share of its rate's matrix, its score and alternatives records
+    out[5] = (int64_t)(g->bytes / (uint64_t)g->n + tap_b + rate_b + tok_b + me.sc.bytes() + me.al.bytes() + me.lv.bytes());      // the member's share of the group's device state; its own input ring, its share of its rate's matrix, its score, alternatives and level records
     out[6] = 0; out[7] = (int64_t)me.steps;                      // no engine step; the member's ticks, each one row of an xf_chain step
     return VOX_OK;
 }
 
 static StreamRound group_stream_round(const vox_stream_group* g, int n_r) {
-    StreamRound r{g->d_mem, g->d_order, n_r, g->g.cap, g->ring_layer, g->mel, g->g.left};
+    StreamRound r{g->d_mem, g->d_order, n_r, g->g.cap, g->ring_layer, g->mel, g->g.left}; r.levels = g->n_leveled > 0;      // (slots of members with levels off return at once)
     if (g->endless) { r.rope = g->rope.enc; r.rope_stride = GROUP_ROPE_ROWS * g->m->cfg.reshape_factor; r.rope_mask = r.rope_stride - 1; }      // every position: the member's ring row (group_rope_refill)
     return r;
 }
@@ -4721,10 +4842,12 @@ static int32_t group_lists_grow(vox_stream_group* g, int member, int need_pos) {
         VOXCHK(list_grow((void**)&me.tokens, &tcap, rows + 2, 4, s));
         if (me.sc.dev) VOXCHK(me.sc.grow(rows + 2, s));
         if (me.al.dev) VOXCHK(me.al.grow(rows + 2, s));
+        if (me.lv.dev) VOXCHK(me.lv.grow(rows + 2, s));
         me.lists_cap = rows;
         StreamMember& hm = g->h_mem[member]; hm.tokens = me.tokens;
         if (hm.scores) { hm.scores = me.sc.dev; hm.scores_cap = me.sc.cap; }
         if (hm.alts) { hm.alts = me.al.dev; hm.alts_cap = me.al.cap; }
+        if (hm.levels) { hm.levels = me.lv.dev; hm.levels_cap = me.lv.cap; }
         VOXCHK(group_upload_members(g));      // synchronises
     }
     return VOX_OK;
@@ -4783,7 +4906,7 @@ static int32_t group_drain(vox_stream_group* g, vox_stream_feed* feeds, const Gr
     std::vector<SessionOut> outs;
     for (size_t k = 0; k < call.fs.size(); k++) {
         GroupMember& me = g->mem[call.fs[k].member];
-        outs.push_back(SessionOut{&me.feed, &me.sc, &me.al, g->h_mem[call.fs[k].member].tokens, feeds[k].out_ids, call.fs[k].plan.due, call.peek, peek_scores ? peek_scores[k] : nullptr});
+        outs.push_back(SessionOut{&me.feed, &me.sc, &me.al, &me.lv, g->h_mem[call.fs[k].member].tokens, feeds[k].out_ids, call.fs[k].plan.due, call.peek, peek_scores ? peek_scores[k] : nullptr});
         VOXCHK(outs.back().enqueue(s));
     }
     if (keep) HIPCHK(launch_stream_keep(*keep, 1, s));
@@ -4884,6 +5007,27 @@ extern "C" int32_t vox_stream_group_scores(const vox_stream_group* g, int32_t me
     ARGCHK(g, "null group"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1);
     return g->mem[member].sc.read(g->mem[member].feed.ids_out, first_id, n, out);
 }
+extern "C" int32_t vox_stream_group_set_levels(vox_stream_group* g, int32_t member, int32_t on) {
+    ARGCHK(g, "null group"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1); ARGCHK(on == 0 || on == 1, "on must be 0 or 1");
+    VOXCHK(ctx_bind(g->ctx));
+    LevelState& lv = g->mem[member].lv;
+    if (on) { char whose[24]; snprintf(whose, sizeof whose, "member %d's", member); VOXCHK(lv.alloc(g->endless ? g->mem[member].lists_cap : g->g.max_pos, whose)); }
+    HIPCHK(hipStreamSynchronize(g->ctx->stream));
+    StreamMember& hm = g->h_mem[member]; const StreamMember was = hm;
+    hm.levels = on ? lv.dev : nullptr; hm.levels_cap = on ? lv.cap : 0;
+    const int32_t r = group_upload_members(g);
+    if (r != VOX_OK) { hm = was; return r; }      // a failed upload leaves the host descriptor with the counter: n_leveled gates the round's launch
+    g->n_leveled += (on != 0) - (int)lv.on; lv.on = on != 0;
+    return VOX_OK;
+}
+extern "C" int32_t vox_stream_group_levels(const vox_stream_group* g, int32_t member, int32_t first_id, int32_t n, vox_tick_level* out) {
+    ARGCHK(g, "null group"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1);
+    return g->mem[member].lv.read(g->mem[member].feed.ids_out, first_id, n, out);
+}
+extern "C" int32_t vox_stream_group_quiet(const vox_stream_group* g, int32_t member, float peak_below, int32_t* ticks) {
+    ARGCHK(g, "null group"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1);
+    return g->mem[member].lv.quiet(g->mem[member].feed.ids_out, peak_below, ticks);
+}
 extern "C" int32_t vox_stream_group_set_alternatives(vox_stream_group* g, int32_t member, int32_t k) {
     ARGCHK(g, "null group"); ARGCHK(k >= 0 && k <= VOX_MAX_ALTERNATIVES, "k %d out of range (0..%d)", k, VOX_MAX_ALTERNATIVES);      // (k before the handle is read)
     ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1);
@@ -4934,7 +5078,7 @@ extern "C" int32_t vox_debug_stream_group_tap_fetch(vox_stream_group* g, int32_t
 static SnapSession group_session(vox_stream_group* g, int i) {
     const vox_model_cfg& c = g->m->cfg; GroupMember& me = g->mem[(size_t)i]; const StreamMember& hm = g->h_mem[(size_t)i];
     static thread_local char who[32]; snprintf(who, sizeof who, "member %d", i);
-    SnapSession ss{}; ss.m = g->m; ss.ctx = g->ctx; ss.t_embed = &group_t_embed(g, i); ss.feed = &me.feed; ss.sc = &me.sc; ss.al = &me.al; ss.gain = hm.gain;
+    SnapSession ss{}; ss.m = g->m; ss.ctx = g->ctx; ss.t_embed = &group_t_embed(g, i); ss.feed = &me.feed; ss.sc = &me.sc; ss.al = &me.al; ss.lv = &me.lv; ss.gain = hm.gain;
     ss.tokens = hm.tokens; ss.samples = const_cast<float*>(hm.samples); ss.state = hm.state; ss.h_state = me.h_state; ss.cap = g->g.cap; ss.PC = g->g.PC; ss.max_pos = g->g.max_pos; ss.who = who;
     ss.enc.cache_k = hm.kring; ss.enc.cache_v = hm.vring; ss.enc.layers = c.enc_layers; ss.enc.heads = c.enc_heads; ss.enc.hd = c.enc_head_dim;
     ss.enc.layout = vox::SNAP_RING; ss.enc.cap = g->g.cap; ss.enc.layer_stride = g->ring_layer; ss.enc.head_stride = (size_t)g->g.cap * c.enc_head_dim;

@@ -420,6 +420,7 @@ struct TokenScore { float logprob, margin; int runner_up, id; };      // vox_tok
 static const int VOX_ALTS_MAX = 8;                                     // VOX_MAX_ALTERNATIVES
 struct TokenAlt { int id; float logprob; };
 struct TokenAlts { float entropy; int n; TokenAlt alt[VOX_ALTS_MAX]; };      // vox_token_alts (voxtral_hip.h)
+struct TickLevel { float peak, mean_square; };                         // vox_tick_level (voxtral_hip.h)
 struct StreamMember {
     const float* samples; float gain;   // the session's 16 kHz sample ring; every sample is multiplied by gain before the mel
     int* state;                         // its StreamWord block
@@ -428,6 +429,7 @@ struct StreamMember {
     float* tap; int tap_max;            // group members: [tap_max][vocab] logits rows (null: not armed)
     struct TokenScore* scores; int scores_cap;      // the session's score records, one per id of the utterance (null: scores off, launch_stream_score skips the slot)
     struct TokenAlts* alts; int alts_cap, alts_k;   // its alternatives records, one per id, and its k (null: alternatives off, launch_stream_alts skips the slot)
+    struct TickLevel* levels; int levels_cap;       // its level records, one per id (null: levels off, launch_stream_level skips the slot)
 };
 // front end: for every slot z < n the log-mel frames STRM_FRAME - halo_back .. + n_frames - 1 of the virtually padded signal zeros(left) + gain * samples of session
 // order[z], token-major into out + z * slot_stride ([n_frames][128]: the layout the conv stem's im2col GEMM reads).  Sample i of a session lives at ring[i & ring_mask];
@@ -551,6 +553,22 @@ struct BatchRecordsParams {
     TokenScore* scores; TokenAlts* alts; int k;
 };
 hipError_t launch_batch_records(const BatchRecordsParams& p, int n_rows, hipStream_t s);
+// ---- levels of the audio behind emitted ids (vox_tick_level; DESIGN.md section 8, "Levels"): record k of a session describes the LEVEL_TICK = 2560 samples that are new
+// to the tick that chooses id k -- the window [2560 (k - 1), 2560 k) of the session's own 16 kHz sample index -- each taken as stream_mel_kernel takes it:
+// v = ring[i & ring_mask]; v *= gain (f32), 0 for i < 0 (the silent left pad).  peak = max |v| (exact); mean_square = (sum v * v) / 2560 in f32 by ONE scan order and ONE
+// reduction tree (level_window, vox_kernels.hip): thread t of 256 squares (one rounding each) and adds its samples t, t + 256, .., t + 2304 in that order (10 additions
+// from 0), 6 butterfly levels add the 64 partials of each wave (__shfl_xor, o = 32 .. 1), the four waves' sums are added as (w0 + w1) + (w2 + w3), one division by
+// 2560 -- 18 additions on every path from a sample to the root, so without underflow the result is within (1 + 2^-24)^20 - 1 < 2^-19 relative of the exact sum of the exact squares; a square below 2^-126 rounds on the
+// subnormal grid, which adds at most 2^-149 absolute to the record.  A non-finite sample makes mean_square non-finite; nothing else is promised then.
+// The record is a function of the window's samples and the gain alone: every launch form below runs the one device function.
+// launch_stream_level, in front of the round's mel launch (the state block is the one the round's first tick finds; the samples the two launches read are the same ones):
+// grid (ticks, n); slot z < n works for session order[z], block (t, z) writes mem[order[z]].levels[STRM_POS - first_pos + t] from the window starting at
+// 160 STRM_FRAME - left + 2560 t.  first_pos: the position whose tick chooses id 0 (VOX_PREFIX_TOKENS - 1).  ticks = 1: a tick / a plain round; ticks = b, desc null: a
+// solo burst of b ticks; desc (device; host: its host copy, checked here): a burst round, slot z runs desc->b[z] <= ticks ticks, blocks beyond leave at once.
+// Sessions whose levels pointer is null are skipped; a record index outside 0 .. levels_cap - 1 writes nothing.
+static const int LEVEL_TICK = 2560;
+hipError_t launch_stream_level(const StreamMember* mem, const int* order, int n, int ring_mask, long left, int first_pos, int ticks, const StreamBurstDesc* desc,
+                               const StreamBurstDesc* host, hipStream_t s);
 // ---- the ring keep of a peek (vox_stream_peek, vox_stream_group_peek): around ticks that are taken back.  Slot z < n works for session order[z] on its own area
 // keep + z * slot_stride (floats, a multiple of 4): [STRM_WORDS ints: the state block][K: layers x n_heads x rows x hd][V: the same].
 // restore = 0 (save, in front of the ticks): the state block, and of every (layer, head) of K and V the `rows` ring rows from STRM_HEAD on, modulo cap -- the slots the

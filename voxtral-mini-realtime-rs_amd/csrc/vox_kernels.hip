@@ -5228,6 +5228,55 @@ hipError_t launch_stream_score(const float* logits, int vocab, const StreamMembe
     return hipGetLastError();
 }
 
+// ---- levels (vox_tick_level, vox_kernels.h): the peak and the mean square of the LEVEL_TICK samples from w0 on, each taken as stream_mel_kernel takes it.  256
+// threads.  THE scan order and THE tree, behind every launch form: thread t takes samples t + 256 j, j = 0 .. 9, in that order -- the square rounded once (__fmul_rn: no
+// fused multiply-add, whatever the compiler's contraction setting), added to the thread's sum (from 0: 10 additions); 6 butterfly levels inside each wave (__shfl_xor,
+// o = 32 .. 1: every lane of a wave ends with the same bits, a + b being b + a); the four waves' sums as (w0 + w1) + (w2 + w3); one division by 2560.  18 additions on
+// every path from a sample to the root.  The peak takes the same route with fmaxf, which is exact in any order.  Every thread returns the record.
+__device__ __forceinline__ TickLevel level_window(const float* __restrict__ ring, int ring_mask, float gain, long w0, float* s_sq, float* s_pk) {
+    float pk = 0.0f, sq = 0.0f;
+#pragma unroll
+    for (int j = 0; j < LEVEL_TICK / 256; j++) {
+        const long i = w0 + (long)threadIdx.x + 256 * j;      // index into the stream's samples; below 0: the silent left pad
+        float v = 0.0f;
+        if (i >= 0) { v = ring[i & (long)ring_mask]; v *= gain; }
+        pk = fmaxf(pk, fabsf(v));
+        sq = __fadd_rn(sq, __fmul_rn(v, v));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { pk = fmaxf(pk, __shfl_xor(pk, o)); sq = __fadd_rn(sq, __shfl_xor(sq, o)); }
+    if ((threadIdx.x & 63) == 0) { s_sq[threadIdx.x >> 6] = sq; s_pk[threadIdx.x >> 6] = pk; }
+    __syncthreads();
+    TickLevel r;
+    r.peak = fmaxf(fmaxf(s_pk[0], s_pk[1]), fmaxf(s_pk[2], s_pk[3]));
+    r.mean_square = __fdiv_rn(__fadd_rn(__fadd_rn(s_sq[0], s_sq[1]), __fadd_rn(s_sq[2], s_sq[3])), (float)LEVEL_TICK);
+    return r;
+}
+// the session form, in front of the round's mel launch: block (t, z) writes the record of tick t of the pass for session order[z] -- record STRM_POS - first_pos + t,
+// from the window 2560 t behind the one the state block's STRM_FRAME names (the block as the pass's first tick finds it).  desc: a burst round's descriptor, slot z runs
+// desc->b[z] ticks.  Every early return is the whole block's.  (VOX_NO_PK_F32: two f32 chains per thread; no packed form is wanted on a stream kernel's lanes.)
+__global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_level_kernel(const StreamMember* __restrict__ mem, const int* __restrict__ order, int ring_mask, long left, int first_pos,
+                                                                        const StreamBurstDesc* __restrict__ desc) {
+    __shared__ float s_sq[4], s_pk[4];
+    const int t = blockIdx.x, z = blockIdx.y;
+    if (desc && t >= desc->b[z]) return;
+    const StreamMember& me = mem[order[z]];
+    if (!me.levels) return;
+    const int k = me.state[STRM_POS] - first_pos + t;
+    if (k < 0 || k >= me.levels_cap) return;           // (never: the host sizes the list by the session's position limit)
+    const long w0 = 160L * me.state[STRM_FRAME] - left + (long)LEVEL_TICK * t;
+    const TickLevel r = level_window(me.samples, ring_mask, me.gain, w0, s_sq, s_pk);
+    if (threadIdx.x == 0) me.levels[k] = r;
+}
+hipError_t launch_stream_level(const StreamMember* mem, const int* order, int n, int ring_mask, long left, int first_pos, int ticks, const StreamBurstDesc* desc,
+                               const StreamBurstDesc* host, hipStream_t s) {
+    if (n < 1 || n > 16 || !mem || !order || ticks < 1 || ticks > 16 || left < 0 || first_pos < 0 || ring_mask < LEVEL_TICK - 1 || (ring_mask & (ring_mask + 1)) || (desc != nullptr) != (host != nullptr))
+        return hipErrorInvalidValue;
+    for (int z = 0; host && z < n; z++) if (host->b[z] < 1 || host->b[z] > ticks) return hipErrorInvalidValue;
+    stream_level_kernel<<<dim3(ticks, n), dim3(256), 0, s>>>(mem, order, ring_mask, left, first_pos, desc);
+    return hipGetLastError();
+}
+
 // the ring keep of a peek: slot z = blockIdx.z copies, for session order[z], `rows` ring rows of every (layer, head) of K and V between the ring and the slot's area, and
 // the session's state block.  The ring rows start at STRM_HEAD -- the live block's at save, the SAVED block's at restore (the live one has moved on by then) -- and wrap
 // at cap.  Nobody writes what another thread reads: the save leaves the live block alone, the restore the saved one.

@@ -670,6 +670,45 @@ def records_rows(ctx, logits, k=0, device_ptr=None, shape=None):
     return sc, al
 
 
+LEVEL_DTYPE = np.dtype([("peak", "<f4"), ("mean_square", "<f4")])      # vox_tick_level
+
+
+def level_window(k: int):
+    """vox_level_window (host arithmetic): the window of level record k as (first, end) in the utterance's own 16 kHz sample index -- [2560 (k - 1), 2560 k), the 2560
+    samples new to the tick that chose id k; record 0 covers the silent left pad alone."""
+    a = C.c_int64(); b = C.c_int64()
+    check(lib().vox_level_window(int(k), C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
+def level_db(x, power: bool = False):
+    """A level record's field in dB relative to full scale: 20 log10(peak), or with power=True 10 log10(mean_square) (the RMS level); -inf at 0, NaN stays NaN.
+    Scalars or arrays."""
+    v = np.asarray(x, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out = (10.0 if power else 20.0) * np.log10(v)
+    return float(out) if out.ndim == 0 else out
+
+
+def _db_peak(db) -> float:
+    """The f32 peak threshold of a dBFS figure (what quiet_ticks compares with)."""
+    p = float(np.float32(10.0 ** (float(db) / 20.0)))
+    if not (np.isfinite(p) and p > 0.0):
+        raise ValueError(f"threshold {db!r} dB is not a finite positive peak in f32")
+    return p
+
+
+def quiet_ticks(levels, db: float = -50.0) -> int:
+    """The end-of-speech hint as a pure function (vox_stream_quiet's rule on a list of records): the number of trailing records whose peak < 10^(db / 20); a NaN
+    record ends the run."""
+    thr = np.float32(_db_peak(db)); n = 0
+    for pk in np.asarray(levels["peak"], dtype=np.float32)[::-1]:
+        if not pk < thr:
+            break
+        n += 1
+    return n
+
+
 def stream_id_due(k: int, sample_rate: int = 16000) -> int:
     """The smallest number of pushed samples (at `sample_rate`) at which a live session hands out id k of its utterance: 2560 k + 40 at 16 kHz, by the schedule; at
     another rate the smallest n with stream_schedule_rate(n)[1] > k, found by bisection (the schedule is monotone).  This is when the session KNOWS the id, the only time
@@ -692,7 +731,7 @@ def stream_id_due(k: int, sample_rate: int = 16000) -> int:
     return hi
 
 
-def words(ids, scores, tokenizer, sample_rate: int = 16000, alternatives=None):
+def words(ids, scores, tokenizer, sample_rate: int = 16000, alternatives=None, levels=None):
     """The ids a live session handed out (ids[k] = id k of the utterance) and their records (LiveStream.scores()) as words.  Text ids are those >= 1000 (control and
     streaming ids are dropped); a word begins at the first text id and at every text id whose bytes begin with ASCII whitespace, so a character split over two ids stays
     in one word.  -> a list of {text (the word's bytes as lossy UTF-8, its leading whitespace included: the texts joined are the decoded transcript), first_id, last_id
@@ -700,7 +739,9 @@ def words(ids, scores, tokenizer, sample_rate: int = 16000, alternatives=None):
     min_margin (the smallest margin among them)}.
     alternatives (LiveStream.alternatives(), one record per id): every word also gets entropy (the largest over its ids; NaN when one of them has none) and weakest =
     {k: the index of its smallest-margin id (the first of them), alternatives: that id's list as [{id, text, logprob}]}; text is the tokenizer's bytes for the id as
-    lossy UTF-8, "" for control ids and ids past the vocabulary."""
+    lossy UTF-8, "" for control ids and ids past the vocabulary.
+    levels (LiveStream.levels(), one record per id): every word also gets peak_db (level_db of the largest peak over its ids) and rms_db (level_db of the mean of its
+    ids' mean_square): what the model had just heard while it chose the word's ids, not where the word was spoken; NaN when one of the ids has no record."""
     from .tokenizer import TEXT_TOKEN_OFFSET
 
     def id_text(t):
@@ -732,6 +773,9 @@ def words(ids, scores, tokenizer, sample_rate: int = 16000, alternatives=None):
             res[-1]["entropy"] = float("nan") if any(e != e for e in ent) else max(ent)
             res[-1]["weakest"] = {"k": w["weakest"], "alternatives": [{"id": int(a["id"]), "text": id_text(int(a["id"])), "logprob": float(a["logprob"])}
                                                                       for a in rec["alt"][:int(rec["n"])]]}
+        if levels is not None:
+            pk = np.asarray([levels["peak"][k] for k in w["ks"]], dtype=np.float64); ms = np.asarray([levels["mean_square"][k] for k in w["ks"]], dtype=np.float64)
+            res[-1]["peak_db"] = level_db(pk.max() if not np.isnan(pk).any() else np.nan); res[-1]["rms_db"] = level_db(ms.mean(), power=True)
     return res
 
 
@@ -887,6 +931,25 @@ class LiveStream:
         out = np.zeros(max(n, 0), dtype=ALTS_DTYPE)
         check(lib().vox_stream_alternatives(self.h, int(first), n, _ptr(out) if out.size else None))
         return out
+
+    def set_levels(self, on: bool = True):
+        """vox_stream_set_levels: from the next push / finish on, every id comes with the level of the 160 ms of audio new to its tick (levels()); survives reset()."""
+        check(lib().vox_stream_set_levels(self.h, 1 if on else 0))
+
+    def levels(self, first: int = 0, n=None) -> np.ndarray:
+        """vox_stream_levels: the records of ids [first, first + n) of the current utterance (n None: up to the last id handed out) as a structured array (peak,
+        mean_square) of the window level_window(k), taken on gain * sample as the front end reads it; an id handed out while levels were off has (NaN, NaN).  Refused
+        while levels are off.  Reads host memory only."""
+        n = self.info()["ids"] - int(first) if n is None else int(n)
+        out = np.zeros(max(n, 0), dtype=LEVEL_DTYPE)
+        check(lib().vox_stream_levels(self.h, int(first), n, _ptr(out) if out.size else None))
+        return out
+
+    def quiet_ticks(self, db: float = -50.0) -> int:
+        """vox_stream_quiet, the end-of-speech hint: how many of the last ids handed out had a window whose peak lies below `db` dBFS (of the gained samples); times
+        160 ms: the quiet time as of the last id.  A NaN record ends the run.  Reads host memory only."""
+        t = C.c_int32(); check(lib().vox_stream_quiet(self.h, _db_peak(db), C.byref(t)))
+        return t.value
 
     def peeked_alternatives(self) -> np.ndarray:
         """vox_stream_peeked_alternatives: the records of the ids the last peek() returned; empty once a push / finish / peek / reset has followed it."""
@@ -1151,6 +1214,22 @@ class LiveStreamGroup:
         out = np.zeros(max(n, 0), dtype=ALTS_DTYPE)
         check(lib().vox_stream_group_alternatives(self.h, int(member), int(first), n, _ptr(out) if out.size else None))
         return out
+
+    def set_levels(self, member, on: bool = True):
+        """vox_stream_group_set_levels: LiveStream.set_levels for one member; survives the member's resets."""
+        check(lib().vox_stream_group_set_levels(self.h, int(member), 1 if on else 0))
+
+    def levels(self, member, first: int = 0, n=None) -> np.ndarray:
+        """vox_stream_group_levels: LiveStream.levels for one member -- the bits a solo stream fed the same samples at the same gain has."""
+        n = self.info(member)["ids"] - int(first) if n is None else int(n)
+        out = np.zeros(max(n, 0), dtype=LEVEL_DTYPE)
+        check(lib().vox_stream_group_levels(self.h, int(member), int(first), n, _ptr(out) if out.size else None))
+        return out
+
+    def quiet_ticks(self, member, db: float = -50.0) -> int:
+        """vox_stream_group_quiet: LiveStream.quiet_ticks for one member."""
+        t = C.c_int32(); check(lib().vox_stream_group_quiet(self.h, int(member), _db_peak(db), C.byref(t)))
+        return t.value
 
     def peeked_alternatives(self, member) -> np.ndarray:
         """vox_stream_group_peeked_alternatives: LiveStream.peeked_alternatives for one member."""
