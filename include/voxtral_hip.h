@@ -1079,6 +1079,57 @@ typedef struct {
 } vox_resid_xf_desc;
 int32_t vox_debug_resid_xf(vox_ctx* ctx, const vox_q4* w, const vox_resid_xf_desc* desc, const float* x, const float* resid, const float* xf_w, const float* scales,
                            const int32_t* order_or_null, float* out, uint16_t* xf_out, float* ssq_out);
+/* debug (tests): ONE operator of the batched XF decode step on caller data, no model -- the launch the decode chain makes for q|k|v (ROPE_KV), wo / w2 (RESID_XF),
+ * w1|w3 (SWIGLU_XF) or the lm_head (STORE), through the chain's own parameter fill.  w: a tile-ordered Q4 tensor [N][K], K % 128 == 0.  Host pointers throughout.
+ *   mode VOX_XF_MODE_STEP: groups = 1 runs launch_q4_gemm on one XF group of M rows (1..16); groups = 2..4 runs the wide step (launch_q4_wide), M = 16 * groups.
+ *     x [16 * groups][K] f32 rows -> the groups' XF planes (launch_xf_rows; group g's planes xf_in_gs 16-bit elements after group 0's).
+ *     n_part > 0: the fused RMSNorm, ssq_part [groups][n_part][16] (on the device ssq_part_gs floats apart); ROPE_KV needs it, RESID_XF takes none, the wide STORE /
+ *     SWIGLU_XF need it.  bias: STORE with one group only.
+ *     STORE: out [16 * groups][N].  ROPE_KV (N = n_q + 2 n_kv hd): out [16 * groups][N], columns < n_q written; kc / vc [kv_slices][n_kv][kv_rows][hd], f32 or (kv_bf16,
+ *       the paged forms) 16-bit; kv_form CONTIG: row r -> slice r at row pos[r]; SLOTS: slice kv_row[r]; PAGED: page kv_row[r], row kv_pos[r] inside it; PAGED_RING:
+ *       PAGED with the RoPE row read from a ring rope_cos [rope_rows / (rope_mask + 1)][rope_mask + 1][hd] (cos | sin), member rope_member[r], row pos[r] & rope_mask.
+ *       Every other form reads rope_cos / rope_sin [rope_rows][hd / 2] at pos[r].  One group: CONTIG .. PAGED_RING; the wide step: CONTIG and SLOTS.
+ *     SWIGLU_XF (N % 256 == 0): xf_out = the XF planes of N / 2 columns.  RESID_XF (N % 128 == 0): out = x W^T + resid [16 * groups][N], xf_out the planes of
+ *       out * xf_w * xf_w2 (xf_w2 may be null), ssq_out [groups][N / 16][16].  Group g's planes xf_out_gs 16-bit elements, its sums ssq_out_gs floats after group 0's.
+ *     A group stride of 0 means packed.  out, kc, vc, xf_out and ssq_out are uploaded as they come and copied back whole: what the operator does not write keeps
+ *     the caller's contents.  Every index (pos, kv_row, kv_pos, rope_member) is checked against the buffers' sizes.
+ *     The plan that ran comes back in the descriptor: plan_ntw (n-tiles per wave); one group: plan_ks (split-K waves), plan_steps (K steps per wave),
+ *     plan_straight (a straight-line instantiation, else the loop); wide: plan_ks = K slices, plan_steps = K steps per slice.
+ *   mode VOX_XF_MODE_WIDE_ROWS: the decoder prefill's 17..48-row form of the same GEMM -- x [M][K] -> ceil(M / 16) XF tiles (launch_xf_rows), launch_q4_skinny_mt2_planes
+ *     (q4_wide_kernel storing row-major K-slice planes [slice][M][N]; refused where the wide plan does not take the weight), then the finishing kernel of `epi`:
+ *     ROPE_KV launch_splitk_finish_rope_kv -- one sequence, row m at position pos_off + m: out [16 * ceil(M / 16)][N] (rows < M, columns < n_q written), kc / vc
+ *       [n_kv][kv_rows][hd] f32 (kv_slices = 1), rope_cos / rope_sin [rope_rows][hd / 2];
+ *     SWIGLU_XF launch_splitk_finish_swiglu_xf (optional bias [N]): xf_out = ceil(M / 16) XF tiles of N / 2 columns (rows >= M of the last tile untouched);
+ *     RESID_XF launch_splitk_finish_resid: out [16 * ceil(M / 16)][N] holds the residual rows on entry and residual + x W^T on return (rows >= M untouched).
+ *     No fused norm (n_part 0), no group strides.  plan_ntw / plan_ks (K slices) / plan_steps come back as for the wide step.
+ *   mode VOX_XF_MODE_ROWS: launch_q4_gemm's EPI_ROPE_ROWS (the encoder's q|k|v) on f32 rows x [M][K]: out [M][N], interleaved-pair RoPE on columns < n_q at row m's
+ *     position -- pos[m], or m % rope_seq_rows, or m; rope_cos / rope_sin [rope_rows][hd / 2].  fused_rope: the RoPE ran in the GEMM's epilogue. */
+#define VOX_XF_EPI_STORE 0
+#define VOX_XF_EPI_ROPE_KV 1
+#define VOX_XF_EPI_SWIGLU_XF 2
+#define VOX_XF_EPI_RESID_XF 3
+#define VOX_XF_KV_CONTIG 0
+#define VOX_XF_KV_SLOTS 1
+#define VOX_XF_KV_PAGED 2
+#define VOX_XF_KV_PAGED_RING 3
+#define VOX_XF_MODE_STEP 0
+#define VOX_XF_MODE_ROWS 1
+#define VOX_XF_MODE_WIDE_ROWS 2
+typedef struct {
+    int32_t mode, groups, M, epi;
+    int32_t n_part; float norm_eps; int32_t hd, n_q;
+    int32_t n_kv, kv_form, kv_bf16, kv_slices;
+    int32_t kv_rows, rope_rows, rope_mask, rope_seq_rows;
+    int32_t xf_in_gs, xf_out_gs, ssq_part_gs, ssq_out_gs;
+    int32_t plan_ntw, plan_ks, plan_steps, plan_straight;      /* out */
+    int32_t fused_rope /* out */, pos_off /* WIDE_ROWS ROPE_KV */, reserved[2] /* 0 */;
+} vox_xf_op_desc;
+typedef struct {
+    const float* x; const float* ssq_part; const float* bias; const float* resid; const float* xf_w; const float* xf_w2; const float* rope_cos; const float* rope_sin;
+    const int32_t* pos; const int32_t* kv_row; const int32_t* kv_pos; const int32_t* rope_member;
+    float* out; void* kc; void* vc; uint16_t* xf_out; float* ssq_out;
+} vox_xf_op_bufs;
+int32_t vox_debug_xf_op(vox_ctx* ctx, const vox_q4* w, vox_xf_op_desc* desc, const vox_xf_op_bufs* bufs);
 /* The live sessions' feed planner on its own (tests): host arithmetic only -- no context, no device, no model.  A fresh session fed at sample_rate (4 encoder rows per
  * position, the Voxtral left pad, no position limit to speak of) takes the calls (n_samples[c], finish[c] 0 / 1) exactly as vox_stream_push / _finish and a group's advance
  * plan and pass them, every due tick taken as run; finish[c] = 2 is a peek (n_samples[c] must be 0): planned as a finish, its one pass emitted, the session as it was.  One row of five words per pass: call index, input samples appended, 16 kHz samples that entered the 16 kHz ring (a

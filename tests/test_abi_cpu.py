@@ -377,3 +377,30 @@ def test_every_source_in_csrc_is_built(pkg):
     assert sorted(n for n in names if n.endswith((".cpp", ".hip"))) == sorted(build.SOURCES)
     assert len(set(build.SOURCES)) == len(build.SOURCES) and set(build.HOST_SOURCES) <= set(build.SOURCES)
     assert sorted(n for n in names if n.endswith(".h")) == sorted(h for h in build.HEADERS if os.sep not in h and "/" not in h)
+
+
+def test_xf_op_hook_layout_and_refusals(pkg):
+    """vox_debug_xf_op: the descriptor and buffer block have the header's layout (the library's static_assert holds the same sizes), and every bad argument is refused
+    with VOX_ERR_INVALID before a device is touched -- this machine may have none, and the weight pointer is never a device tensor here."""
+    import xf_op_lib as X
+    hdr = open(os.path.join(ROOT, "include", "voxtral_hip.h")).read()
+    body = re.search(r"typedef struct \{([^}]*)\}\s*vox_xf_op_desc;", hdr).group(1)
+    names = re.findall(r"\b([A-Za-z_][A-Za-z_0-9]*)(?:\[2\])?\s*[,;]", re.sub(r"/\*.*?\*/", "", body))
+    assert names == [f[0] for f in X.XfOpDesc._fields_] and C.sizeof(X.XfOpDesc) == 112 and X.XfOpDesc.norm_eps.offset == 20 and X.XfOpDesc.plan_ntw.offset == 80
+    bufs = re.search(r"typedef struct \{([^}]*)\}\s*vox_xf_op_bufs;", hdr).group(1)
+    assert re.findall(r"\*\s*([a-z_0-9]+);", bufs) == list(X.BUF_NAMES) and C.sizeof(X.XfOpBufs) == 17 * C.sizeof(C.c_void_p)
+    for name, val in (("VOX_XF_EPI_STORE", X.EPI_STORE), ("VOX_XF_EPI_ROPE_KV", X.EPI_ROPE_KV), ("VOX_XF_EPI_SWIGLU_XF", X.EPI_SWIGLU_XF), ("VOX_XF_EPI_RESID_XF", X.EPI_RESID_XF),
+                      ("VOX_XF_KV_CONTIG", X.KV_CONTIG), ("VOX_XF_KV_SLOTS", X.KV_SLOTS), ("VOX_XF_KV_PAGED", X.KV_PAGED), ("VOX_XF_KV_PAGED_RING", X.KV_PAGED_RING),
+                      ("VOX_XF_MODE_STEP", X.MODE_STEP), ("VOX_XF_MODE_ROWS", X.MODE_ROWS), ("VOX_XF_MODE_WIDE_ROWS", X.MODE_WIDE_ROWS)):
+        assert re.search(rf"#define {name} {val}\b", hdr), name
+    L = pkg.lib(); err = lambda: L.vox_last_error().decode()
+    d = X.XfOpDesc(groups=1, M=1); b = X.XfOpBufs(); dummy = C.c_void_p(1)
+    assert L.vox_debug_xf_op(None, dummy, C.byref(d), C.byref(b)) == 1 and "null argument" in err()
+    assert L.vox_debug_xf_op(dummy, None, C.byref(d), C.byref(b)) == 1 and "null argument" in err()
+    assert L.vox_debug_xf_op(dummy, dummy, None, C.byref(b)) == 1 and L.vox_debug_xf_op(dummy, dummy, C.byref(d), None) == 1
+    d.reserved[1] = 7
+    # a weight handle is read (format, K) before the rest: a host-made stand-in of the handle's head -- ctx pointer, then the Q4W words -- with no tile copy is refused
+    fake = (C.c_uint64 * 16)()
+    assert L.vox_debug_xf_op(dummy, C.byref(fake), C.byref(d), C.byref(b)) == 1 and "reserved" in err()
+    d.reserved[1] = 0
+    assert L.vox_debug_xf_op(dummy, C.byref(fake), C.byref(d), C.byref(b)) == 1 and "tile-ordered" in err()

@@ -75,3 +75,53 @@ def test_linear_ref64_reproduces_reference_python_component_vectors():
     scale, _, _, _ = linear_ref64(wa2, wa2.shape[0], wa2.shape[1], hid.astype(np.float32))
     assert rel_err(scale, g["ada_rms_norm_scale"][0]) < 2e-4
     assert rel_err(g["ada_rms_norm_input"][0] * (1.0 + scale), g["ada_rms_norm_output"][0]) < 2e-4
+
+
+# ---- the XF-step pieces of linear_ref (tests/test_gpu_xf_ops.py)
+def test_xf_planes_round_trip_and_the_layout_comments_slots():
+    """xf_pack / xf_unpack restate xf_store4: a one-hot row sits at the slot the layout comment names -- lane 16 g + row of uint4 [q][j], K-slot order
+    {4g, 4g+2, 16+4g, 16+4g+2, 4g+1, 4g+3, 16+4g+1, 16+4g+3} -- every slot is taken exactly once, and hi + lo gives the row back to 2^-17 |x| (bf16-exact values: exactly)."""
+    import linear_ref as R
+    K = 256
+    order = [0, 2, 16, 18, 1, 3, 17, 19]
+    for row, k in ((0, 0), (3, 2), (15, 255), (7, 128 + 32 * 2 + 4 * 3 + 16 + 1), (9, 37)):
+        x = np.zeros((16, K), np.float32); x[row, k] = 1.5
+        p = R.xf_pack(x)
+        q, j, e = k // 128, (k // 32) % 4, k % 32
+        g = (e % 16) // 4
+        slot = order.index(e - 4 * g)
+        want = (((q * 4 + j) * 64 + 16 * g + row) * 8) + slot
+        assert np.flatnonzero(p).tolist() == [want] and p[want] == 0x3FC0, (row, k)
+    idx = R.xf_index(np.arange(16)[:, None], np.arange(K)[None, :])
+    assert sorted(idx.ravel().tolist()) == list(range(K * 16))
+    rng = np.random.default_rng(3)
+    x = (rng.standard_normal((11, K)) * 10.0 ** rng.integers(-3, 4, (11, 1))).astype(np.float32)
+    val, hi, lo = R.xf_unpack(R.xf_pack(x), K)
+    assert (np.abs(val[:11] - x) <= R.XF_SPLIT * np.abs(x)).all() and not val[11:].any() and (lo[:11] != 0).any()
+    xb = R.bf16_f32(R.bf16_rne(x))
+    assert (R.xf_unpack(R.xf_pack(xb), K)[0][:11] == xb).all()
+    assert R.bf16_rne(np.array([1.0, 1.00390625, 1.01171875, -2.5], np.float32)).tolist() == [0x3F80, 0x3F80, 0x3F82, 0xC020]      # ties to even, both ways
+
+
+def test_xf_step_reference_pieces(pkg, orc):
+    """The folded norm's factor, interleaved-pair RoPE (against the oracle's rope on f32), the bounds' shapes, and the chunked LinearRef against the whole one."""
+    import linear_ref as R
+    rng = np.random.default_rng(9)
+    part = rng.random((7, 16)).astype(np.float32)
+    r = R.rstd64(part, 256, 1e-5)
+    assert r.shape == (16,) and np.allclose(r, 1.0 / np.sqrt(part.astype(np.float64).sum(0) / 256 + 1e-5), rtol=1e-15)
+    pre = rng.standard_normal((3, 8)); c = np.cos(rng.random((3, 4))); s = np.sin(rng.random((3, 4)))
+    out = R.rope64(pre, c, s)
+    for i in range(4):
+        assert np.allclose(out[:, 2 * i], pre[:, 2 * i] * c[:, i] - pre[:, 2 * i + 1] * s[:, i]) and np.allclose(out[:, 2 * i + 1], pre[:, 2 * i + 1] * c[:, i] + pre[:, 2 * i] * s[:, i])
+    b = R.carry_bound(pre, np.full((3, 8), 1e-3), R.EPI_ROPE, cos=c, sin=s)
+    assert b.shape == (3, 8) and (b >= 1e-3 * (np.abs(c) + np.abs(s)).repeat(2, axis=1) * 0.999).all()
+    # a perturbation of `pre` inside the bound moves the result by no more than the carried bound
+    d = 1e-3 * rng.uniform(-1, 1, (3, 8))
+    assert (np.abs(R.rope64(pre + d, c, s) - out) <= b).all()
+    assert (R.norm_bound(pre, np.full((3, 8), 1e-3), np.array([2.0, 3.0, 4.0]), 5) >= 1e-3 * np.array([2.0, 3.0, 4.0])[:, None]).all()
+    N, K = 96, 128
+    raw = pkg.synth.synth_q4_blocks(rng, N * K, 0.04)
+    x = rng.standard_normal((5, K)).astype(np.float32)
+    whole, chunked = R.LinearRef(raw, N, K)(x), R.LinearRef(raw, N, K, chunk_rows=40)(x)
+    assert np.array_equal(whole[1], chunked[1]) and np.array_equal(whole[3], chunked[3])

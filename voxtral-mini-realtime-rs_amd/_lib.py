@@ -269,6 +269,8 @@ SIGNATURES = {
     "vox_stream_group_t_embed": (i32, [vp, i32, vp, i32]),
     # (ctx, w, vox_resid_xf_desc, x, resid, xf_w, scales, order or null, out, xf_out, ssq_out): ONE launch of the wo GEMM's EPI_RESID_XF epilogue
     "vox_debug_resid_xf": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    # (ctx, w, vox_xf_op_desc, vox_xf_op_bufs): ONE operator of the batched XF decode step (one group or the wide step), or the encoder's RoPE rows
+    "vox_debug_xf_op": (i32, [vp, vp, vp, vp]),
     # levels: (stream, on); (stream, first_id, n, out); (stream, peak_below, ticks); the same with a member; (k, first, end);
     # (ctx, n_members, rings, ring_n, gains, pos, frame, order, n_slots, ticks, burst_b or null, list_len, out): ONE launch of the level kernel
     "vox_stream_set_levels": (i32, [vp, i32]),

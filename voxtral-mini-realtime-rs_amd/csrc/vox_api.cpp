@@ -1548,13 +1548,9 @@ static int32_t xf_chain(const vox_model* m, const XfBufs& b, int g0i, int ng, in
     float* hg = b.h + (size_t)r0 * D; float* qg = b.qkv + (size_t)r0 * W; const int* pg = b.pos + r0; const int* rg = b.kv_row ? b.kv_row + r0 : nullptr;
     const size_t row0 = b.kv_row ? 0 : (size_t)r0 * b.seq_stride;
     auto gemm = [&](GemmParams g, const Q4W& w, const uint16_t* xin, int K, int epi) -> hipError_t {      // g: the operator's epilogue fields
-        g.w = w; g.xf = (const uint4*)xin; g.M = M; if (mtw || epi != EPI_RESID_XF) g.norm_eps = c.norm_eps;
-        if (!mtw) return launch_q4_gemm(g, epi, sg);
-        g.wide_mt = mtw; g.xf_gstride = (long)(xf_bytes(K) / 16); g.kz_scratch_bytes = b.planes_bytes;
-        g.kz_scratch = reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(b.planes) + (size_t)chain * b.planes_bytes);
-        if (g.ssq_part) g.ssq_part_gstride = b.ssq_gs;
-        if (epi == EPI_RESID_XF) { g.xf_out_gstride = b.xf1_gs; g.ssq_out_gstride = b.ssq_gs; } else if (epi == EPI_SWIGLU_XF) g.xf_out_gstride = b.xf3_gs;
-        return launch_q4_wide(g, epi, sg);
+        xf_step_bind(g, w, xin, M, epi, c.norm_eps, mtw, reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(b.planes) + (size_t)chain * b.planes_bytes), b.planes_bytes,
+                     (long)(xf_bytes(K) / 2), epi == EPI_SWIGLU_XF ? b.xf3_gs : b.xf1_gs, b.ssq_gs, b.ssq_gs);
+        return xf_step_launch(g, epi, sg);
     };
     for (int l = 0; l < c.dec_layers; l++) {
         const DecLayer& L = m->dec[l];
@@ -1562,10 +1558,9 @@ static int32_t xf_chain(const vox_model* m, const XfBufs& b, int g0i, int ng, in
         if (b.kv_bf16) {      // (a paged pool: row0 is 0) the layer's pages, in 16-bit elements
             kl = reinterpret_cast<float*>(reinterpret_cast<uint16_t*>(b.k) + (size_t)l * b.layer_stride); vl = reinterpret_cast<float*>(reinterpret_cast<uint16_t*>(b.v) + (size_t)l * b.layer_stride);
         }
-        { GemmParams g{}; g.out = qg; g.out_stride = W; g.ssq_part = ssq; g.n_part = l == 0 ? 1 : parts_D; g.pos = pg; g.rope_cos = m->dec_cos; g.rope_sin = m->dec_sin;
-          g.hd = hd; g.n_q = QD; g.n_kv = KV; g.kc = kl; g.vc = vl; g.kv_seq_stride = (long)b.seq_stride; g.kv_head_stride = max_seq * hd; g.kv_row = rg;
-          if (b.page_tab) { g.kv_seq_stride = b.page_floats; g.kv_head_stride = (hd << b.page_shift); g.kv_row = b.kv_page + r0; g.kv_pos = b.kv_in + r0; g.kv_bf16 = b.kv_bf16; }
-          if (b.page_tab && b.rope_ring) { g.rope_cos = b.rope_ring; g.rope_sin = b.rope_ring + hd / 2; g.rope_member = rg; g.rope_mask = b.rope_mask; }
+        { GemmParams g{}; xf_fill_rope_kv(g, qg, W, ssq, l == 0 ? 1 : parts_D, pg, m->dec_cos, m->dec_sin, hd, QD, KV, kl, vl, (long)b.seq_stride, max_seq, rg);
+          if (b.page_tab) xf_fill_rope_kv_paged(g, b.page_floats, 1 << b.page_shift, b.kv_page + r0, b.kv_in + r0, b.kv_bf16);
+          if (b.page_tab && b.rope_ring) xf_fill_rope_ring(g, b.rope_ring, rg, b.rope_mask);
           HIPCHK(gemm(g, L.wqkv.w, xf1, D, EPI_ROPE_KV)); }
         AttnParams ap{}; ap.q = qg; ap.k = kl; ap.v = vl; ap.kv_row_stride = hd; ap.kv_head_stride = max_seq * hd; ap.n_heads = H; ap.n_kv_heads = KV;
         ap.offset = 0; ap.window = c.dec_window; ap.pos_ptr = pg; ap.M = 1; ap.pos_per_seq = 1; ap.q_seq_stride = W; ap.out_seq_stride = QD; ap.kv_seq_stride = (long)b.seq_stride;
@@ -1577,14 +1572,13 @@ static int32_t xf_chain(const vox_model* m, const XfBufs& b, int g0i, int ng, in
             HIPCHK(launch_attn_decode_paged(ap, hd, sg, M));
         } else
         HIPCHK(launch_attn_decode(ap, hd, max_seq, sg, M));
-        { GemmParams g{}; g.out = hg; g.out_stride = D; g.resid = hg; g.resid_stride = D; g.xf_out = xf1; g.xf_w = L.ffn_norm; g.xf_w2 = L.ada_mul; g.ssq_out = ssq;
+        { GemmParams g{}; xf_fill_resid_xf(g, hg, hg, D, xf1, L.ffn_norm, L.ada_mul, ssq);
           if (b.ada_rows) { g.xf_w2 = b.ada_rows + (size_t)l * D; g.xf_w2_row = b.ada_order; g.xf_w2_stride = b.ada_stride; }      // every row its member's scales
           HIPCHK(gemm(g, L.wo.w, xf2, QD, EPI_RESID_XF)); }
-        { GemmParams g{}; g.out = (float*)xf3; g.out_stride = F; g.ssq_part = ssq; g.n_part = parts_D; HIPCHK(gemm(g, L.w13.w, xf1, D, EPI_SWIGLU_XF)); }
-        { GemmParams g{}; g.out = hg; g.out_stride = D; g.resid = hg; g.resid_stride = D; g.xf_out = xf1; g.ssq_out = ssq;
-          g.xf_w = l + 1 < c.dec_layers ? m->dec[l + 1].attn_norm : m->dec_norm; g.xf_w2 = nullptr; HIPCHK(gemm(g, L.w2.w, xf3, F, EPI_RESID_XF)); }
+        { GemmParams g{}; xf_fill_swiglu_xf(g, xf3, F, ssq, parts_D); HIPCHK(gemm(g, L.w13.w, xf1, D, EPI_SWIGLU_XF)); }
+        { GemmParams g{}; xf_fill_resid_xf(g, hg, hg, D, xf1, l + 1 < c.dec_layers ? m->dec[l + 1].attn_norm : m->dec_norm, nullptr, ssq); HIPCHK(gemm(g, L.w2.w, xf3, F, EPI_RESID_XF)); }
     }
-    { GemmParams g{}; g.out = b.logits + (size_t)g0i * 16 * V; g.out_stride = V; g.ssq_part = ssq; g.n_part = parts_D; HIPCHK(gemm(g, m->tok.w, xf1, D, EPI_STORE)); }
+    { GemmParams g{}; xf_fill_store(g, b.logits + (size_t)g0i * 16 * V, V, ssq, parts_D); HIPCHK(gemm(g, m->tok.w, xf1, D, EPI_STORE)); }
     return VOX_OK;
 }
 // The batched decode-layer engine's parameters for group gi (n_rows of its 16): layer table `tab`, edge-buffer block `blk` (a block belongs to a launch, not to a

@@ -126,6 +126,47 @@ hipError_t launch_q4_gemm(const GemmParams& p, int epi, hipStream_t s, bool* fus
 hipError_t launch_dense2_gemm(const GemmParams& p, int epi, hipStream_t s);
 hipError_t launch_transpose(const float* in, int R, int C, float* out, hipStream_t s);   // [R][C] -> [C][R]
 int q4_skinny_resid_xf_parts(int N);   // number of [16]-row partial sums of squares an EPI_RESID_XF launch writes to ssq_out
+// the plan of one <= 16-row launch (q4_skinny_kernel): n-tiles per wave, split-K waves, tile-ordered weights, K steps per wave (the last waves may own fewer),
+// `even`: the steps of EVERY wave when K / 128 divides by ks (else 0), `straight`: a straight-line instantiation runs (XF input only), else the loop
+struct SkinnyPlan { int ntw, ks, tiled, steps, even, straight; };
+int q4_skinny_epi(int epi, bool kv_pos, bool kv_bf16, bool rope_member, bool xf_w2_row);      // the epilogue instantiation of a <= 16-row launch: EPI_ROPE_KV's paged / ring / bf16 forms, EPI_RESID_XF's per-row form
+void q4_skinny_plan(const Q4W& w, int epi_inst, bool xf, bool pro, SkinnyPlan* pl);      // epi_inst: q4_skinny_epi's; xf: XF input; pro: the fused norm
+// The epilogue fields of the batched XF decode step's operators: the decode chain and the tests' operator hook fill them through these alone.
+//  q|k|v: f32 rows out (columns < n_q), the folded norm's partial sums, positions, the RoPE table, the cache (slice stride, head stride; kv_row: slots or null)
+inline void xf_fill_rope_kv(GemmParams& g, float* out, int out_stride, const float* ssq_part, int n_part, const int* pos, const float* cos_t, const float* sin_t,
+                            int hd, int n_q, int n_kv, float* kc, float* vc, long kv_seq_stride, int kv_rows, const int* kv_row) {
+    g.out = out; g.out_stride = out_stride; g.ssq_part = ssq_part; g.n_part = n_part; g.pos = pos; g.rope_cos = cos_t; g.rope_sin = sin_t;
+    g.hd = hd; g.n_q = n_q; g.n_kv = n_kv; g.kc = kc; g.vc = vc; g.kv_seq_stride = kv_seq_stride; g.kv_head_stride = kv_rows * hd; g.kv_row = kv_row;
+}
+//  ... on a paged cache: the page's elements, rows per page = 1 << page_shift, the rows' physical pages and rows inside them; kv_bf16: 16-bit pools
+inline void xf_fill_rope_kv_paged(GemmParams& g, long page_elems, int page_rows, const int* kv_page, const int* kv_in, int kv_bf16) {
+    g.kv_seq_stride = page_elems; g.kv_head_stride = g.hd * page_rows; g.kv_row = kv_page; g.kv_pos = kv_in; g.kv_bf16 = kv_bf16;
+}
+//  ... with the RoPE rows in a member-strided ring [members][rope_mask + 1][cos | sin]
+inline void xf_fill_rope_ring(GemmParams& g, const float* ring, const int* member, int rope_mask) {
+    g.rope_cos = ring; g.rope_sin = ring + g.hd / 2; g.rope_member = member; g.rope_mask = rope_mask;
+}
+//  wo / w2: out = x W^T + resid as f32 rows, the XF planes of out * xf_w * xf_w2 (xf_w2 may be null), the per-tile sums of squares
+inline void xf_fill_resid_xf(GemmParams& g, float* out, const float* resid, int stride, uint16_t* xf_out, const float* xf_w, const float* xf_w2, float* ssq_out) {
+    g.out = out; g.out_stride = stride; g.resid = resid; g.resid_stride = stride; g.xf_out = xf_out; g.xf_w = xf_w; g.xf_w2 = xf_w2; g.ssq_out = ssq_out;
+}
+//  w1|w3: the XF planes of F = N / 2 columns (passed as `out`)
+inline void xf_fill_swiglu_xf(GemmParams& g, uint16_t* xf_out, int F, const float* ssq_part, int n_part) { g.out = (float*)xf_out; g.out_stride = F; g.ssq_part = ssq_part; g.n_part = n_part; }
+//  the lm_head
+inline void xf_fill_store(GemmParams& g, float* out, int out_stride, const float* ssq_part, int n_part) { g.out = out; g.out_stride = out_stride; g.ssq_part = ssq_part; g.n_part = n_part; }
+// One operator of the batched XF decode step (the decode chain and the tests' operator hook): the fields that do not depend on the epilogue.  g holds the operator's
+// epilogue fields; xin: the input XF planes of K columns, M rows.  mtw == 0: one <= 16-row group through launch_q4_gemm.  mtw = 2..4: the wide step's slot groups
+// through launch_q4_wide -- planes: its K-split scratch; the groups' input planes xf_in_gs, output planes xf_out_gs (16-bit elements), partial sums ssq_part_gs and
+// output sums ssq_out_gs (floats) apart.
+inline void xf_step_bind(GemmParams& g, const Q4W& w, const uint16_t* xin, int M, int epi, float norm_eps, int mtw, float* planes, size_t planes_bytes,
+                         long xf_in_gs, long xf_out_gs, long ssq_part_gs, long ssq_out_gs) {
+    g.w = w; g.xf = (const uint4*)xin; g.M = M; if (mtw || epi != EPI_RESID_XF) g.norm_eps = norm_eps;
+    if (!mtw) return;
+    g.wide_mt = mtw; g.xf_gstride = xf_in_gs / 8; g.kz_scratch = planes; g.kz_scratch_bytes = planes_bytes;
+    if (g.ssq_part) g.ssq_part_gstride = ssq_part_gs;
+    if (epi == EPI_RESID_XF) { g.xf_out_gstride = xf_out_gs; g.ssq_out_gstride = ssq_out_gs; } else if (epi == EPI_SWIGLU_XF) g.xf_out_gstride = xf_out_gs;
+}
+inline hipError_t xf_step_launch(const GemmParams& g, int epi, hipStream_t s) { return g.wide_mt ? launch_q4_wide(g, epi, s) : launch_q4_gemm(g, epi, s); }
 
 // ---- small fused ops
 hipError_t launch_q4_repack(const uint8_t* raw, uint4* qs, uint16_t* sc, int64_t n_blocks, int nb, int row_mul, int row_add, hipStream_t s);

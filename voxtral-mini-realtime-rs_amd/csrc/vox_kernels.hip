@@ -2495,11 +2495,42 @@ hipError_t launch_transpose(const float* in, int R, int C, float* out, hipStream
     return hipGetLastError();
 }
 
+// the epilogue instantiation of a <= 16-row launch: the paged, ring and bf16 forms of EPI_ROPE_KV and the per-row form of EPI_RESID_XF are instantiations of their own
+int q4_skinny_epi(int epi, bool kv_pos, bool kv_bf16, bool rope_member, bool xf_w2_row) {
+    if (epi == EPI_ROPE_KV && kv_pos && kv_bf16) epi = rope_member ? EPI_ROPE_KV_PAGED_RING_BF16 : EPI_ROPE_KV_PAGED_BF16;      // (a bf16 pool: the same two forms, 16-bit stores)
+    else if (epi == EPI_ROPE_KV && kv_pos) epi = rope_member ? EPI_ROPE_KV_PAGED_RING : EPI_ROPE_KV_PAGED;      // (launch_q4_gemm_epi admits kv_pos with XF input alone, rope_member with kv_pos alone)
+    if (epi == EPI_RESID_XF && xf_w2_row) epi = EPI_RESID_XF_ROWS;      // (launch_q4_gemm_epi admits xf_w2_row with XF input and xf_w2 alone)
+    return epi;
+}
+static int skinny_epi(const GemmParams& p, int epi) { return q4_skinny_epi(epi, p.kv_pos != nullptr, p.kv_bf16 != 0, p.rope_member != nullptr, epi == EPI_RESID_XF && p.xf_w2_row != nullptr); }
+// the straight-line instantiations of q4_skinny_kernel (n-tiles per wave, epilogue, fused norm, K steps per wave): the decode-step shapes of the real model.  ONE list:
+// q4_skinny_plan answers from it, skinny_launch_n launches from it
+#define VOX_ST_FORMS(X) \
+    X(2, EPI_ROPE_KV, 1, 3) X(2, EPI_ROPE_KV_PAGED, 1, 3) X(2, EPI_ROPE_KV_PAGED_RING, 1, 3) X(2, EPI_ROPE_KV_PAGED_BF16, 1, 3) X(2, EPI_ROPE_KV_PAGED_RING_BF16, 1, 3) X(2, EPI_SWIGLU_XF, 1, 6) \
+    X(1, EPI_SWIGLU_XF, 1, 6) X(1, EPI_RESID_XF, 0, 4) X(4, EPI_SWIGLU_XF, 1, 6) X(1, EPI_RESID_XF, 0, 9) X(4, EPI_STORE, 1, 6) \
+    X(1, EPI_RESID_XF_ROWS, 0, 4) X(1, EPI_RESID_XF_ROWS, 0, 9)      /* the per-row wo epilogue: a form for each of EPI_RESID_XF's */
+// The plan of one <= 16-row launch (launch_q4_skinny and the tests' operator hook both read it):
+//  * n-tiles per wave: as many as still leave >= 192 workgroups (N = 3072 has only 192 tiles); split-K over 4 waves, 8 when the grid is small and K is long enough;
+//  * with XF input and tile-ordered weights, the straight-line in-order pipeline when every wave owns exactly STEPS K steps and the list above holds the form; else the loop.
+void q4_skinny_plan(const Q4W& w, int epi, bool xf, bool pro, SkinnyPlan* pl) {      // epi: the instantiation (q4_skinny_epi)
+    const int nq = w.nb / 4, tiles = (w.N + 15) / 16;
+    int ntw = tiles >= 4 * 192 ? 4 : (tiles >= 2 * 192 ? 2 : 1);      // the x fragments are converted once per wave: more tiles per wave = less VALU
+    int ks = nq >= 4 ? 4 : (nq >= 2 ? 2 : 1);
+    if (tiles / ntw < 256 && nq >= 16) ks = 8;                        // profiles/r01_skinny_sweep.txt
+    if (epi == EPI_RESID_XF || epi == EPI_RESID_XF_ROWS) ntw = 1;       // its partial sums of squares are per workgroup = per 16-column tile
+    // (three n-tiles per wave for w1|w3 -- 768 = 3 x 256 workgroups instead of 576 -- was a round-2 knob: no faster, 15 spilled VGPRs; removed in round 5)
+    pl->ntw = ntw; pl->ks = ks; pl->tiled = w.qt && w.st; pl->steps = (nq + ks - 1) / ks; pl->even = nq % ks == 0 ? nq / ks : 0; pl->straight = 0;
+    if (xf && pl->tiled && pl->even) {
+        const int per = pl->even;
+#define VOX_ST_IS(N_, E_, P_, S_) if (ntw == N_ && epi == E_ && (int)pro == P_ && per == S_) pl->straight = 1;
+        VOX_ST_FORMS(VOX_ST_IS)
+#undef VOX_ST_IS
+    }
+}
 template <int NTW, int TILED>
-static hipError_t skinny_launch_n(const GemmParams& p, int epi, int ks, hipStream_t s) {
-    if (epi == EPI_ROPE_KV && p.kv_pos && p.kv_bf16) epi = p.rope_member ? EPI_ROPE_KV_PAGED_RING_BF16 : EPI_ROPE_KV_PAGED_BF16;      // (a bf16 pool: the same two forms, 16-bit stores)
-    else if (epi == EPI_ROPE_KV && p.kv_pos) epi = p.rope_member ? EPI_ROPE_KV_PAGED_RING : EPI_ROPE_KV_PAGED;      // (launch_q4_gemm_epi admits kv_pos with XF input alone, rope_member with kv_pos alone)
-    if (epi == EPI_RESID_XF && p.xf_w2_row) epi = EPI_RESID_XF_ROWS;      // (launch_q4_gemm_epi admits xf_w2_row with XF input and xf_w2 alone)
+static hipError_t skinny_launch_n(const GemmParams& p, int epi, const SkinnyPlan& pl, hipStream_t s) {
+    epi = skinny_epi(p, epi);
+    const int ks = pl.ks;
     dim3 grid((p.w.N + 16 * NTW - 1) / (16 * NTW));
     const size_t lds = (size_t)ks * NTW * 64 * 4 * sizeof(float);
     if (p.xf) {      // fragment-ordered bf16 hi/lo input (batched decode step); tile-ordered weights only
@@ -2507,13 +2538,12 @@ static hipError_t skinny_launch_n(const GemmParams& p, int epi, int ks, hipStrea
         const bool pro = p.ssq_part != nullptr;
         if (pro && (p.n_part < 1 || p.n_part > 12 * (64 * ks / 16))) return hipErrorInvalidValue;     // partials per thread (q4_skinny_kernel PRO)
         // straight-line in-order pipeline when every wave owns exactly STEPS K-steps (the decode-step shapes of the real model); other shapes: the loop
-        const int nq = p.w.nb / 4, per = nq % ks == 0 ? nq / ks : 0;
-        if (per) {
+        if (pl.straight) {
+            const int per = pl.even;
 #define VOX_ST(N_, E_, P_, S_) if (NTW == N_ && epi == E_ && (int)pro == P_ && per == S_) { \
             if ((E_ == EPI_RESID_XF || E_ == EPI_RESID_XF_ROWS) && (!p.xf_out || !p.xf_w || !p.ssq_out)) return hipErrorInvalidValue; \
             q4_skinny_kernel<N_, E_, 1, 1, P_, S_><<<grid, dim3(64 * ks), lds, s>>>(p); return hipGetLastError(); }
-            VOX_ST(2, EPI_ROPE_KV, 1, 3) VOX_ST(2, EPI_ROPE_KV_PAGED, 1, 3) VOX_ST(2, EPI_ROPE_KV_PAGED_RING, 1, 3) VOX_ST(2, EPI_ROPE_KV_PAGED_BF16, 1, 3) VOX_ST(2, EPI_ROPE_KV_PAGED_RING_BF16, 1, 3) VOX_ST(2, EPI_SWIGLU_XF, 1, 6) VOX_ST(1, EPI_SWIGLU_XF, 1, 6) VOX_ST(1, EPI_RESID_XF, 0, 4) VOX_ST(4, EPI_SWIGLU_XF, 1, 6) VOX_ST(1, EPI_RESID_XF, 0, 9) VOX_ST(4, EPI_STORE, 1, 6)
-            VOX_ST(1, EPI_RESID_XF_ROWS, 0, 4) VOX_ST(1, EPI_RESID_XF_ROWS, 0, 9)      // the per-row wo epilogue: a form for each of EPI_RESID_XF's
+            VOX_ST_FORMS(VOX_ST)
 #undef VOX_ST
         }
         if (epi == EPI_RESID_XF || epi == EPI_RESID_XF_ROWS) {
@@ -2553,19 +2583,12 @@ static hipError_t skinny_launch_n(const GemmParams& p, int epi, int ks, hipStrea
 int q4_skinny_resid_xf_parts(int N) { return (N + 15) / 16; }     // partial sums of squares written by an EPI_RESID_XF launch
 static hipError_t launch_q4_skinny(const GemmParams& p_in, int epi, hipStream_t s) {
     GemmParams p = p_in; p.tl_slot = tl_take_slot(2, epi, p.w.N, p.w.K);
-    const int nq = p.w.nb / 4, tiles = (p.w.N + 15) / 16;
-    // n-tiles per wave: as many as still leave >= 192 workgroups (N = 3072 has only 192 tiles); split-K over 4 waves, 8 when
-    // the grid is small and K is long enough.
-    int ntw = tiles >= 4 * 192 ? 4 : (tiles >= 2 * 192 ? 2 : 1);      // the x fragments are converted once per wave: more tiles per wave = less VALU
-    int ks = nq >= 4 ? 4 : (nq >= 2 ? 2 : 1);
-    if (tiles / ntw < 256 && nq >= 16) ks = 8;                        // profiles/r01_skinny_sweep.txt
-    if (epi == EPI_RESID_XF) ntw = 1;       // its partial sums of squares are per workgroup = per 16-column tile
-    const bool tiled = p.w.qt && p.w.st;
-    // (three n-tiles per wave for w1|w3 -- 768 = 3 x 256 workgroups instead of 576 -- was a round-2 knob: no faster, 15 spilled VGPRs; removed in round 5)
+    SkinnyPlan pl; q4_skinny_plan(p.w, skinny_epi(p, epi), p.xf != nullptr, p.ssq_part != nullptr, &pl);
+    const int ntw = pl.ntw; const bool tiled = pl.tiled;
     hipError_t e;
-    if (ntw == 4) e = tiled ? skinny_launch_n<4, 1>(p, epi, ks, s) : skinny_launch_n<4, 0>(p, epi, ks, s);
-    else if (ntw == 2) e = tiled ? skinny_launch_n<2, 1>(p, epi, ks, s) : skinny_launch_n<2, 0>(p, epi, ks, s);
-    else e = tiled ? skinny_launch_n<1, 1>(p, epi, ks, s) : skinny_launch_n<1, 0>(p, epi, ks, s);
+    if (ntw == 4) e = tiled ? skinny_launch_n<4, 1>(p, epi, pl, s) : skinny_launch_n<4, 0>(p, epi, pl, s);
+    else if (ntw == 2) e = tiled ? skinny_launch_n<2, 1>(p, epi, pl, s) : skinny_launch_n<2, 0>(p, epi, pl, s);
+    else e = tiled ? skinny_launch_n<1, 1>(p, epi, pl, s) : skinny_launch_n<1, 0>(p, epi, pl, s);
     if (e == hipSuccess) gemm_form_note(GEMM_FORM_SKINNY);      // (skinny_launch_n returns an error only where it enqueued nothing)
     return e;
 }

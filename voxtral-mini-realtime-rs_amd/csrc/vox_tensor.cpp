@@ -169,6 +169,179 @@ extern "C" int32_t vox_debug_resid_xf(vox_ctx* c, const vox_q4* w, const vox_res
     HIPCHK(hipMemcpyAsync(ssq_out, dss.p, ssq_b, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
     return VOX_OK;
 }
+// ---- debug: ONE operator of the batched XF decode step (tests; include/voxtral_hip.h): the decode chain's launch for q|k|v, wo / w2, w1|w3 or the lm_head on caller data,
+// through the chain's own parameter fill (xf_step_bind) -- launch_q4_gemm on one XF group, launch_q4_wide on 2..4; or (VOX_XF_MODE_ROWS) the encoder's EPI_ROPE_ROWS on f32 rows.
+// Every argument is checked before a device is touched; the output buffers go up as the caller filled them and come back whole.
+static_assert(sizeof(vox_xf_op_desc) == 112 && sizeof(vox_xf_op_bufs) == 17 * sizeof(void*), "vox_xf_op_desc / vox_xf_op_bufs: the layout tests/test_abi_cpu.py restates");
+static int32_t xf_op_rows(vox_ctx* c, const vox_q4* w, vox_xf_op_desc* d, const vox_xf_op_bufs* b) {
+    const int K = w->w.K, N = w->w.N, M = d->M, hd = d->hd;
+    ARGCHK(b->x && b->out && b->rope_cos && b->rope_sin, "null argument");
+    ARGCHK(M >= 1 && M <= 65536, "M %d out of range (1..65536)", M);
+    ARGCHK((hd == 64 || hd == 128) && d->n_q >= hd && d->n_q <= N && d->n_q % hd == 0, "hd %d, n_q %d: hd is 64 or 128, n_q a multiple of it within N = %d", hd, d->n_q, N);
+    ARGCHK(d->rope_rows >= 1 && d->rope_seq_rows >= 0, "rope_rows %d, rope_seq_rows %d", d->rope_rows, d->rope_seq_rows);
+    if (b->pos) { for (int m = 0; m < M; m++) ARGCHK(b->pos[m] >= 0 && b->pos[m] < d->rope_rows, "pos[%d] = %d is outside the RoPE table (%d rows)", m, b->pos[m], d->rope_rows); }
+    else ARGCHK((d->rope_seq_rows > 0 ? std::min(M, d->rope_seq_rows) : M) <= d->rope_rows, "the rows' positions run past the RoPE table (%d rows)", d->rope_rows);
+    VOXCHK(ctx_bind(c)); hipStream_t s = c->stream;
+    const size_t tab_b = (size_t)d->rope_rows * (hd / 2) * 4;
+    DevBuf dx, dout, dcos, dsin, dpos;
+    HIPCHK(dx.alloc((size_t)M * K * 4)); HIPCHK(dout.alloc((size_t)M * N * 4)); HIPCHK(dcos.alloc(tab_b)); HIPCHK(dsin.alloc(tab_b)); HIPCHK(dpos.alloc((size_t)M * 4));
+    HIPCHK(hipMemcpyAsync(dx.p, b->x, (size_t)M * K * 4, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(dout.p, b->out, (size_t)M * N * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dcos.p, b->rope_cos, tab_b, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(dsin.p, b->rope_sin, tab_b, hipMemcpyHostToDevice, s));
+    if (b->pos) HIPCHK(hipMemcpyAsync(dpos.p, b->pos, (size_t)M * 4, hipMemcpyHostToDevice, s));
+    GemmParams g{}; g.w = w->w; g.x = dx.as<float>(); g.x_stride = K; g.M = M; g.out = dout.as<float>(); g.out_stride = N; g.rope_cos = dcos.as<float>(); g.rope_sin = dsin.as<float>();
+    g.hd = hd; g.n_q = d->n_q; g.pos = b->pos ? (const int*)dpos.p : nullptr; g.rope_seq_rows = d->rope_seq_rows;
+    bool fused = false;
+    HIPCHK(launch_q4_gemm(g, EPI_ROPE_ROWS, s, &fused));
+    HIPCHK(hipMemcpyAsync(b->out, dout.p, (size_t)M * N * 4, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
+    d->fused_rope = fused ? 1 : 0;
+    return VOX_OK;
+}
+// VOX_XF_MODE_WIDE_ROWS: the decoder prefill's 17..48-row form -- rows -> XF tiles, q4_wide_kernel's row-major K-slice planes, the finishing kernel of `epi`
+static int32_t xf_op_wide_rows(vox_ctx* c, const vox_q4* w, vox_xf_op_desc* d, const vox_xf_op_bufs* b) {
+    const int K = w->w.K, N = w->w.N, M = d->M, hd = d->hd, mt = (M + 15) / 16, R = 16 * mt;
+    ARGCHK(b->x, "null argument"); ARGCHK(M > 16 && M <= 48, "M %d out of range (17..48)", M);
+    ARGCHK(d->n_part == 0 && !d->xf_in_gs && !d->xf_out_gs && !d->ssq_part_gs && !d->ssq_out_gs, "the row-major wide form takes no fused norm and no group strides");
+    WidePlan pl; const int KZ = q4_skinny_mt2_plan(w->w, M);
+    ARGCHK(N % 16 == 0 && q4_wide_plan(w->w, mt, EPI_ROPE_KV, &pl) && pl.kz == KZ, "the wide plan does not take this weight (N %d)", N);
+    const int epi = d->epi;
+    if (epi == VOX_XF_EPI_ROPE_KV) {
+        ARGCHK(b->out && b->kc && b->vc && b->rope_cos && b->rope_sin && !b->bias, "null argument (or a bias)");
+        ARGCHK((hd == 64 || hd == 128) && d->n_q >= hd && d->n_q % hd == 0 && d->n_kv >= 1 && (long)d->n_q + 2L * d->n_kv * hd == N, "hd %d, n_q %d, n_kv %d do not make N = %d", hd, d->n_q, d->n_kv, N);
+        ARGCHK(d->kv_form == VOX_XF_KV_CONTIG && !d->kv_bf16 && d->kv_slices == 1 && d->kv_rows >= 1 && d->rope_rows >= 1 && (long)d->n_kv * d->kv_rows * hd < (1L << 28), "one f32 sequence: kv_form 0, kv_slices 1");
+        ARGCHK(d->pos_off >= 0 && (long)d->pos_off + M <= d->kv_rows && (long)d->pos_off + M <= d->rope_rows, "pos_off %d + M %d runs past the cache (%d rows) or the RoPE table (%d rows)", d->pos_off, M, d->kv_rows, d->rope_rows);
+    } else if (epi == VOX_XF_EPI_SWIGLU_XF) { ARGCHK(b->xf_out, "null argument"); ARGCHK(N % 256 == 0, "SWIGLU_XF takes N %% 256 == 0 (N %d)", N); }
+    else if (epi == VOX_XF_EPI_RESID_XF) ARGCHK(b->out && !b->bias, "null argument (or a bias)");
+    else return fail(VOX_ERR_INVALID, "epi %d: the row-major wide form finishes with 1 ROPE_KV, 2 SWIGLU_XF or 3 RESID_XF", epi);
+    d->plan_ntw = pl.ntw; d->plan_ks = pl.kz; d->plan_steps = pl.sps;
+    VOXCHK(ctx_bind(c)); hipStream_t s = c->stream;
+    const size_t out_b = (size_t)R * N * 4, xin_b = (size_t)mt * K * 64, xo_b = (size_t)mt * (N / 2) * 64, planes_b = q4_wide_planes_bytes(w->w, mt, pl);      // (launch_q4_wide asks for room for 16 mt rows per slice; the kernel stores M)
+    const size_t kv_b = epi == VOX_XF_EPI_ROPE_KV ? (size_t)d->n_kv * d->kv_rows * hd * 4 : 0, tab_b = epi == VOX_XF_EPI_ROPE_KV ? (size_t)d->rope_rows * (hd / 2) * 4 : 0;
+    DevBuf dx, dxf, dpl, dout, dxo, dbias, dkc, dvc, dcos, dsin;
+    auto up = [&](DevBuf& db, const void* src, size_t bytes) -> int32_t {
+        if (!src || !bytes) return VOX_OK;
+        HIPCHK(db.alloc(bytes)); HIPCHK(hipMemcpyAsync(db.p, src, bytes, hipMemcpyHostToDevice, s)); return VOX_OK;
+    };
+    VOXCHK(up(dx, b->x, (size_t)M * K * 4)); HIPCHK(dxf.alloc(xin_b)); HIPCHK(dpl.alloc(planes_b));
+    if (epi != VOX_XF_EPI_SWIGLU_XF) VOXCHK(up(dout, b->out, out_b)); else { VOXCHK(up(dxo, b->xf_out, xo_b)); VOXCHK(up(dbias, b->bias, (size_t)N * 4)); }
+    if (epi == VOX_XF_EPI_ROPE_KV) { VOXCHK(up(dkc, b->kc, kv_b)); VOXCHK(up(dvc, b->vc, kv_b)); VOXCHK(up(dcos, b->rope_cos, tab_b)); VOXCHK(up(dsin, b->rope_sin, tab_b)); }
+    HIPCHK(launch_xf_rows(dx.as<float>(), K, M, K, dxf.as<uint16_t>(), s));
+    GemmParams g{}; g.w = w->w; g.xf = (const uint4*)dxf.p; g.M = M; g.kz_scratch = dpl.as<float>(); g.kz_scratch_bytes = planes_b;      // (the prefill's gemm_xf)
+    HIPCHK(launch_q4_skinny_mt2_planes(g, KZ, s));
+    if (epi == VOX_XF_EPI_ROPE_KV)
+        HIPCHK(launch_splitk_finish_rope_kv(dpl.as<float>(), KZ, M, N, dout.as<float>(), N, d->n_q, d->n_kv, hd, d->pos_off, dcos.as<float>(), dsin.as<float>(), dkc.as<float>(), dvc.as<float>(), d->kv_rows * hd, s));
+    else if (epi == VOX_XF_EPI_SWIGLU_XF) HIPCHK(launch_splitk_finish_swiglu_xf(dpl.as<float>(), KZ, M, N, dbias.as<float>(), dxo.as<uint16_t>(), s));
+    else HIPCHK(launch_splitk_finish_resid(dpl.as<float>(), KZ, M, N, dout.as<float>(), N, s));
+    if (epi != VOX_XF_EPI_SWIGLU_XF) HIPCHK(hipMemcpyAsync(b->out, dout.p, out_b, hipMemcpyDeviceToHost, s)); else HIPCHK(hipMemcpyAsync(b->xf_out, dxo.p, xo_b, hipMemcpyDeviceToHost, s));
+    if (epi == VOX_XF_EPI_ROPE_KV) { HIPCHK(hipMemcpyAsync(b->kc, dkc.p, kv_b, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(b->vc, dvc.p, kv_b, hipMemcpyDeviceToHost, s)); }
+    HIPCHK(hipStreamSynchronize(s));
+    return VOX_OK;
+}
+extern "C" int32_t vox_debug_xf_op(vox_ctx* c, const vox_q4* w, vox_xf_op_desc* d, const vox_xf_op_bufs* b) {
+    ARGCHK(c && w && d && b, "null argument");
+    ARGCHK(!d->reserved[0] && !d->reserved[1], "reserved words must be 0");
+    const int K = w->w.K, N = w->w.N, G = d->groups, hd = d->hd, n_part = d->n_part;
+    ARGCHK(w->w.fmt == WFMT_Q4_0 && w->w.qt && w->w.st && K % 128 == 0, "the XF step takes a tile-ordered Q4 weight with K a multiple of 128 (K %d)", K);
+    d->plan_ntw = d->plan_ks = d->plan_steps = d->plan_straight = d->fused_rope = 0;
+    if (d->mode == VOX_XF_MODE_ROWS) return xf_op_rows(c, w, d, b);
+    if (d->mode == VOX_XF_MODE_WIDE_ROWS) return xf_op_wide_rows(c, w, d, b);
+    ARGCHK(d->mode == VOX_XF_MODE_STEP, "mode %d: 0 the XF step, 1 the encoder's RoPE rows, 2 the prefill's row-major wide form", d->mode);
+    ARGCHK(G >= 1 && G <= 4, "groups %d out of range (1..4)", G);
+    ARGCHK(G == 1 ? (d->M >= 1 && d->M <= 16) : d->M == 16 * G, "M %d: 1..16 for one group, 16 * groups for the wide step", d->M);
+    const int M = d->M, R = 16 * G, mtw = G == 1 ? 0 : G;
+    ARGCHK(b->x, "null argument"); ARGCHK(n_part >= 0, "n_part %d is negative", n_part); ARGCHK(n_part == 0 || b->ssq_part, "n_part without ssq_part");
+    ARGCHK(d->norm_eps >= 0.f && d->norm_eps == d->norm_eps, "norm_eps must be a non-negative number");
+    int epi; size_t xout_cols = 0;
+    switch (d->epi) {
+    case VOX_XF_EPI_STORE: epi = EPI_STORE;
+        ARGCHK(b->out, "null argument"); ARGCHK(!b->bias || G == 1, "a bias: the one-group STORE alone takes it"); ARGCHK(G == 1 || (N % 16 == 0 && n_part >= 1), "the wide STORE takes N %% 16 == 0 and the fused norm");
+        break;
+    case VOX_XF_EPI_ROPE_KV: epi = EPI_ROPE_KV;
+        ARGCHK(b->out && b->kc && b->vc && b->pos && b->rope_cos && !b->bias, "null argument (or a bias)"); ARGCHK(n_part >= 1, "ROPE_KV runs with the fused norm (n_part >= 1)");
+        ARGCHK((hd == 64 || hd == 128) && d->n_q >= hd && d->n_q % hd == 0 && d->n_kv >= 1 && (long)d->n_q + 2L * d->n_kv * hd == N, "hd %d, n_q %d, n_kv %d do not make N = %d", hd, d->n_q, d->n_kv, N);
+        ARGCHK(d->kv_form >= VOX_XF_KV_CONTIG && d->kv_form <= VOX_XF_KV_PAGED_RING && (G == 1 || d->kv_form <= VOX_XF_KV_SLOTS), "kv_form %d (the wide step: contiguous or slots)", d->kv_form);
+        ARGCHK(d->kv_bf16 == 0 || (d->kv_bf16 == 1 && d->kv_form >= VOX_XF_KV_PAGED), "kv_bf16 %d: a paged form's, 0 or 1", d->kv_bf16);
+        ARGCHK(d->kv_slices >= 1 && d->kv_rows >= 1 && d->rope_rows >= 1 && (long)d->kv_slices * d->n_kv * d->kv_rows * hd < (1L << 28), "kv_slices %d, kv_rows %d, rope_rows %d", d->kv_slices, d->kv_rows, d->rope_rows);
+        ARGCHK(d->kv_form == VOX_XF_KV_CONTIG || b->kv_row, "kv_row is null"); ARGCHK(d->kv_form < VOX_XF_KV_PAGED || b->kv_pos, "kv_pos is null");
+        if (d->kv_form == VOX_XF_KV_PAGED_RING) {
+            ARGCHK(b->rope_member && d->rope_mask >= 0 && !(d->rope_mask & (d->rope_mask + 1)) && d->rope_rows % (d->rope_mask + 1) == 0, "a RoPE ring: rope_member, rope_mask + 1 a power of two that divides rope_rows");
+        } else ARGCHK(b->rope_sin, "rope_sin is null");
+        for (int r = 0; r < M; r++) {
+            const int ps = b->pos[r], slice = d->kv_form == VOX_XF_KV_CONTIG ? r : b->kv_row[r], row = d->kv_form >= VOX_XF_KV_PAGED ? b->kv_pos[r] : ps;
+            ARGCHK(ps >= 0 && slice >= 0 && slice < d->kv_slices && row >= 0 && row < d->kv_rows, "row %d: position %d, slice %d of %d, cache row %d of %d", r, ps, slice, d->kv_slices, row, d->kv_rows);
+            if (d->kv_form == VOX_XF_KV_PAGED_RING) ARGCHK(b->rope_member[r] >= 0 && b->rope_member[r] < d->rope_rows / (d->rope_mask + 1), "rope_member[%d] = %d names no ring member", r, b->rope_member[r]);
+            else ARGCHK(ps < d->rope_rows, "pos[%d] = %d is outside the RoPE table (%d rows)", r, ps, d->rope_rows);
+        }
+        break;
+    case VOX_XF_EPI_SWIGLU_XF: epi = EPI_SWIGLU_XF; xout_cols = (size_t)N / 2;
+        ARGCHK(b->xf_out && !b->bias, "null argument (or a bias)"); ARGCHK(N % 256 == 0, "SWIGLU_XF takes N %% 256 == 0 (N %d)", N); ARGCHK(G == 1 || n_part >= 1, "the wide SWIGLU_XF runs with the fused norm");
+        break;
+    case VOX_XF_EPI_RESID_XF: epi = EPI_RESID_XF; xout_cols = (size_t)N;
+        ARGCHK(b->out && b->resid && b->xf_w && b->xf_out && b->ssq_out && !b->bias, "null argument (or a bias)"); ARGCHK(N % 128 == 0, "RESID_XF takes N %% 128 == 0 (N %d)", N);
+        ARGCHK(n_part == 0, "RESID_XF takes no fused norm");
+        break;
+    default: return fail(VOX_ERR_INVALID, "epi %d: 0 STORE, 1 ROPE_KV, 2 SWIGLU_XF, 3 RESID_XF", d->epi);
+    }
+    // group strides (0: packed), in the elements the kernels count them in
+    const long xin_pk = (long)K * 32, xout_pk = (long)xout_cols * 32, sp_pk = (long)n_part * 16, so_pk = (long)q4_skinny_resid_xf_parts(N) * 16;
+    const long xin_gs = d->xf_in_gs ? d->xf_in_gs : xin_pk, xout_gs = d->xf_out_gs ? d->xf_out_gs : xout_pk, sp_gs = d->ssq_part_gs ? d->ssq_part_gs : sp_pk, so_gs = d->ssq_out_gs ? d->ssq_out_gs : so_pk;
+    ARGCHK(xin_gs >= xin_pk && xin_gs % 8 == 0 && xout_gs >= xout_pk && xout_gs % 8 == 0 && sp_gs >= sp_pk && so_gs >= so_pk, "a group stride is smaller than its block (or the planes' is no multiple of 8)");
+    // the plan, before anything is allocated: the one-group launcher refuses more partial sums than its threads take (12 each)
+    size_t planes_b = 0;
+    if (mtw) {
+        WidePlan pl; ARGCHK(q4_wide_plan(w->w, mtw, epi, &pl), "the wide step does not take this weight (N %d)", N);
+        d->plan_ntw = pl.ntw; d->plan_ks = pl.kz; d->plan_steps = pl.sps; if (epi != EPI_STORE) planes_b = q4_wide_planes_bytes(w->w, mtw, pl);
+    } else {
+        const bool paged = epi == EPI_ROPE_KV && d->kv_form >= VOX_XF_KV_PAGED;
+        SkinnyPlan pl; q4_skinny_plan(w->w, q4_skinny_epi(epi, paged, paged && d->kv_bf16, paged && d->kv_form == VOX_XF_KV_PAGED_RING, false), true, n_part > 0, &pl);
+        ARGCHK(n_part <= 12 * (64 * pl.ks / 16), "n_part %d: a launch of %d waves takes at most %d", n_part, pl.ks, 12 * (64 * pl.ks / 16));
+        d->plan_ntw = pl.ntw; d->plan_ks = pl.ks; d->plan_steps = pl.steps; d->plan_straight = pl.straight;
+    }
+    VOXCHK(ctx_bind(c)); hipStream_t s = c->stream;
+    const size_t out_b = (size_t)R * N * 4, kv_b = epi == EPI_ROPE_KV ? (size_t)d->kv_slices * d->n_kv * d->kv_rows * hd * (d->kv_bf16 ? 2 : 4) : 0;
+    const bool ring = epi == EPI_ROPE_KV && d->kv_form == VOX_XF_KV_PAGED_RING;
+    const size_t tab_b = epi == EPI_ROPE_KV ? (size_t)d->rope_rows * (ring ? hd : hd / 2) * 4 : 0;
+    DevBuf dx, dxf, dsp, dbias, dres, dw1, dw2, dout, dkc, dvc, dxo, dso, dcos, dsin, dpos, drow, dkp, dmem, dpl;
+    auto up = [&](DevBuf& db, const void* src, size_t bytes) -> int32_t {
+        if (!src || !bytes) return VOX_OK;
+        HIPCHK(db.alloc(bytes)); HIPCHK(hipMemcpyAsync(db.p, src, bytes, hipMemcpyHostToDevice, s)); return VOX_OK;
+    };
+    VOXCHK(up(dx, b->x, (size_t)R * K * 4));
+    HIPCHK(dxf.alloc((size_t)G * xin_gs * 2)); HIPCHK(hipMemsetAsync(dxf.p, 0xFF, (size_t)G * xin_gs * 2, s));      // (the gaps between the groups' planes: NaN)
+    for (int gi = 0; gi < G; gi++) HIPCHK(launch_xf_rows(dx.as<float>() + (size_t)gi * 16 * K, K, 16, K, dxf.as<uint16_t>() + (size_t)gi * xin_gs, s));      // all 16 rows of a group: rows >= M hold data too
+    if (n_part) {
+        HIPCHK(dsp.alloc((size_t)G * sp_gs * 4)); HIPCHK(hipMemsetAsync(dsp.p, 0xFF, (size_t)G * sp_gs * 4, s));
+        for (int gi = 0; gi < G; gi++) HIPCHK(hipMemcpyAsync(dsp.as<float>() + (size_t)gi * sp_gs, b->ssq_part + (size_t)gi * sp_pk, (size_t)sp_pk * 4, hipMemcpyHostToDevice, s));
+    }
+    VOXCHK(up(dbias, b->bias, (size_t)N * 4));
+    if (epi != EPI_SWIGLU_XF) VOXCHK(up(dout, b->out, out_b));
+    if (epi == EPI_RESID_XF) { VOXCHK(up(dres, b->resid, out_b)); VOXCHK(up(dw1, b->xf_w, (size_t)N * 4)); VOXCHK(up(dw2, b->xf_w2, (size_t)N * 4)); VOXCHK(up(dso, b->ssq_out, (size_t)G * so_gs * 4)); }
+    if (xout_cols) VOXCHK(up(dxo, b->xf_out, (size_t)G * xout_gs * 2));
+    if (epi == EPI_ROPE_KV) {
+        VOXCHK(up(dkc, b->kc, kv_b)); VOXCHK(up(dvc, b->vc, kv_b)); VOXCHK(up(dcos, b->rope_cos, tab_b)); if (!ring) VOXCHK(up(dsin, b->rope_sin, tab_b));
+        VOXCHK(up(dpos, b->pos, (size_t)M * 4)); if (d->kv_form != VOX_XF_KV_CONTIG) VOXCHK(up(drow, b->kv_row, (size_t)M * 4));
+        if (d->kv_form >= VOX_XF_KV_PAGED) VOXCHK(up(dkp, b->kv_pos, (size_t)M * 4)); if (ring) VOXCHK(up(dmem, b->rope_member, (size_t)M * 4));
+    }
+    if (planes_b) HIPCHK(dpl.alloc(planes_b));
+    // the operator's epilogue fields, through the decode chain's own fill helpers
+    GemmParams g{}; const float* sp = n_part ? dsp.as<float>() : nullptr;
+    if (epi == EPI_STORE) { xf_fill_store(g, dout.as<float>(), N, sp, n_part); g.bias = dbias.as<float>(); }
+    if (epi == EPI_ROPE_KV) {
+        xf_fill_rope_kv(g, dout.as<float>(), N, sp, n_part, (const int*)dpos.p, dcos.as<float>(), dsin.as<float>(), hd, d->n_q, d->n_kv, dkc.as<float>(), dvc.as<float>(),
+                        (long)d->n_kv * d->kv_rows * hd, d->kv_rows, d->kv_form == VOX_XF_KV_SLOTS ? (const int*)drow.p : nullptr);
+        if (d->kv_form >= VOX_XF_KV_PAGED) xf_fill_rope_kv_paged(g, (long)d->n_kv * d->kv_rows * hd, d->kv_rows, (const int*)drow.p, (const int*)dkp.p, d->kv_bf16);
+        if (ring) xf_fill_rope_ring(g, dcos.as<float>(), (const int*)dmem.p, d->rope_mask);
+    }
+    if (epi == EPI_SWIGLU_XF) xf_fill_swiglu_xf(g, dxo.as<uint16_t>(), N / 2, sp, n_part);
+    if (epi == EPI_RESID_XF) xf_fill_resid_xf(g, dout.as<float>(), dres.as<float>(), N, dxo.as<uint16_t>(), dw1.as<float>(), dw2.as<float>(), dso.as<float>());
+    xf_step_bind(g, w->w, dxf.as<uint16_t>(), M, epi, d->norm_eps, mtw, dpl.as<float>(), planes_b, xin_gs, xout_gs, sp_gs, so_gs);
+    HIPCHK(xf_step_launch(g, epi, s));
+    if (epi != EPI_SWIGLU_XF) HIPCHK(hipMemcpyAsync(b->out, dout.p, out_b, hipMemcpyDeviceToHost, s));
+    if (xout_cols) HIPCHK(hipMemcpyAsync(b->xf_out, dxo.p, (size_t)G * xout_gs * 2, hipMemcpyDeviceToHost, s));
+    if (epi == EPI_RESID_XF) HIPCHK(hipMemcpyAsync(b->ssq_out, dso.p, (size_t)G * so_gs * 4, hipMemcpyDeviceToHost, s));
+    if (epi == EPI_ROPE_KV) { HIPCHK(hipMemcpyAsync(b->kc, dkc.p, kv_b, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(b->vc, dvc.p, kv_b, hipMemcpyDeviceToHost, s)); }
+    HIPCHK(hipStreamSynchronize(s));
+    return VOX_OK;
+}
 // ConvDownsampler::forward (models/layers/conv.rs:78-83): gelu(conv1d k3 s2 p1) twice, x [C][L] -> [O][L2], on the product's im2col MFMA path (conv_stem_dev)
 extern "C" int32_t vox_conv_downsample(vox_ctx* c, const float* x, int32_t C, int32_t L, const float* w1, const float* b1, const float* w2, const float* b2, int32_t O, float* out) {
     ARGCHK(c && x && w1 && b1 && w2 && b2 && out && C > 0 && L > 0 && O > 0, "bad argument"); ARGCHK((3 * C) % 128 == 0 && (3 * O) % 128 == 0, "3 * channels must be a multiple of 128");
