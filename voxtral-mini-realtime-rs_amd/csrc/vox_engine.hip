@@ -361,14 +361,6 @@ struct PassA { uint4 q0; uint2 q1; float s0, s1; };
 // EXACTLY (int32).  Lane group g < 2 then holds the four digit sums of block g for tile row n: Horner in f32, the -8 offset, the two scales.
 typedef int i4v __attribute__((ext_vector_type(4)));
 struct StepCtx { i4v A; float m8sx, sxinv; };
-__device__ __forceinline__ StepCtx load_ctx(const unsigned char* planes, const float2* binfo, int blk0, int lane) {
-    const int n = lane & 15, g = lane >> 4;
-    StepCtx cx; cx.A = i4v{0, 0, 0, 0};
-    if (n < 8 && (g >> 1) == (n >> 2)) cx.A = *reinterpret_cast<const i4v*>(planes + (((blk0 + (n >> 2)) * 4 + (n & 3)) * 2 + (g & 1)) * 16);
-    const float2 bi = binfo[blk0 + (g & 1)];      // lane groups 0 / 1 finish blocks 0 / 1 (groups 2, 3 compute along on the same values; their results are dropped)
-    cx.m8sx = bi.x; cx.sxinv = bi.y;
-    return cx;
-}
 // one step record as this lane holds it: 8 bytes of nibbles + the f16 scale bits of its block.  Records do not depend on the step's activations, so a wave
 // moves them from the ring into REGISTERS while it waits for an edge (and frees the ring slots for the loader: the register file is the bigger buffer)
 struct RecR { i4v B; float sc; };      // the MFMA B operand (nibbles unpacked to int8 -- done while the wave waits, off the critical path) and the block scale as f32
@@ -393,8 +385,63 @@ __device__ __forceinline__ float mstep(const RecR& r, const StepCtx& cx, float a
     t += cx.m8sx;
     return fmaf(t, r.sc * cx.sxinv, acc);
 }
-__device__ __forceinline__ float mstep(const unsigned char* rec, bool half, int lane, const StepCtx& cx, float acc) { return mstep(rec_read(rec, half, lane), cx, acc); }
-__device__ __forceinline__ float g01_sum(float v, int lane) { return v + __shfl(v, (lane + 16) & 63); }      // block 0 + block 1 partial of tile row n (valid in lanes 0..15)
+// ---- paired steps: TWO K-steps per epilogue, on all 64 lanes ----
+// A single step's A has digits in rows 0..7 only, so D rows 8..15 (lane groups 2, 3) are zeros and half the epilogue's lanes work for nothing.  The two halves of D
+// are independent products: a second MFMA accumulates into the same D with an A fragment that lives in rows 8..15 (zeros in rows 0..7),
+//     D = mfma(A_lo(step a), B(a), 0);  D = mfma(A_hi(step b), B(b), D)
+// and lane group g then holds the four digit sums of block g & 1 of step (g >> 1 ? b : a) for tile row n.  ONE epilogue finishes both steps; every per-lane operand
+// (block info, weight block scale) is chosen by lane group where it is READ, so a pair costs no register more than one step's epilogue and no cross-lane move.
+// The two steps may belong to different tiles (w2): lane groups 0, 1 then accumulate one tile's row and groups 2, 3 the other's.
+struct PairCtx { i4v Alo, Ahi; float m8sx, sxinv; };
+__device__ __forceinline__ PairCtx load_ctx2(const unsigned char* planes, const float2* binfo, int blk_a, int blk_b, int lane) {
+    const int n = lane & 15, g = lane >> 4, p = (n & 7) >> 2;      // lanes n < 8 load step a's plane (row n), lanes n >= 8 step b's (row n): digit n & 3 of the step's block p
+    i4v X = i4v{0, 0, 0, 0};
+    if ((g >> 1) == p) X = *reinterpret_cast<const i4v*>(planes + ((((n < 8 ? blk_a : blk_b) + p) * 4 + (n & 3)) * 2 + (g & 1)) * 16);
+    PairCtx cx;
+#pragma unroll
+    for (int i = 0; i < 4; i++) { cx.Alo[i] = n < 8 ? X[i] : 0; cx.Ahi[i] = n < 8 ? 0 : X[i]; }
+    const float2 bi = binfo[(g < 2 ? blk_a : blk_b) + (g & 1)];      // consecutive steps (blk_b = blk_a + 2): binfo[blk_a + g]
+    cx.m8sx = bi.x; cx.sxinv = bi.y;
+    return cx;
+}
+struct RecP { i4v Ba, Bb; float sc; };      // the two steps' B operands and ONE scale register: record a's block scale in lane groups 0, 1, record b's in groups 2, 3
+__device__ __forceinline__ RecP rec_read2(const unsigned char* rec_a, const unsigned char* rec_b, bool half, int lane) {
+    const int n = lane & 15, g = lane >> 4;
+    uint2 qa = make_uint2(0u, 0u), qb = make_uint2(0u, 0u);
+    if (!half) { qa = reinterpret_cast<const uint2*>(rec_a)[lane]; qb = reinterpret_cast<const uint2*>(rec_b)[lane]; }
+    else if (n < 8) { qa = reinterpret_cast<const uint2*>(rec_a)[g * 8 + n]; qb = reinterpret_cast<const uint2*>(rec_b)[g * 8 + n]; }
+    const unsigned short sb = reinterpret_cast<const unsigned short*>((g < 2 ? rec_a : rec_b) + (half ? REC_H_SC : REC_SC))[(half ? 8 : 16) * (g & 1) + (half ? (n & 7) : n)];
+    RecP r;
+    r.Ba[0] = (int)(qa.x & 0x0F0F0F0Fu); r.Ba[1] = (int)(qa.y & 0x0F0F0F0Fu); r.Ba[2] = (int)((qa.x >> 4) & 0x0F0F0F0Fu); r.Ba[3] = (int)((qa.y >> 4) & 0x0F0F0F0Fu);
+    r.Bb[0] = (int)(qb.x & 0x0F0F0F0Fu); r.Bb[1] = (int)(qb.y & 0x0F0F0F0Fu); r.Bb[2] = (int)((qb.x >> 4) & 0x0F0F0F0Fu); r.Bb[3] = (int)((qb.y >> 4) & 0x0F0F0F0Fu);
+    r.sc = __half2float(__ushort_as_half(sb));
+    asm volatile("" : "+v"(r.Ba[0]), "+v"(r.Ba[1]), "+v"(r.Ba[2]), "+v"(r.Ba[3]), "+v"(r.Bb[0]), "+v"(r.Bb[1]), "+v"(r.Bb[2]), "+v"(r.Bb[3]), "+v"(r.sc));      // pinned here, as in rec_read
+    return r;
+}
+// a single step next to paired ones (w2's ninth): its D rows 8..15 are zeros, so lane groups 2, 3 get a ZERO scale and add nothing to the four-group sum
+__device__ __forceinline__ RecR rec_read_lo(const unsigned char* rec, int lane) {
+    RecR r = rec_read(rec, false, lane);
+    r.sc = lane < 32 ? r.sc : 0.f;
+    asm volatile("" : "+v"(r.sc));
+    return r;
+}
+__device__ __forceinline__ float mstep2(const RecP& r, const PairCtx& cx, float acc) {
+    i4v D = __builtin_amdgcn_mfma_i32_16x16x64_i8(cx.Alo, r.Ba, i4v{0, 0, 0, 0}, 0, 0, 0);
+    D = __builtin_amdgcn_mfma_i32_16x16x64_i8(cx.Ahi, r.Bb, D, 0, 0, 0);
+    const int lo = (int)((unsigned)D[0] + ((unsigned)D[1] << 7)), hi = (int)((unsigned)D[2] + ((unsigned)D[3] << 7));
+    float t = fmaf((float)hi, 16384.0f, (float)lo);
+    t += cx.m8sx;
+    return fmaf(t, r.sc * cx.sxinv, acc);
+}
+__device__ __forceinline__ float mstep2(const unsigned char* rec_a, const unsigned char* rec_b, bool half, int lane, const PairCtx& cx, float acc) { return mstep2(rec_read2(rec_a, rec_b, half, lane), cx, acc); }
+// the four lane groups' partials of tile row n in ONE fixed order, (g0 + g2) + (g1 + g3), valid in lanes 0..15: v_permlane32_swap, v_permlane16_swap and two adds --
+// no LDS round trip
+__device__ __forceinline__ float g4_sum(float v) {
+    const auto a = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    const float w = __uint_as_float(a[0]) + __uint_as_float(a[1]);
+    const auto b = __builtin_amdgcn_permlane16_swap(__float_as_uint(w), __float_as_uint(w), false, false);
+    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
+}
 // Four consecutive elements of a 32-element block (8 consecutive lanes = one block, this lane: elements [4 (lane & 7), +4)) -> digit planes + block info
 __device__ __forceinline__ void to_digits(const float (&v)[4], int lane, unsigned char* plane_blk, float2* binfo_blk) {
     float mx = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
@@ -583,19 +630,20 @@ __device__ __forceinline__ void eng_consumer(const EngParams& p, EngCtl* c, unsi
             const gf_p kc = as_g(L->kc) + (size_t)g * p.max_seq * EHD, vc = as_g(L->vc) + (size_t)g * p.max_seq * EHD;
             const int t12 = cw * 64 + lane;
             const int part_ = t12 & 7, ks = t12 >> 3;           // scores: 8 lanes per key, 96 keys per pass
-            // this wave's 8 step records (K-steps 4 cw .. 4 cw + 3 of the 16-row q tile and of the 8-row k|v tile) -> registers, BEFORE the input vector exists
-            RecR rq[8];
+            // this wave's 8 step records (K-steps 4 cw .. 4 cw + 3 of the 16-row q tile and of the 8-row k|v tile) -> registers, BEFORE the input vector exists.
+            // Pairing: K-steps (0, 1) and (2, 3) of each tile -- rq[0], rq[1]: the q tile's pairs, rq[2], rq[3]: the k|v tile's
+            RecP rq[4];
             {
                 int s0, s1, s2;
                 const unsigned char* b0 = cs.slot_wait(cs.P, 2 * REC, s0);
-                rq[0] = rec_read(b0, false, lane); rq[1] = rec_read(b0 + REC, false, lane);
+                rq[0] = rec_read2(b0, b0 + REC, false, lane);
                 cs.slot_release(s0);
                 const unsigned char* b1 = cs.slot_wait(cs.P + 1, 2 * REC, s1);
-                rq[2] = rec_read(b1, false, lane); rq[3] = rec_read(b1 + REC, false, lane);
+                rq[1] = rec_read2(b1, b1 + REC, false, lane);
                 cs.slot_release(s1);
                 const unsigned char* b2 = cs.slot_wait(cs.P + 2, 4 * REC_H, s2);
 #pragma unroll
-                for (int i = 0; i < 4; i++) rq[4 + i] = rec_read(b2 + i * REC_H, true, lane);
+                for (int i = 0; i < 2; i++) rq[2 + i] = rec_read2(b2 + 2 * i * REC_H, b2 + (2 * i + 1) * REC_H, true, lane);
                 cs.slot_release(s2);
                 cs.P += QKV_PK;
             }
@@ -617,11 +665,11 @@ __device__ __forceinline__ void eng_consumer(const EngParams& p, EngCtl* c, unsi
             {
                 float a0 = 0.f, a1 = 0.f;
 #pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    const StepCtx cx = load_ctx(xs, binfo, 2 * (4 * cw + i), lane);
-                    a0 = mstep(rq[i], cx, a0); a1 = mstep(rq[4 + i], cx, a1);
+                for (int i = 0; i < 2; i++) {
+                    const PairCtx cx = load_ctx2(xs, binfo, 8 * cw + 4 * i, 8 * cw + 4 * i + 2, lane);
+                    a0 = mstep2(rq[i], cx, a0); a1 = mstep2(rq[2 + i], cx, a1);
                 }
-                a0 = g01_sum(a0, lane); a1 = g01_sum(a1, lane);
+                a0 = g4_sum(a0); a1 = g4_sum(a1);
                 if (lane < 16) part[lane * NCONS + cw] = a0;
                 if (lane < 8) part[(16 + lane) * NCONS + cw] = a1;
             }
@@ -755,15 +803,13 @@ __device__ __forceinline__ void eng_consumer(const EngParams& p, EngCtl* c, unsi
             }
             if (T) tl(3);
             {   // ---------------- wo: rows [384 s, +384) x head h's 128 columns: this wave's tiles 2 cw, 2 cw + 1, two K-steps each ----------------
-                StepCtx cx[2];
-#pragma unroll
-                for (int i = 0; i < 2; i++) cx[i] = load_ctx(xs, binfo, 8 * cw + 2 * i, lane);
+                const PairCtx cx = load_ctx2(xs, binfo, 8 * cw, 8 * cw + 2, lane);      // pairing: each tile's two K-steps
 #pragma unroll
                 for (int i = 0; i < WO_PK; i++) {
                     int sl_; const unsigned char* bb = cs.slot_wait(cs.P + i, 2 * REC, sl_);
-                    float a = mstep(bb, false, lane, cx[0], 0.f); a = mstep(bb + REC, false, lane, cx[1], a);
+                    float a = mstep2(bb, bb + REC, false, lane, cx, 0.f);
                     cs.slot_release(sl_);
-                    a = g01_sum(a, lane);
+                    a = g4_sum(a);
                     if (lane < 16) publish_b(p.PW, NPW * ED * 8u, (unsigned)(h * ED + 384 * s + 16 * (2 * cw + i) + lane), tag, a, false);
                 }
                 cs.P += WO_PK;
@@ -775,29 +821,27 @@ __device__ __forceinline__ void eng_consumer(const EngParams& p, EngCtl* c, unsi
         if (op == EOP_W13) {
             // ================= w1|w3: 72 rows (36 SwiGLU outputs) x K 3072: this wave's K-steps of 4 full tiles + the 8-row tile =================
             constexpr int NPRE = 3;      // tiles whose records wait in registers (36 VGPRs) while the post-attention stream is still on its way; their ring slots refill meanwhile
-            RecR rw[4 * NPRE];
+            RecP rw[2 * NPRE];      // pairing, in every tile (register-resident, ring-read and the 8-row one alike): K-steps (0, 1) and (2, 3)
 #pragma unroll
             for (int ti = 0; ti < NPRE; ti++) {
                 int s0, s1;
                 const unsigned char* b0 = cs.slot_wait(cs.P + 2 * ti, 2 * REC, s0);
-                rw[4 * ti] = rec_read(b0, false, lane); rw[4 * ti + 1] = rec_read(b0 + REC, false, lane);
+                rw[2 * ti] = rec_read2(b0, b0 + REC, false, lane);
                 cs.slot_release(s0);
                 const unsigned char* b1 = cs.slot_wait(cs.P + 2 * ti + 1, 2 * REC, s1);
-                rw[4 * ti + 2] = rec_read(b1, false, lane); rw[4 * ti + 3] = rec_read(b1 + REC, false, lane);
+                rw[2 * ti + 1] = rec_read2(b1, b1 + REC, false, lane);
                 cs.slot_release(s1);
             }
             cs.all_gather<true>(p.H1, p.SS1, tag, 2u * (unsigned)l + 1u, xs, ssl, binfo, tl, T);
             if (T) tl(5);
-            StepCtx cx[4];
+            PairCtx cx[2];
 #pragma unroll
-            for (int i = 0; i < 4; i++) cx[i] = load_ctx(xs, binfo, 2 * (4 * cw + i), lane);
+            for (int i = 0; i < 2; i++) cx[i] = load_ctx2(xs, binfo, 8 * cw + 4 * i, 8 * cw + 4 * i + 2, lane);
             if (T) tl(24);
 #pragma unroll
             for (int ti = 0; ti < NPRE; ti++) {
-                float a = 0.f;
-#pragma unroll
-                for (int i = 0; i < 4; i++) a = mstep(rw[4 * ti + i], cx[i], a);
-                a = g01_sum(a, lane);
+                float a = mstep2(rw[2 * ti], cx[0], 0.f); a = mstep2(rw[2 * ti + 1], cx[1], a);
+                a = g4_sum(a);
                 if (lane < 16) part[(16 * ti + lane) * NCONS + cw] = a;
             }
 #pragma unroll 1
@@ -805,19 +849,16 @@ __device__ __forceinline__ void eng_consumer(const EngParams& p, EngCtl* c, unsi
                 int s0, s1;
                 const unsigned char* b0 = cs.slot_wait(cs.P + 2 * ti, 2 * REC, s0);
                 const unsigned char* b1 = cs.slot_wait(cs.P + 2 * ti + 1, 2 * REC, s1);
-                float a = mstep(b0, false, lane, cx[0], 0.f); a = mstep(b0 + REC, false, lane, cx[1], a);
-                a = mstep(b1, false, lane, cx[2], a); a = mstep(b1 + REC, false, lane, cx[3], a);
+                float a = mstep2(b0, b0 + REC, false, lane, cx[0], 0.f); a = mstep2(b1, b1 + REC, false, lane, cx[1], a);
                 cs.slot_release(s0); cs.slot_release(s1);
-                a = g01_sum(a, lane);
+                a = g4_sum(a);
                 if (lane < 16) part[(16 * ti + lane) * NCONS + cw] = a;
             }
             {
                 int s2; const unsigned char* b2 = cs.slot_wait(cs.P + 8, 4 * REC_H, s2);
-                float a = 0.f;
-#pragma unroll
-                for (int i = 0; i < 4; i++) a = mstep(b2 + i * REC_H, true, lane, cx[i], a);
+                float a = mstep2(b2, b2 + REC_H, true, lane, cx[0], 0.f); a = mstep2(b2 + 2 * REC_H, b2 + 3 * REC_H, true, lane, cx[1], a);
                 cs.slot_release(s2);
-                a = g01_sum(a, lane);
+                a = g4_sum(a);
                 if (lane < 8) part[(64 + lane) * NCONS + cw] = a;
             }
             cs.P += W13_PK;
@@ -837,13 +878,23 @@ __device__ __forceinline__ void eng_consumer(const EngParams& p, EngCtl* c, unsi
         }
         if (op == EOP_W2) {
             // ================= w2: rows [96 j, +96) x the XCD group's 1152 columns: this wave's 3 K-steps (of 18) of 3 tiles (of 6) =================
-            RecR r2[9];      // this wave's 3 K-steps of its 3 tiles -> registers while the SwiGLU outputs of the XCD group are still being exchanged
-#pragma unroll
-            for (int i = 0; i < W2_PK; i++) {
-                int sl_; const unsigned char* bb = cs.slot_wait(cs.P + i, 3 * REC, sl_);
-#pragma unroll
-                for (int k = 0; k < 3; k++) r2[3 * i + k] = rec_read(bb + k * REC, false, lane);
-                cs.slot_release(sl_);
+            // this wave's 3 K-steps of its 3 tiles -> registers while the SwiGLU outputs of the XCD group are still being exchanged.  Nine steps = four pairs and a single
+            // one: K-steps (0, 1) of every tile (r2[0..2]); K-step 2 of tile 0 with K-step 2 of tile 1 (r2s: lane groups 0, 1 belong to tile 0's rows, groups 2, 3 to
+            // tile 1's); K-step 2 of tile 2 alone (r2l)
+            static_assert(W2_PK == 3, "w2's pairing is written out for three tiles of three K-steps per wave");
+            RecP r2[3], r2s; RecR r2l;
+            {
+                int s0, s1, s2;
+                const unsigned char* b0 = cs.slot_wait(cs.P, 3 * REC, s0);
+                r2[0] = rec_read2(b0, b0 + REC, false, lane);
+                const unsigned char* b1 = cs.slot_wait(cs.P + 1, 3 * REC, s1);
+                r2[1] = rec_read2(b1, b1 + REC, false, lane);
+                r2s = rec_read2(b0 + 2 * REC, b1 + 2 * REC, false, lane);
+                cs.slot_release(s0); cs.slot_release(s1);
+                const unsigned char* b2 = cs.slot_wait(cs.P + 2, 3 * REC, s2);
+                r2[2] = rec_read2(b2, b2 + REC, false, lane);
+                r2l = rec_read_lo(b2 + 2 * REC, lane);
+                cs.slot_release(s2);
             }
             wait_ge(&c->xa_flag, (unsigned)l + 1u, c, p.err, ERR_STAGE);
             if (T) tl(7);
@@ -853,14 +904,19 @@ __device__ __forceinline__ void eng_consumer(const EngParams& p, EngCtl* c, unsi
                 const float v[4] = {v4.x, v4.y, v4.z, v4.w};
                 to_digits(v, lane, xs + (8 * cw + (lane >> 3)) * 128, binfo + 8 * cw + (lane >> 3));
             }
-            StepCtx cx[3];
+            const PairCtx cxp = load_ctx2(xs, binfo, 8 * cw, 8 * cw + 2, lane), cxs = load_ctx2(xs, binfo, 8 * cw + 4, 8 * cw + 4, lane);      // K-steps (0, 1); K-step 2 in both row halves
+            {
+                const float m = mstep2(r2s, cxs, 0.f);      // lane groups 0, 1: tile 0's K-step 2; groups 2, 3: tile 1's
+                float a[3];
+                a[0] = mstep2(r2[0], cxp, lane < 32 ? m : 0.f);
+                a[1] = mstep2(r2[1], cxp, lane < 32 ? 0.f : m);
+                a[2] = mstep2(r2[2], cxp, 0.f);
+                a[2] = mstep(r2l, StepCtx{cxs.Alo, cxs.m8sx, cxs.sxinv}, a[2]);
 #pragma unroll
-            for (int i = 0; i < 3; i++) cx[i] = load_ctx(xs, binfo, 8 * cw + 2 * i, lane);
-#pragma unroll
-            for (int i = 0; i < W2_PK; i++) {
-                float a = mstep(r2[3 * i], cx[0], 0.f); a = mstep(r2[3 * i + 1], cx[1], a); a = mstep(r2[3 * i + 2], cx[2], a);
-                a = g01_sum(a, lane);
-                if (lane < 16) part2[(16 * (3 * tg + i) + lane) * 6 + ksl] = a;
+                for (int i = 0; i < W2_PK; i++) {
+                    const float t = g4_sum(a[i]);
+                    if (lane < 16) part2[(16 * (3 * tg + i) + lane) * 6 + ksl] = t;
+                }
             }
             cs.P += W2_PK;
             cs.cbarrier();
