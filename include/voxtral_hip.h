@@ -444,7 +444,9 @@ int32_t vox_debug_reload_knobs(void);
  * PAGED DECODER CACHE below).  [13] ring single-query decode (vox_debug_attn_decode_ring below): 0 unless a ring launch ran.  [14] paged single-query decode on a RING page table, [15] paged batched
  * GQA decode on one (an endless paged group's step, ENDLESS PAGED GROUPS below; vox_debug_attn_decode_paged_ring): such a launch counts here and not in [11] [12].
  * [16] paged single-query decode on a bf16 pool, [17] paged batched GQA decode on one, [18] [19] their ring-table forms (a bf16 paged group's step, A BF16 K/V POOL
- * below; vox_debug_attn_decode_paged_bf16): a bf16 launch counts there and never in [11] [12] [14] [15].  Entries past [19] are written as 0. */
+ * below; vox_debug_attn_decode_paged_bf16): a bf16 launch counts there and never in [11] [12] [14] [15].  [20] the key-split decode attention's split launch, [21] its merge launch
+ * (KEY-SPLIT DECODE ATTENTION below; vox_debug_attn_decode_split): every layout counts there and in no slot above; both stay 0 in a process that never turns the
+ * feature on.  Entries past [21] are written as 0. */
 int32_t vox_debug_attn_launches(uint64_t* out, int32_t cap);
 /* One decode attention launch on its own (tests): one query row per sequence against a decoder cache, through the launcher and with the parameters of the batched decode
  * steps -- exactly ONE launch; which kernel ran is the launcher's choice and is read from vox_debug_attn_launches ([3] [4] [5] slab, [11] [12] paged).
@@ -492,6 +494,13 @@ int32_t vox_debug_attn_decode_paged_ring(vox_ctx* ctx, const vox_attn_decode_des
  * the output has the bits of vox_debug_attn_decode / _paged_ring on the same pages holding the widened f32 values.  Exactly ONE launch, counted in
  * vox_debug_attn_launches [16] (per-head) / [17] (GQA), on a ring table [18] / [19], in no other slot.  Every argument is checked before the context is bound. */
 int32_t vox_debug_attn_decode_paged_bf16(vox_ctx* ctx, const vox_attn_decode_desc* desc, int32_t page_tab_len, const float* q, const uint16_t* k_bf16, const uint16_t* v_bf16, void* out);
+/* One KEY-SPLIT decode attention on its own (tests): exactly one split launch ([20]) and one merge launch ([21]), no other.  layout 0: flat slices -- the descriptor,
+ * host layouts and checks of vox_debug_attn_decode's slab call; layout 1: ring slices -- vox_debug_attn_decode_ring's; layout 2: paged -- vox_debug_attn_decode's paged
+ * call, with page_tab_len > 0 a ring table under vox_debug_attn_decode_paged_ring's conditions and kv_dtype VOX_KV_BF16 uint16_t pools as vox_debug_attn_decode_paged_bf16
+ * (page_tab_len must be 0 and kv_dtype VOX_KV_F32 for layouts 0 and 1; VOX_KV_F32 / VOX_KV_BF16 are defined below).  desc->out_xf selects the XF planes, from every layout;
+ * prefer_gqa, spec and no_xcd_remap must be 0; n_heads must be 1, 2 or 4 times n_kv_heads.  The output is a function of (q, the visible rows' values, pos, window)
+ * alone: the layouts give the same bits, a bf16 pool those of its widened values; against the plain kernels it differs in rounding (another reduction order). */
+int32_t vox_debug_attn_decode_split(vox_ctx* ctx, const vox_attn_decode_desc* desc, int32_t layout, int32_t page_tab_len, int32_t kv_dtype, const float* q, const void* k, const void* v, void* out);
 /* RoPE rows on their own (tests; host arithmetic, no device): rows first_pos .. first_pos + n - 1 (positions below 2^24) of the tables the kernels read, cos_out /
  * sin_out [n][head_dim / 2], and in inv_out [head_dim / 2] the f32 factors 1 / theta^(2 j / head_dim) they were made from.  The ONE function that produces RoPE rows:
  * the load-time tables and the streaming encoder's table are filled by it.  head_dim 128 is the decoder's geometry, whose load-time table has 16 384 rows; any other
@@ -756,6 +765,18 @@ int32_t vox_stream_schedule_rate(size_t n_samples, uint32_t sample_rate, int32_t
  * runner_up = -1 and its id.  Steps a decode-engine hand-off timeout takes back are scored again from the re-run's logits. */
 int32_t vox_stream_set_scores(vox_stream* s, int32_t on);
 int32_t vox_stream_scores(const vox_stream* s, int32_t first_id, int32_t n, vox_token_score* out);
+/* KEY-SPLIT DECODE ATTENTION (opt-in; off by default everywhere).  The plain single-query decode attention starts one workgroup per (head, sequence) and walks the
+ * session's whole window in it; the key-split form starts one per (KV head, sequence, chunk of 256 logical cache rows) and merges the chunks' partial records {maximum,
+ * sum of exponentials, unnormalised output} in a second launch: out = (sum_c o_c exp(m_c - M)) / (sum_c l_c exp(m_c - M)), M = max_c m_c, chunks ascending.  Its
+ * parallelism grows with the position and its LDS does not depend on the cache length.  vox_stream_set_attn_split: on = 0 / 1, callable between calls, takes effect with
+ * the next push / finish; the cache is untouched -- only which attention the PER-OPERATOR decode step launches changes (flat cache: split + merge + the wo GEMV in place
+ * of the fused attention + wo launch; an endless session's ring: split + merge in place of the ring attention).  While the decode engine serves the session (a cache of up
+ * to 1024 rows) nothing changes.  The first on = 1 allocates the workspace (counted in vox_stream_info [5] from then on, freed with the stream).  The flag survives
+ * vox_stream_reset; it is NOT part of a session blob (vox_stream_snapshot): a restored session has the flag of the stream it was restored into.  Ids: the plain
+ * session's up to near-ties -- the reduction order differs, exactly as a group's ids relate to a solo stream's.  With the flag off a session runs the launches,
+ * allocations and bits it ran before the feature existed.  vox_stream_attn_split: the flag. */
+int32_t vox_stream_set_attn_split(vox_stream* s, int32_t on);
+int32_t vox_stream_attn_split(const vox_stream* s);
 /* PEEK.  vox_stream_peek returns the ids vox_stream_finish would return now -- vox_stream_peek_ids of them: vox_stream_schedule_rate(samples pushed, rate, finished = 1)
  * minus the ids handed out -- and leaves the stream what it was, bit for bit: the ids and logits of every later call, the decoder cache's size and engine binding,
  * vox_stream_info [0..4], [6], [7].  It takes no samples: push first, then peek; it may be repeated, and followed by a push, a finish or a reset alike.  The stream runs
@@ -824,7 +845,7 @@ int32_t vox_debug_stream_front_tap_fetch(vox_stream* s, float* out_mel, float* o
  *   The header holds: magic, format version (VOX_SNAPSHOT_VERSION), total bytes; a model fingerprint and a hash of the bits of the session's t_embed; gain, sample
  *   rate, samples pushed and the other feed counters a later call depends on; D and E; the ids handed out, the scores flag and the alternatives k; the token at
  *   position D; the model geometry the K / V sections are laid out by; offset and length of every section.  Byte order and float format are the writing machine's.
- *   NOT in the blob (rebuilt, or simply absent after a restore): test taps, the peek save area, the decode engine's binding, RoPE rings, staging buffers, the kept
+ *   NOT in the blob (rebuilt, or simply absent after a restore): the key-split attention flag (vox_stream_set_attn_split: the restoring stream's own holds), test taps, the peek save area, the decode engine's binding, RoPE rings, staging buffers, the kept
  *   adapter rows (a snapshot is taken at a verification point), K / V rows outside the windows.  Two snapshots of an untouched session are byte-identical.
  *   The model fingerprint covers the vox_model_cfg words, the byte count of the weights as parsed from the file and a 64-bit hash of a few KB of them (read back once
  *   per model, at its first snapshot or restore).  It is there to stop a blob from going into the WRONG MODEL BY MISTAKE; it proves nothing about integrity, and a blob
@@ -937,6 +958,13 @@ int32_t vox_stream_group_free(vox_stream_group* g);
  * slots, and only while some member has scores on; the member's records are counted in vox_stream_group_info [5] */
 int32_t vox_stream_group_set_scores(vox_stream_group* g, int32_t member, int32_t on);
 int32_t vox_stream_group_scores(const vox_stream_group* g, int32_t member, int32_t first_id, int32_t n, vox_token_score* out);
+/* KEY-SPLIT DECODE ATTENTION (above) for a group, one flag for all members: while on, the decode round of every kind of group -- slab, paged, endless paged, bf16 pool,
+ * a burst group's decode rounds -- launches split + merge in place of its layout's plain attention; the XF planes go to the wo GEMM as before.  The first on allocates
+ * the workspace (16 rows x the most chunks a member can come to; every member's vox_stream_group_info [5] carries its share from then on).  Survives resets; not part of
+ * a group blob.  A split group's ids are the plain group's up to near-ties.  The slab GQA limit (SLAB LIMIT) is still enforced when a slab group is created, whatever
+ * the flag will be: lifting it needs a create-time argument (paged groups have no such limit). */
+int32_t vox_stream_group_set_attn_split(vox_stream_group* g, int32_t on);
+int32_t vox_stream_group_attn_split(const vox_stream_group* g);
 /* vox_stream_peek (PEEK above) for any subset of the members in one call: every entry names a member, out_ids and cap and gets n_ids; its n_samples and finish must be 0.
  * The entries' ids are those vox_stream_group_advance would hand the same members finishing now, and the group -- the peeked members and the others -- stays what it
  * was.  One ring save and one restore launch for all entries, one synchronisation, as advance.  Refusals are advance's for finishing entries (and samples or a finish

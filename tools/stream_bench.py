@@ -30,6 +30,7 @@
    all three groups are warmed alike and run one timed pass per loop: pass i of each covers the same positions (the rate groups' to within one tick).
  * --levels: what levels cost (vox_stream_set_levels: one more launch per tick or round, 10 KB of samples read per member), measured as --scores measures scores: twins
    with levels on, pass i behind pass i of the plain session.  Combines with --scores and --alternatives.
+ * --attn-split: the key-split decode attention (set_attn_split) as a twin, measured as --scores measures scores: pass i behind pass i of the plain session.
  * --scores: what scores cost (vox_stream_set_scores: one more launch per tick, one logits row written and read per session).  A second solo stream -- with --group
    also a second group -- runs with scores on, warmed like the first and timed the same way in the same loop: pass i of the scored session follows pass i of the
    unscored one and covers the same positions.  The unscored figures are the tool's usual ones (comparable with a run without the flag); the difference is reported.
@@ -121,6 +122,8 @@ def launch_counts(pkg):
 def twin_kinds(a):
     """--scores / --alternatives K / --levels: (what is on, how a solo stream turns it on, how a group member does)."""
     kinds = []
+    if a.attn_split:      # (a group's flag is one for all members: setting it per member again changes nothing)
+        kinds.append(("attn split on", lambda st: st.set_attn_split(True), lambda g, k: g.set_attn_split(True)))
     if a.levels:
         kinds.append(("levels on", lambda st: st.set_levels(True), lambda g, k: g.set_levels(k, True)))
     if a.scores:
@@ -132,6 +135,8 @@ def twin_kinds(a):
 
 def twin_recorded(what, st):
     """Every id of the timed twin got its record."""
+    if what.startswith("attn split"):
+        return st.attn_split()
     if what.startswith("levels"):      # (the ids of the warm-up push included: the twin had levels on from its first tick)
         return not np.isnan(st.levels()["peak"]).any()
     return not np.isnan(st.scores()["logprob"]).any() if what.startswith("scores") else not np.isnan(st.alternatives()["entropy"]).any()
@@ -502,6 +507,8 @@ def main():
     ap.add_argument("--group", help="N[,N...]: measure stream-group rounds of these widths next to the solo tick instead of the solo tick and its baseline")
     ap.add_argument("--rate", type=int, default=0, metavar="SR", help="with --group: also time a group whose members are all fed at SR Hz, next to the 16 kHz f32 round")
     ap.add_argument("--s16", action="store_true", help="with --rate: feed that group 16-bit PCM")
+    ap.add_argument("--attn-split", action="store_true", help="also time a stream (with --group: and a group) with the key-split decode attention on "
+                    "(set_attn_split), pass by pass next to the plain one, as --scores does; a solo stream runs it on its per-operator steps alone (past 1024 cache rows)")
     ap.add_argument("--scores", action="store_true", help="also time a stream (with --group: and a group) with scores on, pass by pass next to the unscored one")
     ap.add_argument("--alternatives", type=int, default=0, metavar="K", help="also time a stream (with --group: and a group) with alternatives on at k = K (1..8), as --scores does")
     ap.add_argument("--levels", action="store_true", help="also time a stream (with --group: and a group) with levels on (vox_stream_set_levels: one more launch per tick, in front of the "

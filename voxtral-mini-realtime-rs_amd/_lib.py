@@ -177,6 +177,7 @@ SIGNATURES = {
     "vox_debug_attn_decode": (i32, [vp, vp, vp, vp, vp, vp]),
     "vox_debug_attn_decode_ring": (i32, [vp, vp, vp, vp, vp, vp]),
     "vox_debug_attn_decode_paged_ring": (i32, [vp, vp, i32, vp, vp, vp, vp]),      # a paged launch on a ring page table of page_tab_len entries
+    "vox_debug_attn_decode_split": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),      # the key-split pair on any layout: layout, page_tab_len, kv_dtype
     "vox_debug_attn_decode_paged_bf16": (i32, [vp, vp, i32, vp, vp, vp, vp]),      # the paged launch (flat table: page_tab_len 0) on uint16_t pools
     "vox_debug_rope_rows": (i32, [i32, C.c_float, C.c_int64, i32, vp, vp, vp]),
     "vox_debug_stream_attn": (i32, [vp, vp, vp, vp, vp, vp]),      # (ctx, vox_stream_attn_desc, qkv, kring, vring, out): ONE launch of the streams' ring attention
@@ -228,6 +229,8 @@ SIGNATURES = {
     "vox_debug_stream_feed_passes": (i32, [u32, P(sz), P(i32), i32, sz, P(i64), i32, P(i32)]),
     "vox_score_rows": (i32, [vp, vp, i32, i32, vp, vp, i32]),
     "vox_stream_set_scores": (i32, [vp, i32]),
+    "vox_stream_set_attn_split": (i32, [vp, i32]), "vox_stream_attn_split": (i32, [vp]),
+    "vox_stream_group_set_attn_split": (i32, [vp, i32]), "vox_stream_group_attn_split": (i32, [vp]),
     "vox_stream_scores": (i32, [vp, i32, i32, vp]),
     "vox_stream_group_set_scores": (i32, [vp, i32, i32]),
     "vox_stream_group_scores": (i32, [vp, i32, i32, i32, vp]),

@@ -132,8 +132,9 @@ class Endpoint:
 
 
 def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_rate=False, words_out=None, peek=False, alts_k=0, endless=False, suspend_every=0, burst=0, levels=False,
-                    endpoint_ms=0, endpoint_db=-50.0):
-    """--live: the file through a live session (vox_stream) in pieces of `chunk_ms` milliseconds, the text so far on stderr whenever ids arrive.  The gain is the
+                    endpoint_ms=0, endpoint_db=-50.0, attn_split=False):
+    """(attn_split, --live-attn-split: the session runs with the key-split decode attention on, vox_stream_set_attn_split.)
+    --live: the file through a live session (vox_stream) in pieces of `chunk_ms` milliseconds, the text so far on stderr whenever ids arrive.  The gain is the
     file's peak scale 0.95 / max|x| (bin/transcribe.rs:207; a file is known in advance -- a microphone caller passes its own), the whole file is one utterance (no
     --max-mel-frames chunks: the session's state is bounded by its ring), so the line equals the un-chunked path's.
     native_rate (--live-native-rate), for a file that is not at 16 kHz: the session is created for the file's rate and pushed the file's own samples -- what a capture
@@ -166,7 +167,7 @@ def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_
     gain = float(np.float32(0.95) / peak) if peak >= 1e-10 else 1.0              # audio/io.rs:59-68
     step = max(1, int(round(rate * chunk_ms / 1000.0)))
     def create():
-        st = model.create_stream(t_embed, gain=gain, sample_rate=rate, endless=endless, burst=burst or None)
+        st = model.create_stream(t_embed, gain=gain, sample_rate=rate, endless=endless, burst=burst or None, attn_split=attn_split)
         if words_out is not None:
             st.set_scores(True)
             if alts_k:
@@ -215,8 +216,9 @@ def parse_live_delays(text, n_members):
 
 
 def transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, chunk_ms, n_members, words_out=None, peek=False, alts_k=0, page_rows=None, pool_pages=None, endless=False,
-                          suspend_every=0, kv_dtype=None, delays=None, levels=False, endpoint_ms=0, endpoint_db=-50.0):
-    """(levels / endpoint_ms / endpoint_db: as transcribe_live's, per member -- the members whose trigger is due after a call share one group peek.)
+                          suspend_every=0, kv_dtype=None, delays=None, levels=False, endpoint_ms=0, endpoint_db=-50.0, attn_split=False):
+    """(attn_split, --live-attn-split: the group's decode rounds run the key-split decode attention, vox_stream_group_set_attn_split.)
+    (levels / endpoint_ms / endpoint_db: as transcribe_live's, per member -- the members whose trigger is due after a call share one group peek.)
     (delays, --live-delays: one delay per member -- the group is made by vox_stream_group_create_t_embeds, member k's files run at delays[k], and every --live-words
     line gains "delay"; None: every member at t_embed.)
     (kv_dtype, --live-kv f32 | bf16: the paged group's K/V pool dtype, vox_stream_group_create_kv; the lines have the same form.)
@@ -229,7 +231,7 @@ def transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, chunk_ms, 
     member is refused at 43 minutes); the lines are the same.  suspend_every (--live-suspend-every N): after every N calls each busy member is snapshotted to host
     memory, reset, and restored from its blob (vox_stream_group_snapshot / _restore); the lines are the same."""
     step = max(1, int(round(16000 * chunk_ms / 1000.0)))
-    group = model.create_stream_group(None if delays else t_embed, n_members, page_rows=page_rows, pool_pages=pool_pages, endless=endless, kv_dtype=kv_dtype, delays=delays)
+    group = model.create_stream_group(None if delays else t_embed, n_members, page_rows=page_rows, pool_pages=pool_pages, endless=endless, kv_dtype=kv_dtype, delays=delays, attn_split=attn_split)
     text = lambda ids: tokenizer.decode([t for t in ids if t >= 1000]).strip()
     texts = {}; busy = {}; nxt = 0; calls = 0      # busy: member -> [file index, samples, offset, ids]
     endpoints = {}      # member -> its file's Endpoint
@@ -449,6 +451,9 @@ def main(argv=None):
     ap.add_argument("--live-peek", action="store_true", help="with --live (also with --live-group, --live-native-rate, --live-words): after every push a line starting with "
                     "'  ~[' on stderr: the text so far plus the tentative tail, i.e. the line if the file ended here (vox_stream_peek); stdout, the '  [' lines and the "
                     "words file do not change")
+    ap.add_argument("--live-attn-split", action="store_true", help="with --live (also with --live-group): run the sessions with the key-split decode attention "
+                    "(vox_stream_set_attn_split / vox_stream_group_set_attn_split): the decode attention's work is split over the keys, for long sessions; the text is the "
+                    "plain session's up to near-ties")
     ap.add_argument("--live-levels", action="store_true", help="with --live (also with --live-group): run the sessions with levels on (vox_stream_set_levels): every "
                     "--live-words line also carries peak_db and rms_db, the level of the audio the model had just heard while it chose the word's ids")
     ap.add_argument("--live-endpoint-ms", type=int, default=None, metavar="MS", help="with --live (implies --live-levels): the end-of-speech hint -- after a push whose quiet time "
@@ -483,6 +488,8 @@ def main(argv=None):
     a.live_alternatives = a.live_alternatives or 0
     if a.live_endpoint_ms is not None and (not a.live or a.live_endpoint_ms <= 0):
         ap.error("--live-endpoint-ms MS (MS > 0) applies with --live")
+    if a.live_attn_split and not a.live:
+        ap.error("--live-attn-split applies with --live")
     if a.live_levels and not a.live:
         ap.error("--live-levels applies with --live")
     a.live_endpoint_ms = a.live_endpoint_ms or 0
@@ -612,7 +619,7 @@ def main(argv=None):
                         write_word_lines(rec_out, runner.words.get((i, k), []))
     if a.live_group:
         try:
-            texts = transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_group, words_out, a.live_peek, a.live_alternatives, a.live_page_rows, a.live_pool_pages, a.live_endless, a.live_suspend_every, a.live_kv, a.live_delays, a.live_levels, a.live_endpoint_ms, a.live_endpoint_db)
+            texts = transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_group, words_out, a.live_peek, a.live_alternatives, a.live_page_rows, a.live_pool_pages, a.live_endless, a.live_suspend_every, a.live_kv, a.live_delays, a.live_levels, a.live_endpoint_ms, a.live_endpoint_db, a.live_attn_split)
         except Exception as e:      # the files fall back to one live session each
             log(f"Error in the stream group: {e}"); texts = {}
             if words_out is not None:      # the files' words come again with their lines
@@ -624,7 +631,7 @@ def main(argv=None):
         p = paths[i]
         try:
             t1 = time.time()
-            text = transcribe_live(pkg, p, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_native_rate, words_out, a.live_peek, a.live_alternatives, a.live_endless, a.live_suspend_every, a.live_burst, a.live_levels, a.live_endpoint_ms, a.live_endpoint_db) if a.live else transcribe_one(pkg, p, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed, rec_out, a.alternatives or 0)
+            text = transcribe_live(pkg, p, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_native_rate, words_out, a.live_peek, a.live_alternatives, a.live_endless, a.live_suspend_every, a.live_burst, a.live_levels, a.live_endpoint_ms, a.live_endpoint_db, a.live_attn_split) if a.live else transcribe_one(pkg, p, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed, rec_out, a.alternatives or 0)
             log(f"{p}: {time.time() - t1:.3f}s")
         except Exception as e:      # per-utterance failure isolates to that line (empty), eval_wer.py:211-223 tolerates it
             log(f"Error transcribing {p}: {e}"); text = ""; rc = 1

@@ -482,7 +482,8 @@ static int32_t wo_acc_clear(vox_model* m, hipStream_t s) { if (m->d_wo_acc) HIPC
 // ring (an endless session's step from its wrap on): the cache is a RING of kc->max_seq rows -- the q|k|v GEMV appends at row position % max_seq and reads its RoPE row
 // from the session's ring (EPI_ROPE_KV_RING), the per-head ring attention follows, then the wo GEMV: the fused attention + wo launch has no ring form
 struct DecRingStep { const float* rope; int mask; };      // the session's decoder RoPE ring [mask + 1][cos hd/2 | sin hd/2]
-static int32_t decoder_step_dev(vox_model* m, float* h, vox_cache* kc, const int* pos_ptr, int pos_off, const DecRingStep* ring = nullptr) {
+// split_ws (a live session with vox_stream_set_attn_split on): the attention is the key-split pair (launch_attn_decode_split, flat or ring rows) + the wo GEMV
+static int32_t decoder_step_dev(vox_model* m, float* h, vox_cache* kc, const int* pos_ptr, int pos_off, const DecRingStep* ring = nullptr, float* split_ws = nullptr) {
     const vox_model_cfg& c = m->cfg; hipStream_t s = m->ctx->stream;
     const int D = c.dec_dim, H = c.dec_heads, KV = c.dec_kv_heads, hd = c.dec_head_dim, QD = H * hd, KD = KV * hd, F = c.dec_ffn;
     const size_t lf = kc->layer_stride;
@@ -500,7 +501,7 @@ static int32_t decoder_step_dev(vox_model* m, float* h, vox_cache* kc, const int
             // four launches per layer: attention + wo in one (32-way K split, one partial product per head, combined with int64 fixed-point atomics);
             // w1|w3's prologue adds the sum to the residual and writes the new residual stream (d_h2) for w2's epilogue
             const int R13 = q4_gemv_default_R(L.w13.w.N, L.w13.w.K, EPI_SWIGLU);
-            if (!ring && decode_layer_fuses_attn_wo(m, L, ap, kc) && h != m->d_h2) {
+            if (!ring && !split_ws && decode_layer_fuses_attn_wo(m, L, ap, kc) && h != m->d_h2) {
                 long long* acc = m->d_wo_acc + (size_t)l * D;      // zero on entry: cleared at allocation, and by w2 below after every use
                 HIPCHK(launch_attn_wo(ap, L.wo.w, acc, kc->max_seq, s));
                 GemvParams f{}; f.w = L.w13.w; f.x = h; f.x_stride = D; f.out = m->d_act; f.out_stride = F; f.gamma = L.ffn_norm; f.mul = L.ada_mul; f.eps = c.norm_eps;
@@ -511,6 +512,7 @@ static int32_t decoder_step_dev(vox_model* m, float* h, vox_cache* kc, const int
                 HIPCHK(launch_q4_gemv(d, 1, PRO_NONE, EPI_RESID, q4_gemv_default_R(d.w.N, d.w.K, EPI_RESID), s));
                 continue;
             }
+            if (split_ws) HIPCHK(launch_attn_decode_split(ap, hd, ring ? ATTN_SPLIT_RING : ATTN_SPLIT_FLAT, split_ws, s)); else
             HIPCHK(ring ? launch_attn_decode_ring(ap, hd, kc->max_seq, s) : launch_attn_decode(ap, hd, kc->max_seq, s));
         }
         GemvParams o{}; o.w = L.wo.w; o.x = m->d_att; o.x_stride = QD; o.out = h; o.out_stride = D; o.resid = h; o.resid_stride = D;
@@ -1218,7 +1220,8 @@ extern "C" int32_t vox_debug_attn_gqa_max_seq(vox_ctx* c, int32_t* out) {
 // ring: vox_debug_attn_decode_ring -- the slab call's buffers with the cache slices used as rings of max_seq rows (launch_attn_decode_ring)
 // tab_len > 0: vox_debug_attn_decode_paged_ring -- the paged call with every table row used as a ring of tab_len entries (AttnParams::page_tab_len), positions to 2^24 - 1
 // bf16: vox_debug_attn_decode_paged_bf16 -- the paged call (flat or ring table) on uint16_t pools of the same layout (AttnParams::kv_bf16)
-static int32_t attn_decode_debug(vox_ctx* c, const vox_attn_decode_desc* d, const float* q, const void* k, const void* v, void* out, bool ring, int tab_len = 0, bool bf16 = false) {
+// split: vox_debug_attn_decode_split -- any of the above layouts through launch_attn_decode_split (one split and one merge launch); XF planes from every layout
+static int32_t attn_decode_debug(vox_ctx* c, const vox_attn_decode_desc* d, const float* q, const void* k, const void* v, void* out, bool ring, int tab_len = 0, bool bf16 = false, bool split = false) {
     ARGCHK(c && d && q && k && v && out, "null argument"); ARGCHK(d->pos, "null argument (pos)");
     ARGCHK(d->head_dim == 128, "head_dim %d: the decoder's decode attention serves head_dim 128 alone", d->head_dim);
     ARGCHK(d->n_seq >= 1 && d->n_seq <= 4096, "n_seq %d out of range (1..4096)", d->n_seq);
@@ -1232,7 +1235,7 @@ static int32_t attn_decode_debug(vox_ctx* c, const vox_attn_decode_desc* d, cons
     if (ring) {
         ARGCHK(d->max_seq >= 1 && d->max_seq <= 16384, "max_seq %d (the ring capacity) out of range (1..16384)", d->max_seq);
         ARGCHK(!paged && !d->pool_pages && !d->page_tab && !d->page_tab_stride && !d->score_rows, "a ring call takes no paged field");
-        ARGCHK(!d->prefer_gqa && !d->spec && !d->out_xf, "the ring form is the per-head kernel writing f32 rows: prefer_gqa, spec and out_xf must be 0");
+        ARGCHK(split || (!d->prefer_gqa && !d->spec && !d->out_xf), "the ring form is the per-head kernel writing f32 rows: prefer_gqa, spec and out_xf must be 0");
         ARGCHK(d->window >= 0 && d->window + 1 <= d->max_seq, "window %d: a ring of %d rows serves windows 0..%d", d->window, d->max_seq, d->max_seq - 1);
         for (int i = 0; i < n; i++) ARGCHK(d->pos[i] >= 0 && d->pos[i] < (1 << 24), "pos[%d] = %d outside 0..2^24 - 1", i, d->pos[i]);
     } else if (!paged) {
@@ -1265,6 +1268,10 @@ static int32_t attn_decode_debug(vox_ctx* c, const vox_attn_decode_desc* d, cons
             }
         }
     }
+    if (split) {
+        ARGCHK(!d->prefer_gqa && !d->spec && !d->no_xcd_remap, "the key-split form has one kernel per layout: prefer_gqa, spec and no_xcd_remap must be 0");
+        ARGCHK(H == KV || H == 2 * KV || H == 4 * KV, "the key-split form serves 1, 2 or 4 query heads per KV head (%d over %d)", H, KV);
+    }
     VOXCHK(ctx_bind(c));
     if (!paged && d->prefer_gqa && attn_decode_takes_gqa(hd, H, KV)) {      // (the one check that needs the device: the kernel's attributes)
         int most = 0; HIPCHK(attn_decode_gqa_max_seq(&most));
@@ -1273,7 +1280,9 @@ static int32_t attn_decode_debug(vox_ctx* c, const vox_attn_decode_desc* d, cons
     hipStream_t s = c->stream;
     const size_t slice_f = paged ? (size_t)KV * d->page_rows * hd : (size_t)KV * d->max_seq * hd, kv_f = slice_f * (paged ? d->pool_pages : d->n_slices);
     const int n_grp = (n + 15) / 16; const size_t xf_b = xf_bytes(QD);
-    DevBuf dq, dk, dv, dout, dxf, dint;
+    DevBuf dq, dk, dv, dout, dxf, dint, dws;
+    const size_t ws_b = split ? attn_split_ws_floats(n, H, hd, attn_split_chunks(paged ? d->score_rows : d->max_seq, d->window)) * 4 : 0;
+    if (split) { HIPCHK(dws.alloc(ws_b)); HIPCHK(hipMemsetAsync(dws.p, 0xff, ws_b, c->stream)); }      // a record no workgroup wrote is NaN
     const size_t tab_n = paged ? (size_t)d->n_slices * d->page_tab_stride : 0;
     const size_t kv_b = kv_f * (bf16 ? 2 : 4);
     HIPCHK(dq.alloc((size_t)n * W * 4)); HIPCHK(dk.alloc(kv_b)); HIPCHK(dv.alloc(kv_b)); HIPCHK(dout.alloc((size_t)n * QD * 4)); HIPCHK(dxf.alloc(xf_b * n_grp));
@@ -1294,8 +1303,10 @@ static int32_t attn_decode_debug(vox_ctx* c, const vox_attn_decode_desc* d, cons
     if (paged) {
         ap.kv_head_stride = (hd << shift); ap.page_tab = d_tab; ap.page_tab_stride = d->page_tab_stride; ap.page_shift = shift; ap.page_floats = (long)slice_f; ap.score_rows = d->score_rows;
         ap.page_tab_len = tab_len; ap.kv_bf16 = bf16 ? 1 : 0;
+        if (split) HIPCHK(launch_attn_decode_split(ap, hd, ATTN_SPLIT_PAGED, dws.as<float>(), s, n)); else
         HIPCHK(launch_attn_decode_paged(ap, hd, s, n));
-    } else if (ring) HIPCHK(launch_attn_decode_ring(ap, hd, d->max_seq, s, n));
+    } else if (split) HIPCHK(launch_attn_decode_split(ap, hd, ring ? ATTN_SPLIT_RING : ATTN_SPLIT_FLAT, dws.as<float>(), s, n));
+    else if (ring) HIPCHK(launch_attn_decode_ring(ap, hd, d->max_seq, s, n));
     else HIPCHK(launch_attn_decode(ap, hd, d->max_seq, s, n));
     if (d->out_xf) HIPCHK(hipMemcpyAsync(out, dxf.p, xf_b * n_grp, hipMemcpyDeviceToHost, s));
     else HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)n * QD * 4, hipMemcpyDeviceToHost, s));
@@ -1323,6 +1334,19 @@ extern "C" int32_t vox_debug_attn_decode_paged_bf16(vox_ctx* c, const vox_attn_d
                d->window / d->page_rows + 4);
     }
     return attn_decode_debug(c, d, q, k, v, out, false, page_tab_len, true);
+}
+extern "C" int32_t vox_debug_attn_decode_split(vox_ctx* c, const vox_attn_decode_desc* d, int32_t layout, int32_t page_tab_len, int32_t kv_dtype, const float* q, const void* k, const void* v, void* out) {
+    ARGCHK(d, "null argument"); ARGCHK(layout >= 0 && layout <= 2, "layout %d (0: flat slices, 1: ring slices, 2: paged)", layout);
+    ARGCHK((layout == 2) == (d->page_rows != 0), "layout %d with page_rows %d: a paged call, and no other, names its page size", layout, d->page_rows);
+    ARGCHK(kv_dtype == VOX_KV_F32 || (kv_dtype == VOX_KV_BF16 && layout == 2), "kv_dtype %d: VOX_KV_F32, or VOX_KV_BF16 on a paged call", kv_dtype);
+    ARGCHK(layout == 2 ? page_tab_len >= 0 && page_tab_len <= 1024 : page_tab_len == 0, "page_tab_len %d (a paged call's: 0 a flat table, 1..1024 a ring table)", page_tab_len);
+    if (layout == 2 && page_tab_len) {      // (the ring-table conditions of vox_debug_attn_decode_paged_ring / _paged_bf16)
+        ARGCHK(d->page_rows >= 16 && d->page_rows <= 1024 && !(d->page_rows & (d->page_rows - 1)), "page_rows %d is not a power of two in 16..1024", d->page_rows);
+        ARGCHK(d->window >= 0, "a ring table needs a sliding window (window %d)", d->window);
+        ARGCHK(page_tab_len >= d->window / d->page_rows + 4, "page_tab_len %d: a window of %d in pages of %d rows needs a ring table of at least %d entries", page_tab_len, d->window, d->page_rows,
+               d->window / d->page_rows + 4);
+    }
+    return attn_decode_debug(c, d, q, k, v, out, layout == 1, page_tab_len, kv_dtype == VOX_KV_BF16, true);
 }
 // ---- one launch of the live sessions' encoder ring attention on host buffers (tests): the StreamAttnParams of stream_encode_round -- StreamMember descriptors on the
 // device with state[STRM_ENC_POS], kring and vring alone filled in, the order array, the caller's q|k|v rows, the RoPE rows as a flat table (the model's streaming
@@ -1515,6 +1539,9 @@ struct XfBufs {
     // a stream group with a delay per member: ada_rows [member][dec_layers][dec_dim] every member's Ada scales (ada_stride floats per member), ada_order the rows' members --
     // the wo GEMM's epilogue multiplies row r by member ada_order[r]'s scales (EPI_RESID_XF_ROWS).  null everywhere else: the model's one set, per column
     const float* ada_rows; const int* ada_order; long ada_stride;
+    // a stream group with vox_stream_group_set_attn_split on: the key-split attention's workspace -- the chain launches launch_attn_decode_split in place of the
+    // plain attention of its layout.  null everywhere else
+    float* split_ws;
 };
 // the XF planes and ssq blocks of a step over n_grp groups (0: none, the group strides alone): from the pool, zeroed on s, bound to b
 struct XfPlanes {
@@ -1543,6 +1570,7 @@ static int32_t xf_chain(const vox_model* m, const XfBufs& b, int g0i, int ng, in
     ARGCHK(!(b.page_tab && mtw), "internal: a paged cache runs the one-group chain (the wide step has no paged form)");
     ARGCHK(!b.kv_bf16 || b.page_tab, "internal: a bf16 K/V pool is a paged cache's");
     ARGCHK(!b.ada_rows || (!mtw && b.ada_order), "internal: Ada scales per row run the one-group chain, with the rows' members");
+    ARGCHK(!b.split_ws || !mtw, "internal: the key-split attention runs the one-group chain");
     const int r0 = g0i * 16;      // the chain's first group: its planes, sums, rows, positions and cache slices (a wide chain's further groups follow at the group strides)
     uint16_t* xf1 = b.xf1 + (size_t)g0i * b.xf1_gs; uint16_t* xf2 = b.xf2 + (size_t)g0i * b.xf2_gs; uint16_t* xf3 = b.xf3 + (size_t)g0i * b.xf3_gs; float* ssq = b.ssq + (size_t)g0i * b.ssq_gs;
     float* hg = b.h + (size_t)r0 * D; float* qg = b.qkv + (size_t)r0 * W; const int* pg = b.pos + r0; const int* rg = b.kv_row ? b.kv_row + r0 : nullptr;
@@ -1569,8 +1597,10 @@ static int32_t xf_chain(const vox_model* m, const XfBufs& b, int g0i, int ng, in
         if (b.page_tab) {
             ap.kv_head_stride = (hd << b.page_shift); ap.page_tab = b.page_tab; ap.page_tab_stride = b.page_tab_stride; ap.page_shift = b.page_shift; ap.page_floats = b.page_floats;
             ap.score_rows = b.score_rows; ap.page_tab_len = b.page_tab_len; ap.kv_bf16 = b.kv_bf16;
+            if (b.split_ws) HIPCHK(launch_attn_decode_split(ap, hd, ATTN_SPLIT_PAGED, b.split_ws, sg, M)); else
             HIPCHK(launch_attn_decode_paged(ap, hd, sg, M));
-        } else
+        } else if (b.split_ws) HIPCHK(launch_attn_decode_split(ap, hd, ATTN_SPLIT_FLAT, b.split_ws, sg, M));
+        else
         HIPCHK(launch_attn_decode(ap, hd, max_seq, sg, M));
         { GemmParams g{}; xf_fill_resid_xf(g, hg, hg, D, xf1, L.ffn_norm, L.ada_mul, ssq);
           if (b.ada_rows) { g.xf_w2 = b.ada_rows + (size_t)l * D; g.xf_w2_row = b.ada_order; g.xf_w2_stride = b.ada_stride; }      // every row its member's scales
@@ -3257,6 +3287,9 @@ struct vox_stream {
     // (stream_burst); 1: every tick is stream_tick.  bursts / burst_ticks: the bursts run with b >= 2 and the ticks inside them; single_ticks: the ticks run one by one
     int burst = 1; uint64_t bursts = 0, burst_ticks = 0, single_ticks = 0;
     struct { float *dec = nullptr, *enc = nullptr, *h_dec = nullptr, *h_enc = nullptr; hipEvent_t copied = nullptr; bool pending = false; } rope;
+    // vox_stream_set_attn_split: while on, the per-operator decode step runs the key-split attention (flat rows, ring rows past the wrap) + the wo GEMV; the engine's
+    // steps are what they are.  split_ws: its workspace, for the most chunks the session's cache can come to (dec_limit rows), allocated at the first on
+    bool attn_split = false; float* split_ws = nullptr;
 };
 static const int STREAM_TAIL_TICKS = 63;            // the most ticks a finish / peek tail of an endless session may run (peek_max_ticks at the session's rate, asserted at create and in every peek)
 static const int STREAM_ROPE_DEC_ROWS = 1024;       // rows of an endless session's decoder RoPE ring = the most ticks of one pass; the encoder's ring has reshape_factor times as many
@@ -3354,7 +3387,7 @@ static void stream_release(vox_stream* st) {
     cache_release(st->dec);
     for (void* p : {(void*)st->kring, (void*)st->vring, (void*)st->samples, (void*)st->audio_keep, (void*)st->ws, (void*)st->tokens, (void*)st->state, (void*)st->tap, (void*)st->ftap_mel, (void*)st->ftap_conv,
                     (void*)st->feed.At, (void*)st->feed.in_ring, (void*)st->s16_stage, (void*)st->d_mem, (void*)st->sc.dev, (void*)st->score_row, (void*)st->al.dev, (void*)st->lv.dev,
-                    (void*)st->peek.keep.p, (void*)st->peek.old.k, (void*)st->peek.old.v, (void*)st->rope.dec, (void*)st->rope.enc}) if (p) (void)hipFree(p);
+                    (void*)st->peek.keep.p, (void*)st->peek.old.k, (void*)st->peek.old.v, (void*)st->rope.dec, (void*)st->rope.enc, (void*)st->split_ws}) if (p) (void)hipFree(p);
     if (st->rope.h_dec) (void)hipHostFree(st->rope.h_dec); if (st->rope.h_enc) (void)hipHostFree(st->rope.h_enc);
     if (st->rope.copied) (void)hipEventDestroy(st->rope.copied);
     binding_release(st->eng);
@@ -3495,7 +3528,7 @@ static int32_t stream_decode_step(vox_stream* st, float* h, float* logits_row, i
         st->eng_steps++; st->eng_unverified = true;
     } else {
         const DecRingStep rs{st->rope.dec, STREAM_ROPE_DEC_ROWS - 1};
-        VOXCHK(decoder_step_dev(m, h, kc, pos_word, 0, ring ? &rs : nullptr));
+        VOXCHK(decoder_step_dev(m, h, kc, pos_word, 0, ring ? &rs : nullptr, st->attn_split ? st->split_ws : nullptr));
         VOXCHK(lm_head_argmax_dev(m, h, logits_row));
         HIPCHK(launch_stream_advance(m->d_part_val, m->d_part_idx, m->n_parts, st->tokens, st->state, enc_rows, 4 * enc_rows, st->cap, s));
         st->op_steps++;
@@ -3883,6 +3916,25 @@ extern "C" int32_t vox_stream_set_scores(vox_stream* st, int32_t on) {
     sc.on = on != 0;
     return VOX_OK;
 }
+// the key-split attention on / off (the per-operator step's alone).  The first on allocates the workspace; the cache is untouched.  Behind a synchronisation, as above:
+// a step in flight keeps the form it was enqueued with
+static int32_t attn_split_ws_alloc(const vox_model_cfg& c, int n_seq, int rows, float** ws, uint64_t* bytes) {
+    const size_t b = attn_split_ws_floats(n_seq, c.dec_heads, c.dec_head_dim, attn_split_chunks(rows, c.dec_window)) * 4;
+    ARGCHK(attn_split_chunks(rows, c.dec_window) <= ATTN_SPLIT_MAX_CHUNKS, "the key-split attention serves caches of up to %d rows without a window", (ATTN_SPLIT_MAX_CHUNKS - 2) * ATTN_SPLIT_C);
+    if (hipMalloc((void**)ws, b) != hipSuccess) { (void)hipGetLastError(); *ws = nullptr; return fail(VOX_ERR_HIP, "hipMalloc of the key-split attention's %zu-byte workspace failed", b); }
+    *bytes += b;
+    return VOX_OK;
+}
+extern "C" int32_t vox_stream_set_attn_split(vox_stream* st, int32_t on) {
+    ARGCHK(st, "null stream"); ARGCHK(on == 0 || on == 1, "on must be 0 or 1"); VOXCHK(ctx_bind(st->ctx));
+    const vox_model_cfg& c = st->m->cfg; const int G = c.dec_heads / c.dec_kv_heads;
+    if (on && !(G == 1 || G == 2 || G == 4)) return fail(VOX_ERR_UNSUPPORTED, "the key-split attention serves 1, 2 or 4 query heads per KV head (this model: %d over %d)", c.dec_heads, c.dec_kv_heads);
+    HIPCHK(hipStreamSynchronize(st->ctx->stream));
+    if (on && !st->split_ws) VOXCHK(attn_split_ws_alloc(c, 1, st->dec_limit, &st->split_ws, &st->bytes));
+    st->attn_split = on != 0;
+    return VOX_OK;
+}
+extern "C" int32_t vox_stream_attn_split(const vox_stream* st) { return st && st->attn_split ? 1 : 0; }
 extern "C" int32_t vox_stream_scores(const vox_stream* st, int32_t first_id, int32_t n, vox_token_score* out) {
     ARGCHK(st, "null stream");
     return st->sc.read(st->feed.ids_out, first_id, n, out);
@@ -4375,6 +4427,9 @@ struct vox_stream_group {
     // to device when the member is seeded.  The decode round's wo epilogue reads row r's scales through the pass's order; a call never selects the model's t_embed.
     // Every other group: ada == nullptr, member_te empty, and the rounds read the model's one set
     float* ada = nullptr; std::vector<std::vector<float>> member_te;
+    // vox_stream_group_set_attn_split: while on, every decode round of the group (any kind) runs the key-split attention in place of its layout's plain launch.
+    // split_ws: the workspace for 16 rows and the most chunks a member can come to, allocated at the first on
+    bool attn_split = false; float* split_ws = nullptr;
 };
 static const std::vector<float>& group_t_embed(const vox_stream_group* g, int i) { return g->ada ? g->member_te[(size_t)i] : g->t_embed; }
 static const int GROUP_ROPE_ROWS = 64;         // rows per member of an endless group's decoder RoPE ring: a power of two >= the most ticks of one pass (feed_pass_max_ticks, asserted at create and per pass)
@@ -4469,7 +4524,7 @@ static void group_release(vox_stream_group* g) {
     if (g->rope.copied) (void)hipEventDestroy(g->rope.copied);
     for (size_t i = 0; i < g->mem.size(); i++) group_member_drop_rate(g, (int)i);
     for (void* p : {(void*)g->keep.p, (void*)g->d_ingest, (void*)g->s16_stage, (void*)g->kring, (void*)g->vring, (void*)g->dec_k, (void*)g->dec_v, (void*)g->samples, (void*)g->ws, (void*)g->tokens, (void*)g->state, (void*)g->d_mem, (void*)g->d_order,
-                    (void*)g->qkv, (void*)g->att, (void*)g->logits, (void*)g->ssq, (void*)g->xf1, (void*)g->xf2, (void*)g->xf3, (void*)g->d_tab, (void*)g->d_bdesc, (void*)g->ada}) if (p) (void)hipFree(p);
+                    (void*)g->qkv, (void*)g->att, (void*)g->logits, (void*)g->ssq, (void*)g->xf1, (void*)g->xf2, (void*)g->xf3, (void*)g->d_tab, (void*)g->d_bdesc, (void*)g->ada, (void*)g->split_ws}) if (p) (void)hipFree(p);
     delete g;
 }
 // page_rows < 0: a slab group (pool_pages unread); else a paged one (0: the default page / the default pool)
@@ -4708,6 +4763,7 @@ static int32_t group_decode_round(vox_stream_group* g, const StreamWs& w, int n_
     }
     if (bd) HIPCHK(launch_stream_group_embed_burst(m->tok.w, g->d_mem, g->d_order, n_r, w.arow, bd, t, c.dec_dim, w.h, g->xf1, m->dec[0].attn_norm, g->ssq, g->d_pos, g->d_kv_row, s, g->paged ? &pg : nullptr));
     else HIPCHK(launch_stream_group_embed(m->tok.w, g->d_mem, g->d_order, n_r, w.arow, c.dec_dim, w.h, g->xf1, m->dec[0].attn_norm, g->ssq, g->d_pos, g->d_kv_row, s, g->paged ? &pg : nullptr));
+    if (g->attn_split) xb.split_ws = g->split_ws;
     VOXCHK(xf_chain(m, xb, 0, n_r, 0, 0, true, 0, s));
     HIPCHK(launch_stream_group_advance(g->logits, c.vocab, g->d_mem, g->d_order, n_r, R, 4 * R, g->g.cap, s));
     if (g->n_scored > 0) HIPCHK(launch_stream_score(g->logits, c.vocab, g->d_mem, g->d_order, n_r, VOX_PREFIX_TOKENS, s));      // slots of unscored members return at once
@@ -4997,6 +5053,16 @@ extern "C" int32_t vox_stream_group_set_scores(vox_stream_group* g, int32_t memb
     g->n_scored += (on != 0) - (int)sc.on; sc.on = on != 0;
     return VOX_OK;
 }
+extern "C" int32_t vox_stream_group_set_attn_split(vox_stream_group* g, int32_t on) {
+    ARGCHK(g, "null group"); ARGCHK(on == 0 || on == 1, "on must be 0 or 1"); VOXCHK(ctx_bind(g->ctx));
+    const vox_model_cfg& c = g->m->cfg; const int G = c.dec_heads / c.dec_kv_heads;
+    if (on && !(G == 1 || G == 2 || G == 4)) return fail(VOX_ERR_UNSUPPORTED, "the key-split attention serves 1, 2 or 4 query heads per KV head (this model: %d over %d)", c.dec_heads, c.dec_kv_heads);
+    HIPCHK(hipStreamSynchronize(g->ctx->stream));
+    if (on && !g->split_ws) VOXCHK(attn_split_ws_alloc(c, GROUP_MAX, g->g.max_pos, &g->split_ws, &g->bytes));      // (slab: max_pos rows per slice; paged: score_rows = min(max_pos, window + 1) -- the same chunk bound)
+    g->attn_split = on != 0;
+    return VOX_OK;
+}
+extern "C" int32_t vox_stream_group_attn_split(const vox_stream_group* g) { return g && g->attn_split ? 1 : 0; }
 extern "C" int32_t vox_stream_group_scores(const vox_stream_group* g, int32_t member, int32_t first_id, int32_t n, vox_token_score* out) {
     ARGCHK(g, "null group"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1);
     return g->mem[member].sc.read(g->mem[member].feed.ids_out, first_id, n, out);

@@ -247,6 +247,21 @@ hipError_t launch_attn_decode_paged(const AttnParams& p, int hd, hipStream_t s, 
 // at ring row j % cap, positions are not bound by cap; window >= 0 and window + 1 <= cap (hipErrorInvalidValue otherwise, nothing launched).  The per-head kernel with
 // the ring row policy: a row has launch_attn_decode's bits
 hipError_t launch_attn_decode_ring(const AttnParams& p, int hd, int cap, hipStream_t s, int n_seq = 1);
+// ---- key-split decode attention (attn_decode_split_kernel + attn_decode_merge_kernel, vox_kernels.hip): the same attention as TWO launches whose parallelism grows with
+// the position.  Launch 1: one workgroup per (KV head, sequence, chunk) -- a chunk is the ATTN_SPLIT_C logical rows [c C, (c + 1) C) cut to the sequence's visible rows
+// [j_lo, pos] -- serving the n_heads / n_kv_heads (1, 2 or 4) query heads of its KV head and writing one partial record {m, l, o[hd]} (chunk maximum, sum of
+// exponentials, unnormalised output) per query head into workspace [n_seq][n_heads][chunks][hd + 2].  Launch 2 merges a (sequence, head)'s records in ascending chunk order:
+// out = (sum_c o_c exp(m_c - M)) / (sum_c l_c exp(m_c - M)), M = max_c m_c, written as f32 rows (out, out_seq_stride) or as XF planes (out_xf, out_xf_gstride).
+// layout: how a cache row is found -- ATTN_SPLIT_FLAT launch_attn_decode's slices, ATTN_SPLIT_RING launch_attn_decode_ring's, ATTN_SPLIT_PAGED launch_attn_decode_paged's
+// (flat or ring table, f32 or bf16 pool) -- and the launcher checks what that launcher checks (hipErrorInvalidValue, nothing launched).  The chunks are aligned to absolute
+// row numbers, so a row's bits are a function of (q, the visible rows' values, pos, window) alone: every layout gives the same bits.  LDS is static: no limit on the cache
+// length.  chunks (the grid's third dimension, the records per head): attn_split_chunks(rows a sequence can hold: the slice's / ring's rows, a paged call's score_rows).
+// prefer_gqa, spec_rows and no_xcd_remap are not read.
+enum AttnSplitLayout { ATTN_SPLIT_FLAT = 0, ATTN_SPLIT_RING = 1, ATTN_SPLIT_PAGED = 2 };
+static const int ATTN_SPLIT_C = 256, ATTN_SPLIT_MAX_CHUNKS = 128;
+inline int attn_split_chunks(int rows, int window) { return (window >= 0 && window + 1 < rows ? window + 1 : rows) / ATTN_SPLIT_C + 2; }
+inline size_t attn_split_ws_floats(int n_seq, int n_heads, int hd, int chunks) { return (size_t)n_seq * n_heads * chunks * (hd + 2); }
+hipError_t launch_attn_decode_split(const AttnParams& p, int hd, int layout, float* workspace, hipStream_t s, int n_seq = 1);
 // single sequence: attention + the wo linear in one launch; acc[wo.N] (int64, zero on entry) receives the product in 2^-32 fixed point (consumer: PRO_RMS_MUL_SUM)
 bool attn_wo_supported(const AttnParams& p, const Q4W& wo, int hd, int max_seq);
 hipError_t launch_attn_wo(const AttnParams& p, const Q4W& wo, long long* acc, int max_seq, hipStream_t s);
@@ -259,6 +274,7 @@ enum AttnForm { ATTN_FORM_PREFILL_SMALL, ATTN_FORM_PREFILL_MFMA, ATTN_FORM_PREFI
                 ATTN_FORM_DECODE_PAGED_RING, ATTN_FORM_DECODE_GQA_PAGED_RING,      // the paged decode forms on a ring table (AttnParams::page_tab_len > 0)
                 ATTN_FORM_DECODE_PAGED_BF16, ATTN_FORM_DECODE_GQA_PAGED_BF16,      // the paged decode forms on a bf16 pool (AttnParams::kv_bf16): counted here and in no slot above
                 ATTN_FORM_DECODE_PAGED_RING_BF16, ATTN_FORM_DECODE_GQA_PAGED_RING_BF16,      // ... on a ring table
+                ATTN_FORM_DECODE_SPLIT, ATTN_FORM_DECODE_MERGE,          // the key-split decode attention's two launches (launch_attn_decode_split), every layout
                 ATTN_FORM_COUNT };
 void attn_form_note(AttnForm f);
 void attn_form_counts(unsigned long long out[ATTN_FORM_COUNT]);

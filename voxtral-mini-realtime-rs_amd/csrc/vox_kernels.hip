@@ -4005,6 +4005,248 @@ hipError_t launch_attn_decode_paged(const AttnParams& p_in, int hd, hipStream_t 
     return hipGetLastError();
 }
 
+// ---- key-split decode attention (launch_attn_decode_split; opt-in per live session and per stream group, DESIGN.md section 8, "Key-split decode attention").
+// The kernels above start one workgroup per (KV head or query head, sequence) and walk the whole window in it: 8 workgroups on 256 CUs for one full-size session, 8 MB of
+// K / V per layer strictly in sequence at the window.  Here the KEYS are split: one workgroup per (KV head, sequence, chunk), a chunk being the C = 256 logical rows
+// [c C, (c + 1) C) cut to the sequence's visible rows [j_lo, pos] (blockIdx.z counts chunks from the one that holds j_lo; a workgroup whose chunk holds no visible row
+// exits before any K / V request).  Chunks are aligned to ABSOLUTE row numbers, not to j_lo: a chunk never depends on the layout, a paged chunk touches C / page_rows
+// whole pages (one where page_rows >= C), and the result is a function of (q, the visible rows' values, pos, window) alone -- flat, ring, paged and paged-ring rows give
+// the same bits, a bf16 pool those of the widened values.
+// C = 256 and not 128: at the 8192-key window one full-size session is 33 chunks x 8 KV heads = 264 workgroups, one wave of workgroups over the 256 CUs with a chunk's
+// K / V (256 KB for 4 query heads) still requested once; a chunk is exactly one page of a paged group's default 256 rows; and the merge reads half the records C = 128
+// would leave it.  The price is registers: a lane holds 8 keys x 16 floats of K (128 VGPRs, f32 rows) and the 4 heads' q (64) in the score phase, then 32 float4s of
+// V -- the WHOLE chunk's K, then V, in flight as independent loads (the "maximise independent loads" rule of attn_decode_core, here for every key and not the first
+// 160).  At HD = 128, G = 4 that is 268 VGPRs + 12 AGPRs, no scratch: one workgroup (one wave per SIMD) per CU, whose 32 KB of requests per wave are the latency hiding.
+// Data movement: K as 16-byte loads, 8 lanes per key (HD / 8 contiguous floats each) and a DPP sum over the 8 lanes, 32 keys per pass, 8 passes; q for the G heads in
+// registers, pre-scaled by 1 / sqrt(HD); scores into STATIC LDS [G][C] -- the only score storage, so no launch argument bounds the cache length; V requested before the
+// softmax's first barrier; softmax with thread t on key t (wave trees, then the 4 waves in a fixed tree); P.V with thread -> (key group, float4 column), a group's keys
+// ascending, the groups summed in order through LDS.  Loads are unconditional with the row clamped to the chunk's last visible row; a key past it has its score not
+// stored and weight exactly 0, and rows outside [j_lo, pos] (NaN, stale) are never addressed.
+// No matrix instructions: K / V stay f32 (bf16 widened to f32) with f32 accumulation, held to 2e-5 of a row's maximum; G <= 4 query rows would idle 12 of an MFMA's 16
+// rows; and the operation is ~2 FLOP per byte and head -- it is bound by how many loads are in flight, which is what the split raises.
+// The HD = 64 instantiations (12 split kernels, merge<64>) have no caller and no test, like the plain kernels' -- dec_head_dim is the constant 128 and the test hook
+// refuses anything else: their PER = 8, COLS = GROUPS = 16 indexing is checked by reading and by the compiler's resource figures (no scratch, 160 VGPRs at G = 4) alone.
+// Output per (sequence, query head, chunk): the record {m, l, o[HD]} (8-byte vector stores; HD + 2 floats keep 8-byte alignment) in ws [n_seq][n_heads][gridDim.z][HD + 2].
+template <int HD, int G, class Rows>
+__global__ __launch_bounds__(256) VOX_NO_PK_F32 void attn_decode_split_kernel(const AttnParams p, float* __restrict__ ws) {
+    static_assert(HD == 128 || HD == 64, "head_dim");
+    constexpr int C = ATTN_SPLIT_C, PER = HD / 8, NP = C / 32, COLS = HD / 4, GROUPS = 256 / COLS, NV = C / GROUPS, REC = HD + 2;
+    using T = typename Rows::elem; using E = KvElem<T>;
+    constexpr int KQ = E::KQ; constexpr bool F32 = KQ == 1;
+    constexpr bool RING = std::is_same<Rows, KvRowsRing>::value, PAGED = !RING && !std::is_same<Rows, KvRowsFlat>::value;
+    static_assert(C == 256, "thread t is key t of the chunk in the softmax");
+    __shared__ float sc[G][C];
+    __shared__ float red[2 * G * 4];
+    __shared__ float4 osum[256];
+    __shared__ int ptab[PAGED ? C / 16 : 1];      // the chunk's table entries: C / page_rows of them, page_rows >= 16
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int kvh = blockIdx.x, seq = blockIdx.y;
+    const int pos = (p.pos_ptr ? p.pos_ptr[p.pos_per_seq ? seq : 0] : 0) + p.offset;
+    const int j_lo = p.window >= 0 ? max(0, pos - p.window) : 0;
+    const int c0 = (j_lo / C + (int)blockIdx.z) * C, c_lo = max(j_lo, c0), c_hi = min(pos, c0 + C - 1);
+    if (c_lo > c_hi) return;      // no visible row in this chunk (uniform): nothing requested, nothing written -- the merge knows from (pos, window)
+    const int n = c_hi - c_lo + 1;
+    Rows rows;
+    if constexpr (PAGED) {
+        const int q0 = c_lo >> p.page_shift, nq = (c_hi >> p.page_shift) - q0 + 1;
+        const int* tab = p.page_tab + (size_t)(p.kv_row ? p.kv_row[seq] : seq) * p.page_tab_stride;
+        if (tid < nq) {      // a ring table: logical page q at entry q % L -- the one place the ring index appears
+            const int L = p.page_tab_len;
+            ptab[tid] = tab[L > 0 ? (q0 + tid) % L : q0 + tid];
+        }
+        __syncthreads();
+        const size_t ho = (size_t)kvh * p.kv_head_stride;
+        rows = Rows{reinterpret_cast<const T*>(p.k) + ho, reinterpret_cast<const T*>(p.v) + ho, ptab, q0, p.page_shift, (1 << p.page_shift) - 1, p.kv_row_stride, (size_t)p.page_floats};
+    } else {
+        const int crow = p.kv_row ? p.kv_row[seq] : seq;
+        const float* kb = p.k + (size_t)crow * p.kv_seq_stride + (size_t)kvh * p.kv_head_stride;
+        const float* vb = p.v + (size_t)crow * p.kv_seq_stride + (size_t)kvh * p.kv_head_stride;
+        if constexpr (RING) { const int cap = p.kv_head_stride / p.kv_row_stride; rows = Rows{kb, vb, c_lo % cap, c_lo, cap, p.kv_row_stride}; }      // (n <= window + 1 <= cap: at most one cap less)
+        else rows = Rows{kb, vb, p.kv_row_stride};
+    }
+    const float* qrow = p.q + (size_t)seq * p.q_seq_stride + (size_t)kvh * G * HD;
+    const int ks = tid >> 3, part = tid & 7, grp = tid / COLS, col = tid % COLS;
+    const float scale = 1.0f / sqrtf((float)HD);
+    // every K request of the chunk, then q
+    typename E::KRaw kpre[NP][PER / (4 * KQ)];
+#pragma unroll
+    for (int u = 0; u < NP; u++) {
+        const auto* kr = rows.k(min(c_lo + 32 * u + ks, c_hi)) + part * PER;
+        if constexpr (F32) {
+#pragma unroll
+            for (int e = 0; e < PER / 4; e++) kpre[u][e] = *reinterpret_cast<const float4*>(kr + 4 * e);
+        } else {
+#pragma unroll
+            for (int e = 0; e < PER / 8; e++) kpre[u][e] = E::template ldk<false>(kr + 8 * e);
+        }
+    }
+    float4 qv[G][PER / 4];
+#pragma unroll
+    for (int hh = 0; hh < G; hh++)
+#pragma unroll
+        for (int e = 0; e < PER / 4; e++) {
+            const float4 t = *reinterpret_cast<const float4*>(qrow + hh * HD + part * PER + 4 * e);
+            qv[hh][e] = make_float4(t.x * scale, t.y * scale, t.z * scale, t.w * scale);
+        }
+    __builtin_amdgcn_sched_barrier(0);      // (keep the first score below every request)
+    // scores: key i = 32 u + ks of the chunk, one fma chain over the lane's PER values, then the 8 lanes of the key
+#pragma unroll
+    for (int u = 0; u < NP; u++) {
+        const int i = 32 * u + ks;
+#pragma unroll
+        for (int hh = 0; hh < G; hh++) {
+            float s_ = 0.f;
+#pragma unroll
+            for (int e = 0; e < PER / 4; e++) {
+                float4 kv; const float4 qq = qv[hh][e];
+                if constexpr (F32) kv = kpre[u][e]; else kv = E::wk(kpre[u][e / KQ], e % KQ);
+                s_ = fmaf(qq.x, kv.x, s_); s_ = fmaf(qq.y, kv.y, s_); s_ = fmaf(qq.z, kv.z, s_); s_ = fmaf(qq.w, kv.w, s_);
+            }
+            s_ = group8_sum(s_);
+            if (part == 0 && i < n) sc[hh][i] = s_;
+        }
+    }
+    // the chunk's V rows: in flight while the softmax runs.  Thread (grp, col) takes keys grp + GROUPS w, ascending
+    typename E::VRaw vpre[NV];
+#pragma unroll
+    for (int w = 0; w < NV; w++) {
+        const auto* vr = rows.v(min(c_lo + grp + w * GROUPS, c_hi)) + col * 4;
+        if constexpr (F32) vpre[w] = *reinterpret_cast<const float4*>(vr); else vpre[w] = E::template ldv<false>(vr);
+    }
+    __syncthreads();
+    float sv[G], mx[G], sum[G];
+#pragma unroll
+    for (int hh = 0; hh < G; hh++) {
+        sv[hh] = tid < n ? sc[hh][tid] : -INFINITY;
+        const float m_ = wave_max(sv[hh]);
+        if (lane == 0) red[hh * 4 + wave] = m_;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int hh = 0; hh < G; hh++) {
+        mx[hh] = fmaxf(fmaxf(red[hh * 4], red[hh * 4 + 1]), fmaxf(red[hh * 4 + 2], red[hh * 4 + 3]));
+        const float e = tid < n ? expf(sv[hh] - mx[hh]) : 0.f;      // a key past the chunk's last visible row: weight exactly 0
+        sc[hh][tid] = e;
+        const float s_ = wave_sum(e);
+        if (lane == 0) red[G * 4 + hh * 4 + wave] = s_;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int hh = 0; hh < G; hh++) sum[hh] = (red[G * 4 + hh * 4] + red[G * 4 + hh * 4 + 1]) + (red[G * 4 + hh * 4 + 2] + red[G * 4 + hh * 4 + 3]);
+    float4 o[G];
+#pragma unroll
+    for (int hh = 0; hh < G; hh++) o[hh] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int w = 0; w < NV; w++) {
+        float4 vv;
+        if constexpr (F32) vv = vpre[w]; else vv = E::wv(vpre[w]);
+#pragma unroll
+        for (int hh = 0; hh < G; hh++) {
+            const float pr = sc[hh][grp + w * GROUPS];
+            o[hh].x = fmaf(pr, vv.x, o[hh].x); o[hh].y = fmaf(pr, vv.y, o[hh].y); o[hh].z = fmaf(pr, vv.z, o[hh].z); o[hh].w = fmaf(pr, vv.w, o[hh].w);
+        }
+    }
+#pragma unroll
+    for (int hh = 0; hh < G; hh++) {
+        if (hh) __syncthreads();
+        osum[tid] = o[hh];
+        __syncthreads();
+        float* rec = ws + (((size_t)seq * p.n_heads + kvh * G + hh) * gridDim.z + blockIdx.z) * REC;
+        if (tid < COLS) {
+            float4 t = osum[tid];
+#pragma unroll
+            for (int gq = 1; gq < GROUPS; gq++) { const float4 u = osum[gq * COLS + tid]; t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w; }
+            *reinterpret_cast<float2*>(rec + 2 + 4 * tid) = make_float2(t.x, t.y);
+            *reinterpret_cast<float2*>(rec + 4 + 4 * tid) = make_float2(t.z, t.w);
+        } else if (tid == COLS) *reinterpret_cast<float2*>(rec) = make_float2(mx[hh], sum[hh]);
+    }
+}
+// Launch 2: one wave per (sequence, query head).  The non-empty chunks are the first nc = pos / C - j_lo / C + 1 records of the head, a function of (pos, window) alone.
+// M = max m_c (a maximum has no order); lane c forms w_c = exp(m_c - M) and l_c w_c, lanes own chunks c, c + 64 ascending and the wave tree (wave_sum) adds them; then
+// lane d < HD / 4 sums o_c[4 d .. 4 d + 3] w_c over c ascending in one chain and scales by 1 / L.  Writes what the plain kernels write: an f32 row, or the XF planes.
+template <int HD>
+__global__ __launch_bounds__(64) VOX_NO_PK_F32 void attn_decode_merge_kernel(const AttnParams p, const float* __restrict__ ws, int chunks) {
+    constexpr int C = ATTN_SPLIT_C, REC = HD + 2, COLS = HD / 4;
+    __shared__ float wsh[ATTN_SPLIT_MAX_CHUNKS];
+    const int lane = threadIdx.x, h = blockIdx.x, seq = blockIdx.y;
+    const int pos = (p.pos_ptr ? p.pos_ptr[p.pos_per_seq ? seq : 0] : 0) + p.offset;
+    const int j_lo = p.window >= 0 ? max(0, pos - p.window) : 0;
+    const int nc = min(pos / C - j_lo / C + 1, chunks);      // (never more than the launcher's bound: the clamp keeps a caller's mistake inside the workspace)
+    const float* rec = ws + ((size_t)seq * p.n_heads + h) * chunks * REC;
+    float M = -INFINITY;
+    for (int c = lane; c < nc; c += 64) M = fmaxf(M, rec[(size_t)c * REC]);
+    M = wave_max(M);
+    float L = 0.f;
+    for (int c = lane; c < nc; c += 64) {
+        const float2 ml = *reinterpret_cast<const float2*>(rec + (size_t)c * REC);
+        const float w = expf(ml.x - M);
+        wsh[c] = w; L = fmaf(ml.y, w, L);
+    }
+    L = wave_sum(L);
+    __syncthreads();
+    if (lane >= COLS) return;
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 4
+    for (int c = 0; c < nc; c++) {
+        const float w = wsh[c];
+        const float2 x = *reinterpret_cast<const float2*>(rec + (size_t)c * REC + 2 + 4 * lane), y = *reinterpret_cast<const float2*>(rec + (size_t)c * REC + 4 + 4 * lane);
+        a.x = fmaf(x.x, w, a.x); a.y = fmaf(x.y, w, a.y); a.z = fmaf(y.x, w, a.z); a.w = fmaf(y.y, w, a.w);
+    }
+    const float inv = 1.0f / L;
+    const float4 r4 = make_float4(a.x * inv, a.y * inv, a.z * inv, a.w * inv);
+    if (p.out_xf) xf_store4(p.out_xf + (size_t)(seq >> 4) * p.out_xf_gstride, p.n_heads * HD, seq & 15, h * HD + lane * 4, r4);
+    else *reinterpret_cast<float4*>(p.out + (size_t)seq * p.out_seq_stride + h * HD + lane * 4) = r4;
+}
+template <int HD, int G, class Rows>
+static void attn_split_go(const AttnParams& p, float* ws, int chunks, hipStream_t s, int n_seq) {
+    attn_decode_split_kernel<HD, G, Rows><<<dim3(p.n_kv_heads, n_seq, chunks), dim3(256), 0, s>>>(p, ws);
+}
+template <int HD, int G>
+static void attn_split_rows(const AttnParams& p, int layout, float* ws, int chunks, hipStream_t s, int n_seq) {
+    if (layout == ATTN_SPLIT_FLAT) attn_split_go<HD, G, KvRowsFlat>(p, ws, chunks, s, n_seq);
+    else if (layout == ATTN_SPLIT_RING) attn_split_go<HD, G, KvRowsRing>(p, ws, chunks, s, n_seq);
+    else if (p.kv_bf16) attn_split_go<HD, G, KvRowsPagedT<uint16_t>>(p, ws, chunks, s, n_seq);
+    else attn_split_go<HD, G, KvRowsPagedT<float>>(p, ws, chunks, s, n_seq);
+}
+template <int HD>
+static void attn_split_heads(const AttnParams& p, int G, int layout, float* ws, int chunks, hipStream_t s, int n_seq) {
+    if (G == 4) attn_split_rows<HD, 4>(p, layout, ws, chunks, s, n_seq);
+    else if (G == 2) attn_split_rows<HD, 2>(p, layout, ws, chunks, s, n_seq);
+    else attn_split_rows<HD, 1>(p, layout, ws, chunks, s, n_seq);
+}
+hipError_t launch_attn_decode_split(const AttnParams& p, int hd, int layout, float* ws, hipStream_t s, int n_seq) {
+    if (!ws || n_seq < 1 || (hd != 128 && hd != 64) || p.n_kv_heads < 1 || p.n_heads % p.n_kv_heads || p.kv_row_stride != hd || (!p.out && !p.out_xf)) return hipErrorInvalidValue;
+    const int G = p.n_heads / p.n_kv_heads;
+    if (G != 1 && G != 2 && G != 4) return hipErrorInvalidValue;
+    int rows;      // the rows a sequence can hold: the chunk bound follows from them and the window
+    if (layout == ATTN_SPLIT_FLAT) {
+        if (p.kv_bf16 || p.page_tab || p.kv_head_stride < hd || p.kv_head_stride % hd) return hipErrorInvalidValue;
+        rows = p.kv_head_stride / hd;
+    } else if (layout == ATTN_SPLIT_RING) {      // launch_attn_decode_ring's conditions
+        const int cap = p.kv_head_stride / hd;
+        if (p.kv_bf16 || p.page_tab || !p.pos_ptr || cap < 1 || p.window < 0 || p.window + 1 > cap || p.kv_head_stride != cap * hd) return hipErrorInvalidValue;
+        rows = cap;
+    } else if (layout == ATTN_SPLIT_PAGED) {     // launch_attn_decode_paged's
+        const int page_rows = 1 << p.page_shift, win = p.window >= 0 ? p.window : p.score_rows - 1;
+        if (!p.page_tab || !p.pos_ptr || !p.pos_per_seq || p.page_shift < 4 || p.page_shift > 10 || p.kv_head_stride != page_rows * hd || p.score_rows < 1 ||
+            p.page_floats != (long)p.n_kv_heads * page_rows * hd || p.page_tab_stride < 1 || win / page_rows + 2 > ATTN_PAGE_TAB_MAX) return hipErrorInvalidValue;
+        if (p.page_tab_len != 0 && (p.page_tab_len < 1 || p.page_tab_len > p.page_tab_stride || p.window < 0)) return hipErrorInvalidValue;
+        if (p.kv_bf16 && (p.kv_bf16 != 1 || ((reinterpret_cast<uintptr_t>(p.k) | reinterpret_cast<uintptr_t>(p.v)) & 15))) return hipErrorInvalidValue;
+        rows = p.score_rows;
+    } else return hipErrorInvalidValue;
+    const int chunks = attn_split_chunks(rows, p.window);
+    if (chunks > ATTN_SPLIT_MAX_CHUNKS) return hipErrorInvalidValue;
+    if (hd == 128) attn_split_heads<128>(p, G, layout, ws, chunks, s, n_seq); else attn_split_heads<64>(p, G, layout, ws, chunks, s, n_seq);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    attn_form_note(ATTN_FORM_DECODE_SPLIT);
+    if (hd == 128) attn_decode_merge_kernel<128><<<dim3(p.n_heads, n_seq), dim3(64), 0, s>>>(p, ws, chunks);
+    else attn_decode_merge_kernel<64><<<dim3(p.n_heads, n_seq), dim3(64), 0, s>>>(p, ws, chunks);
+    e = hipGetLastError();
+    if (e == hipSuccess) attn_form_note(ATTN_FORM_DECODE_MERGE);
+    return e;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Conv1d(k3, s2, p1) + exact-erf GELU (models/layers/conv.rs:78-83). f32, LDS-tiled:
 // workgroup = 64 output channels x 64 output positions, 16 input channels per step, 4x4 outputs / thread.

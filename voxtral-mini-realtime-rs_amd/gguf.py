@@ -333,6 +333,32 @@ def attn_decode_ring(ctx, q, k, v, pos, n_heads, n_kv_heads, window):
     return out
 
 
+def attn_decode_split(ctx, q, k, v, pos, n_heads, n_kv_heads, window=-1, kv_row=None, page_tab=None, score_rows=0, ring=False, page_tab_len=0, bf16=False, out_xf=False,
+                      head_dim=128, **flags):
+    """vox_debug_attn_decode_split: ONE key-split decode attention (a split and a merge launch) on attn_decode's buffers.  Flat slices by default; ring: the slices
+    are rings of k.shape[2] rows (attn_decode_ring's call); page_tab given: a paged call (page_tab_len > 0: a ring table; bf16: uint16 pools).  flags: prefer_gqa /
+    spec / no_xcd_remap, which the hook refuses.  Returns attn_decode's f32 rows or XF planes."""
+    paged = page_tab is not None
+    q, pos = _f32(q), np.ascontiguousarray(pos, dtype=np.int32)
+    k, v = (np.ascontiguousarray(k, dtype=np.uint16), np.ascontiguousarray(v, dtype=np.uint16)) if bf16 else (_f32(k), _f32(v))
+    if q.ndim != 2 or k.ndim != 4 or k.shape != v.shape or pos.shape != (q.shape[0],) or k.shape[1] != n_kv_heads or k.shape[3] != 128 or q.shape[1] != n_heads * 128:
+        raise VoxError(1, "attn_decode_split: bad shapes")
+    d = AttnDecodeDesc(n_seq=q.shape[0], n_heads=n_heads, n_kv_heads=n_kv_heads, head_dim=head_dim, window=window, out_xf=int(out_xf), pos=pos.ctypes.data,
+                       **{f: int(x) for f, x in flags.items()})
+    if kv_row is not None:
+        kv_row = np.ascontiguousarray(kv_row, dtype=np.int32).reshape(pos.shape); d.kv_row = kv_row.ctypes.data
+    if paged:
+        page_tab = np.ascontiguousarray(page_tab, dtype=np.int32)
+        d.n_slices, d.page_tab_stride = page_tab.shape
+        d.pool_pages, d.page_rows, d.score_rows, d.page_tab = k.shape[0], k.shape[2], score_rows, page_tab.ctypes.data
+    else:
+        d.n_slices, d.max_seq = k.shape[0], k.shape[2]
+    QD = n_heads * 128
+    out = np.empty(((q.shape[0] + 15) // 16, 2, QD // 128 * 256 * 8), np.uint16) if out_xf else np.empty((q.shape[0], QD), np.float32)
+    check(lib().vox_debug_attn_decode_split(ctx.h, C.byref(d), 2 if paged else int(bool(ring)), int(page_tab_len), 1 if bf16 else 0, _ptr(q), _ptr(k), _ptr(v), _ptr(out)))
+    return out
+
+
 class StreamAttnDesc(C.Structure):
     """vox_stream_attn_desc (include/voxtral_hip.h)."""
     _fields_ = [(n, C.c_int32) for n in ("n_slots", "n_members", "rows", "n_heads", "head_dim", "window", "cap", "layers", "layer", "rope_rows", "rope_per_member")] + \
@@ -911,6 +937,14 @@ class LiveStream:
         """vox_stream_set_scores: from the next push / finish on, every id comes with its record (scores()); survives reset()."""
         check(lib().vox_stream_set_scores(self.h, 1 if on else 0))
 
+    def set_attn_split(self, on: bool = True):
+        """vox_stream_set_attn_split: from the next push / finish on, the per-operator decode steps (the session past the decode engine's 1024 cache rows) run the
+        key-split decode attention -- its parallelism grows with the position.  The cache is untouched; survives reset(); ids are the plain session's up to near-ties."""
+        check(lib().vox_stream_set_attn_split(self.h, 1 if on else 0))
+
+    def attn_split(self) -> bool:
+        return bool(lib().vox_stream_attn_split(self.h))
+
     def scores(self, first: int = 0, n=None) -> np.ndarray:
         """vox_stream_scores: the records of ids [first, first + n) of the current utterance (n None: up to the last id handed out) as a structured array (logprob,
         margin, runner_up, id); an id handed out while scores were off has NaN, NaN, -1 and its id.  Reads host memory only."""
@@ -1197,6 +1231,14 @@ class LiveStreamGroup:
         """vox_stream_group_set_scores: LiveStream.set_scores for one member; survives the member's resets."""
         check(lib().vox_stream_group_set_scores(self.h, int(member), 1 if on else 0))
 
+    def set_attn_split(self, on: bool = True):
+        """vox_stream_group_set_attn_split: from the next advance on, every decode round of the group runs the key-split decode attention in place of its cache
+        layout's plain launch.  The caches are untouched; survives resets; ids are the plain group's up to near-ties."""
+        check(lib().vox_stream_group_set_attn_split(self.h, 1 if on else 0))
+
+    def attn_split(self) -> bool:
+        return bool(lib().vox_stream_group_attn_split(self.h))
+
     def scores(self, member, first: int = 0, n=None) -> np.ndarray:
         """vox_stream_group_scores: LiveStream.scores for one member."""
         n = self.info(member)["ids"] - int(first) if n is None else int(n)
@@ -1444,15 +1486,19 @@ class Q4VoxtralModel:
         check(lib().vox_transcribe_audio_scored(self.h, ptr, n_samples, _ptr(t), _ptr(ids), cap, C.byref(n), _ptr(sc), None if al is None else _ptr(al), k, kind))
         return ids[:n.value].copy(), sc[:n.value].copy(), None if al is None else al[:n.value].copy()
 
-    def create_stream(self, t_embed, gain=1.0, enc_capacity_rows=0, max_positions=0, sample_rate=16000, endless=False, dec_ring_rows=0, burst=None) -> LiveStream:
+    def create_stream(self, t_embed, gain=1.0, enc_capacity_rows=0, max_positions=0, sample_rate=16000, endless=False, dec_ring_rows=0, burst=None, attn_split=False) -> LiveStream:
         """A live session on this model (vox_stream_create / vox_stream_create_rate): push(x) -> ids, finish(), reset(), info(), close().  gain multiplies every sample
         (a stream has no file peak: 0.95 / max|x| of a known file reproduces transcribe_audio).  sample_rate: the rate of the samples that will be pushed.
         endless (vox_stream_create_endless): no 16 384-position limit -- the decoder cache is a ring of dec_ring_rows rows (0: the default, a little more than one window).
-        burst (vox_stream_create_burst): 1..16 -- a backlog's ticks run in bursts of up to that many; None: a plain stream."""
-        return LiveStream(self, t_embed, gain, enc_capacity_rows, max_positions, sample_rate, endless, dec_ring_rows, burst)
+        burst (vox_stream_create_burst): 1..16 -- a backlog's ticks run in bursts of up to that many; None: a plain stream.
+        attn_split: LiveStream.set_attn_split(True) on the new session."""
+        st = LiveStream(self, t_embed, gain, enc_capacity_rows, max_positions, sample_rate, endless, dec_ring_rows, burst)
+        if attn_split:
+            st.set_attn_split(True)
+        return st
 
     def create_stream_group(self, t_embed, n_members, gains=None, enc_capacity_rows=0, max_positions=0, sample_rates=None, page_rows=None, pool_pages=None,
-                            endless=False, kv_dtype=None, burst=None, t_embeds=None, delays=None) -> LiveStreamGroup:
+                            endless=False, kv_dtype=None, burst=None, t_embeds=None, delays=None, attn_split=False) -> LiveStreamGroup:
         """Up to 16 live sessions advanced together (vox_stream_group_create): advance({member: samples}, finish=()) -> {member: ids}, reset(member, gain), info(member),
         close().  gains: one per member (None: 1.0 each); max_positions 0: 2048 decoder positions per member (the group's decoder cache does not grow);
         sample_rates: what each member is fed (None: 16 kHz each; vox_stream_group_create_rates).
@@ -1464,7 +1510,7 @@ class Q4VoxtralModel:
         pages, half the memory and half the bytes the decode attention reads; ids and logits are close to, not equal to, the f32 group's.  pool() then names it.
         t_embeds [n_members][dec_dim] or delays [n_members] (through TimeEmbedding; vox_stream_group_create_t_embeds, any kind of group): a delay PER MEMBER -- t_embed
         is then unread (None); member k's ids are those of member k in a group whose members all run at its delay.  reset(member, delay=) moves a member to another,
-        t_embed(member) reads it back."""
+        t_embed(member) reads it back.  attn_split: LiveStreamGroup.set_attn_split(True) on the new group."""
         if delays is not None and t_embeds is not None:
             raise ValueError("create_stream_group: delays and t_embeds name the same thing, give one")
         if delays is not None:
@@ -1474,7 +1520,10 @@ class Q4VoxtralModel:
             t_embeds = _f32(np.stack([_f32(t).reshape(-1) for t in t_embeds])) if len(t_embeds) else np.zeros((0, self.config.dec_dim), np.float32)
             if t_embeds.shape != (int(n_members), self.config.dec_dim):
                 raise ValueError(f"{t_embeds.shape[0]} t_embeds of {t_embeds.shape[1]} values for {int(n_members)} members of dec_dim {self.config.dec_dim}: one per member")
-        return LiveStreamGroup(self, t_embed, n_members, gains, enc_capacity_rows, max_positions, sample_rates, page_rows, pool_pages, endless, kv_dtype, burst, t_embeds)
+        g = LiveStreamGroup(self, t_embed, n_members, gains, enc_capacity_rows, max_positions, sample_rates, page_rows, pool_pages, endless, kv_dtype, burst, t_embeds)
+        if attn_split:
+            g.set_attn_split(True)
+        return g
 
     def transcribe_batch(self, samples_list, t_embed, device_ptrs=None, n_samples=None, norm_group=None, tap_units=None):
         """Batched whole-path transcription of independent utterances (<= 4096; wider than 16: continuous batching over decode slots): list of float32 sample arrays
