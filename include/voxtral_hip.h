@@ -551,6 +551,13 @@ int32_t vox_debug_stream_attn_burst_launches(uint64_t* out);
  * every slot the launch leaves in out and in every word of that member's K and V ring the bits rows_per_slot[z] / 4 successive vox_debug_stream_attn calls with rows = 4
  * leave (enc_pos moving by 4); members not in `order` keep every ring word. */
 int32_t vox_debug_stream_attn_group_burst(vox_ctx* ctx, const vox_stream_attn_desc* desc, const int32_t* rows_per_slot, const float* qkv, float* kring, float* vring, float* out);
+/* The three forms on a ring of either element (A BF16 ENCODER RING below), on their own: form 0 is vox_debug_stream_attn, 1 vox_debug_stream_attn_burst, 2
+ * vox_debug_stream_attn_group_burst (rows_per_slot given; it must be null for forms 0 and 1) -- their arguments, checks, launches and counters.  enc_kv_dtype
+ * VOX_KV_F32: that entry itself.  VOX_KV_BF16: kring / vring are host [n_members][layers][n_heads][cap][head_dim] of uint16_t, in and out; after the launch the rows
+ * of the served members' layer hold vox_kv_round_bf16 of the rotated k and of the raw v, every other 16-bit word its bits from before, and `out` is the f32 kernel's
+ * arithmetic on the widened ring values and on the launch's own rows rounded and widened.  Any other form or dtype is refused (VOX_ERR_INVALID). */
+int32_t vox_debug_stream_attn_elem(vox_ctx* ctx, const vox_stream_attn_desc* desc, int32_t form, int32_t enc_kv_dtype, const int32_t* rows_per_slot_or_null, const float* qkv,
+                                   void* kring, void* vring, float* out);
 /* The seeding of a session's encoder rings from the model's prefix state, on its own (tests): kv host [layers][rows][k row | v row], token-major, each row n_heads *
  * head_dim wide; kring / vring host [layers][n_heads][cap][head_dim], in and out: ring rows 0 .. rows - 1 of every layer and head receive the input's bits, every
  * other word keeps its own.  layers 1..64, n_heads 1..64, head_dim 64 | 128, cap 1..16384; rows <= 0 and rows > cap are refused, like every argument, before the
@@ -1038,7 +1045,8 @@ int32_t vox_stream_group_create_endless(vox_model* m, const float* t_embed, int3
  *   the prefix rows) and nowhere else: while the ids agree, a bf16 member's layer-0 rows are the rounded layer-0 rows of the f32 member, exactly.  (4) A session blob
  *   holds f32 rows whatever its container: a bf16 member packs its rows widened (exact); a restore rounds (exact for a blob of a bf16 member) -- bf16 to bf16 of the
  *   same kind continues bit for bit.  (5) A bf16 group's ids and logits are NOT the f32 group's; how far apart they are is measured (profiles/stream_group_kv_bf16.txt),
- *   not promised.  Not served: bf16 for slab groups and solo streams, the encoder ring, the offline caches, f16 / fp8, mixed dtypes in one group. */
+ *   not promised.  Not served: a bf16 pool for slab groups and solo streams, the offline caches, f16 / fp8, mixed dtypes in one group (the encoder ring: A BF16 ENCODER
+ *   RING below). */
 #define VOX_KV_F32 0
 #define VOX_KV_BF16 1
 int32_t vox_stream_group_create_kv(vox_model* m, const float* t_embed, int32_t n_members, const float* gains /* null: 1.0 */, const uint32_t* rates /* null: 16000 each */,
@@ -1097,6 +1105,26 @@ int32_t vox_stream_group_create_t_embeds(vox_model* m, const float* t_embeds /* 
                                          int32_t page_rows /* 0: 256 */, int32_t pool_pages /* 0: the default */, int32_t endless, int32_t kv_dtype, int32_t burst_ticks,
                                          vox_stream_group** out);
 int32_t vox_stream_group_reset_t_embed(vox_stream_group* g, int32_t member, float gain, uint32_t sample_rate /* 0: keep */, const float* t_embed);
+/* A BF16 ENCODER RING ("A bf16 encoder ring").  Every tick, a member's encoder layers read their whole window of the member's K / V ring: the ring
+ * is the largest item of a member's memory and of a wide round's HBM traffic.  vox_stream_group_create_enc_kv takes vox_stream_group_create_t_embeds' argument list
+ * plus enc_kv_dtype.  VOX_KV_F32: exactly vox_stream_group_create_t_embeds -- the same checks, the same object, the same launches and allocations.  VOX_KV_BF16: the
+ * members' encoder rings are [layer][head][cap][head_dim] of uint16_t -- half the ring's bytes (vox_stream_group_info's byte word follows), half the bytes the ring
+ * attention reads.  Any other value is refused (VOX_ERR_INVALID) before anything is allocated.  The flag is independent of paged, endless, kv_dtype and burst_ticks,
+ * and fixed for the group's life; vox_stream_group_enc_kv_dtype reads it back (VOX_KV_F32 for every group made by another creator).
+ *   The rounding is the pool's ONE function (A BF16 K/V POOL above).  K is rotated in f32 as ever, then rounded, then stored; V is rounded and stored; q is never
+ *   rounded.  The keys and values a launch appends enter that launch's own scores and sums as the rounded values widened again, so a key has the same bits whether a
+ *   query meets it in the launch that appends it or in the ring one tick later.  From that follow, on a bf16 ring as on an f32 one: ids and logits do not depend on how
+ *   the samples were cut (burst_ticks 1), a burst launch is bit for bit the chain of its tick launches, and the ring capacity changes addresses only.
+ *   reset seeds the ring with the prefix rows rounded by the same function; a peek's save area holds 16-bit rows and the group is bit for bit what it was afterwards;
+ *   scores, alternatives, levels, capture rates, delays per member and attn_split work as in any group.  A session blob holds f32 rows whatever its container: a bf16
+ *   ring packs its rows widened (exact), a restore rounds (exact for a blob of a bf16 ring) -- bf16 ring to bf16 ring continues bit for bit, and blobs move between
+ *   the two dtypes.  A bf16-ring group's ids and logits are NOT the f32 group's; how far apart they are is measured (profiles/stream_group_enc_kv_bf16.txt), not
+ *   promised.  Not served: solo vox_stream sessions, f16 / fp8, a 16-bit blob, mixed ring dtypes in one group, a change of dtype after create. */
+int32_t vox_stream_group_create_enc_kv(vox_model* m, const float* t_embeds /* [n_members][dec_dim] */, int32_t n_members, const float* gains /* null: 1.0 */,
+                                       const uint32_t* rates /* null: 16000 each */, int32_t enc_capacity_rows, int32_t max_positions /* endless: 0 */, int32_t paged,
+                                       int32_t page_rows /* 0: 256 */, int32_t pool_pages /* 0: the default */, int32_t endless, int32_t kv_dtype, int32_t burst_ticks,
+                                       int32_t enc_kv_dtype, vox_stream_group** out);
+int32_t vox_stream_group_enc_kv_dtype(const vox_stream_group* g, int32_t* out);
 int32_t vox_stream_group_t_embed(const vox_stream_group* g, int32_t member, float* out, int32_t cap);
 /* debug (tests): ONE launch of the decode round's wo operator on caller data -- out [M][N] = x [M][K] W^T + resid [M][N] as f32 rows, xf_out the XF planes
  * (2 (N / 128) 256 8 16-bit values) of out * xf_w [N] * scale, ssq_out [(N / 16)][16] the per-tile sums of squares of out.  scales holds n_sets vectors of N floats.

@@ -183,6 +183,9 @@ def bench_groups(pkg, ctx, m, t, tm, a, widths, lines):
         if a.delays:      # the mixed twin of the uniform group: member z at delay 2 + z, the same samples
             gd = m.create_stream_group(None, N, gains=[gain] * N, delays=[2 + z for z in range(N)])
             gd.advance({k: x[:pos] for k in range(N)}); mixed = []; kd = 0
+        if a.enc_kv == "bf16":      # the bf16-ring twin of the group (vox_stream_group_create_enc_kv): the same samples and positions
+            gq = m.create_stream_group(t, N, gains=[gain] * N, enc_kv_dtype="bf16")
+            gq.advance({k: x[:pos] for k in range(N)}); ring16 = []; kq = 0
         if sr:
             g2, g3 = (m.create_stream_group(t, N, gains=[gr] * N, sample_rates=[sr] * N) for _ in range(2)); rpos = per * (warm + 1)      # fed from host / device memory
             for gg in (g2, g3):
@@ -195,8 +198,10 @@ def bench_groups(pkg, ctx, m, t, tm, a, widths, lines):
             feeds = {k: seg for k in range(N)}
             grp.append(tm.ms(lambda: g.advance(feeds)) / a.ticks); k2 = launch_counts(pkg)
             ks += sum(k1) - sum(k0); kg += sum(k2) - sum(k1)
+            if a.enc_kv == "bf16":      # right behind the f32 pass, over the same positions
+                ring16.append(tm.ms(lambda: gq.advance(feeds)) / a.ticks); kq += sum(launch_counts(pkg)) - sum(k2)
             if a.delays:      # right behind the uniform pass, over the same positions
-                mixed.append(tm.ms(lambda: gd.advance(feeds)) / a.ticks); kd += sum(launch_counts(pkg)) - sum(k2)
+                kd0 = launch_counts(pkg); mixed.append(tm.ms(lambda: gd.advance(feeds)) / a.ticks); kd += sum(launch_counts(pkg)) - sum(kd0)
             if a.page_rows:
                 k2p = launch_counts(pkg); w0 = time.perf_counter(); paged.append(tm.ms(lambda: gp.advance(feeds)) / a.ticks); wall_p.append(1e3 * (time.perf_counter() - w0) / a.ticks)
                 kp += sum(launch_counts(pkg)) - sum(k2p)
@@ -224,7 +229,7 @@ def bench_groups(pkg, ctx, m, t, tm, a, widths, lines):
                     out.append(ms / done)
                 rpos += n
         assert g.info(N - 1)["positions"] == st.info()["positions"] == 38 + warm + a.ticks * a.passes
-        st.close(); g.close()
+        g_bytes = g.info(0)["bytes"]; st.close(); g.close()
         for what, st_s, g_s, _, _ in twins:
             assert g_s.info(N - 1)["positions"] == st_s.info()["positions"] == 38 + warm + a.ticks * a.passes and twin_recorded(what, st_s)
             st_s.close(); g_s.close()
@@ -235,6 +240,12 @@ def bench_groups(pkg, ctx, m, t, tm, a, widths, lines):
         rows.append((N, rnd, tick))
         lines += [f"group of {N:2d}: round median {rnd:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in grp) + f"   solo tick median {tick:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in solo),
                   f"  round / ({N} x solo tick) = {rnd / (N * tick):.3f}   per member and tick {rnd / N:.3f} ms   launches per round {lg:.0f} (solo tick {ls:.0f})"]
+        if a.enc_kv == "bf16":
+            assert gq.info(N - 1)["positions"] == 38 + warm + a.ticks * a.passes and gq.enc_kv() == "bf16"
+            iq = gq.info(0); i32 = g_bytes; gq.close(); rq = statistics.median(ring16)
+            lines += [f"  bf16 encoder ring, group of {N:2d}, each pass right behind the f32 one's: round median {rq:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in ring16) +
+                      f"   bf16 - f32 {rq - rnd:+.3f} ms ({100 * (rq - rnd) / rnd:+.2f} %), per pass " + " ".join(f"{v - w:+.3f}" for v, w in zip(ring16, grp)),
+                      f"  launches per round: bf16 ring {kq / ticks + fixed_enc + 2:.0f}, f32 {lg:.0f}; a member's device bytes: bf16 ring {iq['bytes'] / 1e6:.1f} MB, f32 {i32 / 1e6:.1f} MB"]
         if a.delays:
             assert gd.info(N - 1)["positions"] == 38 + warm + a.ticks * a.passes
             gd.close(); rd_ = statistics.median(mixed)
@@ -515,6 +526,7 @@ def main():
                     "mel launch), as --scores does; combines with --scores and --alternatives")
     ap.add_argument("--page-rows", type=int, default=0, metavar="R", help="with --group: also time a paged group (pages of R rows, the default pool) pass by pass next to the slab group")
     ap.add_argument("--kv", choices=("f32", "bf16"), default="f32", help="with --group and --page-rows: bf16 also times a paged group with a bf16 K/V pool pass by pass behind the f32 paged group")
+    ap.add_argument("--enc-kv", choices=("f32", "bf16"), default="f32", help="with --group: bf16 also times a group with a bf16 encoder K/V ring (vox_stream_group_create_enc_kv) pass by pass right behind the f32 group")
     ap.add_argument("--delays", choices=("mixed",), default=None, help="with --group: also time a group with a delay per member (member z at delay 2 + z) pass by pass behind the uniform group")
     ap.add_argument("--peek", action="store_true", help="time vox_stream_peek next to the same number of ordinary ticks of the same session (nothing else is measured)")
     ap.add_argument("--endless", action="store_true", help="time the tick of an endless session past the wrap of its decoder ring next to a bounded session at the same positions (nothing else is measured)")

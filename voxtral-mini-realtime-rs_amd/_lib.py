@@ -268,6 +268,11 @@ SIGNATURES = {
     # a delay per member: (model, t_embeds [n][dec_dim], n_members, gains, rates, cap, max_pos, paged, page_rows, pool_pages, endless, kv_dtype, burst_ticks, out);
     # (group, member, gain, sample_rate or 0, t_embed); (group, member, out, cap)
     "vox_stream_group_create_t_embeds": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, P(vp)]),
+    # a bf16 encoder ring: vox_stream_group_create_t_embeds' arguments with enc_kv_dtype in front of out; (group, out); (ctx, vox_stream_attn_desc, form 0 tick |
+    # 1 burst | 2 ragged, enc_kv_dtype, rows_per_slot or null, qkv, kring, vring, out): ONE launch of the ring attention on rings of that element
+    "vox_stream_group_create_enc_kv": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, P(vp)]),
+    "vox_stream_group_enc_kv_dtype": (i32, [vp, P(i32)]),
+    "vox_debug_stream_attn_elem": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp]),
     "vox_stream_group_reset_t_embed": (i32, [vp, i32, f32, u32, vp]),
     "vox_stream_group_t_embed": (i32, [vp, i32, vp, i32]),
     # (ctx, w, vox_resid_xf_desc, x, resid, xf_w, scales, order or null, out, xf_out, ssq_out): ONE launch of the wo GEMM's EPI_RESID_XF epilogue

@@ -216,8 +216,9 @@ def parse_live_delays(text, n_members):
 
 
 def transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, chunk_ms, n_members, words_out=None, peek=False, alts_k=0, page_rows=None, pool_pages=None, endless=False,
-                          suspend_every=0, kv_dtype=None, delays=None, levels=False, endpoint_ms=0, endpoint_db=-50.0, attn_split=False):
-    """(attn_split, --live-attn-split: the group's decode rounds run the key-split decode attention, vox_stream_group_set_attn_split.)
+                          suspend_every=0, kv_dtype=None, delays=None, levels=False, endpoint_ms=0, endpoint_db=-50.0, attn_split=False, enc_kv_dtype=None):
+    """(enc_kv_dtype, --live-enc-kv f32 | bf16: what the members' encoder K/V rings hold, vox_stream_group_create_enc_kv; the lines have the same form.)
+    (attn_split, --live-attn-split: the group's decode rounds run the key-split decode attention, vox_stream_group_set_attn_split.)
     (levels / endpoint_ms / endpoint_db: as transcribe_live's, per member -- the members whose trigger is due after a call share one group peek.)
     (delays, --live-delays: one delay per member -- the group is made by vox_stream_group_create_t_embeds, member k's files run at delays[k], and every --live-words
     line gains "delay"; None: every member at t_embed.)
@@ -231,7 +232,7 @@ def transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, chunk_ms, 
     member is refused at 43 minutes); the lines are the same.  suspend_every (--live-suspend-every N): after every N calls each busy member is snapshotted to host
     memory, reset, and restored from its blob (vox_stream_group_snapshot / _restore); the lines are the same."""
     step = max(1, int(round(16000 * chunk_ms / 1000.0)))
-    group = model.create_stream_group(None if delays else t_embed, n_members, page_rows=page_rows, pool_pages=pool_pages, endless=endless, kv_dtype=kv_dtype, delays=delays, attn_split=attn_split)
+    group = model.create_stream_group(None if delays else t_embed, n_members, page_rows=page_rows, pool_pages=pool_pages, endless=endless, kv_dtype=kv_dtype, delays=delays, attn_split=attn_split, enc_kv_dtype=enc_kv_dtype)
     text = lambda ids: tokenizer.decode([t for t in ids if t >= 1000]).strip()
     texts = {}; busy = {}; nxt = 0; calls = 0      # busy: member -> [file index, samples, offset, ids]
     endpoints = {}      # member -> its file's Endpoint
@@ -438,6 +439,9 @@ def main(argv=None):
     ap.add_argument("--live-kv", choices=("f32", "bf16"), default=None, help="with --live-group: what the group's decoder K/V pool holds (vox_stream_group_create_kv; makes the "
                     "group a paged one).  bf16: 16-bit pages, half the memory per page and half the bytes the decode attention reads; the text may differ from an f32 group's "
                     "where the model's choice between two tokens is close")
+    ap.add_argument("--live-enc-kv", choices=("f32", "bf16"), default=None, help="with --live-group: what the members' encoder K/V rings hold (vox_stream_group_create_enc_kv; any "
+                    "kind of group).  bf16: half the ring's memory and half the bytes the ring attention reads at every tick; the text may differ from an f32 group's where "
+                    "the model's choice between two tokens is close")
     ap.add_argument("--live-delays", metavar="D,D,...", help="with --live-group: one delay per member (N values; a single value serves all), overriding --delay: the group is "
                     "made with a t_embed per member (vox_stream_group_create_t_embeds), member k's files run at the k-th delay, and every --live-words line gains the "
                     "member's delay")
@@ -508,6 +512,8 @@ def main(argv=None):
         ap.error("--live-page-rows / --live-pool-pages apply with --live-group")
     if a.live_kv is not None and not a.live_group:
         ap.error("--live-kv applies with --live-group")
+    if a.live_enc_kv is not None and not a.live_group:
+        ap.error("--live-enc-kv applies with --live-group")
     if a.live_delays is not None and not a.live_group:
         ap.error("--live-delays applies with --live-group")
     if a.live_delays is not None:
@@ -619,7 +625,7 @@ def main(argv=None):
                         write_word_lines(rec_out, runner.words.get((i, k), []))
     if a.live_group:
         try:
-            texts = transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_group, words_out, a.live_peek, a.live_alternatives, a.live_page_rows, a.live_pool_pages, a.live_endless, a.live_suspend_every, a.live_kv, a.live_delays, a.live_levels, a.live_endpoint_ms, a.live_endpoint_db, a.live_attn_split)
+            texts = transcribe_live_group(pkg, paths, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_group, words_out, a.live_peek, a.live_alternatives, a.live_page_rows, a.live_pool_pages, a.live_endless, a.live_suspend_every, a.live_kv, a.live_delays, a.live_levels, a.live_endpoint_ms, a.live_endpoint_db, a.live_attn_split, a.live_enc_kv)
         except Exception as e:      # the files fall back to one live session each
             log(f"Error in the stream group: {e}"); texts = {}
             if words_out is not None:      # the files' words come again with their lines

@@ -1357,7 +1357,9 @@ extern "C" int32_t vox_debug_attn_decode_split(vox_ctx* c, const vox_attn_decode
 // burst: vox_debug_stream_attn_burst -- rows up to 64, and the ONE launch is launch_stream_attn_burst
 // rows_per_slot (vox_debug_stream_attn_group_burst; null: every slot has d->rows rows): slot z has rows_per_slot[z] rows, a multiple of 4 in 4..64, d->rows is the
 // largest of them; qkv and out hold the slots' rows back to back, and the ONE launch is launch_stream_attn_group_burst with rpt = 4
-static int32_t stream_attn_debug(vox_ctx* c, const vox_stream_attn_desc* d, const float* qkv, float* kring, float* vring, float* out, bool burst, const int32_t* rows_per_slot = nullptr) {
+// ring_dtype (vox_debug_stream_attn_elem; RING_F32: the three entries above it): RING_BF16 -- kring / vring hold 16-bit elements, going in and coming out
+static int32_t stream_attn_debug(vox_ctx* c, const vox_stream_attn_desc* d, const float* qkv, void* kring, void* vring, float* out, bool burst, const int32_t* rows_per_slot = nullptr,
+                                 int ring_dtype = vox::RING_F32) {
     ARGCHK(c && d && qkv && kring && vring && out, "null argument"); ARGCHK(d->order && d->enc_pos, "null argument (order, enc_pos)");
     ARGCHK(d->head_dim == 64 || d->head_dim == 128, "head_dim %d: the ring attention serves head_dim 64 and 128", d->head_dim);
     const int max_rows = burst ? 64 : 8;
@@ -1415,30 +1417,31 @@ static int32_t stream_attn_debug(vox_ctx* c, const vox_stream_attn_desc* d, cons
     VOXCHK(ctx_bind(c));
     hipStream_t s = c->stream;
     const size_t layer_f = (size_t)H * d->cap * hd, mem_f = (size_t)d->layers * layer_f, ring_f = (size_t)NM * mem_f, qkv_f = (size_t)rows_all * 3 * QD, out_f = (size_t)rows_all * QD;
+    const size_t es = ring_dtype == vox::RING_BF16 ? 2 : 4;      // bytes of a ring element; layer_f, mem_f and ring_f count elements
     DevBuf dqkv, dk, dv, dout, drope, dint, dmem, ddesc;
-    HIPCHK(dqkv.alloc(qkv_f * 4)); HIPCHK(dk.alloc(ring_f * 4)); HIPCHK(dv.alloc(ring_f * 4)); HIPCHK(dout.alloc(out_f * 4)); HIPCHK(drope.alloc(rope.size() * 4));
+    HIPCHK(dqkv.alloc(qkv_f * 4)); HIPCHK(dk.alloc(ring_f * es)); HIPCHK(dv.alloc(ring_f * es)); HIPCHK(dout.alloc(out_f * 4)); HIPCHK(drope.alloc(rope.size() * 4));
     HIPCHK(dint.alloc(((size_t)NM * STRM_WORDS + n) * 4)); HIPCHK(dmem.alloc((size_t)NM * sizeof(StreamMember)));
     int* d_state = dint.as<int>(); int* d_order = d_state + (size_t)NM * STRM_WORDS;
     std::vector<int> state((size_t)NM * STRM_WORDS, 0); std::vector<StreamMember> mem((size_t)NM, StreamMember{});
     for (int i = 0; i < NM; i++) {
         state[(size_t)i * STRM_WORDS + STRM_ENC_POS] = d->enc_pos[i];
-        mem[i].state = d_state + (size_t)i * STRM_WORDS; mem[i].kring = dk.as<float>() + (size_t)i * mem_f; mem[i].vring = dv.as<float>() + (size_t)i * mem_f;
+        mem[i].state = d_state + (size_t)i * STRM_WORDS; mem[i].kring = reinterpret_cast<float*>(dk.as<char>() + (size_t)i * mem_f * es); mem[i].vring = reinterpret_cast<float*>(dv.as<char>() + (size_t)i * mem_f * es);
     }
     HIPCHK(hipMemcpyAsync(dqkv.p, qkv, qkv_f * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(dk.p, kring, ring_f * 4, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(dv.p, vring, ring_f * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dk.p, kring, ring_f * es, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(dv.p, vring, ring_f * es, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(drope.p, rope.data(), rope.size() * 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(d_state, state.data(), state.size() * 4, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(d_order, d->order, (size_t)n * 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(dmem.p, mem.data(), mem.size() * sizeof(StreamMember), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(dout.p, 0xff, out_f * 4, s));      // a row the launch does not write stays NaN
     StreamAttnParams ap{}; ap.qkv = dqkv.as<float>(); ap.qkv_stride = 3 * QD; ap.mem = dmem.as<StreamMember>(); ap.order = d_order; ap.n = n; ap.ring_off = (size_t)d->layer * layer_f; ap.cap = d->cap;
     ap.cos_t = drope.as<float>(); ap.sin_t = drope.as<float>() + sin_at; ap.out = dout.as<float>(); ap.out_stride = QD; ap.M = M; ap.n_heads = H; ap.window = d->window;
-    ap.rope_mask = R ? R - 1 : 0; ap.rope_stride = per_member ? R : 0;
+    ap.rope_mask = R ? R - 1 : 0; ap.rope_stride = per_member ? R : 0; ap.ring_dtype = ring_dtype;
     if (rows_per_slot) {
         HIPCHK(ddesc.alloc(sizeof(StreamBurstDesc))); HIPCHK(hipMemcpyAsync(ddesc.p, &bd, sizeof(StreamBurstDesc), hipMemcpyHostToDevice, s));
         HIPCHK(launch_stream_attn_group_burst(ap, ddesc.as<StreamBurstDesc>(), bd, 4, hd, s));
     } else HIPCHK(burst ? launch_stream_attn_burst(ap, hd, s) : launch_stream_attn(ap, hd, s));
     HIPCHK(hipMemcpyAsync(out, dout.p, out_f * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(kring, dk.p, ring_f * 4, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(vring, dv.p, ring_f * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(kring, dk.p, ring_f * es, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(vring, dv.p, ring_f * es, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return VOX_OK;
 }
@@ -1453,6 +1456,15 @@ extern "C" int32_t vox_debug_stream_attn_burst(vox_ctx* c, const vox_stream_attn
 extern "C" int32_t vox_debug_stream_attn_group_burst(vox_ctx* c, const vox_stream_attn_desc* d, const int32_t* rows_per_slot, const float* qkv, float* kring, float* vring, float* out) {
     ARGCHK(rows_per_slot, "null argument");
     return stream_attn_debug(c, d, qkv, kring, vring, out, true, rows_per_slot);
+}
+// the three forms on a ring of either element: form 0 the tick launch, 1 the burst, 2 the ragged burst (rows_per_slot given, null for 0 and 1); enc_kv_dtype VOX_KV_F32:
+// the entry above of that form, VOX_KV_BF16: kring / vring hold 16-bit elements
+extern "C" int32_t vox_debug_stream_attn_elem(vox_ctx* c, const vox_stream_attn_desc* d, int32_t form, int32_t enc_kv_dtype, const int32_t* rows_per_slot, const float* qkv, void* kring,
+                                              void* vring, float* out) {
+    ARGCHK(form >= 0 && form <= 2, "form %d: 0 the tick launch, 1 the burst, 2 the ragged burst", form);
+    ARGCHK(enc_kv_dtype == VOX_KV_F32 || enc_kv_dtype == VOX_KV_BF16, "enc_kv_dtype %d is neither VOX_KV_F32 (0) nor VOX_KV_BF16 (1)", enc_kv_dtype);
+    ARGCHK((form == 2) == (rows_per_slot != nullptr), "rows_per_slot belongs to form 2, the ragged burst, and to no other (form %d)", form);
+    return stream_attn_debug(c, d, qkv, kring, vring, out, form != 0, rows_per_slot, enc_kv_dtype == VOX_KV_BF16 ? vox::RING_BF16 : vox::RING_F32);
 }
 extern "C" int32_t vox_debug_stream_attn_burst_launches(uint64_t* out) {
     ARGCHK(out, "null argument");
@@ -3347,13 +3359,14 @@ static void stream_dec_ungrow(vox_stream* st, DecPlanes* old) {
 // vox_model_set_prefix_cache says -- the model's own setting is restored) copied into the session's ring, its decoder cache rows (`dec`: a cache, or a view of a slab's
 // slice), its tokens and its state block; the session does not look at the model's copy again.  `then`: what the caller enqueues behind the copies; ONE synchronisation.
 template <class Then>
-static int32_t stream_seed(vox_model* m, const float* t_embed, int RC, int PC, int cap, float* kring, float* vring, vox_cache* dec, int* tokens, int* state, int* h_state, Then then) {
+static int32_t stream_seed(vox_model* m, const float* t_embed, int RC, int PC, int cap, float* kring, float* vring, vox_cache* dec, int* tokens, int* state, int* h_state, Then then,
+                           int ring_dtype = vox::RING_F32) {
     const vox_model_cfg& c = m->cfg; hipStream_t s = m->ctx->stream; PrefixState& P = m->pfx;
     const bool was_on = P.on; P.on = true;
     int32_t r = prefix_build(m, t_embed);
     if (r == VOX_OK && !(P.enc_built && P.dec_built && P.RC == RC && P.PC == PC)) r = fail(VOX_ERR_HIP, "the prefix state a stream starts from could not be built");
     auto body = [&]() -> int32_t {
-        HIPCHK(launch_stream_ring_init(P.enc_kv, c.enc_layers, RC, c.enc_heads, c.enc_head_dim, cap, kring, vring, s));
+        HIPCHK(launch_stream_ring_init(P.enc_kv, c.enc_layers, RC, c.enc_heads, c.enc_head_dim, cap, kring, vring, s, ring_dtype));
         if (dec) VOXCHK(prefix_rows_into(m, dec, s));      // (null: `then` places the rows -- a paged group's member)
         VOXCHK(then());
         HIPCHK(prefix_tokens_enqueue(tokens, s));
@@ -3588,7 +3601,7 @@ static int32_t stream_verify(vox_stream* st) {      // inside a long push: befor
 // w1|w3, w2 } -> final norm -> adapter, every weight matrix in ONE launch for all sessions of the round (4 n rows through q4_linear_dev, which picks the kernel by the row
 // count).  Slot z works for session r.order[z] (device arrays); w.arow[z] is its adapter row.  ftap_*: a solo stream's front tap (null: none).
 // rope (null: the model's streaming table): a solo endless session's encoder RoPE ring, rows = position & rope_mask (StreamAttnParams::rope_mask)
-struct StreamRound { const StreamMember* mem; const int* order; int n, cap; size_t ring_layer; MelTables mel; long left; const float* rope = nullptr; int rope_mask = 0, rope_stride = 0; bool levels = false; };      // rope_stride > 0: an endless group's rings, one per member; levels: some session of the round has levels on
+struct StreamRound { const StreamMember* mem; const int* order; int n, cap; size_t ring_layer; MelTables mel; long left; const float* rope = nullptr; int rope_mask = 0, rope_stride = 0; bool levels = false; int ring_dtype = vox::RING_F32; };      // rope_stride > 0: an endless group's rings, one per member; levels: some session of the round has levels on; ring_layer counts elements of ring_dtype
 // b > 1 (a solo burst stream's round of one, n == 1): the encoder of b ticks in one pass.  Everything the b ticks would read is there before the first (the pass's
 // samples, the state block at the burst's first tick), and tick t's rows are rows 4 t .. of every buffer: 16 b + 3 halo frames, 8 b + 1 and 4 b conv windows, 4 b rows
 // through the layers with the burst attention, b adapter rows (w.arow[t]: tick t's).  ftap_*: room for ftap_b of the burst's ticks, in the per-tick layout.
@@ -3626,7 +3639,7 @@ static int32_t stream_encode_round(vox_model* m, const StreamWs& w, const Stream
         VOXCHK(q4_linear_dev(cx, L.wqkv.w, L.wqkv.bias, xn, D, M, w.qkv, 3 * QD));
         StreamAttnParams ap{}; ap.qkv = w.qkv; ap.qkv_stride = 3 * QD; ap.mem = r.mem; ap.order = r.order; ap.n = n; ap.ring_off = (size_t)l * r.ring_layer; ap.cap = r.cap;
         ap.cos_t = m->enc_cos_s; ap.sin_t = m->enc_sin_s; ap.out = w.att;
-        if (r.rope) { ap.cos_t = r.rope; ap.sin_t = r.rope + hd / 2; ap.rope_mask = r.rope_mask; ap.rope_stride = r.rope_stride; } ap.out_stride = QD; ap.M = R * b; ap.n_heads = H; ap.window = c.enc_window;
+        if (r.rope) { ap.cos_t = r.rope; ap.sin_t = r.rope + hd / 2; ap.rope_mask = r.rope_mask; ap.rope_stride = r.rope_stride; } ap.out_stride = QD; ap.M = R * b; ap.n_heads = H; ap.window = c.enc_window; ap.ring_dtype = r.ring_dtype;
         if (rg) HIPCHK(launch_stream_attn_group_burst(ap, rg->dev, *rg->host, R, hd, s));
         else HIPCHK(b >= 2 ? launch_stream_attn_burst(ap, hd, s) : launch_stream_attn(ap, hd, s));
         VOXCHK(q4_linear_dev(cx, L.wo.w, L.wo.bias, w.att, QD, M, x, D, EPI_RESID, x, D));
@@ -3786,9 +3799,9 @@ static int32_t keep_reserve(KeepArea& a, size_t need, uint64_t* bytes, hipStream
 }
 // a peek's ring keep (launch_stream_keep; restore 0 in front of the tail's ticks, 1 in front of the call's synchronisation): slot z saves or puts back the state block
 // of session order[z] and the `rows` encoder ring rows its tail writes
-static StreamKeepParams ring_keep(const vox_model_cfg& c, const StreamMember* mem, const int* order, int n, int rows, int cap, float* keep) {
+static StreamKeepParams ring_keep(const vox_model_cfg& c, const StreamMember* mem, const int* order, int n, int rows, int cap, float* keep, int ring_dtype = vox::RING_F32) {
     StreamKeepParams kp{}; kp.mem = mem; kp.order = order; kp.n = n; kp.layers = c.enc_layers; kp.n_heads = c.enc_heads; kp.hd = c.enc_head_dim; kp.cap = cap;
-    kp.rows = rows; kp.keep = keep; kp.slot_stride = stream_keep_floats(c.enc_layers, c.enc_heads, c.enc_head_dim, rows);
+    kp.rows = rows; kp.keep = keep; kp.ring_dtype = ring_dtype; kp.slot_stride = stream_keep_floats(c.enc_layers, c.enc_heads, c.enc_head_dim, rows, ring_dtype);
     return kp;
 }
 
@@ -4410,6 +4423,10 @@ struct vox_stream_group {
     // a bf16 paged group (vox_stream_group_create_kv with VOX_KV_BF16; DESIGN.md section 8, "A bf16 K/V pool"): dec_k / dec_v point at uint16_t pools of the same layout
     // -- page_floats, seq_stride and layer_stride then count 16-bit elements.  The allocator, the tables and every refusal are the f32 paged group's
     bool kv_bf16 = false;
+    // a group with a bf16 ENCODER ring (vox_stream_group_create_enc_kv with VOX_KV_BF16; DESIGN.md section 8, "A bf16 encoder ring"): kring / vring point at uint16_t
+    // rings of the same shape -- ring_layer and ring_member then count 16-bit elements, and every member's StreamMember::kring / vring is its slice of those.  Any kind
+    // of group; RING_F32: every other group
+    int enc_dtype = vox::RING_F32;
     // An ENDLESS paged group (vox_stream_group_create_endless; DESIGN.md section 8, "Endless paged groups"): g.max_pos is 2^24; the pool's tables are rings of pool_pages
     // entries (d_tab [n][pool.tab_len]); every member has its own token row and record lists (GroupMember::tokens, lists_cap), grown by doubling; and the group owns
     // two member-strided device RoPE rings -- decoder [n][GROUP_ROPE_ROWS][cos hd/2 | sin hd/2], encoder [n][R GROUP_ROPE_ROWS][..] -- with their pinned host images,
@@ -4502,7 +4519,7 @@ static int32_t group_member_seed(vox_stream_group* g, int i) {
                                else VOXCHK(group_table_upload(g, i, 0, std::max(q1, t1)));
                                HIPCHK(launch_stream_pages_seed(g->m->pfx.dec_k, g->m->pfx.dec_v, c.dec_layers, c.dec_kv_heads, g->g.PC, c.dec_head_dim, g->d_tab + (size_t)i * g->pool.tab_len,
                                                                g->pool.shift, g->layer_stride, g->dec_k, g->dec_v, g->ctx->stream, g->kv_bf16));
-                               return VOX_OK; }));
+                               return VOX_OK; }, g->enc_dtype));
         me.feed.restart(g->g.PC); me.steps = 0; me.sc.host.clear(); me.al.restart(); me.lv.restart();
         return group_member_ada(g, i);
     }
@@ -4510,7 +4527,7 @@ static int32_t group_member_seed(vox_stream_group* g, int i) {
     view.layer_stride = g->layer_stride;      // the member's slice of the slab, seen as a cache whose layers lie layer_stride apart
     GroupMember& me = g->mem[i];
     VOXCHK(stream_seed(g->m, group_t_embed(g, i).data(), g->g.RC, g->g.PC, g->g.cap, g->h_mem[i].kring, g->h_mem[i].vring, &view, g->h_mem[i].tokens, g->h_mem[i].state, me.h_state,
-                       []() -> int32_t { return VOX_OK; }));
+                       []() -> int32_t { return VOX_OK; }, g->enc_dtype));
     me.feed.restart(g->g.PC); me.steps = 0; me.sc.host.clear(); me.al.restart(); me.lv.restart();
     return group_member_ada(g, i);
 }
@@ -4532,7 +4549,7 @@ static void group_release(vox_stream_group* g) {
 // per_member: t_embed holds [n_members][dec_dim], one delay per member (vox_stream_group_create_t_embeds); else one [dec_dim] vector for all
 static int32_t group_create(vox_model* m, const float* t_embed, int32_t n_members, const float* gains, const uint32_t* rates, int32_t enc_capacity_rows,
                             int32_t max_positions, int32_t page_rows, int32_t pool_pages, vox_stream_group** out, bool endless = false, bool kv_bf16 = false, int burst = 1,
-                            bool per_member = false) {
+                            bool per_member = false, int enc_dtype = vox::RING_F32) {
     ARGCHK(burst >= 1 && burst <= VOX_STREAM_BURST_MAX, "burst_ticks %d out of range (1..%d)", burst, VOX_STREAM_BURST_MAX);
     ARGCHK(n_members >= 1 && n_members <= GROUP_MAX, "n_members %d out of range (1..%d)", n_members, GROUP_MAX); ARGCHK(m && t_embed && out, "null argument");
     for (int i = 0; gains && i < n_members; i++) ARGCHK(std::isfinite(gains[i]), "gain of member %d is not finite", i);
@@ -4572,7 +4589,7 @@ static int32_t group_create(vox_model* m, const float* t_embed, int32_t n_member
     vox_stream_group* g = new vox_stream_group(); g->m = m; g->ctx = cx; g->n = n_members;
     if (per_member) for (int i = 0; i < n_members; i++) g->member_te.emplace_back(t_embed + (size_t)i * c.dec_dim, t_embed + (size_t)(i + 1) * c.dec_dim);
     else g->t_embed.assign(t_embed, t_embed + c.dec_dim);
-    g->g = sg; g->endless = endless; g->kv_bf16 = kv_bf16; g->burst = burst;
+    g->g = sg; g->endless = endless; g->kv_bf16 = kv_bf16; g->burst = burst; g->enc_dtype = enc_dtype;
     const size_t N = (size_t)n_members; const int D = c.dec_dim, QD = c.dec_heads * c.dec_head_dim, W = QD + 2 * c.dec_kv_heads * c.dec_head_dim, maxp = sg.max_pos;
     g->ring_layer = (size_t)c.enc_heads * sg.cap * c.enc_head_dim; g->ring_member = (size_t)c.enc_layers * g->ring_layer;
     g->seq_stride = (size_t)c.dec_kv_heads * maxp * c.dec_head_dim; g->layer_stride = N * g->seq_stride;
@@ -4584,7 +4601,8 @@ static int32_t group_create(vox_model* m, const float* t_embed, int32_t n_member
     const size_t ws_b = stream_ws_carve(m, n_members, nullptr, nullptr, burst) * 4, slab_b = (size_t)c.dec_layers * g->layer_stride * (kv_bf16 ? 2 : 4);
     hipError_t e = hipSuccess;
     auto A = [&](void** q, size_t nb, bool zero) { if (e == hipSuccess) { e = hipMalloc(q, nb); if (e == hipSuccess) { g->bytes += nb; if (zero) e = hipMemsetAsync(*q, 0, nb, s); } } };
-    A((void**)&g->kring, N * g->ring_member * 4, false); A((void**)&g->vring, N * g->ring_member * 4, false); A((void**)&g->dec_k, slab_b, true); A((void**)&g->dec_v, slab_b, true);
+    const size_t ring_es = enc_dtype == vox::RING_BF16 ? 2 : 4;      // bytes of an encoder ring element
+    A((void**)&g->kring, N * g->ring_member * ring_es, false); A((void**)&g->vring, N * g->ring_member * ring_es, false); A((void**)&g->dec_k, slab_b, true); A((void**)&g->dec_v, slab_b, true);
     A((void**)&g->samples, N * STREAM_SAMPLE_RING * 4, true); A((void**)&g->ws, ws_b, true); if (!endless) A((void**)&g->tokens, N * (maxp + 2) * 4, true); A((void**)&g->state, N * sizeof(int) * STRM_WORDS, true);
     A((void**)&g->d_mem, N * sizeof(StreamMember), true); A((void**)&g->d_order, 5 * GROUP_MAX * 4, true);
     if (paged) A((void**)&g->d_tab, N * (size_t)g->pool.tab_len * 4, false); A((void**)&g->d_ingest, sizeof(GroupIngest), true);
@@ -4613,7 +4631,7 @@ static int32_t group_create(vox_model* m, const float* t_embed, int32_t n_member
     for (size_t i = 0; i < N; i++) {
         StreamMember& me = g->h_mem[i]; me = StreamMember{};
         me.samples = g->samples + i * STREAM_SAMPLE_RING; me.gain = gains ? gains[i] : 1.0f; me.state = g->state + i * STRM_WORDS;
-        me.kring = g->kring + i * g->ring_member; me.vring = g->vring + i * g->ring_member; me.tokens = endless ? g->mem[i].tokens : g->tokens + i * (size_t)(maxp + 2);
+        me.kring = reinterpret_cast<float*>(reinterpret_cast<char*>(g->kring) + i * g->ring_member * ring_es); me.vring = reinterpret_cast<float*>(reinterpret_cast<char*>(g->vring) + i * g->ring_member * ring_es); me.tokens = endless ? g->mem[i].tokens : g->tokens + i * (size_t)(maxp + 2);
     }
     int32_t r = ctx_mel_tables(cx, &g->mel);
     if (r == VOX_OK) r = group_upload_members(g);
@@ -4669,6 +4687,28 @@ extern "C" int32_t vox_stream_group_create_t_embeds(vox_model* m, const float* t
     ARGCHK(page_rows >= 0, "page_rows %d is negative", page_rows);
     ARGCHK(!endless || max_positions == 0, "an endless group takes no max_positions (%d): its members go on to the session limit", max_positions);
     return group_create(m, t_embeds, n_members, gains, rates, enc_capacity_rows, endless ? 0 : max_positions, paged ? page_rows : -1, pool_pages, out, endless != 0, kv_dtype == VOX_KV_BF16, burst_ticks, true);
+}
+// the full-argument creator plus the encoder ring's element: VOX_KV_F32 is vox_stream_group_create_t_embeds, call for call
+extern "C" int32_t vox_stream_group_create_enc_kv(vox_model* m, const float* t_embeds, int32_t n_members, const float* gains, const uint32_t* rates, int32_t enc_capacity_rows,
+                                                  int32_t max_positions, int32_t paged, int32_t page_rows, int32_t pool_pages, int32_t endless, int32_t kv_dtype, int32_t burst_ticks,
+                                                  int32_t enc_kv_dtype, vox_stream_group** out) {
+    ARGCHK(enc_kv_dtype == VOX_KV_F32 || enc_kv_dtype == VOX_KV_BF16, "enc_kv_dtype %d is neither VOX_KV_F32 (0) nor VOX_KV_BF16 (1)", enc_kv_dtype);
+    if (enc_kv_dtype == VOX_KV_F32) return vox_stream_group_create_t_embeds(m, t_embeds, n_members, gains, rates, enc_capacity_rows, max_positions, paged, page_rows, pool_pages, endless, kv_dtype, burst_ticks, out);
+    ARGCHK(m && t_embeds && out, "null argument");
+    ARGCHK(n_members >= 1 && n_members <= GROUP_MAX, "n_members %d out of range (1..%d)", n_members, GROUP_MAX);      // (before t_embeds is read as n_members rows)
+    ARGCHK(burst_ticks >= 1 && burst_ticks <= VOX_STREAM_BURST_MAX, "burst_ticks %d out of range (1..%d)", burst_ticks, VOX_STREAM_BURST_MAX);
+    ARGCHK(paged == 0 || paged == 1, "paged %d is neither 0 nor 1", paged); ARGCHK(endless == 0 || endless == 1, "endless %d is neither 0 nor 1", endless);
+    ARGCHK(kv_dtype == VOX_KV_F32 || kv_dtype == VOX_KV_BF16, "kv_dtype %d is neither VOX_KV_F32 (0) nor VOX_KV_BF16 (1)", kv_dtype);
+    ARGCHK(paged || (!page_rows && !pool_pages && !endless && kv_dtype == VOX_KV_F32), "a slab group (paged 0) takes no page_rows, pool_pages, endless or bf16 pool");
+    ARGCHK(page_rows >= 0, "page_rows %d is negative", page_rows);
+    ARGCHK(!endless || max_positions == 0, "an endless group takes no max_positions (%d): its members go on to the session limit", max_positions);
+    return group_create(m, t_embeds, n_members, gains, rates, enc_capacity_rows, endless ? 0 : max_positions, paged ? page_rows : -1, pool_pages, out, endless != 0, kv_dtype == VOX_KV_BF16, burst_ticks, true,
+                        vox::RING_BF16);
+}
+extern "C" int32_t vox_stream_group_enc_kv_dtype(const vox_stream_group* g, int32_t* out) {
+    ARGCHK(g && out, "null argument");
+    *out = g->enc_dtype == vox::RING_BF16 ? VOX_KV_BF16 : VOX_KV_F32;
+    return VOX_OK;
 }
 extern "C" int32_t vox_stream_group_t_embed(const vox_stream_group* g, int32_t member, float* out, int32_t cap) {
     ARGCHK(g && out, "null argument"); ARGCHK(member >= 0 && member < g->n, "member %d out of range (0..%d)", member, g->n - 1);
@@ -4743,7 +4783,7 @@ extern "C" int32_t vox_stream_group_info(const vox_stream_group* g, int32_t memb
 }
 
 static StreamRound group_stream_round(const vox_stream_group* g, int n_r) {
-    StreamRound r{g->d_mem, g->d_order, n_r, g->g.cap, g->ring_layer, g->mel, g->g.left}; r.levels = g->n_leveled > 0;      // (slots of members with levels off return at once)
+    StreamRound r{g->d_mem, g->d_order, n_r, g->g.cap, g->ring_layer, g->mel, g->g.left}; r.levels = g->n_leveled > 0; r.ring_dtype = g->enc_dtype;      // (slots of members with levels off return at once)
     if (g->endless) { r.rope = g->rope.enc; r.rope_stride = GROUP_ROPE_ROWS * g->m->cfg.reshape_factor; r.rope_mask = r.rope_stride - 1; }      // every position: the member's ring row (group_rope_refill)
     return r;
 }
@@ -5011,7 +5051,7 @@ static int32_t group_run(vox_stream_group* g, vox_stream_feed* feeds, int32_t n_
         const size_t nb = (size_t)g->n * STREAM_SAMPLE_RING * 2;
         HIPCHK(hipMalloc((void**)&g->s16_stage, nb)); g->bytes += nb;
     }
-    if (call.peek) VOXCHK(keep_reserve(g->keep, GROUP_MAX + (size_t)n * stream_keep_floats(c.enc_layers, c.enc_heads, c.enc_head_dim, keep_rows), &g->bytes, s, "group"));
+    if (call.peek) VOXCHK(keep_reserve(g->keep, GROUP_MAX + (size_t)n * stream_keep_floats(c.enc_layers, c.enc_heads, c.enc_head_dim, keep_rows, g->enc_dtype), &g->bytes, s, "group"));
     if (m->pw_pend_rows > 0) VOXCHK(pw_sync(m));
     if (!g->ada) VOXCHK(vox_model_set_t_embed(m, g->t_embed.data()));      // (a delay per member: the round reads the group's own scales, the model's t_embed stays what it is)
     for (GroupFeed& e : call.fs) g->mem[e.member].feed.n_pushed += (int64_t)e.plan.n;
@@ -5019,7 +5059,7 @@ static int32_t group_run(vox_stream_group* g, vox_stream_feed* feeds, int32_t n_
     if (g->paged) { if (call.peek) { pool_was = g->pool.mark(); for (const GroupFeed& e : call.fs) took.push_back(e.member); } VOXCHK(group_take_pages(g, call)); }
     if (!call.peek) { VOXCHK(group_body(g, feeds, call, nullptr, nullptr)); return g->paged ? group_release_pages(g, call) : VOX_OK; }
     // a peek: the peeking members are the ring keep's slots, their numbers the first 16 ints of the save area
-    const StreamKeepParams keep = ring_keep(c, g->d_mem, reinterpret_cast<const int*>(g->keep.p), n, keep_rows, g->g.cap, g->keep.p + GROUP_MAX);
+    const StreamKeepParams keep = ring_keep(c, g->d_mem, reinterpret_cast<const int*>(g->keep.p), n, keep_rows, g->g.cap, g->keep.p + GROUP_MAX, g->enc_dtype);
     std::vector<GroupMark> was; for (const GroupFeed& e : call.fs) was.push_back(GroupMark{g->mem[e.member].feed.mark(), g->mem[e.member].steps});
     const uint64_t rounds_was[3] = {g->burst_rounds, g->burst_member_ticks, g->plain_rounds};      // (a peek's rounds are not counted, as a solo burst stream's)
     const int32_t r = group_body(g, feeds, call, &keep, peek_scores);
@@ -5141,7 +5181,7 @@ static SnapSession group_session(vox_stream_group* g, int i) {
     SnapSession ss{}; ss.m = g->m; ss.ctx = g->ctx; ss.t_embed = &group_t_embed(g, i); ss.feed = &me.feed; ss.sc = &me.sc; ss.al = &me.al; ss.lv = &me.lv; ss.gain = hm.gain;
     ss.tokens = hm.tokens; ss.samples = const_cast<float*>(hm.samples); ss.state = hm.state; ss.h_state = me.h_state; ss.cap = g->g.cap; ss.PC = g->g.PC; ss.max_pos = g->g.max_pos; ss.who = who;
     ss.enc.cache_k = hm.kring; ss.enc.cache_v = hm.vring; ss.enc.layers = c.enc_layers; ss.enc.heads = c.enc_heads; ss.enc.hd = c.enc_head_dim;
-    ss.enc.layout = vox::SNAP_RING; ss.enc.cap = g->g.cap; ss.enc.layer_stride = g->ring_layer; ss.enc.head_stride = (size_t)g->g.cap * c.enc_head_dim;
+    ss.enc.layout = vox::SNAP_RING; ss.enc.cap = g->g.cap; ss.enc.layer_stride = g->ring_layer; ss.enc.head_stride = (size_t)g->g.cap * c.enc_head_dim; ss.enc.kv_bf16 = g->enc_dtype == vox::RING_BF16 ? 1 : 0;
     ss.dec.layers = c.dec_layers; ss.dec.heads = c.dec_kv_heads; ss.dec.hd = c.dec_head_dim; ss.dec.layer_stride = g->layer_stride;
     if (g->paged) {
         ss.dec.cache_k = g->dec_k; ss.dec.cache_v = g->dec_v; ss.dec.layout = g->endless ? vox::SNAP_PAGED_RING : vox::SNAP_PAGED; ss.dec.head_stride = (size_t)g->pool.page_rows * c.dec_head_dim;

@@ -518,10 +518,14 @@ hipError_t launch_stream_group_s16(const StreamS16* desc, const StreamS16* host,
 // one encoder layer's attention for the round's n x M rows (M <= 8 per session, slot z's rows at z * M) against each session's own K / V ring: RoPE on q and k at the
 // session's absolute stream position, k / v appended at position % cap, query m attends the keys j <= position_m, position_m - j <= window in ascending order of j (the
 // ring changes addresses, not the order).  cap > window + M.
+// The ring's element ("A bf16 encoder ring"): RING_F32, or RING_BF16 -- a stream group created with enc_kv_dtype = VOX_KV_BF16.  Every launcher that
+// touches the ring takes one of the two and refuses any other value with hipErrorInvalidValue before it launches.
+enum RingDtype { RING_F32 = 0, RING_BF16 = 1 };
 struct StreamAttnParams {
     const float* qkv; int qkv_stride;        // [n M][q | k | v], each n_heads * hd wide, not rotated
     const StreamMember* mem; const int* order; int n;
-    size_t ring_off; int cap;                // this layer's ring inside a session's kring / vring (floats), [n_heads][cap][hd]
+    size_t ring_off; int cap;                // this layer's ring inside a session's kring / vring, [n_heads][cap][hd]; ring_off counts ELEMENTS of the ring (floats, or
+                                             // 16-bit values with RING_BF16), a multiple of 4 in both; cap counts rows
     const float* cos_t; const float* sin_t;  // [positions][hd / 2]
     float* out; int out_stride;              // [n M][n_heads * hd]
     int M, n_heads, window;
@@ -529,6 +533,10 @@ struct StreamAttnParams {
                                              // rope_mask + 1 rows [cos hd/2 | sin hd/2] (sin_t = cos_t + hd / 2), row = position & rope_mask, refilled by the host for the tick's positions
     int rope_stride;                         // with rope_mask > 0: 0 (the default) one ring for every slot; > 0 (an endless group): a ring per session, rope_stride rows apart --
                                              // slot z reads row order[z] * rope_stride + (position & rope_mask)
+    int ring_dtype;                          // RingDtype.  RING_BF16: StreamMember::kring / vring point at uint16_t rings of the same shape.  K is rotated in f32 as ever, then
+                                             // rounded by kv_bf16_round (vox_kv_bf16.h) and stored; V is rounded and stored; q is never rounded.  The launch's OWN keys and values
+                                             // enter the scores and the sums as those rounded values widened again, so a key has the same bits in this launch and from the ring
+                                             // one tick later: the three forms below keep their bit contracts with one another on a bf16 ring
 };
 hipError_t launch_stream_attn(const StreamAttnParams& p, int hd, hipStream_t s);
 // the same attention for a burst of ticks: 1 <= M <= 64 rows per session (b ticks' 4 b rows, all at STRM_ENC_POS + m), cap > window + M, and with a RoPE ring
@@ -552,7 +560,8 @@ hipError_t launch_stream_attn_group_burst(const StreamAttnParams& a, const Strea
 // of dst -- the encoder input, slot after slot.  max_b: the largest b of the round (the grid)
 hipError_t launch_stream_burst_pack(const float* src, int src_slot_rows, const StreamBurstDesc* desc, int n, int rpt, int max_b, int D, float* dst, hipStream_t s);
 // rows 0 .. rows-1 of every layer's ring from token-major k | v rows (the model's prefix state: [layers][rows][k row | v row])
-hipError_t launch_stream_ring_init(const float* kv, int layers, int rows, int n_heads, int hd, int cap, float* kring, float* vring, hipStream_t s);
+// ring_dtype RING_BF16: kring / vring point at uint16_t rings, the rows are rounded by kv_bf16_round
+hipError_t launch_stream_ring_init(const float* kv, int layers, int rows, int n_heads, int hd, int cap, float* kring, float* vring, hipStream_t s, int ring_dtype = RING_F32);
 // h = audio_row + embed(tokens[STRM_POS]); the adapter row is also kept in audio_keep[STRM_POS % keep_rows] (an engine hand-off timeout re-runs the decode steps from there)
 hipError_t launch_stream_embed(Q4W tok, const int* tokens, const float* audio_row, float* audio_keep, int keep_rows, int D, const int* state, float* h, hipStream_t s);
 // the same input from the kept row (the re-run)
@@ -631,12 +640,15 @@ hipError_t launch_stream_level(const StreamMember* mem, const int* order, int n,
 // restore = 0 (save, in front of the ticks): the state block, and of every (layer, head) of K and V the `rows` ring rows from STRM_HEAD on, modulo cap -- the slots the
 // next rows / 4 ticks write.  restore = 1 (behind them): the same rows back from where the SAVED block's STRM_HEAD points, then the block itself.  16-byte accesses, no
 // arithmetic on the values; the launch arguments of the two directions of a call are the same.  rows <= cap, hd % 4 == 0.
+// ring_dtype RING_BF16: the rings hold 16-bit values and so does the area -- K and V are half as long, the copies move 8 bytes (4 values) where they moved 16.
+// slot_stride counts floats (4 bytes) in both.
 struct StreamKeepParams {
     const StreamMember* mem; const int* order; int n;
     int layers, n_heads, hd, cap, rows;
     float* keep; size_t slot_stride;
+    int ring_dtype;      // RingDtype
 };
-size_t stream_keep_floats(int layers, int n_heads, int hd, int rows);      // one slot's area
+size_t stream_keep_floats(int layers, int n_heads, int hd, int rows, int ring_dtype = RING_F32);      // one slot's area, in floats
 hipError_t launch_stream_keep(const StreamKeepParams& p, int restore, hipStream_t s);
 // ---- a session blob's K / V sections (vox_stream_snapshot / vox_stream_restore; DESIGN.md section 8, "Snapshot and resume"): ONE launch moves the logical rows
 // lo .. hi - 1 of the planes plane0 .. plane0 + n_planes - 1 (plane = layer * heads + head) of K and of V between the blob's dense layout -- blob_k / blob_v
@@ -658,8 +670,8 @@ struct SnapshotKvParams {
     int cap;                                // SNAP_RING
     const int* tab; int shift, tab_len;     // SNAP_PAGED / SNAP_PAGED_RING: device table of the session, log2(page_rows); tab_len: SNAP_PAGED the entries the table has, SNAP_PAGED_RING the ring's
     size_t page_floats;                     // floats between two pages of one layer
-    // SNAP_PAGED / SNAP_PAGED_RING on a bf16 pool: cache_k / cache_v point at uint16_t pools, the three strides count 16-bit elements.  Pack widens (exact), restore
-    // rounds by kv_bf16_round (exact for a blob packed from a bf16 pool); the blob holds f32 rows either way
+    // SNAP_PAGED / SNAP_PAGED_RING on a bf16 pool, SNAP_RING on a bf16 encoder ring: cache_k / cache_v point at uint16_t rows, the three strides count 16-bit
+    // elements.  Pack widens (exact), restore rounds by kv_bf16_round (exact for a blob packed from 16-bit rows); the blob holds f32 rows either way
     int kv_bf16;
 };
 // host: every table entry the range lo .. hi - 1 touches lies in 0 .. pool_pages - 1 (tab: the HOST copy of the table); *bad_page: the first logical page that does not

@@ -4956,8 +4956,31 @@ hipError_t launch_stream_group_s16(const StreamS16* desc, const StreamS16* host,
 // with cap > window + M the rows written now hold positions no query of the tick sees any more.  Scores: 16 lanes per key (one float4 each at hd 64), the keys in
 // ascending position; softmax and the weighted sum in fixed order over the key index relative to the window start -- the ring capacity changes addresses only.
 // (VOX_NO_PK_F32: the rotation is the pair arithmetic of rope_kernel.)
-template <int HD>
+// T: the ring's element (StreamAttnParams::ring_dtype), through RingElem -- KvElem's loads and kv_bf16_round under the four names the ring kernels need:
+//   ld4   the 4 values a lane takes of a key: a float4, or ONE 8-byte load of 4 16-bit values widened in registers -- the lane keeps its 4 elements, so row16_sum adds
+//         the partial sums it always added
+//   ld1   the value thread (d, kg) takes of a v row: a float, or one 16-bit load widened.  The thread keeps its ONE column d (a second element per load would move
+//         column d + 1 to this thread and with it the G strided sums); the 64 lanes of a wave still read one contiguous piece of the row, 128 bytes where it was 256
+//   own   what a k or v value of the launch itself becomes before anything reads it: itself, or widen(round(x)) -- the bits the ring hands out one tick later
+//   put   the stored element: the value, or kv_bf16_round of it (exact on what `own` made)
+// ring_off, and every offset added to kring / vring, counts elements of T.  The LDS of the two instantiations is the same: kn and vn hold f32 either way.
+template <class T> struct RingElem;
+template <> struct RingElem<float> {
+    static __device__ __forceinline__ float4 ld4(const float* q) { return *reinterpret_cast<const float4*>(q); }
+    static __device__ __forceinline__ float ld1(const float* q) { return *q; }
+    static __device__ __forceinline__ float own(float x) { return x; }
+    static __device__ __forceinline__ float put(float x) { return x; }
+};
+template <> struct RingElem<uint16_t> {
+    static __device__ __forceinline__ float4 ld4(const uint16_t* q) { return KvElem<uint16_t>::wv(KvElem<uint16_t>::ldv<false>(q)); }
+    static __device__ __forceinline__ float ld1(const uint16_t* q) { return kv_bf16_widen(*q); }
+    static __device__ __forceinline__ float own(float x) { return kv_bf16_widen(kv_bf16_round(x)); }
+    static __device__ __forceinline__ uint16_t put(float x) { return kv_bf16_round(x); }
+};
+static bool ring_dtype_ok(int dt) { return dt == RING_F32 || dt == RING_BF16; }
+template <int HD, class T = float>
 __global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_attn_kernel(const StreamAttnParams p) {
+    using E = RingElem<T>;
     constexpr int HALF = HD / 2, G = 256 / HD;
     __shared__ __attribute__((aligned(16))) float qs[HD];
     __shared__ __attribute__((aligned(16))) float kn[8][HD];
@@ -4967,7 +4990,7 @@ __global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_attn_kernel(const St
     __shared__ float wred[4];
     const int h = blockIdx.x, m = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const StreamMember& me = p.mem[p.order[blockIdx.z]];
-    float* __restrict__ kring = me.kring + p.ring_off; float* __restrict__ vring = me.vring + p.ring_off;
+    T* __restrict__ kring = reinterpret_cast<T*>(me.kring) + p.ring_off; T* __restrict__ vring = reinterpret_cast<T*>(me.vring) + p.ring_off;
     const float* __restrict__ qkv = p.qkv + (size_t)blockIdx.z * p.M * p.qkv_stride;      // the slot's M rows
     const int enc_pos = me.state[STRM_ENC_POS], qpos = enc_pos + m, QD = p.n_heads * HD;
     for (int i = tid; i < (m + 2) * HALF; i += 256) {      // k rows 0 .. m, then the query row
@@ -4979,11 +5002,12 @@ __global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_attn_kernel(const St
         const float xr = src[0], xi = src[1];
         float* dst = isq ? qs : kn[r];
         dst[2 * j] = xr * c - xi * sn; dst[2 * j + 1] = xr * sn + xi * c;
+        if constexpr (!std::is_same<T, float>::value) if (!isq) { dst[2 * j] = E::own(dst[2 * j]); dst[2 * j + 1] = E::own(dst[2 * j + 1]); }      // (q is never rounded)
     }
-    for (int i = tid; i < (m + 1) * HD; i += 256) { const int r = i / HD, d = i - r * HD; vn[r][d] = qkv[(size_t)r * p.qkv_stride + 2 * QD + h * HD + d]; }
+    for (int i = tid; i < (m + 1) * HD; i += 256) { const int r = i / HD, d = i - r * HD; vn[r][d] = E::own(qkv[(size_t)r * p.qkv_stride + 2 * QD + h * HD + d]); }
     __syncthreads();
     const size_t hbase = (size_t)h * p.cap * HD;
-    if (tid < HD) { const size_t slot = hbase + (size_t)(qpos % p.cap) * HD + tid; kring[slot] = kn[m][tid]; vring[slot] = vn[m][tid]; }
+    if (tid < HD) { const size_t slot = hbase + (size_t)(qpos % p.cap) * HD + tid; kring[slot] = E::put(kn[m][tid]); vring[slot] = E::put(vn[m][tid]); }
     const int j0 = max(0, qpos - p.window), nk = qpos - j0 + 1;      // keys j0 .. qpos (host: window + 1 <= 1024)
     const int g = tid >> 4, li = tid & 15;
     const float scale = HD == 64 ? 0.125f : 0.08838834764831845f;      // head_dim^-0.5
@@ -4993,7 +5017,7 @@ __global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_attn_kernel(const St
 #pragma unroll
         for (int u = 0; u < HD / 64; u++) {
             const int o = (u * 16 + li) * 4;
-            const float4 kv = j < enc_pos ? *reinterpret_cast<const float4*>(kring + hbase + (size_t)(j % p.cap) * HD + o) : *reinterpret_cast<const float4*>(&kn[j - enc_pos][o]);
+            const float4 kv = j < enc_pos ? E::ld4(kring + hbase + (size_t)(j % p.cap) * HD + o) : *reinterpret_cast<const float4*>(&kn[j - enc_pos][o]);
             const float4 qv = *reinterpret_cast<const float4*>(&qs[o]);
             dot = fmaf(qv.x, kv.x, dot); dot = fmaf(qv.y, kv.y, dot); dot = fmaf(qv.z, kv.z, dot); dot = fmaf(qv.w, kv.w, dot);
         }
@@ -5018,7 +5042,7 @@ __global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_attn_kernel(const St
     float acc = 0.f;
     for (int i = kg; i < nk; i += G) {
         const int j = j0 + i;
-        const float vv = j < enc_pos ? vring[hbase + (size_t)(j % p.cap) * HD + d] : vn[j - enc_pos][d];
+        const float vv = j < enc_pos ? E::ld1(vring + hbase + (size_t)(j % p.cap) * HD + d) : vn[j - enc_pos][d];
         acc = fmaf(sc[i], vv, acc);
     }
     red[kg][d] = acc;
@@ -5031,12 +5055,15 @@ __global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_attn_kernel(const St
     }
 }
 hipError_t launch_stream_attn(const StreamAttnParams& p, int hd, hipStream_t s) {
-    // (the ring rows are read as float4: the sessions' rings are hipMalloc'd, a layer's offset is a multiple of hd, hd % 4 == 0 holds for 64 / 128)
-    if ((hd != 64 && hd != 128) || p.M < 1 || p.M > 8 || p.n < 1 || p.n > 16 || !p.mem || !p.order || p.window < 0 || p.window + 1 > 1024 || p.cap <= p.window + p.M || (p.ring_off & 3) || p.rope_mask < 0 ||
+    // (the ring rows are read as float4 -- a bf16 ring's as 8 bytes: the sessions' rings are hipMalloc'd, a layer's offset -- ring_off, in elements of the ring -- is a
+    // multiple of hd, hd % 4 == 0 holds for 64 / 128)
+    if (!ring_dtype_ok(p.ring_dtype) || (hd != 64 && hd != 128) || p.M < 1 || p.M > 8 || p.n < 1 || p.n > 16 || !p.mem || !p.order || p.window < 0 || p.window + 1 > 1024 || p.cap <= p.window + p.M || (p.ring_off & 3) || p.rope_mask < 0 ||
         (p.rope_mask & (p.rope_mask + 1)) || (p.rope_mask && p.rope_mask + 1 < p.M) || (p.rope_stride && (!p.rope_mask || p.rope_stride < p.rope_mask + 1))) return hipErrorInvalidValue;
     attn_form_note(ATTN_FORM_STREAM_RING);      // (behind every refusal: a refused call counts no launch)
-    if (hd == 64) stream_attn_kernel<64><<<dim3(p.n_heads, p.M, p.n), dim3(256), 0, s>>>(p);
-    else stream_attn_kernel<128><<<dim3(p.n_heads, p.M, p.n), dim3(256), 0, s>>>(p);
+    const dim3 grid(p.n_heads, p.M, p.n);
+    if (p.ring_dtype == RING_BF16) { if (hd == 64) stream_attn_kernel<64, uint16_t><<<grid, dim3(256), 0, s>>>(p); else stream_attn_kernel<128, uint16_t><<<grid, dim3(256), 0, s>>>(p); }
+    else if (hd == 64) stream_attn_kernel<64><<<grid, dim3(256), 0, s>>>(p);
+    else stream_attn_kernel<128><<<grid, dim3(256), 0, s>>>(p);
     return hipGetLastError();
 }
 
@@ -5052,8 +5079,11 @@ hipError_t launch_stream_attn(const StreamAttnParams& p, int hd, hipStream_t s) 
 // workgroup reads a ring row another one writes in this launch: with cap > window + M the rows written now held positions below every window of the burst.
 // P = StreamAttnGroupParams: the RAGGED form (a burst group's round, launch_stream_attn_group_burst) -- slot z has its own row count M_z = rpt * b[z] and its rows start
 // at row rpt * tick0[z] of qkv and out (the device descriptor p.desc); a tile at or beyond M_z leaves at once.  Everything behind those two integers is the code above.
-template <int HD, class P = StreamAttnParams>
+// EL: the ring's element (RingElem, above stream_attn_kernel).  On a bf16 ring the burst's own k rows in LDS and its own v values out of qkv are widen(round(x)) -- the
+// bits the ring receives and hands back -- so query t of the burst meets key t - 1 with the bits the chain's launch t reads from the ring.
+template <int HD, class P = StreamAttnParams, class EL = float>
 __global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_attn_burst_kernel(const P p) {
+    using E = RingElem<EL>;
     constexpr bool RAGGED = !std::is_same<P, StreamAttnParams>::value;
     constexpr int HALF = HD / 2, G = 256 / HD, TQ = 4;
     __shared__ __attribute__((aligned(16))) float qs[TQ][HD];
@@ -5067,7 +5097,7 @@ __global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_attn_burst_kernel(co
     else { M = p.M; row0 = blockIdx.z * p.M; }
     const int T = min(TQ, M - m0);      // the tile's query rows m0 .. m0 + T - 1
     const StreamMember& me = p.mem[p.order[blockIdx.z]];
-    float* __restrict__ kring = me.kring + p.ring_off; float* __restrict__ vring = me.vring + p.ring_off;
+    EL* __restrict__ kring = reinterpret_cast<EL*>(me.kring) + p.ring_off; EL* __restrict__ vring = reinterpret_cast<EL*>(me.vring) + p.ring_off;
     const float* __restrict__ qkv = p.qkv + (size_t)row0 * p.qkv_stride;      // the slot's M rows
     const int enc_pos = me.state[STRM_ENC_POS], QD = p.n_heads * HD, nkr = m0 + T;       // k rows 0 .. nkr - 1, then the T query rows
     for (int i = tid; i < (nkr + T) * HALF; i += 256) {
@@ -5078,13 +5108,14 @@ __global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_attn_burst_kernel(co
         const float xr = src[0], xi = src[1];
         float* dst = isq ? qs[r - nkr] : kn[r];
         dst[2 * j] = xr * c - xi * sn; dst[2 * j + 1] = xr * sn + xi * c;
+        if constexpr (!std::is_same<EL, float>::value) if (!isq) { dst[2 * j] = E::own(dst[2 * j]); dst[2 * j + 1] = E::own(dst[2 * j + 1]); }      // (q is never rounded)
     }
     __syncthreads();
     const size_t hbase = (size_t)h * p.cap * HD;
     for (int i = tid; i < T * HD; i += 256) {
         const int q = i / HD, d = i - q * HD, m = m0 + q;
         const size_t slot = hbase + (size_t)((enc_pos + m) % p.cap) * HD + d;
-        kring[slot] = kn[m][d]; vring[slot] = qkv[(size_t)m * p.qkv_stride + 2 * QD + h * HD + d];
+        kring[slot] = E::put(kn[m][d]); vring[slot] = E::put(qkv[(size_t)m * p.qkv_stride + 2 * QD + h * HD + d]);
     }
     // query q: position enc_pos + m0 + q, keys j0[q] .. that position; the tile's union is jlo = j0[0] .. the last query's position
     int j0[TQ], nk[TQ];
@@ -5099,7 +5130,7 @@ __global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_attn_burst_kernel(co
 #pragma unroll
         for (int u = 0; u < HD / 64; u++) {
             const int o = (u * 16 + li) * 4;
-            const float4 kv = j < enc_pos ? *reinterpret_cast<const float4*>(kring + hbase + (size_t)(j % p.cap) * HD + o) : *reinterpret_cast<const float4*>(&kn[j - enc_pos][o]);
+            const float4 kv = j < enc_pos ? E::ld4(kring + hbase + (size_t)(j % p.cap) * HD + o) : *reinterpret_cast<const float4*>(&kn[j - enc_pos][o]);
 #pragma unroll
             for (int q = 0; q < TQ; q++) {
                 const float4 qv = *reinterpret_cast<const float4*>(&qs[q][o]);
@@ -5140,7 +5171,7 @@ __global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_attn_burst_kernel(co
     float acc[TQ] = {0.f, 0.f, 0.f, 0.f};
     for (int u = kg; u < nu; u += G) {
         const int j = jlo + u;
-        const float vv = j < enc_pos ? vring[hbase + (size_t)(j % p.cap) * HD + d] : qkv[(size_t)(j - enc_pos) * p.qkv_stride + 2 * QD + h * HD + d];
+        const float vv = j < enc_pos ? E::ld1(vring + hbase + (size_t)(j % p.cap) * HD + d) : E::own(qkv[(size_t)(j - enc_pos) * p.qkv_stride + 2 * QD + h * HD + d]);
 #pragma unroll
         for (int q = 0; q < TQ; q++) {
             const int i = j - j0[q];
@@ -5162,11 +5193,14 @@ __global__ __launch_bounds__(256) VOX_NO_PK_F32 void stream_attn_burst_kernel(co
 static std::atomic<unsigned long long> g_stream_attn_burst_launches;      // a counter of its own: the slots of attn_form_counts keep their numbers
 unsigned long long stream_attn_burst_launches() { return g_stream_attn_burst_launches.load(std::memory_order_relaxed); }
 hipError_t launch_stream_attn_burst(const StreamAttnParams& p, int hd, hipStream_t s) {
-    if ((hd != 64 && hd != 128) || p.M < 1 || p.M > 64 || p.n < 1 || p.n > 16 || !p.mem || !p.order || p.window < 0 || p.window + 1 > 1024 || p.cap <= p.window + p.M || (p.ring_off & 3) || p.rope_mask < 0 ||
+    if (!ring_dtype_ok(p.ring_dtype) || (hd != 64 && hd != 128) || p.M < 1 || p.M > 64 || p.n < 1 || p.n > 16 || !p.mem || !p.order || p.window < 0 || p.window + 1 > 1024 || p.cap <= p.window + p.M || (p.ring_off & 3) || p.rope_mask < 0 ||
         (p.rope_mask & (p.rope_mask + 1)) || (p.rope_mask && p.rope_mask + 1 < p.M) || (p.rope_stride && (!p.rope_mask || p.rope_stride < p.rope_mask + 1))) return hipErrorInvalidValue;
     g_stream_attn_burst_launches.fetch_add(1, std::memory_order_relaxed);      // (behind every refusal: a refused call counts no launch)
-    if (hd == 64) stream_attn_burst_kernel<64><<<dim3(p.n_heads, (p.M + 3) / 4, p.n), dim3(256), 0, s>>>(p);
-    else stream_attn_burst_kernel<128><<<dim3(p.n_heads, (p.M + 3) / 4, p.n), dim3(256), 0, s>>>(p);
+    const dim3 grid(p.n_heads, (p.M + 3) / 4, p.n);
+    if (p.ring_dtype == RING_BF16) {
+        if (hd == 64) stream_attn_burst_kernel<64, StreamAttnParams, uint16_t><<<grid, dim3(256), 0, s>>>(p); else stream_attn_burst_kernel<128, StreamAttnParams, uint16_t><<<grid, dim3(256), 0, s>>>(p);
+    } else if (hd == 64) stream_attn_burst_kernel<64><<<grid, dim3(256), 0, s>>>(p);
+    else stream_attn_burst_kernel<128><<<grid, dim3(256), 0, s>>>(p);
     return hipGetLastError();
 }
 // a burst round's descriptor as the host holds it: n slots, b in 1 .. 16, tick0 the running sum of the b before it.  *max_b: the largest b
@@ -5178,14 +5212,17 @@ static bool stream_burst_desc_ok(const StreamBurstDesc& d, int n, int* max_b) {
 }
 hipError_t launch_stream_attn_group_burst(const StreamAttnParams& a, const StreamBurstDesc* desc, const StreamBurstDesc& host, int rpt, int hd, hipStream_t s) {
     int max_b = 0;
-    if (!desc || rpt < 1 || !stream_burst_desc_ok(host, a.n, &max_b)) return hipErrorInvalidValue;
+    if (!desc || rpt < 1 || !ring_dtype_ok(a.ring_dtype) || !stream_burst_desc_ok(host, a.n, &max_b)) return hipErrorInvalidValue;
     const int Mx = rpt * max_b;      // the largest M_z
     if ((hd != 64 && hd != 128) || Mx > 64 || !a.mem || !a.order || a.window < 0 || a.window + 1 > 1024 || a.cap <= a.window + Mx || (a.ring_off & 3) || a.rope_mask < 0 ||
         (a.rope_mask & (a.rope_mask + 1)) || (a.rope_mask && a.rope_mask + 1 < Mx) || (a.rope_stride && (!a.rope_mask || a.rope_stride < a.rope_mask + 1))) return hipErrorInvalidValue;
     StreamAttnGroupParams p{}; static_cast<StreamAttnParams&>(p) = a; p.M = 0; p.desc = desc; p.rpt = rpt;
     g_stream_attn_burst_launches.fetch_add(1, std::memory_order_relaxed);      // (behind every refusal: a refused call counts no launch)
-    if (hd == 64) stream_attn_burst_kernel<64, StreamAttnGroupParams><<<dim3(a.n_heads, (Mx + 3) / 4, a.n), dim3(256), 0, s>>>(p);
-    else stream_attn_burst_kernel<128, StreamAttnGroupParams><<<dim3(a.n_heads, (Mx + 3) / 4, a.n), dim3(256), 0, s>>>(p);
+    const dim3 grid(a.n_heads, (Mx + 3) / 4, a.n);
+    if (a.ring_dtype == RING_BF16) {
+        if (hd == 64) stream_attn_burst_kernel<64, StreamAttnGroupParams, uint16_t><<<grid, dim3(256), 0, s>>>(p); else stream_attn_burst_kernel<128, StreamAttnGroupParams, uint16_t><<<grid, dim3(256), 0, s>>>(p);
+    } else if (hd == 64) stream_attn_burst_kernel<64, StreamAttnGroupParams><<<grid, dim3(256), 0, s>>>(p);
+    else stream_attn_burst_kernel<128, StreamAttnGroupParams><<<grid, dim3(256), 0, s>>>(p);
     return hipGetLastError();
 }
 // the pack of a burst round: one workgroup column per slot, float4 copies of the slot's valid rows (rows past rpt * b[z] of a slot are never read)
@@ -5205,20 +5242,22 @@ hipError_t launch_stream_burst_pack(const float* src, int src_slot_rows, const S
     return hipGetLastError();
 }
 
-__global__ void stream_ring_init_kernel(const float* __restrict__ kv, int layers, int rows, int n_heads, int hd, int cap, float* __restrict__ kring, float* __restrict__ vring) {
+template <class T>      // the ring's element: the rows of a bf16 ring are rounded by the attention's own function (RingElem::put)
+__global__ void stream_ring_init_kernel(const float* __restrict__ kv, int layers, int rows, int n_heads, int hd, int cap, T* __restrict__ kring, T* __restrict__ vring) {
     const int QD = n_heads * hd;
     const long total = (long)layers * rows * QD;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int c = (int)(i % QD); const long lr = i / QD; const int r = (int)(lr % rows), l = (int)(lr / rows), h = c / hd, d = c - h * hd;
         const size_t dst = (((size_t)l * n_heads + h) * cap + r) * hd + d, src = (size_t)lr * 2 * QD + c;
-        kring[dst] = kv[src]; vring[dst] = kv[src + QD];
+        kring[dst] = RingElem<T>::put(kv[src]); vring[dst] = RingElem<T>::put(kv[src + QD]);
     }
 }
-hipError_t launch_stream_ring_init(const float* kv, int layers, int rows, int n_heads, int hd, int cap, float* kring, float* vring, hipStream_t s) {
-    if (rows <= 0 || rows > cap) return hipErrorInvalidValue;
+hipError_t launch_stream_ring_init(const float* kv, int layers, int rows, int n_heads, int hd, int cap, float* kring, float* vring, hipStream_t s, int ring_dtype) {
+    if (rows <= 0 || rows > cap || !ring_dtype_ok(ring_dtype)) return hipErrorInvalidValue;
     const long total = (long)layers * rows * n_heads * hd;
     int blocks = (int)((total + 255) / 256); if (blocks > 2048) blocks = 2048;
-    stream_ring_init_kernel<<<dim3(blocks), dim3(256), 0, s>>>(kv, layers, rows, n_heads, hd, cap, kring, vring);
+    if (ring_dtype == RING_BF16) stream_ring_init_kernel<uint16_t><<<dim3(blocks), dim3(256), 0, s>>>(kv, layers, rows, n_heads, hd, cap, reinterpret_cast<uint16_t*>(kring), reinterpret_cast<uint16_t*>(vring));
+    else stream_ring_init_kernel<float><<<dim3(blocks), dim3(256), 0, s>>>(kv, layers, rows, n_heads, hd, cap, kring, vring);
     return hipGetLastError();
 }
 
@@ -5545,7 +5584,8 @@ hipError_t launch_stream_level(const StreamMember* mem, const int* order, int n,
 // the ring keep of a peek: slot z = blockIdx.z copies, for session order[z], `rows` ring rows of every (layer, head) of K and V between the ring and the slot's area, and
 // the session's state block.  The ring rows start at STRM_HEAD -- the live block's at save, the SAVED block's at restore (the live one has moved on by then) -- and wrap
 // at cap.  Nobody writes what another thread reads: the save leaves the live block alone, the restore the saved one.
-template <int RESTORE>
+// V4: the 4 values of a ring row the copies move at once -- float4, or the 8 bytes of 4 16-bit values (a bf16 ring: the area's K and V are 16-bit rows too)
+template <int RESTORE, class V4 = float4>
 __global__ __launch_bounds__(256) void stream_keep_kernel(StreamKeepParams p) {
     const StreamMember& me = p.mem[p.order[blockIdx.z]];
     float* area = p.keep + (size_t)blockIdx.z * p.slot_stride;
@@ -5556,11 +5596,11 @@ __global__ __launch_bounds__(256) void stream_keep_kernel(StreamKeepParams p) {
         if (RESTORE) me.state[threadIdx.x] = kstate[threadIdx.x]; else kstate[threadIdx.x] = me.state[threadIdx.x];
     }
     const int hq = p.hd / 4;
-    const long plane = (long)p.layers * p.n_heads * p.rows * hq;      // float4s of K (and of V)
-    float4* kk = reinterpret_cast<float4*>(area + STRM_WORDS);
-    float4* kv = kk + plane;
-    float4* rk = reinterpret_cast<float4*>(me.kring);
-    float4* rv = reinterpret_cast<float4*>(me.vring);
+    const long plane = (long)p.layers * p.n_heads * p.rows * hq;      // 4-value pieces of K (and of V)
+    V4* kk = reinterpret_cast<V4*>(area + STRM_WORDS);
+    V4* kv = kk + plane;
+    V4* rk = reinterpret_cast<V4*>(me.kring);
+    V4* rv = reinterpret_cast<V4*>(me.vring);
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < plane; i += (long)gridDim.x * blockDim.x) {
         const int q = (int)(i % hq); const long lr = i / hq; const int r = (int)(lr % p.rows); const long lh = lr / p.rows;
         int slot = head + r; if (slot >= p.cap) slot -= p.cap;
@@ -5568,13 +5608,16 @@ __global__ __launch_bounds__(256) void stream_keep_kernel(StreamKeepParams p) {
         if (RESTORE) { rk[ring] = kk[i]; rv[ring] = kv[i]; } else { kk[i] = rk[ring]; kv[i] = rv[ring]; }
     }
 }
-size_t stream_keep_floats(int layers, int n_heads, int hd, int rows) { return (size_t)STRM_WORDS + 2 * (size_t)layers * n_heads * rows * hd; }
+size_t stream_keep_floats(int layers, int n_heads, int hd, int rows, int ring_dtype) {      // (hd % 4 == 0 and STRM_WORDS % 4 == 0: a multiple of 4 either way)
+    return (size_t)STRM_WORDS + 2 * (size_t)layers * n_heads * rows * hd / (ring_dtype == RING_BF16 ? 2 : 1);
+}
 hipError_t launch_stream_keep(const StreamKeepParams& p, int restore, hipStream_t s) {
-    if (p.n < 1 || p.n > 16 || !p.mem || !p.order || !p.keep || p.layers < 1 || p.n_heads < 1 || p.hd < 4 || (p.hd & 3) || p.rows < 1 || p.rows > p.cap) return hipErrorInvalidValue;
-    if ((p.slot_stride & 3) || p.slot_stride < stream_keep_floats(p.layers, p.n_heads, p.hd, p.rows)) return hipErrorInvalidValue;
+    if (!ring_dtype_ok(p.ring_dtype) || p.n < 1 || p.n > 16 || !p.mem || !p.order || !p.keep || p.layers < 1 || p.n_heads < 1 || p.hd < 4 || (p.hd & 3) || p.rows < 1 || p.rows > p.cap) return hipErrorInvalidValue;
+    if ((p.slot_stride & 3) || p.slot_stride < stream_keep_floats(p.layers, p.n_heads, p.hd, p.rows, p.ring_dtype)) return hipErrorInvalidValue;
     const long plane = (long)p.layers * p.n_heads * p.rows * (p.hd / 4);
     int blocks = (int)((plane + 255) / 256); if (blocks > 2048) blocks = 2048;
-    if (restore) stream_keep_kernel<1><<<dim3(blocks, 1, p.n), dim3(256), 0, s>>>(p);
+    if (p.ring_dtype == RING_BF16) { if (restore) stream_keep_kernel<1, u32x2_t><<<dim3(blocks, 1, p.n), dim3(256), 0, s>>>(p); else stream_keep_kernel<0, u32x2_t><<<dim3(blocks, 1, p.n), dim3(256), 0, s>>>(p); }
+    else if (restore) stream_keep_kernel<1><<<dim3(blocks, 1, p.n), dim3(256), 0, s>>>(p);
     else stream_keep_kernel<0><<<dim3(blocks, 1, p.n), dim3(256), 0, s>>>(p);
     return hipGetLastError();
 }
@@ -5617,7 +5660,7 @@ __global__ __launch_bounds__(256) void snapshot_kv_kernel(SnapshotKvParams p) {
         else { const float4 k0 = ck[a0], v0 = cv[a0]; bk[i] = k0; bv[i] = v0; }
     }
 }
-// The paged layouts on a bf16 pool (SnapshotKvParams::kv_bf16; RING: SNAP_PAGED_RING): the blob side moves the float4s of the kernel above, the cache side the same 4
+// The paged layouts on a bf16 pool and the ring layout on a bf16 encoder ring (SnapshotKvParams::kv_bf16; LAYOUT: SNAP_RING, SNAP_PAGED or SNAP_PAGED_RING): the blob side moves the float4s of the kernel above, the cache side the same 4
 // values as 8 bytes -- pack widens them (kv_bf16_widen, exact), restore rounds them (kv_bf16_round: exact for a blob packed from a bf16 pool).  The strides count
 // 16-bit elements; `at` counts 4-value pieces, as above.
 __device__ __forceinline__ float4 kv_pool_widen4(const u32x2_t& r) { return kv_bf16_widen4(r.x, r.y); }
@@ -5626,8 +5669,9 @@ __device__ __forceinline__ u32x2_t kv_pool_round4(const float4& v) {
     r.x = (unsigned)kv_bf16_round(v.x) | ((unsigned)kv_bf16_round(v.y) << 16); r.y = (unsigned)kv_bf16_round(v.z) | ((unsigned)kv_bf16_round(v.w) << 16);
     return r;
 }
-template <int HD, bool RING, int RESTORE>
+template <int HD, int LAYOUT, int RESTORE>
 __global__ __launch_bounds__(256) void snapshot_kv_bf16_kernel(SnapshotKvParams p) {
+    constexpr bool RING = LAYOUT == SNAP_PAGED_RING;
     constexpr int HQ_SHIFT = HD == 64 ? 4 : 5, HQ = 1 << HQ_SHIFT;      // 4-value pieces per row
     const int plane = p.plane0 + (int)blockIdx.y, layer = plane / p.heads, head = plane - layer * p.heads;
     const long n = (long)(p.hi - p.lo) << HQ_SHIFT;
@@ -5636,10 +5680,12 @@ __global__ __launch_bounds__(256) void snapshot_kv_bf16_kernel(SnapshotKvParams 
     u32x2_t* __restrict__ cv = reinterpret_cast<u32x2_t*>(reinterpret_cast<uint16_t*>(p.cache_v) + base);
     float4* __restrict__ bk = reinterpret_cast<float4*>(p.blob_k) + (long)blockIdx.y * n;
     float4* __restrict__ bv = reinterpret_cast<float4*>(p.blob_v) + (long)blockIdx.y * n;
-    const int pg0 = p.lo >> p.shift, e0 = RING ? pg0 % p.tab_len : pg0;
+    const int lo_slot = LAYOUT == SNAP_RING ? p.lo % p.cap : 0;
+    const int pg0 = LAYOUT == SNAP_RING ? 0 : p.lo >> p.shift, e0 = RING ? pg0 % p.tab_len : pg0;
     const long page_q = (long)(p.page_floats >> 2);
     auto at = [&](long i) -> long {      // the cache's piece of the blob's float4 i
         const int r = (int)(i >> HQ_SHIFT), q = (int)(i & (HQ - 1));
+        if (LAYOUT == SNAP_RING) { int slot = lo_slot + r; if (slot >= p.cap) slot -= p.cap; return ((long)slot << HQ_SHIFT) + q; }
         const int row = p.lo + r; int e = e0 + ((row >> p.shift) - pg0);
         if (RING && e >= p.tab_len) e -= p.tab_len;
         return (long)p.tab[e] * page_q + ((long)(row & ((1 << p.shift) - 1)) << HQ_SHIFT) + q;
@@ -5669,7 +5715,7 @@ hipError_t launch_snapshot_kv(const SnapshotKvParams& p, int restore, hipStream_
     const int all = p.layers * p.heads, n_planes = p.n_planes ? p.n_planes : all - p.plane0;
     if (p.layers < 1 || p.heads < 1 || (p.hd != 64 && p.hd != 128) || p.lo < 0 || p.hi < p.lo || p.plane0 < 0 || n_planes < 1 || p.plane0 + n_planes > all || n_planes > 65535) return hipErrorInvalidValue;
     if (p.layout < SNAP_FLAT || p.layout > SNAP_PAGED_RING || (p.layer_stride & 3) || (p.head_stride & 3)) return hipErrorInvalidValue;
-    if (p.kv_bf16 && (p.kv_bf16 != 1 || p.layout < SNAP_PAGED || (p.layer_stride & 7) || (p.head_stride & 7) || (p.page_floats & 7))) return hipErrorInvalidValue;      // a bf16 pool is a paged cache's; 16-byte rows
+    if (p.kv_bf16 && (p.kv_bf16 != 1 || p.layout < SNAP_RING || (p.layer_stride & 7) || (p.head_stride & 7) || (p.layout >= SNAP_PAGED && (p.page_floats & 7)))) return hipErrorInvalidValue;      // a bf16 pool is a paged cache's, a bf16 ring the encoder's; 16-byte rows
     if (p.hi == p.lo) return hipSuccess;      // nothing to move: no launch
     if (!p.cache_k || !p.cache_v || !p.blob_k || !p.blob_v) return hipErrorInvalidValue;
     if ((reinterpret_cast<uintptr_t>(p.cache_k) | reinterpret_cast<uintptr_t>(p.cache_v) | reinterpret_cast<uintptr_t>(p.blob_k) | reinterpret_cast<uintptr_t>(p.blob_v)) & 15) return hipErrorInvalidValue;
@@ -5689,8 +5735,9 @@ hipError_t launch_snapshot_kv(const SnapshotKvParams& p, int restore, hipStream_
 #define SNAP_HD(L) do { if (p.hd == 64) SNAP_GO(64, L); else SNAP_GO(128, L); } while (0)
 #define SNAP_GO_B(HD, L) do { if (restore) snapshot_kv_bf16_kernel<HD, L, 1><<<grid, block, 0, s>>>(q); else snapshot_kv_bf16_kernel<HD, L, 0><<<grid, block, 0, s>>>(q); } while (0)
     if (p.kv_bf16) {
-        if (p.layout == SNAP_PAGED) { if (p.hd == 64) SNAP_GO_B(64, false); else SNAP_GO_B(128, false); }
-        else { if (p.hd == 64) SNAP_GO_B(64, true); else SNAP_GO_B(128, true); }
+        if (p.layout == SNAP_RING) { if (p.hd == 64) SNAP_GO_B(64, SNAP_RING); else SNAP_GO_B(128, SNAP_RING); }
+        else if (p.layout == SNAP_PAGED) { if (p.hd == 64) SNAP_GO_B(64, SNAP_PAGED); else SNAP_GO_B(128, SNAP_PAGED); }
+        else { if (p.hd == 64) SNAP_GO_B(64, SNAP_PAGED_RING); else SNAP_GO_B(128, SNAP_PAGED_RING); }
     } else
     switch (p.layout) {
         case SNAP_FLAT: SNAP_HD(SNAP_FLAT); break;

@@ -408,6 +408,27 @@ def stream_attn_group_burst(ctx, qkv, kring, vring, order, enc_pos, rows_per_slo
     return out, kring, vring
 
 
+def stream_attn_elem(ctx, qkv, kring, vring, order, enc_pos, rows, window, theta, form="tick", enc_kv_dtype="bf16", layer=0, rope_rows=0, rope_per_member=False):
+    """vox_debug_stream_attn_elem: ONE launch of the ring attention in the form "tick" (stream_attn), "burst" (stream_attn_burst) or "ragged" (stream_attn_group_burst:
+    `rows` is then rows_per_slot) on rings of enc_kv_dtype "f32" (float32 arrays) or "bf16" (uint16 arrays of the same shape, in and out).  Returns (out, kring, vring)."""
+    code = {"tick": 0, "burst": 1, "ragged": 2}[form]; dt = LiveStreamGroup.KV_DTYPES[enc_kv_dtype]; el = np.uint16 if dt else np.float32
+    qkv = _f32(qkv); kring = np.ascontiguousarray(kring, dtype=el).copy(); vring = np.ascontiguousarray(vring, dtype=el).copy()
+    order = np.ascontiguousarray(order, dtype=np.int32); enc_pos = np.ascontiguousarray(enc_pos, dtype=np.int32)
+    rps = np.ascontiguousarray(rows, dtype=np.int32) if code == 2 else None
+    if qkv.ndim != 2 or kring.ndim != 5 or kring.shape != vring.shape or order.ndim != 1 or enc_pos.shape != (kring.shape[0],) or (rps is not None and rps.shape != order.shape):
+        raise VoxError(1, "stream_attn_elem: bad shapes")
+    n_members, layers, n_heads, cap, hd = kring.shape
+    n_rows = int(np.maximum(rps, 0).sum()) if rps is not None else len(order) * max(int(rows), 0)
+    if qkv.shape != (n_rows, 3 * n_heads * hd):
+        raise VoxError(1, "stream_attn_elem: qkv is not [the slots' rows][3 * n_heads * head_dim]")
+    d = StreamAttnDesc(n_slots=len(order), n_members=n_members, rows=(int(rps.max()) if rps.size else 0) if rps is not None else int(rows), n_heads=n_heads, head_dim=hd,
+                       window=int(window), cap=cap, layers=layers, layer=int(layer), rope_rows=int(rope_rows), rope_per_member=int(bool(rope_per_member)), theta=float(theta),
+                       order=order.ctypes.data, enc_pos=enc_pos.ctypes.data)
+    out = np.empty((n_rows, n_heads * hd), np.float32)
+    check(lib().vox_debug_stream_attn_elem(ctx.h, C.byref(d), code, dt, None if rps is None else _ptr(rps), _ptr(qkv), _ptr(kring), _ptr(vring), _ptr(out)))
+    return out, kring, vring
+
+
 def stream_attn_burst_launches() -> int:
     """vox_debug_stream_attn_burst_launches: launches of the burst kernel so far (a counter of its own, in no slot of attn_launches)."""
     v = C.c_uint64(); check(lib().vox_debug_stream_attn_burst_launches(C.byref(v)))
@@ -1041,13 +1062,18 @@ class LiveStreamGroup:
     KV_DTYPES = {"f32": 0, "bf16": 1}      # VOX_KV_F32, VOX_KV_BF16
 
     def __init__(self, model, t_embed, n_members, gains=None, enc_capacity_rows=0, max_positions=0, sample_rates=None, page_rows=None, pool_pages=None, endless=False,
-                 kv_dtype=None, burst=None, t_embeds=None):
+                 kv_dtype=None, burst=None, t_embeds=None, enc_kv_dtype=None):
         if burst is not None and (isinstance(burst, bool) or not isinstance(burst, (int, np.integer)) or not 1 <= int(burst) <= STREAM_BURST_MAX):
             raise VoxError(1, f"create_stream_group: burst {burst!r} is not an integer in 1..{STREAM_BURST_MAX}")
         self.model = model; self.h = C.c_void_p(); self.n_members = int(n_members); self._tap_max = {}; self._rates = {}
         self.burst = None if burst is None else int(burst)      # given: a burst group (vox_stream_group_create_burst) of whatever kind the other arguments make
         if kv_dtype is not None and kv_dtype not in self.KV_DTYPES:
             raise ValueError(f"kv_dtype {kv_dtype!r}: a stream group's K/V pool holds 'f32' or 'bf16'")
+        if enc_kv_dtype is not None and enc_kv_dtype not in self.KV_DTYPES:
+            raise ValueError(f"enc_kv_dtype {enc_kv_dtype!r}: a stream group's encoder K/V ring holds 'f32' or 'bf16'")
+        if enc_kv_dtype is not None and t_embeds is None:
+            raise ValueError("enc_kv_dtype: vox_stream_group_create_enc_kv takes a t_embed per member (Model.create_stream_group repeats a single one)")
+        self.enc_kv_dtype = enc_kv_dtype      # given: a group made by vox_stream_group_create_enc_kv (any kind), whose enc_kv() reads the dtype back; None: every other group
         self.kv_dtype = kv_dtype      # given: a paged group made by vox_stream_group_create_kv, whose pool() names the dtype; None: the group the other arguments make
         self.endless = bool(endless)      # an endless paged group (vox_stream_group_create_endless): no max_positions, every member goes on to 2^24 positions
         if self.endless and max_positions:
@@ -1064,9 +1090,12 @@ class LiveStreamGroup:
             r = np.ascontiguousarray([int(v) for v in (sample_rates if sample_rates is not None else [16000] * self.n_members)], dtype=np.uint32)
             if r.size != self.n_members:
                 raise ValueError(f"{r.size} sample rates for {self.n_members} members")
-            check(lib().vox_stream_group_create_t_embeds(model.h, _ptr(te), self.n_members, None if g is None else _ptr(g), _ptr(r), int(enc_capacity_rows), int(max_positions),
-                                                         int(self.paged), int(page_rows or 0), int(pool_pages or 0), int(self.endless), self.KV_DTYPES[kv_dtype or "f32"],
-                                                         int(burst or 1), C.byref(self.h)))
+            args = (model.h, _ptr(te), self.n_members, None if g is None else _ptr(g), _ptr(r), int(enc_capacity_rows), int(max_positions), int(self.paged), int(page_rows or 0),
+                    int(pool_pages or 0), int(self.endless), self.KV_DTYPES[kv_dtype or "f32"], int(burst or 1))
+            if enc_kv_dtype is not None:
+                check(lib().vox_stream_group_create_enc_kv(*args, self.KV_DTYPES[enc_kv_dtype], C.byref(self.h)))
+            else:
+                check(lib().vox_stream_group_create_t_embeds(*args, C.byref(self.h)))
             self._rates = {k: int(v) for k, v in enumerate(r) if int(v) != 16000}
             model._caches.add(self)
             return
@@ -1204,6 +1233,11 @@ class LiveStreamGroup:
     def info(self, member):
         v = (C.c_int64 * 8)(); check(lib().vox_stream_group_info(self.h, int(member), v))
         return dict(zip(("samples", "positions", "ids", "encoder_position", "ring_rows", "bytes", "engine_steps", "operator_steps"), (int(x) for x in v)))
+
+    def enc_kv(self) -> str:
+        """vox_stream_group_enc_kv_dtype: what the members' encoder K / V rings hold, "f32" or "bf16"."""
+        v = C.c_int32(); check(lib().vox_stream_group_enc_kv_dtype(self.h, C.byref(v)))
+        return {code: name for name, code in self.KV_DTYPES.items()}[int(v.value)]
 
     def burst_info(self):
         """vox_stream_group_burst_info: burst_ticks (1: a plain group), the burst rounds run (rounds in which some member ran 2 or more ticks), the member-ticks inside
@@ -1498,7 +1532,7 @@ class Q4VoxtralModel:
         return st
 
     def create_stream_group(self, t_embed, n_members, gains=None, enc_capacity_rows=0, max_positions=0, sample_rates=None, page_rows=None, pool_pages=None,
-                            endless=False, kv_dtype=None, burst=None, t_embeds=None, delays=None, attn_split=False) -> LiveStreamGroup:
+                            endless=False, kv_dtype=None, burst=None, t_embeds=None, delays=None, attn_split=False, enc_kv_dtype=None) -> LiveStreamGroup:
         """Up to 16 live sessions advanced together (vox_stream_group_create): advance({member: samples}, finish=()) -> {member: ids}, reset(member, gain), info(member),
         close().  gains: one per member (None: 1.0 each); max_positions 0: 2048 decoder positions per member (the group's decoder cache does not grow);
         sample_rates: what each member is fed (None: 16 kHz each; vox_stream_group_create_rates).
@@ -1510,7 +1544,11 @@ class Q4VoxtralModel:
         pages, half the memory and half the bytes the decode attention reads; ids and logits are close to, not equal to, the f32 group's.  pool() then names it.
         t_embeds [n_members][dec_dim] or delays [n_members] (through TimeEmbedding; vox_stream_group_create_t_embeds, any kind of group): a delay PER MEMBER -- t_embed
         is then unread (None); member k's ids are those of member k in a group whose members all run at its delay.  reset(member, delay=) moves a member to another,
-        t_embed(member) reads it back.  attn_split: LiveStreamGroup.set_attn_split(True) on the new group."""
+        t_embed(member) reads it back.  attn_split: LiveStreamGroup.set_attn_split(True) on the new group.
+        enc_kv_dtype "f32" | "bf16" (vox_stream_group_create_enc_kv, any kind of group; anything else: ValueError): what the members' ENCODER K / V rings hold.  "bf16":
+        half the ring's memory (info()'s bytes follow) and half the bytes the ring attention reads at every tick; ids and logits are close to, not equal to, the f32
+        group's.  The creator takes a t_embed per member: a single t_embed is repeated n_members times, which is bit for bit the group of one t_embed.  enc_kv() reads
+        the dtype back."""
         if delays is not None and t_embeds is not None:
             raise ValueError("create_stream_group: delays and t_embeds name the same thing, give one")
         if delays is not None:
@@ -1520,7 +1558,9 @@ class Q4VoxtralModel:
             t_embeds = _f32(np.stack([_f32(t).reshape(-1) for t in t_embeds])) if len(t_embeds) else np.zeros((0, self.config.dec_dim), np.float32)
             if t_embeds.shape != (int(n_members), self.config.dec_dim):
                 raise ValueError(f"{t_embeds.shape[0]} t_embeds of {t_embeds.shape[1]} values for {int(n_members)} members of dec_dim {self.config.dec_dim}: one per member")
-        g = LiveStreamGroup(self, t_embed, n_members, gains, enc_capacity_rows, max_positions, sample_rates, page_rows, pool_pages, endless, kv_dtype, burst, t_embeds)
+        if enc_kv_dtype is not None and t_embeds is None:
+            t_embeds = _f32(np.tile(_f32(t_embed).reshape(1, -1), (int(n_members), 1)))
+        g = LiveStreamGroup(self, t_embed, n_members, gains, enc_capacity_rows, max_positions, sample_rates, page_rows, pool_pages, endless, kv_dtype, burst, t_embeds, enc_kv_dtype)
         if attn_split:
             g.set_attn_split(True)
         return g
