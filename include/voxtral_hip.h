@@ -784,6 +784,20 @@ int32_t vox_stream_scores(const vox_stream* s, int32_t first_id, int32_t n, vox_
  * allocations and bits it ran before the feature existed.  vox_stream_attn_split: the flag. */
 int32_t vox_stream_set_attn_split(vox_stream* s, int32_t on);
 int32_t vox_stream_attn_split(const vox_stream* s);
+/* FUSED TICK OPERATORS (opt-in; off by default).  The encoder half of a solo tick runs, per encoder layer, seven launches on the tick's 4 rows: RMSNorm, q|k|v,
+ * ring attention, wo, RMSNorm, w1|w3, w2 -- the four linear operators on the one-row decode GEMV, which streams the weight matrix once per row.  With the flag on, a
+ * pass of exactly 4 rows (a plain tick of a solo stream; not a burst pass of two or more ticks, not a group's round) runs five: the four-row operator
+ * (csrc/vox_rows4.hip: the rows as fixed-point digit planes, exact block sums on the int8 matrix core, ONE pass over the weights) with the norm fused in front of
+ * q|k|v and w1|w3 and the residual / SwiGLU epilogues behind.  The final norm, the adapter, the conv stem, the decode step and every pass with more rows are unchanged.
+ * vox_stream_set_tick_fused: on = 0 / 1, callable between calls, takes effect with the next push / finish; on = 1 is refused with VOX_ERR_INVALID (the message names
+ * the operator; nothing changes) if the four-row operator does not serve an encoder matrix of the model -- it serves Q4_0 matrices with K % 32 == 0, K <= 8192 and
+ * N % 16 == 0.  Nothing is allocated.  The flag survives vox_stream_reset; it is NOT part of a session blob: a restored session has the flag of the stream it was
+ * restored into.  Ids: the plain session's up to near-ties (the summation order differs, as a group's ids relate to a solo stream's); they remain a function of the
+ * samples and the gain alone -- how the samples were cut into calls and where the encoder ring wraps change no bit among fused streams, and a burst stream fed one
+ * tick per call has the fused plain stream's bits when both have the flag on.  With the flag off a session runs the launches, allocations and bits it ran before the
+ * feature existed.  vox_stream_tick_fused: the flag. */
+int32_t vox_stream_set_tick_fused(vox_stream* s, int32_t on);
+int32_t vox_stream_tick_fused(const vox_stream* s);
 /* PEEK.  vox_stream_peek returns the ids vox_stream_finish would return now -- vox_stream_peek_ids of them: vox_stream_schedule_rate(samples pushed, rate, finished = 1)
  * minus the ids handed out -- and leaves the stream what it was, bit for bit: the ids and logits of every later call, the decoder cache's size and engine binding,
  * vox_stream_info [0..4], [6], [7].  It takes no samples: push first, then peek; it may be repeated, and followed by a push, a finish or a reset alike.  The stream runs
@@ -1186,6 +1200,16 @@ typedef struct {
     float* out; void* kc; void* vc; uint16_t* xf_out; float* ssq_out;
 } vox_xf_op_bufs;
 int32_t vox_debug_xf_op(vox_ctx* ctx, const vox_q4* w, vox_xf_op_desc* desc, const vox_xf_op_bufs* bufs);
+/* Debug (tests): ONE launch of the fused tick's four-row operator (csrc/vox_rows4.hip, vox_stream_set_tick_fused) on host buffers:
+ *   out[m][n] = epi( pro(x[m]) . W[n] + bias[n] ),  x [M][K], M in 1..4.
+ * pro: 0 none, 1 RMSNorm (x / sqrt(mean(x^2) + eps) * gamma[K]; gamma required, eps > 0: an all-zero row then gives zeros, not 0 * inf).  epi: 0 store (out [M][N]), 1 residual (out = resid + ., resid [M][N]
+ * required), 2 SwiGLU over interleaved gate / up rows (out [M][N / 2]: silu(row 2 i) * row 2 i + 1).  bias [N]: optional with every epilogue; gamma and resid must be
+ * null where they are not read.  Every argument is checked before the context is bound, and what the operator does not serve -- a tensor that is not Q4_0, M outside
+ * 1..4, K % 32 != 0 or K > 8192, N % 16 != 0 -- is VOX_ERR_INVALID with nothing launched.  vox_debug_rows4_launches: launches of the operator by this process so far
+ * (a counter of its own: vox_debug_gemm_launches does not count them). */
+int32_t vox_debug_rows4_op(vox_ctx* ctx, const vox_q4* w, const float* bias, const float* gamma, float eps, const float* x, int32_t M, float* out, int32_t pro, int32_t epi,
+                           const float* resid);
+int32_t vox_debug_rows4_launches(uint64_t* out);
 /* The live sessions' feed planner on its own (tests): host arithmetic only -- no context, no device, no model.  A fresh session fed at sample_rate (4 encoder rows per
  * position, the Voxtral left pad, no position limit to speak of) takes the calls (n_samples[c], finish[c] 0 / 1) exactly as vox_stream_push / _finish and a group's advance
  * plan and pass them, every due tick taken as run; finish[c] = 2 is a peek (n_samples[c] must be 0): planned as a finish, its one pass emitted, the session as it was.  One row of five words per pass: call index, input samples appended, 16 kHz samples that entered the 16 kHz ring (a

@@ -30,6 +30,8 @@
    all three groups are warmed alike and run one timed pass per loop: pass i of each covers the same positions (the rate groups' to within one tick).
  * --levels: what levels cost (vox_stream_set_levels: one more launch per tick or round, 10 KB of samples read per member), measured as --scores measures scores: twins
    with levels on, pass i behind pass i of the plain session.  Combines with --scores and --alternatives.
+ * --tick-fused: the fused tick operators (set_tick_fused) as a twin of the solo stream, pass i behind pass i of the plain session, with its launches per tick counted
+   (the four-row operator's launches are counted with the linear kernels; the plain tick's two norm launches per encoder layer are gone).
  * --attn-split: the key-split decode attention (set_attn_split) as a twin, measured as --scores measures scores: pass i behind pass i of the plain session.
  * --scores: what scores cost (vox_stream_set_scores: one more launch per tick, one logits row written and read per session).  A second solo stream -- with --group
    also a second group -- runs with scores on, warmed like the first and timed the same way in the same loop: pass i of the scored session follows pass i of the
@@ -116,12 +118,14 @@ class Timer:
 def launch_counts(pkg):
     a = (C.c_uint64 * 20)(); g = (C.c_uint64 * 20)()      # attention forms 0..8, the paged decode forms 11, 12, the ring decode form 13, the ring-table paged forms 14, 15 and the bf16 paged forms 16..19 (9 and 10 are the resampling ingests: not counted here)
     L = pkg.lib(); assert L.vox_debug_attn_launches(a, 20) == 0 and L.vox_debug_gemm_launches(g, 20) == 0
-    return sum(a[:9]) + sum(a[11:]), sum(g)
+    return sum(a[:9]) + sum(a[11:]), sum(g) + pkg.rows4_launches()      # (the fused tick's four-row operator has a counter of its own; a plain stream never launches it)
 
 
 def twin_kinds(a):
     """--scores / --alternatives K / --levels: (what is on, how a solo stream turns it on, how a group member does)."""
     kinds = []
+    if a.tick_fused:      # (a solo stream's flag: the group rows of --group run without it)
+        kinds.append(("tick fused on", lambda st: st.set_tick_fused(True), lambda g, k: None))
     if a.attn_split:      # (a group's flag is one for all members: setting it per member again changes nothing)
         kinds.append(("attn split on", lambda st: st.set_attn_split(True), lambda g, k: g.set_attn_split(True)))
     if a.levels:
@@ -137,6 +141,8 @@ def twin_recorded(what, st):
     """Every id of the timed twin got its record."""
     if what.startswith("attn split"):
         return st.attn_split()
+    if what.startswith("tick fused"):
+        return st.tick_fused()
     if what.startswith("levels"):      # (the ids of the warm-up push included: the twin had levels on from its first tick)
         return not np.isnan(st.levels()["peak"]).any()
     return not np.isnan(st.scores()["logprob"]).any() if what.startswith("scores") else not np.isnan(st.alternatives()["entropy"]).any()
@@ -518,6 +524,8 @@ def main():
     ap.add_argument("--group", help="N[,N...]: measure stream-group rounds of these widths next to the solo tick instead of the solo tick and its baseline")
     ap.add_argument("--rate", type=int, default=0, metavar="SR", help="with --group: also time a group whose members are all fed at SR Hz, next to the 16 kHz f32 round")
     ap.add_argument("--s16", action="store_true", help="with --rate: feed that group 16-bit PCM")
+    ap.add_argument("--tick-fused", action="store_true", help="also time a solo stream with the fused tick operators on (set_tick_fused), pass by pass next to the plain one, "
+                    "and count its launches per tick; not with --group (a group's rounds do not read the flag)")
     ap.add_argument("--attn-split", action="store_true", help="also time a stream (with --group: and a group) with the key-split decode attention on "
                     "(set_attn_split), pass by pass next to the plain one, as --scores does; a solo stream runs it on its per-operator steps alone (past 1024 cache rows)")
     ap.add_argument("--scores", action="store_true", help="also time a stream (with --group: and a group) with scores on, pass by pass next to the unscored one")
@@ -536,6 +544,8 @@ def main():
                     "pass by pass in one run (nothing else is measured)")
     ap.add_argument("--snapshot", action="store_true", help="time vox_stream_snapshot / vox_stream_restore (device and host blobs) at three positions next to a device copy of the same size (nothing else is measured)")
     a = ap.parse_args()
+    if a.tick_fused and a.group:
+        ap.error("--tick-fused times a solo stream: not with --group")
     bursts = [int(v) for v in a.burst.split(",")] if a.burst else []
     if bursts and a.group:      # --group N --burst B[,B...]: the burst groups' mode (B = 0 alone: the plain group by itself, for a build without burst groups)
         if a.endless or a.peek or a.scores or a.alternatives or a.levels or a.page_rows or a.memory_past_window or a.snapshot or a.rate or "," in a.group:
@@ -661,12 +671,14 @@ def main():
     for what, on_solo, _ in twin_kinds(a):
         st_s = m.create_stream(t, gain=gain); on_solo(st_s); st_s.push(x[:pos]); twins.append((what, st_s, []))
     e0 = st.info()
-    per = []; counted = 0
+    per = []; counted = 0; counted_fused = 0
     for _ in range(a.passes):
         seg = x[pos:pos + 2560 * a.ticks]; pos += 2560 * a.ticks
         k0 = launch_counts(pkg); per.append(tm.ms(lambda: st.push(seg)) / a.ticks); k1 = launch_counts(pkg); counted += sum(k1) - sum(k0)
         for what, st_s, per_s in twins:
             k2 = launch_counts(pkg); per_s.append(tm.ms(lambda: st_s.push(seg)) / a.ticks)
+            if what.startswith("tick fused"):
+                counted_fused += sum(launch_counts(pkg)) - sum(k2); continue
             assert sum(launch_counts(pkg)) - sum(k2) == sum(k1) - sum(k0)      # the counted launches are the plain stream's (the record kernel is uncounted: one per tick)
     e1 = st.info()
     ticks = a.ticks * a.passes
@@ -690,6 +702,8 @@ def main():
         ts = statistics.median(per_s)
         lines.append(f"stream tick with {what} (a second stream, pass i behind pass i above): median {ts:.3f} ms  passes " + " ".join(f"{v:.3f}" for v in per_s) +
                      f"   difference to {what.split()[0]} off {ts - tick:+.3f} ms ({100 * (ts - tick) / tick:+.2f} %), per pass " + " ".join(f"{v - w:+.3f}" for v, w in zip(per_s, per)))
+        if what.startswith("tick fused"):
+            lines.append(f"  launches per fused tick: {counted_fused / ticks + fixed - 2 * c.enc_layers:.0f} = {counted_fused / ticks:.0f} counted + {fixed - 2 * c.enc_layers} uncounted (arithmetic, not a count: norm launches have no counter, the plain tick's figure less the two per encoder layer that the fused pass does not make); the plain tick: {counted + fixed:.0f}")
 
     # ---- the baseline: 16-frame chunks through the cached encoder + one piecewise decoder step per chunk
     mel = np.ascontiguousarray(pkg.MelSpectrogram.voxtral(ctx).compute_log(pkg.pad_audio(pkg.peak_normalize(x))).T)      # [128][T]

@@ -230,6 +230,7 @@ SIGNATURES = {
     "vox_score_rows": (i32, [vp, vp, i32, i32, vp, vp, i32]),
     "vox_stream_set_scores": (i32, [vp, i32]),
     "vox_stream_set_attn_split": (i32, [vp, i32]), "vox_stream_attn_split": (i32, [vp]),
+    "vox_stream_set_tick_fused": (i32, [vp, i32]), "vox_stream_tick_fused": (i32, [vp]),
     "vox_stream_group_set_attn_split": (i32, [vp, i32]), "vox_stream_group_attn_split": (i32, [vp]),
     "vox_stream_scores": (i32, [vp, i32, i32, vp]),
     "vox_stream_group_set_scores": (i32, [vp, i32, i32]),
@@ -279,6 +280,7 @@ SIGNATURES = {
     "vox_debug_resid_xf": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     # (ctx, w, vox_xf_op_desc, vox_xf_op_bufs): ONE operator of the batched XF decode step (one group or the wide step), or the encoder's RoPE rows
     "vox_debug_xf_op": (i32, [vp, vp, vp, vp]),
+    "vox_debug_rows4_op": (i32, [vp, vp, vp, vp, C.c_float, vp, i32, vp, i32, i32, vp]), "vox_debug_rows4_launches": (i32, [P(C.c_uint64)]),
     # levels: (stream, on); (stream, first_id, n, out); (stream, peak_below, ticks); the same with a member; (k, first, end);
     # (ctx, n_members, rings, ring_n, gains, pos, frame, order, n_slots, ticks, burst_b or null, list_len, out): ONE launch of the level kernel
     "vox_stream_set_levels": (i32, [vp, i32]),

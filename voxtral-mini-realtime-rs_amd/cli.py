@@ -132,8 +132,9 @@ class Endpoint:
 
 
 def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_rate=False, words_out=None, peek=False, alts_k=0, endless=False, suspend_every=0, burst=0, levels=False,
-                    endpoint_ms=0, endpoint_db=-50.0, attn_split=False):
+                    endpoint_ms=0, endpoint_db=-50.0, attn_split=False, tick_fused=False):
     """(attn_split, --live-attn-split: the session runs with the key-split decode attention on, vox_stream_set_attn_split.)
+    (tick_fused, --live-tick-fused: the session's ticks run their encoder layers on the four-row operator, vox_stream_set_tick_fused; the line is the plain one's up to near-ties.)
     --live: the file through a live session (vox_stream) in pieces of `chunk_ms` milliseconds, the text so far on stderr whenever ids arrive.  The gain is the
     file's peak scale 0.95 / max|x| (bin/transcribe.rs:207; a file is known in advance -- a microphone caller passes its own), the whole file is one utterance (no
     --max-mel-frames chunks: the session's state is bounded by its ring), so the line equals the un-chunked path's.
@@ -167,7 +168,7 @@ def transcribe_live(pkg, path, model, tokenizer, mel, t_embed, chunk_ms, native_
     gain = float(np.float32(0.95) / peak) if peak >= 1e-10 else 1.0              # audio/io.rs:59-68
     step = max(1, int(round(rate * chunk_ms / 1000.0)))
     def create():
-        st = model.create_stream(t_embed, gain=gain, sample_rate=rate, endless=endless, burst=burst or None, attn_split=attn_split)
+        st = model.create_stream(t_embed, gain=gain, sample_rate=rate, endless=endless, burst=burst or None, attn_split=attn_split, tick_fused=tick_fused)
         if words_out is not None:
             st.set_scores(True)
             if alts_k:
@@ -458,6 +459,9 @@ def main(argv=None):
     ap.add_argument("--live-attn-split", action="store_true", help="with --live (also with --live-group): run the sessions with the key-split decode attention "
                     "(vox_stream_set_attn_split / vox_stream_group_set_attn_split): the decode attention's work is split over the keys, for long sessions; the text is the "
                     "plain session's up to near-ties")
+    ap.add_argument("--live-tick-fused", action="store_true", help="with --live (a solo session; not with --live-group): run every tick's encoder layers on the four-row "
+                    "operator (vox_stream_set_tick_fused): five launches per layer instead of seven, one pass over the weights instead of four; the text is the plain "
+                    "session's up to near-ties")
     ap.add_argument("--live-levels", action="store_true", help="with --live (also with --live-group): run the sessions with levels on (vox_stream_set_levels): every "
                     "--live-words line also carries peak_db and rms_db, the level of the audio the model had just heard while it chose the word's ids")
     ap.add_argument("--live-endpoint-ms", type=int, default=None, metavar="MS", help="with --live (implies --live-levels): the end-of-speech hint -- after a push whose quiet time "
@@ -494,6 +498,8 @@ def main(argv=None):
         ap.error("--live-endpoint-ms MS (MS > 0) applies with --live")
     if a.live_attn_split and not a.live:
         ap.error("--live-attn-split applies with --live")
+    if a.live_tick_fused and (not a.live or a.live_group):
+        ap.error("--live-tick-fused applies with --live, to a solo session (not with --live-group)")
     if a.live_levels and not a.live:
         ap.error("--live-levels applies with --live")
     a.live_endpoint_ms = a.live_endpoint_ms or 0
@@ -637,7 +643,7 @@ def main(argv=None):
         p = paths[i]
         try:
             t1 = time.time()
-            text = transcribe_live(pkg, p, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_native_rate, words_out, a.live_peek, a.live_alternatives, a.live_endless, a.live_suspend_every, a.live_burst, a.live_levels, a.live_endpoint_ms, a.live_endpoint_db, a.live_attn_split) if a.live else transcribe_one(pkg, p, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed, rec_out, a.alternatives or 0)
+            text = transcribe_live(pkg, p, model, tokenizer, mel, t_embed, a.live_chunk_ms, a.live_native_rate, words_out, a.live_peek, a.live_alternatives, a.live_endless, a.live_suspend_every, a.live_burst, a.live_levels, a.live_endpoint_ms, a.live_endpoint_db, a.live_attn_split, a.live_tick_fused) if a.live else transcribe_one(pkg, p, model, tokenizer, mel, pad_cfg, chunk_cfg, t_embed, rec_out, a.alternatives or 0)
             log(f"{p}: {time.time() - t1:.3f}s")
         except Exception as e:      # per-utterance failure isolates to that line (empty), eval_wer.py:211-223 tolerates it
             log(f"Error transcribing {p}: {e}"); text = ""; rc = 1

@@ -3302,6 +3302,8 @@ struct vox_stream {
     // vox_stream_set_attn_split: while on, the per-operator decode step runs the key-split attention (flat rows, ring rows past the wrap) + the wo GEMV; the engine's
     // steps are what they are.  split_ws: its workspace, for the most chunks the session's cache can come to (dec_limit rows), allocated at the first on
     bool attn_split = false; float* split_ws = nullptr;
+    // vox_stream_set_tick_fused: while on, a pass of exactly 4 rows (stream_tick) runs its encoder layers on the four-row operator (StreamRound::tick_fused)
+    bool tick_fused = false;
 };
 static const int STREAM_TAIL_TICKS = 63;            // the most ticks a finish / peek tail of an endless session may run (peek_max_ticks at the session's rate, asserted at create and in every peek)
 static const int STREAM_ROPE_DEC_ROWS = 1024;       // rows of an endless session's decoder RoPE ring = the most ticks of one pass; the encoder's ring has reshape_factor times as many
@@ -3601,7 +3603,7 @@ static int32_t stream_verify(vox_stream* st) {      // inside a long push: befor
 // w1|w3, w2 } -> final norm -> adapter, every weight matrix in ONE launch for all sessions of the round (4 n rows through q4_linear_dev, which picks the kernel by the row
 // count).  Slot z works for session r.order[z] (device arrays); w.arow[z] is its adapter row.  ftap_*: a solo stream's front tap (null: none).
 // rope (null: the model's streaming table): a solo endless session's encoder RoPE ring, rows = position & rope_mask (StreamAttnParams::rope_mask)
-struct StreamRound { const StreamMember* mem; const int* order; int n, cap; size_t ring_layer; MelTables mel; long left; const float* rope = nullptr; int rope_mask = 0, rope_stride = 0; bool levels = false; int ring_dtype = vox::RING_F32; };      // rope_stride > 0: an endless group's rings, one per member; levels: some session of the round has levels on; ring_layer counts elements of ring_dtype
+struct StreamRound { const StreamMember* mem; const int* order; int n, cap; size_t ring_layer; MelTables mel; long left; const float* rope = nullptr; int rope_mask = 0, rope_stride = 0; bool levels = false; int ring_dtype = vox::RING_F32; bool tick_fused = false; };      // tick_fused: a solo stream with vox_stream_set_tick_fused on (read by a pass of exactly 4 rows); rope_stride > 0: an endless group's rings, one per member; levels: some session of the round has levels on; ring_layer counts elements of ring_dtype
 // b > 1 (a solo burst stream's round of one, n == 1): the encoder of b ticks in one pass.  Everything the b ticks would read is there before the first (the pass's
 // samples, the state block at the burst's first tick), and tick t's rows are rows 4 t .. of every buffer: 16 b + 3 halo frames, 8 b + 1 and 4 b conv windows, 4 b rows
 // through the layers with the burst attention, b adapter rows (w.arow[t]: tick t's).  ftap_*: room for ftap_b of the burst's ticks, in the per-tick layout.
@@ -3633,15 +3635,32 @@ static int32_t stream_encode_round(vox_model* m, const StreamWs& w, const Stream
         HIPCHK(hipMemcpyAsync(ftap_conv, w.x, (size_t)ftap_b * R * D * 4, hipMemcpyDeviceToDevice, s));
     }
     float *x = w.x, *xn = w.xn;
+    // the fused tick (vox_stream_set_tick_fused): a pass of exactly 4 rows runs every layer as five launches -- the four-row operator with the norm in front of
+    // q|k|v and w1|w3 and the residual / SwiGLU behind (vox_rows4.hip); every other pass runs what it ran
+    const bool fused = r.tick_fused && n == 1 && b == 1 && !rg && M <= 4;
+    const auto rows4 = [&](const Q4W& wt, const float* bias, const float* in, int in_stride, const float* gamma, float* out, int out_stride, int epi) -> int32_t {
+        Rows4Params p{}; p.w = wt; p.x = in; p.x_stride = in_stride; p.M = M; p.out = out; p.out_stride = out_stride; p.bias = bias; p.gamma = gamma; p.eps = c.norm_eps;
+        if (epi == EPI_RESID) { p.resid = out; p.resid_stride = out_stride; }
+        HIPCHK(launch_q4_rows4(p, gamma ? PRO_RMS : PRO_NONE, epi, s)); return VOX_OK;
+    };
     for (int l = 0; l < c.enc_layers; l++) {
         const EncLayer& L = m->enc[l];
-        HIPCHK(launch_rms_norm(x, D, M, D, L.attn_norm, nullptr, c.norm_eps, xn, D, s));
-        VOXCHK(q4_linear_dev(cx, L.wqkv.w, L.wqkv.bias, xn, D, M, w.qkv, 3 * QD));
+        if (fused) VOXCHK(rows4(L.wqkv.w, L.wqkv.bias, x, D, L.attn_norm, w.qkv, 3 * QD, EPI_STORE));
+        else {
+            HIPCHK(launch_rms_norm(x, D, M, D, L.attn_norm, nullptr, c.norm_eps, xn, D, s));
+            VOXCHK(q4_linear_dev(cx, L.wqkv.w, L.wqkv.bias, xn, D, M, w.qkv, 3 * QD));
+        }
         StreamAttnParams ap{}; ap.qkv = w.qkv; ap.qkv_stride = 3 * QD; ap.mem = r.mem; ap.order = r.order; ap.n = n; ap.ring_off = (size_t)l * r.ring_layer; ap.cap = r.cap;
         ap.cos_t = m->enc_cos_s; ap.sin_t = m->enc_sin_s; ap.out = w.att;
         if (r.rope) { ap.cos_t = r.rope; ap.sin_t = r.rope + hd / 2; ap.rope_mask = r.rope_mask; ap.rope_stride = r.rope_stride; } ap.out_stride = QD; ap.M = R * b; ap.n_heads = H; ap.window = c.enc_window; ap.ring_dtype = r.ring_dtype;
         if (rg) HIPCHK(launch_stream_attn_group_burst(ap, rg->dev, *rg->host, R, hd, s));
         else HIPCHK(b >= 2 ? launch_stream_attn_burst(ap, hd, s) : launch_stream_attn(ap, hd, s));
+        if (fused) {
+            VOXCHK(rows4(L.wo.w, L.wo.bias, w.att, QD, nullptr, x, D, EPI_RESID));
+            VOXCHK(rows4(L.w13.w, nullptr, x, D, L.ffn_norm, w.ffn, F, EPI_SWIGLU));
+            VOXCHK(rows4(L.w2.w, L.w2.bias, w.ffn, F, nullptr, x, D, EPI_RESID));
+            continue;
+        }
         VOXCHK(q4_linear_dev(cx, L.wo.w, L.wo.bias, w.att, QD, M, x, D, EPI_RESID, x, D));
         HIPCHK(launch_rms_norm(x, D, M, D, L.ffn_norm, nullptr, c.norm_eps, xn, D, s));
         VOXCHK(q4_linear_dev(cx, L.w13.w, nullptr, xn, D, M, w.ffn, F, EPI_SWIGLU));
@@ -3724,7 +3743,7 @@ static int32_t stream_tick(vox_stream* st) {
     VOXCHK(stream_tick_prepare(st));
     const bool ring = stream_in_ring(st);
     StreamWs w; stream_ws_carve(m, 1, st->ws, &w);
-    StreamRound r{st->d_mem, st->d_order, 1, st->cap, st->ring_layer, st->mel, st->left}; r.levels = st->lv.on;
+    StreamRound r{st->d_mem, st->d_order, 1, st->cap, st->ring_layer, st->mel, st->left}; r.levels = st->lv.on; r.tick_fused = st->tick_fused;
     if (ring) { r.rope = st->rope.enc; r.rope_mask = STREAM_ROPE_DEC_ROWS * R - 1; }
     const int k = st->ftap_mel ? st->ftap_ticks++ : 0; const bool ftap = st->ftap_mel && k < st->ftap_max;      // (a re-run repeats decode steps, never a tick)
     VOXCHK(stream_encode_round(m, w, r, ftap ? st->ftap_mel + (size_t)k * 4 * R * c.n_mels : nullptr, ftap ? st->ftap_conv + (size_t)k * R * c.enc_dim : nullptr));
@@ -3948,6 +3967,25 @@ extern "C" int32_t vox_stream_set_attn_split(vox_stream* st, int32_t on) {
     return VOX_OK;
 }
 extern "C" int32_t vox_stream_attn_split(const vox_stream* st) { return st && st->attn_split ? 1 : 0; }
+// the fused tick operators on / off.  Checked once, here: every encoder operator of the model against the four-row launcher's own predicate, in the form the tick
+// would launch it.  Nothing is allocated; behind a synchronisation, as above: a tick in flight keeps the form it was enqueued with
+extern "C" int32_t vox_stream_set_tick_fused(vox_stream* st, int32_t on) {
+    ARGCHK(st, "null stream"); ARGCHK(on == 0 || on == 1, "on must be 0 or 1");
+    if (on) {
+        const vox_model* m = st->m; const int R = m->cfg.reshape_factor;
+        ARGCHK(R >= 1 && R <= 4, "the fused tick operators take a tick of up to 4 encoder rows (this model: %d)", R);
+        for (int l = 0; l < m->cfg.enc_layers; l++) {
+            const EncLayer& L = m->enc[l];
+            const struct { const char* name; const Q4W* w; int pro, epi; } ops[4] = {{"q|k|v", &L.wqkv.w, PRO_RMS, EPI_STORE}, {"wo", &L.wo.w, PRO_NONE, EPI_RESID}, {"w1|w3", &L.w13.w, PRO_RMS, EPI_SWIGLU}, {"w2", &L.w2.w, PRO_NONE, EPI_RESID}};
+            for (const auto& o : ops)
+                ARGCHK(q4_rows4_serves(*o.w, R, o.pro, o.epi), "the fused tick operators do not serve encoder layer %d's %s (format %d, [%d][%d]): Q4_0 with K %% 32 == 0, K <= 8192, N %% 16 == 0", l, o.name, o.w->fmt, o.w->N, o.w->K);
+        }
+    }
+    VOXCHK(ctx_bind(st->ctx)); HIPCHK(hipStreamSynchronize(st->ctx->stream));
+    st->tick_fused = on != 0;
+    return VOX_OK;
+}
+extern "C" int32_t vox_stream_tick_fused(const vox_stream* st) { return st && st->tick_fused ? 1 : 0; }
 extern "C" int32_t vox_stream_scores(const vox_stream* st, int32_t first_id, int32_t n, vox_token_score* out) {
     ARGCHK(st, "null stream");
     return st->sc.read(st->feed.ids_out, first_id, n, out);

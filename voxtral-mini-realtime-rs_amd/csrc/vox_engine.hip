@@ -37,6 +37,7 @@ namespace vox {
 namespace {
 
 #include "vox_engine_common.h"
+#include "vox_digits.h"      // to_digits, digits_finish, i4v
 
 // lm_head pass q (= 12 * packet + consumer wave) on CU b: the row; lane holds block `lane` and half (lane & 1) of block 64 + lane / 2
 __global__ __launch_bounds__(64) void eng_pack_lm_kernel(Q4W w, unsigned char* __restrict__ stream, size_t op_off, int vocab) {
@@ -359,7 +360,6 @@ struct PassA { uint4 q0; uint2 q1; float s0, s1; };
 // x_int = rint(x * 2^shift) = d0 + 128 d1 + 128^2 d2 + 128^3 d3 (d0..d2 in 0..127, d3 signed), and per block {-8 * sum(x_int), 2^-shift}.
 // MFMA operand A, row m = 4 p + c: digit c of the step's block p, zero in the other block's columns -> D[4 p + c][n] = sum over block p of digit_c(x_k) * q[n][k]
 // EXACTLY (int32).  Lane group g < 2 then holds the four digit sums of block g for tile row n: Horner in f32, the -8 offset, the two scales.
-typedef int i4v __attribute__((ext_vector_type(4)));
 struct StepCtx { i4v A; float m8sx, sxinv; };
 // one step record as this lane holds it: 8 bytes of nibbles + the f16 scale bits of its block.  Records do not depend on the step's activations, so a wave
 // moves them from the ring into REGISTERS while it waits for an edge (and frees the ring slots for the loader: the register file is the bigger buffer)
@@ -379,11 +379,7 @@ __device__ __forceinline__ RecR rec_read(const unsigned char* rec, bool half, in
 // one MFMA step of a 16-row (or 8-row) tile: acc += (block scale) * (x block scale) * sum_k x_int[k] * (q[k] - 8) for this lane's block of tile row n
 __device__ __forceinline__ float mstep(const RecR& r, const StepCtx& cx, float acc) {
     const i4v D = __builtin_amdgcn_mfma_i32_16x16x64_i8(cx.A, r.B, i4v{0, 0, 0, 0}, 0, 0, 0);
-    // digits -> value: (D0 + 128 D1) and (D2 + 128 D3) exactly in int32 (v_lshl_add_u32; |D| <= 32 * 15 * 128), then one f32 FMA (one rounding, as before)
-    const int lo = (int)((unsigned)D[0] + ((unsigned)D[1] << 7)), hi = (int)((unsigned)D[2] + ((unsigned)D[3] << 7));
-    float t = fmaf((float)hi, 16384.0f, (float)lo);
-    t += cx.m8sx;
-    return fmaf(t, r.sc * cx.sxinv, acc);
+    return digits_finish(D, cx.m8sx, r.sc, cx.sxinv, acc);      // vox_digits.h: Horner in int32, one f32 FMA, the -8 offset, the two scales
 }
 // ---- paired steps: TWO K-steps per epilogue, on all 64 lanes ----
 // A single step's A has digits in rows 0..7 only, so D rows 8..15 (lane groups 2, 3) are zeros and half the epilogue's lanes work for nothing.  The two halves of D
@@ -428,10 +424,7 @@ __device__ __forceinline__ RecR rec_read_lo(const unsigned char* rec, int lane) 
 __device__ __forceinline__ float mstep2(const RecP& r, const PairCtx& cx, float acc) {
     i4v D = __builtin_amdgcn_mfma_i32_16x16x64_i8(cx.Alo, r.Ba, i4v{0, 0, 0, 0}, 0, 0, 0);
     D = __builtin_amdgcn_mfma_i32_16x16x64_i8(cx.Ahi, r.Bb, D, 0, 0, 0);
-    const int lo = (int)((unsigned)D[0] + ((unsigned)D[1] << 7)), hi = (int)((unsigned)D[2] + ((unsigned)D[3] << 7));
-    float t = fmaf((float)hi, 16384.0f, (float)lo);
-    t += cx.m8sx;
-    return fmaf(t, r.sc * cx.sxinv, acc);
+    return digits_finish(D, cx.m8sx, r.sc, cx.sxinv, acc);
 }
 __device__ __forceinline__ float mstep2(const unsigned char* rec_a, const unsigned char* rec_b, bool half, int lane, const PairCtx& cx, float acc) { return mstep2(rec_read2(rec_a, rec_b, half, lane), cx, acc); }
 // the four lane groups' partials of tile row n in ONE fixed order, (g0 + g2) + (g1 + g3), valid in lanes 0..15: v_permlane32_swap, v_permlane16_swap and two adds --
@@ -442,29 +435,6 @@ __device__ __forceinline__ float g4_sum(float v) {
     const auto b = __builtin_amdgcn_permlane16_swap(__float_as_uint(w), __float_as_uint(w), false, false);
     return __uint_as_float(b[0]) + __uint_as_float(b[1]);
 }
-// Four consecutive elements of a 32-element block (8 consecutive lanes = one block, this lane: elements [4 (lane & 7), +4)) -> digit planes + block info
-__device__ __forceinline__ void to_digits(const float (&v)[4], int lane, unsigned char* plane_blk, float2* binfo_blk) {
-    float mx = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
-    mx = fmaxf(mx, dppf<0xB1>(mx)); mx = fmaxf(mx, dppf<0x4E>(mx)); mx = fmaxf(mx, dppf<0x141>(mx));      // over the block's 8 lanes
-    int e = __builtin_amdgcn_frexp_expf(mx);          // mx < 2^e (0 for mx == 0)
-    e = max(e, -100);
-    const float f = ldexpf(1.0f, 26 - e);
-    int xi[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) xi[i] = (int)rintf(v[i] * f);
-    int s = (xi[0] + xi[1]) + (xi[2] + xi[3]);
-    s += dppi<0xB1>(s); s += dppi<0x4E>(s); s += dppi<0x141>(s);      // exact: |x_int| <= 2^26, 32 of them
-    if ((lane & 7) == 0) *binfo_blk = make_float2(-8.0f * (float)s, ldexpf(1.0f, e - 26));
-    const int e0 = 4 * (lane & 7), h = (e0 >> 3) & 1, off = (e0 & 4) + 8 * (e0 >> 4);
-#pragma unroll
-    for (int cdig = 0; cdig < 4; cdig++) {
-        unsigned d = 0;
-#pragma unroll
-        for (int i = 0; i < 4; i++) { const int dv = cdig < 3 ? (xi[i] >> (7 * cdig)) & 127 : xi[i] >> 21; d |= (unsigned)(dv & 0xFF) << (8 * i); }
-        *reinterpret_cast<unsigned*>(plane_blk + (cdig * 2 + h) * 16 + off) = d;
-    }
-}
-
 struct Cons {
     const EngParams& p; EngCtl* c; unsigned char* lds; int cw, lane; unsigned P; unsigned cbar_n;
     __device__ __forceinline__ Cons(const EngParams& p_, EngCtl* c_, unsigned char* lds_, int cw_, int lane_) : p(p_), c(c_), lds(lds_), cw(cw_), lane(lane_), P(0), cbar_n(0) {}

@@ -76,6 +76,23 @@ int q4_gemv_nwv(int K, int epi);        // waves per workgroup the launcher will
 int q4_gemv_grid_k(int N, int K, int R, int epi);
 int dense_gemv_grid(int N);        // same, for WFMT_BF16 weights   // workgroups launched for N rows at R rows per wave (== number of argmax partials)
 
+// ---- four-row Q4 operator on the int8 matrix core (vox_rows4.hip; a live session's fused tick): out[m][n] = epi( pro(x[m]) . W[n] + bias[n] ), M <= 4 rows in ONE
+// pass over the weights -- the rows staged once per workgroup as fixed-point digit planes (vox_digits.h), exact int32 block sums on v_mfma_i32_16x16x64_i8.
+// pro: PRO_NONE / PRO_RMS (x / rms(x) * gamma, rstd applied in the epilogue); epi: EPI_STORE / EPI_RESID (out = resid + .; resid may be out) / EPI_SWIGLU (interleaved
+// gate / up rows, out [M][N / 2]); bias optional with every epilogue (SwiGLU: added to gate and up).  x rows and gamma are read as float4 (16-byte aligned, x_stride % 4 == 0).
+struct Rows4Params {
+    Q4W w;
+    const float* x; int x_stride; int M;
+    float* out; int out_stride;
+    const float* bias;                    // [N] or null
+    const float* resid; int resid_stride; // EPI_RESID
+    const float* gamma; float eps;        // PRO_RMS
+};
+// what the launcher serves: WFMT_Q4_0, M in 1..4, K % 32 == 0, K <= 8192 (the digit planes of four rows in a workgroup's LDS), N % 16 == 0, the pro / epi above
+bool q4_rows4_serves(const Q4W& w, int M, int pro, int epi);
+hipError_t launch_q4_rows4(const Rows4Params& p, int pro, int epi, hipStream_t s);      // hipErrorInvalidValue, nothing launched: anything it does not serve
+unsigned long long q4_rows4_launches();      // host-side launch count (vox_debug_rows4_launches); a counter of its own, no GemmForm slot
+
 // ---- Q4 GEMM on MFMA (prefill / encoder, rows of x > 4): out[M][N'] = epi( x[M][K] * W^T )
 struct GemmParams {
     Q4W w;

@@ -342,6 +342,32 @@ extern "C" int32_t vox_debug_xf_op(vox_ctx* c, const vox_q4* w, vox_xf_op_desc* 
     HIPCHK(hipStreamSynchronize(s));
     return VOX_OK;
 }
+// ---- debug: ONE launch of the fused tick's four-row operator (launch_q4_rows4) on host buffers (tests; include/voxtral_hip.h).  Every argument is checked before the
+// context is bound; the launcher's own refusal (q4_rows4_serves) is asked first, so nothing it does not serve reaches a device.
+extern "C" int32_t vox_debug_rows4_op(vox_ctx* c, const vox_q4* w, const float* bias, const float* gamma, float eps, const float* x, int32_t M, float* out, int32_t pro, int32_t epi,
+                                      const float* resid) {
+    ARGCHK(c && w && x && out, "null argument");
+    ARGCHK(pro == 0 || pro == 1, "pro %d: 0 none, 1 RMSNorm", pro); ARGCHK(epi >= 0 && epi <= 2, "epi %d: 0 store, 1 residual, 2 SwiGLU", epi);
+    ARGCHK((pro == 1) == (gamma != nullptr), "gamma goes with pro 1 alone"); ARGCHK((epi == 1) == (resid != nullptr), "resid goes with epi 1 alone");
+    ARGCHK(pro == 0 || eps > 0.f, "eps must be a positive number (with eps 0 an all-zero row's rstd is infinite)");
+    const int K = w->w.K, N = w->w.N, kpro = pro ? PRO_RMS : PRO_NONE, kepi = epi == 1 ? EPI_RESID : epi == 2 ? EPI_SWIGLU : EPI_STORE, No = epi == 2 ? N / 2 : N;
+    ARGCHK(M >= 1 && M <= 4, "M %d out of range (1..4)", M);
+    ARGCHK(q4_rows4_serves(w->w, M, kpro, kepi), "the four-row operator serves Q4_0 tensors with K %% 32 == 0, K <= 8192 and N %% 16 == 0 (fmt %d, K %d, N %d)", w->w.fmt, K, N);
+    VOXCHK(ctx_bind(c)); hipStream_t s = c->stream;
+    DevBuf dx, db, dg, dr, dy;
+    auto up = [&](DevBuf& d, const void* src, size_t bytes) -> int32_t {
+        if (!src) return VOX_OK;
+        HIPCHK(d.alloc(bytes)); HIPCHK(hipMemcpyAsync(d.p, src, bytes, hipMemcpyHostToDevice, s)); return VOX_OK;
+    };
+    VOXCHK(up(dx, x, (size_t)M * K * 4)); VOXCHK(up(db, bias, (size_t)N * 4)); VOXCHK(up(dg, gamma, (size_t)K * 4)); VOXCHK(up(dr, resid, (size_t)M * N * 4));
+    HIPCHK(dy.alloc((size_t)M * No * 4));
+    Rows4Params p{}; p.w = w->w; p.x = dx.as<float>(); p.x_stride = K; p.M = M; p.out = dy.as<float>(); p.out_stride = No; p.bias = bias ? db.as<float>() : nullptr;
+    p.resid = resid ? dr.as<float>() : nullptr; p.resid_stride = N; p.gamma = gamma ? dg.as<float>() : nullptr; p.eps = eps;
+    HIPCHK(launch_q4_rows4(p, kpro, kepi, s));
+    HIPCHK(hipMemcpyAsync(out, dy.p, (size_t)M * No * 4, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
+    return VOX_OK;
+}
+extern "C" int32_t vox_debug_rows4_launches(uint64_t* out) { ARGCHK(out, "null argument"); *out = (uint64_t)q4_rows4_launches(); return VOX_OK; }
 // ConvDownsampler::forward (models/layers/conv.rs:78-83): gelu(conv1d k3 s2 p1) twice, x [C][L] -> [O][L2], on the product's im2col MFMA path (conv_stem_dev)
 extern "C" int32_t vox_conv_downsample(vox_ctx* c, const float* x, int32_t C, int32_t L, const float* w1, const float* b1, const float* w2, const float* b2, int32_t O, float* out) {
     ARGCHK(c && x && w1 && b1 && w2 && b2 && out && C > 0 && L > 0 && O > 0, "bad argument"); ARGCHK((3 * C) % 128 == 0 && (3 * O) % 128 == 0, "3 * channels must be a multiple of 128");

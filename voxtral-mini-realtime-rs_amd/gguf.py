@@ -238,6 +238,28 @@ def linear_forward(weights: Q4Tensor, x, bias=None, epilogue=0):
     return out
 
 
+def rows4_forward(weights: Q4Tensor, x, bias=None, gamma=None, eps=1e-5, epilogue=0, resid=None):
+    """One launch of the fused tick's four-row operator (vox_debug_rows4_op; LiveStream.set_tick_fused runs it in a session): x [M <= 4, K] ->
+    epi(pro(x) W^T + bias).  gamma [K]: RMSNorm in front (x / sqrt(mean(x^2) + eps) * gamma).  epilogue 0 store, 1 residual (resid [M, N]), 2 SwiGLU over
+    interleaved gate / up rows -> N / 2 columns.  What the operator does not serve (a dense tensor, M > 4, N % 16 != 0, K > 8192) raises VoxError."""
+    x = _f32(x)
+    if x.ndim != 2 or x.shape[1] != weights.shape()[1]:
+        raise VoxError(1, f"rows4_forward expects x [M, K={weights.shape()[1]}], got {list(x.shape)}")
+    m, n = x.shape[0], weights.shape()[0]
+    bb, gg, rr = (None if a is None else _f32(a) for a in (bias, gamma, resid))
+    if (bb is not None and bb.size != n) or (gg is not None and gg.size != x.shape[1]) or (rr is not None and rr.shape != (m, n)):
+        raise VoxError(1, "rows4_forward: bias [N], gamma [K], resid [M, N]")
+    out = np.empty((m, n // 2 if epilogue == 2 else n), dtype=np.float32)
+    check(lib().vox_debug_rows4_op(weights.ctx.h, weights.h, None if bb is None else _ptr(bb), None if gg is None else _ptr(gg), float(eps), _ptr(x), m, _ptr(out),
+                                   0 if gg is None else 1, int(epilogue), None if rr is None else _ptr(rr)))
+    return out
+
+
+def rows4_launches() -> int:
+    """Launches of the four-row operator by this process so far (vox_debug_rows4_launches)."""
+    v = C.c_uint64(); check(lib().vox_debug_rows4_launches(C.byref(v))); return int(v.value)
+
+
 def conv_downsample(ctx, x, w1, b1, w2, b2):
     """ConvDownsampler::forward (models/layers/conv.rs:78-83): x [C, L] -> [O, L2] through the conv stem's im2col MFMA path."""
     x, w1, b1, w2, b2 = (_f32(a) for a in (x, w1, b1, w2, b2))
@@ -966,6 +988,15 @@ class LiveStream:
     def attn_split(self) -> bool:
         return bool(lib().vox_stream_attn_split(self.h))
 
+    def set_tick_fused(self, on: bool = True):
+        """vox_stream_set_tick_fused: from the next push / finish on, a tick's encoder layers run on the four-row operator -- five launches per layer instead of seven,
+        one pass over every weight matrix instead of four.  Burst passes of two or more ticks are unchanged.  Refused (VoxError) if the operator does not serve an encoder
+        matrix of the model.  Survives reset(); ids are the plain session's up to near-ties, and a function of the samples and the gain alone."""
+        check(lib().vox_stream_set_tick_fused(self.h, 1 if on else 0))
+
+    def tick_fused(self) -> bool:
+        return bool(lib().vox_stream_tick_fused(self.h))
+
     def scores(self, first: int = 0, n=None) -> np.ndarray:
         """vox_stream_scores: the records of ids [first, first + n) of the current utterance (n None: up to the last id handed out) as a structured array (logprob,
         margin, runner_up, id); an id handed out while scores were off has NaN, NaN, -1 and its id.  Reads host memory only."""
@@ -1520,15 +1551,17 @@ class Q4VoxtralModel:
         check(lib().vox_transcribe_audio_scored(self.h, ptr, n_samples, _ptr(t), _ptr(ids), cap, C.byref(n), _ptr(sc), None if al is None else _ptr(al), k, kind))
         return ids[:n.value].copy(), sc[:n.value].copy(), None if al is None else al[:n.value].copy()
 
-    def create_stream(self, t_embed, gain=1.0, enc_capacity_rows=0, max_positions=0, sample_rate=16000, endless=False, dec_ring_rows=0, burst=None, attn_split=False) -> LiveStream:
+    def create_stream(self, t_embed, gain=1.0, enc_capacity_rows=0, max_positions=0, sample_rate=16000, endless=False, dec_ring_rows=0, burst=None, attn_split=False, tick_fused=False) -> LiveStream:
         """A live session on this model (vox_stream_create / vox_stream_create_rate): push(x) -> ids, finish(), reset(), info(), close().  gain multiplies every sample
         (a stream has no file peak: 0.95 / max|x| of a known file reproduces transcribe_audio).  sample_rate: the rate of the samples that will be pushed.
         endless (vox_stream_create_endless): no 16 384-position limit -- the decoder cache is a ring of dec_ring_rows rows (0: the default, a little more than one window).
         burst (vox_stream_create_burst): 1..16 -- a backlog's ticks run in bursts of up to that many; None: a plain stream.
-        attn_split: LiveStream.set_attn_split(True) on the new session."""
+        attn_split: LiveStream.set_attn_split(True) on the new session.  tick_fused: LiveStream.set_tick_fused(True) on it."""
         st = LiveStream(self, t_embed, gain, enc_capacity_rows, max_positions, sample_rate, endless, dec_ring_rows, burst)
         if attn_split:
             st.set_attn_split(True)
+        if tick_fused:
+            st.set_tick_fused(True)
         return st
 
     def create_stream_group(self, t_embed, n_members, gains=None, enc_capacity_rows=0, max_positions=0, sample_rates=None, page_rows=None, pool_pages=None,
