@@ -78,7 +78,7 @@ struct EngCtl {
     float rstd0, rstd1, pad1, pad2;
     float best_val[16]; int best_idx[16];
     float h_own[16], h1_own[16];
-    unsigned ag_done, pad_q[3];                   // consumer waves through with their all-gather sweep (12 per stage)
+    unsigned ag_done, att_flag, pad_q[2];         // ag_done: consumer waves through with their all-gather sweep (12 per stage); att_flag: layer + 1 whose attention output is staged as digit planes
     float rope_c[24], rope_s[24];                 // RoPE factors of the CU's 24 q|k|v rows (the same in every layer; wave 0 reads them back per layer instead of holding two VGPRs all step)
 };
 constexpr int L_RING = 0;
@@ -240,17 +240,19 @@ __device__ __forceinline__ void eng_comm(const EngParams& p, EngCtl* c, unsigned
             {   // wo: 32 partial planes of this CU's 12 rows -> residual stream after attention, published as the w1|w3 input (gw = ffn_norm * Ada * 512)
                 wait_ge(&c->pub_cnt, NCONS * (4u * (unsigned)l + 2u), c, p.err, ERR_STAGE);
                 lds_st(&c->gathering, 1u);
-                float v[6];
-                sweep<6>(p.PW, NPW * ED * 8u, tag, [&](int u) { const int i = lane + 64 * u, hh = i / OWN, r = i - hh * OWN; return hh * ED + OWN * b + r; }, [&]() { return (lane & 31) * ED + OWN * b; }, PROBE_SMALL, v, c, p.err);
-#pragma unroll
-                for (int u = 0; u < 6; u++) tmp[lane + 64 * u] = v[u];
+                // lane 12 k + r (k < 4) takes row r of planes k, 4 + k, .. 28 + k and sums its eight in registers; one LDS exchange then adds the four lane groups:
+                // 8 + 3 additions in a fixed order ((planes 0, 4, .. 28) + (1, 5, ..)) + ((2, 6, ..) + (3, 7, ..)) instead of 384 stores and a 32-step chain of LDS reads
+                // on a wave that issues one instruction per 8 cycles.  Lanes 48..63 repeat lane group 3 (same addresses; their sums are not read)
+                float v[8];
+                sweep<8>(p.PW, NPW * ED * 8u, tag, [&](int u) { const int ln = min(lane, 4 * OWN - 1), k = ln / OWN, r = ln - k * OWN; return (4 * u + k) * ED + OWN * b + r; }, [&]() { return (lane & 31) * ED + OWN * b; }, PROBE_SMALL, v, c, p.err);
                 lds_st(&c->gathering, 0u);
+                float a = v[0];
+#pragma unroll
+                for (int u = 1; u < 8; u++) a += v[u];      // fixed order
+                tmp[lane] = a;
                 ENG_CFENCE();
-                float a = 0.f;
                 const int r = min(lane, OWN - 1);
-#pragma unroll 4
-                for (int hh = 0; hh < NPW; hh++) a += tmp[hh * OWN + r];      // fixed order
-                wait_ge(&c->gw_flag, (unsigned)NCONS, c, p.err, ERR_STAGE);
+                a = (tmp[r] + tmp[OWN + r]) + (tmp[2 * OWN + r] + tmp[3 * OWN + r]);
                 if (!((p.flags & 16384) && blockIdx.x == 7 && l == 1))      // (flag 16384 = FAULT INJECTION for the test of the bounded waits: workgroup 7 loses a publish)
                     comm_publish_rows(p, lane, c->h_own[r] + a, gwt[(l * 2 + 1) * 16 + r], p.H1, p.SS1, tag, c->h1_own);
             }
@@ -759,21 +761,33 @@ __device__ __forceinline__ void eng_consumer(const EngParams& p, EngCtl* c, unsi
                 if (lane == 0) pl[cw] = lsum;
             }
             if (T) tl(23);
-            cs.cbarrier();
-            if (T) tl(25);
-            if (lane < 32) {      // head h's attention output: lane = 4 consecutive columns, summed over the 12 key groups (fixed order) -> digit planes (4 blocks).
-                // EVERY wave does this for itself, into its own (dead since the q|k|v steps) region of the plane buffer: no barrier before wo
-                const float4* po4 = reinterpret_cast<const float4*>(po);
-                float4 so = make_float4(0.f, 0.f, 0.f, 0.f); float sl = 0.f;
+            // head h's attention output -> digit planes, ONCE per CU: the wave that arrives LAST at this barrier knows that all twelve partials are in LDS, so it sums
+            // them (key groups 0..11: the order does not depend on which wave does it), converts the 128 values (lane = 4 consecutive columns, 4 blocks) into blocks 0..3
+            // of the plane buffer (wave 0's region, dead since the q|k|v steps; the next all-gather cannot write it before every wave has published wo) and raises
+            // att_flag.  The conversion is a latency chain (0.7-0.8 us on one wave or on twelve); done once, behind the flag, the twelve waves start wo TOGETHER:
+            // the last wave publishes wo 0.3 us earlier than when each wave converted for itself (profiles/r10_engine_chain.md).  (wo's step records stay in the ring:
+            // reading them before this barrier only moved their cost, and in front of the q|k|v edge they spill.)
+            cs.cbar_n += NCONS;
+            ENG_CFENCE();
+            unsigned arrived = 0;
+            if (lane == 0) arrived = __hip_atomic_fetch_add(&c->cbar, 1u, RLX, WG);
+            arrived = (unsigned)__builtin_amdgcn_readfirstlane((int)arrived);
+            if (arrived + 1u == cs.cbar_n) {
+                if (lane < 32) {
+                    const float4* po4 = reinterpret_cast<const float4*>(po);
+                    float4 so = make_float4(0.f, 0.f, 0.f, 0.f); float sl = 0.f;
 #pragma unroll
-                for (int q = 0; q < 12; q++) { const float4 a = po4[q * 32 + lane]; so.x += a.x; so.y += a.y; so.z += a.z; so.w += a.w; sl += pl[q]; }
-                const float inv = 1.0f / sl;
-                const float v[4] = {so.x * inv, so.y * inv, so.z * inv, so.w * inv};
-                to_digits(v, lane, xs + (8 * cw + (lane >> 3)) * 128, binfo + 8 * cw + (lane >> 3));
+                    for (int q = 0; q < 12; q++) { const float4 a = po4[q * 32 + lane]; so.x += a.x; so.y += a.y; so.z += a.z; so.w += a.w; sl += pl[q]; }
+                    const float inv = 1.0f / sl;
+                    const float v[4] = {so.x * inv, so.y * inv, so.z * inv, so.w * inv};
+                    to_digits(v, lane, xs + (lane >> 3) * 128, binfo + (lane >> 3));
+                }
+                ENG_CFENCE(); lds_st(&c->att_flag, (unsigned)l + 1u);
             }
-            if (T) tl(3);
+            wait_ge(&c->att_flag, (unsigned)l + 1u, c, p.err, ERR_CBAR);
+            if (T) { tl(25); tl(3); }
             {   // ---------------- wo: rows [384 s, +384) x head h's 128 columns: this wave's tiles 2 cw, 2 cw + 1, two K-steps each ----------------
-                const PairCtx cx = load_ctx2(xs, binfo, 8 * cw, 8 * cw + 2, lane);      // pairing: each tile's two K-steps
+                const PairCtx cx = load_ctx2(xs, binfo, 0, 2, lane);      // the CU's one copy of the attention output; pairing: each tile's two K-steps
 #pragma unroll
                 for (int i = 0; i < WO_PK; i++) {
                     int sl_; const unsigned char* bb = cs.slot_wait(cs.P + i, 2 * REC, sl_);
