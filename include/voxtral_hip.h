@@ -133,7 +133,7 @@ int32_t vox_gguf_close(vox_gguf* g);
 int32_t vox_gguf_version(const vox_gguf* g, uint32_t* out);
 int32_t vox_gguf_tensor_count(const vox_gguf* g, uint64_t* out);
 int32_t vox_gguf_tensor_name(const vox_gguf* g, uint64_t index, const char** out); /* tensor_names */
-/* tensor_info: dims in file order (GGUF = reversed PyTorch order), dtype 0 F32 / 1 F16 / 2 Q4_0 */
+/* tensor_info: dims in file order (GGUF = reversed PyTorch order), dtype 0 F32 / 1 F16 / 2 Q4_0 / 8 Q8_0 (34 bytes per 32 elements) */
 int32_t vox_gguf_tensor_info(const vox_gguf* g, const char* name, uint64_t dims[4], uint32_t* ndims,
                              uint32_t* dtype, uint64_t* nbytes);
 int32_t vox_gguf_tensor_data(const vox_gguf* g, const char* name, void* dst, size_t cap); /* tensor_data */
@@ -141,6 +141,12 @@ int32_t vox_gguf_tensor_data(const vox_gguf* g, const char* name, void* dst, siz
 /* ---- Q4 operator boundary (src/gguf/tensor.rs, op.rs, linear.rs) ------------------------ */
 /* Q4Tensor::from_q4_bytes, gguf/tensor.rs:35-71: validates N*K % 32 == 0 and nbytes == blocks*18 */
 int32_t vox_q4_tensor_from_bytes(vox_ctx* ctx, const uint8_t* raw, size_t nbytes, int64_t N, int64_t K, vox_q4** out);
+/* A Q8_0 tensor (GGML type 8; weight format 4, WFMT_Q8_0): raw = [N][K / 32] blocks of {f16 d; int8 q[32]}, 34 bytes each.  K % 32 == 0, N % 16 == 0 and
+ * nbytes == N * K / 32 * 34, else VOX_ERR_INVALID with nothing allocated.  The handle is a vox_q4: _shape / _num_blocks / _dequantize (exactly f32(d) * q) / _free apply,
+ * vox_q4_matmul / vox_q4_linear_forward / vox_linear_forward_ex (bias, GELU, SwiGLU) multiply by it -- up to 4 rows with K <= 8192 on the int8 matrix core (exact
+ * block sums; a row's bits do not depend on the row count), else on the bf16 hi + lo MFMA GEMM.  No model path takes Q8_0: vox_q4_model_load* refuse a file that
+ * holds such a tensor (VOX_ERR_INVALID, naming it). */
+int32_t vox_q8_tensor_from_bytes(vox_ctx* ctx, const uint8_t* raw, size_t nbytes, int64_t N, int64_t K, vox_q4** out);
 int32_t vox_q4_tensor_shape(const vox_q4* q, int64_t* N, int64_t* K);            /* tensor.rs:74-76 */
 int32_t vox_q4_tensor_num_blocks(const vox_q4* q, int64_t* out);                 /* tensor.rs:79-81 */
 int32_t vox_q4_tensor_dequantize(vox_ctx* ctx, const vox_q4* q, float* out_NxK); /* tensor.rs:88-113 (host out) */

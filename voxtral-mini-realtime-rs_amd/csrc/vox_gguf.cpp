@@ -60,8 +60,9 @@ static int32_t gguf_parse(vox_gguf* g, vox_gguf** out) {
         t.dtype = c.rd<uint32_t>(); t.offset = c.rd<uint64_t>();
         if (c.bad) { vox_gguf_close(g); return fail(VOX_ERR_IO, "Failed to read tensor %llu", (unsigned long long)i); }
         if (ovf || ne > (1ull << 60)) { std::string n = t.name; vox_gguf_close(g); return fail(VOX_ERR_IO, "tensor '%s' has an element count that overflows", n.c_str()); }
-        if (t.dtype > 2) { uint32_t d = t.dtype; vox_gguf_close(g); return fail(VOX_ERR_IO, "Unsupported GGML dtype code: %u", d); }
-        t.nbytes = t.dtype == 0 ? ne * 4 : t.dtype == 1 ? ne * 2 : (ne / 32) * 18;     // reader.rs:37-48
+        if (t.dtype > 2 && t.dtype != 8) { uint32_t d = t.dtype; vox_gguf_close(g); return fail(VOX_ERR_IO, "Unsupported GGML dtype code: %u", d); }
+        if (t.dtype == 8 && ne % 32 != 0) { std::string n = t.name; vox_gguf_close(g); return fail(VOX_ERR_IO, "Q8_0 tensor '%s' has an element count that is no multiple of 32", n.c_str()); }
+        t.nbytes = t.dtype == 0 ? ne * 4 : t.dtype == 1 ? ne * 2 : t.dtype == 8 ? (ne / 32) * 34 : (ne / 32) * 18;     // reader.rs:37-48; 8 = Q8_0: {f16 d; int8 q[32]}
         g->index[t.name] = i;
     }
     g->data_off = (c.pos + 31) / 32 * 32;                                                // reader.rs:177-179

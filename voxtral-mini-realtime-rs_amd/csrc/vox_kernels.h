@@ -27,7 +27,8 @@ struct Q4W {
     // skinny (M <= 16) and the large-M MFMA kernels, whose B fragments then are single coalesced dwordx4 loads
     const uint4* qt = nullptr; const uint16_t* st = nullptr;
 };
-enum WFmt { WFMT_Q4_0 = 0, WFMT_BF16 = 1, WFMT_BF16X2 = 2, WFMT_F32 = 3 };
+enum WFmt { WFMT_Q4_0 = 0, WFMT_BF16 = 1, WFMT_BF16X2 = 2, WFMT_F32 = 3, WFMT_Q8_0 = 4 };
+// WFMT_Q8_0 (a stand-alone tensor handle only, vox_q8.hip): qs = the int8 plane [N][K], the 32 bytes of a block in to_digits' element order; sc = f16 scales [N][nb]
 // WFMT_F32: a dense F32 / F16 checkpoint tensor whose values are NOT bf16-representable (models/weights.rs:16-66 accepts any): qt = the exact f32
 // plane [N][K] (decode GEMV, embedding lookup), qs / sc = bf16 hi / lo planes (w ~= hi + lo to 2^-17; the MFMA GEMMs for > 4 rows).   // BF16X2: f32 weights as two dense bf16 planes, qs = hi [N][K], sc = lo [N][K] (conv stem)
 
@@ -92,6 +93,19 @@ struct Rows4Params {
 bool q4_rows4_serves(const Q4W& w, int M, int pro, int epi);
 hipError_t launch_q4_rows4(const Rows4Params& p, int pro, int epi, hipStream_t s);      // hipErrorInvalidValue, nothing launched: anything it does not serve
 unsigned long long q4_rows4_launches();      // host-side launch count (vox_debug_rows4_launches); a counter of its own, no GemmForm slot
+
+// ---- linear operator on Q8_0 weights (vox_q8.hip; the tensor handle's operators): out[m][n] = epi( x[m] . W[n] + bias[n] ), epi EPI_STORE / EPI_GELU / EPI_SWIGLU
+// (interleaved gate / up rows, out [M][N / 2]).  M <= 4 and K <= 8192: the four-row design on the int8 matrix core (exact block sums, a row's bits independent of M);
+// else the bf16 hi + lo MFMA GEMM.  K % 32 == 0, N % 16 == 0; x rows are read as float4 (16-byte aligned, x_stride % 4 == 0).
+struct Q8LinearParams {
+    Q4W w;
+    const float* x; int x_stride; int M;
+    float* out; int out_stride;
+    const float* bias;                    // [N] or null
+};
+hipError_t launch_q8_linear(const Q8LinearParams& p, int epi, hipStream_t s);      // hipErrorInvalidValue, nothing launched: anything it does not serve
+hipError_t launch_q8_repack(const uint8_t* raw, Q4W w, hipStream_t s);             // raw 34-byte blocks [N][nb] (device) -> w's planes
+hipError_t launch_q8_dequant(Q4W w, float* out, hipStream_t s);                    // out[n][k] = f32(d) * q, one f32 product
 
 // ---- Q4 GEMM on MFMA (prefill / encoder, rows of x > 4): out[M][N'] = epi( x[M][K] * W^T )
 struct GemmParams {

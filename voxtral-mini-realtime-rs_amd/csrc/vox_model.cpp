@@ -461,12 +461,17 @@ static int32_t model_build(vox_ctx* ctx, const TensorSource* src_in, bool q4, bo
     *out = m; return VOX_OK;
 }
 
+// A file that holds a Q8_0 tensor (GGML type 8: the reader and the stand-alone tensor handle take it) is refused whole, before anything is built: no model path runs Q8 weights yet
+static int32_t refuse_q8_file(const vox_gguf* g) {
+    for (const GTensor& t : g->tensors) if (t.dtype == 8) return fail(VOX_ERR_INVALID, "tensor '%s' is Q8_0: Q8_0 models are not loaded yet (vox_q8_tensor_from_bytes takes single tensors)", t.name.c_str());
+    return VOX_OK;
+}
 extern "C" int32_t vox_q4_model_load(vox_ctx* ctx, const char* path, vox_model** out) { return vox_q4_model_load_ex(ctx, path, 0, out); }
 
 // Q4ModelLoader::from_bytes / from_shards + load (gguf/loader.rs:92-128): build the model from an already-open GGUF reader (file,
 // memory image or shards).  The reader is only read during the call; the caller closes it afterwards.
 extern "C" int32_t vox_q4_model_load_gguf(vox_ctx* ctx, vox_gguf* g, uint32_t flags, vox_model** out) {
-    ARGCHK(ctx && g && out, "null argument"); VOXCHK(ctx_bind(ctx));
+    ARGCHK(ctx && g && out, "null argument"); VOXCHK(refuse_q8_file(g)); VOXCHK(ctx_bind(ctx));
     GgufSource src; src.g = g;
     const int32_t r = model_build(ctx, &src, true, (flags & VOX_LOAD_LAYOUT_ONLY) != 0, out);
     src.g = nullptr;      // borrowed
@@ -474,7 +479,7 @@ extern "C" int32_t vox_q4_model_load_gguf(vox_ctx* ctx, vox_gguf* g, uint32_t fl
 }
 extern "C" int32_t vox_q4_model_load_ex(vox_ctx* ctx, const char* path, uint32_t flags, vox_model** out) {
     ARGCHK(ctx && path && out, "null argument"); VOXCHK(ctx_bind(ctx));
-    GgufSource src; VOXCHK(vox_gguf_open(path, &src.g));
+    GgufSource src; VOXCHK(vox_gguf_open(path, &src.g)); VOXCHK(refuse_q8_file(src.g));
     return model_build(ctx, &src, true, (flags & VOX_LOAD_LAYOUT_ONLY) != 0, out);
 }
 

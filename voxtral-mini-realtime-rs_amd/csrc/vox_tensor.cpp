@@ -47,6 +47,27 @@ extern "C" int32_t vox_q4_tensor_from_bytes(vox_ctx* c, const uint8_t* raw, size
     }
     *out = q; return VOX_OK;
 }
+// a Q8_0 tensor (GGML type 8): raw [N][K / 32] blocks of {f16 d; int8 q[32]} -> the int8 plane [N][K] + the f16 scales [N][K / 32] (q8_repack_kernel, vox_q8.hip).
+// The handle is a vox_q4: the shape / dequantize / free / matmul / linear entries serve it; the engines, live sessions and model loader take no Q8 tensor.
+extern "C" int32_t vox_q8_tensor_from_bytes(vox_ctx* c, const uint8_t* raw, size_t nbytes, int64_t N, int64_t K, vox_q4** out) {
+    ARGCHK(c && raw && out, "null argument"); ARGCHK(N > 0 && K > 0 && N <= INT32_MAX && K <= INT32_MAX, "bad shape");
+    ARGCHK(K % 32 == 0, "Q8_0 rows must be a whole number of 32-element blocks (K=%lld)", (long long)K);
+    ARGCHK(N % 16 == 0, "Q8_0 tensors take a whole number of 16-row tiles (N=%lld)", (long long)N);
+    const int64_t nblk = N * (K / 32);
+    ARGCHK((int64_t)nbytes == nblk * 34, "Q8_0 byte count mismatch: expected %lld for %lld blocks, got %zu", (long long)(nblk * 34), (long long)nblk, nbytes);
+    VOXCHK(ctx_bind(c));
+    vox_q4* q = new vox_q4(); q->ctx = c; q->qs_mem = q->sc_mem = nullptr;
+    DevBuf d_raw;
+    if (hipMalloc(&q->qs_mem, (size_t)nblk * 32) != hipSuccess || hipMalloc(&q->sc_mem, (size_t)nblk * 2) != hipSuccess || d_raw.alloc(nbytes) != hipSuccess) {
+        (void)hipGetLastError(); (void)hipFree(q->qs_mem); (void)hipFree(q->sc_mem); delete q; return fail(VOX_ERR_HIP, "hipMalloc failed for Q8 tensor");
+    }
+    q->w = Q4W{(const uint4*)q->qs_mem, (const uint16_t*)q->sc_mem, (int)N, (int)K, (int)(K / 32), WFMT_Q8_0};
+    hipError_t e = hipMemcpyAsync(d_raw.p, raw, nbytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = launch_q8_repack(d_raw.as<uint8_t>(), q->w, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { (void)hipGetLastError(); (void)hipFree(q->qs_mem); (void)hipFree(q->sc_mem); delete q; return fail(VOX_ERR_HIP, "Q8 tensor upload: %s", hipGetErrorString(e)); }
+    *out = q; return VOX_OK;
+}
 extern "C" int32_t vox_q4_tensor_shape(const vox_q4* q, int64_t* N, int64_t* K) { ARGCHK(q && N && K, "null argument"); *N = q->w.N; *K = q->w.K; return VOX_OK; }
 extern "C" int32_t vox_q4_tensor_num_blocks(const vox_q4* q, int64_t* out) { ARGCHK(q && out, "null argument"); *out = (int64_t)q->w.N * q->w.nb; return VOX_OK; }
 extern "C" int32_t vox_q4_tensor_free(vox_q4* q) {
@@ -58,7 +79,7 @@ extern "C" int32_t vox_q4_tensor_dequantize(vox_ctx* c, const vox_q4* q, float* 
     ARGCHK(c && q && out, "null argument"); VOXCHK(ctx_bind(c));
     const size_t ne = (size_t)q->w.N * q->w.K;
     DevBuf d; HIPCHK(d.alloc(ne * 4));
-    HIPCHK(launch_q4_dequant(q->w, d.as<float>(), c->stream));
+    HIPCHK(q->w.fmt == WFMT_Q8_0 ? launch_q8_dequant(q->w, d.as<float>(), c->stream) : launch_q4_dequant(q->w, d.as<float>(), c->stream));
     HIPCHK(hipMemcpyAsync(out, d.p, ne * 4, hipMemcpyDeviceToHost, c->stream)); HIPCHK(hipStreamSynchronize(c->stream));
     return VOX_OK;
 }
@@ -67,6 +88,12 @@ extern "C" int32_t vox_q4_tensor_dequantize(vox_ctx* c, const vox_q4* q, float* 
 namespace vox_host {
 int32_t q4_linear_dev(vox_ctx* c, const Q4W& w, const float* bias, const float* x, int x_stride, int rows, float* out, int out_stride,
                              int epi, const float* resid, int resid_stride, int ksplit) {
+    if (w.fmt == WFMT_Q8_0) {      // a Q8_0 handle: its own unit picks the kernel (vox_q8.hip); bias, GELU, SwiGLU -- no residual form
+        ARGCHK(!resid && (epi == EPI_STORE || epi == EPI_GELU || epi == EPI_SWIGLU), "Q8_0 tensors run with the epilogues none, GELU and SwiGLU (epi %d)", epi);
+        Q8LinearParams p{}; p.w = w; p.x = x; p.x_stride = x_stride; p.M = rows; p.out = out; p.out_stride = out_stride; p.bias = bias;
+        HIPCHK(launch_q8_linear(p, epi, c->stream));
+        return VOX_OK;
+    }
     if (rows <= 4) {
         GemvParams p{}; p.w = w; p.x = x; p.x_stride = x_stride; p.out = out; p.out_stride = out_stride; p.bias = bias;
         p.resid = resid; p.resid_stride = resid_stride;

@@ -12,6 +12,7 @@ from . import _lib
 from ._lib import check, lib, VoxError
 
 F32, F16, Q4_0 = 0, 1, 2
+Q8_0 = 8          # GGML type code: the reader and Q4Tensor.from_q8_bytes take it, the model loader does not
 
 
 def _f32(a):
@@ -178,6 +179,15 @@ class Q4Tensor:
         return cls(ctx, h, [n, k])
 
     @classmethod
+    def from_q8_bytes(cls, raw_bytes, shape, ctx: Context):
+        """A Q8_0 tensor [N, K] from its raw 34-byte blocks {f16 d; int8 q[32]} (vox_q8_tensor_from_bytes; K % 32 == 0, N % 16 == 0): dequantize, q4_matmul and
+        linear_forward serve the handle, no model path does."""
+        raw = np.ascontiguousarray(np.frombuffer(raw_bytes, dtype=np.uint8) if not isinstance(raw_bytes, np.ndarray) else raw_bytes, dtype=np.uint8)
+        n, k = shape; h = C.c_void_p()
+        check(lib().vox_q8_tensor_from_bytes(ctx.h, _ptr(raw), raw.size, n, k, C.byref(h)))
+        return cls(ctx, h, [n, k])
+
+    @classmethod
     def from_f32(cls, w, ctx: Context, other=None):
         """Dense f32-path weight [N, K] (models/weights.rs:16-66) in the f32 model's device format; `other`: a second [N, K] tensor interleaved row by row
         (the fused gate | up operand of SwiGLU, models/layers/swiglu.rs:72-77)."""
@@ -206,6 +216,23 @@ class Q4Tensor:
             self.close()
         except Exception:
             pass
+
+
+def q8_tensor_from_bytes(raw_bytes, shape, ctx: Context):
+    return Q4Tensor.from_q8_bytes(raw_bytes, shape, ctx)
+
+
+def quantize_q8_0(w):
+    """ggml's Q8_0 rule per 32-element block: d = f16(amax / 127), q = rint(x / d) (0 where d == 0) -> raw 34-byte blocks {f16 d; int8 q[32]} (uint8, flat)."""
+    x = _f32(w).reshape(-1, 32)
+    d = (np.abs(x).max(axis=1) / np.float32(127.0)).astype(np.float16)
+    df = d.astype(np.float32)[:, None]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        q = np.where(df != 0, np.rint(x / df), 0.0)
+    out = np.empty((x.shape[0], 34), dtype=np.uint8)
+    out[:, :2] = d.view(np.uint8).reshape(-1, 2)
+    out[:, 2:] = np.clip(q, -128, 127).astype(np.int8).view(np.uint8)
+    return out.reshape(-1)
 
 
 def q4_matmul(x, weights: Q4Tensor):

@@ -25,6 +25,7 @@ TOK = EMB + ".tok_embeddings.weight"
 ADP = EMB + ".audio_language_projection"
 
 GGML_F32, GGML_F16, GGML_Q4_0 = 0, 1, 2
+GGML_Q8_0 = 8          # 34 bytes per 32 elements: {f16 d; int8 q[32]}
 
 
 @dataclass
@@ -161,7 +162,7 @@ def write_gguf(path: str, tensors, version: int = 3):
     sizes = []
     for name, shape, dt, _ in tensors:
         ne = int(np.prod(shape))
-        sizes.append(ne * 4 if dt == GGML_F32 else ne * 2 if dt == GGML_F16 else ne // 32 * 18)
+        sizes.append(ne * 4 if dt == GGML_F32 else ne * 2 if dt == GGML_F16 else ne // 32 * 34 if dt == GGML_Q8_0 else ne // 32 * 18)
     head = bytearray()
     head += struct.pack("<IIQQ", 0x46554747, version, len(tensors), 1)
     head += _gguf_str("general.architecture") + struct.pack("<I", 8) + _gguf_str("voxtral")
@@ -284,7 +285,7 @@ def read_gguf_tensors(path: str):
     data0 = (pos + 31) // 32 * 32
     out = {}
     for name, shape, dt, off in infos:
-        ne = int(np.prod(shape)); nb = ne * 4 if dt == 0 else ne * 2 if dt == 1 else ne // 32 * 18
+        ne = int(np.prod(shape)); nb = ne * 4 if dt == 0 else ne * 2 if dt == 1 else ne // 32 * 34 if dt == GGML_Q8_0 else ne // 32 * 18
         out[name] = (shape, dt, buf[data0 + off:data0 + off + nb])
     return out
 
