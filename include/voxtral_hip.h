@@ -144,9 +144,22 @@ int32_t vox_q4_tensor_from_bytes(vox_ctx* ctx, const uint8_t* raw, size_t nbytes
 /* A Q8_0 tensor (GGML type 8; weight format 4, WFMT_Q8_0): raw = [N][K / 32] blocks of {f16 d; int8 q[32]}, 34 bytes each.  K % 32 == 0, N % 16 == 0 and
  * nbytes == N * K / 32 * 34, else VOX_ERR_INVALID with nothing allocated.  The handle is a vox_q4: _shape / _num_blocks / _dequantize (exactly f32(d) * q) / _free apply,
  * vox_q4_matmul / vox_q4_linear_forward / vox_linear_forward_ex (bias, GELU, SwiGLU) multiply by it -- up to 4 rows with K <= 8192 on the int8 matrix core (exact
- * block sums; a row's bits do not depend on the row count), else on the bf16 hi + lo MFMA GEMM.  No model path takes Q8_0: vox_q4_model_load* refuse a file that
- * holds such a tensor (VOX_ERR_INVALID, naming it). */
+ * block sums; a row's bits do not depend on the row count); up to 4 rows with K > 8192 on the same arithmetic split over K slices of 3072 columns (two launches,
+ * the slices added in ascending order; csrc/vox_q8_slices.hip); 5 rows and more on the bf16 hi + lo MFMA GEMM.  No model path takes Q8_0: vox_q4_model_load* refuse
+ * a file that holds such a tensor (VOX_ERR_INVALID, naming it). */
 int32_t vox_q8_tensor_from_bytes(vox_ctx* ctx, const uint8_t* raw, size_t nbytes, int64_t N, int64_t K, vox_q4** out);
+/* The K-slice operator on its own, at ANY K it serves (also K <= 8192, where the entries above run the one-workgroup rows kernel):
+ *   out[m][n] = epi( pro(x[m]) . W[n] + bias[n] ),  x [M][K], M in 1..4, w a Q8_0 tensor with K <= 65536.
+ * pro: 0 none, 1 RMSNorm (x / sqrt(mean(x^2) + eps) * gamma[K]; gamma required, eps > 0: an all-zero row then gives zeros, not 0 * inf).  epi: 0 store (out [M][N]),
+ * 1 residual (out = resid + ., resid [M][N] required; with device buffers resid may be out), 2 SwiGLU over interleaved gate / up rows (out [M][N / 2]: silu(row 2 i) *
+ * row 2 i + 1), 3 GELU.  bias [N]: optional with every epilogue; gamma and resid must be null where they are not read.  mem_kind: every buffer on the host or every
+ * buffer on the device (x rows and gamma 16-byte aligned).  A row's bits depend on that row, the tensor and K alone.  Every argument is checked before the context is
+ * bound; what the operator does not serve -- a tensor that is not Q8_0, M outside 1..4, K > 65536 -- is VOX_ERR_INVALID naming the shape, with nothing launched.
+ * The K-slice planes live in the context's scratch (grown once if a tensor needs more).  vox_q8_rows_launches: calls of the operator by this process so far, through
+ * this entry or through the linear entries above (one per call: its two launches count once). */
+int32_t vox_q8_rows_forward(vox_ctx* ctx, const vox_q4* w, const float* bias, const float* gamma, float eps, const float* x, int32_t M, float* out, int32_t pro, int32_t epi,
+                            const float* resid, int32_t mem_kind);
+int32_t vox_q8_rows_launches(uint64_t* out);
 int32_t vox_q4_tensor_shape(const vox_q4* q, int64_t* N, int64_t* K);            /* tensor.rs:74-76 */
 int32_t vox_q4_tensor_num_blocks(const vox_q4* q, int64_t* out);                 /* tensor.rs:79-81 */
 int32_t vox_q4_tensor_dequantize(vox_ctx* ctx, const vox_q4* q, float* out_NxK); /* tensor.rs:88-113 (host out) */

@@ -14,5 +14,5 @@ from . import wer  # noqa: F401  (WER / CER harness, scripts/eval_wer.py)
 from . import export  # noqa: F401  (SafeTensors -> Q4_0 GGUF)
 from . import shard  # noqa: F401  (multi-GPU: LPT sharding of independent utterances; torch imported lazily)
 from .models import VoxtralModel, VoxtralModelLoader  # noqa: F401
-from .gguf import (Context, device_count, GgufReader, Q4Tensor, Q4Linear, q4_matmul, q8_tensor_from_bytes, quantize_q8_0, Q4ModelLoader, Q4VoxtralModel, tensor_add_dev, argmax_rows_dev, linear_forward, rows4_forward, rows4_launches, conv_downsample,
+from .gguf import (Context, device_count, GgufReader, Q4Tensor, Q4Linear, q4_matmul, q8_tensor_from_bytes, quantize_q8_0, q8_rows_forward, q8_rows_launches, Q4ModelLoader, Q4VoxtralModel, tensor_add_dev, argmax_rows_dev, linear_forward, rows4_forward, rows4_launches, conv_downsample,
                    LiveStream, LiveStreamGroup, stream_schedule, stream_schedule_rate, stream_peek_ids, stream_group_pages_for, score_rows, stream_id_due, words, SCORE_DTYPE, alternatives_rows, ALTS_DTYPE, records_rows, snapshot_info, snapshot_bytes_for, stream_burst_len, stream_group_burst_rounds, level_window, level_db, quiet_ticks, LEVEL_DTYPE)  # noqa: F401

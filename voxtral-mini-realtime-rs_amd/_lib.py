@@ -113,6 +113,7 @@ SIGNATURES = {
     "vox_gguf_tensor_data": (i32, [vp, C.c_char_p, vp, sz]),
     "vox_q4_tensor_from_bytes": (i32, [vp, vp, sz, i64, i64, P(vp)]),
     "vox_q8_tensor_from_bytes": (i32, [vp, vp, sz, i64, i64, P(vp)]),
+    "vox_q8_rows_forward": (i32, [vp, vp, vp, vp, C.c_float, vp, i32, vp, i32, i32, vp, i32]), "vox_q8_rows_launches": (i32, [P(C.c_uint64)]),
     "vox_q4_tensor_shape": (i32, [vp, P(i64), P(i64)]),
     "vox_q4_tensor_num_blocks": (i32, [vp, P(i64)]),
     "vox_q4_tensor_dequantize": (i32, [vp, vp, vp]),

@@ -35,6 +35,17 @@ struct vox_ctx {
         if (xf) get(reinterpret_cast<void**>(&xf_scratch), &xf_scratch_bytes, XF_SCRATCH_BYTES);
         if (kz) get(reinterpret_cast<void**>(&kz_scratch), &kz_scratch_bytes, KZ_SCRATCH_BYTES);
     }
+    // K-slice planes larger than the buffer's first size (the Q8 slice operator on a very wide matrix): the buffer is replaced by a larger one behind a device
+    // synchronisation -- once per size, never per call.  false: no such memory
+    bool want_kz_bytes(size_t need) {
+        want_scratch(false, true);
+        if (kz_scratch && kz_scratch_bytes >= need) return true;
+        (void)hipDeviceSynchronize();
+        if (kz_scratch) (void)hipFree(kz_scratch);
+        kz_scratch = nullptr; kz_scratch_bytes = 0;
+        if (hipMalloc(reinterpret_cast<void**>(&kz_scratch), need) != hipSuccess) { (void)hipGetLastError(); kz_scratch = nullptr; return false; }
+        kz_scratch_bytes = need; return true;
+    }
     float* rs_matrix = nullptr; uint32_t rs_in = 0, rs_out = 0;    // block matrix of the last resampled rate pair (vox_resample)
     struct vox_model* pw_model = nullptr;      // the model with decode-engine steps of the piecewise surface enqueued on `stream` and not yet verified (see pw_after_sync)
 };

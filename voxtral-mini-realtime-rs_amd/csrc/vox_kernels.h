@@ -96,14 +96,34 @@ unsigned long long q4_rows4_launches();      // host-side launch count (vox_debu
 
 // ---- linear operator on Q8_0 weights (vox_q8.hip; the tensor handle's operators): out[m][n] = epi( x[m] . W[n] + bias[n] ), epi EPI_STORE / EPI_GELU / EPI_SWIGLU
 // (interleaved gate / up rows, out [M][N / 2]).  M <= 4 and K <= 8192: the four-row design on the int8 matrix core (exact block sums, a row's bits independent of M);
-// else the bf16 hi + lo MFMA GEMM.  K % 32 == 0, N % 16 == 0; x rows are read as float4 (16-byte aligned, x_stride % 4 == 0).
+// M <= 4 and K > 8192: the K-slice operator below, on `planes` (q8_slices_planes_bytes; without them the call is refused); else the bf16 hi + lo MFMA GEMM.
+// K % 32 == 0, N % 16 == 0; x rows are read as float4 (16-byte aligned, x_stride % 4 == 0).
 struct Q8LinearParams {
     Q4W w;
     const float* x; int x_stride; int M;
     float* out; int out_stride;
     const float* bias;                    // [N] or null
 };
-hipError_t launch_q8_linear(const Q8LinearParams& p, int epi, hipStream_t s);      // hipErrorInvalidValue, nothing launched: anything it does not serve
+hipError_t launch_q8_linear(const Q8LinearParams& p, int epi, hipStream_t s, float* planes = nullptr, size_t planes_bytes = 0);      // hipErrorInvalidValue, nothing launched: anything it does not serve
+
+// ---- M <= 4 rows of Q8_0 at any K, split over K slices (vox_q8_slices.hip): out[m][n] = epi( pro(x[m]) . W[n] + bias[n] ) in two launches -- q8_slice_kernel writes
+// each K slice's product as a plane [slice][4][N] (and, with PRO_RMS, the slice's sums of squares), q8_slice_finish_kernel adds the planes slice-ascending and applies
+// rstd, bias and the epilogue.  pro: PRO_NONE / PRO_RMS; epi: EPI_STORE / EPI_RESID (out = resid + .; resid may be out) / EPI_SWIGLU (interleaved gate / up rows, out
+// [M][N / 2]) / EPI_GELU; bias optional with every epilogue.  A row's bits depend on that row, the matrix and K alone.
+struct Q8SliceParams {
+    Q4W w;
+    const float* x; int x_stride; int M;
+    float* out; int out_stride;
+    const float* bias;                    // [N] or null
+    const float* resid; int resid_stride; // EPI_RESID
+    const float* gamma; float eps;        // PRO_RMS
+};
+// what the launcher serves: WFMT_Q8_0, M in 1..4, K % 32 == 0, K <= 65536, N % 16 == 0, the pro / epi above
+bool q8_slices_serves(const Q4W& w, int M, int pro, int epi);
+size_t q8_slices_planes_bytes(const Q4W& w);      // room the two launches need between them: the planes and the partial sums of squares
+// x rows and gamma 16-byte aligned, strides % 4 == 0.  hipErrorInvalidValue, nothing launched: anything it does not serve, or planes too small
+hipError_t launch_q8_slices(const Q8SliceParams& p, int pro, int epi, float* planes, size_t planes_bytes, hipStream_t s);
+unsigned long long q8_slices_launches();      // host-side count, one per operator call (vox_q8_rows_launches)
 hipError_t launch_q8_repack(const uint8_t* raw, Q4W w, hipStream_t s);             // raw 34-byte blocks [N][nb] (device) -> w's planes
 hipError_t launch_q8_dequant(Q4W w, float* out, hipStream_t s);                    // out[n][k] = f32(d) * q, one f32 product
 

@@ -14,7 +14,9 @@
 // one fixed order by wave 0, which runs the epilogue.  The grid is min(N / 16, 512) workgroups walking the 16-row output tiles; the next step's (or the next tile's
 // first) loads are issued before the current step is consumed.  A row's bits depend on that row, the matrix and K alone: not on M, the grid or the run.
 //
-// (b) q8_gemm_kernel, M >= 5, and any M when K > 8192 (prefill, bursts, groups): v_mfma_f32_16x16x32_bf16, one MFMA K-step == one Q8_0 block.  A 4-wave workgroup
+// (M <= 4 with K > 8192 goes to the K-slice operator of vox_q8_slices.hip: launch_q8_linear hands it the caller's planes.)
+//
+// (b) q8_gemm_kernel, M >= 5 (prefill, bursts, groups): v_mfma_f32_16x16x32_bf16, one MFMA K-step == one Q8_0 block.  A 4-wave workgroup
 // owns 64 output columns (wave w: n-tile w) for up to 64 rows (1..4 m-tiles: a workgroup runs only the m-tiles that hold rows); M > 64 tiles over grid.y, the weights
 // of a tile re-read from L2.  The activation rows are the A operand, split into bf16 hi + lo ONCE per workgroup and held in LDS in fragment order, K in double-buffered
 // chunks of 64 columns (one barrier per chunk; the next chunk's rows and weights are requested before the current chunk runs).  The weights are the B operand: lane
@@ -29,12 +31,12 @@ namespace {
 
 #include "vox_engine_common.h"
 #include "vox_digits.h"
+#include "vox_q8_common.h"      // WB8, f16_bits_f32, q8_digits_finish: shared with vox_q8_slices.hip
 
 typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 bf16x8;
 typedef __attribute__((__vector_size__(4 * sizeof(float)))) float f32x4;
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ float f16_bits_f32(unsigned short h) { return __half2float(__ushort_as_half(h)); }
 __device__ __forceinline__ float gelu_q8(float x) { return x * 0.5f * (1.0f + erff(x / 1.41421356237309504880f)); }      // gelu_f's form (vox_kernels.hip)
 __device__ __forceinline__ float sbyte_f32(unsigned w, int n) { return (float)(int)(signed char)(w >> (8 * n)); }
 
@@ -71,16 +73,6 @@ constexpr int Q8R_WAVES = 8, Q8R_THREADS = 64 * Q8R_WAVES, Q8R_MAX_GRID = 512, Q
 __host__ __device__ inline int q8r_nbp(int nb) { return (nb + 1) & ~1; }      // blocks per row in LDS: a whole number of K steps (the pad block is zeros)
 __host__ __device__ inline size_t q8r_lds_bytes(int nb) { return (size_t)4 * q8r_nbp(nb) * (128 + 8) + 2 * Q8R_WAVES * 64 * 4; }
 static_assert(4 * (Q8R_MAX_K / 32) * (128 + 8) + 2 * Q8R_WAVES * 64 * 4 <= 160 * 1024, "the largest K must fit a workgroup's LDS");
-
-struct WB8 { u32x4 q; unsigned short s0, s1; };      // one lane's share of a K step: 16 int8 values, the f16 scales of the step's two blocks of its weight row
-
-// digit sums of one block -> value: D0 + 2^7 D1 and D2 + 2^7 D3 in int32 (|D| < 2^20), their 39-bit combination in f64 (exact), ONE rounding to f32, one FMA
-// with the product of the weight block's scale and the activation block's 2^-shift
-__device__ __forceinline__ float q8_digits_finish(const i4v D, float sc, float sxinv, float acc) {
-    const int lo = (int)((unsigned)D[0] + ((unsigned)D[1] << 7)), hi = (int)((unsigned)D[2] + ((unsigned)D[3] << 7));
-    const float t = (float)fma((double)hi, 16384.0, (double)lo);
-    return fmaf(t, sc * sxinv, acc);
-}
 
 template <int EPI>
 __global__ __launch_bounds__(Q8R_THREADS, 1) void q8_rows_kernel(const Q8LinearParams p) {
@@ -302,11 +294,15 @@ hipError_t launch_q8_dequant(Q4W w, float* out, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_q8_linear(const Q8LinearParams& p, int epi, hipStream_t s) {
+hipError_t launch_q8_linear(const Q8LinearParams& p, int epi, hipStream_t s, float* planes, size_t planes_bytes) {
     const Q4W& w = p.w;
     if (w.fmt != WFMT_Q8_0 || !w.qs || !w.sc || p.M < 1 || p.M > 64 * 65535 || w.K < 32 || w.K % 32 || w.nb != w.K / 32 || w.N < 16 || w.N % 16) return hipErrorInvalidValue;
     if (!p.x || !p.out || (p.x_stride & 3) || ((uintptr_t)p.x & 15) || p.x_stride < w.K) return hipErrorInvalidValue;      // the rows are read as float4
     if (epi != EPI_STORE && epi != EPI_GELU && epi != EPI_SWIGLU) return hipErrorInvalidValue;
+    if (p.M <= 4 && w.K > Q8R_MAX_K) {      // decode rows past the rows kernel's LDS: the K-slice operator (vox_q8_slices.hip), which needs the caller's planes
+        Q8SliceParams q{}; q.w = w; q.x = p.x; q.x_stride = p.x_stride; q.M = p.M; q.out = p.out; q.out_stride = p.out_stride; q.bias = p.bias;
+        return launch_q8_slices(q, PRO_NONE, epi, planes, planes_bytes, s);
+    }
     const bool rows = p.M <= 4 && w.K <= Q8R_MAX_K;      // the digit planes of four rows in a workgroup's LDS; beyond, the GEMM
 #define VOX_Q8(E_) if (epi == E_) return rows ? q8_rows_launch_t<E_>(p, s) : q8_gemm_launch_t<E_>(p, s);
     VOX_Q8(EPI_STORE) VOX_Q8(EPI_GELU) VOX_Q8(EPI_SWIGLU)

@@ -91,7 +91,12 @@ int32_t q4_linear_dev(vox_ctx* c, const Q4W& w, const float* bias, const float* 
     if (w.fmt == WFMT_Q8_0) {      // a Q8_0 handle: its own unit picks the kernel (vox_q8.hip); bias, GELU, SwiGLU -- no residual form
         ARGCHK(!resid && (epi == EPI_STORE || epi == EPI_GELU || epi == EPI_SWIGLU), "Q8_0 tensors run with the epilogues none, GELU and SwiGLU (epi %d)", epi);
         Q8LinearParams p{}; p.w = w; p.x = x; p.x_stride = x_stride; p.M = rows; p.out = out; p.out_stride = out_stride; p.bias = bias;
-        HIPCHK(launch_q8_linear(p, epi, c->stream));
+        float* planes = nullptr; size_t planes_bytes = 0;
+        if (rows <= 4 && w.K > 8192) {      // decode rows past the rows kernel's K: the K-slice operator (vox_q8_slices.hip) on the context's K-slice scratch
+            if (!c->want_kz_bytes(q8_slices_planes_bytes(w))) return fail(VOX_ERR_HIP, "no memory for the K-slice planes of a Q8_0 [%d][%d] tensor", w.N, w.K);
+            planes = c->kz_scratch; planes_bytes = c->kz_scratch_bytes;
+        }
+        HIPCHK(launch_q8_linear(p, epi, c->stream, planes, planes_bytes));
         return VOX_OK;
     }
     if (rows <= 4) {
@@ -395,6 +400,38 @@ extern "C" int32_t vox_debug_rows4_op(vox_ctx* c, const vox_q4* w, const float* 
     return VOX_OK;
 }
 extern "C" int32_t vox_debug_rows4_launches(uint64_t* out) { ARGCHK(out, "null argument"); *out = (uint64_t)q4_rows4_launches(); return VOX_OK; }
+// ---- M <= 4 rows of a Q8_0 tensor at any served K through the K-slice operator (launch_q8_slices; include/voxtral_hip.h), host or device buffers.  Every argument
+// is checked before the context is bound; the launcher's own refusal (q8_slices_serves) is asked first, so nothing it does not serve reaches a device.
+extern "C" int32_t vox_q8_rows_forward(vox_ctx* c, const vox_q4* w, const float* bias, const float* gamma, float eps, const float* x, int32_t M, float* out, int32_t pro, int32_t epi,
+                                       const float* resid, int32_t mem_kind) {
+    ARGCHK(c && w && x && out, "null argument");
+    ARGCHK(pro == 0 || pro == 1, "pro %d: 0 none, 1 RMSNorm", pro); ARGCHK(epi >= 0 && epi <= 3, "epi %d: 0 store, 1 residual, 2 SwiGLU, 3 GELU", epi);
+    ARGCHK((pro == 1) == (gamma != nullptr), "gamma goes with pro 1 alone"); ARGCHK((epi == 1) == (resid != nullptr), "resid goes with epi 1 alone");
+    ARGCHK(pro == 0 || eps > 0.f, "eps must be a positive number (with eps 0 an all-zero row's rstd is infinite)");
+    const int K = w->w.K, N = w->w.N, kpro = pro ? PRO_RMS : PRO_NONE, kepi = epi == 1 ? EPI_RESID : epi == 2 ? EPI_SWIGLU : epi == 3 ? EPI_GELU : EPI_STORE, No = epi == 2 ? N / 2 : N;
+    ARGCHK(M >= 1 && M <= 4, "M %d out of range (1..4) for a [%d][%d] tensor", M, N, K);
+    ARGCHK(q8_slices_serves(w->w, M, kpro, kepi), "the K-slice operator serves Q8_0 tensors with K %% 32 == 0, K <= 65536 and N %% 16 == 0 (fmt %d, K %d, N %d)", w->w.fmt, K, N);
+    VOXCHK(ctx_bind(c)); hipStream_t s = c->stream;
+    if (!c->want_kz_bytes(q8_slices_planes_bytes(w->w))) return fail(VOX_ERR_HIP, "no memory for the K-slice planes of a Q8_0 [%d][%d] tensor", N, K);
+    Q8SliceParams p{}; p.w = w->w; p.x_stride = K; p.M = M; p.out_stride = No; p.resid_stride = N; p.eps = eps;
+    if (mem_kind == VOX_MEM_DEVICE) {
+        p.x = x; p.out = out; p.bias = bias; p.resid = resid; p.gamma = gamma;
+        HIPCHK(launch_q8_slices(p, kpro, kepi, c->kz_scratch, c->kz_scratch_bytes, s));
+        return VOX_OK;
+    }
+    DevBuf dx, db, dg, dr, dy;
+    auto up = [&](DevBuf& d, const void* src, size_t bytes) -> int32_t {
+        if (!src) return VOX_OK;
+        HIPCHK(d.alloc(bytes)); HIPCHK(hipMemcpyAsync(d.p, src, bytes, hipMemcpyHostToDevice, s)); return VOX_OK;
+    };
+    VOXCHK(up(dx, x, (size_t)M * K * 4)); VOXCHK(up(db, bias, (size_t)N * 4)); VOXCHK(up(dg, gamma, (size_t)K * 4)); VOXCHK(up(dr, resid, (size_t)M * N * 4));
+    HIPCHK(dy.alloc((size_t)M * No * 4));
+    p.x = dx.as<float>(); p.out = dy.as<float>(); p.bias = bias ? db.as<float>() : nullptr; p.resid = resid ? dr.as<float>() : nullptr; p.gamma = gamma ? dg.as<float>() : nullptr;
+    HIPCHK(launch_q8_slices(p, kpro, kepi, c->kz_scratch, c->kz_scratch_bytes, s));
+    HIPCHK(hipMemcpyAsync(out, dy.p, (size_t)M * No * 4, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
+    return VOX_OK;
+}
+extern "C" int32_t vox_q8_rows_launches(uint64_t* out) { ARGCHK(out, "null argument"); *out = (uint64_t)q8_slices_launches(); return VOX_OK; }
 // ConvDownsampler::forward (models/layers/conv.rs:78-83): gelu(conv1d k3 s2 p1) twice, x [C][L] -> [O][L2], on the product's im2col MFMA path (conv_stem_dev)
 extern "C" int32_t vox_conv_downsample(vox_ctx* c, const float* x, int32_t C, int32_t L, const float* w1, const float* b1, const float* w2, const float* b2, int32_t O, float* out) {
     ARGCHK(c && x && w1 && b1 && w2 && b2 && out && C > 0 && L > 0 && O > 0, "bad argument"); ARGCHK((3 * C) % 128 == 0 && (3 * O) % 128 == 0, "3 * channels must be a multiple of 128");

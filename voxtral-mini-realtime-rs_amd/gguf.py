@@ -287,6 +287,28 @@ def rows4_launches() -> int:
     v = C.c_uint64(); check(lib().vox_debug_rows4_launches(C.byref(v))); return int(v.value)
 
 
+def q8_rows_forward(weights: Q4Tensor, x, bias=None, gamma=None, eps=0.0, epi=0, resid=None):
+    """The K-slice operator on a Q8_0 tensor (vox_q8_rows_forward), at any K it serves: x [M <= 4, K] -> epi(pro(x) W^T + bias).  gamma [K]: RMSNorm in front
+    (x / sqrt(mean(x^2) + eps) * gamma; eps > 0).  epi 0 store, 1 residual (resid [M, N]), 2 SwiGLU over interleaved gate / up rows -> N / 2 columns, 3 GELU.
+    What the operator does not serve (a tensor that is not Q8_0, M > 4, K > 65536) raises VoxError."""
+    x = _f32(x)
+    if x.ndim != 2 or x.shape[1] != weights.shape()[1]:
+        raise VoxError(1, f"q8_rows_forward expects x [M, K={weights.shape()[1]}], got {list(x.shape)}")
+    m, n = x.shape[0], weights.shape()[0]
+    bb, gg, rr = (None if a is None else _f32(a) for a in (bias, gamma, resid))
+    if (bb is not None and bb.size != n) or (gg is not None and gg.size != x.shape[1]) or (rr is not None and rr.shape != (m, n)):
+        raise VoxError(1, "q8_rows_forward: bias [N], gamma [K], resid [M, N]")
+    out = np.empty((m, n // 2 if epi == 2 else n), dtype=np.float32)
+    check(lib().vox_q8_rows_forward(weights.ctx.h, weights.h, None if bb is None else _ptr(bb), None if gg is None else _ptr(gg), float(eps), _ptr(x), m, _ptr(out),
+                                    0 if gg is None else 1, int(epi), None if rr is None else _ptr(rr), 0))
+    return out
+
+
+def q8_rows_launches() -> int:
+    """Calls of the K-slice operator by this process so far, through q8_rows_forward or the linear entries (vox_q8_rows_launches)."""
+    v = C.c_uint64(); check(lib().vox_q8_rows_launches(C.byref(v))); return int(v.value)
+
+
 def conv_downsample(ctx, x, w1, b1, w2, b2):
     """ConvDownsampler::forward (models/layers/conv.rs:78-83): x [C, L] -> [O, L2] through the conv stem's im2col MFMA path."""
     x, w1, b1, w2, b2 = (_f32(a) for a in (x, w1, b1, w2, b2))
