@@ -11,8 +11,9 @@
 //     wave 0       LOADER   global_load_lds_dwordx4 ... nt: this CU's step records of q|k|v, wo, w1|w3, w2 of every layer, then the lm_head rows, as 13.5 / 20 KiB
 //                           packets into a ring of six LDS slots; 1-3 packets in flight; waits only for free slots.  The wave is ISSUE-bound (a lone wave issues about
 //                           one instruction per 8 cycles): four 1 KiB lines per M0 write, the packet's line loop is straight-line code.
-//     wave 1       COMM     sweeps granules written by other CUs into LDS (q|k|v of the head, the XCD group's SwiGLU outputs, partial planes of the CU's 12 residual
-//                           rows), reduces partial sums in a FIXED order (deterministic), publishes the CU's 12 rows (already multiplied by the next norm weight).
+//     wave 1       COMM     sweeps granules written by other CUs into LDS (q|k|v of the head, partial planes of the CU's 12 residual rows), reduces partial sums in a
+//                           FIXED order (deterministic), publishes the CU's 12 rows (already multiplied by the next norm weight).  (The XCD group's SwiGLU outputs are
+//                           polled by the consumer waves themselves, each its own K slice.)
 //     waves 2..13  CONSUMERS  layer operators as EXACT integer dot products on v_mfma_i32_16x16x64_i8: B = Q4 nibbles as int8, A = the activation in per-block fixed
 //                           point split into four digits (rows 4 p + c = digit c of block p), K split over the 12 waves, cross-wave sums through LDS; step records
 //                           are moved into registers while a wave waits for an edge; attention; lm_head (fp8-trick VALU path, one row per wave per packet).
@@ -22,7 +23,8 @@
 //     wo      CU (h, s): rows [384 s, +384) x columns of head h (K = 128)  -> 32 partial planes PW; owner of rows [12 b, +12) sums them + residual -> H1
 //     w1|w3   CU (g, j): SwiGLU outputs [1152 g + 36 j, +36) (K = 3072)     -> granules A (read inside the XCD group only)
 //     w2      CU (g, j): rows [96 j, +96) x the XCD group's K slice [1152 g, +1152) -> 8 partial planes P2; owner sums + residual -> H0 (next layer's input)
-//   An all-gather (H0, H1) is 4 granules per lane for each consumer wave (its own K slice); the other edges are <= 1152 granules.
+//   An all-gather (H0, H1) is 4 granules per lane for each consumer wave (its own K slice), and so is the SwiGLU edge (A: the wave's 6 blocks on 48 lanes); the
+//   other edges are <= 384 granules, swept by the COMM wave.
 // Tags = (launch serial + 1) * 64 + layer + 1: unique per (launch, layer), so no buffer is ever re-initialised and a stale granule can never match.
 // Every spin is bounded (20 ms): on timeout the workgroup sets *err, marks itself dead and runs to completion without waiting.
 // History, measurements and everything that was tried: DESIGN.md section 3.0, profiles/r03_engine_experiments.md.
@@ -72,7 +74,7 @@ __global__ __launch_bounds__(64) void eng_pack_kernel(Q4W w, int op, unsigned ch
 // ------------------------------------------------------------------------------------------------
 struct EngCtl {
     unsigned ring_ready[8], ring_done[8];         // monotonic per slot: fills landed / passes consumed
-    unsigned xs0_flag, xs1_flag, xa_flag, qkv_flag;   // layer + 1 of the staged content (monotonic)
+    unsigned xs0_flag, xs1_flag, xa_done, qkv_flag;   // qkv_flag: layer + 1 of the staged content (monotonic); xa_done: consumer waves that hold their slice of a layer's SwiGLU outputs (12 per layer)
     unsigned cbar, dead, gathering, gw_flag;
     unsigned xcd_ok, xcc_id, ag_flag, pub_cnt;    // pub_cnt: consumer waves that have issued an operator's publishes (12 per operator, 4 operators per layer)       // ag_flag: all-gather stages whose probe has resolved (the consumer waves then sweep the vector themselves)
     float rstd0, rstd1, pad1, pad2;
@@ -85,9 +87,9 @@ constexpr int L_RING = 0;
 constexpr int L_XS = L_RING + NSLOT * SLOT_BYTES;       // 12 KB: the all-gathered (or XCD-gathered) input vector of the next operator, as FIXED-POINT DIGIT PLANES for the MFMA operators
                                                         //   ([block][digit 0..3][half][16 B]: 128 bytes per 32-element block -- the same 4 bytes per element as f32), or as swizzled f32 chunks for
                                                         //   the lm_head.  ONE buffer: it is re-staged only after every consumer wave has published results computed from the previous content
-constexpr int L_U = L_XS + ED * 4;                      // time-shared: cross-wave partial sums of the operator in flight | the XCD group's 1152 SwiGLU outputs (f32, before conversion) | attention scratch
-constexpr int L_XA = L_U;                               //   [1152] f32 staged by the COMM wave after w1|w3, converted to digit planes (in L_XS) by the consumer waves
-constexpr int L_PART = L_U;                             //   [rows][12 or 6] f32 partial sums (<= 72 x 12)
+constexpr int L_U = L_XS + ED * 4;                      // time-shared: cross-wave partial sums of the operator in flight | attention scratch
+constexpr int L_PART = L_U;                             //   [rows][12] f32 partial sums (<= 72 x 12)
+constexpr int L_PART2 = L_U + 1152 * 4;                 //   [96][6] w2's partial sums (behind w1|w3's)
 constexpr int L_SC = L_U;                               //   [SC_MAX] scores; after the softmax: [128] attention output (f32) on its way to digits
 constexpr int L_PO = L_SC + SC_MAX * 4;                 //   [12][128] partial attention outputs
 constexpr int L_PL = L_PO + 12 * 128 * 4;               //   [16] partial softmax sums
@@ -102,7 +104,7 @@ constexpr int L_CTL = L_GW + (MAX_LAYERS + 1) * 32 * 4;
 constexpr int L_TOTAL = L_CTL + (int)sizeof(EngCtl);
 static_assert(L_TOTAL <= 160 * 1024, "LDS budget");
 static_assert(L_TAB % 16 == 0 && sizeof(EngLayerTab) == 40, "layer table");
-static_assert(L_XS % 16 == 0 && L_XA % 16 == 0 && L_QKVN % 16 == 0 && L_PO % 16 == 0 && L_CTL % 16 == 0 && L_BLK % 8 == 0 && 72 * 12 * 4 <= SC_MAX * 4 && 1152 * 4 + 96 * 6 * 4 <= SC_MAX * 4 + 12 * 128 * 4, "aligned carve");
+static_assert(L_XS % 16 == 0 && L_PART2 % 16 == 0 && L_QKVN % 16 == 0 && L_PO % 16 == 0 && L_CTL % 16 == 0 && L_BLK % 8 == 0 && 72 * 12 * 4 <= SC_MAX * 4 && 1152 * 4 + 96 * 6 * 4 <= SC_MAX * 4 + 12 * 128 * 4, "aligned carve");
 
 // ONE rolled loop over the step's packets (the kernel's code must stay small: the instruction cache is shared by two CUs and every layer walks
 // through all three roles' code -- a 100 KB kernel ran 13 % slower than a 68 KB one with the same structure)
@@ -195,7 +197,7 @@ __device__ __forceinline__ float comm_next_input(const EngParams& p, int lane, u
 // stage 2 L = the final norm's input (-> lm_head); the small edges that follow each all-gather hang off the loop body.
 __device__ __forceinline__ void eng_comm(const EngParams& p, EngCtl* c, unsigned char* lds, const int lane0, const Tl& tl) {
     const int b = blockIdx.x, g = b & 7, j = b >> 3, h = 4 * g + (j >> 3);
-    float* xa = reinterpret_cast<float*>(lds + L_XA); float* qkvn = reinterpret_cast<float*>(lds + L_QKVN);
+    float* qkvn = reinterpret_cast<float*>(lds + L_QKVN);
     float* tmp = reinterpret_cast<float*>(lds + L_TMP);
     const EngLayerTab* tab = reinterpret_cast<const EngLayerTab*>(lds + L_TAB);
     const unsigned tag_base = (*p.serial + 1u) * 64u;     // tags of this launch: tag_base (the step's input) .. tag_base + n_layers; never 0, never reused
@@ -258,15 +260,11 @@ __device__ __forceinline__ void eng_comm(const EngParams& p, EngCtl* c, unsigned
             }
             if (T) tl(10);
         } else {
-            const bool xloc_nt = (p.flags & 128) != 0 && (p.flags & 4096) != 0 && lds_ld(&c->xcd_ok) != 0;
-            {   // the XCD group's 1152 SwiGLU outputs -> w2 input
+            {   // the XCD group's 1152 SwiGLU outputs -> w2 input: polled by the consumer waves themselves (each the K slice it multiplies); this wave only tells the
+                // loader, as for every other edge, that the CU is polling memory
                 wait_ge(&c->pub_cnt, NCONS * (4u * (unsigned)l + 3u), c, p.err, ERR_STAGE);
                 lds_st(&c->gathering, 1u);
-                float v[18];
-                sweep<18>(p.A, EF * 8u, tag, [&](int u) { return 1152 * g + lane + 64 * u; }, [&]() { return 1152 * g + 36 * (lane & 31) + 35; }, PROBE_SMALL, v, c, p.err, xloc_nt);      // probe: the last output of each CU of the group
-#pragma unroll
-                for (int u = 0; u < 18; u++) xa[lane + 64 * u] = v[u];      // plain f32: the consumer waves turn it into digit planes
-                ENG_CFENCE(); lds_st(&c->xa_flag, (unsigned)l + 1u);
+                wait_ge(&c->xa_done, NCONS * ((unsigned)l + 1u), c, p.err, ERR_STAGE);
                 lds_st(&c->gathering, 0u);
             }
             if (T) tl(12);
@@ -536,9 +534,8 @@ __device__ __forceinline__ void eng_consumer(const EngParams& p, EngCtl* c, unsi
     const int b = blockIdx.x, g = b & 7, j = b >> 3, h = 4 * g + (j >> 3), s = j & 7;
     unsigned char* xs = lds + L_XS; float* ssl = reinterpret_cast<float*>(lds + L_SSQ);
     float2* binfo = reinterpret_cast<float2*>(lds + L_BLK);
-    const float* xa = reinterpret_cast<const float*>(lds + L_XA);
     float* part = reinterpret_cast<float*>(lds + L_PART);
-    float* part2 = reinterpret_cast<float*>(lds + L_XA + 1152 * 4);      // w2's partial sums: behind the f32 SwiGLU outputs, which slower waves may still be converting
+    float* part2 = reinterpret_cast<float*>(lds + L_PART2);
     const float* qkvn = reinterpret_cast<const float*>(lds + L_QKVN);
     float* sc = reinterpret_cast<float*>(lds + L_SC); float2* po = reinterpret_cast<float2*>(lds + L_PO); float* pl = reinterpret_cast<float*>(lds + L_PL);
     const unsigned tag_base = (*p.serial + 1u) * 64u;
@@ -880,14 +877,30 @@ __device__ __forceinline__ void eng_consumer(const EngParams& p, EngCtl* c, unsi
                 r2l = rec_read_lo(b2 + 2 * REC, lane);
                 cs.slot_release(s2);
             }
-            wait_ge(&c->xa_flag, (unsigned)l + 1u, c, p.err, ERR_STAGE);
-            if (T) tl(7);
+            // The SwiGLU edge, as the all-gathers take theirs: this wave polls the 6 blocks it multiplies (K-steps 3 ksl .. 3 ksl + 2 of the XCD group's 1152 outputs: 4
+            // consecutive granules per lane on 48 lanes, two 16-byte loads; lanes 48..63 repeat lane 47) and turns them into digit planes in its own region -- no sweep of
+            // all 1152 by the COMM wave (18 loads, 18 LDS stores and a flag on a wave that issues an instruction every 8 cycles), no f32 staging, no barrier.  It polls
+            // only once the CU's own twelve waves have published: every CU runs the same schedule, so nothing can be complete much earlier.
             const int ksl = cw % 6, tg = cw / 6;
-            if (lane < 48) {      // this wave's 6 blocks (K-steps 3 ksl .. 3 ksl + 2) of the group's SwiGLU outputs: f32 -> digit planes in the wave's own region -- no barrier
-                const float4 v4 = *reinterpret_cast<const float4*>(xa + 32 * (6 * ksl + (lane >> 3)) + 4 * (lane & 7));
-                const float v[4] = {v4.x, v4.y, v4.z, v4.w};
-                to_digits(v, lane, xs + (8 * cw + (lane >> 3)) * 128, binfo + 8 * cw + (lane >> 3));
+            wait_ge(&c->pub_cnt, NCONS * (4u * (unsigned)l + 3u), c, p.err, ERR_STAGE);
+            {
+                const srd_t sd = make_srd(p.A, EF * 8u);
+                const int ln = min(lane, 47);
+                const unsigned e = (unsigned)(1152 * g + 32 * (6 * ksl + (ln >> 3)) + 4 * (ln & 7));      // <= 9212: the four granules end inside A
+                u32x4 ra, rb; u64 t0 = 0;
+                for (;;) {
+                    ra = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(sd, (int)(e * 8u), 0, 16));
+                    rb = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(sd, (int)(e * 8u + 16u), 0, 16));
+                    if (__all(ra.y == tag && ra.w == tag && rb.y == tag && rb.w == tag)) break;
+                    if (sweep_bail(t0, tag, c, p.err)) break;
+                }
+                if (lane == 0) __hip_atomic_fetch_add(&c->xa_done, 1u, RLX, WG);
+                if (lane < 48) {
+                    const float v[4] = {__uint_as_float(ra.x), __uint_as_float(ra.z), __uint_as_float(rb.x), __uint_as_float(rb.z)};
+                    to_digits(v, lane, xs + (8 * cw + (lane >> 3)) * 128, binfo + 8 * cw + (lane >> 3));
+                }
             }
+            if (T) tl(7);
             const PairCtx cxp = load_ctx2(xs, binfo, 8 * cw, 8 * cw + 2, lane), cxs = load_ctx2(xs, binfo, 8 * cw + 4, 8 * cw + 4, lane);      // K-steps (0, 1); K-step 2 in both row halves
             {
                 const float m = mstep2(r2s, cxs, 0.f);      // lane groups 0, 1: tile 0's K-step 2; groups 2, 3: tile 1's
